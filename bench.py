@@ -23,11 +23,21 @@ Launch: python bench.py [--gpus N --steps K --warmup W] starts by itself for eve
   * WORLD_SIZE unset (the plain command line): ONE process drives the N GPUs -- the reference's process model
     (src/bin/semtools.rs:134-135: one synchronous task) and the one the Rust wrappers use (rust/src/search/hip.rs:
     smt_group_create -> ncclCommInitAll, peer access between the devices): one smt_group, one ShardedCorpus over N device
-    shards, one issuing thread per device inside the library.  --ranks-per-process 1 re-executes the same command under
+    shards, one issuing thread per device inside the library.  --ranks-per-process 1 runs the same command in a child process under
     torch.distributed.run (one rank per process, ncclCommInitRank);
   * WORLD_SIZE set (launched by torch.distributed.run / the driver): one rank per process, as before.
 Fewer than N devices visible, or a group that cannot be created, is reported as a JSON line with "value": null, "error" and
 "n_gpus_visible", exit code 0 -- never a traceback without a line.
+
+Plain run vs --full: a plain run does only what the headline needs -- set up, settle + warm up, time --steps steps, write the last
+step's answer if --dump-outputs DIR is given, print the line (contract keys + config).  No HIP events inside the timed loop, no
+clock sampling.  --full is the complete measurement: the timed loop with HIP events on every --event-every-th scan launch, the
+`roofline`, the fp64 / oracle `checks`, every other leg (c3, c4, c5, embed, workspace, ingest, small calls, group issue) and the
+`cpu_baseline`; each --no-* option drops one of those legs from a --full run.
+
+--dump-outputs DIR: the (row, distance) pairs the timed path returned in its last timed step, written as DIR/topk_rows.npy and
+DIR/topk_distances.npy (float64; rows are exact integers).  The inputs are seeded, so the same arguments give the same inputs on
+every run and two builds can be compared output for output.
 
 Output: the LAST stdout line is one compact JSON object (< 6 KB: the driver keeps an 8 KB tail) -- the contract keys, the c2
 `roofline` and `cpu_baseline`, and every other leg's figures hoisted to flat top-level keys (c3_*, c4_*, ws_*, embed_*, ingest_*,
@@ -35,6 +45,7 @@ ivf_*) plus `checks_ok` / `checks_failed`.  The full per-leg objects (notes, sou
 gpurun_out/bench_detail.json (or --detail-out) and, as one line, to stderr.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -71,7 +82,12 @@ def make_shard(rows, seed, device):
 def parse_args(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=2000, help="timed steps (one query end to end each)")
+    ap.add_argument("--full", action="store_true",
+                    help="the complete measurement: roofline, checks, every other leg and the CPU baseline (a plain run times the "
+                         "headline steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's answer to DIR/topk_rows.npy and DIR/topk_distances.npy (float64)")
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--settle-steps", type=int, default=256,
                     help="untimed steps run BEFORE the warmup (same count on every rank): the first ~15 ms of sustained "
@@ -108,7 +124,7 @@ def parse_args(argv):
                     help="at least this many K2 launches are bracketed by HIP events whatever --steps is")
     ap.add_argument("--ranks-per-process", type=int, default=0, choices=[0, 1],
                     help="0 (default when WORLD_SIZE is unset): ONE process drives all --gpus devices through one smt_group "
-                         "(ncclCommInitAll); 1: one rank per process -- the command re-executes itself under torch.distributed.run")
+                         "(ncclCommInitAll); 1: one rank per process -- the command runs again, in a child process, under torch.distributed.run")
     ap.add_argument("--single-process", action="store_true",
                     help="take the one-process GROUP path even for --gpus 1 (smt_group_create on one device: what a 1-GPU box can run of it)")
     ap.add_argument("--logical-shards", type=int, default=0,
@@ -116,7 +132,10 @@ def parse_args(argv):
                          "n_gpus stays 1 and the line says so)")
     ap.add_argument("--group-transport", default=None, choices=["peer", "rccl", "copy"],
                     help="how the per-shard k-lists meet in the one-process group (default: the library's -- peer reads)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class EnvironmentProblem(Exception):
@@ -162,7 +181,10 @@ def main(argv=None):
             cmd = launcher_argv(args, argv)
             sys.stderr.write("[bench] one rank per process: " + " ".join(cmd) + "\n")
             sys.stderr.flush()
-            os.execv(cmd[0], cmd)
+            # a child process, not an exec: this process has already opened the HIP runtime (visible_gpus)
+            import subprocess
+
+            return subprocess.call(cmd)
         run(args, under_launcher)
     except EnvironmentProblem as exc:
         if rank_env == 0:
@@ -445,19 +467,19 @@ def run(args, under_launcher):
     for i in range(args.warmup):
         step(i)
     sync()
-    # HIP events bracket every launch of the dominant kernel (K2 scan) inside the timed region; the select
+    # --full: HIP events bracket every launch of the dominant kernel (K2 scan) inside the timed region; the select
     # stage is timed in a short extra loop afterwards (each event pair costs ~5 us of stream time)
     # (every local context: at N > 1 the line carries each rank's scan / select time and the merging device's wait for the others)
     for c in local_ctxs:
         c.set_tuning("prof_select", 0)
         c.set_tuning("prof_every", args.event_every)   # an event pair costs ~6 us of stream time: sample the launches
-        c.prof_enable(True)
+        c.prof_enable(args.full)
         c.prof_reset()
     sync()
     uncertain_all()                               # reset the "exactness certificate failed" counters
     status_host.fill_(7)
-    clocks = ClockSampler(local_rank)
-    with clocks.leg("c2"):
+    clocks = ClockSampler(local_rank) if args.full else None
+    with clocks.leg("c2") if clocks else contextlib.nullcontext():
         t0 = time.perf_counter()
         for i in range(args.steps):
             step(i)
@@ -469,6 +491,47 @@ def run(args, under_launcher):
     rank_elapsed = elapsed                                          # this rank's own clock (the MAX over ranks is taken below)
     got_rows = host_rows[(args.steps - 1) % ring].numpy().copy()   # the last timed step's answer (checked below)
     got_dist = host_dist[(args.steps - 1) % ring].numpy().copy()
+    if use_dist:                                  # MAX over the ranks (one process: there is one clock)
+        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+
+    result = {
+        "metric": "chunk-vectors scanned/sec (whole job)",
+        "value": n_shards * rows * args.steps / elapsed,
+        "unit": "rows/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "settle_steps": args.settle_steps,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "host_issue_ms_per_step": issued / args.steps * 1e3,
+        "full": args.full,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": "c2: 1 query x 1M chunks (D=256, f32) per GPU, brute-force cosine + top-k",
+                   "rows_per_gpu": rows, "dim": 256, "top_k": k, "queries_rotated": n_queries,
+                   "corpus_copies_rotated": len(shards),
+                   "sharding": (f"row-sharded over one smt_group of {n_shards} ranks; the per-shard k-lists meet through the group's "
+                                f"'{ginfo['transport']}' transport (peer: the merge kernel reads them in place; rccl: one ncclAllGather) "
+                                "+ device merge on the aux stream, overlapping the next scan") if exchange else "single shard",
+                   "select_stage": "overlapped with the next query's scan (aux stream)" if async_select else "in stream order"},
+    }
+    if exchange and world == 1 and not sp:
+        result["config"]["forced_exchange_on_one_rank"] = True
+    if args.logical_shards:
+        result["config"]["logical_shards_on_one_gpu"] = n_dev   # test hook: n_gpus is 1, the N shards' GPU work serialises
+    if exchange and rank == 0:
+        result["config"]["group"] = ginfo
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, got_rows, got_dist)
+    if not args.full:                             # a plain run: the headline only
+        finish(result, args, rank, use_dist, world)
+        return
+
     # the roofline figure must not rest on a handful of samples when the caller passes a small --steps: top the
     # bracketed launches up to --min-bracketed with more steps of the same pipeline (outside the timed region)
     extra_steps = 0
@@ -510,11 +573,6 @@ def run(args, under_launcher):
         dist.all_gather_object(box, per_rank[0])
         per_rank = box
 
-    if use_dist:                                  # MAX over the ranks (one process: there is one clock)
-        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-
     # ---- sanity of the last step's result against an independent fp64 torch reference
     last = (args.steps - 1) % n_queries
     last_copy = (args.steps - 1) % n_copies          # the copy the last timed step scanned
@@ -550,33 +608,6 @@ def run(args, under_launcher):
             except Exception:
                 torch_ok = None
 
-    result = {
-        "metric": "chunk-vectors scanned/sec (whole job)",
-        "value": n_shards * rows * args.steps / elapsed,
-        "unit": "rows/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "settle_steps": args.settle_steps,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "host_issue_ms_per_step": issued / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": "c2: 1 query x 1M chunks (D=256, f32) per GPU, brute-force cosine + top-k",
-                   "rows_per_gpu": rows, "dim": 256, "top_k": k, "queries_rotated": n_queries,
-                   "corpus_copies_rotated": len(shards),
-                   "sharding": (f"row-sharded over one smt_group of {n_shards} ranks; the per-shard k-lists meet through the group's "
-                                f"'{ginfo['transport']}' transport (peer: the merge kernel reads them in place; rccl: one ncclAllGather) "
-                                "+ device merge on the aux stream, overlapping the next scan") if exchange else "single shard",
-                   "select_stage": "overlapped with the next query's scan (aux stream)" if async_select else "in stream order"},
-    }
-    if exchange and world == 1 and not sp:
-        result["config"]["forced_exchange_on_one_rank"] = True
-    if args.logical_shards:
-        result["config"]["logical_shards_on_one_gpu"] = n_dev   # test hook: n_gpus is 1, the N shards' GPU work serialises
     if rank == 0:
         scan_us = scan_ms / max(n_scan, 1) * 1e3
         rank_scan = [pr["scan_avg_us"] for pr in per_rank if pr.get("scan_avg_us")]
@@ -617,8 +648,6 @@ def run(args, under_launcher):
                             "every_timed_answer_proved_exact": f"{int((verdicts == 0).sum())}/{len(verdicts)}" if want_verdicts else "not asked/asked"}
         if rows_ok is not None:
             result["checks"]["rows_match_fp64_topk_over_all_shards"] = rows_ok
-        if exchange:
-            result["config"]["group"] = ginfo
 
     # the legs below describe ONE GPU driven through a plain context on torch's stream: they run at N = 1 only, and not in the
     # one-process group mode (whose contexts own their streams)
@@ -816,6 +845,17 @@ def run(args, under_launcher):
             result["cpu_baseline"] = {"error": repr(exc)}
     if rank == 0:
         result["clocks"] = clocks.report
+    finish(result, args, rank, use_dist, world)
+
+
+def dump_outputs(out_dir, rows, dists):
+    """--dump-outputs: the last timed step's answer as float64 .npy files (row indices are integers below 2^53: exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "topk_rows.npy"), np.asarray(rows, dtype=np.float64))
+    np.save(os.path.join(out_dir, "topk_distances.npy"), np.asarray(dists, dtype=np.float64))
+
+
+def finish(result, args, rank, use_dist, world):
     # The JSON line must be the LAST thing on stdout.  RCCL prints a version banner through C stdio when a communicator is
     # created; redirected to a file, that text sits in libc's buffer until exit and would land BEHIND the line.  Flush C
     # stdio first, then print and flush the line.
@@ -916,6 +956,8 @@ def compact_line(d):
     line = {key: d.get(key) for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                         "scaling", "vs_baseline", "dtype", "data")}
     line["value"], line["ms_per_step"] = _r(line["value"], 6), _r(line["ms_per_step"], 5)
+    if "full" in d:
+        line["full"] = d["full"]
     cfg = d.get("config", {})
     line["config"] = {"workload": cfg.get("workload"), "rows_per_gpu": cfg.get("rows_per_gpu"), "dim": cfg.get("dim"), "top_k": cfg.get("top_k"),
                       "corpus_copies_rotated": cfg.get("corpus_copies_rotated"),
@@ -1064,9 +1106,10 @@ def compact_line(d):
     put("ivf_pq_queries_per_s", "ivfpq", "global_pq_m32", "queries_per_s")
     put("ivf_pq_build_s", "ivfpq", "global_pq_m32", "build_s")
     n_checks, failed = collect_checks(d)
-    line["checks_total"] = n_checks
-    line["checks_ok"] = not failed
-    line["checks_failed"] = [f[:100] for f in failed[:12]]
+    if n_checks:           # (a plain run checks nothing: no verdict to print)
+        line["checks_total"] = n_checks
+        line["checks_ok"] = not failed
+        line["checks_failed"] = [f[:100] for f in failed[:12]]
     return line
 
 

@@ -125,3 +125,46 @@ def test_a_failure_after_start_up_prints_a_line_and_exits_one(monkeypatch, capsy
     res = json.loads(out.strip().split("\n")[-1])
     assert res["value"] is None and res["n_gpus"] == 8 and "hipErrorLaunchFailure" in res["error"] and "failed after start-up" in res["error"]
     assert "Traceback" in err
+
+
+def test_plain_and_full_options():
+    """A plain run is the default; --full asks for the legs, checks and baselines; --steps sets the timed steps and must be positive."""
+    import pytest
+
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_compact_line_of_a_plain_run():
+    """The line of a plain run: the contract keys and the config, no verdict keys (it checks nothing), and still the last line's shape."""
+    import bench
+
+    d = _canned()
+    plain = {key: d[key] for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "host_issue_ms_per_step",
+                                     "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")}
+    plain["full"] = False
+    line = bench.compact_line(plain)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line[key] is not None, key
+    assert line["full"] is False
+    for key in ("roofline", "cpu_baseline", "checks_ok", "checks_total", "checks_failed", "c3_queries_per_s"):
+        assert key not in line, key
+
+
+def test_dump_outputs_writes_float64_arrays(tmp_path):
+    import numpy as np
+
+    import bench
+
+    rows = np.array([5, 3, 2 ** 40 + 1], dtype=np.int64)
+    dists = np.array([0.25, 0.5, 0.75])
+    bench.dump_outputs(str(tmp_path / "d"), rows, dists)
+    r, s = np.load(tmp_path / "d" / "topk_rows.npy"), np.load(tmp_path / "d" / "topk_distances.npy")
+    assert r.dtype == np.float64 and s.dtype == np.float64
+    assert r.astype(np.int64).tolist() == rows.tolist() and s.tolist() == dists.tolist()

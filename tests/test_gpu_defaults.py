@@ -162,7 +162,7 @@ def test_bench_exchange_path_under_torchrun_on_one_rank():
     the JSON line is the last thing on stdout, carries the contract's keys and passes its own checks."""
     env = dict(os.environ, SEMTOOLS_BENCH_FORCE_EXCHANGE="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--settle-steps", "8",
+           "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "5", "--warmup", "2", "--settle-steps", "8",
            "--no-secondary", "--no-ivfpq", "--no-embed", "--no-cpu-baseline", "--no-workspace", "--no-ingest", "--no-group-issue", "--c4-rows", "4000000",
            "--c4-steps", "4", "--detail-out", os.path.join(ROOT, "gpurun_out", "bench_detail_forced_exchange.json")]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
@@ -190,7 +190,7 @@ def test_bench_exchange_path_under_torchrun_on_one_rank():
     assert detail["checks"]["every_timed_answer_proved_exact"] == "5/5"
 
 
-SMALL = ["--steps", "5", "--warmup", "2", "--settle-steps", "8", "--no-secondary", "--no-ivfpq", "--no-embed", "--no-cpu-baseline",
+SMALL = ["--full", "--steps", "5", "--warmup", "2", "--settle-steps", "8", "--no-secondary", "--no-ivfpq", "--no-embed", "--no-cpu-baseline",
          "--no-workspace", "--no-ingest", "--no-group-issue", "--c4-rows", "4000000", "--c4-steps", "4"]
 
 
@@ -256,13 +256,50 @@ def test_bench_more_gpus_than_the_box_has_is_a_line_not_a_traceback():
             assert key in res, key
 
 
+def test_plain_bench_times_the_headline_only_and_dumps_its_last_answer(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the contract keys and nothing from the other legs; with --dump-outputs
+    the last timed step's (row, distance) pairs -- the same on a second run, and the fp64 top-k of the query and corpus copy that step
+    scanned (the seeded inputs regenerated here with bench.make_shard)."""
+    import torch
+
+    import bench
+
+    steps, k = 37, 10
+    outs = []
+    for n in range(2):
+        d = tmp_path / f"run{n}"
+        r, res, line = _bench(["--gpus", "1", "--steps", str(steps), "--warmup", "3", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert res[key] is not None, key
+        assert res["steps"] == steps and res["full"] is False and res["value"] > 0 and res["dtype"] == "f32"
+        assert abs(res["value"] - 1_000_000 / (res["ms_per_step"] * 1e-3)) / res["value"] < 1e-3
+        for key in ("roofline", "checks_ok", "cpu_baseline", "c3_queries_per_s", "c4_rows_per_s", "ivf_queries_per_s", "clk_c2_mhz"):
+            assert key not in res, key
+        rows, dist = np.load(d / "topk_rows.npy"), np.load(d / "topk_distances.npy")
+        assert rows.dtype == np.float64 and dist.dtype == np.float64 and rows.shape == dist.shape == (k,)
+        outs.append((rows, dist))
+    assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
+    rows, dist = outs[0]
+    dev = torch.device("cuda:0")
+    shard = bench.make_shard(1_000_000, seed=3 + 1000 * ((steps - 1) % 2), device=dev)   # copy (steps - 1) % 2, query (steps - 1) % 16
+    g = torch.Generator(device=dev)
+    g.manual_seed(4)
+    q = torch.randn(16, 256, device=dev, generator=g)
+    q /= q.norm(dim=1, keepdim=True)
+    ref = (1.0 - shard.double() @ q[(steps - 1) % 16].double()).cpu().numpy()
+    assert np.array_equal(rows, np.round(rows)) and rows.min() >= 0 and rows.max() < len(ref)
+    assert np.allclose(np.sort(ref)[:k], dist, rtol=0, atol=1e-6) and np.all(np.diff(dist) >= 0)
+    assert np.allclose(ref[rows.astype(np.int64)], dist, rtol=0, atol=1e-6)      # each row carries its own distance
+
+
 def test_bench_abandons_a_c4_leg_that_hangs_and_still_prints_the_line():
     """With several ranks c4 is collective: a rank that fails inside it would leave the others in ncclAllGather for ever and the c2
     figures, complete by then, unprinted.  bench.py's watchdog abandons the leg after --c4-timeout seconds.  Driven here on one rank
     with a leg that sleeps for ever (SEMTOOLS_BENCH_FAKE_C4_HANG): exit code 0, the JSON line last on stdout with the c2 figures,
     the abandoned leg listed among the failed checks."""
     env = dict(os.environ, SEMTOOLS_BENCH_FAKE_C4_HANG="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--settle-steps", "8", "--no-secondary", "--no-ivfpq",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--settle-steps", "8", "--no-secondary", "--no-ivfpq",
            "--no-embed", "--no-cpu-baseline", "--no-workspace", "--no-ingest", "--no-group-issue", "--c4-timeout", "3",
            "--detail-out", os.path.join(ROOT, "gpurun_out", "bench_detail_c4_abandoned.json")]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)

@@ -6,7 +6,7 @@ out="$(pwd)/gpurun_out"
 mkdir -p "$out"
 for pipe in 1 0; do
 SEMTOOLS_BENCH_PIPELINE=$pipe SEMTOOLS_BENCH_FORCE_EXCHANGE=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-    --master-addr 127.0.0.1 --master-port 2953$pipe bench.py --gpus 1 --steps 200 --warmup 20 \
+    --master-addr 127.0.0.1 --master-port 2953$pipe bench.py --full --gpus 1 --steps 200 --warmup 20 \
     --no-cpu-baseline --no-secondary --no-ivfpq > "$out/bench_exchange_${tag}_pipe$pipe.json" 2> "$out/bench_exchange_${tag}_pipe$pipe.err"
 python - "$out/bench_exchange_${tag}_pipe$pipe.json" <<'PY'
 import json, sys

@@ -6,7 +6,7 @@ step() { echo "=== $1 ($(date +%T))"; }
 step "pytest -m gpu"
 timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 > "$out/pytest_gpu_r04a.log"; cat "$out/pytest_gpu_r04a.log"
 step "bench"
-timeout 600 python bench.py > "$out/bench_r04a.json" 2> "$out/bench_r04a.err"; tail -c 6500 "$out/bench_r04a.json"; grep -v "bench detail" "$out/bench_r04a.err" | tail -5
+timeout 600 python bench.py --full > "$out/bench_r04a.json" 2> "$out/bench_r04a.err"; tail -c 6500 "$out/bench_r04a.json"; grep -v "bench detail" "$out/bench_r04a.err" | tail -5
 cp "$out/bench_detail.json" "$out/bench_detail_r04a.json" 2>/dev/null
 step "K1 A/B"
 timeout 400 python tools/embed_ab.py 1 3 7 > "$out/embed_ab_r04a.json" 2> "$out/embed_ab_r04a.err"; cat "$out/embed_ab_r04a.json"; tail -3 "$out/embed_ab_r04a.err"

@@ -4,7 +4,7 @@
 # write-ahead; the sharded IVF figures with every call's time.
 tag="${1:-r05}"
 root="$(pwd)"; out="$root/gpurun_out"; mkdir -p "$out"
-timeout 900 python bench.py --detail-out "$out/${tag}_bench_detail.json" > "$out/${tag}_bench_line.json" 2> "$out/${tag}_bench.err"; echo "bench rc=$? line bytes=$(tail -1 "$out/${tag}_bench_line.json" | wc -c)"
+timeout 900 python bench.py --full --detail-out "$out/${tag}_bench_detail.json" > "$out/${tag}_bench_line.json" 2> "$out/${tag}_bench.err"; echo "bench rc=$? line bytes=$(tail -1 "$out/${tag}_bench_line.json" | wc -c)"
 cd /tmp && export TMPDIR=/tmp
 all_off="--no-cpu-baseline --no-c4 --no-secondary --no-embed --no-ivfpq --no-workspace --no-ingest --no-group-issue"
 for leg in c2 c4 c3 embed workspace ivfpq; do
@@ -16,7 +16,7 @@ for leg in c2 c4 c3 embed workspace ivfpq; do
     workspace) flags="${all_off/--no-workspace/} --steps 20 --warmup 5";;
     ivfpq) flags="${all_off/--no-ivfpq/} --c5-full-rows 0 --steps 20 --warmup 5";;
   esac
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof_${tag}_$leg" -o bench -- python "$root/bench.py" $flags --detail-out "$out/${tag}_bench_detail_prof_$leg.json" > "$out/prof_${tag}_$leg.log" 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof_${tag}_$leg" -o bench -- python "$root/bench.py" --full $flags --detail-out "$out/${tag}_bench_detail_prof_$leg.json" > "$out/prof_${tag}_$leg.log" 2>&1
   trace=$(find "$out/prof_${tag}_$leg" -name "*kernel_trace.csv" | head -1)
   stats=$(find "$out/prof_${tag}_$leg" -name "*kernel_stats.csv" | head -1)
   [ -n "$stats" ] && cp "$stats" "$out/${tag}_bench_${leg}_kernel_stats.csv"

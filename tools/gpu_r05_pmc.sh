@@ -13,8 +13,8 @@ pmc valu SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES
 pmc wait SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_VMEM_RD SQ_INSTS_LDS
 pmc lds SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_SALU
 cmd="--steps 20 --warmup 3 --settle-steps 8 --no-cpu-baseline --no-ivfpq --no-ingest --no-group-issue --c4-steps 3"
-timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$out/pmc_fetch_r05" -o bench -- python "$root/bench.py" $cmd --detail-out "$out/r05_bench_detail_pmc.json" > "$out/pmc_fetch_r05.log" 2>&1
-python "$root/tools/summarize_pmc.py" "$out/pmc_fetch_r05" "$out/r05_pmc_fetch.json" "rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py $cmd" > /dev/null 2>&1
+timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$out/pmc_fetch_r05" -o bench -- python "$root/bench.py" --full $cmd --detail-out "$out/r05_bench_detail_pmc.json" > "$out/pmc_fetch_r05.log" 2>&1
+python "$root/tools/summarize_pmc.py" "$out/pmc_fetch_r05" "$out/r05_pmc_fetch.json" "rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py --full $cmd" > /dev/null 2>&1
 find "$out" -name "*.csv" -size +8M -delete
 python - <<'PY'
 import json, glob

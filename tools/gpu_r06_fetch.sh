@@ -5,8 +5,8 @@
 root="$(pwd)"; out="$root/gpurun_out"; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 cmd="--steps 20 --warmup 3 --settle-steps 8 --no-cpu-baseline --no-ivfpq --no-ingest --no-group-issue --no-small-calls --c4-steps 3"
-timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$out/pmc_fetch_r06" -o bench -- python "$root/bench.py" $cmd --detail-out "$out/r06_bench_detail_pmc.json" > "$out/pmc_fetch_r06.log" 2>&1
-python "$root/tools/summarize_pmc.py" "$out/pmc_fetch_r06" "$out/r06_pmc_fetch.json" "rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py $cmd" > /dev/null 2>&1
+timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$out/pmc_fetch_r06" -o bench -- python "$root/bench.py" --full $cmd --detail-out "$out/r06_bench_detail_pmc.json" > "$out/pmc_fetch_r06.log" 2>&1
+python "$root/tools/summarize_pmc.py" "$out/pmc_fetch_r06" "$out/r06_pmc_fetch.json" "rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py --full $cmd" > /dev/null 2>&1
 find "$out" -name "*.csv" -size +8M -delete
 python - <<'PY'
 import json

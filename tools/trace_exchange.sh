@@ -2,7 +2,7 @@
 # kernel timeline of bench.py's N>1 path forced onto one rank: per-kernel average duration and the scan-to-scan period
 root="$(pwd)"; out="$root/gpurun_out"; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-SEMTOOLS_BENCH_FORCE_EXCHANGE=1 rocprofv3 --kernel-trace --output-format csv -d "$out/trace_xchg" -o t -- python "$root/bench.py" --steps 400 --warmup 50 --settle-steps 64 --no-secondary --no-ivfpq --no-cpu-baseline --no-c4 > "$out/trace_xchg.log" 2>&1
+SEMTOOLS_BENCH_FORCE_EXCHANGE=1 rocprofv3 --kernel-trace --output-format csv -d "$out/trace_xchg" -o t -- python "$root/bench.py" --full --steps 400 --warmup 50 --settle-steps 64 --no-secondary --no-ivfpq --no-cpu-baseline --no-c4 > "$out/trace_xchg.log" 2>&1
 grep '"metric"' "$out/trace_xchg.log" | cut -c1-400
 python - "$out/trace_xchg" <<'PY'
 import csv, glob, sys, collections
