@@ -206,7 +206,8 @@ int smt_search(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t t
 
 /* Resident top-k (mode DOCUMENTS, no threshold, no ranges): queries_dev
  * [nq x D] and outputs [nq x top_k] are device pointers; unused slots are
- * (row = UINT64_MAX, dist = +inf).  Enqueues on the stream, no sync.  1 <= top_k <= 56. */
+ * (row = UINT64_MAX, dist = +inf).  Enqueues on the stream, no sync.  1 <= top_k <= 1024 (57 .. 1024: the
+ * sampled-threshold route, tuning key largek_sampled; with largek_sampled = 0, 1 <= top_k <= 56). */
 int smt_search_topk_device(smt_corpus *corpus, const float *queries_dev, uint32_t nq,
                            uint32_t top_k, uint64_t row_base, uint64_t *out_rows_dev,
                            double *out_dist_dev);
@@ -438,7 +439,8 @@ int smt_sharded_search(smt_sharded_corpus *corpus, const float *queries, uint32_
  * device-addressable memory of local device i -- HBM or pinned host -- receiving [nq][2][top_k] 8-byte words:
  * global rows (padding UINT64_MAX), then the f64 distance bit patterns (padding +inf).  With tuning key
  * async_select set on the contexts and nq == 1, the select, the all-gather and the merge of call i run on the
- * contexts' aux streams while the scan of call i+1 streams. */
+ * contexts' aux streams while the scan of call i+1 streams.  1 <= top_k <= 1024 with n_ranks * top_k <= 8192 (57 .. 1024: the
+ * sampled-threshold route on every shard, tuning key largek_sampled; with largek_sampled = 0, top_k <= 56). */
 int smt_sharded_search_topk_device(smt_sharded_corpus *corpus, const float *const *queries_dev, uint32_t nq, uint32_t top_k,
                                    uint64_t *const *out_packed);
 /* ... with the per-query verdict of smt_search_topk_device_ex: out_status (NULL = none) holds one pointer per LOCAL device,

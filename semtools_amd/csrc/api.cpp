@@ -349,6 +349,7 @@ void smt_ctx_destroy(smt_ctx *ctx)
     for (auto &kv : ctx->prof)
         for (hipEvent_t ev : kv.second.ev) (void)hipEventDestroy(ev);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
+    if (ctx->d_largek) (void)hipFree(ctx->d_largek);
     if (ctx->d_embed_runs) (void)hipFree(ctx->d_embed_runs);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
     if (ctx->h_pinned_in) (void)hipHostFree(ctx->h_pinned_in);
@@ -457,6 +458,7 @@ try {
     else if (k == "gemm_bf16x3") ctx->tune.gemm_bf16x3 = (int)value;
     else if (k == "gemm_rowreg") ctx->tune.gemm_rowreg = (int)value;
     else if (k == "gemm_nominate") ctx->tune.gemm_nominate = (value >= 1 && value <= 3) ? (int)value : 0;
+    else if (k == "largek_sampled") ctx->tune.largek_sampled = value ? 1 : 0;
     else if (k == "fallback_batch_min_rows") ctx->tune.fallback_batch_min_rows = value < 0 ? 0 : value;
     else if (k == "guard_band") ctx->tune.guard_band = (int)std::max<int64_t>(8, std::min<int64_t>(56, value));
     else if (k == "gemm_min_nq") ctx->tune.gemm_min_nq = (int)std::max<int64_t>(2, std::min<int64_t>(8, value));

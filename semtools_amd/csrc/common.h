@@ -83,6 +83,7 @@ struct Tuning {
     int gemm_bf16x3 = 1;        // 1: K3 nominates candidates with bf16 x 3 split products on the bf16 MFMA pipe (mfma_tile.h); 0: f32 MFMA
     int gemm_ldsrow = 1;        // 1: batches <= 128 queries and range-filtered batches use the LDS-row kernel (64 queries per pass)
     int prof_select = 1;        // 0: do not bracket the select stage with events (2 fewer event records per query)
+    int largek_sampled = 1;     // 1: 57 <= top_k <= 1024 take the sampled-threshold route (topk_large.hip); 0: the all-keys path (largek.hip, A/B and parity tests)
     int direct_delivery = 1;    // 1: host-form top-k searches with small answers (<= 8 KiB) get them DELIVERED by the select kernel into pinned host memory, completion word last; the host waits on that word (search.cpp; 0: D2H copy + hipStreamSynchronize, A/B)
     int64_t scan_debug_ptr = 0;    // device pointer to (2*waves + blocks) u64 wall_clock64 stamps (profiling only)
     int64_t select_debug_ptr = 0;  // device pointer to 16 u64 for phase stamps (profiling only)
@@ -98,6 +99,8 @@ struct smt_ctx {
     // scratch (grown on demand, reused across calls)
     void *d_scratch = nullptr;
     size_t scratch_bytes = 0;
+    void *d_largek = nullptr;   // the large-k route's buffers (topk_large.hip): beside the scratch, which its K3 sweep uses
+    size_t largek_bytes = 0;
     uint64_t *d_embed_runs = nullptr;   // K1: first line of every group's run (token-balanced runs, embed_kernels.hip), made on first use
     size_t embed_runs_cap = 0;          // entries
     void *h_pinned = nullptr;
@@ -362,6 +365,8 @@ constexpr double F32_ERR_F16X2 = 5.2e-4;
 constexpr double F32_ERR_F16X1 = 1.0e-3;
 // K2/K3 keep k + 8 <= 64 candidates per list: top_k above this goes to the all-keys path (largek.hip)
 constexpr uint32_t SCAN_MAX_K = 56;
+// 57 <= top_k <= LARGEK_MAX_K: the sampled-threshold route (topk_large.hip); above it the all-keys path (largek.hip)
+constexpr uint32_t LARGEK_MAX_K = 1024;
 
 // per-query result list of the host-side search (search.cpp)
 struct LocalHits {
@@ -411,6 +416,9 @@ int launch_merge_topk(smt_ctx *ctx, const uint64_t *rows, const double *dist, ui
 int launch_merge_topk_packed(smt_ctx *ctx, const uint64_t *packed, uint32_t n_lists, uint32_t nq, uint32_t k_in,
                              uint32_t k_out, uint64_t *out_packed);
 
+// 57 <= k <= 1024: sampled threshold, collect, exact finish -- lists and SMT_STATUS_* verdicts (a.out_status / a.out_uncertain) for
+// a.nq queries, enqueued without a host synchronisation (topk_large.hip)
+int launch_topk_large(smt_ctx *ctx, const ScanArgs &a);
 // top_k > 64 (rare): all keys + radix sort + exact rescoring of the best n_cand rows
 int launch_largek_candidates(smt_ctx *ctx, const float *corpus, const float *query_dev, const smt_range *ranges_dev,
                              const uint64_t *prefix_dev, uint32_t n_ranges, uint64_t n_virtual, uint64_t n_cand,
@@ -461,7 +469,8 @@ int launch_split_rows_bf16(smt_ctx *ctx, const float *rows, uint32_t n, uint32_t
 // batched threshold pass (gemm_topk.hip): rows with nominating distance <= tau[q], per query, in scratch buffers
 int launch_gemm_threshold(smt_ctx *ctx, const float *corpus, uint64_t rows, const void *image, const uint32_t *image_zero,
                           const float *queries, uint32_t nq, const float *tau, const key_t64 **cand_out,
-                          const unsigned int **counts_out, uint32_t *cand_stride);
+                          const unsigned int **counts_out, uint32_t *cand_stride, uint32_t cap = 2048 /* CAND_CAP */,
+                          key_t64 *cand_ext = nullptr, unsigned int *counts_ext = nullptr);
 // test hook: the nominating f32 distances of the K3 kernels for <= 32 queries (gemm_topk.hip)
 int launch_gemm_debug_scores(smt_ctx *ctx, const float *corpus, uint64_t first_row, uint32_t n_rows, const float *queries,
                              uint32_t nq, float *out);

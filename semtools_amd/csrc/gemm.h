@@ -12,6 +12,7 @@
 namespace smt {
 
 constexpr uint32_t CAND_CAP = 2048;            // candidate slots per query
+static_assert(CAND_CAP == 2048, "common.h: launch_gemm_threshold's default capacity");
 // Level plan: tiles are visited in levels of geometrically growing size (every ratio^j-th tile first).  Level 0
 // (<= LEVEL0_MAX_TILES tiles = 1024 rows) appends every row; each later level appends about ratio x k' candidates
 // per query.  Measured alternative (MI355X, 10 M rows): ratio 64 with 4096 slots -- three levels instead of five --
@@ -46,7 +47,7 @@ struct GemmParams {
     const float *tau;         // [nqt*32] distance thresholds (+inf = take everything, <0 = padding)
     const float *qconst;      // gemm_rowreg_kernel: [nqt*32][2] = (score threshold = score_threshold(tau, rq), 1/|q|) per query;
                               // the thresholds are kept by level_select_kernel; padding queries: (-1, 0)
-    key_t64 *cand;            // [nq][CAND_CAP]
+    key_t64 *cand;            // [nq][cand_cap]
     unsigned int *counts;     // [nq]
     // range-filtered batches (gemm_ldsrow_kernel<.., true>): the rows to scan are the FILTER_CHUNK-row chunks of the
     // chunk table (scan_kernels.hip: row0 | valid rows << 32); a "tile" is then 8 consecutive chunks
@@ -62,6 +63,7 @@ struct GemmParams {
     const void *image;            // gemm_rowreg_kernel<MODE, true>: the corpus' fp16 operand image (16 KiB per 32-row tile) ...
     const uint32_t *image_zero;   // ... and per tile the mask of its zero rows
     int buffered;                 // gemm_rowreg_kernel: nominations go through the wave's LDS buffer (every level but the first)
+    uint32_t cand_cap = CAND_CAP; // gemm_rowreg_kernel: candidate slots per query (launch_gemm_threshold's callers may size their own)
     unsigned long long *stamps;   // trace builds only (SMT_RR_EXP & 256, tools/exp_k3_trace.sh): s_memtime stamps of one block
 };
 
@@ -75,7 +77,8 @@ __device__ __forceinline__ uint64_t level_tile(uint64_t i, uint64_t stride, int 
 }
 
 __device__ __forceinline__ void append_candidates(const f32x16 &acc, unsigned zero16, unsigned valid16, uint32_t q,
-                                                  float thr, float rq, uint64_t row0, int h, key_t64 *cand, unsigned int *counts);
+                                                  float thr, float rq, uint64_t row0, int h, key_t64 *cand, unsigned int *counts,
+                                                  uint32_t cap = CAND_CAP);
 // The candidate test in the SCORE domain.  The row tile is scaled by 1/|row| once when it is loaded, so an
 // accumulator is already cos * |q|; "distance <= tau" becomes acc >= (1 - tau) / |q|^-1 ... i.e. ONE compare
 // per (row, query) in the epilogue instead of two multiplies, a subtract, a max and a compare (the epilogue
@@ -132,28 +135,29 @@ __device__ __forceinline__ float acc_select(const f32x16 &acc, int r)
 // measured ~1150 cycles per nominating product at 1000 x 10 M, during which the other seven waves stood at the ring barrier.)
 // straight to the per-query lists: one slot grab per lane per tile
 __device__ __forceinline__ void append_direct(const f32x16 &acc, unsigned pass, unsigned zero16, uint32_t q, float rq, uint64_t row0, int h,
-                                              key_t64 *cand, unsigned int *counts)
+                                              key_t64 *cand, unsigned int *counts, uint32_t cap = CAND_CAP)
 {
     unsigned slot = 0;
     if (pass) slot = atomicAdd(&counts[q], (unsigned)__popc(pass));
-    key_t64 *dst = cand + (size_t)q * CAND_CAP;
+    key_t64 *dst = cand + (size_t)q * cap;
     unsigned todo = pass;
     while (__builtin_amdgcn_ballot_w64(todo != 0)) {
         const int r = todo ? __builtin_ctz(todo) : 0;
         const float a = acc_select(acc, r);
         if (todo) {
             const float d = rq == 0.0f ? ((zero16 >> r) & 1u ? 0.0f : 1.0f) : fmaxf(1.0f - a * rq, 0.0f);
-            if (slot < CAND_CAP) dst[slot] = make_key(d, (uint32_t)(row0 + acc_row(r, h)));
+            if (slot < cap) dst[slot] = make_key(d, (uint32_t)(row0 + acc_row(r, h)));
             ++slot;
             todo &= todo - 1;
         }
     }
 }
 __device__ __forceinline__ void append_candidates(const f32x16 &acc, unsigned zero16, unsigned valid16, uint32_t q,
-                                                  float thr, float rq, uint64_t row0, int h, key_t64 *cand, unsigned int *counts)
+                                                  float thr, float rq, uint64_t row0, int h, key_t64 *cand, unsigned int *counts,
+                                                  uint32_t cap)
 {
     const unsigned pass = nomination_mask(acc, zero16, valid16, thr, rq);
-    if (__builtin_amdgcn_ballot_w64(pass != 0)) append_direct(acc, pass, zero16, q, rq, row0, h, cand, counts);
+    if (__builtin_amdgcn_ballot_w64(pass != 0)) append_direct(acc, pass, zero16, q, rq, row0, h, cand, counts, cap);
 }
 
 // Per query: keep the kp best of the candidates gathered so far (sorted, at the

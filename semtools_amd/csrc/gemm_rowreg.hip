@@ -32,7 +32,7 @@ namespace smt {
 // the wave's nomination buffer (its transpose buffer, idle during a sweep): keys at cb, queries behind them; n_buf is wave-uniform
 __device__ __forceinline__ void append_candidates_lds(const f32x16 &acc, unsigned zero16, unsigned valid16, uint32_t q, float thr, float rq,
                                                       uint64_t row0, int h, int lane, unsigned char *cb, uint32_t &n_buf,
-                                                      key_t64 *cand, unsigned int *counts CB_DBG_PARAMS)
+                                                      key_t64 *cand, unsigned int *counts CB_DBG_PARAMS, uint32_t cap = CAND_CAP)
 {
     // Every VALU instruction of an epilogue competes with the MFMA stream of the SIMD's other wave (~12 cycles apiece there), and
     // while it runs the block's other waves may be standing at the ring barrier.  So, in order of frequency:
@@ -73,7 +73,7 @@ __device__ __forceinline__ void append_candidates_lds(const f32x16 &acc, unsigne
             run += (uint32_t)__builtin_amdgcn_readlane((int)mine, l);
         }
         if (run > (uint32_t)RR_CB_CAP) {   // wave-uniform: no room: this tile goes straight to the lists
-            append_direct(acc, pass, zero16, q, rq, row0, h, cand, counts);
+            append_direct(acc, pass, zero16, q, rq, row0, h, cand, counts, cap);
             return;
         }
         n_buf = run;
@@ -109,20 +109,21 @@ __device__ __forceinline__ void append_candidates_lds(const f32x16 &acc, unsigne
                 n_buf += n;
             } else if (mine) {   // no room (a loose threshold): straight to the list
                 const unsigned slot = atomicAdd(&counts[q], 1u);
-                if (slot < CAND_CAP) cand[(size_t)q * CAND_CAP + slot] = key;
+                if (slot < cap) cand[(size_t)q * cap + slot] = key;
             }
         }
     }
     CB_STAMP(13);
 }
-__device__ __forceinline__ void flush_candidates_lds(int lane, const unsigned char *cb, uint32_t &n_buf, key_t64 *cand, unsigned int *counts)
+__device__ __forceinline__ void flush_candidates_lds(int lane, const unsigned char *cb, uint32_t &n_buf, key_t64 *cand, unsigned int *counts,
+                                                     uint32_t cap = CAND_CAP)
 {
     const key_t64 *keys = reinterpret_cast<const key_t64 *>(cb);
     const uint32_t *qs = reinterpret_cast<const uint32_t *>(cb + RR_CB_CAP * 8);
     for (uint32_t i = (uint32_t)lane; i < n_buf; i += 64) {
         const uint32_t q = qs[i];
         const unsigned slot = atomicAdd(&counts[q], 1u);
-        if (slot < CAND_CAP) cand[(size_t)q * CAND_CAP + slot] = keys[i];
+        if (slot < cap) cand[(size_t)q * cap + slot] = keys[i];
     }
     n_buf = 0;
 }
@@ -341,7 +342,7 @@ __global__ void __launch_bounds__(RR_THREADS, 2) gemm_rowreg_kernel(GemmParams p
 #pragma unroll
                 for (int m = 0; m < 16; ++m) Ah[m] = __builtin_nontemporal_load(img + m * 64);
                 RR_STAMP(2);
-                if (n_buf) flush_candidates_lds(lane, tbuf, n_buf, p.cand, p.counts);
+                if (n_buf) flush_candidates_lds(lane, tbuf, n_buf, p.cand, p.counts, p.cand_cap);
                 const uint32_t zm = p.image_zero[tile] >> (4 * h);   // bit 8u + c: tile row 8u + c + 4h
                 zero16 = 0;
                 valid16 = 0;
@@ -373,7 +374,7 @@ __global__ void __launch_bounds__(RR_THREADS, 2) gemm_rowreg_kernel(GemmParams p
             }
             RR_STAMP(2);   // row loads issued
             // the previous sweep's nominations leave the transpose buffer now: the atomics' round trip hides behind the row loads
-            if (n_buf) flush_candidates_lds(lane, tbuf, n_buf, p.cand, p.counts);
+            if (n_buf) flush_candidates_lds(lane, tbuf, n_buf, p.cand, p.counts, p.cand_cap);
             // ---- 1/|row| for the four rows this lane holds pieces of (8 lanes per row)
             float rb[4];
 #pragma unroll
@@ -534,9 +535,10 @@ __global__ void __launch_bounds__(RR_THREADS, 2) gemm_rowreg_kernel(GemmParams p
                 if (p.buffered) append_candidates_lds(acc, zero16, valid16, qt * QT_ROWS + j, qc.x, qc.y, row0, h, lane, tbuf, n_buf, p.cand, p.counts,
                                                       tracing && n_stamp < 1000 ? p.stamps + wave * 1024 : nullptr, n_stamp);
 #else
-                if (p.buffered) append_candidates_lds(acc, zero16, valid16, qt * QT_ROWS + j, qc.x, qc.y, row0, h, lane, tbuf, n_buf, p.cand, p.counts);
+                if (p.buffered) append_candidates_lds(acc, zero16, valid16, qt * QT_ROWS + j, qc.x, qc.y, row0, h, lane, tbuf, n_buf, p.cand, p.counts,
+                                                      p.cand_cap);
 #endif
-                else append_candidates(acc, zero16, valid16, qt * QT_ROWS + j, qc.x, qc.y, row0, h, p.cand, p.counts);
+                else append_candidates(acc, zero16, valid16, qt * QT_ROWS + j, qc.x, qc.y, row0, h, p.cand, p.counts, p.cand_cap);
             }
         };
         auto tile_product = [&](uint32_t qt, int slot, bool stage, uint32_t stage_qt, int stage_slot) __attribute__((always_inline)) {
@@ -582,7 +584,7 @@ __global__ void __launch_bounds__(RR_THREADS, 2) gemm_rowreg_kernel(GemmParams p
             }
         }
     }
-    if (n_buf) flush_candidates_lds(lane, tbuf, n_buf, p.cand, p.counts);
+    if (n_buf) flush_candidates_lds(lane, tbuf, n_buf, p.cand, p.counts, p.cand_cap);
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): no LDS-DMA may outlive the block's LDS allocation
 }
 

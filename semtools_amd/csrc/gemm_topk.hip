@@ -729,28 +729,30 @@ int launch_split_rows_bf16(smt_ctx *ctx, const float *rows, uint32_t n, uint32_t
 
 // ---- batched threshold pass: the exhaustive re-answer of MANY uncertain queries in one sweep (search.cpp).  Every row
 // whose nominating distance is <= tau[q] lands in query q's candidate buffer: gemm_rowreg_kernel over all tiles as a
-// single level with preset thresholds.  A query with more than CAND_CAP such rows reports count > CAND_CAP (the caller
+// single level with preset thresholds.  A query with more than `cap` such rows reports count > cap (the caller
 // re-answers it with the streaming K4 scan).  Buffers live in the context's scratch until the next launch.
 int launch_gemm_threshold(smt_ctx *ctx, const float *corpus, uint64_t rows, const void *image, const uint32_t *image_zero,
                           const float *queries, uint32_t nq, const float *tau, const key_t64 **cand_out,
-                          const unsigned int **counts_out, uint32_t *cand_stride)
+                          const unsigned int **counts_out, uint32_t *cand_stride, uint32_t cap, key_t64 *cand_ext, unsigned int *counts_ext)
 {
     const bool f16 = image != nullptr;   // over the corpus' operand image: f16 x 2 (the caller widened tau by F32_ERR_F16X2)
     SMT_REQUIRE(nq >= 1 && rows >= 1 && rows < 0xFFFFFFFFull, "threshold pass: bad sizes");
+    SMT_REQUIRE(cap >= 1 && (cand_ext == nullptr) == (counts_ext == nullptr), "threshold pass: candidate buffers");
     if (int rc_attr = ensure_gemm_attrs(ctx)) return rc_attr;
     const uint32_t nqt = (nq + QT_ROWS - 1) / QT_ROWS;
-    const size_t b_cand = (size_t)nq * CAND_CAP * sizeof(key_t64);
-    const size_t b_cnt = (((size_t)nq * 4) + 255) & ~(size_t)255;
+    const bool ext = cand_ext != nullptr;   // the caller's buffers [nq][cap] + [nq] (topk_large.hip): only the query staging is scratch
+    const size_t b_cand = ext ? 0 : (size_t)nq * cap * sizeof(key_t64);
+    const size_t b_cnt = ext ? 0 : (((size_t)nq * 4) + 255) & ~(size_t)255;
     const size_t b_qc = (((size_t)nqt * QT_ROWS * 8) + 255) & ~(size_t)255;
     const size_t b_split = (size_t)nqt * QT_ROWS * 1024;
     int rc = ensure_scratch(ctx, b_cand + b_cnt + b_qc + b_split + 256);
     if (rc) return rc;
     char *base = reinterpret_cast<char *>(ctx->d_scratch);
-    key_t64 *cand = reinterpret_cast<key_t64 *>(base);
-    unsigned int *counts = reinterpret_cast<unsigned int *>(base + b_cand);
+    key_t64 *cand = ext ? cand_ext : reinterpret_cast<key_t64 *>(base);
+    unsigned int *counts = ext ? counts_ext : reinterpret_cast<unsigned int *>(base + b_cand);
     float *qconst = reinterpret_cast<float *>(base + b_cand + b_cnt);
     uint32_t *q_split = reinterpret_cast<uint32_t *>(base + b_cand + b_cnt + b_qc);
-    SMT_HIP_CHECK(hipMemsetAsync(counts, 0, b_cnt, ctx->stream));
+    SMT_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)nq * sizeof(unsigned int), ctx->stream));
     if (f16) hipLaunchKernelGGL(split_queries_f16_kernel, dim3(nqt * QT_ROWS / 4), dim3(256), 0, ctx->stream, queries, nq, nqt * QT_ROWS, q_split);
     else hipLaunchKernelGGL(split_queries_kernel, dim3(nqt * QT_ROWS / 2), dim3(256), 0, ctx->stream, queries, nq, nqt * QT_ROWS, q_split);
     hipLaunchKernelGGL(query_consts_kernel, dim3(nqt * QT_ROWS / 4), dim3(256), 0, ctx->stream, queries, nq, nqt * QT_ROWS, qconst, f16 ? 1 : 0);
@@ -770,6 +772,7 @@ int launch_gemm_threshold(smt_ctx *ctx, const float *corpus, uint64_t rows, cons
     g.qconst = qconst;
     g.cand = cand;
     g.counts = counts;
+    g.cand_cap = cap;
     g.chunk_table = nullptr;
     g.tile_table = nullptr;
     g.stamps = nullptr;
@@ -787,7 +790,7 @@ int launch_gemm_threshold(smt_ctx *ctx, const float *corpus, uint64_t rows, cons
     SMT_HIP_CHECK(hipGetLastError());
     *cand_out = cand;
     *counts_out = counts;
-    *cand_stride = CAND_CAP;
+    *cand_stride = cap;
     return SMT_OK;
 }
 

@@ -1360,8 +1360,12 @@ int smt_sharded_search_topk_device_ex(smt_sharded_corpus *sc, const float *const
                                       uint64_t *const *out_packed, uint32_t *const *out_status)
 try {
     SMT_REQUIRE(sc && queries_dev && out_packed, "null argument");
-    SMT_REQUIRE(top_k >= 1 && top_k <= SCAN_MAX_K, "top_k must be in [1, 56]");
     smt_group *g = sc->group;
+    // 57 <= top_k <= 1024: every shard takes the large-k route (topk_large.hip, tuning key largek_sampled); the buffers below follow
+    // rank_words, the merges take n_ranks x top_k <= 8192 candidates
+    const bool largek = g->ctx[0]->tune.largek_sampled != 0;
+    SMT_REQUIRE(top_k >= 1 && top_k <= (largek ? LARGEK_MAX_K : SCAN_MAX_K),
+                largek ? "top_k must be in [1, 1024]" : "top_k must be in [1, 56] (largek_sampled = 0)");
     SMT_REQUIRE((uint64_t)g->n_ranks * top_k <= 8192, "device merge handles up to 8192 candidates per query");
     if (nq == 0) return SMT_OK;
     // with per-query verdicts wanted, every rank's nq status words (SMT_STATUS_* codes written by its select) travel behind its lists
@@ -1376,7 +1380,7 @@ try {
     for (int i = 0; i < g->n_local; ++i) SMT_REQUIRE(queries_dev[i] != nullptr, "queries_dev");
     // the select of a single query may run on the aux stream while the NEXT call's scan streams (async select); the exchange and
     // the merge then follow it there, and the main stream carries nothing but scans
-    for (int i = 0; i < g->n_local; ++i) on_aux[i] = g->ctx[i]->tune.async_select && nq == 1 && sc->shard[i]->rows >= top_k ? 1 : 0;
+    for (int i = 0; i < g->n_local; ++i) on_aux[i] = g->ctx[i]->tune.async_select && nq == 1 && sc->shard[i]->rows >= top_k && top_k <= SCAN_MAX_K ? 1 : 0;
     const bool spread = peer && g->spread_waits && g->workers != nullptr && g->n_local <= 64;
     std::vector<std::atomic<uint64_t>> awaiting(g->n_local);   // [m]: ranks whose list is published and whose wait on m's stream nobody has enqueued yet
     std::vector<std::atomic<int>> issued(g->n_local);          // [m]: m's own scan + select + publish are on its stream

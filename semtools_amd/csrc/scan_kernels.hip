@@ -497,67 +497,7 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
     if (p.stamps && threadIdx.x == 0) p.stamps[(uint64_t)gridDim.x * waves_per_block * 2 + blockIdx.x] = wall_clock64();
 }
 
-// --------------------------------------------------- exact f64 distance (A5)
-// Bit-for-bit the oracle's orc_cosine_f32_accurate: f64 accumulators, index
-// order, then cos_finish.  The product of two f32 values is exact in f64, so
-// fma(a, b, acc) rounds exactly like acc + a*b: letting the compiler contract
-// to v_fma_f64 cannot change a bit (the oracle is built with contraction off).
-// cos_finish of the oracle.  Contraction OFF here: 1 - (ab*ra)*rb must round the
-// products before the subtraction exactly as the CPU code does.
-__device__ __forceinline__ double cos_finish_exact(double ab, double a2, double b2)
-{
-#pragma clang fp contract(off)
-    if (a2 == 0.0 && b2 == 0.0) return 0.0;
-    if (ab == 0.0) return 1.0;
-    const double ra = 1.0 / sqrt(a2);
-    const double rb = 1.0 / sqrt(b2);
-    const double t = ab * ra;
-    const double u = t * rb;
-    const double unclipped = 1.0 - u;
-    return unclipped > 0.0 ? unclipped : 0.0;
-}
-
-// ab and b2 chains for one row (index order), a2 supplied by the caller (same for every row).
-template <typename QP, typename RP>
-__device__ __forceinline__ void exact_sums(QP q4, RP r4, double &ab_out, double &b2_out)
-{
-    double ab = 0.0, b2 = 0.0;
-#pragma unroll 8
-    for (int i = 0; i < 64; ++i) {
-        const f32x4 a = q4[i];
-        const f32x4 b = r4[i];
-        const double ax = a.x, ay = a.y, az = a.z, aw = a.w;
-        const double bx = b.x, by = b.y, bz = b.z, bw = b.w;
-        ab = ab + ax * bx; b2 = b2 + bx * bx;
-        ab = ab + ay * by; b2 = b2 + by * by;
-        ab = ab + az * bz; b2 = b2 + bz * bz;
-        ab = ab + aw * bw; b2 = b2 + bw * bw;
-    }
-    ab_out = ab;
-    b2_out = b2;
-}
-
-template <typename QP>
-__device__ __forceinline__ double exact_norm2(QP q4)
-{
-    double a2 = 0.0;
-#pragma unroll 8
-    for (int i = 0; i < 64; ++i) {
-        const f32x4 a = q4[i];
-        const double ax = a.x, ay = a.y, az = a.z, aw = a.w;
-        a2 = a2 + ax * ax; a2 = a2 + ay * ay; a2 = a2 + az * az; a2 = a2 + aw * aw;
-    }
-    return a2;
-}
-
-template <typename QP, typename RP>
-__device__ __forceinline__ double exact_distance(QP q4, RP r4)
-{
-    double ab, b2;
-    exact_sums(q4, r4, ab, b2);
-    return cos_finish_exact(ab, exact_norm2(q4), b2);
-}
-
+// --------------------------------------------------- exact f64 distance (A5): device_utils.h exact_distance
 __global__ void rescore_rows_kernel(const float *corpus, const float *query, const uint32_t *rows,
                                     uint64_t n, double *out)
 {
@@ -1463,8 +1403,19 @@ int launch_merge_topk_sources_on(hipStream_t st, const MergeSources &src, uint32
                                  uint64_t *out_packed)
 {
     SMT_REQUIRE(n_lists >= 1 && n_lists <= SMT_MAX_MERGE_SOURCES, "1..64 lists are merged in place");
-    SMT_REQUIRE((uint64_t)n_lists * k_in <= 4096, "the in-place merge stages up to 4096 candidates per query");
+    SMT_REQUIRE((uint64_t)n_lists * k_in <= 8192, "the in-place merge stages up to 8192 candidates per query");
     const size_t smem = (size_t)n_lists * k_in * 16;
+    if (smem > 64 * 1024) {   // more than 4096 candidates (large k: up to 8 x 1024): 128 KiB of LDS, allowed once per device
+        static bool big[64] = {};
+        int dev = 0;
+        SMT_HIP_CHECK(hipGetDevice(&dev));
+        if (dev < 0 || dev >= 64) return SMT_E_INVALID;
+        if (!big[dev]) {
+            SMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(merge_topk_sources_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              8192 * 16));
+            big[dev] = true;
+        }
+    }
     hipLaunchKernelGGL(merge_topk_sources_kernel, dim3(nq), dim3(256), smem, st, src, n_lists, (uint64_t)2 * k_in, k_in, k_out, out_packed,
                        reinterpret_cast<double *>(out_packed + k_out), (uint64_t)2 * k_out);
     SMT_HIP_CHECK(hipGetLastError());

@@ -388,6 +388,16 @@ static int topk_dispatch(smt_ctx *ctx, smt_corpus *corpus, ScanArgs &a)
 // (oracle: orc_search_line_embeddings against orc_cosine_*; src/workspace/store.rs:500-531).  The answer is a constant, so it is
 // written here instead of being computed: with a threshold nothing unless 0 > 1 - max_distance (f32), else the first top_k rows of
 // the subset in storage order (equal scores: earlier row first, as in the oracle), each at distance 1.0.
+// The large-k route (topk_large.hip) for a staged call: unfiltered batches of five or more queries sweep the corpus' fp16 operand image
+// when it has one (f16 x 2, half the bytes), like the batched re-answer; everything else reads the f32 rows.
+static int largek_route(smt_ctx *ctx, smt_corpus *corpus, ScanArgs &a)
+{
+    if (a.n_ranges == 0 && a.nq >= 5 && ctx->tune.gemm_image != 0 && corpus->rows <= (1ull << 28)) {
+        if (int rc_img = corpus_image_sync(corpus, a.nq, &a.image, &a.image_zero)) return rc_img;
+    }
+    return launch_topk_large(ctx, a);
+}
+
 bool query_is_zero(const float *q)
 {
     for (uint32_t d = 0; d < SMT_DIM; ++d)
@@ -491,7 +501,10 @@ static int search_local_host_impl(smt_corpus *corpus, const float *queries, uint
     const size_t p_bytes = (size_t)(nr + 1) * sizeof(uint64_t);
     // one persistent staging buffer per context: [queries | ranges | 3 prefixes | result lists] (no per-call hipMalloc/hipFree)
     const size_t in_bytes = (q_bytes + r_bytes + 3 * p_bytes + 255) & ~(size_t)255;
-    const uint32_t k_stage = all_under_threshold ? 0u : (uint32_t)std::min<uint64_t>(std::min<uint64_t>(top_k, n_virtual), 64);
+    // (the result lists of the large-k route, 57 <= k <= 1024, are staged here too)
+    const uint64_t k_lists = std::min<uint64_t>(top_k, n_virtual);
+    const bool largek_lists = ctx->tune.largek_sampled && k_lists > SCAN_MAX_K && k_lists <= LARGEK_MAX_K;
+    const uint32_t k_stage = all_under_threshold ? 0u : (uint32_t)std::min<uint64_t>(k_lists, largek_lists ? LARGEK_MAX_K : 64);
     const size_t out_bytes_stage = (size_t)nq * k_stage * 16 + (size_t)2 * nq * sizeof(uint64_t);
     if ((rc = ensure_stage(ctx, in_bytes + out_bytes_stage + 64))) return rc;
     char *stage = reinterpret_cast<char *>(ctx->d_stage);
@@ -526,7 +539,50 @@ static int search_local_host_impl(smt_corpus *corpus, const float *queries, uint
             const uint64_t n_cand = std::min<uint64_t>(n_virtual, (uint64_t)k_eff + guard);
             const bool ws_thr = (mode == SMT_MODE_WORKSPACE && has_thr);
             const float thr_score = 1.0f - (float)max_distance;
+            std::vector<char> proved(nq, 0);
+            if (ctx->tune.largek_sampled && k_eff <= LARGEK_MAX_K) {
+                // 57 <= k <= 1024: the sampled-threshold route (topk_large.hip) answers every query of the call in three launches;
+                // a query it cannot prove (ties across tau, an overflowed buffer) is re-answered below exactly as before
+                // lists [rows | distances | verdicts] in the stage behind the inputs, home through the pinned buffer
+                const size_t kw = (size_t)nq * k_eff, o_words = 2 * kw + nq;
+                uint64_t *d_out = reinterpret_cast<uint64_t *>(stage + in_bytes);
+                ScanArgs a{};
+                a.corpus = corpus->d_rows;
+                a.rows = corpus->rows;
+                a.queries = d_q;
+                a.nq = nq;
+                a.k_out = k_eff;
+                a.ranges = nr ? d_r : nullptr;
+                a.range_prefix = nr ? d_p : nullptr;
+                a.range_chunk_prefix = nr ? d_cp : nullptr;
+                a.n_chunks = n_chunks;
+                a.n_ranges = nr;
+                a.n_virtual = n_virtual;
+                a.ws_threshold = ws_thr ? 1 : 0;
+                a.ws_thr_score = thr_score;
+                a.row_base = row_base;
+                a.out_rows = d_out;
+                a.out_dist = reinterpret_cast<double *>(d_out + kw);
+                a.out_uncertain = d_out + 2 * kw;
+                a.range_set = rset;
+                if ((rc = largek_route(ctx, corpus, a))) return rc;
+                if ((rc = ensure_pinned(ctx, o_words * sizeof(uint64_t)))) return rc;
+                const uint64_t *h = reinterpret_cast<const uint64_t *>(ctx->h_pinned);
+                SMT_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned, d_out, o_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+                SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+                for (uint32_t q = 0; q < nq; ++q) {
+                    if (h[2 * kw + q] != SMT_STATUS_PROVED) continue;
+                    proved[q] = 1;
+                    const uint64_t *r = h + (size_t)q * k_eff;
+                    const double *d = reinterpret_cast<const double *>(h + kw) + (size_t)q * k_eff;
+                    uint32_t n = 0;
+                    while (n < k_eff && r[n] != UINT64_MAX) ++n;
+                    out[q].rows.assign(r, r + n);
+                    out[q].dist.assign(d, d + n);
+                }
+            }
             for (uint32_t q = 0; q < nq; ++q) {
+                if (proved[q]) continue;
                 std::vector<uint32_t> c_rows;
                 std::vector<double> c_dist;
                 float next_d32 = 0.f;
@@ -734,15 +790,17 @@ int deliver_hits(const std::vector<LocalHits> &hits, uint64_t *out_rows, double 
 // One shard's top-k with everything on the device (the exchange path of group.cpp).  queries_dev [nq x 256];
 // ranges_local = sorted, disjoint LOCAL row ranges (host array); filtered && n_ranges == 0 means "the filter
 // leaves this shard nothing to scan".  packed_dev [nq][2][k_pad] receives global rows, then f64 distance bit
-// patterns, padded with (UINT64_MAX, +inf).  1 <= k_pad <= SCAN_MAX_K.  Enqueued on the context's stream (the
+// patterns, padded with (UINT64_MAX, +inf).  1 <= k_pad <= LARGEK_MAX_K (above SCAN_MAX_K: topk_large.hip).  Enqueued on the context's stream (the
 // select stage on the aux stream when allow_async and the async_select tuning key say so); no host sync.
 int search_topk_packed_local(smt_corpus *corpus, const float *queries_dev, uint32_t nq, uint32_t k_pad, int ws_threshold,
                              float ws_thr_score, const smt_range *ranges_local, uint32_t n_ranges, bool filtered,
                              uint64_t row_base, uint64_t *packed_dev, uint64_t *uncertain_dev, bool allow_async)
 {
     SMT_REQUIRE(corpus && queries_dev && packed_dev, "null argument");
-    SMT_REQUIRE(k_pad >= 1 && k_pad <= SCAN_MAX_K, "top_k of the device exchange path must be in [1, 56]");
     smt_ctx *ctx = corpus->ctx;
+    SMT_REQUIRE(k_pad >= 1 && k_pad <= (ctx->tune.largek_sampled ? LARGEK_MAX_K : SCAN_MAX_K),
+                ctx->tune.largek_sampled ? "top_k of the device exchange path must be in [1, 1024]"
+                                         : "top_k of the device exchange path must be in [1, 56] (largek_sampled = 0)");
     uint64_t n_virtual = corpus->rows;
     std::vector<smt_range> rr;
     RangeSet *rset = nullptr;
@@ -757,7 +815,7 @@ int search_topk_packed_local(smt_corpus *corpus, const float *queries_dev, uint3
         n_virtual = total;
     }
     const uint32_t k_eff = (uint32_t)std::min<uint64_t>(k_pad, n_virtual);
-    const bool async = allow_async && ctx->tune.async_select && nq == 1 && !filtered && k_eff == k_pad;
+    const bool async = allow_async && ctx->tune.async_select && nq == 1 && !filtered && k_eff == k_pad && k_pad <= SCAN_MAX_K;
     int rc = bind_device(ctx, !async);
     if (rc) return rc;
     if (k_eff < k_pad) {  // short or empty shard: padding first, the select then overwrites the head of each list
@@ -817,7 +875,7 @@ int search_topk_packed_local(smt_corpus *corpus, const float *queries_dev, uint3
     a.allow_async = async;
     a.out_stride = (uint64_t)2 * k_pad;
     a.range_set = rset;
-    rc = topk_dispatch(ctx, corpus, a);
+    rc = k_eff > SCAN_MAX_K ? largek_route(ctx, corpus, a) : topk_dispatch(ctx, corpus, a);
     return rc;
 }
 
@@ -863,9 +921,11 @@ int smt_search_topk_device_ex(smt_corpus *corpus, const float *queries_dev, uint
 try {
     SMT_REQUIRE(corpus != nullptr, "corpus");
     SMT_REQUIRE(nq == 0 || (queries_dev && out_rows_dev && out_dist_dev), "null argument");
-    SMT_REQUIRE(top_k >= 1 && top_k <= SCAN_MAX_K, "top_k must be in [1, 56]");
     smt_ctx *ctx = corpus->ctx;
-    const bool async = ctx->tune.async_select && nq == 1 && corpus->rows > 0;  // launch_scan_topk keeps the pipeline going
+    const bool large = top_k > SCAN_MAX_K;   // 57..1024: the sampled-threshold route (topk_large.hip; tuning key largek_sampled)
+    SMT_REQUIRE(top_k >= 1 && top_k <= (ctx->tune.largek_sampled ? LARGEK_MAX_K : SCAN_MAX_K),
+                ctx->tune.largek_sampled ? "top_k must be in [1, 1024]" : "top_k must be in [1, 56] (largek_sampled = 0)");
+    const bool async = !large && ctx->tune.async_select && nq == 1 && corpus->rows > 0;  // launch_scan_topk keeps the pipeline going
     int rc = bind_device(ctx, !async);
     if (rc) return rc;
     if (nq == 0) return SMT_OK;
@@ -889,6 +949,7 @@ try {
     a.out_counts = nullptr;
     a.out_status = out_status_dev;
     a.allow_async = async;
+    if (large) return largek_route(ctx, corpus, a);   // (also pads the lists of an empty corpus)
     if (corpus->rows == 0) {
         // nothing to scan: fill with padding through the merge kernel on zero lists (an empty answer is a proved one)
         if (out_status_dev) SMT_HIP_CHECK(hipMemsetAsync(out_status_dev, 0, (size_t)nq * sizeof(uint32_t), ctx->stream));
