@@ -512,7 +512,8 @@ int smt_debug_group_fail_next(smt_group *group, int where, int code);
 int smt_debug_batched_scores(smt_corpus *corpus, const float *queries, uint32_t nq, uint64_t first_row, uint32_t n_rows,
                              float *out);
 
-/* The context's second stream (hipStream_t), created on first use: async selects run on it.  A host that
+/* The context's second stream (hipStream_t), created on first use: async selects run on it, or, with tuning key
+ * scan_overlap, it waits for them (every select of an overlapped call enqueued before the work).  A host that
  * chains more work behind an async select (an RCCL all-gather of its output, the merge of the gathered
  * lists with tuning key merge_on_aux) enqueues it here so that the main stream carries nothing but scans. */
 int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
@@ -557,11 +558,21 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *                        it, which the host waits on -- no D2H copy command, no hipStreamSynchronize (~10 us of a small call); 0: A/B
  *   prof_select (0/1), prof_every (N: HIP events on one launch in N)       profiling cost control
  *   scan_debug_ptr, select_debug_ptr                                       device pointers for phase stamps
- *   async_select (0/1)   smt_search_topk_device with ONE query: the select stage of call i runs on an
- *                        internal second stream WHILE the scan of call i+1 runs (device-scope flags between
- *                        the two kernels).  Outputs are complete after smt_ctx_synchronize (or any other
- *                        call on the context, which drains the pipeline first).  Throughput mode for
- *                        back-to-back single queries; off by default.
+ *   async_select (0/1)   smt_search_topk_device with ONE query: calls pipeline -- call i's select runs while call i+1
+ *                        scans.  By default (scan_overlap = 1, one unfiltered query) call i enqueues its scan AND its select
+ *                        on internal stream i & 1, behind an event on the context's stream (inputs written on that stream
+ *                        before the call are seen), so scan i + 1 also overlaps the end of scan i; the aux stream
+ *                        (smt_ctx_aux_stream) waits for each such select.  With scan_overlap = 0, and on the group path, the
+ *                        scans stay on the context's stream and the select runs on the aux stream, the two kernels meeting
+ *                        through device-scope flags.  Outputs are complete after smt_ctx_synchronize (or any other call on
+ *                        the context, which drains the pipeline first; both wait for every internal stream).  Throughput mode
+ *                        for back-to-back single queries; off by default.
+ *   scan_overlap (1/0)   see async_select (default 1; 0 = the aux-stream / flag pipeline).  A launch bracketed by profiling
+ *                        events (prof_every) waits for its predecessor and the next launch waits for it, so the events
+ *                        time the kernel alone, not the gate or a shared HBM.
+ *   scan_gate_pct (0..100)  scan_overlap: a scan's blocks start loading rows once this per cent of the previous scan's blocks have
+ *                        finished theirs, or after a bound of at most 0.5 ms (default 50; 0 = at once).  Changes timing only,
+ *                        never an answer
  *   merge_on_aux (0/1)   smt_merge_topk_packed_device is enqueued on the aux stream (see smt_ctx_aux_stream) */
 int smt_set_tuning(smt_ctx *ctx, const char *key, int64_t value);
 

@@ -57,8 +57,8 @@ class Context:
         return int(n.value)
 
     def aux_stream(self):
-        """Raw hipStream_t of the context's second stream (async selects run there); wrap it with
-        torch.cuda.ExternalStream to chain torch / RCCL work behind an async select."""
+        """Raw hipStream_t of the context's second stream (async selects run there, or -- tuning key scan_overlap -- it
+        waits for them); wrap it with torch.cuda.ExternalStream to chain torch / RCCL work behind an async select."""
         st = C.c_void_p()
         L.check(L.lib().smt_ctx_aux_stream(self._h, C.byref(st)))
         return int(st.value or 0)

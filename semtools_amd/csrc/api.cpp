@@ -29,7 +29,7 @@ int ensure_scratch(smt_ctx *ctx, size_t bytes)
     if (bytes <= ctx->scratch_bytes) return SMT_OK;
     // stream-ordered safety: earlier kernels (main stream, async selects on the aux stream) may still read the old buffer
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->aux_stream) SMT_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
+    if (int rc = sync_side_streams(ctx)) return rc;
     if (ctx->d_scratch) SMT_HIP_CHECK(hipFree(ctx->d_scratch));
     ctx->d_scratch = nullptr;
     ctx->scratch_bytes = 0;
@@ -50,10 +50,46 @@ int ensure_async(smt_ctx *ctx)
     return SMT_OK;
 }
 
+int ensure_overlap(smt_ctx *ctx)
+{
+    if (ctx->ov_stream[0]) return SMT_OK;
+    SMT_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&ctx->d_gate), 64));
+    SMT_HIP_CHECK(hipMemsetAsync(ctx->d_gate, 0, 64, ctx->stream));
+    SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    ctx->gate_total = 0;
+    ctx->gate_prev_blocks = 0;
+    ctx->gate_prev_rows = 0;
+    for (int b = 0; b < 2; ++b) SMT_HIP_CHECK(hipEventCreateWithFlags(&ctx->ov_ready[b], hipEventDisableTiming));
+    SMT_HIP_CHECK(hipEventCreateWithFlags(&ctx->ov_done, hipEventDisableTiming));
+    for (int b = 0; b < 2; ++b) SMT_HIP_CHECK(hipEventCreateWithFlags(&ctx->ov_sel[b], hipEventDisableTiming));
+    for (int b = 0; b < 2; ++b) SMT_HIP_CHECK(hipStreamCreateWithFlags(&ctx->ov_stream[b], hipStreamNonBlocking));
+    return SMT_OK;
+}
+
+int sync_side_streams(smt_ctx *ctx)
+{
+    if (ctx->aux_stream) SMT_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
+    for (hipStream_t st : ctx->ov_stream)
+        if (st) SMT_HIP_CHECK(hipStreamSynchronize(st));
+    return SMT_OK;
+}
+
+int order_aux_after_overlap(smt_ctx *ctx)
+{
+    if (!ctx->aux_stream || !ctx->ov_stream[0]) return SMT_OK;
+    for (int b = 0; b < 2; ++b) {
+        SMT_HIP_CHECK(hipEventRecord(ctx->ov_sel[b], ctx->ov_stream[b]));
+        SMT_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ctx->ov_sel[b], 0));
+    }
+    return SMT_OK;
+}
+
 int drain_async(smt_ctx *ctx)
 {
     if (!ctx->async_pending) return SMT_OK;
     ctx->async_pending = false;
+    for (hipStream_t st : ctx->ov_stream)   // scan_overlap: scan + select of a call, in stream order, on one of these
+        if (st) SMT_HIP_CHECK(hipStreamSynchronize(st));
     if (!ctx->aux_stream || !ctx->d_flags) return SMT_OK;
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));      // the scans the selects are waiting for
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
@@ -129,6 +165,13 @@ void prof_end_on(smt_ctx *ctx, const char *name, hipStream_t st)
     e.armed = false;
     (void)hipEventRecord(e.ev[e.used + 1], st);
     e.used += 2;
+}
+
+bool prof_arms_next(smt_ctx *ctx, const char *name)
+{
+    if (!ctx->prof_on) return false;
+    const uint64_t every = ctx->tune.prof_every > 1 ? (uint64_t)ctx->tune.prof_every : 1;
+    return ctx->prof[name].calls % every == 0;
 }
 
 void prof_begin(smt_ctx *ctx, const char *name) { prof_begin_on(ctx, name, ctx->stream); }
@@ -343,6 +386,13 @@ void smt_ctx_destroy(smt_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->aux_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
+    for (int b = 0; b < 2; ++b) {
+        if (ctx->ov_stream[b]) { (void)hipStreamSynchronize(ctx->ov_stream[b]); (void)hipStreamDestroy(ctx->ov_stream[b]); }
+        if (ctx->ov_ready[b]) (void)hipEventDestroy(ctx->ov_ready[b]);
+        if (ctx->ov_sel[b]) (void)hipEventDestroy(ctx->ov_sel[b]);
+    }
+    if (ctx->ov_done) (void)hipEventDestroy(ctx->ov_done);
+    if (ctx->d_gate) (void)hipFree(ctx->d_gate);
     if (ctx->d_flags) (void)hipFree(ctx->d_flags);
     if (ctx->d_status) (void)hipFree(ctx->d_status);
     if (ctx->d_steal) (void)hipFree(ctx->d_steal);
@@ -388,6 +438,7 @@ try {
     SMT_REQUIRE(stream_out != nullptr, "null argument");
     SMT_HIP_CHECK(hipSetDevice(ctx->device));
     if ((rc = ensure_async(ctx))) return rc;
+    if ((rc = order_aux_after_overlap(ctx))) return rc;   // (selects of overlapped calls made before the aux stream existed)
     *stream_out = reinterpret_cast<void *>(ctx->aux_stream);
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
@@ -415,7 +466,7 @@ try {
     if (rc) return rc;
     SMT_REQUIRE(kernel && launches && total_ms, "null argument");
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->aux_stream) SMT_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));   // ("exchange" / "merge" pairs may lie on it)
+    if ((rc = sync_side_streams(ctx))) return rc;   // ("exchange" / "merge" pairs may lie on aux, overlapped scans on the scan streams)
     *launches = 0;
     *total_ms = 0.0;
     auto it = ctx->prof.find(kernel);
@@ -488,6 +539,14 @@ try {
         int rc2 = drain_async(ctx);
         if (rc2) return rc2;
         ctx->tune.async_select = (int)value;
+    }
+    else if (k == "scan_overlap") {
+        int rc2 = drain_async(ctx);
+        if (rc2) return rc2;
+        ctx->tune.scan_overlap = value ? 1 : 0;
+    } else if (k == "scan_gate_pct") {
+        SMT_REQUIRE(value >= 0 && value <= 100, "scan_gate_pct: 0..100 per cent of the previous scan's blocks (0 = no gate)");
+        ctx->tune.scan_gate_pct = (int)value;
     }
     else if (k == "scan_debug_ptr") ctx->tune.scan_debug_ptr = value;
     else if (k == "select_debug_ptr") ctx->tune.select_debug_ptr = value;

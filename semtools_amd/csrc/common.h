@@ -63,6 +63,8 @@ struct Tuning {
     int prof_every = 1;         // HIP events bracket one launch in N (an event pair costs ~6 us of stream time)
     int merge_on_aux = 0;       // 1: smt_merge_topk_packed_device runs on the aux stream (behind the async select it consumes)
     int async_select = 0;       // 1: single-query top-k searches overlap their select stage with the next scan
+    int scan_overlap = 1;       // async_select, smt_search_topk_device: scan + select of call i on internal stream i & 1 (consecutive scans overlap; 0 = the aux-stream / flag pipeline)
+    int scan_gate_pct = 50;     // scan_overlap: a scan's blocks start once this share of its predecessor's blocks has finished its rows (0 = no gate)
     int gemm_image = 1;         // 1: batched searches read the corpus' fp16 operand image when it has one (0: A/B only)
     int64_t image_scan_min_rows = 1500000;   // shards this large answer ONE query from the operand image too, when they have one; 2..7 queries from a third of this (0: never)
     int64_t image_use_min_rows = 400000;     // a corpus that already HAS its image answers one query from it from this many rows (unfiltered calls), two from 1/5 of it, three and more from 1/60 (0: only the image_scan_min_rows rule)
@@ -116,6 +118,19 @@ struct smt_ctx {
     unsigned long long *d_flags = nullptr;  // [0] scan_done step, [1] select_done step, [2] blocks finished, [3] timeout flag
     uint64_t async_step = 0;
     bool async_pending = false;
+    bool async_overlap = false;              // the pending pipeline is the scan_overlap one (calls of the other kind drain it first)
+    // scan_overlap (tuning key): call i enqueues its scan AND its select on ov_stream[i & 1], behind ov_ready[i & 1] recorded on
+    // `stream`; consecutive scans overlap, paced by the start gate d_gate (scan_kernels.hip ScanParams::gate)
+    hipStream_t ov_stream[2] = {nullptr, nullptr};
+    hipEvent_t ov_ready[2] = {nullptr, nullptr};
+    hipEvent_t ov_done = nullptr;            // a profiled launch waits on its predecessor through this
+    hipEvent_t ov_sel[2] = {nullptr, nullptr};   // the select of the latest call on stream b: the aux stream waits on it (smt_ctx_aux_stream)
+    bool ov_after_timed = false;             // the previous overlapped scan was bracketed by profiling events
+    unsigned long long *d_gate = nullptr;    // blocks of overlapped scans that have finished their rows (monotonic)
+    uint64_t ov_step = 0;
+    uint64_t gate_total = 0;                 // blocks of all overlapped scans launched so far (the counter's value once they are done)
+    uint64_t gate_prev_blocks = 0;           // ... and of the latest one
+    uint64_t gate_prev_rows = 0;
     unsigned int *d_steal = nullptr;         // K2 STEAL: 64 group counters, one per launch in rotation (scan_kernels.hip)
     uint64_t steal_seq = 0;
     unsigned long long deliver_seq = 0;      // sequence number of the last delivered answer (its completion word in pinned memory)
@@ -207,6 +222,12 @@ int ensure_stage(smt_ctx *ctx, size_t bytes);
 // Wait for select kernels still running on the aux stream (no-op unless async_select was used).  Every entry
 // point that touches the context's scratch or reads results on the main stream calls this first.
 int drain_async(smt_ctx *ctx);
+// scan_overlap: the two scan streams, their events and the gate counter, made on first use
+int ensure_overlap(smt_ctx *ctx);
+// every stream that may still run kernels of this context besides `stream` (aux, the two scan streams)
+int sync_side_streams(smt_ctx *ctx);
+// scan_overlap + an aux stream: work enqueued on aux from now on runs behind every overlapped select enqueued so far
+int order_aux_after_overlap(smt_ctx *ctx);
 int ensure_async(smt_ctx *ctx);  // aux stream + flags
 
 // RAII-less helpers for event timing around a kernel family.
@@ -216,6 +237,8 @@ void prof_end(smt_ctx *ctx, const char *name);
 // ends in front of the merge that waited for every other rank's list)
 void prof_begin_on(smt_ctx *ctx, const char *name, hipStream_t st);
 void prof_end_on(smt_ctx *ctx, const char *name, hipStream_t st);
+// the next prof_begin* of `name` records an event pair (profiling on, and this call is the sampled one of prof_every)
+bool prof_arms_next(smt_ctx *ctx, const char *name);
 
 // ---- kernel launchers (defined in the .hip files) -------------------------
 // K2: single/few-query f32 scan with per-wave top-k' lists, then merge +
@@ -247,6 +270,7 @@ struct ScanArgs {
     uint32_t *out_status = nullptr;     // device [nq] or nullptr: the same verdict as a SMT_STATUS_* code per query -- what the
                                         // *_device_ex entry points hand their caller (include/semtools_hip.h)
     bool allow_async = false; // the caller does not read the outputs on the main stream before smt_ctx_synchronize
+    bool allow_overlap = false;   // ... and (smt_search_topk_device) the scan may leave the main stream too: tuning key scan_overlap
     const void *image = nullptr;          // the corpus' fp16 operand image covering all `rows` (smt_corpus::image), or nullptr
     const uint32_t *image_zero = nullptr;
     uint64_t out_stride = 0;  // words between the output lists of consecutive queries (0 = k_out); the packed
@@ -339,6 +363,7 @@ struct SelectArgs {
     // launch_gemm_topk read this flag back after every batch).
     const unsigned int *overflow = nullptr;
     const Delivery *deliver = nullptr;   // the last block carries the answers home (not with async_step)
+    hipStream_t stream = nullptr;        // the stream to enqueue on (nullptr: the context's; not with async_step)
 };
 int launch_select(smt_ctx *ctx, const SelectArgs &s);
 

@@ -115,7 +115,7 @@ int ensure_dev(smt_group *g, int i, size_t bytes)
     int rc = drain_async(c);
     if (rc) return rc;
     SMT_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (c->aux_stream) SMT_HIP_CHECK(hipStreamSynchronize(c->aux_stream));
+    if ((rc = sync_side_streams(c))) return rc;
     if (b.dev) SMT_HIP_CHECK(hipFree(b.dev));
     b.dev = nullptr;
     b.dev_bytes = 0;

@@ -37,6 +37,14 @@ struct ScanParams {
     unsigned int *steal_ctr;     // STEAL: this launch's group counter (zero at launch), see scan_topk_kernel
     uint32_t steal_lr;           // STEAL: log2 of the rounds per group
     uint32_t steal_static;       // STEAL: a block's first steal_static groups are dealt statically (group g of block b = g * blocks + b)
+    // START GATE (tuning keys scan_overlap, scan_gate_pct; nullptr = none): consecutive one-query scans run on two streams and overlap.
+    // Every block adds 1 to *gate once its waves have finished their rows, and thread 0 of every block waits, before any row load,
+    // until *gate >= gate_open -- the predecessor scan has finished scan_gate_pct per cent of its blocks' rows -- or gate_ticks of the
+    // 100 MHz wall clock have passed.  The counter only grows (the host keeps the running total), so a later launch reads as "open"
+    // too.  Advisory: it orders no data (list buffers and selects meet in stream order), so it can cost time, never an answer.
+    unsigned long long *gate;
+    unsigned long long gate_open;   // 0: no wait
+    unsigned long long gate_ticks;
 };
 
 // ---- async select: device-scope flags between the scan of step i (main stream) and its select (aux stream) ----
@@ -60,6 +68,13 @@ __device__ __forceinline__ void flag_wait(unsigned long long *flags, int which, 
         if (flag_load(flags + 3) != 0ull) break;
         if (wall_clock64() - t0 > 200000000ull) { flag_store(flags + 3, 1ull); break; }
     }
+}
+
+__device__ __forceinline__ void gate_wait(const ScanParams &p)
+{
+    if (flag_load(p.gate) >= p.gate_open) return;
+    const unsigned long long t0 = wall_clock64();
+    while (flag_load(p.gate) < p.gate_open && wall_clock64() - t0 < p.gate_ticks) __builtin_amdgcn_s_sleep(8);
 }
 
 // Range filter (path-subset search, src/workspace/store.rs:507-515): the rows to scan are the concatenation
@@ -227,6 +242,9 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
     // STEAL: ring[g & 7] = (group g of this block | its base slot / 2^steal_lr); the first STEAL_DEPTH groups are static
     uint2 *s_ring = reinterpret_cast<uint2 *>(s_next + 2);
     if (threadIdx.x == 0) *s_next = (uint32_t)waves_per_block;  // chunks 0..waves-1 are dealt: wave w starts on chunk w
+    if constexpr (!STEAL) {   // (the host never gates a STEAL launch: launch_scan_topk)
+        if (p.gate && threadIdx.x == 0 && p.gate_open) gate_wait(p);   // (the barrier below holds the other waves)
+    }
     if constexpr (STEAL) {
         if (threadIdx.x < 8) s_ring[threadIdx.x] = make_uint2(0xFFFFFFFFu, 0u);
     }
@@ -454,6 +472,9 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
     // stores, so every query -- the one-query headline launch included -- paid a store round trip or two in its tail: a one-row
     // search cost 4.4 / 9.4 / 15 / 18.5 us of scan kernel with 1 / 2 / 3 / 4 queries.)
     __syncthreads();
+    if constexpr (!STEAL) {
+        if (p.gate && threadIdx.x == 0) (void)__hip_atomic_fetch_add(p.gate, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     unsigned int *s_valid = reinterpret_cast<unsigned int *>(s_keys + (size_t)NQ * waves_per_block * 64);   // [NQ][waves] valid keys per wave list
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
@@ -1127,20 +1148,20 @@ static inline uint32_t candidates_per_list(const smt_ctx *ctx, uint32_t k_out)
 }
 
 template <int NQ, int U>
-static int launch_scan_variant(smt_ctx *ctx, const ScanParams &p, int blocks, int threads, bool nt)
+static int launch_scan_variant(smt_ctx *ctx, const ScanParams &p, int blocks, int threads, bool nt, hipStream_t st)
 {
     const size_t smem = (size_t)NQ * (threads / 64) * 64 * sizeof(key_t64) + 16 + 64 + 256;  // per-query, per-wave key slots (the chunk counter and the STEAL ring live in the second query's until the merge) + the waves' key counts
     dim3 g(blocks), b(threads);
     if constexpr (U == 4) {
         if (p.steal_ctr) {   // groups of rounds dealt while the kernel runs (512-thread blocks, checked by the caller)
-            if (nt) hipLaunchKernelGGL((scan_topk_kernel<NQ, U, true, false, true>), g, b, smem, ctx->stream, p);
-            else hipLaunchKernelGGL((scan_topk_kernel<NQ, U, false, false, true>), g, b, smem, ctx->stream, p);
+            if (nt) hipLaunchKernelGGL((scan_topk_kernel<NQ, U, true, false, true>), g, b, smem, st, p);
+            else hipLaunchKernelGGL((scan_topk_kernel<NQ, U, false, false, true>), g, b, smem, st, p);
             SMT_HIP_CHECK(hipGetLastError());
             return SMT_OK;
         }
     }
-    if (nt) hipLaunchKernelGGL((scan_topk_kernel<NQ, U, true, false>), g, b, smem, ctx->stream, p);
-    else hipLaunchKernelGGL((scan_topk_kernel<NQ, U, false, false>), g, b, smem, ctx->stream, p);
+    if (nt) hipLaunchKernelGGL((scan_topk_kernel<NQ, U, true, false>), g, b, smem, st, p);
+    else hipLaunchKernelGGL((scan_topk_kernel<NQ, U, false, false>), g, b, smem, st, p);
     SMT_HIP_CHECK(hipGetLastError());
     return SMT_OK;
 }
@@ -1211,15 +1232,16 @@ int launch_select(smt_ctx *ctx, const SelectArgs &a)
         SMT_HIP_CHECK(hipGetLastError());
         return SMT_OK;
     }
-    if (ctx->tune.prof_select) prof_begin(ctx, "select");
+    hipStream_t st = a.stream ? a.stream : ctx->stream;
+    if (ctx->tune.prof_select) prof_begin_on(ctx, "select", st);
     if (a.overflow) {
-        if (small) hipLaunchKernelGGL((final_select_kernel<8, true>), dim3(a.nq), dim3(SEL_THREADS), smem, ctx->stream, f);
-        else hipLaunchKernelGGL((final_select_kernel<36, true>), dim3(a.nq), dim3(SEL_THREADS), smem, ctx->stream, f);
+        if (small) hipLaunchKernelGGL((final_select_kernel<8, true>), dim3(a.nq), dim3(SEL_THREADS), smem, st, f);
+        else hipLaunchKernelGGL((final_select_kernel<36, true>), dim3(a.nq), dim3(SEL_THREADS), smem, st, f);
     } else {
-        if (small) hipLaunchKernelGGL(final_select_kernel<8>, dim3(a.nq), dim3(SEL_THREADS), smem, ctx->stream, f);
-        else hipLaunchKernelGGL(final_select_kernel<36>, dim3(a.nq), dim3(SEL_THREADS), smem, ctx->stream, f);
+        if (small) hipLaunchKernelGGL(final_select_kernel<8>, dim3(a.nq), dim3(SEL_THREADS), smem, st, f);
+        else hipLaunchKernelGGL(final_select_kernel<36>, dim3(a.nq), dim3(SEL_THREADS), smem, st, f);
     }
-    if (ctx->tune.prof_select) prof_end(ctx, "select");
+    if (ctx->tune.prof_select) prof_end_on(ctx, "select", st);
     SMT_HIP_CHECK(hipGetLastError());
     return SMT_OK;
 }
@@ -1243,11 +1265,19 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
     // async select (one query per call): two list buffers alternate, the select of step i reads buffer i&1 on
     // the aux stream while the scan of step i+1 fills the other one
     const bool async = a.allow_async && ctx->tune.async_select && a.nq == 1;
+    // scan_overlap: scan AND select of step i on scan stream i&1, behind an event on the main stream (the caller's inputs).  List
+    // buffer b belongs to stream b, so stream order protects it and no flag is needed; the two streams let scan i+1 start while
+    // scan i drains, paced by the start gate (ScanParams::gate).  (Not with STEAL: its counter ring is reset in stream order.)
+    const bool overlap = async && a.allow_overlap && ctx->tune.scan_overlap && !filtered && ctx->tune.scan_steal == 0;
     int rc = SMT_OK;
-    if (async && (rc = ensure_async(ctx))) return rc;
+    if (async && ctx->async_overlap != overlap && (rc = drain_async(ctx))) return rc;   // the two pipelines share the list buffers
+    if (async && (rc = overlap ? ensure_overlap(ctx) : ensure_async(ctx))) return rc;
     if (!async && (rc = drain_async(ctx))) return rc;
-    const uint64_t step = async ? ++ctx->async_step : 0;
-    const size_t list_bytes = (((size_t)a.nq * blocks * kp * sizeof(key_t64)) + 255) & ~(size_t)255;
+    const uint64_t step = overlap ? ++ctx->ov_step : async ? ++ctx->async_step : 0;
+    // (scan_overlap: scans of consecutive calls run at the same time, and their grids differ with the corpus -- the two buffers get a
+    // fixed place, the largest one-query list set, or a small call's buffer 1 would lie inside a large call's buffer 0)
+    const size_t list_bytes = overlap ? (size_t)SEL_MAX_LISTS * 64 * sizeof(key_t64)
+                                      : (((size_t)a.nq * blocks * kp * sizeof(key_t64)) + 255) & ~(size_t)255;
     const size_t table_bytes = filtered ? (size_t)n_chunks * sizeof(uint64_t) : 0;
     rc = ensure_scratch(ctx, 2 * list_bytes + table_bytes);
     if (rc != SMT_OK) return rc;
@@ -1255,7 +1285,28 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
     uint64_t *table = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(ctx->d_scratch) + 2 * list_bytes);
 
     const bool nt = ctx->tune.scan_nontemporal != 0;
-    prof_begin(ctx, "scan");
+    hipStream_t st = ctx->stream;
+    unsigned long long gate_open = 0, gate_ticks = 0;
+    if (overlap) {
+        st = ctx->ov_stream[step & 1];
+        SMT_HIP_CHECK(hipEventRecord(ctx->ov_ready[step & 1], ctx->stream));
+        SMT_HIP_CHECK(hipStreamWaitEvent(st, ctx->ov_ready[step & 1], 0));
+        // a timed launch waits for its predecessor (and that one's select), and the launch after it waits for it: the events bracket a
+        // kernel that has the part to itself, not a gate or an HBM shared with a neighbour
+        const bool timed = prof_arms_next(ctx, "scan");
+        if (timed || ctx->ov_after_timed) {
+            SMT_HIP_CHECK(hipEventRecord(ctx->ov_done, ctx->ov_stream[(step & 1) ^ 1]));
+            SMT_HIP_CHECK(hipStreamWaitEvent(st, ctx->ov_done, 0));
+        }
+        ctx->ov_after_timed = timed;
+        if (ctx->tune.scan_gate_pct > 0 && ctx->gate_prev_blocks > 0) {
+            gate_open = ctx->gate_total - ctx->gate_prev_blocks + (ctx->gate_prev_blocks * (uint64_t)ctx->tune.scan_gate_pct + 99) / 100;
+            // the bound: the predecessor's rows at 4 TB/s (half the part's HBM rate; 1 KiB rows, 10 ns ticks) + 20 us, at most 0.5 ms (a
+            // grid that cannot be resident twice -- scan_blocks / scan_threads -- may hold back predecessor blocks while it waits)
+            gate_ticks = std::min<uint64_t>(ctx->gate_prev_rows / 39 + 2000, 50000);
+        }
+    }
+    prof_begin_on(ctx, "scan", st);
     const uint64_t *use_table = table;
     if (filtered && (rc = range_chunk_table(ctx, a, table, &use_table))) return rc;
     for (uint32_t q0 = 0; q0 < a.nq;) {
@@ -1268,10 +1319,13 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
         p.kp = kp;
         p.block_lists = lists + (size_t)q0 * blocks * kp;
         p.stamps = reinterpret_cast<unsigned long long *>(ctx->tune.scan_debug_ptr);
-        p.flags = async ? ctx->d_flags : nullptr;
+        p.flags = async && !overlap ? ctx->d_flags : nullptr;
         p.step = step;
         p.steal_ctr = nullptr;
         p.steal_lr = 0;
+        p.gate = overlap ? ctx->d_gate : nullptr;
+        p.gate_open = gate_open;
+        p.gate_ticks = gate_ticks;
         // Dynamic groups (scan_topk_kernel STEAL; tuning key scan_steal = rounds per group, 0 = the static deal): unfiltered scans of
         // 8-wave blocks over enough rows that every block gets well past its static groups.  Each launch has its own counter: a ring
         // of 64, zeroed together every 64th launch (one 256-byte memset in stream order).
@@ -1296,24 +1350,33 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
         // query's for two / four queries -- 172 / 230 us at 1 M rows -- against 335 us for a pass of two and a pass of one)
         if (left >= 3) {
             rc = filtered ? launch_scan_filtered<4>(ctx, p, blocks, threads, nt)
-                 : (U == 4) ? launch_scan_variant<4, 4>(ctx, p, blocks, threads, nt)
-                            : launch_scan_variant<4, 8>(ctx, p, blocks, threads, nt);
+                 : (U == 4) ? launch_scan_variant<4, 4>(ctx, p, blocks, threads, nt, st)
+                            : launch_scan_variant<4, 8>(ctx, p, blocks, threads, nt, st);
             q0 += p.nq_active;
         } else if (left >= 2) {
             rc = filtered ? launch_scan_filtered<2>(ctx, p, blocks, threads, nt)
-                 : (U == 4) ? launch_scan_variant<2, 4>(ctx, p, blocks, threads, nt)
-                            : launch_scan_variant<2, 8>(ctx, p, blocks, threads, nt);
+                 : (U == 4) ? launch_scan_variant<2, 4>(ctx, p, blocks, threads, nt, st)
+                            : launch_scan_variant<2, 8>(ctx, p, blocks, threads, nt, st);
             q0 += 2;
         } else {
             if (filtered) rc = launch_scan_filtered<1>(ctx, p, blocks, threads, nt);
-            else if (U == 2) rc = launch_scan_variant<1, 2>(ctx, p, blocks, threads, nt);
-            else if (U == 4) rc = launch_scan_variant<1, 4>(ctx, p, blocks, threads, nt);
-            else rc = launch_scan_variant<1, 8>(ctx, p, blocks, threads, nt);
+            else if (U == 2) rc = launch_scan_variant<1, 2>(ctx, p, blocks, threads, nt, st);
+            else if (U == 4) rc = launch_scan_variant<1, 4>(ctx, p, blocks, threads, nt, st);
+            else rc = launch_scan_variant<1, 8>(ctx, p, blocks, threads, nt, st);
             q0 += 1;
         }
         if (rc != SMT_OK) return rc;
     }
-    prof_end(ctx, "scan");
+    prof_end_on(ctx, "scan", st);
+    if (overlap) {
+        ctx->gate_total += (uint64_t)blocks;
+        ctx->gate_prev_blocks = (uint64_t)blocks;
+        ctx->gate_prev_rows = a.n_virtual;
+        ctx->async_pending = true;
+        ctx->async_overlap = true;
+    } else if (async) {
+        ctx->async_overlap = false;
+    }
     SelectArgs s;
     s.corpus = a.corpus;
     s.queries = a.queries;
@@ -1329,13 +1392,20 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
     s.out_rows = a.out_rows;
     s.out_dist = a.out_dist;
     s.out_counts = a.out_counts;
-    s.async_step = step;
+    s.async_step = overlap ? 0 : step;
+    s.stream = st;
     s.out_stride = a.out_stride;
     s.f32_err = F32_ERR_SCAN;
     s.out_uncertain = a.out_uncertain;
     s.out_status = a.out_status;
     s.deliver = a.deliver;
-    return launch_select(ctx, s);
+    rc = launch_select(ctx, s);
+    // the aux stream's contract (smt_ctx_aux_stream): work a host chains there runs behind this call's select
+    if (rc == SMT_OK && overlap && ctx->aux_stream) {
+        SMT_HIP_CHECK(hipEventRecord(ctx->ov_sel[step & 1], st));
+        SMT_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ctx->ov_sel[step & 1], 0));
+    }
+    return rc;
 }
 
 int launch_rescore_rows(smt_ctx *ctx, const float *corpus, const float *query, const uint32_t *rows,

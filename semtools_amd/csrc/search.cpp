@@ -112,7 +112,7 @@ static int range_set_build(smt_corpus *corpus, const smt_range *ranges_in, uint3
         for (size_t i = 1; i < corpus->range_sets.size(); ++i)
             if (corpus->range_sets[i]->last_use < corpus->range_sets[lru]->last_use) lru = i;
         SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (ctx->aux_stream) SMT_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
+        if (int rc = sync_side_streams(ctx)) return rc;
         range_set_free(corpus->range_sets[lru]);
         corpus->range_sets.erase(corpus->range_sets.begin() + (long)lru);
     }
@@ -949,6 +949,7 @@ try {
     a.out_counts = nullptr;
     a.out_status = out_status_dev;
     a.allow_async = async;
+    a.allow_overlap = async;
     if (large) return largek_route(ctx, corpus, a);   // (also pads the lists of an empty corpus)
     if (corpus->rows == 0) {
         // nothing to scan: fill with padding through the merge kernel on zero lists (an empty answer is a proved one)

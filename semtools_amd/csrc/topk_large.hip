@@ -384,7 +384,7 @@ int ensure_largek(smt_ctx *ctx, size_t bytes)
 {
     if (bytes <= ctx->largek_bytes) return SMT_OK;
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->aux_stream) SMT_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
+    if (int rc_side = sync_side_streams(ctx)) return rc_side;
     if (ctx->d_largek) SMT_HIP_CHECK(hipFree(ctx->d_largek));
     ctx->d_largek = nullptr;
     ctx->largek_bytes = 0;
