@@ -186,7 +186,7 @@ struct smt_corpus {
     uint32_t small_searches = 0; // searches of < 8 queries seen while the shard was large enough to scan its image (search.cpp topk_dispatch)
     int image_mode = 0;          // 0: by policy (tuning key corpus_image; owned corpora only), 1: requested (smt_corpus_prepack), -1: refused
     struct smt::FileWriter *writer = nullptr;  // corpus_io.cpp: the background writer of SMT_APPEND_WRITE_AHEAD
-    std::vector<smt::RangeSet *> range_sets;   // search.cpp: ranges_on_device
+    std::vector<smt::RangeSet *> range_sets;   // search.cpp: RangePlan
     uint64_t range_clock = 0;
     uint64_t range_seen[16][2] = {};           // hashes of lists seen once (a set is built on the second sight)
     uint32_t range_seen_next = 0;
@@ -245,25 +245,25 @@ bool prof_arms_next(smt_ctx *ctx, const char *name);
 // f64 rescoring.  All pointers device.  Results: out_rows[nq][k_out],
 // out_dist[nq][k_out], out_counts[nq] (device).
 struct ScanArgs {
-    const float *corpus;      // [rows x 256]
-    uint64_t rows;            // rows in this shard (< 2^32)
-    const float *queries;     // device [nq x 256]
-    uint32_t nq;
-    uint32_t k_out;           // results wanted per query
-    const smt_range *ranges;  // device, or nullptr
-    const uint64_t *range_prefix;  // device exclusive prefix of range lengths [n_ranges+1] (large-k path)
-    const uint64_t *range_chunk_prefix;  // device exclusive prefix of ceil(len / FILTER_CHUNK) [n_ranges+1]
-    uint32_t n_ranges;
-    uint64_t n_virtual;       // rows to scan (sum of ranges, or rows)
-    uint64_t n_chunks;        // with ranges: total chunks = range_chunk_prefix[n_ranges]
+    const float *corpus = nullptr;      // [rows x 256]
+    uint64_t rows = 0;        // rows in this shard (< 2^32)
+    const float *queries = nullptr;     // device [nq x 256]
+    uint32_t nq = 0;
+    uint32_t k_out = 0;       // results wanted per query
+    const smt_range *ranges = nullptr;  // device, or nullptr
+    const uint64_t *range_prefix = nullptr;  // device exclusive prefix of range lengths [n_ranges+1] (large-k path)
+    const uint64_t *range_chunk_prefix = nullptr;  // device exclusive prefix of ceil(len / FILTER_CHUNK) [n_ranges+1]
+    uint32_t n_ranges = 0;
+    uint64_t n_virtual = 0;   // rows to scan (sum of ranges, or rows)
+    uint64_t n_chunks = 0;    // with ranges: total chunks = range_chunk_prefix[n_ranges]
     const uint64_t *range_tile_prefix = nullptr;  // device exclusive prefix of the aligned 32-row tiles each range is the FIRST to touch [n_ranges+1]
     uint64_t n_vtiles = 0;    // with ranges: tiles holding at least one wanted row = range_tile_prefix[n_ranges]
-    int ws_threshold;         // 1: apply score > thr_score (f32) in the final stage
-    float ws_thr_score;
-    uint64_t row_base;
-    uint64_t *out_rows;
-    double *out_dist;
-    uint64_t *out_counts;     // may be nullptr
+    int ws_threshold = 0;     // 1: apply score > thr_score (f32) in the final stage
+    float ws_thr_score = 0.f;
+    uint64_t row_base = 0;
+    uint64_t *out_rows = nullptr;
+    double *out_dist = nullptr;
+    uint64_t *out_counts = nullptr;     // may be nullptr
     uint64_t *out_uncertain = nullptr;  // device [nq] or nullptr: non-zero where the f32 nomination could not be PROVEN to
                                         // contain the exact top-k (see SelectArgs::f32_err; SMT_STATUS_* code); the host API
                                         // then re-answers that query exhaustively
@@ -298,15 +298,15 @@ inline bool tiles_dense(uint64_t n_virtual, uint64_t n_vtiles) { return n_vtiles
 // K4 (threshold.hip): every row with distance < max_distance, ordered (distance asc, row asc).
 // Returns pointers into the context's pinned staging buffer, valid until the next call on the context.
 struct ThresholdQuery {
-    const float *corpus;
-    uint64_t rows;
-    const float *query;       // device [256]
-    const smt_range *ranges;
-    const uint64_t *range_chunk_prefix;  // see ScanArgs
-    uint32_t n_ranges;
-    uint64_t n_virtual;
-    uint64_t n_chunks;
-    double max_distance;
+    const float *corpus = nullptr;
+    uint64_t rows = 0;
+    const float *query = nullptr;       // device [256]
+    const smt_range *ranges = nullptr;
+    const uint64_t *range_chunk_prefix = nullptr;  // see ScanArgs
+    uint32_t n_ranges = 0;
+    uint64_t n_virtual = 0;
+    uint64_t n_chunks = 0;
+    double max_distance = 0.0;
 };
 int run_threshold_query(smt_ctx *ctx, const ThresholdQuery &t, const uint32_t **rows_host, const double **dist_host,
                         uint64_t *n_pass);

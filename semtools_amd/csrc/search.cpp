@@ -2,14 +2,13 @@
 // calls) and the host logic behind them: which kernel answers a call (topk_dispatch), the exactness fall-backs, threshold mode,
 // delivery.  No CPU fallback: every path ends in a HIP kernel.
 #include <algorithm>
+#include <atomic>
 #include <cerrno>
+#include <chrono>
 #include <cmath>
 #include <limits>
 #include <string>
 #include <vector>
-
-#include <atomic>
-#include <chrono>
 
 #include "common.h"
 
@@ -56,10 +55,56 @@ void corpus_range_sets_drop(smt_corpus *c)
     c->range_sets.clear();
 }
 
-// Ranges validated (as validate_ranges) and identified in one pass; the set kept for this list if there is one, else nullptr
-// (with *build = true when the list has been seen before and deserves one now).
-static int range_set_find(smt_corpus *corpus, const smt_range *ranges, uint32_t n, uint64_t *total, RangeSet **found, bool *build,
-                          uint64_t *h1_out, uint64_t *h2_out)
+// The range filter of ONE search call, resolved in one place for the host form and the device exchange form alike: the set kept for
+// the list if the corpus has one (only the queries go up), else the non-empty ranges and their three prefixes, which the caller
+// stages with its own upload.  Two steps, because a call may end between them (nothing to scan, top_k = 0) and a list that ends a
+// call early is never built: range_plan_find validates and identifies the list, range_plan_finish prefixes it (and builds the kept
+// set on second sight).  Then bind() fixes the device pointers -- null without ranges -- and apply() hands them to a launch.
+struct RangePlan {
+    const smt_range *ranges_in = nullptr;   // the list as passed (empty ranges included: part of the identity)
+    uint32_t n_in = 0;
+    RangeSet *rset = nullptr;               // the kept set that answers for the list, or nullptr
+    bool build = false;                     // seen before and not kept: range_plan_finish builds the set
+    uint64_t h1 = 0, h2 = 0;
+    std::vector<smt_range> rr;              // without a kept set: the non-empty ranges ...
+    std::vector<uint64_t> prefixes;         // ... and [prefix | chunk_prefix | tile_prefix] (range_prefixes)
+    uint32_t nr = 0;                        // ranges on the device
+    uint64_t n_virtual = 0, n_chunks = 0, n_vtiles = 0;   // rows to scan (the caller starts it at the corpus' rows); chunks; tiles
+    const smt_range *d_r = nullptr;
+    const uint64_t *d_p = nullptr, *d_cp = nullptr, *d_tp = nullptr;
+
+    size_t r_bytes() const { return (size_t)nr * sizeof(smt_range); }
+    // bytes of [ranges | prefix | chunk_prefix | tile_prefix], and what of them the caller uploads (0: no ranges, or a kept set has them)
+    size_t table_bytes() const { return r_bytes() + 3 * (size_t)(nr + 1) * sizeof(uint64_t); }
+    size_t upload_bytes() const { return nr && !rset ? table_bytes() : 0; }
+    void write(char *host) const
+    {
+        if (!upload_bytes()) return;
+        memcpy(host, rr.data(), r_bytes());
+        memcpy(host + r_bytes(), prefixes.data(), prefixes.size() * sizeof(uint64_t));
+    }
+    // dev: where the caller's upload of upload_bytes() lies (not read when there is none)
+    void bind(char *dev)
+    {
+        if (rset) { d_r = rset->d_r; d_p = rset->d_p; d_cp = rset->d_cp; d_tp = rset->d_tp; }
+        else if (nr) {
+            d_r = reinterpret_cast<const smt_range *>(dev);
+            d_p = reinterpret_cast<const uint64_t *>(dev + r_bytes());
+            d_cp = d_p + (nr + 1);
+            d_tp = d_cp + (nr + 1);
+        }
+    }
+    void apply(ScanArgs &a) const
+    {
+        a.ranges = d_r; a.range_prefix = d_p; a.range_chunk_prefix = d_cp; a.range_tile_prefix = d_tp;
+        a.n_ranges = nr; a.n_virtual = n_virtual; a.n_chunks = n_chunks; a.n_vtiles = n_vtiles;
+        a.range_set = rset;
+    }
+};
+
+// Ranges validated (as validate_ranges) and identified in one pass: p.n_virtual, and the set kept for this list if there is one --
+// else its non-empty ranges (with p.build = true when the list has been seen before and deserves a set now).
+static int range_plan_find(smt_corpus *corpus, const smt_range *ranges, uint32_t n, RangePlan &p)
 {
     uint64_t prev_end = 0, t = 0, h1 = 0x9E3779B97F4A7C15ull ^ n, h2 = 0xC2B2AE3D27D4EB4Full + n;
     for (uint32_t i = 0; i < n; ++i) {
@@ -73,39 +118,36 @@ static int range_set_find(smt_corpus *corpus, const smt_range *ranges, uint32_t 
         h2 = (h2 + b) * 0x9FB21C651E98DF25ull; h2 = ((h2 << 31) | (h2 >> 33)) + e;
     }
     h1 = mix64(h1); h2 = mix64(h2 ^ t);
-    *total = t;
-    *h1_out = h1; *h2_out = h2;
-    *found = nullptr;
-    *build = false;
+    p.ranges_in = ranges; p.n_in = n;
+    p.n_virtual = t;
+    p.h1 = h1; p.h2 = h2;
     for (RangeSet *rs : corpus->range_sets)
         if (rs->h1 == h1 && rs->h2 == h2 && rs->n_in == n && rs->n_virtual == t && rs->host_ranges.size() == n &&
             (n == 0 || memcmp(rs->host_ranges.data(), ranges, (size_t)n * sizeof(smt_range)) == 0)) {   // (a collision must not answer for another subset)
             rs->last_use = ++corpus->range_clock;
             ++corpus->range_set_hits;
-            *found = rs;
+            p.rset = rs;
             return SMT_OK;
         }
+    for (uint32_t i = 0; i < n; ++i) if (ranges[i].end > ranges[i].begin) p.rr.push_back(ranges[i]);
     for (auto &seen : corpus->range_seen)
-        if (seen[0] == h1 && seen[1] == h2) { *build = true; return SMT_OK; }
+        if (seen[0] == h1 && seen[1] == h2) { p.build = true; return SMT_OK; }
     corpus->range_seen[corpus->range_seen_next % 16][0] = h1;
     corpus->range_seen[corpus->range_seen_next % 16][1] = h2;
     ++corpus->range_seen_next;
     return SMT_OK;
 }
 
-// A new kept set for (rr, prefixes): one device block, uploaded on the context's stream from pinned memory.
-static int range_set_build(smt_corpus *corpus, const smt_range *ranges_in, uint32_t n_in, uint64_t h1, uint64_t h2,
-                           const std::vector<smt_range> &rr, const std::vector<uint64_t> &prefixes, uint64_t n_virtual, RangeSet **out)
+// A new kept set for the plan's list (p.rr, p.prefixes): one device block, uploaded on the context's stream from pinned memory.
+static int range_set_build(smt_corpus *corpus, RangePlan &p)
 {
     smt_ctx *ctx = corpus->ctx;
-    *out = nullptr;
-    const uint32_t nr = (uint32_t)rr.size();
-    const uint64_t n_chunks = prefixes[2 * (nr + 1) - 1], n_vtiles = prefixes[3 * (nr + 1) - 1];
+    const uint32_t nr = p.nr;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t r_bytes = al((size_t)nr * sizeof(smt_range)), p_bytes = (size_t)(nr + 1) * sizeof(uint64_t);
     const size_t head = r_bytes + al(3 * p_bytes);
-    const bool keep_tables = (n_vtiles + n_chunks) * 8 <= RANGE_SET_TABLE_BYTES_MAX;
-    const size_t b_tile = keep_tables ? al((size_t)n_vtiles * 8) : 0, b_chunk = keep_tables ? al((size_t)n_chunks * 8) : 0;
+    const bool keep_tables = (p.n_vtiles + p.n_chunks) * 8 <= RANGE_SET_TABLE_BYTES_MAX;
+    const size_t b_tile = keep_tables ? al((size_t)p.n_vtiles * 8) : 0, b_chunk = keep_tables ? al((size_t)p.n_chunks * 8) : 0;
     if (corpus->range_sets.size() >= (size_t)RANGE_SETS_MAX) {
         // the least recently used set goes; kernels of earlier calls may still read it
         size_t lru = 0;
@@ -122,9 +164,9 @@ static int range_set_build(smt_corpus *corpus, const smt_range *ranges_in, uint3
         delete rs;
         return SMT_OK;
     }
-    rs->h1 = h1; rs->h2 = h2; rs->n_in = n_in; rs->nr = nr;
-    rs->host_ranges.assign(ranges_in, ranges_in + n_in);
-    rs->n_virtual = n_virtual; rs->n_chunks = n_chunks; rs->n_vtiles = n_vtiles;
+    rs->h1 = p.h1; rs->h2 = p.h2; rs->n_in = p.n_in; rs->nr = nr;
+    rs->host_ranges.assign(p.ranges_in, p.ranges_in + p.n_in);
+    rs->n_virtual = p.n_virtual; rs->n_chunks = p.n_chunks; rs->n_vtiles = p.n_vtiles;
     rs->d_r = reinterpret_cast<smt_range *>(rs->dev);
     rs->d_p = reinterpret_cast<uint64_t *>(rs->dev + r_bytes);
     rs->d_cp = rs->d_p + (nr + 1);
@@ -135,8 +177,8 @@ static int range_set_build(smt_corpus *corpus, const smt_range *ranges_in, uint3
     if (!rc) {
         // (h_pinned_in is reused by the caller for the queries: the upload must have left it before this returns -- once per set)
         char *pin = reinterpret_cast<char *>(ctx->h_pinned_in);
-        memcpy(pin, rr.data(), (size_t)nr * sizeof(smt_range));
-        memcpy(pin + r_bytes, prefixes.data(), 3 * p_bytes);
+        memcpy(pin, p.rr.data(), (size_t)nr * sizeof(smt_range));
+        memcpy(pin + r_bytes, p.prefixes.data(), 3 * p_bytes);
         hipError_t e = hipMemcpyAsync(rs->dev, pin, head, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) { set_error("range set upload: %s", hipGetErrorString(e)); rc = SMT_E_HIP; }
@@ -145,8 +187,20 @@ static int range_set_build(smt_corpus *corpus, const smt_range *ranges_in, uint3
     rs->last_use = ++corpus->range_clock;
     ++corpus->range_set_builds;
     corpus->range_sets.push_back(rs);
-    *out = rs;
+    p.rset = rs;
     return SMT_OK;
+}
+
+// The second step: nr / n_chunks / n_vtiles from the kept set, or from the prefixes made here -- and the set itself when p.build.
+static int range_plan_finish(smt_corpus *corpus, RangePlan &p)
+{
+    if (p.rset) { p.nr = p.rset->nr; p.n_chunks = p.rset->n_chunks; p.n_vtiles = p.rset->n_vtiles; return SMT_OK; }
+    p.nr = (uint32_t)p.rr.size();
+    if (!p.nr) return SMT_OK;
+    range_prefixes(p.rr, p.prefixes);
+    p.n_chunks = p.prefixes[2 * (p.nr + 1) - 1];
+    p.n_vtiles = p.prefixes[3 * (p.nr + 1) - 1];
+    return p.build ? range_set_build(corpus, p) : SMT_OK;
 }
 
 int range_tile_table(smt_ctx *ctx, const ScanArgs &a, uint64_t *scratch_table, const uint64_t **table)
@@ -181,38 +235,95 @@ int range_chunk_table(smt_ctx *ctx, const ScanArgs &a, uint64_t *scratch_table, 
     return launch_build_chunk_table(ctx, a.ranges, a.range_chunk_prefix, a.n_ranges, a.n_chunks, scratch_table);
 }
 
-// Exhaustive answer for ONE query whose f32 nomination failed its exactness certificate: K4 collects every row
-// whose exact distance is <= bound (its own f32 prefilter carries an 8e-6 guard band; rescoring is exact f64), in
-// (distance asc, row asc) order; the answer is the first k_eff of them (after the workspace score filter).
-// `bound` is the k-th exact distance found so far -- an upper bound of the true k-th -- or, when fewer than k rows
-// passed the workspace threshold, the largest distance that threshold admits.  O(rows <= bound): a cluster of
-// near-duplicates costs its own size, exactly what the reference pays for every query (it sorts all N).
-static int exact_fallback(smt_ctx *ctx, smt_corpus *corpus, const float *query_dev, const smt_range *ranges_dev,
-                          const uint64_t *chunk_prefix_dev, uint32_t nr, uint64_t n_virtual, uint64_t n_chunks, double bound,
-                          uint32_t k_eff, bool ws_thr, float thr_score, uint64_t row_base, LocalHits &out)
+// ---------------------------------------------------------------- launch arguments, the order of an answer
+// What every search call fills the same way; the caller adds what is its own (ranges: RangePlan::apply; outputs, stride, the
+// workspace threshold, async flags, delivery).
+static ScanArgs scan_args(const smt_corpus *corpus, const float *queries_dev, uint32_t nq, uint32_t k_out, uint64_t row_base)
+{
+    ScanArgs a;
+    a.corpus = corpus->d_rows;
+    a.rows = corpus->rows;
+    a.queries = queries_dev;
+    a.nq = nq;
+    a.k_out = k_out;
+    a.n_virtual = corpus->rows;
+    a.row_base = row_base;
+    return a;
+}
+
+// K4's arguments for ONE query of a call: every row of the plan with distance < max_distance
+static ThresholdQuery threshold_query(const smt_corpus *corpus, const float *query_dev, const RangePlan &plan, double max_distance)
 {
     ThresholdQuery t;
     t.corpus = corpus->d_rows;
     t.rows = corpus->rows;
     t.query = query_dev;
-    t.ranges = ranges_dev;
-    t.range_chunk_prefix = chunk_prefix_dev;
-    t.n_chunks = n_chunks;
-    t.n_ranges = nr;
-    t.n_virtual = n_virtual;
-    t.max_distance = std::nextafter(bound, std::numeric_limits<double>::infinity());  // K4 keeps d < max_distance: include == bound
+    t.ranges = plan.d_r; t.range_chunk_prefix = plan.d_cp;
+    t.n_ranges = plan.nr; t.n_virtual = plan.n_virtual; t.n_chunks = plan.n_chunks;
+    t.max_distance = max_distance;
+    return t;
+}
+
+// The workspace score rule (store.rs:502-503): a hit needs score > threshold, the score in f64, the threshold an f32.
+static inline bool ws_score_passes(double dist, float thr_score) { return (1.0 - dist) > (double)thr_score; }
+
+// Which of a query's candidates make its answer, besides the caller's distance bound: at most k, past the workspace threshold.
+struct HitRule {
+    uint64_t k = 0;
+    bool ws_thr = false;
+    float thr_score = 0.f;
+    uint64_t row_base = 0;
+};
+
+// The answer from n candidates with EXACT distances: those with distance <= bound (`strict`: < bound; either way NaN never passes;
+// +inf = no bound) that pass the rule's threshold, in (distance asc, row asc) order, the first k of them, as global rows.
+// `sorted`: the candidates come in that order already (K4).
+static void order_hits(const uint32_t *rows, const double *dist, uint64_t n, double bound, bool strict, bool sorted, const HitRule &rule,
+                       LocalHits &out)
+{
+    std::vector<uint64_t> order;
+    for (uint64_t i = 0; i < n && !(sorted && order.size() >= rule.k); ++i) {
+        if (strict ? !(dist[i] < bound) : !(dist[i] <= bound)) continue;
+        if (rule.ws_thr && !ws_score_passes(dist[i], rule.thr_score)) continue;
+        order.push_back(i);
+    }
+    if (!sorted)
+        std::sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) {
+            if (dist[x] != dist[y]) return dist[x] < dist[y];
+            return rows[x] < rows[y];
+        });
+    const uint64_t m = std::min<uint64_t>(order.size(), rule.k);
+    out.rows.resize(m);
+    out.dist.resize(m);
+    for (uint64_t i = 0; i < m; ++i) {
+        out.rows[i] = rule.row_base + rows[order[i]];
+        out.dist[i] = dist[order[i]];
+    }
+}
+
+// Sweeps that may read the corpus' fp16 operand image instead of its f32 rows (the batched re-answer, the large-k route)
+static inline bool image_sweep_allowed(const smt_ctx *ctx, const smt_corpus *corpus)
+{
+    return ctx->tune.gemm_image != 0 && corpus->rows <= (1ull << 28);
+}
+
+// Exhaustive answer for ONE query whose f32 nomination failed its exactness certificate: K4 collects every row
+// whose exact distance is <= bound (its own f32 prefilter carries an 8e-6 guard band; rescoring is exact f64), in
+// (distance asc, row asc) order; the answer is the first k of them (after the workspace score filter).
+// `bound` is the k-th exact distance found so far -- an upper bound of the true k-th -- or, when fewer than k rows
+// passed the workspace threshold, the largest distance that threshold admits.  O(rows <= bound): a cluster of
+// near-duplicates costs its own size, exactly what the reference pays for every query (it sorts all N).
+static int exact_fallback(smt_ctx *ctx, smt_corpus *corpus, const float *query_dev, const RangePlan &plan, double bound, const HitRule &rule,
+                          LocalHits &out)
+{
+    const double inf = std::numeric_limits<double>::infinity();
+    const ThresholdQuery t = threshold_query(corpus, query_dev, plan, std::nextafter(bound, inf));  // K4 keeps d < max_distance: include == bound
     const uint32_t *h_rows = nullptr;
     const double *h_dist = nullptr;
     uint64_t n_ok = 0;
     int rc = run_threshold_query(ctx, t, &h_rows, &h_dist, &n_ok);
     if (rc) return rc;
-    out.rows.clear();
-    out.dist.clear();
-    for (uint64_t i = 0; i < n_ok && out.rows.size() < k_eff; ++i) {
-        if (ws_thr && !((1.0 - h_dist[i]) > (double)thr_score)) continue;  // store.rs:502-503
-        out.rows.push_back(row_base + h_rows[i]);
-        out.dist.push_back(h_dist[i]);
-    }
+    order_hits(h_rows, h_dist, n_ok, inf, false, /*sorted=*/true, rule, out);
     return SMT_OK;
 }
 
@@ -220,10 +331,10 @@ static int exact_fallback(smt_ctx *ctx, smt_corpus *corpus, const float *query_d
 // row whose nominating distance is <= bound + F32_ERR_BF16X3 (a superset of the rows with exact distance <= bound);
 // they are re-scored exactly, ordered (distance, row) and cut at k -- what exact_fallback does with one K4 scan per
 // query.  Queries whose band holds more rows than a candidate buffer (2048) come back in `left` for the K4 route.
-// The same sweep answers threshold searches of several queries at once (`strict`: distance < bound, every hit: k_eff = all).
+// The same sweep answers threshold searches of several queries at once (`strict`: distance < bound, every hit: rule.k = all).
 static int batched_fallback(smt_ctx *ctx, smt_corpus *corpus, const float *queries_dev, const std::vector<uint32_t> &redo,
-                            const std::vector<double> &bounds, uint64_t k_eff, bool ws_thr, float thr_score, uint64_t row_base,
-                            std::vector<LocalHits> &out, std::vector<uint32_t> &left, bool strict = false)
+                            const std::vector<double> &bounds, const HitRule &rule, std::vector<LocalHits> &out,
+                            std::vector<uint32_t> &left, bool strict = false)
 {
     const uint32_t n = (uint32_t)redo.size();
     float *d_qc = nullptr;   // compact copies of the uncertain queries + their f32 thresholds (rare path: plain hipMalloc)
@@ -235,7 +346,7 @@ static int batched_fallback(smt_ctx *ctx, smt_corpus *corpus, const float *queri
     // the sweep runs over the corpus' fp16 operand image when it has one (f16 x 2, half the bytes), else over the f32 rows (bf16 x 3)
     const void *image = nullptr;
     const uint32_t *image_zero = nullptr;
-    if (ctx->tune.gemm_image != 0 && corpus->rows <= (1ull << 28)) {
+    if (image_sweep_allowed(ctx, corpus)) {
         if (int rc_img = corpus_image_sync(corpus, n, &image, &image_zero)) return rc_img;
     }
     const double band = image ? F32_ERR_F16X2 : F32_ERR_BF16X3;
@@ -281,118 +392,84 @@ static int batched_fallback(smt_ctx *ctx, smt_corpus *corpus, const float *queri
     }
     for (uint32_t i = 0; i < n; ++i) {
         if (cnt[i] > stride) { left.push_back(redo[i]); continue; }
-        std::vector<uint64_t> order;
-        for (uint64_t c = first[i]; c < first[i + 1]; ++c) {
-            if (strict ? !(dist[c] < bounds[i]) : !(dist[c] <= bounds[i])) continue;   // (also drops NaN)
-            if (ws_thr && !((1.0 - dist[c]) > (double)thr_score)) continue;         // store.rs:502-503
-            order.push_back(c);
-        }
-        std::sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) {
-            if (dist[x] != dist[y]) return dist[x] < dist[y];
-            return rows[x] < rows[y];
-        });
-        LocalHits &o = out[redo[i]];
-        o.rows.clear();
-        o.dist.clear();
-        for (uint64_t c : order) {
-            if (o.rows.size() >= k_eff) break;
-            o.rows.push_back(row_base + rows[c]);
-            o.dist.push_back(dist[c]);
-        }
+        order_hits(rows.data() + first[i], dist.data() + first[i], first[i + 1] - first[i], bounds[i], strict, /*sorted=*/false, rule,
+                   out[redo[i]]);
     }
     return SMT_OK;
 }
 
-// The body of smt_search with per-query result vectors instead of caller arrays: group.cpp runs it once per
-// local shard (threshold mode / top_k > 64, whose result sizes are not known up front) and exchanges the lists.
+// ---------------------------------------------------------------- K2 or K3
+// Which kernel answers a top-k call of nq queries over `scanned` rows: the scan kernel (K2, <= 4 queries per corpus pass) or the
+// batched kernel (K3, one pass for the whole batch; about 1.15 single-query passes whatever its size, while a K2 pass slows down
+// with every query it carries).  A pure function of the tuning and the call; the rule as it stands (us per host call, K2 | K3; the
+// measurements that moved each border over rounds 2-5 are in profiles/HISTORY.md, "topk_dispatch"):
+//  * 8+ queries: K3, always.
+//  * `rowreg` -- gemm_bf16x3 and gemm_rowreg on, and a range-filtered call fills its 32-row tiles (tiles_dense, common.h; it counts
+//    with the rows it SCANS) -- is required by every rule below.
+//  * gemm_min_nq (5) .. 7 queries: K3 at every size when unfiltered (five queries 1000 rows 89 | 76, 2 M 709 | 472); document subsets
+//    once rows x queries >= 1.2 x gemm_min_rows_small (1 M), their tile table being one more launch (profiles/r04_k2_k3_small.json).
+//  * up to two queries below gemm_min_nq (three, four), unfiltered: K3 between gemm_min_rows_small / 50 and 4/5 of it, 20 k .. 800 k
+//    rows (three queries 50 k 88 | 79, 700 k 213 | 208, 1 M 259 | 266; two: K2 everywhere; profiles/r05_sweep_crossover.json).
+//  * the fp16 operand image (gemm_image, a call over the whole corpus, not async; image_scan_min_rows > 0): K3 over 512-B rows
+//    - from image_scan_min_rows (1.5 M) rows for one or two queries, 2/3 of that for three and more, filtered calls included (one
+//      query 1.5 M 245 | 214, 4 M 612 | 461; profiles/r04_image_scan_sweep.json).  Calls of < 8 queries this large COUNT towards
+//      building the image of an owned corpus that has none (topk_dispatch);
+//    - an image that EXISTS answers unfiltered calls from image_use_min_rows (400 k) rows for one query, 1/5 of that for two, 1/60
+//      for three and more (one query 300 k 83 | 86, 500 k 111 | 105; two 50 k 68 | 68, 100 k 77 | 71; profiles/r05_sweep_crossover.json).
+struct Route {
+    bool batched;            // K3 answers
+    bool rowreg;             // ... with gemm_rowreg_kernel, which reads the image of a whole corpus
+    bool counts_for_image;
+};
+// a: what the call asks (nq, n_virtual = the rows it scans, n_ranges, n_vtiles, allow_async); whole: it covers the corpus' own rows, all
+// of them; has_image: the corpus has an operand image and may use it
+static Route topk_route(const Tuning &tune, const ScanArgs &a, bool whole, bool has_image)
+{
+    const uint64_t scanned = a.n_virtual;
+    const bool rowreg = tune.gemm_bf16x3 && tune.gemm_rowreg && (a.n_ranges == 0 || tiles_dense(scanned, a.n_vtiles));
+    const uint64_t small = (uint64_t)tune.gemm_min_rows_small;
+    const bool image_ok = rowreg && tune.gemm_image && !a.allow_async && whole && tune.image_scan_min_rows > 0;
+    const uint64_t image_min = (uint64_t)tune.image_scan_min_rows * (a.nq >= 3 ? 2 : 3) / 3;
+    const bool scan_sized = image_ok && scanned >= image_min;
+    const uint64_t use_min = (uint64_t)tune.image_use_min_rows * (a.nq >= 3 ? 1 : a.nq == 2 ? 12 : 60) / 60;
+    const bool use_sized = image_ok && a.n_ranges == 0 && tune.image_use_min_rows > 0 && scanned >= use_min;
+    const bool mid_band = a.n_ranges == 0 && a.nq >= 3 && a.nq + 2 >= (uint32_t)tune.gemm_min_nq && small > 0 &&
+                          scanned >= small / 50 && scanned <= small / 5 * 4;
+    const bool batched = a.nq >= 8 ||
+                         (rowreg && a.nq >= (uint32_t)tune.gemm_min_nq && (a.n_ranges == 0 || scanned * a.nq >= small + small / 5)) ||
+                         (rowreg && mid_band) || ((scan_sized || use_sized) && has_image);
+    return Route{batched, rowreg, scan_sized && a.nq < 8};
+}
 
-// K2 (scan, <= 4 queries per corpus pass) or K3 (batched, one pass for the whole batch)?  8+ queries always take K3.
-// With the bf16 x 3 row-register kernel a batch costs about 1.15 single-query passes whatever its size, while a K2 pass
-// slows down with every query it carries (per row and query a DPP reduction tree: 10 M rows, 1 / 2 / 4 queries per
-// pass = 1.43 / 2.0 / 3.2 ms).  Measured on MI355X, wall ms per call, K2 | K3:
-//   10 M rows: 2 queries 2.03 | 1.77, 3: 3.54 | 1.84, 4: 3.24 | 1.71, 5: 4.83 | 1.75, 7: 6.71 | 1.77
-//    2 M rows: 2: 0.49 | 0.52, 3: 0.87 | 0.52, 4: 0.75 | 0.53;   1 M rows: 2: 0.27 | 0.36, 3: 0.44 | 0.37, 4: 0.42 | 0.37
-//  300 k rows: 3: 0.17 | 0.25 (K3's fixed cost: five level launches + selects)
-// => (rounds 2-3) K3 from gemm_min_nq (3) queries on shards of gemm_min_rows_small (1 M) rows, from 2 queries on 4 x that;
-// round 4: from gemm_min_nq queries when rows x queries >= 1.2 x gemm_min_rows_small (see below).
+// One top-k launch by the rule above; a batched launch that answers SMT_E_UNSUPPORTED falls back to the scan kernel.
+// A resident host asking one query at a time -- `semtools serve` -- never sends the batch of 8 that builds the image of an owned
+// corpus: the fourth counted search builds it here, and the route is asked again because this same call then uses it.
 static int topk_dispatch(smt_ctx *ctx, smt_corpus *corpus, ScanArgs &a)
 {
-    // (range-filtered calls whose rows fill their 32-row tiles well enough take the same kernel over a tile table -- tiles_dense,
-    // common.h -- and count with the rows they SCAN)
-    const bool fast_k3 = ctx->tune.gemm_bf16x3 && ctx->tune.gemm_rowreg && (a.n_ranges == 0 || tiles_dense(a.n_virtual, a.n_vtiles));
-    const uint64_t small = (uint64_t)ctx->tune.gemm_min_rows_small;
-    const uint64_t scanned = a.n_virtual;
-    // A corpus that HAS its fp16 operand image answers even one or two queries through the batched kernel once the shard is
-    // large (tuning key image_scan_min_rows; 4 M in round 3, 1.5 M now): one pass over 512-B rows plus the levels and selects beats a scan
-    // pass over 1 KiB rows -- 10 M rows: 0.95 against 1.5 ms; the scan kernel keeps the small shards and the async mode.
-    // (A resident host asking one query at a time -- `semtools serve` -- never sends the batch of 8 that builds the image of an
-    // owned corpus: the fourth small search of a shard this large builds it.)
     const bool whole = corpus->d_rows == a.corpus && corpus->rows == a.rows;
-    // Round 4, measured again with the bootstrap plan (profiles/r04_image_scan_sweep.json, us per call, scan of the f32 rows | batched
-    // kernel over the image): ONE query 1 M rows 170 | 170, 1.5 M 245 | 214, 2 M 321 | 264, 4 M 612 | 461; TWO queries 0.5 M 134 | 120,
-    // 1 M 230 | 167, 2 M 424 | 261 -- the image answers one query from image_scan_min_rows (1.5 M) rows, two and more from a third of that.
-    // Late in round 4 the scan kernel reduces the four rows of a chunk together when it carries several queries (scan_kernels.hip
-    // SMT_REDUCE_CHUNK4): two queries cost 1.06 x one query's pass, four 1.4 x (were 1.4 x / 2.3 x) -- 1 M rows: 172 / 230 us, 2 M: 315 /
-    // 381 -- so the image takes over where it does for one query (two queries) or at two thirds of that (three, four).
-    const uint64_t image_min = (uint64_t)ctx->tune.image_scan_min_rows * (a.nq >= 3 ? 2 : 3) / 3;
-    const bool scan_sized = fast_k3 && ctx->tune.gemm_image && !a.allow_async && whole &&
-                            ctx->tune.image_scan_min_rows > 0 && scanned >= image_min;
-    // Round 5, late: every route timed alone across sizes (profiles/r05_sweep_crossover.json, tools/sweep_crossover.py; us per host
-    // call, scan kernel | batched kernel over the image): ONE query 500 k rows 110 | 114, 700 k 139 | 132, 1 M 181 | 155, 1.5 M 254 | 193;
-    // TWO 200 k 91 | 92, 300 k 103 | 95, 500 k 130 | 111, 1 M 200 | 156; THREE 50 k 88 | 66, 100 k 104 | 88, 1 M 259 | 161; four and more:
-    // the image at every size (1000 rows: 80 | 70).  The batched call lost its host read-back in this round and with it ~25 us: an
-    // image that EXISTS is used from image_use_min_rows rows by one query, 1/5 of that by two, 1/60 by three and more (unfiltered
-    // calls; building one for a corpus that has none keeps the thresholds above).  Measured once more after the bootstrap stride of
-    // mid-sized corpora was graded (gemm_topk.hip; same table): ONE query 300 k rows 83 | 86, 500 k 111 | 105; TWO 50 k 68 | 68, 100 k
-    // 77 | 71, 300 k 104 | 86 -- image_use_min_rows = 400 k.
-    const uint64_t use_min = (uint64_t)ctx->tune.image_use_min_rows * (a.nq >= 3 ? 1 : a.nq == 2 ? 12 : 60) / 60;
-    const bool use_sized = fast_k3 && ctx->tune.gemm_image && !a.allow_async && whole && a.n_ranges == 0 && ctx->tune.image_scan_min_rows > 0 &&
-                           ctx->tune.image_use_min_rows > 0 && scanned >= use_min;
-    if (scan_sized && a.nq < 8 && !corpus->image && corpus->owned && corpus->image_mode == 0 && ctx->tune.corpus_image != 0 &&
+    Route r = topk_route(ctx->tune, a, whole, corpus->image && corpus->image_mode >= 0);
+    if (r.counts_for_image && !corpus->image && corpus->owned && corpus->image_mode == 0 && ctx->tune.corpus_image != 0 &&
         ++corpus->small_searches >= 4) {
         const void *img;
         const uint32_t *zero;
         corpus->image_mode = 1;
         if (int rc_img = corpus_image_sync(corpus, a.nq, &img, &zero)) return rc_img;
         if (corpus->image_mode == 1) corpus->image_mode = 0;   // (-1 when there was no room)
+        r = topk_route(ctx->tune, a, whole, corpus->image && corpus->image_mode >= 0);
     }
-    const bool image_scan = (scan_sized || use_sized) && corpus->image && corpus->image_mode >= 0;
-    // Round 4 (bootstrap level: three launches and three select passes fewer per batch) moved the crossover down; measured again
-    // (profiles/r04_k2_k3_small.json, us per device-resident call, K2 | K3, no image): 400 k rows 3 queries 175 | 172, 4: 182 | 170,
-    // 5: 244 | 171; 200 k rows 4: 115 | 134, 5: 152 | 133, 7: 210 | 138; 100 k rows 5: 104 | 120, 7: 141 | 129; 1 M rows 2: 236 | 275,
-    // 3: 377 | 296; 2 M rows 2: 428 | 457 -- K3 from gemm_min_nq queries once rows x queries reaches 1.2 x gemm_min_rows_small.
-    // With the chunk-wise reduction (us per call, K2 | K3, profiles/r04_k2_k3_small.json refreshed): 1 M rows 2 queries 172 | 264, 4: 230 |
-    // 270, 5: 379 | 280; 400 k rows 4: 134 | 161, 5: 196 | 162; 100 k rows 5: 98 | 111, 7: 133 | 117; 2 M rows 4: 381 | 455, 5: 672 | 475 --
-    // up to four queries stay on the scan kernel (gemm_min_nq = 5), five to seven move as before.
-    // Same sweep, scan kernel | batched kernel over f32 rows: FIVE queries 1000 rows 89 | 76, 100 k 131 | 99, 2 M 709 | 472 -- the batched
-    // kernel at every size (unfiltered; the rows x queries bound above stays for document subsets, whose tile table is one more
-    // launch); THREE 50 k 88 | 79, 300 k 146 | 129, 700 k 213 | 208, 1 M 259 | 266; FOUR 50 k 95 | 80, 300 k 152 | 129, 1 M 266 | 261, 1.5 M
-    // 340 | 360; TWO: the scan kernel everywhere (2 M: 345 | 443).  So up to two queries below gemm_min_nq (three, four) take the
-    // batched kernel in the band [small / 50, 0.8 small] = 20 k .. 800 k rows.
-    const bool mid_band = a.n_ranges == 0 && a.nq >= 3 && a.nq + 2 >= (uint32_t)ctx->tune.gemm_min_nq && small > 0 &&
-                          scanned >= small / 50 && scanned <= small / 5 * 4;
-    const bool batched = a.nq >= 8 ||
-                         (fast_k3 && a.nq >= (uint32_t)ctx->tune.gemm_min_nq && (a.n_ranges == 0 || scanned * a.nq >= small + small / 5)) ||
-                         (fast_k3 && mid_band) || image_scan;
-    if (batched && fast_k3 && whole) {
+    if (r.batched && r.rowreg && whole) {
         if (int rc_img = corpus_image_sync(corpus, a.nq, &a.image, &a.image_zero)) return rc_img;
     }
-    int rc = batched ? launch_gemm_topk(ctx, a) : launch_scan_topk(ctx, a);
-    if (rc == SMT_E_UNSUPPORTED && batched) rc = launch_scan_topk(ctx, a);
+    int rc = r.batched ? launch_gemm_topk(ctx, a) : launch_scan_topk(ctx, a);
+    if (rc == SMT_E_UNSUPPORTED && r.batched) rc = launch_scan_topk(ctx, a);
     return rc;
 }
 
-// Store::search_line_embeddings with a ZERO query vector (an empty query, or one made of unknown tokens only: model2vec pools it to
-// zeros).  qdrant's cosine_preprocess leaves a vector with |x|^2 < f32::EPSILON as it is, so the query scores 0 against EVERY point --
-// distance 1.0 for all of them, zero rows included -- where simsimd's rule for search_documents says (zero, zero) -> distance 0
-// (oracle: orc_search_line_embeddings against orc_cosine_*; src/workspace/store.rs:500-531).  The answer is a constant, so it is
-// written here instead of being computed: with a threshold nothing unless 0 > 1 - max_distance (f32), else the first top_k rows of
-// the subset in storage order (equal scores: earlier row first, as in the oracle), each at distance 1.0.
 // The large-k route (topk_large.hip) for a staged call: unfiltered batches of five or more queries sweep the corpus' fp16 operand image
 // when it has one (f16 x 2, half the bytes), like the batched re-answer; everything else reads the f32 rows.
 static int largek_route(smt_ctx *ctx, smt_corpus *corpus, ScanArgs &a)
 {
-    if (a.n_ranges == 0 && a.nq >= 5 && ctx->tune.gemm_image != 0 && corpus->rows <= (1ull << 28)) {
+    if (a.n_ranges == 0 && a.nq >= 5 && image_sweep_allowed(ctx, corpus)) {
         if (int rc_img = corpus_image_sync(corpus, a.nq, &a.image, &a.image_zero)) return rc_img;
     }
     return launch_topk_large(ctx, a);
@@ -418,9 +495,287 @@ void workspace_zero_query_hits(const smt_range *ranges, uint32_t n_ranges, uint6
     for (uint32_t i = 0; i < n_ranges && out.rows.size() < top_k; ++i) take(ranges[i].begin, ranges[i].end);
 }
 
-static int search_local_host_impl(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, double max_distance, int mode,
-                                  const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, std::vector<LocalHits> &out);
+// A host-form call after its prologue (search_local_host_impl): queries and ranges on the device, the outputs' place behind them.
+struct StagedCall {
+    smt_ctx *ctx;
+    smt_corpus *corpus;
+    const float *d_q;        // [nq x 256]
+    uint32_t nq;
+    const RangePlan &plan;
+    char *d_out;             // the stage behind the inputs: the result lists of a top-k call
+    HitRule rule;            // k = min(top_k, rows to scan); the workspace threshold; row_base
+    double max_distance;
+};
 
+static ScanArgs staged_scan_args(const StagedCall &c)
+{
+    ScanArgs a = scan_args(c.corpus, c.d_q, c.nq, (uint32_t)c.rule.k, c.rule.row_base);
+    c.plan.apply(a);
+    a.ws_threshold = c.rule.ws_thr ? 1 : 0;
+    a.ws_thr_score = c.rule.thr_score;  // store.rs:502-503
+    return a;
+}
+
+// The answer of a delivering launch (common.h Delivery): spin on the completion word (a small search is over in tens of
+// microseconds); past 200 us ask the runtime, which also reports a launch that failed.
+static int await_delivery(smt_ctx *ctx, const Delivery &dl)
+{
+    volatile unsigned long long *flag = dl.host_flag;
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned long long got = 0;
+    for (unsigned spins = 1; (got = *flag) == 0; ++spins) {
+#if defined(__x86_64__) || defined(__i386__)
+        __builtin_ia32_pause();   // (a polite spin: the sibling hyperthread keeps its issue slots)
+#endif
+        if ((spins & 63) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(200)) {
+            SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            got = *flag;
+            break;
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (got != dl.seq) {
+        (void)hipStreamSynchronize(ctx->stream);   // (whatever is left of the launch) -- and the block counter starts from zero again
+        (void)hipMemsetAsync(ctx->d_status + 4, 0, sizeof(unsigned long long), ctx->stream);
+        set_error("the select kernel did not deliver its answer (completion word %llu, expected %llu)", got, dl.seq);
+        return SMT_E_HIP;
+    }
+    ++ctx->deliveries;
+    return SMT_OK;
+}
+
+// ... and of any other launch: a D2H copy and a synchronise
+static int fetch_answer(smt_ctx *ctx, void *host, const void *dev, size_t bytes)
+{
+    SMT_HIP_CHECK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return SMT_OK;
+}
+
+// ---------------- top-k <= SCAN_MAX_K (optionally with the workspace score threshold): K2 or K3, then the uncertain queries again
+static int search_topk_small(const StagedCall &c, std::vector<LocalHits> &out)
+{
+    smt_ctx *ctx = c.ctx;
+    const uint32_t nq = c.nq, k_eff = (uint32_t)c.rule.k;
+    const size_t o_rows = (size_t)nq * k_eff * sizeof(uint64_t);
+    const size_t o_dist = (size_t)nq * k_eff * sizeof(double);
+    const size_t o_cnt = (size_t)2 * nq * sizeof(uint64_t);  // counts, then the "uncertain" flags
+    const size_t o_bytes = o_rows + o_dist + o_cnt;
+    uint64_t *d_ocnt = reinterpret_cast<uint64_t *>(c.d_out + o_rows + o_dist);
+    ScanArgs a = staged_scan_args(c);
+    a.out_rows = reinterpret_cast<uint64_t *>(c.d_out);
+    a.out_dist = reinterpret_cast<double *>(c.d_out + o_rows);
+    a.out_counts = d_ocnt;
+    a.out_uncertain = d_ocnt + nq;
+    int rc = ensure_pinned(ctx, 64 + o_bytes);
+    if (rc) return rc;
+    // the answers' place in the pinned buffer: behind a 64-byte line whose first word is the completion word of a delivered answer
+    char *h_ans = reinterpret_cast<char *>(ctx->h_pinned) + 64;
+    // A SMALL answer is delivered by the select kernel itself (common.h Delivery): its last block copies the device block
+    // [rows | distances | counts | flags] into the pinned buffer and stores this call's sequence number behind it; the host waits
+    // for that word -- no D2H copy command, no hipStreamSynchronize: ~10 us of every small call (profiles/r06_call_floor.json,
+    // profiles/r06_small_calls.json).  One select launch answers the whole call (<= 32 queries: below the batched kernel's pass size).
+    const bool direct = ctx->tune.direct_delivery != 0 && nq <= 32 && o_bytes <= 8192;
+    Delivery dl;
+    if (direct) {
+        dl.dev_out = reinterpret_cast<const unsigned long long *>(c.d_out);
+        dl.host_out = reinterpret_cast<unsigned long long *>(h_ans);
+        dl.n_words = (uint32_t)(o_bytes / 8);
+        dl.host_flag = reinterpret_cast<unsigned long long *>(ctx->h_pinned);
+        dl.seq = ++ctx->deliver_seq;
+        dl.done = ctx->d_status + 4;
+        *reinterpret_cast<volatile unsigned long long *>(dl.host_flag) = 0;
+        a.deliver = &dl;
+    }
+    if ((rc = topk_dispatch(ctx, c.corpus, a))) return rc;
+    if ((rc = direct ? await_delivery(ctx, dl) : fetch_answer(ctx, h_ans, c.d_out, o_bytes))) return rc;
+    const uint64_t *h_rows = reinterpret_cast<const uint64_t *>(h_ans);
+    const double *h_dist = reinterpret_cast<const double *>(h_ans + o_rows);
+    const uint64_t *h_cnt = reinterpret_cast<const uint64_t *>(h_ans + o_rows + o_dist);
+    std::vector<uint32_t> redo;
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint64_t n = h_cnt[q];
+        out[q].rows.assign(h_rows + (size_t)q * k_eff, h_rows + (size_t)q * k_eff + n);
+        out[q].dist.assign(h_dist + (size_t)q * k_eff, h_dist + (size_t)q * k_eff + n);
+        if (h_cnt[nq + q]) redo.push_back(q);  // (h_pinned is reused by the fallback: copy everything out first)
+    }
+    // queries whose f32 nomination could not be proven sufficient (a cluster of near-ties around the k-th
+    // place that is wider than the guard band): answer them exhaustively -- several of them with ONE batched
+    // threshold pass over the shard (batched_fallback), the rest (and whatever overflows there) one K4 scan each
+    auto bound_of = [&](uint32_t q) {
+        return out[q].rows.size() == k_eff ? out[q].dist.back() : 1.0 - (double)c.rule.thr_score;
+    };
+    if (c.plan.nr == 0 && redo.size() >= 2 && ctx->tune.gemm_bf16x3 && ctx->tune.gemm_rowreg &&
+        c.corpus->rows >= (uint64_t)ctx->tune.fallback_batch_min_rows) {
+        std::vector<double> bounds;
+        for (uint32_t q : redo) bounds.push_back(bound_of(q));
+        std::vector<uint32_t> left;
+        if ((rc = batched_fallback(ctx, c.corpus, c.d_q, redo, bounds, c.rule, out, left))) return rc;
+        redo.swap(left);
+    }
+    for (uint32_t q : redo)
+        if ((rc = exact_fallback(ctx, c.corpus, c.d_q + (size_t)q * SMT_DIM, c.plan, bound_of(q), c.rule, out[q]))) return rc;
+    return SMT_OK;
+}
+
+// 57 <= k <= 1024: the sampled-threshold route (topk_large.hip) answers every query of the call in three launches; proved[q] = 1
+// where it could prove its answer (not: ties across tau, an overflowed buffer).  Lists [rows | distances | verdicts] in the stage
+// behind the inputs, home through the pinned buffer.
+static int largek_sampled(const StagedCall &c, std::vector<char> &proved, std::vector<LocalHits> &out)
+{
+    smt_ctx *ctx = c.ctx;
+    const uint32_t nq = c.nq, k_eff = (uint32_t)c.rule.k;
+    const size_t kw = (size_t)nq * k_eff, o_words = 2 * kw + nq;
+    uint64_t *d_out = reinterpret_cast<uint64_t *>(c.d_out);
+    ScanArgs a = staged_scan_args(c);
+    a.out_rows = d_out;
+    a.out_dist = reinterpret_cast<double *>(d_out + kw);
+    a.out_uncertain = d_out + 2 * kw;
+    int rc = largek_route(ctx, c.corpus, a);
+    if (rc) return rc;
+    if ((rc = ensure_pinned(ctx, o_words * sizeof(uint64_t)))) return rc;
+    const uint64_t *h = reinterpret_cast<const uint64_t *>(ctx->h_pinned);
+    if ((rc = fetch_answer(ctx, ctx->h_pinned, d_out, o_words * sizeof(uint64_t)))) return rc;
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (h[2 * kw + q] != SMT_STATUS_PROVED) continue;
+        proved[q] = 1;
+        const uint64_t *r = h + (size_t)q * k_eff;
+        const double *d = reinterpret_cast<const double *>(h + kw) + (size_t)q * k_eff;
+        uint32_t n = 0;
+        while (n < k_eff && r[n] != UINT64_MAX) ++n;
+        out[q].rows.assign(r, r + n);
+        out[q].dist.assign(d, d + n);
+    }
+    return SMT_OK;
+}
+
+// ONE query by the all-keys path (largek.hip): all keys + sort + exact rescoring of k + guard candidates, then the exactness
+// certificate over them and the K4 re-answer where it fails.
+static int largek_all_keys(const StagedCall &c, uint32_t q, LocalHits &out)
+{
+    const RangePlan &plan = c.plan;
+    const uint64_t k_eff = c.rule.k;
+    const uint64_t guard = std::max<uint64_t>(64, k_eff / 16);
+    const uint64_t n_cand = std::min<uint64_t>(plan.n_virtual, k_eff + guard);
+    const float *query_dev = c.d_q + (size_t)q * SMT_DIM;
+    std::vector<uint32_t> c_rows;
+    std::vector<double> c_dist;
+    float next_d32 = 0.f;
+    int rc = launch_largek_candidates(c.ctx, c.corpus->d_rows, query_dev, plan.d_r, plan.d_p, plan.nr, plan.n_virtual, n_cand, c_rows, c_dist,
+                                      &next_d32);
+    if (rc) return rc;
+    order_hits(c_rows.data(), c_dist.data(), c_rows.size(), std::numeric_limits<double>::infinity(), false, /*sorted=*/false, c.rule, out);
+    // exactness certificate (SelectArgs::f32_err): rows outside the candidates have exact distance >= floor_out
+    const uint64_t n = out.rows.size();
+    const double floor_out = (double)next_d32 - F32_ERR_SCAN;
+    const bool certain = n == k_eff ? floor_out > out.dist[n - 1]
+                                    : (c.rule.ws_thr ? !ws_score_passes(floor_out, c.rule.thr_score) : next_d32 == __builtin_inff());
+    if (certain) return SMT_OK;
+    const double bound = n == k_eff ? out.dist[n - 1] : 1.0 - (double)c.rule.thr_score;
+    return exact_fallback(c.ctx, c.corpus, query_dev, plan, bound, c.rule, out);
+}
+
+// ---------------- top-k > SCAN_MAX_K (also k in 57..64, where the f32 scan's candidate lists have no room left for the guard band)
+static int search_topk_large(const StagedCall &c, std::vector<LocalHits> &out)
+{
+    std::vector<char> proved(c.nq, 0);
+    if (c.ctx->tune.largek_sampled && c.rule.k <= LARGEK_MAX_K)
+        if (int rc = largek_sampled(c, proved, out)) return rc;
+    for (uint32_t q = 0; q < c.nq; ++q)   // what the sampled route did not prove (or take) is answered exactly as before it existed
+        if (!proved[q])
+            if (int rc = largek_all_keys(c, q, out[q])) return rc;
+    return SMT_OK;
+}
+
+// ---------------- all rows with distance < max_distance (mod.rs:88-89,115-116)
+static int search_all_under(const StagedCall &c, std::vector<LocalHits> &out)
+{
+    smt_ctx *ctx = c.ctx;
+    // several queries on a large unfiltered shard: ONE sweep of the batched kernel collects every query's hits (up to a
+    // candidate buffer, 2048 rows, each); a query with more hits than that takes the streaming K4 scan below
+    std::vector<uint32_t> todo(c.nq);
+    for (uint32_t q = 0; q < c.nq; ++q) todo[q] = q;
+    if (c.plan.nr == 0 && c.nq >= 2 && ctx->tune.gemm_bf16x3 && ctx->tune.gemm_rowreg && c.max_distance <= 2.5 &&
+        c.corpus->rows >= (uint64_t)ctx->tune.fallback_batch_min_rows) {
+        std::vector<double> bounds(c.nq, c.max_distance);
+        std::vector<uint32_t> left;
+        const HitRule every{~0ull, false, 0.f, c.rule.row_base};
+        if (int rc = batched_fallback(ctx, c.corpus, c.d_q, todo, bounds, every, out, left, /*strict=*/true)) return rc;
+        todo.swap(left);
+    }
+    for (uint32_t q : todo) {
+        const ThresholdQuery t = threshold_query(c.corpus, c.d_q + (size_t)q * SMT_DIM, c.plan, c.max_distance);
+        const uint32_t *h_rows = nullptr;
+        const double *h_dist = nullptr;
+        uint64_t n_ok = 0;
+        if (int rc = run_threshold_query(ctx, t, &h_rows, &h_dist, &n_ok)) return rc;
+        out[q].rows.resize(n_ok);
+        for (uint64_t i = 0; i < n_ok; ++i) out[q].rows[i] = c.rule.row_base + h_rows[i];
+        out[q].dist.assign(h_dist, h_dist + n_ok);
+    }
+    return SMT_OK;
+}
+
+// The search proper: argument checks, the range plan, ONE upload of everything the call reads, then one of the three bodies above.
+static int search_local_host_impl(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, double max_distance, int mode,
+                                  const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, std::vector<LocalHits> &out)
+{
+    SMT_REQUIRE(corpus != nullptr, "corpus");
+    SMT_REQUIRE(mode == SMT_MODE_DOCUMENTS || mode == SMT_MODE_WORKSPACE, "mode");
+    SMT_REQUIRE(nq == 0 || queries, "null argument");
+    SMT_REQUIRE(n_ranges == 0 || ranges != nullptr, "ranges");
+    smt_ctx *ctx = corpus->ctx;
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    out.assign(nq, LocalHits());
+    if (nq == 0) return SMT_OK;
+    if ((rc = require_queries_domain_host(queries, nq, "search"))) return rc;   // (domain.hip: finite, ordinary magnitudes)
+
+    const bool has_thr = !std::isnan(max_distance);
+    const bool all_under_threshold = (mode == SMT_MODE_DOCUMENTS) && has_thr;
+
+    // drop empty ranges; total rows to scan.  A list searched before has its device copy (and tables) kept on the corpus.
+    RangePlan plan;
+    plan.n_virtual = corpus->rows;
+    if (n_ranges && (rc = range_plan_find(corpus, ranges, n_ranges, plan))) return rc;
+    if (plan.n_virtual == 0) return SMT_OK;
+    if (!all_under_threshold && top_k == 0) return SMT_OK;  // take(0) / store.rs:489-491
+    if ((rc = range_plan_finish(corpus, plan))) return rc;
+
+    // ---- device staging: one persistent buffer per context, [queries | ranges | 3 prefixes | result lists] (no per-call hipMalloc/hipFree)
+    const size_t q_bytes = (size_t)nq * SMT_DIM * sizeof(float);
+    const size_t up_bytes = q_bytes + plan.upload_bytes();
+    const size_t in_bytes = (q_bytes + plan.table_bytes() + 255) & ~(size_t)255;
+    // (the result lists of the large-k route, 57 <= k <= 1024, are staged here too)
+    const uint64_t k_eff = std::min<uint64_t>(top_k, plan.n_virtual);
+    const bool largek_lists = ctx->tune.largek_sampled && k_eff > SCAN_MAX_K && k_eff <= LARGEK_MAX_K;
+    const uint32_t k_stage = all_under_threshold ? 0u : (uint32_t)std::min<uint64_t>(k_eff, largek_lists ? LARGEK_MAX_K : 64);
+    const size_t out_bytes_stage = (size_t)nq * k_stage * 16 + (size_t)2 * nq * sizeof(uint64_t);
+    if ((rc = ensure_stage(ctx, in_bytes + out_bytes_stage + 64))) return rc;
+    char *stage = reinterpret_cast<char *>(ctx->d_stage);
+    // queries, ranges and the three prefixes are assembled in ONE pinned buffer (laid out like the device stage) and go up in one
+    // copy: four pageable hipMemcpyAsync calls -- each staged by the runtime before it returns -- were ~50 us of a 0.6 ms call
+    if ((rc = ensure_pinned_in(ctx, up_bytes))) return rc;
+    char *pin = reinterpret_cast<char *>(ctx->h_pinned_in);
+    memcpy(pin, queries, q_bytes);
+    plan.write(pin + q_bytes);
+    SMT_HIP_CHECK(hipMemcpyAsync(stage, pin, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    plan.bind(stage + q_bytes);   // (a kept set: only the queries went up)
+
+    const HitRule rule{k_eff, mode == SMT_MODE_WORKSPACE && has_thr, 1.0f - (float)max_distance /* store.rs:502-503 */, row_base};
+    const StagedCall call{ctx, corpus, reinterpret_cast<const float *>(stage), nq, plan, stage + in_bytes, rule, max_distance};
+    if (all_under_threshold) return search_all_under(call, out);
+    return k_eff > SCAN_MAX_K ? search_topk_large(call, out) : search_topk_small(call, out);
+}
+
+// The body of smt_search with per-query result vectors instead of caller arrays: group.cpp runs it once per
+// local shard (threshold mode / top_k > 64, whose result sizes are not known up front) and exchanges the lists.
+// Store::search_line_embeddings with a ZERO query vector (an empty query, or one made of unknown tokens only: model2vec pools it to
+// zeros).  qdrant's cosine_preprocess leaves a vector with |x|^2 < f32::EPSILON as it is, so the query scores 0 against EVERY point --
+// distance 1.0 for all of them, zero rows included -- where simsimd's rule for search_documents says (zero, zero) -> distance 0
+// (oracle: orc_search_line_embeddings against orc_cosine_*; src/workspace/store.rs:500-531).  The answer is a constant, so it is
+// written here instead of being computed: with a threshold nothing unless 0 > 1 - max_distance (f32), else the first top_k rows of
+// the subset in storage order (equal scores: earlier row first, as in the oracle), each at distance 1.0.
 int search_local_host(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, double max_distance, int mode,
                       const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, std::vector<LocalHits> &out)
 {
@@ -453,318 +808,6 @@ int search_local_host(smt_corpus *corpus, const float *queries, uint32_t nq, uin
     for (uint32_t q = 0; q < nq; ++q)
         if (query_is_zero(queries + (size_t)q * SMT_DIM))
             workspace_zero_query_hits(ranges, n_ranges, corpus->rows, top_k, !std::isnan(max_distance), max_distance, row_base, out[q]);
-    return SMT_OK;
-}
-
-static int search_local_host_impl(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, double max_distance, int mode,
-                                  const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, std::vector<LocalHits> &out)
-{
-    SMT_REQUIRE(corpus != nullptr, "corpus");
-    SMT_REQUIRE(mode == SMT_MODE_DOCUMENTS || mode == SMT_MODE_WORKSPACE, "mode");
-    SMT_REQUIRE(nq == 0 || queries, "null argument");
-    SMT_REQUIRE(n_ranges == 0 || ranges != nullptr, "ranges");
-    smt_ctx *ctx = corpus->ctx;
-    int rc = bind_device(ctx);
-    if (rc) return rc;
-    out.assign(nq, LocalHits());
-    if (nq == 0) return SMT_OK;
-    if ((rc = require_queries_domain_host(queries, nq, "search"))) return rc;   // (domain.hip: finite, ordinary magnitudes)
-
-    const bool has_thr = !std::isnan(max_distance);
-    const bool all_under_threshold = (mode == SMT_MODE_DOCUMENTS) && has_thr;
-
-    // drop empty ranges; total rows to scan.  A list searched before has its device copy (and tables) kept on the corpus.
-    std::vector<smt_range> rr;
-    uint64_t n_virtual = corpus->rows;
-    RangeSet *rset = nullptr;
-    bool rset_build = false;
-    uint64_t rh1 = 0, rh2 = 0;
-    if (n_ranges) {
-        uint64_t total = 0;
-        if ((rc = range_set_find(corpus, ranges, n_ranges, &total, &rset, &rset_build, &rh1, &rh2))) return rc;
-        n_virtual = total;
-        if (!rset)
-            for (uint32_t i = 0; i < n_ranges; ++i) if (ranges[i].end > ranges[i].begin) rr.push_back(ranges[i]);
-    }
-    if (n_virtual == 0) return SMT_OK;
-    if (!all_under_threshold && top_k == 0) return SMT_OK;  // take(0) / store.rs:489-491
-    std::vector<uint64_t> prefixes;
-    if (!rset && !rr.empty()) {
-        range_prefixes(rr, prefixes);
-        if (rset_build && (rc = range_set_build(corpus, ranges, n_ranges, rh1, rh2, rr, prefixes, n_virtual, &rset))) return rc;
-    }
-
-    // ---- device staging: queries, ranges(+prefix)
-    const uint32_t nr = rset ? rset->nr : (uint32_t)rr.size();
-    const size_t q_bytes = (size_t)nq * SMT_DIM * sizeof(float);
-    const size_t r_bytes = (size_t)nr * sizeof(smt_range);
-    const size_t p_bytes = (size_t)(nr + 1) * sizeof(uint64_t);
-    // one persistent staging buffer per context: [queries | ranges | 3 prefixes | result lists] (no per-call hipMalloc/hipFree)
-    const size_t in_bytes = (q_bytes + r_bytes + 3 * p_bytes + 255) & ~(size_t)255;
-    // (the result lists of the large-k route, 57 <= k <= 1024, are staged here too)
-    const uint64_t k_lists = std::min<uint64_t>(top_k, n_virtual);
-    const bool largek_lists = ctx->tune.largek_sampled && k_lists > SCAN_MAX_K && k_lists <= LARGEK_MAX_K;
-    const uint32_t k_stage = all_under_threshold ? 0u : (uint32_t)std::min<uint64_t>(k_lists, largek_lists ? LARGEK_MAX_K : 64);
-    const size_t out_bytes_stage = (size_t)nq * k_stage * 16 + (size_t)2 * nq * sizeof(uint64_t);
-    if ((rc = ensure_stage(ctx, in_bytes + out_bytes_stage + 64))) return rc;
-    char *stage = reinterpret_cast<char *>(ctx->d_stage);
-    float *d_q = reinterpret_cast<float *>(stage);
-    smt_range *d_r = reinterpret_cast<smt_range *>(stage + q_bytes);
-    uint64_t *d_p = reinterpret_cast<uint64_t *>(stage + q_bytes + r_bytes);
-    uint64_t *d_cp = d_p + (nr + 1), *d_tp = d_cp + (nr + 1);
-    // queries, ranges and the three prefixes are assembled in ONE pinned buffer (laid out like the device stage) and go up in one
-    // copy: four pageable hipMemcpyAsync calls -- each staged by the runtime before it returns -- were ~50 us of a 0.6 ms call
-    const size_t up_bytes = q_bytes + (nr && !rset ? r_bytes + 3 * p_bytes : 0);
-    if ((rc = ensure_pinned_in(ctx, up_bytes))) return rc;
-    {
-        char *pin = reinterpret_cast<char *>(ctx->h_pinned_in);
-        memcpy(pin, queries, q_bytes);
-        if (nr && !rset) {
-            memcpy(pin + q_bytes, rr.data(), r_bytes);
-            memcpy(pin + q_bytes + r_bytes, prefixes.data(), 3 * p_bytes);
-        }
-        SMT_HIP_CHECK(hipMemcpyAsync(stage, pin, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (rset) { d_r = rset->d_r; d_p = rset->d_p; d_cp = rset->d_cp; d_tp = rset->d_tp; }   // (only the queries went up)
-    const uint64_t n_chunks = rset ? rset->n_chunks : nr ? prefixes[2 * (nr + 1) - 1] : 0;
-    const uint64_t n_vtiles = rset ? rset->n_vtiles : nr ? prefixes[3 * (nr + 1) - 1] : 0;
-
-    if (!all_under_threshold) {
-        // ---------------- top-k (optionally with the workspace score threshold)
-        const uint32_t k_eff = (uint32_t)std::min<uint64_t>(top_k, n_virtual);
-        if (k_eff > SCAN_MAX_K) {
-            // large-k request (also k in 57..64, where the f32 scan's candidate lists have no room left for the
-            // guard band): all keys + sort + exact rescoring of k + guard candidates
-            const uint64_t guard = std::max<uint64_t>(64, k_eff / 16);
-            const uint64_t n_cand = std::min<uint64_t>(n_virtual, (uint64_t)k_eff + guard);
-            const bool ws_thr = (mode == SMT_MODE_WORKSPACE && has_thr);
-            const float thr_score = 1.0f - (float)max_distance;
-            std::vector<char> proved(nq, 0);
-            if (ctx->tune.largek_sampled && k_eff <= LARGEK_MAX_K) {
-                // 57 <= k <= 1024: the sampled-threshold route (topk_large.hip) answers every query of the call in three launches;
-                // a query it cannot prove (ties across tau, an overflowed buffer) is re-answered below exactly as before
-                // lists [rows | distances | verdicts] in the stage behind the inputs, home through the pinned buffer
-                const size_t kw = (size_t)nq * k_eff, o_words = 2 * kw + nq;
-                uint64_t *d_out = reinterpret_cast<uint64_t *>(stage + in_bytes);
-                ScanArgs a{};
-                a.corpus = corpus->d_rows;
-                a.rows = corpus->rows;
-                a.queries = d_q;
-                a.nq = nq;
-                a.k_out = k_eff;
-                a.ranges = nr ? d_r : nullptr;
-                a.range_prefix = nr ? d_p : nullptr;
-                a.range_chunk_prefix = nr ? d_cp : nullptr;
-                a.n_chunks = n_chunks;
-                a.n_ranges = nr;
-                a.n_virtual = n_virtual;
-                a.ws_threshold = ws_thr ? 1 : 0;
-                a.ws_thr_score = thr_score;
-                a.row_base = row_base;
-                a.out_rows = d_out;
-                a.out_dist = reinterpret_cast<double *>(d_out + kw);
-                a.out_uncertain = d_out + 2 * kw;
-                a.range_set = rset;
-                if ((rc = largek_route(ctx, corpus, a))) return rc;
-                if ((rc = ensure_pinned(ctx, o_words * sizeof(uint64_t)))) return rc;
-                const uint64_t *h = reinterpret_cast<const uint64_t *>(ctx->h_pinned);
-                SMT_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned, d_out, o_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-                SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                for (uint32_t q = 0; q < nq; ++q) {
-                    if (h[2 * kw + q] != SMT_STATUS_PROVED) continue;
-                    proved[q] = 1;
-                    const uint64_t *r = h + (size_t)q * k_eff;
-                    const double *d = reinterpret_cast<const double *>(h + kw) + (size_t)q * k_eff;
-                    uint32_t n = 0;
-                    while (n < k_eff && r[n] != UINT64_MAX) ++n;
-                    out[q].rows.assign(r, r + n);
-                    out[q].dist.assign(d, d + n);
-                }
-            }
-            for (uint32_t q = 0; q < nq; ++q) {
-                if (proved[q]) continue;
-                std::vector<uint32_t> c_rows;
-                std::vector<double> c_dist;
-                float next_d32 = 0.f;
-                rc = launch_largek_candidates(ctx, corpus->d_rows, d_q + (size_t)q * SMT_DIM, nr ? d_r : nullptr,
-                                              nr ? d_p : nullptr, nr, n_virtual, n_cand, c_rows, c_dist, &next_d32);
-                if (rc) return rc;
-                std::vector<uint64_t> order;
-                for (uint64_t i = 0; i < c_rows.size(); ++i) {
-                    if (c_dist[i] != c_dist[i]) continue;                                   // NaN rows never match
-                    if (ws_thr && !((1.0 - c_dist[i]) > (double)thr_score)) continue;      // store.rs:502-503
-                    order.push_back(i);
-                }
-                std::sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) {
-                    if (c_dist[x] != c_dist[y]) return c_dist[x] < c_dist[y];
-                    return c_rows[x] < c_rows[y];
-                });
-                const uint64_t n = std::min<uint64_t>(order.size(), k_eff);
-                out[q].rows.resize(n);
-                out[q].dist.resize(n);
-                for (uint64_t i = 0; i < n; ++i) {
-                    out[q].rows[i] = row_base + c_rows[order[i]];
-                    out[q].dist[i] = c_dist[order[i]];
-                }
-                // exactness certificate (SelectArgs::f32_err): rows outside the candidates have exact distance >= floor_out
-                const double floor_out = (double)next_d32 - F32_ERR_SCAN;
-                const bool certain = n == k_eff ? floor_out > out[q].dist[n - 1]
-                                                : (ws_thr ? !((1.0 - floor_out) > (double)thr_score) : next_d32 == __builtin_inff());
-                if (!certain) {
-                    const double bound = n == k_eff ? out[q].dist[n - 1] : 1.0 - (double)thr_score;
-                    rc = exact_fallback(ctx, corpus, d_q + (size_t)q * SMT_DIM, nr ? d_r : nullptr, nr ? d_cp : nullptr, nr,
-                                        n_virtual, n_chunks, bound, k_eff, ws_thr, thr_score, row_base, out[q]);
-                    if (rc) return rc;
-                }
-            }
-            return SMT_OK;
-        }
-        const size_t o_rows = (size_t)nq * k_eff * sizeof(uint64_t);
-        const size_t o_dist = (size_t)nq * k_eff * sizeof(double);
-        const size_t o_cnt = (size_t)2 * nq * sizeof(uint64_t);  // counts, then the "uncertain" flags
-        char *outs = stage + in_bytes;
-        uint64_t *d_orow = reinterpret_cast<uint64_t *>(outs);
-        double *d_odist = reinterpret_cast<double *>(outs + o_rows);
-        uint64_t *d_ocnt = reinterpret_cast<uint64_t *>(outs + o_rows + o_dist);
-
-        ScanArgs a;
-        a.corpus = corpus->d_rows;
-        a.rows = corpus->rows;
-        a.queries = d_q;
-        a.nq = nq;
-        a.k_out = k_eff;
-        a.ranges = nr ? d_r : nullptr;
-        a.range_prefix = nr ? d_p : nullptr;
-        a.range_chunk_prefix = nr ? d_cp : nullptr;
-        a.n_chunks = n_chunks;
-        a.range_tile_prefix = nr ? d_tp : nullptr;
-        a.n_vtiles = n_vtiles;
-        a.n_ranges = nr;
-        a.n_virtual = n_virtual;
-        a.ws_threshold = (mode == SMT_MODE_WORKSPACE && has_thr) ? 1 : 0;
-        a.ws_thr_score = 1.0f - (float)max_distance;  // store.rs:502-503
-        a.row_base = row_base;
-        a.out_rows = d_orow;
-        a.out_dist = d_odist;
-        a.out_counts = d_ocnt;
-        a.out_uncertain = d_ocnt + nq;
-        a.range_set = rset;
-        if ((rc = ensure_pinned(ctx, 64 + o_rows + o_dist + o_cnt))) return rc;
-        // the answers' place in the pinned buffer: behind a 64-byte line whose first word is the completion word of a delivered answer
-        char *h_ans = reinterpret_cast<char *>(ctx->h_pinned) + 64;
-        // A SMALL answer is delivered by the select kernel itself (common.h Delivery): its last block copies the device block
-        // [rows | distances | counts | flags] into the pinned buffer and stores this call's sequence number behind it; the host waits
-        // for that word -- no D2H copy command, no hipStreamSynchronize: ~10 us of every small call (profiles/r06_call_floor.json,
-        // profiles/r06_small_calls.json).  One select launch answers the whole call (<= 32 queries: below the batched kernel's pass size).
-        const bool direct = ctx->tune.direct_delivery != 0 && nq <= 32 && o_rows + o_dist + o_cnt <= 8192;
-        Delivery dl;
-        volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(ctx->h_pinned);
-        if (direct) {
-            dl.dev_out = reinterpret_cast<const unsigned long long *>(outs);
-            dl.host_out = reinterpret_cast<unsigned long long *>(h_ans);
-            dl.n_words = (uint32_t)((o_rows + o_dist + o_cnt) / 8);
-            dl.host_flag = const_cast<unsigned long long *>(flag);
-            dl.seq = ++ctx->deliver_seq;
-            dl.done = ctx->d_status + 4;
-            *flag = 0;
-            a.deliver = &dl;
-        }
-        // K2 or K3: topk_dispatch above
-        rc = topk_dispatch(ctx, corpus, a);
-        if (rc) return rc;
-        if (direct) {
-            // spin on the completion word (a small search is over in tens of microseconds); past 200 us ask the runtime, which also
-            // reports a launch that failed
-            const auto t0 = std::chrono::steady_clock::now();
-            unsigned long long got = 0;
-            for (unsigned spins = 1; (got = *flag) == 0; ++spins) {
-#if defined(__x86_64__) || defined(__i386__)
-                __builtin_ia32_pause();   // (a polite spin: the sibling hyperthread keeps its issue slots)
-#endif
-                if ((spins & 63) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(200)) {
-                    SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                    got = *flag;
-                    break;
-                }
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-            if (got != dl.seq) {
-                (void)hipStreamSynchronize(ctx->stream);   // (whatever is left of the launch) -- and the block counter starts from zero again
-                (void)hipMemsetAsync(ctx->d_status + 4, 0, sizeof(unsigned long long), ctx->stream);
-                set_error("the select kernel did not deliver its answer (completion word %llu, expected %llu)", got, dl.seq);
-                return SMT_E_HIP;
-            }
-            ++ctx->deliveries;
-        } else {
-            SMT_HIP_CHECK(hipMemcpyAsync(h_ans, outs, o_rows + o_dist + o_cnt, hipMemcpyDeviceToHost, ctx->stream));
-            SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        }
-        const uint64_t *h_rows = reinterpret_cast<const uint64_t *>(h_ans);
-        const double *h_dist = reinterpret_cast<const double *>(h_ans + o_rows);
-        const uint64_t *h_cnt = reinterpret_cast<const uint64_t *>(h_ans + o_rows + o_dist);
-        std::vector<uint32_t> redo;
-        for (uint32_t q = 0; q < nq; ++q) {
-            const uint64_t n = h_cnt[q];
-            out[q].rows.assign(h_rows + (size_t)q * k_eff, h_rows + (size_t)q * k_eff + n);
-            out[q].dist.assign(h_dist + (size_t)q * k_eff, h_dist + (size_t)q * k_eff + n);
-            if (h_cnt[nq + q]) redo.push_back(q);  // (h_pinned is reused by the fallback: copy everything out first)
-        }
-        // queries whose f32 nomination could not be proven sufficient (a cluster of near-ties around the k-th
-        // place that is wider than the guard band): answer them exhaustively -- several of them with ONE batched
-        // threshold pass over the shard (batched_fallback), the rest (and whatever overflows there) one K4 scan each
-        const bool ws_thr = a.ws_threshold != 0;
-        auto bound_of = [&](uint32_t q) {
-            return out[q].rows.size() == k_eff ? out[q].dist.back() : 1.0 - (double)a.ws_thr_score;
-        };
-        if (nr == 0 && redo.size() >= 2 && ctx->tune.gemm_bf16x3 && ctx->tune.gemm_rowreg &&
-            corpus->rows >= (uint64_t)ctx->tune.fallback_batch_min_rows) {
-            std::vector<double> bounds;
-            for (uint32_t q : redo) bounds.push_back(bound_of(q));
-            std::vector<uint32_t> left;
-            rc = batched_fallback(ctx, corpus, d_q, redo, bounds, k_eff, ws_thr, a.ws_thr_score, row_base, out, left);
-            if (rc) return rc;
-            redo.swap(left);
-        }
-        for (uint32_t q : redo) {
-            rc = exact_fallback(ctx, corpus, d_q + (size_t)q * SMT_DIM, nr ? d_r : nullptr, nr ? d_cp : nullptr, nr, n_virtual,
-                                n_chunks, bound_of(q), k_eff, ws_thr, a.ws_thr_score, row_base, out[q]);
-            if (rc) return rc;
-        }
-        return SMT_OK;
-    }
-
-    // ---------------- all rows with distance < max_distance (mod.rs:88-89,115-116)
-    // several queries on a large unfiltered shard: ONE sweep of the batched kernel collects every query's hits (up to a
-    // candidate buffer, 2048 rows, each); a query with more hits than that takes the streaming K4 scan below
-    std::vector<uint32_t> todo(nq);
-    for (uint32_t q = 0; q < nq; ++q) todo[q] = q;
-    if (nr == 0 && nq >= 2 && ctx->tune.gemm_bf16x3 && ctx->tune.gemm_rowreg && max_distance <= 2.5 &&
-        corpus->rows >= (uint64_t)ctx->tune.fallback_batch_min_rows) {
-        std::vector<double> bounds(nq, max_distance);
-        std::vector<uint32_t> left;
-        rc = batched_fallback(ctx, corpus, d_q, todo, bounds, ~0ull, false, 0.f, row_base, out, left, /*strict=*/true);
-        if (rc) return rc;
-        todo.swap(left);
-    }
-    for (uint32_t q : todo) {
-        ThresholdQuery t;
-        t.corpus = corpus->d_rows;
-        t.rows = corpus->rows;
-        t.query = d_q + (size_t)q * SMT_DIM;
-        t.ranges = nr ? d_r : nullptr;
-        t.range_chunk_prefix = nr ? d_cp : nullptr;
-        t.n_chunks = n_chunks;
-        t.n_ranges = nr;
-        t.n_virtual = n_virtual;
-        t.max_distance = max_distance;
-        const uint32_t *h_rows = nullptr;
-        const double *h_dist = nullptr;
-        uint64_t n_ok = 0;
-        if ((rc = run_threshold_query(ctx, t, &h_rows, &h_dist, &n_ok))) return rc;
-        out[q].rows.resize(n_ok);
-        for (uint64_t i = 0; i < n_ok; ++i) out[q].rows[i] = row_base + h_rows[i];
-        out[q].dist.assign(h_dist, h_dist + n_ok);
-    }
     return SMT_OK;
 }
 
@@ -801,20 +844,11 @@ int search_topk_packed_local(smt_corpus *corpus, const float *queries_dev, uint3
     SMT_REQUIRE(k_pad >= 1 && k_pad <= (ctx->tune.largek_sampled ? LARGEK_MAX_K : SCAN_MAX_K),
                 ctx->tune.largek_sampled ? "top_k of the device exchange path must be in [1, 1024]"
                                          : "top_k of the device exchange path must be in [1, 56] (largek_sampled = 0)");
-    uint64_t n_virtual = corpus->rows;
-    std::vector<smt_range> rr;
-    RangeSet *rset = nullptr;
-    bool rset_build = false;
-    uint64_t rh1 = 0, rh2 = 0;
-    if (filtered) {
-        uint64_t total = 0;
-        int rcv = range_set_find(corpus, ranges_local, n_ranges, &total, &rset, &rset_build, &rh1, &rh2);
-        if (rcv) return rcv;
-        if (!rset)
-            for (uint32_t i = 0; i < n_ranges; ++i) if (ranges_local[i].end > ranges_local[i].begin) rr.push_back(ranges_local[i]);
-        n_virtual = total;
-    }
-    const uint32_t k_eff = (uint32_t)std::min<uint64_t>(k_pad, n_virtual);
+    RangePlan plan;
+    plan.n_virtual = corpus->rows;
+    if (filtered)
+        if (int rcv = range_plan_find(corpus, ranges_local, n_ranges, plan)) return rcv;
+    const uint32_t k_eff = (uint32_t)std::min<uint64_t>(k_pad, plan.n_virtual);
     const bool async = allow_async && ctx->tune.async_select && nq == 1 && !filtered && k_eff == k_pad && k_pad <= SCAN_MAX_K;
     int rc = bind_device(ctx, !async);
     if (rc) return rc;
@@ -825,58 +859,25 @@ int search_topk_packed_local(smt_corpus *corpus, const float *queries_dev, uint3
             return SMT_OK;
         }
     }
-    std::vector<uint64_t> prefixes;
-    if (!rset && !rr.empty()) {
-        range_prefixes(rr, prefixes);
-        if (rset_build && (rc = range_set_build(corpus, ranges_local, n_ranges, rh1, rh2, rr, prefixes, n_virtual, &rset))) return rc;
-    }
-    const uint32_t nr = rset ? rset->nr : (uint32_t)rr.size();
-    smt_range *d_r = nullptr;
-    uint64_t *d_p = nullptr, *d_cp = nullptr, *d_tp = nullptr;
-    uint64_t n_chunks = 0, n_vtiles = 0;
-    if (rset) {
-        d_r = rset->d_r; d_p = rset->d_p; d_cp = rset->d_cp; d_tp = rset->d_tp;
-        n_chunks = rset->n_chunks; n_vtiles = rset->n_vtiles;
-    } else if (nr) {
-        const size_t r_bytes = (size_t)nr * sizeof(smt_range), p_bytes = (size_t)(nr + 1) * sizeof(uint64_t);
-        if ((rc = ensure_stage(ctx, r_bytes + 3 * p_bytes + 64))) return rc;
-        char *stage = reinterpret_cast<char *>(ctx->d_stage);
-        d_r = reinterpret_cast<smt_range *>(stage);
-        d_p = reinterpret_cast<uint64_t *>(stage + r_bytes);
-        d_cp = d_p + (nr + 1);
-        d_tp = d_cp + (nr + 1);
-        n_chunks = prefixes[2 * (nr + 1) - 1];
-        n_vtiles = prefixes[3 * (nr + 1) - 1];
-        SMT_HIP_CHECK(hipMemcpyAsync(d_r, rr.data(), r_bytes, hipMemcpyHostToDevice, ctx->stream));
-        SMT_HIP_CHECK(hipMemcpyAsync(d_p, prefixes.data(), 3 * p_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = range_plan_finish(corpus, plan))) return rc;
+    if (plan.upload_bytes() && (rc = ensure_stage(ctx, plan.upload_bytes() + 64))) return rc;
+    plan.bind(reinterpret_cast<char *>(ctx->d_stage));
+    if (plan.upload_bytes()) {
+        SMT_HIP_CHECK(hipMemcpyAsync(const_cast<smt_range *>(plan.d_r), plan.rr.data(), plan.r_bytes(), hipMemcpyHostToDevice, ctx->stream));
+        SMT_HIP_CHECK(hipMemcpyAsync(const_cast<uint64_t *>(plan.d_p), plan.prefixes.data(), plan.prefixes.size() * sizeof(uint64_t),
+                                     hipMemcpyHostToDevice, ctx->stream));
         SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the host vectors die with this frame
     }
-    ScanArgs a;
-    a.corpus = corpus->d_rows;
-    a.rows = corpus->rows;
-    a.queries = queries_dev;
-    a.nq = nq;
-    a.k_out = k_eff;
-    a.ranges = d_r;
-    a.range_prefix = d_p;
-    a.range_chunk_prefix = d_cp;
-    a.n_chunks = n_chunks;
-    a.range_tile_prefix = d_tp;
-    a.n_vtiles = n_vtiles;
-    a.n_ranges = nr;
-    a.n_virtual = n_virtual;
+    ScanArgs a = scan_args(corpus, queries_dev, nq, k_eff, row_base);
+    plan.apply(a);
     a.ws_threshold = ws_threshold;
     a.ws_thr_score = ws_thr_score;
-    a.row_base = row_base;
     a.out_rows = packed_dev;
     a.out_dist = reinterpret_cast<double *>(packed_dev + k_pad);
-    a.out_counts = nullptr;
     a.out_uncertain = uncertain_dev;
     a.allow_async = async;
     a.out_stride = (uint64_t)2 * k_pad;
-    a.range_set = rset;
-    rc = k_eff > SCAN_MAX_K ? largek_route(ctx, corpus, a) : topk_dispatch(ctx, corpus, a);
-    return rc;
+    return k_eff > SCAN_MAX_K ? largek_route(ctx, corpus, a) : topk_dispatch(ctx, corpus, a);
 }
 
 }  // namespace smt
@@ -929,24 +930,9 @@ try {
     int rc = bind_device(ctx, !async);
     if (rc) return rc;
     if (nq == 0) return SMT_OK;
-    ScanArgs a;
-    a.corpus = corpus->d_rows;
-    a.rows = corpus->rows;
-    a.queries = queries_dev;
-    a.nq = nq;
-    a.k_out = top_k;
-    a.ranges = nullptr;
-    a.range_prefix = nullptr;
-    a.range_chunk_prefix = nullptr;
-    a.n_chunks = 0;
-    a.n_ranges = 0;
-    a.n_virtual = corpus->rows;
-    a.ws_threshold = 0;
-    a.ws_thr_score = 0.f;
-    a.row_base = row_base;
+    ScanArgs a = scan_args(corpus, queries_dev, nq, top_k, row_base);
     a.out_rows = out_rows_dev;
     a.out_dist = out_dist_dev;
-    a.out_counts = nullptr;
     a.out_status = out_status_dev;
     a.allow_async = async;
     a.allow_overlap = async;
@@ -956,8 +942,7 @@ try {
         if (out_status_dev) SMT_HIP_CHECK(hipMemsetAsync(out_status_dev, 0, (size_t)nq * sizeof(uint32_t), ctx->stream));
         return launch_merge_topk(ctx, out_rows_dev, out_dist_dev, 0, nq, 1, top_k, out_rows_dev, out_dist_dev);
     }
-    rc = topk_dispatch(ctx, corpus, a);
-    return rc;
+    return topk_dispatch(ctx, corpus, a);
 } catch (...) { return smt::api_catch(); }
 
 int smt_debug_batched_scores(smt_corpus *corpus, const float *queries, uint32_t nq, uint64_t first_row, uint32_t n_rows,
