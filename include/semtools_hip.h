@@ -515,7 +515,10 @@ int smt_debug_batched_scores(smt_corpus *corpus, const float *queries, uint32_t 
 /* The context's second stream (hipStream_t), created on first use: async selects run on it, or, with tuning key
  * scan_overlap, it waits for them (every select of an overlapped call enqueued before the work).  A host that
  * chains more work behind an async select (an RCCL all-gather of its output, the merge of the gathered
- * lists with tuning key merge_on_aux) enqueues it here so that the main stream carries nothing but scans. */
+ * lists with tuning key merge_on_aux) enqueues it here so that the main stream carries nothing but scans.
+ * The aux stream is ordered behind async selects ONLY.  Every other device call -- several queries, a filtered call, top_k > 56
+ * (the sampled-threshold route) -- runs on the context's stream, and work that depends on its output goes on that stream, or on
+ * the aux stream after it has been made to wait for the context's stream (an event, hipStreamWaitEvent). */
 int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
 
 /* Tuning knobs; for benchmarking sweeps and throughput pipelines.  Keys:

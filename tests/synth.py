@@ -115,3 +115,57 @@ def clustered_sample_torch(model, n, seed, spread=0.35, noise=0.01):
         xs += (noise / 16.0) * torch.randn(e - b, 256, device=model["device"], generator=g)
         x[b:e] = xs / xs.norm(dim=1, keepdim=True)
     return x
+
+
+# ---- inputs for the large-k route's sampled threshold; shared by the adversarial tests and the fuzz suite
+
+def largek_plan(n, k):
+    """The documented plan of the sampled route for n scanned rows: sample size S, rank r of the sampled order statistic, guard,
+    candidate capacity, and the sampled (virtual) rows s * n // S.  Used to CHOOSE inputs, never to predict a verdict."""
+    k_eff = min(k, n)
+    guard = max(64, k_eff // 16)
+    kg = k_eff + guard
+    if n <= 16384:
+        return dict(S=0, rank=0, guard=guard, cap=n, grid=np.zeros(0, dtype=np.int64), sampled=False)
+    S = min(n, max(8192, n // 256))
+    rank = min(S, max(8, -(-3 * kg * S // n)))
+    cap = min(16384, max(8 * kg, 3 * (rank * n // S)))
+    cap = min(16384, (cap + 255) & ~255)
+    grid = (np.arange(S, dtype=np.int64) * n) // S
+    return dict(S=S, rank=rank, guard=guard, cap=cap, grid=grid, sampled=True)
+
+
+def graded_near_rows(q, m, seed, lo=0.05, hi=1.2):
+    """m rows q + s_i * u_i with u_i a unit vector orthogonal to q and s_i rising from lo to hi: cosine distance 1 - 1/sqrt(1 + s_i^2),
+    ascending in i, distinct, and far below the ~0.7 that the nearest of 10^5..10^6 random unit rows reaches."""
+    rng = np.random.default_rng(seed)
+    q = q.astype(np.float64) / np.linalg.norm(q.astype(np.float64))
+    u = rng.standard_normal((m, DIM))
+    u -= (u @ q)[:, None] * q[None, :]
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    s = np.linspace(lo, hi, m)[:, None]
+    x = q[None, :] + s * u
+    x /= np.linalg.norm(x, axis=1, keepdims=True)
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def plant_near_rows(emb, q, m, seed, on_grid, grid, shuffle=True, lo=0.05, hi=1.2, eligible=None):
+    """Overwrite m rows of emb with graded near rows of q: `on_grid` of them (a random subset of the ranks) at sampled positions
+    `grid`, the rest at positions the sample never reads (rows of `eligible`, when a range list narrows the scan).  Returns the positions, in the near rows' rank order."""
+    rng = np.random.default_rng(seed + 1)
+    n = len(emb)
+    on_grid = int(min(on_grid, m, len(grid)))
+    off = np.setdiff1d(np.arange(n, dtype=np.int64) if eligible is None else eligible, grid)
+    m = int(min(m, on_grid + len(off)))
+    pos = np.empty(m, dtype=np.int64)
+    ranks_on = rng.choice(m, size=on_grid, replace=False)
+    mask = np.zeros(m, dtype=bool)
+    mask[ranks_on] = True
+    pos[mask] = rng.choice(grid, size=on_grid, replace=False)
+    pos[~mask] = rng.choice(off, size=m - on_grid, replace=False)
+    if not shuffle:
+        pos[mask] = np.sort(pos[mask])
+        pos[~mask] = np.sort(pos[~mask])
+    emb[pos] = graded_near_rows(q, m, seed, lo, hi)
+    return pos
+

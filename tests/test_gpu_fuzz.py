@@ -9,6 +9,7 @@ from hypothesis import HealthCheck, given, settings, strategies as st
 from oracle import oracle as orc
 from tests import synth
 from tests.compare import assert_topk_tie_aware, reference_distances
+from tests.soundness import assert_sound, host_both, oracle_topk
 
 pytestmark = pytest.mark.gpu
 SCALE = int(os.environ.get("SMT_FUZZ_SCALE", "1"))  # SMT_FUZZ_SCALE=10: ten times the examples (soak run)
@@ -185,3 +186,44 @@ def test_sharded_random_shapes_against_the_oracle(gpu_ctx, n_shards, transport, 
     finally:
         sc.close()
         g.close()
+
+
+@settings(max_examples=12 * SCALE, deadline=None, derandomize=DERANDOMIZE, suppress_health_check=[HealthCheck.function_scoped_fixture])
+@given(n=st.integers(16_385, 120_000), k=st.integers(57, 1024), nq=st.sampled_from([1, 2, 4, 5, 9, 33]), seed=st.integers(0, 10_000),
+       dup=st.sampled_from([0.0, 0.05, 0.5]), use_ranges=st.booleans(), image=st.booleans(),
+       planted=st.sampled_from(["none", "on the sample grid", "off the sample grid"]))
+def test_largek_sampled_regime_is_sound(gpu_ctx, n, k, nq, seed, dup, use_ranges, image, planted):
+    """The sampled-threshold route (topk_large.hip) above its 16 384-row shortcut, with near rows of query 0 planted at or between the
+    sampled positions: every PROVED list of the device form is the oracle's, the host form equals the oracle for every query
+    (tests/soundness.py); over ranges, the host form against the oracle on the eligible rows."""
+    import semtools_amd as smt
+
+    emb = synth.unit_rows(n, seed=seed, dup_frac=dup, zero_frac=0.01)
+    qs = synth.unit_query(seed + 1, nq=nq)
+    rng = np.random.default_rng(seed)
+    ranges, idx = None, np.arange(n)
+    if use_ranges:
+        cuts = np.sort(rng.choice(np.arange(1, n), size=40, replace=False))
+        ranges = [(int(a), int(b)) for a, b in zip(cuts[::2], cuts[1::2])]
+        idx = np.concatenate([np.arange(a, b) for a, b in ranges])
+    if planted != "none":
+        plan = synth.largek_plan(len(idx), k)      # the sample reads virtual rows of the range list: idx[grid]
+        m = int(rng.integers(1, 3 * plan["cap"]))
+        synth.plant_near_rows(emb, qs[0], m, seed=seed + 2, on_grid=m if planted.startswith("on") else 0, grid=idx[plan["grid"]],
+                              eligible=idx)
+    c = smt.Corpus(gpu_ctx)
+    c.append(emb)
+    if image:
+        c.prepack()
+    try:
+        note = (n, k, nq, seed, dup, use_ranges, image, planted)
+        if use_ranges:   # the device form takes no ranges: the host form alone
+            got = host_both(c, qs, top_k=k, ranges=ranges)
+            for i in range(nq):
+                orows, odist = oracle_topk(emb[idx], qs[i], k)
+                assert got[i][0].tolist() == idx[np.array(orows, dtype=np.int64)].tolist(), (note, i)
+                assert got[i][1].tobytes() == odist.tobytes(), (note, i)
+        else:
+            assert_sound(c, emb, qs, k, family=None)
+    finally:
+        c.close()

@@ -67,6 +67,9 @@ def _series(torch, ctx, stream, corpora, qs, n, ks, overlap, wait="ctx", fresh_q
         corpora[i % len(corpora)].search_topk_device(q.data_ptr(), 1, k, 0, rows[i].data_ptr(), dist[i].data_ptr(),
                                                      out_status_ptr=status[i:].data_ptr())
         if aux is not None:
+            if k > 56:
+                # not an async select: the sampled-threshold route runs on the context's stream, which is what orders work behind it
+                aux.wait_stream(stream)
             with torch.cuda.stream(aux):
                 rows2[i].copy_(rows[i])
                 dist2[i].copy_(dist[i])
@@ -94,6 +97,29 @@ def test_overlap_series_equals_aux_pipeline(setup, ks):
     assert (want[2] == 0).all()
     for rep in range(2):
         got = _series(torch, ctx, stream, corpora, qs, 240, ks, 1)
+        _same(got, want)
+
+
+@pytest.mark.parametrize("on_aux", [False, True])
+@pytest.mark.parametrize("ks", [(10, 100), (56, 57, 1, 1024, 10)])
+def test_large_k_calls_inside_the_overlapped_series(setup, ks, on_aux):
+    """k > 56 takes the sampled-threshold route on the context's stream (bind_device(ctx, true)) between one-query calls whose scan
+    and select run on the two internal streams: rows, distances and status words are the bytes of scan_overlap = 0.  on_aux: the
+    answers are copied on the aux stream right behind each call; behind a large-k call that stream first waits for the context's."""
+    torch, ctx, stream, corpora, qs = setup
+    want = _series(torch, ctx, stream, corpora, qs, 240, ks, 0, on_aux=on_aux)
+    assert set(want[2].tolist()) <= {0, 1, 2}
+    small = [i for i in range(240) if ks[i % len(ks)] <= 56]
+    assert (want[2][small] == 0).all()
+    large = [i for i in range(240) if ks[i % len(ks)] > 56]
+    assert (want[2][large] == 0).sum() >= 0.95 * len(large)        # and the large-k calls did prove their lists
+    assert (want[2][large] != 2).all()                             # (an overflowed buffer keeps keys in the order of its atomics)
+    for i in large:                                                # a written list, padded behind min(k, n)
+        k = ks[i % len(ks)]
+        n = SIZES[i % len(SIZES)]
+        assert (want[0][i, :min(k, n)] >= 0).all() and (want[0][i, min(k, n):k] == -1).all() and (want[0][i, k:] == -7).all()
+    for rep in range(2):
+        got = _series(torch, ctx, stream, corpora, qs, 240, ks, 1, on_aux=on_aux)
         _same(got, want)
 
 
