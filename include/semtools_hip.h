@@ -152,6 +152,27 @@ int smt_corpus_write_rows(smt_corpus *corpus, uint64_t first_row, const float *r
                           uint64_t n_rows);
 int smt_corpus_read_rows(smt_corpus *corpus, uint64_t first_row, uint64_t n_rows, float *out_host);
 int smt_corpus_truncate(smt_corpus *corpus, uint64_t n_rows);
+/* Keep exactly the rows inside `keep` (sorted, disjoint, inside [0, rows)), in order, and close the gaps IN PLACE:
+ * afterwards the corpus holds sum(len) rows and old row keep[i].begin + j is row prefix[i] + j.  n_keep == 0 empties it.
+ * What qdrant's optimiser does behind the reference's store when it vacuums deleted points (src/workspace/store.rs:152-166
+ * opens the collection it maintains); here the rows move HBM to HBM (compact.hip), never through the host, and no second
+ * corpus exists meanwhile.  Rows in front of the first dropped row are not touched; *rows_moved (may be NULL) = the kept rows
+ * behind it.  A list that drops nothing is a no-op: no kernel is enqueued and 0 rows move -- so the row count never stays
+ * the same while rows change places.
+ *   - A list that is unsorted, overlapping or out of range: SMT_E_INVALID, the corpus untouched.
+ *   - A corpus adopted with smt_corpus_from_device: SMT_E_UNSUPPORTED (its memory is the caller's to rearrange).
+ *   - Ordering: the move runs after everything already enqueued on the context (its stream and the scan streams of the
+ *     one-query pipeline, tuning keys async_select / scan_overlap) and before anything enqueued later; the call does not wait
+ *     for the move itself.
+ *   - The fp16 operand image is derived data: the tiles from the first moved row on are packed again by the next batch that
+ *     wants them; the allocation and the prepack mode stay.  Kept range sets depend on ranges only and stay.
+ *   - An smt_ivfpq built on the corpus names rows BY POSITION: after a compaction that dropped rows it refuses to search
+ *     ("the corpus shrank ... rebuild").  Destroy and rebuild it.
+ * Steps whose gap is shorter than the bounce buffer go through it (tuning key compact_bounce_rows). */
+int smt_corpus_compact(smt_corpus *corpus, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved /* may be NULL */);
+/* smt_corpus_compact calls that succeeded on this context (no-ops included) and the rows they moved; any pointer may be NULL;
+ * reset != 0 clears both. */
+int smt_ctx_compact_stats(smt_ctx *ctx, uint64_t *calls, uint64_t *rows_moved, int reset);
 /* The fp16 OPERAND IMAGE of a corpus: what the batched nomination modes multiply with (unit rows x 2^10 as fp16 in MFMA operand
  * order, 512 B per row beside the 1 KiB of f32), so that a batch of >= 8 queries reads half the bytes per row and converts
  * nothing.  Derived data only: nominations come from it, every returned distance is re-scored from the f32 rows, results are
@@ -410,6 +431,12 @@ int smt_sharded_corpus_shard(smt_sharded_corpus *corpus, int local_index, smt_co
 int smt_sharded_corpus_append_host(smt_sharded_corpus *corpus, const float *rows, uint64_t n_rows, uint64_t *first_row);
 int smt_sharded_corpus_read_rows(smt_sharded_corpus *corpus, uint64_t first_row, uint64_t n_rows, float *out_host);
 int smt_sharded_corpus_write_rows(smt_sharded_corpus *corpus, uint64_t first_row, const float *rows, uint64_t n_rows);
+/* smt_corpus_compact over the sharded corpus: `keep_global` names GLOBAL rows.  Every shard keeps its part of the list and closes
+ * its own gaps in place (no row changes rank); the piece list shrinks with it -- empty pieces go, neighbours of one rank that
+ * became contiguous merge -- so global order, and with it the tie order of every search, is unchanged.  *rows_moved (may be NULL)
+ * = the rows moved on all shards.  One-process groups only (physical or logical): SMT_E_UNSUPPORTED for a one-rank-per-process
+ * group, and for a corpus made of adopted device buffers.  A refused call leaves the corpus untouched. */
+int smt_sharded_corpus_compact(smt_sharded_corpus *corpus, const smt_range *keep_global, uint32_t n_keep, uint64_t *rows_moved);
 
 /* The embedding table replicated on every device of the group, and K1 sharded by line ("K1 shards by
  * line with a replicated table", no collective): the device half of StaticModel::from_pretrained / encode_with_args
@@ -576,7 +603,10 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *   scan_gate_pct (0..100)  scan_overlap: a scan's blocks start loading rows once this per cent of the previous scan's blocks have
  *                        finished theirs, or after a bound of at most 0.5 ms (default 50; 0 = at once).  Changes timing only,
  *                        never an answer
- *   merge_on_aux (0/1)   smt_merge_topk_packed_device is enqueued on the aux stream (see smt_ctx_aux_stream) */
+ *   merge_on_aux (0/1)   smt_merge_topk_packed_device is enqueued on the aux stream (see smt_ctx_aux_stream)
+ *   compact_bounce_rows (64 .. 2^20, default 65536 = 64 MiB)  smt_corpus_compact: a step whose rows move down by fewer rows than this
+ *                        goes through a bounce buffer of this many rows in the context's scratch (a launch must not overwrite its own
+ *                        sources); a step with a longer gap is one direct launch.  At most 2 x ceil(rows / this) enqueues per call */
 int smt_set_tuning(smt_ctx *ctx, const char *key, int64_t value);
 
 /* ------------------------------------------------------------------ host ids

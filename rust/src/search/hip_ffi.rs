@@ -127,6 +127,13 @@ extern "C" {
     pub fn smt_corpus_write_rows(corpus: *mut SmtCorpus, first_row: u64, rows: *const f32, n_rows: u64) -> c_int;
     pub fn smt_corpus_read_rows(corpus: *mut SmtCorpus, first_row: u64, n_rows: u64, out_host: *mut f32) -> c_int;
     pub fn smt_corpus_truncate(corpus: *mut SmtCorpus, n_rows: u64) -> c_int;
+    pub fn smt_corpus_compact(
+        corpus: *mut SmtCorpus,
+        keep: *const SmtRange,
+        n_keep: u32,
+        rows_moved: *mut u64,
+    ) -> c_int;
+    pub fn smt_ctx_compact_stats(ctx: *mut SmtCtx, calls: *mut u64, rows_moved: *mut u64, reset: c_int) -> c_int;
     pub fn smt_corpus_prepack(corpus: *mut SmtCorpus, enable: c_int) -> c_int;
     pub fn smt_corpus_image_bytes(corpus: *const SmtCorpus) -> u64;
     pub fn smt_corpus_rows(corpus: *const SmtCorpus) -> u64;
@@ -338,6 +345,12 @@ extern "C" {
         first_row: u64,
         rows: *const f32,
         n_rows: u64,
+    ) -> c_int;
+    pub fn smt_sharded_corpus_compact(
+        corpus: *mut SmtShardedCorpus,
+        keep_global: *const SmtRange,
+        n_keep: u32,
+        rows_moved: *mut u64,
     ) -> c_int;
     pub fn smt_sharded_model_create(
         group: *mut SmtGroup,

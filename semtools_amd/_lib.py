@@ -40,6 +40,7 @@ EXPORTS = [
     "smt_sharded_ivfpq_save", "smt_sharded_ivfpq_load", "smt_sharded_ivfpq_append", "smt_sharded_ivfpq_info",
     "smt_group_set_transport", "smt_group_transport", "smt_debug_range_sets", "smt_sharded_corpus_append_to_file_ex",
     "smt_debug_group_fail_next", "smt_search_topk_device_ex", "smt_sharded_search_topk_device_ex", "smt_debug_deliveries",
+    "smt_corpus_compact", "smt_ctx_compact_stats", "smt_sharded_corpus_compact",
 ]
 STATUS_PROVED, STATUS_UNCERTAIN, STATUS_OVERFLOW, STATUS_INVALID_QUERY = 0, 1, 2, 3
 TRANSPORT_RCCL, TRANSPORT_COPY, TRANSPORT_PEER = 0, 1, 2
@@ -137,6 +138,8 @@ def lib():
     L.smt_corpus_image_bytes.restype = u64
     L.smt_corpus_read_rows.argtypes = [vp, u64, u64, vp]
     L.smt_corpus_truncate.argtypes = [vp, u64]
+    L.smt_corpus_compact.argtypes = [vp, vp, u32, P(u64)]
+    L.smt_ctx_compact_stats.argtypes = [vp, P(u64), P(u64), i32]
     L.smt_corpus_rows.argtypes = [vp]
     L.smt_corpus_rows.restype = u64
     L.smt_corpus_dim.argtypes = [vp]
@@ -222,6 +225,7 @@ def lib():
     L.smt_sharded_corpus_append_to_file.argtypes = [vp, C.c_char_p, u64]
     L.smt_sharded_corpus_read_rows.argtypes = [vp, u64, u64, vp]
     L.smt_sharded_corpus_write_rows.argtypes = [vp, u64, vp, u64]
+    L.smt_sharded_corpus_compact.argtypes = [vp, vp, u32, P(u64)]
     L.smt_sharded_model_create.argtypes = [vp, vp, u64, u32, i32, P(vp)]
     L.smt_sharded_model_create_from_file.argtypes = [vp, C.c_char_p, u64, u64, u32, i32, P(vp)]
     L.smt_sharded_model_destroy.argtypes = [vp]

@@ -1,10 +1,14 @@
 """Object wrappers over the C ABI handles (context / model / corpus)."""
+import collections
 import ctypes as C
 import math
 
 import numpy as np
 
 from . import _lib as L
+
+
+CompactStats = collections.namedtuple("CompactStats", "calls rows_moved")
 
 
 def _f32c(a):
@@ -55,6 +59,12 @@ class Context:
         n = C.c_uint64(0)
         L.check(L.lib().smt_debug_deliveries(self._h, C.byref(n)))
         return int(n.value)
+
+    def compact_stats(self, reset=False):
+        """CompactStats(calls, rows_moved): the Corpus.compact calls that succeeded on this context and the rows they moved."""
+        n, m = C.c_uint64(0), C.c_uint64(0)
+        L.check(L.lib().smt_ctx_compact_stats(self._h, C.byref(n), C.byref(m), int(bool(reset))))
+        return CompactStats(int(n.value), int(m.value))
 
     def aux_stream(self):
         """Raw hipStream_t of the context's second stream (async selects run there, or -- tuning key scan_overlap -- it
@@ -198,6 +208,14 @@ class Corpus:
 
     def truncate(self, n_rows):
         L.check(L.lib().smt_corpus_truncate(self._h, int(n_rows)))
+
+    def compact(self, ranges):
+        """smt_corpus_compact: keep exactly the rows inside `ranges` ([(begin, end), ...] sorted, disjoint) and close the gaps in place,
+        on the device.  Returns the rows that moved (the kept rows behind the first dropped one)."""
+        rng, n = _ranges_arg(list(ranges))
+        moved = C.c_uint64(0)
+        L.check(L.lib().smt_corpus_compact(self._h, C.cast(rng, C.c_void_p), n, C.byref(moved)))
+        return int(moved.value)
 
     def prepack(self, enable=True):
         """smt_corpus_prepack: build (or drop) the fp16 operand image the batched searches read -- half the bytes per row.  For a
@@ -537,6 +555,13 @@ class ShardedCorpus:
     def write_rows(self, first_row, rows):
         rows = _f32c(rows).reshape(-1, L.DIM)
         L.check(L.lib().smt_sharded_corpus_write_rows(self._h, int(first_row), L.np_ptr(rows), rows.shape[0]))
+
+    def compact(self, ranges):
+        """smt_sharded_corpus_compact: Corpus.compact with GLOBAL rows; every shard closes its own gaps.  Returns the rows moved."""
+        rng, n = _ranges_arg(list(ranges))
+        moved = C.c_uint64(0)
+        L.check(L.lib().smt_sharded_corpus_compact(self._h, C.cast(rng, C.c_void_p), n, C.byref(moved)))
+        return int(moved.value)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

@@ -552,6 +552,7 @@ try {
     else if (k == "select_debug_ptr") ctx->tune.select_debug_ptr = value;
     else if (k == "prof_select") ctx->tune.prof_select = (int)value;
     else if (k == "direct_delivery") ctx->tune.direct_delivery = (int)value;
+    else if (k == "compact_bounce_rows") ctx->tune.compact_bounce_rows = std::max<int64_t>(64, std::min<int64_t>((int64_t)1 << 20, value));
     else { set_error("unknown tuning key '%s'", key); return SMT_E_INVALID; }
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
@@ -748,6 +749,21 @@ try {
     corpus_writer_drain(c);   // (later appends reuse the space: a write-ahead job must not still be reading the old rows there)
     c->rows = n_rows;
     c->image_rows = std::min<uint64_t>(c->image_rows, n_rows / 32 * 32);   // rows appended later land in tiles the image packs again
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_corpus_compact(smt_corpus *c, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved)
+try {
+    return corpus_compact(c, keep, n_keep, rows_moved);
+} catch (...) { return smt::api_catch(); }
+
+int smt_ctx_compact_stats(smt_ctx *ctx, uint64_t *calls, uint64_t *rows_moved, int reset)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (calls) *calls = ctx->compact_calls;
+    if (rows_moved) *rows_moved = ctx->compact_rows_moved;
+    if (reset) ctx->compact_calls = ctx->compact_rows_moved = 0;
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 

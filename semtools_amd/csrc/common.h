@@ -87,6 +87,7 @@ struct Tuning {
     int prof_select = 1;        // 0: do not bracket the select stage with events (2 fewer event records per query)
     int largek_sampled = 1;     // 1: 57 <= top_k <= 1024 take the sampled-threshold route (topk_large.hip); 0: the all-keys path (largek.hip, A/B and parity tests)
     int direct_delivery = 1;    // 1: host-form top-k searches with small answers (<= 8 KiB) get them DELIVERED by the select kernel into pinned host memory, completion word last; the host waits on that word (search.cpp; 0: D2H copy + hipStreamSynchronize, A/B)
+    int64_t compact_bounce_rows = 65536;   // smt_corpus_compact: rows of the bounce buffer a step with a gap shorter than itself goes through (64 MiB; 64 .. 2^20), compact.hip
     int64_t scan_debug_ptr = 0;    // device pointer to (2*waves + blocks) u64 wall_clock64 stamps (profiling only)
     int64_t select_debug_ptr = 0;  // device pointer to 16 u64 for phase stamps (profiling only)
 };
@@ -135,6 +136,8 @@ struct smt_ctx {
     uint64_t steal_seq = 0;
     unsigned long long deliver_seq = 0;      // sequence number of the last delivered answer (its completion word in pinned memory)
     uint64_t deliveries = 0;                 // host-form searches answered that way (smt_debug_deliveries)
+    uint64_t compact_calls = 0;              // smt_corpus_compact calls that succeeded on this context, and the rows they moved (smt_ctx_compact_stats)
+    uint64_t compact_rows_moved = 0;
     bool prof_on = false;
     // kernels whose >64 KiB dynamic-LDS attribute has been set ON THIS DEVICE (bit per kernel family, smt::ATTR_*).
     // Per context, not per process: hipFuncSetAttribute applies to the current device's copy of the function, and a
@@ -215,6 +218,9 @@ int corpus_image_sync(smt_corpus *c, uint32_t nq, const void **image, const uint
 void corpus_image_drop(smt_corpus *c);
 int launch_pack_image(smt_ctx *ctx, const float *corpus, uint64_t n_rows, uint64_t first_tile, uint64_t n_tiles, void *image,
                       uint32_t *image_zero);
+// compact.hip: keep exactly the rows inside `keep` (sorted, disjoint, inside [0, rows)) and close the gaps in place -- the body of
+// smt_corpus_compact.  Validates first: a refused list leaves the corpus untouched.
+int corpus_compact(smt_corpus *c, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved);
 int ensure_scratch(smt_ctx *ctx, size_t bytes);
 int ensure_pinned(smt_ctx *ctx, size_t bytes);
 int ensure_pinned_in(smt_ctx *ctx, size_t bytes);

@@ -345,6 +345,7 @@ private:
     std::string dir_;
     smt_group *group_ = nullptr;
     smt_sharded_corpus *corpus_ = nullptr;
+    bool compact_in_place(const std::vector<std::pair<uint64_t, std::string>> &order);   // compact_if_sparse on the device; false: not possible / not wise here
     void drop_index();                           // index_ (points into corpus_) and its files: rows are about to move
     void remove_index_files() const;             // every line_index.* of the directory, whatever rank count wrote it
     uint64_t generation_ = 0;                    // bumped by drop_index; line_rows.json and line_index.gen carry it

@@ -608,6 +608,57 @@ Store::ReembedReport Store::reembed_from_token_cache(const search::StaticModel &
     return rep;
 }
 
+// Compaction on the device (smt_sharded_corpus_compact): every shard closes its own gaps HBM to HBM, no row crosses PCIe and no
+// second corpus exists meanwhile.  Same resulting row order as the copy through the host below -- live extents back to back in
+// first_row order -- hence the same line_embeddings.f32 bytes and line_rows.json extents.  false = not done, nothing changed.
+bool Store::compact_in_place(const std::vector<std::pair<uint64_t, std::string>> &order)
+{
+    std::vector<smt_range> keep;
+    for (auto &o : order) {
+        const Extent &x = extents_[o.second];
+        if (!x.n_rows) continue;
+        if (!keep.empty() && keep.back().end == x.first_row) keep.back().end += x.n_rows;
+        else keep.push_back(smt_range{x.first_row, x.first_row + x.n_rows});
+    }
+    // No row changes rank in place, and dead rows can pile up on one shard (appends alone re-balance slowly): when the fullest rank
+    // would be left with more than 1.5 x the mean rank's rows, the copy through the host deals them evenly again.  1.5 x is a
+    // policy -- a scan waits for its fullest shard -- not a measurement.
+    int n_ranks = 1;
+    check(smt_group_info(group_, &n_ranks, nullptr, nullptr, nullptr, nullptr), "compact");
+    if (n_ranks > 1) {
+        const uint64_t n_pieces = smt_sharded_corpus_layout(corpus_, nullptr, nullptr, 0);
+        std::vector<uint64_t> piece_rows(n_pieces), left((size_t)n_ranks, 0);
+        std::vector<uint32_t> piece_rank(n_pieces);
+        smt_sharded_corpus_layout(corpus_, piece_rows.data(), piece_rank.data(), n_pieces);
+        uint64_t pb = 0, live = 0;
+        size_t ki = 0;
+        for (uint64_t k = 0; k < n_pieces; ++k) {
+            const uint64_t pe = pb + piece_rows[k];
+            while (ki < keep.size() && keep[ki].end <= pb) ++ki;
+            for (size_t j = ki; j < keep.size() && keep[j].begin < pe; ++j) {
+                const uint64_t b = std::max(keep[j].begin, pb), e = std::min(keep[j].end, pe);
+                if (e > b) { left[piece_rank[k]] += e - b; live += e - b; }
+            }
+            pb = pe;
+        }
+        const uint64_t fullest = *std::max_element(left.begin(), left.end());
+        if (fullest * 2 * (uint64_t)n_ranks > live * 3) return false;
+    }
+    drop_index();                            // the index names rows by position: it goes before they move
+    const int rc = smt_sharded_corpus_compact(corpus_, keep.data(), (uint32_t)keep.size(), nullptr);
+    if (rc == SMT_E_UNSUPPORTED) return false;   // (refused before any row moved)
+    check(rc, "compact");
+    uint64_t at = 0;
+    for (auto &o : order) {
+        Extent &x = extents_[o.second];
+        x.first_row = at;
+        at += x.n_rows;
+    }
+    dead_rows_ = 0;
+    rows_on_disk_valid_ = false;  // rows moved: the file must be rewritten
+    return true;
+}
+
 void Store::compact_if_sparse()
 {
     const uint64_t total = smt_sharded_corpus_rows(corpus_);
@@ -616,6 +667,9 @@ void Store::compact_if_sparse()
     std::vector<std::pair<uint64_t, std::string>> order;
     for (auto &kv : extents_) order.emplace_back(kv.second.first_row, kv.first);
     std::sort(order.begin(), order.end());
+    if (compact_in_place(order)) return;
+    // The copy through the host into a fresh corpus: what a group the library cannot compact in place gets (one rank per process),
+    // and what re-deals the rows when the in-place move would leave the shards lopsided (compact_in_place).
     smt_sharded_corpus *fresh = nullptr;
     check(smt_sharded_corpus_create(group_, SMT_DIM, &fresh), "compact");
     std::map<std::string, Extent> fresh_extents;

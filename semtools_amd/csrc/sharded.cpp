@@ -524,6 +524,63 @@ try {
     return sharded_copy_rows(sc, first_row, n_rows, nullptr, rows);
 } catch (...) { return smt::api_catch(); }
 
+int smt_sharded_corpus_compact(smt_sharded_corpus *sc, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved)
+try {
+    SMT_REQUIRE(sc && (keep || n_keep == 0), "null argument");
+    smt_group *g = sc->group;
+    if (rows_moved) *rows_moved = 0;
+    // the ranks' rows of other processes cannot be told to move from here, and the host layer above is one process
+    if (!single_process(g)) { set_error("compaction needs a single-process group"); return SMT_E_UNSUPPORTED; }
+    uint64_t prev_end = 0;
+    for (uint32_t k = 0; k < n_keep; ++k) {
+        SMT_REQUIRE(keep[k].begin <= keep[k].end, "range begin > end");
+        SMT_REQUIRE(keep[k].end <= sc->total(), "range extends past the corpus");
+        SMT_REQUIRE(k == 0 || keep[k].begin >= prev_end, "ranges must be sorted and disjoint");
+        prev_end = keep[k].end;
+    }
+    for (smt_corpus *c : sc->shard)   // (before any shard moves a row: a refused call leaves the corpus as it was)
+        if (!c->owned) { set_error("smt_sharded_corpus_compact: a shard adopted from device memory is the caller's to rearrange"); return SMT_E_UNSUPPORTED; }
+    // every shard keeps its part of the list (local rows ascend with global rows inside a rank) and closes its own gaps
+    uint64_t moved = 0;
+    std::vector<smt_range> local;
+    for (int i = 0; i < g->n_local; ++i) {
+        layout_localize(sc, g->first_rank + i, keep, n_keep, local);
+        uint64_t m = 0;
+        const int rc = smt_corpus_compact(sc->shard[i], local.data(), (uint32_t)local.size(), &m);
+        if (rc) return rc;
+        moved += m;
+    }
+    // the piece list: each piece shrinks to its kept rows, empty ones go, both numberings are prefixed again; neighbours in global
+    // order that lie on one rank are neighbours in its local order too (nothing of that rank lies between them) and merge
+    std::vector<ShardPiece> pieces;
+    std::vector<uint64_t> rank_rows(g->n_ranks, 0);
+    uint64_t total = 0;
+    uint32_t ki = 0;
+    for (const ShardPiece &p : sc->pieces) {
+        const uint64_t pb = p.global_begin, pe = pb + p.n_rows;
+        uint64_t kept = 0;
+        while (ki < n_keep && keep[ki].end <= pb) ++ki;
+        for (uint32_t j = ki; j < n_keep && keep[j].begin < pe; ++j) {
+            const uint64_t b = std::max(keep[j].begin, pb), e = std::min(keep[j].end, pe);
+            if (e > b) kept += e - b;
+        }
+        if (!kept) continue;
+        if (!pieces.empty() && pieces.back().rank == p.rank) pieces.back().n_rows += kept;
+        else {
+            ShardPiece q;
+            q.global_begin = total; q.n_rows = kept; q.local_begin = rank_rows[p.rank]; q.rank = p.rank;
+            pieces.push_back(q);
+        }
+        rank_rows[p.rank] += kept;
+        total += kept;
+    }
+    sc->pieces.swap(pieces);
+    sc->rank_rows.swap(rank_rows);
+    layout_reindex(sc);   // (bumps layout_version: the device piece tables of layout_translate_packed are uploaded again)
+    if (rows_moved) *rows_moved = moved;
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
 /* ------------------------------------------------- replicated model + sharded K1 ---- */
 
 void smt_sharded_model_destroy(smt_sharded_model *m)
