@@ -1,6 +1,6 @@
 // api.cpp -- host side of libsemtools_hip.so: error text, contexts, tuning keys, models, corpora (with their fp16 operand image),
 // embed, ids -- the extern "C" entry points of include/semtools_hip.h that are not searches (search.cpp), files (corpus_io.cpp),
-// groups (group.cpp, sharded.cpp) or indexes (ivfpq_*.hip).  There is no CPU fallback anywhere: every compute entry point needs
+// groups (group.cpp, group_exchange.cpp, sharded_search.cpp, sharded.cpp) or indexes (ivfpq_*.hip).  There is no CPU fallback anywhere: every compute entry point needs
 // a live gfx950 context.
 #include <algorithm>
 #include <cerrno>

@@ -280,7 +280,7 @@ struct ScanArgs {
     const void *image = nullptr;          // the corpus' fp16 operand image covering all `rows` (smt_corpus::image), or nullptr
     const uint32_t *image_zero = nullptr;
     uint64_t out_stride = 0;  // words between the output lists of consecutive queries (0 = k_out); the packed
-                              // [nq][2][k] exchange layout of group.cpp uses 2*k with out_dist = out_rows + k
+                              // [nq][2][k] exchange layout of group_exchange.cpp uses 2*k with out_dist = out_rows + k
     struct RangeSet *range_set = nullptr;   // the ranges come from a kept set: its tile / chunk tables are built once and reused
     const struct Delivery *deliver = nullptr;   // the select stage delivers the answers to pinned host memory (below)
 };
@@ -414,7 +414,7 @@ int deliver_hits(const std::vector<LocalHits> &hits, uint64_t *out_rows, double 
 int search_topk_packed_local(smt_corpus *corpus, const float *queries_dev, uint32_t nq, uint32_t k_pad, int ws_threshold,
                              float ws_thr_score, const smt_range *ranges_local, uint32_t n_ranges, bool filtered,
                              uint64_t row_base, uint64_t *packed_dev, uint64_t *uncertain_dev, bool allow_async);
-// corpus file slices (corpus_io.cpp): shared by smt_corpus_save/load and the sharded corpus of group.cpp
+// corpus file slices (corpus_io.cpp): shared by smt_corpus_save/load and the sharded corpus of sharded.cpp
 int corpus_file_info(const char *path, uint64_t *rows, uint32_t *dim);
 int corpus_load_slice(smt_corpus *c, const char *path, uint64_t first_row, uint64_t n_rows);
 int corpus_file_begin(const char *path, uint32_t dim, uint64_t total_rows);
@@ -430,7 +430,7 @@ int corpus_file_commit(const char *path, uint64_t rows);
 int launch_merge_topk_packed_on(smt_ctx *ctx, hipStream_t st, const uint64_t *packed, uint32_t n_lists, uint32_t nq,
                                 uint32_t k_in, uint32_t k_out, uint64_t *out_packed, uint64_t list_stride_words = 0);
 
-// merge of lists read where they lie (one base pointer per list): the peer transport of group.cpp
+// merge of lists read where they lie (one base pointer per list): the peer transport of group_exchange.cpp
 #define SMT_MAX_MERGE_SOURCES 64
 struct MergeSources { const uint64_t *list[SMT_MAX_MERGE_SOURCES]; };
 int launch_merge_topk_sources_on(hipStream_t st, const MergeSources &src, uint32_t n_lists, uint32_t nq, uint32_t k_in, uint32_t k_out,
@@ -456,7 +456,7 @@ int launch_largek_candidates(smt_ctx *ctx, const float *corpus, const float *que
                              std::vector<uint32_t> &rows_out, std::vector<double> &dist_out, float *next_d32 = nullptr
                              /* f32 distance of the best row NOT among the candidates (+inf if none) */);
 
-// IVF index as one rank of a shared-centroid build / packed search (ivfpq_build.hip / ivfpq_search.hip <-> group.cpp)
+// IVF index as one rank of a shared-centroid build / packed search (ivfpq_build.hip / ivfpq_search.hip <-> sharded_search.cpp, group_exchange.cpp)
 struct IvfBuildShare {
     uint32_t rank = 0, n_ranks = 1;
     // sum `sums` (n_sums int64, 2^-32 fixed point) and `counts` (n_counts u32) over the ranks, in place, enqueued on

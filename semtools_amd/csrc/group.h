@@ -1,5 +1,7 @@
-// group.h -- internal declarations shared by group.cpp (groups, collectives, sharded search) and sharded.cpp (the
-// sharded corpus' row layout and storage, the replicated model + sharded embed, the sharded index life cycle).
+// group.h -- internal declarations shared by group.cpp (the RCCL binding, group life cycle, issuing threads, barriers),
+// group_exchange.cpp (the transports that move lists between ranks, and the merges on top of them), sharded_search.cpp (the sharded
+// search entry points and the sharded IVF index) and sharded.cpp (the sharded corpus' row layout and storage, the replicated
+// model + sharded embed).
 #pragma once
 #include <rccl/rccl.h>
 
@@ -19,6 +21,18 @@ struct GroupBuf {
     size_t dev_bytes = 0;
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
+};
+
+// What every local rank made of one step: its status and, where it failed, the message of the thread that ran it.
+struct smt_group;
+struct RankStatuses {
+    std::vector<int> rcs;
+    std::vector<std::string> errs;
+    explicit RankStatuses(int n = 0) : rcs(n, SMT_OK), errs(n) {}
+    void record(int i, int rc);   // rank i's status, with the calling thread's last error when it failed
+    int failed() const;           // the first failing rank's status, 0 if none
+    // the first failing rank's status and its message, as "shard %d: ..." with `prefix`, as this thread's error; 0 if none
+    int report(const smt_group *g, bool prefix = true) const;
 };
 
 // Issuing threads: one per local device of a single-process group.  The caller is ONE synchronous host thread
@@ -42,8 +56,7 @@ struct GroupWorkers {
     std::atomic<int> caller_blocked{0};  // the caller is blocked (or about to block) on cv_done
     std::atomic<bool> stop{false};
     long long spin_ns = 100000;          // $SEMTOOLS_GROUP_SPIN_US (0: block at once)
-    std::vector<int> rcs;
-    std::vector<std::string> errs;
+    RankStatuses status;                 // [n_local] slot i belongs to rank i's thread until `pending` reaches 0
 };
 
 struct smt_group {
@@ -145,12 +158,15 @@ struct smt_sharded_model {
 
 namespace smt {
 
+// ---- groups (group.cpp)
 int group_bind(smt_group *g, int i);
-int ensure_dev(smt_group *g, int i, size_t bytes);
-int ensure_host(smt_group *g, int i, size_t bytes);
-// All-gather `words` u64 per rank: send_off / recv_off are BYTE offsets into each local device's exchange buffer.
-int allgather_words(smt_group *g, size_t send_off, size_t recv_off, size_t words, const std::vector<char> *on_aux = nullptr);
 int group_sync_all(smt_group *g);
+int sync_every_stream(smt_group *g);   // group_sync_all + the aux streams
+// the RCCL halves of allgather_words and group_allreduce_sums (the binding is private to group.cpp)
+int rccl_allgather_words(smt_group *g, size_t send_off, size_t recv_off, size_t words, const std::vector<char> *on_aux);
+int rccl_allreduce_sums(smt_group *g, int i, long long *sums, size_t n_sums, unsigned int *counts, size_t n_counts);
+// fn(i) for i in [0, n) on n threads that all exist before any starts; false (error set) = they could not be had and nothing ran
+bool run_on_threads(int n, const std::function<void(int)> &fn);
 int group_barrier(smt_group *g);
 // Barrier that carries a status: every rank contributes `rc` and all of them return the first non-zero one (0 if none).
 // Error paths of collective operations go through this so that no rank leaves while the others wait.
@@ -159,6 +175,80 @@ int group_agree(smt_group *g, int rc);
 int group_debug_fail(smt_group *g, int where);
 // run work(i) for every local device, on one host thread per device when there are several; first error wins
 int group_for_each_local(smt_group *g, const std::function<int(int)> &work, bool threads = true);
+
+// ---- exchange (group_exchange.cpp)
+constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// One exchange buffer: [queries | local list + `extra_words` (flags, statuses) | gathered: n_ranks of those | merged list], every
+// region 256-byte aligned.  Host-in searches have all four; the device form has neither queries nor a merged list.
+struct ExchangeLayout {
+    size_t list_words, rank_words;       // per rank: the [nq][2][k] lists; the same + the words behind them
+    size_t loc_off, gath_off, out_off;   // BYTE offsets of the local list, the gathered block, the merged list (0: none)
+    size_t dev_bytes;
+    constexpr ExchangeLayout(uint32_t nq, uint32_t k, size_t extra_words, int n_ranks, bool has_queries, bool has_merged)
+        : list_words((size_t)nq * 2 * k), rank_words(list_words + extra_words),
+          loc_off(has_queries ? align256((size_t)nq * SMT_DIM * 4) : 0), gath_off(loc_off + align256(rank_words * 8)),
+          out_off(has_merged ? gath_off + align256((size_t)n_ranks * rank_words * 8) : 0),
+          dev_bytes((has_merged ? out_off + list_words * 8 : gath_off + (size_t)n_ranks * rank_words * 8) + 64) {}
+};
+static_assert(ExchangeLayout(3, 56, 4, 8, true, true).out_off == 3072 + 2816 + 21760 && ExchangeLayout(3, 56, 4, 8, true, true).dev_bytes == 27648 + 2688 + 64 &&
+              ExchangeLayout(1, 10, 1, 3, false, false).dev_bytes == 256 + 3 * 168 + 64, "exchange layout");
+
+int ensure_dev(smt_group *g, int i, size_t bytes);
+int ensure_host(smt_group *g, int i, size_t bytes);
+inline hipStream_t exchange_stream(const smt_group *g, int i, const std::vector<char> *on_aux)
+{
+    return (on_aux && (*on_aux)[i]) ? g->ctx[i]->aux_stream : g->ctx[i]->stream;
+}
+// All-gather `words` u64 per rank: send_off / recv_off are BYTE offsets into each local device's exchange buffer.
+int allgather_words(smt_group *g, size_t send_off, size_t recv_off, size_t words, const std::vector<char> *on_aux = nullptr);
+// Every local rank i contributes the `w` host words mine[i * w ..]; all-gather; `all` = the n_ranks x w words as local device 0
+// received them, every stream drained -- or (`every_local`) as each local device did, [n_local][n_ranks][w], each read synchronised.
+int gather_host_words(smt_group *g, size_t w, const uint64_t *mine, std::vector<uint64_t> &all, bool every_local = false);
+// Rank j's list of an exchange: in its exchange buffer at L.loc_off (slot < 0), or in slot `slot` of its ring.
+uint64_t *exchange_list(smt_group *g, int j, const ExchangeLayout &L, int slot);
+// Peer transport, rank j, after the last kernel that writes its list on `st`.
+int peer_publish(smt_group *g, int j, hipStream_t st);
+// The caller's thread, after every local rank has published (peer) or after allgather_words: local device i merges the ranks'
+// packed lists [nq][2][k] into out_packed on its stream `st` -- read in place (peer transport; `waits_enqueued`: the ranks' issuers
+// have enqueued the waits, WaitBoard) or from the gathered block; `done` (may be null) is recorded behind the merge.  Records the
+// "exchange" / "merge" profiling pairs.  combine_ranks_status_on: the same sources' nq status words, worst of the ranks.
+int merge_ranks_on(smt_group *g, int i, hipStream_t st, const ExchangeLayout &L, int slot, uint32_t nq, uint32_t k, uint64_t *out_packed,
+                   hipEvent_t done = nullptr, bool waits_enqueued = false);
+int combine_ranks_status_on(smt_group *g, int i, hipStream_t st, const ExchangeLayout &L, int slot, uint32_t nq, uint32_t *out_status);
+void ring_free(smt_group *g);
+int ring_ensure(smt_group *g, size_t slot_bytes);
+int ring_next_slot(smt_group *g, int *slot_out);
+int ring_done_event(smt_group *g, int slot, int i, hipEvent_t *ev);
+bool peer_self_test(smt_group *g);
+// per-rank host lists of any length -> the first `keep` of their (distance, row) merge, per query
+int exchange_host_lists(smt_group *g, const std::vector<std::vector<LocalHits>> &local, uint32_t nq, uint64_t keep, std::vector<LocalHits> &merged);
+// IvfBuildShare::allreduce / ::agree for local rank `local` of g (user = a ShareCtx), called from that rank's host thread
+struct ShareCtx { smt_group *g; int local; };
+int group_allreduce_sums(void *user, long long *sums, size_t n_sums, unsigned int *counts, size_t n_counts);
+int group_share_agree(void *user, int rc);
+
+// The spread-waits hand-shake of one pipelined search (peer transport, smt_group::spread_waits).  Every merge that will want a
+// rank's list waits for it, enqueued off the caller's thread -- but never AHEAD of the merging device's own scan: a wait for rank
+// i's event that lands on device m's stream before m's issuer has put its scan and select there makes shard m's whole share queue
+// up behind shard i's (twice the latency, by timing).  So a wait is enqueued by whoever comes SECOND: rank i posts its
+// bit in awaiting[m] and then looks at issued[m]; if m's own work is on its stream already, i takes the bit back and, if it still
+// had it, enqueues the wait itself; m, once its own work is issued, raises issued[m] and enqueues the waits of every bit it finds.
+// Each bit is claimed exactly once (every access seq_cst).
+struct WaitBoard {
+    static constexpr int MAX_RANKS = 64;   // one bit per rank in a 64-bit mask: larger groups leave the waits to the caller's thread
+    smt_group *g;
+    const std::vector<char> &on_aux;       // [n_local] device m merges on its aux stream
+    const bool active;                     // false: every operation is a no-op and merge_ranks_on enqueues the waits
+    uint64_t merging = 0;                  // bit m: local device m wants the answer
+    WaitBoard(smt_group *g, const std::vector<char> &on_aux, uint64_t *const *out_packed);
+    int own_work_issued(int i);   // rank i's issuer: my own work is on my stream -- I enqueue the waits posted for me so far
+    int published(int i);         // rank i's issuer, behind peer_publish: post to every merging device, or enqueue where it has issued
+    int sweep();                  // the caller's thread, after every issuer: enqueue what is left
+private:
+    std::atomic<uint64_t> awaiting[MAX_RANKS];   // [m]: ranks whose list is published and whose wait on m's stream nobody has enqueued yet
+    std::atomic<int> issued[MAX_RANKS];          // [m]: m's own scan + select + publish are on its stream
+    int await_all(uint64_t ranks, int m);
+};
 
 // ---- row layout of a sharded corpus (sharded.cpp)
 void layout_set_contiguous(smt_sharded_corpus *sc, const std::vector<uint64_t> &rank_rows);

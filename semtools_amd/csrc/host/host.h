@@ -6,7 +6,7 @@
 //
 // Everything here runs on an smt_group -- the GPUs the one calling process owns (src/bin/semtools.rs:134-135 is one
 // synchronous task): the embedding table is replicated per GPU, every matrix of line embeddings is an
-// smt_sharded_corpus whose rows are dealt over the GPUs, searches end in the all-gather + merge of group.cpp.  The
+// smt_sharded_corpus whose rows are dealt over the GPUs, searches end in the all-gather + merge of group_exchange.cpp.  The
 // default group has ONE rank (smt_group_from_ctx), for which every smt_sharded_* call IS its single-GPU counterpart.
 //
 // The reference is Rust; no Rust toolchain exists here, so this C++ layer is

@@ -170,7 +170,7 @@ __global__ void ivf_finalize_kernel(const long long *sums, const unsigned int *c
     if (n) centroids[i] = (float)((double)sums[i] / FIXED_SCALE / (double)n);  // empty cluster keeps its centroid
 }
 
-// Shared-centroid builds (group.cpp): rank r seeds the lists l with l % n_ranks == r; every other list contributes
+// Shared-centroid builds (sharded_search.cpp): rank r seeds the lists l with l % n_ranks == r; every other list contributes
 // nothing, so the all-reduce of (sums, counts) followed by ivf_finalize_kernel gives every rank the same start.
 __global__ void ivf_seed_sums_kernel(const float *centroids, uint32_t nlist, uint32_t rank, uint32_t n_ranks, long long *sums,
                                      unsigned int *counts)

@@ -688,7 +688,7 @@ try {
 
 }  // extern "C"
 
-// one shard's answer in the packed exchange layout of group.cpp: [nq][2][top_k] words (global rows | f64 bits)
+// one shard's answer in the packed exchange layout of group_exchange.cpp: [nq][2][top_k] words (global rows | f64 bits)
 int smt::ivfpq_search_packed(smt_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
                              uint64_t row_base, uint64_t *packed_dev)
 {

@@ -1098,7 +1098,7 @@ __global__ void merge_topk_kernel(const uint64_t *rows, const double *dist, uint
 // The same merge over lists that are NOT gathered: list l starts at src.list[l] -- for a one-process group the exchange buffer of
 // rank l, read IN PLACE over xGMI (peer access) or on this device (logical ranks).  Nothing is copied between the ranks: the
 // exchange is this kernel's loads (n_lists x k_in x 16 B per query -- 1280 B at 8 ranks, k = 10: latency-bound), ordered
-// after the ranks' select kernels by one stream event per rank (group.cpp: peer transport).  The candidates are staged in LDS once
+// after the ranks' select kernels by one stream event per rank (group_exchange.cpp: peer transport).  The candidates are staged in LDS once
 // (16 B each, M <= 4096) so that the M x M rank computation never goes back over the links.
 __global__ void merge_topk_sources_kernel(MergeSources src, uint32_t n_lists, uint64_t query_stride, uint32_t k_in, uint32_t k_out,
                                           uint64_t *out_rows, double *out_dist, uint64_t out_query_stride)
@@ -1453,7 +1453,7 @@ int launch_merge_topk(smt_ctx *ctx, const uint64_t *rows, const double *dist, ui
     return SMT_OK;
 }
 
-// Packed lists [n_lists][nq][2][k_in] (list_stride_words apart: the exchange buffers of group.cpp carry a few status
+// Packed lists [n_lists][nq][2][k_in] (list_stride_words apart: the exchange buffers of group_exchange.cpp carry a few status
 // words behind each rank's lists; 0 = dense) -> out_packed [nq][2][k_out], on stream `st`.  n_lists == 0 writes padding.
 int launch_merge_topk_packed_on(smt_ctx *ctx, hipStream_t st, const uint64_t *packed, uint32_t n_lists, uint32_t nq, uint32_t k_in,
                                 uint32_t k_out, uint64_t *out_packed, uint64_t list_stride_words)

@@ -768,7 +768,7 @@ static int search_local_host_impl(smt_corpus *corpus, const float *queries, uint
     return k_eff > SCAN_MAX_K ? search_topk_large(call, out) : search_topk_small(call, out);
 }
 
-// The body of smt_search with per-query result vectors instead of caller arrays: group.cpp runs it once per
+// The body of smt_search with per-query result vectors instead of caller arrays: sharded_search.cpp runs it once per
 // local shard (threshold mode / top_k > 64, whose result sizes are not known up front) and exchanges the lists.
 // Store::search_line_embeddings with a ZERO query vector (an empty query, or one made of unknown tokens only: model2vec pools it to
 // zeros).  qdrant's cosine_preprocess leaves a vector with |x|^2 < f32::EPSILON as it is, so the query scores 0 against EVERY point --
@@ -830,7 +830,7 @@ int deliver_hits(const std::vector<LocalHits> &hits, uint64_t *out_rows, double 
     return SMT_OK;
 }
 
-// One shard's top-k with everything on the device (the exchange path of group.cpp).  queries_dev [nq x 256];
+// One shard's top-k with everything on the device (the exchange path of sharded_search.cpp).  queries_dev [nq x 256];
 // ranges_local = sorted, disjoint LOCAL row ranges (host array); filtered && n_ranges == 0 means "the filter
 // leaves this shard nothing to scan".  packed_dev [nq][2][k_pad] receives global rows, then f64 distance bit
 // patterns, padded with (UINT64_MAX, +inf).  1 <= k_pad <= LARGEK_MAX_K (above SCAN_MAX_K: topk_large.hip).  Enqueued on the context's stream (the

@@ -1,6 +1,6 @@
 """Multi-GPU glue for Python hosts: one process per GPU (torchrun), corpus row-sharded, ONE exchange step.
 
-The exchange lives INSIDE libsemtools_hip.so (csrc/group.cpp: smt_group_* / smt_sharded_*: per-shard scan -> ncclAllGather of the
+The exchange lives INSIDE libsemtools_hip.so (csrc/group.cpp, group_exchange.cpp, sharded_search.cpp: smt_group_* / smt_sharded_*: per-shard scan -> ncclAllGather of the
 packed k-lists -> merge_topk_kernel); this module only joins the ranks of a torch.distributed job into one library group (rank 0's
 ncclUniqueId travels through torch's store).  core.ShardedCorpus / core.ShardedIvfPq / core.ShardedModel hand the work to that
 group.  (The torch-tensor restatement of the exchange that rounds 1-3 kept here for the gloo tests is tests/dist_protocol.py now.)

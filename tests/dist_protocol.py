@@ -1,6 +1,6 @@
 """The exchange step of the N > 1 path restated over torch.distributed CPU tensors ("gloo"): TEST INFRASTRUCTURE.
 
-On GPUs the exchange lives inside libsemtools_hip.so (csrc/group.cpp: per-shard scan -> ncclAllGather of the packed k-lists ->
+On GPUs the exchange lives inside libsemtools_hip.so (csrc/sharded_search.cpp, group_exchange.cpp: per-shard scan -> ncclAllGather of the packed k-lists ->
 merge_topk_kernel; threshold mode: counts, then one padded gather).  A box without GPUs cannot run that; what it CAN run is the
 protocol -- padding, packed [nq][2][k] layout, threshold mode's count-then-padded-gather, the (distance, global row) merge -- over
 gloo with world_size 2, with the CPU oracle standing in for the per-shard scan (tests/test_dist_cpu.py).  Until round 4 this lived
@@ -31,7 +31,7 @@ def allgather_merge_packed(local_packed, k_out, ctx=None, group=None, gathered=N
     else:
         g[0].copy_(local_packed)
     o = out if out is not None else torch.empty((nq, 2, k_out), dtype=torch.int64, device=local_packed.device)
-    assert not local_packed.is_cuda, "CPU protocol model: the device exchange is the library's (csrc/group.cpp)"
+    assert not local_packed.is_cuda, "CPU protocol model: the device exchange is the library's (csrc/group_exchange.cpp)"
     rows_u = np.ascontiguousarray(g[:, :, 0, :].numpy()).view(np.uint64)
     dd = np.ascontiguousarray(g[:, :, 1, :].numpy()).view(np.float64)
     mr, md, _ = core.merge_topk(rows_u, dd, k_out)
@@ -60,7 +60,7 @@ def allgather_merge_topk(local_rows, local_dist, k_out, ctx=None, group=None, ga
     else:
         g_rows[0].copy_(local_rows)
         g_dist[0].copy_(local_dist)
-    assert not local_rows.is_cuda, "CPU protocol model: the device exchange is the library's (csrc/group.cpp)"
+    assert not local_rows.is_cuda, "CPU protocol model: the device exchange is the library's (csrc/group_exchange.cpp)"
     rows_u = g_rows.numpy().view(np.uint64)
     mr, md, _ = core.merge_topk(rows_u, g_dist.numpy(), k_out)
     return torch.from_numpy(mr.view(np.int64)), torch.from_numpy(md)

@@ -1,7 +1,7 @@
 // fake_rccl.cpp -- TEST INFRASTRUCTURE: a test double for librccl.so.1 that lets N processes form one communicator ON ONE GPU.
 //
 // Why: RCCL refuses two ranks on one device, and the GPU boxes the tests run on have one.  The product's one-rank-per-process
-// group (semtools_amd/csrc/group.cpp: smt_group_create_rank -> ncclCommInitRank, allgather_words, group_agree, group_barrier,
+// group (semtools_amd/csrc/group.cpp, group_exchange.cpp: smt_group_create_rank -> ncclCommInitRank, allgather_words, group_agree, group_barrier,
 // exchange_host_lists, the shared-centroid ncclAllReduce) would otherwise never execute with n_ranks > 1 before a real 8-GPU
 // node runs it.  The library binds RCCL with dlopen("librccl.so.1", RTLD_NOLOAD) first (group.cpp load_rccl), so an object with
 // that SONAME already mapped into the process -- LD_PRELOAD, or ctypes.CDLL(..., RTLD_GLOBAL) before the first group -- takes

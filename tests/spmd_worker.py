@@ -1,6 +1,6 @@
 """ONE RANK of an n-rank, one-rank-per-process smt_group, all ranks on GPU 0 -- TEST INFRASTRUCTURE (tests/test_gpu_spmd.py spawns n of these).
 
-This is the process model a torchrun / MPI driver uses (semtools_amd/csrc/group.cpp: smt_group_unique_id on rank 0, the 128 bytes
+This is the process model a torchrun / MPI driver uses (semtools_amd/csrc/group.cpp, sharded_search.cpp: smt_group_unique_id on rank 0, the 128 bytes
 travel by any means -- a file here --, smt_group_create_rank -> ncclCommInitRank, then SPMD calls).  RCCL refuses two ranks on one
 device, so the communicator is tests/fake_rccl's double, mapped into the process BEFORE the library looks for "librccl.so.1"
 (load_rccl tries RTLD_NOLOAD first: the product is unchanged).  Every rank runs the same scenarios on the same host arguments and

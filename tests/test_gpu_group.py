@@ -265,6 +265,33 @@ def test_back_to_back_exchanges_keep_their_answers_apart(plain, transport):
     sc.close(); g.close()
 
 
+@pytest.mark.parametrize("transport", ["peer", "copy"])
+def test_injected_failures_in_a_one_process_group(plain, transport):
+    """smt_debug_group_fail_next on a group whose ranks all live in this process: the per-rank statuses of the stage, of the status
+    agreement in front of the host-list exchange and of a shared-centroid index build are collected on the caller's thread.  Each
+    armed call raises exactly the injected code with the hook's message; the next call on the same group is exact again."""
+    import semtools_amd as smt
+    from semtools_amd import _lib as L
+
+    emb, c = plain
+    g = smt.Group.logical(0, 3)
+    g.set_transport(transport)
+    sc = smt.ShardedCorpus(g, rows=emb)
+    qs = synth.unit_query(4, nq=3)
+    build = lambda: smt.ShardedIvfPq(sc, nlist=32, train_iters=3, shared_centroids=True).close()
+    for where, call, after in ((1, lambda: sc.search(qs, top_k=5), dict(top_k=5)),          # SMT_DEBUG_FAIL_STAGE
+                               (2, lambda: sc.search(qs, top_k=100), dict(top_k=100)),      # SMT_DEBUG_FAIL_AGREE: the host-list route
+                               (3, build, dict(top_k=5))):                                  # SMT_DEBUG_FAIL_BUILD
+        g.debug_fail_next(where, L.SMT_E_NOMEM)
+        with pytest.raises(smt.SmtError) as e:
+            call()
+        assert e.value.code == L.SMT_E_NOMEM, (where, str(e.value))
+        assert "injected failure (smt_debug_group_fail_next, kind %d)" % where in str(e.value), str(e.value)
+        _same(sc.search(qs, **after), c.search(qs, **after))
+    build()                                                     # (and the build itself goes through un-armed)
+    sc.close(); g.close()
+
+
 def test_adopted_device_shards_of_unequal_size(plain):
     import torch
     import semtools_amd as smt

@@ -2,7 +2,7 @@
 runs under torch.distributed.run) -- executed on one GPU against a test double for RCCL (tests/fake_rccl, mapped before the library
 looks for librccl.so.1: no product change).
 
-What runs here that no logical-shard test reaches (semtools_amd/csrc/group.cpp): smt_group_create_rank -> ncclCommInitRank with
+What runs here that no logical-shard test reaches (semtools_amd/csrc/group.cpp, group_exchange.cpp, sharded_search.cpp): smt_group_create_rank -> ncclCommInitRank with
 n > 1, group_barrier, the packed k-list ncclAllGather + merge on every rank, the per-rank status words that make all ranks return
 an error together, group_agree, exchange_host_lists' count + padded all-gathers (threshold mode, k > 56), the shared-centroid
 ncclAllReduce, the per-rank streaming of save / load, dealt appends and the sharded embed with ranks in different processes.
