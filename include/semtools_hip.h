@@ -120,6 +120,24 @@ int smt_model_create_from_device(smt_ctx *ctx, const float *table_dev, uint64_t 
                                  int normalize, smt_model **out);
 void smt_model_destroy(smt_model *model);
 
+/* Typed tables.  StaticModel::from_pretrained accepts an `embeddings` tensor of dtype F32, F16 or I8; the three creators below
+ * take the table AS STORED -- nothing is widened on the host or in HBM, a half table occupies V x 512 bytes and an int8 table
+ * V x 256 -- and K1 widens the rows in registers (half -> f32 and i8 as f32 are exact, I8 has no scale, as in model2vec-rs), so
+ * every output row is bit-identical to that of an f32 model built from the widened table.  The three creators above are the
+ * SMT_TABLE_F32 case of these.  An unknown dtype is SMT_E_INVALID; table_dev must be 16-byte aligned, else SMT_E_INVALID.
+ * smt_embed / smt_embed_device are unchanged: the model carries its type. */
+#define SMT_TABLE_F32 0 /* float, 1024-byte rows           */
+#define SMT_TABLE_F16 1 /* IEEE binary16, 512-byte rows    */
+#define SMT_TABLE_I8 2  /* signed 8-bit, 256-byte rows     */
+int smt_model_create_typed(smt_ctx *ctx, const void *table_host, int table_dtype, uint64_t V, uint32_t D,
+                           int normalize, smt_model **out);
+int smt_model_create_from_file_typed(smt_ctx *ctx, const char *path, uint64_t byte_offset, int table_dtype, uint64_t V,
+                                     uint32_t D, int normalize, smt_model **out);
+int smt_model_create_from_device_typed(smt_ctx *ctx, const void *table_dev, int table_dtype, uint64_t V, uint32_t D,
+                                       int normalize, smt_model **out);
+/* what the model holds: its SMT_TABLE_* kind, row count and the bytes of the table in device memory; any out may be NULL */
+int smt_model_info(const smt_model *model, int *table_dtype, uint64_t *V, uint64_t *table_bytes);
+
 /* Replaces the pool step of StaticModel::encode_with_args / encode_single
  * (call sites src/search/mod.rs:69,138,153; src/cmds/search.rs:136,154).
  * Tokenisation stays on the host: `ids` are the unk-filtered token ids of all
@@ -450,6 +468,13 @@ typedef struct smt_sharded_model smt_sharded_model;
 int smt_sharded_model_create(smt_group *group, const float *table_host, uint64_t V, uint32_t D, int normalize, smt_sharded_model **out);
 int smt_sharded_model_create_from_file(smt_group *group, const char *path, uint64_t byte_offset, uint64_t V, uint32_t D,
                                        int normalize, smt_sharded_model **out);
+/* the same over a table of SMT_TABLE_F32 / F16 / I8 as stored (smt_model_create_typed): one typed replica per local device */
+int smt_sharded_model_create_typed(smt_group *group, const void *table_host, int table_dtype, uint64_t V, uint32_t D, int normalize,
+                                   smt_sharded_model **out);
+int smt_sharded_model_create_from_file_typed(smt_group *group, const char *path, uint64_t byte_offset, int table_dtype, uint64_t V,
+                                             uint32_t D, int normalize, smt_sharded_model **out);
+/* smt_model_info of the replicas (they are alike): table_bytes is what ONE replica holds in device memory */
+int smt_sharded_model_info(const smt_sharded_model *model, int *table_dtype, uint64_t *V, uint64_t *table_bytes);
 void smt_sharded_model_destroy(smt_sharded_model *model);
 int smt_sharded_embed(smt_sharded_model *model, const uint32_t *ids, const uint64_t *offsets, uint64_t n_lines, uint32_t max_tokens,
                       float *out_host, smt_sharded_corpus *append_to, uint64_t *first_row);

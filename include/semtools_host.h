@@ -43,6 +43,10 @@ int smt_host_model_create(smt_ctx *ctx, const float *table, uint64_t V, int norm
                           uint32_t unk_id, uint32_t median_len, smt_host_model **out);
 /* directory with model.safetensors ("embeddings", F32 or F16), vocab.txt, optional config.json */
 int smt_host_model_from_dir(smt_ctx *ctx, const char *dir, smt_host_model **out);
+/* The model's embedding table as the device holds it: its SMT_TABLE_* kind (F16 and I8 tables of a model directory stay as stored),
+ * rows, and bytes per replica.  *resident = 0 while a directory-backed model has not uploaded the whole table yet (it serves small
+ * calls from compact tables of the rows they touch); the figures then describe the table in the file.  Any out may be NULL. */
+int smt_host_model_table_info(const smt_host_model *model, int *table_dtype, uint64_t *V, uint64_t *table_bytes, int *resident);
 void smt_host_model_destroy(smt_host_model *model);
 
 /* encode_with_args(texts, Some(max_length) / None when 0, batch 16384) -> out [n x 256] */

@@ -40,6 +40,9 @@ pub const SMT_E_UNSUPPORTED: c_int = -6;
 pub const SMT_DIM: u32 = 256;
 pub const SMT_MODE_DOCUMENTS: c_int = 0;
 pub const SMT_MODE_WORKSPACE: c_int = 1;
+pub const SMT_TABLE_F32: c_int = 0;
+pub const SMT_TABLE_F16: c_int = 1;
+pub const SMT_TABLE_I8: c_int = 2;
 pub const SMT_STATUS_PROVED: c_int = 0;
 pub const SMT_STATUS_UNCERTAIN: c_int = 1;
 pub const SMT_STATUS_OVERFLOW: c_int = 2;
@@ -91,6 +94,40 @@ extern "C" {
         out: *mut *mut SmtModel,
     ) -> c_int;
     pub fn smt_model_destroy(model: *mut SmtModel);
+    pub fn smt_model_create_typed(
+        ctx: *mut SmtCtx,
+        table_host: *const c_void,
+        table_dtype: c_int,
+        V: u64,
+        D: u32,
+        normalize: c_int,
+        out: *mut *mut SmtModel,
+    ) -> c_int;
+    pub fn smt_model_create_from_file_typed(
+        ctx: *mut SmtCtx,
+        path: *const c_char,
+        byte_offset: u64,
+        table_dtype: c_int,
+        V: u64,
+        D: u32,
+        normalize: c_int,
+        out: *mut *mut SmtModel,
+    ) -> c_int;
+    pub fn smt_model_create_from_device_typed(
+        ctx: *mut SmtCtx,
+        table_dev: *const c_void,
+        table_dtype: c_int,
+        V: u64,
+        D: u32,
+        normalize: c_int,
+        out: *mut *mut SmtModel,
+    ) -> c_int;
+    pub fn smt_model_info(
+        model: *const SmtModel,
+        table_dtype: *mut c_int,
+        V: *mut u64,
+        table_bytes: *mut u64,
+    ) -> c_int;
     pub fn smt_embed(
         model: *mut SmtModel,
         ids: *const u32,
@@ -368,6 +405,31 @@ extern "C" {
         D: u32,
         normalize: c_int,
         out: *mut *mut SmtShardedModel,
+    ) -> c_int;
+    pub fn smt_sharded_model_create_typed(
+        group: *mut SmtGroup,
+        table_host: *const c_void,
+        table_dtype: c_int,
+        V: u64,
+        D: u32,
+        normalize: c_int,
+        out: *mut *mut SmtShardedModel,
+    ) -> c_int;
+    pub fn smt_sharded_model_create_from_file_typed(
+        group: *mut SmtGroup,
+        path: *const c_char,
+        byte_offset: u64,
+        table_dtype: c_int,
+        V: u64,
+        D: u32,
+        normalize: c_int,
+        out: *mut *mut SmtShardedModel,
+    ) -> c_int;
+    pub fn smt_sharded_model_info(
+        model: *const SmtShardedModel,
+        table_dtype: *mut c_int,
+        V: *mut u64,
+        table_bytes: *mut u64,
     ) -> c_int;
     pub fn smt_sharded_model_destroy(model: *mut SmtShardedModel);
     pub fn smt_sharded_embed(

@@ -41,7 +41,21 @@ EXPORTS = [
     "smt_group_set_transport", "smt_group_transport", "smt_debug_range_sets", "smt_sharded_corpus_append_to_file_ex",
     "smt_debug_group_fail_next", "smt_search_topk_device_ex", "smt_sharded_search_topk_device_ex", "smt_debug_deliveries",
     "smt_corpus_compact", "smt_ctx_compact_stats", "smt_sharded_corpus_compact",
+    "smt_model_create_typed", "smt_model_create_from_file_typed", "smt_model_create_from_device_typed", "smt_model_info",
+    "smt_sharded_model_create_typed", "smt_sharded_model_create_from_file_typed", "smt_sharded_model_info",
 ]
+TABLE_F32, TABLE_F16, TABLE_I8 = 0, 1, 2
+TABLE_DTYPES = {np.dtype(np.float32): TABLE_F32, np.dtype(np.float16): TABLE_F16, np.dtype(np.int8): TABLE_I8}
+TABLE_NP = {v: k for k, v in TABLE_DTYPES.items()}
+
+
+def table_dtype_code(dtype):
+    """SMT_TABLE_* of a numpy dtype; a table of any other dtype is an error (nothing is converted silently)."""
+    try:
+        return TABLE_DTYPES[np.dtype(dtype)]
+    except (KeyError, TypeError):
+        raise TypeError(f"embedding table dtype {dtype!r} is not supported: the table must be float32, float16 or int8") from None
+
 STATUS_PROVED, STATUS_UNCERTAIN, STATUS_OVERFLOW, STATUS_INVALID_QUERY = 0, 1, 2, 3
 TRANSPORT_RCCL, TRANSPORT_COPY, TRANSPORT_PEER = 0, 1, 2
 TRANSPORT_NAMES = {TRANSPORT_RCCL: "rccl", TRANSPORT_COPY: "copy", TRANSPORT_PEER: "peer"}
@@ -55,6 +69,7 @@ HOST_EXPORTS = [
     "smt_host_split_lines", "smt_host_to_lowercase",
     "smt_host_group_from_spec", "smt_host_model_create_group", "smt_host_model_from_dir_group",
     "smt_host_workspace_use_group", "smt_host_workspace_status_group", "smt_host_workspace_prune_group",
+    "smt_host_model_table_info",
 ]
 TOKENIZE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
                           C.POINTER(C.c_uint64))
@@ -123,6 +138,10 @@ def lib():
     L.smt_model_create.argtypes = [vp, vp, u64, u32, i32, P(vp)]
     L.smt_model_create_from_file.argtypes = [vp, C.c_char_p, u64, u64, u32, i32, P(vp)]
     L.smt_model_create_from_device.argtypes = [vp, vp, u64, u32, i32, P(vp)]
+    L.smt_model_create_typed.argtypes = [vp, vp, i32, u64, u32, i32, P(vp)]
+    L.smt_model_create_from_file_typed.argtypes = [vp, C.c_char_p, u64, i32, u64, u32, i32, P(vp)]
+    L.smt_model_create_from_device_typed.argtypes = [vp, vp, i32, u64, u32, i32, P(vp)]
+    L.smt_model_info.argtypes = [vp, P(i32), P(u64), P(u64)]
     L.smt_model_destroy.argtypes = [vp]
     L.smt_model_destroy.restype = None
     L.smt_embed.argtypes = [vp, vp, vp, u64, u32, vp, vp, P(u64)]
@@ -228,6 +247,9 @@ def lib():
     L.smt_sharded_corpus_compact.argtypes = [vp, vp, u32, P(u64)]
     L.smt_sharded_model_create.argtypes = [vp, vp, u64, u32, i32, P(vp)]
     L.smt_sharded_model_create_from_file.argtypes = [vp, C.c_char_p, u64, u64, u32, i32, P(vp)]
+    L.smt_sharded_model_create_typed.argtypes = [vp, vp, i32, u64, u32, i32, P(vp)]
+    L.smt_sharded_model_create_from_file_typed.argtypes = [vp, C.c_char_p, u64, i32, u64, u32, i32, P(vp)]
+    L.smt_sharded_model_info.argtypes = [vp, P(i32), P(u64), P(u64)]
     L.smt_sharded_model_destroy.argtypes = [vp]
     L.smt_sharded_model_destroy.restype = None
     L.smt_sharded_embed.argtypes = [vp, vp, vp, u64, u32, vp, vp, P(u64)]
@@ -245,6 +267,7 @@ def lib():
     L.smt_host_workspace_prune_group.argtypes = [vp, C.c_char_p, i32, P(vp)]
     L.smt_host_model_create.argtypes = [vp, vp, u64, i32, i32, C.c_char_p, C.c_char_p, TOKENIZE_CB, vp, u32, u32, P(vp)]
     L.smt_host_model_from_dir.argtypes = [vp, C.c_char_p, P(vp)]
+    L.smt_host_model_table_info.argtypes = [vp, P(i32), P(u64), P(u64), P(i32)]
     L.smt_host_model_destroy.argtypes = [vp]
     L.smt_host_model_destroy.restype = None
     L.smt_host_encode.argtypes = [vp, cpp, u64, u32, vp]

@@ -15,6 +15,15 @@ def _f32c(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _table(a):
+    """An embedding table as the library takes it: a C-contiguous float32, float16 or int8 array, kept in its own dtype.
+    Anything that is not a numpy array (a list of rows) becomes float32; an array of another dtype is an error."""
+    if not isinstance(a, np.ndarray):
+        return _f32c(a)
+    L.table_dtype_code(a.dtype)
+    return np.ascontiguousarray(a)
+
+
 class Context:
     """One GPU + one HIP stream (smt_ctx).
 
@@ -100,19 +109,46 @@ class Context:
 class Model:
     """Device-resident model2vec table (smt_model)."""
 
-    def __init__(self, ctx, table=None, normalize=True, device_ptr=None, V=None):
+    def __init__(self, ctx, table=None, normalize=True, device_ptr=None, V=None, dtype=np.float32):
+        """table: a float32, float16 or int8 array [V x 256], uploaded as it is (K1 widens narrow rows in registers).
+        device_ptr / V / dtype: adopt a table of that dtype already in device memory."""
         self.ctx = ctx
         self._h = C.c_void_p()
         if device_ptr is not None:
-            L.check(L.lib().smt_model_create_from_device(ctx._h, C.c_void_p(device_ptr), int(V), L.DIM,
-                                                         int(normalize), C.byref(self._h)))
+            L.check(L.lib().smt_model_create_from_device_typed(ctx._h, C.c_void_p(device_ptr), L.table_dtype_code(dtype), int(V), L.DIM,
+                                                               int(normalize), C.byref(self._h)))
             self.V = int(V)
         else:
-            table = _f32c(table)
+            table = _table(table)
             assert table.ndim == 2
-            L.check(L.lib().smt_model_create(ctx._h, L.np_ptr(table), table.shape[0], table.shape[1],
-                                             int(normalize), C.byref(self._h)))
+            L.check(L.lib().smt_model_create_typed(ctx._h, L.np_ptr(table), L.table_dtype_code(table.dtype), table.shape[0],
+                                                   table.shape[1], int(normalize), C.byref(self._h)))
             self.V = table.shape[0]
+
+    @classmethod
+    def from_file(cls, ctx, path, byte_offset, V, normalize=True, dtype=np.float32):
+        """Stream a table [V x 256] of `dtype` that sits at `byte_offset` of a file into device memory as stored."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        L.check(L.lib().smt_model_create_from_file_typed(ctx._h, str(path).encode(), int(byte_offset), L.table_dtype_code(dtype), int(V),
+                                                         L.DIM, int(normalize), C.byref(self._h)))
+        self.V = int(V)
+        return self
+
+    def _info(self):
+        dt, v, nbytes = C.c_int(), C.c_uint64(), C.c_uint64()
+        L.check(L.lib().smt_model_info(self._h, C.byref(dt), C.byref(v), C.byref(nbytes)))
+        return int(dt.value), int(v.value), int(nbytes.value)
+
+    @property
+    def table_dtype(self):
+        """numpy dtype of the table in device memory"""
+        return L.TABLE_NP[self._info()[0]]
+
+    @property
+    def table_bytes(self):
+        return self._info()[2]
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -477,9 +513,17 @@ class ShardedModel:
     def __init__(self, group, table, normalize=True):
         self.group = group
         self._h = C.c_void_p()
-        table = _f32c(table).reshape(-1, L.DIM)
+        table = _table(table).reshape(-1, L.DIM)
         self.V = table.shape[0]
-        L.check(L.lib().smt_sharded_model_create(group._h, L.np_ptr(table), self.V, L.DIM, int(normalize), C.byref(self._h)))
+        L.check(L.lib().smt_sharded_model_create_typed(group._h, L.np_ptr(table), L.table_dtype_code(table.dtype), self.V, L.DIM,
+                                                       int(normalize), C.byref(self._h)))
+
+    @property
+    def table_bytes(self):
+        """bytes of the table in device memory, per replica"""
+        nbytes = C.c_uint64()
+        L.check(L.lib().smt_sharded_model_info(self._h, None, None, C.byref(nbytes)))
+        return int(nbytes.value)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

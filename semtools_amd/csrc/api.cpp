@@ -559,21 +559,27 @@ try {
 
 /* ---------------------------------------------------------------- model ---- */
 
-int smt_model_create(smt_ctx *ctx, const float *table_host, uint64_t V, uint32_t D, int normalize,
-                     smt_model **out)
+#define SMT_REQUIRE_DTYPE(dt)                                                                                                   \
+    do {                                                                                                                        \
+        if (smt::table_elem_bytes(dt) == 0) { set_error("unknown table dtype %d (SMT_TABLE_F32, SMT_TABLE_F16, SMT_TABLE_I8)", (int)(dt)); return SMT_E_INVALID; } \
+    } while (0)
+
+int smt_model_create_typed(smt_ctx *ctx, const void *table_host, int table_dtype, uint64_t V, uint32_t D, int normalize,
+                           smt_model **out)
 try {
     int rc = check_ctx(ctx);
     if (rc) return rc;
     SMT_REQUIRE(out && table_host, "null argument");
     *out = nullptr;
+    SMT_REQUIRE_DTYPE(table_dtype);
     if (D != SMT_DIM) { set_error("embedding dim %u unsupported (kernels are specialised for 256)", D); return SMT_E_UNSUPPORTED; }
     SMT_REQUIRE(V > 0, "empty table");
     if ((rc = bind_device(ctx))) return rc;
     smt_model *m = new (std::nothrow) smt_model();
     if (!m) { set_error("out of host memory"); return SMT_E_NOMEM; }
-    m->ctx = ctx; m->V = V; m->D = D; m->normalize = normalize ? 1 : 0; m->owned = true;
-    const size_t bytes = (size_t)V * D * sizeof(float);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&m->d_table), bytes);
+    m->ctx = ctx; m->V = V; m->D = D; m->normalize = normalize ? 1 : 0; m->owned = true; m->table_dtype = table_dtype;
+    const size_t bytes = (size_t)V * D * smt::table_elem_bytes(table_dtype);
+    hipError_t e = hipMalloc(&m->d_table, bytes);
     if (e != hipSuccess) { delete m; set_error("hipMalloc(%zu) for the embedding table: %s", bytes, hipGetErrorString(e)); return SMT_E_NOMEM; }
     e = hipMemcpyAsync(m->d_table, table_host, bytes, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -582,20 +588,44 @@ try {
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
-int smt_model_create_from_device(smt_ctx *ctx, const float *table_dev, uint64_t V, uint32_t D,
-                                 int normalize, smt_model **out)
+int smt_model_create(smt_ctx *ctx, const float *table_host, uint64_t V, uint32_t D, int normalize,
+                     smt_model **out)
+try {
+    return smt_model_create_typed(ctx, table_host, SMT_TABLE_F32, V, D, normalize, out);
+} catch (...) { return smt::api_catch(); }
+
+int smt_model_create_from_device_typed(smt_ctx *ctx, const void *table_dev, int table_dtype, uint64_t V, uint32_t D,
+                                       int normalize, smt_model **out)
 try {
     int rc = check_ctx(ctx);
     if (rc) return rc;
     SMT_REQUIRE(out && table_dev, "null argument");
     *out = nullptr;
+    SMT_REQUIRE_DTYPE(table_dtype);
     if (D != SMT_DIM) { set_error("embedding dim %u unsupported", D); return SMT_E_UNSUPPORTED; }
+    // K1 reads rows with 16-byte lane loads
+    if (reinterpret_cast<uintptr_t>(table_dev) % 16 != 0) { set_error("the device table must be 16-byte aligned"); return SMT_E_INVALID; }
     smt_model *m = new (std::nothrow) smt_model();
     if (!m) { set_error("out of host memory"); return SMT_E_NOMEM; }
-    m->ctx = ctx; m->V = V; m->D = D; m->normalize = normalize ? 1 : 0;
-    m->d_table = const_cast<float *>(table_dev);
+    m->ctx = ctx; m->V = V; m->D = D; m->normalize = normalize ? 1 : 0; m->table_dtype = table_dtype;
+    m->d_table = const_cast<void *>(table_dev);
     m->owned = false;
     *out = m;
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_model_create_from_device(smt_ctx *ctx, const float *table_dev, uint64_t V, uint32_t D,
+                                 int normalize, smt_model **out)
+try {
+    return smt_model_create_from_device_typed(ctx, table_dev, SMT_TABLE_F32, V, D, normalize, out);
+} catch (...) { return smt::api_catch(); }
+
+int smt_model_info(const smt_model *model, int *table_dtype, uint64_t *V, uint64_t *table_bytes)
+try {
+    SMT_REQUIRE(model != nullptr, "model");
+    if (table_dtype) *table_dtype = model->table_dtype;
+    if (V) *V = model->V;
+    if (table_bytes) *table_bytes = model->V * model->D * smt::table_elem_bytes(model->table_dtype);
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
@@ -776,7 +806,7 @@ try {
     SMT_REQUIRE(n_lines == 0 || (offsets_dev && out_dev), "null argument");
     int rc = bind_device(model->ctx);
     if (rc) return rc;
-    return launch_embed(model->ctx, model->d_table, model->V, model->normalize, ids_dev, offsets_dev, n_lines,
+    return launch_embed(model->ctx, model->d_table, model->table_dtype, model->V, model->normalize, ids_dev, offsets_dev, n_lines,
                         max_tokens, out_dev, 0);
 } catch (...) { return smt::api_catch(); }
 
@@ -822,7 +852,7 @@ try {
         if ((rc = corpus_reserve(append_to, append_to->rows + n_lines))) return rc;
         d_out = append_to->d_rows + (size_t)append_to->rows * append_to->dim;
     }
-    rc = launch_embed(ctx, model->d_table, model->V, model->normalize, d_ids, d_off, n_lines, max_tokens, d_out,
+    rc = launch_embed(ctx, model->d_table, model->table_dtype, model->V, model->normalize, d_ids, d_off, n_lines, max_tokens, d_out,
                       std::max<uint64_t>(n_ids, 1));
     if (rc) return rc;
     if (out_host)

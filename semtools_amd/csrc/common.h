@@ -198,7 +198,8 @@ struct smt_corpus {
 
 struct smt_model {
     smt_ctx *ctx = nullptr;
-    float *d_table = nullptr;
+    void *d_table = nullptr;       // [V x 256] elements of table_dtype, as stored
+    int table_dtype = SMT_TABLE_F32;
     uint64_t V = 0;
     uint32_t D = 0;
     int normalize = 1;
@@ -207,6 +208,11 @@ struct smt_model {
 
 namespace smt {
 
+// bytes of one table element, 0 for an unknown SMT_TABLE_* kind
+inline size_t table_elem_bytes(int table_dtype)
+{
+    return table_dtype == SMT_TABLE_F32 ? 4 : table_dtype == SMT_TABLE_F16 ? 2 : table_dtype == SMT_TABLE_I8 ? 1 : 0;
+}
 int check_ctx(const smt_ctx *ctx);
 int bind_device(smt_ctx *ctx, bool drain = true);   // hipSetDevice + (drain) wait for async selects
 // The handler of every int-returning extern "C" entry point (each is a function-try-block): a C++ exception -- bad_alloc from a host
@@ -489,7 +495,7 @@ int64_t first_outside_domain_host(const float *v, uint64_t n, uint32_t dim);
 int require_queries_domain_host(const float *queries, uint32_t nq, const char *what);
 
 // K1
-int launch_embed(smt_ctx *ctx, const float *table, uint64_t V, int normalize, const uint32_t *ids,
+int launch_embed(smt_ctx *ctx, const void *table, int table_dtype, uint64_t V, int normalize, const uint32_t *ids,
                  const uint64_t *offsets, uint64_t n_lines, uint32_t max_tokens, float *out,
                  uint64_t n_tokens_known /* total tokens of the batch when the host has the offsets, else 0 */);
 

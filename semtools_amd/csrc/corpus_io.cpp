@@ -514,13 +514,15 @@ try {
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
-int smt_model_create_from_file(smt_ctx *ctx, const char *path, uint64_t byte_offset, uint64_t V, uint32_t D, int normalize,
-                               smt_model **out)
+int smt_model_create_from_file_typed(smt_ctx *ctx, const char *path, uint64_t byte_offset, int table_dtype, uint64_t V, uint32_t D,
+                                     int normalize, smt_model **out)
 try {
     int rc = check_ctx(ctx);
     if (rc) return rc;
     SMT_REQUIRE(out && path, "null argument");
     *out = nullptr;
+    const size_t elem = smt::table_elem_bytes(table_dtype);
+    if (elem == 0) { set_error("unknown table dtype %d (SMT_TABLE_F32, SMT_TABLE_F16, SMT_TABLE_I8)", table_dtype); return SMT_E_INVALID; }
     if (D != SMT_DIM) { set_error("embedding dim %u unsupported (kernels are specialised for 256)", D); return SMT_E_UNSUPPORTED; }
     SMT_REQUIRE(V > 0, "empty table");
     if ((rc = bind_device(ctx))) return rc;
@@ -528,9 +530,9 @@ try {
     if (!f) { set_error("cannot open '%s': %s", path, strerror(errno)); return SMT_E_IO; }
     smt_model *m = new (std::nothrow) smt_model();
     if (!m) { fclose(f); set_error("out of host memory"); return SMT_E_NOMEM; }
-    m->ctx = ctx; m->V = V; m->D = D; m->normalize = normalize ? 1 : 0; m->owned = true;
-    const size_t row_bytes = (size_t)D * sizeof(float);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&m->d_table), (size_t)V * row_bytes);
+    m->ctx = ctx; m->V = V; m->D = D; m->normalize = normalize ? 1 : 0; m->owned = true; m->table_dtype = table_dtype;
+    const size_t row_bytes = (size_t)D * elem;   // the stored bytes go to HBM as they are: K1 widens in registers
+    hipError_t e = hipMalloc(&m->d_table, (size_t)V * row_bytes);
     if (e != hipSuccess) { fclose(f); delete m; set_error("hipMalloc for the embedding table: %s", hipGetErrorString(e)); return SMT_E_NOMEM; }
     auto bail = [&](int code) { fclose(f); (void)hipStreamSynchronize(ctx->stream); (void)hipFree(m->d_table); delete m; return code; };
     const size_t chunk = io_chunk_rows(V);
@@ -544,7 +546,7 @@ try {
             if (io < 0) set_error("'%s' is truncated", path); else set_error("reading '%s': %s", path, strerror(io));
             return bail(SMT_E_IO);
         }
-        e = hipMemcpyAsync(m->d_table + (size_t)r * D, pp.buf[j], n * row_bytes, hipMemcpyHostToDevice, ctx->stream);
+        e = hipMemcpyAsync(static_cast<char *>(m->d_table) + (size_t)r * row_bytes, pp.buf[j], n * row_bytes, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(pp.ev[j], ctx->stream);
         if (e != hipSuccess) { set_error("table upload: %s", hipGetErrorString(e)); return bail(SMT_E_HIP); }
         pp.busy[j] = true;
@@ -555,6 +557,12 @@ try {
     if (e != hipSuccess) { (void)hipFree(m->d_table); delete m; set_error("table upload: %s", hipGetErrorString(e)); return SMT_E_HIP; }
     *out = m;
     return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_model_create_from_file(smt_ctx *ctx, const char *path, uint64_t byte_offset, uint64_t V, uint32_t D, int normalize,
+                               smt_model **out)
+try {
+    return smt_model_create_from_file_typed(ctx, path, byte_offset, SMT_TABLE_F32, V, D, normalize, out);
 } catch (...) { return smt::api_catch(); }
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 // Replaces the pool step of StaticModel::encode_with_args / encode_single
 // (model2vec-rs 0.1.3; reference call sites src/search/mod.rs:69,138,153 and
 // src/cmds/search.rs:136,154): for every line, gather the token rows of the
-// f32 table [V x 256], sum them IN TOKEN ORDER in f32, divide by the token
+// table [V x 256] (f32, IEEE half or int8 as stored; narrow rows are widened in registers, which is exact), sum them IN TOKEN ORDER in f32, divide by the token
 // count, then divide by max(sqrt(sum_d v_d^2), 1e-12) with the squares summed
 // IN DIMENSION ORDER -- i.e. exactly the serial f32 chains of the CPU code, so
 // the output is bit-identical to the oracle (oracle/semtools_oracle.c
@@ -22,6 +22,13 @@
 // first version gave a wave four lines and iterated to the longest of them: with ragged lines (0..32 tokens) a third of
 // the gather slots sat idle and the kernel stopped at 5.3 TB/s on uniform ids (0.76 of what the probe shows the part
 // delivers for this access pattern).
+//
+// Typed tables: the kernel is a template over the table element.  The f32 instantiation is the mapping above, behind
+// `if constexpr`.  A half row is 512 B = 2 gather instructions (lane a owns dims {128c + 8a .. 128c + 8a + 7 : c = 0, 1}), an
+// int8 row 256 B = 1 (lane a owns dims 16a .. 16a + 15): the same 16 lanes x 16 B contiguous pieces, 32 / 16 row registers in
+// flight instead of 64.  half -> f32 and int8 -> f32 lose nothing (half subnormals are normal f32 values; the FP16 denormal
+// mode stays at its default, on), the 16 accumulators per lane are the same independent f32 chains, and the norm chain walks
+// the dimensions in order whatever the ownership -- so a typed model gives the bits of the f32 model built from the widened table.
 #include "common.h"
 
 namespace smt {
@@ -37,8 +44,20 @@ __device__ __forceinline__ float dppf(float v)
         float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
 }
 
+typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+typedef signed char char16_t_ __attribute__((ext_vector_type(16)));
+
+// what a lane holds of one table row while it is in flight: NC 16-byte pieces
+template <typename T> struct RowPiece;
+template <> struct RowPiece<float> { using type = float4; static constexpr int NC = 4; };
+template <> struct RowPiece<_Float16> { using type = half8_t; static constexpr int NC = 2; };
+template <> struct RowPiece<signed char> { using type = char16_t_; static constexpr int NC = 1; };
+
+// accumulator k = 4 c + j of a lane lives in component j of acc[c]
+__device__ __forceinline__ float &comp(float4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
+
 struct EmbedParams {
-    const float *table;
+    const unsigned char *table; // rows of 256 elements of `kind`, as stored
     uint64_t V;
     const uint32_t *ids;
     const uint64_t *offsets;
@@ -52,6 +71,7 @@ struct EmbedParams {
     uint64_t n_groups;
     uint64_t span_limit;        // PF kernel: runs spanning this many tokens or more are left to the generic kernel (2^32; tests: small)
     int only_large;             // generic kernel: 1 = walk only the runs the PF kernel left
+    int kind;                   // SMT_TABLE_F32 / F16 / I8: which instantiation the launch picked
 };
 
 // PF: the token ids of step s + 1 are requested while the rows of step s are in flight (the next position is pure arithmetic on the
@@ -83,10 +103,15 @@ __global__ void __launch_bounds__(256) embed_runs_kernel(const uint64_t *__restr
     run_start[g] = g == n_groups ? n_lines : lo;
 }
 
-template <bool PF>
+template <typename T, bool PF>
 __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
 {
 #pragma clang fp contract(off)
+    constexpr bool F32 = std::is_same<T, float>::value;
+    using piece_t = typename RowPiece<T>::type;
+    constexpr int NC = RowPiece<T>::NC;        // gather instructions per token
+    constexpr int EPL = 16 / NC;               // dims per 16-byte piece
+    constexpr uint64_t ROW_BYTES = 256 * sizeof(T);
     const int lane = threadIdx.x & 63;
     const int a = lane & 15;        // position inside the group
     const uint64_t group = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
@@ -156,17 +181,30 @@ __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
                     sq[c][2] = pend[c].z * pend[c].z; sq[c][3] = pend[c].w * pend[c].w;
                 }
                 float s = 0.0f;
+                if constexpr (F32) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
+                    for (int c = 0; c < 4; ++c) {
 #pragma unroll
-                    for (int step = 0; step < 16; ++step) {
-                        // take the running sum from the previous lane of the row (lane 15 -> lane 0 wraps
-                        // into the next 64-dim chunk); at the very first step everyone holds 0.
-                        const float in = (c == 0 && step == 0) ? 0.0f : dppf<DPP_ROW_ROR1>(s);
-                        s = (((in + sq[c][0]) + sq[c][1]) + sq[c][2]) + sq[c][3];
+                        for (int step = 0; step < 16; ++step) {
+                            // take the running sum from the previous lane of the row (lane 15 -> lane 0 wraps
+                            // into the next 64-dim chunk); at the very first step everyone holds 0.
+                            const float in = (c == 0 && step == 0) ? 0.0f : dppf<DPP_ROW_ROR1>(s);
+                            s = (((in + sq[c][0]) + sq[c][1]) + sq[c][2]) + sq[c][3];
+                        }
+                    }
+                } else {
+                    // the lane's piece c holds EPL consecutive dims (accumulators EPL c .. EPL c + EPL - 1): NC x 16 steps of EPL adds
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+#pragma unroll
+                        for (int step = 0; step < 16; ++step) {
+                            s = (c == 0 && step == 0) ? 0.0f : dppf<DPP_ROW_ROR1>(s);
+#pragma unroll
+                            for (int e = 0; e < EPL; ++e) s = s + sq[(EPL * c + e) >> 2][(EPL * c + e) & 3];
+                        }
                     }
                 }
-                // after 64 steps the full chain value is in lane 15 of each group
+                // after the last step the full chain value is in lane 15 of each group
                 const float ss = __shfl(s, (lane & 48) | 15);
                 float norm = sqrtf(ss);
                 if (!(norm > 1e-12f)) norm = 1e-12f;
@@ -178,7 +216,11 @@ __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
             }
             float4 *o = reinterpret_cast<float4 *>(p.out + (line0 + li - 1) * 256);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) o[c * 16 + a] = pend[c];
+            for (int c = 0; c < 4; ++c) {
+                if constexpr (F32) o[c * 16 + a] = pend[c];
+                else if constexpr (NC == 2) o[(c >> 1) * 32 + 2 * a + (c & 1)] = pend[c];   // dims 128 c' + 8 a + 4 h ..
+                else o[4 * a + c] = pend[c];                                                // dims 16 a + 4 c ..
+            }
             has_pend = false;
         }
     };
@@ -191,7 +233,7 @@ __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
     const uint32_t *ids = p.ids + tb;
     if constexpr (PF) nid = (active && (t + (a & 3)) < t_end) ? ids[t + (a & 3)] : 0u;
     while (__any(active)) {
-        float4 r[TU][4];
+        piece_t r[TU][NC];
         uint32_t idq[TU] = {0u, 0u, 0u, 0u};
         if constexpr (PF) {   // quad_perm broadcasts of lane u of every quad
             idq[0] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)nid, 0x00, 0xF, 0xF, false);
@@ -206,12 +248,16 @@ __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
             if constexpr (PF) id = idq[u];
             else id = on ? (uint64_t)ids[t + u] : 0;
             const bool ok = on && id < p.V;  // out-of-vocab ids contribute nothing
-            const float4 *row = reinterpret_cast<const float4 *>(p.table + (ok ? id : 0) * 256);
+            // (plain loads, not nontemporal: natural text is Zipf-distributed and its hot rows must stay in L2 / MALL --
+            // measured with the nt policy: Zipf ids 3.50 -> 4.59 ms, uniform ids 5.97 -> 6.27 ms; round 4: 3.18 -> 4.68, 6.56 -> 6.77)
+            if constexpr (F32) {
+                const float4 *row = reinterpret_cast<const float4 *>(p.table + (ok ? id : 0) * ROW_BYTES);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                // (plain loads, not nontemporal: natural text is Zipf-distributed and its hot rows must stay in L2 / MALL --
-                // measured with the nt policy: Zipf ids 3.50 -> 4.59 ms, uniform ids 5.97 -> 6.27 ms; round 4: 3.18 -> 4.68, 6.56 -> 6.77)
-                r[u][c] = ok ? row[c * 16 + a] : make_float4(0.f, 0.f, 0.f, 0.f);
+                for (int c = 0; c < 4; ++c) r[u][c] = ok ? row[c * 16 + a] : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                const piece_t *row = reinterpret_cast<const piece_t *>(p.table + (ok ? id : 0) * ROW_BYTES);
+#pragma unroll
+                for (int c = 0; c < NC; ++c) r[u][c] = ok ? row[c * 16 + a] : piece_t(0);   // (all-zero bits are +0 in every type)
             }
         }
         // where the group stands after this step -- known before any row has arrived
@@ -226,12 +272,23 @@ __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
 #pragma unroll
         for (int u = 0; u < TU; ++u) {
             if (active && (t + u) < t_end) {  // token order: u ascending
+                if constexpr (F32) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    acc[c].x = acc[c].x + r[u][c].x;
-                    acc[c].y = acc[c].y + r[u][c].y;
-                    acc[c].z = acc[c].z + r[u][c].z;
-                    acc[c].w = acc[c].w + r[u][c].w;
+                    for (int c = 0; c < 4; ++c) {
+                        acc[c].x = acc[c].x + r[u][c].x;
+                        acc[c].y = acc[c].y + r[u][c].y;
+                        acc[c].z = acc[c].z + r[u][c].z;
+                        acc[c].w = acc[c].w + r[u][c].w;
+                    }
+                } else {   // widened in registers (exact), then the same f32 add
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+#pragma unroll
+                        for (int e = 0; e < EPL; ++e) {
+                            float &d = comp(acc[(EPL * c + e) >> 2], (EPL * c + e) & 3);
+                            d = d + (float)r[u][c][e];
+                        }
+                    }
                 }
             }
         }
@@ -264,12 +321,31 @@ __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
     if (__any(has_pend)) finalize();
 }
 
-int launch_embed(smt_ctx *ctx, const float *table, uint64_t V, int normalize, const uint32_t *ids,
+template <typename T>
+static void launch_embed_typed(smt_ctx *ctx, EmbedParams &p, unsigned blocks, uint64_t n_tokens_known)
+{
+    // (A/B: embed_batched bit 1 = ids prefetched one step ahead.  Probed in round 4 and removed: the same kernel at three waves per
+    // SIMD without spills -- Zipf 3.11 -> 3.32 ms -- and nontemporal row loads -- 4.68 / 6.77 ms; profiles/r04_k1/)
+    p.only_large = 0;
+    if (ctx->tune.embed_batched & 2) {
+        hipLaunchKernelGGL((embed_kernel<T, true>), dim3(blocks), dim3(256), 0, ctx->stream, p);
+        // the runs it left: none when the caller knows the batch holds fewer tokens than the limit (n_tokens_known = 0: offsets
+        // only exist on the device -- the launch finds nothing to do and costs a few microseconds)
+        if (n_tokens_known == 0 || n_tokens_known >= p.span_limit) {
+            p.only_large = 1;
+            hipLaunchKernelGGL((embed_kernel<T, false>), dim3(blocks), dim3(256), 0, ctx->stream, p);
+        }
+    } else hipLaunchKernelGGL((embed_kernel<T, false>), dim3(blocks), dim3(256), 0, ctx->stream, p);
+}
+
+int launch_embed(smt_ctx *ctx, const void *table, int table_dtype, uint64_t V, int normalize, const uint32_t *ids,
                  const uint64_t *offsets, uint64_t n_lines, uint32_t max_tokens, float *out, uint64_t n_tokens_known)
 {
     if (n_lines == 0) return SMT_OK;
+    SMT_REQUIRE(table_dtype == SMT_TABLE_F32 || table_dtype == SMT_TABLE_F16 || table_dtype == SMT_TABLE_I8, "unknown table dtype");
     EmbedParams p;
-    p.table = table;
+    p.table = static_cast<const unsigned char *>(table);
+    p.kind = table_dtype;
     p.V = V;
     p.ids = ids;
     p.offsets = offsets;
@@ -307,20 +383,11 @@ int launch_embed(smt_ctx *ctx, const float *table, uint64_t V, int normalize, co
     if (balanced)
         hipLaunchKernelGGL(embed_runs_kernel, dim3((unsigned)((groups + 1 + 255) / 256)), dim3(256), 0, ctx->stream, offsets, n_lines, groups,
                            ctx->d_embed_runs);
-    // (A/B: embed_batched bit 1 = ids prefetched one step ahead.  Probed in round 4 and removed: the same kernel at three waves per
-    // SIMD without spills -- Zipf 3.11 -> 3.32 ms -- and nontemporal row loads -- 4.68 / 6.77 ms; profiles/r04_k1/)
     // embed_batched bit 2 (tests): the PF kernel leaves every run of 64 tokens or more to the generic kernel
     p.span_limit = (ctx->tune.embed_batched & 4) ? 64ull : EMBED_SPAN_LIMIT;
-    p.only_large = 0;
-    if (ctx->tune.embed_batched & 2) {
-        hipLaunchKernelGGL(embed_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, p);
-        // the runs it left: none when the caller knows the batch holds fewer tokens than the limit (n_tokens_known = 0: offsets
-        // only exist on the device -- the launch finds nothing to do and costs a few microseconds)
-        if (n_tokens_known == 0 || n_tokens_known >= p.span_limit) {
-            p.only_large = 1;
-            hipLaunchKernelGGL(embed_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, p);
-        }
-    } else hipLaunchKernelGGL(embed_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, p);
+    if (table_dtype == SMT_TABLE_F16) launch_embed_typed<_Float16>(ctx, p, (unsigned)blocks, n_tokens_known);
+    else if (table_dtype == SMT_TABLE_I8) launch_embed_typed<signed char>(ctx, p, (unsigned)blocks, n_tokens_known);
+    else launch_embed_typed<float>(ctx, p, (unsigned)blocks, n_tokens_known);
     prof_end(ctx, "embed");
     SMT_HIP_CHECK(hipGetLastError());
     return SMT_OK;

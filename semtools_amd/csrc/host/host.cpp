@@ -395,12 +395,16 @@ StaticModel::StaticModel(smt_group *group, std::unique_ptr<Tokenizer> tok, const
 }
 
 StaticModel::StaticModel(smt_group *group, std::unique_ptr<Tokenizer> tok, const std::string &path, uint64_t byte_offset, uint64_t V,
-                         bool normalize)
+                         bool normalize, int table_dtype)
     : group_(group), tok_(std::move(tok))
 {
+    if (table_dtype != SMT_TABLE_F32 && table_dtype != SMT_TABLE_F16 && table_dtype != SMT_TABLE_I8) throw Error("unknown table dtype");
+    lazy_dtype_ = table_dtype;
+    lazy_row_bytes_ = (size_t)SMT_DIM * (table_dtype == SMT_TABLE_F32 ? 4 : table_dtype == SMT_TABLE_F16 ? 2 : 1);
     const char *eager = getenv("SEMTOOLS_EAGER_MODEL");
     if (eager && eager[0] == '1') {
-        check(smt_sharded_model_create_from_file(group, path.c_str(), byte_offset, V, SMT_DIM, normalize ? 1 : 0, &model_), "StaticModel");
+        check(smt_sharded_model_create_from_file_typed(group, path.c_str(), byte_offset, table_dtype, V, SMT_DIM, normalize ? 1 : 0, &model_),
+              "StaticModel");
         return;
     }
     lazy_path_ = path;
@@ -417,10 +421,20 @@ StaticModel::~StaticModel()
     if (lazy_fd_ >= 0) close(lazy_fd_);
 }
 
+void StaticModel::table_info(int *table_dtype, uint64_t *V, uint64_t *table_bytes, bool *resident) const
+{
+    if (resident) *resident = model_ != nullptr;
+    if (model_) { check(smt_sharded_model_info(model_, table_dtype, V, table_bytes), "model info"); return; }
+    if (table_dtype) *table_dtype = lazy_dtype_;
+    if (V) *V = lazy_V_;
+    if (table_bytes) *table_bytes = lazy_V_ * lazy_row_bytes_;
+}
+
 smt_sharded_model *StaticModel::full_model() const
 {
     if (!model_) {
-        check(smt_sharded_model_create_from_file(group_, lazy_path_.c_str(), lazy_offset_, lazy_V_, SMT_DIM, lazy_normalize_ ? 1 : 0, &model_),
+        check(smt_sharded_model_create_from_file_typed(group_, lazy_path_.c_str(), lazy_offset_, lazy_dtype_, lazy_V_, SMT_DIM,
+                                                       lazy_normalize_ ? 1 : 0, &model_),
               "StaticModel (full table upload)");
         PhaseTimer::mark("model_table_upload");
     }
@@ -450,12 +464,13 @@ void StaticModel::embed_csr(const std::vector<uint32_t> &ids, const std::vector<
     }
     std::sort(uniq.begin(), uniq.end());          // file order: neighbouring rows share pages
     for (size_t s = 0; s < uniq.size(); ++s) lazy_slot_[uniq[s]] = (uint32_t)s + 1;
-    std::vector<float> compact(std::max<size_t>(uniq.size(), 1) * SMT_DIM, 0.0f);
+    const size_t rb = lazy_row_bytes_;   // the compact table keeps the stored dtype (all-zero bytes are 0 in each of them)
+    std::vector<unsigned char> compact(std::max<size_t>(uniq.size(), 1) * rb, 0);
     try {
         parallel_slices(uniq.size(), 512, [&](size_t sb, size_t se) {
             for (size_t s = sb; s < se; ++s) {
-                const off_t at = (off_t)(lazy_offset_ + (uint64_t)uniq[s] * SMT_DIM * sizeof(float));
-                if (pread(lazy_fd_, &compact[s * SMT_DIM], SMT_DIM * sizeof(float), at) != (ssize_t)(SMT_DIM * sizeof(float)))
+                const off_t at = (off_t)(lazy_offset_ + (uint64_t)uniq[s] * rb);
+                if (pread(lazy_fd_, &compact[s * rb], rb, at) != (ssize_t)rb)
                     throw Error("short read from " + lazy_path_);
             }
         });
@@ -467,7 +482,8 @@ void StaticModel::embed_csr(const std::vector<uint32_t> &ids, const std::vector<
     for (size_t i = 0; i < ids.size(); ++i) remapped[i] = lazy_slot_[ids[i]] - 1;
     for (uint32_t id : uniq) lazy_slot_[id] = 0;
     smt_sharded_model *tmp = nullptr;   // (a few MB: replicated like the full table)
-    check(smt_sharded_model_create(group_, compact.data(), std::max<size_t>(uniq.size(), 1), SMT_DIM, lazy_normalize_ ? 1 : 0, &tmp), "embed (compact table)");
+    check(smt_sharded_model_create_typed(group_, compact.data(), lazy_dtype_, std::max<size_t>(uniq.size(), 1), SMT_DIM, lazy_normalize_ ? 1 : 0, &tmp),
+          "embed (compact table)");
     const int rc = smt_sharded_embed(tmp, remapped.data(), offsets.data(), n_lines, 0, out_host, corpus, nullptr);
     smt_sharded_model_destroy(tmp);
     check(rc, "embed (compact table)");

@@ -92,7 +92,7 @@ class StaticModel {
 public:
     // table: [V x 256] f32 host array (the `embeddings` tensor), uploaded once (to every GPU of the group).
     StaticModel(smt_group *group, std::unique_ptr<Tokenizer> tok, const float *table, uint64_t V, bool normalize);
-    // the f32 table sits at `byte_offset` of `path` (model.safetensors).  LAZY: nothing is uploaded until an embed call
+    // the table (f32, half or int8 rows as stored: table_dtype = SMT_TABLE_*) sits at `byte_offset` of `path` (model.safetensors).  LAZY: nothing is uploaded until an embed call
     // shows what it needs.  A one-shot CLI run (c1: 1000 lines; a warm workspace search: the query alone) touches a few
     // thousand of the 500 k rows: those rows are read from the file (pread, a few MB), uploaded as a compact table
     // with remapped ids, pooled and dropped -- same values, same order, bit-identical embeddings -- instead of
@@ -100,7 +100,7 @@ public:
     // 32768 lines, or whose ids cover more than 1/16 of the table, uploads the whole table once (and for good).
     // SEMTOOLS_EAGER_MODEL=1 restores the eager upload.
     StaticModel(smt_group *group, std::unique_ptr<Tokenizer> tok, const std::string &path, uint64_t byte_offset, uint64_t V,
-                bool normalize);
+                bool normalize, int table_dtype = SMT_TABLE_F32);
     ~StaticModel();
     StaticModel(const StaticModel &) = delete;
 
@@ -127,6 +127,9 @@ public:
 
     smt_group *group() const { return group_; }
     const Tokenizer &tokenizer() const { return *tok_; }
+    // the table as the device holds it (or will, in lazy mode before the full upload: *resident = false): SMT_TABLE_* kind, rows,
+    // bytes per replica
+    void table_info(int *table_dtype, uint64_t *V, uint64_t *table_bytes, bool *resident) const;
 
 private:
     void tokenize_batch(const std::string_view *sentences, size_t begin, size_t end,
@@ -139,8 +142,10 @@ private:
     smt_group *group_;
     std::unique_ptr<Tokenizer> tok_;
     mutable smt_sharded_model *model_ = nullptr;
-    // lazy mode (file-backed f32 table not uploaded yet)
+    // lazy mode (file-backed table not uploaded yet)
     std::string lazy_path_;
+    int lazy_dtype_ = SMT_TABLE_F32;
+    size_t lazy_row_bytes_ = SMT_DIM * sizeof(float);
     uint64_t lazy_offset_ = 0, lazy_V_ = 0;
     bool lazy_normalize_ = true;
     int lazy_fd_ = -1;

@@ -71,52 +71,9 @@ search::SearchConfig make_config(uint64_t n_lines, uint64_t top_k, double max_di
 }
 
 // ---- minimal safetensors reader: u64 header length, JSON header, raw little-endian data
-std::vector<float> read_safetensors_embeddings(const std::string &path, uint64_t &V)
-{
-    std::ifstream f(path, std::ios::binary);
-    if (!f) throw Error("cannot open " + path);
-    uint64_t hlen = 0;
-    f.read(reinterpret_cast<char *>(&hlen), 8);
-    if (!f || hlen > (1ull << 30)) throw Error("bad safetensors header in " + path);
-    std::string hdr(hlen, '\0');
-    f.read(&hdr[0], (std::streamsize)hlen);
-    const json::Value h = json::parse(hdr);
-    const json::Value *t = h.get("embeddings");
-    if (!t) throw Error("tensor 'embeddings' not found in " + path);
-    const std::string dtype = t->get("dtype")->s;
-    const auto &shape = t->get("shape")->arr;
-    if (shape.size() != 2 || shape[1].as_u64() != SMT_DIM) throw Error("'embeddings' must be [V, 256]");
-    V = shape[0].as_u64();
-    const uint64_t b0 = t->get("data_offsets")->arr[0].as_u64();
-    std::vector<float> out((size_t)V * SMT_DIM);
-    f.seekg((std::streamoff)(8 + hlen + b0));
-    if (dtype == "F32") {
-        f.read(reinterpret_cast<char *>(out.data()), (std::streamsize)(out.size() * 4));
-    } else if (dtype == "F16") {
-        std::vector<uint16_t> raw(out.size());
-        f.read(reinterpret_cast<char *>(raw.data()), (std::streamsize)(raw.size() * 2));
-        for (size_t i = 0; i < raw.size(); ++i) {  // IEEE half -> float
-            const uint32_t s = (raw[i] >> 15) & 1, e = (raw[i] >> 10) & 0x1F, m = raw[i] & 0x3FF;
-            uint32_t bits;
-            if (e == 0) {
-                if (m == 0) bits = s << 31;
-                else { int sh = 0; uint32_t mm = m; while (!(mm & 0x400)) { mm <<= 1; ++sh; }
-                       bits = (s << 31) | ((uint32_t)(127 - 15 - sh + 1) << 23) | ((mm & 0x3FF) << 13); }
-            } else if (e == 31) bits = (s << 31) | 0x7F800000u | (m << 13);
-            else bits = (s << 31) | ((e - 15 + 127) << 23) | (m << 13);
-            memcpy(&out[i], &bits, 4);
-        }
-    } else if (dtype == "I8") {  // model2vec-rs converts each byte `as i8 as f32` (no scale)
-        std::vector<int8_t> raw(out.size());
-        f.read(reinterpret_cast<char *>(raw.data()), (std::streamsize)raw.size());
-        for (size_t i = 0; i < raw.size(); ++i) out[i] = (float)raw[i];
-    } else throw Error("unsupported embeddings dtype " + dtype + " (F32, F16, I8)");
-    if (!f) throw Error("truncated safetensors file " + path);
-    return out;
-}
-
-// dtype / shape / byte offset of the `embeddings` tensor (no data read)
-bool safetensors_f32_span(const std::string &path, uint64_t &V, uint64_t &byte_offset)
+// dtype (SMT_TABLE_*) / shape / byte offset of the `embeddings` tensor (no data read: the table goes to the device as stored,
+// StaticModel streams or preads it)
+int safetensors_embeddings_span(const std::string &path, uint64_t &V, uint64_t &byte_offset)
 {
     std::ifstream f(path, std::ios::binary);
     if (!f) throw Error("cannot open " + path);
@@ -132,7 +89,11 @@ bool safetensors_f32_span(const std::string &path, uint64_t &V, uint64_t &byte_o
     if (shape.size() != 2 || shape[1].as_u64() != SMT_DIM) throw Error("'embeddings' must be [V, 256]");
     V = shape[0].as_u64();
     byte_offset = 8 + hlen + t->get("data_offsets")->arr[0].as_u64();
-    return t->get("dtype")->s == "F32";
+    const std::string dtype = t->get("dtype")->s;
+    if (dtype == "F32") return SMT_TABLE_F32;
+    if (dtype == "F16") return SMT_TABLE_F16;
+    if (dtype == "I8") return SMT_TABLE_I8;   // model2vec-rs converts each byte `as i8 as f32` (no scale): so does K1
+    throw Error("unsupported embeddings dtype " + dtype + " (F32, F16, I8)");
 }
 
 }  // namespace
@@ -270,10 +231,8 @@ static int host_model_from_dir(smt_ctx *ctx, smt_group *group, const char *dir, 
         const std::string d(dir);
         search::PhaseTimer::mark("process_start_and_hip_context");   // (everything before the model directory is touched)
         uint64_t V = 0, table_offset = 0;
-        // F32 tables (what model2vec ships) stream file -> pinned -> HBM; F16 / I8 tables are widened on the host first
-        const bool stream_f32 = safetensors_f32_span(d + "/model.safetensors", V, table_offset);
-        std::vector<float> table;
-        if (!stream_f32) table = read_safetensors_embeddings(d + "/model.safetensors", V);
+        // the table streams file -> pinned -> HBM (or is read row by row: StaticModel's lazy mode) in the dtype it is stored in
+        const int table_dtype = safetensors_embeddings_span(d + "/model.safetensors", V, table_offset);
         bool normalize = true;
         std::string unk = "[UNK]";
         try {
@@ -293,8 +252,7 @@ static int host_model_from_dir(smt_ctx *ctx, smt_group *group, const char *dir, 
         search::PhaseTimer::mark("tokenizer_load");
         std::unique_ptr<smt_host_model> h(new smt_host_model());
         if (group) h->group.use(group); else h->group.wrap(ctx);
-        if (stream_f32) h->m = std::make_unique<search::StaticModel>(h->group.g, std::move(tok), d + "/model.safetensors", table_offset, V, normalize);
-        else h->m = std::make_unique<search::StaticModel>(h->group.g, std::move(tok), table.data(), V, normalize);
+        h->m = std::make_unique<search::StaticModel>(h->group.g, std::move(tok), d + "/model.safetensors", table_offset, V, normalize, table_dtype);
         *out = h.release();
         return SMT_OK;
     } catch (const std::exception &e) { return fail(e); }
@@ -304,6 +262,17 @@ int smt_host_model_from_dir(smt_ctx *ctx, const char *dir, smt_host_model **out)
 int smt_host_model_from_dir_group(smt_group *group, const char *dir, smt_host_model **out) { return host_model_from_dir(nullptr, group, dir, out); }
 
 void smt_host_model_destroy(smt_host_model *model) { delete model; }
+
+int smt_host_model_table_info(const smt_host_model *model, int *table_dtype, uint64_t *V, uint64_t *table_bytes, int *resident)
+{
+    if (!model || !model->m) { smt::set_error("null argument"); return SMT_E_INVALID; }
+    try {
+        bool res = false;
+        model->m->table_info(table_dtype, V, table_bytes, &res);
+        if (resident) *resident = res ? 1 : 0;
+        return SMT_OK;
+    } catch (const std::exception &e) { return fail(e); }
+}
 
 int smt_host_encode(smt_host_model *model, const char *const *texts, uint64_t n, uint32_t max_length, float *out)
 {

@@ -617,6 +617,26 @@ try {
     return sharded_model_make(group, [&](int i, smt_model **m) { return smt_model_create_from_file(group->ctx[i], path, byte_offset, V, D, normalize, m); }, out);
 } catch (...) { return smt::api_catch(); }
 
+int smt_sharded_model_create_typed(smt_group *group, const void *table_host, int table_dtype, uint64_t V, uint32_t D, int normalize,
+                                   smt_sharded_model **out)
+try {
+    SMT_REQUIRE(group && table_host && out, "null argument");
+    return sharded_model_make(group, [&](int i, smt_model **m) { return smt_model_create_typed(group->ctx[i], table_host, table_dtype, V, D, normalize, m); }, out);
+} catch (...) { return smt::api_catch(); }
+
+int smt_sharded_model_create_from_file_typed(smt_group *group, const char *path, uint64_t byte_offset, int table_dtype, uint64_t V,
+                                             uint32_t D, int normalize, smt_sharded_model **out)
+try {
+    SMT_REQUIRE(group && path && out, "null argument");
+    return sharded_model_make(group, [&](int i, smt_model **m) { return smt_model_create_from_file_typed(group->ctx[i], path, byte_offset, table_dtype, V, D, normalize, m); }, out);
+} catch (...) { return smt::api_catch(); }
+
+int smt_sharded_model_info(const smt_sharded_model *model, int *table_dtype, uint64_t *V, uint64_t *table_bytes)
+try {
+    SMT_REQUIRE(model != nullptr && !model->model.empty(), "model");
+    return smt_model_info(model->model[0], table_dtype, V, table_bytes);
+} catch (...) { return smt::api_catch(); }
+
 int smt_sharded_embed(smt_sharded_model *model, const uint32_t *ids, const uint64_t *offsets, uint64_t n_lines, uint32_t max_tokens,
                       float *out_host, smt_sharded_corpus *append_to, uint64_t *first_row)
 try {

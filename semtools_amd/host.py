@@ -75,6 +75,16 @@ class StaticModel:
         except Exception:
             pass
 
+    def table_info(self):
+        """(numpy dtype of the table on the device, rows, bytes per replica, whether the whole table is resident)"""
+        dt, v, nbytes, res = C.c_int(), C.c_uint64(), C.c_uint64(), C.c_int()
+        L.check(L.lib().smt_host_model_table_info(self._h, C.byref(dt), C.byref(v), C.byref(nbytes), C.byref(res)))
+        return L.TABLE_NP[int(dt.value)], int(v.value), int(nbytes.value), bool(res.value)
+
+    @property
+    def table_bytes(self):
+        return self.table_info()[2]
+
     def encode_with_args(self, sentences, max_length=2048):
         out = np.empty((len(sentences), L.DIM), dtype=np.float32)
         L.check(L.lib().smt_host_encode(self._h, _cstrs(sentences), len(sentences), int(max_length or 0), L.np_ptr(out)))
