@@ -138,6 +138,29 @@ int smt_model_create_from_device_typed(smt_ctx *ctx, const void *table_dev, int 
 /* what the model holds: its SMT_TABLE_* kind, row count and the bytes of the table in device memory; any out may be NULL */
 int smt_model_info(const smt_model *model, int *table_dtype, uint64_t *V, uint64_t *table_bytes);
 
+/* Indexed tables (vocabulary-quantised model2vec models: `embeddings` [n_rows x 256] shared by many tokens, `mapping` [n_tokens]
+ * token id -> row, `weights` [n_tokens] one scalar per token).  A line's sum is, in token order,
+ *     acc_d = acc_d + fl32(weights[t] * widen(table[mapping[t]][d]))        for every id t < n_tokens
+ * (product rounded to f32, then added, no FMA), divided by max(count, 1) where the count includes ids >= n_tokens, then the usual norm
+ * step: bit-identical to a plain SMT_TABLE_F32 model over the expanded table E'[t] = fl32(weights[t] * widen(table[mapping[t]])).
+ * These semantics are this project's restatement of newer model2vec versions; they are not pinned against a crate.
+ * mapping (u32) and weights (f32) have n_tokens entries; either may be NULL (identity / 1).  With mapping NULL, n_tokens must equal
+ * n_rows.  Both NULL == smt_model_create*_typed.  The library keeps its own packed copy (8 B per token): the arrays may be
+ * freed after the call.  SMT_E_INVALID, with nothing left allocated and *out untouched: unknown dtype, unaligned table_dev, n_tokens == 0
+ * with an array given, mapping NULL and n_tokens != n_rows, a mapping entry >= n_rows, a weight that is not finite (the message names
+ * the first such token).  smt_embed / smt_embed_device are unchanged: the model carries its form. */
+int smt_model_create_indexed(smt_ctx *ctx, const void *table_host, int table_dtype, uint64_t n_rows, uint32_t D,
+                             const uint32_t *mapping_host, const float *weights_host, uint64_t n_tokens, int normalize, smt_model **out);
+int smt_model_create_from_file_indexed(smt_ctx *ctx, const char *path, uint64_t byte_offset, int table_dtype, uint64_t n_rows, uint32_t D,
+                                       const uint32_t *mapping_host, const float *weights_host, uint64_t n_tokens, int normalize,
+                                       smt_model **out);
+int smt_model_create_from_device_indexed(smt_ctx *ctx, const void *table_dev, int table_dtype, uint64_t n_rows, uint32_t D,
+                                         const uint32_t *mapping_dev, const float *weights_dev, uint64_t n_tokens, int normalize,
+                                         smt_model **out);
+/* the token side of a model (smt_model_info keeps reporting table rows and table bytes): the number of token ids it knows (a plain
+ * model: its rows), whether it was given a mapping / weights, and the bytes of its token array (0 for a plain model); any out may be NULL */
+int smt_model_token_info(const smt_model *model, uint64_t *n_tokens, int *has_mapping, int *has_weights, uint64_t *token_bytes);
+
 /* Replaces the pool step of StaticModel::encode_with_args / encode_single
  * (call sites src/search/mod.rs:69,138,153; src/cmds/search.rs:136,154).
  * Tokenisation stays on the host: `ids` are the unk-filtered token ids of all
@@ -473,6 +496,15 @@ int smt_sharded_model_create_typed(smt_group *group, const void *table_host, int
                                    smt_sharded_model **out);
 int smt_sharded_model_create_from_file_typed(smt_group *group, const char *path, uint64_t byte_offset, int table_dtype, uint64_t V,
                                              uint32_t D, int normalize, smt_sharded_model **out);
+/* the indexed form (smt_model_create_indexed): one replica of table and token array per local device */
+int smt_sharded_model_create_indexed(smt_group *group, const void *table_host, int table_dtype, uint64_t n_rows, uint32_t D,
+                                     const uint32_t *mapping_host, const float *weights_host, uint64_t n_tokens, int normalize,
+                                     smt_sharded_model **out);
+int smt_sharded_model_create_from_file_indexed(smt_group *group, const char *path, uint64_t byte_offset, int table_dtype, uint64_t n_rows,
+                                               uint32_t D, const uint32_t *mapping_host, const float *weights_host, uint64_t n_tokens,
+                                               int normalize, smt_sharded_model **out);
+int smt_sharded_model_token_info(const smt_sharded_model *model, uint64_t *n_tokens, int *has_mapping, int *has_weights,
+                                 uint64_t *token_bytes);
 /* smt_model_info of the replicas (they are alike): table_bytes is what ONE replica holds in device memory */
 int smt_sharded_model_info(const smt_sharded_model *model, int *table_dtype, uint64_t *V, uint64_t *table_bytes);
 void smt_sharded_model_destroy(smt_sharded_model *model);

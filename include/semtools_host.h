@@ -47,6 +47,11 @@ int smt_host_model_from_dir(smt_ctx *ctx, const char *dir, smt_host_model **out)
  * rows, and bytes per replica.  *resident = 0 while a directory-backed model has not uploaded the whole table yet (it serves small
  * calls from compact tables of the rows they touch); the figures then describe the table in the file.  Any out may be NULL. */
 int smt_host_model_table_info(const smt_host_model *model, int *table_dtype, uint64_t *V, uint64_t *table_bytes, int *resident);
+/* The token side of the model (smt_model_token_info).  A directory whose model.safetensors also carries `mapping` (I32 / I64) and / or
+ * `weights` (F64 / F32 / F16) is a vocabulary-quantised model: n_tokens is those tensors' length (the tokenizer's vocabulary is checked
+ * against it, not against the table's rows), token_bytes the 8 B per token of the device array per replica.  A plain model reports its
+ * rows, 0, 0, 0.  Any out may be NULL. */
+int smt_host_model_token_info(const smt_host_model *model, uint64_t *n_tokens, int *has_mapping, int *has_weights, uint64_t *token_bytes);
 void smt_host_model_destroy(smt_host_model *model);
 
 /* encode_with_args(texts, Some(max_length) / None when 0, batch 16384) -> out [n x 256] */

@@ -128,6 +128,50 @@ extern "C" {
         V: *mut u64,
         table_bytes: *mut u64,
     ) -> c_int;
+    pub fn smt_model_create_indexed(
+        ctx: *mut SmtCtx,
+        table_host: *const c_void,
+        table_dtype: c_int,
+        n_rows: u64,
+        D: u32,
+        mapping_host: *const u32,
+        weights_host: *const f32,
+        n_tokens: u64,
+        normalize: c_int,
+        out: *mut *mut SmtModel,
+    ) -> c_int;
+    pub fn smt_model_create_from_file_indexed(
+        ctx: *mut SmtCtx,
+        path: *const c_char,
+        byte_offset: u64,
+        table_dtype: c_int,
+        n_rows: u64,
+        D: u32,
+        mapping_host: *const u32,
+        weights_host: *const f32,
+        n_tokens: u64,
+        normalize: c_int,
+        out: *mut *mut SmtModel,
+    ) -> c_int;
+    pub fn smt_model_create_from_device_indexed(
+        ctx: *mut SmtCtx,
+        table_dev: *const c_void,
+        table_dtype: c_int,
+        n_rows: u64,
+        D: u32,
+        mapping_dev: *const u32,
+        weights_dev: *const f32,
+        n_tokens: u64,
+        normalize: c_int,
+        out: *mut *mut SmtModel,
+    ) -> c_int;
+    pub fn smt_model_token_info(
+        model: *const SmtModel,
+        n_tokens: *mut u64,
+        has_mapping: *mut c_int,
+        has_weights: *mut c_int,
+        token_bytes: *mut u64,
+    ) -> c_int;
     pub fn smt_embed(
         model: *mut SmtModel,
         ids: *const u32,
@@ -424,6 +468,38 @@ extern "C" {
         D: u32,
         normalize: c_int,
         out: *mut *mut SmtShardedModel,
+    ) -> c_int;
+    pub fn smt_sharded_model_create_indexed(
+        group: *mut SmtGroup,
+        table_host: *const c_void,
+        table_dtype: c_int,
+        n_rows: u64,
+        D: u32,
+        mapping_host: *const u32,
+        weights_host: *const f32,
+        n_tokens: u64,
+        normalize: c_int,
+        out: *mut *mut SmtShardedModel,
+    ) -> c_int;
+    pub fn smt_sharded_model_create_from_file_indexed(
+        group: *mut SmtGroup,
+        path: *const c_char,
+        byte_offset: u64,
+        table_dtype: c_int,
+        n_rows: u64,
+        D: u32,
+        mapping_host: *const u32,
+        weights_host: *const f32,
+        n_tokens: u64,
+        normalize: c_int,
+        out: *mut *mut SmtShardedModel,
+    ) -> c_int;
+    pub fn smt_sharded_model_token_info(
+        model: *const SmtShardedModel,
+        n_tokens: *mut u64,
+        has_mapping: *mut c_int,
+        has_weights: *mut c_int,
+        token_bytes: *mut u64,
     ) -> c_int;
     pub fn smt_sharded_model_info(
         model: *const SmtShardedModel,

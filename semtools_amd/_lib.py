@@ -43,6 +43,8 @@ EXPORTS = [
     "smt_corpus_compact", "smt_ctx_compact_stats", "smt_sharded_corpus_compact",
     "smt_model_create_typed", "smt_model_create_from_file_typed", "smt_model_create_from_device_typed", "smt_model_info",
     "smt_sharded_model_create_typed", "smt_sharded_model_create_from_file_typed", "smt_sharded_model_info",
+    "smt_model_create_indexed", "smt_model_create_from_file_indexed", "smt_model_create_from_device_indexed", "smt_model_token_info",
+    "smt_sharded_model_create_indexed", "smt_sharded_model_create_from_file_indexed", "smt_sharded_model_token_info",
 ]
 TABLE_F32, TABLE_F16, TABLE_I8 = 0, 1, 2
 TABLE_DTYPES = {np.dtype(np.float32): TABLE_F32, np.dtype(np.float16): TABLE_F16, np.dtype(np.int8): TABLE_I8}
@@ -55,6 +57,36 @@ def table_dtype_code(dtype):
         return TABLE_DTYPES[np.dtype(dtype)]
     except (KeyError, TypeError):
         raise TypeError(f"embedding table dtype {dtype!r} is not supported: the table must be float32, float16 or int8") from None
+
+def token_arrays(mapping, weights, n_rows):
+    """(uint32 mapping or None, float32 weights or None, n_tokens) of an indexed model, checked on the host before anything touches the
+    device: one-dimensional, of one length, the mapping an integer array without a negative entry, and, without a mapping, as
+    many weights as the table has rows.  Both None: (None, None, n_rows), a plain model."""
+    if mapping is None and weights is None:
+        return None, None, int(n_rows)
+    if mapping is not None:
+        mapping = np.asarray(mapping)
+        if mapping.ndim != 1 or mapping.dtype.kind not in "iu":
+            raise ValueError("mapping must be a one-dimensional integer array (token id -> table row)")
+        if mapping.size and int(mapping.min()) < 0:
+            raise ValueError(f"mapping has a negative entry (token {int(np.argmax(mapping < 0))})")
+        if mapping.size and int(mapping.max()) > 0xFFFFFFFF:
+            raise ValueError("mapping has an entry beyond 2^32 - 1")
+        mapping = np.ascontiguousarray(mapping.astype(np.uint32))
+    if weights is not None:
+        weights = np.asarray(weights)
+        if weights.ndim != 1 or weights.dtype.kind != "f":
+            raise ValueError("weights must be a one-dimensional floating-point array (one scalar per token)")
+        weights = np.ascontiguousarray(weights.astype(np.float32))   # by value
+    if mapping is not None and weights is not None and mapping.size != weights.size:
+        raise ValueError(f"mapping has {mapping.size} entries, weights {weights.size}: both have one per token")
+    n_tokens = int(mapping.size if mapping is not None else weights.size)
+    if mapping is None and n_tokens != int(n_rows):
+        raise ValueError(f"without a mapping the weights need one entry per table row ({int(n_rows)}), not {n_tokens}")
+    if n_tokens == 0:
+        raise ValueError("mapping / weights are empty")
+    return mapping, weights, n_tokens
+
 
 STATUS_PROVED, STATUS_UNCERTAIN, STATUS_OVERFLOW, STATUS_INVALID_QUERY = 0, 1, 2, 3
 TRANSPORT_RCCL, TRANSPORT_COPY, TRANSPORT_PEER = 0, 1, 2
@@ -69,7 +101,7 @@ HOST_EXPORTS = [
     "smt_host_split_lines", "smt_host_to_lowercase",
     "smt_host_group_from_spec", "smt_host_model_create_group", "smt_host_model_from_dir_group",
     "smt_host_workspace_use_group", "smt_host_workspace_status_group", "smt_host_workspace_prune_group",
-    "smt_host_model_table_info",
+    "smt_host_model_table_info", "smt_host_model_token_info",
 ]
 TOKENIZE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
                           C.POINTER(C.c_uint64))
@@ -142,6 +174,10 @@ def lib():
     L.smt_model_create_from_file_typed.argtypes = [vp, C.c_char_p, u64, i32, u64, u32, i32, P(vp)]
     L.smt_model_create_from_device_typed.argtypes = [vp, vp, i32, u64, u32, i32, P(vp)]
     L.smt_model_info.argtypes = [vp, P(i32), P(u64), P(u64)]
+    L.smt_model_create_indexed.argtypes = [vp, vp, i32, u64, u32, vp, vp, u64, i32, P(vp)]
+    L.smt_model_create_from_file_indexed.argtypes = [vp, C.c_char_p, u64, i32, u64, u32, vp, vp, u64, i32, P(vp)]
+    L.smt_model_create_from_device_indexed.argtypes = [vp, vp, i32, u64, u32, vp, vp, u64, i32, P(vp)]
+    L.smt_model_token_info.argtypes = [vp, P(u64), P(i32), P(i32), P(u64)]
     L.smt_model_destroy.argtypes = [vp]
     L.smt_model_destroy.restype = None
     L.smt_embed.argtypes = [vp, vp, vp, u64, u32, vp, vp, P(u64)]
@@ -250,6 +286,9 @@ def lib():
     L.smt_sharded_model_create_typed.argtypes = [vp, vp, i32, u64, u32, i32, P(vp)]
     L.smt_sharded_model_create_from_file_typed.argtypes = [vp, C.c_char_p, u64, i32, u64, u32, i32, P(vp)]
     L.smt_sharded_model_info.argtypes = [vp, P(i32), P(u64), P(u64)]
+    L.smt_sharded_model_create_indexed.argtypes = [vp, vp, i32, u64, u32, vp, vp, u64, i32, P(vp)]
+    L.smt_sharded_model_create_from_file_indexed.argtypes = [vp, C.c_char_p, u64, i32, u64, u32, vp, vp, u64, i32, P(vp)]
+    L.smt_sharded_model_token_info.argtypes = [vp, P(u64), P(i32), P(i32), P(u64)]
     L.smt_sharded_model_destroy.argtypes = [vp]
     L.smt_sharded_model_destroy.restype = None
     L.smt_sharded_embed.argtypes = [vp, vp, vp, u64, u32, vp, vp, P(u64)]
@@ -268,6 +307,7 @@ def lib():
     L.smt_host_model_create.argtypes = [vp, vp, u64, i32, i32, C.c_char_p, C.c_char_p, TOKENIZE_CB, vp, u32, u32, P(vp)]
     L.smt_host_model_from_dir.argtypes = [vp, C.c_char_p, P(vp)]
     L.smt_host_model_table_info.argtypes = [vp, P(i32), P(u64), P(u64), P(i32)]
+    L.smt_host_model_token_info.argtypes = [vp, P(u64), P(i32), P(i32), P(u64)]
     L.smt_host_model_destroy.argtypes = [vp]
     L.smt_host_model_destroy.restype = None
     L.smt_host_encode.argtypes = [vp, cpp, u64, u32, vp]

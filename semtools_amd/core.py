@@ -109,32 +109,69 @@ class Context:
 class Model:
     """Device-resident model2vec table (smt_model)."""
 
-    def __init__(self, ctx, table=None, normalize=True, device_ptr=None, V=None, dtype=np.float32):
+    def __init__(self, ctx, table=None, normalize=True, device_ptr=None, V=None, dtype=np.float32, mapping=None, weights=None,
+                 mapping_ptr=None, weights_ptr=None, n_tokens=None):
         """table: a float32, float16 or int8 array [V x 256], uploaded as it is (K1 widens narrow rows in registers).
-        device_ptr / V / dtype: adopt a table of that dtype already in device memory."""
+        device_ptr / V / dtype: adopt a table of that dtype already in device memory.
+        mapping / weights: the indexed form of a vocabulary-quantised model -- token id -> table row (integers) and one scalar per
+        token (converted to float32 by value); either may be None (identity / 1).  A line pools weights[t] * table[mapping[t]].
+        With device_ptr they are given as device pointers to uint32 / float32 arrays (mapping_ptr, weights_ptr, n_tokens)."""
         self.ctx = ctx
         self._h = C.c_void_p()
         if device_ptr is not None:
-            L.check(L.lib().smt_model_create_from_device_typed(ctx._h, C.c_void_p(device_ptr), L.table_dtype_code(dtype), int(V), L.DIM,
-                                                               int(normalize), C.byref(self._h)))
+            if mapping is not None or weights is not None:
+                raise ValueError("with device_ptr the token arrays are device pointers too: mapping_ptr / weights_ptr / n_tokens")
+            indexed = mapping_ptr is not None or weights_ptr is not None
+            L.check(L.lib().smt_model_create_from_device_indexed(
+                ctx._h, C.c_void_p(device_ptr), L.table_dtype_code(dtype), int(V), L.DIM,
+                C.c_void_p(mapping_ptr) if mapping_ptr is not None else None, C.c_void_p(weights_ptr) if weights_ptr is not None else None,
+                int(n_tokens if n_tokens is not None else V) if indexed else 0, int(normalize), C.byref(self._h)))
             self.V = int(V)
         else:
             table = _table(table)
             assert table.ndim == 2
-            L.check(L.lib().smt_model_create_typed(ctx._h, L.np_ptr(table), L.table_dtype_code(table.dtype), table.shape[0],
-                                                   table.shape[1], int(normalize), C.byref(self._h)))
+            mapping, weights, n_tok = L.token_arrays(mapping, weights, table.shape[0])
+            L.check(L.lib().smt_model_create_indexed(ctx._h, L.np_ptr(table), L.table_dtype_code(table.dtype), table.shape[0],
+                                                     table.shape[1], L.np_ptr(mapping), L.np_ptr(weights), n_tok, int(normalize),
+                                                     C.byref(self._h)))
             self.V = table.shape[0]
 
     @classmethod
-    def from_file(cls, ctx, path, byte_offset, V, normalize=True, dtype=np.float32):
-        """Stream a table [V x 256] of `dtype` that sits at `byte_offset` of a file into device memory as stored."""
+    def from_file(cls, ctx, path, byte_offset, V, normalize=True, dtype=np.float32, mapping=None, weights=None):
+        """Stream a table [V x 256] of `dtype` that sits at `byte_offset` of a file into device memory as stored; mapping / weights
+        (host arrays) as in the constructor."""
+        mapping, weights, n_tok = L.token_arrays(mapping, weights, int(V))
         self = cls.__new__(cls)
         self.ctx = ctx
         self._h = C.c_void_p()
-        L.check(L.lib().smt_model_create_from_file_typed(ctx._h, str(path).encode(), int(byte_offset), L.table_dtype_code(dtype), int(V),
-                                                         L.DIM, int(normalize), C.byref(self._h)))
+        L.check(L.lib().smt_model_create_from_file_indexed(ctx._h, str(path).encode(), int(byte_offset), L.table_dtype_code(dtype), int(V),
+                                                           L.DIM, L.np_ptr(mapping), L.np_ptr(weights), n_tok, int(normalize),
+                                                           C.byref(self._h)))
         self.V = int(V)
         return self
+
+    def _token_info(self):
+        n, hm, hw, nb = C.c_uint64(), C.c_int(), C.c_int(), C.c_uint64()
+        L.check(L.lib().smt_model_token_info(self._h, C.byref(n), C.byref(hm), C.byref(hw), C.byref(nb)))
+        return int(n.value), bool(hm.value), bool(hw.value), int(nb.value)
+
+    @property
+    def n_tokens(self):
+        """token ids the model knows (a plain model: its rows)"""
+        return self._token_info()[0]
+
+    @property
+    def has_mapping(self):
+        return self._token_info()[1]
+
+    @property
+    def has_weights(self):
+        return self._token_info()[2]
+
+    @property
+    def token_bytes(self):
+        """bytes of the packed token array in device memory (8 per token; 0 for a plain model)"""
+        return self._token_info()[3]
 
     def _info(self):
         dt, v, nbytes = C.c_int(), C.c_uint64(), C.c_uint64()
@@ -306,7 +343,7 @@ class Corpus:
 
     def search_topk_device(self, queries_ptr, nq, top_k, row_base, out_rows_ptr, out_dist_ptr, out_status_ptr=None):
         """out_status_ptr: device-addressable uint32[nq] receiving the per-query verdict (smt_search_topk_device_ex: 0 proved exact,
-        1 certificate failed, 2 candidate buffer overflowed), or None."""
+        1 certificate failed, 2 candidate buffer overflowed, 3 = SMT_STATUS_INVALID_QUERY: the query lies outside the domain), or None."""
         if out_status_ptr:
             L.check(L.lib().smt_search_topk_device_ex(self._h, C.c_void_p(queries_ptr), int(nq), int(top_k), int(row_base),
                                                       C.c_void_p(out_rows_ptr), C.c_void_p(out_dist_ptr), C.c_void_p(int(out_status_ptr))))
@@ -510,13 +547,24 @@ class Group:
 class ShardedModel:
     """The embedding table replicated on every GPU of a Group; embed() = Model.embed with the lines dealt over the ranks."""
 
-    def __init__(self, group, table, normalize=True):
+    def __init__(self, group, table, normalize=True, mapping=None, weights=None):
         self.group = group
         self._h = C.c_void_p()
         table = _table(table).reshape(-1, L.DIM)
         self.V = table.shape[0]
-        L.check(L.lib().smt_sharded_model_create_typed(group._h, L.np_ptr(table), L.table_dtype_code(table.dtype), self.V, L.DIM,
-                                                       int(normalize), C.byref(self._h)))
+        mapping, weights, n_tok = L.token_arrays(mapping, weights, self.V)
+        L.check(L.lib().smt_sharded_model_create_indexed(group._h, L.np_ptr(table), L.table_dtype_code(table.dtype), self.V, L.DIM,
+                                                         L.np_ptr(mapping), L.np_ptr(weights), n_tok, int(normalize), C.byref(self._h)))
+
+    def _token_info(self):
+        n, hm, hw, nb = C.c_uint64(), C.c_int(), C.c_int(), C.c_uint64()
+        L.check(L.lib().smt_sharded_model_token_info(self._h, C.byref(n), C.byref(hm), C.byref(hw), C.byref(nb)))
+        return int(n.value), bool(hm.value), bool(hw.value), int(nb.value)
+
+    n_tokens = property(lambda self: self._token_info()[0])
+    has_mapping = property(lambda self: self._token_info()[1])
+    has_weights = property(lambda self: self._token_info()[2])
+    token_bytes = property(lambda self: self._token_info()[3], doc="bytes of the token array, per replica")
 
     @property
     def table_bytes(self):

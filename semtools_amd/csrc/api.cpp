@@ -629,11 +629,104 @@ try {
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
+}  // extern "C"
+
+namespace smt {
+
+int check_indexed_args(const void *mapping, const void *weights, uint64_t n_tokens, uint64_t n_rows)
+{
+    if (!mapping && !weights) return SMT_OK;
+    if (n_tokens == 0) { set_error("invalid argument: n_tokens is 0 with a mapping or weights array given"); return SMT_E_INVALID; }
+    if (n_tokens > (1ull << 32)) { set_error("invalid argument: n_tokens %llu exceeds 2^32 (token ids are 32-bit)", (unsigned long long)n_tokens); return SMT_E_INVALID; }
+    if (!mapping && n_tokens != n_rows) {
+        set_error("invalid argument: without a mapping n_tokens (%llu) must equal n_rows (%llu)", (unsigned long long)n_tokens, (unsigned long long)n_rows);
+        return SMT_E_INVALID;
+    }
+    return SMT_OK;
+}
+
+int model_attach_tokens(smt_model *m, const uint32_t *mapping, const float *weights, uint64_t n_tokens, bool on_device)
+{
+    if (!mapping && !weights) return SMT_OK;
+    smt_ctx *ctx = m->ctx;
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    uint32_t *d_map = nullptr;
+    float *d_w = nullptr;
+    auto drop = [&] { if (d_map) (void)hipFree(d_map); if (d_w) (void)hipFree(d_w); };
+    const uint32_t *pm = mapping;
+    const float *pw = weights;
+    if (!on_device) {
+        hipError_t e = hipSuccess;
+        if (mapping) {
+            e = hipMalloc(reinterpret_cast<void **>(&d_map), n_tokens * sizeof(uint32_t));
+            if (e == hipSuccess) e = hipMemcpy(d_map, mapping, n_tokens * sizeof(uint32_t), hipMemcpyHostToDevice);
+            pm = d_map;
+        }
+        if (e == hipSuccess && weights) {
+            e = hipMalloc(reinterpret_cast<void **>(&d_w), n_tokens * sizeof(float));
+            if (e == hipSuccess) e = hipMemcpy(d_w, weights, n_tokens * sizeof(float), hipMemcpyHostToDevice);
+            pw = d_w;
+        }
+        if (e != hipSuccess) { drop(); set_error("uploading mapping / weights: %s", hipGetErrorString(e)); return SMT_E_HIP; }
+    }
+    void *tok = nullptr;
+    rc = build_token_array(ctx, pm, pw, n_tokens, m->V, &tok);
+    drop();
+    if (rc) return rc;
+    m->d_tok = tok;
+    m->n_tokens = n_tokens;
+    m->has_mapping = mapping != nullptr;
+    m->has_weights = weights != nullptr;
+    return SMT_OK;
+}
+
+}  // namespace smt
+
+extern "C" {
+
+int smt_model_create_indexed(smt_ctx *ctx, const void *table_host, int table_dtype, uint64_t n_rows, uint32_t D, const uint32_t *mapping_host,
+                             const float *weights_host, uint64_t n_tokens, int normalize, smt_model **out)
+try {
+    SMT_REQUIRE(out != nullptr, "out");
+    int rc = smt::check_indexed_args(mapping_host, weights_host, n_tokens, n_rows);
+    if (rc) return rc;
+    smt_model *m = nullptr;
+    if ((rc = smt_model_create_typed(ctx, table_host, table_dtype, n_rows, D, normalize, &m))) return rc;
+    if ((rc = smt::model_attach_tokens(m, mapping_host, weights_host, n_tokens, false))) { smt_model_destroy(m); return rc; }
+    *out = m;
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_model_create_from_device_indexed(smt_ctx *ctx, const void *table_dev, int table_dtype, uint64_t n_rows, uint32_t D,
+                                         const uint32_t *mapping_dev, const float *weights_dev, uint64_t n_tokens, int normalize, smt_model **out)
+try {
+    SMT_REQUIRE(out != nullptr, "out");
+    int rc = smt::check_indexed_args(mapping_dev, weights_dev, n_tokens, n_rows);
+    if (rc) return rc;
+    smt_model *m = nullptr;
+    if ((rc = smt_model_create_from_device_typed(ctx, table_dev, table_dtype, n_rows, D, normalize, &m))) return rc;
+    if ((rc = smt::model_attach_tokens(m, mapping_dev, weights_dev, n_tokens, true))) { smt_model_destroy(m); return rc; }
+    *out = m;
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_model_token_info(const smt_model *model, uint64_t *n_tokens, int *has_mapping, int *has_weights, uint64_t *token_bytes)
+try {
+    SMT_REQUIRE(model != nullptr, "model");
+    if (n_tokens) *n_tokens = model->d_tok ? model->n_tokens : model->V;   // (a plain model: every row is its own token)
+    if (has_mapping) *has_mapping = model->has_mapping ? 1 : 0;
+    if (has_weights) *has_weights = model->has_weights ? 1 : 0;
+    if (token_bytes) *token_bytes = model->d_tok ? model->n_tokens * 8 : 0;
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
 void smt_model_destroy(smt_model *model)
 {
     if (!model) return;
     (void)hipSetDevice(model->ctx->device);
     (void)hipStreamSynchronize(model->ctx->stream);
+    if (model->d_tok) (void)hipFree(model->d_tok);
     if (model->owned && model->d_table) (void)hipFree(model->d_table);
     delete model;
 }
@@ -807,7 +900,7 @@ try {
     int rc = bind_device(model->ctx);
     if (rc) return rc;
     return launch_embed(model->ctx, model->d_table, model->table_dtype, model->V, model->normalize, ids_dev, offsets_dev, n_lines,
-                        max_tokens, out_dev, 0);
+                        max_tokens, out_dev, 0, model->d_tok, model->n_tokens);
 } catch (...) { return smt::api_catch(); }
 
 int smt_embed(smt_model *model, const uint32_t *ids, const uint64_t *offsets, uint64_t n_lines, uint32_t max_tokens,
@@ -853,7 +946,7 @@ try {
         d_out = append_to->d_rows + (size_t)append_to->rows * append_to->dim;
     }
     rc = launch_embed(ctx, model->d_table, model->table_dtype, model->V, model->normalize, d_ids, d_off, n_lines, max_tokens, d_out,
-                      std::max<uint64_t>(n_ids, 1));
+                      std::max<uint64_t>(n_ids, 1), model->d_tok, model->n_tokens);
     if (rc) return rc;
     if (out_host)
         SMT_HIP_CHECK(hipMemcpyAsync(out_host, d_out, (size_t)n_lines * model->D * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));

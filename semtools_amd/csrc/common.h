@@ -200,6 +200,10 @@ struct smt_model {
     smt_ctx *ctx = nullptr;
     void *d_table = nullptr;       // [V x 256] elements of table_dtype, as stored
     int table_dtype = SMT_TABLE_F32;
+    // indexed form (smt_model_create_indexed): library-owned uint2 tok[n_tokens] = {table row, weight bits}; nullptr for a plain model
+    void *d_tok = nullptr;
+    uint64_t n_tokens = 0;
+    bool has_mapping = false, has_weights = false;
     uint64_t V = 0;
     uint32_t D = 0;
     int normalize = 1;
@@ -497,7 +501,15 @@ int require_queries_domain_host(const float *queries, uint32_t nq, const char *w
 // K1
 int launch_embed(smt_ctx *ctx, const void *table, int table_dtype, uint64_t V, int normalize, const uint32_t *ids,
                  const uint64_t *offsets, uint64_t n_lines, uint32_t max_tokens, float *out,
-                 uint64_t n_tokens_known /* total tokens of the batch when the host has the offsets, else 0 */);
+                 uint64_t n_tokens_known /* total tokens of the batch when the host has the offsets, else 0 */,
+                 const void *tok_array = nullptr /* indexed models: uint2 [n_tok] in device memory */, uint64_t n_tok = 0);
+// packs and validates the token array of an indexed model from DEVICE arrays (either may be null); SMT_E_INVALID names the first token
+// whose row is outside the table or whose weight is not finite.  *tok_out is hipMalloc'ed on success.
+int build_token_array(smt_ctx *ctx, const uint32_t *mapping_dev, const float *weights_dev, uint64_t n_tokens, uint64_t n_rows, void **tok_out);
+// the argument rules of the *_indexed creators, checked before anything is allocated
+int check_indexed_args(const void *mapping, const void *weights, uint64_t n_tokens, uint64_t n_rows);
+// gives a freshly created plain model its token array (nothing to do when both arrays are null); host arrays are uploaded first
+int model_attach_tokens(smt_model *m, const uint32_t *mapping, const float *weights, uint64_t n_tokens, bool on_device);
 
 // K3: batched queries, f32 MFMA with fused candidate selection.
 int launch_gemm_topk(smt_ctx *ctx, const ScanArgs &a);

@@ -559,6 +559,19 @@ try {
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
+int smt_model_create_from_file_indexed(smt_ctx *ctx, const char *path, uint64_t byte_offset, int table_dtype, uint64_t n_rows, uint32_t D,
+                                       const uint32_t *mapping_host, const float *weights_host, uint64_t n_tokens, int normalize, smt_model **out)
+try {
+    SMT_REQUIRE(out != nullptr, "out");
+    int rc = smt::check_indexed_args(mapping_host, weights_host, n_tokens, n_rows);
+    if (rc) return rc;
+    smt_model *m = nullptr;
+    if ((rc = smt_model_create_from_file_typed(ctx, path, byte_offset, table_dtype, n_rows, D, normalize, &m))) return rc;
+    if ((rc = smt::model_attach_tokens(m, mapping_host, weights_host, n_tokens, false))) { smt_model_destroy(m); return rc; }
+    *out = m;
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
 int smt_model_create_from_file(smt_ctx *ctx, const char *path, uint64_t byte_offset, uint64_t V, uint32_t D, int normalize,
                                smt_model **out)
 try {

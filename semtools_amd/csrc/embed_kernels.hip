@@ -29,6 +29,13 @@
 // flight instead of 64.  half -> f32 and int8 -> f32 lose nothing (half subnormals are normal f32 values; the FP16 denormal
 // mode stays at its default, on), the 16 accumulators per lane are the same independent f32 chains, and the norm chain walks
 // the dimensions in order whatever the ownership -- so a typed model gives the bits of the f32 model built from the widened table.
+//
+// Indexed tables (vocabulary-quantised models): the model also holds tok[n_tokens] = {row, weight bits}, built and validated once by
+// embed_pack_tokens_kernel from `mapping` (token id -> row) and `weights` (one scalar per token).  embed_indexed_kernel is the same body
+// with one more link: id -> tok[id] -> row pieces, each widened, multiplied by the weight (the product rounded to f32; contraction is
+// off, so no FMA) and added to the same 16 accumulators.  An id >= n_tokens adds nothing and still counts in the mean.  The output
+// is bit-identical to plain pooling over E'[t] = fl32(weights[t] * widen(table[mapping[t]])).  These semantics are this project's
+// restatement of newer model2vec versions; they are not pinned against a crate.
 #include "common.h"
 
 namespace smt {
@@ -103,8 +110,25 @@ __global__ void __launch_bounds__(256) embed_runs_kernel(const uint64_t *__restr
     run_start[g] = g == n_groups ? n_lines : lo;
 }
 
-template <typename T, bool PF>
-__global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
+// what embed_pack_tokens_kernel stores for nothing and the indexed PF kernel for a position without a known token: no table has 2^32 - 1 rows
+constexpr uint32_t EMBED_NO_ROW = 0xFFFFFFFFu;
+
+// where a group stands one step on (known before any row has arrived): whether this step completes its line, and the next step's
+// active flag, first token and line end
+__device__ __forceinline__ void one_step_on(bool active, uint32_t t, uint32_t t_end, uint32_t li, uint32_t n_run, uint32_t o_end,
+                                            uint32_t o_next, uint32_t max_tokens, bool &d0, bool &a1, uint32_t &t1, uint32_t &e1)
+{
+    d0 = active && t + 4 >= t_end;
+    a1 = d0 ? li + 1 < n_run : active;
+    t1 = d0 ? o_end : t + 4;
+    e1 = d0 ? o_next : t_end;
+    if (d0 && max_tokens != 0 && e1 - t1 > max_tokens) e1 = t1 + max_tokens;
+}
+
+// IX: the indexed form (header comment): token id -> tok[id] = {row, weight} -> row pieces, each widened, multiplied by the weight
+// (rounded to f32, no FMA) and added.  The plain form is the IX = false instantiation, unchanged.
+template <typename T, bool PF, bool IX>
+__device__ __forceinline__ void embed_body(const EmbedParams p, const uint2 *__restrict__ tok)
 {
 #pragma clang fp contract(off)
     constexpr bool F32 = std::is_same<T, float>::value;
@@ -144,10 +168,12 @@ __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
     // token range of the current line [t, t_end) (max_tokens applied), its token count, and the NEXT line's end (read one
     // line ahead: a group that moves on must not wait for a dependent offsets load)
     pos_t t = 0, t_end = 0, o_end = 0, o_next = 0;
+    pos_t o_next2 = 0;               // indexed PF kernel: the end of the line after the next (it looks two steps ahead)
     if (active) {
         t = (pos_t)(p.offsets[line0] - tb);
         o_end = (pos_t)(p.offsets[line0 + 1] - tb);
         o_next = 1 < n_run ? (pos_t)(p.offsets[line0 + 2] - tb) : o_end;
+        if constexpr (PF && IX) o_next2 = 2 < n_run ? (pos_t)(p.offsets[line0 + 3] - tb) : o_next;
         t_end = o_end;
         if (p.max_tokens != 0 && t_end - t > (pos_t)p.max_tokens) t_end = t + p.max_tokens;
     }
@@ -232,10 +258,34 @@ __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
     uint32_t nid = 0;
     const uint32_t *ids = p.ids + tb;
     if constexpr (PF) nid = (active && (t + (a & 3)) < t_end) ? ids[t + (a & 3)] : 0u;
+    // Indexed PF: a three-link chain ids -> tok[] -> rows.  The lane holds tok[id] of ITS token of the step about to run (`ntk`, fetched one
+    // step ahead) and the id of its token of the step after (`nid`, fetched two steps ahead), so a step still waits for one round trip.
+    // A position without a token, or with an id >= n_tokens, holds {EMBED_NO_ROW, +0}.
+    uint2 ntk = make_uint2(EMBED_NO_ROW, 0u);
+    if constexpr (PF && IX) {   // (prologue, once per run: two dependent loads)
+        const bool v0 = active && (t + (a & 3)) < t_end && (uint64_t)nid < p.V;
+        if (v0) ntk = tok[nid];
+        bool d0, a1;
+        pos_t t1, e1;
+        one_step_on(active, t, t_end, li, n_run, o_end, o_next, p.max_tokens, d0, a1, t1, e1);
+        nid = (a1 && (t1 + (a & 3)) < e1) ? ids[t1 + (a & 3)] : 0u;
+    }
     while (__any(active)) {
         piece_t r[TU][NC];
         uint32_t idq[TU] = {0u, 0u, 0u, 0u};
-        if constexpr (PF) {   // quad_perm broadcasts of lane u of every quad
+        uint32_t wcur = 0u;   // IX: the weight of the lane's token of this step (broadcast over the quad when it is added)
+        if constexpr (IX && !PF) {   // generic: both links inside the step, still one token per lane of a quad
+            const bool onq = active && (t + (a & 3)) < t_end;
+            const uint32_t idv = onq ? ids[t + (a & 3)] : 0u;
+            ntk = (onq && (uint64_t)idv < p.V) ? tok[idv] : make_uint2(EMBED_NO_ROW, 0u);
+        }
+        if constexpr (IX) {   // idq = the ROWS of the step's tokens
+            idq[0] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ntk.x, 0x00, 0xF, 0xF, false);
+            idq[1] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ntk.x, 0x55, 0xF, 0xF, false);
+            idq[2] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ntk.x, 0xAA, 0xF, 0xF, false);
+            idq[3] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ntk.x, 0xFF, 0xF, 0xF, false);
+            wcur = ntk.y;
+        } else if constexpr (PF) {   // quad_perm broadcasts of lane u of every quad
             idq[0] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)nid, 0x00, 0xF, 0xF, false);
             idq[1] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)nid, 0x55, 0xF, 0xF, false);
             idq[2] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)nid, 0xAA, 0xF, 0xF, false);
@@ -245,9 +295,11 @@ __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
         for (int u = 0; u < TU; ++u) {
             const bool on = active && (t + u) < t_end;
             uint64_t id;
-            if constexpr (PF) id = idq[u];
+            if constexpr (PF || IX) id = idq[u];
             else id = on ? (uint64_t)ids[t + u] : 0;
-            const bool ok = on && id < p.V;  // out-of-vocab ids contribute nothing
+            bool ok;
+            if constexpr (!IX) ok = on && id < p.V;  // out-of-vocab ids contribute nothing
+            else ok = on && idq[u] != EMBED_NO_ROW;  // (the pack kernel checked every row against the table: no guard here)
             // (plain loads, not nontemporal: natural text is Zipf-distributed and its hot rows must stay in L2 / MALL --
             // measured with the nt policy: Zipf ids 3.50 -> 4.59 ms, uniform ids 5.97 -> 6.27 ms; round 4: 3.18 -> 4.68, 6.56 -> 6.77)
             if constexpr (F32) {
@@ -262,7 +314,21 @@ __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
         }
         // where the group stands after this step -- known before any row has arrived
         const bool done = active && t + TU >= t_end;
-        if constexpr (PF) {
+        if constexpr (PF && IX) {
+            bool d0, a1;
+            pos_t t1, e1;
+            one_step_on(active, t, t_end, li, n_run, o_end, o_next, p.max_tokens, d0, a1, t1, e1);
+            // tok[] of the next step's token, from the id fetched a step ago
+            const bool v1 = a1 && (t1 + (a & 3)) < e1 && (uint64_t)nid < p.V;
+            ntk = v1 ? tok[nid] : make_uint2(EMBED_NO_ROW, 0u);
+            // the id of the token of the step after that: the next step may complete a line too
+            const bool d1 = a1 && t1 + TU >= e1;
+            const bool a2 = d1 ? li + (d0 ? 2u : 1u) < n_run : a1;
+            const pos_t t2 = d1 ? (d0 ? o_next : o_end) : t1 + TU;
+            pos_t e2 = d1 ? (d0 ? o_next2 : o_next) : e1;
+            if (d1 && p.max_tokens != 0 && e2 - t2 > (pos_t)p.max_tokens) e2 = t2 + p.max_tokens;
+            nid = (a2 && (t2 + (a & 3)) < e2) ? ids[t2 + (a & 3)] : 0u;
+        } else if constexpr (PF) {
             const bool n_active = done ? li + 1 < n_run : active;
             const pos_t nt = done ? o_end : t + TU;
             pos_t nt_end = done ? o_next : t_end;
@@ -272,7 +338,31 @@ __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
 #pragma unroll
         for (int u = 0; u < TU; ++u) {
             if (active && (t + u) < t_end) {  // token order: u ascending
-                if constexpr (F32) {
+                if constexpr (IX) {   // the product is rounded to f32, then added (contract off: no FMA); an unknown id adds +0 * +0
+                    const float w =   // (u is a constant once unrolled: one quad broadcast remains)
+                            __builtin_bit_cast(float, u == 0   ? __builtin_amdgcn_update_dpp(0, (int)wcur, 0x00, 0xF, 0xF, false)
+                                                      : u == 1 ? __builtin_amdgcn_update_dpp(0, (int)wcur, 0x55, 0xF, 0xF, false)
+                                                      : u == 2 ? __builtin_amdgcn_update_dpp(0, (int)wcur, 0xAA, 0xF, 0xF, false)
+                                                               : __builtin_amdgcn_update_dpp(0, (int)wcur, 0xFF, 0xF, 0xF, false));
+                    if constexpr (F32) {
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+                            acc[c].x = acc[c].x + w * r[u][c].x;
+                            acc[c].y = acc[c].y + w * r[u][c].y;
+                            acc[c].z = acc[c].z + w * r[u][c].z;
+                            acc[c].w = acc[c].w + w * r[u][c].w;
+                        }
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) {
+#pragma unroll
+                            for (int e = 0; e < EPL; ++e) {
+                                float &d = comp(acc[(EPL * c + e) >> 2], (EPL * c + e) & 3);
+                                d = d + w * (float)r[u][c][e];
+                            }
+                        }
+                    }
+                } else if constexpr (F32) {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         acc[c].x = acc[c].x + r[u][c].x;
@@ -311,7 +401,14 @@ __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
             active = li < n_run;
             t = o_end;
             o_end = o_next;
-            if (li + 1 < n_run) o_next = (pos_t)(p.offsets[line0 + li + 2] - tb);
+            // (register diet of the indexed f32 kernels: left alone the compiler keeps &offsets[line0] in two registers of its own across the
+            // loop -- and spills them; behind the empty asm the address is rebuilt from line0 where it is used, one instruction per line)
+            uint64_t lb = line0;
+            if constexpr (IX) asm volatile("" : "+v"(lb));
+            if constexpr (PF && IX) {
+                o_next = o_next2;
+                if (li + 2 < n_run) o_next2 = (pos_t)(p.offsets[lb + li + 3] - tb);
+            } else if (li + 1 < n_run) o_next = (pos_t)(p.offsets[lb + li + 2] - tb);
             t_end = o_end;
             if (p.max_tokens != 0 && t_end - t > (pos_t)p.max_tokens) t_end = t + p.max_tokens;
             cnt_cur = (float)(t_end - t > 0 ? t_end - t : 1);
@@ -321,9 +418,93 @@ __global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
     if (__any(has_pend)) finalize();
 }
 
-template <typename T>
-static void launch_embed_typed(smt_ctx *ctx, EmbedParams &p, unsigned blocks, uint64_t n_tokens_known)
+template <typename T, bool PF>
+__global__ void __launch_bounds__(256, 4) embed_kernel(EmbedParams p)
 {
+    embed_body<T, PF, false>(p, nullptr);
+}
+
+// the same over a model with a token array (a kernel name of its own: the plain instantiations stay what they are)
+template <typename T, bool PF>
+__global__ void __launch_bounds__(256, 4) embed_indexed_kernel(EmbedParams p, const uint2 *__restrict__ tok)
+{
+    embed_body<T, PF, true>(p, tok);
+}
+
+// The token array of an indexed model: tok[i] = {mapping[i] or i, bits of weights[i] or 1.0f}.  Validation happens here, once, so that
+// the gather needs none: the smallest i whose row is outside the table or whose weight is not finite goes to *first_bad (preset to
+// 2^64 - 1), and such an entry is stored as {EMBED_NO_ROW, +0}.
+__global__ void __launch_bounds__(256) embed_pack_tokens_kernel(const uint32_t *__restrict__ mapping, const float *__restrict__ weights,
+                                                                uint64_t n_tokens, uint64_t n_rows, uint2 *__restrict__ tok,
+                                                                unsigned long long *__restrict__ first_bad)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_tokens) return;
+    const uint32_t row = mapping ? mapping[i] : (uint32_t)i;
+    const uint32_t wbits = weights ? __builtin_bit_cast(uint32_t, weights[i]) : 0x3F800000u;
+    const bool bad = (uint64_t)row >= n_rows || (wbits & 0x7F800000u) == 0x7F800000u;   // (exponent all ones: inf or NaN)
+    if (bad) atomicMin(first_bad, (unsigned long long)i);
+    tok[i] = bad ? make_uint2(EMBED_NO_ROW, 0u) : make_uint2(row, wbits);
+}
+
+int build_token_array(smt_ctx *ctx, const uint32_t *mapping_dev, const float *weights_dev, uint64_t n_tokens, uint64_t n_rows,
+                      void **tok_out)
+{
+    *tok_out = nullptr;
+    SMT_REQUIRE(n_tokens > 0 && n_tokens <= (1ull << 32), "n_tokens must be in 1 .. 2^32 (token ids are 32-bit)");
+    SMT_REQUIRE(n_rows < EMBED_NO_ROW, "an indexed table has fewer than 2^32 - 1 rows");
+    uint2 *tok = nullptr;
+    unsigned long long *d_bad = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&tok), n_tokens * sizeof(uint2));
+    if (e != hipSuccess) { set_error("hipMalloc(%llu) for the token array: %s", (unsigned long long)(n_tokens * sizeof(uint2)), hipGetErrorString(e)); return SMT_E_NOMEM; }
+    e = hipMalloc(reinterpret_cast<void **>(&d_bad), sizeof(unsigned long long));
+    if (e != hipSuccess) { (void)hipFree(tok); set_error("hipMalloc for the token array: %s", hipGetErrorString(e)); return SMT_E_NOMEM; }
+    unsigned long long bad = ~0ull;
+    e = hipMemsetAsync(d_bad, 0xFF, sizeof(unsigned long long), ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(embed_pack_tokens_kernel, dim3((unsigned)((n_tokens + 255) / 256)), dim3(256), 0, ctx->stream, mapping_dev, weights_dev,
+                           n_tokens, n_rows, tok, d_bad);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    uint32_t row = 0;
+    float w = 1.0f;
+    if (e == hipSuccess && bad != ~0ull) {   // what the offending token holds, for the message
+        if (mapping_dev) e = hipMemcpy(&row, mapping_dev + bad, sizeof(row), hipMemcpyDeviceToHost);
+        else row = (uint32_t)bad;
+        if (e == hipSuccess && weights_dev) e = hipMemcpy(&w, weights_dev + bad, sizeof(w), hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d_bad);
+    if (e != hipSuccess) { (void)hipFree(tok); set_error("building the token array: %s", hipGetErrorString(e)); return SMT_E_HIP; }
+    if (bad != ~0ull) {
+        (void)hipFree(tok);
+        if ((uint64_t)row >= n_rows)
+            set_error("token %llu: mapping entry %u is outside the table (n_rows %llu)", bad, row, (unsigned long long)n_rows);
+        else set_error("token %llu: weight %g is not finite", bad, (double)w);
+        return SMT_E_INVALID;
+    }
+    *tok_out = tok;
+    return SMT_OK;
+}
+
+template <typename T>
+static void launch_embed_indexed(smt_ctx *ctx, EmbedParams &p, const uint2 *tok, unsigned blocks, uint64_t n_tokens_known)
+{
+    p.only_large = 0;
+    if (ctx->tune.embed_batched & 2) {
+        hipLaunchKernelGGL((embed_indexed_kernel<T, true>), dim3(blocks), dim3(256), 0, ctx->stream, p, tok);
+        if (n_tokens_known == 0 || n_tokens_known >= p.span_limit) {
+            p.only_large = 1;
+            hipLaunchKernelGGL((embed_indexed_kernel<T, false>), dim3(blocks), dim3(256), 0, ctx->stream, p, tok);
+        }
+    } else hipLaunchKernelGGL((embed_indexed_kernel<T, false>), dim3(blocks), dim3(256), 0, ctx->stream, p, tok);
+}
+
+template <typename T>
+static void launch_embed_typed(smt_ctx *ctx, EmbedParams &p, const uint2 *tok, unsigned blocks, uint64_t n_tokens_known)
+{
+    if (tok) return launch_embed_indexed<T>(ctx, p, tok, blocks, n_tokens_known);
     // (A/B: embed_batched bit 1 = ids prefetched one step ahead.  Probed in round 4 and removed: the same kernel at three waves per
     // SIMD without spills -- Zipf 3.11 -> 3.32 ms -- and nontemporal row loads -- 4.68 / 6.77 ms; profiles/r04_k1/)
     p.only_large = 0;
@@ -339,14 +520,16 @@ static void launch_embed_typed(smt_ctx *ctx, EmbedParams &p, unsigned blocks, ui
 }
 
 int launch_embed(smt_ctx *ctx, const void *table, int table_dtype, uint64_t V, int normalize, const uint32_t *ids,
-                 const uint64_t *offsets, uint64_t n_lines, uint32_t max_tokens, float *out, uint64_t n_tokens_known)
+                 const uint64_t *offsets, uint64_t n_lines, uint32_t max_tokens, float *out, uint64_t n_tokens_known,
+                 const void *tok_array, uint64_t n_tok)
 {
+    const uint2 *tok = static_cast<const uint2 *>(tok_array);
     if (n_lines == 0) return SMT_OK;
     SMT_REQUIRE(table_dtype == SMT_TABLE_F32 || table_dtype == SMT_TABLE_F16 || table_dtype == SMT_TABLE_I8, "unknown table dtype");
     EmbedParams p;
     p.table = static_cast<const unsigned char *>(table);
     p.kind = table_dtype;
-    p.V = V;
+    p.V = tok ? n_tok : V;   // what an id is checked against: the token array's length in the indexed form
     p.ids = ids;
     p.offsets = offsets;
     p.n_lines = n_lines;
@@ -385,9 +568,9 @@ int launch_embed(smt_ctx *ctx, const void *table, int table_dtype, uint64_t V, i
                            ctx->d_embed_runs);
     // embed_batched bit 2 (tests): the PF kernel leaves every run of 64 tokens or more to the generic kernel
     p.span_limit = (ctx->tune.embed_batched & 4) ? 64ull : EMBED_SPAN_LIMIT;
-    if (table_dtype == SMT_TABLE_F16) launch_embed_typed<_Float16>(ctx, p, (unsigned)blocks, n_tokens_known);
-    else if (table_dtype == SMT_TABLE_I8) launch_embed_typed<signed char>(ctx, p, (unsigned)blocks, n_tokens_known);
-    else launch_embed_typed<float>(ctx, p, (unsigned)blocks, n_tokens_known);
+    if (table_dtype == SMT_TABLE_F16) launch_embed_typed<_Float16>(ctx, p, tok, (unsigned)blocks, n_tokens_known);
+    else if (table_dtype == SMT_TABLE_I8) launch_embed_typed<signed char>(ctx, p, tok, (unsigned)blocks, n_tokens_known);
+    else launch_embed_typed<float>(ctx, p, tok, (unsigned)blocks, n_tokens_known);
     prof_end(ctx, "embed");
     SMT_HIP_CHECK(hipGetLastError());
     return SMT_OK;

@@ -401,18 +401,73 @@ StaticModel::StaticModel(smt_group *group, std::unique_ptr<Tokenizer> tok, const
     if (table_dtype != SMT_TABLE_F32 && table_dtype != SMT_TABLE_F16 && table_dtype != SMT_TABLE_I8) throw Error("unknown table dtype");
     lazy_dtype_ = table_dtype;
     lazy_row_bytes_ = (size_t)SMT_DIM * (table_dtype == SMT_TABLE_F32 ? 4 : table_dtype == SMT_TABLE_F16 ? 2 : 1);
-    const char *eager = getenv("SEMTOOLS_EAGER_MODEL");
-    if (eager && eager[0] == '1') {
-        check(smt_sharded_model_create_from_file_typed(group, path.c_str(), byte_offset, table_dtype, V, SMT_DIM, normalize ? 1 : 0, &model_),
-              "StaticModel");
-        return;
-    }
     lazy_path_ = path;
     lazy_offset_ = byte_offset;
     lazy_V_ = V;
+    n_tokens_ = V;
     lazy_normalize_ = normalize;
+    const char *eager = getenv("SEMTOOLS_EAGER_MODEL");
+    if (eager && eager[0] == '1') {
+        model_ = upload_full();
+        return;
+    }
     lazy_fd_ = open(path.c_str(), O_RDONLY);
     if (lazy_fd_ < 0) throw Error("cannot open " + path + ": " + strerror(errno));
+}
+
+StaticModel::StaticModel(smt_group *group, std::unique_ptr<Tokenizer> tok, const std::string &path, uint64_t byte_offset, uint64_t n_rows,
+                         bool normalize, int table_dtype, std::vector<uint32_t> mapping, std::vector<float> weights)
+    : group_(group), tok_(std::move(tok))
+{
+    if (table_dtype != SMT_TABLE_F32 && table_dtype != SMT_TABLE_F16 && table_dtype != SMT_TABLE_I8) throw Error("unknown table dtype");
+    if (!mapping.empty() && !weights.empty() && mapping.size() != weights.size()) throw Error("mapping and weights differ in length");
+    if (mapping.empty() && !weights.empty() && weights.size() != n_rows) throw Error("without a mapping, weights need one entry per table row");
+    // (checked here as well as by the pack kernel: the compact path indexes the file by these rows before any kernel sees them)
+    for (size_t i = 0; i < mapping.size(); ++i)
+        if (mapping[i] >= n_rows) throw Error("token " + std::to_string(i) + ": mapping entry " + std::to_string(mapping[i]) + " is outside the table");
+    for (size_t i = 0; i < weights.size(); ++i)
+        if (!std::isfinite(weights[i])) throw Error("token " + std::to_string(i) + ": weight is not finite");
+    lazy_dtype_ = table_dtype;
+    lazy_row_bytes_ = (size_t)SMT_DIM * (table_dtype == SMT_TABLE_F32 ? 4 : table_dtype == SMT_TABLE_F16 ? 2 : 1);
+    lazy_path_ = path;
+    lazy_offset_ = byte_offset;
+    lazy_V_ = n_rows;
+    lazy_normalize_ = normalize;
+    tok_map_ = std::move(mapping);
+    tok_w_ = std::move(weights);
+    n_tokens_ = !tok_map_.empty() ? tok_map_.size() : !tok_w_.empty() ? tok_w_.size() : n_rows;
+    const char *eager = getenv("SEMTOOLS_EAGER_MODEL");
+    if (eager && eager[0] == '1') {
+        model_ = upload_full();
+        return;
+    }
+    lazy_fd_ = open(path.c_str(), O_RDONLY);
+    if (lazy_fd_ < 0) throw Error("cannot open " + path + ": " + strerror(errno));
+}
+
+smt_sharded_model *StaticModel::upload_full() const
+{
+    smt_sharded_model *m = nullptr;
+    check(smt_sharded_model_create_from_file_indexed(group_, lazy_path_.c_str(), lazy_offset_, lazy_dtype_, lazy_V_, SMT_DIM,
+                                                     tok_map_.empty() ? nullptr : tok_map_.data(), tok_w_.empty() ? nullptr : tok_w_.data(),
+                                                     indexed() ? n_tokens_ : 0, lazy_normalize_ ? 1 : 0, &m),
+          "StaticModel (full table upload)");
+    return m;
+}
+
+void StaticModel::token_info(uint64_t *n_tokens, bool *has_mapping, bool *has_weights, uint64_t *token_bytes) const
+{
+    if (model_) {
+        int hm = 0, hw = 0;
+        check(smt_sharded_model_token_info(model_, n_tokens, &hm, &hw, token_bytes), "model token info");
+        if (has_mapping) *has_mapping = hm != 0;
+        if (has_weights) *has_weights = hw != 0;
+        return;
+    }
+    if (n_tokens) *n_tokens = n_tokens_;
+    if (has_mapping) *has_mapping = !tok_map_.empty();
+    if (has_weights) *has_weights = !tok_w_.empty();
+    if (token_bytes) *token_bytes = indexed() ? n_tokens_ * 8 : 0;
 }
 
 StaticModel::~StaticModel()
@@ -433,9 +488,7 @@ void StaticModel::table_info(int *table_dtype, uint64_t *V, uint64_t *table_byte
 smt_sharded_model *StaticModel::full_model() const
 {
     if (!model_) {
-        check(smt_sharded_model_create_from_file_typed(group_, lazy_path_.c_str(), lazy_offset_, lazy_dtype_, lazy_V_, SMT_DIM,
-                                                       lazy_normalize_ ? 1 : 0, &model_),
-              "StaticModel (full table upload)");
+        model_ = upload_full();
         PhaseTimer::mark("model_table_upload");
     }
     return model_;
@@ -448,28 +501,49 @@ void StaticModel::embed_csr(const std::vector<uint32_t> &ids, const std::vector<
         check(smt_sharded_embed(model_, ids.data(), offsets.data(), n_lines, 0, out_host, corpus, nullptr), "embed");
         return;
     }
-    // ---- lazy: which rows does this batch touch?
-    if (lazy_slot_.size() != lazy_V_) lazy_slot_.assign(lazy_V_, 0);
+    // ---- lazy: which tokens (plain model: rows) does this batch touch?
+    if (lazy_slot_.size() != n_tokens_) lazy_slot_.assign(n_tokens_, 0);
     std::vector<uint32_t> uniq;
     for (uint32_t id : ids) {
-        if (id >= lazy_V_) throw Error("token id outside the embedding table");
+        if (id >= n_tokens_) throw Error("token id outside the embedding table");
         if (!lazy_slot_[id]) { lazy_slot_[id] = 1; uniq.push_back(id); }
     }
     // a sizeable part of the table, or the 65th small call of this process (`semtools search` over hundreds of files embeds
     // them one by one; each compact table costs a device allocation and an upload): upload all of it, once
-    if ((uint64_t)uniq.size() * 16 > lazy_V_ || ++lazy_calls_ > 64) {
+    if ((uint64_t)uniq.size() * 16 > n_tokens_ || ++lazy_calls_ > 64) {
         for (uint32_t id : uniq) lazy_slot_[id] = 0;
         check(smt_sharded_embed(full_model(), ids.data(), offsets.data(), n_lines, 0, out_host, corpus, nullptr), "embed");
         return;
     }
     std::sort(uniq.begin(), uniq.end());          // file order: neighbouring rows share pages
     for (size_t s = 0; s < uniq.size(); ++s) lazy_slot_[uniq[s]] = (uint32_t)s + 1;
+    // indexed form: the distinct ROWS the touched tokens map to make the compact table; the compact token array keeps each touched
+    // token's own weight and points at its row's slot, so every product is the one the full model forms
+    const bool ix = indexed() && !uniq.empty();
+    std::vector<uint32_t> rows_store, cmap;
+    std::vector<float> cw;
+    if (ix) {
+        rows_store.reserve(uniq.size());
+        for (uint32_t t : uniq) rows_store.push_back(tok_map_.empty() ? t : tok_map_[t]);
+        std::sort(rows_store.begin(), rows_store.end());
+        rows_store.erase(std::unique(rows_store.begin(), rows_store.end()), rows_store.end());
+        cmap.resize(uniq.size());
+        for (size_t s = 0; s < uniq.size(); ++s) {
+            const uint32_t row = tok_map_.empty() ? uniq[s] : tok_map_[uniq[s]];
+            cmap[s] = (uint32_t)(std::lower_bound(rows_store.begin(), rows_store.end(), row) - rows_store.begin());
+        }
+        if (!tok_w_.empty()) {
+            cw.resize(uniq.size());
+            for (size_t s = 0; s < uniq.size(); ++s) cw[s] = tok_w_[uniq[s]];
+        }
+    }
+    const std::vector<uint32_t> &rows = ix ? rows_store : uniq;
     const size_t rb = lazy_row_bytes_;   // the compact table keeps the stored dtype (all-zero bytes are 0 in each of them)
-    std::vector<unsigned char> compact(std::max<size_t>(uniq.size(), 1) * rb, 0);
+    std::vector<unsigned char> compact(std::max<size_t>(rows.size(), 1) * rb, 0);
     try {
-        parallel_slices(uniq.size(), 512, [&](size_t sb, size_t se) {
+        parallel_slices(rows.size(), 512, [&](size_t sb, size_t se) {
             for (size_t s = sb; s < se; ++s) {
-                const off_t at = (off_t)(lazy_offset_ + (uint64_t)uniq[s] * rb);
+                const off_t at = (off_t)(lazy_offset_ + (uint64_t)rows[s] * rb);
                 if (pread(lazy_fd_, &compact[s * rb], rb, at) != (ssize_t)rb)
                     throw Error("short read from " + lazy_path_);
             }
@@ -482,7 +556,9 @@ void StaticModel::embed_csr(const std::vector<uint32_t> &ids, const std::vector<
     for (size_t i = 0; i < ids.size(); ++i) remapped[i] = lazy_slot_[ids[i]] - 1;
     for (uint32_t id : uniq) lazy_slot_[id] = 0;
     smt_sharded_model *tmp = nullptr;   // (a few MB: replicated like the full table)
-    check(smt_sharded_model_create_typed(group_, compact.data(), lazy_dtype_, std::max<size_t>(uniq.size(), 1), SMT_DIM, lazy_normalize_ ? 1 : 0, &tmp),
+    check(smt_sharded_model_create_indexed(group_, compact.data(), lazy_dtype_, std::max<size_t>(rows.size(), 1), SMT_DIM,
+                                           ix ? cmap.data() : nullptr, ix && !cw.empty() ? cw.data() : nullptr, ix ? uniq.size() : 0,
+                                           lazy_normalize_ ? 1 : 0, &tmp),
           "embed (compact table)");
     const int rc = smt_sharded_embed(tmp, remapped.data(), offsets.data(), n_lines, 0, out_host, corpus, nullptr);
     smt_sharded_model_destroy(tmp);

@@ -101,6 +101,11 @@ public:
     // SEMTOOLS_EAGER_MODEL=1 restores the eager upload.
     StaticModel(smt_group *group, std::unique_ptr<Tokenizer> tok, const std::string &path, uint64_t byte_offset, uint64_t V,
                 bool normalize, int table_dtype = SMT_TABLE_F32);
+    // the indexed form of a vocabulary-quantised directory (smt_model_create_indexed): `mapping` (token id -> table row) and / or
+    // `weights` (one scalar per token), each empty when the file has no such tensor, else n_tokens long.  Lazy like the form above: a
+    // small call uploads the distinct rows its tokens map to, a compact token array over the touched tokens and remapped ids.
+    StaticModel(smt_group *group, std::unique_ptr<Tokenizer> tok, const std::string &path, uint64_t byte_offset, uint64_t n_rows,
+                bool normalize, int table_dtype, std::vector<uint32_t> mapping, std::vector<float> weights);
     ~StaticModel();
     StaticModel(const StaticModel &) = delete;
 
@@ -130,6 +135,9 @@ public:
     // the table as the device holds it (or will, in lazy mode before the full upload: *resident = false): SMT_TABLE_* kind, rows,
     // bytes per replica
     void table_info(int *table_dtype, uint64_t *V, uint64_t *table_bytes, bool *resident) const;
+    // the token side (smt_model_token_info): token ids the model knows, whether it has a mapping / weights, bytes of the token array per
+    // replica (0 for a plain model)
+    void token_info(uint64_t *n_tokens, bool *has_mapping, bool *has_weights, uint64_t *token_bytes) const;
 
 private:
     void tokenize_batch(const std::string_view *sentences, size_t begin, size_t end,
@@ -149,6 +157,11 @@ private:
     uint64_t lazy_offset_ = 0, lazy_V_ = 0;
     bool lazy_normalize_ = true;
     int lazy_fd_ = -1;
+    std::vector<uint32_t> tok_map_;             // indexed form: token id -> table row (empty: identity)
+    std::vector<float> tok_w_;                  // indexed form: one weight per token (empty: 1)
+    uint64_t n_tokens_ = 0;                     // ids the model knows: the arrays' length, or lazy_V_ for a plain model
+    bool indexed() const { return !tok_map_.empty() || !tok_w_.empty(); }
+    smt_sharded_model *upload_full() const;
     mutable std::vector<uint32_t> lazy_slot_;   // id -> compact slot + 1 (0 = unseen), reset after every call
     mutable uint32_t lazy_calls_ = 0;           // compact-table calls so far: a long series of small calls gets the full table too
 };

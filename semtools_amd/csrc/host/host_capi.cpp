@@ -96,6 +96,77 @@ int safetensors_embeddings_span(const std::string &path, uint64_t &V, uint64_t &
     throw Error("unsupported embeddings dtype " + dtype + " (F32, F16, I8)");
 }
 
+// IEEE binary16 -> f32 by value
+float half_to_float(uint16_t h)
+{
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, ex = (h >> 10) & 0x1Fu, man = h & 0x3FFu;
+    uint32_t bits;
+    if (ex == 0x1F) bits = sign | 0x7F800000u | (man << 13);
+    else if (ex != 0) bits = sign | ((ex + 112u) << 23) | (man << 13);
+    else if (man == 0) bits = sign;
+    else {   // subnormal half: a normal f32
+        int e = -1;
+        uint32_t m = man;
+        do { ++e; m <<= 1; } while (!(m & 0x400u));
+        bits = sign | ((uint32_t)(112 - e) << 23) | ((m & 0x3FFu) << 13);
+    }
+    float f;
+    memcpy(&f, &bits, 4);
+    return f;
+}
+
+// the optional tensors of a vocabulary-quantised model: `mapping` [n_tokens] (I32 / I64 -> u32, a negative entry is an error) and
+// `weights` [n_tokens] (F64 / F32 / F16 -> f32 by value); a tensor that is absent leaves its vector empty
+void safetensors_token_arrays(const std::string &path, std::vector<uint32_t> &mapping, std::vector<float> &weights)
+{
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw Error("cannot open " + path);
+    uint64_t hlen = 0;
+    f.read(reinterpret_cast<char *>(&hlen), 8);
+    if (!f || hlen > (1ull << 30)) throw Error("bad safetensors header in " + path);
+    std::string hdr(hlen, '\0');
+    f.read(&hdr[0], (std::streamsize)hlen);
+    const json::Value h = json::parse(hdr);
+    auto raw = [&](const json::Value *t, const char *name, size_t elem, uint64_t &n) {
+        const auto &shape = t->get("shape")->arr;
+        if (shape.size() != 1 || shape[0].as_u64() == 0 || shape[0].as_u64() > (1ull << 32)) throw Error(std::string("'") + name + "' must be a non-empty vector");
+        n = shape[0].as_u64();
+        const uint64_t b = t->get("data_offsets")->arr[0].as_u64(), e = t->get("data_offsets")->arr[1].as_u64();
+        if (e - b != n * elem) throw Error(std::string("'") + name + "': data size does not match its shape");
+        std::vector<unsigned char> buf(n * elem);
+        f.seekg((std::streamoff)(8 + hlen + b));
+        f.read(reinterpret_cast<char *>(buf.data()), (std::streamsize)buf.size());
+        if (!f) throw Error(path + " is truncated");
+        return buf;
+    };
+    if (const json::Value *t = h.get("mapping")) {
+        const std::string dtype = t->get("dtype")->s;
+        if (dtype != "I32" && dtype != "I64") throw Error("unsupported mapping dtype " + dtype + " (I32, I64)");
+        uint64_t n = 0;
+        const auto buf = raw(t, "mapping", dtype == "I64" ? 8 : 4, n);
+        mapping.resize(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            int64_t v;
+            if (dtype == "I64") memcpy(&v, &buf[i * 8], 8);
+            else { int32_t x; memcpy(&x, &buf[i * 4], 4); v = x; }
+            if (v < 0 || v > (int64_t)0xFFFFFFFFll) throw Error("token " + std::to_string(i) + ": mapping entry " + std::to_string(v) + " is not a table row");
+            mapping[i] = (uint32_t)v;
+        }
+    }
+    if (const json::Value *t = h.get("weights")) {
+        const std::string dtype = t->get("dtype")->s;
+        if (dtype != "F64" && dtype != "F32" && dtype != "F16") throw Error("unsupported weights dtype " + dtype + " (F64, F32, F16)");
+        uint64_t n = 0;
+        const auto buf = raw(t, "weights", dtype == "F64" ? 8 : dtype == "F32" ? 4 : 2, n);
+        weights.resize(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            if (dtype == "F64") { double v; memcpy(&v, &buf[i * 8], 8); weights[i] = (float)v; }
+            else if (dtype == "F32") memcpy(&weights[i], &buf[i * 4], 4);
+            else { uint16_t v; memcpy(&v, &buf[i * 2], 2); weights[i] = half_to_float(v); }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -248,11 +319,25 @@ static int host_model_from_dir(smt_ctx *ctx, smt_group *group, const char *dir, 
             if (tj.good()) tok = make_hf_tokenizer(d + "/tokenizer.json");
             else tok = make_vocab_tokenizer(d + "/vocab.txt", unk);
         }
-        if (tok->vocab_size() > V) throw Error("vocab.txt has more tokens than the embedding table has rows");
+        // a vocabulary-quantised model: token id -> row and a scalar per token; the vocabulary is then checked against n_tokens
+        std::vector<uint32_t> mapping;
+        std::vector<float> weights;
+        safetensors_token_arrays(d + "/model.safetensors", mapping, weights);
+        const bool indexed = !mapping.empty() || !weights.empty();
+        if (!mapping.empty() && !weights.empty() && mapping.size() != weights.size()) throw Error("'mapping' and 'weights' differ in length");
+        const uint64_t n_tokens = !mapping.empty() ? mapping.size() : !weights.empty() ? weights.size() : V;
+        if (mapping.empty() && n_tokens != V) throw Error("'weights' without 'mapping' must have one entry per embedding row");
+        if (tok->vocab_size() > n_tokens)
+            throw Error(indexed ? "the vocabulary has more tokens than 'mapping' / 'weights' have entries"
+                                : "vocab.txt has more tokens than the embedding table has rows");
         search::PhaseTimer::mark("tokenizer_load");
         std::unique_ptr<smt_host_model> h(new smt_host_model());
         if (group) h->group.use(group); else h->group.wrap(ctx);
-        h->m = std::make_unique<search::StaticModel>(h->group.g, std::move(tok), d + "/model.safetensors", table_offset, V, normalize, table_dtype);
+        if (indexed)
+            h->m = std::make_unique<search::StaticModel>(h->group.g, std::move(tok), d + "/model.safetensors", table_offset, V, normalize, table_dtype,
+                                                         std::move(mapping), std::move(weights));
+        else
+            h->m = std::make_unique<search::StaticModel>(h->group.g, std::move(tok), d + "/model.safetensors", table_offset, V, normalize, table_dtype);
         *out = h.release();
         return SMT_OK;
     } catch (const std::exception &e) { return fail(e); }
@@ -270,6 +355,18 @@ int smt_host_model_table_info(const smt_host_model *model, int *table_dtype, uin
         bool res = false;
         model->m->table_info(table_dtype, V, table_bytes, &res);
         if (resident) *resident = res ? 1 : 0;
+        return SMT_OK;
+    } catch (const std::exception &e) { return fail(e); }
+}
+
+int smt_host_model_token_info(const smt_host_model *model, uint64_t *n_tokens, int *has_mapping, int *has_weights, uint64_t *token_bytes)
+{
+    if (!model || !model->m) { smt::set_error("null argument"); return SMT_E_INVALID; }
+    try {
+        bool hm = false, hw = false;
+        model->m->token_info(n_tokens, &hm, &hw, token_bytes);
+        if (has_mapping) *has_mapping = hm ? 1 : 0;
+        if (has_weights) *has_weights = hw ? 1 : 0;
         return SMT_OK;
     } catch (const std::exception &e) { return fail(e); }
 }

@@ -631,6 +631,44 @@ try {
     return sharded_model_make(group, [&](int i, smt_model **m) { return smt_model_create_from_file_typed(group->ctx[i], path, byte_offset, table_dtype, V, D, normalize, m); }, out);
 } catch (...) { return smt::api_catch(); }
 
+int smt_sharded_model_create_indexed(smt_group *group, const void *table_host, int table_dtype, uint64_t n_rows, uint32_t D,
+                                     const uint32_t *mapping_host, const float *weights_host, uint64_t n_tokens, int normalize,
+                                     smt_sharded_model **out)
+try {
+    SMT_REQUIRE(group && table_host && out, "null argument");
+    int rc = smt::check_indexed_args(mapping_host, weights_host, n_tokens, n_rows);
+    if (rc) return rc;
+    smt_sharded_model *sm = nullptr;
+    rc = sharded_model_make(group, [&](int i, smt_model **m) {
+        return smt_model_create_indexed(group->ctx[i], table_host, table_dtype, n_rows, D, mapping_host, weights_host, n_tokens, normalize, m); }, &sm);
+    if (rc) return rc;
+    *out = sm;
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_sharded_model_create_from_file_indexed(smt_group *group, const char *path, uint64_t byte_offset, int table_dtype, uint64_t n_rows,
+                                               uint32_t D, const uint32_t *mapping_host, const float *weights_host, uint64_t n_tokens,
+                                               int normalize, smt_sharded_model **out)
+try {
+    SMT_REQUIRE(group && path && out, "null argument");
+    int rc = smt::check_indexed_args(mapping_host, weights_host, n_tokens, n_rows);
+    if (rc) return rc;
+    smt_sharded_model *sm = nullptr;
+    rc = sharded_model_make(group, [&](int i, smt_model **m) {
+        return smt_model_create_from_file_indexed(group->ctx[i], path, byte_offset, table_dtype, n_rows, D, mapping_host, weights_host, n_tokens,
+                                                  normalize, m); }, &sm);
+    if (rc) return rc;
+    *out = sm;
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+/* smt_model_token_info of the replicas (they are alike): token_bytes is what ONE replica holds */
+int smt_sharded_model_token_info(const smt_sharded_model *model, uint64_t *n_tokens, int *has_mapping, int *has_weights, uint64_t *token_bytes)
+try {
+    SMT_REQUIRE(model != nullptr && !model->model.empty(), "model");
+    return smt_model_token_info(model->model[0], n_tokens, has_mapping, has_weights, token_bytes);
+} catch (...) { return smt::api_catch(); }
+
 int smt_sharded_model_info(const smt_sharded_model *model, int *table_dtype, uint64_t *V, uint64_t *table_bytes)
 try {
     SMT_REQUIRE(model != nullptr && !model->model.empty(), "model");

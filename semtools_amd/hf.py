@@ -13,13 +13,37 @@ import numpy as np
 from . import host
 
 
-def load_static_model(ctx, model_dir):
+def read_model_tensors(model_dir):
+    """(table as stored, uint32 mapping or None, float32 weights or None) of a model directory's model.safetensors.  `embeddings`
+    keeps its dtype (F32 / F16 / I8).  A vocabulary-quantised model also carries `mapping` [n_tokens] (I32 / I64: token id -> table
+    row; a negative entry is an error) and / or `weights` [n_tokens] (F64 / F32 / F16: one scalar per token, converted to float32 by
+    value).  The tokenizer's vocabulary belongs to n_tokens then, not to the table's rows."""
     from safetensors.numpy import load_file
+
+    from . import _lib as L
+
+    tensors = load_file(os.path.join(model_dir, "model.safetensors"))
+    table = np.ascontiguousarray(tensors["embeddings"])
+    L.table_dtype_code(table.dtype)
+    mapping, weights = tensors.get("mapping"), tensors.get("weights")
+    if mapping is not None and mapping.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+        raise TypeError(f"mapping dtype {mapping.dtype} is not supported (int32, int64)")
+    if weights is not None and weights.dtype not in (np.dtype(np.float64), np.dtype(np.float32), np.dtype(np.float16)):
+        raise TypeError(f"weights dtype {weights.dtype} is not supported (float64, float32, float16)")
+    mapping, weights, _ = L.token_arrays(mapping, weights, table.shape[0])
+    return table, mapping, weights
+
+
+def load_static_model(ctx, model_dir):
     from tokenizers import Tokenizer
 
     tok = Tokenizer.from_file(os.path.join(model_dir, "tokenizer.json"))
-    tensors = load_file(os.path.join(model_dir, "model.safetensors"))
-    emb = np.ascontiguousarray(tensors["embeddings"].astype(np.float32))
+    table, mapping, weights = read_model_tensors(model_dir)
+    if mapping is not None or weights is not None:
+        # (the callback-tokenizer creator takes a plain f32 table; the weights belong to the token, so nothing is remapped on the host)
+        raise NotImplementedError("a vocabulary-quantised model (mapping / weights) is served by host.StaticModel(ctx, model_dir=...), "
+                                  "which reads tokenizer.json natively")
+    emb = np.ascontiguousarray(table.astype(np.float32))
     normalize = True
     cfg_path = os.path.join(model_dir, "config.json")
     if os.path.exists(cfg_path):

@@ -85,6 +85,13 @@ class StaticModel:
     def table_bytes(self):
         return self.table_info()[2]
 
+    def token_info(self):
+        """(token ids the model knows, has a mapping, has weights, bytes of the token array per replica): the token side of a
+        vocabulary-quantised directory (`mapping` / `weights` beside `embeddings`); a plain model gives (rows, False, False, 0)"""
+        n, hm, hw, nb = C.c_uint64(), C.c_int(), C.c_int(), C.c_uint64()
+        L.check(L.lib().smt_host_model_token_info(self._h, C.byref(n), C.byref(hm), C.byref(hw), C.byref(nb)))
+        return int(n.value), bool(hm.value), bool(hw.value), int(nb.value)
+
     def encode_with_args(self, sentences, max_length=2048):
         out = np.empty((len(sentences), L.DIM), dtype=np.float32)
         L.check(L.lib().smt_host_encode(self._h, _cstrs(sentences), len(sentences), int(max_length or 0), L.np_ptr(out)))
