@@ -338,9 +338,17 @@ typedef struct smt_ivfpq_params {
 } smt_ivfpq_params;
 int smt_ivfpq_build(smt_corpus *corpus, const smt_ivfpq_params *params, smt_ivfpq **out);
 void smt_ivfpq_destroy(smt_ivfpq *index);
-/* nprobe lists scanned per query; in every probed list the `rerank` best ADC candidates
+/* nprobe lists scanned per query; in every probed list UP TO `rerank` ADC candidates
  * (0 = 512; range [4, 512]) are re-scored against the full-precision rows inside the scan
  * kernel, and the best top_k + 8 of all lists get the exact f64 distance.  top_k <= 56.
+ * `rerank` is a budget, not a count: the codes of a list (of each 8192-code segment of a long
+ * list) are dealt to the 4 or 8 waves of a block in groups of 64 (8 waves above a budget of 256;
+ * when nprobe leaves a long list fewer segments than it wants, the budget per segment grows by the
+ * same factor first), each wave keeps its own ceil(budget / waves) best, and it compares the top
+ * 16 bits of the f32 ADC distance (a relative step of 2^-7).  A list of 64 rows lies in one wave: rerank = 64 re-scores 16 of
+ * its rows, not all 64.  What IS guaranteed: a row is re-scored whenever fewer than
+ * ceil(rerank / 8) rows of its list have an ADC distance <= its own * (1 + 2^-7); and a list of
+ * at most 512 rows is re-scored entirely at rerank = 512 (tests/test_gpu_ivf_search_contract.py).
  * Outputs as in smt_search. */
 int smt_ivfpq_search(smt_ivfpq *index, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe,
                      uint32_t rerank, uint64_t row_base, uint64_t *out_rows, double *out_dist,
