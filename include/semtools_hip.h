@@ -358,6 +358,26 @@ int smt_ivfpq_search(smt_ivfpq *index, const float *queries, uint32_t nq, uint32
  * the context's stream, complete after smt_ctx_synchronize. */
 int smt_ivfpq_search_device(smt_ivfpq *index, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe,
                             uint32_t rerank, uint64_t row_base, uint64_t *out_rows_dev, double *out_dist_dev);
+/* The same search INSIDE ROW RANGES (the path subset of a workspace search): only rows of `ranges` are candidates.  Ranges are
+ * corpus-local row positions (before row_base is added), sorted and disjoint, begin <= end <= corpus rows, empty ones allowed, as in
+ * smt_search; a violation, or ranges == NULL with n_ranges > 0, is SMT_E_INVALID, found before anything is enqueued.  n_ranges == 0
+ * IS the unfiltered search: the same code path and the same bytes as smt_ivfpq_search.  Rows at or beyond the row count the index
+ * covers (appended to the corpus, not yet taken in by smt_ivfpq_append) are not in the index and are never returned.  A query gets
+ * fewer than top_k hits when its probed lists hold fewer rows of the ranges; counts and padding as in smt_ivfpq_search.
+ * How: every call turns the ranges into a bitmap over the index's list positions (one pass over the 4 B row ids, nothing kept
+ * between calls); the scan skips the positions whose bit is clear -- no code bytes are read for them -- and is otherwise the scan of
+ * smt_ivfpq_search.  Its guarantee therefore carries over with "rows" read as "in-range rows": a row is re-scored whenever fewer
+ * than ceil(rerank / 8) IN-RANGE rows of its list segment have an ADC distance <= its own * (1 + 2^-7); and a list with at most 512
+ * in-range rows per segment is re-scored entirely at rerank = 512 (tests/test_gpu_ivf_ranges.py). */
+int smt_ivfpq_search_ranges(smt_ivfpq *index, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe,
+                            uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, uint64_t row_base,
+                            uint64_t *out_rows, double *out_dist, uint64_t *out_counts, uint64_t out_cap);
+/* Device-resident form of the search inside ranges; `ranges` is a HOST array, copied into a pinned buffer of the context before the
+ * call returns.  Enqueued like smt_ivfpq_search_device: the call does not wait for the stream (only, when ranged calls follow each
+ * other, for the previous call's few-KiB range upload to have left that buffer). */
+int smt_ivfpq_search_ranges_device(smt_ivfpq *index, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe,
+                                   uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, uint64_t row_base,
+                                   uint64_t *out_rows_dev, double *out_dist_dev);
 /* build_ms4 = {coarse k-means, assign all rows, PQ training, sort + encode} */
 int smt_ivfpq_info(const smt_ivfpq *index, uint64_t *n_rows, uint32_t *nlist, uint64_t *index_bytes,
                    double *build_ms4);
@@ -556,6 +576,11 @@ void smt_sharded_ivfpq_destroy(smt_sharded_ivfpq *index);
 smt_ivfpq *smt_sharded_ivfpq_shard(smt_sharded_ivfpq *index, int local_index); /* smt_ivfpq_info etc.; NULL if out of range */
 int smt_sharded_ivfpq_search(smt_sharded_ivfpq *index, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe,
                              uint32_t rerank, uint64_t *out_rows, double *out_dist, uint64_t *out_counts, uint64_t out_cap);
+/* Inside GLOBAL row ranges (rules as in smt_sharded_search; n_ranges == 0 is smt_sharded_ivfpq_search): every rank searches its
+ * index inside its part of the ranges (smt_ivfpq_search_ranges), a rank they leave nothing contributes nothing. */
+int smt_sharded_ivfpq_search_ranges(smt_sharded_ivfpq *index, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe,
+                                    uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, uint64_t *out_rows,
+                                    double *out_dist, uint64_t *out_counts, uint64_t out_cap);
 /* Life cycle, shard by shard (smt_ivfpq_save / _load / _append / _info on every local rank).  A one-rank group uses `path`
  * itself; otherwise rank r's part is `<path>.r<r>of<n_ranks>` -- the files name LOCAL rows by position, so they are valid
  * for the layout they were built on (persist it with smt_sharded_corpus_layout, restore it with _load_layout).

@@ -313,6 +313,34 @@ extern "C" {
         out_rows_dev: *mut u64,
         out_dist_dev: *mut f64,
     ) -> c_int;
+    pub fn smt_ivfpq_search_ranges(
+        index: *mut SmtIvfpq,
+        queries: *const f32,
+        nq: u32,
+        top_k: u32,
+        nprobe: u32,
+        rerank: u32,
+        ranges: *const SmtRange,
+        n_ranges: u32,
+        row_base: u64,
+        out_rows: *mut u64,
+        out_dist: *mut f64,
+        out_counts: *mut u64,
+        out_cap: u64,
+    ) -> c_int;
+    pub fn smt_ivfpq_search_ranges_device(
+        index: *mut SmtIvfpq,
+        queries_dev: *const f32,
+        nq: u32,
+        top_k: u32,
+        nprobe: u32,
+        rerank: u32,
+        ranges: *const SmtRange,
+        n_ranges: u32,
+        row_base: u64,
+        out_rows_dev: *mut u64,
+        out_dist_dev: *mut f64,
+    ) -> c_int;
     pub fn smt_ivfpq_info(
         index: *const SmtIvfpq,
         n_rows: *mut u64,
@@ -562,6 +590,20 @@ extern "C" {
         top_k: u32,
         nprobe: u32,
         rerank: u32,
+        out_rows: *mut u64,
+        out_dist: *mut f64,
+        out_counts: *mut u64,
+        out_cap: u64,
+    ) -> c_int;
+    pub fn smt_sharded_ivfpq_search_ranges(
+        index: *mut SmtShardedIvfpq,
+        queries: *const f32,
+        nq: u32,
+        top_k: u32,
+        nprobe: u32,
+        rerank: u32,
+        ranges: *const SmtRange,
+        n_ranges: u32,
         out_rows: *mut u64,
         out_dist: *mut f64,
         out_counts: *mut u64,

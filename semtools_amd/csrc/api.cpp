@@ -403,6 +403,8 @@ void smt_ctx_destroy(smt_ctx *ctx)
     if (ctx->d_embed_runs) (void)hipFree(ctx->d_embed_runs);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
     if (ctx->h_pinned_in) (void)hipHostFree(ctx->h_pinned_in);
+    if (ctx->h_ivf_ranges) (void)hipHostFree(ctx->h_ivf_ranges);
+    if (ctx->ivf_ranges_up) (void)hipEventDestroy(ctx->ivf_ranges_up);
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;

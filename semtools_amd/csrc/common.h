@@ -112,6 +112,12 @@ struct smt_ctx {
     size_t pinned_in_bytes = 0;
     void *d_stage = nullptr;   // smt_search's per-call inputs/outputs (queries, ranges, result lists)
     size_t stage_bytes = 0;
+    // smt_ivfpq_search_ranges and its forms: the call's ranges on their way up.  Pinned, so the upload is enqueued without waiting for
+    // the stream, and its own buffer (not h_pinned_in), because the _device form returns before the upload has run: ivf_ranges_up
+    // marks the latest upload's end, and the next ranged call waits for THAT before it overwrites the buffer (ivfpq_search.hip).
+    void *h_ivf_ranges = nullptr;
+    size_t ivf_ranges_bytes = 0;
+    hipEvent_t ivf_ranges_up = nullptr;
     // async select (tuning key async_select): the select of query i runs on aux_stream WHILE query i+1 scans;
     // the two kernels meet through device-scope flags, not stream events
     hipStream_t aux_stream = nullptr;
@@ -231,6 +237,20 @@ int launch_pack_image(smt_ctx *ctx, const float *corpus, uint64_t n_rows, uint64
 // compact.hip: keep exactly the rows inside `keep` (sorted, disjoint, inside [0, rows)) and close the gaps in place -- the body of
 // smt_corpus_compact.  Validates first: a refused list leaves the corpus untouched.
 int corpus_compact(smt_corpus *c, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved);
+// The range rules of smt_search for the callers that check them on their own, before they enqueue anything (the sharded searches on
+// GLOBAL rows, the IVF search inside ranges): a list where n > 0, begin <= end <= rows, sorted and disjoint; empty ranges allowed.
+inline int validate_ranges(const smt_range *ranges, uint32_t n, uint64_t rows)
+{
+    SMT_REQUIRE(n == 0 || ranges != nullptr, "ranges");
+    uint64_t prev_end = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        SMT_REQUIRE(ranges[i].begin <= ranges[i].end, "range begin > end");
+        SMT_REQUIRE(ranges[i].end <= rows, "range extends past the corpus");
+        SMT_REQUIRE(i == 0 || ranges[i].begin >= prev_end, "ranges must be sorted and disjoint");
+        prev_end = ranges[i].end;
+    }
+    return SMT_OK;
+}
 int ensure_scratch(smt_ctx *ctx, size_t bytes);
 int ensure_pinned(smt_ctx *ctx, size_t bytes);
 int ensure_pinned_in(smt_ctx *ctx, size_t bytes);
@@ -483,7 +503,7 @@ struct smt_ivfpq_params;
 namespace smt {
 int ivfpq_build_shared(smt_corpus *corpus, const smt_ivfpq_params *prm, const IvfBuildShare *share, smt_ivfpq **out);
 int ivfpq_search_packed(smt_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
-                        uint64_t row_base, uint64_t *packed_dev);
+                        const smt_range *ranges_local, uint32_t n_ranges, bool filtered, uint64_t row_base, uint64_t *packed_dev);
 
 // domain.hip: the numeric domain of rows and queries (finite, largest magnitude 0 or within [2^-40, 2^40]) and its checks
 constexpr uint32_t DOMAIN_MIN_BITS = 0x2B800000u;   // 2^-40f

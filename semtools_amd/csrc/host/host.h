@@ -347,12 +347,14 @@ public:
     // Approximate index policy -- OPT-IN (min_rows = UINT64_MAX, the default, never uses it: the reference's store always
     // searches with `exact: true`, src/workspace/store.rs:619,632).  When enabled (SEMTOOLS_INDEX_MIN_ROWS, or
     // "approximate_index_min_rows" in the workspace's config.json), whole-workspace searches (the path subset covers
-    // every stored document) over at least `min_rows` rows go through an IVF index with per-list PCA codes (local_pca = 1) that lives
+    // every stored document) of a store of at least `min_rows` rows, and searches over a path subset that itself holds at least
+    // `min_rows` rows (smt_sharded_ivfpq_search_ranges: the index searched inside the subset's row ranges, so dead rows never
+    // come back and no head-room is fetched), go through an IVF index with per-list PCA codes (local_pca = 1) that lives
     // beside the vectors (`line_index.ivf`), is extended incrementally when rows are appended and rebuilt when rows
     // move (compaction) or the corpus has doubled.  oversample_factor (WorkspaceConfig, src/workspace/mod.rs:13,22 --
     // vestigial in the reference, whose store scans exactly) sets the re-score depth: 2 * top_k * oversample_factor
     // ADC candidates per probed list (at least 64) are re-scored against the full-precision rows.  Every returned
-    // distance is exact; only membership is approximate.  Searches over a path subset, top_k > 24, or smaller
+    // distance is exact; only membership is approximate.  Searches over a smaller path subset, top_k > 24, or smaller
     // stores use the exact scan, and so does a search to which the index returns fewer than top_k live rows.
     void set_index_policy(size_t oversample_factor, uint64_t min_rows, uint32_t nprobe);
     bool has_index() const { return index_ != nullptr || index_on_disk_; }

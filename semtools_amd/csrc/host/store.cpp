@@ -748,19 +748,28 @@ std::vector<RankedLine> Store::search_line_embeddings(const std::vector<float> &
     std::vector<double> dist(top_k);
     uint64_t n = 0;
     bool answered = false;
-    // ---- approximate path: whole-workspace search over a large store (see set_index_policy)
+    // ---- approximate path: a search over a large store, or over a large subset of one (see set_index_policy)
     uint64_t ranged = 0;
     for (auto &r : ranges) ranged += r.end - r.begin;
-    if (smt_sharded_corpus_rows(corpus_) >= index_min_rows_ && top_k <= 24 && ranged == count_line_embeddings() && ensure_index()) {
-        const uint32_t fetch = (uint32_t)std::min<size_t>(56, 2 * top_k + 8);  // head-room for dead rows and the threshold
+    const bool whole = ranged == count_line_embeddings();
+    if (smt_sharded_corpus_rows(corpus_) >= index_min_rows_ && top_k <= 24 && (whole || ranged >= index_min_rows_) && ensure_index()) {
+        // every stored line: the unfiltered search, with head-room for dead rows (the host drops them below) and the threshold;
+        // a real subset: the search inside its ranges -- dead rows lie outside every range, so top_k candidates are enough
+        const uint32_t fetch = whole ? (uint32_t)std::min<size_t>(56, 2 * top_k + 8) : (uint32_t)top_k;
         const uint32_t rerank = (uint32_t)std::min<size_t>(512, std::max<size_t>(64, 2 * top_k * oversample_factor_));
         std::vector<uint64_t> c_rows(fetch);
         std::vector<double> c_dist(fetch);
         uint64_t c_n = 0;
         uint32_t n_lists = 0;
         check(smt_sharded_ivfpq_info(index_, nullptr, &n_lists, nullptr), "search_line_embeddings (index)");
-        check(smt_sharded_ivfpq_search(index_, query_vec.data(), 1, fetch, std::min<uint32_t>(std::min<uint32_t>(index_nprobe_, n_lists), 512),
-                                       rerank, c_rows.data(), c_dist.data(), &c_n, fetch), "search_line_embeddings (index)");
+        const uint32_t nprobe = std::min<uint32_t>(std::min<uint32_t>(index_nprobe_, n_lists), 512);
+        if (whole)
+            check(smt_sharded_ivfpq_search(index_, query_vec.data(), 1, fetch, nprobe, rerank, c_rows.data(), c_dist.data(), &c_n, fetch),
+                  "search_line_embeddings (index)");
+        else
+            check(smt_sharded_ivfpq_search_ranges(index_, query_vec.data(), 1, fetch, nprobe, rerank, ranges.data(), (uint32_t)ranges.size(),
+                                                  c_rows.data(), c_dist.data(), &c_n, fetch),
+                  "search_line_embeddings (index, subset)");
         const float thr_score = max_distance ? 1.0f - *max_distance : 0.0f;
         bool cut_by_threshold = false;
         for (uint64_t i = 0; i < c_n && n < top_k; ++i) {
@@ -773,7 +782,7 @@ std::vector<RankedLine> Store::search_line_embeddings(const std::vector<float> &
         }
         // A short list is only an answer when the THRESHOLD cut it (the candidates are sorted by exact distance, so
         // nothing behind the cut passes either).  Otherwise -- dead rows crowded the list, the probed lists held fewer
-        // than top_k rows -- the exact scan answers.
+        // than top_k rows (of the subset) -- the exact scan answers.
         answered = n == top_k || cut_by_threshold;
         if (!answered) n = 0;
     }

@@ -2,6 +2,8 @@
 // per-list projection, the ADC scan with its in-kernel re-score of the shortlist, and the search entry points.  ivfpq.h, DESIGN.md 4.6.
 #include <atomic>
 #include <chrono>
+#include <cstddef>
+#include <type_traits>
 
 #include "ivfpq.h"
 
@@ -180,7 +182,58 @@ struct AdcParams {
     uint32_t shortlist;        // ADC candidates kept per WAVE (<= 64); 4 or 8 waves per (query, list segment)
     uint32_t kp;               // re-scored candidates emitted per (query, list)  (<= 64)
     key_t64 *lists;            // [nq][nprobe][kp]
+    const uint64_t *mask;      // RANGED: one bit per list position, set = the row lies in the caller's ranges (ivf_range_mask_kernel)
 };
+
+static_assert(std::is_standard_layout_v<AdcParams> && std::is_trivially_copyable_v<AdcParams>,
+              "the RANGED re-score stage reads AdcParams fields from the kernel-argument segment by offsetof");
+
+// ------------------------------------------------------------------ query: row ranges -> a bitmap in LIST order
+// A search inside row ranges (smt_ivfpq_search_ranges) scans the same lists and skips the positions whose row lies outside.  The
+// bitmap is in LIST order because that is the order the ADC scan walks: a wave's 64 consecutive positions lie in at most two
+// adjacent words, where a bitmap in row order would cost one random 4-byte read per code through ids[].
+// One lane per position, one wave per 64-bit word: a coalesced load of ids[p], a binary search of the sorted, disjoint, non-empty
+// ranges (staged in LDS when they fit, read from global memory otherwise), one ballot, one 8-byte store by lane 0.  A block takes
+// MASK_WORDS_PER_WAVE words per wave, so the ranges are staged once per 4096 positions.  No atomics; nothing is read but ids[0, n_rows) and
+// ranges[0, n_ranges); positions at or past n_rows in the last word come out 0.
+constexpr int MASK_THREADS = 256;
+constexpr int MASK_WORDS_PER_WAVE = 16;
+constexpr uint32_t MASK_LDS_RANGES = 1024;   // 16 KiB
+
+__global__ void __launch_bounds__(MASK_THREADS) ivf_range_mask_kernel(const uint32_t *ids, uint64_t n_rows, const smt_range *ranges,
+                                                                       uint32_t n_ranges, uint64_t *mask)
+{
+    __shared__ smt_range s_ranges[MASK_LDS_RANGES];
+    const bool staged = n_ranges <= MASK_LDS_RANGES;   // block-uniform
+    if (staged) {
+        for (uint32_t e = threadIdx.x; e < n_ranges; e += MASK_THREADS) s_ranges[e] = ranges[e];
+        __syncthreads();
+    }
+    // the last range with begin <= row, if there is one, is the only one that can hold the row
+    auto inside = [n_ranges](const smt_range *r, uint64_t row) -> bool {
+        uint32_t lo = 0, hi = n_ranges;   // #(begin <= row) lies in [lo, hi]
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (r[mid].begin <= row) lo = mid + 1; else hi = mid;
+        }
+        return lo != 0 && row < r[lo - 1].end;
+    };
+    const int lane = threadIdx.x & 63;
+    const uint64_t n_words = (n_rows + 63) >> 6;
+    const uint64_t w0 = ((uint64_t)blockIdx.x * (MASK_THREADS / 64) + (threadIdx.x >> 6)) * MASK_WORDS_PER_WAVE;
+    for (int u = 0; u < MASK_WORDS_PER_WAVE; ++u) {
+        const uint64_t w = w0 + u;
+        if (w >= n_words) return;   // wave-uniform
+        const uint64_t p = w * 64 + lane;
+        bool in = false;
+        if (p < n_rows) {
+            const uint64_t row = ids[p];
+            in = staged ? inside(s_ranges, row) : inside(ranges, row);
+        }
+        const unsigned long long word = __ballot(in);
+        if (lane == 0) mask[w] = word;
+    }
+}
 
 // KIND 0: product quantisation, the query's 256 x 32 LUT staged in LDS (32 KiB: 4 blocks per CU); KIND 1: per-list PCA codes scored
 // with 32 block-uniform weights -- no LUT, 2-4 KiB of LDS per block, so the register budget (50 VGPRs) decides the occupancy:
@@ -194,7 +247,10 @@ struct AdcParams {
 // the index, its files or its append path): each lane rotates its 32-byte record by l mod 32 bytes in registers -- three conditional
 // dword stages and one v_alignbyte per dword, 32 VALU instructions per row beside the 96 of the lookups.  (Until round 5 both kinds were one kernel and the unused LUT array halved the resident waves of
 // the shipped coding: the re-score stage is random 1 KiB row reads, i.e. latency hidden by waves in flight.)
-template <int ADC_THREADS, int KIND>
+// RANGED: the search is inside row ranges; a position whose bit in p.mask is 0 stays empty -- no code bytes are loaded for it and it
+// never becomes a candidate -- and everything after the distances (shortlists, bisection, compaction, re-score, merge) is the same
+// code, so what holds for "the rows of a list segment" without ranges holds for its IN-RANGE rows with them.
+template <int ADC_THREADS, int KIND, bool RANGED>
 __global__ void __launch_bounds__(ADC_THREADS) ivf_adc_kernel(AdcParams p)
 {
     __shared__ __attribute__((aligned(16))) float s_lut[KIND == 0 ? PQ_M * PQ_K : 4];
@@ -286,6 +342,16 @@ __global__ void __launch_bounds__(ADC_THREADS) ivf_adc_kernel(AdcParams p)
     float ld = __builtin_inff();       // carried set: lane i < n_carry holds a real entry
     uint32_t lr = 0xFFFFFFFFu;
     key_t64 *s_short = s_keys + wave * 64;  // per-wave compaction scratch (s_keys is reused by the block merge later)
+    // RANGED: a lane's positions lie whole multiples of 64 apart, so its mask bits share ONE bit index and their words follow from
+    // one per-lane pointer that moves with the passes -- three VGPRs; the kernel argument's two SGPRs are free again after this line
+    // (the per-list PCA kind keeps its 32 weights in SGPRs and has none to spare)
+    const uint64_t *mword = nullptr;
+    uint32_t mshift = 0;
+    if constexpr (RANGED) {
+        const uint64_t first = begin + (uint64_t)wave * 64 + (uint64_t)lane;
+        mword = p.mask + (first >> 6);
+        mshift = (uint32_t)first & 63u;
+    }
     // (64-code groups are dealt to the waves round-robin, so every wave sees codes from the whole list: lists are in
     // row order and neighbours cluster -- contiguous 512-code chunks per wave cost a point of recall)
     for (uint64_t base_i = begin; base_i < end; base_i += (uint64_t)(ADC_THREADS / 64) * 64 * ADC_R) {
@@ -295,7 +361,11 @@ __global__ void __launch_bounds__(ADC_THREADS) ivf_adc_kernel(AdcParams p)
             const uint64_t i = base_i + ((uint64_t)r * (ADC_THREADS / 64) + wave) * 64 + lane;
             kd[r] = 0xFFFFFFFFu;
             kpos[r] = 0xFFFFFFFFu;
-            if (i < end) {
+            bool take = i < end;
+            if constexpr (RANGED) {   // bit i of the mask (a wave reads at most two adjacent words; none is read past the list's end)
+                if (take) take = ((mword[r * (ADC_THREADS / 64)] >> mshift) & 1ull) != 0ull;
+            }
+            if (take) {
                 const uint4 c0 = reinterpret_cast<const uint4 *>(p.codes + i * PQ_M)[0];
                 const uint4 c1 = reinterpret_cast<const uint4 *>(p.codes + i * PQ_M)[1];
                 const uint32_t w[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
@@ -387,6 +457,7 @@ __global__ void __launch_bounds__(ADC_THREADS) ivf_adc_kernel(AdcParams p)
         __builtin_amdgcn_wave_barrier();
         ld = mine != KEY_PAD ? __uint_as_float((uint32_t)(mine >> 32) << 16) : __builtin_inff();
         lr = mine != KEY_PAD ? (uint32_t)(mine & 0xFFFFFFFFull) : 0xFFFFFFFFu;
+        if constexpr (RANGED) mword += (ADC_THREADS / 64) * ADC_R;
     }
 
     // (An int8 refinement stage between the two -- a 260 B/row copy of the rows ranking the shortlist so that only a few
@@ -397,7 +468,23 @@ __global__ void __launch_bounds__(ADC_THREADS) ivf_adc_kernel(AdcParams p)
 
     // ---- stage 2: re-score the survivors with the full-precision rows (coalesced 1 KiB loads, f32),
     //      keep the kp best; the select stage then recomputes those exactly in f64
-    const uint32_t my_row = (lane < n_short && ((go >> lane) & 1ull)) ? p.ids[lr] : 0xFFFFFFFFu;  // one gather, before the loop
+    // RANGED: the two pointers of this stage are read from the kernel arguments HERE.  Left to the compiler they are loaded at the
+    // kernel's entry and held in SGPRs across the scan loop, where the mask test's second level of lane masks takes two more than
+    // the per-list PCA kind has (its 32 weights live there): it spilled p.corpus.  (The kernel's only argument is p, by value, so it
+    // sits at offset 0 of the kernel-argument segment; AdcParams is standard-layout, see the static_assert below it.  What guards
+    // this workaround is tests/test_ivf_ranges_resources.py: 0 spills and the twin's occupancy step for every RANGED instantiation --
+    // a compiler that no longer needs it shows there as well, and the block can then go.)
+    const uint32_t *ids = p.ids;
+    const float *corpus = p.corpus;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (RANGED) {
+        const char *ka = reinterpret_cast<const char *>(__builtin_amdgcn_kernarg_segment_ptr());
+        asm volatile("" : "+s"(ka));   // (opaque: nothing read through it moves above this line)
+        ids = *reinterpret_cast<const uint32_t *const *>(ka + offsetof(AdcParams, ids));
+        corpus = *reinterpret_cast<const float *const *>(ka + offsetof(AdcParams, corpus));
+    }
+#endif
+    const uint32_t my_row = (lane < n_short && ((go >> lane) & 1ull)) ? ids[lr] : 0xFFFFFFFFu;  // one gather, before the loop
     float ld2 = __builtin_inff();
     uint32_t lr2 = 0xFFFFFFFFu;
     float thr2_d = __builtin_inff();
@@ -417,7 +504,7 @@ __global__ void __launch_bounds__(ADC_THREADS) ivf_adc_kernel(AdcParams p)
             const int src = ok[u] ? __ffsll((long long)go) - 1 : 0;
             if (ok[u]) go &= go - 1;
             rr[u] = (uint32_t)__builtin_amdgcn_readlane((int)my_row, src);
-            c[u] = reinterpret_cast<const f32x4 *>(p.corpus + (uint64_t)(ok[u] ? rr[u] : 0u) * 256)[lane];
+            c[u] = reinterpret_cast<const f32x4 *>(corpus + (uint64_t)(ok[u] ? rr[u] : 0u) * 256)[lane];
         }
         // four rows' norms and dot products reduced together (device_utils.h wave_sum4: lane l ends with the sum of row l % 4)
 #pragma unroll
@@ -457,10 +544,33 @@ __global__ void __launch_bounds__(ADC_THREADS) ivf_adc_kernel(AdcParams p)
 using namespace smt;
 
 
+// The pinned buffer a ranged call writes its ranges into (smt_ctx::h_ivf_ranges), at least `bytes` long and free to be overwritten:
+// the previous ranged call's upload has left it.  Waiting for that upload's event is not waiting for the stream -- the searches
+// enqueued since go on running -- and a buffer that is never reused while in flight is what lets the _device form return at once.
+static int ranges_pinned(smt_ctx *ctx, size_t bytes, smt_range **pin)
+{
+    if (!ctx->ivf_ranges_up) IVF_HIP(hipEventCreateWithFlags(&ctx->ivf_ranges_up, hipEventDisableTiming));
+    else IVF_HIP(hipEventSynchronize(ctx->ivf_ranges_up));
+    if (bytes > ctx->ivf_ranges_bytes) {
+        if (ctx->h_ivf_ranges) IVF_HIP(hipHostFree(ctx->h_ivf_ranges));
+        ctx->h_ivf_ranges = nullptr;
+        ctx->ivf_ranges_bytes = 0;
+        const size_t want = std::max(bytes, (size_t)1 << 16);
+        IVF_HIP(hipHostMalloc(&ctx->h_ivf_ranges, want, hipHostMallocDefault));
+        ctx->ivf_ranges_bytes = want;
+    }
+    *pin = reinterpret_cast<smt_range *>(ctx->h_ivf_ranges);
+    return SMT_OK;
+}
+
 extern "C" {
 
+// `filtered`: the search is inside `ranges` (VALID corpus-local rows: the callers check them); without it the ranges are not looked
+// at and every launch, every scratch offset and every byte of the answer is what it was before ranges existed.  A filter that
+// leaves nothing (no range, or empty ones only) is still a filter: the mask is all zeros and the answer is empty.
 static int ivfpq_search_core(smt_ivfpq *ix, const float *queries, bool queries_on_device, uint32_t nq, uint32_t top_k, uint32_t nprobe,
-                             uint32_t rerank, uint64_t row_base, uint64_t *d_or_user, double *d_od_user, uint64_t *d_oc_user,
+                             uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, bool filtered, uint64_t row_base,
+                             uint64_t *d_or_user, double *d_od_user, uint64_t *d_oc_user,
                              uint64_t **d_or_out, size_t *out_bytes_contig, uint64_t out_stride = 0, smt::Delivery *deliver = nullptr)
 {
     smt_ctx *ctx = ix->corpus->ctx;
@@ -505,9 +615,33 @@ static int ivfpq_search_core(smt_ivfpq *ix, const float *queries, bool queries_o
     const size_t o_oc = o_od + b_od, b_oc = al((size_t)nq * 8);
     const size_t o_sc = o_oc + b_oc, b_sc = al((size_t)nq * ix->nlist * 4);
     const size_t o_lw = o_sc + b_sc, b_lw = ix->kind == 1 ? al((size_t)nq * nprobe * PQ_M * 4) : 0;
-    int rc = smt::ensure_scratch(ctx, o_lw + b_lw);
+    // inside ranges: the non-empty ranges and the list-order bitmap built from them, behind everything else (0 bytes without a filter)
+    uint32_t n_rr = 0;
+    for (uint32_t i = 0; filtered && i < n_ranges; ++i) n_rr += ranges[i].end > ranges[i].begin ? 1u : 0u;
+    const uint64_t mask_words = (ix->n_rows + 63) / 64;
+    const size_t o_rg = o_lw + b_lw, b_rg = filtered ? al((size_t)n_rr * sizeof(smt_range)) : 0;
+    const size_t o_mask = o_rg + b_rg, b_mask = filtered ? al((size_t)mask_words * 8) : 0;
+    int rc = smt::ensure_scratch(ctx, o_mask + b_mask);
     if (rc) return rc;
     char *base = reinterpret_cast<char *>(ctx->d_scratch);
+    if (filtered) {   // (rebuilt on every call: no mask outlives its search)
+        const smt_range *d_rg = reinterpret_cast<const smt_range *>(base + o_rg);
+        if (n_rr) {   // through the context's pinned range buffer: enqueued, not waited for
+            smt_range *pin = nullptr;
+            if ((rc = ranges_pinned(ctx, (size_t)n_rr * sizeof(smt_range), &pin))) return rc;
+            uint32_t w = 0;
+            for (uint32_t i = 0; i < n_ranges; ++i)
+                if (ranges[i].end > ranges[i].begin) pin[w++] = ranges[i];
+            IVF_HIP(hipMemcpyAsync(base + o_rg, pin, (size_t)n_rr * sizeof(smt_range), hipMemcpyHostToDevice, ctx->stream));
+            IVF_HIP(hipEventRecord(ctx->ivf_ranges_up, ctx->stream));
+        }
+        const uint64_t words_per_block = (uint64_t)(MASK_THREADS / 64) * MASK_WORDS_PER_WAVE;
+        prof_begin(ctx, "ivf_mask");
+        if (mask_words)
+            hipLaunchKernelGGL(ivf_range_mask_kernel, dim3((unsigned)((mask_words + words_per_block - 1) / words_per_block)), dim3(MASK_THREADS),
+                               0, ctx->stream, ix->d_ids, ix->n_rows, d_rg, n_rr, reinterpret_cast<uint64_t *>(base + o_mask));
+        prof_end(ctx, "ivf_mask");
+    }
     const float *d_q = queries;
     if (!queries_on_device) {
         IVF_HIP(hipMemcpyAsync(base + o_q, queries, (size_t)nq * 256 * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -562,14 +696,23 @@ static int ivfpq_search_core(smt_ivfpq *ix, const float *queries, bool queries_o
     ap.shortlist = shortlist;
     ap.kp = kp;
     ap.lists = reinterpret_cast<key_t64 *>(base + o_lists);
+    ap.mask = filtered ? reinterpret_cast<const uint64_t *>(base + o_mask) : nullptr;
     prof_begin(ctx, "ivf_adc");
     const dim3 adc_grid(((nq + 7) / 8) * 8 * nprobe * n_seg);   // (one line: see the XCD-aware order in the kernel)
-    if (ix->kind == 1) {
-        if (adc_waves == 8) hipLaunchKernelGGL((ivf_adc_kernel<512, 1>), adc_grid, dim3(512), 0, ctx->stream, ap);
-        else hipLaunchKernelGGL((ivf_adc_kernel<256, 1>), adc_grid, dim3(256), 0, ctx->stream, ap);
+    if (filtered) {
+        if (ix->kind == 1) {
+            if (adc_waves == 8) hipLaunchKernelGGL((ivf_adc_kernel<512, 1, true>), adc_grid, dim3(512), 0, ctx->stream, ap);
+            else hipLaunchKernelGGL((ivf_adc_kernel<256, 1, true>), adc_grid, dim3(256), 0, ctx->stream, ap);
+        } else {
+            if (adc_waves == 8) hipLaunchKernelGGL((ivf_adc_kernel<512, 0, true>), adc_grid, dim3(512), 0, ctx->stream, ap);
+            else hipLaunchKernelGGL((ivf_adc_kernel<256, 0, true>), adc_grid, dim3(256), 0, ctx->stream, ap);
+        }
+    } else if (ix->kind == 1) {
+        if (adc_waves == 8) hipLaunchKernelGGL((ivf_adc_kernel<512, 1, false>), adc_grid, dim3(512), 0, ctx->stream, ap);
+        else hipLaunchKernelGGL((ivf_adc_kernel<256, 1, false>), adc_grid, dim3(256), 0, ctx->stream, ap);
     } else {
-        if (adc_waves == 8) hipLaunchKernelGGL((ivf_adc_kernel<512, 0>), adc_grid, dim3(512), 0, ctx->stream, ap);
-        else hipLaunchKernelGGL((ivf_adc_kernel<256, 0>), adc_grid, dim3(256), 0, ctx->stream, ap);
+        if (adc_waves == 8) hipLaunchKernelGGL((ivf_adc_kernel<512, 0, false>), adc_grid, dim3(512), 0, ctx->stream, ap);
+        else hipLaunchKernelGGL((ivf_adc_kernel<256, 0, false>), adc_grid, dim3(256), 0, ctx->stream, ap);
     }
     prof_end(ctx, "ivf_adc");
     IVF_HIP(hipGetLastError());
@@ -602,11 +745,14 @@ static int ivfpq_search_core(smt_ivfpq *ix, const float *queries, bool queries_o
     return SMT_OK;
 }
 
-int smt_ivfpq_search(smt_ivfpq *ix, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
-                     uint64_t row_base, uint64_t *out_rows, double *out_dist, uint64_t *out_counts, uint64_t out_cap)
-try {
+// the host form of the search, with or without ranges (n_ranges == 0: without)
+static int ivfpq_search_host(smt_ivfpq *ix, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
+                             const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, uint64_t *out_rows, double *out_dist,
+                             uint64_t *out_counts, uint64_t out_cap)
+{
     SMT_REQUIRE(ix != nullptr, "index");
     SMT_REQUIRE(nq == 0 || (queries && out_rows && out_dist && out_counts), "null argument");
+    if (int rcr = smt::validate_ranges(ranges, n_ranges, ix->corpus->rows)) return rcr;
     smt_ctx *ctx = ix->corpus->ctx;
     IVF_HIP(hipSetDevice(ctx->device));
     { int rc_drain = smt::drain_async(ctx); if (rc_drain) return rc_drain; }
@@ -631,8 +777,8 @@ try {
         dl.done = ctx->d_status + 4;
         *flag = 0;
     }
-    rc = ivfpq_search_core(ix, queries, false, nq, top_k, nprobe, rerank, row_base, nullptr, nullptr, nullptr, &d_or, &out_bytes, 0,
-                           direct ? &dl : nullptr);
+    rc = ivfpq_search_core(ix, queries, false, nq, top_k, nprobe, rerank, ranges, n_ranges, n_ranges != 0, row_base, nullptr, nullptr,
+                           nullptr, &d_or, &out_bytes, 0, direct ? &dl : nullptr);
     if (rc) return rc;
     if (direct) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -671,31 +817,61 @@ try {
     }
     if (truncated) { smt::set_error("out_cap smaller than the number of hits"); return SMT_E_TRUNCATED; }
     return SMT_OK;
+}
+
+static int ivfpq_search_dev(smt_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
+                            const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, uint64_t *out_rows_dev, double *out_dist_dev)
+{
+    SMT_REQUIRE(ix != nullptr, "index");
+    SMT_REQUIRE(nq == 0 || (queries_dev && out_rows_dev && out_dist_dev), "null argument");
+    SMT_REQUIRE(top_k >= 1, "top_k");
+    if (int rcr = smt::validate_ranges(ranges, n_ranges, ix->corpus->rows)) return rcr;
+    smt_ctx *ctx = ix->corpus->ctx;
+    IVF_HIP(hipSetDevice(ctx->device));
+    { int rc_drain = smt::drain_async(ctx); if (rc_drain) return rc_drain; }
+    if (nq == 0) return SMT_OK;
+    return ivfpq_search_core(ix, queries_dev, true, nq, top_k, nprobe, rerank, ranges, n_ranges, n_ranges != 0, row_base, out_rows_dev,
+                             out_dist_dev, nullptr, nullptr, nullptr);
+}
+
+int smt_ivfpq_search(smt_ivfpq *ix, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
+                     uint64_t row_base, uint64_t *out_rows, double *out_dist, uint64_t *out_counts, uint64_t out_cap)
+try {
+    return ivfpq_search_host(ix, queries, nq, top_k, nprobe, rerank, nullptr, 0, row_base, out_rows, out_dist, out_counts, out_cap);
+} catch (...) { return smt::api_catch(); }
+
+int smt_ivfpq_search_ranges(smt_ivfpq *ix, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
+                            const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, uint64_t *out_rows, double *out_dist,
+                            uint64_t *out_counts, uint64_t out_cap)
+try {
+    return ivfpq_search_host(ix, queries, nq, top_k, nprobe, rerank, ranges, n_ranges, row_base, out_rows, out_dist, out_counts, out_cap);
 } catch (...) { return smt::api_catch(); }
 
 int smt_ivfpq_search_device(smt_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
                             uint64_t row_base, uint64_t *out_rows_dev, double *out_dist_dev)
 try {
-    SMT_REQUIRE(ix != nullptr, "index");
-    SMT_REQUIRE(nq == 0 || (queries_dev && out_rows_dev && out_dist_dev), "null argument");
-    SMT_REQUIRE(top_k >= 1, "top_k");
-    smt_ctx *ctx = ix->corpus->ctx;
-    IVF_HIP(hipSetDevice(ctx->device));
-    { int rc_drain = smt::drain_async(ctx); if (rc_drain) return rc_drain; }
-    if (nq == 0) return SMT_OK;
-    return ivfpq_search_core(ix, queries_dev, true, nq, top_k, nprobe, rerank, row_base, out_rows_dev, out_dist_dev, nullptr, nullptr, nullptr);
+    return ivfpq_search_dev(ix, queries_dev, nq, top_k, nprobe, rerank, nullptr, 0, row_base, out_rows_dev, out_dist_dev);
+} catch (...) { return smt::api_catch(); }
+
+int smt_ivfpq_search_ranges_device(smt_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
+                                   const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, uint64_t *out_rows_dev,
+                                   double *out_dist_dev)
+try {
+    return ivfpq_search_dev(ix, queries_dev, nq, top_k, nprobe, rerank, ranges, n_ranges, row_base, out_rows_dev, out_dist_dev);
 } catch (...) { return smt::api_catch(); }
 
 }  // extern "C"
 
 // one shard's answer in the packed exchange layout of group_exchange.cpp: [nq][2][top_k] words (global rows | f64 bits)
+// (`filtered` apart from the count, as in search_topk_packed_local: a shard that the caller's ranges leave nothing returns NOTHING;
+// ranges_local come out of layout_localize from ranges the caller validated)
 int smt::ivfpq_search_packed(smt_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
-                             uint64_t row_base, uint64_t *packed_dev)
+                             const smt_range *ranges_local, uint32_t n_ranges, bool filtered, uint64_t row_base, uint64_t *packed_dev)
 {
     SMT_REQUIRE(ix && queries_dev && packed_dev, "null argument");
     smt_ctx *ctx = ix->corpus->ctx;
     IVF_HIP(hipSetDevice(ctx->device));
     { int rc_drain = smt::drain_async(ctx); if (rc_drain) return rc_drain; }
-    return ivfpq_search_core(ix, queries_dev, true, nq, top_k, nprobe, rerank, row_base, packed_dev,
+    return ivfpq_search_core(ix, queries_dev, true, nq, top_k, nprobe, rerank, ranges_local, n_ranges, filtered, row_base, packed_dev,
                              reinterpret_cast<double *>(packed_dev + top_k), nullptr, nullptr, nullptr, (uint64_t)2 * top_k);
 }

@@ -10,18 +10,6 @@ using namespace smt;
 
 namespace smt {
 
-static int validate_global_ranges(const smt_range *ranges, uint32_t n, uint64_t rows)
-{
-    uint64_t prev_end = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        SMT_REQUIRE(ranges[i].begin <= ranges[i].end, "range begin > end");
-        SMT_REQUIRE(ranges[i].end <= rows, "range extends past the corpus");
-        SMT_REQUIRE(i == 0 || ranges[i].begin >= prev_end, "ranges must be sorted and disjoint");
-        prev_end = ranges[i].end;
-    }
-    return SMT_OK;
-}
-
 // Per-shard host search of a query subset on every local device (one host thread per device when there are
 // several: the K4 / large-k paths synchronise internally and would otherwise serialise the GPUs).
 static int local_host_search(smt_sharded_corpus *sc, const float *queries, uint32_t nq, uint32_t top_k, double max_distance,
@@ -66,6 +54,59 @@ static void unpack_packed_hits(const uint64_t *h, uint32_t nq, uint32_t k, std::
     }
 }
 
+// The sharded index search, over everything (n_ranges == 0) or inside GLOBAL row ranges: validated once, localised per rank; a rank
+// the ranges leave nothing still takes part and contributes an empty list.
+static int sharded_ivfpq_search_impl(smt_sharded_ivfpq *six, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe,
+                                     uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, const char *who, uint64_t *out_rows,
+                                     double *out_dist, uint64_t *out_counts, uint64_t out_cap)
+{
+    SMT_REQUIRE(six != nullptr, "index");
+    SMT_REQUIRE(nq == 0 || (queries && out_rows && out_dist && out_counts), "null argument");
+    SMT_REQUIRE(n_ranges == 0 || ranges != nullptr, "ranges");
+    SMT_REQUIRE(top_k >= 1 && top_k <= SCAN_MAX_K, "top_k must be in [1, 56]");
+    smt_sharded_corpus *sc = six->corpus;
+    smt_group *g = sc->group;
+    SMT_REQUIRE((uint64_t)g->n_ranks * top_k <= 8192, "device merge handles up to 8192 candidates per query");
+    int rc;
+    if (n_ranges && (rc = validate_ranges(ranges, n_ranges, sc->total()))) return rc;   // (before anything is enqueued)
+    if (nq == 0) return SMT_OK;
+    if (int rcq = require_queries_domain_host(queries, nq, who)) return rcq;   // (domain.hip; SPMD: all ranks alike)
+    if (g->n_ranks == 1)
+        return n_ranges ? smt_ivfpq_search_ranges(six->shard[0], queries, nq, top_k, nprobe, rerank, ranges, n_ranges, 0, out_rows, out_dist,
+                                                  out_counts, out_cap)
+                        : smt_ivfpq_search(six->shard[0], queries, nq, top_k, nprobe, rerank, 0, out_rows, out_dist, out_counts, out_cap);
+    const ExchangeLayout L(nq, top_k, 0, g->n_ranks, true, true);
+    const size_t list_words = L.list_words;
+    const bool peer = g->transport == SMT_TRANSPORT_PEER;
+    static_assert(SMT_MAX_MERGE_SOURCES * SCAN_MAX_K == 3584, "a peer group's n_ranks x top_k candidates always fit the in-place merge");
+    for (int i = 0; i < g->n_local; ++i) {
+        const int r = g->first_rank + i;
+        if ((rc = group_bind(g, i))) return rc;
+        if ((rc = ensure_dev(g, i, L.dev_bytes))) return rc;
+        char *base = reinterpret_cast<char *>(g->buf[i].dev);
+        uint64_t *loc = exchange_list(g, i, L, -1);
+        if ((rc = drain_async(g->ctx[i]))) return rc;   // (see smt_sharded_search: the buffer may still be read on the aux stream)
+        SMT_HIP_CHECK(hipMemcpyAsync(base, queries, (size_t)nq * SMT_DIM * 4, hipMemcpyHostToDevice, g->ctx[i]->stream));
+        std::vector<smt_range> lr;
+        if (n_ranges) layout_localize(sc, r, ranges, n_ranges, lr);
+        if ((rc = ivfpq_search_packed(six->shard[i], reinterpret_cast<const float *>(base), nq, top_k, nprobe, rerank, lr.data(),
+                                      (uint32_t)lr.size(), n_ranges != 0, sc->contiguous ? sc->rank_base[r] : 0, loc)))
+            return rc;
+        if (!sc->contiguous && (rc = layout_translate_packed(sc, i, g->ctx[i]->stream, loc, nq, top_k))) return rc;
+        if (peer && (rc = peer_publish(g, i, g->ctx[i]->stream))) return rc;
+    }
+    if (!peer && (rc = allgather_words(g, L.loc_off, L.gath_off, list_words))) return rc;
+    uint64_t *merged = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(g->buf[0].dev) + L.out_off);
+    if ((rc = merge_ranks_on(g, 0, g->ctx[0]->stream, L, -1, nq, top_k, merged))) return rc;
+    if ((rc = ensure_host(g, 0, list_words * 8))) return rc;
+    uint64_t *h = reinterpret_cast<uint64_t *>(g->buf[0].pinned);
+    SMT_HIP_CHECK(hipMemcpyAsync(h, merged, list_words * 8, hipMemcpyDeviceToHost, g->ctx[0]->stream));
+    if ((rc = group_sync_all(g))) return rc;
+    std::vector<LocalHits> hits(nq);
+    unpack_packed_hits(h, nq, top_k, hits);
+    return deliver_hits(hits, out_rows, out_dist, out_counts, out_cap);
+}
+
 }  // namespace smt
 
 extern "C" {
@@ -89,7 +130,7 @@ try {
     for (uint32_t q = 0; q < nq; ++q) out_counts[q] = 0;
     const uint64_t total = sc->total();
     int rc;
-    if (n_ranges && (rc = validate_global_ranges(ranges, n_ranges, total))) return rc;
+    if (n_ranges && (rc = validate_ranges(ranges, n_ranges, total))) return rc;
     uint64_t n_virtual = total;
     if (n_ranges) {
         n_virtual = 0;
@@ -338,44 +379,16 @@ smt_ivfpq *smt_sharded_ivfpq_shard(smt_sharded_ivfpq *six, int local_index)
 int smt_sharded_ivfpq_search(smt_sharded_ivfpq *six, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
                              uint64_t *out_rows, double *out_dist, uint64_t *out_counts, uint64_t out_cap)
 try {
-    SMT_REQUIRE(six != nullptr, "index");
-    SMT_REQUIRE(nq == 0 || (queries && out_rows && out_dist && out_counts), "null argument");
-    SMT_REQUIRE(top_k >= 1 && top_k <= SCAN_MAX_K, "top_k must be in [1, 56]");
-    smt_sharded_corpus *sc = six->corpus;
-    smt_group *g = sc->group;
-    SMT_REQUIRE((uint64_t)g->n_ranks * top_k <= 8192, "device merge handles up to 8192 candidates per query");
-    if (nq == 0) return SMT_OK;
-    if (int rcq = require_queries_domain_host(queries, nq, "smt_sharded_ivfpq_search")) return rcq;   // (domain.hip; SPMD: all ranks alike)
-    if (g->n_ranks == 1) return smt_ivfpq_search(six->shard[0], queries, nq, top_k, nprobe, rerank, 0, out_rows, out_dist, out_counts, out_cap);
-    const ExchangeLayout L(nq, top_k, 0, g->n_ranks, true, true);
-    const size_t list_words = L.list_words;
-    const bool peer = g->transport == SMT_TRANSPORT_PEER;
-    static_assert(SMT_MAX_MERGE_SOURCES * SCAN_MAX_K == 3584, "a peer group's n_ranks x top_k candidates always fit the in-place merge");
-    int rc;
-    for (int i = 0; i < g->n_local; ++i) {
-        const int r = g->first_rank + i;
-        if ((rc = group_bind(g, i))) return rc;
-        if ((rc = ensure_dev(g, i, L.dev_bytes))) return rc;
-        char *base = reinterpret_cast<char *>(g->buf[i].dev);
-        uint64_t *loc = exchange_list(g, i, L, -1);
-        if ((rc = drain_async(g->ctx[i]))) return rc;   // (see smt_sharded_search: the buffer may still be read on the aux stream)
-        SMT_HIP_CHECK(hipMemcpyAsync(base, queries, (size_t)nq * SMT_DIM * 4, hipMemcpyHostToDevice, g->ctx[i]->stream));
-        if ((rc = ivfpq_search_packed(six->shard[i], reinterpret_cast<const float *>(base), nq, top_k, nprobe, rerank,
-                                      sc->contiguous ? sc->rank_base[r] : 0, loc)))
-            return rc;
-        if (!sc->contiguous && (rc = layout_translate_packed(sc, i, g->ctx[i]->stream, loc, nq, top_k))) return rc;
-        if (peer && (rc = peer_publish(g, i, g->ctx[i]->stream))) return rc;
-    }
-    if (!peer && (rc = allgather_words(g, L.loc_off, L.gath_off, list_words))) return rc;
-    uint64_t *merged = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(g->buf[0].dev) + L.out_off);
-    if ((rc = merge_ranks_on(g, 0, g->ctx[0]->stream, L, -1, nq, top_k, merged))) return rc;
-    if ((rc = ensure_host(g, 0, list_words * 8))) return rc;
-    uint64_t *h = reinterpret_cast<uint64_t *>(g->buf[0].pinned);
-    SMT_HIP_CHECK(hipMemcpyAsync(h, merged, list_words * 8, hipMemcpyDeviceToHost, g->ctx[0]->stream));
-    if ((rc = group_sync_all(g))) return rc;
-    std::vector<LocalHits> hits(nq);
-    unpack_packed_hits(h, nq, top_k, hits);
-    return deliver_hits(hits, out_rows, out_dist, out_counts, out_cap);
+    return sharded_ivfpq_search_impl(six, queries, nq, top_k, nprobe, rerank, nullptr, 0, "smt_sharded_ivfpq_search", out_rows, out_dist,
+                                     out_counts, out_cap);
+} catch (...) { return smt::api_catch(); }
+
+int smt_sharded_ivfpq_search_ranges(smt_sharded_ivfpq *six, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe,
+                                    uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, uint64_t *out_rows, double *out_dist,
+                                    uint64_t *out_counts, uint64_t out_cap)
+try {
+    return sharded_ivfpq_search_impl(six, queries, nq, top_k, nprobe, rerank, ranges, n_ranges, "smt_sharded_ivfpq_search_ranges", out_rows,
+                                     out_dist, out_counts, out_cap);
 } catch (...) { return smt::api_catch(); }
 
 }  // extern "C"
