@@ -610,6 +610,12 @@ int smt_debug_range_sets(const smt_corpus *corpus, uint64_t *kept, uint64_t *hit
  * into pinned host memory by the select kernel and waited on its completion word, instead of a D2H copy + hipStreamSynchronize. */
 int smt_debug_deliveries(smt_ctx *ctx, uint64_t *count);
 
+/* Test hook for paired scans (tuning key scan_pair): after a synchronise, how many one-query scans of this context's scan_overlap
+ * pipeline took the query of the call two steps later along (paired), ran with their own query only (alone), or found their rows
+ * already scanned by the call two steps earlier and ended at once (absorbed; equal to paired once the pipeline is empty).
+ * Counted on the device since the context was created. */
+int smt_debug_scan_pairs(smt_ctx *ctx, uint64_t *paired, uint64_t *alone, uint64_t *absorbed);
+
 /* Test hook for the SPMD error paths of multi-process groups: arms ONE injected failure with status `code` (an SMT_E_* value) on
  * THIS process's ranks; it fires at the next step of kind `where` and disarms.  The tests arm it on one rank of an n-rank group and
  * check that every rank returns `code` from the same call and that none is left waiting inside a collective.
@@ -693,6 +699,19 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *   scan_gate_pct (0..100)  scan_overlap: a scan's blocks start loading rows once this per cent of the previous scan's blocks have
  *                        finished theirs, or after a bound of at most 0.5 ms (default 50; 0 = at once).  Changes timing only,
  *                        never an answer
+ *   scan_pair (0/1)      scan_overlap: a scan that queues up behind a predecessor on its internal stream looks, on the device when it
+ *                        starts, for the call two steps later (the next one on that stream); if that call is queued in front of the same corpus with the same list
+ *                        size and grid, and no work was pending on the context's stream when it was made, the scan takes its query
+ *                        along in the same corpus pass and that call's own scan ends at once.  Each call's select, outputs and
+ *                        status word stay its own, so no answer changes.  A launch bracketed by profiling events and its successor
+ *                        never pair, and a call made while the GPU keeps up runs the plain kernel.  Switching it drains
+ *                        the pipeline (default 1)
+ *   scan_pair_ring (64..4096, a power of two)  scan_pair: slots of the descriptor ring in use.  A call can be taken along while the
+ *                        host is fewer calls ahead of the GPU than this; a call further ahead simply scans for itself.  Switching
+ *                        it drains the pipeline (default 4096; tests use 64 to see slots reused)
+ *   scan_pair_wait_us (0..5000)  tests only: every call counts as queued behind a predecessor, and the block that decides waits this
+ *                        long for the later call's descriptor, which makes pairing deterministic on corpora that scan in a few
+ *                        microseconds (default 0)
  *   merge_on_aux (0/1)   smt_merge_topk_packed_device is enqueued on the aux stream (see smt_ctx_aux_stream)
  *   compact_bounce_rows (64 .. 2^20, default 65536 = 64 MiB)  smt_corpus_compact: a step whose rows move down by fewer rows than this
  *                        goes through a bounce buffer of this many rows in the context's scratch (a launch must not overwrite its own

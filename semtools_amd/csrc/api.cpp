@@ -90,6 +90,16 @@ int drain_async(smt_ctx *ctx)
     ctx->async_pending = false;
     for (hipStream_t st : ctx->ov_stream)   // scan_overlap: scan + select of a call, in stream order, on one of these
         if (st) SMT_HIP_CHECK(hipStreamSynchronize(st));
+    if (ctx->pair_live) {
+        ctx->pair_live = false;
+        unsigned long long gave_up = 0;
+        SMT_HIP_CHECK(hipMemcpy(&gave_up, ctx->d_gate + 1, sizeof(gave_up), hipMemcpyDeviceToHost));
+        if (gave_up) {
+            (void)hipMemset(ctx->d_gate + 1, 0, sizeof(gave_up));
+            set_error("scan_pair: a scan block gave up waiting for its launch's pairing decision");
+            return SMT_E_HIP;
+        }
+    }
     if (!ctx->aux_stream || !ctx->d_flags) return SMT_OK;
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));      // the scans the selects are waiting for
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->aux_stream));
@@ -393,6 +403,8 @@ void smt_ctx_destroy(smt_ctx *ctx)
     }
     if (ctx->ov_done) (void)hipEventDestroy(ctx->ov_done);
     if (ctx->d_gate) (void)hipFree(ctx->d_gate);
+    if (ctx->d_pair_recs) (void)hipFree(ctx->d_pair_recs);
+    if (ctx->h_pair_ring) (void)hipHostFree(ctx->h_pair_ring);
     if (ctx->d_flags) (void)hipFree(ctx->d_flags);
     if (ctx->d_status) (void)hipFree(ctx->d_status);
     if (ctx->d_steal) (void)hipFree(ctx->d_steal);
@@ -430,6 +442,22 @@ try {
     SMT_HIP_CHECK(hipMemcpy(&v, ctx->d_status, sizeof(v), hipMemcpyDeviceToHost));
     if (reset && v) SMT_HIP_CHECK(hipMemset(ctx->d_status, 0, sizeof(v)));
     *count = v;
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_scan_pairs(smt_ctx *ctx, uint64_t *paired, uint64_t *alone, uint64_t *absorbed)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    SMT_REQUIRE(paired && alone && absorbed, "null argument");
+    if ((rc = bind_device(ctx))) return rc;
+    SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if ((rc = sync_side_streams(ctx))) return rc;
+    unsigned long long v[3] = {0, 0, 0};
+    if (ctx->d_gate) SMT_HIP_CHECK(hipMemcpy(v, ctx->d_gate + 2, sizeof(v), hipMemcpyDeviceToHost));
+    *paired = v[0];
+    *alone = v[1] + ctx->pair_alone_host;
+    *absorbed = v[2];
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
@@ -546,6 +574,18 @@ try {
         int rc2 = drain_async(ctx);
         if (rc2) return rc2;
         ctx->tune.scan_overlap = value ? 1 : 0;
+    } else if (k == "scan_pair") {
+        int rc2 = drain_async(ctx);
+        if (rc2) return rc2;
+        ctx->tune.scan_pair = value ? 1 : 0;
+    } else if (k == "scan_pair_ring") {
+        SMT_REQUIRE(value >= 64 && value <= 4096 && (value & (value - 1)) == 0, "scan_pair_ring: a power of two, 64..4096 slots");
+        int rc2 = drain_async(ctx);
+        if (rc2) return rc2;
+        ctx->tune.scan_pair_ring = (int)value;
+    } else if (k == "scan_pair_wait_us") {
+        SMT_REQUIRE(value >= 0 && value <= 5000, "scan_pair_wait_us: 0..5000 us (tests only)");
+        ctx->tune.scan_pair_wait_us = (int)value;
     } else if (k == "scan_gate_pct") {
         SMT_REQUIRE(value >= 0 && value <= 100, "scan_gate_pct: 0..100 per cent of the previous scan's blocks (0 = no gate)");
         ctx->tune.scan_gate_pct = (int)value;

@@ -65,6 +65,9 @@ struct Tuning {
     int async_select = 0;       // 1: single-query top-k searches overlap their select stage with the next scan
     int scan_overlap = 1;       // async_select, smt_search_topk_device: scan + select of call i on internal stream i & 1 (consecutive scans overlap; 0 = the aux-stream / flag pipeline)
     int scan_gate_pct = 50;     // scan_overlap: a scan's blocks start once this share of its predecessor's blocks has finished its rows (0 = no gate)
+    int scan_pair = 1;          // scan_overlap: a scan that starts behind a predecessor takes the query of the call two steps later (the next one on its stream) along in the same corpus pass (scan_kernels.hip scan_pair_kernel)
+    int scan_pair_ring = 4096;  // scan_pair: slots of the descriptor ring in use (a power of two, 64 .. 4096): a call is found by the scan two steps earlier while the host is fewer calls ahead of the GPU than this (tests use 64 to see slots reused)
+    int scan_pair_wait_us = 0;  // scan_pair, tests only: the deciding block waits this long (<= 5000) for the partner's descriptor
     int gemm_image = 1;         // 1: batched searches read the corpus' fp16 operand image when it has one (0: A/B only)
     int64_t image_scan_min_rows = 1500000;   // shards this large answer ONE query from the operand image too, when they have one; 2..7 queries from a third of this (0: never)
     int64_t image_use_min_rows = 400000;     // a corpus that already HAS its image answers one query from it from this many rows (unfiltered calls), two from 1/5 of it, three and more from 1/60 (0: only the image_scan_min_rows rule)
@@ -138,6 +141,12 @@ struct smt_ctx {
     uint64_t gate_total = 0;                 // blocks of all overlapped scans launched so far (the counter's value once they are done)
     uint64_t gate_prev_blocks = 0;           // ... and of the latest one
     uint64_t gate_prev_rows = 0;
+    // scan_pair: the descriptor ring (pinned host memory, one slot per step) and the per-step decision records (device); the
+    // counters and the wait-ran-out flag live behind the gate counter, d_gate[1..4] (scan_kernels.hip PairParams::ctl)
+    void *h_pair_ring = nullptr;
+    void *d_pair_recs = nullptr;
+    uint64_t pair_alone_host = 0;            // scan_pair calls that got the plain kernel: nothing queued in front of them, or profiled (smt_debug_scan_pairs counts them as alone)
+    bool pair_live = false;                  // paired-mode scans were launched since the last drain (their error flag is unread)
     unsigned int *d_steal = nullptr;         // K2 STEAL: 64 group counters, one per launch in rotation (scan_kernels.hip)
     uint64_t steal_seq = 0;
     unsigned long long deliver_seq = 0;      // sequence number of the last delivered answer (its completion word in pinned memory)
@@ -262,6 +271,8 @@ int drain_async(smt_ctx *ctx);
 int ensure_overlap(smt_ctx *ctx);
 // every stream that may still run kernels of this context besides `stream` (aux, the two scan streams)
 int sync_side_streams(smt_ctx *ctx);
+// scan_pair: the descriptor ring and the decision records, made on first use (scan_kernels.hip)
+int ensure_pair(smt_ctx *ctx);
 // scan_overlap + an aux stream: work enqueued on aux from now on runs behind every overlapped select enqueued so far
 int order_aux_after_overlap(smt_ctx *ctx);
 int ensure_async(smt_ctx *ctx);  // aux stream + flags

@@ -281,7 +281,9 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
     // (row, query) pairs per instruction) and one ballot finds the pairs under the query's threshold; only those (rare once the
     // lists have filled) are read out and inserted.  Per chunk and query 15 + ~14 instructions instead of 4 x (11 + ~14): with the
     // row-at-a-time form the reductions made two queries cost 1.4 x and four 2.3 x one query's pass (instruction issue, not HBM).
-    // VALID(j): wave-uniform, is row j of the chunk a real row.
+    // VALID(j): wave-uniform, is row j of the chunk a real row.  SMT_QUERY_ON(n): does query n take part (scan_pair_kernel decides
+    // that while it runs; a constant here).
+#define SMT_QUERY_ON(n) true
 #define SMT_REDUCE_CHUNK4(cq, rq4, VALID)                                                                         \
     do {                                                                                                          \
         const int jj = lane & 3;                                                                                  \
@@ -293,6 +295,7 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
             pb[j] = (cq)[j].x * (cq)[j].x + (cq)[j].y * (cq)[j].y + (cq)[j].z * (cq)[j].z + (cq)[j].w * (cq)[j].w; \
         const float b2 = wave_sum4(pb[0], pb[1], pb[2], pb[3], lane);                                             \
         _Pragma("unroll") for (int n = 0; n < NQ; ++n) {                                                          \
+            if (!(SMT_QUERY_ON(n))) continue;                                                                     \
             float pa[4];                                                                                          \
             _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                         \
                 pa[j] = (cq)[j].x * q[n].x + (cq)[j].y * q[n].y + (cq)[j].z * q[n].z + (cq)[j].w * q[n].w;        \
@@ -456,7 +459,8 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
         }
     }
 #undef SMT_REDUCE_ROW
-#undef SMT_REDUCE_CHUNK4
+#undef SMT_QUERY_ON
+    // (SMT_REDUCE_CHUNK4 is used once more, by scan_pair_kernel below)
 
     if (p.stamps && lane == 0) p.stamps[wave_global * 2 + 1] = wall_clock64();
 
@@ -517,6 +521,268 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
     }
     if (p.stamps && threadIdx.x == 0) p.stamps[(uint64_t)gridDim.x * waves_per_block * 2 + blockIdx.x] = wall_clock64();
 }
+
+// ------------------------------------------------------------- K2, paired (tuning key scan_pair)
+// Queued one-query scans of the scan_overlap pipeline share a corpus pass.  Every call still launches its scan and its select at
+// once; the scan of step i decides ON THE DEVICE, when it starts, whether it takes the query of step i + 2 -- the next call on its
+// own stream -- along: then it runs the two-query row loop and writes two list sets, its own and the partner's, and the scan of
+// step i + 2 finds itself ABSORBED and exits before its gate and before any row load.  The selects run where they always did, each
+// on its own list set with its own query, outputs and status word: the scan only nominates, so no answer changes.
+//   host -> device: a ring of PairSlot in pinned host memory, indexed by step; the host fills slot i before it launches scan i and
+//     writes the step number last (release); the reader checks the number before and after the fields (a slot reused PAIR_RING
+//     steps later fails that check).
+//   block -> block: one PairRecord per step in device memory, state = step << 2 | code.  One block wins a CAS on it, decides, and
+//     publishes the record with an agent-scope release; the others wait for it with a bounded wait (PairParams::ctl[0] is raised
+//     when one runs out, and drain_async turns that into an error code).  The scan of step i + 2 reads record i, complete by
+//     stream order.
+// WHEN a launch looks is decided by the host: only a launch that queues up behind a predecessor on its internal stream
+// (hipStreamQuery at the call) runs this kernel at all -- a call made while the GPU keeps up, a launch bracketed by profiling events
+// and the one after it run scan_topk_kernel as before, so their latency and the profiled kernel time are the plain kernel's.  The
+// deciding block reads the slot before it waits at its gate, the others learn the decision after they have requested their first
+// rows (the same rows either way): no row load starts later than in scan_topk_kernel.  (Looking only when the block had to wait
+// at its gate was measured too: 78.7 instead of 78.2 us per step, and under counter collection, which serialises kernels, nothing
+// pairs at all -- profiles/scan_pairing.json.)
+constexpr int PAIR_RING = 4096;   // slots: the host may run this many calls ahead of the GPU and still be found (256 KiB, pinned; tuning key scan_pair_ring uses fewer)
+constexpr int PAIR_RECS = 64;     // records: record i is read by the scan of step i + 2 only
+struct PairSlot {   // 64 bytes of pinned host memory
+    unsigned long long step;        // written last
+    unsigned long long corpus, n_virtual, query, lists;
+    unsigned long long kp_blocks;   // kp | grid size << 32
+    unsigned long long absorbable;
+    unsigned long long pad;
+};
+struct PairRecord {
+    unsigned long long state;       // step << 2 | PAIR_DECIDING / PAIR_ALONE / PAIR_PAIRED (any other step: undecided)
+    unsigned long long query, lists;   // PAIR_PAIRED: the partner's
+    unsigned long long pad;
+};
+struct PairParams {
+    const PairSlot *ring;
+    PairRecord *recs;
+    unsigned long long *ctl;        // [0] a bounded wait ran out, [1] launches that paired, [2] ran alone, [3] were absorbed
+    unsigned int absorbable;        // this launch's own slot says so: only then can record step - 2 name it
+    unsigned long long wait_ticks;  // tuning key scan_pair_wait_us, in 10 ns ticks
+    unsigned long long ring_mask;   // slots in use - 1 (tuning key scan_pair_ring)
+};
+enum : unsigned long long { PAIR_DECIDING = 1, PAIR_ALONE = 2, PAIR_PAIRED = 3, PAIR_ABSORBED = 4 };
+
+__device__ __forceinline__ unsigned long long sys_load(const unsigned long long *f)
+{
+    return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// The deciding block: the slot of step + 2 -> PAIR_PAIRED (query and lists filled in) or PAIR_ALONE.
+__device__ __forceinline__ unsigned long long pair_decide(const ScanParams &p, const PairParams &pp, unsigned long long &query,
+                                                          unsigned long long &lists)
+{
+    const PairSlot *s = pp.ring + ((p.step + 2) & pp.ring_mask);
+    const unsigned long long want = p.step + 2;
+    unsigned long long s1 = __hip_atomic_load(&s->step, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (s1 != want && pp.wait_ticks) {   // (tests: corpora that scan faster than the host issues calls)
+        const unsigned long long t0 = wall_clock64();
+        while (s1 != want && wall_clock64() - t0 < pp.wait_ticks) {
+            __builtin_amdgcn_s_sleep(32);
+            s1 = __hip_atomic_load(&s->step, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    if (s1 != want) return PAIR_ALONE;
+    const unsigned long long corpus = sys_load(&s->corpus), n_virtual = sys_load(&s->n_virtual), kp_blocks = sys_load(&s->kp_blocks);
+    const unsigned long long absorbable = sys_load(&s->absorbable);
+    query = sys_load(&s->query);
+    lists = sys_load(&s->lists);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+    if (sys_load(&s->step) != want) return PAIR_ALONE;   // the host was rewriting the slot (64 steps ahead)
+    const bool same = corpus == (unsigned long long)(uintptr_t)p.corpus && n_virtual == p.n_virtual &&
+                      kp_blocks == ((unsigned long long)p.kp | (unsigned long long)gridDim.x << 32);
+    return absorbable && same ? PAIR_PAIRED : PAIR_ALONE;
+}
+
+// (8 waves per SIMD = 64 VGPRs: what the select needs beside it, 2 x 64 + 4 x 96 = 512.  The two row loops need 52 and 62; left to
+// itself the allocator spreads the two instantiations over 76.)
+template <bool NT>
+__global__ void __launch_bounds__(1024) scan_pair_kernel(ScanParams p, PairParams pp)
+{
+    constexpr int U = 4;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    key_t64 *s_keys = reinterpret_cast<key_t64 *>(smem_raw);  // [2][waves][64]: the launch is sized for a pair
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int waves_per_block = blockDim.x >> 6;
+    // (as in scan_topk_kernel: the chunk counter lives in the second query's key slots until the merge; so does the decision)
+    uint32_t *s_next = reinterpret_cast<uint32_t *>(s_keys + waves_per_block * 64);
+    unsigned long long *s_pair = reinterpret_cast<unsigned long long *>(s_next + 4);   // [0] absorbed?, [1] query, [2] lists, [3] record state as read, [4] code
+    const int kp = (int)p.kp;
+    PairRecord *rec = pp.recs + p.step % PAIR_RECS;
+    const unsigned long long tag = p.step << 2;
+
+    f32x4 q[2];
+    float rq[2];
+    bool qz[2];
+    {
+        q[0] = reinterpret_cast<const f32x4 *>(p.queries)[lane];
+        const float a2 = wave_sum(q[0].x * q[0].x + q[0].y * q[0].y + q[0].z * q[0].z + q[0].w * q[0].w);
+        qz[0] = (a2 == 0.0f);
+        rq[0] = qz[0] ? 0.0f : __frsqrt_rn(a2);
+    }
+
+    if (threadIdx.x == 0) {
+        *s_next = (uint32_t)waves_per_block;
+        // three independent reads, one round trip (scan_topk_kernel reads its gate here)
+        const unsigned long long g = p.gate_open ? flag_load(p.gate) : 0ull;
+        const unsigned long long prev = pp.absorbable ? flag_load(&pp.recs[(p.step - 2) % PAIR_RECS].state) : 0ull;
+        unsigned long long cur = flag_load(&rec->state);
+        unsigned long long code = 0;
+        if (pp.absorbable && prev == (((p.step - 2) << 2) | PAIR_PAIRED)) {
+            code = PAIR_ABSORBED;
+        } else {
+            // the first block to get here looks for a partner while the others wait at the gate
+            if ((cur >> 2) != p.step &&
+                __hip_atomic_compare_exchange_strong(&rec->state, &cur, tag | PAIR_DECIDING, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                     __HIP_MEMORY_SCOPE_AGENT)) {
+                unsigned long long query = 0, lists = 0;
+                const unsigned long long d = pair_decide(p, pp, query, lists);
+                flag_store(&rec->query, query);
+                flag_store(&rec->lists, lists);
+                cur = tag | d;
+                __hip_atomic_store(&rec->state, cur, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                (void)__hip_atomic_fetch_add(pp.ctl + (d == PAIR_PAIRED ? 1 : 2), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (g < p.gate_open) gate_wait(p);
+        }
+        s_pair[0] = code;
+        s_pair[3] = cur;
+    }
+    __syncthreads();
+    if (uniform_u64(s_pair[0]) == PAIR_ABSORBED) {
+        if (blockIdx.x == 0 && threadIdx.x == 0)
+            (void)__hip_atomic_fetch_add(pp.ctl + 3, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+
+    auto chunk_v0 = [&](uint32_t t) -> uint64_t {   // (the division runs on the VALU: say that the result is wave-uniform)
+        return uniform_u64((((uint64_t)(t / waves_per_block) * gridDim.x + blockIdx.x) * waves_per_block + t % waves_per_block) * U);
+    };
+    auto claim = [&]() -> uint32_t {
+        uint32_t t = 0;
+        if (lane == 0) t = atomicAdd(s_next, 1u);
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+    };
+    auto issue_rows = [&](uint64_t v0, f32x4 (&c)[U], uint32_t (&row)[U]) {
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            uint64_t v = v0 + j;
+            if (v >= p.n_virtual) v = p.n_virtual - 1;  // clamp (result discarded)
+            row[j] = (uint32_t)v;
+            const f32x4 *src = reinterpret_cast<const f32x4 *>(p.corpus + (uint64_t)row[j] * 256) + lane;
+            c[j] = NT ? __builtin_nontemporal_load(src) : *src;
+        }
+    };
+    // the first rows are on their way before the decision is known: they are the same rows either way
+    f32x4 cn[U];
+    uint32_t rown[U];
+    uint64_t v0 = chunk_v0((uint32_t)wave);
+    uint64_t v0n = 0;
+    if (v0 < p.n_virtual) {
+        issue_rows(v0, cn, rown);
+        v0n = chunk_v0(claim());
+    }
+
+    if (threadIdx.x == 0) {
+        unsigned long long cur = s_pair[3];   // (this step's: the block has won the CAS and decided, or lost it)
+        if (cur == (tag | PAIR_DECIDING)) {   // bounded like flag_wait: a decision that never comes ends in an error code
+            const unsigned long long t0 = wall_clock64();
+            while ((cur = flag_load(&rec->state)) == (tag | PAIR_DECIDING)) {
+                __builtin_amdgcn_s_sleep(8);
+                if (flag_load(pp.ctl) != 0ull) break;
+                if (wall_clock64() - t0 > 200000000ull) { flag_store(pp.ctl, 1ull); break; }
+            }
+        }
+        unsigned long long code = PAIR_ALONE;
+        if (cur == (tag | PAIR_PAIRED)) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            s_pair[1] = flag_load(&rec->query);
+            s_pair[2] = flag_load(&rec->lists);
+            code = PAIR_PAIRED;
+        } else if (cur != (tag | PAIR_ALONE)) {
+            flag_store(pp.ctl, 1ull);   // (a wait that ran out, or a record that is not this step's: alone, and the context reports it)
+        }
+        s_pair[4] = code;
+    }
+    __syncthreads();
+    const bool paired = uniform_u64(s_pair[4]) == PAIR_PAIRED;   // (LDS reads: told to be wave-uniform)
+    key_t64 *lists2 = nullptr;
+    if (paired) {
+        lists2 = reinterpret_cast<key_t64 *>((uintptr_t)uniform_u64(s_pair[2]));
+        q[1] = reinterpret_cast<const f32x4 *>((uintptr_t)uniform_u64(s_pair[1]))[lane];
+        const float a2 = wave_sum(q[1].x * q[1].x + q[1].y * q[1].y + q[1].z * q[1].z + q[1].w * q[1].w);
+        qz[1] = (a2 == 0.0f);
+        rq[1] = qz[1] ? 0.0f : __frsqrt_rn(a2);
+    }
+
+    // the row loop and the block merge of scan_topk_kernel<2, 4, NT, false>, the second query's share of both skipped by a launch
+    // that runs alone.  (ONE loop: two instantiations behind a branch share the first rows' registers, and the allocator then takes
+    // 76 VGPRs where each loop alone takes 53 / 63 -- the select needs this kernel at 64 or fewer beside it.)
+    constexpr int NQ = 2;
+#define SMT_QUERY_ON(n) ((n) == 0 || paired)
+    float ld[NQ];
+    uint32_t lr[NQ];
+    float thr_d[NQ];
+    uint32_t thr_r[NQ];
+#pragma unroll
+    for (int n = 0; n < NQ; ++n) {
+        ld[n] = __builtin_inff();
+        lr[n] = 0xFFFFFFFFu;
+        thr_d[n] = __builtin_inff();
+        thr_r[n] = 0xFFFFFFFFu;
+    }
+    while (v0 < p.n_virtual) {
+        f32x4 c[U];
+        uint32_t row[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) { c[j] = cn[j]; row[j] = rown[j]; }
+        if (v0n < p.n_virtual) issue_rows(v0n, cn, rown);
+        const uint64_t v0nn = chunk_v0(claim());
+#define SMT_VALID_UNF(j) ((v0 + (j)) < p.n_virtual)
+        SMT_REDUCE_CHUNK4(c, row, SMT_VALID_UNF);
+#undef SMT_VALID_UNF
+        v0 = v0n;
+        v0n = v0nn;
+    }
+    __syncthreads();
+    // a paired block counts for its partner's block too: the host's running totals count every launch
+    if (threadIdx.x == 0) (void)__hip_atomic_fetch_add(p.gate, paired ? 2ull : 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned int *s_valid = reinterpret_cast<unsigned int *>(s_keys + (size_t)NQ * waves_per_block * 64);   // [NQ][waves]
+#pragma unroll
+    for (int n = 0; n < NQ; ++n) {
+        if (!(SMT_QUERY_ON(n))) break;
+        const bool have = lane < kp && lr[n] != 0xFFFFFFFFu;
+        s_keys[((size_t)n * waves_per_block + wave) * 64 + lane] = have ? make_key(ld[n], lr[n]) : KEY_PAD;
+        const unsigned int cnt = (unsigned int)__popcll(__ballot(have));
+        if (lane == 0) s_valid[n * waves_per_block + wave] = cnt;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < NQ; ++n) {
+        if (!(SMT_QUERY_ON(n))) break;
+        const key_t64 *keys_n = s_keys + (size_t)n * waves_per_block * 64;
+        key_t64 *out = (n == 0 ? p.block_lists : lists2) + (size_t)blockIdx.x * kp;
+        const key_t64 mine = keys_n[wave * 64 + lane];
+        if (mine != KEY_PAD) {
+            int rank = 0;
+            for (int w = 0; w < waves_per_block; ++w)
+                for (int i = 0; i < kp; ++i) rank += (keys_n[w * 64 + i] < mine) ? 1 : 0;
+            if (rank < kp) out[rank] = mine;
+        }
+        if (wave == 0 && lane < kp) {   // the padding: slots [valid keys of the block, kp)
+            unsigned int total = 0;
+            for (int w = 0; w < waves_per_block; ++w) total += s_valid[n * waves_per_block + w];
+            if ((unsigned int)lane >= total) out[lane] = KEY_PAD;
+        }
+    }
+#undef SMT_QUERY_ON
+}
+#undef SMT_REDUCE_CHUNK4
 
 // --------------------------------------------------- exact f64 distance (A5): device_utils.h exact_distance
 __global__ void rescore_rows_kernel(const float *corpus, const float *query, const uint32_t *rows,
@@ -1177,6 +1443,41 @@ static int launch_scan_filtered(smt_ctx *ctx, const ScanParams &p, int blocks, i
     return SMT_OK;
 }
 
+int ensure_pair(smt_ctx *ctx)
+{
+    if (ctx->h_pair_ring) return SMT_OK;
+    SMT_HIP_CHECK(hipMalloc(&ctx->d_pair_recs, PAIR_RECS * sizeof(PairRecord)));
+    SMT_HIP_CHECK(hipMemset(ctx->d_pair_recs, 0, PAIR_RECS * sizeof(PairRecord)));
+    SMT_HIP_CHECK(hipHostMalloc(&ctx->h_pair_ring, PAIR_RING * sizeof(PairSlot), hipHostMallocDefault));
+    memset(ctx->h_pair_ring, 0, PAIR_RING * sizeof(PairSlot));
+    return SMT_OK;
+}
+
+// Publishes this step's slot (what a predecessor needs to take the call along), then launches the pair-capable one-query scan.
+static int launch_scan_pair(smt_ctx *ctx, const ScanParams &p, PairParams pp, int blocks, int threads, bool nt, hipStream_t st)
+{
+    pp.ring_mask = (unsigned long long)std::min(ctx->tune.scan_pair_ring, PAIR_RING) - 1;
+    PairSlot *slot = reinterpret_cast<PairSlot *>(ctx->h_pair_ring) + (p.step & pp.ring_mask);
+    __atomic_store_n(&slot->step, 0ull, __ATOMIC_SEQ_CST);   // (a reader of the slot's previous use fails its second check)
+    slot->corpus = (unsigned long long)(uintptr_t)p.corpus;
+    slot->n_virtual = p.n_virtual;
+    slot->query = (unsigned long long)(uintptr_t)p.queries;
+    slot->lists = (unsigned long long)(uintptr_t)p.block_lists;
+    slot->kp_blocks = (unsigned long long)p.kp | (unsigned long long)blocks << 32;
+    slot->absorbable = pp.absorbable;
+    __atomic_store_n(&slot->step, p.step, __ATOMIC_RELEASE);
+    pp.ring = reinterpret_cast<const PairSlot *>(ctx->h_pair_ring);
+    pp.recs = reinterpret_cast<PairRecord *>(ctx->d_pair_recs);
+    pp.ctl = ctx->d_gate + 1;
+    pp.wait_ticks = (unsigned long long)ctx->tune.scan_pair_wait_us * 100ull;
+    const size_t smem = (size_t)2 * (threads / 64) * 64 * sizeof(key_t64) + 16 + 64 + 256;   // launch_scan_variant<2, 4>'s
+    if (nt) hipLaunchKernelGGL(scan_pair_kernel<true>, dim3(blocks), dim3(threads), smem, st, p, pp);
+    else hipLaunchKernelGGL(scan_pair_kernel<false>, dim3(blocks), dim3(threads), smem, st, p, pp);
+    SMT_HIP_CHECK(hipGetLastError());
+    ctx->pair_live = true;
+    return SMT_OK;
+}
+
 // Block lists -> final answer in ONE launch (per query: prune + rank + rescore).
 int launch_select(smt_ctx *ctx, const SelectArgs &a)
 {
@@ -1279,16 +1580,36 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
     const size_t list_bytes = overlap ? (size_t)SEL_MAX_LISTS * 64 * sizeof(key_t64)
                                       : (((size_t)a.nq * blocks * kp * sizeof(key_t64)) + 255) & ~(size_t)255;
     const size_t table_bytes = filtered ? (size_t)n_chunks * sizeof(uint64_t) : 0;
-    rc = ensure_scratch(ctx, 2 * list_bytes + table_bytes);
+    // (scan_overlap: a ring of four sets -- a paired scan of step i fills the set of step i + 2 as well, on the same stream, while
+    // the select of step i - 2, which read that set's predecessor in a ring of two, is behind it in stream order only with four)
+    const size_t n_sets = overlap ? 4 : 2;
+    rc = ensure_scratch(ctx, n_sets * list_bytes + table_bytes);
     if (rc != SMT_OK) return rc;
-    key_t64 *lists = reinterpret_cast<key_t64 *>(reinterpret_cast<char *>(ctx->d_scratch) + (step & 1) * list_bytes);
-    uint64_t *table = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(ctx->d_scratch) + 2 * list_bytes);
+    key_t64 *lists = reinterpret_cast<key_t64 *>(reinterpret_cast<char *>(ctx->d_scratch) + (step & (n_sets - 1)) * list_bytes);
+    uint64_t *table = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(ctx->d_scratch) + n_sets * list_bytes);
+    // scan_pair: the launch may share its corpus pass with the call two steps later, or be absorbed by the one two steps earlier
+    // (scan_pair_kernel).  Not with wave stamps (profiling of the plain kernel).
+    const bool pair = overlap && ctx->tune.scan_pair && U == 4 && ctx->tune.scan_debug_ptr == 0;
+    if (pair && (rc = ensure_pair(ctx))) return rc;
 
     const bool nt = ctx->tune.scan_nontemporal != 0;
     hipStream_t st = ctx->stream;
     unsigned long long gate_open = 0, gate_ticks = 0;
+    PairParams pp{};
+    bool may_pair = false;   // scan_pair: this launch runs scan_pair_kernel (it looks for a partner, and may find itself absorbed)
     if (overlap) {
         st = ctx->ov_stream[step & 1];
+        // a predecessor that takes this call's query along reads it without waiting for ov_ready: only a query that no work queued on
+        // the caller's stream can still be writing may be taken
+        // ... and only a launch that queues up behind a predecessor on its stream can be absorbed by it, or has reason to look for a
+        // partner itself (a call made while the GPU is idle must cost what it did: no look, no wait; scan_pair_wait_us: tests)
+        if (pair) {
+            const bool behind = ctx->tune.scan_pair_wait_us > 0 || hipStreamQuery(st) != hipSuccess;
+            const bool idle = behind && hipStreamQuery(ctx->stream) == hipSuccess;
+            (void)hipGetLastError();   // (hipErrorNotReady is an answer here)
+            pp.absorbable = idle ? 1u : 0u;
+            may_pair = behind;
+        }
         SMT_HIP_CHECK(hipEventRecord(ctx->ov_ready[step & 1], ctx->stream));
         SMT_HIP_CHECK(hipStreamWaitEvent(st, ctx->ov_ready[step & 1], 0));
         // a timed launch waits for its predecessor (and that one's select), and the launch after it waits for it: the events bracket a
@@ -1298,6 +1619,8 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
             SMT_HIP_CHECK(hipEventRecord(ctx->ov_done, ctx->ov_stream[(step & 1) ^ 1]));
             SMT_HIP_CHECK(hipStreamWaitEvent(st, ctx->ov_done, 0));
         }
+        // (a timed launch and its successor neither absorb nor get absorbed: the events keep bracketing a one-query pass)
+        if (timed || ctx->ov_after_timed) { may_pair = false; pp.absorbable = 0; }
         ctx->ov_after_timed = timed;
         if (ctx->tune.scan_gate_pct > 0 && ctx->gate_prev_blocks > 0) {
             gate_open = ctx->gate_total - ctx->gate_prev_blocks + (ctx->gate_prev_blocks * (uint64_t)ctx->tune.scan_gate_pct + 99) / 100;
@@ -1360,6 +1683,8 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
             q0 += 2;
         } else {
             if (filtered) rc = launch_scan_filtered<1>(ctx, p, blocks, threads, nt);
+            else if (pair && may_pair) rc = launch_scan_pair(ctx, p, pp, blocks, threads, nt, st);
+            else if (pair) { ++ctx->pair_alone_host; rc = launch_scan_variant<1, 4>(ctx, p, blocks, threads, nt, st); }
             else if (U == 2) rc = launch_scan_variant<1, 2>(ctx, p, blocks, threads, nt, st);
             else if (U == 4) rc = launch_scan_variant<1, 4>(ctx, p, blocks, threads, nt, st);
             else rc = launch_scan_variant<1, 8>(ctx, p, blocks, threads, nt, st);

@@ -1,0 +1,61 @@
+"""A/B of paired one-query scans (tuning key scan_pair; scan_gate_pct swept in pair mode) in ONE process on one box, settings
+alternated: the wall time per pipelined step (async select, scan_overlap, no events) over two 1 M-row corpora used in turn (as
+bench.py) and over one corpus alone, how many launches paired (smt_debug_scan_pairs), and the answers and status words compared
+with scan_pair = 0.  "sync": one call, synchronise, repeat -- the latency of a call when the GPU is not behind, where nothing can
+pair and the pair-capable kernel must cost what the plain one does.  python tools/ab_pairing.py [rows] [rounds] [out.json]"""
+import json, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+import semtools_amd as smt
+rows = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
+rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+dev = torch.device("cuda:0")
+g = torch.Generator(device=dev); g.manual_seed(3)
+x = torch.randn(rows, 256, device=dev, generator=g); x /= x.norm(dim=1, keepdim=True)
+x2 = torch.randn(rows, 256, device=dev, generator=g); x2 /= x2.norm(dim=1, keepdim=True)
+q = torch.randn(16, 256, device=dev, generator=g); q /= q.norm(dim=1, keepdim=True)
+torch.cuda.synchronize()
+torch.cuda.set_stream(torch.cuda.Stream(dev))
+ctx = smt.Context(0, stream=torch.cuda.current_stream().cuda_stream)
+both = [smt.Corpus(ctx, device_ptr=t.data_ptr(), rows=rows) for t in (x, x2)]
+out = torch.empty((64, 2, 10), dtype=torch.int64, device=dev)
+st = torch.full((2048,), 7, dtype=torch.int32, device=dev)
+def run(n, corpora, sync_each=False):
+    for i in range(n):
+        corpora[i % len(corpora)].search_topk_device(q[i % 16].data_ptr(), 1, 10, 0, out[i % 64, 0].data_ptr(), out[i % 64, 1].data_ptr(),
+                                                     out_status_ptr=st[i % 2048:].data_ptr())
+        if sync_each: torch.cuda.synchronize()
+    ctx.synchronize()
+ctx.set_tuning("prof_select", 0)
+ctx.set_tuning("async_select", 1)
+settings = [(0, 50, 0), (1, 50, 0), (1, 0, 0), (1, 65, 0), (1, 75, 0), (1, 90, 0), (1, 100, 0)]   # (scan_pair, scan_gate_pct, scan_pair_wait_us)
+loads = {"two_corpora": (both, False, settings), "one_corpus": (both[:1], False, settings), "sync": (both, True, settings[:2])}
+res, ref = {}, {}
+for r in range(rounds):
+    for load, (corpora, sync_each, todo) in loads.items():
+        for pair, gate, wait_us in todo:
+            ctx.set_tuning("scan_pair", pair)
+            ctx.set_tuning("scan_gate_pct", gate)
+            ctx.set_tuning("scan_pair_wait_us", wait_us)
+            run(300, corpora, sync_each)
+            st.fill_(7)
+            c0 = ctx.scan_pairs()
+            t0 = time.perf_counter(); run(2000, corpora, sync_each); step = (time.perf_counter() - t0) / 2000 * 1e6
+            c1 = ctx.scan_pairs()
+            ans = out.cpu().numpy().copy()
+            ref.setdefault(load, ans)
+            same = bool((ans == ref[load]).all()) and bool((st[:2000].cpu() == 0).all())
+            key = f"{load}/" + ("off" if pair == 0 else f"pair_gate{gate}")
+            res.setdefault(key, []).append({"step_us": round(step, 2), "paired": c1[0] - c0[0], "alone": c1[1] - c0[1],
+                                            "absorbed": c1[2] - c0[2], "answers_and_status_match": same})
+            print(json.dumps({"round": r, "setting": key, **res[key][-1]}), file=sys.stderr, flush=True)
+ctx.set_tuning("scan_gate_pct", 50)
+ctx.set_tuning("scan_pair_wait_us", 0)
+summary = {k: {"median_step_us": sorted(x["step_us"] for x in v)[len(v) // 2], "min": min(x["step_us"] for x in v),
+               "max": max(x["step_us"] for x in v), "paired_of_2000": [x["paired"] for x in v],
+               "all_match": all(x["answers_and_status_match"] for x in v)} for k, v in res.items()}
+report = json.dumps({"rows": rows, "rounds": rounds, "summary": summary, "by_setting": res}, indent=1)
+if len(sys.argv) > 3:
+    open(sys.argv[3], "w").write(report + "\n")
+else:
+    print(report)
