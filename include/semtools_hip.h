@@ -207,8 +207,9 @@ int smt_corpus_truncate(smt_corpus *corpus, uint64_t n_rows);
  *     for the move itself.
  *   - The fp16 operand image is derived data: the tiles from the first moved row on are packed again by the next batch that
  *     wants them; the allocation and the prepack mode stay.  Kept range sets depend on ranges only and stay.
- *   - An smt_ivfpq built on the corpus names rows BY POSITION: after a compaction that dropped rows it refuses to search
- *     ("the corpus shrank ... rebuild").  Destroy and rebuild it.
+ *   - An smt_ivfpq built on the corpus names rows BY POSITION.  smt_ivfpq_compact (below, with the index) is this call AND the
+ *     index following it: use it instead of this one.  An index that was not carried refuses to search after a compaction that
+ *     dropped rows ("the corpus shrank ... rebuild"): destroy and rebuild it.
  * Steps whose gap is shorter than the bounce buffer go through it (tuning key compact_bounce_rows). */
 int smt_corpus_compact(smt_corpus *corpus, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved /* may be NULL */);
 /* smt_corpus_compact calls that succeeded on this context (no-ops included) and the rows they moved; any pointer may be NULL;
@@ -384,7 +385,8 @@ int smt_ivfpq_info(const smt_ivfpq *index, uint64_t *n_rows, uint32_t *nlist, ui
 int smt_ivfpq_list_sizes(const smt_ivfpq *index, uint64_t *sizes_host /* [nlist] */);
 /* Persist / restore the index (centroids, quantisers, list table, ids, codes: ~36 B per row).  The file
  * refers to corpus rows by position: load fails with SMT_E_INVALID unless `corpus` holds AT LEAST the
- * row count the index covers (then smt_ivfpq_append if the corpus only grew, else rebuild -- 0.5 s per 10 M rows). */
+ * row count the index covers (then smt_ivfpq_append if the corpus only grew; smt_ivfpq_compact carries a loaded index through a
+ * compaction; else rebuild -- 0.5 s per 10 M rows). */
 int smt_ivfpq_save(smt_ivfpq *index, const char *path);
 int smt_ivfpq_load(smt_corpus *corpus, const char *path, smt_ivfpq **out);
 /* Incremental insert: rows appended to the corpus since the index was built (or last extended) are assigned to
@@ -392,6 +394,31 @@ int smt_ivfpq_load(smt_corpus *corpus, const char *path, smt_ivfpq **out);
  * inverted lists -- O(new rows) arithmetic plus one 36 B/row re-layout.  *n_added = rows taken in (may be NULL).
  * The quantisers drift away from the data as it grows: rebuild when the corpus has roughly doubled. */
 int smt_ivfpq_append(smt_ivfpq *index, uint64_t *n_added);
+/* Compact the corpus AND carry the index along, instead of a rebuild.  The call compacts index->corpus exactly as smt_corpus_compact
+ * would -- the same validation, ordering rules, *rows_moved, effect on the image and on kept range sets -- and the index then describes
+ * the compacted corpus.  One call on purpose: the index update needs the keep list in the row numbering from BEFORE the compaction.
+ * With P the list's prefix map (old row keep[i].begin + j -> prefix[i] + j) and n_old the rows the index covered:
+ *   ids      P(id) of every kept entry and nothing else, in their old relative order: every list stays ascending by row
+ *   codes    the kept entries' 32 bytes, unchanged
+ *   offsets  offsets[l] = kept entries in front of list l; offsets[nlist] = the new covered row count = the kept rows below n_old
+ *   rows at or past n_old stay uncovered, as before the call: a later smt_ivfpq_append takes them in
+ *   centroids, |c|^2 / 2, codebooks, per-list bases and scales: the same allocations, the same bytes
+ *   *entries_dropped (may be NULL) = n_old - the new covered row count
+ * One stable stream compaction over the 36-byte entries and an id remap (ivfpq_compact.hip), out of place into fresh arrays sized for
+ * the kept count; no k-means, no quantiser fit, no encode, no sort.  The quantisers stay fitted to the rows of the build, as with
+ * smt_ivfpq_append.
+ *   - A list that drops nothing is a no-op for the index too: no kernel, no allocation, *entries_dropped = 0.
+ *   - Refused with the corpus AND the index untouched: an invalid list (SMT_E_INVALID), a corpus adopted with
+ *     smt_corpus_from_device (SMT_E_UNSUPPORTED), a list that keeps no row the index covers (SMT_E_UNSUPPORTED -- compact the
+ *     corpus alone and rebuild: this call never leaves an empty index).
+ *   - If the rows moved and the index then could not follow (memory, a HIP error), the index is marked stale: every later search,
+ *     append, save or compact on it returns SMT_E_INVALID ("... rebuild").  It is never left half updated.
+ *   - The call drains the one-query pipeline first and waits for the context's stream before it frees the old arrays: device
+ *     searches enqueued earlier complete with the answers of the corpus as it was.
+ *   - Only THIS index is carried.  A second smt_ivfpq on the same corpus is not: it is what an index is after smt_corpus_compact --
+ *     destroy and rebuild it. */
+int smt_ivfpq_compact(smt_ivfpq *index, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved /* may be NULL */,
+                      uint64_t *entries_dropped /* may be NULL */);
 
 /* ------------------------------------------------------- groups of GPUs (RCCL)
  * The reference runs the whole search synchronously from ONE task of ONE process (src/bin/semtools.rs:134-135,
@@ -589,6 +616,13 @@ int smt_sharded_ivfpq_save(smt_sharded_ivfpq *index, const char *path);
 int smt_sharded_ivfpq_load(smt_sharded_corpus *corpus, const char *path, smt_sharded_ivfpq **out);
 int smt_sharded_ivfpq_append(smt_sharded_ivfpq *index, uint64_t *n_added);
 int smt_sharded_ivfpq_info(const smt_sharded_ivfpq *index, uint64_t *rows_covered, uint32_t *nlist, uint64_t *index_bytes);
+/* smt_sharded_corpus_compact over index->corpus (GLOBAL rows, the same rules and refusals) with every shard's index following its
+ * shard's rows as in smt_ivfpq_compact: each rank's part of the list is cut out against the piece layout as it is before the call,
+ * then the piece list shrinks.  Every shard is checked before one row moves: SMT_E_UNSUPPORTED if the list leaves some shard's index
+ * without a covered row.  *rows_moved / *entries_dropped (may be NULL): summed over the shards.  If a shard's rows moved and its
+ * index could not follow, the compaction is completed on every shard, every shard's index is marked stale and the error is returned. */
+int smt_sharded_ivfpq_compact(smt_sharded_ivfpq *index, const smt_range *keep_global, uint32_t n_keep, uint64_t *rows_moved,
+                              uint64_t *entries_dropped);
 
 /* Exactness bookkeeping.  The f32 scan nominates top_k + 8 rows per list and the select stage PROVES per query
  * that no other row can belong to the exact answer (the k-th exact distance lies more than the f32 error bound

@@ -185,6 +185,15 @@ impl Drop for GpuSearch {
     }
 }
 
+/// Compact the corpus behind a sharded IVF index and carry the index along instead of rebuilding it
+/// (`smt_sharded_ivfpq_compact`): `keep` are the GLOBAL row ranges that stay, sorted and disjoint.
+/// Returns (rows moved, index entries dropped).  No reference counterpart: the reference's store has no index.
+pub fn compact_with_index(index: *mut SmtShardedIvfpq, keep: &[SmtRange]) -> Result<(u64, u64)> {
+    let (mut moved, mut dropped) = (0u64, 0u64);
+    check(unsafe { smt_sharded_ivfpq_compact(index, keep.as_ptr(), keep.len() as u32, &mut moved, &mut dropped) })?;
+    Ok((moved, dropped))
+}
+
 /// `search_with_workspace` (mod.rs:146-216) with the store of `crate::workspace::hip_store`: new / changed
 /// documents are embedded straight into the workspace corpus (no `Vec<Vec<f32>>`, no per-point JSON), then the
 /// path-subset search runs on the GPU.  The stderr progress lines and the order of the steps are the reference's.

@@ -352,6 +352,13 @@ extern "C" {
     pub fn smt_ivfpq_save(index: *mut SmtIvfpq, path: *const c_char) -> c_int;
     pub fn smt_ivfpq_load(corpus: *mut SmtCorpus, path: *const c_char, out: *mut *mut SmtIvfpq) -> c_int;
     pub fn smt_ivfpq_append(index: *mut SmtIvfpq, n_added: *mut u64) -> c_int;
+    pub fn smt_ivfpq_compact(
+        index: *mut SmtIvfpq,
+        keep: *const SmtRange,
+        n_keep: u32,
+        rows_moved: *mut u64,
+        entries_dropped: *mut u64,
+    ) -> c_int;
     pub fn smt_init(devices: *const c_int, n_dev: c_int) -> c_int;
     pub fn smt_shutdown() -> c_int;
     pub fn smt_default_group() -> *mut SmtGroup;
@@ -621,6 +628,13 @@ extern "C" {
         rows_covered: *mut u64,
         nlist: *mut u32,
         index_bytes: *mut u64,
+    ) -> c_int;
+    pub fn smt_sharded_ivfpq_compact(
+        index: *mut SmtShardedIvfpq,
+        keep_global: *const SmtRange,
+        n_keep: u32,
+        rows_moved: *mut u64,
+        entries_dropped: *mut u64,
     ) -> c_int;
     pub fn smt_ctx_uncertain_count(ctx: *mut SmtCtx, count: *mut u64, reset: c_int) -> c_int;
     pub fn smt_debug_range_sets(corpus: *const SmtCorpus, kept: *mut u64, hits: *mut u64, builds: *mut u64) -> c_int;

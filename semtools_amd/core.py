@@ -393,6 +393,14 @@ class IvfPq:
         L.check(L.lib().smt_ivfpq_append(self._h, C.byref(n)))
         return int(n.value)
 
+    def compact(self, ranges):
+        """smt_ivfpq_compact: Corpus.compact(ranges) on the index's corpus, with the index carried along instead of rebuilt (dead
+        entries dropped, kept ones renamed, quantisers untouched).  Returns (rows_moved, entries_dropped)."""
+        rng, n = _ranges_arg(list(ranges))
+        moved, dropped = C.c_uint64(0), C.c_uint64(0)
+        L.check(L.lib().smt_ivfpq_compact(self._h, C.cast(rng, C.c_void_p), n, C.byref(moved), C.byref(dropped)))
+        return int(moved.value), int(dropped.value)
+
     @classmethod
     def load(cls, corpus, path):
         """Restore an index saved beside `corpus` (fails unless the row count matches)."""
@@ -774,6 +782,14 @@ class ShardedIvfPq:
         n = C.c_uint64(0)
         L.check(L.lib().smt_sharded_ivfpq_append(self._h, C.byref(n)))
         return int(n.value)
+
+    def compact(self, ranges):
+        """smt_sharded_ivfpq_compact: ShardedCorpus.compact(ranges) (GLOBAL rows) with every shard's index carried along.  Returns
+        (rows_moved, entries_dropped), summed over the shards."""
+        rng, n = _ranges_arg(list(ranges))
+        moved, dropped = C.c_uint64(0), C.c_uint64(0)
+        L.check(L.lib().smt_sharded_ivfpq_compact(self._h, C.cast(rng, C.c_void_p), n, C.byref(moved), C.byref(dropped)))
+        return int(moved.value), int(dropped.value)
 
     def info(self):
         rows, nlist, nbytes = C.c_uint64(), C.c_uint32(), C.c_uint64()

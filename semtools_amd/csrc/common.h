@@ -246,6 +246,16 @@ int launch_pack_image(smt_ctx *ctx, const float *corpus, uint64_t n_rows, uint64
 // compact.hip: keep exactly the rows inside `keep` (sorted, disjoint, inside [0, rows)) and close the gaps in place -- the body of
 // smt_corpus_compact.  Validates first: a refused list leaves the corpus untouched.
 int corpus_compact(smt_corpus *c, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved);
+// ... in its two halves, for a caller that has to look at the validated list before a row moves (ivfpq_compact.hip carries an index
+// along): _plan checks the corpus and the list exactly as smt_corpus_compact does and leaves the non-empty ranges, the exclusive
+// prefix of their lengths, the new row count and the first row that moves; _run is everything behind the validation.
+struct CompactPlan {
+    std::vector<smt_range> ranges;   // the non-empty kept ranges
+    std::vector<uint64_t> prefix;    // [ranges.size() + 1]: old row ranges[i].begin + j becomes row prefix[i] + j
+    uint64_t new_rows = 0, first_moved = 0;
+};
+int corpus_compact_plan(const smt_corpus *c, const smt_range *keep, uint32_t n_keep, CompactPlan &plan);
+int corpus_compact_run(smt_corpus *c, const CompactPlan &plan, uint64_t *rows_moved);
 // The range rules of smt_search for the callers that check them on their own, before they enqueue anything (the sharded searches on
 // GLOBAL rows, the IVF search inside ranges): a list where n > 0, begin <= end <= rows, sorted and disjoint; empty ranges allowed.
 inline int validate_ranges(const smt_range *ranges, uint32_t n, uint64_t rows)

@@ -86,15 +86,16 @@ struct Step { uint64_t v, n; bool bounced; };
 
 }  // namespace
 
-int corpus_compact(smt_corpus *c, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved)
+int corpus_compact_plan(const smt_corpus *c, const smt_range *keep, uint32_t n_keep, CompactPlan &plan)
 {
     SMT_REQUIRE(c != nullptr, "corpus");
     SMT_REQUIRE(keep || n_keep == 0, "keep");
-    if (rows_moved) *rows_moved = 0;
     if (!c->owned) { set_error("smt_corpus_compact: a corpus adopted from device memory is the caller's to rearrange"); return SMT_E_UNSUPPORTED; }
     // validate, drop empty ranges, prefix; first_moved = the first virtual row whose source is not itself
-    std::vector<smt_range> rr;
-    std::vector<uint64_t> prefix(1, 0);
+    std::vector<smt_range> &rr = plan.ranges;
+    std::vector<uint64_t> &prefix = plan.prefix;
+    rr.clear();
+    prefix.assign(1, 0);
     uint64_t prev_end = 0, new_rows = 0, first_moved = 0;
     bool gap = false;
     for (uint32_t k = 0; k < n_keep; ++k) {
@@ -110,6 +111,26 @@ int corpus_compact(smt_corpus *c, const smt_range *keep, uint32_t n_keep, uint64
         prefix.push_back(new_rows);
     }
     if (!gap) first_moved = new_rows;
+    plan.new_rows = new_rows;
+    plan.first_moved = first_moved;
+    return SMT_OK;
+}
+
+int corpus_compact(smt_corpus *c, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved)
+{
+    if (rows_moved) *rows_moved = 0;
+    CompactPlan plan;
+    int rc = corpus_compact_plan(c, keep, n_keep, plan);
+    if (rc) return rc;
+    return corpus_compact_run(c, plan, rows_moved);
+}
+
+int corpus_compact_run(smt_corpus *c, const CompactPlan &plan, uint64_t *rows_moved)
+{
+    if (rows_moved) *rows_moved = 0;
+    const std::vector<smt_range> &rr = plan.ranges;
+    const std::vector<uint64_t> &prefix = plan.prefix;
+    const uint64_t new_rows = plan.new_rows, first_moved = plan.first_moved;
     smt_ctx *ctx = c->ctx;
     // a list that drops nothing covers [0, rows): no row moves, nothing is enqueued (and an index built on the corpus stays valid)
     if (new_rows == c->rows) { ++ctx->compact_calls; return SMT_OK; }

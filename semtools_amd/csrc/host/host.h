@@ -350,8 +350,9 @@ public:
     // every stored document) of a store of at least `min_rows` rows, and searches over a path subset that itself holds at least
     // `min_rows` rows (smt_sharded_ivfpq_search_ranges: the index searched inside the subset's row ranges, so dead rows never
     // come back and no head-room is fetched), go through an IVF index with per-list PCA codes (local_pca = 1) that lives
-    // beside the vectors (`line_index.ivf`), is extended incrementally when rows are appended and rebuilt when rows
-    // move (compaction) or the corpus has doubled.  oversample_factor (WorkspaceConfig, src/workspace/mod.rs:13,22 --
+    // beside the vectors (`line_index.ivf`), is extended incrementally when rows are appended, follows an in-place compaction
+    // (smt_sharded_ivfpq_compact: carried and saved again, not rebuilt) and is rebuilt when rows change rank or are rewritten, or the
+    // corpus has doubled.  oversample_factor (WorkspaceConfig, src/workspace/mod.rs:13,22 --
     // vestigial in the reference, whose store scans exactly) sets the re-score depth: 2 * top_k * oversample_factor
     // ADC candidates per probed list (at least 64) are re-scored against the full-precision rows.  Every returned
     // distance is exact; only membership is approximate.  Searches over a smaller path subset, top_k > 24, or smaller
@@ -368,7 +369,7 @@ private:
     bool compact_in_place(const std::vector<std::pair<uint64_t, std::string>> &order);   // compact_if_sparse on the device; false: not possible / not wise here
     void drop_index();                           // index_ (points into corpus_) and its files: rows are about to move
     void remove_index_files() const;             // every line_index.* of the directory, whatever rank count wrote it
-    uint64_t generation_ = 0;                    // bumped by drop_index; line_rows.json and line_index.gen carry it
+    uint64_t generation_ = 0;                    // bumped by drop_index and by a compaction that carried the index; line_rows.json and line_index.gen carry it
     std::string index_file(int rank) const;
     std::map<std::string, DocMeta> docs_;        // documents shard
     std::map<std::string, Extent> extents_;      // path -> rows holding its lines (line i = first_row + i)
@@ -381,6 +382,7 @@ private:
     void write_rows_ahead() const;
     // approximate index (built / extended lazily by the first search that qualifies)
     bool ensure_index() const;
+    void save_index() const;                     // index_ -> line_index.ivf*, then line_index.gen (generation, rank count)
     mutable smt_sharded_ivfpq *index_ = nullptr;
     mutable bool index_on_disk_ = false;
     mutable uint64_t index_built_rows_ = 0;      // corpus rows when the quantisers were trained

@@ -269,19 +269,25 @@ bool Store::ensure_index() const
         index_built_rows_ = rows;
         changed = true;
     }
-    if (changed) {  // persist beside the vectors (a sibling first, then rename: smt_sharded_ivfpq_save)
-        if (smt_sharded_ivfpq_save(index_, file.c_str()) == SMT_OK) {
-            json::Value g = json::Value::object();
-            g.set("generation", json::Value::uint(generation_));
-            g.set("n_ranks", json::Value::uint((uint64_t)n_ranks));
-            g.set("rows", json::Value::uint(rows));
-            try {
-                write_file_atomic(dir_ + "/line_index.gen", json::to_string_pretty(g));
-                index_on_disk_ = true;
-            } catch (const std::exception &) { remove_index_files(); }
-        }
-    }
+    if (changed) save_index();
     return true;
+}
+
+// persist the index beside the vectors (a sibling first, then rename: smt_sharded_ivfpq_save), then line_index.gen naming the corpus
+// generation and the rank count it is valid for
+void Store::save_index() const
+{
+    int n_ranks = 1;
+    (void)smt_group_info(group_, &n_ranks, nullptr, nullptr, nullptr, nullptr);
+    if (smt_sharded_ivfpq_save(index_, (dir_ + "/line_index.ivf").c_str()) != SMT_OK) return;
+    json::Value g = json::Value::object();
+    g.set("generation", json::Value::uint(generation_));
+    g.set("n_ranks", json::Value::uint((uint64_t)n_ranks));
+    g.set("rows", json::Value::uint(smt_sharded_corpus_rows(corpus_)));
+    try {
+        write_file_atomic(dir_ + "/line_index.gen", json::to_string_pretty(g));
+        index_on_disk_ = true;
+    } catch (const std::exception &) { remove_index_files(); }
 }
 
 std::unordered_map<std::string, DocMeta> Store::get_existing_docs(const std::vector<std::string> &paths) const
@@ -644,10 +650,37 @@ bool Store::compact_in_place(const std::vector<std::pair<uint64_t, std::string>>
         const uint64_t fullest = *std::max_element(left.begin(), left.end());
         if (fullest * 2 * (uint64_t)n_ranks > live * 3) return false;
     }
-    drop_index();                            // the index names rows by position: it goes before they move
-    const int rc = smt_sharded_corpus_compact(corpus_, keep.data(), (uint32_t)keep.size(), nullptr);
-    if (rc == SMT_E_UNSUPPORTED) return false;   // (refused before any row moved)
-    check(rc, "compact");
+    // An index in memory or on disk FOLLOWS the rows (smt_sharded_ivfpq_compact: dead entries dropped, kept ones renamed, quantisers
+    // untouched) instead of being dropped and rebuilt by the next search.  One on disk is loaded first, against the corpus as it
+    // still is.  index_built_rows_ stays: "rebuild once the corpus is past twice the rows the quantisers were fitted to" goes on
+    // deciding when the lists are too old.
+    if (!index_ && index_on_disk_) {
+        if (smt_sharded_ivfpq_load(corpus_, (dir_ + "/line_index.ivf").c_str(), &index_) != SMT_OK) index_ = nullptr;
+        if (index_) { uint64_t n = 0; smt_sharded_ivfpq_info(index_, &n, nullptr, nullptr); index_built_rows_ = n; }
+    }
+    uint64_t live = 0;
+    for (const smt_range &r : keep) live += r.end - r.begin;
+    bool carried = false, moved = false;
+    if (index_) {
+        const int rc = smt_sharded_ivfpq_compact(index_, keep.data(), (uint32_t)keep.size(), nullptr, nullptr);
+        carried = rc == SMT_OK;
+        // not carried: either refused before a row moved (a list that leaves a shard's index empty, ...) -- today's path below -- or
+        // the rows moved and the index could not follow: the compaction itself stands, only the stale index goes
+        moved = !carried && smt_sharded_corpus_rows(corpus_) == live;
+    }
+    if (carried) {
+        // a new corpus generation either way, and every line_index.* file of the old one goes (also those of another rank count)
+        ++generation_;
+        remove_index_files();
+        index_on_disk_ = false;
+    } else {
+        drop_index();                            // the index names rows by position: it goes before they move
+        if (!moved) {
+            const int rc = smt_sharded_corpus_compact(corpus_, keep.data(), (uint32_t)keep.size(), nullptr);
+            if (rc == SMT_E_UNSUPPORTED) return false;   // (refused before any row moved)
+            check(rc, "compact");
+        }
+    }
     uint64_t at = 0;
     for (auto &o : order) {
         Extent &x = extents_[o.second];
@@ -656,6 +689,7 @@ bool Store::compact_in_place(const std::vector<std::pair<uint64_t, std::string>>
     }
     dead_rows_ = 0;
     rows_on_disk_valid_ = false;  // rows moved: the file must be rewritten
+    if (carried) save_index();    // at once, under the new generation: the process that opens the store next finds it
     return true;
 }
 

@@ -75,6 +75,7 @@ struct smt_ivfpq {
     float *d_basis = nullptr;       // kind 1: [nlist][32][256]
     float *d_lscale = nullptr;      // kind 1: [nlist][32]
     uint64_t max_list = 0;          // longest inverted list (segments per probed list at query time)
+    bool stale = false;             // smt_ivfpq_compact moved the corpus and then failed on the index: every later use asks for a rebuild
     double build_ms[4] = {0, 0, 0, 0};  // coarse train, assign all, pq train, encode+lists
 };
 
@@ -86,6 +87,9 @@ struct smt_ivfpq {
             return SMT_E_HIP;                                                                  \
         }                                                                                      \
     } while (0)
+
+// an index left behind by a failed smt_ivfpq_compact answers nothing any more (search, append, save, compact)
+#define IVF_REQUIRE_FRESH(ix) SMT_REQUIRE(!(ix)->stale, "the corpus was compacted and the index could not follow: rebuild")
 
 namespace smt {
 
@@ -102,5 +106,11 @@ inline int ivf_dev_alloc(IvfDevBuf &b, size_t bytes)
 }
 
 int ivf_compute_max_list(smt_ivfpq *ix);   // longest inverted list, from the offsets on the device (ivfpq_io.hip)
+
+// smt_ivfpq_compact in its two halves (ivfpq_compact.hip), so that the sharded form can check every shard before one row moves:
+// _check refuses (stale index, invalid list, adopted corpus, no kept row the index covers) and leaves the validated list in `plan`
+// and the rows the index will cover in n_new; _apply carries the index, then compacts the corpus (corpus_compact_run).
+int ivfpq_compact_check(const smt_ivfpq *ix, const smt_range *keep, uint32_t n_keep, CompactPlan &plan, uint64_t &n_new);
+int ivfpq_compact_apply(smt_ivfpq *ix, const CompactPlan &plan, uint64_t n_new, uint64_t *rows_moved, uint64_t *entries_dropped);
 
 }  // namespace smt

@@ -746,6 +746,7 @@ try {
     smt_corpus *corpus = ix->corpus;
     smt_ctx *ctx = corpus->ctx;
     if (n_added) *n_added = 0;
+    IVF_REQUIRE_FRESH(ix);
     SMT_REQUIRE(corpus->rows >= ix->n_rows, "the corpus shrank since the index was built: rebuild");
     const uint64_t n_old = ix->n_rows, n_new = corpus->rows - n_old, N = corpus->rows;
     if (n_new == 0) return SMT_OK;

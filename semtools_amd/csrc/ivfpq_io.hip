@@ -110,6 +110,7 @@ extern "C" {
 int smt_ivfpq_save(smt_ivfpq *ix, const char *path)
 try {
     SMT_REQUIRE(ix && path, "null argument");
+    IVF_REQUIRE_FRESH(ix);
     smt_ctx *ctx = ix->corpus->ctx;
     IVF_HIP(hipSetDevice(ctx->device));
     { int rc_drain = smt::drain_async(ctx); if (rc_drain) return rc_drain; }

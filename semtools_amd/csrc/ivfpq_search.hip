@@ -574,6 +574,7 @@ static int ivfpq_search_core(smt_ivfpq *ix, const float *queries, bool queries_o
                              uint64_t **d_or_out, size_t *out_bytes_contig, uint64_t out_stride = 0, smt::Delivery *deliver = nullptr)
 {
     smt_ctx *ctx = ix->corpus->ctx;
+    IVF_REQUIRE_FRESH(ix);
     SMT_REQUIRE(ix->corpus->rows >= ix->n_rows, "the corpus shrank after the index was built: rebuild");
     SMT_REQUIRE(nprobe >= 1 && nprobe <= ix->nlist && nprobe <= 512, "nprobe must be in [1, min(nlist, 512)]");
     SMT_REQUIRE(top_k <= 56, "top_k must be <= 56 for the IVF-PQ path");

@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "group.h"
+#include "ivfpq.h"
 
 using namespace smt;
 
@@ -524,11 +525,16 @@ try {
     return sharded_copy_rows(sc, first_row, n_rows, nullptr, rows);
 } catch (...) { return smt::api_catch(); }
 
-int smt_sharded_corpus_compact(smt_sharded_corpus *sc, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved)
-try {
+// The body of smt_sharded_corpus_compact and of smt_sharded_ivfpq_compact (six != nullptr: every shard's index follows its shard's
+// rows, smt_ivfpq_compact's steps).  The index form checks EVERY shard before one row moves, and does the per-shard steps inside the
+// loop below because the keep list is localised against the piece list as it is BEFORE the compaction rewrites it.
+static int sharded_compact(smt_sharded_corpus *sc, smt_sharded_ivfpq *six, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved,
+                           uint64_t *entries_dropped)
+{
     SMT_REQUIRE(sc && (keep || n_keep == 0), "null argument");
     smt_group *g = sc->group;
     if (rows_moved) *rows_moved = 0;
+    if (entries_dropped) *entries_dropped = 0;
     // the ranks' rows of other processes cannot be told to move from here, and the host layer above is one process
     if (!single_process(g)) { set_error("compaction needs a single-process group"); return SMT_E_UNSUPPORTED; }
     uint64_t prev_end = 0;
@@ -540,15 +546,35 @@ try {
     }
     for (smt_corpus *c : sc->shard)   // (before any shard moves a row: a refused call leaves the corpus as it was)
         if (!c->owned) { set_error("smt_sharded_corpus_compact: a shard adopted from device memory is the caller's to rearrange"); return SMT_E_UNSUPPORTED; }
-    // every shard keeps its part of the list (local rows ascend with global rows inside a rank) and closes its own gaps
-    uint64_t moved = 0;
     std::vector<smt_range> local;
-    for (int i = 0; i < g->n_local; ++i) {
+    std::vector<CompactPlan> plans(six ? g->n_local : 0);
+    std::vector<uint64_t> n_new(six ? g->n_local : 0, 0);
+    for (int i = 0; six && i < g->n_local; ++i) {   // (a stale shard index, a shard whose index would end empty: refused here)
         layout_localize(sc, g->first_rank + i, keep, n_keep, local);
-        uint64_t m = 0;
-        const int rc = smt_corpus_compact(sc->shard[i], local.data(), (uint32_t)local.size(), &m);
+        const int rc = ivfpq_compact_check(six->shard[i], local.data(), (uint32_t)local.size(), plans[i], n_new[i]);
         if (rc) return rc;
+    }
+    // every shard keeps its part of the list (local rows ascend with global rows inside a rank) and closes its own gaps
+    uint64_t moved = 0, dropped = 0;
+    int index_rc = SMT_OK;       // a shard whose rows moved and whose index could not follow: the compaction goes on without the index
+    std::string index_why;
+    for (int i = 0; i < g->n_local; ++i) {
+        uint64_t m = 0, d = 0;
+        int rc;
+        if (six && index_rc == SMT_OK) {
+            rc = ivfpq_compact_apply(six->shard[i], plans[i], n_new[i], &m, &d);
+            if (rc && six->shard[i]->stale && sc->shard[i]->rows == plans[i].new_rows) { index_rc = rc; index_why = smt_last_error(); rc = SMT_OK; }
+        } else {
+            layout_localize(sc, g->first_rank + i, keep, n_keep, local);
+            rc = smt_corpus_compact(sc->shard[i], local.data(), (uint32_t)local.size(), &m);
+        }
+        if (rc) {
+            // shards in front of this one may have moved: the index no longer describes the corpus as a whole
+            if (six && (i > 0 || six->shard[i]->stale)) { const std::string why = smt_last_error(); for (smt_ivfpq *ix : six->shard) ix->stale = true; set_error("%s", why.c_str()); }
+            return rc;
+        }
         moved += m;
+        dropped += d;
     }
     // the piece list: each piece shrinks to its kept rows, empty ones go, both numberings are prefixed again; neighbours in global
     // order that lie on one rank are neighbours in its local order too (nothing of that rank lies between them) and merge
@@ -578,7 +604,24 @@ try {
     sc->rank_rows.swap(rank_rows);
     layout_reindex(sc);   // (bumps layout_version: the device piece tables of layout_translate_packed are uploaded again)
     if (rows_moved) *rows_moved = moved;
+    if (index_rc) {   // the corpus is compacted and consistent; the index as a whole is not
+        for (smt_ivfpq *ix : six->shard) ix->stale = true;
+        set_error("%s", index_why.c_str());
+        return index_rc;
+    }
+    if (entries_dropped) *entries_dropped = dropped;
     return SMT_OK;
+}
+
+int smt_sharded_corpus_compact(smt_sharded_corpus *sc, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved)
+try {
+    return sharded_compact(sc, nullptr, keep, n_keep, rows_moved, nullptr);
+} catch (...) { return smt::api_catch(); }
+
+int smt_sharded_ivfpq_compact(smt_sharded_ivfpq *six, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved, uint64_t *entries_dropped)
+try {
+    SMT_REQUIRE(six != nullptr, "index");
+    return sharded_compact(six->corpus, six, keep, n_keep, rows_moved, entries_dropped);
 } catch (...) { return smt::api_catch(); }
 
 /* ------------------------------------------------- replicated model + sharded K1 ---- */
