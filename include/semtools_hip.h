@@ -640,6 +640,12 @@ int smt_ctx_uncertain_count(smt_ctx *ctx, uint64_t *count, int reset);
  * searching the same file set again uploads only its queries.  kept: sets alive; hits: searches answered from one; builds: sets made. */
 int smt_debug_range_sets(const smt_corpus *corpus, uint64_t *kept, uint64_t *hits, uint64_t *builds);
 
+/* Test hook for the fp16 operand image: brings the image up to date, as a batched search would, and copies the 16 KiB of 32-row
+ * tile `tile` (and the tile's zero-row mask, bit r = tile row r packed as a zero row) to the host.  The tests compare the tile that
+ * straddles the row count between corpora whose memory behind the rows differs: rows at or past the row count are packed as zero
+ * rows, whatever lies there.  SMT_E_INVALID when the corpus has no image or the tile holds no row. */
+int smt_debug_image_tile(smt_corpus *corpus, uint64_t tile, void *out_tile_host, uint32_t *out_zero_mask);
+
 /* Test hook for delivered answers (tuning key direct_delivery): how many host-form searches on this context got their answer written
  * into pinned host memory by the select kernel and waited on its completion word, instead of a D2H copy + hipStreamSynchronize. */
 int smt_debug_deliveries(smt_ctx *ctx, uint64_t *count);

@@ -638,6 +638,7 @@ extern "C" {
     ) -> c_int;
     pub fn smt_ctx_uncertain_count(ctx: *mut SmtCtx, count: *mut u64, reset: c_int) -> c_int;
     pub fn smt_debug_range_sets(corpus: *const SmtCorpus, kept: *mut u64, hits: *mut u64, builds: *mut u64) -> c_int;
+    pub fn smt_debug_image_tile(corpus: *mut SmtCorpus, tile: u64, out_tile_host: *mut c_void, out_zero_mask: *mut u32) -> c_int;
     pub fn smt_debug_deliveries(ctx: *mut SmtCtx, count: *mut u64) -> c_int;
     pub fn smt_debug_scan_pairs(ctx: *mut SmtCtx, paired: *mut u64, alone: *mut u64, absorbed: *mut u64) -> c_int;
     pub fn smt_debug_group_fail_next(group: *mut SmtGroup, where_: c_int, code: c_int) -> c_int;

@@ -308,6 +308,13 @@ class Corpus:
     def image_bytes(self):
         return int(L.lib().smt_corpus_image_bytes(self._h))
 
+    def image_tile(self, tile):
+        """Test hook (smt_debug_image_tile): (the 16 KiB of tile `tile` of the up-to-date operand image as bytes, its zero-row mask)."""
+        buf = np.empty(16384, dtype=np.uint8)
+        zm = C.c_uint32(0)
+        L.check(L.lib().smt_debug_image_tile(self._h, int(tile), L.np_ptr(buf), C.byref(zm)))
+        return buf.tobytes(), int(zm.value)
+
     def debug_batched_scores(self, queries, first_row=0, n_rows=None):
         """Test hook (smt_debug_batched_scores): the f32 distances the batched kernels nominate candidates with,
         float32 [n_rows, nq]."""

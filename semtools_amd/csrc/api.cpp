@@ -894,6 +894,22 @@ try {
 
 uint64_t smt_corpus_image_bytes(const smt_corpus *c) { return c && c->image ? c->image_cap_tiles * (16384 + 4) : 0; }
 
+int smt_debug_image_tile(smt_corpus *c, uint64_t tile, void *out_tile_host, uint32_t *out_zero_mask)
+try {
+    SMT_REQUIRE(c != nullptr && out_tile_host != nullptr && out_zero_mask != nullptr, "null argument");
+    int rc = bind_device(c->ctx);
+    if (rc) return rc;
+    const void *img = nullptr;
+    const uint32_t *zero = nullptr;
+    if ((rc = corpus_image_sync(c, 0, &img, &zero))) return rc;
+    SMT_REQUIRE(img != nullptr && zero != nullptr, "the corpus has no operand image");
+    SMT_REQUIRE(tile < (c->rows + 31) / 32, "tile outside the corpus");
+    SMT_HIP_CHECK(hipMemcpyAsync(out_tile_host, static_cast<const char *>(img) + (size_t)tile * 16384, 16384, hipMemcpyDeviceToHost, c->ctx->stream));
+    SMT_HIP_CHECK(hipMemcpyAsync(out_zero_mask, zero + tile, sizeof(uint32_t), hipMemcpyDeviceToHost, c->ctx->stream));
+    SMT_HIP_CHECK(hipStreamSynchronize(c->ctx->stream));
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
 int smt_corpus_read_rows(smt_corpus *c, uint64_t first_row, uint64_t n_rows, float *out_host)
 try {
     SMT_REQUIRE(c != nullptr && (out_host || n_rows == 0), "null argument");
