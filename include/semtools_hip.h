@@ -653,8 +653,14 @@ int smt_debug_deliveries(smt_ctx *ctx, uint64_t *count);
 /* Test hook for paired scans (tuning key scan_pair): after a synchronise, how many one-query scans of this context's scan_overlap
  * pipeline took the query of the call two steps later along (paired), ran with their own query only (alone), or found their rows
  * already scanned by the call two steps earlier and ended at once (absorbed; equal to paired once the pipeline is empty).
- * Counted on the device since the context was created. */
+ * Counted on the device since the context was created.  With scan_pair > 1 a scan may take up to three later calls along: `paired`
+ * counts the scans that took at least one, `absorbed` every scan that ended at once (paired <= absorbed <= 3 x paired). */
 int smt_debug_scan_pairs(smt_ctx *ctx, uint64_t *paired, uint64_t *alone, uint64_t *absorbed);
+
+/* The same launches by the number of calls their corpus pass served: by_size[n - 1] = scans that served n calls, their own and
+ * n - 1 taken along (n = 1..4).  by_size[0] is `alone` above, by_size[1] + by_size[2] + by_size[3] is `paired`, and the sum of
+ * n x by_size[n - 1] is the number of calls once the pipeline is empty.  Synchronises. */
+int smt_debug_scan_groups(smt_ctx *ctx, uint64_t *by_size /* [4] */);
 
 /* Test hook for the SPMD error paths of multi-process groups: arms ONE injected failure with status `code` (an SMT_E_* value) on
  * THIS process's ranks; it fires at the next step of kind `where` and disarms.  The tests arm it on one rank of an n-rank group and
@@ -736,16 +742,20 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *   scan_overlap (1/0)   see async_select (default 1; 0 = the aux-stream / flag pipeline).  A launch bracketed by profiling
  *                        events (prof_every) waits for its predecessor and the next launch waits for it, so the events
  *                        time the kernel alone, not the gate or a shared HBM.
- *   scan_gate_pct (0..100)  scan_overlap: a scan's blocks start loading rows once this per cent of the previous scan's blocks have
- *                        finished theirs, or after a bound of at most 0.5 ms (default 50; 0 = at once).  Changes timing only,
- *                        never an answer
- *   scan_pair (0/1)      scan_overlap: a scan that queues up behind a predecessor on its internal stream looks, on the device when it
- *                        starts, for the call two steps later (the next one on that stream); if that call is queued in front of the same corpus with the same list
- *                        size and grid, and no work was pending on the context's stream when it was made, the scan takes its query
- *                        along in the same corpus pass and that call's own scan ends at once.  Each call's select, outputs and
- *                        status word stay its own, so no answer changes.  A launch bracketed by profiling events and its successor
- *                        never pair, and a call made while the GPU keeps up runs the plain kernel.  Switching it drains
- *                        the pipeline (default 1)
+ *   scan_gate_pct (-1..100)  scan_overlap: a scan's blocks start loading rows once this per cent of the previous call's blocks have
+ *                        finished theirs, or after a bound of at most 0.5 ms (0 = at once).  The gate counts calls served: a
+ *                        scan that serves n calls in one pass (scan_pair) counts n for each of its blocks, so the point lies at
+ *                        (m - 1 + pct / 100) / n of that pass when the previous call is the m-th it serves.  Default -1: 50, and
+ *                        no gate with scan_pair >= 2.  Changes timing only, never an answer
+ *   scan_pair (0..3)     scan_overlap: the number of later calls a scan may take along.  A scan that queues up behind a predecessor on
+ *                        its internal stream looks, on the device when it starts, for the calls two, four and six steps later (the
+ *                        next ones on that stream); the longest run of them that is queued in front of the same corpus with the same
+ *                        list size and grid, with no work pending on the context's stream when each was made, has its queries
+ *                        taken along in the same corpus pass, and those calls' own scans end at once.  The run is a prefix: a call
+ *                        that cannot be taken ends it.  Each call's select, outputs and status word stay its own, so no answer
+ *                        changes.  A launch bracketed by profiling events and its successor neither take nor are taken, and a
+ *                        call made while the GPU keeps up runs the plain kernel.  1 = pairs only.  Switching it drains the
+ *                        pipeline (default 3)
  *   scan_pair_ring (64..4096, a power of two)  scan_pair: slots of the descriptor ring in use.  A call can be taken along while the
  *                        host is fewer calls ahead of the GPU than this; a call further ahead simply scans for itself.  Switching
  *                        it drains the pipeline (default 4096; tests use 64 to see slots reused)

@@ -71,12 +71,20 @@ class Context:
 
     def scan_pairs(self):
         """(paired, alone, absorbed): one-query scans of the scan_overlap pipeline that took the query of the call two steps later
-        along, ran alone, or were absorbed by the call two steps earlier (smt_debug_scan_pairs).  Synchronises.
-        Tuning keys: scan_pair (1/0, default 1; switching it drains the pipeline), scan_pair_ring (slots of the descriptor ring in
+        along, ran alone, or were absorbed by the call two steps earlier (smt_debug_scan_pairs).  Synchronises.  With scan_pair > 1 a
+        scan takes up to three later calls along: paired counts the scans that took any, absorbed every scan that ended at once.
+        Tuning keys: scan_pair (0..3 calls taken along, default 3; switching it drains the pipeline), scan_pair_ring (slots of the descriptor ring in
         use, 64..4096) and, for tests, scan_pair_wait_us (0..5000: the deciding block waits that long for the later call)."""
         v = [C.c_uint64(0) for _ in range(3)]
         L.check(L.lib().smt_debug_scan_pairs(self._h, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
+
+    def scan_groups(self):
+        """by_size: by_size[n - 1] = scans of the scan_overlap pipeline whose corpus pass served n calls, n = 1..4
+        (smt_debug_scan_groups).  Synchronises."""
+        v = (C.c_uint64 * 4)()
+        L.check(L.lib().smt_debug_scan_groups(self._h, v))
+        return tuple(int(x) for x in v)
 
     def compact_stats(self, reset=False):
         """CompactStats(calls, rows_moved): the Corpus.compact calls that succeeded on this context and the rows they moved."""

@@ -96,7 +96,7 @@ int drain_async(smt_ctx *ctx)
         SMT_HIP_CHECK(hipMemcpy(&gave_up, ctx->d_gate + 1, sizeof(gave_up), hipMemcpyDeviceToHost));
         if (gave_up) {
             (void)hipMemset(ctx->d_gate + 1, 0, sizeof(gave_up));
-            set_error("scan_pair: a scan block gave up waiting for its launch's pairing decision");
+            set_error("scan_pair: a scan block gave up waiting for its launch's grouping decision");
             return SMT_E_HIP;
         }
     }
@@ -461,6 +461,23 @@ try {
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
+int smt_debug_scan_groups(smt_ctx *ctx, uint64_t *by_size)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    SMT_REQUIRE(by_size != nullptr, "null argument");
+    if ((rc = bind_device(ctx))) return rc;
+    SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if ((rc = sync_side_streams(ctx))) return rc;
+    unsigned long long v[6] = {0, 0, 0, 0, 0, 0};   // paired, alone, absorbed, served 2 / 3 / 4 (scan_kernels.hip PairParams::ctl)
+    if (ctx->d_gate) SMT_HIP_CHECK(hipMemcpy(v, ctx->d_gate + 2, sizeof(v), hipMemcpyDeviceToHost));
+    by_size[0] = v[1] + ctx->pair_alone_host;
+    by_size[1] = v[3];
+    by_size[2] = v[4];
+    by_size[3] = v[5];
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
 int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out)
 try {
     int rc = check_ctx(ctx);
@@ -577,7 +594,8 @@ try {
     } else if (k == "scan_pair") {
         int rc2 = drain_async(ctx);
         if (rc2) return rc2;
-        ctx->tune.scan_pair = value ? 1 : 0;
+        SMT_REQUIRE(value >= 0 && value <= 3, "scan_pair: 0..3 later calls a queued scan may take along");
+        ctx->tune.scan_pair = (int)value;
     } else if (k == "scan_pair_ring") {
         SMT_REQUIRE(value >= 64 && value <= 4096 && (value & (value - 1)) == 0, "scan_pair_ring: a power of two, 64..4096 slots");
         int rc2 = drain_async(ctx);
@@ -587,7 +605,7 @@ try {
         SMT_REQUIRE(value >= 0 && value <= 5000, "scan_pair_wait_us: 0..5000 us (tests only)");
         ctx->tune.scan_pair_wait_us = (int)value;
     } else if (k == "scan_gate_pct") {
-        SMT_REQUIRE(value >= 0 && value <= 100, "scan_gate_pct: 0..100 per cent of the previous scan's blocks (0 = no gate)");
+        SMT_REQUIRE(value >= -1 && value <= 100, "scan_gate_pct: 0..100 per cent of the previous scan's blocks (0 = no gate), or -1 for the default");
         ctx->tune.scan_gate_pct = (int)value;
     }
     else if (k == "scan_debug_ptr") ctx->tune.scan_debug_ptr = value;

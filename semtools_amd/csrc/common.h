@@ -64,8 +64,8 @@ struct Tuning {
     int merge_on_aux = 0;       // 1: smt_merge_topk_packed_device runs on the aux stream (behind the async select it consumes)
     int async_select = 0;       // 1: single-query top-k searches overlap their select stage with the next scan
     int scan_overlap = 1;       // async_select, smt_search_topk_device: scan + select of call i on internal stream i & 1 (consecutive scans overlap; 0 = the aux-stream / flag pipeline)
-    int scan_gate_pct = 50;     // scan_overlap: a scan's blocks start once this share of its predecessor's blocks has finished its rows (0 = no gate)
-    int scan_pair = 1;          // scan_overlap: a scan that starts behind a predecessor takes the query of the call two steps later (the next one on its stream) along in the same corpus pass (scan_kernels.hip scan_pair_kernel)
+    int scan_gate_pct = -1;     // scan_overlap: a scan's blocks start once this share of its predecessor call's blocks has finished its rows (0 = no gate; -1, the default: 50, and no gate when scans take two or three calls along, scan_pair >= 2 -- DESIGN.md 4.1 has both sweeps)
+    int scan_pair = 3;          // scan_overlap: a scan that starts behind a predecessor takes the queries of up to this many later calls of its stream (steps + 2, + 4, + 6) along in the same corpus pass (0..3; scan_kernels.hip scan_pair_kernel)
     int scan_pair_ring = 4096;  // scan_pair: slots of the descriptor ring in use (a power of two, 64 .. 4096): a call is found by the scan two steps earlier while the host is fewer calls ahead of the GPU than this (tests use 64 to see slots reused)
     int scan_pair_wait_us = 0;  // scan_pair, tests only: the deciding block waits this long (<= 5000) for the partner's descriptor
     int gemm_image = 1;         // 1: batched searches read the corpus' fp16 operand image when it has one (0: A/B only)
@@ -142,7 +142,7 @@ struct smt_ctx {
     uint64_t gate_prev_blocks = 0;           // ... and of the latest one
     uint64_t gate_prev_rows = 0;
     // scan_pair: the descriptor ring (pinned host memory, one slot per step) and the per-step decision records (device); the
-    // counters and the wait-ran-out flag live behind the gate counter, d_gate[1..4] (scan_kernels.hip PairParams::ctl)
+    // counters and the wait-ran-out flag live behind the gate counter, d_gate[1..7] (scan_kernels.hip PairParams::ctl)
     void *h_pair_ring = nullptr;
     void *d_pair_recs = nullptr;
     uint64_t pair_alone_host = 0;            // scan_pair calls that got the plain kernel: nothing queued in front of them, or profiled (smt_debug_scan_pairs counts them as alone)

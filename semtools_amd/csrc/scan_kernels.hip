@@ -38,7 +38,8 @@ struct ScanParams {
     uint32_t steal_lr;           // STEAL: log2 of the rounds per group
     uint32_t steal_static;       // STEAL: a block's first steal_static groups are dealt statically (group g of block b = g * blocks + b)
     // START GATE (tuning keys scan_overlap, scan_gate_pct; nullptr = none): consecutive one-query scans run on two streams and overlap.
-    // Every block adds 1 to *gate once its waves have finished their rows, and thread 0 of every block waits, before any row load,
+    // Every block adds 1 to *gate once its waves have finished their rows (a block of scan_pair_kernel: the number of calls its pass
+    // serves; an absorbed launch nothing: the counter counts calls served, in blocks), and thread 0 of every block waits, before any row load,
     // until *gate >= gate_open -- the predecessor scan has finished scan_gate_pct per cent of its blocks' rows -- or gate_ticks of the
     // 100 MHz wall clock have passed.  The counter only grows (the host keeps the running total), so a later launch reads as "open"
     // too.  Advisory: it orders no data (list buffers and selects meet in stream order), so it can cost time, never an answer.
@@ -282,8 +283,10 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
     // lists have filled) are read out and inserted.  Per chunk and query 15 + ~14 instructions instead of 4 x (11 + ~14): with the
     // row-at-a-time form the reductions made two queries cost 1.4 x and four 2.3 x one query's pass (instruction issue, not HBM).
     // VALID(j): wave-uniform, is row j of the chunk a real row.  SMT_QUERY_ON(n): does query n take part (scan_pair_kernel decides
-    // that while it runs; a constant here).
+    // that while it runs; a constant here).  SMT_QUERY_VEC(n): this lane's four components of query n -- registers here, an LDS
+    // image in scan_pair_kernel, whose register budget has no room for four queries.
 #define SMT_QUERY_ON(n) true
+#define SMT_QUERY_VEC(n) q[n]
 #define SMT_REDUCE_CHUNK4(cq, rq4, VALID)                                                                         \
     do {                                                                                                          \
         const int jj = lane & 3;                                                                                  \
@@ -297,8 +300,9 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
         _Pragma("unroll") for (int n = 0; n < NQ; ++n) {                                                          \
             if (!(SMT_QUERY_ON(n))) continue;                                                                     \
             float pa[4];                                                                                          \
+            const f32x4 qv = SMT_QUERY_VEC(n);                                                                    \
             _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                         \
-                pa[j] = (cq)[j].x * q[n].x + (cq)[j].y * q[n].y + (cq)[j].z * q[n].z + (cq)[j].w * q[n].w;        \
+                pa[j] = (cq)[j].x * qv.x + (cq)[j].y * qv.y + (cq)[j].z * qv.z + (cq)[j].w * qv.w;                \
             const float ab = wave_sum4(pa[0], pa[1], pa[2], pa[3], lane);                                         \
             const float d4 = dist_f32(ab, b2, rq[n], qz[n]);                                                      \
             const bool cand = valid_mine && (d4 < thr_d[n] || (d4 == thr_d[n] && r_mine < thr_r[n]));             \
@@ -460,6 +464,7 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
     }
 #undef SMT_REDUCE_ROW
 #undef SMT_QUERY_ON
+#undef SMT_QUERY_VEC
     // (SMT_REDUCE_CHUNK4 is used once more, by scan_pair_kernel below)
 
     if (p.stamps && lane == 0) p.stamps[wave_global * 2 + 1] = wall_clock64();
@@ -522,28 +527,38 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
     if (p.stamps && threadIdx.x == 0) p.stamps[(uint64_t)gridDim.x * waves_per_block * 2 + blockIdx.x] = wall_clock64();
 }
 
-// ------------------------------------------------------------- K2, paired (tuning key scan_pair)
+// ------------------------------------------------------------- K2, grouped (tuning key scan_pair)
 // Queued one-query scans of the scan_overlap pipeline share a corpus pass.  Every call still launches its scan and its select at
-// once; the scan of step i decides ON THE DEVICE, when it starts, whether it takes the query of step i + 2 -- the next call on its
-// own stream -- along: then it runs the two-query row loop and writes two list sets, its own and the partner's, and the scan of
-// step i + 2 finds itself ABSORBED and exits before its gate and before any row load.  The selects run where they always did, each
-// on its own list set with its own query, outputs and status word: the scan only nominates, so no answer changes.
+// once; the scan of step i decides ON THE DEVICE, when it starts, how many of the steps i + 2, i + 4, i + 6 -- the next calls on its
+// own stream -- it takes along: then it runs the row loop over up to four queries and writes up to four list sets, its own and the
+// others', and the scans of the steps it took find themselves ABSORBED and exit before their gate and before any row load.  The
+// selects run where they always did, each on its own list set with its own query, outputs and status word: the scan only
+// nominates, so no answer changes.
 //   host -> device: a ring of PairSlot in pinned host memory, indexed by step; the host fills slot i before it launches scan i and
 //     writes the step number last (release); the reader checks the number before and after the fields (a slot reused PAIR_RING
 //     steps later fails that check).
-//   block -> block: one PairRecord per step in device memory, state = step << 2 | code.  One block wins a CAS on it, decides, and
-//     publishes the record with an agent-scope release; the others wait for it with a bounded wait (PairParams::ctl[0] is raised
-//     when one runs out, and drain_async turns that into an error code).  The scan of step i + 2 reads record i, complete by
-//     stream order.
+//   block -> block: one PairRecord per step in device memory, state = step << 3 | code.  One block wins a CAS on it, decides, and
+//     publishes the record -- the group size and the (query, lists) of the calls taken -- with one agent-scope release; the others
+//     wait for it with a bounded wait (PairParams::ctl[0] is raised when one runs out, and drain_async turns that into an error
+//     code).
+//   leader -> absorbed: the deciding block MARKS the records of the steps it takes (state = that step << 3 | PAIR_ABSORBED) before
+//     it publishes its own, and a launch learns its fate from its OWN record, the one it reads anyway: marked, it exits; anything
+//     else, it leads.  The marks are complete by stream order: leader and absorbed launch are on one stream.  (The other way round,
+//     an absorbed step looking for its leader, needs the records of steps i - 2, i - 4 and i - 6.)  Record reuse: the record of
+//     step s is that of s - PAIR_RECS, a launch of the same stream that finished long ago, and is touched by the leader of s and
+//     by s alone; a mark for a step whose slot check failed is never written, so a cut descriptor ring (scan_pair_ring = 64, the
+//     host more than 64 calls ahead) only ends groups early.
+// The group is a PREFIX: a refused step i + 2 ends it, so the calls of a group are consecutive on their stream.
 // WHEN a launch looks is decided by the host: only a launch that queues up behind a predecessor on its internal stream
 // (hipStreamQuery at the call) runs this kernel at all -- a call made while the GPU keeps up, a launch bracketed by profiling events
 // and the one after it run scan_topk_kernel as before, so their latency and the profiled kernel time are the plain kernel's.  The
-// deciding block reads the slot before it waits at its gate, the others learn the decision after they have requested their first
+// deciding block reads the slots before it waits at its gate, the others learn the decision after they have requested their first
 // rows (the same rows either way): no row load starts later than in scan_topk_kernel.  (Looking only when the block had to wait
 // at its gate was measured too: 78.7 instead of 78.2 us per step, and under counter collection, which serialises kernels, nothing
 // pairs at all -- profiles/scan_pairing.json.)
 constexpr int PAIR_RING = 4096;   // slots: the host may run this many calls ahead of the GPU and still be found (256 KiB, pinned; tuning key scan_pair_ring uses fewer)
-constexpr int PAIR_RECS = 64;     // records: record i is read by the scan of step i + 2 only
+constexpr int PAIR_RECS = 64;     // records: record i is written by the leader of step i (a mark) and by step i, and read by step i
+constexpr int GROUP_MAX = 4;      // calls one corpus pass serves: the leader's and up to three taken along
 struct PairSlot {   // 64 bytes of pinned host memory
     unsigned long long step;        // written last
     unsigned long long corpus, n_virtual, query, lists;
@@ -551,107 +566,122 @@ struct PairSlot {   // 64 bytes of pinned host memory
     unsigned long long absorbable;
     unsigned long long pad;
 };
-struct PairRecord {
-    unsigned long long state;       // step << 2 | PAIR_DECIDING / PAIR_ALONE / PAIR_PAIRED (any other step: undecided)
-    unsigned long long query, lists;   // PAIR_PAIRED: the partner's
-    unsigned long long pad;
+struct PairRecord {   // 64 bytes
+    unsigned long long state;       // step << 3 | PAIR_DECIDING / PAIR_ALONE / PAIR_PAIRED / PAIR_ABSORBED (any other step: undecided)
+    unsigned long long taken;       // PAIR_PAIRED: calls taken along (1 .. GROUP_MAX - 1) ...
+    unsigned long long query[GROUP_MAX - 1], lists[GROUP_MAX - 1];   // ... and theirs
 };
 struct PairParams {
     const PairSlot *ring;
     PairRecord *recs;
-    unsigned long long *ctl;        // [0] a bounded wait ran out, [1] launches that paired, [2] ran alone, [3] were absorbed
-    unsigned int absorbable;        // this launch's own slot says so: only then can record step - 2 name it
+    unsigned long long *ctl;        // [0] a bounded wait ran out; launches that [1] took calls along, [2] ran alone, [3] were absorbed, [4..6] served 2, 3, 4 calls
+    unsigned int absorbable;        // this launch's own slot says so: only then can a leader have marked its record
+    unsigned int max_take;          // tuning key scan_pair: calls a launch may take along (1 .. GROUP_MAX - 1)
     unsigned long long wait_ticks;  // tuning key scan_pair_wait_us, in 10 ns ticks
     unsigned long long ring_mask;   // slots in use - 1 (tuning key scan_pair_ring)
 };
 enum : unsigned long long { PAIR_DECIDING = 1, PAIR_ALONE = 2, PAIR_PAIRED = 3, PAIR_ABSORBED = 4 };
+constexpr int PAIR_SHIFT = 3;
 
 __device__ __forceinline__ unsigned long long sys_load(const unsigned long long *f)
 {
     return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// The deciding block: the slot of step + 2 -> PAIR_PAIRED (query and lists filled in) or PAIR_ALONE.
-__device__ __forceinline__ unsigned long long pair_decide(const ScanParams &p, const PairParams &pp, unsigned long long &query,
-                                                          unsigned long long &lists)
+// The deciding block: the slots of step + 2, + 4, + 6 -> how many of them this launch takes along (their queries and list sets
+// go into the record), the longest prefix that passes.  scan_pair_wait_us bounds the waits for all of them together.
+__device__ __forceinline__ unsigned int pair_decide(const ScanParams &p, const PairParams &pp, PairRecord *rec)
 {
-    const PairSlot *s = pp.ring + ((p.step + 2) & pp.ring_mask);
-    const unsigned long long want = p.step + 2;
-    unsigned long long s1 = __hip_atomic_load(&s->step, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (s1 != want && pp.wait_ticks) {   // (tests: corpora that scan faster than the host issues calls)
-        const unsigned long long t0 = wall_clock64();
-        while (s1 != want && wall_clock64() - t0 < pp.wait_ticks) {
-            __builtin_amdgcn_s_sleep(32);
-            s1 = __hip_atomic_load(&s->step, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
+    const unsigned long long t0 = wall_clock64();
+    unsigned int taken = 0;
+    while (taken < pp.max_take) {
+        const unsigned long long want = p.step + 2ull * (taken + 1);
+        const PairSlot *s = pp.ring + (want & pp.ring_mask);
+        unsigned long long s1 = __hip_atomic_load(&s->step, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (s1 < want && pp.wait_ticks) {   // (tests: corpora that scan faster than the host issues calls; a LATER step's number: the slot was reused)
+            while (s1 < want && wall_clock64() - t0 < pp.wait_ticks) {
+                __builtin_amdgcn_s_sleep(32);
+                s1 = __hip_atomic_load(&s->step, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
         }
+        if (s1 != want) break;
+        const unsigned long long corpus = sys_load(&s->corpus), n_virtual = sys_load(&s->n_virtual), kp_blocks = sys_load(&s->kp_blocks);
+        const unsigned long long absorbable = sys_load(&s->absorbable);
+        const unsigned long long query = sys_load(&s->query), lists = sys_load(&s->lists);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+        if (sys_load(&s->step) != want) break;   // the host was rewriting the slot (a ring's length ahead)
+        const bool same = corpus == (unsigned long long)(uintptr_t)p.corpus && n_virtual == p.n_virtual &&
+                          kp_blocks == ((unsigned long long)p.kp | (unsigned long long)gridDim.x << 32);
+        if (!(absorbable && same)) break;
+        flag_store(&rec->query[taken], query);
+        flag_store(&rec->lists[taken], lists);
+        flag_store(&pp.recs[want % PAIR_RECS].state, (want << PAIR_SHIFT) | PAIR_ABSORBED);   // the mark
+        ++taken;
     }
-    if (s1 != want) return PAIR_ALONE;
-    const unsigned long long corpus = sys_load(&s->corpus), n_virtual = sys_load(&s->n_virtual), kp_blocks = sys_load(&s->kp_blocks);
-    const unsigned long long absorbable = sys_load(&s->absorbable);
-    query = sys_load(&s->query);
-    lists = sys_load(&s->lists);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-    if (sys_load(&s->step) != want) return PAIR_ALONE;   // the host was rewriting the slot (64 steps ahead)
-    const bool same = corpus == (unsigned long long)(uintptr_t)p.corpus && n_virtual == p.n_virtual &&
-                      kp_blocks == ((unsigned long long)p.kp | (unsigned long long)gridDim.x << 32);
-    return absorbable && same ? PAIR_PAIRED : PAIR_ALONE;
+    flag_store(&rec->taken, (unsigned long long)taken);
+    return taken;
 }
 
-// (8 waves per SIMD = 64 VGPRs: what the select needs beside it, 2 x 64 + 4 x 96 = 512.  The two row loops need 52 and 62; left to
-// itself the allocator spreads the two instantiations over 76.)
+// (8 waves per SIMD = 64 VGPRs: what the select needs beside it, 2 x 64 + 4 x 96 = 512.  The four-query row loop with its queries
+// in registers takes 81; with all four read from one LDS image per block and the norms held as wave-uniform values it fits.)
 template <bool NT>
 __global__ void __launch_bounds__(1024) scan_pair_kernel(ScanParams p, PairParams pp)
 {
     constexpr int U = 4;
+    constexpr int NQ = GROUP_MAX;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    key_t64 *s_keys = reinterpret_cast<key_t64 *>(smem_raw);  // [2][waves][64]: the launch is sized for a pair
+    key_t64 *s_keys = reinterpret_cast<key_t64 *>(smem_raw);  // [NQ][waves][64]: the launch is sized for a full group
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int waves_per_block = blockDim.x >> 6;
-    // (as in scan_topk_kernel: the chunk counter lives in the second query's key slots until the merge; so does the decision)
-    uint32_t *s_next = reinterpret_cast<uint32_t *>(s_keys + waves_per_block * 64);
-    unsigned long long *s_pair = reinterpret_cast<unsigned long long *>(s_next + 4);   // [0] absorbed?, [1] query, [2] lists, [3] record state as read, [4] code
+    unsigned int *s_valid = reinterpret_cast<unsigned int *>(s_keys + (size_t)NQ * waves_per_block * 64);   // [NQ][waves] (256 B)
+    f32x4 *s_q = reinterpret_cast<f32x4 *>(s_valid + 64);                                // [NQ][64]: the queries, one image per block
+    unsigned long long *s_pair = reinterpret_cast<unsigned long long *>(s_q + NQ * 64);   // [0] absorbed?, [1] calls served, [2] record state as read, [3..5] lists
+    unsigned long long *s_qptr = s_pair + 6;                                             // [3] queries taken along
+    uint32_t *s_next = reinterpret_cast<uint32_t *>(s_qptr + 3);                         // the block's next unclaimed chunk
     const int kp = (int)p.kp;
     PairRecord *rec = pp.recs + p.step % PAIR_RECS;
-    const unsigned long long tag = p.step << 2;
+    const unsigned long long tag = p.step << PAIR_SHIFT;
 
-    f32x4 q[2];
-    float rq[2];
-    bool qz[2];
-    {
-        q[0] = reinterpret_cast<const f32x4 *>(p.queries)[lane];
-        const float a2 = wave_sum(q[0].x * q[0].x + q[0].y * q[0].y + q[0].z * q[0].z + q[0].w * q[0].w);
-        qz[0] = (a2 == 0.0f);
-        rq[0] = qz[0] ? 0.0f : __frsqrt_rn(a2);
-    }
+    // (the norms are the same in every lane: held as wave-uniform values they cost no vector register)
+    float rq[NQ];
+    bool qz[NQ];
+#define SMT_LOAD_QUERY(n, ptr)                                                                                    \
+    do {                                                                                                          \
+        const f32x4 qn = reinterpret_cast<const f32x4 *>(ptr)[lane];                                              \
+        if (wave == 0) s_q[(n) * 64 + lane] = qn;                                                                 \
+        const float a2 = wave_sum(qn.x * qn.x + qn.y * qn.y + qn.z * qn.z + qn.w * qn.w);                         \
+        qz[n] = readlane_f(a2, 0) == 0.0f;                                                                        \
+        rq[n] = qz[n] ? 0.0f : readlane_f(__frsqrt_rn(a2), 0);                                                    \
+    } while (0)
+#pragma unroll
+    for (int n = 1; n < NQ; ++n) { rq[n] = 0.0f; qz[n] = true; }
+    SMT_LOAD_QUERY(0, p.queries);
 
     if (threadIdx.x == 0) {
         *s_next = (uint32_t)waves_per_block;
-        // three independent reads, one round trip (scan_topk_kernel reads its gate here)
+        // two independent reads, one round trip (scan_topk_kernel reads its gate here)
         const unsigned long long g = p.gate_open ? flag_load(p.gate) : 0ull;
-        const unsigned long long prev = pp.absorbable ? flag_load(&pp.recs[(p.step - 2) % PAIR_RECS].state) : 0ull;
         unsigned long long cur = flag_load(&rec->state);
         unsigned long long code = 0;
-        if (pp.absorbable && prev == (((p.step - 2) << 2) | PAIR_PAIRED)) {
-            code = PAIR_ABSORBED;
+        if (pp.absorbable && cur == (tag | PAIR_ABSORBED)) {
+            code = PAIR_ABSORBED;   // (marked by the leader, an earlier launch of this stream)
         } else {
-            // the first block to get here looks for a partner while the others wait at the gate
-            if ((cur >> 2) != p.step &&
+            // the first block to get here looks for calls to take along while the others wait at the gate
+            if ((cur >> PAIR_SHIFT) != p.step &&
                 __hip_atomic_compare_exchange_strong(&rec->state, &cur, tag | PAIR_DECIDING, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                                      __HIP_MEMORY_SCOPE_AGENT)) {
-                unsigned long long query = 0, lists = 0;
-                const unsigned long long d = pair_decide(p, pp, query, lists);
-                flag_store(&rec->query, query);
-                flag_store(&rec->lists, lists);
-                cur = tag | d;
+                const unsigned int taken = pair_decide(p, pp, rec);
+                cur = tag | (taken ? PAIR_PAIRED : PAIR_ALONE);
                 __hip_atomic_store(&rec->state, cur, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                (void)__hip_atomic_fetch_add(pp.ctl + (d == PAIR_PAIRED ? 1 : 2), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                (void)__hip_atomic_fetch_add(pp.ctl + (taken ? 1 : 2), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (taken) (void)__hip_atomic_fetch_add(pp.ctl + 3 + taken, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             if (g < p.gate_open) gate_wait(p);
         }
         s_pair[0] = code;
-        s_pair[3] = cur;
+        s_pair[2] = cur;
     }
     __syncthreads();
     if (uniform_u64(s_pair[0]) == PAIR_ABSORBED) {
@@ -689,7 +719,7 @@ __global__ void __launch_bounds__(1024) scan_pair_kernel(ScanParams p, PairParam
     }
 
     if (threadIdx.x == 0) {
-        unsigned long long cur = s_pair[3];   // (this step's: the block has won the CAS and decided, or lost it)
+        unsigned long long cur = s_pair[2];   // (this step's: the block has won the CAS and decided, or lost it)
         if (cur == (tag | PAIR_DECIDING)) {   // bounded like flag_wait: a decision that never comes ends in an error code
             const unsigned long long t0 = wall_clock64();
             while ((cur = flag_load(&rec->state)) == (tag | PAIR_DECIDING)) {
@@ -698,33 +728,36 @@ __global__ void __launch_bounds__(1024) scan_pair_kernel(ScanParams p, PairParam
                 if (wall_clock64() - t0 > 200000000ull) { flag_store(pp.ctl, 1ull); break; }
             }
         }
-        unsigned long long code = PAIR_ALONE;
+        unsigned long long served = 1;
         if (cur == (tag | PAIR_PAIRED)) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            s_pair[1] = flag_load(&rec->query);
-            s_pair[2] = flag_load(&rec->lists);
-            code = PAIR_PAIRED;
+            unsigned long long taken = flag_load(&rec->taken);
+            if (taken > (unsigned long long)(NQ - 1)) taken = NQ - 1;   // (never: the record is this step's)
+            for (unsigned long long j = 0; j < taken; ++j) {
+                s_qptr[j] = flag_load(&rec->query[j]);
+                s_pair[3 + j] = flag_load(&rec->lists[j]);
+            }
+            served = 1 + taken;
         } else if (cur != (tag | PAIR_ALONE)) {
             flag_store(pp.ctl, 1ull);   // (a wait that ran out, or a record that is not this step's: alone, and the context reports it)
         }
-        s_pair[4] = code;
+        s_pair[1] = served;
     }
     __syncthreads();
-    const bool paired = uniform_u64(s_pair[4]) == PAIR_PAIRED;   // (LDS reads: told to be wave-uniform)
-    key_t64 *lists2 = nullptr;
-    if (paired) {
-        lists2 = reinterpret_cast<key_t64 *>((uintptr_t)uniform_u64(s_pair[2]));
-        q[1] = reinterpret_cast<const f32x4 *>((uintptr_t)uniform_u64(s_pair[1]))[lane];
-        const float a2 = wave_sum(q[1].x * q[1].x + q[1].y * q[1].y + q[1].z * q[1].z + q[1].w * q[1].w);
-        qz[1] = (a2 == 0.0f);
-        rq[1] = qz[1] ? 0.0f : __frsqrt_rn(a2);
+    const int n_on = (int)(uint32_t)uniform_u64(s_pair[1]);   // calls this pass serves, 1 .. NQ (an LDS read: told to be wave-uniform)
+    if (n_on > 1) {   // (uniform over the block)
+#pragma unroll
+        for (int n = 1; n < NQ; ++n)
+            if (n < n_on) SMT_LOAD_QUERY(n, (uintptr_t)uniform_u64(s_qptr[n - 1]));
+        __syncthreads();   // the images are wave 0's stores
     }
+#undef SMT_LOAD_QUERY
 
-    // the row loop and the block merge of scan_topk_kernel<2, 4, NT, false>, the second query's share of both skipped by a launch
-    // that runs alone.  (ONE loop: two instantiations behind a branch share the first rows' registers, and the allocator then takes
-    // 76 VGPRs where each loop alone takes 53 / 63 -- the select needs this kernel at 64 or fewer beside it.)
-    constexpr int NQ = 2;
-#define SMT_QUERY_ON(n) ((n) == 0 || paired)
+    // the row loop and the block merge of scan_topk_kernel<4, 4, NT, false>, the share of the queries that are not there skipped.
+    // (ONE loop: instantiations behind a branch share the first rows' registers, and the allocator then takes more than either
+    // alone -- the select needs this kernel at 64 VGPRs or fewer beside it.)
+#define SMT_QUERY_ON(n) ((n) < n_on)
+#define SMT_QUERY_VEC(n) s_q[(n) * 64 + lane]
     float ld[NQ];
     uint32_t lr[NQ];
     float thr_d[NQ];
@@ -750,9 +783,8 @@ __global__ void __launch_bounds__(1024) scan_pair_kernel(ScanParams p, PairParam
         v0n = v0nn;
     }
     __syncthreads();
-    // a paired block counts for its partner's block too: the host's running totals count every launch
-    if (threadIdx.x == 0) (void)__hip_atomic_fetch_add(p.gate, paired ? 2ull : 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned int *s_valid = reinterpret_cast<unsigned int *>(s_keys + (size_t)NQ * waves_per_block * 64);   // [NQ][waves]
+    // a leader's block counts for the blocks of the calls it serves: the host's running totals count every launch
+    if (threadIdx.x == 0) (void)__hip_atomic_fetch_add(p.gate, (unsigned long long)n_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
         if (!(SMT_QUERY_ON(n))) break;
@@ -766,7 +798,7 @@ __global__ void __launch_bounds__(1024) scan_pair_kernel(ScanParams p, PairParam
     for (int n = 0; n < NQ; ++n) {
         if (!(SMT_QUERY_ON(n))) break;
         const key_t64 *keys_n = s_keys + (size_t)n * waves_per_block * 64;
-        key_t64 *out = (n == 0 ? p.block_lists : lists2) + (size_t)blockIdx.x * kp;
+        key_t64 *out = (n == 0 ? p.block_lists : reinterpret_cast<key_t64 *>((uintptr_t)uniform_u64(s_pair[2 + n]))) + (size_t)blockIdx.x * kp;
         const key_t64 mine = keys_n[wave * 64 + lane];
         if (mine != KEY_PAD) {
             int rank = 0;
@@ -781,8 +813,14 @@ __global__ void __launch_bounds__(1024) scan_pair_kernel(ScanParams p, PairParam
         }
     }
 #undef SMT_QUERY_ON
+#undef SMT_QUERY_VEC
 }
 #undef SMT_REDUCE_CHUNK4
+// dynamic LDS of a scan_pair_kernel launch: the four key regions, the waves' key counts, the query images, the block's control words
+static inline size_t pair_smem_bytes(int threads)
+{
+    return (size_t)GROUP_MAX * (threads / 64) * 64 * sizeof(key_t64) + 256 + (size_t)GROUP_MAX * 1024 + 9 * 8 + 16;
+}
 
 // --------------------------------------------------- exact f64 distance (A5): device_utils.h exact_distance
 __global__ void rescore_rows_kernel(const float *corpus, const float *query, const uint32_t *rows,
@@ -1470,7 +1508,8 @@ static int launch_scan_pair(smt_ctx *ctx, const ScanParams &p, PairParams pp, in
     pp.recs = reinterpret_cast<PairRecord *>(ctx->d_pair_recs);
     pp.ctl = ctx->d_gate + 1;
     pp.wait_ticks = (unsigned long long)ctx->tune.scan_pair_wait_us * 100ull;
-    const size_t smem = (size_t)2 * (threads / 64) * 64 * sizeof(key_t64) + 16 + 64 + 256;   // launch_scan_variant<2, 4>'s
+    pp.max_take = (unsigned int)std::min(std::max(ctx->tune.scan_pair, 1), GROUP_MAX - 1);
+    const size_t smem = pair_smem_bytes(threads);
     if (nt) hipLaunchKernelGGL(scan_pair_kernel<true>, dim3(blocks), dim3(threads), smem, st, p, pp);
     else hipLaunchKernelGGL(scan_pair_kernel<false>, dim3(blocks), dim3(threads), smem, st, p, pp);
     SMT_HIP_CHECK(hipGetLastError());
@@ -1580,9 +1619,12 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
     const size_t list_bytes = overlap ? (size_t)SEL_MAX_LISTS * 64 * sizeof(key_t64)
                                       : (((size_t)a.nq * blocks * kp * sizeof(key_t64)) + 255) & ~(size_t)255;
     const size_t table_bytes = filtered ? (size_t)n_chunks * sizeof(uint64_t) : 0;
-    // (scan_overlap: a ring of four sets -- a paired scan of step i fills the set of step i + 2 as well, on the same stream, while
-    // the select of step i - 2, which read that set's predecessor in a ring of two, is behind it in stream order only with four)
-    const size_t n_sets = overlap ? 4 : 2;
+    // (scan_overlap: a ring of eight sets, step & 7.  A leading scan of step i fills the sets of steps i, i + 2, i + 4 and i + 6, all
+    // on its own stream, and set s is shared by the steps s, s +- 8, s +- 16 ...: the last readers of the four sets it writes are the
+    // selects of steps i - 8, i - 6, i - 4 and i - 2, launched on the SAME stream before scan i, so stream order alone has them
+    // finished.  The other stream's steps have the other parity and the other four sets.  With fewer sets the scan of step i
+    // would write the set of step i + 6 into one that a select of the other stream, ordered against nothing here, may be reading.)
+    const size_t n_sets = overlap ? 8 : 2;
     rc = ensure_scratch(ctx, n_sets * list_bytes + table_bytes);
     if (rc != SMT_OK) return rc;
     key_t64 *lists = reinterpret_cast<key_t64 *>(reinterpret_cast<char *>(ctx->d_scratch) + (step & (n_sets - 1)) * list_bytes);
@@ -1622,8 +1664,16 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
         // (a timed launch and its successor neither absorb nor get absorbed: the events keep bracketing a one-query pass)
         if (timed || ctx->ov_after_timed) { may_pair = false; pp.absorbable = 0; }
         ctx->ov_after_timed = timed;
-        if (ctx->tune.scan_gate_pct > 0 && ctx->gate_prev_blocks > 0) {
-            gate_open = ctx->gate_total - ctx->gate_prev_blocks + (ctx->gate_prev_blocks * (uint64_t)ctx->tune.scan_gate_pct + 99) / 100;
+        // What the gate counts is CALLS served, in blocks: a plain launch's block adds 1 when its rows are done, a leader's block the
+        // number of calls its pass serves, an absorbed launch nothing, and gate_total below counts one grid per call.  So "gate_pct of
+        // the predecessor" is: every call before the predecessor call is served, and gate_pct per cent of the predecessor call's
+        // grid.  When that call is the m-th of n that one pass serves, the point lies at (m - 1 + gate_pct / 100) / n of the pass'
+        // blocks: 75 % of a pair's pass and 87.5 % of a full group's at gate_pct = 50, while a leader still at its gate holds
+        // successors back only until their bound.  The default by the sweeps: 50 for plain and paired launches, and
+        // no gate where launches may take two or three calls along (there every gated setting measured 4 us per step behind).
+        const int gate_pct = ctx->tune.scan_gate_pct >= 0 ? ctx->tune.scan_gate_pct : (pair && ctx->tune.scan_pair >= 2) ? 0 : 50;
+        if (gate_pct > 0 && ctx->gate_prev_blocks > 0) {
+            gate_open = ctx->gate_total - ctx->gate_prev_blocks + (ctx->gate_prev_blocks * (uint64_t)gate_pct + 99) / 100;
             // the bound: the predecessor's rows at 4 TB/s (half the part's HBM rate; 1 KiB rows, 10 ns ticks) + 20 us, at most 0.5 ms (a
             // grid that cannot be resident twice -- scan_blocks / scan_threads -- may hold back predecessor blocks while it waits)
             gate_ticks = std::min<uint64_t>(ctx->gate_prev_rows / 39 + 2000, 50000);

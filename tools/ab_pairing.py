@@ -1,8 +1,9 @@
-"""A/B of paired one-query scans (tuning key scan_pair; scan_gate_pct swept in pair mode) in ONE process on one box, settings
-alternated: the wall time per pipelined step (async select, scan_overlap, no events) over two 1 M-row corpora used in turn (as
-bench.py) and over one corpus alone, how many launches paired (smt_debug_scan_pairs), and the answers and status words compared
-with scan_pair = 0.  "sync": one call, synchronise, repeat -- the latency of a call when the GPU is not behind, where nothing can
-pair and the pair-capable kernel must cost what the plain one does.  python tools/ab_pairing.py [rows] [rounds] [out.json]"""
+"""A/B of grouped one-query scans (tuning key scan_pair = 0 / 1 / 2 / 3 later calls taken along; scan_gate_pct swept in group mode)
+in ONE process on one box, settings alternated: the wall time per pipelined step (async select, scan_overlap, no events) over two
+1 M-row corpora used in turn (as bench.py) and over one corpus alone, how many launches took calls along (smt_debug_scan_pairs) and
+how many calls each launch served (smt_debug_scan_groups), and the answers and status words compared with scan_pair = 0.  "sync":
+one call, synchronise, repeat -- the latency of a call when the GPU is not behind, where nothing can be taken along and the
+group-capable kernel must cost what the plain one does.  python tools/ab_pairing.py [rows] [rounds] [out.json]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -28,8 +29,9 @@ def run(n, corpora, sync_each=False):
     ctx.synchronize()
 ctx.set_tuning("prof_select", 0)
 ctx.set_tuning("async_select", 1)
-settings = [(0, 50, 0), (1, 50, 0), (1, 0, 0), (1, 65, 0), (1, 75, 0), (1, 90, 0), (1, 100, 0)]   # (scan_pair, scan_gate_pct, scan_pair_wait_us)
-loads = {"two_corpora": (both, False, settings), "one_corpus": (both[:1], False, settings), "sync": (both, True, settings[:2])}
+# (scan_pair, scan_gate_pct, scan_pair_wait_us): the four group limits at the shipped gate, then the gate swept at the limit of three
+settings = [(0, 50, 0), (1, 50, 0), (2, 50, 0), (3, 50, 0), (3, 0, 0), (2, 0, 0), (3, 5, 0), (3, 10, 0), (3, 25, 0), (3, 65, 0), (3, 75, 0), (3, 90, 0), (3, 100, 0), (1, 75, 0)]
+loads = {"two_corpora": (both, False, settings), "one_corpus": (both[:1], False, settings), "sync": (both, True, settings[:4])}
 res, ref = {}, {}
 for r in range(rounds):
     for load, (corpora, sync_each, todo) in loads.items():
@@ -39,20 +41,22 @@ for r in range(rounds):
             ctx.set_tuning("scan_pair_wait_us", wait_us)
             run(300, corpora, sync_each)
             st.fill_(7)
-            c0 = ctx.scan_pairs()
+            c0, g0 = ctx.scan_pairs(), ctx.scan_groups()
             t0 = time.perf_counter(); run(2000, corpora, sync_each); step = (time.perf_counter() - t0) / 2000 * 1e6
-            c1 = ctx.scan_pairs()
+            c1, g1 = ctx.scan_pairs(), ctx.scan_groups()
             ans = out.cpu().numpy().copy()
             ref.setdefault(load, ans)
             same = bool((ans == ref[load]).all()) and bool((st[:2000].cpu() == 0).all())
-            key = f"{load}/" + ("off" if pair == 0 else f"pair_gate{gate}")
+            key = f"{load}/" + ("off" if pair == 0 else f"take{pair}_gate{gate}")
             res.setdefault(key, []).append({"step_us": round(step, 2), "paired": c1[0] - c0[0], "alone": c1[1] - c0[1],
-                                            "absorbed": c1[2] - c0[2], "answers_and_status_match": same})
+                                            "absorbed": c1[2] - c0[2], "launches_by_calls_served": [b - a for a, b in zip(g0, g1)],
+                                            "answers_and_status_match": same})
             print(json.dumps({"round": r, "setting": key, **res[key][-1]}), file=sys.stderr, flush=True)
-ctx.set_tuning("scan_gate_pct", 50)
+ctx.set_tuning("scan_gate_pct", -1)
 ctx.set_tuning("scan_pair_wait_us", 0)
 summary = {k: {"median_step_us": sorted(x["step_us"] for x in v)[len(v) // 2], "min": min(x["step_us"] for x in v),
                "max": max(x["step_us"] for x in v), "paired_of_2000": [x["paired"] for x in v],
+               "launches_by_calls_served": [x["launches_by_calls_served"] for x in v],
                "all_match": all(x["answers_and_status_match"] for x in v)} for k, v in res.items()}
 report = json.dumps({"rows": rows, "rounds": rounds, "summary": summary, "by_setting": res}, indent=1)
 if len(sys.argv) > 3:
