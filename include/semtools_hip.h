@@ -341,7 +341,8 @@ int smt_ivfpq_build(smt_corpus *corpus, const smt_ivfpq_params *params, smt_ivfp
 void smt_ivfpq_destroy(smt_ivfpq *index);
 /* nprobe lists scanned per query; in every probed list UP TO `rerank` ADC candidates
  * (0 = 512; range [4, 512]) are re-scored against the full-precision rows inside the scan
- * kernel, and the best top_k + 8 of all lists get the exact f64 distance.  top_k <= 56.
+ * kernel, and the best top_k + 8 of all lists get the exact f64 distance.  top_k <= 56
+ * (smt_ivfpq_search_wide below takes up to 1024).
  * `rerank` is a budget, not a count: the codes of a list (of each 8192-code segment of a long
  * list) are dealt to the 4 or 8 waves of a block in groups of 64 (8 waves above a budget of 256;
  * when nprobe leaves a long list fewer segments than it wants, the budget per segment grows by the
@@ -379,6 +380,27 @@ int smt_ivfpq_search_ranges(smt_ivfpq *index, const float *queries, uint32_t nq,
 int smt_ivfpq_search_ranges_device(smt_ivfpq *index, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe,
                                    uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, uint64_t row_base,
                                    uint64_t *out_rows_dev, double *out_dist_dev);
+/* WIDE searches: 1 <= top_k <= 1024 (the host form also takes 0), with or without ranges in one entry point.  ranges == NULL is the
+ * unfiltered search; a non-NULL `ranges` is a filter even with n_ranges == 0 (an empty filter: every answer is empty); the rules for
+ * the ranges themselves are those of smt_ivfpq_search_ranges.  top_k <= 56 is forwarded to the narrow route above and returns the
+ * same bytes.  For 57 <= top_k <= 1024 the answer is DEFINED as follows.  Let C(q) be the rows that the scan re-scores in f32 for
+ * query q: the same set the narrow route draws from, for the same nprobe, rerank and list segments (every guarantee stated for
+ * smt_ivfpq_search / _ranges about which rows are re-scored holds unchanged).  Let S be the kg = min(|C|, top_k + max(64, top_k / 16))
+ * rows of C with the smallest (f32 re-scored distance, row) keys.  The answer is the top_k best rows of S by (exact f64 distance,
+ * row), with their exact distances; when C holds fewer than top_k rows the answer is shorter.  Counts and padding as in
+ * smt_ivfpq_search.  In particular, where every list segment is re-scored entirely (lists of at most 512 rows at rerank = 512) the
+ * answer is the exact top_k over the rows of the probed lists (tests/test_gpu_ivf_wide.py).
+ * How: the scan writes every re-scored row of a query into a candidate pool in the context's scratch -- nprobe x segments x 256 or
+ * 512 keys, at most 2 MiB per query -- and one block per query selects S from it (radix select on the 64-bit keys: deterministic,
+ * ties by row) and finishes exactly.  A batch whose pool would pass 256 MiB runs in rounds of queries.
+ * The host form waits for its answer.  The device form is enqueued on the context's stream and does not wait, except when the
+ * context's scratch has to grow (and, inside ranges, as smt_ivfpq_search_ranges_device does). */
+int smt_ivfpq_search_wide(smt_ivfpq *index, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe,
+                          uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, uint64_t row_base,
+                          uint64_t *out_rows, double *out_dist, uint64_t *out_counts, uint64_t out_cap);
+int smt_ivfpq_search_wide_device(smt_ivfpq *index, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe,
+                                 uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, uint64_t row_base,
+                                 uint64_t *out_rows_dev, double *out_dist_dev);
 /* build_ms4 = {coarse k-means, assign all rows, PQ training, sort + encode} */
 int smt_ivfpq_info(const smt_ivfpq *index, uint64_t *n_rows, uint32_t *nlist, uint64_t *index_bytes,
                    double *build_ms4);
@@ -595,7 +617,7 @@ int smt_sharded_search_topk_device_ex(smt_sharded_corpus *corpus, const float *c
  * ranks end with the SAME nlist centroids -- "nlist lists over the whole corpus", each list spread over the shards --
  * while quantisers and codes are fitted locally.  shared_centroids == 0: independent per-shard indexes (own centroids,
  * no collective in the build).  Search: per-shard smt_ivfpq_search with global rows -> the same all-gather + merge as
- * smt_sharded_search.  Exact distances, approximate membership; top_k <= 56. */
+ * smt_sharded_search.  Exact distances, approximate membership; top_k <= 56 (smt_sharded_ivfpq_search_wide: up to 1024). */
 typedef struct smt_sharded_ivfpq smt_sharded_ivfpq;
 int smt_sharded_ivfpq_build(smt_sharded_corpus *corpus, const smt_ivfpq_params *params, int shared_centroids,
                             smt_sharded_ivfpq **out);
@@ -608,6 +630,13 @@ int smt_sharded_ivfpq_search(smt_sharded_ivfpq *index, const float *queries, uin
 int smt_sharded_ivfpq_search_ranges(smt_sharded_ivfpq *index, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe,
                                     uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, uint64_t *out_rows,
                                     double *out_dist, uint64_t *out_counts, uint64_t out_cap);
+/* The wide form over a sharded corpus: 1 <= top_k <= 1024 and n_ranks x top_k <= 8192, GLOBAL ranges or NULL, with the meaning of
+ * NULL / n_ranges == 0 of smt_ivfpq_search_wide.  Every rank answers as smt_ivfpq_search_wide defines it for its own rows (for
+ * top_k <= 56: the narrow route), and the ranks' lists of top_k are merged by (exact distance, global row) through the exchange of
+ * smt_sharded_search_topk_device_ex, on either transport.  Every argument is checked before anything is enqueued. */
+int smt_sharded_ivfpq_search_wide(smt_sharded_ivfpq *index, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe,
+                                  uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, uint64_t *out_rows,
+                                  double *out_dist, uint64_t *out_counts, uint64_t out_cap);
 /* Life cycle, shard by shard (smt_ivfpq_save / _load / _append / _info on every local rank).  A one-rank group uses `path`
  * itself; otherwise rank r's part is `<path>.r<r>of<n_ranks>` -- the files name LOCAL rows by position, so they are valid
  * for the layout they were built on (persist it with smt_sharded_corpus_layout, restore it with _load_layout).

@@ -341,6 +341,34 @@ extern "C" {
         out_rows_dev: *mut u64,
         out_dist_dev: *mut f64,
     ) -> c_int;
+    pub fn smt_ivfpq_search_wide(
+        index: *mut SmtIvfpq,
+        queries: *const f32,
+        nq: u32,
+        top_k: u32,
+        nprobe: u32,
+        rerank: u32,
+        ranges: *const SmtRange,
+        n_ranges: u32,
+        row_base: u64,
+        out_rows: *mut u64,
+        out_dist: *mut f64,
+        out_counts: *mut u64,
+        out_cap: u64,
+    ) -> c_int;
+    pub fn smt_ivfpq_search_wide_device(
+        index: *mut SmtIvfpq,
+        queries_dev: *const f32,
+        nq: u32,
+        top_k: u32,
+        nprobe: u32,
+        rerank: u32,
+        ranges: *const SmtRange,
+        n_ranges: u32,
+        row_base: u64,
+        out_rows_dev: *mut u64,
+        out_dist_dev: *mut f64,
+    ) -> c_int;
     pub fn smt_ivfpq_info(
         index: *const SmtIvfpq,
         n_rows: *mut u64,
@@ -616,6 +644,20 @@ extern "C" {
         out_counts: *mut u64,
         out_cap: u64,
     ) -> c_int;
+    pub fn smt_sharded_ivfpq_search_wide(
+        index: *mut SmtShardedIvfpq,
+        queries: *const f32,
+        nq: u32,
+        top_k: u32,
+        nprobe: u32,
+        rerank: u32,
+        ranges: *const SmtRange,
+        n_ranges: u32,
+        out_rows: *mut u64,
+        out_dist: *mut f64,
+        out_counts: *mut u64,
+        out_cap: u64,
+    ) -> c_int;
     pub fn smt_sharded_ivfpq_save(index: *mut SmtShardedIvfpq, path: *const c_char) -> c_int;
     pub fn smt_sharded_ivfpq_load(
         corpus: *mut SmtShardedCorpus,
@@ -638,7 +680,12 @@ extern "C" {
     ) -> c_int;
     pub fn smt_ctx_uncertain_count(ctx: *mut SmtCtx, count: *mut u64, reset: c_int) -> c_int;
     pub fn smt_debug_range_sets(corpus: *const SmtCorpus, kept: *mut u64, hits: *mut u64, builds: *mut u64) -> c_int;
-    pub fn smt_debug_image_tile(corpus: *mut SmtCorpus, tile: u64, out_tile_host: *mut c_void, out_zero_mask: *mut u32) -> c_int;
+    pub fn smt_debug_image_tile(
+        corpus: *mut SmtCorpus,
+        tile: u64,
+        out_tile_host: *mut c_void,
+        out_zero_mask: *mut u32,
+    ) -> c_int;
     pub fn smt_debug_deliveries(ctx: *mut SmtCtx, count: *mut u64) -> c_int;
     pub fn smt_debug_scan_pairs(ctx: *mut SmtCtx, paired: *mut u64, alone: *mut u64, absorbed: *mut u64) -> c_int;
     pub fn smt_debug_scan_groups(ctx: *mut SmtCtx, by_size: *mut u64) -> c_int;

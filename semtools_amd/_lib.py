@@ -25,7 +25,7 @@ EXPORTS = [
     "smt_corpus_write_rows", "smt_corpus_read_rows", "smt_corpus_truncate", "smt_corpus_rows", "smt_corpus_dim",
     "smt_corpus_prepack", "smt_corpus_image_bytes",
     "smt_corpus_save", "smt_corpus_load", "smt_corpus_append_to_file", "smt_search", "smt_search_topk_device", "smt_merge_topk",
-    "smt_merge_topk_device", "smt_merge_topk_packed_device", "smt_ivfpq_build", "smt_ivfpq_destroy", "smt_ivfpq_search", "smt_ivfpq_search_device", "smt_ivfpq_search_ranges", "smt_ivfpq_search_ranges_device", "smt_ivfpq_info", "smt_ivfpq_list_sizes", "smt_ivfpq_save", "smt_ivfpq_load", "smt_ivfpq_append", "smt_ivfpq_compact", "smt_sharded_ivfpq_compact",
+    "smt_merge_topk_device", "smt_merge_topk_packed_device", "smt_ivfpq_build", "smt_ivfpq_destroy", "smt_ivfpq_search", "smt_ivfpq_search_device", "smt_ivfpq_search_ranges", "smt_ivfpq_search_ranges_device", "smt_ivfpq_search_wide", "smt_ivfpq_search_wide_device", "smt_ivfpq_info", "smt_ivfpq_list_sizes", "smt_ivfpq_save", "smt_ivfpq_load", "smt_ivfpq_append", "smt_ivfpq_compact", "smt_sharded_ivfpq_compact",
     "smt_set_tuning", "smt_fnv1a_hash", "smt_line_embedding_id", "smt_doc_meta_id",
     "smt_ctx_uncertain_count", "smt_debug_batched_scores",
     "smt_init", "smt_shutdown", "smt_default_group", "smt_group_create", "smt_group_create_logical", "smt_group_unique_id", "smt_group_create_rank",
@@ -33,7 +33,7 @@ EXPORTS = [
     "smt_sharded_corpus_from_host", "smt_sharded_corpus_from_device", "smt_sharded_corpus_load", "smt_sharded_corpus_save",
     "smt_sharded_corpus_destroy", "smt_sharded_corpus_rows", "smt_sharded_corpus_rank_rows", "smt_sharded_corpus_shard",
     "smt_sharded_corpus_append_host", "smt_sharded_search", "smt_sharded_search_topk_device",
-    "smt_sharded_ivfpq_build", "smt_sharded_ivfpq_destroy", "smt_sharded_ivfpq_shard", "smt_sharded_ivfpq_search", "smt_sharded_ivfpq_search_ranges",
+    "smt_sharded_ivfpq_build", "smt_sharded_ivfpq_destroy", "smt_sharded_ivfpq_shard", "smt_sharded_ivfpq_search", "smt_sharded_ivfpq_search_ranges", "smt_sharded_ivfpq_search_wide",
     "smt_group_from_ctx", "smt_sharded_corpus_create", "smt_sharded_corpus_load_layout", "smt_sharded_corpus_layout",
     "smt_sharded_corpus_append_to_file", "smt_sharded_corpus_read_rows", "smt_sharded_corpus_write_rows",
     "smt_sharded_model_create", "smt_sharded_model_create_from_file", "smt_sharded_model_destroy", "smt_sharded_embed",
@@ -216,6 +216,8 @@ def lib():
     L.smt_ivfpq_search_device.argtypes = [vp, vp, u32, u32, u32, u32, u64, vp, vp]
     L.smt_ivfpq_search_ranges.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, u64, vp, vp, vp, u64]
     L.smt_ivfpq_search_ranges_device.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, u64, vp, vp]
+    L.smt_ivfpq_search_wide.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, u64, vp, vp, vp, u64]
+    L.smt_ivfpq_search_wide_device.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, u64, vp, vp]
     L.smt_ivfpq_info.argtypes = [vp, P(u64), P(u32), P(u64), P(f64)]
     L.smt_ivfpq_list_sizes.argtypes = [vp, vp]
     L.smt_ivfpq_append.argtypes = [vp, P(u64)]
@@ -281,6 +283,7 @@ def lib():
     L.smt_sharded_ivfpq_shard.restype = vp
     L.smt_sharded_ivfpq_search.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp, u64]
     L.smt_sharded_ivfpq_search_ranges.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, vp, vp, vp, u64]
+    L.smt_sharded_ivfpq_search_wide.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, vp, vp, vp, u64]
     L.smt_group_from_ctx.argtypes = [vp, P(vp)]
     L.smt_sharded_corpus_create.argtypes = [vp, u32, P(vp)]
     L.smt_sharded_corpus_load_layout.argtypes = [vp, C.c_char_p, vp, vp, u64, P(vp)]

@@ -433,16 +433,23 @@ class IvfPq:
         L.check(L.lib().smt_ivfpq_list_sizes(self._h, L.np_ptr(out)))
         return out
 
-    def search(self, queries, top_k=10, nprobe=32, rerank=0, row_base=0, ranges=None):
+    def search(self, queries, top_k=10, nprobe=32, rerank=0, row_base=0, ranges=None, wide=False):
         """ranges: search inside these corpus rows only (smt_ivfpq_search_ranges: [(begin, end)] sorted and disjoint, or a
-        PackedRanges; an empty list is the unfiltered search); None calls smt_ivfpq_search."""
+        PackedRanges; an empty list is the unfiltered search); None calls smt_ivfpq_search.
+        wide: through smt_ivfpq_search_wide, which takes top_k up to 1024 (top_k <= 56: the same bytes as without it); there an
+        empty list of ranges is an empty filter, and the answer is empty."""
         q = _f32c(queries).reshape(-1, L.DIM)
         nq = q.shape[0]
         cap = max(int(top_k), 1)
         out_rows = np.empty((nq, cap), dtype=np.uint64)
         out_dist = np.empty((nq, cap), dtype=np.float64)
         counts = np.zeros(nq, dtype=np.uint64)
-        if ranges is None:
+        if wide:
+            rng, n_rng = _ranges_arg(ranges)
+            L.check(L.lib().smt_ivfpq_search_wide(self._h, L.np_ptr(q), nq, int(top_k), int(nprobe), int(rerank),
+                                                  C.cast(rng, C.c_void_p) if rng is not None else None, n_rng, int(row_base),
+                                                  L.np_ptr(out_rows), L.np_ptr(out_dist), L.np_ptr(counts), cap))
+        elif ranges is None:
             L.check(L.lib().smt_ivfpq_search(self._h, L.np_ptr(q), nq, int(top_k), int(nprobe), int(rerank), int(row_base),
                                              L.np_ptr(out_rows), L.np_ptr(out_dist), L.np_ptr(counts), cap))
         else:
@@ -452,9 +459,15 @@ class IvfPq:
                                                     L.np_ptr(out_rows), L.np_ptr(out_dist), L.np_ptr(counts), cap))
         return [(out_rows[i, :int(counts[i])].copy(), out_dist[i, :int(counts[i])].copy()) for i in range(nq)]
 
-    def search_device(self, queries_ptr, nq, top_k, nprobe, rerank, row_base, out_rows_ptr, out_dist_ptr, ranges=None):
+    def search_device(self, queries_ptr, nq, top_k, nprobe, rerank, row_base, out_rows_ptr, out_dist_ptr, ranges=None, wide=False):
         """Device-resident form (raw pointers; asynchronous on the context's stream).  ranges (host side, as in search): inside
-        these rows only, through smt_ivfpq_search_ranges_device."""
+        these rows only, through smt_ivfpq_search_ranges_device.  wide: smt_ivfpq_search_wide_device (top_k up to 1024)."""
+        if wide:
+            rng, n_rng = _ranges_arg(ranges)
+            L.check(L.lib().smt_ivfpq_search_wide_device(self._h, C.c_void_p(queries_ptr), int(nq), int(top_k), int(nprobe), int(rerank),
+                                                         C.cast(rng, C.c_void_p) if rng is not None else None, n_rng, int(row_base),
+                                                         C.c_void_p(out_rows_ptr), C.c_void_p(out_dist_ptr)))
+            return
         if ranges is None:
             L.check(L.lib().smt_ivfpq_search_device(self._h, C.c_void_p(queries_ptr), int(nq), int(top_k), int(nprobe), int(rerank),
                                                     int(row_base), C.c_void_p(out_rows_ptr), C.c_void_p(out_dist_ptr)))
@@ -828,15 +841,21 @@ class ShardedIvfPq:
         L.check(L.lib().smt_ivfpq_list_sizes(C.c_void_p(h), L.np_ptr(out)))
         return out
 
-    def search(self, queries, top_k=10, nprobe=16, rerank=128, ranges=None):
-        """ranges: GLOBAL rows to search inside (smt_sharded_ivfpq_search_ranges); None calls smt_sharded_ivfpq_search."""
+    def search(self, queries, top_k=10, nprobe=16, rerank=128, ranges=None, wide=False):
+        """ranges: GLOBAL rows to search inside (smt_sharded_ivfpq_search_ranges); None calls smt_sharded_ivfpq_search.
+        wide: smt_sharded_ivfpq_search_wide (top_k up to 1024 with n_ranks x top_k <= 8192; an empty list of ranges is an empty filter)."""
         q = _f32c(queries).reshape(-1, L.DIM)
         nq = q.shape[0]
         cap = max(int(top_k), 1)
         out_rows = np.empty((nq, cap), dtype=np.uint64)
         out_dist = np.empty((nq, cap), dtype=np.float64)
         counts = np.zeros(nq, dtype=np.uint64)
-        if ranges is None:
+        if wide:
+            rng, n_rng = _ranges_arg(ranges)
+            L.check(L.lib().smt_sharded_ivfpq_search_wide(self._h, L.np_ptr(q), nq, int(top_k), int(nprobe), int(rerank),
+                                                          C.cast(rng, C.c_void_p) if rng is not None else None, n_rng,
+                                                          L.np_ptr(out_rows), L.np_ptr(out_dist), L.np_ptr(counts), cap))
+        elif ranges is None:
             L.check(L.lib().smt_sharded_ivfpq_search(self._h, L.np_ptr(q), nq, int(top_k), int(nprobe), int(rerank),
                                                      L.np_ptr(out_rows), L.np_ptr(out_dist), L.np_ptr(counts), cap))
         else:

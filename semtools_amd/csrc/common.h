@@ -524,7 +524,8 @@ struct smt_ivfpq_params;
 namespace smt {
 int ivfpq_build_shared(smt_corpus *corpus, const smt_ivfpq_params *prm, const IvfBuildShare *share, smt_ivfpq **out);
 int ivfpq_search_packed(smt_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
-                        const smt_range *ranges_local, uint32_t n_ranges, bool filtered, uint64_t row_base, uint64_t *packed_dev);
+                        const smt_range *ranges_local, uint32_t n_ranges, bool filtered, uint64_t row_base, uint64_t *packed_dev,
+                        bool wide = false);   // wide: 57 <= top_k <= LARGEK_MAX_K through the candidate pool
 
 // domain.hip: the numeric domain of rows and queries (finite, largest magnitude 0 or within [2^-40, 2^40]) and its checks
 constexpr uint32_t DOMAIN_MIN_BITS = 0x2B800000u;   // 2^-40f

@@ -176,5 +176,19 @@ __device__ __forceinline__ double exact_distance(QP q4, RP r4)
     return cos_finish_exact(ab, exact_norm2(q4), b2);
 }
 
+// Ascending bitonic sort of n (a power of two) LDS entries, compare-exchange given as a functor on two indices and the
+// direction; every thread of the block calls it (topk_large.hip, ivfpq_search.hip)
+template <typename CX>
+__device__ __forceinline__ void bitonic_sort(uint32_t n, CX cx)
+{
+    for (uint32_t size = 2; size <= n; size <<= 1)
+        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+            for (uint32_t i = threadIdx.x; i < n / 2; i += blockDim.x) {
+                const uint32_t lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+                cx(lo, hi, (lo & size) == 0);
+            }
+            __syncthreads();
+        }
+}
 
 }  // namespace smt

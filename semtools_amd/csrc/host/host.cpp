@@ -998,9 +998,11 @@ std::vector<workspace::RankedLine> search_with_workspace(const std::vector<std::
     {
         // the approximate index is OPT-IN: the reference's store always searches exactly (store.rs:619,632)
         const char *min_rows = getenv("SEMTOOLS_INDEX_MIN_ROWS"), *nprobe = getenv("SEMTOOLS_INDEX_NPROBE");
+        const char *max_k = getenv("SEMTOOLS_INDEX_MAX_TOP_K");   // the largest top_k the index answers (default 24; up to 508)
         uint64_t min = ws.config.approximate_index_min_rows ? ws.config.approximate_index_min_rows : UINT64_MAX;
         if (min_rows) { min = strtoull(min_rows, nullptr, 10); if (min == 0) min = UINT64_MAX; }
-        store->set_index_policy(ws.config.oversample_factor, min, nprobe ? (uint32_t)strtoul(nprobe, nullptr, 10) : 16u);
+        store->set_index_policy(ws.config.oversample_factor, min, nprobe ? (uint32_t)strtoul(nprobe, nullptr, 10) : 16u,
+                                max_k ? (uint32_t)std::min<unsigned long>(strtoul(max_k, nullptr, 10), 508ul) : 24u);
     }
 
     // Step 1: changed / new / unchanged (mod.rs:158)

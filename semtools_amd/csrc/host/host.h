@@ -355,9 +355,12 @@ public:
     // corpus has doubled.  oversample_factor (WorkspaceConfig, src/workspace/mod.rs:13,22 --
     // vestigial in the reference, whose store scans exactly) sets the re-score depth: 2 * top_k * oversample_factor
     // ADC candidates per probed list (at least 64) are re-scored against the full-precision rows.  Every returned
-    // distance is exact; only membership is approximate.  Searches over a smaller path subset, top_k > 24, or smaller
+    // distance is exact; only membership is approximate.  Searches over a smaller path subset, top_k > max_top_k, or smaller
     // stores use the exact scan, and so does a search to which the index returns fewer than top_k live rows.
-    void set_index_policy(size_t oversample_factor, uint64_t min_rows, uint32_t nprobe);
+    // max_top_k (SEMTOOLS_INDEX_MAX_TOP_K; default 24, clamped to 508): the largest top_k the index may answer.  Up to 24 the
+    // narrow index search fetches 2 * top_k + 8 <= 56 candidates; above it the wide one (smt_sharded_ivfpq_search_wide) fetches
+    // min(1024, 2 * top_k + 8) for the whole store and top_k inside the ranges of a subset.
+    void set_index_policy(size_t oversample_factor, uint64_t min_rows, uint32_t nprobe, uint32_t max_top_k = 24);
     bool has_index() const { return index_ != nullptr || index_on_disk_; }
 
 private:
@@ -393,6 +396,7 @@ private:
     mutable uint64_t token_log_fingerprint_ = 0;   // fingerprint in the log's header (0 = not read yet / no log)
     uint64_t index_min_rows_ = UINT64_MAX;   // opt-in (see set_index_policy)
     uint32_t index_nprobe_ = 16;
+    uint32_t index_max_top_k_ = 24;
 };
 
 }  // namespace workspace

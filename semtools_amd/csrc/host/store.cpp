@@ -215,8 +215,9 @@ void Store::remove_index_files() const
     for (auto &v : victims) (void)remove(v.c_str());
 }
 
-void Store::set_index_policy(size_t oversample_factor, uint64_t min_rows, uint32_t nprobe)
+void Store::set_index_policy(size_t oversample_factor, uint64_t min_rows, uint32_t nprobe, uint32_t max_top_k)
 {
+    index_max_top_k_ = std::min<uint32_t>(std::max<uint32_t>(1, max_top_k), 508);   // 2 * top_k + 8 <= 1024
     oversample_factor_ = std::max<size_t>(1, oversample_factor);
     index_min_rows_ = min_rows;
     index_nprobe_ = std::max<uint32_t>(1, nprobe);
@@ -786,10 +787,17 @@ std::vector<RankedLine> Store::search_line_embeddings(const std::vector<float> &
     uint64_t ranged = 0;
     for (auto &r : ranges) ranged += r.end - r.begin;
     const bool whole = ranged == count_line_embeddings();
-    if (smt_sharded_corpus_rows(corpus_) >= index_min_rows_ && top_k <= 24 && (whole || ranged >= index_min_rows_) && ensure_index()) {
+    // (top_k <= 24: the narrow index search, whose 2 * top_k + 8 candidates fit its 56; above it, and up to the policy's largest
+    //  top_k, the wide one -- smt_sharded_ivfpq_search_wide, which takes n_ranks x candidates <= 8192)
+    const bool wide = top_k > 24;
+    const size_t want_fetch = whole ? std::min<size_t>(wide ? 1024 : 56, 2 * top_k + 8) : top_k;
+    int n_ranks_now = 1;
+    if (wide) (void)smt_group_info(group_, &n_ranks_now, nullptr, nullptr, nullptr, nullptr);
+    const bool index_takes_k = !wide || (top_k <= index_max_top_k_ && (uint64_t)n_ranks_now * want_fetch <= 8192);
+    if (smt_sharded_corpus_rows(corpus_) >= index_min_rows_ && index_takes_k && (whole || ranged >= index_min_rows_) && ensure_index()) {
         // every stored line: the unfiltered search, with head-room for dead rows (the host drops them below) and the threshold;
         // a real subset: the search inside its ranges -- dead rows lie outside every range, so top_k candidates are enough
-        const uint32_t fetch = whole ? (uint32_t)std::min<size_t>(56, 2 * top_k + 8) : (uint32_t)top_k;
+        const uint32_t fetch = (uint32_t)want_fetch;
         const uint32_t rerank = (uint32_t)std::min<size_t>(512, std::max<size_t>(64, 2 * top_k * oversample_factor_));
         std::vector<uint64_t> c_rows(fetch);
         std::vector<double> c_dist(fetch);
@@ -797,7 +805,11 @@ std::vector<RankedLine> Store::search_line_embeddings(const std::vector<float> &
         uint32_t n_lists = 0;
         check(smt_sharded_ivfpq_info(index_, nullptr, &n_lists, nullptr), "search_line_embeddings (index)");
         const uint32_t nprobe = std::min<uint32_t>(std::min<uint32_t>(index_nprobe_, n_lists), 512);
-        if (whole)
+        if (wide)
+            check(smt_sharded_ivfpq_search_wide(index_, query_vec.data(), 1, fetch, nprobe, rerank, whole ? nullptr : ranges.data(),
+                                                whole ? 0 : (uint32_t)ranges.size(), c_rows.data(), c_dist.data(), &c_n, fetch),
+                  "search_line_embeddings (index, wide)");
+        else if (whole)
             check(smt_sharded_ivfpq_search(index_, query_vec.data(), 1, fetch, nprobe, rerank, c_rows.data(), c_dist.data(), &c_n, fetch),
                   "search_line_embeddings (index)");
         else

@@ -250,292 +250,185 @@ __global__ void __launch_bounds__(MASK_THREADS) ivf_range_mask_kernel(const uint
 // RANGED: the search is inside row ranges; a position whose bit in p.mask is 0 stays empty -- no code bytes are loaded for it and it
 // never becomes a candidate -- and everything after the distances (shortlists, bisection, compaction, re-score, merge) is the same
 // code, so what holds for "the rows of a list segment" without ranges holds for its IN-RANGE rows with them.
-template <int ADC_THREADS, int KIND, bool RANGED>
-__global__ void __launch_bounds__(ADC_THREADS) ivf_adc_kernel(AdcParams p)
+#define IVF_ADC_KERNEL ivf_adc_kernel
+#define IVF_ADC_POOL 0
+#include "ivfpq_adc_body.h"
+#undef IVF_ADC_KERNEL
+#undef IVF_ADC_POOL
+#define IVF_ADC_KERNEL ivf_adc_pool_kernel
+#define IVF_ADC_POOL 1
+#include "ivfpq_adc_body.h"
+#undef IVF_ADC_KERNEL
+#undef IVF_ADC_POOL
+
+// ------------------------------------------------------------------ wide searches: the pool's finish
+// One block per query over its P = lists x slots pool keys (ivf_adc_pool_kernel).  With `valid` keys that are not KEY_PAD and
+// kg = min(valid, top_k + guard) (guard = max(64, top_k / 16) as in topk_large.hip, so kg <= 1088):
+//   valid <= PF_SORT   every valid key goes to LDS and is sorted there; the first kg are taken;
+//   otherwise          the kg-th smallest 64-BIT key is found by radix select (eight 8-bit passes over an LDS histogram, the pattern
+//                      of largek_tau_kernel) and the keys at or below it are compacted into LDS.  Keys are unique -- a row lies in
+//                      exactly one list segment and is part of its key -- so exactly kg pass: ties of the f32 distance break by row,
+//                      nothing overflows, nothing depends on the order the threads arrive in.
+// Those rows are re-scored with exact_distance against the query AS GIVEN, sorted by (f64 bits, row), and the top_k best written
+// with row_base added, padded with (UINT64_MAX, +inf), out_stride apart; counts where wanted.
+// A KEY_PAD key must never reach exact_distance (its row field is 0xFFFFFFFF: the load would leave the corpus).  Three things see to
+// it: KEY_PAD is never counted, histogrammed or compacted; the re-score tests the key again; and it tests row < n_rows.
+constexpr int PF_THREADS = 1024;
+constexpr uint32_t PF_SORT = 2048;                        // LDS entries: the direct path's limit, and >= kg (LK_SORT_MAX of topk_large.hip)
+constexpr size_t IVF_POOL_BUDGET = (size_t)256 << 20;     // bytes of pool per round of queries
+
+struct PoolFinishParams {
+    const float *corpus;
+    uint64_t n_rows;             // rows the index covers: no other row can be in a key
+    const float *queries;        // as given
+    const key_t64 *pool;         // [nq][P]
+    uint32_t P;
+    uint32_t top_k;
+    uint32_t kg;                 // top_k + guard
+    uint64_t row_base;
+    uint64_t *out_rows;
+    double *out_dist;
+    uint64_t *out_counts;        // [nq] or nullptr
+    uint64_t out_stride;
+    unsigned long long *status;  // the context's counter of non-zero verdicts: a query outside the domain is counted there
+};
+
+__global__ void __launch_bounds__(PF_THREADS) ivf_pool_finish_kernel(PoolFinishParams p)
 {
-    __shared__ __attribute__((aligned(16))) float s_lut[KIND == 0 ? PQ_M * PQ_K : 4];
-    __shared__ key_t64 s_keys[(ADC_THREADS / 64) * 64];
-    // XCD-aware block order.  Workgroups go to the 8 XCDs round-robin by their linear id, and each XCD has its own L2: with one grid
-    // row per query the P = nprobe x n_seg blocks of a query landed on P different XCDs and every one of them fetched the query's
-    // 32 KiB LUT (kind 0) from HBM again -- 262 MB of a 2.4 GB launch (profiles/r05_ivf/, r06_ivf/).  The grid is one line of
-    // ceil(nq / 8) x 8 x P blocks: XCD x takes the queries q = 8 j + x, and the P blocks of a query follow each other ON that XCD.
-    const uint32_t P = p.nprobe * p.n_seg;
-    const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
-    const uint32_t qi = (slot / P) * 8u + xcd, pblk = slot % P;
-    if (qi >= p.nq) return;   // (the last group of eight queries may be short)
-    const uint32_t pi = pblk / p.n_seg, seg = pblk % p.n_seg;
+    __shared__ key_t64 s_keys[PF_SORT];
+    __shared__ uint64_t s_dbits[PF_SORT];   // f64 distance bits (non-negative or +inf: they order like the values)
+    __shared__ uint32_t s_row[PF_SORT];
+    __shared__ unsigned int s_hist[256];
+    __shared__ unsigned long long s_prefix; // radix select: the digits found so far
+    __shared__ unsigned int s_misc[5];      // [0] valid keys, [1] compaction cursor, [2] max |query| bits, [3] rows kept, [4] rank still wanted
+    const uint32_t qi = blockIdx.x;
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int kp = (int)p.kp;
-    const int ks = (int)p.shortlist;
-    key_t64 *out = p.lists + ((size_t)qi * p.nprobe * p.n_seg + pblk) * kp;
+    const key_t64 *pool = p.pool + (size_t)qi * p.P;
+    if (threadIdx.x < 5) s_misc[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_prefix = 0ull;
+    __syncthreads();
+    if (threadIdx.x < 256) atomicMax(&s_misc[2], __float_as_uint(p.queries[(size_t)qi * 256 + threadIdx.x]) & 0x7fffffffu);
     {
-        // this block's segment of the probed list; most lists are shorter than n_seg segments: leave an empty list
-        const uint32_t l0 = p.probe_list[(size_t)qi * p.nprobe + pi];
-        const uint64_t b0 = p.list_offsets[l0], e0 = p.list_offsets[l0 + 1];
-        if (b0 + (uint64_t)seg * p.seg_len >= e0) {  // block-uniform
-            if ((int)threadIdx.x < kp) out[threadIdx.x] = KEY_PAD;
-            return;
+        uint32_t cnt = 0;   // wave-uniform
+        for (uint32_t i0 = threadIdx.x - lane; i0 < p.P; i0 += PF_THREADS) {
+            const uint32_t i = i0 + lane;
+            cnt += (uint32_t)__popcll(__ballot(i < p.P && pool[i] != KEY_PAD));
         }
+        if (lane == 0 && cnt) atomicAdd(&s_misc[0], cnt);
     }
-
-    if constexpr (KIND == 0) {
-        const f32x4 *lsrc = reinterpret_cast<const f32x4 *>(p.lut + (size_t)qi * PQ_M * PQ_K);
-        for (int e = threadIdx.x; e < PQ_M * PQ_K / 4; e += ADC_THREADS) reinterpret_cast<f32x4 *>(s_lut)[e] = lsrc[e];
-    }
-    // kind 1: the 32 weights of this (query, list) pair, block-uniform (scalar loads)
-    float lw[PQ_M];
-    if constexpr (KIND == 1) {
-        const float *src = p.lw + ((size_t)qi * p.nprobe + pi) * PQ_M;
-#pragma unroll
-        for (int k = 0; k < PQ_M; ++k) lw[k] = src[k];
+    __syncthreads();
+    const uint32_t valid = s_misc[0];
+    const uint32_t kg = valid < p.kg ? valid : p.kg;
+    // keys that pass `take` go to consecutive LDS slots (one LDS atomic per wave and step; the order among them is settled by the sorts)
+    auto compact = [&](key_t64 limit) {
+        for (uint32_t i0 = threadIdx.x - lane; i0 < p.P; i0 += PF_THREADS) {
+            const uint32_t i = i0 + lane;
+            const key_t64 key = i < p.P ? pool[i] : KEY_PAD;
+            const bool take = key != KEY_PAD && key <= limit;
+            const unsigned long long m = __ballot(take);
+            if (m == 0ull) continue;
+            unsigned int at = 0;
+            if (lane == 0) at = atomicAdd(&s_misc[1], (unsigned int)__popcll(m));
+            at = (unsigned int)__builtin_amdgcn_readfirstlane((int)at) + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
+            if (take && at < PF_SORT) s_keys[at] = key;
+        }
+    };
+    uint32_t m;   // rows to re-score: s_keys[0, m)
+    if (valid <= PF_SORT) {
+        uint32_t np = 1;
+        while (np < valid) np <<= 1;
+        for (uint32_t i = threadIdx.x; i < np; i += PF_THREADS) s_keys[i] = KEY_PAD;
+        __syncthreads();
+        compact(KEY_PAD);
+        __syncthreads();
+        bitonic_sort(np, [&](uint32_t a, uint32_t b, bool up) {
+            const key_t64 x = s_keys[a], y = s_keys[b];
+            if ((x > y) == up && x != y) { s_keys[a] = y; s_keys[b] = x; }
+        });
+        m = kg;
     } else {
-#pragma unroll
-        for (int k = 0; k < PQ_M; ++k) lw[k] = 0.0f;
-    }
-    float lw_bias = 0.0f;
-    if constexpr (KIND == 1) {
-#pragma unroll
-        for (int k = 0; k < PQ_M; ++k) lw_bias += lw[k];
-        lw_bias *= 128.0f;
-    }
-    const uint32_t rot = (uint32_t)lane & 31u;   // KIND 0: this lane's walk through the sub-quantisers starts at rot
-    const uint32_t m16 = (rot & 16u) ? 0xFFFFFFFFu : 0u, m8 = (rot & 8u) ? 0xFFFFFFFFu : 0u, m4 = (rot & 4u) ? 0xFFFFFFFFu : 0u;
-    auto bfi = [](uint32_t m, uint32_t a, uint32_t b) -> uint32_t {   // (a & m) | (b & ~m) in ONE instruction, and opaque to the optimiser
-        uint32_t d;
-        asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "v"(m), "v"(a), "v"(b));
-        return d;
-    };
-    const f32x4 qv = reinterpret_cast<const f32x4 *>(p.queries + (size_t)qi * 256)[lane];
-    const float a2 = wave_sum(qv.x * qv.x + qv.y * qv.y + qv.z * qv.z + qv.w * qv.w);
-    const bool qz = a2 == 0.0f;
-    const float rq = qz ? 0.0f : __frsqrt_rn(a2);
-    const uint32_t list = p.probe_list[(size_t)qi * p.nprobe + pi];
-    const float base = p.probe_dot[(size_t)qi * p.nprobe + pi];
-    const uint64_t begin = p.list_offsets[list] + (uint64_t)seg * p.seg_len;
-    const uint64_t list_end = p.list_offsets[list + 1];
-    const uint64_t end = seg + 1 == p.n_seg ? list_end : min(list_end, begin + (uint64_t)p.seg_len);  // the last segment takes the rest
-    __syncthreads();
-
-    // wave-uniform insert of (cd, cr) into a lane-distributed sorted list of `cap` entries
-    auto insert = [&](float cd, uint32_t cr, float &ld, uint32_t &lr, float &thr_d, uint32_t &thr_r, int cap) {
-        if (cd < thr_d || (cd == thr_d && cr < thr_r)) {
-            const bool less = (ld < cd) || (ld == cd && lr < cr);
-            const int pos = __popcll(__ballot(less));
-            const float sd = dpp_f<DPP_WAVE_SHR1>(ld);
-            const uint32_t sr = dpp_u<DPP_WAVE_SHR1>(lr);
-            if (lane > pos) { ld = sd; lr = sr; }
-            else if (lane == pos) { ld = cd; lr = cr; }
-            thr_d = readlane_f(ld, cap - 1);
-            thr_r = (uint32_t)__builtin_amdgcn_readlane((int)lr, cap - 1);
-        }
-    };
-
-    // ---- stage 1: ADC scan of the list's codes -> the wave's `ks` best approximate candidates (an unordered SET:
-    // lane i < n_short ends up holding one of them in (ld, lr)).  A wave takes 64 x ADC_R codes per pass, keeps
-    // their ADC distances in registers next to the set carried over from the previous pass, finds the ks-th
-    // smallest by bisection on the distance bits (one ballot + scalar popcount per register and step) and
-    // compacts the winners through LDS.  (The first version inserted candidates one at a time into a sorted
-    // lane-distributed list: ~160 serial inserts per wave at ks = 64 -- that, not the re-score reads, was what
-    // bounded this kernel.)
-    constexpr int ADC_R = 8;
-    float ld = __builtin_inff();       // carried set: lane i < n_carry holds a real entry
-    uint32_t lr = 0xFFFFFFFFu;
-    key_t64 *s_short = s_keys + wave * 64;  // per-wave compaction scratch (s_keys is reused by the block merge later)
-    // RANGED: a lane's positions lie whole multiples of 64 apart, so its mask bits share ONE bit index and their words follow from
-    // one per-lane pointer that moves with the passes -- three VGPRs; the kernel argument's two SGPRs are free again after this line
-    // (the per-list PCA kind keeps its 32 weights in SGPRs and has none to spare)
-    const uint64_t *mword = nullptr;
-    uint32_t mshift = 0;
-    if constexpr (RANGED) {
-        const uint64_t first = begin + (uint64_t)wave * 64 + (uint64_t)lane;
-        mword = p.mask + (first >> 6);
-        mshift = (uint32_t)first & 63u;
-    }
-    // (64-code groups are dealt to the waves round-robin, so every wave sees codes from the whole list: lists are in
-    // row order and neighbours cluster -- contiguous 512-code chunks per wave cost a point of recall)
-    for (uint64_t base_i = begin; base_i < end; base_i += (uint64_t)(ADC_THREADS / 64) * 64 * ADC_R) {
-        uint32_t kd[ADC_R + 1], kpos[ADC_R + 1];  // orderable distance bits (0xFFFFFFFF = empty) and list positions
-#pragma unroll
-        for (int r = 0; r < ADC_R; ++r) {
-            const uint64_t i = base_i + ((uint64_t)r * (ADC_THREADS / 64) + wave) * 64 + lane;
-            kd[r] = 0xFFFFFFFFu;
-            kpos[r] = 0xFFFFFFFFu;
-            bool take = i < end;
-            if constexpr (RANGED) {   // bit i of the mask (a wave reads at most two adjacent words; none is read past the list's end)
-                if (take) take = ((mword[r * (ADC_THREADS / 64)] >> mshift) & 1ull) != 0ull;
+        if (threadIdx.x == 0) s_misc[4] = kg;   // (1-based rank; kg >= 1 here)
+        key_t64 mask = 0ull;
+        for (int shift = 56; shift >= 0; shift -= 8) {
+            if (threadIdx.x < 256) s_hist[threadIdx.x] = 0;
+            __syncthreads();
+            const key_t64 prefix = s_prefix;
+            for (uint32_t i = threadIdx.x; i < p.P; i += PF_THREADS) {
+                const key_t64 v = pool[i];
+                if (v != KEY_PAD && (v & mask) == prefix) atomicAdd(&s_hist[(uint32_t)(v >> shift) & 255u], 1u);
             }
-            if (take) {
-                const uint4 c0 = reinterpret_cast<const uint4 *>(p.codes + i * PQ_M)[0];
-                const uint4 c1 = reinterpret_cast<const uint4 *>(p.codes + i * PQ_M)[1];
-                const uint32_t w[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-                float acc = base;
-                if constexpr (KIND == 1) {   // signed bytes times the pair's weights
-                    // s = u - 128 with u = s ^ 0x80 as an unsigned byte: one v_cvt_f32_ubyteN per byte instead of a sign-extending
-                    // bit-field extract + convert, and 128 x sum(lw) comes off the block-uniform base (lw_bias)
-                    acc = base - lw_bias;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const uint32_t x = w[u] ^ 0x80808080u;
-                        acc += lw[4 * u + 0] * (float)(x & 0xFF);
-                        acc += lw[4 * u + 1] * (float)((x >> 8) & 0xFF);
-                        acc += lw[4 * u + 2] * (float)((x >> 16) & 0xFF);
-                        acc += lw[4 * u + 3] * (float)(x >> 24);
-                    }
-                } else {
-                    // the record rotated left by rot = lane % 32 bytes: byte t of x[] is the code of sub-quantiser (t + rot) % 32
-                    // (bit selects through lane masks, one v_bfi_b32 each, as inline asm: written as `rot & 16 ? a : b` clang folds the three stages into ONE
-                    // dynamically indexed pick per dword -- seven compare + select pairs each, 1400 of them per pass, 0.36 of HBM)
-                    uint32_t x[8], y[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) y[u] = bfi(m16, w[(u + 4) & 7], w[u]);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) x[u] = bfi(m8, y[(u + 2) & 7], y[u]);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) y[u] = bfi(m4, x[(u + 1) & 7], x[u]);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) x[u] = __builtin_amdgcn_alignbyte(y[(u + 1) & 7], y[u], rot & 3);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        acc += s_lut[((x[u] & 0xFF) << 5) | ((4 * u + 0 + rot) & 31)];
-                        acc += s_lut[(((x[u] >> 8) & 0xFF) << 5) | ((4 * u + 1 + rot) & 31)];
-                        acc += s_lut[(((x[u] >> 16) & 0xFF) << 5) | ((4 * u + 2 + rot) & 31)];
-                        acc += s_lut[((x[u] >> 24) << 5) | ((4 * u + 3 + rot) & 31)];
-                    }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                uint32_t want = s_misc[4], d = 0;
+                for (; d < 255; ++d) {
+                    if (s_hist[d] >= want) break;
+                    want -= s_hist[d];
                 }
-                const float d = fmaxf(1.0f - acc * rq, 0.0f);  // rows are unit-norm (model2vec output), zero rows score ~0
-                if (acc == acc) {                                // a NaN score never becomes a candidate
-                    kd[r] = min(__float_as_uint(d), 0xFFFFFFFEu);  // d >= 0: the bit pattern orders like the value
-                    kpos[r] = (uint32_t)i;                         // position in list order (codes / ids / int8 rows share it)
-                }
+                s_prefix = prefix | ((key_t64)d << shift);
+                s_misc[4] = want;
             }
+            mask |= (key_t64)255 << shift;
+            __syncthreads();
         }
-        kd[ADC_R] = lr != 0xFFFFFFFFu ? __float_as_uint(ld) : 0xFFFFFFFFu;  // (ld keeps only the top 16 bits: enough here)
-        kpos[ADC_R] = lr;
-        // (wave-wide counts through ballots: the compare writes a lane mask to SGPRs and s_bcnt1 counts it on the scalar unit --
-        // 9 VALU instructions per bisection step instead of 9 + 9 + an 11-instruction lane reduction)
-        uint32_t total = 0;
-#pragma unroll
-        for (int r = 0; r <= ADC_R; ++r) total += (uint32_t)__popcll(__ballot(kd[r] != 0xFFFFFFFFu));
-        // The ADC distance is itself an approximation (error ~1e-2): its top 16 bits (relative step 2^-8 of the value)
-        // are all the selection needs, which halves the bisection; ties in that bucket go by scan order.
-#pragma unroll
-        for (int r = 0; r <= ADC_R; ++r) kd[r] = kd[r] == 0xFFFFFFFFu ? 0xFFFFFFFFu : (kd[r] >> 16);
-        uint32_t T = 0xFFFFFFFEu, need_eq = 0xFFFFFFFFu;  // winners: kd < T, plus the first need_eq entries with kd == T
-        if (total > (uint32_t)ks) {
-            uint32_t lo = 0u, hi = 0xFFFFu;               // smallest T with #(kd <= T) >= ks
-            while (lo < hi) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                uint32_t cnt = 0;
-#pragma unroll
-                for (int r = 0; r <= ADC_R; ++r) cnt += (uint32_t)__popcll(__ballot(kd[r] <= mid));
-                if (cnt >= (uint32_t)ks) hi = mid; else lo = mid + 1u;
-            }
-            T = lo;
-            uint32_t n_lt = 0;
-#pragma unroll
-            for (int r = 0; r <= ADC_R; ++r) n_lt += (uint32_t)__popcll(__ballot(kd[r] < T));
-            need_eq = (uint32_t)ks - n_lt;
-        }
-        // compaction: winners take consecutive LDS slots, then lane i reads slot i
-        uint32_t n_out = 0, n_eq_seen = 0;
-        const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-        for (int r = 0; r <= ADC_R; ++r) {
-            const bool valid = kd[r] != 0xFFFFFFFFu;
-            const bool lt = valid && kd[r] < T;
-            const bool eq = valid && kd[r] == T;
-            const unsigned long long m_eq = __ballot(eq);
-            const bool eq_win = eq && (n_eq_seen + (uint32_t)__popcll(m_eq & below)) < need_eq;
-            const unsigned long long m_win = __ballot(lt || eq_win);
-            if (lt || eq_win) s_short[n_out + (uint32_t)__popcll(m_win & below)] = ((key_t64)kd[r] << 32) | kpos[r];
-            n_out += (uint32_t)__popcll(m_win);
-            n_eq_seen += (uint32_t)__popcll(m_eq);
-        }
-        __builtin_amdgcn_wave_barrier();
-        const key_t64 mine = (uint32_t)lane < n_out ? reinterpret_cast<volatile key_t64 *>(s_short)[lane] : KEY_PAD;
-        __builtin_amdgcn_wave_barrier();
-        ld = mine != KEY_PAD ? __uint_as_float((uint32_t)(mine >> 32) << 16) : __builtin_inff();
-        lr = mine != KEY_PAD ? (uint32_t)(mine & 0xFFFFFFFFull) : 0xFFFFFFFFu;
-        if constexpr (RANGED) mword += (ADC_THREADS / 64) * ADC_R;
+        compact(s_prefix);   // (the kg-th smallest key: a real one, below KEY_PAD)
+        __syncthreads();
+        const uint32_t got = s_misc[1];
+        m = got < PF_SORT ? got : PF_SORT;   // == kg: keys are unique
     }
-
-    // (An int8 refinement stage between the two -- a 260 B/row copy of the rows ranking the shortlist so that only a few
-    // candidates need their 1 KiB row -- was built in round 1, measured at +6 % queries/s for a 7x larger index, kept opt-in
-    // for two rounds and removed in round 3.)
-    const int n_short = __popcll(__ballot(lr != 0xFFFFFFFFu));  // the set sits in lanes 0..n_short-1
-    unsigned long long go = n_short >= 64 ? ~0ull : ((1ull << n_short) - 1ull);  // lanes whose candidate is re-scored
-
-    // ---- stage 2: re-score the survivors with the full-precision rows (coalesced 1 KiB loads, f32),
-    //      keep the kp best; the select stage then recomputes those exactly in f64
-    // RANGED: the two pointers of this stage are read from the kernel arguments HERE.  Left to the compiler they are loaded at the
-    // kernel's entry and held in SGPRs across the scan loop, where the mask test's second level of lane masks takes two more than
-    // the per-list PCA kind has (its 32 weights live there): it spilled p.corpus.  (The kernel's only argument is p, by value, so it
-    // sits at offset 0 of the kernel-argument segment; AdcParams is standard-layout, see the static_assert below it.  What guards
-    // this workaround is tests/test_ivf_ranges_resources.py: 0 spills and the twin's occupancy step for every RANGED instantiation --
-    // a compiler that no longer needs it shows there as well, and the block can then go.)
-    const uint32_t *ids = p.ids;
-    const float *corpus = p.corpus;
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (RANGED) {
-        const char *ka = reinterpret_cast<const char *>(__builtin_amdgcn_kernarg_segment_ptr());
-        asm volatile("" : "+s"(ka));   // (opaque: nothing read through it moves above this line)
-        ids = *reinterpret_cast<const uint32_t *const *>(ka + offsetof(AdcParams, ids));
-        corpus = *reinterpret_cast<const float *const *>(ka + offsetof(AdcParams, corpus));
-    }
-#endif
-    const uint32_t my_row = (lane < n_short && ((go >> lane) & 1ull)) ? ids[lr] : 0xFFFFFFFFu;  // one gather, before the loop
-    float ld2 = __builtin_inff();
-    uint32_t lr2 = 0xFFFFFFFFu;
-    float thr2_d = __builtin_inff();
-    uint32_t thr2_r = 0xFFFFFFFFu;
-    // Rows in flight per wave: the reads are random 1 KiB rows, i.e. latency, and what hides it is rows in flight per CU.  The PQ
-    // kind's 32 KiB LUT keeps it at 4 waves per SIMD where the per-list PCA kind runs 7, so its waves keep EIGHT rows in flight
-    // instead of four (round 6: the re-scored rows are 60 % of this kernel's bytes -- 128 KiB per block against 88 KiB of codes --
-    // and their latency, not the LUT gathers, was what held the PQ kind at 0.57 of HBM).
-    constexpr int RS = KIND == 0 ? 8 : 4;
-    while (go) {
-        f32x4 c[RS];
-        uint32_t rr[RS];
-        bool ok[RS];
-#pragma unroll
-        for (int u = 0; u < RS; ++u) {
-            ok[u] = go != 0ull;
-            const int src = ok[u] ? __ffsll((long long)go) - 1 : 0;
-            if (ok[u]) go &= go - 1;
-            rr[u] = (uint32_t)__builtin_amdgcn_readlane((int)my_row, src);
-            c[u] = reinterpret_cast<const f32x4 *>(corpus + (uint64_t)(ok[u] ? rr[u] : 0u) * 256)[lane];
+    uint32_t mp = 1;
+    while (mp < m) mp <<= 1;
+    const f32x4 *q4 = reinterpret_cast<const f32x4 *>(p.queries + (size_t)qi * 256);
+    for (uint32_t i = threadIdx.x; i < mp; i += PF_THREADS) {
+        uint64_t dbits = 0x7FF0000000000000ull;
+        uint32_t r = 0xFFFFFFFFu;
+        const key_t64 key = i < m ? s_keys[i] : KEY_PAD;
+        const uint32_t row = (uint32_t)(key & 0xFFFFFFFFull);
+        if (key != KEY_PAD && (uint64_t)row < p.n_rows) {
+            const double d = exact_distance(q4, reinterpret_cast<const f32x4 *>(p.corpus + (uint64_t)row * 256));
+            if (d == d) { dbits = (uint64_t)__double_as_longlong(d); r = row; atomicAdd(&s_misc[3], 1u); }
         }
-        // four rows' norms and dot products reduced together (device_utils.h wave_sum4: lane l ends with the sum of row l % 4)
-#pragma unroll
-        for (int g4 = 0; g4 < RS; g4 += 4) {
-            float pb[4], pa[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const f32x4 cu = c[g4 + u];
-                pb[u] = cu.x * cu.x + cu.y * cu.y + cu.z * cu.z + cu.w * cu.w;
-                pa[u] = cu.x * qv.x + cu.y * qv.y + cu.z * qv.z + cu.w * qv.w;
-            }
-            const float b2s = wave_sum4(pb[0], pb[1], pb[2], pb[3], lane);
-            const float abs4 = wave_sum4(pa[0], pa[1], pa[2], pa[3], lane);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float b2 = readlane_f(b2s, u), ab = readlane_f(abs4, u);
-                if (ok[g4 + u]) insert(dist_f32(ab, b2, rq, qz), rr[g4 + u], ld2, lr2, thr2_d, thr2_r, kp);
-            }
-        }
+        s_dbits[i] = dbits;
+        s_row[i] = r;
     }
-
-    // block merge of the wave lists (rank by counting), as in K2
-    s_keys[wave * 64 + lane] = (lane < kp && lr2 != 0xFFFFFFFFu) ? make_key(ld2, lr2) : KEY_PAD;
-    if ((int)threadIdx.x < kp) out[threadIdx.x] = KEY_PAD;
     __syncthreads();
-    const key_t64 mine = s_keys[wave * 64 + lane];
-    if (mine != KEY_PAD) {
-        int rank = 0;
-        for (int w = 0; w < ADC_THREADS / 64; ++w)
-            for (int i = 0; i < kp; ++i) rank += (s_keys[w * 64 + i] < mine) ? 1 : 0;
-        if (rank < kp) out[rank] = mine;
+    bitonic_sort(mp, [&](uint32_t a, uint32_t b, bool up) {
+        const uint64_t da = s_dbits[a], db = s_dbits[b];
+        const uint32_t ra = s_row[a], rb = s_row[b];
+        const bool gt = da > db || (da == db && ra > rb);
+        const bool lt = da < db || (da == db && ra < rb);
+        if (up ? gt : lt) { s_dbits[a] = db; s_dbits[b] = da; s_row[a] = rb; s_row[b] = ra; }
+    });
+    const uint32_t kept = s_misc[3];
+    const uint32_t n_out = kept < p.top_k ? kept : p.top_k;
+    uint64_t *orow = p.out_rows + (size_t)qi * p.out_stride;
+    double *odist = p.out_dist + (size_t)qi * p.out_stride;
+    for (uint32_t t = threadIdx.x; t < p.top_k; t += PF_THREADS) {
+        if (t < n_out) { orow[t] = p.row_base + s_row[t]; odist[t] = __longlong_as_double((long long)s_dbits[t]); }
+        else { orow[t] = 0xFFFFFFFFFFFFFFFFull; odist[t] = __builtin_inf(); }
+    }
+    if (threadIdx.x == 0) {
+        if (p.out_counts) p.out_counts[qi] = n_out;
+        // (a query outside the domain, domain.hip: the host forms refuse it before the launch, a device form counts it like the select)
+        if (!magnitude_in_domain(s_misc[2]) && p.status) atomicAdd(p.status, 1ull);
+    }
+}
+
+static void launch_adc_pool(uint32_t kind, int adc_waves, bool filtered, dim3 grid, hipStream_t st, const AdcParams &ap)
+{
+    if (filtered) {
+        if (kind == 1) {
+            if (adc_waves == 8) hipLaunchKernelGGL((ivf_adc_pool_kernel<512, 1, true>), grid, dim3(512), 0, st, ap);
+            else hipLaunchKernelGGL((ivf_adc_pool_kernel<256, 1, true>), grid, dim3(256), 0, st, ap);
+        } else {
+            if (adc_waves == 8) hipLaunchKernelGGL((ivf_adc_pool_kernel<512, 0, true>), grid, dim3(512), 0, st, ap);
+            else hipLaunchKernelGGL((ivf_adc_pool_kernel<256, 0, true>), grid, dim3(256), 0, st, ap);
+        }
+    } else if (kind == 1) {
+        if (adc_waves == 8) hipLaunchKernelGGL((ivf_adc_pool_kernel<512, 1, false>), grid, dim3(512), 0, st, ap);
+        else hipLaunchKernelGGL((ivf_adc_pool_kernel<256, 1, false>), grid, dim3(256), 0, st, ap);
+    } else {
+        if (adc_waves == 8) hipLaunchKernelGGL((ivf_adc_pool_kernel<512, 0, false>), grid, dim3(512), 0, st, ap);
+        else hipLaunchKernelGGL((ivf_adc_pool_kernel<256, 0, false>), grid, dim3(256), 0, st, ap);
     }
 }
 
@@ -565,21 +458,16 @@ static int ranges_pinned(smt_ctx *ctx, size_t bytes, smt_range **pin)
 
 extern "C" {
 
-// `filtered`: the search is inside `ranges` (VALID corpus-local rows: the callers check them); without it the ranges are not looked
-// at and every launch, every scratch offset and every byte of the answer is what it was before ranges existed.  A filter that
-// leaves nothing (no range, or empty ones only) is still a filter: the mask is all zeros and the answer is empty.
-static int ivfpq_search_core(smt_ivfpq *ix, const float *queries, bool queries_on_device, uint32_t nq, uint32_t top_k, uint32_t nprobe,
-                             uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, bool filtered, uint64_t row_base,
-                             uint64_t *d_or_user, double *d_od_user, uint64_t *d_oc_user,
-                             uint64_t **d_or_out, size_t *out_bytes_contig, uint64_t out_stride = 0, smt::Delivery *deliver = nullptr)
+// How a search cuts the probed lists into blocks: segments per list, their length, waves per block and shortlist per wave.  The same
+// for the narrow and the wide route (`rerank` as the caller gave it, 0 = 512, checked).
+struct AdcPlan {
+    uint32_t n_seg, seg_len, shortlist;
+    int adc_waves;
+};
+
+static AdcPlan adc_plan(const smt_ivfpq *ix, uint32_t nprobe, uint32_t rerank)
 {
-    smt_ctx *ctx = ix->corpus->ctx;
-    IVF_REQUIRE_FRESH(ix);
-    SMT_REQUIRE(ix->corpus->rows >= ix->n_rows, "the corpus shrank after the index was built: rebuild");
-    SMT_REQUIRE(nprobe >= 1 && nprobe <= ix->nlist && nprobe <= 512, "nprobe must be in [1, min(nlist, 512)]");
-    SMT_REQUIRE(top_k <= 56, "top_k must be <= 56 for the IVF-PQ path");
-    if (rerank == 0) rerank = 512;
-    SMT_REQUIRE(rerank >= 4 && rerank <= 512, "rerank (full-precision re-scored ADC candidates per probed list) must be in [4, 512]");
+    AdcPlan pl;
     // A list longer than ADC_SEGMENT codes is scanned by several blocks, each with its own shortlist of `rerank`
     // candidates (config 5's 100 M rows over 4096 lists: 24 k codes per list -- one shortlist of 512 would re-score
     // 2 % of them and recall@10 drops to 0.75); the select stage takes at most 512 lists per query.
@@ -600,9 +488,50 @@ static int ivfpq_search_core(smt_ivfpq *ix, const float *queries, bool queries_o
 
     // waves per (query, list segment) block.  (PQ, kind 0, with 8-wave blocks -- two blocks' worth of waves sharing one 32 KiB LUT --
     // measured +4 % queries/s for -0.5 point of recall@10 at rerank 128: sixteen candidates per wave are too few.  Not taken.)
-    const int adc_waves = rerank > 256 ? 8 : 4;
-    const uint32_t shortlist = (rerank + adc_waves - 1) / adc_waves;  // per wave
-    const uint32_t kp = top_k + 8;                // re-scored candidates handed to the exact select stage
+    pl.adc_waves = rerank > 256 ? 8 : 4;
+    pl.shortlist = (rerank + pl.adc_waves - 1) / pl.adc_waves;  // per wave
+    pl.n_seg = n_seg;
+    pl.seg_len = seg_len;
+    return pl;
+}
+
+// `filtered`: the search is inside `ranges` (VALID corpus-local rows: the callers check them); without it the ranges are not looked
+// at and every launch, every scratch offset and every byte of the answer is what it was before ranges existed.  A filter that
+// leaves nothing (no range, or empty ones only) is still a filter: the mask is all zeros and the answer is empty.
+static int ivfpq_search_core(smt_ivfpq *ix, const float *queries, bool queries_on_device, uint32_t nq, uint32_t top_k, uint32_t nprobe,
+                             uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, bool filtered, uint64_t row_base,
+                             uint64_t *d_or_user, double *d_od_user, uint64_t *d_oc_user,
+                             uint64_t **d_or_out, size_t *out_bytes_contig, uint64_t out_stride = 0, smt::Delivery *deliver = nullptr,
+                             bool wide = false)
+{
+    smt_ctx *ctx = ix->corpus->ctx;
+    IVF_REQUIRE_FRESH(ix);
+    SMT_REQUIRE(ix->corpus->rows >= ix->n_rows, "the corpus shrank after the index was built: rebuild");
+    SMT_REQUIRE(nprobe >= 1 && nprobe <= ix->nlist && nprobe <= 512, "nprobe must be in [1, min(nlist, 512)]");
+    if (wide) SMT_REQUIRE(top_k > SCAN_MAX_K && top_k <= LARGEK_MAX_K, "top_k must be <= 1024 for the wide IVF-PQ path");
+    else SMT_REQUIRE(top_k <= 56, "top_k must be <= 56 for the IVF-PQ path");
+    if (rerank == 0) rerank = 512;
+    SMT_REQUIRE(rerank >= 4 && rerank <= 512, "rerank (full-precision re-scored ADC candidates per probed list) must be in [4, 512]");
+    const AdcPlan plan = adc_plan(ix, nprobe, rerank);
+    const uint32_t n_seg = plan.n_seg, seg_len = plan.seg_len, shortlist = plan.shortlist;
+    const int adc_waves = plan.adc_waves;
+    const uint32_t kp = top_k + 8;                // re-scored candidates handed to the exact select stage (narrow route)
+    // wide: every re-scored row of a query goes to its pool, [nprobe * n_seg][waves * 64] keys (at most 512 x 512 = 2 MiB); a batch
+    // whose pool would pass IVF_POOL_BUDGET runs in rounds of queries, each round the whole route on its part of the caller's buffers
+    const uint32_t pool_slots = (uint32_t)adc_waves * 64u;
+    const size_t pool_per_query = (size_t)nprobe * n_seg * pool_slots * sizeof(key_t64);
+    if (wide && (size_t)nq * pool_per_query > IVF_POOL_BUDGET) {
+        SMT_REQUIRE(queries_on_device && d_or_user && d_od_user && !deliver, "a wide search in rounds writes to the caller's device buffers");
+        const uint32_t nq_round = (uint32_t)std::max<size_t>(1, IVF_POOL_BUDGET / pool_per_query);
+        const uint64_t stride = out_stride ? out_stride : top_k;
+        for (uint32_t q0 = 0; q0 < nq; q0 += nq_round) {
+            const int rc_round = ivfpq_search_core(ix, queries + (size_t)q0 * 256, true, std::min(nq_round, nq - q0), top_k, nprobe, rerank, ranges,
+                                                   n_ranges, filtered, row_base, d_or_user + (size_t)q0 * stride, d_od_user + (size_t)q0 * stride,
+                                                   d_oc_user ? d_oc_user + q0 : nullptr, nullptr, nullptr, out_stride, nullptr, true);
+            if (rc_round) return rc_round;
+        }
+        return SMT_OK;
+    }
     // every temporary lives in the context's scratch (no hipMalloc/hipFree per call), results come back through
     // the pinned staging buffer
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -610,7 +539,7 @@ static int ivfpq_search_core(smt_ivfpq *ix, const float *queries, bool queries_o
     const size_t o_pl = o_q + b_q, b_pl = al((size_t)nq * nprobe * 4);
     const size_t o_pd = o_pl + b_pl, b_pd = b_pl;
     const size_t o_lut = o_pd + b_pd, b_lut = al((size_t)nq * PQ_M * PQ_K * 4);
-    const size_t o_lists = o_lut + b_lut, b_lists = al((size_t)nq * nprobe * n_seg * kp * 8);
+    const size_t o_lists = o_lut + b_lut, b_lists = wide ? 0 : al((size_t)nq * nprobe * n_seg * kp * 8);
     const size_t o_or = o_lists + b_lists, b_or = (size_t)nq * top_k * 8;   // rows | dist | counts contiguous: one D2H
     const size_t o_od = o_or + b_or, b_od = b_or;
     const size_t o_oc = o_od + b_od, b_oc = al((size_t)nq * 8);
@@ -622,7 +551,8 @@ static int ivfpq_search_core(smt_ivfpq *ix, const float *queries, bool queries_o
     const uint64_t mask_words = (ix->n_rows + 63) / 64;
     const size_t o_rg = o_lw + b_lw, b_rg = filtered ? al((size_t)n_rr * sizeof(smt_range)) : 0;
     const size_t o_mask = o_rg + b_rg, b_mask = filtered ? al((size_t)mask_words * 8) : 0;
-    int rc = smt::ensure_scratch(ctx, o_mask + b_mask);
+    const size_t o_pool = o_mask + b_mask, b_pool = wide ? al((size_t)nq * pool_per_query) : 0;   // (behind everything of the narrow route)
+    int rc = smt::ensure_scratch(ctx, o_pool + b_pool);
     if (rc) return rc;
     char *base = reinterpret_cast<char *>(ctx->d_scratch);
     if (filtered) {   // (rebuilt on every call: no mask outlives its search)
@@ -696,11 +626,12 @@ static int ivfpq_search_core(smt_ivfpq *ix, const float *queries, bool queries_o
     ap.seg_len = seg_len ? seg_len : 512;
     ap.shortlist = shortlist;
     ap.kp = kp;
-    ap.lists = reinterpret_cast<key_t64 *>(base + o_lists);
+    ap.lists = reinterpret_cast<key_t64 *>(base + (wide ? o_pool : o_lists));
     ap.mask = filtered ? reinterpret_cast<const uint64_t *>(base + o_mask) : nullptr;
     prof_begin(ctx, "ivf_adc");
     const dim3 adc_grid(((nq + 7) / 8) * 8 * nprobe * n_seg);   // (one line: see the XCD-aware order in the kernel)
-    if (filtered) {
+    if (wide) launch_adc_pool(ix->kind, adc_waves, filtered, adc_grid, ctx->stream, ap);
+    else if (filtered) {
         if (ix->kind == 1) {
             if (adc_waves == 8) hipLaunchKernelGGL((ivf_adc_kernel<512, 1, true>), adc_grid, dim3(512), 0, ctx->stream, ap);
             else hipLaunchKernelGGL((ivf_adc_kernel<256, 1, true>), adc_grid, dim3(256), 0, ctx->stream, ap);
@@ -720,6 +651,29 @@ static int ivfpq_search_core(smt_ivfpq *ix, const float *queries, bool queries_o
     uint64_t *d_or = d_or_user ? d_or_user : reinterpret_cast<uint64_t *>(base + o_or);
     double *d_od = d_od_user ? d_od_user : reinterpret_cast<double *>(base + o_od);
     uint64_t *d_oc = d_or_user ? d_oc_user : reinterpret_cast<uint64_t *>(base + o_oc);
+    if (wide) {   // the pool's finish in place of the select stage
+        PoolFinishParams fp;
+        fp.corpus = ix->corpus->d_rows;
+        fp.n_rows = ix->n_rows;
+        fp.queries = d_q_given;
+        fp.pool = ap.lists;
+        fp.P = nprobe * n_seg * pool_slots;
+        fp.top_k = top_k;
+        fp.kg = top_k + std::max<uint32_t>(64, top_k / 16);
+        fp.row_base = row_base;
+        fp.out_rows = d_or;
+        fp.out_dist = d_od;
+        fp.out_counts = d_oc;
+        fp.out_stride = out_stride ? out_stride : top_k;
+        fp.status = ctx->d_status;
+        prof_begin(ctx, "ivf_finish");
+        hipLaunchKernelGGL(ivf_pool_finish_kernel, dim3(nq), dim3(PF_THREADS), 0, ctx->stream, fp);
+        prof_end(ctx, "ivf_finish");
+        IVF_HIP(hipGetLastError());
+        if (d_or_out) *d_or_out = d_or;
+        if (out_bytes_contig) *out_bytes_contig = b_or + b_od + (size_t)nq * 8;
+        return SMT_OK;
+    }
     SelectArgs sel;  // no exactness certificate: the index is approximate by contract (f32_err = 0)
     sel.corpus = ix->corpus->d_rows;
     sel.queries = d_q_given;
@@ -746,13 +700,68 @@ static int ivfpq_search_core(smt_ivfpq *ix, const float *queries, bool queries_o
     return SMT_OK;
 }
 
-// the host form of the search, with or without ranges (n_ranges == 0: without)
+// The wide host form, 57 <= top_k <= LARGEK_MAX_K: rounds of queries under the pool's byte budget, each round's answer copied home
+// and waited for (no delivery by a kernel: nothing here is latency-bound at these sizes).
+static int ivfpq_search_host_wide(smt_ivfpq *ix, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
+                                  const smt_range *ranges, uint32_t n_ranges, bool filtered, uint64_t row_base, uint64_t *out_rows,
+                                  double *out_dist, uint64_t *out_counts, uint64_t out_cap)
+{
+    if (int rcr = smt::validate_ranges(ranges, n_ranges, ix->corpus->rows)) return rcr;
+    SMT_REQUIRE(nprobe >= 1 && nprobe <= ix->nlist && nprobe <= 512, "nprobe must be in [1, min(nlist, 512)]");
+    SMT_REQUIRE(rerank == 0 || (rerank >= 4 && rerank <= 512), "rerank (full-precision re-scored ADC candidates per probed list) must be in [4, 512]");
+    smt_ctx *ctx = ix->corpus->ctx;
+    IVF_HIP(hipSetDevice(ctx->device));
+    { int rc_drain = smt::drain_async(ctx); if (rc_drain) return rc_drain; }
+    if (nq == 0) return SMT_OK;
+    for (uint32_t q = 0; q < nq; ++q) out_counts[q] = 0;
+    if (int rcq = smt::require_queries_domain_host(queries, nq, "smt_ivfpq_search_wide")) return rcq;   // (domain.hip)
+    const AdcPlan plan = adc_plan(ix, nprobe, rerank ? rerank : 512);
+    const size_t pool_per_query = (size_t)nprobe * plan.n_seg * plan.adc_waves * 64 * sizeof(key_t64);
+    const uint32_t nq_round = (uint32_t)std::min<size_t>(nq, std::max<size_t>(1, IVF_POOL_BUDGET / pool_per_query));
+    const size_t b_or = (size_t)nq_round * top_k * 8;
+    int rc = smt::ensure_pinned(ctx, 2 * b_or + (size_t)nq_round * 8);
+    if (rc) return rc;
+    char *h_ans = reinterpret_cast<char *>(ctx->h_pinned);
+    bool truncated = false;
+    for (uint32_t q0 = 0; q0 < nq; q0 += nq_round) {
+        const uint32_t nqr = std::min(nq_round, nq - q0);
+        uint64_t *d_or = nullptr;
+        size_t out_bytes = 0;
+        rc = ivfpq_search_core(ix, queries + (size_t)q0 * 256, false, nqr, top_k, nprobe, rerank, ranges, n_ranges, filtered, row_base, nullptr,
+                               nullptr, nullptr, &d_or, &out_bytes, 0, nullptr, true);
+        if (rc) return rc;
+        IVF_HIP(hipMemcpyAsync(h_ans, d_or, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        IVF_HIP(hipStreamSynchronize(ctx->stream));
+        const size_t b_r = (size_t)nqr * top_k * 8;   // [rows | distances | counts] of this round
+        const uint64_t *h_rows = reinterpret_cast<const uint64_t *>(h_ans);
+        const double *h_dist = reinterpret_cast<const double *>(h_ans + b_r);
+        const uint64_t *h_cnt = reinterpret_cast<const uint64_t *>(h_ans + 2 * b_r);
+        for (uint32_t q = 0; q < nqr; ++q) {
+            out_counts[q0 + q] = h_cnt[q];
+            const uint64_t w = std::min<uint64_t>(h_cnt[q], out_cap);
+            if (h_cnt[q] > out_cap) truncated = true;
+            for (uint64_t i = 0; i < w; ++i) {
+                out_rows[(size_t)(q0 + q) * out_cap + i] = h_rows[(size_t)q * top_k + i];
+                out_dist[(size_t)(q0 + q) * out_cap + i] = h_dist[(size_t)q * top_k + i];
+            }
+        }
+    }
+    if (truncated) { smt::set_error("out_cap smaller than the number of hits"); return SMT_E_TRUNCATED; }
+    return SMT_OK;
+}
+
+// the host form of the search, with or without ranges (`filtered`); `wide`: top_k up to LARGEK_MAX_K (57 and above through the pool)
 static int ivfpq_search_host(smt_ivfpq *ix, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
-                             const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, uint64_t *out_rows, double *out_dist,
-                             uint64_t *out_counts, uint64_t out_cap)
+                             const smt_range *ranges, uint32_t n_ranges, bool filtered, uint64_t row_base, uint64_t *out_rows,
+                             double *out_dist, uint64_t *out_counts, uint64_t out_cap, bool wide = false)
 {
     SMT_REQUIRE(ix != nullptr, "index");
     SMT_REQUIRE(nq == 0 || (queries && out_rows && out_dist && out_counts), "null argument");
+    SMT_REQUIRE(!wide || top_k <= LARGEK_MAX_K, "top_k must be <= 1024 for the wide IVF-PQ path");
+    SMT_REQUIRE(n_ranges == 0 || ranges != nullptr, "ranges");
+    if (wide && top_k > SCAN_MAX_K)
+        return ivfpq_search_host_wide(ix, queries, nq, top_k, nprobe, rerank, ranges, n_ranges, filtered, row_base, out_rows, out_dist,
+                                      out_counts, out_cap);
     if (int rcr = smt::validate_ranges(ranges, n_ranges, ix->corpus->rows)) return rcr;
     smt_ctx *ctx = ix->corpus->ctx;
     IVF_HIP(hipSetDevice(ctx->device));
@@ -778,7 +787,7 @@ static int ivfpq_search_host(smt_ivfpq *ix, const float *queries, uint32_t nq, u
         dl.done = ctx->d_status + 4;
         *flag = 0;
     }
-    rc = ivfpq_search_core(ix, queries, false, nq, top_k, nprobe, rerank, ranges, n_ranges, n_ranges != 0, row_base, nullptr, nullptr,
+    rc = ivfpq_search_core(ix, queries, false, nq, top_k, nprobe, rerank, ranges, n_ranges, filtered, row_base, nullptr, nullptr,
                            nullptr, &d_or, &out_bytes, 0, direct ? &dl : nullptr);
     if (rc) return rc;
     if (direct) {
@@ -821,44 +830,63 @@ static int ivfpq_search_host(smt_ivfpq *ix, const float *queries, uint32_t nq, u
 }
 
 static int ivfpq_search_dev(smt_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
-                            const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, uint64_t *out_rows_dev, double *out_dist_dev)
+                            const smt_range *ranges, uint32_t n_ranges, bool filtered, uint64_t row_base, uint64_t *out_rows_dev,
+                            double *out_dist_dev, bool wide = false)
 {
     SMT_REQUIRE(ix != nullptr, "index");
     SMT_REQUIRE(nq == 0 || (queries_dev && out_rows_dev && out_dist_dev), "null argument");
     SMT_REQUIRE(top_k >= 1, "top_k");
+    SMT_REQUIRE(!wide || top_k <= LARGEK_MAX_K, "top_k must be <= 1024 for the wide IVF-PQ path");
+    SMT_REQUIRE(n_ranges == 0 || ranges != nullptr, "ranges");
     if (int rcr = smt::validate_ranges(ranges, n_ranges, ix->corpus->rows)) return rcr;
     smt_ctx *ctx = ix->corpus->ctx;
     IVF_HIP(hipSetDevice(ctx->device));
     { int rc_drain = smt::drain_async(ctx); if (rc_drain) return rc_drain; }
     if (nq == 0) return SMT_OK;
-    return ivfpq_search_core(ix, queries_dev, true, nq, top_k, nprobe, rerank, ranges, n_ranges, n_ranges != 0, row_base, out_rows_dev,
-                             out_dist_dev, nullptr, nullptr, nullptr);
+    return ivfpq_search_core(ix, queries_dev, true, nq, top_k, nprobe, rerank, ranges, n_ranges, filtered, row_base, out_rows_dev,
+                             out_dist_dev, nullptr, nullptr, nullptr, 0, nullptr, wide && top_k > SCAN_MAX_K);
 }
 
 int smt_ivfpq_search(smt_ivfpq *ix, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
                      uint64_t row_base, uint64_t *out_rows, double *out_dist, uint64_t *out_counts, uint64_t out_cap)
 try {
-    return ivfpq_search_host(ix, queries, nq, top_k, nprobe, rerank, nullptr, 0, row_base, out_rows, out_dist, out_counts, out_cap);
+    return ivfpq_search_host(ix, queries, nq, top_k, nprobe, rerank, nullptr, 0, false, row_base, out_rows, out_dist, out_counts, out_cap);
 } catch (...) { return smt::api_catch(); }
 
 int smt_ivfpq_search_ranges(smt_ivfpq *ix, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
                             const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, uint64_t *out_rows, double *out_dist,
                             uint64_t *out_counts, uint64_t out_cap)
 try {
-    return ivfpq_search_host(ix, queries, nq, top_k, nprobe, rerank, ranges, n_ranges, row_base, out_rows, out_dist, out_counts, out_cap);
+    return ivfpq_search_host(ix, queries, nq, top_k, nprobe, rerank, ranges, n_ranges, n_ranges != 0, row_base, out_rows, out_dist, out_counts,
+                             out_cap);
 } catch (...) { return smt::api_catch(); }
 
 int smt_ivfpq_search_device(smt_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
                             uint64_t row_base, uint64_t *out_rows_dev, double *out_dist_dev)
 try {
-    return ivfpq_search_dev(ix, queries_dev, nq, top_k, nprobe, rerank, nullptr, 0, row_base, out_rows_dev, out_dist_dev);
+    return ivfpq_search_dev(ix, queries_dev, nq, top_k, nprobe, rerank, nullptr, 0, false, row_base, out_rows_dev, out_dist_dev);
 } catch (...) { return smt::api_catch(); }
 
 int smt_ivfpq_search_ranges_device(smt_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
                                    const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, uint64_t *out_rows_dev,
                                    double *out_dist_dev)
 try {
-    return ivfpq_search_dev(ix, queries_dev, nq, top_k, nprobe, rerank, ranges, n_ranges, row_base, out_rows_dev, out_dist_dev);
+    return ivfpq_search_dev(ix, queries_dev, nq, top_k, nprobe, rerank, ranges, n_ranges, n_ranges != 0, row_base, out_rows_dev, out_dist_dev);
+} catch (...) { return smt::api_catch(); }
+
+int smt_ivfpq_search_wide(smt_ivfpq *ix, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
+                          const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, uint64_t *out_rows, double *out_dist,
+                          uint64_t *out_counts, uint64_t out_cap)
+try {
+    return ivfpq_search_host(ix, queries, nq, top_k, nprobe, rerank, ranges, ranges ? n_ranges : 0, ranges != nullptr, row_base, out_rows,
+                             out_dist, out_counts, out_cap, true);
+} catch (...) { return smt::api_catch(); }
+
+int smt_ivfpq_search_wide_device(smt_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
+                                 const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, uint64_t *out_rows_dev, double *out_dist_dev)
+try {
+    return ivfpq_search_dev(ix, queries_dev, nq, top_k, nprobe, rerank, ranges, ranges ? n_ranges : 0, ranges != nullptr, row_base,
+                            out_rows_dev, out_dist_dev, true);
 } catch (...) { return smt::api_catch(); }
 
 }  // extern "C"
@@ -867,12 +895,14 @@ try {
 // (`filtered` apart from the count, as in search_topk_packed_local: a shard that the caller's ranges leave nothing returns NOTHING;
 // ranges_local come out of layout_localize from ranges the caller validated)
 int smt::ivfpq_search_packed(smt_ivfpq *ix, const float *queries_dev, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
-                             const smt_range *ranges_local, uint32_t n_ranges, bool filtered, uint64_t row_base, uint64_t *packed_dev)
+                             const smt_range *ranges_local, uint32_t n_ranges, bool filtered, uint64_t row_base, uint64_t *packed_dev,
+                             bool wide)
 {
     SMT_REQUIRE(ix && queries_dev && packed_dev, "null argument");
     smt_ctx *ctx = ix->corpus->ctx;
     IVF_HIP(hipSetDevice(ctx->device));
     { int rc_drain = smt::drain_async(ctx); if (rc_drain) return rc_drain; }
     return ivfpq_search_core(ix, queries_dev, true, nq, top_k, nprobe, rerank, ranges_local, n_ranges, filtered, row_base, packed_dev,
-                             reinterpret_cast<double *>(packed_dev + top_k), nullptr, nullptr, nullptr, (uint64_t)2 * top_k);
+                             reinterpret_cast<double *>(packed_dev + top_k), nullptr, nullptr, nullptr, (uint64_t)2 * top_k, nullptr,
+                             wide && top_k > SCAN_MAX_K);
 }

@@ -5,6 +5,7 @@
 #include <new>
 
 #include "group.h"
+#include "ivfpq.h"
 
 using namespace smt;
 
@@ -54,16 +55,19 @@ static void unpack_packed_hits(const uint64_t *h, uint32_t nq, uint32_t k, std::
     }
 }
 
-// The sharded index search, over everything (n_ranges == 0) or inside GLOBAL row ranges: validated once, localised per rank; a rank
-// the ranges leave nothing still takes part and contributes an empty list.
+// The sharded index search, over everything (`filtered` off) or inside GLOBAL row ranges: validated once, localised per rank; a rank
+// the ranges leave nothing still takes part and contributes an empty list.  `wide`: top_k up to LARGEK_MAX_K -- every shard answers
+// 57 and above from its candidate pool (ivfpq_search.hip), and the exchange carries lists of that length as it does for
+// smt_sharded_search_topk_device_ex.  Every argument is checked before anything is enqueued.
 static int sharded_ivfpq_search_impl(smt_sharded_ivfpq *six, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe,
-                                     uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, const char *who, uint64_t *out_rows,
-                                     double *out_dist, uint64_t *out_counts, uint64_t out_cap)
+                                     uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, bool filtered, bool wide, const char *who,
+                                     uint64_t *out_rows, double *out_dist, uint64_t *out_counts, uint64_t out_cap)
 {
     SMT_REQUIRE(six != nullptr, "index");
     SMT_REQUIRE(nq == 0 || (queries && out_rows && out_dist && out_counts), "null argument");
     SMT_REQUIRE(n_ranges == 0 || ranges != nullptr, "ranges");
-    SMT_REQUIRE(top_k >= 1 && top_k <= SCAN_MAX_K, "top_k must be in [1, 56]");
+    if (wide) SMT_REQUIRE(top_k >= 1 && top_k <= LARGEK_MAX_K, "top_k must be in [1, 1024]");
+    else SMT_REQUIRE(top_k >= 1 && top_k <= SCAN_MAX_K, "top_k must be in [1, 56]");
     smt_sharded_corpus *sc = six->corpus;
     smt_group *g = sc->group;
     SMT_REQUIRE((uint64_t)g->n_ranks * top_k <= 8192, "device merge handles up to 8192 candidates per query");
@@ -71,10 +75,21 @@ static int sharded_ivfpq_search_impl(smt_sharded_ivfpq *six, const float *querie
     if (n_ranges && (rc = validate_ranges(ranges, n_ranges, sc->total()))) return rc;   // (before anything is enqueued)
     if (nq == 0) return SMT_OK;
     if (int rcq = require_queries_domain_host(queries, nq, who)) return rcq;   // (domain.hip; SPMD: all ranks alike)
-    if (g->n_ranks == 1)
+    if (wide) {   // (a shard would refuse these itself, but only after the first one's work was enqueued)
+        for (smt_ivfpq *ix : six->shard) {
+            SMT_REQUIRE(nprobe >= 1 && nprobe <= ix->nlist && nprobe <= 512, "nprobe must be in [1, min(nlist, 512)]");
+            IVF_REQUIRE_FRESH(ix);
+            SMT_REQUIRE(ix->corpus->rows >= ix->n_rows, "the corpus shrank after the index was built: rebuild");
+        }
+        SMT_REQUIRE(rerank == 0 || (rerank >= 4 && rerank <= 512), "rerank (full-precision re-scored ADC candidates per probed list) must be in [4, 512]");
+    }
+    if (g->n_ranks == 1) {
+        if (wide)
+            return smt_ivfpq_search_wide(six->shard[0], queries, nq, top_k, nprobe, rerank, ranges, n_ranges, 0, out_rows, out_dist, out_counts, out_cap);
         return n_ranges ? smt_ivfpq_search_ranges(six->shard[0], queries, nq, top_k, nprobe, rerank, ranges, n_ranges, 0, out_rows, out_dist,
                                                   out_counts, out_cap)
                         : smt_ivfpq_search(six->shard[0], queries, nq, top_k, nprobe, rerank, 0, out_rows, out_dist, out_counts, out_cap);
+    }
     const ExchangeLayout L(nq, top_k, 0, g->n_ranks, true, true);
     const size_t list_words = L.list_words;
     const bool peer = g->transport == SMT_TRANSPORT_PEER;
@@ -90,7 +105,7 @@ static int sharded_ivfpq_search_impl(smt_sharded_ivfpq *six, const float *querie
         std::vector<smt_range> lr;
         if (n_ranges) layout_localize(sc, r, ranges, n_ranges, lr);
         if ((rc = ivfpq_search_packed(six->shard[i], reinterpret_cast<const float *>(base), nq, top_k, nprobe, rerank, lr.data(),
-                                      (uint32_t)lr.size(), n_ranges != 0, sc->contiguous ? sc->rank_base[r] : 0, loc)))
+                                      (uint32_t)lr.size(), filtered, sc->contiguous ? sc->rank_base[r] : 0, loc, wide)))
             return rc;
         if (!sc->contiguous && (rc = layout_translate_packed(sc, i, g->ctx[i]->stream, loc, nq, top_k))) return rc;
         if (peer && (rc = peer_publish(g, i, g->ctx[i]->stream))) return rc;
@@ -379,16 +394,24 @@ smt_ivfpq *smt_sharded_ivfpq_shard(smt_sharded_ivfpq *six, int local_index)
 int smt_sharded_ivfpq_search(smt_sharded_ivfpq *six, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe, uint32_t rerank,
                              uint64_t *out_rows, double *out_dist, uint64_t *out_counts, uint64_t out_cap)
 try {
-    return sharded_ivfpq_search_impl(six, queries, nq, top_k, nprobe, rerank, nullptr, 0, "smt_sharded_ivfpq_search", out_rows, out_dist,
-                                     out_counts, out_cap);
+    return sharded_ivfpq_search_impl(six, queries, nq, top_k, nprobe, rerank, nullptr, 0, false, false, "smt_sharded_ivfpq_search", out_rows,
+                                     out_dist, out_counts, out_cap);
 } catch (...) { return smt::api_catch(); }
 
 int smt_sharded_ivfpq_search_ranges(smt_sharded_ivfpq *six, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe,
                                     uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, uint64_t *out_rows, double *out_dist,
                                     uint64_t *out_counts, uint64_t out_cap)
 try {
-    return sharded_ivfpq_search_impl(six, queries, nq, top_k, nprobe, rerank, ranges, n_ranges, "smt_sharded_ivfpq_search_ranges", out_rows,
-                                     out_dist, out_counts, out_cap);
+    return sharded_ivfpq_search_impl(six, queries, nq, top_k, nprobe, rerank, ranges, n_ranges, n_ranges != 0, false,
+                                     "smt_sharded_ivfpq_search_ranges", out_rows, out_dist, out_counts, out_cap);
+} catch (...) { return smt::api_catch(); }
+
+int smt_sharded_ivfpq_search_wide(smt_sharded_ivfpq *six, const float *queries, uint32_t nq, uint32_t top_k, uint32_t nprobe,
+                                  uint32_t rerank, const smt_range *ranges, uint32_t n_ranges, uint64_t *out_rows, double *out_dist,
+                                  uint64_t *out_counts, uint64_t out_cap)
+try {
+    return sharded_ivfpq_search_impl(six, queries, nq, top_k, nprobe, rerank, ranges, ranges ? n_ranges : 0, ranges != nullptr, true,
+                                     "smt_sharded_ivfpq_search_wide", out_rows, out_dist, out_counts, out_cap);
 } catch (...) { return smt::api_catch(); }
 
 }  // extern "C"

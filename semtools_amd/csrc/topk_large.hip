@@ -291,20 +291,6 @@ struct FinishParams {
     double err;                   // |collected key's distance - exact distance| bound: F32_ERR_SCAN, or the K3 sweep's nominating band
 };
 
-// ascending bitonic sort of n (a power of two) LDS entries, compare-exchange given as a functor on two indices
-template <typename CX>
-__device__ __forceinline__ void bitonic_sort(uint32_t n, CX cx)
-{
-    for (uint32_t size = 2; size <= n; size <<= 1)
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t i = threadIdx.x; i < n / 2; i += blockDim.x) {
-                const uint32_t lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-                cx(lo, hi, (lo & size) == 0);
-            }
-            __syncthreads();
-        }
-}
-
 __global__ void __launch_bounds__(LK_THREADS) largek_finish_kernel(FinishParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
