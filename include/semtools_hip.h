@@ -670,9 +670,10 @@ int smt_ctx_uncertain_count(smt_ctx *ctx, uint64_t *count, int reset);
 int smt_debug_range_sets(const smt_corpus *corpus, uint64_t *kept, uint64_t *hits, uint64_t *builds);
 
 /* Test hook for the fp16 operand image: brings the image up to date, as a batched search would, and copies the 16 KiB of 32-row
- * tile `tile` (and the tile's zero-row mask, bit r = tile row r packed as a zero row) to the host.  The tests compare the tile that
- * straddles the row count between corpora whose memory behind the rows differs: rows at or past the row count are packed as zero
- * rows, whatever lies there.  SMT_E_INVALID when the corpus has no image or the tile holds no row. */
+ * tile `tile` (and the tile's zero-row mask, bit r = tile row r packed as a zero row) to the host.  Rows at or past the row count are
+ * packed as zero rows, whatever lies there: tests/test_gpu_image_tile.py compares the tile that straddles the row count between
+ * corpora whose memory behind the rows differs, and every tile's content with a float64 reference.  SMT_E_INVALID when the corpus
+ * has no image or the tile holds no row. */
 int smt_debug_image_tile(smt_corpus *corpus, uint64_t tile, void *out_tile_host, uint32_t *out_zero_mask);
 
 /* Test hook for delivered answers (tuning key direct_delivery): how many host-form searches on this context got their answer written
@@ -709,6 +710,22 @@ int smt_debug_group_fail_next(smt_group *group, int where, int code);
  * These values never reach an answer: results carry exact (f64) distances. */
 int smt_debug_batched_scores(smt_corpus *corpus, const float *queries, uint32_t nq, uint64_t first_row, uint32_t n_rows,
                              float *out);
+
+/* Test hook for what the batched PRODUCTION kernels nominate (smt_debug_batched_scores above runs a 64-thread restatement of one
+ * of them).  Builds the launch arguments of a real batched top_k call of nq <= 64 host queries over the corpus -- optional row ranges
+ * as smt_search takes them, the operand image when the corpus has one -- and runs the kernel family the current tuning picks for that
+ * call (row-register, LDS-row or level kernel; bf16 x 3, f16 x 2, f16 x 1 or f32 MFMA) with the production query preparation, as ONE
+ * level over all tiles: for a filtered call the entries of its tile resp. chunk table.  tau [nq]: the distance threshold of each query
+ * (+inf admits every row); buffered != 0: row-register nominations go through the wave's LDS buffer.  At most 2048 rows may be scanned
+ * (the capacity of a candidate list): SMT_E_INVALID beyond that and beyond 64 queries.
+ *   out_dist   [rows of the corpus][nq] f32, preset to NaN: the distance bits of a nominated key, at the slot of the key's row
+ *   out_hits   [rows of the corpus][nq] how many keys named that (row, query) pair: a pair written twice shows here
+ *   out_counts [ceil(nq / 32) * 32] the raw nomination count per query, the padding queries of the last query tile included
+ *   out_route  family (0 row-register, 1 LDS-row, 2 level) | arithmetic << 4 (0 bf16 x 3, 1 f16 x 2, 2 f16 x 1, 3 f32 MFMA)
+ *              | 0x100 operands from the image | 0x200 range-filtered
+ * A key that names a row outside the corpus, or a counted slot that was never written, is SMT_E_INVALID. */
+int smt_debug_nominations(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                          const float *tau, int buffered, float *out_dist, uint32_t *out_hits, uint32_t *out_counts, uint32_t *out_route);
 
 /* The context's second stream (hipStream_t), created on first use: async selects run on it, or, with tuning key
  * scan_overlap, it waits for them (every select of an overlapped call enqueued before the work).  A host that

@@ -698,6 +698,20 @@ extern "C" {
         n_rows: u32,
         out: *mut f32,
     ) -> c_int;
+    pub fn smt_debug_nominations(
+        corpus: *mut SmtCorpus,
+        queries: *const f32,
+        nq: u32,
+        top_k: u32,
+        ranges: *const SmtRange,
+        n_ranges: u32,
+        tau: *const f32,
+        buffered: c_int,
+        out_dist: *mut f32,
+        out_hits: *mut u32,
+        out_counts: *mut u32,
+        out_route: *mut u32,
+    ) -> c_int;
     pub fn smt_ctx_aux_stream(ctx: *mut SmtCtx, stream_out: *mut *mut c_void) -> c_int;
     pub fn smt_set_tuning(ctx: *mut SmtCtx, key: *const c_char, value: i64) -> c_int;
     pub fn smt_fnv1a_hash(bytes: *const u8, n: u64) -> u64;

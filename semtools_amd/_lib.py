@@ -45,7 +45,7 @@ EXPORTS = [
     "smt_sharded_model_create_typed", "smt_sharded_model_create_from_file_typed", "smt_sharded_model_info",
     "smt_model_create_indexed", "smt_model_create_from_file_indexed", "smt_model_create_from_device_indexed", "smt_model_token_info",
     "smt_sharded_model_create_indexed", "smt_sharded_model_create_from_file_indexed", "smt_sharded_model_token_info",
-    "smt_debug_scan_pairs", "smt_debug_image_tile", "smt_debug_scan_groups",
+    "smt_debug_scan_pairs", "smt_debug_image_tile", "smt_debug_scan_groups", "smt_debug_nominations",
 ]
 TABLE_F32, TABLE_F16, TABLE_I8 = 0, 1, 2
 TABLE_DTYPES = {np.dtype(np.float32): TABLE_F32, np.dtype(np.float16): TABLE_F16, np.dtype(np.int8): TABLE_I8}
@@ -257,6 +257,7 @@ def lib():
         L.smt_debug_scan_pairs.argtypes = [vp, P(C.c_uint64), P(C.c_uint64), P(C.c_uint64)]
         L.smt_debug_image_tile.argtypes = [vp, u64, vp, P(C.c_uint32)]
         L.smt_debug_scan_groups.argtypes = [vp, P(C.c_uint64)]
+        L.smt_debug_nominations.argtypes = [vp, vp, u32, u32, vp, u32, vp, i32, vp, vp, vp, P(C.c_uint32)]
     except AttributeError:
         pass
     L.smt_sharded_corpus_append_to_file_ex.argtypes = [vp, C.c_char_p, u64, u64, i32]

@@ -332,6 +332,25 @@ class Corpus:
         L.check(L.lib().smt_debug_batched_scores(self._h, L.np_ptr(q), q.shape[0], int(first_row), n_rows, L.np_ptr(out)))
         return out[:, :q.shape[0]].copy()
 
+    def debug_nominations(self, queries, tau=None, buffered=False, ranges=None, top_k=10):
+        """Test hook (smt_debug_nominations): what the PRODUCTION kernels of a batched top_k call over this corpus nominate in one
+        level over all tiles, under the distance thresholds tau (one per query; None = +inf, admit everything).  Returns
+        (dist float32 [rows, nq], NaN where the pair was not nominated; hits uint32 [rows, nq], the keys that named the pair;
+        counts uint32 [ceil(nq / 32) * 32], raw per query, padding queries included; route, see the header)."""
+        q = _f32c(queries).reshape(-1, L.DIM)
+        nq = q.shape[0]
+        t = np.full(nq, np.inf, dtype=np.float32) if tau is None else np.ascontiguousarray(tau, dtype=np.float32).reshape(nq)
+        rng, n_rng = _ranges_arg(ranges)
+        rows = self.rows
+        dist = np.empty((rows, nq), dtype=np.float32)
+        hits = np.empty((rows, nq), dtype=np.uint32)
+        counts = np.empty((nq + 31) // 32 * 32, dtype=np.uint32)
+        route = C.c_uint32(0)
+        L.check(L.lib().smt_debug_nominations(self._h, L.np_ptr(q), nq, int(top_k), C.cast(rng, C.c_void_p) if rng is not None else None,
+                                              n_rng, L.np_ptr(t), int(bool(buffered)), L.np_ptr(dist), L.np_ptr(hits), L.np_ptr(counts),
+                                              C.byref(route)))
+        return dist, hits, counts, int(route.value)
+
     def search(self, queries, top_k=3, max_distance=None, mode=L.MODE_DOCUMENTS, ranges=None, row_base=0,
                out_cap=None):
         """Returns a list (one per query) of (rows uint64[n], dist float64[n]).

@@ -562,6 +562,10 @@ int launch_gemm_threshold(smt_ctx *ctx, const float *corpus, uint64_t rows, cons
                           const float *queries, uint32_t nq, const float *tau, const key_t64 **cand_out,
                           const unsigned int **counts_out, uint32_t *cand_stride, uint32_t cap = 2048 /* CAND_CAP */,
                           key_t64 *cand_ext = nullptr, unsigned int *counts_ext = nullptr);
+// test hook: what the production kernels of a batched call's route nominate in ONE level over all tiles, under the caller's
+// thresholds (gemm_topk.hip): keys [ceil(nq / 32) * 32][2048] and raw counts in scratch, padding queries included
+int launch_gemm_debug_nominations(smt_ctx *ctx, const ScanArgs &a, const float *tau_dev, int buffered, const key_t64 **cand_out,
+                                  const unsigned int **counts_out, uint32_t *route_out);
 // test hook: the nominating f32 distances of the K3 kernels for <= 32 queries (gemm_topk.hip)
 int launch_gemm_debug_scores(smt_ctx *ctx, const float *corpus, uint64_t first_row, uint32_t n_rows, const float *queries,
                              uint32_t nq, float *out);

@@ -85,10 +85,16 @@ __device__ __forceinline__ void append_candidates(const f32x16 &acc, unsigned ze
 // cost 5 % of a 1000 x 10 M batch).  The bound is lowered by two ulps: a borderline row is admitted rather
 // than lost (candidates are nominations; the final distances are exact).  Zero query (rq == 0): every
 // distance is 1 (0 against a zero row), the slot then carries tau itself.
+// The certificate reads the threshold in the DISTANCE domain: every row that was not nominated has a nominating distance
+// d = fl(1 - fl(acc * rq)) >= tau.  d can round DOWN onto tau (or below) while 1 - acc * rq lies up to half an ulp of tau above it --
+// more than the two relative ulps of the score give when |1 - tau| is small (cosines near 0: tau ~ 1, 1 - tau ~ 0.1, two ulps of
+// that are 2.4e-8 against ulp(tau) / 2 = 3e-8) -- so the bar is first lowered by 2^-23 tau >= ulp(tau) / 2 in the distance domain.
+// tests/test_gpu_nominations.py: under a threshold that IS one of the all-pass distances (what level_select_kernel publishes) every
+// pair at or below it is nominated, none more than 4 ulp(tau) above it.
 __device__ __forceinline__ float score_threshold(float tau, float rq)
 {
     if (rq == 0.0f) return tau;
-    const float t = (1.0f - tau) / rq;  // tau = +inf (first level) -> -inf: everything passes
+    const float t = ((1.0f - tau) - 1.2e-7f * tau) / rq;  // tau = +inf (first level) -> -inf: everything passes
     return t - fabsf(t) * 2.4e-7f;
 }
 

@@ -130,8 +130,10 @@ __device__ __forceinline__ void flush_candidates_lds(int lane, const unsigned ch
 
 // THE CORPUS' fp16 OPERAND IMAGE (smt_corpus::image, api.cpp): per 32-row tile the sixteen operand quads gemm_rowreg_kernel's fp16
 // modes build in their row phase -- unit row x 2^10, fp16, quad (K-step m, lane l = 32 h + j) at 16 (64 m + l) bytes of the
-// tile's 16 KiB -- written ONCE per row by this kernel with the same arithmetic in the same order (the tests compare the
-// nominations of both forms bit for bit), plus the tile's zero-row mask.  One wave per tile.
+// tile's 16 KiB -- written ONCE per row by this kernel with the same arithmetic in the same order, plus the tile's zero-row mask: bit r
+// <=> tile row r is a zero row; rows at or past n_rows are zero rows.  One wave per tile.  tests/test_gpu_nominations.py compares the
+// nominations of both forms bit for bit (f16 x 2 and f16 x 1, from the image and from the f32 rows); tests/test_gpu_image_tile.py
+// reads every tile back and holds its values, mask bits and zero quads against a float64 reference (tests/nominate_ref.py).
 __global__ void __launch_bounds__(256) pack_image_kernel(const float *corpus, uint64_t n_rows, uint64_t first_tile, uint64_t n_tiles,
                                                          uint32_t *image, uint32_t *image_zero)
 {

@@ -266,7 +266,9 @@ __global__ void fill_f32_kernel(float *p, float v, uint32_t n)
 
 // ---- test hook: the NOMINATING distances themselves (never part of an answer).  One wave per 32-row tile against one
 // tile of <= 32 queries, the same operand preparation and MFMA sequence as gemm_level_kernel; out[row][32] = the f32
-// distance the candidate test sees.  tests/test_gpu_batched.py measures |out - exact| against F32_ERR_MFMA / _BF16X3.
+// distance the candidate test sees.  tests/test_gpu_batched.py measures |out - exact| against F32_ERR_MFMA / _BF16X3; a RESTATEMENT,
+// not a production kernel: tests/test_gpu_nominations.py holds gemm_level_kernel's own nominations against it bit for bit (MODE 0
+// and 1) and measures every production family through launch_gemm_debug_nominations below.
 template <int MODE>   // 0 f32 MFMA, 1 bf16 x 3, 2 f16 x 2, 3 f16 x 1
 __global__ void __launch_bounds__(64) gemm_debug_scores_kernel(const float *corpus, uint64_t first_row, uint32_t n_rows,
                                                                const float *queries, uint32_t nq, float *out)
@@ -279,7 +281,7 @@ __global__ void __launch_bounds__(64) gemm_debug_scores_kernel(const float *corp
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    float rpart = 0.0f, qpart = 0.0f;
+    float rpart = 0.0f;
     f32x4 R[32], Q[32];
     // f32: lane (j, h) feeds dims 8m + 4h .. + 3 of group m; bf16: dims 16m + 8h .. + 7 of K-step m
 #pragma unroll
@@ -288,9 +290,18 @@ __global__ void __launch_bounds__(64) gemm_debug_scores_kernel(const float *corp
         R[m] = row_ok ? rsrc[idx] : (f32x4){0.f, 0.f, 0.f, 0.f};
         Q[m] = (uint32_t)j < nq ? qsrc[idx] : (f32x4){0.f, 0.f, 0.f, 0.f};
         rpart += R[m].x * R[m].x + R[m].y * R[m].y + R[m].z * R[m].z + R[m].w * R[m].w;
-        qpart += Q[m].x * Q[m].x + Q[m].y * Q[m].y + Q[m].z * Q[m].z + Q[m].w * Q[m].w;
     }
-    const float r2 = rpart + __shfl_xor(rpart, 32), q2 = qpart + __shfl_xor(qpart, 32);
+    // |q|^2 as the production kernels form it (gemm_level_kernel's prologue, query_consts_kernel, split_queries_f16*_kernel): one
+    // query per wave-wide sum over lane-contiguous float4.  Until the nominations of gemm_level_kernel were compared with this
+    // kernel bit for bit (tests/test_gpu_nominations.py) the sum ran over the lane's K-permuted operand quads instead: another
+    // order, 1/|q| off by an ulp or two for some queries, about 1 % of the distances off in their last bits.
+    float q2 = 0.0f;
+    for (uint32_t q = 0; q < nq; ++q) {   // wave-uniform
+        const f32x4 v = reinterpret_cast<const f32x4 *>(queries + (size_t)q * 256)[lane];
+        const float a2 = wave_sum(v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w);
+        if ((uint32_t)j == q) q2 = a2;
+    }
+    const float r2 = rpart + __shfl_xor(rpart, 32);
     const float rb = r2 == 0.0f ? 0.0f : __frsqrt_rn(r2);
     float rq = q2 == 0.0f ? 0.0f : __frsqrt_rn(q2);
     if constexpr (MODE >= 2) {
@@ -359,13 +370,16 @@ static int ensure_gemm_attrs(smt_ctx *ctx)
     return SMT_OK;
 }
 
-int launch_gemm_topk(smt_ctx *ctx, const ScanArgs &a)
+// Which kernel family answers a batched call and how it nominates: ONE decision, taken here for launch_gemm_topk and for the test hook
+// that returns the production kernels' nominations (launch_gemm_debug_nominations), so that the hook cannot drift from production.
+struct GemmRoute {
+    bool filtered, rowreg, f16x1, f16x2, use_image, lds_rows;
+    uint32_t nqt, kp;
+};
+static GemmRoute gemm_route(const smt_ctx *ctx, const ScanArgs &a)
 {
-    if (a.k_out + 8 > 64 || a.k_out < 1) { set_error("batched path: top_k must be in [1, 56]"); return SMT_E_UNSUPPORTED; }
-    SMT_REQUIRE(a.rows < 0xFFFFFFFFull, "a shard holds fewer than 2^32-1 rows");
     const bool filtered = a.n_ranges != 0;
     const uint32_t nqt = (a.nq + QT_ROWS - 1) / QT_ROWS;
-    const uint64_t ostride = a.out_stride ? a.out_stride : a.k_out;
     // Which kernel (measured on MI355X, 10 M rows, ms per batch: LDS-row kernel / gemm_level_kernel):
     //   8..32 queries 1.84 / 3.1;  64 queries 3.05 / 3.24;  96 queries 4.96 (two passes) / 4.32;  128: 6.04 / 5.48.
     // So: up to 64 queries, and every range-filtered batch (in passes of 64), take the LDS-row kernel; larger batches
@@ -411,6 +425,45 @@ int launch_gemm_topk(smt_ctx *ctx, const ScanArgs &a)
     // (the proof needs the k-th exact distance to lie 2 x the band below the worst nominated one): 8 / 16 / 24
     const uint32_t kp = std::min<uint32_t>(64, a.k_out + (uint32_t)std::max(ctx->tune.guard_band, f16x1 ? 24 : f16x2 ? 16 : 8));
     const bool lds_rows = !rowreg && ctx->tune.gemm_ldsrow && (filtered || nqt <= 2);
+    return GemmRoute{filtered, rowreg, f16x1, f16x2, use_image, lds_rows, nqt, kp};
+}
+
+// The head of a batch, as every level launch expects it: the split image of the queries in the form the route's kernels read, and the
+// per-query state -- score thresholds and 1/|q| (row-register kernels), nomination counts and overflow flags 0, tau +inf.  Shared by
+// launch_gemm_topk and the test hook below.  head.counts / head.overflow lie b_cnt bytes apart ([nq] words each).
+static int gemm_prepare_queries(smt_ctx *ctx, const GemmRoute &r, const ScanArgs &a, uint32_t *q_split, const BatchHead &head, size_t b_cnt)
+{
+    const uint32_t nqt = r.nqt;
+    const bool bf16 = ctx->tune.gemm_bf16x3 != 0;
+    if (r.f16x1)
+        hipLaunchKernelGGL(split_queries_f16x1_kernel, dim3(nqt * QT_ROWS / 4), dim3(256), 0, ctx->stream, a.queries, a.nq,
+                           nqt * QT_ROWS, q_split, head);
+    else if (r.f16x2)
+        hipLaunchKernelGGL(split_queries_f16_kernel, dim3(nqt * QT_ROWS / 4), dim3(256), 0, ctx->stream, a.queries, a.nq,
+                           nqt * QT_ROWS, q_split, head);
+    else if (bf16)
+        hipLaunchKernelGGL(split_queries_kernel, dim3(nqt * QT_ROWS / 2), dim3(256), 0, ctx->stream, a.queries, a.nq,
+                           nqt * QT_ROWS, q_split);
+    if (r.rowreg && !(r.f16x1 || r.f16x2))   // bf16 x 3: its split kernel has no wave per query
+        hipLaunchKernelGGL(query_consts_kernel, dim3(nqt * QT_ROWS / 4), dim3(256), 0, ctx->stream, a.queries, a.nq,
+                           nqt * QT_ROWS, head.qconst, 0, head.counts, head.overflow, head.tau, head.fill, head.n_fill);
+    if (!r.rowreg) {
+        SMT_HIP_CHECK(hipMemsetAsync(head.counts, 0, 2 * b_cnt, ctx->stream));
+        hipLaunchKernelGGL(fill_f32_kernel, dim3((nqt * QT_ROWS + 255) / 256), dim3(256), 0, ctx->stream, head.tau,
+                           __builtin_inff(), nqt * QT_ROWS);
+    }
+    return SMT_OK;
+}
+
+int launch_gemm_topk(smt_ctx *ctx, const ScanArgs &a)
+{
+    if (a.k_out + 8 > 64 || a.k_out < 1) { set_error("batched path: top_k must be in [1, 56]"); return SMT_E_UNSUPPORTED; }
+    SMT_REQUIRE(a.rows < 0xFFFFFFFFull, "a shard holds fewer than 2^32-1 rows");
+    const GemmRoute route = gemm_route(ctx, a);
+    const bool filtered = route.filtered, rowreg = route.rowreg, f16x1 = route.f16x1, f16x2 = route.f16x2, use_image = route.use_image;
+    const bool lds_rows = route.lds_rows;
+    const uint32_t nqt = route.nqt, kp = route.kp;
+    const uint64_t ostride = a.out_stride ? a.out_stride : a.k_out;
     if (filtered && !lds_rows && !rowreg) { set_error("range-filtered batches need the row-register or the LDS-row kernel (tuning keys gemm_rowreg, gemm_ldsrow)"); return SMT_E_UNSUPPORTED; }
     const uint32_t pass_nq = lds_rows ? 2 * QT_ROWS : GEMM_MAX_NQ;
     if (a.nq > pass_nq) {
@@ -480,28 +533,12 @@ int launch_gemm_topk(smt_ctx *ctx, const ScanArgs &a)
         head.fill = tile_min;
         head.n_fill = (uint32_t)(boot_slots * nqt * QT_ROWS);
     }
-    if (f16x1)
-        hipLaunchKernelGGL(split_queries_f16x1_kernel, dim3(nqt * QT_ROWS / 4), dim3(256), 0, ctx->stream, a.queries, a.nq,
-                           nqt * QT_ROWS, q_split, head);
-    else if (f16x2)
-        hipLaunchKernelGGL(split_queries_f16_kernel, dim3(nqt * QT_ROWS / 4), dim3(256), 0, ctx->stream, a.queries, a.nq,
-                           nqt * QT_ROWS, q_split, head);
-    else if (bf16)
-        hipLaunchKernelGGL(split_queries_kernel, dim3(nqt * QT_ROWS / 2), dim3(256), 0, ctx->stream, a.queries, a.nq,
-                           nqt * QT_ROWS, q_split);
-    if (rowreg && !(f16x1 || f16x2))   // bf16 x 3: its split kernel has no wave per query
-        hipLaunchKernelGGL(query_consts_kernel, dim3(nqt * QT_ROWS / 4), dim3(256), 0, ctx->stream, a.queries, a.nq,
-                           nqt * QT_ROWS, qconst, 0, counts, overflow, tau, head.fill, head.n_fill);
+    if ((rc = gemm_prepare_queries(ctx, route, a, q_split, head, b_cnt))) return rc;
     // (the table of a KEPT range set -- search.cpp -- is built the first time a call needs it and then only read)
     const uint64_t *use_table = chunk_table;
     if (filtered && rowreg) {
         if ((rc = range_tile_table(ctx, a, chunk_table, &use_table))) return rc;
     } else if (filtered && (rc = range_chunk_table(ctx, a, chunk_table, &use_table))) return rc;
-    if (!rowreg) {
-        SMT_HIP_CHECK(hipMemsetAsync(counts, 0, 2 * b_cnt, ctx->stream));
-        hipLaunchKernelGGL(fill_f32_kernel, dim3((nqt * QT_ROWS + 255) / 256), dim3(256), 0, ctx->stream, tau,
-                           __builtin_inff(), nqt * QT_ROWS);
-    }
 
     // LEVEL PLAN.  A level = every stride-th tile that no coarser level has visited (`skip` = the ratio to the coarser level: the
     // multiples of it are left out; 0 = none left out), appended under the thresholds the levels before it produced.
@@ -791,6 +828,96 @@ int launch_gemm_threshold(smt_ctx *ctx, const float *corpus, uint64_t rows, cons
     *cand_out = cand;
     *counts_out = counts;
     *cand_stride = cap;
+    return SMT_OK;
+}
+
+// ---- test hook: what the PRODUCTION kernels nominate.  The route of a real batched call (gemm_route), its query preparation
+// (gemm_prepare_queries), then ONE level over all tiles -- for a range-filtered call the entries of the tile resp. chunk table -- with
+// the caller's distance threshold per query (tau_dev [nq], +inf = admit everything) in place of the level plan's.  The lists hold up to
+// CAND_CAP keys per query, so a.n_virtual <= CAND_CAP rows may be scanned; they and the counts cover the PADDING queries of the last
+// query tile too (nothing may ever land there), preset to KEY_PAD resp. 0.  route_out: family (0 row-register, 1 LDS-row, 2 level)
+// | arithmetic << 4 (0 bf16 x 3, 1 f16 x 2, 2 f16 x 1, 3 f32 MFMA) | 0x100 from the operand image | 0x200 range-filtered.
+// The buffers live in the context's scratch until the next launch.
+int launch_gemm_debug_nominations(smt_ctx *ctx, const ScanArgs &a, const float *tau_dev, int buffered, const key_t64 **cand_out,
+                                  const unsigned int **counts_out, uint32_t *route_out)
+{
+    SMT_REQUIRE(a.nq >= 1 && a.nq <= 2 * QT_ROWS, "debug nominations: 1..64 queries");
+    SMT_REQUIRE(a.n_virtual >= 1 && a.n_virtual <= CAND_CAP, "debug nominations: 1..2048 scanned rows (the capacity of a candidate list)");
+    SMT_REQUIRE(a.k_out >= 1 && a.k_out + 8 <= 64, "debug nominations: top_k must be in [1, 56]");
+    const GemmRoute r = gemm_route(ctx, a);
+    if (r.filtered && !r.lds_rows && !r.rowreg) { set_error("range-filtered batches need the row-register or the LDS-row kernel (tuning keys gemm_rowreg, gemm_ldsrow)"); return SMT_E_UNSUPPORTED; }
+    if (int rc_attr = ensure_gemm_attrs(ctx)) return rc_attr;
+    const bool bf16 = ctx->tune.gemm_bf16x3 != 0;
+    const uint32_t nqt = r.nqt, nq_pad = nqt * QT_ROWS;
+    const uint64_t n_table = !r.filtered ? 0 : r.rowreg ? a.n_vtiles : a.n_chunks;
+    const uint64_t n_tiles = !r.filtered ? (a.rows + 31) / 32 : r.rowreg ? n_table : (n_table + 7) / 8;
+    // scratch: cand [nq_pad][CAP] | counts [nq_pad] | overflow [nq_pad] | tau [nq_pad] | qconst [nq_pad][2] | split queries | table
+    const size_t b_cand = (size_t)nq_pad * CAND_CAP * sizeof(key_t64);
+    const size_t b_cnt = (size_t)nq_pad * 4;
+    const size_t o_split = (b_cand + 2 * b_cnt + 3 * (size_t)nq_pad * 4 + 255) & ~(size_t)255;
+    const size_t o_table = o_split + (size_t)nq_pad * 1024;
+    int rc = ensure_scratch(ctx, o_table + (size_t)n_table * sizeof(uint64_t) + 64);
+    if (rc) return rc;
+    char *base = reinterpret_cast<char *>(ctx->d_scratch);
+    key_t64 *cand = reinterpret_cast<key_t64 *>(base);
+    unsigned int *counts = reinterpret_cast<unsigned int *>(base + b_cand);
+    unsigned int *overflow = reinterpret_cast<unsigned int *>(base + b_cand + b_cnt);
+    float *tau = reinterpret_cast<float *>(base + b_cand + 2 * b_cnt);
+    float *qconst = tau + nq_pad;
+    uint32_t *q_split = reinterpret_cast<uint32_t *>(base + o_split);
+    uint64_t *table = reinterpret_cast<uint64_t *>(base + o_table);
+    SMT_HIP_CHECK(hipMemsetAsync(cand, 0xFF, b_cand, ctx->stream));
+    SMT_HIP_CHECK(hipMemsetAsync(counts, 0, 2 * b_cnt, ctx->stream));
+    const BatchHead head{qconst, counts, overflow, tau};
+    if ((rc = gemm_prepare_queries(ctx, r, a, q_split, head, b_cnt))) return rc;
+    // the caller's thresholds: the f32 / LDS-row / level kernels read tau, the row-register kernels its score-domain form
+    SMT_HIP_CHECK(hipMemcpyAsync(tau, tau_dev, (size_t)a.nq * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    if (r.rowreg) hipLaunchKernelGGL(set_qconst_thresholds_kernel, dim3(1), dim3(256), 0, ctx->stream, qconst, tau, a.nq);
+    const uint64_t *use_table = table;
+    if (r.filtered && r.rowreg) {
+        if ((rc = range_tile_table(ctx, a, table, &use_table))) return rc;
+    } else if (r.filtered && (rc = range_chunk_table(ctx, a, table, &use_table))) return rc;
+    GemmParams g;
+    memset(&g, 0, sizeof(g));
+    g.corpus = a.corpus;
+    g.n_rows = a.rows;
+    g.queries = a.queries;
+    g.queries_split = bf16 ? q_split : nullptr;
+    g.nq = a.nq;
+    g.nqt = nqt;
+    g.level_tiles = n_tiles;
+    g.tile_begin = 0;
+    g.stride = 1;
+    g.skip16 = 0;
+    g.qsplit = 1;
+    g.tau = tau;
+    g.qconst = qconst;
+    g.cand = cand;
+    g.counts = counts;
+    g.cand_cap = CAND_CAP;
+    g.chunk_table = r.filtered && !r.rowreg ? use_table : nullptr;
+    g.tile_table = r.filtered && r.rowreg ? use_table : nullptr;
+    g.n_chunks = n_table;
+    g.buffered = buffered ? 1 : 0;
+    g.image = r.use_image ? a.image : nullptr;
+    g.image_zero = r.use_image ? a.image_zero : nullptr;
+    // blocks and the query split as launch_gemm_topk sizes them for a level of this many tiles
+    const int blocks = ctx->tune.gemm_blocks > 0 ? ctx->tune.gemm_blocks : ctx->num_cus;
+    const int waves = r.rowreg ? RR_WAVES : r.lds_rows ? LR_WAVES : GEMM_WAVES;
+    const uint64_t need_blocks = (n_tiles + waves - 1) / waves;
+    int nb = (int)std::min<uint64_t>((uint64_t)blocks, need_blocks);
+    if (!r.lds_rows && ctx->tune.gemm_qsplit && need_blocks < (uint64_t)blocks) {
+        g.qsplit = (uint32_t)std::min<uint64_t>(nqt, std::max<uint64_t>(1, (uint64_t)2 * blocks / need_blocks));
+        nb = (int)(need_blocks * g.qsplit);
+    }
+    if (r.rowreg) gemm_rowreg_launch(ctx, r.f16x1 ? 2 : r.f16x2 ? 1 : 0, r.use_image, nb, g);
+    else if (r.lds_rows) gemm_ldsrow_launch(ctx, bf16, nqt, r.filtered, ctx->tune.gemm_dma_nt != 0, nb, g);
+    else gemm_level_launch(ctx, bf16, nqt, nb, g);
+    SMT_HIP_CHECK(hipGetLastError());
+    *cand_out = cand;
+    *counts_out = counts;
+    *route_out = (r.rowreg ? 0u : r.lds_rows ? 1u : 2u) | ((r.f16x1 ? 2u : r.f16x2 ? 1u : bf16 ? 0u : 3u) << 4) | (r.use_image ? 0x100u : 0u) |
+                 (r.filtered ? 0x200u : 0u);
     return SMT_OK;
 }
 

@@ -964,6 +964,68 @@ try {
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
+int smt_debug_nominations(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                          const float *tau, int buffered, float *out_dist, uint32_t *out_hits, uint32_t *out_counts, uint32_t *out_route)
+try {
+    SMT_REQUIRE(corpus && queries && tau && out_dist && out_hits && out_counts && out_route, "null argument");
+    SMT_REQUIRE(n_ranges == 0 || ranges != nullptr, "ranges");
+    SMT_REQUIRE(nq >= 1 && nq <= 64, "debug nominations: 1..64 queries");
+    smt_ctx *ctx = corpus->ctx;
+    int rc = bind_device(ctx, true);
+    if (rc) return rc;
+    const uint32_t nq_pad = (nq + 31) / 32 * 32;
+    const uint64_t rows = corpus->rows;
+    for (uint64_t i = 0; i < rows * nq; ++i) { out_dist[i] = std::numeric_limits<float>::quiet_NaN(); out_hits[i] = 0; }
+    for (uint32_t q = 0; q < nq_pad; ++q) out_counts[q] = 0;
+    *out_route = 0;
+    // the ScanArgs of a real batched call over the whole corpus: ranges through the range plan, the operand image as topk_dispatch
+    RangePlan plan;
+    plan.n_virtual = rows;
+    if (n_ranges && (rc = range_plan_find(corpus, ranges, n_ranges, plan))) return rc;
+    SMT_REQUIRE(plan.n_virtual >= 1 && plan.n_virtual <= 2048, "debug nominations: 1..2048 scanned rows (the capacity of a candidate list)");
+    if ((rc = range_plan_finish(corpus, plan))) return rc;
+    const size_t q_bytes = (size_t)nq * SMT_DIM * sizeof(float), t_bytes = (size_t)nq_pad * sizeof(float);
+    if ((rc = ensure_stage(ctx, q_bytes + t_bytes + plan.table_bytes() + 64))) return rc;
+    char *stage = reinterpret_cast<char *>(ctx->d_stage);
+    SMT_HIP_CHECK(hipMemcpyAsync(stage, queries, q_bytes, hipMemcpyHostToDevice, ctx->stream));
+    SMT_HIP_CHECK(hipMemcpyAsync(stage + q_bytes, tau, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    plan.bind(stage + q_bytes + t_bytes);
+    if (plan.upload_bytes()) {
+        SMT_HIP_CHECK(hipMemcpyAsync(const_cast<smt_range *>(plan.d_r), plan.rr.data(), plan.r_bytes(), hipMemcpyHostToDevice, ctx->stream));
+        SMT_HIP_CHECK(hipMemcpyAsync(const_cast<uint64_t *>(plan.d_p), plan.prefixes.data(), plan.prefixes.size() * sizeof(uint64_t),
+                                     hipMemcpyHostToDevice, ctx->stream));
+    }
+    ScanArgs a = scan_args(corpus, reinterpret_cast<const float *>(stage), nq, top_k, 0);
+    plan.apply(a);
+    if (ctx->tune.gemm_bf16x3 && ctx->tune.gemm_rowreg && (a.n_ranges == 0 || tiles_dense(a.n_virtual, a.n_vtiles))) {
+        if ((rc = corpus_image_sync(corpus, a.nq, &a.image, &a.image_zero))) return rc;
+    }
+    const key_t64 *cand = nullptr;
+    const unsigned int *counts = nullptr;
+    if ((rc = launch_gemm_debug_nominations(ctx, a, reinterpret_cast<const float *>(stage + q_bytes), buffered, &cand, &counts, out_route)))
+        return rc;
+    std::vector<key_t64> keys((size_t)nq_pad * 2048);
+    SMT_HIP_CHECK(hipMemcpyAsync(keys.data(), cand, keys.size() * sizeof(key_t64), hipMemcpyDeviceToHost, ctx->stream));
+    SMT_HIP_CHECK(hipMemcpyAsync(out_counts, counts, (size_t)nq_pad * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (uint32_t q = 0; q < nq; ++q) {
+        SMT_REQUIRE(out_counts[q] <= 2048, "debug nominations: a query was nominated more often than rows were scanned");
+        for (uint32_t i = 0; i < out_counts[q]; ++i) {
+            const key_t64 key = keys[(size_t)q * 2048 + i];
+            const uint64_t row = key & 0xFFFFFFFFull;
+            if (row >= rows) {
+                set_error("debug nominations: slot %u of query %u names row %llu (the corpus has %llu; 4294967295 = a counted slot nobody wrote)",
+                          i, q, (unsigned long long)row, (unsigned long long)rows);
+                return SMT_E_INVALID;
+            }
+            const uint32_t bits = (uint32_t)(key >> 32);
+            memcpy(&out_dist[row * nq + q], &bits, sizeof(bits));
+            ++out_hits[row * nq + q];
+        }
+    }
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
 int smt_merge_topk(const uint64_t *rows, const double *dist, uint32_t n_lists, uint32_t nq, uint32_t k_in, uint32_t k_out,
                    uint64_t *out_rows, double *out_dist, uint64_t *out_counts)
 try {

@@ -9,6 +9,7 @@ import pytest
 from oracle import oracle as orc
 from tests import synth
 from tests.compare import assert_topk_tie_aware, reference_distances
+from tests.nominate_ref import worst_case_rows_bf16x3 as _worst_case_rows_bf16x3, worst_case_rows_f16x2 as _worst_case_rows_f16x2
 
 pytestmark = pytest.mark.gpu
 
@@ -259,56 +260,9 @@ def test_nominating_distance_error_is_inside_the_certificate_bound(gpu_ctx, nomi
     c.close()
 
 
-def _bf16_rne(x):
-    """f32 -> bf16 (round to nearest even) -> f32, as v_cvt_pk_bf16_f32 does"""
-    b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    b = (b + 0x7FFF + ((b >> 16) & 1)) & 0xFFFF0000
-    return b.astype(np.uint32).view(np.float32)
-
-
-def _worst_case_rows_f16x2(rng, n_rows):
-    """Unit rows whose elements x 2^10 sit EXACTLY on fp16 rounding midpoints, in two binades so that the row has unit norm
-    to within 2^-14: the kernel's normalisation then shifts every element off its midpoint in the SAME direction and all
-    256 roundings go the same way.  With a query of matching signs the rounding errors add up instead of cancelling:
-    |error| = sum |delta_i q_i| -- the situation F32_ERR_F16X2 = 2^-11 (+ accumulation) is the bound for."""
-    rows = np.zeros((n_rows, 256), dtype=np.float64)
-    for r in range(n_rows):
-        i = int(rng.integers(0, 4))
-        j = 3 * (2 * i + 1) + (0 if r % 2 else -1)          # (2j + 1) = 6 (2i + 1) -+ 1: the norm is off by 2^-14 only
-        a = 2.0 ** -3 * (1 + (2 * i + 1) * 2.0 ** -11)       # 48 elements just above 2^-3: midpoint of the fp16 grid after x 2^10
-        b = 2.0 ** -4 * (1 - (2 * j + 1) * 2.0 ** -12)       # 64 elements just below 2^-4
-        pos = rng.permutation(256)
-        sign = rng.choice([-1.0, 1.0], size=256)
-        rows[r, pos[:48]] = a * sign[pos[:48]]
-        rows[r, pos[48:112]] = b * sign[pos[48:112]]
-    return rows
-
-
-def _worst_case_rows_bf16x3(rng, n_rows):
-    """Unit rows (to within f32 rounding: one free element absorbs the rest of the norm) whose elements carry the bit
-    pattern that maximises what bf16 x 3 drops: x = hi + lo + r with lo ~ 2^-8 |x| (the residual just below half a bf16
-    ulp, so hi rounds DOWN) and r = 0.75 * 2^-17 |x| of the same sign (lo rounds down too).  With q = x the dropped terms
-    lo.lo + 2 r.x are all positive: error ~ 2^-15 |x||q| = 3.1e-5, the worst this scheme can do -- against a bound of 1.5e-4."""
-    rows = np.zeros((n_rows, 256), dtype=np.float64)
-    frac = 2.0 ** -8 - 2.0 ** -16 + 0.75 * 2.0 ** -17       # bits below the 7 fraction bits of hi
-    for r in range(n_rows):
-        while True:
-            n = 62
-            t = rng.integers(0, 3, size=n)                   # the top 7 fraction bits are free: they tune the norm
-            mags = 2.0 ** -3 * (1 + t * 2.0 ** -7 + frac)
-            rest = 1.0 - float((mags ** 2).sum())
-            if 2.0 ** -8 < rest < 2.0 ** -5:
-                break
-        pos = rng.permutation(256)
-        sign = rng.choice([-1.0, 1.0], size=256)
-        rows[r, pos[:n]] = mags * sign[pos[:n]]
-        rows[r, pos[n]] = np.sqrt(rest) * sign[pos[n]]       # the free element
-    return rows
-
-
 def test_constructed_worst_case_rows_stay_inside_the_certificate_bound(gpu_ctx, nominate_with):
     """the certificate's bounds were only ever checked on random corpora.  Here the rows are BUILT to make
-    every rounding of the nominating arithmetic err in the same direction (see the two generators), at unit norm and scaled
+    every rounding of the nominating arithmetic err in the same direction (see the two generators in tests/nominate_ref.py), at unit norm and scaled
     by powers of two and by 3.7 / 1e-3 (non-unit norms: the kernels normalise), and the queries are the rows themselves and
     sign-matched vectors of other magnitudes.  Asserted: |nominating - exact| <= the compiled-in bound in every mode, the
     construction really is adversarial in the mode it targets (several times the random-corpus maximum), and searches over
