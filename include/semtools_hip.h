@@ -163,7 +163,8 @@ int smt_model_token_info(const smt_model *model, uint64_t *n_tokens, int *has_ma
 
 /* Replaces the pool step of StaticModel::encode_with_args / encode_single
  * (call sites src/search/mod.rs:69,138,153; src/cmds/search.rs:136,154).
- * Tokenisation stays on the host: `ids` are the unk-filtered token ids of all
+ * Tokenisation happens before this call -- on the host, or for pure-ASCII lines of a WordPiece tokenizer on the
+ * device (section "tokenizer" below, smt_wordpiece_*): `ids` are the unk-filtered token ids of all
  * lines back to back, `offsets[n_lines+1]` the CSR boundaries.  Each line is
  * truncated to `max_tokens` ids (2048 for lines, 512 for queries; 0 = no cap),
  * rows are summed in token order in f32, divided by the count, and (if the
@@ -175,6 +176,62 @@ int smt_embed(smt_model *model, const uint32_t *ids, const uint64_t *offsets, ui
 /* everything resident: ids/offsets/out are device pointers; async on the stream */
 int smt_embed_device(smt_model *model, const uint32_t *ids_dev, const uint64_t *offsets_dev,
                      uint64_t n_lines, uint32_t max_tokens, float *out_dev);
+
+/* ---------------------------------------------------------------- tokenizer
+ * Pure-ASCII lines through BertNormalizer -> BertPreTokenizer -> WordPiece on the device (tokenize_kernels.hip): the
+ * byte rules of the host tokenizer's ASCII path, the same ids.  A line the kernel does not cover -- a byte >= 0x80, or an added
+ * token standing in it -- is FLAGGED and left to the caller, who may splice its ids in as a patch.
+ *
+ * The vocabulary as tokenizer.json has it: `pool` holds all pieces back to back (continuing pieces WITH their prefix), piece i is
+ * [piece_off[i], piece_off[i + 1]) with id piece_id[i]; of a repeated piece the later entry wins.  A piece with a byte >= 0x80 can
+ * never match and is left out.  unk_id -1: a word without a match yields nothing.  Everything is copied: the arrays may be freed
+ * after smt_wordpiece_create. */
+#define SMT_WP_NORMALIZER 1u /* a BertNormalizer is present (without it the two flags below mean nothing) */
+#define SMT_WP_CLEAN_TEXT 2u /* \t \n \r become ' ', NUL / controls / DEL are dropped and JOIN their neighbours */
+#define SMT_WP_LOWERCASE 4u  /* A-Z are lowered */
+typedef struct smt_wordpiece smt_wordpiece;
+typedef struct smt_wordpiece_params {
+    const char *pool;
+    const uint32_t *piece_off; /* [n_pieces + 1] */
+    const uint32_t *piece_id;  /* [n_pieces] */
+    uint64_t n_pieces;
+    const char *prefix; /* continuing_subword_prefix ("##") */
+    uint32_t prefix_len;
+    int64_t unk_id;
+    uint32_t max_input_chars_per_word;
+    uint32_t flags;            /* SMT_WP_* */
+    const char *added_pool;    /* pure-ASCII added tokens matched on the raw text: a line in which one stands is FLAGGED */
+    const uint32_t *added_off; /* [n_added + 1] */
+    uint32_t n_added;
+} smt_wordpiece_params;
+int smt_wordpiece_create(smt_ctx *ctx, const smt_wordpiece_params *p, smt_wordpiece **out);
+void smt_wordpiece_destroy(smt_wordpiece *tok);
+
+/* Pass 1: tokenize.  text_dev: text_bytes bytes; line i is [line_begin[i], line_begin[i] + line_len[i]) of them.  The lines lie in
+ * line order and do not overlap (line_begin[i] + line_len[i] <= line_begin[i + 1]; gaps and no separators are both fine) and end
+ * inside the text: the work is dealt by text position, so the host form checks this, and the device form trusts it -- a list that
+ * breaks the rule gives unspecified ids, but no access outside the text.  Only the first min(line_len[i], keep_bytes) bytes of a
+ * line are looked at (keep_bytes = max_tokens * median token length, the truncation of the host layer; 0 = no cut).
+ * counts_dev[i] = ids the line yields after the unk drop (drop_unk != 0) and the max_tokens cap (0 = none); flags_dev[i] != 0: not
+ * covered (a byte >= 0x80 within the looked-at bytes, or an added token standing there), count 0.  *n_flagged_dev = flagged lines.
+ * Enqueued on the context's stream; does not wait.  The ids stay inside `tok` for pass 2; the four per-line arrays must stay
+ * valid and unchanged until pass 2 has run.  One scan at a time per tokenizer: a second scan forgets the first. */
+int smt_wordpiece_scan_device(smt_wordpiece *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev,
+                              const uint32_t *line_len_dev, uint64_t n_lines, uint32_t keep_bytes, uint32_t max_tokens,
+                              int drop_unk, uint32_t *counts_dev, uint8_t *flags_dev, uint32_t *n_flagged_dev);
+/* Pass 2: lay the ids of the last scan out as the CSR smt_embed_device reads.  Optional patch: the ids of n_patch lines (sorted
+ * line numbers, each flagged by pass 1; a patch for a line that is not flagged is ignored) tokenized elsewhere, n_patch_ids in
+ * all, spliced in at their place.  ids_cap >= min(text_bytes, n_lines * keep_bytes) + n_patch_ids always suffices (a token is at
+ * least one byte); less is SMT_E_INVALID before anything is enqueued.  Enqueued on the context's stream; does not wait. */
+int smt_wordpiece_emit_device(smt_wordpiece *tok, uint64_t n_lines, const uint64_t *patch_line_dev,
+                              const uint64_t *patch_off_dev /* [n_patch + 1] */, const uint32_t *patch_ids_dev, uint64_t n_patch,
+                              uint64_t n_patch_ids, uint32_t *ids_out_dev, uint64_t ids_cap, uint64_t *offsets_out_dev /* [n_lines + 1] */);
+/* Host convenience (tests, small callers): upload, both passes without a patch, download.  ids_cap >= the looked-at bytes of all
+ * lines, else SMT_E_INVALID; a line list out of order, overlapping or outside the text (its end is taken as the largest line
+ * end) likewise.  flags_out may be NULL. */
+int smt_wordpiece_tokenize(smt_wordpiece *tok, const char *text, const uint64_t *line_begin, const uint32_t *line_len,
+                           uint64_t n_lines, uint32_t keep_bytes, uint32_t max_tokens, int drop_unk, uint32_t *ids_out,
+                           uint64_t ids_cap, uint64_t *offsets_out, uint8_t *flags_out);
 
 /* ------------------------------------------------------------------- corpus
  * Replaces `Document::embeddings: Vec<Vec<f32>>` (src/search/mod.rs:18-22)

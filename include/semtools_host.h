@@ -128,6 +128,18 @@ int smt_host_tokenizer_load(const char *tokenizer_json_path, smt_host_tokenizer 
 void smt_host_tokenizer_free(smt_host_tokenizer *tok);
 int smt_host_tokenizer_encode(smt_host_tokenizer *tok, const char *text, uint32_t *ids, uint64_t cap, uint64_t *n_ids);
 int smt_host_tokenizer_info(smt_host_tokenizer *tok, uint64_t *vocab_size, int64_t *unk_id, uint64_t *median_token_bytes);
+/* The device form of the tokenizer (include/semtools_hip.h, section "tokenizer"): its vocabulary, byte rules and added tokens as an
+ * smt_wordpiece on `ctx`, to be freed with smt_wordpiece_destroy.  SMT_E_UNSUPPORTED for a tokenizer whose pure-ASCII lines are not
+ * BertNormalizer (or none) -> BertPreTokenizer -> WordPiece: Unigram models, other pre-tokenizers. */
+int smt_host_tokenizer_to_device(smt_host_tokenizer *tok, smt_ctx *ctx, smt_wordpiece **out);
+/* The device tokenizer route of a model.  OFF by default; the environment variable SEMTOOLS_DEVICE_TOKENIZER=1 turns
+ * it on when the model is created.  With it on, a batch of lines is packed, uploaded and tokenized on the GPU when the model's
+ * tokenizer has a device form (smt_host_tokenizer_to_device), the group has one rank and the full table is resident (or about to be:
+ * calls of more than 32768 lines); lines the kernel flags are tokenized by the host tokenizer and spliced in; everything else keeps
+ * the host path.  Rows, search output and the workspace's cached ids are bit-identical with the switch on and off.
+ * smt_host_debug_device_tokenized (test hook): lines of this model tokenized on the device so far. */
+int smt_host_model_set_device_tokenizer(smt_host_model *model, int on);
+int smt_host_debug_device_tokenized(smt_host_model *model, uint64_t *lines);
 /* Wall-clock phases of this process so far as one JSON object (malloc'd): model_load, read_tokenize_embed_files,
  * embed_query, store_open_corpus_load, change_detection, embed_and_persist_changed_files, scan_select, ... -- what the
  * CLI prints to stderr under SEMTOOLS_TIMING=1. */

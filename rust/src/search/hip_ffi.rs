@@ -8,7 +8,7 @@
 use std::os::raw::{c_char, c_int, c_void};
 
 macro_rules! opaque { ($($name:ident),*) => { $( #[repr(C)] pub struct $name { _private: [u8; 0] } )* } }
-opaque!(SmtCtx, SmtModel, SmtCorpus, SmtIvfpq, SmtGroup, SmtShardedCorpus, SmtShardedIvfpq, SmtShardedModel);
+opaque!(SmtCtx, SmtModel, SmtCorpus, SmtIvfpq, SmtGroup, SmtShardedCorpus, SmtShardedIvfpq, SmtShardedModel, SmtWordpiece);
 
 /// half-open range of corpus rows [begin, end)
 #[repr(C)]
@@ -30,6 +30,24 @@ pub struct SmtIvfpqParams {
     pub local_pca: u32,
 }
 
+/// a WordPiece vocabulary and its byte rules for the device tokenizer (smt_wordpiece_create copies everything)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SmtWordpieceParams {
+    pub pool: *const c_char,
+    pub piece_off: *const u32,
+    pub piece_id: *const u32,
+    pub n_pieces: u64,
+    pub prefix: *const c_char,
+    pub prefix_len: u32,
+    pub unk_id: i64,
+    pub max_input_chars_per_word: u32,
+    pub flags: u32,
+    pub added_pool: *const c_char,
+    pub added_off: *const u32,
+    pub n_added: u32,
+}
+
 pub const SMT_OK: c_int = 0;
 pub const SMT_E_INVALID: c_int = -1;
 pub const SMT_E_HIP: c_int = -2;
@@ -43,6 +61,9 @@ pub const SMT_MODE_WORKSPACE: c_int = 1;
 pub const SMT_TABLE_F32: c_int = 0;
 pub const SMT_TABLE_F16: c_int = 1;
 pub const SMT_TABLE_I8: c_int = 2;
+pub const SMT_WP_NORMALIZER: c_int = 1;
+pub const SMT_WP_CLEAN_TEXT: c_int = 2;
+pub const SMT_WP_LOWERCASE: c_int = 4;
 pub const SMT_STATUS_PROVED: c_int = 0;
 pub const SMT_STATUS_UNCERTAIN: c_int = 1;
 pub const SMT_STATUS_OVERFLOW: c_int = 2;
@@ -189,6 +210,52 @@ extern "C" {
         n_lines: u64,
         max_tokens: u32,
         out_dev: *mut f32,
+    ) -> c_int;
+    pub fn smt_wordpiece_create(
+        ctx: *mut SmtCtx,
+        p: *const SmtWordpieceParams,
+        out: *mut *mut SmtWordpiece,
+    ) -> c_int;
+    pub fn smt_wordpiece_destroy(tok: *mut SmtWordpiece);
+    pub fn smt_wordpiece_scan_device(
+        tok: *mut SmtWordpiece,
+        text_dev: *const u8,
+        text_bytes: u64,
+        line_begin_dev: *const u64,
+        line_len_dev: *const u32,
+        n_lines: u64,
+        keep_bytes: u32,
+        max_tokens: u32,
+        drop_unk: c_int,
+        counts_dev: *mut u32,
+        flags_dev: *mut u8,
+        n_flagged_dev: *mut u32,
+    ) -> c_int;
+    pub fn smt_wordpiece_emit_device(
+        tok: *mut SmtWordpiece,
+        n_lines: u64,
+        patch_line_dev: *const u64,
+        patch_off_dev: *const u64,
+        patch_ids_dev: *const u32,
+        n_patch: u64,
+        n_patch_ids: u64,
+        ids_out_dev: *mut u32,
+        ids_cap: u64,
+        offsets_out_dev: *mut u64,
+    ) -> c_int;
+    pub fn smt_wordpiece_tokenize(
+        tok: *mut SmtWordpiece,
+        text: *const c_char,
+        line_begin: *const u64,
+        line_len: *const u32,
+        n_lines: u64,
+        keep_bytes: u32,
+        max_tokens: u32,
+        drop_unk: c_int,
+        ids_out: *mut u32,
+        ids_cap: u64,
+        offsets_out: *mut u64,
+        flags_out: *mut u8,
     ) -> c_int;
     pub fn smt_corpus_create(ctx: *mut SmtCtx, D: u32, capacity_rows: u64, out: *mut *mut SmtCorpus) -> c_int;
     pub fn smt_corpus_from_device(

@@ -254,6 +254,9 @@ private:
 void layout_set_contiguous(smt_sharded_corpus *sc, const std::vector<uint64_t> &rank_rows);
 // n new rows (global rows total .. total + n) dealt to the ranks: add[r] consecutive rows each, in rank order
 void layout_append(smt_sharded_corpus *sc, const std::vector<uint64_t> &add);
+// sharded.cpp: smt_sharded_embed's append path for a token CSR in device memory (one-rank groups; waits for the stream)
+int sharded_embed_device_append(smt_sharded_model *model, const uint32_t *ids_dev, const uint64_t *offsets_dev, uint64_t n_lines,
+                                smt_sharded_corpus *append_to);
 // how an append of n rows is dealt: the emptier shards are filled first (water level), small appends go to one shard
 void layout_deal(const smt_sharded_corpus *sc, uint64_t n, std::vector<uint64_t> &add);
 // global ranges (sorted, disjoint) -> the LOCAL row ranges of rank r

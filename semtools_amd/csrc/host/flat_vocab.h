@@ -51,6 +51,15 @@ public:
     }
     int64_t find(const std::string &s) const { return find(s.data(), s.size()); }
     size_t size() const { return entries_.size(); }
+    // the pieces in the order they were added: the pool, [size() + 1] offsets into it, [size()] ids
+    void export_pieces(std::string &pool, std::vector<uint32_t> &off, std::vector<uint32_t> &id) const
+    {
+        pool = pool_;
+        off.clear();
+        id.clear();
+        for (const Entry &e : entries_) { off.push_back(e.off); id.push_back(e.id); }   // (add() appends: entry i ends where i + 1 begins)
+        off.push_back((uint32_t)pool_.size());
+    }
 
 private:
     struct Entry { uint32_t off, len, id; };

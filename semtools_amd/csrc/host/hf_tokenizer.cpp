@@ -609,6 +609,23 @@ public:
     uint64_t vocab_size() const override { return size_; }
     size_t lines_per_thread() const override { return 1024; }
 
+    bool export_wordpiece(WordpieceExport &x) const override
+    {
+        if (!ascii_fast_ || !unk_) return false;
+        vocab_.export_pieces(x.pool, x.piece_off, x.piece_id);
+        x.prefix = prefix_;
+        x.unk_id = (int64_t)*unk_;
+        x.max_input_chars_per_word = (uint32_t)std::min<size_t>(max_chars_, 0xFFFFFFFFu);
+        x.flags = has_norm_ ? SMT_WP_NORMALIZER | (norm_.clean_text ? SMT_WP_CLEAN_TEXT : 0u) | (norm_.lowercase ? SMT_WP_LOWERCASE : 0u) : 0u;
+        x.added_pool.clear();
+        x.added_off.assign(1, 0);
+        for (const AddedToken &t : added_ascii_) {   // (the tokens encode_ascii sends a line away for)
+            x.added_pool.append(t.bytes);
+            x.added_off.push_back((uint32_t)x.added_pool.size());
+        }
+        return true;
+    }
+
 private:
     static bool is_word_char(uint32_t c) { return c == '_' || (c < 0x80 ? isalnum((int)c) != 0 : !is_white_space(c) && !is_punct_cat(c)); }
 

@@ -472,6 +472,7 @@ void StaticModel::token_info(uint64_t *n_tokens, bool *has_mapping, bool *has_we
 
 StaticModel::~StaticModel()
 {
+    device_route_destroy(dev_route_);
     if (model_) smt_sharded_model_destroy(model_);
     if (lazy_fd_ >= 0) close(lazy_fd_);
 }
@@ -708,6 +709,40 @@ void StaticModel::tokenize_batch(const std::string_view *sentences, size_t begin
     for (auto &f : failed) if (f) std::rethrow_exception(f);
 }
 
+DeviceTokenRoute *StaticModel::device_route() const
+{
+    if (!device_tok_) return nullptr;
+    if (!dev_route_tried_) {
+        dev_route_tried_ = true;
+        dev_route_ = device_route_create(group_, *tok_);
+    }
+    return dev_route_;
+}
+
+bool StaticModel::device_batch(int which, size_t n, const std::string_view *sentences, std::optional<size_t> max_length, float *out_host,
+                               smt_sharded_corpus *corpus, TokenCsr *sink) const
+{
+    // keep_bytes = truncate_len's max_tokens * median characters: a line that is pure ASCII that far has one byte per character
+    const uint64_t keep = max_length ? (uint64_t)*max_length * tok_->median_token_length() : 0;
+    const uint32_t keep_bytes = (uint32_t)std::min<uint64_t>(keep, 0xFFFFFFFFull);   // (a line holds fewer bytes than that anyway)
+    const uint32_t max_tokens = max_length ? (uint32_t)std::min<size_t>(*max_length, 0xFFFFFFFFull) : 0;
+    if (max_length && (keep_bytes == 0 || max_tokens == 0)) {   // max_length 0: every line is empty (0 means "no cut" to the kernel)
+        std::vector<uint32_t> ids;
+        std::vector<uint64_t> offsets(n + 1, 0);
+        embed_csr(ids, offsets, n, out_host, corpus);
+        if (sink) sink->lens.insert(sink->lens.end(), n, 0u);
+        return false;
+    }
+    const DeviceFlaggedFn flagged = [&](const std::vector<uint64_t> &lines, std::vector<uint32_t> &ids, std::vector<uint64_t> &offsets) {
+        std::vector<std::string_view> views(lines.size());
+        for (size_t i = 0; i < lines.size(); ++i) views[i] = sentences[lines[i]];
+        tokenize_batch(views.data(), 0, views.size(), max_length, ids, offsets);
+    };
+    const uint64_t n_flagged = device_route_run(dev_route_, which, model_, keep_bytes, max_tokens, tok_->unk_id().has_value(), flagged, out_host,
+                                                corpus, sink);
+    return n_flagged * 2 > n;
+}
+
 std::vector<std::vector<float>> StaticModel::encode_with_args(const std::vector<std::string> &sentences,
                                                               std::optional<size_t> max_length,
                                                               size_t batch_size) const
@@ -719,10 +754,18 @@ std::vector<std::vector<float>> StaticModel::encode_with_args(const std::vector<
     std::vector<float> buf;
     if (batch_size == 0) batch_size = 1;
     const std::vector<std::string_view> views(sentences.begin(), sentences.end());
+    // the route needs the full table RESIDENT (model_ set): a lazy table keeps the host path, whose small calls pick the rows to upload
+    // from the ids.  (Only encode_into has the "about to be resident" rule: it uploads the table for n > 32768 before it gets here.)
+    bool on_device = model_ && device_route();
     for (size_t b = 0; b < sentences.size(); b += batch_size) {
         const size_t e = std::min(sentences.size(), b + batch_size);
-        tokenize_batch(views.data(), b, e, max_length, ids, offsets);
         buf.resize((e - b) * SMT_DIM);
+        if (on_device && device_route_pack(dev_route_, 0, views.data() + b, e - b)) {
+            if (device_batch(0, e - b, views.data() + b, max_length, buf.data(), nullptr, nullptr)) on_device = false;
+            for (size_t i = 0; i < e - b; ++i) out.emplace_back(buf.begin() + i * SMT_DIM, buf.begin() + (i + 1) * SMT_DIM);
+            continue;
+        }
+        tokenize_batch(views.data(), b, e, max_length, ids, offsets);
         embed_csr(ids, offsets, e - b, buf.data(), nullptr);   // (tokenize_batch already truncated to max_length)
         for (size_t i = 0; i < e - b; ++i) out.emplace_back(buf.begin() + i * SMT_DIM, buf.begin() + (i + 1) * SMT_DIM);
     }
@@ -761,9 +804,43 @@ uint64_t StaticModel::encode_into(const std::vector<std::string_view> &sentences
         tokenize_batch(sentences.data(), b, std::min(n, b + batch_size), max_length, s.ids, s.offsets);
         PhaseTimer::add("within_embed:tokenize_batches", ms_since(t0));
     };
-    tokenize(0, slots[0]);
+    // ---- the device route (off by default): batch i runs on the GPU -- upload, tokenize, pool -- while batch i + 1 is packed into
+    // the other pinned slot.  A batch that comes back mostly flagged (a corpus that is not ASCII runs pass 1 for nothing) hands the
+    // rest of the call to the host path below; rows and cached ids are the same either way.
+    // model_ is set when the table is resident -- from the start, or by the n > 32768 rule's full_model() a few lines up ("about to be").
+    size_t done = 0;
+    if (model_ && device_route()) {
+        int cur = 0;
+        bool packed = device_route_pack(dev_route_, 0, sentences.data(), std::min(n, batch_size));
+        while (packed && done < n) {
+            const size_t e = std::min(n, done + batch_size);
+            std::thread next;
+            std::exception_ptr next_failed, run_failed;
+            bool next_packed = false, give_up = false;
+            if (e < n) next = std::thread([&, e, cur]() {
+                try { next_packed = device_route_pack(dev_route_, cur ^ 1, sentences.data() + e, std::min(n, e + batch_size) - e); }
+                catch (...) { next_failed = std::current_exception(); }
+            });
+            try {
+                give_up = device_batch(cur, e - done, sentences.data() + done, max_length, nullptr, corpus, sink);
+                if (after_batch && *after_batch) {
+                    const auto t_after = std::chrono::steady_clock::now();
+                    (*after_batch)();
+                    PhaseTimer::add("within_embed:after_batch", ms_since(t_after));
+                }
+            } catch (...) { run_failed = std::current_exception(); }
+            if (next.joinable()) next.join();
+            if (run_failed) std::rethrow_exception(run_failed);
+            if (next_failed) std::rethrow_exception(next_failed);
+            done = e;
+            cur ^= 1;
+            packed = next_packed && !give_up;
+        }
+        if (done == n) return first;
+    }
+    tokenize(done, slots[0]);
     int cur = 0;
-    for (size_t b = 0; b < n; b += batch_size) {
+    for (size_t b = done; b < n; b += batch_size) {
         const size_t e = std::min(n, b + batch_size);
         std::thread next;
         std::exception_ptr next_failed;

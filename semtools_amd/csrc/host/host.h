@@ -15,6 +15,7 @@
 #pragma once
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <functional>
 #include <map>
 #include <memory>
@@ -45,6 +46,32 @@ std::string read_to_string(const std::string &path);  // throws Error like `?` o
 // Stand-in for tokenizers::Tokenizer (the HF crate the reference uses through
 // model2vec-rs).  encode() returns ids with add_special_tokens=false; the
 // model drops unk ids and truncates, exactly where model2vec-rs does.
+// what a tokenizer whose pure-ASCII lines are BertNormalizer (or none) -> BertPreTokenizer -> WordPiece hands the device tokenizer
+// (include/semtools_hip.h smt_wordpiece_params, which points into these)
+struct WordpieceExport {
+    std::string pool, prefix, added_pool;
+    std::vector<uint32_t> piece_off, piece_id, added_off;
+    int64_t unk_id = -1;
+    uint32_t max_input_chars_per_word = 100, flags = 0;
+    smt_wordpiece_params params() const   // (points into this object)
+    {
+        smt_wordpiece_params p{};
+        p.pool = pool.data();
+        p.piece_off = piece_off.data();
+        p.piece_id = piece_id.data();
+        p.n_pieces = piece_id.size();
+        p.prefix = prefix.data();
+        p.prefix_len = (uint32_t)prefix.size();
+        p.unk_id = unk_id;
+        p.max_input_chars_per_word = max_input_chars_per_word;
+        p.flags = flags;
+        p.added_pool = added_pool.data();
+        p.added_off = added_off.data();
+        p.n_added = (uint32_t)(added_off.empty() ? 0 : added_off.size() - 1);
+        return p;
+    }
+};
+
 class Tokenizer {
 public:
     virtual ~Tokenizer() = default;
@@ -55,6 +82,9 @@ public:
     // lines worth starting one more thread for, in a batch (a thread costs ~30 us to start: ~0.15 us per hashed line, ~1-4 us per
     // line through a tokenizer.json pipeline)
     virtual size_t lines_per_thread() const { return 8192; }
+    // optional: the device form of this tokenizer's ASCII path.  false: not supported (Unigram, other pre-tokenizers, the vocab.txt,
+    // hash and callback tokenizers)
+    virtual bool export_wordpiece(WordpieceExport &) const { return false; }
 };
 // whitespace words looked up in a vocab file (one token per line, id = line index)
 std::unique_ptr<Tokenizer> make_vocab_tokenizer(const std::string &vocab_path, const std::string &unk_token);
@@ -87,6 +117,22 @@ struct TokenCsr {
     std::vector<uint32_t> ids;
     std::vector<uint32_t> lens;
 };
+
+// The device route of a batch of lines (device_tokenize.cpp): text up, WordPiece on the device, flagged lines through the host
+// tokenizer, K1 on the device CSR.  One-rank groups and tokenizers with a device form only (device_route_create: nullptr otherwise).
+struct DeviceTokenRoute;
+// fills the CSR (ids, offsets [lines.size() + 1]) of the batch's flagged lines, given by their index in the batch
+using DeviceFlaggedFn = std::function<void(const std::vector<uint64_t> &lines, std::vector<uint32_t> &ids, std::vector<uint64_t> &offsets)>;
+DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok);
+void device_route_destroy(DeviceTokenRoute *r);
+uint64_t device_route_lines(const DeviceTokenRoute *r);   // lines tokenized on the device so far
+// the batch's bytes back to back into pinned slot `which` (0 / 1: one is packed while the other one runs); false: the batch is
+// outside the scan's limits and keeps the host path
+bool device_route_pack(DeviceTokenRoute *r, int which, const std::string_view *sentences, size_t n);
+// upload, pass 1, flagged lines on the host, pass 2, K1 into out_host and / or appended to corpus; sink receives the pooled ids.
+// Returns the number of flagged lines.
+uint64_t device_route_run(DeviceTokenRoute *r, int which, smt_sharded_model *model, uint32_t keep_bytes, uint32_t max_tokens, bool drop_unk,
+                          const DeviceFlaggedFn &tokenize_flagged, float *out_host, smt_sharded_corpus *corpus, TokenCsr *sink);
 
 class StaticModel {
 public:
@@ -132,6 +178,12 @@ public:
 
     smt_group *group() const { return group_; }
     const Tokenizer &tokenizer() const { return *tok_; }
+    // the device tokenizer route (off by default; SEMTOOLS_DEVICE_TOKENIZER=1 turns it on at construction): with it on, batches of a
+    // one-rank group whose tokenizer has a device form are tokenized on the GPU once the full table is resident.  Rows and cached
+    // ids do not depend on it.
+    void set_device_tokenizer(bool on) { device_tok_ = on; }
+    bool device_tokenizer() const { return device_tok_; }
+    uint64_t device_tokenized_lines() const { return device_route_lines(dev_route_); }
     // the table as the device holds it (or will, in lazy mode before the full upload: *resident = false): SMT_TABLE_* kind, rows,
     // bytes per replica
     void table_info(int *table_dtype, uint64_t *V, uint64_t *table_bytes, bool *resident) const;
@@ -147,6 +199,15 @@ private:
     void embed_csr(const std::vector<uint32_t> &ids, const std::vector<uint64_t> &offsets, uint64_t n_lines, float *out_host,
                    smt_sharded_corpus *corpus) const;
     smt_sharded_model *full_model() const;   // uploads the whole table on first use (lazy mode)
+    // the device route, made on first use (like model_, lazy_slot_ and lazy_calls_ above: a StaticModel serves ONE calling thread at a
+    // time -- the host layer's entry points never share a model between threads); nullptr when the switch is off, the group has several ranks or the tokenizer has no device form
+    DeviceTokenRoute *device_route() const;
+    // one packed batch through the route; true: the batch was mostly flagged (the rest of the call keeps the host path)
+    bool device_batch(int which, size_t n, const std::string_view *sentences, std::optional<size_t> max_length, float *out_host,
+                      smt_sharded_corpus *corpus, TokenCsr *sink) const;
+    bool device_tok_ = [] { const char *e = getenv("SEMTOOLS_DEVICE_TOKENIZER"); return e && e[0] == '1'; }();
+    mutable DeviceTokenRoute *dev_route_ = nullptr;
+    mutable bool dev_route_tried_ = false;
     smt_group *group_;
     std::unique_ptr<Tokenizer> tok_;
     mutable smt_sharded_model *model_ = nullptr;

@@ -294,6 +294,35 @@ int smt_host_tokenizer_info(smt_host_tokenizer *tok, uint64_t *vocab_size, int64
     return SMT_OK;
 }
 
+int smt_host_model_set_device_tokenizer(smt_host_model *model, int on)
+{
+    if (!model) { smt::set_error("null argument"); return SMT_E_INVALID; }
+    model->m->set_device_tokenizer(on != 0);
+    return SMT_OK;
+}
+
+int smt_host_debug_device_tokenized(smt_host_model *model, uint64_t *lines)
+{
+    if (!model || !lines) { smt::set_error("null argument"); return SMT_E_INVALID; }
+    *lines = model->m->device_tokenized_lines();
+    return SMT_OK;
+}
+
+int smt_host_tokenizer_to_device(smt_host_tokenizer *tok, smt_ctx *ctx, smt_wordpiece **out)
+{
+    if (!tok || !out) { smt::set_error("null argument"); return SMT_E_INVALID; }
+    *out = nullptr;
+    try {
+        WordpieceExport x;
+        if (!tok->t->export_wordpiece(x)) {
+            smt::set_error("this tokenizer has no device form (pure-ASCII lines of BertNormalizer -> BertPreTokenizer -> WordPiece only)");
+            return SMT_E_UNSUPPORTED;
+        }
+        const smt_wordpiece_params p = x.params();
+        return smt_wordpiece_create(ctx, &p, out);   // (no context: SMT_E_HIP on a machine without a device)
+    } catch (const std::exception &e) { return fail(e); }
+}
+
 static int host_model_from_dir(smt_ctx *ctx, smt_group *group, const char *dir, smt_host_model **out)
 {
     if ((!ctx && !group) || !dir || !out) { smt::set_error("null argument"); return SMT_E_INVALID; }

@@ -762,6 +762,38 @@ try {
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
+}  // extern "C"
+
+namespace smt {
+
+// The append path of smt_sharded_embed for a token CSR that is already in device memory (the host layer's device tokenizer route):
+// one-rank groups only.  Same steps as smt_embed with append_to -- room, K1 into the rows behind the last one, the domain check, then
+// the row count and the layout -- so that an append is recorded in one file whichever side the ids came from.  Waits for the stream.
+int sharded_embed_device_append(smt_sharded_model *model, const uint32_t *ids_dev, const uint64_t *offsets_dev, uint64_t n_lines,
+                                smt_sharded_corpus *append_to)
+{
+    SMT_REQUIRE(model != nullptr && append_to != nullptr, "null argument");
+    SMT_REQUIRE(model->group->n_ranks == 1 && append_to->group == model->group, "one-rank groups only, model and corpus on the same one");
+    if (n_lines == 0) return SMT_OK;
+    smt_model *m = model->model[0];
+    smt_corpus *c = append_to->shard[0];
+    SMT_REQUIRE(c->ctx == m->ctx, "corpus belongs to a different context");
+    SMT_REQUIRE(c->dim == m->D, "corpus dim differs from the model's");
+    int rc = corpus_reserve(c, c->rows + n_lines);
+    if (rc) return rc;
+    float *d_out = c->d_rows + (size_t)c->rows * c->dim;
+    if ((rc = smt_embed_device(m, ids_dev, offsets_dev, n_lines, 0, d_out))) return rc;
+    SMT_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+    if ((rc = require_rows_domain(m->ctx, d_out, n_lines, "embed of a device CSR (rows pooled from the table)", 0))) return rc;
+    c->rows += n_lines;
+    layout_append(append_to, std::vector<uint64_t>(1, n_lines));
+    return SMT_OK;
+}
+
+}  // namespace smt
+
+extern "C" {
+
 /* ------------------------------------------------ sharded index: life cycle ---- */
 
 int smt_sharded_ivfpq_save(smt_sharded_ivfpq *six, const char *path)

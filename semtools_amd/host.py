@@ -30,8 +30,10 @@ class StaticModel:
     tokenizer: "hash" (whitespace words hashed into the table), ("vocab", path, unk_token) or a
     Python callable text -> list of ids (e.g. tokenizers.Tokenizer(...).encode(t, add_special_tokens=False).ids)."""
 
-    def __init__(self, ctx, table=None, tokenizer="hash", normalize=True, unk_id=None, median_len=5, model_dir=None):
-        """ctx: a core.Context (one GPU) or a core.Group (the host layer then runs sharded over its GPUs)."""
+    def __init__(self, ctx, table=None, tokenizer="hash", normalize=True, unk_id=None, median_len=5, model_dir=None, device_tokenizer=None):
+        """ctx: a core.Context (one GPU) or a core.Group (the host layer then runs sharded over its GPUs).
+        device_tokenizer: True / False switch the device tokenizer route on / off (None: the library's default, off unless
+        SEMTOOLS_DEVICE_TOKENIZER=1); it applies to tokenizer.json models of the Bert / WordPiece family on one GPU."""
         from .core import Group
         self.ctx = ctx
         on_group = isinstance(ctx, Group)
@@ -41,6 +43,8 @@ class StaticModel:
         if model_dir is not None:
             fn = lib.smt_host_model_from_dir_group if on_group else lib.smt_host_model_from_dir
             L.check(fn(ctx._h, str(model_dir).encode(), C.byref(self._h)))
+            if device_tokenizer is not None:
+                self.set_device_tokenizer(device_tokenizer)
             return
         table = np.ascontiguousarray(table, dtype=np.float32)
         kind, vocab, unk = 0, None, None
@@ -63,6 +67,17 @@ class StaticModel:
         fn = lib.smt_host_model_create_group if on_group else lib.smt_host_model_create
         L.check(fn(ctx._h, L.np_ptr(table), table.shape[0], int(normalize), kind, vocab, unk,
                    self._cb, None, 0xFFFFFFFF if unk_id is None else int(unk_id), int(median_len), C.byref(self._h)))
+        if device_tokenizer is not None:
+            self.set_device_tokenizer(device_tokenizer)
+
+    def set_device_tokenizer(self, on):
+        L.check(L.lib().smt_host_model_set_device_tokenizer(self._h, int(bool(on))))
+
+    def device_tokenized_lines(self):
+        """lines of this model tokenized on the device so far (test hook)"""
+        n = C.c_uint64()
+        L.check(L.lib().smt_host_debug_device_tokenized(self._h, C.byref(n)))
+        return int(n.value)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

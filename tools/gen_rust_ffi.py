@@ -22,7 +22,7 @@ PRELUDE = '''//! FFI declarations for libsemtools_hip.so -- GENERATED from inclu
 use std::os::raw::{c_char, c_int, c_void};
 
 macro_rules! opaque { ($($name:ident),*) => { $( #[repr(C)] pub struct $name { _private: [u8; 0] } )* } }
-opaque!(SmtCtx, SmtModel, SmtCorpus, SmtIvfpq, SmtGroup, SmtShardedCorpus, SmtShardedIvfpq, SmtShardedModel);
+opaque!(SmtCtx, SmtModel, SmtCorpus, SmtIvfpq, SmtGroup, SmtShardedCorpus, SmtShardedIvfpq, SmtShardedModel, SmtWordpiece);
 
 /// half-open range of corpus rows [begin, end)
 #[repr(C)]
@@ -42,6 +42,24 @@ pub struct SmtIvfpqParams {
     pub train_sample: u64,
     pub reserved: u32,
     pub local_pca: u32,
+}
+
+/// a WordPiece vocabulary and its byte rules for the device tokenizer (smt_wordpiece_create copies everything)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SmtWordpieceParams {
+    pub pool: *const c_char,
+    pub piece_off: *const u32,
+    pub piece_id: *const u32,
+    pub n_pieces: u64,
+    pub prefix: *const c_char,
+    pub prefix_len: u32,
+    pub unk_id: i64,
+    pub max_input_chars_per_word: u32,
+    pub flags: u32,
+    pub added_pool: *const c_char,
+    pub added_off: *const u32,
+    pub n_added: u32,
 }
 
 '''
