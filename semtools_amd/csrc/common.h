@@ -64,7 +64,7 @@ struct Tuning {
     int merge_on_aux = 0;       // 1: smt_merge_topk_packed_device runs on the aux stream (behind the async select it consumes)
     int async_select = 0;       // 1: single-query top-k searches overlap their select stage with the next scan
     int scan_overlap = 1;       // async_select, smt_search_topk_device: scan + select of call i on internal stream i & 1 (consecutive scans overlap; 0 = the aux-stream / flag pipeline)
-    int scan_gate_pct = -1;     // scan_overlap: a scan's blocks start once this share of its predecessor call's blocks has finished its rows (0 = no gate; -1, the default: 50, and no gate when scans take two or three calls along, scan_pair >= 2 -- DESIGN.md 4.1 has both sweeps)
+    int scan_gate_pct = -1;     // scan_overlap: a scan's blocks start once this share of its predecessor call's blocks has finished its rows (0 = no gate; -1, the default: 50 in every mode -- DESIGN.md 4.1 has the sweeps)
     int scan_pair = 3;          // scan_overlap: a scan that starts behind a predecessor takes the queries of up to this many later calls of its stream (steps + 2, + 4, + 6) along in the same corpus pass (0..3; scan_kernels.hip scan_pair_kernel)
     int scan_pair_ring = 4096;  // scan_pair: slots of the descriptor ring in use (a power of two, 64 .. 4096): a call is found by the scan two steps earlier while the host is fewer calls ahead of the GPU than this (tests use 64 to see slots reused)
     int scan_pair_wait_us = 0;  // scan_pair, tests only: the deciding block waits this long (<= 5000) for the partner's descriptor

@@ -76,6 +76,75 @@ __device__ __forceinline__ float wave_sum4(float a, float b, float c, float d, i
     return add_lane_xor32(v);
 }
 
+// T wave_sum4 trees at once: out[t] is bit for bit wave_sum4(in[t][0], in[t][1], in[t][2], in[t][3], lane) -- every tree performs the
+// same operations in the same order -- with the trees' instructions interleaved level by level, so that each DPP step of one tree
+// stands in the wait states of the others', and ONE s_nop in front of each level's permlane swaps covers all T of them.
+template <int T>
+__device__ __forceinline__ void swap_lanes_xor16(float (&a)[T], float (&b)[T]);
+template <int T>
+__device__ __forceinline__ void swap_lanes_xor32(float (&a)[T], float (&b)[T]);
+template <>
+__device__ __forceinline__ void swap_lanes_xor16<2>(float (&a)[2], float (&b)[2])
+{
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32_e32 %0, %1\n\tv_permlane16_swap_b32_e32 %2, %3"
+                 : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]));
+}
+template <>
+__device__ __forceinline__ void swap_lanes_xor32<2>(float (&a)[2], float (&b)[2])
+{
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32_e32 %0, %1\n\tv_permlane32_swap_b32_e32 %2, %3"
+                 : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]));
+}
+template <>
+__device__ __forceinline__ void swap_lanes_xor16<3>(float (&a)[3], float (&b)[3])
+{
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32_e32 %0, %1\n\tv_permlane16_swap_b32_e32 %2, %3\n\tv_permlane16_swap_b32_e32 %4, %5"
+                 : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]));
+}
+template <>
+__device__ __forceinline__ void swap_lanes_xor32<3>(float (&a)[3], float (&b)[3])
+{
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32_e32 %0, %1\n\tv_permlane32_swap_b32_e32 %2, %3\n\tv_permlane32_swap_b32_e32 %4, %5"
+                 : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]));
+}
+// (in two halves, so that a caller short of registers can place work between them: the head leaves ONE live value per tree)
+template <int T>
+__device__ __forceinline__ void wave_sum4_multi_head(const float (&in)[T][4], float (&v)[T], int lane)
+{
+    const bool odd = lane & 1, upper = lane & 2;
+    float ab[T], cd[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) ab[t] = (odd ? in[t][1] : in[t][0]) + dpp_f<DPP_XOR1>(odd ? in[t][0] : in[t][1]);
+#pragma unroll
+    for (int t = 0; t < T; ++t) cd[t] = (odd ? in[t][3] : in[t][2]) + dpp_f<DPP_XOR1>(odd ? in[t][2] : in[t][3]);
+#pragma unroll
+    for (int t = 0; t < T; ++t) v[t] = (upper ? cd[t] : ab[t]) + dpp_f<DPP_XOR2>(upper ? ab[t] : cd[t]);
+}
+template <int T>
+__device__ __forceinline__ void wave_sum4_multi_tail(float (&v)[T], float (&out)[T])
+{
+    float w[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) v[t] += dpp_f<DPP_ROW_ROR4>(v[t]);
+#pragma unroll
+    for (int t = 0; t < T; ++t) v[t] += dpp_f<DPP_ROW_ROR8>(v[t]);
+#pragma unroll
+    for (int t = 0; t < T; ++t) w[t] = v[t];
+    swap_lanes_xor16<T>(v, w);   // v = rows {0, 0, 2, 2}, w = rows {1, 1, 3, 3}
+#pragma unroll
+    for (int t = 0; t < T; ++t) { v[t] = v[t] + w[t]; w[t] = v[t]; }
+    swap_lanes_xor32<T>(v, w);   // v = {lo, lo}, w = {hi, hi}
+#pragma unroll
+    for (int t = 0; t < T; ++t) out[t] = v[t] + w[t];
+}
+template <int T>
+__device__ __forceinline__ void wave_sum4_multi(const float (&in)[T][4], float (&out)[T], int lane)
+{
+    float v[T];
+    wave_sum4_multi_head<T>(in, v, lane);
+    wave_sum4_multi_tail<T>(v, out);
+}
+
 // Integer sum over the 64 lanes, result in every lane.
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 {

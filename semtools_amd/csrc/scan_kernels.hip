@@ -625,7 +625,7 @@ __device__ __forceinline__ unsigned int pair_decide(const ScanParams &p, const P
 // (8 waves per SIMD = 64 VGPRs: what the select needs beside it, 2 x 64 + 4 x 96 = 512.  The four-query row loop with its queries
 // in registers takes 81; with all four read from one LDS image per block and the norms held as wave-uniform values it fits.)
 template <bool NT>
-__global__ void __launch_bounds__(1024) scan_pair_kernel(ScanParams p, PairParams pp)
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) scan_pair_kernel(ScanParams p, PairParams pp)
 {
     constexpr int U = 4;
     constexpr int NQ = GROUP_MAX;
@@ -685,7 +685,7 @@ __global__ void __launch_bounds__(1024) scan_pair_kernel(ScanParams p, PairParam
     }
     __syncthreads();
     if (uniform_u64(s_pair[0]) == PAIR_ABSORBED) {
-        if (blockIdx.x == 0 && threadIdx.x == 0)
+        if (blockIdx.x == 0 && wave == 0 && lane == 0)
             (void)__hip_atomic_fetch_add(pp.ctl + 3, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
@@ -698,23 +698,24 @@ __global__ void __launch_bounds__(1024) scan_pair_kernel(ScanParams p, PairParam
         if (lane == 0) t = atomicAdd(s_next, 1u);
         return (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
     };
-    auto issue_rows = [&](uint64_t v0, f32x4 (&c)[U], uint32_t (&row)[U]) {
+    // (row numbers are far below 2^63: the sign of the difference is a scalar compare, where "<" on 64 bits takes the VALU and a
+    // vector register pair for n_virtual -- this kernel has none to spare)
+    auto in_corpus = [&](uint64_t v) -> bool { return (int64_t)(v - p.n_virtual) < 0; };
+    auto issue_rows = [&](uint64_t v0, f32x4 (&c)[U]) {
 #pragma unroll
         for (int j = 0; j < U; ++j) {
             uint64_t v = v0 + j;
-            if (v >= p.n_virtual) v = p.n_virtual - 1;  // clamp (result discarded)
-            row[j] = (uint32_t)v;
-            const f32x4 *src = reinterpret_cast<const f32x4 *>(p.corpus + (uint64_t)row[j] * 256) + lane;
+            if (!in_corpus(v)) v = p.n_virtual - 1;  // clamp (result discarded)
+            const f32x4 *src = reinterpret_cast<const f32x4 *>(p.corpus + (uint64_t)(uint32_t)v * 256) + lane;
             c[j] = NT ? __builtin_nontemporal_load(src) : *src;
         }
     };
     // the first rows are on their way before the decision is known: they are the same rows either way
     f32x4 cn[U];
-    uint32_t rown[U];
     uint64_t v0 = chunk_v0((uint32_t)wave);
     uint64_t v0n = 0;
-    if (v0 < p.n_virtual) {
-        issue_rows(v0, cn, rown);
+    if (in_corpus(v0)) {
+        issue_rows(v0, cn);
         v0n = chunk_v0(claim());
     }
 
@@ -756,35 +757,134 @@ __global__ void __launch_bounds__(1024) scan_pair_kernel(ScanParams p, PairParam
     // the row loop and the block merge of scan_topk_kernel<4, 4, NT, false>, the share of the queries that are not there skipped.
     // (ONE loop: instantiations behind a branch share the first rows' registers, and the allocator then takes more than either
     // alone -- the select needs this kernel at 64 VGPRs or fewer beside it.)
+    //
+    // The group reducer.  SMT_REDUCE_CHUNK4 runs one basic block per query: an LDS read of the query image with its wait directly
+    // behind it, one wave_sum4 tree alone (its DPP wait states padded with s_nop) and a candidate test of nested exec-mask regions,
+    // four times per chunk although the four queries test the same four rows -- the grouped pass was bound by instruction issue, not
+    // by HBM.  Here the images are read at the top of the chunk, the trees run interleaved (device_utils.h wave_sum4_multi: <c, c>
+    // with the first two queries, then the other two; five trees at once do not fit 64 VGPRs), and ONE distance, ONE compare and ONE
+    // ballot serve the sixteen (row, query) pairs: lane 16 g + j takes query g and row j, against its query's threshold.  The
+    // arithmetic is frozen: per-lane FMA expression, tree and dist_f32 are bit for bit those of scan_topk_kernel<1, 4>, because an
+    // UNCERTAIN answer depends on which near-ties the f32 scan nominated.  That is why query g sits in ROW g of the wave (lanes
+    // 16 g .. 16 g + 3) and not in quad g: the rotations by 4 and 8 of wave_sum4 add the four quads of a row in an order that
+    // depends on the quad -- lanes 4 .. 7 hold (q1 + q0) + (q3 + q2) where lanes 0 .. 3, which the one-query loop reads, hold
+    // (q0 + q3) + (q2 + q1), one rounding apart -- while the same position of another row holds the same bits.
 #define SMT_QUERY_ON(n) ((n) < n_on)
-#define SMT_QUERY_VEC(n) s_q[(n) * 64 + lane]
+#define SMT_ROW_DOT(cj, qv) ((cj).x * (qv).x + (cj).y * (qv).y + (cj).z * (qv).z + (cj).w * (qv).w)
+#define SMT_GROUP_INSERT(n)                                                                                       \
+    do {                                                                                                          \
+        uint32_t m = (((n) < 2 ? pending_lo : pending_hi) >> (16 * ((n) & 1))) & 0xFu;                            \
+        while (m) {                                                                                               \
+            const int j = __builtin_ctz(m);                                                                       \
+            m &= m - 1;                                                                                           \
+            const float d = readlane_f(d4, 16 * (n) + j);                                                         \
+            const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)r_mine, j);                               \
+            const bool less = (ld[n] < d) || (ld[n] == d && lr[n] < r);                                           \
+            const int pos = __popcll(__ballot(less));                                                             \
+            /* (an earlier insert may have moved the threshold, the entry of lane kp - 1: the list is sorted over all */ \
+            /* its lanes and a row comes once, so "(d, r) before the threshold" is "fewer than kp entries before (d, r)" */ \
+            /* -- the same test, without a copy of the threshold in registers)                                          */ \
+            if (pos < kp) {                                                                                       \
+                const float sd = dpp_f<DPP_WAVE_SHR1>(ld[n]);                                                     \
+                const uint32_t sr = dpp_u<DPP_WAVE_SHR1>(lr[n]);                                                  \
+                if (lane > pos) { ld[n] = sd; lr[n] = sr; }                                                       \
+                else if (lane == pos) { ld[n] = d; lr[n] = r; }                                                   \
+                const float td = readlane_f(ld[n], kp - 1);                                                       \
+                const uint32_t tr = (uint32_t)__builtin_amdgcn_readlane((int)lr[n], kp - 1);                      \
+                if (gq == (n)) { s_mine->z = td; s_mine->w = __uint_as_float(tr); }                               \
+            }                                                                                                     \
+        }                                                                                                         \
+    } while (0)
+#define SMT_REDUCE_GROUP4(cq, rq4, VALID)                                                                         \
+    do {                                                                                                          \
+        const f32x4 qv0 = s_q[lane];                                                                              \
+        const bool valid_mine = (uint32_t)jj < (VALID);   /* (VALID: the chunk's real rows, a wave-uniform count) */ \
+        const uint32_t r_mine = (rq4) + (uint32_t)jj;   /* (a real row of the chunk is its first row + j) */      \
+        /* <c, c> and the first two queries (a launch that serves one call reduces an image it does not use: a separate  */ \
+        /* two-tree path costs registers, and the three interleaved trees cost what the two lone ones did).  One image   */ \
+        /* at a time is live, read one query ahead of its products.                                                      */ \
+        float part[3][4], s[3];                                                                                   \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) part[0][j] = SMT_ROW_DOT((cq)[j], (cq)[j]);                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        const f32x4 qv1 = s_q[64 + lane];                                                                         \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) part[1][j] = SMT_ROW_DOT((cq)[j], qv0);                     \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) part[2][j] = SMT_ROW_DOT((cq)[j], qv1);                     \
+        float v3[3];                                                                                              \
+        wave_sum4_multi_head<3>(part, v3, lane);                                                                  \
+        /* twelve partial sums have become three: now there is room for the other two images and this lane's record, */ \
+        /* which land behind the rest of the trees (the barriers keep the scheduler from moving the reads up)         */ \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        const f32x4 qv2 = s_q[128 + lane], qv3 = s_q[192 + lane];                                                 \
+        const f32x4 mine = *s_mine;   /* this lane's query: 1 / |q|, is it zero, threshold distance and row */    \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        wave_sum4_multi_tail<3>(v3, s);                                                                           \
+        const float b2 = s[0];                                                                                    \
+        float ab_mine = gq == 1 ? s[2] : s[1];                                                                    \
+        if (n_on > 2) {                                                                                           \
+            float part2[2][4], s2[2];                                                                             \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                       \
+                part2[0][j] = SMT_ROW_DOT((cq)[j], qv2);                                                          \
+                part2[1][j] = SMT_ROW_DOT((cq)[j], qv3);                                                          \
+            }                                                                                                     \
+            wave_sum4_multi<2>(part2, s2, lane);                                                                  \
+            ab_mine = gq == 2 ? s2[0] : gq == 3 ? s2[1] : ab_mine;                                                \
+        }                                                                                                         \
+        const float d4 = dist_f32(ab_mine, b2, mine.x, mine.y != 0.0f);                                           \
+        /* plain compares joined bitwise: no exec-mask region */                                                  \
+        const uint32_t thr_r_mine = __float_as_uint(mine.w);                                                      \
+        const bool cand = (on_mine & valid_mine) & ((d4 < mine.z) | ((d4 == mine.z) & (r_mine < thr_r_mine)));    \
+        const uint64_t ballot = __ballot(cand);   /* (in two halves: 64-bit scalar compares take the VALU and a register pair) */ \
+        const uint32_t pending_lo = (uint32_t)ballot & 0x000F000Fu, pending_hi = (uint32_t)(ballot >> 32) & 0x000F000Fu; \
+        if (pending_lo | pending_hi) {   /* bits 16 g .. 16 g + 3: list g; query-major, rows ascending, as the per-query loop inserted */ \
+            SMT_GROUP_INSERT(0);                                                                                  \
+            SMT_GROUP_INSERT(1);                                                                                  \
+            SMT_GROUP_INSERT(2);                                                                                  \
+            SMT_GROUP_INSERT(3);                                                                                  \
+        }                                                                                                         \
+    } while (0)
+    const int jj = lane & 3, gq = lane >> 4;         // this lane's row of the chunk and its query of the group
+    const bool on_mine = gq < n_on;                  // (an absent query has thr = +inf and must never insert)
+    // What a lane needs of ITS query -- 1 / |q|, "q is zero", the threshold (distance, row) -- lies in LDS, not in four registers
+    // the loop does not have: a 16-byte record per lane in the key regions, which nothing else touches before the block merge
+    // (behind the barrier that follows the loop).  Read once per chunk behind the first trees, rewritten by the lanes of a list
+    // when an insert moves its threshold; a lane reads only what it wrote itself.
+    f32x4 *s_mine = reinterpret_cast<f32x4 *>(smem_raw) + wave * 64 + lane;
+    {
+        const float rq_mine = gq == 0 ? rq[0] : gq == 1 ? rq[1] : gq == 2 ? rq[2] : rq[3];
+        const bool qz_mine = gq == 0 ? qz[0] : gq == 1 ? qz[1] : gq == 2 ? qz[2] : qz[3];
+        f32x4 rec;
+        rec.x = rq_mine;
+        rec.y = qz_mine ? 1.0f : 0.0f;
+        rec.z = __builtin_inff();
+        rec.w = __uint_as_float(0xFFFFFFFFu);
+        *s_mine = rec;
+    }
     float ld[NQ];
     uint32_t lr[NQ];
-    float thr_d[NQ];
-    uint32_t thr_r[NQ];
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
         ld[n] = __builtin_inff();
         lr[n] = 0xFFFFFFFFu;
-        thr_d[n] = __builtin_inff();
-        thr_r[n] = 0xFFFFFFFFu;
     }
-    while (v0 < p.n_virtual) {
+    while (in_corpus(v0)) {
         f32x4 c[U];
-        uint32_t row[U];
 #pragma unroll
-        for (int j = 0; j < U; ++j) { c[j] = cn[j]; row[j] = rown[j]; }
-        if (v0n < p.n_virtual) issue_rows(v0n, cn, rown);
+        for (int j = 0; j < U; ++j) c[j] = cn[j];
+        if (in_corpus(v0n)) issue_rows(v0n, cn);
         const uint64_t v0nn = chunk_v0(claim());
-#define SMT_VALID_UNF(j) ((v0 + (j)) < p.n_virtual)
-        SMT_REDUCE_CHUNK4(c, row, SMT_VALID_UNF);
-#undef SMT_VALID_UNF
+        const uint64_t left = p.n_virtual - v0;
+        SMT_REDUCE_GROUP4(c, (uint32_t)v0, left < 4 ? (uint32_t)left : 4u);
         v0 = v0n;
         v0n = v0nn;
     }
+#undef SMT_REDUCE_GROUP4
+#undef SMT_GROUP_INSERT
+#undef SMT_ROW_DOT
     __syncthreads();
     // a leader's block counts for the blocks of the calls it serves: the host's running totals count every launch
-    if (threadIdx.x == 0) (void)__hip_atomic_fetch_add(p.gate, (unsigned long long)n_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (thread 0 by wave and lane: threadIdx.x itself would be one more register alive across the loop)
+    if (wave == 0 && lane == 0) (void)__hip_atomic_fetch_add(p.gate, (unsigned long long)n_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
         if (!(SMT_QUERY_ON(n))) break;
@@ -813,7 +913,6 @@ __global__ void __launch_bounds__(1024) scan_pair_kernel(ScanParams p, PairParam
         }
     }
 #undef SMT_QUERY_ON
-#undef SMT_QUERY_VEC
 }
 #undef SMT_REDUCE_CHUNK4
 // dynamic LDS of a scan_pair_kernel launch: the four key regions, the waves' key counts, the query images, the block's control words
@@ -1669,9 +1768,11 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
         // the predecessor" is: every call before the predecessor call is served, and gate_pct per cent of the predecessor call's
         // grid.  When that call is the m-th of n that one pass serves, the point lies at (m - 1 + gate_pct / 100) / n of the pass'
         // blocks: 75 % of a pair's pass and 87.5 % of a full group's at gate_pct = 50, while a leader still at its gate holds
-        // successors back only until their bound.  The default by the sweeps: 50 for plain and paired launches, and
-        // no gate where launches may take two or three calls along (there every gated setting measured 4 us per step behind).
-        const int gate_pct = ctx->tune.scan_gate_pct >= 0 ? ctx->tune.scan_gate_pct : (pair && ctx->tune.scan_pair >= 2) ? 0 : 50;
+        // successors back only until their bound.  The default by the sweeps: 50 for every mode.  (While the grouped
+        // pass ran one tree per query, launches that take two or three calls along ran 4 us per step faster with no gate: two leaders
+        // on a CU filled each other's stalls.  With the group reducer every gate from 5 to 100 measures 48.0 us per step and no gate
+        // 50.1 with a spread of 3 us, profiles/scan_group_loop.json.)
+        const int gate_pct = ctx->tune.scan_gate_pct >= 0 ? ctx->tune.scan_gate_pct : 50;
         if (gate_pct > 0 && ctx->gate_prev_blocks > 0) {
             gate_open = ctx->gate_total - ctx->gate_prev_blocks + (ctx->gate_prev_blocks * (uint64_t)gate_pct + 99) / 100;
             // the bound: the predecessor's rows at 4 TB/s (half the part's HBM rate; 1 KiB rows, 10 ns ticks) + 20 us, at most 0.5 ms (a
