@@ -233,6 +233,49 @@ int smt_wordpiece_tokenize(smt_wordpiece *tok, const char *text, const uint64_t 
                            uint64_t n_lines, uint32_t keep_bytes, uint32_t max_tokens, int drop_unk, uint32_t *ids_out,
                            uint64_t ids_cap, uint64_t *offsets_out, uint8_t *flags_out);
 
+/* Pure-ASCII lines through a per-byte normalizer -> Metaspace -> Unigram on the device (unigram_kernels.hip): the ids of
+ * the host tokenizer's Viterbi (f64 sums, one add per edge; among equal sums for one end the smallest start wins; consecutive
+ * unknowns of a piece fuse).  byte_map[c] is what byte c < 0x80 becomes: an ASCII byte (' ' = a space, which Metaspace turns into
+ * the replacement character and which starts a piece), or 0xFF = dropped.  The vocabulary as tokenizer.json has it: piece i is
+ * [piece_off[i], piece_off[i + 1]) of `pool` with id piece_id[i] and score scores[i]; of a repeated piece the later entry wins.  A
+ * piece with a byte >= 0x80 other than a leading replacement cannot match and is left out of the table (it still counts for the
+ * longest piece).  unk_score: what an unknown character costs (the vocabulary's lowest score - 10); unk_id -1: none.  A line is
+ * FLAGGED for a byte >= 0x80, an added token standing in it, an unknown character on its best path while unk_id is -1, or a piece
+ * whose raw bytes (its space, dropped bytes and a prepended replacement counted) exceed SMT_UG_MAX_WORD.  Everything is copied. */
+#define SMT_UG_MAX_WORD 64
+typedef struct smt_unigram smt_unigram;
+typedef struct smt_unigram_params {
+    const char *pool;
+    const uint32_t *piece_off; /* [n_pieces + 1] */
+    const uint32_t *piece_id;  /* [n_pieces] */
+    uint64_t n_pieces;
+    const double *scores; /* [n_pieces] */
+    double unk_score;
+    int64_t unk_id;
+    const char *replacement; /* Metaspace's replacement character as UTF-8: one character >= U+0080 */
+    uint32_t replacement_len;
+    uint32_t prepend;          /* 0 always, 1 first, 2 never */
+    const uint8_t *byte_map;   /* [128] */
+    const char *added_pool;    /* pure-ASCII added tokens matched on the raw text: a line in which one stands is FLAGGED */
+    const uint32_t *added_off; /* [n_added + 1] */
+    uint32_t n_added;
+} smt_unigram_params;
+int smt_unigram_create(smt_ctx *ctx, const smt_unigram_params *p, smt_unigram **out);
+void smt_unigram_destroy(smt_unigram *tok);
+/* The two passes and the host convenience: the contracts of smt_wordpiece_scan_device / _emit_device / _tokenize, with one
+ * difference: a line can hold one token more than looked-at bytes (the prepended replacement), so
+ * ids_cap >= min(text_bytes, n_lines * keep_bytes) + n_lines + n_patch_ids for the device form, and the looked-at bytes of all
+ * lines + n_lines for smt_unigram_tokenize; less is SMT_E_INVALID before anything is enqueued. */
+int smt_unigram_scan_device(smt_unigram *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev,
+                            const uint32_t *line_len_dev, uint64_t n_lines, uint32_t keep_bytes, uint32_t max_tokens, int drop_unk,
+                            uint32_t *counts_dev, uint8_t *flags_dev, uint32_t *n_flagged_dev);
+int smt_unigram_emit_device(smt_unigram *tok, uint64_t n_lines, const uint64_t *patch_line_dev,
+                            const uint64_t *patch_off_dev /* [n_patch + 1] */, const uint32_t *patch_ids_dev, uint64_t n_patch,
+                            uint64_t n_patch_ids, uint32_t *ids_out_dev, uint64_t ids_cap, uint64_t *offsets_out_dev /* [n_lines + 1] */);
+int smt_unigram_tokenize(smt_unigram *tok, const char *text, const uint64_t *line_begin, const uint32_t *line_len, uint64_t n_lines,
+                         uint32_t keep_bytes, uint32_t max_tokens, int drop_unk, uint32_t *ids_out, uint64_t ids_cap,
+                         uint64_t *offsets_out, uint8_t *flags_out);
+
 /* ------------------------------------------------------------------- corpus
  * Replaces `Document::embeddings: Vec<Vec<f32>>` (src/search/mod.rs:18-22)
  * and the vector half of the workspace store (line_embeddings.qdrant,

@@ -132,6 +132,10 @@ int smt_host_tokenizer_info(smt_host_tokenizer *tok, uint64_t *vocab_size, int64
  * smt_wordpiece on `ctx`, to be freed with smt_wordpiece_destroy.  SMT_E_UNSUPPORTED for a tokenizer whose pure-ASCII lines are not
  * BertNormalizer (or none) -> BertPreTokenizer -> WordPiece: Unigram models, other pre-tokenizers. */
 int smt_host_tokenizer_to_device(smt_host_tokenizer *tok, smt_ctx *ctx, smt_wordpiece **out);
+/* ... and of a Unigram tokenizer: an smt_unigram on `ctx`, to be freed with smt_unigram_destroy.  SMT_E_UNSUPPORTED unless the model
+ * is Unigram behind exactly one Metaspace (split, a replacement character >= U+0080) and its normalizer, if any, is built only of
+ * Lowercase / NFD / StripAccents / BertNormalizer (each acts on an ASCII character without context). */
+int smt_host_tokenizer_to_device_unigram(smt_host_tokenizer *tok, smt_ctx *ctx, smt_unigram **out);
 /* The device tokenizer route of a model.  OFF by default; the environment variable SEMTOOLS_DEVICE_TOKENIZER=1 turns
  * it on when the model is created.  With it on, a batch of lines is packed, uploaded and tokenized on the GPU when the model's
  * tokenizer has a device form (smt_host_tokenizer_to_device), the group has one rank and the full table is resident (or about to be:

@@ -8,7 +8,7 @@
 use std::os::raw::{c_char, c_int, c_void};
 
 macro_rules! opaque { ($($name:ident),*) => { $( #[repr(C)] pub struct $name { _private: [u8; 0] } )* } }
-opaque!(SmtCtx, SmtModel, SmtCorpus, SmtIvfpq, SmtGroup, SmtShardedCorpus, SmtShardedIvfpq, SmtShardedModel, SmtWordpiece);
+opaque!(SmtCtx, SmtModel, SmtCorpus, SmtIvfpq, SmtGroup, SmtShardedCorpus, SmtShardedIvfpq, SmtShardedModel, SmtWordpiece, SmtUnigram);
 
 /// half-open range of corpus rows [begin, end)
 #[repr(C)]
@@ -48,6 +48,26 @@ pub struct SmtWordpieceParams {
     pub n_added: u32,
 }
 
+/// a Unigram vocabulary, Metaspace's settings and the byte table for the device tokenizer (smt_unigram_create copies everything)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SmtUnigramParams {
+    pub pool: *const c_char,
+    pub piece_off: *const u32,
+    pub piece_id: *const u32,
+    pub n_pieces: u64,
+    pub scores: *const f64,
+    pub unk_score: f64,
+    pub unk_id: i64,
+    pub replacement: *const c_char,
+    pub replacement_len: u32,
+    pub prepend: u32,
+    pub byte_map: *const u8,
+    pub added_pool: *const c_char,
+    pub added_off: *const u32,
+    pub n_added: u32,
+}
+
 pub const SMT_OK: c_int = 0;
 pub const SMT_E_INVALID: c_int = -1;
 pub const SMT_E_HIP: c_int = -2;
@@ -64,6 +84,7 @@ pub const SMT_TABLE_I8: c_int = 2;
 pub const SMT_WP_NORMALIZER: c_int = 1;
 pub const SMT_WP_CLEAN_TEXT: c_int = 2;
 pub const SMT_WP_LOWERCASE: c_int = 4;
+pub const SMT_UG_MAX_WORD: c_int = 64;
 pub const SMT_STATUS_PROVED: c_int = 0;
 pub const SMT_STATUS_UNCERTAIN: c_int = 1;
 pub const SMT_STATUS_OVERFLOW: c_int = 2;
@@ -245,6 +266,48 @@ extern "C" {
     ) -> c_int;
     pub fn smt_wordpiece_tokenize(
         tok: *mut SmtWordpiece,
+        text: *const c_char,
+        line_begin: *const u64,
+        line_len: *const u32,
+        n_lines: u64,
+        keep_bytes: u32,
+        max_tokens: u32,
+        drop_unk: c_int,
+        ids_out: *mut u32,
+        ids_cap: u64,
+        offsets_out: *mut u64,
+        flags_out: *mut u8,
+    ) -> c_int;
+    pub fn smt_unigram_create(ctx: *mut SmtCtx, p: *const SmtUnigramParams, out: *mut *mut SmtUnigram) -> c_int;
+    pub fn smt_unigram_destroy(tok: *mut SmtUnigram);
+    pub fn smt_unigram_scan_device(
+        tok: *mut SmtUnigram,
+        text_dev: *const u8,
+        text_bytes: u64,
+        line_begin_dev: *const u64,
+        line_len_dev: *const u32,
+        n_lines: u64,
+        keep_bytes: u32,
+        max_tokens: u32,
+        drop_unk: c_int,
+        counts_dev: *mut u32,
+        flags_dev: *mut u8,
+        n_flagged_dev: *mut u32,
+    ) -> c_int;
+    pub fn smt_unigram_emit_device(
+        tok: *mut SmtUnigram,
+        n_lines: u64,
+        patch_line_dev: *const u64,
+        patch_off_dev: *const u64,
+        patch_ids_dev: *const u32,
+        n_patch: u64,
+        n_patch_ids: u64,
+        ids_out_dev: *mut u32,
+        ids_cap: u64,
+        offsets_out_dev: *mut u64,
+    ) -> c_int;
+    pub fn smt_unigram_tokenize(
+        tok: *mut SmtUnigram,
         text: *const c_char,
         line_begin: *const u64,
         line_len: *const u32,

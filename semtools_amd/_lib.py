@@ -47,8 +47,11 @@ EXPORTS = [
     "smt_sharded_model_create_indexed", "smt_sharded_model_create_from_file_indexed", "smt_sharded_model_token_info",
     "smt_debug_scan_pairs", "smt_debug_image_tile", "smt_debug_scan_groups", "smt_debug_nominations",
     "smt_wordpiece_create", "smt_wordpiece_destroy", "smt_wordpiece_scan_device", "smt_wordpiece_emit_device", "smt_wordpiece_tokenize",
+    "smt_unigram_create", "smt_unigram_destroy", "smt_unigram_scan_device", "smt_unigram_emit_device", "smt_unigram_tokenize",
 ]
 WP_NORMALIZER, WP_CLEAN_TEXT, WP_LOWERCASE = 1, 2, 4
+UG_MAX_WORD = 64
+UG_PREPEND = {"always": 0, "first": 1, "never": 2}
 TABLE_F32, TABLE_F16, TABLE_I8 = 0, 1, 2
 TABLE_DTYPES = {np.dtype(np.float32): TABLE_F32, np.dtype(np.float16): TABLE_F16, np.dtype(np.int8): TABLE_I8}
 TABLE_NP = {v: k for k, v in TABLE_DTYPES.items()}
@@ -104,7 +107,7 @@ HOST_EXPORTS = [
     "smt_host_split_lines", "smt_host_to_lowercase",
     "smt_host_group_from_spec", "smt_host_model_create_group", "smt_host_model_from_dir_group",
     "smt_host_workspace_use_group", "smt_host_workspace_status_group", "smt_host_workspace_prune_group",
-    "smt_host_model_table_info", "smt_host_model_token_info", "smt_host_tokenizer_to_device",
+    "smt_host_model_table_info", "smt_host_model_token_info", "smt_host_tokenizer_to_device", "smt_host_tokenizer_to_device_unigram",
     "smt_host_model_set_device_tokenizer", "smt_host_debug_device_tokenized",
 ]
 TOKENIZE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
@@ -124,6 +127,13 @@ class SmtWordpieceParams(C.Structure):
     _fields_ = [("pool", C.c_char_p), ("piece_off", C.c_void_p), ("piece_id", C.c_void_p), ("n_pieces", C.c_uint64),
                 ("prefix", C.c_char_p), ("prefix_len", C.c_uint32), ("unk_id", C.c_int64), ("max_input_chars_per_word", C.c_uint32),
                 ("flags", C.c_uint32), ("added_pool", C.c_char_p), ("added_off", C.c_void_p), ("n_added", C.c_uint32)]
+
+
+class SmtUnigramParams(C.Structure):
+    _fields_ = [("pool", C.c_char_p), ("piece_off", C.c_void_p), ("piece_id", C.c_void_p), ("n_pieces", C.c_uint64),
+                ("scores", C.c_void_p), ("unk_score", C.c_double), ("unk_id", C.c_int64), ("replacement", C.c_char_p),
+                ("replacement_len", C.c_uint32), ("prepend", C.c_uint32), ("byte_map", C.c_void_p), ("added_pool", C.c_char_p),
+                ("added_off", C.c_void_p), ("n_added", C.c_uint32)]
 
 
 class SmtError(RuntimeError):
@@ -198,6 +208,12 @@ def lib():
     L.smt_wordpiece_scan_device.argtypes = [vp, vp, u64, vp, vp, u64, u32, u32, i32, vp, vp, vp]
     L.smt_wordpiece_emit_device.argtypes = [vp, u64, vp, vp, vp, u64, u64, vp, u64, vp]
     L.smt_wordpiece_tokenize.argtypes = [vp, vp, vp, vp, u64, u32, u32, i32, vp, u64, vp, vp]
+    L.smt_unigram_create.argtypes = [vp, P(SmtUnigramParams), P(vp)]
+    L.smt_unigram_destroy.argtypes = [vp]
+    L.smt_unigram_destroy.restype = None
+    L.smt_unigram_scan_device.argtypes = [vp, vp, u64, vp, vp, u64, u32, u32, i32, vp, vp, vp]
+    L.smt_unigram_emit_device.argtypes = [vp, u64, vp, vp, vp, u64, u64, vp, u64, vp]
+    L.smt_unigram_tokenize.argtypes = [vp, vp, vp, vp, u64, u32, u32, i32, vp, u64, vp, vp]
     L.smt_corpus_create.argtypes = [vp, u32, u64, P(vp)]
     L.smt_corpus_from_device.argtypes = [vp, vp, u64, u32, P(vp)]
     L.smt_corpus_destroy.argtypes = [vp]
@@ -360,6 +376,7 @@ def lib():
     L.smt_host_tokenizer_encode.argtypes = [vp, C.c_char_p, vp, u64, P(u64)]
     L.smt_host_tokenizer_info.argtypes = [vp, P(u64), P(C.c_int64), P(u64)]
     L.smt_host_tokenizer_to_device.argtypes = [vp, vp, P(vp)]
+    L.smt_host_tokenizer_to_device_unigram.argtypes = [vp, vp, P(vp)]
     L.smt_host_model_set_device_tokenizer.argtypes = [vp, i32]
     L.smt_host_debug_device_tokenized.argtypes = [vp, P(u64)]
     L.smt_host_timing_json.argtypes = []

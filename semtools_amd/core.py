@@ -319,6 +319,90 @@ class WordPiece:
                                                   int(n_patch_ids), vp(ids_out_ptr), int(ids_cap), vp(offsets_out_ptr)))
 
 
+class Unigram:
+    """The device tokenizer (smt_unigram): pure-ASCII lines through a per-byte normalizer -> Metaspace -> Unigram.
+
+    Unigram(ctx, vocab=[(piece, score), ..], unk_id=.., replacement="\u2581", prepend="always", byte_map=.., added=[..]) builds it
+    from a vocabulary (the id of a piece is its index; unk_score defaults to the lowest score - 10; byte_map: 128 entries, the byte
+    a byte becomes or 0xFF for dropped, default the identity); Unigram(ctx, host_tokenizer=<smt_host_tokenizer handle>) takes the
+    device form of a loaded tokenizer.json (SmtError with code SMT_E_UNSUPPORTED when it has none)."""
+
+    pack = staticmethod(WordPiece.pack)
+
+    def __init__(self, ctx, vocab=None, unk_id=-1, replacement="\u2581", prepend="always", byte_map=None, added=(), unk_score=None,
+                 host_tokenizer=None):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        if host_tokenizer is not None:
+            L.check(L.lib().smt_host_tokenizer_to_device_unigram(host_tokenizer, ctx._h, C.byref(self._h)))
+            return
+        pieces = [(p.encode() if isinstance(p, str) else bytes(p), float(s)) for p, s in vocab]
+        pool = b"".join(p for p, _ in pieces)
+        off = np.zeros(len(pieces) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(p) for p, _ in pieces], dtype=np.uint64)
+        ids = np.arange(len(pieces), dtype=np.uint32)
+        scores = np.array([s for _, s in pieces], dtype=np.float64)
+        if unk_score is None:
+            unk_score = (float(scores.min()) if len(pieces) else 0.0) - 10.0
+        added_b = [a.encode() if isinstance(a, str) else bytes(a) for a in added]
+        aoff = np.zeros(len(added_b) + 1, dtype=np.uint32)
+        aoff[1:] = np.cumsum([len(a) for a in added_b], dtype=np.uint64)
+        rep = replacement.encode() if isinstance(replacement, str) else bytes(replacement)
+        bmap = np.arange(128, dtype=np.uint8) if byte_map is None else np.ascontiguousarray(byte_map, dtype=np.uint8)
+        if bmap.size != 128:
+            raise ValueError("byte_map has 128 entries")
+        prm = L.SmtUnigramParams(pool, L.np_ptr(off), L.np_ptr(ids), len(pieces), L.np_ptr(scores), float(unk_score), int(unk_id), rep,
+                                 len(rep), int(L.UG_PREPEND.get(prepend, prepend)), L.np_ptr(bmap), b"".join(added_b), L.np_ptr(aoff),
+                                 len(added_b))
+        L.check(L.lib().smt_unigram_create(ctx._h, C.byref(prm), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            L.lib().smt_unigram_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # best effort
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def tokenize(self, lines=None, text=None, line_begin=None, line_len=None, keep_bytes=0, max_tokens=0, drop_unk=True, ids_cap=None):
+        """-> (ids uint32, offsets uint64 [n + 1], flags uint8 [n]) through smt_unigram_tokenize.  `lines` are packed back to
+        back; or give text / line_begin / line_len.  ids_cap defaults to the looked-at bytes of all lines + one per line."""
+        if lines is not None:
+            text, line_begin, line_len = self.pack(lines)
+        line_begin = np.ascontiguousarray(line_begin, dtype=np.uint64)
+        line_len = np.ascontiguousarray(line_len, dtype=np.uint32)
+        n = len(line_len)
+        if ids_cap is None:
+            ids_cap = int(np.minimum(line_len, keep_bytes).sum() if keep_bytes else line_len.sum()) + n
+        ids = np.zeros(max(int(ids_cap), 1), dtype=np.uint32)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        flags = np.zeros(max(n, 1), dtype=np.uint8)
+        buf = C.create_string_buffer(bytes(text), max(len(text), 1))
+        L.check(L.lib().smt_unigram_tokenize(self._h, C.cast(buf, C.c_void_p), L.np_ptr(line_begin), L.np_ptr(line_len), n, int(keep_bytes),
+                                             int(max_tokens), int(bool(drop_unk)), L.np_ptr(ids), int(ids_cap), L.np_ptr(offsets),
+                                             L.np_ptr(flags)))
+        return ids[:int(offsets[n])].copy(), offsets, flags[:n].copy()
+
+    def scan_device(self, text_ptr, text_bytes, line_begin_ptr, line_len_ptr, n_lines, keep_bytes, max_tokens, drop_unk, counts_ptr, flags_ptr,
+                    n_flagged_ptr):
+        """pass 1 on raw device pointers (ints); enqueued on the context's stream"""
+        vp = C.c_void_p
+        L.check(L.lib().smt_unigram_scan_device(self._h, vp(text_ptr), int(text_bytes), vp(line_begin_ptr), vp(line_len_ptr), int(n_lines),
+                                                int(keep_bytes), int(max_tokens), int(bool(drop_unk)), vp(counts_ptr), vp(flags_ptr),
+                                                vp(n_flagged_ptr)))
+
+    def emit_device(self, n_lines, ids_out_ptr, ids_cap, offsets_out_ptr, patch_line_ptr=None, patch_off_ptr=None, patch_ids_ptr=None, n_patch=0,
+                    n_patch_ids=0):
+        """pass 2 on raw device pointers (ints); enqueued on the context's stream.  ids_cap >= min(text bytes, n_lines * keep_bytes)
+        + n_lines + n_patch_ids"""
+        vp = C.c_void_p
+        L.check(L.lib().smt_unigram_emit_device(self._h, int(n_lines), vp(patch_line_ptr), vp(patch_off_ptr), vp(patch_ids_ptr), int(n_patch),
+                                                int(n_patch_ids), vp(ids_out_ptr), int(ids_cap), vp(offsets_out_ptr)))
+
+
 class Corpus:
     """Row-major f32 [rows x 256] matrix resident in HBM (smt_corpus)."""
 

@@ -1,6 +1,6 @@
 // device_tokenize.cpp -- the host layer's device route for a batch of lines: pack the line bytes back to back into a
-// pinned buffer, upload, tokenize on the device (smt_wordpiece_scan_device), tokenize the lines the kernel flags with the host
-// tokenizer, splice them in (smt_wordpiece_emit_device) and pool the device CSR with K1 -- the token ids never visit the host
+// pinned buffer, upload, tokenize on the device (smt_wordpiece_scan_device or smt_unigram_scan_device), tokenize the lines the kernel
+// flags with the host tokenizer, splice them in (smt_*_emit_device) and pool the device CSR with K1 -- the token ids never visit the host
 // unless a caller wants them (the workspace's cached ids).  One-rank groups only; StaticModel decides when the route applies.
 #include <chrono>
 
@@ -15,7 +15,8 @@ namespace search {
 struct DeviceTokenRoute {
     smt_group *group = nullptr;
     smt_ctx *ctx = nullptr;
-    smt_wordpiece *wp = nullptr;
+    smt_wordpiece *wp = nullptr;   // one of the two
+    smt_unigram *ug = nullptr;
     struct Slot {   // one batch packed for upload: line_begin u64 [n] | line_len u32 [n] | text
         char *pin = nullptr;
         size_t pin_bytes = 0;
@@ -64,17 +65,26 @@ DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok)
 {
     int n_ranks = 0;
     if (smt_group_info(group, &n_ranks, nullptr, nullptr, nullptr, nullptr) != SMT_OK || n_ranks != 1) return nullptr;
-    WordpieceExport x;
-    if (!tok.export_wordpiece(x)) return nullptr;
     smt_ctx *ctx = smt_group_ctx(group, 0);
     if (!ctx) return nullptr;
-    const smt_wordpiece_params p = x.params();
     smt_wordpiece *wp = nullptr;
-    api_ok(smt_wordpiece_create(ctx, &p, &wp), "smt_wordpiece_create");
+    smt_unigram *ug = nullptr;
+    WordpieceExport x;
+    UnigramExport u;
+    if (tok.export_wordpiece(x)) {
+        const smt_wordpiece_params p = x.params();
+        api_ok(smt_wordpiece_create(ctx, &p, &wp), "smt_wordpiece_create");
+    } else if (tok.export_unigram(u)) {
+        const smt_unigram_params p = u.params();
+        api_ok(smt_unigram_create(ctx, &p, &ug), "smt_unigram_create");
+    } else {
+        return nullptr;
+    }
     auto *r = new DeviceTokenRoute();
     r->group = group;
     r->ctx = ctx;
     r->wp = wp;
+    r->ug = ug;
     return r;
 }
 
@@ -84,6 +94,7 @@ void device_route_destroy(DeviceTokenRoute *r)
     (void)hipSetDevice(r->ctx->device);
     (void)hipStreamSynchronize(r->ctx->stream);
     smt_wordpiece_destroy(r->wp);
+    smt_unigram_destroy(r->ug);
     for (auto &s : r->slot) if (s.pin) (void)hipHostFree(s.pin);
     for (void *p : {r->d_main, r->d_ids, r->d_patch, r->d_rows}) if (p) (void)hipFree(p);
     delete r;
@@ -145,10 +156,15 @@ uint64_t device_route_run(DeviceTokenRoute *r, int which, smt_sharded_model *mod
     char *d = static_cast<char *>(r->d_main);
     hip_ok(hipMemcpyAsync(d, s.pin, s.up_bytes, hipMemcpyHostToDevice, st), "upload of the packed lines");
     uint8_t *d_flags = reinterpret_cast<uint8_t *>(d + o_flags);
-    api_ok(smt_wordpiece_scan_device(r->wp, reinterpret_cast<const uint8_t *>(d + s.o_text), s.text_bytes, reinterpret_cast<const uint64_t *>(d),
-                                     reinterpret_cast<const uint32_t *>(d + s.o_len), n, keep_bytes, max_tokens, drop_unk ? 1 : 0,
-                                     reinterpret_cast<uint32_t *>(d + o_counts), d_flags, reinterpret_cast<uint32_t *>(d + o_nflag)),
-           "pass 1");
+    {
+        const uint8_t *text = reinterpret_cast<const uint8_t *>(d + s.o_text);
+        const uint64_t *begin = reinterpret_cast<const uint64_t *>(d);
+        const uint32_t *len = reinterpret_cast<const uint32_t *>(d + s.o_len);
+        uint32_t *counts = reinterpret_cast<uint32_t *>(d + o_counts), *nflag = reinterpret_cast<uint32_t *>(d + o_nflag);
+        api_ok(r->wp ? smt_wordpiece_scan_device(r->wp, text, s.text_bytes, begin, len, n, keep_bytes, max_tokens, drop_unk ? 1 : 0, counts, d_flags, nflag)
+                     : smt_unigram_scan_device(r->ug, text, s.text_bytes, begin, len, n, keep_bytes, max_tokens, drop_unk ? 1 : 0, counts, d_flags, nflag),
+               "pass 1");
+    }
     uint32_t n_flagged = 0;
     hip_ok(hipMemcpyAsync(&n_flagged, d + o_nflag, 4, hipMemcpyDeviceToHost, st), "n_flagged");
     hip_ok(hipStreamSynchronize(st), "pass 1");
@@ -168,7 +184,8 @@ uint64_t device_route_run(DeviceTokenRoute *r, int which, smt_sharded_model *mod
     }
     t0 = std::chrono::steady_clock::now();
     const uint64_t n_patch = patch_line.size(), n_patch_ids = patch_ids.size();
-    const uint64_t ids_cap = (keep_bytes ? std::min<uint64_t>(s.text_bytes, n * (uint64_t)keep_bytes) : s.text_bytes) + n_patch_ids;
+    // (a Unigram line can hold one token more than looked-at bytes: the prepended replacement)
+    const uint64_t ids_cap = (keep_bytes ? std::min<uint64_t>(s.text_bytes, n * (uint64_t)keep_bytes) : s.text_bytes) + (r->ug ? n : 0) + n_patch_ids;
     grow_device(r, &r->d_ids, &r->ids_bytes, (size_t)ids_cap * 4 + 16, "token ids");
     const size_t p_off = up16(n_patch * 8), p_ids = p_off + up16((n_patch + 1) * 8);
     char *dp = nullptr;
@@ -181,9 +198,13 @@ uint64_t device_route_run(DeviceTokenRoute *r, int which, smt_sharded_model *mod
     }
     uint32_t *d_ids = static_cast<uint32_t *>(r->d_ids);
     uint64_t *d_off = reinterpret_cast<uint64_t *>(d + o_off);
-    api_ok(smt_wordpiece_emit_device(r->wp, n, reinterpret_cast<const uint64_t *>(dp), dp ? reinterpret_cast<const uint64_t *>(dp + p_off) : nullptr,
-                                     dp ? reinterpret_cast<const uint32_t *>(dp + p_ids) : nullptr, n_patch, n_patch_ids, d_ids, ids_cap, d_off),
-           "pass 2");
+    {
+        const uint64_t *pl = reinterpret_cast<const uint64_t *>(dp), *po = dp ? reinterpret_cast<const uint64_t *>(dp + p_off) : nullptr;
+        const uint32_t *pi = dp ? reinterpret_cast<const uint32_t *>(dp + p_ids) : nullptr;
+        api_ok(r->wp ? smt_wordpiece_emit_device(r->wp, n, pl, po, pi, n_patch, n_patch_ids, d_ids, ids_cap, d_off)
+                     : smt_unigram_emit_device(r->ug, n, pl, po, pi, n_patch, n_patch_ids, d_ids, ids_cap, d_off),
+               "pass 2");
+    }
     // ---- K1 on the device CSR (the lines are already truncated: no cap here, as on the host path)
     smt_model *m = model->model.at(0);
     if (corpus) api_ok(smt::sharded_embed_device_append(model, d_ids, d_off, n, corpus), "K1 into the corpus");   // (waits for the stream)

@@ -626,7 +626,54 @@ public:
         return true;
     }
 
+    // Unigram behind exactly one Metaspace (split, a replacement >= U+0080) and a normalizer that acts on an ASCII character without
+    // context: the byte table is what apply_normalizer makes of every single byte
+    bool export_unigram(UnigramExport &x) const override
+    {
+        if (wordpiece_ || !has_pre_) return false;
+        const PreTokenizer *ms = &pre_;
+        if (ms->kind == PreTokenizer::Seq) {
+            if (ms->children.size() != 1) return false;
+            ms = &ms->children[0];
+        }
+        if (ms->kind != PreTokenizer::Metaspace || !ms->split || ms->replacement < 0x80) return false;
+        if (has_norm_ && !bytewise(norm_)) return false;
+        for (uint32_t c = 0; c < 128; ++c) {
+            U32 s(1, c);
+            if (has_norm_) apply_normalizer(norm_, s);
+            if (s.empty()) x.byte_map[c] = 0xFF;
+            else if (s.size() == 1 && s[0] < 0x80) x.byte_map[c] = (uint8_t)s[0];
+            else return false;
+        }
+        vocab_.export_pieces(x.pool, x.piece_off, x.piece_id);
+        if (x.piece_id.size() != scores_.size()) return false;
+        x.scores = scores_;
+        x.unk_score = unk_score_;
+        x.unk_id = unk_ ? (int64_t)*unk_ : -1;
+        x.replacement.clear();
+        encode_cp(x.replacement, ms->replacement);
+        x.prepend = (uint32_t)ms->prepend;
+        x.added_pool.clear();
+        x.added_off.assign(1, 0);
+        for (const AddedToken &t : added_ascii_) {
+            x.added_pool.append(t.bytes);
+            x.added_off.push_back((uint32_t)x.added_pool.size());
+        }
+        return true;
+    }
+
 private:
+    // a normalizer built only of components that map an ASCII character on its own (no Strip, no Replace)
+    static bool bytewise(const Normalizer &n)
+    {
+        switch (n.kind) {
+            case Normalizer::Lower: case Normalizer::Nfd: case Normalizer::StripAcc: case Normalizer::Bert: return true;
+            case Normalizer::Seq:
+                for (const Normalizer &c : n.children) if (!bytewise(c)) return false;
+                return true;
+            default: return false;
+        }
+    }
     static bool is_word_char(uint32_t c) { return c == '_' || (c < 0x80 ? isalnum((int)c) != 0 : !is_white_space(c) && !is_punct_cat(c)); }
 
     void encode_section(U32 s, bool first_section, std::vector<uint32_t> &ids) const

@@ -72,6 +72,37 @@ struct WordpieceExport {
     }
 };
 
+// what a Unigram tokenizer whose pure-ASCII lines are a per-byte normalizer -> Metaspace -> Unigram hands the device tokenizer
+// (include/semtools_hip.h smt_unigram_params, which points into these)
+struct UnigramExport {
+    std::string pool, replacement, added_pool;
+    std::vector<uint32_t> piece_off, piece_id, added_off;
+    std::vector<double> scores;
+    double unk_score = 0.0;
+    int64_t unk_id = -1;
+    uint32_t prepend = 0;
+    uint8_t byte_map[128] = {};
+    smt_unigram_params params() const   // (points into this object)
+    {
+        smt_unigram_params p{};
+        p.pool = pool.data();
+        p.piece_off = piece_off.data();
+        p.piece_id = piece_id.data();
+        p.n_pieces = piece_id.size();
+        p.scores = scores.data();
+        p.unk_score = unk_score;
+        p.unk_id = unk_id;
+        p.replacement = replacement.data();
+        p.replacement_len = (uint32_t)replacement.size();
+        p.prepend = prepend;
+        p.byte_map = byte_map;
+        p.added_pool = added_pool.data();
+        p.added_off = added_off.data();
+        p.n_added = (uint32_t)(added_off.empty() ? 0 : added_off.size() - 1);
+        return p;
+    }
+};
+
 class Tokenizer {
 public:
     virtual ~Tokenizer() = default;
@@ -82,9 +113,10 @@ public:
     // lines worth starting one more thread for, in a batch (a thread costs ~30 us to start: ~0.15 us per hashed line, ~1-4 us per
     // line through a tokenizer.json pipeline)
     virtual size_t lines_per_thread() const { return 8192; }
-    // optional: the device form of this tokenizer's ASCII path.  false: not supported (Unigram, other pre-tokenizers, the vocab.txt,
-    // hash and callback tokenizers)
+    // optional: the device form of this tokenizer's ASCII path, for one of the two families the device covers.  false: not this
+    // family, or not supported (other pre-tokenizers, Strip / Replace normalizers, the vocab.txt, hash and callback tokenizers)
     virtual bool export_wordpiece(WordpieceExport &) const { return false; }
+    virtual bool export_unigram(UnigramExport &) const { return false; }
 };
 // whitespace words looked up in a vocab file (one token per line, id = line index)
 std::unique_ptr<Tokenizer> make_vocab_tokenizer(const std::string &vocab_path, const std::string &unk_token);
@@ -118,7 +150,7 @@ struct TokenCsr {
     std::vector<uint32_t> lens;
 };
 
-// The device route of a batch of lines (device_tokenize.cpp): text up, WordPiece on the device, flagged lines through the host
+// The device route of a batch of lines (device_tokenize.cpp): text up, WordPiece or Unigram on the device, flagged lines through the host
 // tokenizer, K1 on the device CSR.  One-rank groups and tokenizers with a device form only (device_route_create: nullptr otherwise).
 struct DeviceTokenRoute;
 // fills the CSR (ids, offsets [lines.size() + 1]) of the batch's flagged lines, given by their index in the batch

@@ -323,6 +323,21 @@ int smt_host_tokenizer_to_device(smt_host_tokenizer *tok, smt_ctx *ctx, smt_word
     } catch (const std::exception &e) { return fail(e); }
 }
 
+int smt_host_tokenizer_to_device_unigram(smt_host_tokenizer *tok, smt_ctx *ctx, smt_unigram **out)
+{
+    if (!tok || !out) { smt::set_error("null argument"); return SMT_E_INVALID; }
+    *out = nullptr;
+    try {
+        UnigramExport x;
+        if (!tok->t->export_unigram(x)) {
+            smt::set_error("this tokenizer has no Unigram device form (pure-ASCII lines of a per-byte normalizer -> Metaspace -> Unigram only)");
+            return SMT_E_UNSUPPORTED;
+        }
+        const smt_unigram_params p = x.params();
+        return smt_unigram_create(ctx, &p, out);   // (no context: SMT_E_HIP on a machine without a device)
+    } catch (const std::exception &e) { return fail(e); }
+}
+
 static int host_model_from_dir(smt_ctx *ctx, smt_group *group, const char *dir, smt_host_model **out)
 {
     if ((!ctx && !group) || !dir || !out) { smt::set_error("null argument"); return SMT_E_INVALID; }

@@ -18,14 +18,15 @@
 #include <vector>
 
 #include "common.h"
+#include "tokenize_pass2.h"
 #include "wordpiece_bytes.h"
 
 namespace {
 
-constexpr uint32_t WP_NONE = 0xFFFFFFFFu;   // an ids_tmp slot that holds no token
-constexpr unsigned SCAN_THREADS = 256;      // pass 1: one position per thread
-constexpr unsigned EMIT_THREADS = 256;      // pass 2: four slots per thread
-constexpr unsigned EMIT_CHUNK = EMIT_THREADS * 4;
+constexpr uint32_t WP_NONE = smt::TOK_NONE;   // an ids_tmp slot that holds no token
+constexpr unsigned SCAN_THREADS = 256;        // pass 1: one position per thread
+constexpr unsigned EMIT_THREADS = smt::TOK_EMIT_THREADS;   // pass 2: four slots per thread
+constexpr unsigned EMIT_CHUNK = smt::TOK_EMIT_CHUNK;
 
 struct WpTable {
     const unsigned long long *slots;   // (tag << 32) | entry + 1; 0 = empty
@@ -323,29 +324,18 @@ struct smt_wordpiece {
     void *d_table = nullptr;          // slots | entries | pool | byte tables | added pool | added offsets
     WpTable T{};
     // the state of the last scan
-    uint32_t *d_ids_tmp = nullptr;    // [slots_cap]
-    uint64_t slots_cap = 0;
-    void *d_lines = nullptr;          // raw_count u32 [n] | final_count u32 [n] | raw_base u64 [n + 1]
-    uint64_t lines_cap = 0;
-    void *d_chunks = nullptr;         // chunk_count u32 [c] | chunk_base u64 [c + 1]
-    uint64_t chunks_cap = 0;
+    smt::TokScratch S;
     bool scanned = false;
     uint64_t text_bytes = 0, n_lines = 0, ids_bound = 0;
     const uint64_t *line_begin = nullptr;
     const uint32_t *counts = nullptr;
     const uint8_t *flags = nullptr;
-
-    uint32_t *raw_count() const { return static_cast<uint32_t *>(d_lines); }
-    uint32_t *final_count() const { return raw_count() + lines_cap; }
-    uint64_t *raw_base() const { return reinterpret_cast<uint64_t *>(final_count() + lines_cap); }
-    uint32_t *chunk_count() const { return static_cast<uint32_t *>(d_chunks); }
-    uint64_t *chunk_base() const { return reinterpret_cast<uint64_t *>(chunk_count() + chunks_cap); }
 };
 
 namespace smt {
 
 // a compute entry point handed a null handle: on a machine without a device that is what every caller ends up with
-static int null_handle(const char *what)
+int tok_null_handle(const char *what)
 {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
@@ -356,6 +346,8 @@ static int null_handle(const char *what)
     set_error("invalid argument: %s (null handle)", what);
     return SMT_E_INVALID;
 }
+
+static int null_handle(const char *what) { return tok_null_handle(what); }
 
 static int grow(smt_ctx *ctx, void **p, size_t bytes, const char *what)
 {
@@ -371,6 +363,118 @@ static uint64_t hash_bytes(const char *b, size_t n, uint64_t h = WP_HASH_SEED)
 {
     for (size_t i = 0; i < n; ++i) h = (h ^ (uint8_t)b[i]) * WP_HASH_MUL;
     return h;
+}
+
+void tok_build_table(const char *pool, const std::vector<TokEntry> &in, TokTable &out)
+{
+    uint32_t cap = 16;
+    while ((uint64_t)cap < 2 * (uint64_t)in.size()) cap <<= 1;
+    const uint32_t mask = cap - 1;
+    out.mask = mask;
+    out.slots.assign(cap, 0);
+    out.ents.clear();
+    out.winner.clear();
+    out.ents.reserve(in.size());
+    out.winner.reserve(in.size());
+    for (const TokEntry &e : in) {
+        uint32_t idx = (uint32_t)e.h & mask;
+        const uint32_t tag = (uint32_t)(e.h >> 32);
+        for (;;) {
+            const unsigned long long s = out.slots[idx];
+            if (s == 0) {
+                out.ents.push_back(make_uint4(e.off, e.len, e.id, e.kind));
+                out.winner.push_back(e.src);
+                out.slots[idx] = ((unsigned long long)tag << 32) | (unsigned long long)out.ents.size();
+                break;
+            }
+            uint4 &o = out.ents[(uint32_t)s - 1];
+            if ((uint32_t)(s >> 32) == tag && o.w == e.kind && o.y == e.len && memcmp(pool + o.x, pool + e.off, e.len) == 0) {
+                o.z = e.id;   // a repeated piece: the later entry wins
+                out.winner[(uint32_t)s - 1] = e.src;
+                break;
+            }
+            idx = (idx + 1) & mask;   // (load <= 0.5: an empty slot exists)
+        }
+    }
+}
+
+int tok_scratch_reserve(smt_ctx *ctx, TokScratch &s, uint64_t n_slots, uint64_t n_lines)
+{
+    int rc;
+    const uint64_t chunks = TokScratch::chunks_of(n_slots);
+    if (chunks * EMIT_CHUNK > s.slots_cap) {
+        s.slots_cap = 0;
+        if ((rc = grow(ctx, reinterpret_cast<void **>(&s.d_ids_tmp), (size_t)chunks * EMIT_CHUNK * 4, "tokenizer id slots"))) return rc;
+        s.slots_cap = chunks * EMIT_CHUNK;
+    }
+    if (chunks > s.chunks_cap) {
+        s.chunks_cap = 0;
+        if ((rc = grow(ctx, &s.d_chunks, (size_t)chunks * 4 + ((size_t)chunks + 1) * 8 + 8, "tokenizer chunk sums"))) return rc;
+        s.chunks_cap = chunks + (chunks & 1);   // (keeps the u64 part 8-byte aligned)
+    }
+    if (n_lines > s.lines_cap) {
+        s.lines_cap = 0;
+        if ((rc = grow(ctx, &s.d_lines, (size_t)n_lines * 8 + ((size_t)n_lines + 1) * 8 + (size_t)n_lines * 8, "tokenizer line sums"))) return rc;
+        s.lines_cap = n_lines;
+    }
+    return SMT_OK;
+}
+
+int tok_scratch_clear(smt_ctx *ctx, TokScratch &s, uint64_t n_slots, uint64_t n_lines)
+{
+    const uint64_t chunks = TokScratch::chunks_of(n_slots);
+    if (n_lines) SMT_HIP_CHECK(hipMemsetAsync(s.raw_count(), 0, (size_t)n_lines * 4, ctx->stream));
+    if (chunks) SMT_HIP_CHECK(hipMemsetAsync(s.d_ids_tmp, 0xFF, (size_t)chunks * EMIT_CHUNK * 4, ctx->stream));
+    return SMT_OK;
+}
+
+void tok_scratch_free(TokScratch &s)
+{
+    if (s.d_ids_tmp) (void)hipFree(s.d_ids_tmp);
+    if (s.d_lines) (void)hipFree(s.d_lines);
+    if (s.d_chunks) (void)hipFree(s.d_chunks);
+    s = TokScratch();
+}
+
+int tok_line_counts(smt_ctx *ctx, const TokScratch &s, uint64_t n_lines, const uint8_t *flags_dev, uint32_t max_tokens, uint32_t *counts_dev,
+                    uint32_t *n_flagged_dev)
+{
+    if (!n_lines) return SMT_OK;
+    hipLaunchKernelGGL(wp_lines_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, ctx->stream, n_lines, s.raw_count(), flags_dev,
+                       max_tokens, counts_dev, n_flagged_dev);
+    SMT_HIP_CHECK(hipGetLastError());
+    return SMT_OK;
+}
+
+int tok_pass2(smt_ctx *ctx, const TokScratch &s, uint64_t n_slots, const uint64_t *slot_begin_dev, uint64_t n_lines, const uint32_t *counts_dev,
+              const uint8_t *flags_dev, const uint64_t *patch_line_dev, const uint64_t *patch_off_dev, const uint32_t *patch_ids_dev,
+              uint64_t n_patch, uint64_t n_patch_ids, uint32_t *ids_out_dev, uint64_t ids_cap, uint64_t *offsets_out_dev)
+{
+    hipStream_t st = ctx->stream;
+    if (n_lines) SMT_HIP_CHECK(hipMemcpyAsync(s.final_count(), counts_dev, (size_t)n_lines * 4, hipMemcpyDeviceToDevice, st));
+    if (n_patch) {
+        hipLaunchKernelGGL(wp_patch_counts_kernel, dim3((unsigned)((n_patch + 255) / 256)), dim3(256), 0, st, n_patch, n_lines, patch_line_dev,
+                           patch_off_dev, flags_dev, s.final_count());
+        SMT_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(wp_exscan_kernel, dim3(1), dim3(1024), 0, st, s.final_count(), n_lines, offsets_out_dev);
+    SMT_HIP_CHECK(hipGetLastError());
+    const uint64_t chunks = TokScratch::chunks_of(n_slots);
+    if (n_lines && chunks) {
+        hipLaunchKernelGGL(wp_exscan_kernel, dim3(1), dim3(1024), 0, st, s.raw_count(), n_lines, s.raw_base());
+        hipLaunchKernelGGL(wp_chunk_count_kernel, dim3((unsigned)chunks), dim3(EMIT_THREADS), 0, st, reinterpret_cast<const uint4 *>(s.d_ids_tmp),
+                           s.chunk_count());
+        hipLaunchKernelGGL(wp_exscan_kernel, dim3(1), dim3(1024), 0, st, s.chunk_count(), chunks, s.chunk_base());
+        hipLaunchKernelGGL(wp_emit_kernel, dim3((unsigned)chunks), dim3(EMIT_THREADS), 0, st, reinterpret_cast<const uint4 *>(s.d_ids_tmp), n_slots,
+                           s.chunk_base(), slot_begin_dev, n_lines, s.raw_base(), flags_dev, s.final_count(), offsets_out_dev, ids_out_dev, ids_cap);
+        SMT_HIP_CHECK(hipGetLastError());
+    }
+    if (n_patch) {
+        hipLaunchKernelGGL(wp_patch_copy_kernel, dim3((unsigned)std::min<uint64_t>(n_patch, 65536)), dim3(256), 0, st, n_patch, n_lines,
+                           patch_line_dev, patch_off_dev, patch_ids_dev, n_patch_ids, flags_dev, offsets_out_dev, ids_out_dev, ids_cap);
+        SMT_HIP_CHECK(hipGetLastError());
+    }
+    return SMT_OK;
 }
 
 }  // namespace smt
@@ -397,8 +501,7 @@ try {
     if (rc) return rc;
 
     // ---- entries: every ASCII piece as a whole word; one that starts with the prefix and goes on, as a continuing piece too
-    struct Ent { uint32_t off, len, id, kind; uint64_t h; };
-    std::vector<Ent> ents;
+    std::vector<TokEntry> ents;
     ents.reserve(p->n_pieces * 2);
     uint32_t max_piece = 0;
     const uint64_t prefix_state = hash_bytes(p->prefix, p->prefix_len);
@@ -410,33 +513,14 @@ try {
         if (!ascii) continue;
         const uint64_t h = hash_bytes(p->pool + off, len);
         max_piece = std::max(max_piece, len);
-        ents.push_back({off, len, p->piece_id[i], 0, h});
-        if (len > p->prefix_len && memcmp(p->pool + off, p->prefix, p->prefix_len) == 0) ents.push_back({off, len, p->piece_id[i], 1, h});
+        ents.push_back({off, len, p->piece_id[i], 0, h, i});
+        if (len > p->prefix_len && memcmp(p->pool + off, p->prefix, p->prefix_len) == 0) ents.push_back({off, len, p->piece_id[i], 1, h, i});
     }
-    uint32_t cap = 16;
-    while ((uint64_t)cap < 2 * (uint64_t)ents.size()) cap <<= 1;
-    const uint32_t mask = cap - 1;
-    std::vector<unsigned long long> slots(cap, 0);
-    std::vector<uint4> dev_ents;
-    dev_ents.reserve(ents.size());
-    for (const Ent &e : ents) {
-        uint32_t idx = (uint32_t)e.h & mask;
-        const uint32_t tag = (uint32_t)(e.h >> 32);
-        for (;;) {
-            const unsigned long long s = slots[idx];
-            if (s == 0) {
-                dev_ents.push_back(make_uint4(e.off, e.len, e.id, e.kind));
-                slots[idx] = ((unsigned long long)tag << 32) | (unsigned long long)dev_ents.size();
-                break;
-            }
-            uint4 &o = dev_ents[(uint32_t)s - 1];
-            if ((uint32_t)(s >> 32) == tag && o.w == e.kind && o.y == e.len && memcmp(p->pool + o.x, p->pool + e.off, e.len) == 0) {
-                o.z = e.id;   // a repeated piece: the later entry wins
-                break;
-            }
-            idx = (idx + 1) & mask;   // (load <= 0.5: an empty slot exists)
-        }
-    }
+    TokTable table;
+    tok_build_table(p->pool, ents, table);
+    const uint32_t cap = (uint32_t)table.slots.size(), mask = table.mask;
+    const std::vector<unsigned long long> &slots = table.slots;
+    const std::vector<uint4> &dev_ents = table.ents;
     const size_t pool_bytes = p->n_pieces ? p->piece_off[p->n_pieces] : 0;
     const size_t added_bytes = p->n_added ? p->added_off[p->n_added] : 0;
     uint8_t bytes[256];
@@ -498,9 +582,7 @@ void smt_wordpiece_destroy(smt_wordpiece *tok)
     (void)hipSetDevice(tok->ctx->device);
     (void)hipStreamSynchronize(tok->ctx->stream);
     if (tok->d_table) (void)hipFree(tok->d_table);
-    if (tok->d_ids_tmp) (void)hipFree(tok->d_ids_tmp);
-    if (tok->d_lines) (void)hipFree(tok->d_lines);
-    if (tok->d_chunks) (void)hipFree(tok->d_chunks);
+    tok_scratch_free(tok->S);
     delete tok;
 }
 
@@ -518,41 +600,19 @@ try {
     int rc = bind_device(ctx);
     if (rc) return rc;
     tok->scanned = false;
-    const uint64_t chunks = (text_bytes + EMIT_CHUNK - 1) / EMIT_CHUNK;
-    if (chunks * EMIT_CHUNK > tok->slots_cap) {
-        tok->slots_cap = 0;
-        if ((rc = grow(ctx, reinterpret_cast<void **>(&tok->d_ids_tmp), (size_t)chunks * EMIT_CHUNK * 4, "wordpiece id slots"))) return rc;
-        tok->slots_cap = chunks * EMIT_CHUNK;
-    }
-    if (chunks > tok->chunks_cap) {
-        tok->chunks_cap = 0;
-        if ((rc = grow(ctx, &tok->d_chunks, (size_t)chunks * 4 + ((size_t)chunks + 1) * 8 + 8, "wordpiece chunk sums"))) return rc;
-        tok->chunks_cap = chunks + (chunks & 1);   // (keeps the u64 part 8-byte aligned)
-    }
-    if (n_lines > tok->lines_cap) {
-        tok->lines_cap = 0;
-        if ((rc = grow(ctx, &tok->d_lines, (size_t)n_lines * 8 + ((size_t)n_lines + 1) * 8, "wordpiece line sums"))) return rc;
-        tok->lines_cap = n_lines;
-    }
+    if ((rc = tok_scratch_reserve(ctx, tok->S, text_bytes, n_lines))) return rc;
     hipStream_t st = ctx->stream;
     SMT_HIP_CHECK(hipMemsetAsync(n_flagged_dev, 0, sizeof(uint32_t), st));
-    if (n_lines) {
-        SMT_HIP_CHECK(hipMemsetAsync(flags_dev, 0, n_lines, st));
-        SMT_HIP_CHECK(hipMemsetAsync(tok->raw_count(), 0, (size_t)n_lines * 4, st));
-    }
-    if (chunks) SMT_HIP_CHECK(hipMemsetAsync(tok->d_ids_tmp, 0xFF, (size_t)chunks * EMIT_CHUNK * 4, st));
+    if (n_lines) SMT_HIP_CHECK(hipMemsetAsync(flags_dev, 0, n_lines, st));
+    if ((rc = tok_scratch_clear(ctx, tok->S, text_bytes, n_lines))) return rc;
     prof_begin(ctx, "tokenize");
     if (n_lines && text_bytes) {
         hipLaunchKernelGGL(wp_scan_kernel, dim3((unsigned)((text_bytes + SCAN_THREADS - 1) / SCAN_THREADS)), dim3(SCAN_THREADS), 0, st, tok->T,
-                           text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, tok->d_ids_tmp, tok->raw_count(),
+                           text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, tok->S.d_ids_tmp, tok->S.raw_count(),
                            flags_dev);
         SMT_HIP_CHECK(hipGetLastError());
     }
-    if (n_lines) {
-        hipLaunchKernelGGL(wp_lines_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, st, n_lines, tok->raw_count(), flags_dev,
-                           max_tokens, counts_dev, n_flagged_dev);
-        SMT_HIP_CHECK(hipGetLastError());
-    }
+    if ((rc = tok_line_counts(ctx, tok->S, n_lines, flags_dev, max_tokens, counts_dev, n_flagged_dev))) return rc;
     prof_end(ctx, "tokenize");
     tok->scanned = true;
     tok->text_bytes = text_bytes;
@@ -581,32 +641,10 @@ try {
     smt_ctx *ctx = tok->ctx;
     int rc = bind_device(ctx);
     if (rc) return rc;
-    hipStream_t st = ctx->stream;
     prof_begin(ctx, "tokenize_emit");
-    if (n_lines) SMT_HIP_CHECK(hipMemcpyAsync(tok->final_count(), tok->counts, (size_t)n_lines * 4, hipMemcpyDeviceToDevice, st));
-    if (n_patch) {
-        hipLaunchKernelGGL(wp_patch_counts_kernel, dim3((unsigned)((n_patch + 255) / 256)), dim3(256), 0, st, n_patch, n_lines, patch_line_dev,
-                           patch_off_dev, tok->flags, tok->final_count());
-        SMT_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(wp_exscan_kernel, dim3(1), dim3(1024), 0, st, tok->final_count(), n_lines, offsets_out_dev);
-    SMT_HIP_CHECK(hipGetLastError());
-    const uint64_t chunks = (tok->text_bytes + EMIT_CHUNK - 1) / EMIT_CHUNK;
-    if (n_lines && chunks) {
-        hipLaunchKernelGGL(wp_exscan_kernel, dim3(1), dim3(1024), 0, st, tok->raw_count(), n_lines, tok->raw_base());
-        hipLaunchKernelGGL(wp_chunk_count_kernel, dim3((unsigned)chunks), dim3(EMIT_THREADS), 0, st, reinterpret_cast<const uint4 *>(tok->d_ids_tmp),
-                           tok->chunk_count());
-        hipLaunchKernelGGL(wp_exscan_kernel, dim3(1), dim3(1024), 0, st, tok->chunk_count(), chunks, tok->chunk_base());
-        hipLaunchKernelGGL(wp_emit_kernel, dim3((unsigned)chunks), dim3(EMIT_THREADS), 0, st, reinterpret_cast<const uint4 *>(tok->d_ids_tmp),
-                           tok->text_bytes, tok->chunk_base(), tok->line_begin, n_lines, tok->raw_base(), tok->flags, tok->final_count(),
-                           offsets_out_dev, ids_out_dev, ids_cap);
-        SMT_HIP_CHECK(hipGetLastError());
-    }
-    if (n_patch) {
-        hipLaunchKernelGGL(wp_patch_copy_kernel, dim3((unsigned)std::min<uint64_t>(n_patch, 65536)), dim3(256), 0, st, n_patch, n_lines,
-                           patch_line_dev, patch_off_dev, patch_ids_dev, n_patch_ids, tok->flags, offsets_out_dev, ids_out_dev, ids_cap);
-        SMT_HIP_CHECK(hipGetLastError());
-    }
+    if ((rc = tok_pass2(ctx, tok->S, tok->text_bytes, tok->line_begin, n_lines, tok->counts, tok->flags, patch_line_dev, patch_off_dev, patch_ids_dev,
+                        n_patch, n_patch_ids, ids_out_dev, ids_cap, offsets_out_dev)))
+        return rc;
     prof_end(ctx, "tokenize_emit");
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }

@@ -1,0 +1,497 @@
+// unigram_kernels.hip -- Unigram over pure-ASCII lines on the device ("Unigram"): a per-byte normalizer table, Metaspace
+// and the Viterbi of hf_tokenizer.cpp's unigram(), the same ids, as the CSR K1 reads.
+//
+// Pass 1 is dealt by TEXT POSITION, one lane per byte, as wp_scan_kernel: the lane finds its line (the block-narrowed binary search),
+// flags the line for a byte >= 0x80 or an added token standing there, and OWNS a piece when it stands at the piece's start: a byte
+// the table maps to ' ' (it becomes the replacement character R, and every R starts a piece), or the line's first byte (the piece in
+// front of the first R, with R prepended unless the scheme is `never`).  The owner walks to the piece's end, then runs the lattice
+// over the piece's characters: from every character position one forward walk carries the FNV state byte by byte and probes every
+// end up to the longest piece (no candidate is hashed twice), f64 sums formed as score[piece] + best[at], one add per edge.  THE TIE
+// RULE: among candidates of equal sum for one end position the one with the SMALLEST START wins (the unknown edge has the largest
+// start its end can have); it is stated in relax() as a comparison of starts, not left to the visiting order.
+//
+// The lattice lives in LDS: a node (best sum f64, id u32, start + unknown bit u16 = 14 bytes) per raw byte the block's pieces can
+// reach -- a piece is at most SMT_UG_MAX_WORD raw bytes, so the pieces that start in a block of 256 bytes end within 256 +
+// SMT_UG_MAX_WORD bytes, pieces are disjoint, and no two lanes share a node.  The node behind a leading R is held in registers.  No
+// global scratch besides the id slots: 4 bytes per text byte + 4 per line (+ 8 per line for the slots' line starts).
+//
+// A line of n looked-at bytes can hold n + 1 tokens (the prepended R), so line i owns the slots [begin_i + i, begin_{i+1} + i + 1): the
+// first piece writes from begin_i + i, the piece of a space at p from p + i + 1.  A piece has no more tokens than characters, so no two
+// pieces share a slot and slot order is token order; pass 2 is the WordPiece one (tokenize_pass2.h) on these slots.
+//
+// Every loop is bounded: probes by the table's capacity, walks by the longest piece and the piece's end, pieces by SMT_UG_MAX_WORD.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "common.h"
+#include "tokenize_pass2.h"
+
+namespace {
+
+constexpr unsigned UG_THREADS = 256;                       // pass 1: one position per thread
+constexpr unsigned UG_NODES = UG_THREADS + SMT_UG_MAX_WORD;
+constexpr uint8_t UG_DROP = 0xFF;                          // byte_map: the byte is dropped
+constexpr uint32_t KEY_START = 0, KEY_R = 1;               // a node's start: the piece's start, the node behind R, or 2 + (raw byte - owner)
+constexpr uint16_t FROM_UNSET = 0xFFFF, FROM_UNK = 0x8000;
+
+struct UgTable {
+    const unsigned long long *slots;   // (tag << 32) | entry + 1; 0 = empty
+    const uint4 *ent;                  // {pool offset of the piece, its length, its id, 1 = the piece starts with R}
+    const double *score;               // per entry
+    const uint8_t *pool;
+    const uint8_t *map;                // [128]: the normalised byte, UG_DROP
+    const uint8_t *added_pool;
+    const uint32_t *added_off;
+    uint32_t mask;                     // capacity - 1
+    uint32_t max_piece;                // longest piece of the vocabulary, in bytes
+    uint32_t n_added;
+    uint32_t unk;                      // TOK_NONE: none
+    uint32_t rlen;                     // bytes of R
+    uint32_t prepend;                  // 0 always, 1 first, 2 never
+    uint32_t r_id, r_unk;              // the edge over R alone: the piece R, or the unknown edge
+    double r_score;
+    double unk_score;
+    unsigned long long r_state;        // the hash after R
+    unsigned long long added_first[2]; // bit c: an added token starts with byte c
+};
+
+__device__ __forceinline__ uint64_t ug_count_le(const uint64_t *__restrict__ begin, uint64_t lo, uint64_t hi, uint64_t p)
+{
+    for (int step = 0; step < 64 && lo < hi; ++step) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (begin[mid] <= p) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// the candidate: clen kept bytes from raw position s (dropped bytes skipped), behind R for kind 1, hash h: its entry + 1, or 0
+__device__ __forceinline__ uint32_t ug_probe(const UgTable &T, const uint8_t *__restrict__ text, const uint8_t *map, unsigned long long h,
+                                             uint32_t kind, uint64_t s, uint32_t clen)
+{
+    uint32_t idx = (uint32_t)h & T.mask;
+    const uint32_t tag = (uint32_t)(h >> 32);
+    const uint32_t skip = kind ? T.rlen : 0;
+    for (uint32_t probe = 0; probe <= T.mask; ++probe) {
+        const unsigned long long slot = T.slots[idx];
+        if (slot == 0) return 0;
+        if ((uint32_t)(slot >> 32) == tag) {
+            const uint4 e = T.ent[(uint32_t)slot - 1];
+            if (e.w == kind && e.y == clen + skip) {
+                const uint8_t *piece = T.pool + e.x + skip;
+                uint64_t q = s;
+                uint32_t j = 0;
+                bool same = true;
+                while (j < clen) {   // (the candidate was walked once already: it has clen kept bytes before the piece's end)
+                    const uint8_t m = map[text[q++]];
+                    if (m == UG_DROP) continue;
+                    if (m != piece[j]) { same = false; break; }
+                    ++j;
+                }
+                if (same) return (uint32_t)slot;
+            }
+        }
+        idx = (idx + 1) & T.mask;
+    }
+    return 0;
+}
+
+__global__ void __launch_bounds__(256) ug_slot_begin_kernel(const uint64_t *__restrict__ line_begin, uint64_t n_lines, uint64_t *__restrict__ slot_begin)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_lines) slot_begin[i] = line_begin[i] + i;
+}
+
+__global__ void __launch_bounds__(UG_THREADS) ug_scan_kernel(UgTable T, const uint8_t *__restrict__ text, uint64_t text_bytes,
+                                                             const uint64_t *__restrict__ line_begin, const uint32_t *__restrict__ line_len,
+                                                             uint64_t n_lines, uint32_t keep_bytes, int drop_unk, uint32_t *__restrict__ ids_tmp,
+                                                             uint32_t *__restrict__ raw_count, uint8_t *__restrict__ flags)
+{
+    __shared__ uint8_t s_map[128];
+    __shared__ uint64_t s_win[2];
+    __shared__ double s_score[UG_NODES];
+    __shared__ uint32_t s_id[UG_NODES];
+    __shared__ uint16_t s_from[UG_NODES];
+    if (threadIdx.x < 128) s_map[threadIdx.x] = T.map[threadIdx.x];
+    const uint64_t first = (uint64_t)blockIdx.x * UG_THREADS;
+    if (threadIdx.x < 2) {
+        const uint64_t last = first + UG_THREADS - 1 < text_bytes ? first + UG_THREADS - 1 : text_bytes - 1;
+        s_win[threadIdx.x] = ug_count_le(line_begin, 0, n_lines, threadIdx.x == 0 ? first : last);
+    }
+    __syncthreads();   // (the only barrier: lanes leave freely below)
+    const uint64_t p = first + threadIdx.x;
+    if (p >= text_bytes) return;
+    const uint64_t n_le = ug_count_le(line_begin, s_win[0], s_win[1], p);
+    if (n_le == 0) return;                       // in front of the first line
+    const uint64_t line = n_le - 1;
+    const uint64_t lb = line_begin[line];
+    const uint32_t ll = line_len[line];
+    const uint64_t le_line = lb + (keep_bytes && keep_bytes < ll ? keep_bytes : ll);
+    const uint64_t le = le_line < text_bytes ? le_line : text_bytes;   // the end of what is looked at
+    if (p < lb || p >= le) return;               // behind the cut, or between two lines
+    const uint8_t c = text[p];
+    if (c >= 0x80) { flags[line] = 1; return; }
+    if (((c < 64 ? T.added_first[0] : T.added_first[1]) >> (c & 63)) & 1) {
+        for (uint32_t t = 0; t < T.n_added; ++t) {
+            const uint32_t a = T.added_off[t], tl = T.added_off[t + 1] - a;
+            if (tl == 0 || p + tl > le) continue;
+            bool same = true;
+            for (uint32_t j = 0; j < tl && same; ++j) same = text[p + j] == T.added_pool[a + j];
+            if (same) { flags[line] = 1; break; }
+        }
+    }
+    const bool at_space = s_map[c] == ' ';
+    if (!at_space && p != lb) return;            // no piece starts here
+    // ---- the piece: [R] + the kept bytes of [run, end); its measure is its raw bytes (+ 1 for a prepended R)
+    const bool has_r = at_space || T.prepend != 2;
+    const uint64_t run = at_space ? p + 1 : p;
+    const uint64_t base = at_space ? p + line + 1 : lb + line;   // the piece's first slot
+    const uint32_t rel = (uint32_t)(p - first);  // node of raw byte q: q - first; its key: 2 + q - p
+    uint32_t measure = has_r ? 1 : 0, n_kept = 0;
+    uint64_t end = run, last_q = run;
+    for (; end < le; ++end) {
+        const uint8_t b = text[end];
+        if (b >= 0x80) return;                   // (the line is flagged by that byte's lane: nothing of it is used)
+        const uint8_t m = s_map[b];
+        if (m == ' ') break;
+        if (++measure > SMT_UG_MAX_WORD) { flags[line] = 1; return; }
+        if (m == UG_DROP) continue;
+        s_from[end - first] = FROM_UNSET;
+        last_q = end;
+        ++n_kept;
+    }
+    if (!at_space && n_kept == 0 && end < le) return;   // the normalised text starts with R: that byte's lane owns the first piece
+    if (!has_r && n_kept == 0) return;                   // nothing is left of the line
+    // ---- the lattice
+    const double r_score = T.r_score + 0.0;
+    // every edge out of one start: the pieces of `kind` found while the end walks forward from q0, the unknown edge over the first
+    // character when no piece covers exactly it (the walk from the piece's start through R offers none: R's own edge is T.r_*)
+    auto relax = [&](double here, uint32_t key, unsigned long long h, uint32_t kind, uint64_t q0) {
+        bool single = false;
+        uint32_t clen = 0, len = kind ? T.rlen : 0;
+        uint64_t first_q = end;
+        for (uint64_t q = q0; q < end; ++q) {
+            const uint8_t m = s_map[text[q]];
+            if (m == UG_DROP) continue;
+            if (clen == 0) first_q = q;
+            if (len >= T.max_piece) break;
+            h = (h ^ m) * smt::TOK_HASH_MUL;
+            ++clen;
+            ++len;
+            const uint32_t e = ug_probe(T, text, s_map, h, kind, q0, clen);
+            if (!e) continue;
+            if (clen == 1) single = true;
+            const double cand = T.score[e - 1] + here;
+            const uint32_t n = (uint32_t)(q - first);
+            const uint16_t f = s_from[n];
+            if (f == FROM_UNSET || cand > s_score[n] || (cand == s_score[n] && key < (uint32_t)(f & 0x7FFF))) {
+                s_score[n] = cand;
+                s_id[n] = T.ent[e - 1].z;
+                s_from[n] = (uint16_t)key;
+            }
+        }
+        if (kind == 0 && !single && first_q < end) {
+            const double cand = T.unk_score + here;
+            const uint32_t n = (uint32_t)(first_q - first);
+            const uint16_t f = s_from[n];
+            if (f == FROM_UNSET || cand > s_score[n] || (cand == s_score[n] && key < (uint32_t)(f & 0x7FFF))) {
+                s_score[n] = cand;
+                s_id[n] = T.unk == smt::TOK_NONE ? 0u : T.unk;
+                s_from[n] = (uint16_t)(key | FROM_UNK);
+            }
+        }
+    };
+    if (has_r) {
+        relax(0.0, KEY_START, T.r_state, 1, run);
+        relax(r_score, KEY_R, smt::TOK_HASH_SEED, 0, run);
+    } else {
+        relax(0.0, KEY_START, smt::TOK_HASH_SEED, 0, run);
+    }
+    for (uint64_t q = run; q < end; ++q) {
+        if (s_map[text[q]] == UG_DROP) continue;
+        relax(s_score[q - first], 2 + (uint32_t)(q - p), smt::TOK_HASH_SEED, 0, q + 1);
+    }
+    // ---- back along the best path, twice: count what stays (consecutive unknowns fuse, the unk id is dropped), then write
+    const uint32_t end_key = n_kept ? 2 + (uint32_t)(last_q - p) : KEY_R;
+    const bool dropping = drop_unk && T.unk != smt::TOK_NONE;
+    uint32_t n_tok = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        uint32_t key = end_key, k = n_tok;
+        for (uint32_t step = 0; step <= SMT_UG_MAX_WORD && key != KEY_START; ++step) {
+            uint32_t id, from;
+            bool unk;
+            if (key == KEY_R) { id = T.r_id; unk = T.r_unk != 0; from = KEY_START; }
+            else { const uint32_t n = rel + key - 2; const uint16_t f = s_from[n]; id = s_id[n]; unk = (f & FROM_UNK) != 0; from = f & 0x7FFF; }
+            bool pred_unk = false;
+            if (from == KEY_R) pred_unk = T.r_unk != 0;
+            else if (from != KEY_START) pred_unk = (s_from[rel + from - 2] & FROM_UNK) != 0;
+            if (unk && T.unk == smt::TOK_NONE) { flags[line] = 1; return; }   // (first pass: nothing is written yet)
+            if (!(unk && pred_unk) && !(dropping && id == T.unk)) {
+                if (pass == 0) ++n_tok;
+                else ids_tmp[base + --k] = id;
+            }
+            key = from;
+        }
+    }
+    if (n_tok) atomicAdd(&raw_count[line], n_tok);
+}
+
+}  // namespace
+
+struct smt_unigram {
+    smt_ctx *ctx = nullptr;
+    void *d_table = nullptr;          // slots | entries | scores | pool | byte map | added pool | added offsets
+    UgTable T{};
+    smt::TokScratch S;                // the state of the last scan
+    bool scanned = false;
+    uint64_t text_bytes = 0, n_lines = 0, ids_bound = 0;
+    const uint32_t *counts = nullptr;
+    const uint8_t *flags = nullptr;
+};
+
+using namespace smt;
+
+extern "C" {
+
+int smt_unigram_create(smt_ctx *ctx, const smt_unigram_params *p, smt_unigram **out)
+try {
+    if (!ctx) return tok_null_handle("smt_unigram_create");
+    SMT_REQUIRE(p != nullptr && out != nullptr, "null argument");
+    *out = nullptr;
+    SMT_REQUIRE(p->n_pieces == 0 || (p->pool && p->piece_off && p->piece_id && p->scores), "vocabulary arrays");
+    SMT_REQUIRE(p->n_pieces < 0x7FFFFFFFull, "too many pieces");
+    SMT_REQUIRE(p->unk_id >= -1 && p->unk_id < 0xFFFFFFFFll, "unk_id");
+    SMT_REQUIRE(p->replacement != nullptr && p->replacement_len >= 2 && p->replacement_len <= 4, "the replacement must be one character >= U+0080");
+    SMT_REQUIRE((uint8_t)p->replacement[0] >= 0xC0, "the replacement must be one character >= U+0080");
+    for (uint32_t i = 1; i < p->replacement_len; ++i) SMT_REQUIRE(((uint8_t)p->replacement[i] & 0xC0) == 0x80, "the replacement must be one UTF-8 character");
+    SMT_REQUIRE(p->prepend <= 2, "prepend");
+    SMT_REQUIRE(p->byte_map != nullptr, "byte_map");
+    for (int c = 0; c < 128; ++c) SMT_REQUIRE(p->byte_map[c] < 0x80 || p->byte_map[c] == UG_DROP, "byte_map entries are ASCII bytes or 0xFF");
+    SMT_REQUIRE(p->n_added == 0 || (p->added_pool && p->added_off), "added tokens");
+    for (uint64_t i = 0; i < p->n_pieces; ++i) SMT_REQUIRE(p->piece_off[i] <= p->piece_off[i + 1], "piece_off must be non-decreasing");
+    for (uint32_t i = 0; i < p->n_added; ++i) SMT_REQUIRE(p->added_off[i] <= p->added_off[i + 1], "added_off must be non-decreasing");
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+
+    // ---- entries: every ASCII piece (kind 0) and every piece that is R + ASCII bytes (kind 1).  R alone is no entry: its edge is
+    // fixed (T.r_*).  Every other piece with a byte >= 0x80 cannot match an ASCII line, but counts for the longest-piece bound.
+    const uint32_t rlen = p->replacement_len;
+    const uint64_t r_state = tok_hash_bytes(p->replacement, rlen);
+    std::vector<TokEntry> ents;
+    ents.reserve(p->n_pieces);
+    uint32_t max_piece = 0;
+    bool r_known = false;
+    uint32_t r_id = 0;
+    double r_score = 0.0;
+    for (uint64_t i = 0; i < p->n_pieces; ++i) {
+        const uint32_t off = p->piece_off[i], len = p->piece_off[i + 1] - off;
+        max_piece = std::max(max_piece, len);
+        if (len == 0) continue;
+        const bool with_r = len >= rlen && memcmp(p->pool + off, p->replacement, rlen) == 0;
+        bool ascii = true;
+        for (uint32_t j = with_r ? rlen : 0; j < len && ascii; ++j) ascii = (uint8_t)p->pool[off + j] < 0x80;
+        if (!ascii) continue;
+        if (with_r && len == rlen) { r_known = true; r_id = p->piece_id[i]; r_score = p->scores[i]; continue; }   // (repeated: the later one wins)
+        ents.push_back({off, len, p->piece_id[i], with_r ? 1u : 0u, tok_hash_bytes(p->pool + off, len), i});
+    }
+    TokTable table;
+    tok_build_table(p->pool, ents, table);
+    std::vector<double> scores(table.ents.size());
+    for (size_t j = 0; j < scores.size(); ++j) scores[j] = p->scores[table.winner[j]];
+    const size_t cap = table.slots.size();
+    const size_t pool_bytes = p->n_pieces ? p->piece_off[p->n_pieces] : 0;
+    const size_t added_bytes = p->n_added ? p->added_off[p->n_added] : 0;
+    unsigned long long added_first[2] = {0, 0};
+    for (uint32_t t = 0; t < p->n_added; ++t) {
+        const uint32_t a = p->added_off[t], tl = p->added_off[t + 1] - a;
+        for (uint32_t j = 0; j < tl; ++j) SMT_REQUIRE((uint8_t)p->added_pool[a + j] < 0x80, "added tokens must be ASCII");
+        if (tl) added_first[(uint8_t)p->added_pool[a] >> 6] |= 1ull << ((uint8_t)p->added_pool[a] & 63);
+    }
+    // ---- one blob, every part 16-byte aligned
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_slots = 0, o_ent = o_slots + up16(cap * 8), o_score = o_ent + up16(table.ents.size() * sizeof(uint4) + 16),
+                 o_pool = o_score + up16(scores.size() * 8 + 16), o_map = o_pool + up16(pool_bytes + 16), o_apool = o_map + 128,
+                 o_aoff = o_apool + up16(added_bytes + 16), total = o_aoff + up16(((size_t)p->n_added + 1) * 4);
+    std::vector<uint8_t> blob(total, 0);
+    memcpy(blob.data() + o_slots, table.slots.data(), cap * 8);
+    if (!table.ents.empty()) memcpy(blob.data() + o_ent, table.ents.data(), table.ents.size() * sizeof(uint4));
+    if (!scores.empty()) memcpy(blob.data() + o_score, scores.data(), scores.size() * 8);
+    if (pool_bytes) memcpy(blob.data() + o_pool, p->pool, pool_bytes);
+    memcpy(blob.data() + o_map, p->byte_map, 128);
+    if (added_bytes) memcpy(blob.data() + o_apool, p->added_pool, added_bytes);
+    if (p->n_added) memcpy(blob.data() + o_aoff, p->added_off, ((size_t)p->n_added + 1) * 4);
+
+    smt_unigram *tok = new smt_unigram();
+    tok->ctx = ctx;
+    hipError_t e = hipMalloc(&tok->d_table, total);
+    if (e == hipSuccess) e = hipMemcpy(tok->d_table, blob.data(), total, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (tok->d_table) (void)hipFree(tok->d_table);
+        delete tok;
+        set_error("unigram table upload (%zu bytes): %s", total, hipGetErrorString(e));
+        return SMT_E_NOMEM;
+    }
+    const uint8_t *base = static_cast<const uint8_t *>(tok->d_table);
+    UgTable &T = tok->T;
+    T.slots = reinterpret_cast<const unsigned long long *>(base + o_slots);
+    T.ent = reinterpret_cast<const uint4 *>(base + o_ent);
+    T.score = reinterpret_cast<const double *>(base + o_score);
+    T.pool = base + o_pool;
+    T.map = base + o_map;
+    T.added_pool = base + o_apool;
+    T.added_off = reinterpret_cast<const uint32_t *>(base + o_aoff);
+    T.mask = table.mask;
+    T.max_piece = max_piece;
+    T.n_added = p->n_added;
+    T.unk = p->unk_id < 0 ? TOK_NONE : (uint32_t)p->unk_id;
+    T.rlen = rlen;
+    T.prepend = p->prepend;
+    T.r_unk = r_known ? 0u : 1u;
+    T.r_id = r_known ? r_id : (p->unk_id < 0 ? 0u : (uint32_t)p->unk_id);
+    T.r_score = r_known ? r_score : p->unk_score;
+    T.unk_score = p->unk_score;
+    T.r_state = r_state;
+    T.added_first[0] = added_first[0];
+    T.added_first[1] = added_first[1];
+    *out = tok;
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+void smt_unigram_destroy(smt_unigram *tok)
+{
+    if (!tok) return;
+    (void)hipSetDevice(tok->ctx->device);
+    (void)hipStreamSynchronize(tok->ctx->stream);
+    if (tok->d_table) (void)hipFree(tok->d_table);
+    tok_scratch_free(tok->S);
+    delete tok;
+}
+
+int smt_unigram_scan_device(smt_unigram *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev,
+                            const uint32_t *line_len_dev, uint64_t n_lines, uint32_t keep_bytes, uint32_t max_tokens, int drop_unk,
+                            uint32_t *counts_dev, uint8_t *flags_dev, uint32_t *n_flagged_dev)
+try {
+    if (!tok) return tok_null_handle("smt_unigram_scan_device");
+    SMT_REQUIRE(n_flagged_dev != nullptr, "n_flagged_dev");
+    SMT_REQUIRE(n_lines == 0 || (line_begin_dev && line_len_dev && counts_dev && flags_dev), "null argument");
+    SMT_REQUIRE(text_bytes == 0 || text_dev != nullptr, "text_dev");
+    SMT_REQUIRE(text_bytes <= (1ull << 32), "at most 4 GiB of text per scan");
+    SMT_REQUIRE(n_lines <= (1ull << 32), "at most 2^32 lines per scan");
+    smt_ctx *ctx = tok->ctx;
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    tok->scanned = false;
+    const uint64_t n_slots = text_bytes + n_lines;   // every line has one slot more than bytes
+    if ((rc = tok_scratch_reserve(ctx, tok->S, n_slots, n_lines))) return rc;
+    hipStream_t st = ctx->stream;
+    SMT_HIP_CHECK(hipMemsetAsync(n_flagged_dev, 0, sizeof(uint32_t), st));
+    if (n_lines) SMT_HIP_CHECK(hipMemsetAsync(flags_dev, 0, n_lines, st));
+    if ((rc = tok_scratch_clear(ctx, tok->S, n_slots, n_lines))) return rc;
+    prof_begin(ctx, "tokenize");
+    if (n_lines) {
+        hipLaunchKernelGGL(ug_slot_begin_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, st, line_begin_dev, n_lines, tok->S.slot_begin());
+        SMT_HIP_CHECK(hipGetLastError());
+    }
+    if (n_lines && text_bytes) {
+        hipLaunchKernelGGL(ug_scan_kernel, dim3((unsigned)((text_bytes + UG_THREADS - 1) / UG_THREADS)), dim3(UG_THREADS), 0, st, tok->T, text_dev,
+                           text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, tok->S.d_ids_tmp, tok->S.raw_count(), flags_dev);
+        SMT_HIP_CHECK(hipGetLastError());
+    }
+    if ((rc = tok_line_counts(ctx, tok->S, n_lines, flags_dev, max_tokens, counts_dev, n_flagged_dev))) return rc;
+    prof_end(ctx, "tokenize");
+    tok->scanned = true;
+    tok->text_bytes = text_bytes;
+    tok->n_lines = n_lines;
+    tok->ids_bound = (keep_bytes ? std::min<uint64_t>(text_bytes, n_lines * (uint64_t)keep_bytes) : text_bytes) + n_lines;
+    tok->counts = counts_dev;
+    tok->flags = flags_dev;
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_unigram_emit_device(smt_unigram *tok, uint64_t n_lines, const uint64_t *patch_line_dev, const uint64_t *patch_off_dev,
+                            const uint32_t *patch_ids_dev, uint64_t n_patch, uint64_t n_patch_ids, uint32_t *ids_out_dev, uint64_t ids_cap,
+                            uint64_t *offsets_out_dev)
+try {
+    if (!tok) return tok_null_handle("smt_unigram_emit_device");
+    SMT_REQUIRE(tok->scanned, "no scan to emit (smt_unigram_scan_device comes first)");
+    SMT_REQUIRE(n_lines == tok->n_lines, "n_lines differs from the scan's");
+    SMT_REQUIRE(offsets_out_dev != nullptr, "offsets_out_dev");
+    SMT_REQUIRE(n_patch == 0 || (patch_line_dev && patch_off_dev), "patch arrays");
+    SMT_REQUIRE(n_patch <= n_lines, "more patched lines than lines");
+    SMT_REQUIRE(n_patch_ids == 0 || (n_patch && patch_ids_dev), "patch ids");
+    SMT_REQUIRE(n_patch_ids <= (1ull << 40), "patch ids");
+    SMT_REQUIRE(ids_cap >= tok->ids_bound + n_patch_ids, "ids_cap is below the looked-at bytes of all lines + one per line + the patch ids");
+    SMT_REQUIRE(ids_cap == 0 || ids_out_dev != nullptr, "ids_out_dev");
+    smt_ctx *ctx = tok->ctx;
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    prof_begin(ctx, "tokenize_emit");
+    if ((rc = tok_pass2(ctx, tok->S, tok->text_bytes + n_lines, tok->S.slot_begin(), n_lines, tok->counts, tok->flags, patch_line_dev, patch_off_dev,
+                        patch_ids_dev, n_patch, n_patch_ids, ids_out_dev, ids_cap, offsets_out_dev)))
+        return rc;
+    prof_end(ctx, "tokenize_emit");
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_unigram_tokenize(smt_unigram *tok, const char *text, const uint64_t *line_begin, const uint32_t *line_len, uint64_t n_lines,
+                         uint32_t keep_bytes, uint32_t max_tokens, int drop_unk, uint32_t *ids_out, uint64_t ids_cap, uint64_t *offsets_out,
+                         uint8_t *flags_out)
+try {
+    if (!tok) return tok_null_handle("smt_unigram_tokenize");
+    SMT_REQUIRE(offsets_out != nullptr, "offsets_out");
+    SMT_REQUIRE(n_lines == 0 || (line_begin && line_len), "null argument");
+    uint64_t text_bytes = 0, looked = 0;
+    for (uint64_t i = 0; i < n_lines; ++i) {
+        SMT_REQUIRE(line_begin[i] >= text_bytes, "lines must lie in line order and must not overlap");
+        text_bytes = line_begin[i] + line_len[i];
+        looked += keep_bytes && keep_bytes < line_len[i] ? keep_bytes : line_len[i];
+    }
+    SMT_REQUIRE(text_bytes == 0 || text != nullptr, "text");
+    SMT_REQUIRE(ids_cap >= looked + n_lines, "ids_cap is below the looked-at bytes of all lines + one per line");
+    SMT_REQUIRE(ids_cap == 0 || ids_out != nullptr, "ids_out");
+    smt_ctx *ctx = tok->ctx;
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const uint64_t dev_cap = std::max<uint64_t>(ids_cap, text_bytes + n_lines);   // (the device form's bound)
+    const size_t o_begin = 0, o_off = o_begin + up16((size_t)n_lines * 8 + 8), o_ids = o_off + up16(((size_t)n_lines + 1) * 8),
+                 o_len = o_ids + up16((size_t)dev_cap * 4 + 4), o_counts = o_len + up16((size_t)n_lines * 4 + 4),
+                 o_nflag = o_counts + up16((size_t)n_lines * 4 + 4), o_flags = o_nflag + 16, o_text = o_flags + up16((size_t)n_lines + 1),
+                 total = o_text + up16((size_t)text_bytes + 1);
+    struct Temp { void *p = nullptr; ~Temp() { if (p) (void)hipFree(p); } } tmp;
+    {
+        const hipError_t e = hipMalloc(&tmp.p, total);
+        if (e != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc(%zu) for tokenizer staging: %s", total, hipGetErrorString(e)); return SMT_E_NOMEM; }
+    }
+    char *d = static_cast<char *>(tmp.p);
+    hipStream_t st = ctx->stream;
+    if (n_lines) {
+        SMT_HIP_CHECK(hipMemcpyAsync(d + o_begin, line_begin, (size_t)n_lines * 8, hipMemcpyHostToDevice, st));
+        SMT_HIP_CHECK(hipMemcpyAsync(d + o_len, line_len, (size_t)n_lines * 4, hipMemcpyHostToDevice, st));
+    }
+    if (text_bytes) SMT_HIP_CHECK(hipMemcpyAsync(d + o_text, text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
+    uint8_t *d_flags = reinterpret_cast<uint8_t *>(d + o_flags);
+    if ((rc = smt_unigram_scan_device(tok, reinterpret_cast<const uint8_t *>(d + o_text), text_bytes, reinterpret_cast<const uint64_t *>(d + o_begin),
+                                      reinterpret_cast<const uint32_t *>(d + o_len), n_lines, keep_bytes, max_tokens, drop_unk,
+                                      reinterpret_cast<uint32_t *>(d + o_counts), d_flags, reinterpret_cast<uint32_t *>(d + o_nflag)))) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if ((rc = smt_unigram_emit_device(tok, n_lines, nullptr, nullptr, nullptr, 0, 0, reinterpret_cast<uint32_t *>(d + o_ids), dev_cap,
+                                      reinterpret_cast<uint64_t *>(d + o_off)))) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    SMT_HIP_CHECK(hipMemcpyAsync(offsets_out, d + o_off, ((size_t)n_lines + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (flags_out && n_lines) SMT_HIP_CHECK(hipMemcpyAsync(flags_out, d_flags, (size_t)n_lines, hipMemcpyDeviceToHost, st));
+    SMT_HIP_CHECK(hipStreamSynchronize(st));
+    const uint64_t n_ids = offsets_out[n_lines];
+    if (n_ids > ids_cap) { set_error("tokenizer produced more ids than ids_cap"); return SMT_E_HIP; }
+    if (n_ids) SMT_HIP_CHECK(hipMemcpy(ids_out, d + o_ids, (size_t)n_ids * 4, hipMemcpyDeviceToHost));
+    tok->scanned = false;   // (the staged line arrays go away with this call)
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+}  // extern "C"

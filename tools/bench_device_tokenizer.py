@@ -5,8 +5,10 @@ Latin-1 word).  The tokenizer.json is written here: a WordPiece vocabulary over 
 tail through ## pieces).  The process pins itself to --cpus CPUs first (default 16, what an ordinary deployment has; 0 = all it is
 given), so the host tokenizer's threads and the route's copy threads share that many.  Each setting gets one discarded warm-up call
 (first-use allocations), then three timed ones.  Merges its result under the key cpus_<n> into profiles/device_tokenizer.json.
+--model unigram runs the same lines through a synthetic Unigram vocabulary of the same size behind BertNormalizer -> Metaspace (the
+other device tokenizer) and writes profiles/device_tokenizer_unigram.json.
 
-    python tools/bench_device_tokenizer.py [--lines 1000000] [--cpus 16] [--out profiles/device_tokenizer.json]"""
+    python tools/bench_device_tokenizer.py [--model wordpiece|unigram] [--lines 1000000] [--cpus 16] [--out profiles/device_tokenizer.json]"""
 import argparse
 import ctypes as C
 import json
@@ -14,6 +16,8 @@ import os
 import sys
 import tempfile
 import time
+
+import math
 
 import numpy as np
 
@@ -27,6 +31,7 @@ import semtools_amd as smt  # noqa: E402
 from semtools_amd import _lib as L  # noqa: E402
 from semtools_amd import host  # noqa: E402
 from tests import synth  # noqa: E402
+from tests import unigram_ref as U  # noqa: E402
 from tests import wordpiece_ref as W  # noqa: E402
 
 SYL = ["ta", "re", "mi", "con", "ver", "sion", "al", "ing", "er", "pro", "de", "ment", "un", "st", "or", "an", "en", "ti", "ly", "ex", "per", "for",
@@ -60,6 +65,19 @@ def make_vocab(words):
         vocab.setdefault("##" + s, len(vocab))
     for w in words[: len(words) * 3 // 4]:      # three quarters of the words are pieces; the rest split into syllables
         vocab.setdefault(w, len(vocab))
+    return vocab
+
+
+def make_unigram_vocab(words):
+    """[(piece, score)]: <unk>, R, every printable ASCII character, the syllables bare and behind R, three quarters of the words behind R (the
+    rest split into syllables by the lattice); scores fall with the logarithm of the rank, as a trained model's do"""
+    pieces = ["<unk>", U.R] + [chr(c) for c in range(0x21, 0x7F)] + SYL + [U.R + s for s in SYL]
+    pieces += [U.R + w for w in words[: len(words) * 3 // 4]] + [U.R + w.capitalize() for w in words[:2000]]
+    seen, vocab = set(), []
+    for p in pieces:
+        if p not in seen:
+            seen.add(p)
+            vocab.append((p, 0.0 if p == "<unk>" else -(4.0 + math.log(len(vocab) + 1.0))))
     return vocab
 
 
@@ -111,13 +129,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lines", type=int, default=1_000_000)
     ap.add_argument("--cpus", type=int, default=16)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "device_tokenizer.json"))
+    ap.add_argument("--model", choices=["wordpiece", "unigram"], default="wordpiece")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    unigram = a.model == "unigram"
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "device_tokenizer_unigram.json" if unigram else "device_tokenizer.json")
     if a.cpus and hasattr(os, "sched_setaffinity"):
         os.sched_setaffinity(0, sorted(os.sched_getaffinity(0))[: a.cpus])
     rng = np.random.default_rng(7)
     words = make_words(30_000, rng)
-    vocab = make_vocab(words)
+    vocab = make_unigram_vocab(words) if unigram else make_vocab(words)
     distinct = make_lines(20_000, words, rng)
     lines = [distinct[i % len(distinct)] for i in range(a.lines)]
     flagged = [ln.replace(" ", " café ", 1) if i % 10 == 0 else ln for i, ln in enumerate(lines)]
@@ -126,16 +148,19 @@ def main():
     ctx.prof_enable(True)
     result = {"what": "host-layer ingest (smt_host_search_content: split + tokenize + K1 + one search), device tokenizer route off / on",
               "lines": a.lines, "cpus_available": cores, "gpu": torch.cuda.get_device_name(0), "vocabulary_pieces": len(vocab),
-              "host_cpu": cpu_model(),
+              "host_cpu": cpu_model(), "tokenizer": "BertNormalizer -> Metaspace -> Unigram" if unigram else "BertNormalizer -> BertPreTokenizer -> WordPiece",
               "note": "kernel profiling events are on in both settings; per setting one warm-up call is discarded, seconds is the best of 3 "
                       "timed calls, phases are the mean of those 3; 'off' runs before 'on' in the same process"}
     with tempfile.TemporaryDirectory() as d:
         from safetensors.numpy import save_file
 
         save_file({"embeddings": synth.table(len(vocab), seed=2)}, os.path.join(d, "model.safetensors"))
-        W.write_tokenizer(os.path.join(d, "tokenizer.json"), 7, vocab=vocab)
+        if unigram:
+            U.write_tokenizer(os.path.join(d, "tokenizer.json"), norm="bert_clean", prepend="always", vocab=vocab, added=[])
+        else:
+            W.write_tokenizer(os.path.join(d, "tokenizer.json"), 7, vocab=vocab)
         with open(os.path.join(d, "config.json"), "w") as f:
-            json.dump({"normalize": True, "unk_token": "[UNK]"}, f)
+            json.dump({"normalize": True, "unk_token": "<unk>" if unigram else "[UNK]"}, f)
         for corpus_name, corpus in (("ascii", lines), ("ten_percent_flagged", flagged)):
             content_b = ("\n".join(corpus) + "\n").encode()
             query_b = corpus[17].encode()

@@ -22,7 +22,7 @@ PRELUDE = '''//! FFI declarations for libsemtools_hip.so -- GENERATED from inclu
 use std::os::raw::{c_char, c_int, c_void};
 
 macro_rules! opaque { ($($name:ident),*) => { $( #[repr(C)] pub struct $name { _private: [u8; 0] } )* } }
-opaque!(SmtCtx, SmtModel, SmtCorpus, SmtIvfpq, SmtGroup, SmtShardedCorpus, SmtShardedIvfpq, SmtShardedModel, SmtWordpiece);
+opaque!(SmtCtx, SmtModel, SmtCorpus, SmtIvfpq, SmtGroup, SmtShardedCorpus, SmtShardedIvfpq, SmtShardedModel, SmtWordpiece, SmtUnigram);
 
 /// half-open range of corpus rows [begin, end)
 #[repr(C)]
@@ -57,6 +57,26 @@ pub struct SmtWordpieceParams {
     pub unk_id: i64,
     pub max_input_chars_per_word: u32,
     pub flags: u32,
+    pub added_pool: *const c_char,
+    pub added_off: *const u32,
+    pub n_added: u32,
+}
+
+/// a Unigram vocabulary, Metaspace's settings and the byte table for the device tokenizer (smt_unigram_create copies everything)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SmtUnigramParams {
+    pub pool: *const c_char,
+    pub piece_off: *const u32,
+    pub piece_id: *const u32,
+    pub n_pieces: u64,
+    pub scores: *const f64,
+    pub unk_score: f64,
+    pub unk_id: i64,
+    pub replacement: *const c_char,
+    pub replacement_len: u32,
+    pub prepend: u32,
+    pub byte_map: *const u8,
     pub added_pool: *const c_char,
     pub added_off: *const u32,
     pub n_added: u32,
