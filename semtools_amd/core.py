@@ -24,6 +24,14 @@ def _table(a):
     return np.ascontiguousarray(a)
 
 
+def _open(obj):
+    """The wrapper still owns a native handle.  An object made ON another one (a sharded corpus on its group) points into it, and its
+    destroy reads it: close() asks this of the owner first, because the cycle collector finalises a dropped set of objects in any
+    order -- the frames of a failed test, group first -- and a destroy that follows its owner's would read freed memory.  What is
+    skipped then went with the owner's contexts or stays allocated until the process ends; close dependents first to free it."""
+    return getattr(obj, "_h", None) is not None and bool(obj._h)
+
+
 class Context:
     """One GPU + one HIP stream (smt_ctx).
 
@@ -819,8 +827,9 @@ class ShardedModel:
         return int(nbytes.value)
 
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            L.lib().smt_sharded_model_destroy(self._h)
+        if _open(self):
+            if _open(self.group):
+                L.lib().smt_sharded_model_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -901,8 +910,9 @@ class ShardedCorpus:
         return int(moved.value)
 
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            L.lib().smt_sharded_corpus_destroy(self._h)
+        if _open(self):
+            if _open(self.group):
+                L.lib().smt_sharded_corpus_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -124,7 +124,7 @@ struct smt_ctx {
     // async select (tuning key async_select): the select of query i runs on aux_stream WHILE query i+1 scans;
     // the two kernels meet through device-scope flags, not stream events
     hipStream_t aux_stream = nullptr;
-    unsigned long long *d_status = nullptr; // [0] selects whose exactness certificate failed since the last read (sticky); [2], [3] the row domain check's (count, first row) (domain.hip); [4] the select blocks of a delivering launch that have finished (scan_kernels.hip)
+    unsigned long long *d_status = nullptr; // [0] selects whose exactness certificate failed since the last read (sticky); [2], [3] the row domain check's (count, first row) (domain.hip); [4] the select blocks of a delivering launch that have finished (select.hip)
     unsigned long long *d_flags = nullptr;  // [0] scan_done step, [1] select_done step, [2] blocks finished, [3] timeout flag
     uint64_t async_step = 0;
     bool async_pending = false;
@@ -341,11 +341,11 @@ void corpus_range_sets_drop(smt_corpus *c);   // search.cpp (smt_corpus_destroy)
 int range_tile_table(smt_ctx *ctx, const ScanArgs &a, uint64_t *scratch_table, const uint64_t **table);
 int range_chunk_table(smt_ctx *ctx, const ScanArgs &a, uint64_t *scratch_table, const uint64_t **table);
 
-// Range-filtered scans stream FILTER_CHUNK-row chunks described by a per-chunk table (scan_kernels.hip).
+// Range-filtered scans stream FILTER_CHUNK-row chunks described by a per-chunk table (range_tables.hip).
 constexpr int FILTER_CHUNK = 4;
 int launch_build_chunk_table(smt_ctx *ctx, const smt_range *ranges, const uint64_t *chunk_prefix, uint32_t n_ranges,
                              uint64_t n_chunks, uint64_t *table);
-// ... and, for gemm_rowreg_kernel, the aligned 32-row tiles they touch: tile | row mask << 32 per tile (scan_kernels.hip)
+// ... and, for gemm_rowreg_kernel, the aligned 32-row tiles they touch: tile | row mask << 32 per tile (range_tables.hip)
 int launch_build_tile_table(smt_ctx *ctx, const smt_range *ranges, const uint64_t *tile_prefix, uint32_t n_ranges, uint64_t n_vtiles,
                             uint64_t *table);
 // A filtered batch takes gemm_rowreg_kernel (and the operand image) when the wanted rows fill at least a quarter of the tiles they
@@ -388,7 +388,8 @@ struct Delivery {
     unsigned long long *done = nullptr;   // device counter of finished select blocks (0 between launches)
 };
 
-// Select stage: block lists -> best k_out per query with exact f64 distances (scan_kernels.hip).
+// Select stage: block lists -> best k_out per query with exact f64 distances (select.hip).
+constexpr int SEL_MAX_LISTS = 512;   // lists per query the select takes: the scan launches at most this many blocks
 struct SelectArgs {
     const float *corpus = nullptr;
     const float *queries = nullptr;

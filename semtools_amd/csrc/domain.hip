@@ -19,7 +19,7 @@
 // tests/test_gpu_domain.py walks every kernel family at both ends).  Rows are checked where they ENTER a corpus
 // (smt_corpus_append_host, smt_corpus_write_rows, smt_corpus_from_device, smt_embed(append_to), the file loaders and their sharded
 // forms): SMT_E_INVALID, the corpus unchanged, the message names the first offending row.  Host-form queries are checked on the host;
-// the device entry points report SMT_STATUS_INVALID_QUERY per query (final_select_kernel, scan_kernels.hip).
+// the device entry points report SMT_STATUS_INVALID_QUERY per query (final_select_kernel, select.hip).
 // model2vec's pool step with `normalize` emits unit or zero rows, so nothing the reference's own path produces is ever refused --
 // only a corrupt table or hand-made vectors are.
 #include "common.h"

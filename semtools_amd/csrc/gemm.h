@@ -50,7 +50,7 @@ struct GemmParams {
     key_t64 *cand;            // [nq][cand_cap]
     unsigned int *counts;     // [nq]
     // range-filtered batches (gemm_ldsrow_kernel<.., true>): the rows to scan are the FILTER_CHUNK-row chunks of the
-    // chunk table (scan_kernels.hip: row0 | valid rows << 32); a "tile" is then 8 consecutive chunks
+    // chunk table (range_tables.hip: row0 | valid rows << 32); a "tile" is then 8 consecutive chunks
     const uint64_t *chunk_table;
     uint64_t n_chunks;
     // range-filtered batches of gemm_rowreg_kernel: the level's tiles are the ENTRIES of this table (aligned 32-row tile | mask of the

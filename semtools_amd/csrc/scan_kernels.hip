@@ -1,7 +1,8 @@
-// scan_kernels.hip -- K2 (single/few-query cosine scan + per-wave top-k'), the
-// chunk table of range-filtered scans, the select stage (merge + exact f64
-// rescoring, optionally overlapped with the next scan: async select), and the
-// cross-shard top-k merge.  K4 (threshold mode) lives in threshold.hip.
+// scan_kernels.hip -- K2 (single/few-query cosine scan + per-wave top-k'): scan_topk_kernel, the grouped
+// scan_pair_kernel with its host/device pairing protocol, and launch_scan_topk, which runs the passes of a call
+// and hands the block lists to the select stage (select.hip; optionally overlapped with the next scan: async
+// select).  The chunk table of range-filtered scans is built in range_tables.hip, the cross-shard top-k merge
+// lives in merge.hip, K4 (threshold mode) in threshold.hip.
 // gfx950 only (wave64, DPP, 16 B/lane row loads).
 //
 // Replaces the `for doc / for line: f32::cosine(q, e)` loop and the
@@ -19,6 +20,8 @@
 // so returned distances/ordering do not depend on the reduction tree.
 #include "common.h"
 #include "device_utils.h"
+#include "device_flags.h"
+#include "chunk_deal.h"
 
 namespace smt {
 
@@ -48,103 +51,11 @@ struct ScanParams {
     unsigned long long gate_ticks;
 };
 
-// ---- async select: device-scope flags between the scan of step i (main stream) and its select (aux stream) ----
-__device__ __forceinline__ unsigned long long flag_load(const unsigned long long *f)
-{
-    return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void flag_store(unsigned long long *f, unsigned long long v)
-{
-    __hip_atomic_store(f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// One thread waits until *f >= want.  Gives up after ~2 s of the 100 MHz wall clock and raises flags[3]
-// (after which no kernel waits any more): a missing partner kernel must end in an error code at the next
-// synchronise, never in a hung GPU.
-__device__ __forceinline__ void flag_wait(unsigned long long *flags, int which, unsigned long long want)
-{
-    if (flag_load(flags + which) >= want) return;
-    const unsigned long long t0 = wall_clock64();
-    while (flag_load(flags + which) < want) {
-        __builtin_amdgcn_s_sleep(16);
-        if (flag_load(flags + 3) != 0ull) break;
-        if (wall_clock64() - t0 > 200000000ull) { flag_store(flags + 3, 1ull); break; }
-    }
-}
-
 __device__ __forceinline__ void gate_wait(const ScanParams &p)
 {
     if (flag_load(p.gate) >= p.gate_open) return;
     const unsigned long long t0 = wall_clock64();
     while (flag_load(p.gate) < p.gate_open && wall_clock64() - t0 < p.gate_ticks) __builtin_amdgcn_s_sleep(8);
-}
-
-// Range filter (path-subset search, src/workspace/store.rs:507-515): the rows to scan are the concatenation
-// of sorted, disjoint row ranges.  Each range is cut into chunks of FILTER_CHUNK rows (the last one short),
-// and ONE descriptor per chunk says where it starts and how many of its rows are valid, so the streaming
-// kernels never search the range list: they read descriptor c (a wave-uniform 8-byte load, requested one
-// pipeline stage before the rows) and stream row0 .. row0+cnt-1.  2 B per scanned row of extra traffic.
-// (The first version binary-searched the ranges per ROW inside the scan loop: 3 dependent scalar loads in
-// front of every row load made a 2-range search of 1 M rows 3x slower than the unfiltered one.)
-__global__ void build_chunk_table_kernel(const smt_range *ranges, const uint64_t *chunk_prefix, uint32_t n_ranges,
-                                         uint64_t n_chunks, uint64_t *table)
-{
-    const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_chunks) return;
-    uint32_t lo = 0, hi = n_ranges;  // invariant: chunk_prefix[lo] <= c < chunk_prefix[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (chunk_prefix[mid] <= c) lo = mid; else hi = mid;
-    }
-    const uint64_t row0 = ranges[lo].begin + (c - chunk_prefix[lo]) * FILTER_CHUNK;
-    const uint64_t cnt = ranges[lo].end - row0 < (uint64_t)FILTER_CHUNK ? ranges[lo].end - row0 : (uint64_t)FILTER_CHUNK;
-    table[c] = row0 | (cnt << 32);
-}
-
-int launch_build_chunk_table(smt_ctx *ctx, const smt_range *ranges, const uint64_t *chunk_prefix, uint32_t n_ranges,
-                             uint64_t n_chunks, uint64_t *table)
-{
-    if (n_chunks == 0) return SMT_OK;
-    hipLaunchKernelGGL(build_chunk_table_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, ctx->stream, ranges,
-                       chunk_prefix, n_ranges, n_chunks, table);
-    SMT_HIP_CHECK(hipGetLastError());
-    return SMT_OK;
-}
-
-// The same filter for the MFMA kernel (gemm_rowreg_kernel), whose unit is the ALIGNED 32-row tile -- the unit of the corpus' fp16
-// operand image: one descriptor per tile that holds at least one wanted row, tile index | row mask << 32.  Ranges that meet
-// inside a tile share its descriptor (tile_prefix counts a tile for the first range that touches it: search.cpp stage_ranges),
-// so no tile is read twice however small the documents are.
-__global__ void build_tile_table_kernel(const smt_range *ranges, const uint64_t *tile_prefix, uint32_t n_ranges, uint64_t n_vtiles,
-                                        uint64_t *table)
-{
-    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= n_vtiles) return;
-    uint32_t lo = 0, hi = n_ranges;  // first range i with tile_prefix[i + 1] > v (ranges that own no tile are skipped)
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (tile_prefix[mid + 1] > v) hi = mid; else lo = mid + 1;
-    }
-    const uint32_t i = lo;
-    const uint64_t first = ranges[i].begin >> 5;
-    const bool shared = i > 0 && ((ranges[i - 1].end - 1) >> 5) == first;   // (empty ranges were dropped by the host)
-    const uint64_t tile = first + (shared ? 1 : 0) + (v - tile_prefix[i]);
-    const uint64_t t0 = tile << 5, t1 = t0 + 32;
-    uint32_t mask = 0;
-    for (uint32_t k = i; k < n_ranges && ranges[k].begin < t1; ++k) {
-        const uint64_t b = ranges[k].begin > t0 ? ranges[k].begin : t0, e = ranges[k].end < t1 ? ranges[k].end : t1;
-        if (e > b) mask |= (uint32_t)((~0ull >> (64 - (e - b))) << (b - t0));
-    }
-    table[v] = tile | ((uint64_t)mask << 32);
-}
-
-int launch_build_tile_table(smt_ctx *ctx, const smt_range *ranges, const uint64_t *tile_prefix, uint32_t n_ranges, uint64_t n_vtiles,
-                            uint64_t *table)
-{
-    if (n_vtiles == 0) return SMT_OK;
-    hipLaunchKernelGGL(build_tile_table_kernel, dim3((unsigned)((n_vtiles + 255) / 256)), dim3(256), 0, ctx->stream, ranges,
-                       tile_prefix, n_ranges, n_vtiles, table);
-    SMT_HIP_CHECK(hipGetLastError());
-    return SMT_OK;
 }
 
 // ------------------------------------------------------------------------- K2
@@ -174,7 +85,10 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
 {
     static_assert(!FILTERED || U == FILTER_CHUNK, "filtered scans use the chunk table's chunk size");
     static_assert(!STEAL || !FILTERED, "dynamic groups are for the unfiltered scan");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    // (No alignment attribute on smem_raw here, in scan_pair_kernel and in select.hip: while they shared a unit with the merge kernels,
+    // whose declaration has none, that one decided the symbol's alignment -- ds_read2_b64 where a 16-byte base gives ds_read_b128.
+    // Kept as it has always been compiled: other instructions in 32 kernels are a tuning change, to be measured on its own.)
+    extern __shared__ unsigned char smem_raw[];
     key_t64 *s_keys = reinterpret_cast<key_t64 *>(smem_raw);  // [waves][64]
 
     const int lane = threadIdx.x & 63;
@@ -209,37 +123,18 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
         thr_r[n] = 0xFFFFFFFFu;
     }
 
-    // The block owns the chunks (U rows each) c(t) = ((t / waves) * gridDim.x + blockIdx.x) * waves + t % waves,
-    // t = 0, 1, ... -- the same rows a static grid-stride deal would give it -- but its waves CLAIM them from
-    // an LDS counter.  The CU's arbiter favours the older wave of each SIMD: with a static deal waves 0-3
-    // finished 12 us before waves 4-7 (of 145) and the CU ran half empty at the end.  Which wave reduces a
-    // chunk cannot change the block's top-k' (same row set), so the output is still a function of the data.
+    // (which chunks the block owns and how its waves claim them: chunk_deal.h)
     const uint64_t n_chunks = p.n_chunks;
     // the table was written by an earlier kernel and is read-only here: constant address space => scalar loads
     // (a plain global load is a VECTOR load that returns in order with the row loads and drains the pipeline)
     const const_u64_ptr const_table = (const_u64_ptr)(uintptr_t)p.chunk_table;
-    auto chunk_id = [&](uint32_t t) -> uint64_t {
-        const uint64_t c = ((uint64_t)(t / waves_per_block) * gridDim.x + blockIdx.x) * waves_per_block + t % waves_per_block;
-        return uniform_u64(c);  // the division runs on the VALU: tell the compiler the result is wave-uniform (scalar loads)
-    };
-    auto claim = [&]() -> uint32_t {
-        uint32_t t = 0;
-        if (lane == 0) t = atomicAdd(s_next, 1u);
-        return (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-    };
+    auto chunk_id = [&](uint32_t t) -> uint64_t { return deal_chunk(t, waves_per_block); };
+    auto claim = [&]() -> uint32_t { return deal_claim(s_next, lane); };
     // descriptor of chunk c: first corpus row | valid rows << 32 (0 rows beyond the end)
     auto fetch_desc = [&](uint64_t c) -> uint64_t {
         return c < n_chunks ? const_table[c] : 0ull;  // wave-uniform address in the constant address space: s_load
     };
-    auto issue_loads = [&](uint64_t desc, f32x4 (&c)[U], uint32_t (&row)[U]) {
-        const uint32_t row0 = (uint32_t)desc, cnt = (uint32_t)(desc >> 32);
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            row[j] = row0 + ((uint32_t)j < cnt ? (uint32_t)j : 0u);  // rows beyond cnt re-read row0 (result discarded)
-            const f32x4 *src = reinterpret_cast<const f32x4 *>(p.corpus + (uint64_t)row[j] * 256) + lane;
-            c[j] = NT ? __builtin_nontemporal_load(src) : *src;
-        }
-    };
+    auto issue_loads = [&](uint64_t desc, f32x4 (&c)[U], uint32_t (&row)[U]) { deal_issue_loads<U, NT>(p, desc, lane, c, row); };
     // STEAL: ring[g & 7] = (group g of this block | its base slot / 2^steal_lr); the first STEAL_DEPTH groups are static
     uint2 *s_ring = reinterpret_cast<uint2 *>(s_next + 2);
     if (threadIdx.x == 0) *s_next = (uint32_t)waves_per_block;  // chunks 0..waves-1 are dealt: wave w starts on chunk w
@@ -251,6 +146,18 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
     }
     __syncthreads();
 
+    // insert (d, r) into list n keeping (distance asc, row asc) order; the threshold is the entry of lane kp - 1
+#define SMT_LIST_INSERT(n, d, r)                                                                                  \
+    do {                                                                                                          \
+        const bool less = (ld[n] < (d)) || (ld[n] == (d) && lr[n] < (r));                                         \
+        const int pos = __popcll(__ballot(less));                                                                 \
+        const float sd = dpp_f<DPP_WAVE_SHR1>(ld[n]);                                                             \
+        const uint32_t sr = dpp_u<DPP_WAVE_SHR1>(lr[n]);                                                          \
+        if (lane > pos) { ld[n] = sd; lr[n] = sr; }                                                               \
+        else if (lane == pos) { ld[n] = (d); lr[n] = (r); }                                                       \
+        thr_d[n] = readlane_f(ld[n], kp - 1);                                                                     \
+        thr_r[n] = (uint32_t)__builtin_amdgcn_readlane((int)lr[n], kp - 1);                                       \
+    } while (0)
     // One row against the NQ queries.  `valid` is wave-uniform and gates only the (rare) insert, never the
     // arithmetic: the four rows' DPP chains must stay free to interleave.  How `valid` is WRITTEN matters: with
     // "j < rows_in_chunk" clang hoists a branch in front of every row's reduction (+2 us per 1 M-row launch,
@@ -264,15 +171,7 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
             const float d = dist_f32(ab, b2, rq[n], qz[n]);                                                       \
             const uint32_t r = (rj);                                                                              \
             if (valid && (d < thr_d[n] || (d == thr_d[n] && r < thr_r[n]))) {                                     \
-                /* insert (d, r) keeping (distance asc, row asc) order */                                         \
-                const bool less = (ld[n] < d) || (ld[n] == d && lr[n] < r);                                       \
-                const int pos = __popcll(__ballot(less));                                                         \
-                const float sd = dpp_f<DPP_WAVE_SHR1>(ld[n]);                                                     \
-                const uint32_t sr = dpp_u<DPP_WAVE_SHR1>(lr[n]);                                                  \
-                if (lane > pos) { ld[n] = sd; lr[n] = sr; }                                                       \
-                else if (lane == pos) { ld[n] = d; lr[n] = r; }                                                   \
-                thr_d[n] = readlane_f(ld[n], kp - 1);                                                             \
-                thr_r[n] = (uint32_t)__builtin_amdgcn_readlane((int)lr[n], kp - 1);                               \
+                SMT_LIST_INSERT(n, d, r);                                                                         \
             }                                                                                                     \
         }                                                                                                         \
     } while (0)
@@ -282,11 +181,7 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
     // (row, query) pairs per instruction) and one ballot finds the pairs under the query's threshold; only those (rare once the
     // lists have filled) are read out and inserted.  Per chunk and query 15 + ~14 instructions instead of 4 x (11 + ~14): with the
     // row-at-a-time form the reductions made two queries cost 1.4 x and four 2.3 x one query's pass (instruction issue, not HBM).
-    // VALID(j): wave-uniform, is row j of the chunk a real row.  SMT_QUERY_ON(n): does query n take part (scan_pair_kernel decides
-    // that while it runs; a constant here).  SMT_QUERY_VEC(n): this lane's four components of query n -- registers here, an LDS
-    // image in scan_pair_kernel, whose register budget has no room for four queries.
-#define SMT_QUERY_ON(n) true
-#define SMT_QUERY_VEC(n) q[n]
+    // VALID(j): wave-uniform, is row j of the chunk a real row.
 #define SMT_REDUCE_CHUNK4(cq, rq4, VALID)                                                                         \
     do {                                                                                                          \
         const int jj = lane & 3;                                                                                  \
@@ -298,9 +193,8 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
             pb[j] = (cq)[j].x * (cq)[j].x + (cq)[j].y * (cq)[j].y + (cq)[j].z * (cq)[j].z + (cq)[j].w * (cq)[j].w; \
         const float b2 = wave_sum4(pb[0], pb[1], pb[2], pb[3], lane);                                             \
         _Pragma("unroll") for (int n = 0; n < NQ; ++n) {                                                          \
-            if (!(SMT_QUERY_ON(n))) continue;                                                                     \
             float pa[4];                                                                                          \
-            const f32x4 qv = SMT_QUERY_VEC(n);                                                                    \
+            const f32x4 qv = q[n];                                                                                \
             _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                         \
                 pa[j] = (cq)[j].x * qv.x + (cq)[j].y * qv.y + (cq)[j].z * qv.z + (cq)[j].w * qv.w;                \
             const float ab = wave_sum4(pa[0], pa[1], pa[2], pa[3], lane);                                         \
@@ -313,14 +207,7 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
                 const float d = readlane_f(d4, j);                                                                \
                 const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)r_mine, j);                           \
                 if (d < thr_d[n] || (d == thr_d[n] && r < thr_r[n])) {   /* (an earlier insert may have moved the threshold) */ \
-                    const bool less = (ld[n] < d) || (ld[n] == d && lr[n] < r);                                   \
-                    const int pos = __popcll(__ballot(less));                                                     \
-                    const float sd = dpp_f<DPP_WAVE_SHR1>(ld[n]);                                                 \
-                    const uint32_t sr = dpp_u<DPP_WAVE_SHR1>(lr[n]);                                              \
-                    if (lane > pos) { ld[n] = sd; lr[n] = sr; }                                                   \
-                    else if (lane == pos) { ld[n] = d; lr[n] = r; }                                               \
-                    thr_d[n] = readlane_f(ld[n], kp - 1);                                                         \
-                    thr_r[n] = (uint32_t)__builtin_amdgcn_readlane((int)lr[n], kp - 1);                           \
+                    SMT_LIST_INSERT(n, d, r);                                                                     \
                 }                                                                                                 \
             }                                                                                                     \
         }                                                                                                         \
@@ -463,9 +350,8 @@ __global__ void __launch_bounds__(1024) scan_topk_kernel(ScanParams p)
         }
     }
 #undef SMT_REDUCE_ROW
-#undef SMT_QUERY_ON
-#undef SMT_QUERY_VEC
-    // (SMT_REDUCE_CHUNK4 is used once more, by scan_pair_kernel below)
+#undef SMT_REDUCE_CHUNK4
+#undef SMT_LIST_INSERT
 
     if (p.stamps && lane == 0) p.stamps[wave_global * 2 + 1] = wall_clock64();
 
@@ -629,7 +515,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
 {
     constexpr int U = 4;
     constexpr int NQ = GROUP_MAX;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    extern __shared__ unsigned char smem_raw[];
     key_t64 *s_keys = reinterpret_cast<key_t64 *>(smem_raw);  // [NQ][waves][64]: the launch is sized for a full group
 
     const int lane = threadIdx.x & 63;
@@ -690,14 +576,8 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
         return;
     }
 
-    auto chunk_v0 = [&](uint32_t t) -> uint64_t {   // (the division runs on the VALU: say that the result is wave-uniform)
-        return uniform_u64((((uint64_t)(t / waves_per_block) * gridDim.x + blockIdx.x) * waves_per_block + t % waves_per_block) * U);
-    };
-    auto claim = [&]() -> uint32_t {
-        uint32_t t = 0;
-        if (lane == 0) t = atomicAdd(s_next, 1u);
-        return (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-    };
+    auto chunk_v0 = [&](uint32_t t) -> uint64_t { return deal_chunk(t, waves_per_block) * U; };   // (chunk_deal.h)
+    auto claim = [&]() -> uint32_t { return deal_claim(s_next, lane); };
     // (row numbers are far below 2^63: the sign of the difference is a scalar compare, where "<" on 64 bits takes the VALU and a
     // vector register pair for n_virtual -- this kernel has none to spare)
     auto in_corpus = [&](uint64_t v) -> bool { return (int64_t)(v - p.n_virtual) < 0; };
@@ -758,7 +638,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
     // (ONE loop: instantiations behind a branch share the first rows' registers, and the allocator then takes more than either
     // alone -- the select needs this kernel at 64 VGPRs or fewer beside it.)
     //
-    // The group reducer.  SMT_REDUCE_CHUNK4 runs one basic block per query: an LDS read of the query image with its wait directly
+    // The group reducer.  SMT_REDUCE_CHUNK4 (scan_topk_kernel's, used here at first with the queries read from LDS) runs one basic block per query: an LDS read of the query image with its wait directly
     // behind it, one wave_sum4 tree alone (its DPP wait states padded with s_nop) and a candidate test of nested exec-mask regions,
     // four times per chunk although the four queries test the same four rows -- the grouped pass was bound by instruction issue, not
     // by HBM.  Here the images are read at the top of the chunk, the trees run interleaved (device_utils.h wave_sum4_multi: <c, c>
@@ -769,7 +649,6 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
     // 16 g .. 16 g + 3) and not in quad g: the rotations by 4 and 8 of wave_sum4 add the four quads of a row in an order that
     // depends on the quad -- lanes 4 .. 7 hold (q1 + q0) + (q3 + q2) where lanes 0 .. 3, which the one-query loop reads, hold
     // (q0 + q3) + (q2 + q1), one rounding apart -- while the same position of another row holds the same bits.
-#define SMT_QUERY_ON(n) ((n) < n_on)
 #define SMT_ROW_DOT(cj, qv) ((cj).x * (qv).x + (cj).y * (qv).y + (cj).z * (qv).z + (cj).w * (qv).w)
 #define SMT_GROUP_INSERT(n)                                                                                       \
     do {                                                                                                          \
@@ -887,7 +766,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
     if (wave == 0 && lane == 0) (void)__hip_atomic_fetch_add(p.gate, (unsigned long long)n_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
-        if (!(SMT_QUERY_ON(n))) break;
+        if (n >= n_on) break;
         const bool have = lane < kp && lr[n] != 0xFFFFFFFFu;
         s_keys[((size_t)n * waves_per_block + wave) * 64 + lane] = have ? make_key(ld[n], lr[n]) : KEY_PAD;
         const unsigned int cnt = (unsigned int)__popcll(__ballot(have));
@@ -896,7 +775,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
     __syncthreads();
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
-        if (!(SMT_QUERY_ON(n))) break;
+        if (n >= n_on) break;
         const key_t64 *keys_n = s_keys + (size_t)n * waves_per_block * 64;
         key_t64 *out = (n == 0 ? p.block_lists : reinterpret_cast<key_t64 *>((uintptr_t)uniform_u64(s_pair[2 + n]))) + (size_t)blockIdx.x * kp;
         const key_t64 mine = keys_n[wave * 64 + lane];
@@ -912,631 +791,11 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
             if ((unsigned int)lane >= total) out[lane] = KEY_PAD;
         }
     }
-#undef SMT_QUERY_ON
 }
-#undef SMT_REDUCE_CHUNK4
 // dynamic LDS of a scan_pair_kernel launch: the four key regions, the waves' key counts, the query images, the block's control words
 static inline size_t pair_smem_bytes(int threads)
 {
     return (size_t)GROUP_MAX * (threads / 64) * 64 * sizeof(key_t64) + 256 + (size_t)GROUP_MAX * 1024 + 9 * 8 + 16;
-}
-
-// --------------------------------------------------- exact f64 distance (A5): device_utils.h exact_distance
-__global__ void rescore_rows_kernel(const float *corpus, const float *query, const uint32_t *rows,
-                                    uint64_t n, double *out)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        out[i] = exact_distance(reinterpret_cast<const f32x4 *>(query),
-                                reinterpret_cast<const f32x4 *>(corpus + (uint64_t)rows[i] * 256));
-}
-
-// the same for the rows of MANY queries in one launch: row i belongs to query qidx[i] of the [n_queries][256] block
-__global__ void rescore_rows_multi_kernel(const float *corpus, const float *queries, const uint32_t *rows, const uint32_t *qidx,
-                                          uint64_t n, double *out)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        out[i] = exact_distance(reinterpret_cast<const f32x4 *>(queries + (uint64_t)qidx[i] * 256),
-                                reinterpret_cast<const f32x4 *>(corpus + (uint64_t)rows[i] * 256));
-}
-
-// dst[i] = src[idx[i]] for rows of 256 f32: one wave per row
-__global__ void gather_rows256_kernel(const float *src, const uint32_t *idx, uint32_t n, float *dst)
-{
-    const uint32_t i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (i < n)
-        reinterpret_cast<f32x4 *>(dst + (size_t)i * 256)[threadIdx.x & 63] =
-            reinterpret_cast<const f32x4 *>(src + (size_t)idx[i] * 256)[threadIdx.x & 63];
-}
-
-// ------------------------------------------------ select: prune, rank, rescore
-// Input: n_lists sorted lists (one per scan block) of kp keys each, ascending,
-// padded with KEY_PAD; valid keys are distinct (distinct rows).  We need the kp
-// smallest keys of the union WITHOUT sorting M = n_lists*kp keys.
-//
-// Pruning bound.  For a column j (1-based) let c_j = ceil(kp / j) and let
-// tau_j be the c_j-th smallest of the lists' j-th entries.  At least c_j lists
-// hold >= j keys <= tau_j, i.e. >= kp keys of the union are <= tau_j, so the
-// union's kp-th smallest key is <= tau_j.  tau = min over a dyadic set of
-// columns {1,2,4,..,kp}.  Keys > tau can be dropped.  Survivors are few: if
-// m_b = #keys of list b that are <= tau then #{b : m_b >= j} <= c_j' for the
-// largest used column j' <= j, hence S = sum_b m_b <= sum_j' (gap_j' * c_j')
-// which is <= kp * (log2(kp) + 2) in the WORST case (<= 512 for kp <= 72), and
-// about kp + 2 on uncorrelated data (column 1 alone is then nearly tight).
-// Survivors are ranked by counting (S^2 / threads compares), no sort.
-constexpr int SEL_THREADS = 1024;
-constexpr int SEL_MAX_LISTS = 512;
-constexpr int SEL_MAX_COLS = 8;
-constexpr int SEL_SURV_CAP = 1024;
-constexpr int SEL_FEW_KEYS = 512;    // up to this many keys over all lists the select ranks them all (no column bounds)
-constexpr int ROW_STRIDE_F4 = 65;  // LDS row stride in float4 (1040 B): conflict-free b128 reads
-constexpr int PROD_STRIDE = 258;   // LDS row stride of the f64 product tables (2064 B)
-constexpr int SEL_FAST_KP = 34;    // product tables fit the 160 KiB LDS up to this k' (k <= 26)
-
-// c-th smallest key of `col[0..L)` (PAD = missing), published with atomicMin into *tau.
-// Executed by ONE wave; slots beyond L hold PAD which never satisfies the predicates below.
-template <int NS>
-__device__ __forceinline__ void column_tau(const key_t64 *col, int L, int c, key_t64 *tau)
-{
-    const int lane = threadIdx.x & 63;
-    uint32_t vh[NS], vl[NS];
-#pragma unroll
-    for (int u = 0; u < NS; ++u) {
-        const int b = lane + u * 64;
-        const key_t64 x = b < L ? col[b] : KEY_PAD;
-        vh[u] = (uint32_t)(x >> 32);
-        vl[u] = (uint32_t)x;
-    }
-    uint32_t lo = 0, hi = 0xFFFFFFFFu;
-    while (lo < hi) {  // smallest distance t with #{vh <= t} >= c   (mid <= 0xFFFFFFFE: PAD never counts)
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        int cnt = 0;
-#pragma unroll
-        for (int u = 0; u < NS; ++u) cnt += __popcll(__ballot(vh[u] <= mid));
-        if (cnt >= c) hi = mid; else lo = mid + 1;
-    }
-    if (lo == 0xFFFFFFFFu) return;  // fewer than c entries: no bound from this column
-    const uint32_t dstar = lo;
-    int below = 0, ties = 0;
-#pragma unroll
-    for (int u = 0; u < NS; ++u) {
-        below += __popcll(__ballot(vh[u] < dstar));
-        ties += __popcll(__ballot(vh[u] == dstar));
-    }
-    const int need = c - below;  // need-th smallest row among the entries at distance dstar (>= 1)
-    uint32_t rlo = 0xFFFFFFFFu;  // every tie needed: tau = (dstar, max row)
-    if (ties != need) {
-        rlo = 0;
-        uint32_t rhi = 0xFFFFFFFFu;
-        while (rlo < rhi) {
-            const uint32_t mid = rlo + ((rhi - rlo) >> 1);
-            int cnt = 0;
-#pragma unroll
-            for (int u = 0; u < NS; ++u) cnt += __popcll(__ballot(vh[u] == dstar && vl[u] <= mid));
-            if (cnt >= need) rhi = mid; else rlo = mid + 1;
-        }
-    }
-    if (lane == 0) atomicMin(tau, ((key_t64)dstar << 32) | (key_t64)rlo);
-}
-
-struct FinalParams {
-    const float *corpus;
-    const float *queries;
-    const key_t64 *lists;  // query qi's lists start at lists + qi*list_stride: [n_lists][kp]
-    uint64_t list_stride;  // in keys
-    uint32_t n_lists;      // <= SEL_MAX_LISTS
-    uint32_t kp;
-    uint32_t k_out;
-    int ws_threshold;
-    float ws_thr_score;
-    uint64_t row_base;
-    uint64_t *out_rows;   // [nq][k_out]
-    double *out_dist;     // [nq][k_out]
-    uint64_t *out_counts; // [nq] or nullptr
-    uint64_t out_stride;  // words between consecutive queries' output lists (>= k_out)
-    double f32_err;       // > 0: exactness certificate (SelectArgs::f32_err)
-    uint64_t *out_uncertain;       // [nq] or nullptr
-    unsigned int *out_status;      // [nq] or nullptr (SelectArgs::out_status)
-    unsigned long long *status;    // the context's sticky "uncertain selects" counter
-    unsigned long long *dbg;  // optional: s_memtime stamps of query 0's phases (tuning key select_debug_ptr)
-    unsigned long long *flags;  // async select (or nullptr), see ScanParams
-    unsigned long long step;
-    const unsigned int *overflow;  // SelectArgs::overflow
-    // delivery by the last block to finish (common.h Delivery; host_flag == nullptr: none)
-    const unsigned long long *dev_out;
-    unsigned long long *host_out;
-    unsigned long long *host_flag;
-    unsigned long long *done;
-    unsigned long long seq;
-    uint32_t out_words;
-};
-
-#define SEL_STAMP(i) do { if (p.dbg && blockIdx.x == 0 && threadIdx.x == 0) p.dbg[i] = __builtin_readcyclecounter(); } while (0)
-
-// One block per query.
-// KREG = keys a thread holds in registers: 8 covers n_lists * k' <= 8192 (every k <= 24 at 256 lists) in 70
-// VGPRs, so that the 16-wave block fits on a CU NEXT TO a scan block (async select); 36 covers the maximum
-// (512 lists x 72) and takes the whole register file.
-// OVF: the batched path's instantiation, which also reads the candidate-buffer overflow flag (SelectArgs::overflow).  A template
-// parameter and not a null test: with the flag code in it final_select_kernel<8> allocated 106 VGPRs instead of 90 and no longer
-// fitted on a CU NEXT TO a scan block (4 waves/SIMD x 96 + the scan's 2 x 56 <= 512) -- the async select of the one-query pipeline
-// then waited for scan blocks to leave and a 1 M-row step went from 153 to 204 us (found by the round-5 closing bench run).
-template <int KREG, bool OVF>
-__device__ __forceinline__ void final_select_body(const FinalParams &p, const uint32_t qi, unsigned char *smem_raw)
-{
-    const int kp = (int)p.kp;
-    const int L = (int)p.n_lists;
-    // LDS carve (all offsets multiples of 16; no static LDS in this kernel): small arrays first, then one big
-    // region used twice -- [candidate-row tiles | survivors | column entries] until the best k' are known,
-    // then (fast path) the exact-product tables of the rescoring stage.
-    unsigned int *s_srank = reinterpret_cast<unsigned int *>(smem_raw);        // [96]
-    unsigned int *s_rank = s_srank + 96;                                        // [kp+pad] final ranks
-    double *s_qd = reinterpret_cast<double *>(s_rank + 80);                     // [256] query as f64 (slow path)
-    key_t64 *s_best = reinterpret_cast<key_t64 *>(s_qd + 256);                  // [kp] (+pad to even)
-    double *s_d = reinterpret_cast<double *>(s_best + ((kp + 1) & ~1));        // [kp]
-    double *s_b2 = s_d + ((kp + 1) & ~1);                                       // [kp] row norms^2 (fast path)
-    uint32_t *s_r = reinterpret_cast<uint32_t *>(s_b2 + ((kp + 1) & ~1));      // [kp]
-    key_t64 *s_tau = reinterpret_cast<key_t64 *>(s_r + ((kp + 3) & ~3));       // [1]
-    double *s_a2 = reinterpret_cast<double *>(s_tau + 1);                       // [1] query norm^2
-    unsigned int *s_cnt = reinterpret_cast<unsigned int *>(s_a2 + 1);          // [0]=survivors [1]=valid [2]=max |q_i| bits [3]=this block delivers
-    unsigned char *s_big = reinterpret_cast<unsigned char *>(s_cnt + 4);
-    f32x4 *s_rows = reinterpret_cast<f32x4 *>(s_big);                           // [kp+1][65] float4
-    key_t64 *s_surv = reinterpret_cast<key_t64 *>(s_rows + (size_t)(kp + 1) * ROW_STRIDE_F4);  // [SEL_SURV_CAP]
-    key_t64 *s_col = s_surv + SEL_SURV_CAP;                                      // [ncols][L] column entries
-    double *s_P = reinterpret_cast<double *>(s_big);                            // [kp][PROD_STRIDE] q_i * c_i (exact in f64)
-    double *s_B = s_P + (size_t)kp * PROD_STRIDE;                               // [kp][PROD_STRIDE] c_i * c_i
-    double *s_Q = s_B + (size_t)kp * PROD_STRIDE;                               // [256]            q_i * q_i
-    const bool fast_rescore = kp <= SEL_FAST_KP;
-
-    const key_t64 *lists = p.lists + (size_t)qi * p.list_stride;
-    if (p.flags) {
-        // launched on the aux stream while the scan of this step may still be running on the main stream
-        if (threadIdx.x == 0) {
-            flag_wait(p.flags, 0, p.step);
-            // acquire at agent scope by ONE thread (invalidates this CU's vector L1 and the XCD's non-coherent
-            // L2 lines: the lists were written through other XCDs' L2s); the barrier hands it to the block
-            (void)__hip_atomic_load(p.flags + 0, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-    }
-    SEL_STAMP(0);
-
-    static_assert(KREG == 8 || KREG == (SEL_MAX_LISTS * 72 + SEL_THREADS - 1) / SEL_THREADS, "8 or 36");
-    if (L == 1) {
-        // ONE list per query (the batched kernel's level select left the k' best of every query sorted at the head of its buffer;
-        // an index search with one probed segment): it IS the answer's candidate set -- no column bounds, no compaction, no ranks.
-        // (Round 5: those three phases were ~7 us of dependent latencies in front of every batched call's rescoring, 10 % of a
-        // small batch over a small corpus.)
-        if (threadIdx.x == 0) { *s_tau = KEY_PAD; s_cnt[0] = 0; s_cnt[1] = 0; s_cnt[2] = 0; }
-        for (int t = threadIdx.x; t < kp; t += blockDim.x) { s_best[t] = lists[t]; s_rank[t] = 0; }
-        __syncthreads();
-    } else {
-    // ---- ONE global-latency phase: every key of the L lists goes to registers (<= 36 per thread)
-    const int M = L * kp;
-    const int n_round = (M + SEL_THREADS - 1) / SEL_THREADS;  // block-uniform
-    key_t64 kreg[KREG];
-    if (KREG == 8 || n_round <= 8) {  // common case (k <= 24): 8 back-to-back loads, one wait
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int e = (int)threadIdx.x + i * SEL_THREADS;
-            const key_t64 x = lists[e < M ? e : M - 1];  // clamped: no branch between the loads
-            kreg[i] = e < M ? x : KEY_PAD;
-        }
-#pragma unroll
-        for (int i = 8; i < KREG; ++i) kreg[i] = KEY_PAD;
-    } else {
-#pragma unroll
-        for (int i = 0; i < KREG; ++i) {
-            const int e = (int)threadIdx.x + i * SEL_THREADS;
-            const key_t64 x = lists[e < M ? e : M - 1];
-            kreg[i] = e < M ? x : KEY_PAD;
-        }
-    }
-
-    // dyadic columns 1,2,4,.. < kp, plus kp: column jj holds entry (1 << jj) except the last = kp
-    int ncols = 1;
-    for (int j = 1; j < kp && ncols < SEL_MAX_COLS; j <<= 1) ++ncols;
-    auto col_of = [&](int jj) { return jj < ncols - 1 ? (1 << jj) : kp; };
-    // the column entries are fetched in the same latency window as the keys (<= 4 per thread)
-    // FEW keys in all (a small corpus: 16 blocks x 11 keys for 1000 rows): no pruning bound -- every key is a survivor and the ranks
-    // below order them directly.  (The column bounds are ~3 us of dependent bisection steps, a quarter of this stage, to prune a set
-    // that is already small.)
-    const bool few = M <= SEL_FEW_KEYS;   // block-uniform
-    key_t64 cval[(SEL_MAX_COLS * SEL_MAX_LISTS) / SEL_THREADS];
-    const int n_col_entries = few ? 0 : ncols * L;
-    if (!few) {
-#pragma unroll
-        for (int u = 0; u < (SEL_MAX_COLS * SEL_MAX_LISTS) / SEL_THREADS; ++u) {
-            int t = (int)threadIdx.x + u * SEL_THREADS;
-            const bool ok = t < n_col_entries;
-            t = ok ? t : 0;
-            const int jj = t / L, bb = t - jj * L;
-            const key_t64 x = lists[(size_t)bb * kp + (col_of(jj) - 1)];
-            cval[u] = ok ? x : KEY_PAD;
-        }
-    }
-    if (threadIdx.x == 0) { *s_tau = KEY_PAD; s_cnt[0] = 0; s_cnt[1] = 0; s_cnt[2] = 0; }
-    for (int t = threadIdx.x; t < kp; t += blockDim.x) { s_best[t] = KEY_PAD; s_rank[t] = 0; }
-    if (!few) {
-#pragma unroll
-        for (int u = 0; u < (SEL_MAX_COLS * SEL_MAX_LISTS) / SEL_THREADS; ++u) {
-            const int t = (int)threadIdx.x + u * SEL_THREADS;
-            if (t < n_col_entries) s_col[t] = cval[u];
-        }
-    }
-    __syncthreads();
-    SEL_STAMP(1);
-
-    // tau_j = c_j-th smallest key of column j.  One wave per column: the column sits in registers
-    // (4 or 8 keys per lane); bisection on the 32 distance bits with ballot counts, then -- only if
-    // several entries share that distance -- on the row bits.  No sort, no O(L^2) ranks.
-    if (!few) {
-        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-        if (wave < ncols) {
-            const int colv = col_of(wave);
-            const int c = (kp + colv - 1) / colv;
-            if (L <= 256) column_tau<4>(s_col + (size_t)wave * L, L, c, s_tau);
-            else column_tau<8>(s_col + (size_t)wave * L, L, c, s_tau);
-        }
-        __syncthreads();
-    }
-    SEL_STAMP(2);
-    const key_t64 tau = *s_tau;   // (few: still KEY_PAD -- every real key passes)
-
-    // compact the survivors (keys <= tau) straight from the registers
-#pragma unroll
-    for (int i = 0; i < KREG; ++i) {
-        if (i < n_round) {
-            const key_t64 key = kreg[i];
-            if (key != KEY_PAD && key <= tau) {
-                const unsigned int slot = atomicAdd(&s_cnt[0], 1u);
-                if (slot < (unsigned)SEL_SURV_CAP) s_surv[slot] = key;
-            }
-        }
-    }
-    __syncthreads();
-    SEL_STAMP(3);
-    const int S = min((int)s_cnt[0], SEL_SURV_CAP);  // bound above guarantees S <= cap for kp <= 72
-    if (S <= 96) {
-        // pair-parallel ranks: thread <-> (i, j), rank[i] += key[j] < key[i]
-        for (int t = threadIdx.x; t < S; t += blockDim.x) s_srank[t] = 0;
-        __syncthreads();
-        for (int pr = threadIdx.x; pr < S * S; pr += blockDim.x) {
-            const int i = pr / S, j = pr - i * S;
-            if (s_surv[j] < s_surv[i]) atomicAdd(&s_srank[i], 1u);
-        }
-        __syncthreads();
-        for (int t = threadIdx.x; t < S; t += blockDim.x)
-            if ((int)s_srank[t] < kp) s_best[s_srank[t]] = s_surv[t];
-    } else {
-        // T = 1024 / S' threads share a survivor (S' = the power of two >= S): each ranks it against a T-th of the set and adds its
-        // share to the survivor's counter.  (One thread per survivor walked all S keys alone while the other 1024 - S threads
-        // idled: 176 survivors -- 16 lists x 11 keys, no column bounds -- took 2.9 us, 349 took 6.3.)  The counters reuse the column
-        // entries' space, which nobody reads any more.
-        unsigned int *s_rk = reinterpret_cast<unsigned int *>(s_col);
-        for (int t = threadIdx.x; t < S; t += blockDim.x) s_rk[t] = 0;
-        __syncthreads();
-        int Sp = 128;
-        while (Sp < S) Sp <<= 1;                      // <= SEL_SURV_CAP = SEL_THREADS
-        const int T = SEL_THREADS / Sp;               // 8, 4, 2 or 1 threads per survivor
-        const int e = (int)threadIdx.x / T, part = (int)threadIdx.x - e * T;
-        if (e < S) {
-            const key_t64 key = s_surv[e];
-            const int per = (S + T - 1) / T, lo = part * per, hi = min(S, lo + per);
-            unsigned int rank = 0;
-            int i = lo;
-#pragma unroll 1
-            for (; i + 4 <= hi; i += 4) {
-                key_t64 x[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) x[u] = s_surv[i + u];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) rank += (x[u] < key) ? 1u : 0u;
-            }
-            for (; i < hi; ++i) rank += (s_surv[i] < key) ? 1u : 0u;
-            if (rank) atomicAdd(&s_rk[e], rank);
-        }
-        __syncthreads();
-        for (int t = threadIdx.x; t < S; t += blockDim.x)
-            if ((int)s_rk[t] < kp) s_best[s_rk[t]] = s_surv[t];
-    }
-    __syncthreads();
-    if (p.dbg && blockIdx.x == 0 && threadIdx.x == 0) p.dbg[8] = (unsigned long long)S;
-    }   // (L > 1)
-    SEL_STAMP(4);
-
-    // ---- exact rescoring (bit-identical to the oracle's index-order f64 sums, see exact_sums()).
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    double my_ab = 0.0, my_b2 = 0.0;
-    const key_t64 my_key = (int)threadIdx.x < kp ? s_best[threadIdx.x] : KEY_PAD;
-    if (fast_rescore) {
-        // The product of two f32 values is EXACT in f64, so "acc = acc + (double)a * (double)b" only rounds in
-        // the add.  All 1024 threads compute the products q_i*c_i, c_i*c_i, q_i*q_i into LDS in parallel (one
-        // wave per candidate row, coalesced 16 B per lane); what stays sequential is one chain of 256 dependent
-        // f64 ADDS per sum, run by 2*k'+1 threads in three different waves.  (Before: each of the k' threads
-        // converted and multiplied inside its chain -- 9.2k cycles for this stage, now the adds alone.)
-        const f32x4 qv = reinterpret_cast<const f32x4 *>(p.queries + (size_t)qi * 256)[lane];
-        // a wave owns candidates wave, wave+16, (wave+32): request all its rows first (ONE global latency)
-        constexpr int ROWS_PER_WAVE = (SEL_FAST_KP + SEL_THREADS / 64 - 1) / (SEL_THREADS / 64);  // 3
-        f32x4 bv[ROWS_PER_WAVE];
-        bool have[ROWS_PER_WAVE];
-#pragma unroll
-        for (int u = 0; u < ROWS_PER_WAVE; ++u) {
-            const int c = wave + u * n_waves;
-            have[u] = c < kp && s_best[c] != KEY_PAD;
-            const uint32_t row = have[u] ? (uint32_t)(s_best[c] & 0xFFFFFFFFull) : 0u;
-            bv[u] = reinterpret_cast<const f32x4 *>(p.corpus + (uint64_t)row * 256)[lane];
-        }
-        // (conversions only now: the query and all row loads above are in flight together)
-        const double q0 = qv.x, q1 = qv.y, q2 = qv.z, q3 = qv.w;
-        if (wave == n_waves - 1) {
-            double *dst = s_Q + 4 * lane;
-            dst[0] = q0 * q0; dst[1] = q1 * q1; dst[2] = q2 * q2; dst[3] = q3 * q3;
-            // the query's largest magnitude, for the domain verdict below (domain.hip)
-            atomicMax(&s_cnt[2], max(max(__float_as_uint(qv.x) & 0x7fffffffu, __float_as_uint(qv.y) & 0x7fffffffu),
-                                     max(__float_as_uint(qv.z) & 0x7fffffffu, __float_as_uint(qv.w) & 0x7fffffffu)));
-        }
-#pragma unroll
-        for (int u = 0; u < ROWS_PER_WAVE; ++u) {
-            if (have[u]) {
-                const int c = wave + u * n_waves;
-                const double b0 = bv[u].x, b1 = bv[u].y, b2 = bv[u].z, b3 = bv[u].w;
-                double *dp = s_P + (size_t)c * PROD_STRIDE + 4 * lane;
-                double *db = s_B + (size_t)c * PROD_STRIDE + 4 * lane;
-                dp[0] = q0 * b0; dp[1] = q1 * b1; dp[2] = q2 * b2; dp[3] = q3 * b3;
-                db[0] = b0 * b0; db[1] = b1 * b1; db[2] = b2 * b2; db[3] = b3 * b3;
-            }
-        }
-        __syncthreads();
-        SEL_STAMP(5);
-        // chains: threads [0,kp) sum P, threads [64,64+kp) sum B, thread 128 sums Q
-        const int role = (int)threadIdx.x >> 6, idx = (int)threadIdx.x & 63;
-        const double *src = nullptr;
-        if (role == 0 && idx < kp && s_best[idx] != KEY_PAD) src = s_P + (size_t)idx * PROD_STRIDE;
-        else if (role == 1 && idx < kp && s_best[idx] != KEY_PAD) src = s_B + (size_t)idx * PROD_STRIDE;
-        else if (threadIdx.x == 128) src = s_Q;
-        if (src) {
-            double acc = 0.0;
-#pragma unroll 16
-            for (int i = 0; i < 256; ++i) acc = acc + src[i];
-            if (role == 0) my_ab = acc;
-            else if (role == 1) s_b2[idx] = acc;
-            else *s_a2 = acc;
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < kp) my_b2 = s_b2[threadIdx.x];
-    } else {
-        // large k': stage the candidate rows (one wave per row, 16 B per lane) and the query converted to f64
-        if (threadIdx.x < 256) {
-            const float qf = p.queries[(size_t)qi * 256 + threadIdx.x];
-            s_qd[threadIdx.x] = (double)qf;
-            atomicMax(&s_cnt[2], __float_as_uint(qf) & 0x7fffffffu);
-        }
-        for (int c = wave; c < kp; c += n_waves) {
-            if (s_best[c] != KEY_PAD) {
-                const float *g = p.corpus + (uint64_t)(uint32_t)(s_best[c] & 0xFFFFFFFFull) * 256;
-                s_rows[(size_t)c * ROW_STRIDE_F4 + lane] = reinterpret_cast<const f32x4 *>(g)[lane];
-            }
-        }
-        __syncthreads();
-        SEL_STAMP(5);
-        // thread t < kp walks candidate t's row; thread 128 (another wave) walks the query
-        if (my_key != KEY_PAD) {
-            const f32x4 *r4 = s_rows + (size_t)threadIdx.x * ROW_STRIDE_F4;
-#pragma unroll 8
-            for (int i = 0; i < 64; ++i) {
-                const f32x4 b = r4[i];
-                const double a0 = s_qd[4 * i], a1 = s_qd[4 * i + 1], a2 = s_qd[4 * i + 2], a3 = s_qd[4 * i + 3];
-                const double bx = b.x, by = b.y, bz = b.z, bw = b.w;
-                my_ab = my_ab + a0 * bx; my_b2 = my_b2 + bx * bx;
-                my_ab = my_ab + a1 * by; my_b2 = my_b2 + by * by;
-                my_ab = my_ab + a2 * bz; my_b2 = my_b2 + bz * bz;
-                my_ab = my_ab + a3 * bw; my_b2 = my_b2 + bw * bw;
-            }
-        }
-        if (threadIdx.x == 128) {
-            double a2 = 0.0;
-#pragma unroll 8
-            for (int i = 0; i < 256; ++i) a2 = a2 + s_qd[i] * s_qd[i];
-            *s_a2 = a2;
-        }
-        __syncthreads();
-    }
-    if ((int)threadIdx.x < kp) {
-        double d = __builtin_inf();
-        uint32_t r = 0xFFFFFFFFu;
-        if (my_key != KEY_PAD) {
-            r = (uint32_t)(my_key & 0xFFFFFFFFull);
-            d = cos_finish_exact(my_ab, *s_a2, my_b2);
-            if (p.ws_threshold) {
-                // qdrant score_threshold keeps score > threshold (similarity metrics)
-                if (!((1.0 - d) > (double)p.ws_thr_score)) { d = __builtin_inf(); r = 0xFFFFFFFFu; }
-            }
-        }
-        s_d[threadIdx.x] = d;
-        s_r[threadIdx.x] = r;
-        if (r != 0xFFFFFFFFu) atomicAdd(&s_cnt[1], 1u);
-    }
-    uint64_t *orow = p.out_rows + (size_t)qi * p.out_stride;
-    double *odist = p.out_dist + (size_t)qi * p.out_stride;
-    if (threadIdx.x < p.k_out) { orow[threadIdx.x] = 0xFFFFFFFFFFFFFFFFull; odist[threadIdx.x] = __builtin_inf(); }
-    if (threadIdx.x == 0 && p.out_uncertain) p.out_uncertain[qi] = 0;
-    if (threadIdx.x == 0 && p.out_status) p.out_status[qi] = 0;
-    __syncthreads();
-    SEL_STAMP(6);
-    for (int pr = threadIdx.x; pr < kp * kp; pr += blockDim.x) {
-        const int i = pr / kp, j = pr - i * kp;
-        const uint32_t ri = s_r[i], rj = s_r[j];
-        if (ri != 0xFFFFFFFFu && rj != 0xFFFFFFFFu) {
-            const double di = s_d[i], dj = s_d[j];
-            if (dj < di || (dj == di && rj < ri)) atomicAdd(&s_rank[i], 1u);
-        }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < kp && s_r[threadIdx.x] != 0xFFFFFFFFu) {
-        const unsigned rank = s_rank[threadIdx.x];
-        if (rank < p.k_out) { orow[rank] = p.row_base + s_r[threadIdx.x]; odist[rank] = s_d[threadIdx.x]; }
-    }
-    if (!magnitude_in_domain(s_cnt[2])) {
-        // The query is outside the library's domain (a non-finite component, or a magnitude the f32 nominating kernels do not answer
-        // for: domain.hip).  The host entry points refuse such queries before anything is launched; a device entry point says so
-        // here -- SMT_STATUS_INVALID_QUERY: the list means nothing.
-        if (threadIdx.x == 0) {
-            if (p.out_uncertain) p.out_uncertain[qi] = 3;
-            if (p.out_status) p.out_status[qi] = 3u;
-            if (p.status) atomicAdd(p.status, 1ull);
-        }
-    } else if (p.f32_err > 0.0 && s_best[kp - 1] != KEY_PAD) {
-        // Exactness certificate (SelectArgs::f32_err).  kp rows were nominated, so rows outside the lists may
-        // exist; each of them has f32 distance >= tau32, hence exact distance >= tau32 - f32_err.  Exactly one
-        // thread decides: the owner of the k_out-th result, or thread 0 when fewer than k_out rows qualified
-        // (only possible with the workspace score threshold, which then bounds what an outside row would need).
-        const double floor_out = (double)__uint_as_float((unsigned)(s_best[kp - 1] >> 32)) - p.f32_err;
-        bool decide = false, uncertain = false;
-        if ((int)threadIdx.x < kp && s_r[threadIdx.x] != 0xFFFFFFFFu && s_rank[threadIdx.x] == p.k_out - 1) {
-            decide = true;
-            uncertain = !(floor_out > s_d[threadIdx.x]);
-        } else if (threadIdx.x == 0 && s_cnt[1] < p.k_out) {
-            decide = true;
-            uncertain = p.ws_threshold ? ((1.0 - floor_out) > (double)p.ws_thr_score) : true;
-        }
-        unsigned int code = uncertain ? 1u : 0u;   // SMT_STATUS_UNCERTAIN
-        if constexpr (OVF) {
-            if (decide && p.overflow[qi]) { uncertain = true; code = 2u; }   // rows were dropped on the way (SelectArgs::overflow): SMT_STATUS_OVERFLOW
-        }
-        if (decide && uncertain) {
-            if (p.out_uncertain) p.out_uncertain[qi] = code;
-            if (p.out_status) p.out_status[qi] = code;
-            if (p.status) atomicAdd(p.status, 1ull);
-        }
-    } else if constexpr (OVF) {
-        if (threadIdx.x == 0 && p.overflow[qi]) {
-            if (p.out_uncertain) p.out_uncertain[qi] = 2;
-            if (p.out_status) p.out_status[qi] = 2u;
-            if (p.status) atomicAdd(p.status, 1ull);
-        }
-    }
-    if (threadIdx.x == 0 && p.out_counts)
-        p.out_counts[qi] = s_cnt[1] < p.k_out ? s_cnt[1] : p.k_out;
-    if (p.flags) {
-        __syncthreads();
-        if (threadIdx.x == 0 && blockIdx.x == 0)  // async mode: one query per launch
-            __hip_atomic_store(p.flags + 1, p.step, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (p.host_flag) {
-        // Delivery (common.h): count this block as finished -- thread 0's agent-scope release covers the block's output stores, ordered
-        // before it by the barrier, the same hand-over the scan kernel uses for its lists -- and let the LAST block carry every query's
-        // answer home: ONE wave copies the device block to pinned host memory and raises the completion word behind it (its own
-        // stores, one system-scope release; a fence in each of the 16 waves would be 16 write-backs of the L2).
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned long long prev = __hip_atomic_fetch_add(p.done, 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            s_cnt[3] = prev == (unsigned long long)gridDim.x - 1ull ? 1u : 0u;
-        }
-        __syncthreads();
-        if (s_cnt[3] && threadIdx.x < 64) {
-            for (uint32_t i = threadIdx.x; i < p.out_words; i += 64)
-                p.host_out[i] = __hip_atomic_load(p.dev_out + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(p.done, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // system scope: the copy is out before the flag
-            if (threadIdx.x == 0) __hip_atomic_store(p.host_flag, p.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-    SEL_STAMP(7);
-}
-
-template <int KREG, bool OVF = false>
-__global__ void __launch_bounds__(SEL_THREADS) final_select_kernel(FinalParams p)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    final_select_body<KREG, OVF>(p, blockIdx.x, smem_raw);
-}
-
-static size_t final_smem_bytes(uint32_t n_lists, uint32_t kp)
-{
-    (void)n_lists;
-    const size_t kp2 = (kp + 1) & ~1u;
-    const size_t small = (size_t)(96 + 80) * 4 + 256 * 8 + kp2 * 8 * 3 + (size_t)((kp + 3) & ~3u) * 4 + 8 + 8 + 16;
-    const size_t big_select = (size_t)(kp + 1) * ROW_STRIDE_F4 * 16 + (size_t)SEL_SURV_CAP * 8 + (size_t)SEL_MAX_COLS * SEL_MAX_LISTS * 8;
-    const size_t big_rescore = kp <= (uint32_t)SEL_FAST_KP ? ((size_t)2 * kp * PROD_STRIDE + 256) * 8 : 0;
-    return small + std::max(big_select, big_rescore) + 64;
-}
-
-// ------------------------------------------------- cross-shard top-k merge
-// Entry (list l, query qi, slot i): rows[l*list_stride + qi*query_stride + i], same for dist.
-// Plain layout [n_lists][nq][k_in]: list_stride = nq*k_in, query_stride = k_in.  Packed layout
-// [n_lists][nq][2][k_in] (rows then distance bits, one all-gather instead of two):
-// list_stride = nq*2*k_in, query_stride = 2*k_in, dist = rows + k_in.  One block per query.
-__global__ void merge_topk_kernel(const uint64_t *rows, const double *dist, uint32_t n_lists, uint64_t list_stride,
-                                  uint64_t query_stride, uint32_t k_in, uint32_t k_out, uint64_t *out_rows,
-                                  double *out_dist, uint64_t out_query_stride)
-{
-    const uint32_t qi = blockIdx.x;
-    const uint32_t M = n_lists * k_in;
-    uint64_t *orow = out_rows + (size_t)qi * out_query_stride;
-    double *odist = out_dist + (size_t)qi * out_query_stride;
-    for (uint32_t t = threadIdx.x; t < k_out; t += blockDim.x) {
-        orow[t] = 0xFFFFFFFFFFFFFFFFull;
-        odist[t] = __builtin_inf();
-    }
-    __syncthreads();
-    for (uint32_t e = threadIdx.x; e < M; e += blockDim.x) {
-        const size_t idx = (size_t)(e / k_in) * list_stride + (size_t)qi * query_stride + (e % k_in);
-        const uint64_t r = rows[idx];
-        if (r == 0xFFFFFFFFFFFFFFFFull) continue;
-        const double d = dist[idx];
-        uint32_t rank = 0;
-        for (uint32_t f = 0; f < M; ++f) {
-            const size_t jdx = (size_t)(f / k_in) * list_stride + (size_t)qi * query_stride + (f % k_in);
-            const uint64_t rf = rows[jdx];
-            if (rf == 0xFFFFFFFFFFFFFFFFull) continue;
-            const double df = dist[jdx];
-            if (df < d || (df == d && rf < r)) ++rank;
-        }
-        if (rank < k_out) { orow[rank] = r; odist[rank] = d; }
-    }
-}
-
-// The same merge over lists that are NOT gathered: list l starts at src.list[l] -- for a one-process group the exchange buffer of
-// rank l, read IN PLACE over xGMI (peer access) or on this device (logical ranks).  Nothing is copied between the ranks: the
-// exchange is this kernel's loads (n_lists x k_in x 16 B per query -- 1280 B at 8 ranks, k = 10: latency-bound), ordered
-// after the ranks' select kernels by one stream event per rank (group_exchange.cpp: peer transport).  The candidates are staged in LDS once
-// (16 B each, M <= 4096) so that the M x M rank computation never goes back over the links.
-__global__ void merge_topk_sources_kernel(MergeSources src, uint32_t n_lists, uint64_t query_stride, uint32_t k_in, uint32_t k_out,
-                                          uint64_t *out_rows, double *out_dist, uint64_t out_query_stride)
-{
-    extern __shared__ unsigned char smem_raw[];
-    uint64_t *s_row = reinterpret_cast<uint64_t *>(smem_raw);
-    const uint32_t qi = blockIdx.x;
-    const uint32_t M = n_lists * k_in;
-    double *s_dist = reinterpret_cast<double *>(s_row + M);
-    uint64_t *orow = out_rows + (size_t)qi * out_query_stride;
-    double *odist = out_dist + (size_t)qi * out_query_stride;
-    for (uint32_t t = threadIdx.x; t < k_out; t += blockDim.x) {
-        orow[t] = 0xFFFFFFFFFFFFFFFFull;
-        odist[t] = __builtin_inf();
-    }
-    for (uint32_t e = threadIdx.x; e < M; e += blockDim.x) {
-        const uint64_t *l = src.list[e / k_in] + (size_t)qi * query_stride;
-        const uint32_t i = e % k_in;
-        s_row[e] = l[i];
-        s_dist[e] = reinterpret_cast<const double *>(l + k_in)[i];
-    }
-    __syncthreads();
-    for (uint32_t e = threadIdx.x; e < M; e += blockDim.x) {
-        const uint64_t r = s_row[e];
-        if (r == 0xFFFFFFFFFFFFFFFFull) continue;
-        const double d = s_dist[e];
-        uint32_t rank = 0;
-        for (uint32_t f = 0; f < M; ++f) {
-            const uint64_t rf = s_row[f];
-            if (rf == 0xFFFFFFFFFFFFFFFFull) continue;
-            const double df = s_dist[f];
-            if (df < d || (df == d && rf < r)) ++rank;
-        }
-        if (rank < k_out) { orow[rank] = r; odist[rank] = d; }
-    }
 }
 
 // ------------------------------------------------------------------ launchers
@@ -1550,34 +809,192 @@ static inline uint32_t candidates_per_list(const smt_ctx *ctx, uint32_t k_out)
     return std::min<uint32_t>(64, k_out + (uint32_t)ctx->tune.guard_band);
 }
 
-template <int NQ, int U>
-static int launch_scan_variant(smt_ctx *ctx, const ScanParams &p, int blocks, int threads, bool nt, hipStream_t st)
+// What the launches of one call have in common: plan_scan decides before anything is enqueued, the next two steps fill in the rest.
+struct ScanPlan {
+    bool filtered, nt;
+    int blocks, threads, U;   // grid, block, rows per chunk
+    uint32_t kp;              // candidates kept per list
+    uint64_t n_chunks;
+    bool async, overlap;      // the pipeline: async select (one query per call), and of those the two-stream overlap
+    bool pair;                // scan_pair: one-query launches may share a corpus pass
+    // enter_pipeline
+    uint64_t step = 0;        // of the pipeline (0: synchronous)
+    key_t64 *lists = nullptr; // this step's list set, and behind the sets the chunk table of a filtered call
+    uint64_t *table = nullptr;
+    // overlap_prologue
+    hipStream_t st = nullptr;
+    unsigned long long gate_open = 0, gate_ticks = 0;
+    bool may_pair = false;    // scan_pair: this launch runs scan_pair_kernel (it looks for a partner, and may find itself absorbed)
+    unsigned int absorbable = 0;
+};
+
+static ScanPlan plan_scan(const smt_ctx *ctx, const ScanArgs &a)
 {
-    const size_t smem = (size_t)NQ * (threads / 64) * 64 * sizeof(key_t64) + 16 + 64 + 256;  // per-query, per-wave key slots (the chunk counter and the STEAL ring live in the second query's until the merge) + the waves' key counts
-    dim3 g(blocks), b(threads);
-    if constexpr (U == 4) {
-        if (p.steal_ctr) {   // groups of rounds dealt while the kernel runs (512-thread blocks, checked by the caller)
-            if (nt) hipLaunchKernelGGL((scan_topk_kernel<NQ, U, true, false, true>), g, b, smem, st, p);
-            else hipLaunchKernelGGL((scan_topk_kernel<NQ, U, false, false, true>), g, b, smem, st, p);
-            SMT_HIP_CHECK(hipGetLastError());
-            return SMT_OK;
-        }
+    ScanPlan pl;
+    pl.filtered = a.n_ranges > 0;
+    pl.nt = ctx->tune.scan_nontemporal != 0;
+    pl.kp = candidates_per_list(ctx, a.k_out);
+    pl.blocks = ctx->tune.scan_blocks > 0 ? ctx->tune.scan_blocks : ctx->num_cus;
+    if (pl.blocks > SEL_MAX_LISTS) pl.blocks = SEL_MAX_LISTS;
+    pl.threads = ctx->tune.scan_threads;
+    pl.U = pl.filtered ? FILTER_CHUNK : ctx->tune.scan_unroll;
+    pl.n_chunks = pl.filtered ? a.n_chunks : (a.n_virtual + (uint64_t)pl.U - 1) / (uint64_t)pl.U;
+    const uint64_t waves_per_block = (uint64_t)(pl.threads / 64);
+    if ((uint64_t)pl.blocks * waves_per_block > pl.n_chunks) {  // tiny inputs: do not launch idle blocks
+        const uint64_t need = (pl.n_chunks + waves_per_block - 1) / waves_per_block;
+        pl.blocks = (int)(need > 0 ? need : 1);
     }
-    if (nt) hipLaunchKernelGGL((scan_topk_kernel<NQ, U, true, false>), g, b, smem, st, p);
-    else hipLaunchKernelGGL((scan_topk_kernel<NQ, U, false, false>), g, b, smem, st, p);
-    SMT_HIP_CHECK(hipGetLastError());
+    // async select (one query per call): two list buffers alternate, the select of step i reads buffer i&1 on
+    // the aux stream while the scan of step i+1 fills the other one
+    pl.async = a.allow_async && ctx->tune.async_select && a.nq == 1;
+    // scan_overlap: scan AND select of step i on scan stream i&1, behind an event on the main stream (the caller's inputs).  List
+    // buffer b belongs to stream b, so stream order protects it and no flag is needed; the two streams let scan i+1 start while
+    // scan i drains, paced by the start gate (ScanParams::gate).  (Not with STEAL: its counter ring is reset in stream order.)
+    pl.overlap = pl.async && a.allow_overlap && ctx->tune.scan_overlap && !pl.filtered && ctx->tune.scan_steal == 0;
+    // scan_pair: the launch may share its corpus pass with the call two steps later, or be absorbed by the one two steps earlier
+    // (scan_pair_kernel).  Not with wave stamps (profiling of the plain kernel).
+    pl.pair = pl.overlap && ctx->tune.scan_pair && pl.U == 4 && ctx->tune.scan_debug_ptr == 0;
+    pl.st = ctx->stream;
+    return pl;
+}
+
+// Leaves the other pipeline if the last call ran it, makes this one's, takes the step number and carves up the scratch buffer.
+static int enter_pipeline(smt_ctx *ctx, const ScanArgs &a, ScanPlan &pl)
+{
+    int rc = SMT_OK;
+    if (pl.async && ctx->async_overlap != pl.overlap && (rc = drain_async(ctx))) return rc;   // the two pipelines share the list buffers
+    if (pl.async && (rc = pl.overlap ? ensure_overlap(ctx) : ensure_async(ctx))) return rc;
+    if (!pl.async && (rc = drain_async(ctx))) return rc;
+    pl.step = pl.overlap ? ++ctx->ov_step : pl.async ? ++ctx->async_step : 0;
+    // (scan_overlap: scans of consecutive calls run at the same time, and their grids differ with the corpus -- the two buffers get a
+    // fixed place, the largest one-query list set, or a small call's buffer 1 would lie inside a large call's buffer 0)
+    const size_t list_bytes = pl.overlap ? (size_t)SEL_MAX_LISTS * 64 * sizeof(key_t64)
+                                         : (((size_t)a.nq * pl.blocks * pl.kp * sizeof(key_t64)) + 255) & ~(size_t)255;
+    const size_t table_bytes = pl.filtered ? (size_t)pl.n_chunks * sizeof(uint64_t) : 0;
+    // (scan_overlap: a ring of eight sets, step & 7.  A leading scan of step i fills the sets of steps i, i + 2, i + 4 and i + 6, all
+    // on its own stream, and set s is shared by the steps s, s +- 8, s +- 16 ...: the last readers of the four sets it writes are the
+    // selects of steps i - 8, i - 6, i - 4 and i - 2, launched on the SAME stream before scan i, so stream order alone has them
+    // finished.  The other stream's steps have the other parity and the other four sets.  With fewer sets the scan of step i
+    // would write the set of step i + 6 into one that a select of the other stream, ordered against nothing here, may be reading.)
+    const size_t n_sets = pl.overlap ? 8 : 2;
+    if ((rc = ensure_scratch(ctx, n_sets * list_bytes + table_bytes))) return rc;
+    pl.lists = reinterpret_cast<key_t64 *>(reinterpret_cast<char *>(ctx->d_scratch) + (pl.step & (n_sets - 1)) * list_bytes);
+    pl.table = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(ctx->d_scratch) + n_sets * list_bytes);
+    return pl.pair ? ensure_pair(ctx) : SMT_OK;
+}
+
+// scan_overlap: the step's stream goes behind the caller's; timed-launch bracketing, may_pair / absorbable, the start gate.
+static int overlap_prologue(smt_ctx *ctx, ScanPlan &pl)
+{
+    const uint64_t step = pl.step;
+    hipStream_t st = pl.st = ctx->ov_stream[step & 1];
+    // a predecessor that takes this call's query along reads it without waiting for ov_ready: only a query that no work queued on
+    // the caller's stream can still be writing may be taken
+    // ... and only a launch that queues up behind a predecessor on its stream can be absorbed by it, or has reason to look for a
+    // partner itself (a call made while the GPU is idle must cost what it did: no look, no wait; scan_pair_wait_us: tests)
+    if (pl.pair) {
+        const bool behind = ctx->tune.scan_pair_wait_us > 0 || hipStreamQuery(st) != hipSuccess;
+        const bool idle = behind && hipStreamQuery(ctx->stream) == hipSuccess;
+        (void)hipGetLastError();   // (hipErrorNotReady is an answer here)
+        pl.absorbable = idle ? 1u : 0u;
+        pl.may_pair = behind;
+    }
+    SMT_HIP_CHECK(hipEventRecord(ctx->ov_ready[step & 1], ctx->stream));
+    SMT_HIP_CHECK(hipStreamWaitEvent(st, ctx->ov_ready[step & 1], 0));
+    // a timed launch waits for its predecessor (and that one's select), and the launch after it waits for it: the events bracket a
+    // kernel that has the part to itself, not a gate or an HBM shared with a neighbour
+    const bool timed = prof_arms_next(ctx, "scan");
+    if (timed || ctx->ov_after_timed) {
+        SMT_HIP_CHECK(hipEventRecord(ctx->ov_done, ctx->ov_stream[(step & 1) ^ 1]));
+        SMT_HIP_CHECK(hipStreamWaitEvent(st, ctx->ov_done, 0));
+        // (a timed launch and its successor neither absorb nor get absorbed: the events keep bracketing a one-query pass)
+        pl.may_pair = false;
+        pl.absorbable = 0;
+    }
+    ctx->ov_after_timed = timed;
+    // What the gate counts is CALLS served, in blocks: a plain launch's block adds 1 when its rows are done, a leader's block the
+    // number of calls its pass serves, an absorbed launch nothing, and gate_total (launch_scan_topk, behind the passes) counts one grid per call.  So "gate_pct of
+    // the predecessor" is: every call before the predecessor call is served, and gate_pct per cent of the predecessor call's
+    // grid.  When that call is the m-th of n that one pass serves, the point lies at (m - 1 + gate_pct / 100) / n of the pass'
+    // blocks: 75 % of a pair's pass and 87.5 % of a full group's at gate_pct = 50, while a leader still at its gate holds
+    // successors back only until their bound.  The default by the sweeps: 50 for every mode.  (While the grouped
+    // pass ran one tree per query, launches that take two or three calls along ran 4 us per step faster with no gate: two leaders
+    // on a CU filled each other's stalls.  With the group reducer every gate from 5 to 100 measures 48.0 us per step and no gate
+    // 50.1 with a spread of 3 us, profiles/scan_group_loop.json.)
+    const int gate_pct = ctx->tune.scan_gate_pct >= 0 ? ctx->tune.scan_gate_pct : 50;
+    if (gate_pct > 0 && ctx->gate_prev_blocks > 0) {
+        pl.gate_open = ctx->gate_total - ctx->gate_prev_blocks + (ctx->gate_prev_blocks * (uint64_t)gate_pct + 99) / 100;
+        // the bound: the predecessor's rows at 4 TB/s (half the part's HBM rate; 1 KiB rows, 10 ns ticks) + 20 us, at most 0.5 ms (a
+        // grid that cannot be resident twice -- scan_blocks / scan_threads -- may hold back predecessor blocks while it waits)
+        pl.gate_ticks = std::min<uint64_t>(ctx->gate_prev_rows / 39 + 2000, 50000);
+    }
     return SMT_OK;
 }
 
-template <int NQ>
-static int launch_scan_filtered(smt_ctx *ctx, const ScanParams &p, int blocks, int threads, bool nt)
+// The parameters of the pass over the queries q0 .. q0 + nq_active - 1 (STEAL: see steal_setup).
+static ScanParams scan_params(const smt_ctx *ctx, const ScanArgs &a, const ScanPlan &pl, const uint64_t *chunk_table, uint32_t q0,
+                              uint32_t nq_active)
 {
-    const size_t smem = (size_t)NQ * (threads / 64) * 64 * sizeof(key_t64) + 16 + 64 + 256;
-    dim3 g(blocks), b(threads);
-    if (nt) hipLaunchKernelGGL((scan_topk_kernel<NQ, FILTER_CHUNK, true, true>), g, b, smem, ctx->stream, p);
-    else hipLaunchKernelGGL((scan_topk_kernel<NQ, FILTER_CHUNK, false, true>), g, b, smem, ctx->stream, p);
-    SMT_HIP_CHECK(hipGetLastError());
+    ScanParams p{};
+    p.corpus = a.corpus;
+    p.queries = a.queries + (size_t)q0 * 256;
+    p.n_virtual = a.n_virtual;
+    p.chunk_table = pl.filtered ? chunk_table : nullptr;
+    p.n_chunks = pl.n_chunks;
+    p.kp = pl.kp;
+    p.nq_active = nq_active;
+    p.block_lists = pl.lists + (size_t)q0 * pl.blocks * pl.kp;
+    p.stamps = reinterpret_cast<unsigned long long *>(ctx->tune.scan_debug_ptr);
+    p.flags = pl.async && !pl.overlap ? ctx->d_flags : nullptr;
+    p.step = pl.step;
+    p.gate = pl.overlap ? ctx->d_gate : nullptr;
+    p.gate_open = pl.gate_open;
+    p.gate_ticks = pl.gate_ticks;
+    return p;
+}
+
+// Dynamic groups (scan_topk_kernel STEAL; tuning key scan_steal = rounds per group, 0 = the static deal): unfiltered scans of
+// 8-wave blocks over enough rows that every block gets well past its static groups.  Each launch has its own counter: a ring
+// of 64, zeroed together every 64th launch (one 256-byte memset in stream order).
+static int steal_setup(smt_ctx *ctx, const ScanPlan &pl, ScanParams &p)
+{
+    if (pl.filtered || pl.U != 4 || pl.threads != 512 || ctx->tune.scan_steal <= 0 ||
+        pl.n_chunks < (uint64_t)pl.blocks * 8u * (uint64_t)ctx->tune.scan_steal * 8u)
+        return SMT_OK;
+    if (!ctx->d_steal) SMT_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&ctx->d_steal), 64 * sizeof(unsigned int)));
+    if (ctx->steal_seq % 64 == 0) SMT_HIP_CHECK(hipMemsetAsync(ctx->d_steal, 0, 64 * sizeof(unsigned int), ctx->stream));
+    p.steal_ctr = ctx->d_steal + (ctx->steal_seq % 64);
+    ++ctx->steal_seq;
+    uint32_t lr = 0;
+    while ((2 << lr) <= ctx->tune.scan_steal) ++lr;
+    p.steal_lr = lr;
+    // the dynamic share: scan_steal_pct per cent of the groups (at least STEAL_DEPTH + 1 per block stay static)
+    const uint64_t n_groups = (pl.n_chunks + (8ull << lr) - 1) / (8ull << lr);
+    const uint64_t per_block = n_groups / (uint64_t)pl.blocks;
+    const uint64_t n_static = per_block * (uint64_t)(100 - ctx->tune.scan_steal_pct) / 100;
+    p.steal_static = (uint32_t)std::max<uint64_t>(n_static, 3);
     return SMT_OK;
+}
+
+using scan_kernel_t = void (*)(ScanParams);
+template <int NQ, int U>
+static scan_kernel_t scan_kernel_of(bool nt, bool filtered, bool steal)
+{
+    if constexpr (U == FILTER_CHUNK) {   // (the chunk table's chunk, and the STEAL deal's, is four rows)
+        if (filtered) return nt ? scan_topk_kernel<NQ, U, true, true> : scan_topk_kernel<NQ, U, false, true>;
+        if (steal) return nt ? scan_topk_kernel<NQ, U, true, false, true> : scan_topk_kernel<NQ, U, false, false, true>;
+    }
+    return nt ? scan_topk_kernel<NQ, U, true, false> : scan_topk_kernel<NQ, U, false, false>;
+}
+
+// The instantiation for a pass of `slots` query slots (1, 2, 4) over chunks of U rows (a filtered scan: FILTER_CHUNK).
+static scan_kernel_t scan_kernel_for(int slots, int U, bool nt, bool filtered, bool steal)
+{
+    if (slots > 1 && U == 2) U = 8;   // two and four queries are built for 4 and 8 rows per chunk: scan_unroll = 2 runs them at 8
+    if (slots == 1) return U == 2 ? scan_kernel_of<1, 2>(nt, filtered, steal) : U == 4 ? scan_kernel_of<1, 4>(nt, filtered, steal)
+                                                                                      : scan_kernel_of<1, 8>(nt, filtered, steal);
+    if (slots == 2) return U == 4 ? scan_kernel_of<2, 4>(nt, filtered, steal) : scan_kernel_of<2, 8>(nt, filtered, steal);
+    return U == 4 ? scan_kernel_of<4, 4>(nt, filtered, steal) : scan_kernel_of<4, 8>(nt, filtered, steal);
 }
 
 int ensure_pair(smt_ctx *ctx)
@@ -1591,8 +1008,10 @@ int ensure_pair(smt_ctx *ctx)
 }
 
 // Publishes this step's slot (what a predecessor needs to take the call along), then launches the pair-capable one-query scan.
-static int launch_scan_pair(smt_ctx *ctx, const ScanParams &p, PairParams pp, int blocks, int threads, bool nt, hipStream_t st)
+static int launch_scan_pair(smt_ctx *ctx, const ScanParams &p, const ScanPlan &pl)
 {
+    PairParams pp{};
+    pp.absorbable = pl.absorbable;
     pp.ring_mask = (unsigned long long)std::min(ctx->tune.scan_pair_ring, PAIR_RING) - 1;
     PairSlot *slot = reinterpret_cast<PairSlot *>(ctx->h_pair_ring) + (p.step & pp.ring_mask);
     __atomic_store_n(&slot->step, 0ull, __ATOMIC_SEQ_CST);   // (a reader of the slot's previous use fails its second check)
@@ -1600,7 +1019,7 @@ static int launch_scan_pair(smt_ctx *ctx, const ScanParams &p, PairParams pp, in
     slot->n_virtual = p.n_virtual;
     slot->query = (unsigned long long)(uintptr_t)p.queries;
     slot->lists = (unsigned long long)(uintptr_t)p.block_lists;
-    slot->kp_blocks = (unsigned long long)p.kp | (unsigned long long)blocks << 32;
+    slot->kp_blocks = (unsigned long long)p.kp | (unsigned long long)pl.blocks << 32;
     slot->absorbable = pp.absorbable;
     __atomic_store_n(&slot->step, p.step, __ATOMIC_RELEASE);
     pp.ring = reinterpret_cast<const PairSlot *>(ctx->h_pair_ring);
@@ -1608,259 +1027,39 @@ static int launch_scan_pair(smt_ctx *ctx, const ScanParams &p, PairParams pp, in
     pp.ctl = ctx->d_gate + 1;
     pp.wait_ticks = (unsigned long long)ctx->tune.scan_pair_wait_us * 100ull;
     pp.max_take = (unsigned int)std::min(std::max(ctx->tune.scan_pair, 1), GROUP_MAX - 1);
-    const size_t smem = pair_smem_bytes(threads);
-    if (nt) hipLaunchKernelGGL(scan_pair_kernel<true>, dim3(blocks), dim3(threads), smem, st, p, pp);
-    else hipLaunchKernelGGL(scan_pair_kernel<false>, dim3(blocks), dim3(threads), smem, st, p, pp);
+    hipLaunchKernelGGL(pl.nt ? scan_pair_kernel<true> : scan_pair_kernel<false>, dim3(pl.blocks), dim3(pl.threads),
+                       pair_smem_bytes(pl.threads), pl.st, p, pp);
     SMT_HIP_CHECK(hipGetLastError());
     ctx->pair_live = true;
     return SMT_OK;
 }
 
-// Block lists -> final answer in ONE launch (per query: prune + rank + rescore).
-int launch_select(smt_ctx *ctx, const SelectArgs &a)
+// One pass: `slots` query slots, of which p.nq_active hold a query.  THE launch site of scan_topk_kernel.
+static int launch_scan_pass(smt_ctx *ctx, const ScanPlan &pl, const ScanParams &p, int slots)
 {
-    SMT_REQUIRE(a.n_lists >= 1 && a.n_lists <= (uint32_t)SEL_MAX_LISTS, "select stage accepts 1..512 block lists");
-    SMT_REQUIRE(a.async_step == 0 || (a.nq == 1 && ctx->aux_stream && ctx->d_flags), "async select handles one query per launch");
-    if (!(ctx->attr_done & ATTR_SELECT)) {  // per context == per device (a group runs several GPUs in one process)
-        SMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(final_select_kernel<8>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        SMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(final_select_kernel<36>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        SMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(final_select_kernel<8, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        SMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(final_select_kernel<36, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ctx->attr_done |= ATTR_SELECT;
+    if (slots == 1 && pl.pair) {
+        if (pl.may_pair) return launch_scan_pair(ctx, p, pl);
+        ++ctx->pair_alone_host;
     }
-    FinalParams f;
-    f.corpus = a.corpus;
-    f.queries = a.queries;
-    f.lists = a.lists;
-    f.list_stride = a.list_stride;
-    f.n_lists = a.n_lists;
-    f.kp = a.kp;
-    f.k_out = a.k_out;
-    f.ws_threshold = a.ws_threshold;
-    f.ws_thr_score = a.ws_thr_score;
-    f.row_base = a.row_base;
-    f.out_rows = a.out_rows;
-    f.out_dist = a.out_dist;
-    f.out_counts = a.out_counts;
-    f.out_stride = a.out_stride ? a.out_stride : a.k_out;
-    f.f32_err = a.f32_err;
-    f.out_uncertain = a.out_uncertain;
-    f.out_status = a.out_status;
-    f.status = ctx->d_status;
-    f.dbg = reinterpret_cast<unsigned long long *>(ctx->tune.select_debug_ptr);
-    f.flags = a.async_step ? ctx->d_flags : nullptr;
-    f.step = a.async_step;
-    f.overflow = a.overflow;
-    const Delivery *dl = a.async_step ? nullptr : a.deliver;
-    f.dev_out = dl ? dl->dev_out : nullptr;
-    f.host_out = dl ? dl->host_out : nullptr;
-    f.host_flag = dl ? dl->host_flag : nullptr;
-    f.done = dl ? dl->done : nullptr;
-    f.seq = dl ? dl->seq : 0;
-    f.out_words = dl ? dl->n_words : 0;
-    const bool small = (uint64_t)a.n_lists * a.kp <= (uint64_t)8 * SEL_THREADS;
-    const size_t smem = final_smem_bytes(a.n_lists, a.kp);
-    if (a.async_step) {
-        if (small) hipLaunchKernelGGL(final_select_kernel<8>, dim3(a.nq), dim3(SEL_THREADS), smem, ctx->aux_stream, f);
-        else hipLaunchKernelGGL(final_select_kernel<36>, dim3(a.nq), dim3(SEL_THREADS), smem, ctx->aux_stream, f);
-        ctx->async_pending = true;
-        SMT_HIP_CHECK(hipGetLastError());
-        return SMT_OK;
-    }
-    hipStream_t st = a.stream ? a.stream : ctx->stream;
-    if (ctx->tune.prof_select) prof_begin_on(ctx, "select", st);
-    if (a.overflow) {
-        if (small) hipLaunchKernelGGL((final_select_kernel<8, true>), dim3(a.nq), dim3(SEL_THREADS), smem, st, f);
-        else hipLaunchKernelGGL((final_select_kernel<36, true>), dim3(a.nq), dim3(SEL_THREADS), smem, st, f);
-    } else {
-        if (small) hipLaunchKernelGGL(final_select_kernel<8>, dim3(a.nq), dim3(SEL_THREADS), smem, st, f);
-        else hipLaunchKernelGGL(final_select_kernel<36>, dim3(a.nq), dim3(SEL_THREADS), smem, st, f);
-    }
-    if (ctx->tune.prof_select) prof_end_on(ctx, "select", st);
+    // per-query, per-wave key slots (the chunk counter and the STEAL ring live in the second query's until the merge) + the waves' key counts
+    const size_t smem = (size_t)slots * (pl.threads / 64) * 64 * sizeof(key_t64) + 16 + 64 + 256;
+    // (STEAL: groups of rounds dealt while the kernel runs -- 512-thread blocks, four rows per chunk: steal_setup)
+    hipLaunchKernelGGL(scan_kernel_for(slots, pl.U, pl.nt, pl.filtered, p.steal_ctr != nullptr), dim3(pl.blocks), dim3(pl.threads), smem,
+                       pl.st, p);
     SMT_HIP_CHECK(hipGetLastError());
     return SMT_OK;
 }
 
-int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
+static SelectArgs select_args(const ScanArgs &a, const ScanPlan &pl)
 {
-    SMT_REQUIRE(a.k_out >= 1 && a.k_out <= SCAN_MAX_K, "top_k for the scan path must be in [1, 56]");
-    SMT_REQUIRE(a.rows < 0xFFFFFFFFull, "a shard holds fewer than 2^32-1 rows");
-    const bool filtered = a.n_ranges > 0;
-    const uint32_t kp = candidates_per_list(ctx, a.k_out);
-    int blocks = ctx->tune.scan_blocks > 0 ? ctx->tune.scan_blocks : ctx->num_cus;
-    if (blocks > SEL_MAX_LISTS) blocks = SEL_MAX_LISTS;
-    const int threads = ctx->tune.scan_threads;
-    const int U = filtered ? FILTER_CHUNK : ctx->tune.scan_unroll;
-    const uint64_t n_chunks = filtered ? a.n_chunks : (a.n_virtual + (uint64_t)U - 1) / (uint64_t)U;
-    const uint64_t waves_per_block = (uint64_t)(threads / 64);
-    if ((uint64_t)blocks * waves_per_block > n_chunks) {  // tiny inputs: do not launch idle blocks
-        const uint64_t need = (n_chunks + waves_per_block - 1) / waves_per_block;
-        blocks = (int)(need > 0 ? need : 1);
-    }
-    // async select (one query per call): two list buffers alternate, the select of step i reads buffer i&1 on
-    // the aux stream while the scan of step i+1 fills the other one
-    const bool async = a.allow_async && ctx->tune.async_select && a.nq == 1;
-    // scan_overlap: scan AND select of step i on scan stream i&1, behind an event on the main stream (the caller's inputs).  List
-    // buffer b belongs to stream b, so stream order protects it and no flag is needed; the two streams let scan i+1 start while
-    // scan i drains, paced by the start gate (ScanParams::gate).  (Not with STEAL: its counter ring is reset in stream order.)
-    const bool overlap = async && a.allow_overlap && ctx->tune.scan_overlap && !filtered && ctx->tune.scan_steal == 0;
-    int rc = SMT_OK;
-    if (async && ctx->async_overlap != overlap && (rc = drain_async(ctx))) return rc;   // the two pipelines share the list buffers
-    if (async && (rc = overlap ? ensure_overlap(ctx) : ensure_async(ctx))) return rc;
-    if (!async && (rc = drain_async(ctx))) return rc;
-    const uint64_t step = overlap ? ++ctx->ov_step : async ? ++ctx->async_step : 0;
-    // (scan_overlap: scans of consecutive calls run at the same time, and their grids differ with the corpus -- the two buffers get a
-    // fixed place, the largest one-query list set, or a small call's buffer 1 would lie inside a large call's buffer 0)
-    const size_t list_bytes = overlap ? (size_t)SEL_MAX_LISTS * 64 * sizeof(key_t64)
-                                      : (((size_t)a.nq * blocks * kp * sizeof(key_t64)) + 255) & ~(size_t)255;
-    const size_t table_bytes = filtered ? (size_t)n_chunks * sizeof(uint64_t) : 0;
-    // (scan_overlap: a ring of eight sets, step & 7.  A leading scan of step i fills the sets of steps i, i + 2, i + 4 and i + 6, all
-    // on its own stream, and set s is shared by the steps s, s +- 8, s +- 16 ...: the last readers of the four sets it writes are the
-    // selects of steps i - 8, i - 6, i - 4 and i - 2, launched on the SAME stream before scan i, so stream order alone has them
-    // finished.  The other stream's steps have the other parity and the other four sets.  With fewer sets the scan of step i
-    // would write the set of step i + 6 into one that a select of the other stream, ordered against nothing here, may be reading.)
-    const size_t n_sets = overlap ? 8 : 2;
-    rc = ensure_scratch(ctx, n_sets * list_bytes + table_bytes);
-    if (rc != SMT_OK) return rc;
-    key_t64 *lists = reinterpret_cast<key_t64 *>(reinterpret_cast<char *>(ctx->d_scratch) + (step & (n_sets - 1)) * list_bytes);
-    uint64_t *table = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(ctx->d_scratch) + n_sets * list_bytes);
-    // scan_pair: the launch may share its corpus pass with the call two steps later, or be absorbed by the one two steps earlier
-    // (scan_pair_kernel).  Not with wave stamps (profiling of the plain kernel).
-    const bool pair = overlap && ctx->tune.scan_pair && U == 4 && ctx->tune.scan_debug_ptr == 0;
-    if (pair && (rc = ensure_pair(ctx))) return rc;
-
-    const bool nt = ctx->tune.scan_nontemporal != 0;
-    hipStream_t st = ctx->stream;
-    unsigned long long gate_open = 0, gate_ticks = 0;
-    PairParams pp{};
-    bool may_pair = false;   // scan_pair: this launch runs scan_pair_kernel (it looks for a partner, and may find itself absorbed)
-    if (overlap) {
-        st = ctx->ov_stream[step & 1];
-        // a predecessor that takes this call's query along reads it without waiting for ov_ready: only a query that no work queued on
-        // the caller's stream can still be writing may be taken
-        // ... and only a launch that queues up behind a predecessor on its stream can be absorbed by it, or has reason to look for a
-        // partner itself (a call made while the GPU is idle must cost what it did: no look, no wait; scan_pair_wait_us: tests)
-        if (pair) {
-            const bool behind = ctx->tune.scan_pair_wait_us > 0 || hipStreamQuery(st) != hipSuccess;
-            const bool idle = behind && hipStreamQuery(ctx->stream) == hipSuccess;
-            (void)hipGetLastError();   // (hipErrorNotReady is an answer here)
-            pp.absorbable = idle ? 1u : 0u;
-            may_pair = behind;
-        }
-        SMT_HIP_CHECK(hipEventRecord(ctx->ov_ready[step & 1], ctx->stream));
-        SMT_HIP_CHECK(hipStreamWaitEvent(st, ctx->ov_ready[step & 1], 0));
-        // a timed launch waits for its predecessor (and that one's select), and the launch after it waits for it: the events bracket a
-        // kernel that has the part to itself, not a gate or an HBM shared with a neighbour
-        const bool timed = prof_arms_next(ctx, "scan");
-        if (timed || ctx->ov_after_timed) {
-            SMT_HIP_CHECK(hipEventRecord(ctx->ov_done, ctx->ov_stream[(step & 1) ^ 1]));
-            SMT_HIP_CHECK(hipStreamWaitEvent(st, ctx->ov_done, 0));
-        }
-        // (a timed launch and its successor neither absorb nor get absorbed: the events keep bracketing a one-query pass)
-        if (timed || ctx->ov_after_timed) { may_pair = false; pp.absorbable = 0; }
-        ctx->ov_after_timed = timed;
-        // What the gate counts is CALLS served, in blocks: a plain launch's block adds 1 when its rows are done, a leader's block the
-        // number of calls its pass serves, an absorbed launch nothing, and gate_total below counts one grid per call.  So "gate_pct of
-        // the predecessor" is: every call before the predecessor call is served, and gate_pct per cent of the predecessor call's
-        // grid.  When that call is the m-th of n that one pass serves, the point lies at (m - 1 + gate_pct / 100) / n of the pass'
-        // blocks: 75 % of a pair's pass and 87.5 % of a full group's at gate_pct = 50, while a leader still at its gate holds
-        // successors back only until their bound.  The default by the sweeps: 50 for every mode.  (While the grouped
-        // pass ran one tree per query, launches that take two or three calls along ran 4 us per step faster with no gate: two leaders
-        // on a CU filled each other's stalls.  With the group reducer every gate from 5 to 100 measures 48.0 us per step and no gate
-        // 50.1 with a spread of 3 us, profiles/scan_group_loop.json.)
-        const int gate_pct = ctx->tune.scan_gate_pct >= 0 ? ctx->tune.scan_gate_pct : 50;
-        if (gate_pct > 0 && ctx->gate_prev_blocks > 0) {
-            gate_open = ctx->gate_total - ctx->gate_prev_blocks + (ctx->gate_prev_blocks * (uint64_t)gate_pct + 99) / 100;
-            // the bound: the predecessor's rows at 4 TB/s (half the part's HBM rate; 1 KiB rows, 10 ns ticks) + 20 us, at most 0.5 ms (a
-            // grid that cannot be resident twice -- scan_blocks / scan_threads -- may hold back predecessor blocks while it waits)
-            gate_ticks = std::min<uint64_t>(ctx->gate_prev_rows / 39 + 2000, 50000);
-        }
-    }
-    prof_begin_on(ctx, "scan", st);
-    const uint64_t *use_table = table;
-    if (filtered && (rc = range_chunk_table(ctx, a, table, &use_table))) return rc;
-    for (uint32_t q0 = 0; q0 < a.nq;) {
-        ScanParams p;
-        p.corpus = a.corpus;
-        p.queries = a.queries + (size_t)q0 * 256;
-        p.n_virtual = a.n_virtual;
-        p.chunk_table = filtered ? use_table : nullptr;
-        p.n_chunks = n_chunks;
-        p.kp = kp;
-        p.block_lists = lists + (size_t)q0 * blocks * kp;
-        p.stamps = reinterpret_cast<unsigned long long *>(ctx->tune.scan_debug_ptr);
-        p.flags = async && !overlap ? ctx->d_flags : nullptr;
-        p.step = step;
-        p.steal_ctr = nullptr;
-        p.steal_lr = 0;
-        p.gate = overlap ? ctx->d_gate : nullptr;
-        p.gate_open = gate_open;
-        p.gate_ticks = gate_ticks;
-        // Dynamic groups (scan_topk_kernel STEAL; tuning key scan_steal = rounds per group, 0 = the static deal): unfiltered scans of
-        // 8-wave blocks over enough rows that every block gets well past its static groups.  Each launch has its own counter: a ring
-        // of 64, zeroed together every 64th launch (one 256-byte memset in stream order).
-        if (!filtered && U == 4 && threads == 512 && ctx->tune.scan_steal > 0 &&
-            n_chunks >= (uint64_t)blocks * 8u * (uint64_t)ctx->tune.scan_steal * 8u) {
-            if (!ctx->d_steal) SMT_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&ctx->d_steal), 64 * sizeof(unsigned int)));
-            if (ctx->steal_seq % 64 == 0) SMT_HIP_CHECK(hipMemsetAsync(ctx->d_steal, 0, 64 * sizeof(unsigned int), ctx->stream));
-            p.steal_ctr = ctx->d_steal + (ctx->steal_seq % 64);
-            ++ctx->steal_seq;
-            uint32_t lr = 0;
-            while ((2 << lr) <= ctx->tune.scan_steal) ++lr;
-            p.steal_lr = lr;
-            // the dynamic share: scan_steal_pct per cent of the groups (at least STEAL_DEPTH + 1 per block stay static)
-            const uint64_t n_groups = (n_chunks + (8ull << lr) - 1) / (8ull << lr);
-            const uint64_t per_block = n_groups / (uint64_t)blocks;
-            const uint64_t n_static = per_block * (uint64_t)(100 - ctx->tune.scan_steal_pct) / 100;
-            p.steal_static = (uint32_t)std::max<uint64_t>(n_static, 3);
-        }
-        const uint32_t left = a.nq - q0;
-        p.nq_active = left >= 4 ? 4u : left;
-        // (three queries ride in the four-query kernel: with the four rows of a chunk reduced together a pass costs 1.06 x / 1.4 x one
-        // query's for two / four queries -- 172 / 230 us at 1 M rows -- against 335 us for a pass of two and a pass of one)
-        if (left >= 3) {
-            rc = filtered ? launch_scan_filtered<4>(ctx, p, blocks, threads, nt)
-                 : (U == 4) ? launch_scan_variant<4, 4>(ctx, p, blocks, threads, nt, st)
-                            : launch_scan_variant<4, 8>(ctx, p, blocks, threads, nt, st);
-            q0 += p.nq_active;
-        } else if (left >= 2) {
-            rc = filtered ? launch_scan_filtered<2>(ctx, p, blocks, threads, nt)
-                 : (U == 4) ? launch_scan_variant<2, 4>(ctx, p, blocks, threads, nt, st)
-                            : launch_scan_variant<2, 8>(ctx, p, blocks, threads, nt, st);
-            q0 += 2;
-        } else {
-            if (filtered) rc = launch_scan_filtered<1>(ctx, p, blocks, threads, nt);
-            else if (pair && may_pair) rc = launch_scan_pair(ctx, p, pp, blocks, threads, nt, st);
-            else if (pair) { ++ctx->pair_alone_host; rc = launch_scan_variant<1, 4>(ctx, p, blocks, threads, nt, st); }
-            else if (U == 2) rc = launch_scan_variant<1, 2>(ctx, p, blocks, threads, nt, st);
-            else if (U == 4) rc = launch_scan_variant<1, 4>(ctx, p, blocks, threads, nt, st);
-            else rc = launch_scan_variant<1, 8>(ctx, p, blocks, threads, nt, st);
-            q0 += 1;
-        }
-        if (rc != SMT_OK) return rc;
-    }
-    prof_end_on(ctx, "scan", st);
-    if (overlap) {
-        ctx->gate_total += (uint64_t)blocks;
-        ctx->gate_prev_blocks = (uint64_t)blocks;
-        ctx->gate_prev_rows = a.n_virtual;
-        ctx->async_pending = true;
-        ctx->async_overlap = true;
-    } else if (async) {
-        ctx->async_overlap = false;
-    }
     SelectArgs s;
     s.corpus = a.corpus;
     s.queries = a.queries;
     s.nq = a.nq;
-    s.lists = lists;
-    s.n_lists = (uint32_t)blocks;
-    s.kp = kp;
-    s.list_stride = (uint64_t)blocks * kp;
+    s.lists = pl.lists;
+    s.n_lists = (uint32_t)pl.blocks;
+    s.kp = pl.kp;
+    s.list_stride = (uint64_t)pl.blocks * pl.kp;
     s.k_out = a.k_out;
     s.ws_threshold = a.ws_threshold;
     s.ws_thr_score = a.ws_thr_score;
@@ -1868,138 +1067,55 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
     s.out_rows = a.out_rows;
     s.out_dist = a.out_dist;
     s.out_counts = a.out_counts;
-    s.async_step = overlap ? 0 : step;
-    s.stream = st;
+    s.async_step = pl.overlap ? 0 : pl.step;
+    s.stream = pl.st;
     s.out_stride = a.out_stride;
     s.f32_err = F32_ERR_SCAN;
     s.out_uncertain = a.out_uncertain;
     s.out_status = a.out_status;
     s.deliver = a.deliver;
-    rc = launch_select(ctx, s);
+    return s;
+}
+
+int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
+{
+    SMT_REQUIRE(a.k_out >= 1 && a.k_out <= SCAN_MAX_K, "top_k for the scan path must be in [1, 56]");
+    SMT_REQUIRE(a.rows < 0xFFFFFFFFull, "a shard holds fewer than 2^32-1 rows");
+    ScanPlan pl = plan_scan(ctx, a);
+    int rc = enter_pipeline(ctx, a, pl);
+    if (rc != SMT_OK) return rc;
+    if (pl.overlap && (rc = overlap_prologue(ctx, pl))) return rc;
+
+    prof_begin_on(ctx, "scan", pl.st);
+    const uint64_t *chunk_table = pl.table;
+    if (pl.filtered && (rc = range_chunk_table(ctx, a, pl.table, &chunk_table))) return rc;
+    for (uint32_t q0 = 0; q0 < a.nq;) {
+        // (three queries ride in the four-query kernel: with the four rows of a chunk reduced together a pass costs 1.06 x / 1.4 x one
+        // query's for two / four queries -- 172 / 230 us at 1 M rows -- against 335 us for a pass of two and a pass of one)
+        const uint32_t left = a.nq - q0;
+        const int slots = left >= 3 ? 4 : (int)left;
+        ScanParams p = scan_params(ctx, a, pl, chunk_table, q0, std::min(left, 4u));
+        if ((rc = steal_setup(ctx, pl, p)) || (rc = launch_scan_pass(ctx, pl, p, slots))) return rc;
+        q0 += p.nq_active;
+    }
+    prof_end_on(ctx, "scan", pl.st);
+
+    if (pl.overlap) {
+        ctx->gate_total += (uint64_t)pl.blocks;
+        ctx->gate_prev_blocks = (uint64_t)pl.blocks;
+        ctx->gate_prev_rows = a.n_virtual;
+        ctx->async_pending = true;
+        ctx->async_overlap = true;
+    } else if (pl.async) {
+        ctx->async_overlap = false;
+    }
+    rc = launch_select(ctx, select_args(a, pl));
     // the aux stream's contract (smt_ctx_aux_stream): work a host chains there runs behind this call's select
-    if (rc == SMT_OK && overlap && ctx->aux_stream) {
-        SMT_HIP_CHECK(hipEventRecord(ctx->ov_sel[step & 1], st));
-        SMT_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ctx->ov_sel[step & 1], 0));
+    if (rc == SMT_OK && pl.overlap && ctx->aux_stream) {
+        SMT_HIP_CHECK(hipEventRecord(ctx->ov_sel[pl.step & 1], pl.st));
+        SMT_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ctx->ov_sel[pl.step & 1], 0));
     }
     return rc;
-}
-
-int launch_rescore_rows(smt_ctx *ctx, const float *corpus, const float *query, const uint32_t *rows,
-                        uint64_t n, double *out_dist)
-{
-    if (n == 0) return SMT_OK;
-    const int threads = 64;
-    const uint64_t blocks = (n + threads - 1) / threads;
-    prof_begin(ctx, "select");
-    hipLaunchKernelGGL(rescore_rows_kernel, dim3((unsigned)blocks), dim3(threads), 0, ctx->stream, corpus,
-                       query, rows, n, out_dist);
-    prof_end(ctx, "select");
-    SMT_HIP_CHECK(hipGetLastError());
-    return SMT_OK;
-}
-
-int launch_gather_rows256(smt_ctx *ctx, const float *src, const uint32_t *idx_dev, uint32_t n, float *dst)
-{
-    if (n == 0) return SMT_OK;
-    hipLaunchKernelGGL(gather_rows256_kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, src, idx_dev, n, dst);
-    SMT_HIP_CHECK(hipGetLastError());
-    return SMT_OK;
-}
-
-int launch_rescore_rows_multi(smt_ctx *ctx, const float *corpus, const float *queries, const uint32_t *rows, const uint32_t *qidx,
-                              uint64_t n, double *out_dist)
-{
-    if (n == 0) return SMT_OK;
-    const int threads = 64;
-    prof_begin(ctx, "select");
-    hipLaunchKernelGGL(rescore_rows_multi_kernel, dim3((unsigned)((n + threads - 1) / threads)), dim3(threads), 0, ctx->stream, corpus,
-                       queries, rows, qidx, n, out_dist);
-    prof_end(ctx, "select");
-    SMT_HIP_CHECK(hipGetLastError());
-    return SMT_OK;
-}
-
-int launch_merge_topk(smt_ctx *ctx, const uint64_t *rows, const double *dist, uint32_t n_lists,
-                      uint32_t nq, uint32_t k_in, uint32_t k_out, uint64_t *out_rows, double *out_dist)
-{
-    SMT_REQUIRE((uint64_t)n_lists * k_in <= 8192, "device merge handles up to 8192 candidates per query");
-    hipLaunchKernelGGL(merge_topk_kernel, dim3(nq), dim3(256), 0, ctx->stream, rows, dist, n_lists, (uint64_t)nq * k_in,
-                       (uint64_t)k_in, k_in, k_out, out_rows, out_dist, (uint64_t)k_out);
-    SMT_HIP_CHECK(hipGetLastError());
-    return SMT_OK;
-}
-
-// Packed lists [n_lists][nq][2][k_in] (list_stride_words apart: the exchange buffers of group_exchange.cpp carry a few status
-// words behind each rank's lists; 0 = dense) -> out_packed [nq][2][k_out], on stream `st`.  n_lists == 0 writes padding.
-int launch_merge_topk_packed_on(smt_ctx *ctx, hipStream_t st, const uint64_t *packed, uint32_t n_lists, uint32_t nq, uint32_t k_in,
-                                uint32_t k_out, uint64_t *out_packed, uint64_t list_stride_words)
-{
-    (void)ctx;
-    SMT_REQUIRE((uint64_t)n_lists * k_in <= 8192, "device merge handles up to 8192 candidates per query");
-    const uint64_t ls = list_stride_words ? list_stride_words : (uint64_t)nq * 2 * k_in;
-    hipLaunchKernelGGL(merge_topk_kernel, dim3(nq), dim3(256), 0, st, packed, reinterpret_cast<const double *>(packed + k_in),
-                       n_lists, ls, (uint64_t)2 * k_in, k_in, k_out, out_packed, reinterpret_cast<double *>(out_packed + k_out),
-                       (uint64_t)2 * k_out);
-    SMT_HIP_CHECK(hipGetLastError());
-    return SMT_OK;
-}
-
-// Packed lists [nq][2][k_in], one per source pointer (see merge_topk_sources_kernel) -> out_packed [nq][2][k_out] on stream `st`.
-int launch_merge_topk_sources_on(hipStream_t st, const MergeSources &src, uint32_t n_lists, uint32_t nq, uint32_t k_in, uint32_t k_out,
-                                 uint64_t *out_packed)
-{
-    SMT_REQUIRE(n_lists >= 1 && n_lists <= SMT_MAX_MERGE_SOURCES, "1..64 lists are merged in place");
-    SMT_REQUIRE((uint64_t)n_lists * k_in <= 8192, "the in-place merge stages up to 8192 candidates per query");
-    const size_t smem = (size_t)n_lists * k_in * 16;
-    if (smem > 64 * 1024) {   // more than 4096 candidates (large k: up to 8 x 1024): 128 KiB of LDS, allowed once per device
-        static bool big[64] = {};
-        int dev = 0;
-        SMT_HIP_CHECK(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 64) return SMT_E_INVALID;
-        if (!big[dev]) {
-            SMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(merge_topk_sources_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              8192 * 16));
-            big[dev] = true;
-        }
-    }
-    hipLaunchKernelGGL(merge_topk_sources_kernel, dim3(nq), dim3(256), smem, st, src, n_lists, (uint64_t)2 * k_in, k_in, k_out, out_packed,
-                       reinterpret_cast<double *>(out_packed + k_out), (uint64_t)2 * k_out);
-    SMT_HIP_CHECK(hipGetLastError());
-    return SMT_OK;
-}
-
-__global__ void combine_status_kernel(MergeSources src, const uint64_t *base, uint64_t stride_words, uint32_t n, uint32_t nq, uint32_t *out)
-{
-    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nq) return;
-    uint64_t worst = 0;
-    for (uint32_t j = 0; j < n; ++j) {
-        const uint64_t v = base ? base[(size_t)j * stride_words + q] : src.list[j][q];
-        worst = v > worst ? v : worst;
-    }
-    out[q] = (uint32_t)worst;
-}
-
-int launch_combine_status_on(hipStream_t st, const MergeSources *src, const uint64_t *base, uint64_t stride_words, uint32_t n, uint32_t nq,
-                             uint32_t *out)
-{
-    SMT_REQUIRE((src != nullptr) != (base != nullptr), "status sources: pointers or a strided buffer");
-    SMT_REQUIRE(src == nullptr || n <= SMT_MAX_MERGE_SOURCES, "1..64 status sources are read in place");
-    if (nq == 0) return SMT_OK;
-    MergeSources none{};
-    hipLaunchKernelGGL(combine_status_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, src ? *src : none, base, stride_words, n, nq, out);
-    SMT_HIP_CHECK(hipGetLastError());
-    return SMT_OK;
-}
-
-int launch_merge_topk_packed(smt_ctx *ctx, const uint64_t *packed, uint32_t n_lists, uint32_t nq, uint32_t k_in,
-                             uint32_t k_out, uint64_t *out_packed)
-{
-    // async pipeline: the merge follows the select it consumes on the aux stream (tuning key merge_on_aux)
-    const bool on_aux = ctx->tune.merge_on_aux && ctx->aux_stream != nullptr;
-    hipStream_t st = on_aux ? ctx->aux_stream : ctx->stream;  // (ctx->stream may itself be the null stream)
-    if (on_aux) ctx->async_pending = true;
-    return launch_merge_topk_packed_on(ctx, st, packed, n_lists, nq, k_in, k_out, out_packed, 0);
 }
 
 }  // namespace smt

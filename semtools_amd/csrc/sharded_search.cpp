@@ -296,6 +296,11 @@ try {
     // the select of a single query may run on the aux stream while the NEXT call's scan streams (async select); the exchange and
     // the merge then follow it there, and the main stream carries nothing but scans
     for (int i = 0; i < g->n_local; ++i) on_aux[i] = g->ctx[i]->tune.async_select && nq == 1 && sc->shard[i]->rows >= top_k && top_k <= SCAN_MAX_K ? 1 : 0;
+    // (the aux streams exist before anything names them: the first async scan of a context would make its own only inside the
+    // rank's search below, after exchange_stream had answered with a null stream -- the list was then published, and awaited by
+    // the other ranks' issuers, on the default stream, which orders nothing against the select)
+    for (int i = 0; i < g->n_local; ++i)
+        if (on_aux[i] && ((rc = group_bind(g, i)) || (rc = ensure_async(g->ctx[i])))) return rc;
     WaitBoard board(g, on_aux, out_packed);   // (peer transport with issuing threads: the ranks' issuers enqueue the merges' waits)
     int slot = -1;
     if (peer) {   // rank j writes its list into slot `slot` of its ring; whoever needs the answer reads the slots in place

@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "device_utils.h"
+#include "chunk_deal.h"
 
 namespace smt {
 
@@ -27,7 +28,7 @@ struct ThrParams {
     const float *corpus;
     const float *query;
     uint64_t n_virtual;
-    const uint64_t *chunk_table;  // FILTERED: row0 | valid rows << 32 per chunk (scan_kernels.hip)
+    const uint64_t *chunk_table;  // FILTERED: row0 | valid rows << 32 per chunk (range_tables.hip)
     uint64_t n_chunks;
     float prefilter;
     uint32_t *hit_rows;
@@ -54,29 +55,13 @@ __global__ void __launch_bounds__(1024) scan_threshold_kernel(ThrParams p)
 
     const uint64_t n_chunks = p.n_chunks;
     const const_u64_ptr const_table = (const_u64_ptr)(uintptr_t)p.chunk_table;
-    auto chunk_id = [&](uint32_t t) -> uint64_t {  // chunk t of this block (same deal as K2, see scan_kernels.hip)
-        const uint64_t c = ((uint64_t)(t / waves_per_block) * gridDim.x + blockIdx.x) * waves_per_block + t % waves_per_block;
-        return uniform_u64(c);  // the division runs on the VALU: tell the compiler the result is wave-uniform (scalar loads)
-    };
-    auto claim = [&]() -> uint32_t {
-        uint32_t t = 0;
-        if (lane == 0) t = atomicAdd(s_next, 1u);
-        return (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-    };
+    // (the chunk deal of all streaming kernels: chunk_deal.h)
     auto fetch_desc = [&](uint64_t c) -> uint64_t {
         if (c >= n_chunks) return 0ull;
-        if (FILTERED) return const_table[c];  // constant address space: scalar load (see scan_kernels.hip)
+        if (FILTERED) return const_table[c];  // constant address space: scalar load (see scan_topk_kernel, scan_kernels.hip)
         const uint64_t v0 = c * U;
         const uint64_t left = p.n_virtual - v0;
         return v0 | ((left < (uint64_t)U ? left : (uint64_t)U) << 32);
-    };
-    auto issue_loads = [&](uint64_t desc, f32x4 (&c)[U], uint32_t (&row)[U]) {
-        const uint32_t row0 = (uint32_t)desc, cnt = (uint32_t)(desc >> 32);
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            row[j] = row0 + ((uint32_t)j < cnt ? (uint32_t)j : 0u);
-            c[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p.corpus + (uint64_t)row[j] * 256) + lane);
-        }
     };
     if (threadIdx.x == 0) *s_next = (uint32_t)waves_per_block;
     __syncthreads();
@@ -99,13 +84,13 @@ __global__ void __launch_bounds__(1024) scan_threshold_kernel(ThrParams p)
 
     f32x4 cn[U];
     uint32_t rown[U];
-    uint64_t cA = chunk_id((uint32_t)wave), cB = n_chunks, cC = n_chunks;
+    uint64_t cA = deal_chunk((uint32_t)wave, waves_per_block), cB = n_chunks, cC = n_chunks;
     uint64_t dA = fetch_desc(cA), dB = 0;
     if (cA < n_chunks) {
-        issue_loads(dA, cn, rown);
-        cB = chunk_id(claim());
+        deal_issue_loads<U, true>(p, dA, lane, cn, rown);
+        cB = deal_chunk(deal_claim(s_next, lane), waves_per_block);
         dB = fetch_desc(cB);
-        if (FILTERED) cC = chunk_id(claim());  // only a table descriptor needs a stage of its own
+        if (FILTERED) cC = deal_chunk(deal_claim(s_next, lane), waves_per_block);  // only a table descriptor needs a stage of its own
     }
     while (cA < n_chunks) {
         f32x4 c[U];
@@ -113,10 +98,10 @@ __global__ void __launch_bounds__(1024) scan_threshold_kernel(ThrParams p)
 #pragma unroll
         for (int j = 0; j < U; ++j) { c[j] = cn[j]; row[j] = rown[j]; }
         const uint64_t first = dA & 0xFFFFFFFFull, end = first + (dA >> 32);  // rows [first, end) of this chunk are real
-        if (cB < n_chunks) issue_loads(dB, cn, rown);
+        if (cB < n_chunks) deal_issue_loads<U, true>(p, dB, lane, cn, rown);
         uint64_t cN, dN;  // the chunk after B
-        if (FILTERED) { cN = cC; dN = fetch_desc(cC); cC = chunk_id(claim()); }
-        else { cN = chunk_id(claim()); dN = fetch_desc(cN); }
+        if (FILTERED) { cN = cC; dN = fetch_desc(cC); cC = deal_chunk(deal_claim(s_next, lane), waves_per_block); }
+        else { cN = deal_chunk(deal_claim(s_next, lane), waves_per_block); dN = fetch_desc(cN); }
 
         // lane j (< U) remembers whether row j passed
         bool pass_mine = false;

@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "device_utils.h"
+#include "chunk_deal.h"
 
 namespace smt {
 
@@ -145,7 +146,7 @@ struct CollectParams {
     const float *corpus;
     const float *queries;
     uint64_t n_virtual;
-    const uint64_t *chunk_table;   // FILTERED: row0 | valid rows << 32 per chunk (scan_kernels.hip)
+    const uint64_t *chunk_table;   // FILTERED: row0 | valid rows << 32 per chunk (range_tables.hip)
     uint64_t n_chunks;
     const float *tau;              // [nq]
     key_t64 *cand;                 // [nq][cap]
@@ -176,29 +177,13 @@ __global__ void __launch_bounds__(1024) largek_collect_kernel(CollectParams p)
 
     const uint64_t n_chunks = p.n_chunks;
     const const_u64_ptr const_table = (const_u64_ptr)(uintptr_t)p.chunk_table;
-    auto chunk_id = [&](uint32_t t) -> uint64_t {
-        const uint64_t c = ((uint64_t)(t / waves_per_block) * gridDim.x + blockIdx.x) * waves_per_block + t % waves_per_block;
-        return uniform_u64(c);
-    };
-    auto claim = [&]() -> uint32_t {
-        uint32_t t = 0;
-        if (lane == 0) t = atomicAdd(s_next, 1u);
-        return (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-    };
+    // (the chunk deal of all streaming kernels: chunk_deal.h)
     auto fetch_desc = [&](uint64_t c) -> uint64_t {
         if (c >= n_chunks) return 0ull;
         if (FILTERED) return const_table[c];
         const uint64_t v0 = c * U;
         const uint64_t left = p.n_virtual - v0;
         return v0 | ((left < (uint64_t)U ? left : (uint64_t)U) << 32);
-    };
-    auto issue_loads = [&](uint64_t desc, f32x4 (&c)[U], uint32_t (&row)[U]) {
-        const uint32_t row0 = (uint32_t)desc, cnt = (uint32_t)(desc >> 32);
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            row[j] = row0 + ((uint32_t)j < cnt ? (uint32_t)j : 0u);
-            c[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p.corpus + (uint64_t)row[j] * 256) + lane);
-        }
     };
     if (threadIdx.x == 0) *s_next = (uint32_t)waves_per_block;
     __syncthreads();
@@ -220,13 +205,13 @@ __global__ void __launch_bounds__(1024) largek_collect_kernel(CollectParams p)
 
     f32x4 cn[U];
     uint32_t rown[U];
-    uint64_t cA = chunk_id((uint32_t)wave), cB = n_chunks, cC = n_chunks;
+    uint64_t cA = deal_chunk((uint32_t)wave, waves_per_block), cB = n_chunks, cC = n_chunks;
     uint64_t dA = fetch_desc(cA), dB = 0;
     if (cA < n_chunks) {
-        issue_loads(dA, cn, rown);
-        cB = chunk_id(claim());
+        deal_issue_loads<U, true>(p, dA, lane, cn, rown);
+        cB = deal_chunk(deal_claim(s_next, lane), waves_per_block);
         dB = fetch_desc(cB);
-        if (FILTERED) cC = chunk_id(claim());
+        if (FILTERED) cC = deal_chunk(deal_claim(s_next, lane), waves_per_block);
     }
     while (cA < n_chunks) {
         f32x4 c[U];
@@ -234,10 +219,10 @@ __global__ void __launch_bounds__(1024) largek_collect_kernel(CollectParams p)
 #pragma unroll
         for (int j = 0; j < U; ++j) { c[j] = cn[j]; row[j] = rown[j]; }
         const uint64_t first = dA & 0xFFFFFFFFull, end = first + (dA >> 32);
-        if (cB < n_chunks) issue_loads(dB, cn, rown);
+        if (cB < n_chunks) deal_issue_loads<U, true>(p, dB, lane, cn, rown);
         uint64_t cN, dN;
-        if (FILTERED) { cN = cC; dN = fetch_desc(cC); cC = chunk_id(claim()); }
-        else { cN = chunk_id(claim()); dN = fetch_desc(cN); }
+        if (FILTERED) { cN = cC; dN = fetch_desc(cC); cC = deal_chunk(deal_claim(s_next, lane), waves_per_block); }
+        else { cN = deal_chunk(deal_claim(s_next, lane), waves_per_block); dN = fetch_desc(cN); }
 
         float pb[4], pa[4];
 #pragma unroll

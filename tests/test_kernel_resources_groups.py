@@ -2,9 +2,9 @@
 tests/test_kernel_resources_pairing.py, which pins its registers (<= 64 VGPRs, no spill).
 
 Here: no scratch at all; its LDS -- static plus the dynamic size the launcher asks for -- small enough that two scan blocks of
-neighbouring streams share a CU with one select (160 KiB per CU, 84 KiB of them the select's at the headline's k = 10); and the
-query accessor that SMT_REDUCE_CHUNK4 got for it (LDS images instead of registers) left every scan_topk_kernel instantiation with
-the registers it had in the parent commit."""
+neighbouring streams share a CU with one select (160 KiB per CU, 84 KiB of them the select's at the headline's k = 10); and every
+scan_topk_kernel instantiation has the registers it had before this kernel came (SMT_REDUCE_CHUNK4 carried a query accessor for
+it for a while -- LDS images instead of registers; it reads q[n] directly again)."""
 import os
 import re
 

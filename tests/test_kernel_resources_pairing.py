@@ -16,5 +16,5 @@ def test_pair_capable_scan_fits_beside_the_select_and_does_not_spill():
     for k, v in pair.items():
         assert v["VGPRs"] <= 64 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0, (k, v)
         assert v.get("ScratchSize [bytes/lane]", 0) == 0, (k, v)
-    sel = [v for k, v in u.items() if "final_select_kernelILi8ELb0" in k]
+    sel = [v for k, v in _usage("select.hip").items() if "final_select_kernelILi8ELb0" in k]
     assert len(sel) == 1 and sel[0]["VGPRs"] <= 96, sel
