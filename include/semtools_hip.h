@@ -178,7 +178,7 @@ int smt_embed_device(smt_model *model, const uint32_t *ids_dev, const uint64_t *
                      uint64_t n_lines, uint32_t max_tokens, float *out_dev);
 
 /* ---------------------------------------------------------------- tokenizer
- * Pure-ASCII lines through BertNormalizer -> BertPreTokenizer -> WordPiece on the device (tokenize_kernels.hip): the
+ * Pure-ASCII lines through BertNormalizer -> BertPreTokenizer -> WordPiece on the device (wordpiece_kernels.hip): the
  * byte rules of the host tokenizer's ASCII path, the same ids.  A line the kernel does not cover -- a byte >= 0x80, or an added
  * token standing in it -- is FLAGGED and left to the caller, who may splice its ids in as a patch.
  *

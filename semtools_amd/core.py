@@ -244,12 +244,79 @@ class Model:
                                          int(max_tokens), C.c_void_p(out_ptr)))
 
 
-class WordPiece:
+class _DeviceTokenizer:
+    """What the device tokenizers share: the calls on the C functions smt_<_prefix>_*.  A line owns its looked-at bytes as id slots,
+    and _extra_slot more."""
+
+    _prefix = None
+    _extra_slot = 0
+
+    def _c(self, name):
+        return getattr(L.lib(), "smt_%s_%s" % (self._prefix, name))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._c("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):  # best effort
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def pack(lines):
+        """(text bytes, uint64 line_begin, uint32 line_len) of lines packed back to back, no separator"""
+        lines = [x.encode() if isinstance(x, str) else bytes(x) for x in lines]
+        lens = np.array([len(x) for x in lines], dtype=np.uint32)
+        begin = np.zeros(len(lines), dtype=np.uint64)
+        if len(lines) > 1:
+            begin[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        return b"".join(lines), begin, lens
+
+    def tokenize(self, lines=None, text=None, line_begin=None, line_len=None, keep_bytes=0, max_tokens=0, drop_unk=True, ids_cap=None):
+        """-> (ids uint32, offsets uint64 [n + 1], flags uint8 [n]) through smt_<family>_tokenize.  `lines` are packed back to
+        back; or give text / line_begin / line_len.  ids_cap defaults to the looked-at bytes of all lines (Unigram: + one per line)."""
+        if lines is not None:
+            text, line_begin, line_len = self.pack(lines)
+        line_begin = np.ascontiguousarray(line_begin, dtype=np.uint64)
+        line_len = np.ascontiguousarray(line_len, dtype=np.uint32)
+        n = len(line_len)
+        if ids_cap is None:
+            ids_cap = int(np.minimum(line_len, keep_bytes).sum() if keep_bytes else line_len.sum()) + n * self._extra_slot
+        ids = np.zeros(max(int(ids_cap), 1), dtype=np.uint32)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        flags = np.zeros(max(n, 1), dtype=np.uint8)
+        buf = C.create_string_buffer(bytes(text), max(len(text), 1))
+        L.check(self._c("tokenize")(self._h, C.cast(buf, C.c_void_p), L.np_ptr(line_begin), L.np_ptr(line_len), n, int(keep_bytes),
+                                    int(max_tokens), int(bool(drop_unk)), L.np_ptr(ids), int(ids_cap), L.np_ptr(offsets), L.np_ptr(flags)))
+        return ids[:int(offsets[n])].copy(), offsets, flags[:n].copy()
+
+    def scan_device(self, text_ptr, text_bytes, line_begin_ptr, line_len_ptr, n_lines, keep_bytes, max_tokens, drop_unk, counts_ptr, flags_ptr,
+                    n_flagged_ptr):
+        """pass 1 on raw device pointers (ints); enqueued on the context's stream"""
+        vp = C.c_void_p
+        L.check(self._c("scan_device")(self._h, vp(text_ptr), int(text_bytes), vp(line_begin_ptr), vp(line_len_ptr), int(n_lines),
+                                       int(keep_bytes), int(max_tokens), int(bool(drop_unk)), vp(counts_ptr), vp(flags_ptr), vp(n_flagged_ptr)))
+
+    def emit_device(self, n_lines, ids_out_ptr, ids_cap, offsets_out_ptr, patch_line_ptr=None, patch_off_ptr=None, patch_ids_ptr=None, n_patch=0,
+                    n_patch_ids=0):
+        """pass 2 on raw device pointers (ints); enqueued on the context's stream.  ids_cap >= min(text bytes, n_lines * keep_bytes)
+        + n_patch_ids (Unigram: + n_lines)"""
+        vp = C.c_void_p
+        L.check(self._c("emit_device")(self._h, int(n_lines), vp(patch_line_ptr), vp(patch_off_ptr), vp(patch_ids_ptr), int(n_patch),
+                                       int(n_patch_ids), vp(ids_out_ptr), int(ids_cap), vp(offsets_out_ptr)))
+
+
+class WordPiece(_DeviceTokenizer):
     """The device tokenizer (smt_wordpiece): pure-ASCII lines through BertNormalizer -> BertPreTokenizer -> WordPiece.
 
     WordPiece(ctx, vocab={piece: id}, unk_id=.., flags=L.WP_*, added=[..]) builds it from a vocabulary;
     WordPiece(ctx, host_tokenizer=<smt_host_tokenizer handle>) takes the device form of a loaded tokenizer.json
-    (SmtError with code SMT_E_UNSUPPORTED when it has none)."""
+    (SmtError with code SMT_E_UNSUPPORTED when it has none).  Calls smt_wordpiece_{tokenize,scan_device,emit_device,destroy}."""
+
+    _prefix = "wordpiece"
 
     def __init__(self, ctx, vocab=None, unk_id=-1, prefix="##", max_input_chars_per_word=100,
                  flags=L.WP_NORMALIZER | L.WP_CLEAN_TEXT | L.WP_LOWERCASE, added=(), host_tokenizer=None):
@@ -271,71 +338,17 @@ class WordPiece:
                                    int(max_input_chars_per_word), int(flags), b"".join(added_b), L.np_ptr(aoff), len(added_b))
         L.check(L.lib().smt_wordpiece_create(ctx._h, C.byref(prm), C.byref(self._h)))
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            L.lib().smt_wordpiece_destroy(self._h)
-            self._h = None
 
-    def __del__(self):  # best effort
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @staticmethod
-    def pack(lines):
-        """(text bytes, uint64 line_begin, uint32 line_len) of lines packed back to back, no separator"""
-        lines = [x.encode() if isinstance(x, str) else bytes(x) for x in lines]
-        lens = np.array([len(x) for x in lines], dtype=np.uint32)
-        begin = np.zeros(len(lines), dtype=np.uint64)
-        if len(lines) > 1:
-            begin[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-        return b"".join(lines), begin, lens
-
-    def tokenize(self, lines=None, text=None, line_begin=None, line_len=None, keep_bytes=0, max_tokens=0, drop_unk=True, ids_cap=None):
-        """-> (ids uint32, offsets uint64 [n + 1], flags uint8 [n]) through smt_wordpiece_tokenize.  `lines` are packed back to
-        back; or give text / line_begin / line_len."""
-        if lines is not None:
-            text, line_begin, line_len = self.pack(lines)
-        line_begin = np.ascontiguousarray(line_begin, dtype=np.uint64)
-        line_len = np.ascontiguousarray(line_len, dtype=np.uint32)
-        n = len(line_len)
-        if ids_cap is None:
-            ids_cap = int(np.minimum(line_len, keep_bytes).sum() if keep_bytes else line_len.sum())
-        ids = np.zeros(max(int(ids_cap), 1), dtype=np.uint32)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        flags = np.zeros(max(n, 1), dtype=np.uint8)
-        buf = C.create_string_buffer(bytes(text), max(len(text), 1))
-        L.check(L.lib().smt_wordpiece_tokenize(self._h, C.cast(buf, C.c_void_p), L.np_ptr(line_begin), L.np_ptr(line_len), n, int(keep_bytes),
-                                               int(max_tokens), int(bool(drop_unk)), L.np_ptr(ids), int(ids_cap), L.np_ptr(offsets),
-                                               L.np_ptr(flags)))
-        return ids[:int(offsets[n])].copy(), offsets, flags[:n].copy()
-
-    def scan_device(self, text_ptr, text_bytes, line_begin_ptr, line_len_ptr, n_lines, keep_bytes, max_tokens, drop_unk, counts_ptr, flags_ptr,
-                    n_flagged_ptr):
-        """pass 1 on raw device pointers (ints); enqueued on the context's stream"""
-        vp = C.c_void_p
-        L.check(L.lib().smt_wordpiece_scan_device(self._h, vp(text_ptr), int(text_bytes), vp(line_begin_ptr), vp(line_len_ptr), int(n_lines),
-                                                  int(keep_bytes), int(max_tokens), int(bool(drop_unk)), vp(counts_ptr), vp(flags_ptr),
-                                                  vp(n_flagged_ptr)))
-
-    def emit_device(self, n_lines, ids_out_ptr, ids_cap, offsets_out_ptr, patch_line_ptr=None, patch_off_ptr=None, patch_ids_ptr=None, n_patch=0,
-                    n_patch_ids=0):
-        """pass 2 on raw device pointers (ints); enqueued on the context's stream"""
-        vp = C.c_void_p
-        L.check(L.lib().smt_wordpiece_emit_device(self._h, int(n_lines), vp(patch_line_ptr), vp(patch_off_ptr), vp(patch_ids_ptr), int(n_patch),
-                                                  int(n_patch_ids), vp(ids_out_ptr), int(ids_cap), vp(offsets_out_ptr)))
-
-
-class Unigram:
+class Unigram(_DeviceTokenizer):
     """The device tokenizer (smt_unigram): pure-ASCII lines through a per-byte normalizer -> Metaspace -> Unigram.
 
     Unigram(ctx, vocab=[(piece, score), ..], unk_id=.., replacement="\u2581", prepend="always", byte_map=.., added=[..]) builds it
     from a vocabulary (the id of a piece is its index; unk_score defaults to the lowest score - 10; byte_map: 128 entries, the byte
     a byte becomes or 0xFF for dropped, default the identity); Unigram(ctx, host_tokenizer=<smt_host_tokenizer handle>) takes the
-    device form of a loaded tokenizer.json (SmtError with code SMT_E_UNSUPPORTED when it has none)."""
+    device form of a loaded tokenizer.json (SmtError with code SMT_E_UNSUPPORTED when it has none).  Calls
+    smt_unigram_{tokenize,scan_device,emit_device,destroy}; a line can hold one token more than looked-at bytes."""
 
-    pack = staticmethod(WordPiece.pack)
+    _prefix, _extra_slot = "unigram", 1
 
     def __init__(self, ctx, vocab=None, unk_id=-1, replacement="\u2581", prepend="always", byte_map=None, added=(), unk_score=None,
                  host_tokenizer=None):
@@ -363,52 +376,6 @@ class Unigram:
                                  len(rep), int(L.UG_PREPEND.get(prepend, prepend)), L.np_ptr(bmap), b"".join(added_b), L.np_ptr(aoff),
                                  len(added_b))
         L.check(L.lib().smt_unigram_create(ctx._h, C.byref(prm), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            L.lib().smt_unigram_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # best effort
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def tokenize(self, lines=None, text=None, line_begin=None, line_len=None, keep_bytes=0, max_tokens=0, drop_unk=True, ids_cap=None):
-        """-> (ids uint32, offsets uint64 [n + 1], flags uint8 [n]) through smt_unigram_tokenize.  `lines` are packed back to
-        back; or give text / line_begin / line_len.  ids_cap defaults to the looked-at bytes of all lines + one per line."""
-        if lines is not None:
-            text, line_begin, line_len = self.pack(lines)
-        line_begin = np.ascontiguousarray(line_begin, dtype=np.uint64)
-        line_len = np.ascontiguousarray(line_len, dtype=np.uint32)
-        n = len(line_len)
-        if ids_cap is None:
-            ids_cap = int(np.minimum(line_len, keep_bytes).sum() if keep_bytes else line_len.sum()) + n
-        ids = np.zeros(max(int(ids_cap), 1), dtype=np.uint32)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        flags = np.zeros(max(n, 1), dtype=np.uint8)
-        buf = C.create_string_buffer(bytes(text), max(len(text), 1))
-        L.check(L.lib().smt_unigram_tokenize(self._h, C.cast(buf, C.c_void_p), L.np_ptr(line_begin), L.np_ptr(line_len), n, int(keep_bytes),
-                                             int(max_tokens), int(bool(drop_unk)), L.np_ptr(ids), int(ids_cap), L.np_ptr(offsets),
-                                             L.np_ptr(flags)))
-        return ids[:int(offsets[n])].copy(), offsets, flags[:n].copy()
-
-    def scan_device(self, text_ptr, text_bytes, line_begin_ptr, line_len_ptr, n_lines, keep_bytes, max_tokens, drop_unk, counts_ptr, flags_ptr,
-                    n_flagged_ptr):
-        """pass 1 on raw device pointers (ints); enqueued on the context's stream"""
-        vp = C.c_void_p
-        L.check(L.lib().smt_unigram_scan_device(self._h, vp(text_ptr), int(text_bytes), vp(line_begin_ptr), vp(line_len_ptr), int(n_lines),
-                                                int(keep_bytes), int(max_tokens), int(bool(drop_unk)), vp(counts_ptr), vp(flags_ptr),
-                                                vp(n_flagged_ptr)))
-
-    def emit_device(self, n_lines, ids_out_ptr, ids_cap, offsets_out_ptr, patch_line_ptr=None, patch_off_ptr=None, patch_ids_ptr=None, n_patch=0,
-                    n_patch_ids=0):
-        """pass 2 on raw device pointers (ints); enqueued on the context's stream.  ids_cap >= min(text bytes, n_lines * keep_bytes)
-        + n_lines + n_patch_ids"""
-        vp = C.c_void_p
-        L.check(L.lib().smt_unigram_emit_device(self._h, int(n_lines), vp(patch_line_ptr), vp(patch_off_ptr), vp(patch_ids_ptr), int(n_patch),
-                                                int(n_patch_ids), vp(ids_out_ptr), int(ids_cap), vp(offsets_out_ptr)))
 
 
 class Corpus:

@@ -1,11 +1,12 @@
 // device_tokenize.cpp -- the host layer's device route for a batch of lines: pack the line bytes back to back into a
-// pinned buffer, upload, tokenize on the device (smt_wordpiece_scan_device or smt_unigram_scan_device), tokenize the lines the kernel
-// flags with the host tokenizer, splice them in (smt_*_emit_device) and pool the device CSR with K1 -- the token ids never visit the host
+// pinned buffer, upload, tokenize on the device (tok_scan_device of tokenize_frame.h, whichever family the handle is), tokenize the lines
+// the kernel flags with the host tokenizer, splice them in (tok_emit_device) and pool the device CSR with K1 -- the token ids never visit the host
 // unless a caller wants them (the workspace's cached ids).  One-rank groups only; StaticModel decides when the route applies.
 #include <chrono>
 
 #include "../common.h"
 #include "../group.h"
+#include "../tokenize_frame.h"
 #include "host.h"
 #include "host_internal.h"
 
@@ -15,8 +16,7 @@ namespace search {
 struct DeviceTokenRoute {
     smt_group *group = nullptr;
     smt_ctx *ctx = nullptr;
-    smt_wordpiece *wp = nullptr;   // one of the two
-    smt_unigram *ug = nullptr;
+    smt::TokHandle *tok = nullptr;   // an smt_wordpiece or an smt_unigram
     struct Slot {   // one batch packed for upload: line_begin u64 [n] | line_len u32 [n] | text
         char *pin = nullptr;
         size_t pin_bytes = 0;
@@ -67,34 +67,34 @@ DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok)
     if (smt_group_info(group, &n_ranks, nullptr, nullptr, nullptr, nullptr) != SMT_OK || n_ranks != 1) return nullptr;
     smt_ctx *ctx = smt_group_ctx(group, 0);
     if (!ctx) return nullptr;
-    smt_wordpiece *wp = nullptr;
-    smt_unigram *ug = nullptr;
+    smt::TokHandle *h = nullptr;
     WordpieceExport x;
     UnigramExport u;
     if (tok.export_wordpiece(x)) {
         const smt_wordpiece_params p = x.params();
+        smt_wordpiece *wp = nullptr;
         api_ok(smt_wordpiece_create(ctx, &p, &wp), "smt_wordpiece_create");
+        h = smt::tok_handle(wp);
     } else if (tok.export_unigram(u)) {
         const smt_unigram_params p = u.params();
+        smt_unigram *ug = nullptr;
         api_ok(smt_unigram_create(ctx, &p, &ug), "smt_unigram_create");
+        h = smt::tok_handle(ug);
     } else {
         return nullptr;
     }
     auto *r = new DeviceTokenRoute();
     r->group = group;
     r->ctx = ctx;
-    r->wp = wp;
-    r->ug = ug;
+    r->tok = h;
     return r;
 }
 
 void device_route_destroy(DeviceTokenRoute *r)
 {
     if (!r) return;
+    smt::tok_destroy(r->tok);   // (waits for the stream)
     (void)hipSetDevice(r->ctx->device);
-    (void)hipStreamSynchronize(r->ctx->stream);
-    smt_wordpiece_destroy(r->wp);
-    smt_unigram_destroy(r->ug);
     for (auto &s : r->slot) if (s.pin) (void)hipHostFree(s.pin);
     for (void *p : {r->d_main, r->d_ids, r->d_patch, r->d_rows}) if (p) (void)hipFree(p);
     delete r;
@@ -161,9 +161,7 @@ uint64_t device_route_run(DeviceTokenRoute *r, int which, smt_sharded_model *mod
         const uint64_t *begin = reinterpret_cast<const uint64_t *>(d);
         const uint32_t *len = reinterpret_cast<const uint32_t *>(d + s.o_len);
         uint32_t *counts = reinterpret_cast<uint32_t *>(d + o_counts), *nflag = reinterpret_cast<uint32_t *>(d + o_nflag);
-        api_ok(r->wp ? smt_wordpiece_scan_device(r->wp, text, s.text_bytes, begin, len, n, keep_bytes, max_tokens, drop_unk ? 1 : 0, counts, d_flags, nflag)
-                     : smt_unigram_scan_device(r->ug, text, s.text_bytes, begin, len, n, keep_bytes, max_tokens, drop_unk ? 1 : 0, counts, d_flags, nflag),
-               "pass 1");
+        api_ok(smt::tok_scan_device(r->tok, text, s.text_bytes, begin, len, n, keep_bytes, max_tokens, drop_unk ? 1 : 0, counts, d_flags, nflag), "pass 1");
     }
     uint32_t n_flagged = 0;
     hip_ok(hipMemcpyAsync(&n_flagged, d + o_nflag, 4, hipMemcpyDeviceToHost, st), "n_flagged");
@@ -184,8 +182,7 @@ uint64_t device_route_run(DeviceTokenRoute *r, int which, smt_sharded_model *mod
     }
     t0 = std::chrono::steady_clock::now();
     const uint64_t n_patch = patch_line.size(), n_patch_ids = patch_ids.size();
-    // (a Unigram line can hold one token more than looked-at bytes: the prepended replacement)
-    const uint64_t ids_cap = (keep_bytes ? std::min<uint64_t>(s.text_bytes, n * (uint64_t)keep_bytes) : s.text_bytes) + (r->ug ? n : 0) + n_patch_ids;
+    const uint64_t ids_cap = r->tok->ids_bound + n_patch_ids;   // (the scan's bound on its own ids)
     grow_device(r, &r->d_ids, &r->ids_bytes, (size_t)ids_cap * 4 + 16, "token ids");
     const size_t p_off = up16(n_patch * 8), p_ids = p_off + up16((n_patch + 1) * 8);
     char *dp = nullptr;
@@ -201,9 +198,7 @@ uint64_t device_route_run(DeviceTokenRoute *r, int which, smt_sharded_model *mod
     {
         const uint64_t *pl = reinterpret_cast<const uint64_t *>(dp), *po = dp ? reinterpret_cast<const uint64_t *>(dp + p_off) : nullptr;
         const uint32_t *pi = dp ? reinterpret_cast<const uint32_t *>(dp + p_ids) : nullptr;
-        api_ok(r->wp ? smt_wordpiece_emit_device(r->wp, n, pl, po, pi, n_patch, n_patch_ids, d_ids, ids_cap, d_off)
-                     : smt_unigram_emit_device(r->ug, n, pl, po, pi, n_patch, n_patch_ids, d_ids, ids_cap, d_off),
-               "pass 2");
+        api_ok(smt::tok_emit_device(r->tok, n, pl, po, pi, n_patch, n_patch_ids, d_ids, ids_cap, d_off), "pass 2");
     }
     // ---- K1 on the device CSR (the lines are already truncated: no cap here, as on the host path)
     smt_model *m = model->model.at(0);

@@ -17,15 +17,16 @@
 //
 // A line of n looked-at bytes can hold n + 1 tokens (the prepended R), so line i owns the slots [begin_i + i, begin_{i+1} + i + 1): the
 // first piece writes from begin_i + i, the piece of a space at p from p + i + 1.  A piece has no more tokens than characters, so no two
-// pieces share a slot and slot order is token order; pass 2 is the WordPiece one (tokenize_pass2.h) on these slots.
+// pieces share a slot and slot order is token order; pass 2 is the shared one (tokenize_frame.h) on these slots.
 //
 // Every loop is bounded: probes by the table's capacity, walks by the longest piece and the piece's end, pieces by SMT_UG_MAX_WORD.
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "common.h"
-#include "tokenize_pass2.h"
+#include "tokenize_frame.h"
 
 namespace {
 
@@ -41,11 +42,8 @@ struct UgTable {
     const double *score;               // per entry
     const uint8_t *pool;
     const uint8_t *map;                // [128]: the normalised byte, UG_DROP
-    const uint8_t *added_pool;
-    const uint32_t *added_off;
     uint32_t mask;                     // capacity - 1
     uint32_t max_piece;                // longest piece of the vocabulary, in bytes
-    uint32_t n_added;
     uint32_t unk;                      // TOK_NONE: none
     uint32_t rlen;                     // bytes of R
     uint32_t prepend;                  // 0 always, 1 first, 2 never
@@ -53,18 +51,8 @@ struct UgTable {
     double r_score;
     double unk_score;
     unsigned long long r_state;        // the hash after R
-    unsigned long long added_first[2]; // bit c: an added token starts with byte c
+    smt::TokAdded added;
 };
-
-__device__ __forceinline__ uint64_t ug_count_le(const uint64_t *__restrict__ begin, uint64_t lo, uint64_t hi, uint64_t p)
-{
-    for (int step = 0; step < 64 && lo < hi; ++step) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (begin[mid] <= p) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // the candidate: clen kept bytes from raw position s (dropped bytes skipped), behind R for kind 1, hash h: its entry + 1, or 0
 __device__ __forceinline__ uint32_t ug_probe(const UgTable &T, const uint8_t *__restrict__ text, const uint8_t *map, unsigned long long h,
@@ -114,33 +102,11 @@ __global__ void __launch_bounds__(UG_THREADS) ug_scan_kernel(UgTable T, const ui
     __shared__ uint32_t s_id[UG_NODES];
     __shared__ uint16_t s_from[UG_NODES];
     if (threadIdx.x < 128) s_map[threadIdx.x] = T.map[threadIdx.x];
-    const uint64_t first = (uint64_t)blockIdx.x * UG_THREADS;
-    if (threadIdx.x < 2) {
-        const uint64_t last = first + UG_THREADS - 1 < text_bytes ? first + UG_THREADS - 1 : text_bytes - 1;
-        s_win[threadIdx.x] = ug_count_le(line_begin, 0, n_lines, threadIdx.x == 0 ? first : last);
-    }
-    __syncthreads();   // (the only barrier: lanes leave freely below)
-    const uint64_t p = first + threadIdx.x;
-    if (p >= text_bytes) return;
-    const uint64_t n_le = ug_count_le(line_begin, s_win[0], s_win[1], p);
-    if (n_le == 0) return;                       // in front of the first line
-    const uint64_t line = n_le - 1;
-    const uint64_t lb = line_begin[line];
-    const uint32_t ll = line_len[line];
-    const uint64_t le_line = lb + (keep_bytes && keep_bytes < ll ? keep_bytes : ll);
-    const uint64_t le = le_line < text_bytes ? le_line : text_bytes;   // the end of what is looked at
-    if (p < lb || p >= le) return;               // behind the cut, or between two lines
-    const uint8_t c = text[p];
-    if (c >= 0x80) { flags[line] = 1; return; }
-    if (((c < 64 ? T.added_first[0] : T.added_first[1]) >> (c & 63)) & 1) {
-        for (uint32_t t = 0; t < T.n_added; ++t) {
-            const uint32_t a = T.added_off[t], tl = T.added_off[t + 1] - a;
-            if (tl == 0 || p + tl > le) continue;
-            bool same = true;
-            for (uint32_t j = 0; j < tl && same; ++j) same = text[p + j] == T.added_pool[a + j];
-            if (same) { flags[line] = 1; break; }
-        }
-    }
+    uint64_t line, lb, le;
+    uint8_t c;
+    // (the only barrier is in there: lanes leave freely below)
+    if (!smt::tok_scan_lane(T.added, UG_THREADS, s_win, text, text_bytes, line_begin, line_len, n_lines, keep_bytes, flags, line, lb, le, c)) return;
+    const uint64_t first = (uint64_t)blockIdx.x * UG_THREADS, p = first + threadIdx.x;
     const bool at_space = s_map[c] == ' ';
     if (!at_space && p != lb) return;            // no piece starts here
     // ---- the piece: [R] + the kept bytes of [run, end); its measure is its raw bytes (+ 1 for a prepended R)
@@ -237,20 +203,33 @@ __global__ void __launch_bounds__(UG_THREADS) ug_scan_kernel(UgTable T, const ui
     if (n_tok) atomicAdd(&raw_count[line], n_tok);
 }
 
+constexpr smt::TokWords UG_WORDS = {"no scan to emit (smt_unigram_scan_device comes first)",
+                                    "ids_cap is below the looked-at bytes of all lines + one per line + the patch ids",
+                                    "ids_cap is below the looked-at bytes of all lines + one per line (ids_cap >= looked + n_lines)"};
+
 }  // namespace
 
-struct smt_unigram {
-    smt_ctx *ctx = nullptr;
-    void *d_table = nullptr;          // slots | entries | scores | pool | byte map | added pool | added offsets
-    UgTable T{};
-    smt::TokScratch S;                // the state of the last scan
-    bool scanned = false;
-    uint64_t text_bytes = 0, n_lines = 0, ids_bound = 0;
-    const uint32_t *counts = nullptr;
-    const uint8_t *flags = nullptr;
+struct smt_unigram : smt::TokHandle {   // every line has one slot more than bytes
+    UgTable T{};                      // points into d_table: slots | entries | scores | pool | byte map | added pool | added offsets
+    explicit smt_unigram(smt_ctx *c) : smt::TokHandle(c, true, UG_WORDS) {}
+    int pass1(const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev, uint64_t n_lines,
+              uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev) override
+    {
+        if (!n_lines) return SMT_OK;
+        hipLaunchKernelGGL(ug_slot_begin_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, ctx->stream, line_begin_dev, n_lines,
+                           S.slot_begin());
+        SMT_HIP_CHECK(hipGetLastError());
+        if (!text_bytes) return SMT_OK;
+        hipLaunchKernelGGL(ug_scan_kernel, dim3((unsigned)((text_bytes + UG_THREADS - 1) / UG_THREADS)), dim3(UG_THREADS), 0, ctx->stream, T, text_dev,
+                           text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, S.d_ids_tmp, S.raw_count(), flags_dev);
+        SMT_HIP_CHECK(hipGetLastError());
+        return SMT_OK;
+    }
 };
 
 using namespace smt;
+
+TokHandle *smt::tok_handle(smt_unigram *tok) { return tok; }
 
 extern "C" {
 
@@ -299,52 +278,29 @@ try {
     tok_build_table(p->pool, ents, table);
     std::vector<double> scores(table.ents.size());
     for (size_t j = 0; j < scores.size(); ++j) scores[j] = p->scores[table.winner[j]];
-    const size_t cap = table.slots.size();
-    const size_t pool_bytes = p->n_pieces ? p->piece_off[p->n_pieces] : 0;
-    const size_t added_bytes = p->n_added ? p->added_off[p->n_added] : 0;
-    unsigned long long added_first[2] = {0, 0};
-    for (uint32_t t = 0; t < p->n_added; ++t) {
-        const uint32_t a = p->added_off[t], tl = p->added_off[t + 1] - a;
-        for (uint32_t j = 0; j < tl; ++j) SMT_REQUIRE((uint8_t)p->added_pool[a + j] < 0x80, "added tokens must be ASCII");
-        if (tl) added_first[(uint8_t)p->added_pool[a] >> 6] |= 1ull << ((uint8_t)p->added_pool[a] & 63);
-    }
-    // ---- one blob, every part 16-byte aligned
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_slots = 0, o_ent = o_slots + up16(cap * 8), o_score = o_ent + up16(table.ents.size() * sizeof(uint4) + 16),
-                 o_pool = o_score + up16(scores.size() * 8 + 16), o_map = o_pool + up16(pool_bytes + 16), o_apool = o_map + 128,
-                 o_aoff = o_apool + up16(added_bytes + 16), total = o_aoff + up16(((size_t)p->n_added + 1) * 4);
-    std::vector<uint8_t> blob(total, 0);
-    memcpy(blob.data() + o_slots, table.slots.data(), cap * 8);
-    if (!table.ents.empty()) memcpy(blob.data() + o_ent, table.ents.data(), table.ents.size() * sizeof(uint4));
-    if (!scores.empty()) memcpy(blob.data() + o_score, scores.data(), scores.size() * 8);
-    if (pool_bytes) memcpy(blob.data() + o_pool, p->pool, pool_bytes);
-    memcpy(blob.data() + o_map, p->byte_map, 128);
-    if (added_bytes) memcpy(blob.data() + o_apool, p->added_pool, added_bytes);
-    if (p->n_added) memcpy(blob.data() + o_aoff, p->added_off, ((size_t)p->n_added + 1) * 4);
-
-    smt_unigram *tok = new smt_unigram();
-    tok->ctx = ctx;
-    hipError_t e = hipMalloc(&tok->d_table, total);
-    if (e == hipSuccess) e = hipMemcpy(tok->d_table, blob.data(), total, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (tok->d_table) (void)hipFree(tok->d_table);
-        delete tok;
-        set_error("unigram table upload (%zu bytes): %s", total, hipGetErrorString(e));
-        return SMT_E_NOMEM;
-    }
-    const uint8_t *base = static_cast<const uint8_t *>(tok->d_table);
+    std::unique_ptr<smt_unigram> tok(new smt_unigram(ctx));
     UgTable &T = tok->T;
-    T.slots = reinterpret_cast<const unsigned long long *>(base + o_slots);
-    T.ent = reinterpret_cast<const uint4 *>(base + o_ent);
-    T.score = reinterpret_cast<const double *>(base + o_score);
-    T.pool = base + o_pool;
-    T.map = base + o_map;
-    T.added_pool = base + o_apool;
-    T.added_off = reinterpret_cast<const uint32_t *>(base + o_aoff);
+    if ((rc = tok_added_first(p, T.added))) return rc;
+    const uint8_t *at[7];
+    if ((rc = tok_upload_table("unigram",
+                               {{table.slots.data(), table.slots.size() * 8},
+                                {table.ents.data(), table.ents.size() * sizeof(uint4)},
+                                {scores.data(), scores.size() * 8},
+                                {p->pool, p->n_pieces ? p->piece_off[p->n_pieces] : 0},
+                                {p->byte_map, 128},
+                                {p->added_pool, p->n_added ? p->added_off[p->n_added] : 0},
+                                {p->added_off, p->n_added ? ((size_t)p->n_added + 1) * 4 : 0}},
+                               &tok->d_table, at)))
+        return rc;
+    T.slots = reinterpret_cast<const unsigned long long *>(at[0]);
+    T.ent = reinterpret_cast<const uint4 *>(at[1]);
+    T.score = reinterpret_cast<const double *>(at[2]);
+    T.pool = at[3];
+    T.map = at[4];
+    T.added.pool = at[5];
+    T.added.off = reinterpret_cast<const uint32_t *>(at[6]);
     T.mask = table.mask;
     T.max_piece = max_piece;
-    T.n_added = p->n_added;
     T.unk = p->unk_id < 0 ? TOK_NONE : (uint32_t)p->unk_id;
     T.rlen = rlen;
     T.prepend = p->prepend;
@@ -353,61 +309,19 @@ try {
     T.r_score = r_known ? r_score : p->unk_score;
     T.unk_score = p->unk_score;
     T.r_state = r_state;
-    T.added_first[0] = added_first[0];
-    T.added_first[1] = added_first[1];
-    *out = tok;
+    *out = tok.release();
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
-void smt_unigram_destroy(smt_unigram *tok)
-{
-    if (!tok) return;
-    (void)hipSetDevice(tok->ctx->device);
-    (void)hipStreamSynchronize(tok->ctx->stream);
-    if (tok->d_table) (void)hipFree(tok->d_table);
-    tok_scratch_free(tok->S);
-    delete tok;
-}
+void smt_unigram_destroy(smt_unigram *tok) { tok_destroy(tok); }
 
 int smt_unigram_scan_device(smt_unigram *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev,
                             const uint32_t *line_len_dev, uint64_t n_lines, uint32_t keep_bytes, uint32_t max_tokens, int drop_unk,
                             uint32_t *counts_dev, uint8_t *flags_dev, uint32_t *n_flagged_dev)
 try {
     if (!tok) return tok_null_handle("smt_unigram_scan_device");
-    SMT_REQUIRE(n_flagged_dev != nullptr, "n_flagged_dev");
-    SMT_REQUIRE(n_lines == 0 || (line_begin_dev && line_len_dev && counts_dev && flags_dev), "null argument");
-    SMT_REQUIRE(text_bytes == 0 || text_dev != nullptr, "text_dev");
-    SMT_REQUIRE(text_bytes <= (1ull << 32), "at most 4 GiB of text per scan");
-    SMT_REQUIRE(n_lines <= (1ull << 32), "at most 2^32 lines per scan");
-    smt_ctx *ctx = tok->ctx;
-    int rc = bind_device(ctx);
-    if (rc) return rc;
-    tok->scanned = false;
-    const uint64_t n_slots = text_bytes + n_lines;   // every line has one slot more than bytes
-    if ((rc = tok_scratch_reserve(ctx, tok->S, n_slots, n_lines))) return rc;
-    hipStream_t st = ctx->stream;
-    SMT_HIP_CHECK(hipMemsetAsync(n_flagged_dev, 0, sizeof(uint32_t), st));
-    if (n_lines) SMT_HIP_CHECK(hipMemsetAsync(flags_dev, 0, n_lines, st));
-    if ((rc = tok_scratch_clear(ctx, tok->S, n_slots, n_lines))) return rc;
-    prof_begin(ctx, "tokenize");
-    if (n_lines) {
-        hipLaunchKernelGGL(ug_slot_begin_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, st, line_begin_dev, n_lines, tok->S.slot_begin());
-        SMT_HIP_CHECK(hipGetLastError());
-    }
-    if (n_lines && text_bytes) {
-        hipLaunchKernelGGL(ug_scan_kernel, dim3((unsigned)((text_bytes + UG_THREADS - 1) / UG_THREADS)), dim3(UG_THREADS), 0, st, tok->T, text_dev,
-                           text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, tok->S.d_ids_tmp, tok->S.raw_count(), flags_dev);
-        SMT_HIP_CHECK(hipGetLastError());
-    }
-    if ((rc = tok_line_counts(ctx, tok->S, n_lines, flags_dev, max_tokens, counts_dev, n_flagged_dev))) return rc;
-    prof_end(ctx, "tokenize");
-    tok->scanned = true;
-    tok->text_bytes = text_bytes;
-    tok->n_lines = n_lines;
-    tok->ids_bound = (keep_bytes ? std::min<uint64_t>(text_bytes, n_lines * (uint64_t)keep_bytes) : text_bytes) + n_lines;
-    tok->counts = counts_dev;
-    tok->flags = flags_dev;
-    return SMT_OK;
+    return tok_scan_device(tok, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, max_tokens, drop_unk, counts_dev, flags_dev,
+                           n_flagged_dev);
 } catch (...) { return smt::api_catch(); }
 
 int smt_unigram_emit_device(smt_unigram *tok, uint64_t n_lines, const uint64_t *patch_line_dev, const uint64_t *patch_off_dev,
@@ -415,24 +329,7 @@ int smt_unigram_emit_device(smt_unigram *tok, uint64_t n_lines, const uint64_t *
                             uint64_t *offsets_out_dev)
 try {
     if (!tok) return tok_null_handle("smt_unigram_emit_device");
-    SMT_REQUIRE(tok->scanned, "no scan to emit (smt_unigram_scan_device comes first)");
-    SMT_REQUIRE(n_lines == tok->n_lines, "n_lines differs from the scan's");
-    SMT_REQUIRE(offsets_out_dev != nullptr, "offsets_out_dev");
-    SMT_REQUIRE(n_patch == 0 || (patch_line_dev && patch_off_dev), "patch arrays");
-    SMT_REQUIRE(n_patch <= n_lines, "more patched lines than lines");
-    SMT_REQUIRE(n_patch_ids == 0 || (n_patch && patch_ids_dev), "patch ids");
-    SMT_REQUIRE(n_patch_ids <= (1ull << 40), "patch ids");
-    SMT_REQUIRE(ids_cap >= tok->ids_bound + n_patch_ids, "ids_cap is below the looked-at bytes of all lines + one per line + the patch ids");
-    SMT_REQUIRE(ids_cap == 0 || ids_out_dev != nullptr, "ids_out_dev");
-    smt_ctx *ctx = tok->ctx;
-    int rc = bind_device(ctx);
-    if (rc) return rc;
-    prof_begin(ctx, "tokenize_emit");
-    if ((rc = tok_pass2(ctx, tok->S, tok->text_bytes + n_lines, tok->S.slot_begin(), n_lines, tok->counts, tok->flags, patch_line_dev, patch_off_dev,
-                        patch_ids_dev, n_patch, n_patch_ids, ids_out_dev, ids_cap, offsets_out_dev)))
-        return rc;
-    prof_end(ctx, "tokenize_emit");
-    return SMT_OK;
+    return tok_emit_device(tok, n_lines, patch_line_dev, patch_off_dev, patch_ids_dev, n_patch, n_patch_ids, ids_out_dev, ids_cap, offsets_out_dev);
 } catch (...) { return smt::api_catch(); }
 
 int smt_unigram_tokenize(smt_unigram *tok, const char *text, const uint64_t *line_begin, const uint32_t *line_len, uint64_t n_lines,
@@ -440,58 +337,7 @@ int smt_unigram_tokenize(smt_unigram *tok, const char *text, const uint64_t *lin
                          uint8_t *flags_out)
 try {
     if (!tok) return tok_null_handle("smt_unigram_tokenize");
-    SMT_REQUIRE(offsets_out != nullptr, "offsets_out");
-    SMT_REQUIRE(n_lines == 0 || (line_begin && line_len), "null argument");
-    uint64_t text_bytes = 0, looked = 0;
-    for (uint64_t i = 0; i < n_lines; ++i) {
-        SMT_REQUIRE(line_begin[i] >= text_bytes, "lines must lie in line order and must not overlap");
-        text_bytes = line_begin[i] + line_len[i];
-        looked += keep_bytes && keep_bytes < line_len[i] ? keep_bytes : line_len[i];
-    }
-    SMT_REQUIRE(text_bytes == 0 || text != nullptr, "text");
-    SMT_REQUIRE(ids_cap >= looked + n_lines, "ids_cap is below the looked-at bytes of all lines + one per line");
-    SMT_REQUIRE(ids_cap == 0 || ids_out != nullptr, "ids_out");
-    smt_ctx *ctx = tok->ctx;
-    int rc = bind_device(ctx);
-    if (rc) return rc;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const uint64_t dev_cap = std::max<uint64_t>(ids_cap, text_bytes + n_lines);   // (the device form's bound)
-    const size_t o_begin = 0, o_off = o_begin + up16((size_t)n_lines * 8 + 8), o_ids = o_off + up16(((size_t)n_lines + 1) * 8),
-                 o_len = o_ids + up16((size_t)dev_cap * 4 + 4), o_counts = o_len + up16((size_t)n_lines * 4 + 4),
-                 o_nflag = o_counts + up16((size_t)n_lines * 4 + 4), o_flags = o_nflag + 16, o_text = o_flags + up16((size_t)n_lines + 1),
-                 total = o_text + up16((size_t)text_bytes + 1);
-    struct Temp { void *p = nullptr; ~Temp() { if (p) (void)hipFree(p); } } tmp;
-    {
-        const hipError_t e = hipMalloc(&tmp.p, total);
-        if (e != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc(%zu) for tokenizer staging: %s", total, hipGetErrorString(e)); return SMT_E_NOMEM; }
-    }
-    char *d = static_cast<char *>(tmp.p);
-    hipStream_t st = ctx->stream;
-    if (n_lines) {
-        SMT_HIP_CHECK(hipMemcpyAsync(d + o_begin, line_begin, (size_t)n_lines * 8, hipMemcpyHostToDevice, st));
-        SMT_HIP_CHECK(hipMemcpyAsync(d + o_len, line_len, (size_t)n_lines * 4, hipMemcpyHostToDevice, st));
-    }
-    if (text_bytes) SMT_HIP_CHECK(hipMemcpyAsync(d + o_text, text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
-    uint8_t *d_flags = reinterpret_cast<uint8_t *>(d + o_flags);
-    if ((rc = smt_unigram_scan_device(tok, reinterpret_cast<const uint8_t *>(d + o_text), text_bytes, reinterpret_cast<const uint64_t *>(d + o_begin),
-                                      reinterpret_cast<const uint32_t *>(d + o_len), n_lines, keep_bytes, max_tokens, drop_unk,
-                                      reinterpret_cast<uint32_t *>(d + o_counts), d_flags, reinterpret_cast<uint32_t *>(d + o_nflag)))) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    if ((rc = smt_unigram_emit_device(tok, n_lines, nullptr, nullptr, nullptr, 0, 0, reinterpret_cast<uint32_t *>(d + o_ids), dev_cap,
-                                      reinterpret_cast<uint64_t *>(d + o_off)))) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    SMT_HIP_CHECK(hipMemcpyAsync(offsets_out, d + o_off, ((size_t)n_lines + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (flags_out && n_lines) SMT_HIP_CHECK(hipMemcpyAsync(flags_out, d_flags, (size_t)n_lines, hipMemcpyDeviceToHost, st));
-    SMT_HIP_CHECK(hipStreamSynchronize(st));
-    const uint64_t n_ids = offsets_out[n_lines];
-    if (n_ids > ids_cap) { set_error("tokenizer produced more ids than ids_cap"); return SMT_E_HIP; }
-    if (n_ids) SMT_HIP_CHECK(hipMemcpy(ids_out, d + o_ids, (size_t)n_ids * 4, hipMemcpyDeviceToHost));
-    tok->scanned = false;   // (the staged line arrays go away with this call)
-    return SMT_OK;
+    return tok_tokenize(tok, text, line_begin, line_len, n_lines, keep_bytes, max_tokens, drop_unk, ids_out, ids_cap, offsets_out, flags_out);
 } catch (...) { return smt::api_catch(); }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // wordpiece_bytes.h -- the byte rules of a pure-ASCII line through BertNormalizer -> BertPreTokenizer -> WordPiece, stated once as a
 // 128-entry table (hf_tokenizer.cpp encode_ascii states the same rules as code; tests/wordpiece_ref.py restates them in Python).
-// Host-only: the device reads the table tokenize_kernels.hip uploads.
+// Host-only: the device reads the table wordpiece_kernels.hip uploads.
 #pragma once
 
 #include <cstdint>
@@ -32,9 +32,5 @@ inline void wordpiece_byte_table(uint32_t flags, uint8_t cls[128], uint8_t nrm[1
         nrm[c] = (uint8_t)(lower && c >= 'A' && c <= 'Z' ? c + 32 : c);
     }
 }
-
-// the hash the device table is built with and probed by: FNV-1a, 64 bits, carried byte by byte
-constexpr uint64_t WP_HASH_SEED = 0xcbf29ce484222325ull;
-constexpr uint64_t WP_HASH_MUL = 0x100000001b3ull;
 
 }  // namespace smt

@@ -1,6 +1,5 @@
-"""Register budgets of the kernels the device tokenizers share (tokenize_kernels.hip: pass 2), checked at build time (no GPU: hipcc
-cross-compiles and reports): every kernel of the file -- the per-line finish, the prefix sums, the emit and the patch kernels -- must
-show no spilled VGPR and no scratch.  The families' scans: test_wordpiece_resources.py, test_unigram_resources.py."""
+"""Register budgets of the WordPiece device tokenizer's kernel (wordpiece_kernels.hip), checked at build time (no GPU: hipcc
+cross-compiles and reports): every kernel of the file -- the scan -- must show no spilled VGPR and no scratch."""
 import os
 import re
 import subprocess
@@ -8,13 +7,13 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ["wp_lines_kernel", "wp_patch_counts_kernel", "wp_exscan_kernel", "wp_chunk_count_kernel", "wp_emit_kernel", "wp_patch_copy_kernel"]
+KERNELS = ["wp_scan_kernel"]
 
 
 @pytest.fixture(scope="module")
 def usage():
     r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-gpu-rdc", "-x", "hip", "--offload-device-only",
-                        "-c", os.path.join(ROOT, "semtools_amd", "csrc", "tokenize_kernels.hip"), "-o", "/dev/null",
+                        "-c", os.path.join(ROOT, "semtools_amd", "csrc", "wordpiece_kernels.hip"), "-o", "/dev/null",
                         "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out, name = {}, None
