@@ -145,6 +145,45 @@ __device__ __forceinline__ void wave_sum4_multi(const float (&in)[T][4], float (
     wave_sum4_multi_tail<T>(v, out);
 }
 
+// The trees of a GROUP (scan_pair_kernel): <c, c> and four query trees whose totals are wanted in ONE row of the wave each -- tree g
+// in row g, where lane 16 g + j tests row j of the chunk against query g -- so the four query trees share one tail.
+// wave_sum4_rows: the rotations by 4 and 8 of wave_sum4 on T trees, interleaved; every lane then holds its 16-lane row's sum r_R.
+template <int T>
+__device__ __forceinline__ void wave_sum4_rows(float (&v)[T])
+{
+#pragma unroll
+    for (int t = 0; t < T; ++t) v[t] += dpp_f<DPP_ROW_ROR4>(v[t]);
+#pragma unroll
+    for (int t = 0; t < T; ++t) v[t] += dpp_f<DPP_ROW_ROR8>(v[t]);
+}
+// wave_sum4_group_tail: cc and t0 .. t3 come from wave_sum4_rows.  v_permlane16_swap(t0, t1) and one add leave
+// t0.(r0 + r1) | t1.(r0 + r1) | t0.(r2 + r3) | t1.(r2 + r3) in the four rows, the same with (t2, t3); v_permlane32_swap of the two
+// results and one add leave tree g's (r0 + r1) + (r2 + r3) in row g: the additions of wave_sum4's tail, same operands, same order,
+// six instructions for the four trees and no copy.  cc keeps the replicating tail (every row needs <c, c>).  Returns: cc = what
+// wave_sum4 leaves, in every lane; t0 = in row g what wave_sum4 leaves for tree g.  t1 .. t3 are used up.  A tree that does not
+// exist (a group of fewer than four calls) may be any register: its row holds a sum nobody reads, the other rows never see it.
+// (One block of assembly so that the order is the one written: a swap may read a register two wait states after a VALU write at
+// the earliest, and the independent instructions of the other trees stand in those states -- two s_nop 0 are left.)
+__device__ __forceinline__ void wave_sum4_group_tail(float &cc, float &t0, float &t1, float &t2, float &t3)
+{
+    float w;
+    asm volatile("v_mov_b32 %5, %0\n\t"
+                 "s_nop 0\n\t"
+                 "v_permlane16_swap_b32_e32 %1, %2\n\t"
+                 "v_permlane16_swap_b32_e32 %3, %4\n\t"
+                 "v_permlane16_swap_b32_e32 %0, %5\n\t"
+                 "v_add_f32 %1, %1, %2\n\t"
+                 "v_add_f32 %3, %3, %4\n\t"
+                 "v_add_f32 %0, %0, %5\n\t"
+                 "v_mov_b32 %5, %0\n\t"
+                 "v_permlane32_swap_b32_e32 %1, %3\n\t"
+                 "s_nop 0\n\t"
+                 "v_permlane32_swap_b32_e32 %0, %5\n\t"
+                 "v_add_f32 %1, %1, %3\n\t"
+                 "v_add_f32 %0, %0, %5"
+                 : "+v"(cc), "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3), "=&v"(w));
+}
+
 // Integer sum over the 64 lanes, result in every lane.
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 {

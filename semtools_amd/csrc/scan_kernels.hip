@@ -580,14 +580,40 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
     auto claim = [&]() -> uint32_t { return deal_claim(s_next, lane); };
     // (row numbers are far below 2^63: the sign of the difference is a scalar compare, where "<" on 64 bits takes the VALU and a
     // vector register pair for n_virtual -- this kernel has none to spare)
-    auto in_corpus = [&](uint64_t v) -> bool { return (int64_t)(v - p.n_virtual) < 0; };
+    // (... and the sign is asked of the high word behind an empty asm: the compiler folds "high word < 0" back into a 64-bit signed
+    // compare, for which the scalar unit has no instruction -- a v_cmp_lt_i64 of two scalar values, three times per chunk)
+    auto in_corpus = [&](uint64_t v) -> bool {
+        uint32_t hi = (uint32_t)((v - p.n_virtual) >> 32);
+        asm("" : "+s"(hi));
+        return (int32_t)hi < 0;
+    };
+    // A chunk's rows are 1024 B apart and the load's immediate offset reaches 3072: a full chunk is ONE wave-uniform base address
+    // in scalar registers, the lane's 16 B offset and four immediates -- no vector instruction.  Only the chunk that crosses
+    // n_virtual clamps its rows one by one.  (The base passes through an empty asm: otherwise the compiler regroups the sum as
+    // (corpus + 16 lane) + row offset, hoists the bracket into a vector register pair and adds the rest on the VALU, per row.  The
+    // ragged chunk's rows pass through one too: loads of the same kind on both sides of a branch are joined behind it, and the
+    // joined load is back at one address per row.)
+    // (the global address space by name: a pointer made from an integer is a generic one, and its loads flat_load)
+    typedef const f32x4 __attribute__((address_space(1))) *global_rows_ptr;
+    auto row_ptr = [&](uint64_t v) -> global_rows_ptr {
+        uint64_t base = (uint64_t)(uintptr_t)p.corpus + v * 1024u;
+        asm volatile("" : "+s"(base));
+        return (global_rows_ptr)(uintptr_t)base + lane;
+    };
     auto issue_rows = [&](uint64_t v0, f32x4 (&c)[U]) {
+        if (in_corpus(v0 + (U - 1))) {   // (uniform)
+            const global_rows_ptr src = row_ptr(v0);
 #pragma unroll
-        for (int j = 0; j < U; ++j) {
-            uint64_t v = v0 + j;
-            if (!in_corpus(v)) v = p.n_virtual - 1;  // clamp (result discarded)
-            const f32x4 *src = reinterpret_cast<const f32x4 *>(p.corpus + (uint64_t)(uint32_t)v * 256) + lane;
-            c[j] = NT ? __builtin_nontemporal_load(src) : *src;
+            for (int j = 0; j < U; ++j) c[j] = NT ? __builtin_nontemporal_load(src + 64 * j) : src[64 * j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                uint64_t v = v0 + j;
+                if (!in_corpus(v)) v = p.n_virtual - 1;  // clamp (result discarded)
+                const global_rows_ptr src = row_ptr((uint64_t)(uint32_t)v);
+                c[j] = NT ? __builtin_nontemporal_load(src) : *src;
+                asm volatile("" : "+v"(c[j]));
+            }
         }
     };
     // the first rows are on their way before the decision is known: they are the same rows either way
@@ -641,15 +667,20 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
     // The group reducer.  SMT_REDUCE_CHUNK4 (scan_topk_kernel's, used here at first with the queries read from LDS) runs one basic block per query: an LDS read of the query image with its wait directly
     // behind it, one wave_sum4 tree alone (its DPP wait states padded with s_nop) and a candidate test of nested exec-mask regions,
     // four times per chunk although the four queries test the same four rows -- the grouped pass was bound by instruction issue, not
-    // by HBM.  Here the images are read at the top of the chunk, the trees run interleaved (device_utils.h wave_sum4_multi: <c, c>
-    // with the first two queries, then the other two; five trees at once do not fit 64 VGPRs), and ONE distance, ONE compare and ONE
+    // by HBM.  Here the images are read at the top of the chunk, the trees run interleaved (device_utils.h: the heads of wave_sum4_multi,
+    // <c, c> with the first two queries, then the other two -- five full trees at once do not fit 64 VGPRs --, then the row steps of
+    // all five and ONE tail for the four query trees, wave_sum4_group_tail, which leaves tree g's total in row g), and ONE distance, ONE compare and ONE
     // ballot serve the sixteen (row, query) pairs: lane 16 g + j takes query g and row j, against its query's threshold.  The
     // arithmetic is frozen: per-lane FMA expression, tree and dist_f32 are bit for bit those of scan_topk_kernel<1, 4>, because an
     // UNCERTAIN answer depends on which near-ties the f32 scan nominated.  That is why query g sits in ROW g of the wave (lanes
     // 16 g .. 16 g + 3) and not in quad g: the rotations by 4 and 8 of wave_sum4 add the four quads of a row in an order that
     // depends on the quad -- lanes 4 .. 7 hold (q1 + q0) + (q3 + q2) where lanes 0 .. 3, which the one-query loop reads, hold
     // (q0 + q3) + (q2 + q1), one rounding apart -- while the same position of another row holds the same bits.
-#define SMT_ROW_DOT(cj, qv) ((cj).x * (qv).x + (cj).y * (qv).y + (cj).z * (qv).z + (cj).w * (qv).w)
+    // (The per-lane expression spelled out as the compiler contracts "x qx + y qy + z qz + w qw" in the one-query loop -- y qy, then
+    // fused adds of x, z, w -- so that no vectoriser's regrouping can move a rounding; SMT_OPAQUE keeps a tree's value a scalar: left
+    // to itself the SLP vectoriser pairs the trees into v_pk_add_f32, which cannot carry a DPP operand.)
+#define SMT_ROW_DOT(cj, qv) __builtin_fmaf((cj).w, (qv).w, __builtin_fmaf((cj).z, (qv).z, __builtin_fmaf((cj).x, (qv).x, (cj).y * (qv).y)))
+#define SMT_OPAQUE(v) asm volatile("" : "+v"(v))
 #define SMT_GROUP_INSERT(n)                                                                                       \
     do {                                                                                                          \
         uint32_t m = (((n) < 2 ? pending_lo : pending_hi) >> (16 * ((n) & 1))) & 0xFu;                            \
@@ -682,7 +713,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
         /* <c, c> and the first two queries (a launch that serves one call reduces an image it does not use: a separate  */ \
         /* two-tree path costs registers, and the three interleaved trees cost what the two lone ones did).  One image   */ \
         /* at a time is live, read one query ahead of its products.                                                      */ \
-        float part[3][4], s[3];                                                                                   \
+        float part[3][4];                                                                                         \
         _Pragma("unroll") for (int j = 0; j < 4; ++j) part[0][j] = SMT_ROW_DOT((cq)[j], (cq)[j]);                 \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         const f32x4 qv1 = s_q[64 + lane];                                                                         \
@@ -691,24 +722,33 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
         _Pragma("unroll") for (int j = 0; j < 4; ++j) part[2][j] = SMT_ROW_DOT((cq)[j], qv1);                     \
         float v3[3];                                                                                              \
         wave_sum4_multi_head<3>(part, v3, lane);                                                                  \
+        SMT_OPAQUE(v3[0]); SMT_OPAQUE(v3[1]); SMT_OPAQUE(v3[2]);                                                  \
         /* twelve partial sums have become three: now there is room for the other two images and this lane's record, */ \
         /* which land behind the rest of the trees (the barriers keep the scheduler from moving the reads up)         */ \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         const f32x4 qv2 = s_q[128 + lane], qv3 = s_q[192 + lane];                                                 \
-        const f32x4 mine = *s_mine;   /* this lane's query: 1 / |q|, is it zero, threshold distance and row */    \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
-        wave_sum4_multi_tail<3>(v3, s);                                                                           \
-        const float b2 = s[0];                                                                                    \
-        float ab_mine = gq == 1 ? s[2] : s[1];                                                                    \
+        /* The heads of queries 2 and 3 if the pass serves them; with one or two calls those trees do not exist and the tail is */ \
+        /* fed registers that are there anyway (rows 2 and 3 are off).                                                          */ \
+        float v5[5] = {v3[0], v3[1], v3[2], v3[1], v3[2]};                                                        \
         if (n_on > 2) {                                                                                           \
-            float part2[2][4], s2[2];                                                                             \
+            float part2[2][4], v2[2];                                                                             \
             _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                       \
                 part2[0][j] = SMT_ROW_DOT((cq)[j], qv2);                                                          \
                 part2[1][j] = SMT_ROW_DOT((cq)[j], qv3);                                                          \
             }                                                                                                     \
-            wave_sum4_multi<2>(part2, s2, lane);                                                                  \
-            ab_mine = gq == 2 ? s2[0] : gq == 3 ? s2[1] : ab_mine;                                                \
+            wave_sum4_multi_head<2>(part2, v2, lane);                                                             \
+            SMT_OPAQUE(v2[0]); SMT_OPAQUE(v2[1]);                                                                 \
+            v5[3] = v2[0]; v5[4] = v2[1];                                                                         \
         }                                                                                                         \
+        /* five values are live: this lane's record lands behind the row steps, then ONE tail for the four query trees -- tree */ \
+        /* g's total comes out in row g, where this lane reads it                                                             */ \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        const f32x4 mine = *s_mine;   /* this lane's query: 1 / |q|, is it zero, threshold distance and row */    \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        wave_sum4_rows<5>(v5);                                                                                    \
+        wave_sum4_group_tail(v5[0], v5[1], v5[2], v5[3], v5[4]);                                                  \
+        const float b2 = v5[0], ab_mine = v5[1];                                                                  \
         const float d4 = dist_f32(ab_mine, b2, mine.x, mine.y != 0.0f);                                           \
         /* plain compares joined bitwise: no exec-mask region */                                                  \
         const uint32_t thr_r_mine = __float_as_uint(mine.w);                                                      \
@@ -746,19 +786,30 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
         ld[n] = __builtin_inff();
         lr[n] = 0xFFFFFFFFu;
     }
+    // The software pipeline of scan_topk_kernel -- the next chunk's rows are requested once the current chunk's have arrived and fly
+    // during its reduction -- without the register copy: the loop is unrolled by two and the two row buffers swap names.  The empty
+    // wait on `cur` stands where the copy stood: it keeps the request timing (ONE chunk in flight per wave; two, the ping-pong,
+    // measured slower), and the claims come in the same order, so every wave takes the chunks it took.
+#define SMT_GROUP_STEP(cur, nxt)                                                                                  \
+    do {                                                                                                          \
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"((cur)[0]), "+v"((cur)[1]), "+v"((cur)[2]), "+v"((cur)[3]) : : "memory"); \
+        if (in_corpus(v0n)) issue_rows(v0n, nxt);                                                                 \
+        const uint64_t v0nn = chunk_v0(claim());                                                                  \
+        /* (the chunk's real rows, asked the scalar way) */                                                       \
+        SMT_REDUCE_GROUP4(cur, (uint32_t)v0, in_corpus(v0 + (U - 1)) ? 4u : (uint32_t)(p.n_virtual - v0));        \
+        v0 = v0n;                                                                                                 \
+        v0n = v0nn;                                                                                               \
+    } while (0)
+    f32x4 cm[U];
     while (in_corpus(v0)) {
-        f32x4 c[U];
-#pragma unroll
-        for (int j = 0; j < U; ++j) c[j] = cn[j];
-        if (in_corpus(v0n)) issue_rows(v0n, cn);
-        const uint64_t v0nn = chunk_v0(claim());
-        const uint64_t left = p.n_virtual - v0;
-        SMT_REDUCE_GROUP4(c, (uint32_t)v0, left < 4 ? (uint32_t)left : 4u);
-        v0 = v0n;
-        v0n = v0nn;
+        SMT_GROUP_STEP(cn, cm);
+        if (!in_corpus(v0)) break;
+        SMT_GROUP_STEP(cm, cn);
     }
+#undef SMT_GROUP_STEP
 #undef SMT_REDUCE_GROUP4
 #undef SMT_GROUP_INSERT
+#undef SMT_OPAQUE
 #undef SMT_ROW_DOT
     __syncthreads();
     // a leader's block counts for the blocks of the calls it serves: the host's running totals count every launch
