@@ -792,6 +792,11 @@ int smt_debug_scan_pairs(smt_ctx *ctx, uint64_t *paired, uint64_t *alone, uint64
  * n x by_size[n - 1] is the number of calls once the pipeline is empty.  Synchronises. */
 int smt_debug_scan_groups(smt_ctx *ctx, uint64_t *by_size /* [4] */);
 
+/* The same with the passes of more than four calls (tuning key scan_take): by_size[n - 1] = scans that served n calls, n = 1..8.  The
+ * first four entries are those of smt_debug_scan_groups; the sum of n x by_size[n - 1] is the number of calls once the pipeline is
+ * empty, whichever kernel served them.  With scan_take > 3, absorbed <= 7 x paired.  Synchronises. */
+int smt_debug_scan_groups_wide(smt_ctx *ctx, uint64_t *by_size /* [8] */);
+
 /* Test hook for the SPMD error paths of multi-process groups: arms ONE injected failure with status `code` (an SMT_E_* value) on
  * THIS process's ranks; it fires at the next step of kind `where` and disarms.  The tests arm it on one rank of an n-rank group and
  * check that every rank returns `code` from the same call and that none is left waiting inside a collective.
@@ -901,7 +906,11 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *                        that cannot be taken ends it.  Each call's select, outputs and status word stay its own, so no answer
  *                        changes.  A launch bracketed by profiling events and its successor neither take nor are taken, and a
  *                        call made while the GPU keeps up runs the plain kernel.  1 = pairs only.  Switching it drains the
- *                        pipeline (default 3)
+ *                        pipeline.  The key sets the limit that scan_take sets, within the range of the four-call kernel
+ *   scan_take (0..7)     the same limit with the range of the eight-call kernel (default 7): above 3, a launch whose lists hold at
+ *                        most 32 candidates (top_k <= 24 at the default guard_band) in blocks of at most 512 threads runs
+ *                        scan_wide_kernel and looks for the calls two, four, ... fourteen steps later; any other launch runs as
+ *                        with scan_pair = 3.  Switching it drains the pipeline
  *   scan_pair_ring (64..4096, a power of two)  scan_pair: slots of the descriptor ring in use.  A call can be taken along while the
  *                        host is fewer calls ahead of the GPU than this; a call further ahead simply scans for itself.  Switching
  *                        it drains the pipeline (default 4096; tests use 64 to see slots reused)

@@ -184,6 +184,23 @@ __device__ __forceinline__ void wave_sum4_group_tail(float &cc, float &t0, float
                  : "+v"(cc), "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3), "=&v"(w));
 }
 
+// The same tail for four query trees whose <c, c> is already known (scan_wide_kernel's second four queries of a chunk): the
+// additions of wave_sum4_group_tail on t0 .. t3, same operands, same order, without the cc column.  t0 = in row g what wave_sum4
+// leaves for tree g; t1 .. t3 are used up.  (The callers' last VALU writes stand directly in front: two wait states before the
+// first swaps, and two between the adds and the swap that reads them.)
+__device__ __forceinline__ void wave_sum4_group_tail_queries(float &t0, float &t1, float &t2, float &t3)
+{
+    asm volatile("s_nop 1\n\t"
+                 "v_permlane16_swap_b32_e32 %0, %1\n\t"
+                 "v_permlane16_swap_b32_e32 %2, %3\n\t"
+                 "v_add_f32 %0, %0, %1\n\t"
+                 "v_add_f32 %2, %2, %3\n\t"
+                 "s_nop 1\n\t"
+                 "v_permlane32_swap_b32_e32 %0, %2\n\t"
+                 "v_add_f32 %0, %0, %2"
+                 : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3));
+}
+
 // Integer sum over the 64 lanes, result in every lane.
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 {

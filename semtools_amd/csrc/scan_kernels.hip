@@ -1,5 +1,6 @@
 // scan_kernels.hip -- K2 (single/few-query cosine scan + per-wave top-k'): scan_topk_kernel, the grouped
-// scan_pair_kernel with its host/device pairing protocol, and launch_scan_topk, which runs the passes of a call
+// scan_pair_kernel (up to four calls per pass) and scan_wide_kernel (up to eight) with their host/device pairing
+// protocol, and launch_scan_topk, which runs the passes of a call
 // and hands the block lists to the select stage (select.hip; optionally overlapped with the next scan: async
 // select).  The chunk table of range-filtered scans is built in range_tables.hip, the cross-shard top-k merge
 // lives in merge.hip, K4 (threshold mode) in threshold.hip.
@@ -476,7 +477,10 @@ __device__ __forceinline__ unsigned long long sys_load(const unsigned long long 
 
 // The deciding block: the slots of step + 2, + 4, + 6 -> how many of them this launch takes along (their queries and list sets
 // go into the record), the longest prefix that passes.  scan_pair_wait_us bounds the waits for all of them together.
-__device__ __forceinline__ unsigned int pair_decide(const ScanParams &p, const PairParams &pp, PairRecord *rec)
+// (FAMILY: which group-capable kernel the leader runs, in spare bits of PairSlot::kp_blocks -- a leader takes launches of its own
+// kernel only, their records are of its kind; RECS: the records of that kind)
+template <unsigned long long FAMILY, int RECS, class PP, class REC>
+__device__ __forceinline__ unsigned int group_decide(const ScanParams &p, const PP &pp, REC *rec)
 {
     const unsigned long long t0 = wall_clock64();
     unsigned int taken = 0;
@@ -497,15 +501,19 @@ __device__ __forceinline__ unsigned int pair_decide(const ScanParams &p, const P
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
         if (sys_load(&s->step) != want) break;   // the host was rewriting the slot (a ring's length ahead)
         const bool same = corpus == (unsigned long long)(uintptr_t)p.corpus && n_virtual == p.n_virtual &&
-                          kp_blocks == ((unsigned long long)p.kp | (unsigned long long)gridDim.x << 32);
+                          kp_blocks == ((unsigned long long)p.kp | FAMILY | (unsigned long long)gridDim.x << 32);
         if (!(absorbable && same)) break;
         flag_store(&rec->query[taken], query);
         flag_store(&rec->lists[taken], lists);
-        flag_store(&pp.recs[want % PAIR_RECS].state, (want << PAIR_SHIFT) | PAIR_ABSORBED);   // the mark
+        flag_store(&pp.recs[want % RECS].state, (want << PAIR_SHIFT) | PAIR_ABSORBED);   // the mark
         ++taken;
     }
     flag_store(&rec->taken, (unsigned long long)taken);
     return taken;
+}
+__device__ __forceinline__ unsigned int pair_decide(const ScanParams &p, const PairParams &pp, PairRecord *rec)
+{
+    return group_decide<0ull, PAIR_RECS>(p, pp, rec);
 }
 
 // (8 waves per SIMD = 64 VGPRs: what the select needs beside it, 2 x 64 + 4 x 96 = 512.  The four-query row loop with its queries
@@ -849,6 +857,384 @@ static inline size_t pair_smem_bytes(int threads)
     return (size_t)GROUP_MAX * (threads / 64) * 64 * sizeof(key_t64) + 256 + (size_t)GROUP_MAX * 1024 + 9 * 8 + 16;
 }
 
+// ------------------------------------------------------------- K2, groups of eight (tuning key scan_take)
+// scan_pair_kernel's protocol with a longer reach: a leader of step i reads the slots of steps i + 2 .. i + 14 and takes the longest
+// prefix that passes, up to seven calls, so one corpus pass serves up to eight.  A launch of this kernel says so in its slot
+// (WIDE_FAMILY in kp_blocks) and has a record of its own kind (WideRecord, an array of its own): a leader takes launches of its own
+// kernel only, and scan_pair_kernel refuses these by the same compare.  Marks, the own-record test, the bounded waits, the error
+// flag, the gate and the first rows requested before the decision is known are scan_pair_kernel's.
+// A chunk is reduced in two PHASES over the same sixteen row registers.  Phase A is SMT_REDUCE_GROUP4: <c, c> and queries 0 .. 3,
+// query g in row g of the wave.  Phase B, behind a wave-uniform n_on > 4, keeps <c, c> (one register) and runs queries 4 .. 7
+// through the same heads, row steps and tail (wave_sum4_group_tail_queries: the query trees' additions without the <c, c>
+// column), query g + 4 in row g -- so every query's nominations are bit for bit the one-query loop's (the row-not-quad rule).
+// A lane holds two 16-byte LDS records, its query's of phase A and of phase B.
+// Eight lists at a register pair each do not fit 64 VGPRs: a pair holds two, query g's in lanes 0 .. 31 and query g + 4's in lanes
+// 32 .. 63, so this kernel serves kp <= 32.  An insert works inside its half: the position is counted from that half of the ballot,
+// the shifted entry is taken only by the half's lanes above the position (lane 32 never takes lane 31's), the threshold is read
+// from lane kp - 1 of the half.  The first kp entries of a sorted list do not depend on how many are kept behind them.
+constexpr int WIDE_MAX = 8;       // calls one corpus pass of scan_wide_kernel serves: the leader's and up to seven taken along
+constexpr int WIDE_RECS = 64;     // records (reuse distance 64 > 14, as PAIR_RECS)
+constexpr unsigned long long WIDE_FAMILY = 1ull << 16;   // PairSlot::kp_blocks of a scan_wide_kernel launch (kp <= 64 below it, the grid above)
+struct WideRecord {   // 128 bytes
+    unsigned long long state;       // as PairRecord
+    unsigned long long taken;       // PAIR_PAIRED: calls taken along (1 .. WIDE_MAX - 1) ...
+    unsigned long long query[WIDE_MAX - 1], lists[WIDE_MAX - 1];   // ... and theirs
+};
+struct WideParams {
+    const PairSlot *ring;
+    WideRecord *recs;
+    unsigned long long *ctl;        // PairParams::ctl, and behind it [7..10] launches that served 5, 6, 7, 8 calls
+    unsigned int absorbable;
+    unsigned int max_take;          // tuning key scan_take: calls a launch may take along (1 .. WIDE_MAX - 1)
+    unsigned long long wait_ticks;
+    unsigned long long ring_mask;
+};
+
+template <bool NT>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) scan_wide_kernel(ScanParams p, WideParams pp)
+{
+    constexpr int U = 4;
+    constexpr int NQ = WIDE_MAX;
+    extern __shared__ unsigned char smem_raw[];
+    key_t64 *s_keys = reinterpret_cast<key_t64 *>(smem_raw);  // [NQ][waves][32]; during the row loop [waves][2][64] lane records
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int waves_per_block = blockDim.x >> 6;
+    unsigned int *s_valid = reinterpret_cast<unsigned int *>(s_keys + (size_t)NQ * waves_per_block * 32);   // [NQ][waves] (<= 256 B)
+    f32x4 *s_q = reinterpret_cast<f32x4 *>(s_valid + 64);                                // [NQ][64]: the queries, one image per block
+    unsigned long long *s_ctl = reinterpret_cast<unsigned long long *>(s_q + NQ * 64);    // [0] absorbed?, [1] calls served, [2] record state as read, [3..10] the list sets, own first
+    unsigned long long *s_qptr = s_ctl + 3 + NQ;                                         // [7] queries taken along
+    uint32_t *s_next = reinterpret_cast<uint32_t *>(s_qptr + (NQ - 1));                  // the block's next unclaimed chunk
+    const int kp = (int)p.kp;
+    WideRecord *rec = pp.recs + p.step % WIDE_RECS;
+    const unsigned long long tag = p.step << PAIR_SHIFT;
+
+    const int jj = lane & 3, gq = lane >> 4;         // this lane's row of the chunk and its query of each phase's four
+    // What a lane needs of ITS query of a phase -- 1 / |q|, "q is zero", the threshold (distance, row) -- lies in LDS as in
+    // scan_pair_kernel: two 16-byte records per lane, [wave][phase][64], in the key regions.  A query's norm goes straight into the
+    // records of its lanes (sixteen scalar registers for eight norms are not there either); a lane reads only what it wrote itself.
+    f32x4 *s_mine = reinterpret_cast<f32x4 *>(smem_raw) + wave * 128 + lane;
+    {
+        f32x4 r;   // a query that is not there: zero, nothing under its threshold
+        r.x = 0.0f;
+        r.y = 1.0f;
+        r.z = __builtin_inff();
+        r.w = __uint_as_float(0xFFFFFFFFu);
+        s_mine[0] = r;
+        s_mine[64] = r;
+    }
+#define SMT_QUERY_NORM(n, qn)                                                                                     \
+    do {                                                                                                          \
+        if (wave == 0) s_q[(n) * 64 + lane] = (qn);                                                               \
+        const float a2 = wave_sum((qn).x * (qn).x + (qn).y * (qn).y + (qn).z * (qn).z + (qn).w * (qn).w);         \
+        const bool qz = readlane_f(a2, 0) == 0.0f;                                                                \
+        const float rq = qz ? 0.0f : readlane_f(__frsqrt_rn(a2), 0);                                              \
+        if (gq == ((n) & 3)) { s_mine[64 * ((n) >> 2)].x = rq; s_mine[64 * ((n) >> 2)].y = qz ? 1.0f : 0.0f; }    \
+    } while (0)
+    {
+        const f32x4 q0 = reinterpret_cast<const f32x4 *>(p.queries)[lane];
+        SMT_QUERY_NORM(0, q0);
+    }
+
+    if (threadIdx.x == 0) {
+        *s_next = (uint32_t)waves_per_block;
+        const unsigned long long g = p.gate_open ? flag_load(p.gate) : 0ull;
+        unsigned long long cur = flag_load(&rec->state);
+        unsigned long long code = 0;
+        if (pp.absorbable && cur == (tag | PAIR_ABSORBED)) {
+            code = PAIR_ABSORBED;   // (marked by the leader, an earlier launch of this stream)
+        } else {
+            if ((cur >> PAIR_SHIFT) != p.step &&
+                __hip_atomic_compare_exchange_strong(&rec->state, &cur, tag | PAIR_DECIDING, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                     __HIP_MEMORY_SCOPE_AGENT)) {
+                const unsigned int taken = group_decide<WIDE_FAMILY, WIDE_RECS>(p, pp, rec);
+                cur = tag | (taken ? PAIR_PAIRED : PAIR_ALONE);
+                __hip_atomic_store(&rec->state, cur, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                (void)__hip_atomic_fetch_add(pp.ctl + (taken ? 1 : 2), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (taken) (void)__hip_atomic_fetch_add(pp.ctl + 3 + taken, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (g < p.gate_open) gate_wait(p);
+        }
+        s_ctl[0] = code;
+        s_ctl[2] = cur;
+        s_ctl[3] = (unsigned long long)(uintptr_t)p.block_lists;
+    }
+    __syncthreads();
+    if (uniform_u64(s_ctl[0]) == PAIR_ABSORBED) {
+        if (blockIdx.x == 0 && wave == 0 && lane == 0)
+            (void)__hip_atomic_fetch_add(pp.ctl + 3, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+
+    // (the chunk deal, the scalar row test and the scalar row addresses: see scan_pair_kernel)
+    auto chunk_v0 = [&](uint32_t t) -> uint64_t { return deal_chunk(t, waves_per_block) * U; };
+    auto claim = [&]() -> uint32_t { return deal_claim(s_next, lane); };
+    auto in_corpus = [&](uint64_t v) -> bool {
+        uint32_t hi = (uint32_t)((v - p.n_virtual) >> 32);
+        asm("" : "+s"(hi));
+        return (int32_t)hi < 0;
+    };
+    typedef const f32x4 __attribute__((address_space(1))) *global_rows_ptr;
+    auto row_ptr = [&](uint64_t v) -> global_rows_ptr {
+        uint64_t base = (uint64_t)(uintptr_t)p.corpus + v * 1024u;
+        asm volatile("" : "+s"(base));
+        return (global_rows_ptr)(uintptr_t)base + lane;
+    };
+    auto issue_rows = [&](uint64_t v0, f32x4 (&c)[U]) {
+        if (in_corpus(v0 + (U - 1))) {   // (uniform)
+            const global_rows_ptr src = row_ptr(v0);
+#pragma unroll
+            for (int j = 0; j < U; ++j) c[j] = NT ? __builtin_nontemporal_load(src + 64 * j) : src[64 * j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                uint64_t v = v0 + j;
+                if (!in_corpus(v)) v = p.n_virtual - 1;  // clamp (result discarded)
+                const global_rows_ptr src = row_ptr((uint64_t)(uint32_t)v);
+                c[j] = NT ? __builtin_nontemporal_load(src) : *src;
+                asm volatile("" : "+v"(c[j]));
+            }
+        }
+    };
+    // the first rows are on their way before the decision is known: they are the same rows either way
+    f32x4 cn[U];
+    uint64_t v0 = chunk_v0((uint32_t)wave);
+    uint64_t v0n = 0;
+    if (in_corpus(v0)) {
+        issue_rows(v0, cn);
+        v0n = chunk_v0(claim());
+    }
+
+    if (threadIdx.x == 0) {
+        unsigned long long cur = s_ctl[2];   // (this step's: the block has won the CAS and decided, or lost it)
+        if (cur == (tag | PAIR_DECIDING)) {   // bounded like flag_wait: a decision that never comes ends in an error code
+            const unsigned long long t0 = wall_clock64();
+            while ((cur = flag_load(&rec->state)) == (tag | PAIR_DECIDING)) {
+                __builtin_amdgcn_s_sleep(8);
+                if (flag_load(pp.ctl) != 0ull) break;
+                if (wall_clock64() - t0 > 200000000ull) { flag_store(pp.ctl, 1ull); break; }
+            }
+        }
+        unsigned long long served = 1;
+        if (cur == (tag | PAIR_PAIRED)) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            unsigned long long taken = flag_load(&rec->taken);
+            if (taken > (unsigned long long)(NQ - 1)) taken = NQ - 1;   // (never: the record is this step's)
+            for (unsigned long long j = 0; j < taken; ++j) {
+                s_qptr[j] = flag_load(&rec->query[j]);
+                s_ctl[4 + j] = flag_load(&rec->lists[j]);
+            }
+            served = 1 + taken;
+        } else if (cur != (tag | PAIR_ALONE)) {
+            flag_store(pp.ctl, 1ull);   // (a wait that ran out, or a record that is not this step's: alone, and the context reports it)
+        }
+        s_ctl[1] = served;
+    }
+    __syncthreads();
+    const int n_on = (int)(uint32_t)uniform_u64(s_ctl[1]);   // calls this pass serves, 1 .. NQ (an LDS read: told to be wave-uniform)
+    if (n_on > 1) {   // (uniform over the block)
+        // a phase's images are requested together, before its first norm is reduced: seven round trips one after the other would
+        // stand in front of the row loop (a slot without a call reads the first taken query again: its lanes never insert, on_mine
+        // below); a pass of four or fewer does not look at phase B's slots
+        f32x4 qn[NQ - 1];
+#pragma unroll
+        for (int n = 1; n < NQ; ++n)
+            if (n < 4 || n_on > 4) qn[n - 1] = reinterpret_cast<const f32x4 *>((uintptr_t)uniform_u64(s_qptr[n < n_on ? n - 1 : 0]))[lane];
+#pragma unroll
+        for (int n = 1; n < NQ; ++n)
+            if (n < 4 || n_on > 4) SMT_QUERY_NORM(n, qn[n - 1]);
+        __syncthreads();   // the images are wave 0's stores
+    }
+#undef SMT_QUERY_NORM
+
+#define SMT_ROW_DOT(cj, qv) __builtin_fmaf((cj).w, (qv).w, __builtin_fmaf((cj).z, (qv).z, __builtin_fmaf((cj).x, (qv).x, (cj).y * (qv).y)))
+#define SMT_OPAQUE(v) asm volatile("" : "+v"(v))
+    // list pair g, half h (query g + 4 h); D4: the phase's distances, lane 16 g + j holds row j against the query
+#define SMT_WIDE_INSERT(g, h, D4)                                                                                 \
+    do {                                                                                                          \
+        uint32_t m = (((g) < 2 ? pending_lo : pending_hi) >> (16 * ((g) & 1))) & 0xFu;                            \
+        while (m) {                                                                                               \
+            const int j = __builtin_ctz(m);                                                                       \
+            m &= m - 1;                                                                                           \
+            const float d = readlane_f(D4, 16 * (g) + j);                                                         \
+            const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)r_mine, j);                               \
+            const bool less = (ld[g] < d) || (ld[g] == d && lr[g] < r);                                           \
+            const uint64_t before = __ballot(less);                                                               \
+            const int pos = __popc((h) ? (uint32_t)(before >> 32) : (uint32_t)before);                            \
+            /* (the test of SMT_GROUP_INSERT: fewer than kp entries of this list before (d, r)) */                \
+            if (pos < kp) {                                                                                       \
+                const float sd = dpp_f<DPP_WAVE_SHR1>(ld[g]);                                                     \
+                const uint32_t sr = dpp_u<DPP_WAVE_SHR1>(lr[g]);                                                  \
+                /* (the lane's half and query asked of an opaque copy: as loop invariants they would be hoisted into a dozen */ \
+                /* scalar registers of lane masks, which the loop does not have)                                             */ \
+                int ln = lane;                                                                                    \
+                asm volatile("" : "+v"(ln));                                                                      \
+                const int at = ln - 32 * (h);   /* the lane's place in list g + 4 h: 0 .. 31 inside it */         \
+                if (at > pos && at < 32) { ld[g] = sd; lr[g] = sr; }                                              \
+                else if (at == pos) { ld[g] = d; lr[g] = r; }                                                     \
+                const float td = readlane_f(ld[g], 32 * (h) + kp - 1);                                            \
+                const uint32_t tr = (uint32_t)__builtin_amdgcn_readlane((int)lr[g], 32 * (h) + kp - 1);           \
+                if ((ln >> 4) == (g)) { s_mine[64 * (h)].z = td; s_mine[64 * (h)].w = __uint_as_float(tr); }      \
+            }                                                                                                     \
+        }                                                                                                         \
+    } while (0)
+#define SMT_WIDE_TEST_INSERT(h, MINE, ON, AB, D4)                                                                 \
+    do {                                                                                                          \
+        const float D4 = dist_f32(AB, b2, (MINE).x, (MINE).y != 0.0f);                                            \
+        const uint32_t thr_r_mine = __float_as_uint((MINE).w);                                                    \
+        const bool cand = ((ON) & valid_mine) & ((D4 < (MINE).z) | ((D4 == (MINE).z) & (r_mine < thr_r_mine)));   \
+        const uint64_t ballot = __ballot(cand);                                                                   \
+        const uint32_t pending_lo = (uint32_t)ballot & 0x000F000Fu, pending_hi = (uint32_t)(ballot >> 32) & 0x000F000Fu; \
+        if (pending_lo | pending_hi) {   /* query-major, rows ascending */                                        \
+            SMT_WIDE_INSERT(0, h, D4);                                                                            \
+            SMT_WIDE_INSERT(1, h, D4);                                                                            \
+            SMT_WIDE_INSERT(2, h, D4);                                                                            \
+            SMT_WIDE_INSERT(3, h, D4);                                                                            \
+        }                                                                                                         \
+    } while (0)
+    // phase A: SMT_REDUCE_GROUP4 of scan_pair_kernel, instruction for instruction up to the distance; phase B behind it
+#define SMT_REDUCE_WIDE(cq, rq4, VALID)                                                                           \
+    do {                                                                                                          \
+        const f32x4 qv0 = s_q[lane];                                                                              \
+        const bool valid_mine = (uint32_t)jj < (VALID);                                                           \
+        const uint32_t r_mine = (rq4) + (uint32_t)jj;                                                             \
+        float part[3][4];                                                                                         \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) part[0][j] = SMT_ROW_DOT((cq)[j], (cq)[j]);                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        const f32x4 qv1 = s_q[64 + lane];                                                                         \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) part[1][j] = SMT_ROW_DOT((cq)[j], qv0);                     \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) part[2][j] = SMT_ROW_DOT((cq)[j], qv1);                     \
+        float v3[3];                                                                                              \
+        wave_sum4_multi_head<3>(part, v3, lane);                                                                  \
+        SMT_OPAQUE(v3[0]); SMT_OPAQUE(v3[1]); SMT_OPAQUE(v3[2]);                                                  \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        const f32x4 qv2 = s_q[128 + lane], qv3 = s_q[192 + lane];                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        float v5[5] = {v3[0], v3[1], v3[2], v3[1], v3[2]};                                                        \
+        if (n_on > 2) {                                                                                           \
+            float part2[2][4], v2[2];                                                                             \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                       \
+                part2[0][j] = SMT_ROW_DOT((cq)[j], qv2);                                                          \
+                part2[1][j] = SMT_ROW_DOT((cq)[j], qv3);                                                          \
+            }                                                                                                     \
+            wave_sum4_multi_head<2>(part2, v2, lane);                                                             \
+            SMT_OPAQUE(v2[0]); SMT_OPAQUE(v2[1]);                                                                 \
+            v5[3] = v2[0]; v5[4] = v2[1];                                                                         \
+        }                                                                                                         \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        const f32x4 mine = s_mine[0];                                                                             \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        wave_sum4_rows<5>(v5);                                                                                    \
+        wave_sum4_group_tail(v5[0], v5[1], v5[2], v5[3], v5[4]);                                                  \
+        const float b2 = v5[0];                                                                                   \
+        SMT_WIDE_TEST_INSERT(0, mine, on_mine, v5[1], d4);                                                        \
+        if (n_on > 4) {                                                                                           \
+            __builtin_amdgcn_sched_barrier(0);                                                                    \
+            const f32x4 qv4 = s_q[256 + lane], qv5 = s_q[320 + lane];                                             \
+            float part4[2][4], w2[2];                                                                             \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                       \
+                part4[0][j] = SMT_ROW_DOT((cq)[j], qv4);                                                          \
+                part4[1][j] = SMT_ROW_DOT((cq)[j], qv5);                                                          \
+            }                                                                                                     \
+            wave_sum4_multi_head<2>(part4, w2, lane);                                                             \
+            SMT_OPAQUE(w2[0]); SMT_OPAQUE(w2[1]);                                                                 \
+            float v4[4] = {w2[0], w2[1], w2[0], w2[1]};                                                           \
+            if (n_on > 6) {                                                                                       \
+                __builtin_amdgcn_sched_barrier(0);                                                                \
+                const f32x4 qv6 = s_q[384 + lane], qv7 = s_q[448 + lane];                                         \
+                float part6[2][4], x2[2];                                                                         \
+                _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                   \
+                    part6[0][j] = SMT_ROW_DOT((cq)[j], qv6);                                                      \
+                    part6[1][j] = SMT_ROW_DOT((cq)[j], qv7);                                                      \
+                }                                                                                                 \
+                wave_sum4_multi_head<2>(part6, x2, lane);                                                         \
+                SMT_OPAQUE(x2[0]); SMT_OPAQUE(x2[1]);                                                             \
+                v4[2] = x2[0]; v4[3] = x2[1];                                                                     \
+            }                                                                                                     \
+            __builtin_amdgcn_sched_barrier(0);                                                                    \
+            const f32x4 mine_b = s_mine[64];                                                                      \
+            __builtin_amdgcn_sched_barrier(0);                                                                    \
+            wave_sum4_rows<4>(v4);                                                                                \
+            wave_sum4_group_tail_queries(v4[0], v4[1], v4[2], v4[3]);                                             \
+            SMT_WIDE_TEST_INSERT(1, mine_b, on_mine_b, v4[0], d4b);                                               \
+        }                                                                                                         \
+    } while (0)
+    const bool on_mine = gq < n_on, on_mine_b = gq + 4 < n_on;   // (an absent query has thr = +inf and must never insert)
+    float ld[4];
+    uint32_t lr[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        ld[g] = __builtin_inff();
+        lr[g] = 0xFFFFFFFFu;
+    }
+    // (the two-buffer pipeline of scan_pair_kernel: one chunk in flight per wave, the claims in the same order)
+#define SMT_WIDE_STEP(cur, nxt)                                                                                   \
+    do {                                                                                                          \
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"((cur)[0]), "+v"((cur)[1]), "+v"((cur)[2]), "+v"((cur)[3]) : : "memory"); \
+        if (in_corpus(v0n)) issue_rows(v0n, nxt);                                                                 \
+        const uint64_t v0nn = chunk_v0(claim());                                                                  \
+        SMT_REDUCE_WIDE(cur, (uint32_t)v0, in_corpus(v0 + (U - 1)) ? 4u : (uint32_t)(p.n_virtual - v0));          \
+        v0 = v0n;                                                                                                 \
+        v0n = v0nn;                                                                                               \
+    } while (0)
+    f32x4 cm[U];
+    while (in_corpus(v0)) {
+        SMT_WIDE_STEP(cn, cm);
+        if (!in_corpus(v0)) break;
+        SMT_WIDE_STEP(cm, cn);
+    }
+#undef SMT_WIDE_STEP
+#undef SMT_REDUCE_WIDE
+#undef SMT_WIDE_TEST_INSERT
+#undef SMT_WIDE_INSERT
+#undef SMT_OPAQUE
+#undef SMT_ROW_DOT
+    __syncthreads();
+    if (wave == 0 && lane == 0) (void)__hip_atomic_fetch_add(p.gate, (unsigned long long)n_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // block merge, two queries at a time: the lower half of the wave ranks list g, the upper half list g + 4
+    const int half = lane >> 5, l5 = lane & 31;      // this lane's list of a register pair and its place in it
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        if (g >= n_on) break;
+        const bool have = l5 < kp && lr[g] != 0xFFFFFFFFu;
+        s_keys[((size_t)(g + 4 * half) * waves_per_block + wave) * 32 + l5] = have ? make_key(ld[g], lr[g]) : KEY_PAD;
+        const uint64_t kept = __ballot(have);
+        if (lane == 0) {
+            s_valid[g * waves_per_block + wave] = (unsigned int)__popc((uint32_t)kept);
+            s_valid[(g + 4) * waves_per_block + wave] = (unsigned int)__popc((uint32_t)(kept >> 32));
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        if (g >= n_on) break;
+        const int n = g + 4 * half;
+        if (n >= n_on) continue;   // (the upper half of a pass that does not serve query g + 4)
+        const key_t64 *keys_n = s_keys + (size_t)n * waves_per_block * 32;
+        key_t64 *out = reinterpret_cast<key_t64 *>((uintptr_t)s_ctl[3 + n]) + (size_t)blockIdx.x * kp;
+        const key_t64 mine = keys_n[wave * 32 + l5];
+        if (mine != KEY_PAD) {
+            int rank = 0;
+            for (int w = 0; w < waves_per_block; ++w)
+                for (int i = 0; i < kp; ++i) rank += (keys_n[w * 32 + i] < mine) ? 1 : 0;
+            if (rank < kp) out[rank] = mine;
+        }
+        if (wave == 0 && l5 < kp) {   // the padding: slots [valid keys of the block, kp)
+            unsigned int total = 0;
+            for (int w = 0; w < waves_per_block; ++w) total += s_valid[n * waves_per_block + w];
+            if ((unsigned int)l5 >= total) out[l5] = KEY_PAD;
+        }
+    }
+}
+// dynamic LDS of a scan_wide_kernel launch: the eight key regions (32 keys a wave), the waves' key counts, the query images, the
+// block's control words
+static inline size_t wide_smem_bytes(int threads)
+{
+    return (size_t)WIDE_MAX * (threads / 64) * 32 * sizeof(key_t64) + 256 + (size_t)WIDE_MAX * 1024 + 18 * 8 + 16;
+}
+
 // ------------------------------------------------------------------ launchers
 static inline uint32_t candidates_per_list(const smt_ctx *ctx, uint32_t k_out)
 {
@@ -876,6 +1262,7 @@ struct ScanPlan {
     hipStream_t st = nullptr;
     unsigned long long gate_open = 0, gate_ticks = 0;
     bool may_pair = false;    // scan_pair: this launch runs scan_pair_kernel (it looks for a partner, and may find itself absorbed)
+    bool wide = false;        // scan_take: ... or scan_wide_kernel, when the limit exceeds what scan_pair_kernel serves
     unsigned int absorbable = 0;
 };
 
@@ -905,6 +1292,8 @@ static ScanPlan plan_scan(const smt_ctx *ctx, const ScanArgs &a)
     // scan_pair: the launch may share its corpus pass with the call two steps later, or be absorbed by the one two steps earlier
     // (scan_pair_kernel).  Not with wave stamps (profiling of the plain kernel).
     pl.pair = pl.overlap && ctx->tune.scan_pair && pl.U == 4 && ctx->tune.scan_debug_ptr == 0;
+    // more than three calls taken along: scan_wide_kernel, whose half-wave lists hold 32 keys and whose LDS is sized for 8 waves
+    pl.wide = pl.pair && ctx->tune.scan_pair > GROUP_MAX - 1 && pl.kp <= 32 && pl.threads <= 512;
     pl.st = ctx->stream;
     return pl;
 }
@@ -922,12 +1311,12 @@ static int enter_pipeline(smt_ctx *ctx, const ScanArgs &a, ScanPlan &pl)
     const size_t list_bytes = pl.overlap ? (size_t)SEL_MAX_LISTS * 64 * sizeof(key_t64)
                                          : (((size_t)a.nq * pl.blocks * pl.kp * sizeof(key_t64)) + 255) & ~(size_t)255;
     const size_t table_bytes = pl.filtered ? (size_t)pl.n_chunks * sizeof(uint64_t) : 0;
-    // (scan_overlap: a ring of eight sets, step & 7.  A leading scan of step i fills the sets of steps i, i + 2, i + 4 and i + 6, all
-    // on its own stream, and set s is shared by the steps s, s +- 8, s +- 16 ...: the last readers of the four sets it writes are the
-    // selects of steps i - 8, i - 6, i - 4 and i - 2, launched on the SAME stream before scan i, so stream order alone has them
-    // finished.  The other stream's steps have the other parity and the other four sets.  With fewer sets the scan of step i
-    // would write the set of step i + 6 into one that a select of the other stream, ordered against nothing here, may be reading.)
-    const size_t n_sets = pl.overlap ? 8 : 2;
+    // (scan_overlap: a ring of sixteen sets, step & 15.  A leading scan of step i fills the sets of steps i, i + 2, ... i + 14, all
+    // on its own stream, and set s is shared by the steps s, s +- 16, s +- 32 ...: the last readers of the eight sets it writes are the
+    // selects of steps i - 16, i - 14, ... i - 2, launched on the SAME stream before scan i, so stream order alone has them
+    // finished.  The other stream's steps have the other parity and the other eight sets.  With fewer sets the scan of step i
+    // would write the set of step i + 14 into one that a select of the other stream, ordered against nothing here, may be reading.)
+    const size_t n_sets = pl.overlap ? 2 * WIDE_MAX : 2;
     if ((rc = ensure_scratch(ctx, n_sets * list_bytes + table_bytes))) return rc;
     pl.lists = reinterpret_cast<key_t64 *>(reinterpret_cast<char *>(ctx->d_scratch) + (pl.step & (n_sets - 1)) * list_bytes);
     pl.table = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(ctx->d_scratch) + n_sets * list_bytes);
@@ -1053,33 +1442,48 @@ int ensure_pair(smt_ctx *ctx)
     if (ctx->h_pair_ring) return SMT_OK;
     SMT_HIP_CHECK(hipMalloc(&ctx->d_pair_recs, PAIR_RECS * sizeof(PairRecord)));
     SMT_HIP_CHECK(hipMemset(ctx->d_pair_recs, 0, PAIR_RECS * sizeof(PairRecord)));
+    SMT_HIP_CHECK(hipMalloc(&ctx->d_wide_recs, WIDE_RECS * sizeof(WideRecord)));
+    SMT_HIP_CHECK(hipMemset(ctx->d_wide_recs, 0, WIDE_RECS * sizeof(WideRecord)));
     SMT_HIP_CHECK(hipHostMalloc(&ctx->h_pair_ring, PAIR_RING * sizeof(PairSlot), hipHostMallocDefault));
     memset(ctx->h_pair_ring, 0, PAIR_RING * sizeof(PairSlot));
     return SMT_OK;
 }
 
-// Publishes this step's slot (what a predecessor needs to take the call along), then launches the pair-capable one-query scan.
+// Publishes this step's slot (what a predecessor needs to take the call along), then launches the group-capable one-query scan:
+// scan_pair_kernel, or scan_wide_kernel (pl.wide).
+template <class PP>
+static void group_params(const smt_ctx *ctx, const ScanPlan &pl, PP &pp, int max_take)
+{
+    pp.absorbable = pl.absorbable;
+    pp.ring_mask = (unsigned long long)std::min(ctx->tune.scan_pair_ring, PAIR_RING) - 1;
+    pp.ring = reinterpret_cast<const PairSlot *>(ctx->h_pair_ring);
+    pp.ctl = ctx->d_gate + 1;
+    pp.wait_ticks = (unsigned long long)ctx->tune.scan_pair_wait_us * 100ull;
+    pp.max_take = (unsigned int)std::min(std::max(ctx->tune.scan_pair, 1), max_take);
+}
 static int launch_scan_pair(smt_ctx *ctx, const ScanParams &p, const ScanPlan &pl)
 {
     PairParams pp{};
-    pp.absorbable = pl.absorbable;
-    pp.ring_mask = (unsigned long long)std::min(ctx->tune.scan_pair_ring, PAIR_RING) - 1;
+    WideParams wp{};
+    group_params(ctx, pl, pp, GROUP_MAX - 1);
+    group_params(ctx, pl, wp, WIDE_MAX - 1);
     PairSlot *slot = reinterpret_cast<PairSlot *>(ctx->h_pair_ring) + (p.step & pp.ring_mask);
     __atomic_store_n(&slot->step, 0ull, __ATOMIC_SEQ_CST);   // (a reader of the slot's previous use fails its second check)
     slot->corpus = (unsigned long long)(uintptr_t)p.corpus;
     slot->n_virtual = p.n_virtual;
     slot->query = (unsigned long long)(uintptr_t)p.queries;
     slot->lists = (unsigned long long)(uintptr_t)p.block_lists;
-    slot->kp_blocks = (unsigned long long)p.kp | (unsigned long long)pl.blocks << 32;
+    slot->kp_blocks = (unsigned long long)p.kp | (pl.wide ? WIDE_FAMILY : 0ull) | (unsigned long long)pl.blocks << 32;
     slot->absorbable = pp.absorbable;
     __atomic_store_n(&slot->step, p.step, __ATOMIC_RELEASE);
-    pp.ring = reinterpret_cast<const PairSlot *>(ctx->h_pair_ring);
     pp.recs = reinterpret_cast<PairRecord *>(ctx->d_pair_recs);
-    pp.ctl = ctx->d_gate + 1;
-    pp.wait_ticks = (unsigned long long)ctx->tune.scan_pair_wait_us * 100ull;
-    pp.max_take = (unsigned int)std::min(std::max(ctx->tune.scan_pair, 1), GROUP_MAX - 1);
-    hipLaunchKernelGGL(pl.nt ? scan_pair_kernel<true> : scan_pair_kernel<false>, dim3(pl.blocks), dim3(pl.threads),
-                       pair_smem_bytes(pl.threads), pl.st, p, pp);
+    wp.recs = reinterpret_cast<WideRecord *>(ctx->d_wide_recs);
+    if (pl.wide)
+        hipLaunchKernelGGL(pl.nt ? scan_wide_kernel<true> : scan_wide_kernel<false>, dim3(pl.blocks), dim3(pl.threads),
+                           wide_smem_bytes(pl.threads), pl.st, p, wp);
+    else
+        hipLaunchKernelGGL(pl.nt ? scan_pair_kernel<true> : scan_pair_kernel<false>, dim3(pl.blocks), dim3(pl.threads),
+                           pair_smem_bytes(pl.threads), pl.st, p, pp);
     SMT_HIP_CHECK(hipGetLastError());
     ctx->pair_live = true;
     return SMT_OK;

@@ -1,7 +1,7 @@
-"""A/B of grouped one-query scans (tuning key scan_pair = 0 / 1 / 2 / 3 later calls taken along; scan_gate_pct swept in group mode)
+"""A/B of grouped one-query scans (tuning key scan_take = 0 .. 7 later calls taken along; scan_gate_pct swept at the limit of seven)
 in ONE process on one box, settings alternated: the wall time per pipelined step (async select, scan_overlap, no events) over two
 1 M-row corpora used in turn (as bench.py) and over one corpus alone, how many launches took calls along (smt_debug_scan_pairs) and
-how many calls each launch served (smt_debug_scan_groups), and the answers and status words compared with scan_pair = 0.  "sync":
+how many calls each launch served (smt_debug_scan_groups_wide, eight entries), and the answers and status words compared with scan_take = 0.  "sync":
 one call, synchronise, repeat -- the latency of a call when the GPU is not behind, where nothing can be taken along and the
 group-capable kernel must cost what the plain one does.  python tools/ab_pairing.py [rows] [rounds] [out.json]"""
 import json, os, sys, time
@@ -29,21 +29,21 @@ def run(n, corpora, sync_each=False):
     ctx.synchronize()
 ctx.set_tuning("prof_select", 0)
 ctx.set_tuning("async_select", 1)
-# (scan_pair, scan_gate_pct, scan_pair_wait_us): the four group limits at the shipped gate, then the gate swept at the limit of three
-settings = [(0, 50, 0), (1, 50, 0), (2, 50, 0), (3, 50, 0), (3, 0, 0), (2, 0, 0), (3, 5, 0), (3, 10, 0), (3, 25, 0), (3, 65, 0), (3, 75, 0), (3, 90, 0), (3, 100, 0), (1, 75, 0)]
-loads = {"two_corpora": (both, False, settings), "one_corpus": (both[:1], False, settings), "sync": (both, True, settings[:4])}
+# (scan_take, scan_gate_pct, scan_pair_wait_us): the eight group limits at the shipped gate, then the gate swept at the limit of seven
+settings = [(take, 50, 0) for take in range(8)] + [(7, 0, 0), (7, 25, 0), (7, 75, 0), (7, 100, 0)]
+loads = {"two_corpora": (both, False, settings), "one_corpus": (both[:1], False, settings), "sync": (both, True, settings[:8:7])}
 res, ref = {}, {}
 for r in range(rounds):
     for load, (corpora, sync_each, todo) in loads.items():
         for pair, gate, wait_us in todo:
-            ctx.set_tuning("scan_pair", pair)
+            ctx.set_tuning("scan_take", pair)
             ctx.set_tuning("scan_gate_pct", gate)
             ctx.set_tuning("scan_pair_wait_us", wait_us)
             run(300, corpora, sync_each)
             st.fill_(7)
-            c0, g0 = ctx.scan_pairs(), ctx.scan_groups()
+            c0, g0 = ctx.scan_pairs(), ctx.scan_groups_wide()
             t0 = time.perf_counter(); run(2000, corpora, sync_each); step = (time.perf_counter() - t0) / 2000 * 1e6
-            c1, g1 = ctx.scan_pairs(), ctx.scan_groups()
+            c1, g1 = ctx.scan_pairs(), ctx.scan_groups_wide()
             ans = out.cpu().numpy().copy()
             ref.setdefault(load, ans)
             same = bool((ans == ref[load]).all()) and bool((st[:2000].cpu() == 0).all())
