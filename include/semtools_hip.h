@@ -207,6 +207,45 @@ typedef struct smt_wordpiece_params {
 int smt_wordpiece_create(smt_ctx *ctx, const smt_wordpiece_params *p, smt_wordpiece **out);
 void smt_wordpiece_destroy(smt_wordpiece *tok);
 
+/* The UTF-8 form of the same tokenizer (wordpiece_utf8_kernels.hip, DESIGN 4.9 "WordPiece over UTF-8 lines"): the handle and the
+ * calls below are shared, only pass 1 differs.  BertNormalizer and BertPreTokenizer act on one code point without context, so the
+ * caller states what every code point >= U+0080 becomes: n sorted, disjoint ranges first[i] .. last[i] (>= U+0080, <= U+10FFFF),
+ * each with a class and an output, out_pool[out_off[i], out_off[i + 1]), valid UTF-8.  An empty output on a class other than DROPPED
+ * and FLAG means "itself" (one character); a range with an explicit output is a single code point.  A code point in no range is
+ * FLAG.  ASCII keeps coming from p->flags.
+ *   ORDINARY  every output character is a character of a word (there may be several: a Hangul syllable becomes its jamo)
+ *   SPACE     white space: ends a word, yields nothing (an explicit output is not used)
+ *   ALONE     the output is ONE character that is a word by itself: punctuation, a CJK character (given WITHOUT the two spaces)
+ *   DROPPED   no output; the neighbours join
+ *   FLAG      the line is left to the caller
+ * An output may not hold more characters than the UTF-8 form of `first` has bytes: a word's tokens then fit into the word's own
+ * bytes, as in the ASCII form.  All pieces enter the table, those with bytes >= 0x80 too; max_input_chars_per_word counts
+ * normalised CHARACTERS; the continuing prefix and the added tokens stay pure ASCII.
+ * A line is FLAGGED for an added token standing in it, a FLAG code point, malformed UTF-8 (a lone continuation byte, a sequence cut
+ * by the line's end, an overlong form, a surrogate, a value above U+10FFFF), or ANY byte >= 0x80 within the looked-at bytes of a line
+ * that is longer than keep_bytes: the host layer cuts such a line by characters, the kernel by bytes, and the two agree only while
+ * the looked-at part is ASCII.  Malformed input ends in a flag, never in an access outside the text.
+ * SMT_E_INVALID, before anything is uploaded, for ranges out of order or overlapping, offsets that decrease, an unknown class, an
+ * output that is not UTF-8 or too long, an explicit output on a range of several code points or on DROPPED / FLAG, an ALONE output
+ * of more than one character, a non-ASCII added token.  Everything is copied. */
+#define SMT_WP_CP_ORDINARY 0u
+#define SMT_WP_CP_SPACE 1u
+#define SMT_WP_CP_ALONE 2u
+#define SMT_WP_CP_DROPPED 3u
+#define SMT_WP_CP_FLAG 4u
+typedef struct smt_wordpiece_codepoints {
+    const uint32_t *first;   /* [n] */
+    const uint32_t *last;    /* [n] */
+    const uint8_t *cls;      /* [n] SMT_WP_CP_* */
+    const char *out_pool;
+    const uint32_t *out_off; /* [n + 1] */
+    uint64_t n;
+} smt_wordpiece_codepoints;
+int smt_wordpiece_create_utf8(smt_ctx *ctx, const smt_wordpiece_params *p, const smt_wordpiece_codepoints *cp, smt_wordpiece **out);
+/* what the handle holds on the device: all of its table in bytes, the code-point part of it (page index + distinct pages + outputs;
+ * 0 for the ASCII form), and which form it is.  Any out may be NULL. */
+int smt_wordpiece_info(const smt_wordpiece *tok, uint64_t *table_bytes, uint64_t *codepoint_bytes, int *utf8);
+
 /* Pass 1: tokenize.  text_dev: text_bytes bytes; line i is [line_begin[i], line_begin[i] + line_len[i]) of them.  The lines lie in
  * line order and do not overlap (line_begin[i] + line_len[i] <= line_begin[i + 1]; gaps and no separators are both fine) and end
  * inside the text: the work is dealt by text position, so the host form checks this, and the device form trusts it -- a list that

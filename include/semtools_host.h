@@ -132,6 +132,12 @@ int smt_host_tokenizer_info(smt_host_tokenizer *tok, uint64_t *vocab_size, int64
  * smt_wordpiece on `ctx`, to be freed with smt_wordpiece_destroy.  SMT_E_UNSUPPORTED for a tokenizer whose pure-ASCII lines are not
  * BertNormalizer (or none) -> BertPreTokenizer -> WordPiece: Unigram models, other pre-tokenizers. */
 int smt_host_tokenizer_to_device(smt_host_tokenizer *tok, smt_ctx *ctx, smt_wordpiece **out);
+/* ... and its UTF-8 form (smt_wordpiece_create_utf8): the same vocabulary, and what every code point U+0080 .. U+10FFFF becomes under the
+ * tokenizer's own normalizer and pre-tokenizer, as ranges.  A code point is FLAG when its output mixes classes, keeps a character of
+ * non-zero canonical combining class (NFD's reordering would depend on the neighbours), or holds more characters than the code
+ * point has bytes.  SMT_E_UNSUPPORTED on the terms of smt_host_tokenizer_to_device, and when an added token matched on the raw text
+ * holds a non-ASCII byte. */
+int smt_host_tokenizer_to_device_utf8(smt_host_tokenizer *tok, smt_ctx *ctx, smt_wordpiece **out);
 /* ... and of a Unigram tokenizer: an smt_unigram on `ctx`, to be freed with smt_unigram_destroy.  SMT_E_UNSUPPORTED unless the model
  * is Unigram behind exactly one Metaspace (split, a replacement character >= U+0080) and its normalizer, if any, is built only of
  * Lowercase / NFD / StripAccents / BertNormalizer (each acts on an ASCII character without context). */
@@ -141,6 +147,8 @@ int smt_host_tokenizer_to_device_unigram(smt_host_tokenizer *tok, smt_ctx *ctx, 
  * tokenizer has a device form (smt_host_tokenizer_to_device), the group has one rank and the full table is resident (or about to be:
  * calls of more than 32768 lines); lines the kernel flags are tokenized by the host tokenizer and spliced in; everything else keeps
  * the host path.  Rows, search output and the workspace's cached ids are bit-identical with the switch on and off.
+ * on = 2 (SEMTOOLS_DEVICE_TOKENIZER=2) chooses the UTF-8 form of a WordPiece tokenizer (smt_host_tokenizer_to_device_utf8) where it has
+ * one: lines with valid UTF-8 of covered code points stay on the device.  Otherwise 2 chooses what 1 chooses.
  * smt_host_debug_device_tokenized (test hook): lines of this model tokenized on the device so far. */
 int smt_host_model_set_device_tokenizer(smt_host_model *model, int on);
 int smt_host_debug_device_tokenized(smt_host_model *model, uint64_t *lines);

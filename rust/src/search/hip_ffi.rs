@@ -48,6 +48,18 @@ pub struct SmtWordpieceParams {
     pub n_added: u32,
 }
 
+/// what every code point >= U+0080 becomes, for the UTF-8 form of the device tokenizer (smt_wordpiece_create_utf8 copies everything)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SmtWordpieceCodepoints {
+    pub first: *const u32,
+    pub last: *const u32,
+    pub cls: *const u8,
+    pub out_pool: *const c_char,
+    pub out_off: *const u32,
+    pub n: u64,
+}
+
 /// a Unigram vocabulary, Metaspace's settings and the byte table for the device tokenizer (smt_unigram_create copies everything)
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -84,6 +96,11 @@ pub const SMT_TABLE_I8: c_int = 2;
 pub const SMT_WP_NORMALIZER: c_int = 1;
 pub const SMT_WP_CLEAN_TEXT: c_int = 2;
 pub const SMT_WP_LOWERCASE: c_int = 4;
+pub const SMT_WP_CP_ORDINARY: c_int = 0;
+pub const SMT_WP_CP_SPACE: c_int = 1;
+pub const SMT_WP_CP_ALONE: c_int = 2;
+pub const SMT_WP_CP_DROPPED: c_int = 3;
+pub const SMT_WP_CP_FLAG: c_int = 4;
 pub const SMT_UG_MAX_WORD: c_int = 64;
 pub const SMT_STATUS_PROVED: c_int = 0;
 pub const SMT_STATUS_UNCERTAIN: c_int = 1;
@@ -238,6 +255,18 @@ extern "C" {
         out: *mut *mut SmtWordpiece,
     ) -> c_int;
     pub fn smt_wordpiece_destroy(tok: *mut SmtWordpiece);
+    pub fn smt_wordpiece_create_utf8(
+        ctx: *mut SmtCtx,
+        p: *const SmtWordpieceParams,
+        cp: *const SmtWordpieceCodepoints,
+        out: *mut *mut SmtWordpiece,
+    ) -> c_int;
+    pub fn smt_wordpiece_info(
+        tok: *const SmtWordpiece,
+        table_bytes: *mut u64,
+        codepoint_bytes: *mut u64,
+        utf8: *mut c_int,
+    ) -> c_int;
     pub fn smt_wordpiece_scan_device(
         tok: *mut SmtWordpiece,
         text_dev: *const u8,

@@ -46,10 +46,11 @@ EXPORTS = [
     "smt_model_create_indexed", "smt_model_create_from_file_indexed", "smt_model_create_from_device_indexed", "smt_model_token_info",
     "smt_sharded_model_create_indexed", "smt_sharded_model_create_from_file_indexed", "smt_sharded_model_token_info",
     "smt_debug_scan_pairs", "smt_debug_image_tile", "smt_debug_scan_groups", "smt_debug_scan_groups_wide", "smt_debug_nominations",
-    "smt_wordpiece_create", "smt_wordpiece_destroy", "smt_wordpiece_scan_device", "smt_wordpiece_emit_device", "smt_wordpiece_tokenize",
+    "smt_wordpiece_create", "smt_wordpiece_create_utf8", "smt_wordpiece_info", "smt_wordpiece_destroy", "smt_wordpiece_scan_device", "smt_wordpiece_emit_device", "smt_wordpiece_tokenize",
     "smt_unigram_create", "smt_unigram_destroy", "smt_unigram_scan_device", "smt_unigram_emit_device", "smt_unigram_tokenize",
 ]
 WP_NORMALIZER, WP_CLEAN_TEXT, WP_LOWERCASE = 1, 2, 4
+WP_CP_ORDINARY, WP_CP_SPACE, WP_CP_ALONE, WP_CP_DROPPED, WP_CP_FLAG = 0, 1, 2, 3, 4
 UG_MAX_WORD = 64
 UG_PREPEND = {"always": 0, "first": 1, "never": 2}
 TABLE_F32, TABLE_F16, TABLE_I8 = 0, 1, 2
@@ -107,7 +108,7 @@ HOST_EXPORTS = [
     "smt_host_split_lines", "smt_host_to_lowercase",
     "smt_host_group_from_spec", "smt_host_model_create_group", "smt_host_model_from_dir_group",
     "smt_host_workspace_use_group", "smt_host_workspace_status_group", "smt_host_workspace_prune_group",
-    "smt_host_model_table_info", "smt_host_model_token_info", "smt_host_tokenizer_to_device", "smt_host_tokenizer_to_device_unigram",
+    "smt_host_model_table_info", "smt_host_model_token_info", "smt_host_tokenizer_to_device", "smt_host_tokenizer_to_device_unigram", "smt_host_tokenizer_to_device_utf8",
     "smt_host_model_set_device_tokenizer", "smt_host_debug_device_tokenized",
 ]
 TOKENIZE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
@@ -127,6 +128,11 @@ class SmtWordpieceParams(C.Structure):
     _fields_ = [("pool", C.c_char_p), ("piece_off", C.c_void_p), ("piece_id", C.c_void_p), ("n_pieces", C.c_uint64),
                 ("prefix", C.c_char_p), ("prefix_len", C.c_uint32), ("unk_id", C.c_int64), ("max_input_chars_per_word", C.c_uint32),
                 ("flags", C.c_uint32), ("added_pool", C.c_char_p), ("added_off", C.c_void_p), ("n_added", C.c_uint32)]
+
+
+class SmtWordpieceCodepoints(C.Structure):
+    _fields_ = [("first", C.c_void_p), ("last", C.c_void_p), ("cls", C.c_void_p), ("out_pool", C.c_char_p), ("out_off", C.c_void_p),
+                ("n", C.c_uint64)]
 
 
 class SmtUnigramParams(C.Structure):
@@ -203,6 +209,8 @@ def lib():
     L.smt_embed.argtypes = [vp, vp, vp, u64, u32, vp, vp, P(u64)]
     L.smt_embed_device.argtypes = [vp, vp, vp, u64, u32, vp]
     L.smt_wordpiece_create.argtypes = [vp, P(SmtWordpieceParams), P(vp)]
+    L.smt_wordpiece_create_utf8.argtypes = [vp, P(SmtWordpieceParams), P(SmtWordpieceCodepoints), P(vp)]
+    L.smt_wordpiece_info.argtypes = [vp, P(u64), P(u64), P(i32)]
     L.smt_wordpiece_destroy.argtypes = [vp]
     L.smt_wordpiece_destroy.restype = None
     L.smt_wordpiece_scan_device.argtypes = [vp, vp, u64, vp, vp, u64, u32, u32, i32, vp, vp, vp]
@@ -378,6 +386,7 @@ def lib():
     L.smt_host_tokenizer_info.argtypes = [vp, P(u64), P(C.c_int64), P(u64)]
     L.smt_host_tokenizer_to_device.argtypes = [vp, vp, P(vp)]
     L.smt_host_tokenizer_to_device_unigram.argtypes = [vp, vp, P(vp)]
+    L.smt_host_tokenizer_to_device_utf8.argtypes = [vp, vp, P(vp)]
     L.smt_host_model_set_device_tokenizer.argtypes = [vp, i32]
     L.smt_host_debug_device_tokenized.argtypes = [vp, P(u64)]
     L.smt_host_timing_json.argtypes = []

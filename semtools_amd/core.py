@@ -317,20 +317,24 @@ class _DeviceTokenizer:
 
 
 class WordPiece(_DeviceTokenizer):
-    """The device tokenizer (smt_wordpiece): pure-ASCII lines through BertNormalizer -> BertPreTokenizer -> WordPiece.
+    """The device tokenizer (smt_wordpiece): lines through BertNormalizer -> BertPreTokenizer -> WordPiece.  Pure-ASCII lines by
+    default; with `codepoints` (or utf8=True beside host_tokenizer) the UTF-8 form, which covers the code points the caller states.
 
     WordPiece(ctx, vocab={piece: id}, unk_id=.., flags=L.WP_*, added=[..]) builds it from a vocabulary;
     WordPiece(ctx, host_tokenizer=<smt_host_tokenizer handle>) takes the device form of a loaded tokenizer.json
-    (SmtError with code SMT_E_UNSUPPORTED when it has none).  Calls smt_wordpiece_{tokenize,scan_device,emit_device,destroy}."""
+    (SmtError with code SMT_E_UNSUPPORTED when it has none); utf8=True takes its UTF-8 form (smt_host_tokenizer_to_device_utf8).
+    codepoints: a list of (first, last, class L.WP_CP_*, output str or bytes, "" = itself) for the code points >= U+0080, sorted and
+    disjoint (smt_wordpiece_create_utf8).  Calls smt_wordpiece_{tokenize,scan_device,emit_device,destroy}."""
 
     _prefix = "wordpiece"
 
     def __init__(self, ctx, vocab=None, unk_id=-1, prefix="##", max_input_chars_per_word=100,
-                 flags=L.WP_NORMALIZER | L.WP_CLEAN_TEXT | L.WP_LOWERCASE, added=(), host_tokenizer=None):
+                 flags=L.WP_NORMALIZER | L.WP_CLEAN_TEXT | L.WP_LOWERCASE, added=(), host_tokenizer=None, codepoints=None, utf8=False):
         self.ctx = ctx
         self._h = C.c_void_p()
         if host_tokenizer is not None:
-            L.check(L.lib().smt_host_tokenizer_to_device(host_tokenizer, ctx._h, C.byref(self._h)))
+            to_device = L.lib().smt_host_tokenizer_to_device_utf8 if utf8 else L.lib().smt_host_tokenizer_to_device
+            L.check(to_device(host_tokenizer, ctx._h, C.byref(self._h)))
             return
         pieces = [(p.encode() if isinstance(p, str) else bytes(p), int(i)) for p, i in (vocab.items() if hasattr(vocab, "items") else vocab)]
         pool = b"".join(p for p, _ in pieces)
@@ -343,7 +347,23 @@ class WordPiece(_DeviceTokenizer):
         pre = prefix.encode() if isinstance(prefix, str) else bytes(prefix)
         prm = L.SmtWordpieceParams(pool, L.np_ptr(off), L.np_ptr(ids), len(pieces), pre, len(pre), int(unk_id),
                                    int(max_input_chars_per_word), int(flags), b"".join(added_b), L.np_ptr(aoff), len(added_b))
-        L.check(L.lib().smt_wordpiece_create(ctx._h, C.byref(prm), C.byref(self._h)))
+        if codepoints is None:
+            L.check(L.lib().smt_wordpiece_create(ctx._h, C.byref(prm), C.byref(self._h)))
+            return
+        outs = [(o.encode() if isinstance(o, str) else bytes(o)) for _, _, _, o in codepoints]
+        first = np.array([c[0] for c in codepoints], dtype=np.uint32)
+        last = np.array([c[1] for c in codepoints], dtype=np.uint32)
+        cls = np.array([c[2] for c in codepoints], dtype=np.uint8)
+        ooff = np.zeros(len(outs) + 1, dtype=np.uint32)
+        ooff[1:] = np.cumsum([len(o) for o in outs], dtype=np.uint64)
+        cps = L.SmtWordpieceCodepoints(L.np_ptr(first), L.np_ptr(last), L.np_ptr(cls), b"".join(outs), L.np_ptr(ooff), len(outs))
+        L.check(L.lib().smt_wordpiece_create_utf8(ctx._h, C.byref(prm), C.byref(cps), C.byref(self._h)))
+
+    def info(self):
+        """(bytes of the whole device table, bytes of its code-point part -- 0 for the ASCII form --, True for the UTF-8 form)"""
+        table, cps, utf8 = C.c_uint64(), C.c_uint64(), C.c_int()
+        L.check(L.lib().smt_wordpiece_info(self._h, C.byref(table), C.byref(cps), C.byref(utf8)))
+        return int(table.value), int(cps.value), bool(utf8.value)
 
 
 class Unigram(_DeviceTokenizer):

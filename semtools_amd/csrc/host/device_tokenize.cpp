@@ -61,7 +61,7 @@ double ms_since(std::chrono::steady_clock::time_point t0)
 
 }  // namespace
 
-DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok)
+DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bool utf8)
 {
     int n_ranks = 0;
     if (smt_group_info(group, &n_ranks, nullptr, nullptr, nullptr, nullptr) != SMT_OK || n_ranks != 1) return nullptr;
@@ -70,7 +70,14 @@ DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok)
     smt::TokHandle *h = nullptr;
     WordpieceExport x;
     UnigramExport u;
-    if (tok.export_wordpiece(x)) {
+    WordpieceUtf8Export x8;
+    if (utf8 && tok.export_wordpiece_utf8(x8)) {
+        const smt_wordpiece_params p = x8.base.params();
+        const smt_wordpiece_codepoints cp = x8.codepoints();
+        smt_wordpiece *wp = nullptr;
+        api_ok(smt_wordpiece_create_utf8(ctx, &p, &cp, &wp), "smt_wordpiece_create_utf8");
+        h = smt::tok_handle(wp);
+    } else if (tok.export_wordpiece(x)) {
         const smt_wordpiece_params p = x.params();
         smt_wordpiece *wp = nullptr;
         api_ok(smt_wordpiece_create(ctx, &p, &wp), "smt_wordpiece_create");

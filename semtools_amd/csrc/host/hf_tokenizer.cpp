@@ -626,6 +626,56 @@ public:
         return true;
     }
 
+    // The UTF-8 form: BertNormalizer's four steps and BertPreTokenizer's split act on one code point without context, so the table is
+    // what apply_normalizer makes of every single code point, classified with the pre-tokenizer's own predicates.  FLAG (the line
+    // stays with encode()): the outputs mix classes; an output keeps a character of non-zero combining class (NFD's canonical
+    // reordering would then depend on the neighbours); the outputs number more characters than the source has bytes (the kernel's
+    // token slots are the word's own bytes).  Equal neighbours merge into ranges.
+    bool export_wordpiece_utf8(WordpieceUtf8Export &x) const override
+    {
+        for (const AddedToken &t : added_) {
+            if (t.normalized) continue;
+            for (uint32_t c : t.content) if (c >= 0x80) return false;   // (matched on the raw text: the kernel's added tokens are ASCII)
+        }
+        if (!export_wordpiece(x.base)) return false;
+        x.first.clear(); x.last.clear(); x.cls.clear(); x.out_pool.clear();
+        x.out_off.assign(1, 0);
+        U32 s;
+        for (uint32_t cp = 0x80; cp <= 0x10FFFF; ++cp) {
+            if (cp == 0xD800) cp = 0xE000;
+            s.assign(1, cp);
+            if (has_norm_) apply_normalizer(norm_, s);
+            uint8_t k = SMT_WP_CP_FLAG;
+            size_t b = 0, e = s.size();
+            while (b < e && is_white_space(s[b])) ++b;
+            while (e > b && is_white_space(s[e - 1])) --e;
+            bool plain = true, marks = false;   // plain: every character of [b, e) is a word's character
+            for (size_t i = b; i < e; ++i) {
+                plain = plain && !is_white_space(s[i]) && !is_bert_punc(s[i]);
+                marks = marks || ccc_of(s[i]) != 0;
+            }
+            const size_t src = cp < 0x800 ? 2 : cp < 0x10000 ? 3 : 4;
+            if (s.empty()) k = SMT_WP_CP_DROPPED;
+            else if (s.size() > src || marks) k = SMT_WP_CP_FLAG;
+            else if (b == e) k = SMT_WP_CP_SPACE;
+            else if (b == 0 && e == s.size()) k = plain ? SMT_WP_CP_ORDINARY : e == 1 ? SMT_WP_CP_ALONE : SMT_WP_CP_FLAG;
+            else if (b == 1 && e + 1 == s.size() && e - b == 1) k = SMT_WP_CP_ALONE;   // ' ' + a Chinese character + ' '
+            if (k == SMT_WP_CP_FLAG) continue;   // (a code point in no range is FLAG)
+            std::string out;
+            if ((k == SMT_WP_CP_ORDINARY || k == SMT_WP_CP_ALONE) && !(e - b == 1 && s[b] == cp)) out = to_utf8(s, b, e);
+            if (out.empty() && !x.first.empty() && x.last.back() + 1 == cp && x.cls.back() == k && x.out_off[x.out_off.size() - 2] == x.out_off.back()) {
+                x.last.back() = cp;
+                continue;
+            }
+            x.first.push_back(cp);
+            x.last.push_back(cp);
+            x.cls.push_back(k);
+            x.out_pool += out;
+            x.out_off.push_back((uint32_t)x.out_pool.size());
+        }
+        return true;
+    }
+
     // Unigram behind exactly one Metaspace (split, a replacement >= U+0080) and a normalizer that acts on an ASCII character without
     // context: the byte table is what apply_normalizer makes of every single byte
     bool export_unigram(UnigramExport &x) const override

@@ -712,9 +712,15 @@ void StaticModel::tokenize_batch(const std::string_view *sentences, size_t begin
 DeviceTokenRoute *StaticModel::device_route() const
 {
     if (!device_tok_) return nullptr;
+    if (dev_route_tried_ && dev_route_mode_ != device_tok_) {
+        device_route_destroy(dev_route_);
+        dev_route_ = nullptr;
+        dev_route_tried_ = false;
+    }
     if (!dev_route_tried_) {
         dev_route_tried_ = true;
-        dev_route_ = device_route_create(group_, *tok_);
+        dev_route_mode_ = device_tok_;
+        dev_route_ = device_route_create(group_, *tok_, device_tok_ == 2);
     }
     return dev_route_;
 }

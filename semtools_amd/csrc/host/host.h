@@ -72,6 +72,26 @@ struct WordpieceExport {
     }
 };
 
+// the same family for UTF-8 lines (smt_wordpiece_create_utf8): the vocabulary as above, and what every code point >= U+0080 becomes
+// under the normalizer and the pre-tokenizer, as ranges (smt_wordpiece_codepoints, which points into these)
+struct WordpieceUtf8Export {
+    WordpieceExport base;
+    std::vector<uint32_t> first, last, out_off;
+    std::vector<uint8_t> cls;
+    std::string out_pool;
+    smt_wordpiece_codepoints codepoints() const   // (points into this object)
+    {
+        smt_wordpiece_codepoints c{};
+        c.first = first.data();
+        c.last = last.data();
+        c.cls = cls.data();
+        c.out_pool = out_pool.data();
+        c.out_off = out_off.data();
+        c.n = first.size();
+        return c;
+    }
+};
+
 // what a Unigram tokenizer whose pure-ASCII lines are a per-byte normalizer -> Metaspace -> Unigram hands the device tokenizer
 // (include/semtools_hip.h smt_unigram_params, which points into these)
 struct UnigramExport {
@@ -117,6 +137,8 @@ public:
     // family, or not supported (other pre-tokenizers, Strip / Replace normalizers, the vocab.txt, hash and callback tokenizers)
     virtual bool export_wordpiece(WordpieceExport &) const { return false; }
     virtual bool export_unigram(UnigramExport &) const { return false; }
+    // the UTF-8 form of export_wordpiece: the same family, and no added token matched on the raw text may hold a non-ASCII byte
+    virtual bool export_wordpiece_utf8(WordpieceUtf8Export &) const { return false; }
 };
 // whitespace words looked up in a vocab file (one token per line, id = line index)
 std::unique_ptr<Tokenizer> make_vocab_tokenizer(const std::string &vocab_path, const std::string &unk_token);
@@ -155,7 +177,8 @@ struct TokenCsr {
 struct DeviceTokenRoute;
 // fills the CSR (ids, offsets [lines.size() + 1]) of the batch's flagged lines, given by their index in the batch
 using DeviceFlaggedFn = std::function<void(const std::vector<uint64_t> &lines, std::vector<uint32_t> &ids, std::vector<uint64_t> &offsets)>;
-DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok);
+// utf8: the UTF-8 form of a WordPiece tokenizer where it has one (export_wordpiece_utf8), else what utf8 = false makes
+DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bool utf8 = false);
 void device_route_destroy(DeviceTokenRoute *r);
 uint64_t device_route_lines(const DeviceTokenRoute *r);   // lines tokenized on the device so far
 // the batch's bytes back to back into pinned slot `which` (0 / 1: one is packed while the other one runs); false: the batch is
@@ -212,9 +235,10 @@ public:
     const Tokenizer &tokenizer() const { return *tok_; }
     // the device tokenizer route (off by default; SEMTOOLS_DEVICE_TOKENIZER=1 turns it on at construction): with it on, batches of a
     // one-rank group whose tokenizer has a device form are tokenized on the GPU once the full table is resident.  Rows and cached
-    // ids do not depend on it.
-    void set_device_tokenizer(bool on) { device_tok_ = on; }
-    bool device_tokenizer() const { return device_tok_; }
+    // ids do not depend on it.  Mode 2 (SEMTOOLS_DEVICE_TOKENIZER=2) chooses the UTF-8 form of a WordPiece tokenizer where it has one,
+    // and what 1 chooses otherwise; 1 keeps the ASCII forms.
+    void set_device_tokenizer(int mode) { device_tok_ = mode < 0 ? 0 : mode > 2 ? 2 : mode; }
+    int device_tokenizer() const { return device_tok_; }
     uint64_t device_tokenized_lines() const { return device_route_lines(dev_route_); }
     // the table as the device holds it (or will, in lazy mode before the full upload: *resident = false): SMT_TABLE_* kind, rows,
     // bytes per replica
@@ -237,9 +261,10 @@ private:
     // one packed batch through the route; true: the batch was mostly flagged (the rest of the call keeps the host path)
     bool device_batch(int which, size_t n, const std::string_view *sentences, std::optional<size_t> max_length, float *out_host,
                       smt_sharded_corpus *corpus, TokenCsr *sink) const;
-    bool device_tok_ = [] { const char *e = getenv("SEMTOOLS_DEVICE_TOKENIZER"); return e && e[0] == '1'; }();
+    int device_tok_ = [] { const char *e = getenv("SEMTOOLS_DEVICE_TOKENIZER"); return e && e[0] == '1' ? 1 : e && e[0] == '2' ? 2 : 0; }();
     mutable DeviceTokenRoute *dev_route_ = nullptr;
     mutable bool dev_route_tried_ = false;
+    mutable int dev_route_mode_ = 0;   // the mode dev_route_ was made for: a change of mode makes it anew
     smt_group *group_;
     std::unique_ptr<Tokenizer> tok_;
     mutable smt_sharded_model *model_ = nullptr;

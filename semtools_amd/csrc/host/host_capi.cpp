@@ -297,7 +297,7 @@ int smt_host_tokenizer_info(smt_host_tokenizer *tok, uint64_t *vocab_size, int64
 int smt_host_model_set_device_tokenizer(smt_host_model *model, int on)
 {
     if (!model) { smt::set_error("null argument"); return SMT_E_INVALID; }
-    model->m->set_device_tokenizer(on != 0);
+    model->m->set_device_tokenizer(on);   // 0 off, 1 the ASCII forms, 2 the UTF-8 form where the tokenizer has one
     return SMT_OK;
 }
 
@@ -320,6 +320,23 @@ int smt_host_tokenizer_to_device(smt_host_tokenizer *tok, smt_ctx *ctx, smt_word
         }
         const smt_wordpiece_params p = x.params();
         return smt_wordpiece_create(ctx, &p, out);   // (no context: SMT_E_HIP on a machine without a device)
+    } catch (const std::exception &e) { return fail(e); }
+}
+
+int smt_host_tokenizer_to_device_utf8(smt_host_tokenizer *tok, smt_ctx *ctx, smt_wordpiece **out)
+{
+    if (!tok || !out) { smt::set_error("null argument"); return SMT_E_INVALID; }
+    *out = nullptr;
+    try {
+        WordpieceUtf8Export x;
+        if (!tok->t->export_wordpiece_utf8(x)) {
+            smt::set_error("this tokenizer has no UTF-8 device form (BertNormalizer -> BertPreTokenizer -> WordPiece with an unk token and "
+                           "ASCII added tokens only)");
+            return SMT_E_UNSUPPORTED;
+        }
+        const smt_wordpiece_params p = x.base.params();
+        const smt_wordpiece_codepoints cp = x.codepoints();
+        return smt_wordpiece_create_utf8(ctx, &p, &cp, out);   // (no context: SMT_E_HIP on a machine without a device)
     } catch (const std::exception &e) { return fail(e); }
 }
 

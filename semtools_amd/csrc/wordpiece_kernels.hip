@@ -13,6 +13,9 @@
 // line's start is the token's place in its line; lines are laid out by a prefix sum of their (capped, or patched) counts.
 //
 // Every loop is bounded: probes by the table's capacity, a word's pieces by max_input_chars_per_word, a walk by the line's end.
+//
+// Also here: the create of both forms of the handle.  The UTF-8 form's pass 1 is wordpiece_utf8_kernels.hip; the table and the handle
+// the two share are in wordpiece_table.h.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -21,25 +24,14 @@
 #include "common.h"
 #include "tokenize_frame.h"
 #include "wordpiece_bytes.h"
+#include "wordpiece_table.h"
 
 namespace {
 
 constexpr uint32_t WP_NONE = smt::TOK_NONE;   // an ids_tmp slot that holds no token
 constexpr unsigned SCAN_THREADS = 256;        // pass 1: one position per thread
 
-struct WpTable {
-    smt::TokAdded added;               // (in front: of three places measured, the one where pass 1 is no slower than before the struct)
-    const unsigned long long *slots;   // (tag << 32) | entry + 1; 0 = empty
-    const uint4 *ent;                  // {pool offset of the piece, its length, its id, 1 = continuing piece}
-    const uint8_t *pool;
-    const uint8_t *bytes;              // cls[128] | nrm[128]
-    uint32_t mask;                     // capacity - 1
-    uint32_t prefix_len;
-    uint32_t max_piece;                // longest piece, in bytes: no match can be longer
-    uint32_t max_chars;
-    uint32_t unk;                      // WP_NONE: none
-    unsigned long long prefix_state;   // the hash after the continuing prefix
-};
+using smt::WpTable;   // (wordpiece_table.h: shared with the UTF-8 form)
 
 // the candidate: clen characters from raw position s (dropped bytes skipped), hash h, as a whole word (kind 0) or a continuing piece
 __device__ __forceinline__ uint32_t wp_probe(const WpTable &T, const uint8_t *__restrict__ text, const uint8_t *cls, const uint8_t *nrm,
@@ -154,29 +146,25 @@ constexpr smt::TokWords WP_WORDS = {"no scan to emit (smt_wordpiece_scan_device 
 
 }  // namespace
 
-struct smt_wordpiece : smt::TokHandle {
-    WpTable T{};                      // points into d_table: slots | entries | pool | byte tables | added pool | added offsets
-    explicit smt_wordpiece(smt_ctx *c) : smt::TokHandle(c, false, WP_WORDS) {}
-    int pass1(const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev, uint64_t n_lines,
-              uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev) override
-    {
-        if (!n_lines || !text_bytes) return SMT_OK;
-        hipLaunchKernelGGL(wp_scan_kernel, dim3((unsigned)((text_bytes + SCAN_THREADS - 1) / SCAN_THREADS)), dim3(SCAN_THREADS), 0, ctx->stream, T,
-                           text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, S.d_ids_tmp, S.raw_count(), flags_dev);
-        SMT_HIP_CHECK(hipGetLastError());
-        return SMT_OK;
-    }
-};
+int smt_wordpiece::pass1(const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev, uint64_t n_lines,
+                         uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev)
+{
+    if (!n_lines || !text_bytes) return SMT_OK;
+    if (utf8) return smt::wp_scan_utf8_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev);
+    hipLaunchKernelGGL(wp_scan_kernel, dim3((unsigned)((text_bytes + SCAN_THREADS - 1) / SCAN_THREADS)), dim3(SCAN_THREADS), 0, ctx->stream, T,
+                       text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, S.d_ids_tmp, S.raw_count(), flags_dev);
+    SMT_HIP_CHECK(hipGetLastError());
+    return SMT_OK;
+}
 
 using namespace smt;
 
 TokHandle *smt::tok_handle(smt_wordpiece *tok) { return tok; }
 
-extern "C" {
-
-int smt_wordpiece_create(smt_ctx *ctx, const smt_wordpiece_params *p, smt_wordpiece **out)
-try {
-    if (!ctx) return tok_null_handle("smt_wordpiece_create");
+// the body of both creates.  cp == nullptr: the ASCII form (a byte >= 0x80 flags its line, pieces with such a byte cannot match and
+// are left out); otherwise the UTF-8 form: all pieces enter, the code points come from *cp
+static int wp_create(smt_ctx *ctx, const smt_wordpiece_params *p, const smt_wordpiece_codepoints *cp, smt_wordpiece **out)
+{
     SMT_REQUIRE(p != nullptr && out != nullptr, "null argument");
     *out = nullptr;
     SMT_REQUIRE(p->n_pieces == 0 || (p->pool && p->piece_off && p->piece_id), "vocabulary arrays");
@@ -188,10 +176,13 @@ try {
     for (uint64_t i = 0; i < p->n_pieces; ++i) SMT_REQUIRE(p->piece_off[i] <= p->piece_off[i + 1], "piece_off must be non-decreasing");
     for (uint32_t i = 0; i < p->n_added; ++i) SMT_REQUIRE(p->added_off[i] <= p->added_off[i + 1], "added_off must be non-decreasing");
     for (uint32_t i = 0; i < p->prefix_len; ++i) SMT_REQUIRE((uint8_t)p->prefix[i] < 0x80, "the continuing prefix must be ASCII");
-    int rc = bind_device(ctx);
+    WpCodepointImage img;
+    int rc = cp ? wp_codepoint_image(cp, img) : SMT_OK;   // (validated before anything is uploaded)
     if (rc) return rc;
+    if ((rc = bind_device(ctx))) return rc;
 
-    // ---- entries: every ASCII piece as a whole word; one that starts with the prefix and goes on, as a continuing piece too
+    // ---- entries: every piece (the ASCII form: every ASCII piece) as a whole word; one that starts with the prefix and goes on, as a
+    // continuing piece too
     std::vector<TokEntry> ents;
     ents.reserve(p->n_pieces * 2);
     uint32_t max_piece = 0;
@@ -200,7 +191,7 @@ try {
         if (len == 0) continue;
         bool ascii = true;
         for (uint32_t j = 0; j < len && ascii; ++j) ascii = (uint8_t)p->pool[off + j] < 0x80;
-        if (!ascii) continue;
+        if (!ascii && !cp) continue;
         const uint64_t h = tok_hash_bytes(p->pool + off, len);
         max_piece = std::max(max_piece, len);
         ents.push_back({off, len, p->piece_id[i], 0, h, i});
@@ -210,17 +201,20 @@ try {
     tok_build_table(p->pool, ents, table);
     uint8_t bytes[256];
     wordpiece_byte_table(p->flags, bytes, bytes + 128);
-    std::unique_ptr<smt_wordpiece> tok(new smt_wordpiece(ctx));
+    std::unique_ptr<smt_wordpiece> tok(new smt_wordpiece(ctx, WP_WORDS));
     WpTable &T = tok->T;
     if ((rc = tok_added_first(p, T.added))) return rc;
-    const uint8_t *at[6];
+    const uint8_t *at[9];
     if ((rc = tok_upload_table("wordpiece",
                                {{table.slots.data(), table.slots.size() * 8},
                                 {table.ents.data(), table.ents.size() * sizeof(uint4)},
                                 {p->pool, p->n_pieces ? p->piece_off[p->n_pieces] : 0},
                                 {bytes, 256},
                                 {p->added_pool, p->n_added ? p->added_off[p->n_added] : 0},
-                                {p->added_off, p->n_added ? ((size_t)p->n_added + 1) * 4 : 0}},
+                                {p->added_off, p->n_added ? ((size_t)p->n_added + 1) * 4 : 0},
+                                {img.page.data(), img.page.size() * 2},
+                                {img.ent.data(), img.ent.size() * 4},
+                                {img.out.data(), img.out.size()}},
                                &tok->d_table, at)))
         return rc;
     T.slots = reinterpret_cast<const unsigned long long *>(at[0]);
@@ -235,7 +229,43 @@ try {
     T.max_chars = p->max_input_chars_per_word;
     T.unk = p->unk_id < 0 ? WP_NONE : (uint32_t)p->unk_id;
     T.prefix_state = tok_hash_bytes(p->prefix, p->prefix_len);
+    tok->table_bytes = table.slots.size() * 8 + table.ents.size() * sizeof(uint4) + (p->n_pieces ? p->piece_off[p->n_pieces] : 0) + 256 +
+                       (p->n_added ? p->added_off[p->n_added] + ((size_t)p->n_added + 1) * 4 : 0);
+    if (cp) {
+        tok->utf8 = true;
+        tok->codepoint_bytes = img.page.size() * 2 + img.ent.size() * 4 + img.out.size();
+        tok->table_bytes += tok->codepoint_bytes;
+        tok->U.page = reinterpret_cast<const uint16_t *>(at[6]);
+        tok->U.ent = reinterpret_cast<const uint32_t *>(at[7]);
+        tok->U.out = at[8];
+        tok->U.n_pages = (uint32_t)(img.ent.size() / 256);
+        tok->U.out_bytes = (uint32_t)img.out.size();
+    }
     *out = tok.release();
+    return SMT_OK;
+}
+
+extern "C" {
+
+int smt_wordpiece_create(smt_ctx *ctx, const smt_wordpiece_params *p, smt_wordpiece **out)
+try {
+    if (!ctx) return tok_null_handle("smt_wordpiece_create");
+    return wp_create(ctx, p, nullptr, out);
+} catch (...) { return smt::api_catch(); }
+
+int smt_wordpiece_create_utf8(smt_ctx *ctx, const smt_wordpiece_params *p, const smt_wordpiece_codepoints *cp, smt_wordpiece **out)
+try {
+    if (!ctx) return tok_null_handle("smt_wordpiece_create_utf8");
+    SMT_REQUIRE(cp != nullptr, "null argument");
+    return wp_create(ctx, p, cp, out);
+} catch (...) { return smt::api_catch(); }
+
+int smt_wordpiece_info(const smt_wordpiece *tok, uint64_t *table_bytes, uint64_t *codepoint_bytes, int *utf8)
+try {
+    if (!tok) return tok_null_handle("smt_wordpiece_info");
+    if (table_bytes) *table_bytes = tok->table_bytes;
+    if (codepoint_bytes) *codepoint_bytes = tok->codepoint_bytes;
+    if (utf8) *utf8 = tok->utf8 ? 1 : 0;
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 

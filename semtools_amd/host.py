@@ -33,7 +33,7 @@ class StaticModel:
     def __init__(self, ctx, table=None, tokenizer="hash", normalize=True, unk_id=None, median_len=5, model_dir=None, device_tokenizer=None):
         """ctx: a core.Context (one GPU) or a core.Group (the host layer then runs sharded over its GPUs).
         device_tokenizer: True / False switch the device tokenizer route on / off (None: the library's default, off unless
-        SEMTOOLS_DEVICE_TOKENIZER=1); it applies to tokenizer.json models of the Bert / WordPiece and the Metaspace / Unigram families on one GPU."""
+        SEMTOOLS_DEVICE_TOKENIZER=1 or 2); 2 chooses the UTF-8 form of a WordPiece tokenizer where it has one; it applies to tokenizer.json models of the Bert / WordPiece and the Metaspace / Unigram families on one GPU."""
         from .core import Group
         self.ctx = ctx
         on_group = isinstance(ctx, Group)
@@ -71,7 +71,7 @@ class StaticModel:
             self.set_device_tokenizer(device_tokenizer)
 
     def set_device_tokenizer(self, on):
-        L.check(L.lib().smt_host_model_set_device_tokenizer(self._h, int(bool(on))))
+        L.check(L.lib().smt_host_model_set_device_tokenizer(self._h, int(on)))
 
     def device_tokenized_lines(self):
         """lines of this model tokenized on the device so far (test hook)"""

@@ -7,8 +7,14 @@ given), so the host tokenizer's threads and the route's copy threads share that 
 (first-use allocations), then three timed ones.  Merges its result under the key cpus_<n> into profiles/device_tokenizer.json.
 --model unigram runs the same lines through a synthetic Unigram vocabulary of the same size behind BertNormalizer -> Metaspace (the
 other device tokenizer) and writes profiles/device_tokenizer_unigram.json.
+--utf8 measures the UTF-8 form of the WordPiece route instead (settings off / 1 / 2, alternated in one process, one warm-up call each
+discarded, best of three with the spread, every timed call ends in a device synchronise): a text in which every tenth line holds a
+non-ASCII character (curly quotes, an accented word, a CJK phrase), the pure-ASCII text (pass 1 of the UTF-8 kernel against the ASCII
+kernel: the price of 2 where it is not needed), the same lines transliterated into Cyrillic letters (every word non-ASCII, the
+vocabulary transliterated with them) and rewritten as CJK characters without spaces (every character a word of its own), and the size
+of the code-point table.  Writes profiles/device_tokenizer_utf8.json.
 
-    python tools/bench_device_tokenizer.py [--model wordpiece|unigram] [--lines 1000000] [--cpus 16] [--out profiles/device_tokenizer.json]"""
+    python tools/bench_device_tokenizer.py [--model wordpiece|unigram] [--utf8] [--lines 1000000] [--cpus 16] [--out profiles/device_tokenizer.json]"""
 import argparse
 import ctypes as C
 import json
@@ -16,6 +22,7 @@ import os
 import sys
 import tempfile
 import time
+import zlib
 
 import math
 
@@ -125,24 +132,130 @@ def run(ctx, model, content_b, query_b, n_lines, repeats=3):
     return res
 
 
+NON_ASCII = [lambda ln: ln.replace(" ", " \u201c", 1).replace(",", "\u201d,", 1), lambda ln: ln.replace(" ", " caf\u00e9 na\u00efve ", 1),
+             lambda ln: ln.replace(" ", " \u4e2d\u6587\u5b57\u7b26 ", 1)]
+
+
+CYRILLIC = str.maketrans("abcdefghijklmnopqrstuvwxyz" + "ABCDEFGHIJKLMNOPQRSTUVWXYZ",
+                         "абвгдежзиклмнопрстуфхцчшщы" + "АБВГДЕЖЗИКЛМНОПРСТУФХЦЧШЩЫ")   # (no й: NFD splits it)
+CJK_POOL = [chr(0x4E00 + 3 * i) for i in range(2000)]
+
+
+def to_cjk(line):
+    """every word becomes one to three characters of CJK_POOL (chosen by its CRC), written without spaces; , and . stay"""
+    out = []
+    for w in line.split(" "):
+        tail = w[-1] if w[-1:] in (",", ".") else ""
+        h = zlib.crc32(w.lower().encode())
+        out.append("".join(CJK_POOL[(h >> (11 * k)) % len(CJK_POOL)] for k in range(1 + h % 3)) + tail)
+    return "".join(out)
+
+
+def run_utf8(ctx, d, corpus, n_lines, repeats=3):
+    """off / 1 / 2 on one text: a model per setting, a discarded warm-up call each, then `repeats` rounds that visit the settings in
+    turn; every timed call ends in a device synchronise"""
+    content_b = ("\n".join(corpus) + "\n").encode()
+    query_b = corpus[17].encode()
+    models = {name: host.StaticModel(ctx, model_dir=d, device_tokenizer=mode) for name, mode in (("off", 0), ("1", 1), ("2", 2))}
+    times = {name: [] for name in models}
+    pass1 = {name: [0, 0.0] for name in models}
+    first = {}
+
+    def call(m):
+        out = C.c_void_p()
+        L.check(L.lib().smt_host_search_content(m._h, query_b, b"<stdin>", content_b, 0, 3, float("nan"), 0, 0, 0, C.byref(out)))
+        ctx.synchronize()
+        return host._take_text(out).split("\n")[0]
+
+    for m in models.values():
+        call(m)
+    for _ in range(repeats):
+        for name, m in models.items():
+            ctx.prof_reset()
+            t0 = time.perf_counter()
+            first[name] = call(m)
+            times[name].append(time.perf_counter() - t0)
+            n, ms = ctx.prof_read("tokenize")
+            pass1[name][0] += n
+            pass1[name][1] += ms
+    entry = {"text_bytes": len(content_b)}
+    for name, m in models.items():
+        best = min(times[name])
+        res = {"seconds_best": round(best, 4), "seconds_all": [round(t, 4) for t in times[name]],
+               "spread_percent": round(100.0 * (max(times[name]) - best) / best, 1), "lines_per_s": round(n_lines / best),
+               "device_tokenized_lines_per_call": m.device_tokenized_lines() // (repeats + 1), "first_hit": first[name][:80]}
+        if pass1[name][0]:
+            res["pass1_ms_per_call"] = round(pass1[name][1] / repeats, 3)
+            res["pass1_launches_per_call"] = pass1[name][0] // repeats
+            res["pass1_GB_per_s"] = round(len(content_b) * repeats / (pass1[name][1] * 1e-3) / 1e9, 2)
+        entry[name] = res
+        m.close()
+    entry["same_first_hit"] = len(set(first.values())) == 1
+    entry["2_over_1"] = round(entry["2"]["lines_per_s"] / entry["1"]["lines_per_s"], 3)
+    entry["2_over_off"] = round(entry["2"]["lines_per_s"] / entry["off"]["lines_per_s"], 3)
+    entry["1_over_off"] = round(entry["1"]["lines_per_s"] / entry["off"]["lines_per_s"], 3)
+    return entry
+
+
+def measure_on_off(ctx, d, corpora, n_lines, result):
+    for corpus_name, corpus in corpora:
+        content_b = ("\n".join(corpus) + "\n").encode()
+        query_b = corpus[17].encode()
+        entry = {"text_bytes": len(content_b)}
+        for setting, on in (("off", False), ("on", True)):
+            m = host.StaticModel(ctx, model_dir=d, device_tokenizer=on)
+            entry[setting] = run(ctx, m, content_b, query_b, n_lines)
+            m.close()
+        entry["on_over_off"] = round(entry["on"]["lines_per_s"] / entry["off"]["lines_per_s"], 3)
+        entry["same_first_hit"] = entry["on"]["first_hit"] == entry["off"]["first_hit"]
+        result[corpus_name] = entry
+
+
+def measure_utf8(ctx, d, lines, n_lines, result):
+    result["what"] = "host-layer ingest (smt_host_search_content), device tokenizer route off / 1 (ASCII form) / 2 (UTF-8 form)"
+    result["note"] = ("kernel profiling events are on in all settings; per setting one warm-up call is discarded, then three rounds visit "
+                      "off, 1, 2 in turn; every timed call ends in a device synchronise; seconds_best is the best of 3, spread_percent "
+                      "(max - best) / best")
+    h = C.c_void_p()
+    L.check(L.lib().smt_host_tokenizer_load(os.path.join(d, "tokenizer.json").encode(), C.byref(h)))
+    t0 = time.perf_counter()
+    tok = smt.WordPiece(ctx, host_tokenizer=h, utf8=True)
+    result["code_point_table"] = {"create_seconds": round(time.perf_counter() - t0, 3), "table_bytes": tok.info()[0],
+                                  "code_point_bytes": tok.info()[1]}
+    tok.close()
+    L.lib().smt_host_tokenizer_free(h)
+    mixed = [NON_ASCII[(i // 10) % 3](ln) if i % 10 == 0 else ln for i, ln in enumerate(lines)]
+    result["every_tenth_line_non_ascii"] = run_utf8(ctx, d, mixed, n_lines)
+    result["ascii"] = run_utf8(ctx, d, lines, n_lines)
+    result["cyrillic"] = run_utf8(ctx, d, [ln.translate(CYRILLIC) for ln in lines], n_lines)
+    result["cjk_no_spaces"] = run_utf8(ctx, d, [to_cjk(ln) for ln in lines], n_lines)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--utf8", action="store_true")
     ap.add_argument("--lines", type=int, default=1_000_000)
     ap.add_argument("--cpus", type=int, default=16)
     ap.add_argument("--model", choices=["wordpiece", "unigram"], default="wordpiece")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     unigram = a.model == "unigram"
+    if a.utf8 and unigram:
+        ap.error("--utf8 is the WordPiece route's")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "device_tokenizer_unigram.json" if unigram else "device_tokenizer.json")
+        a.out = os.path.join(ROOT, "profiles", "device_tokenizer_utf8.json" if a.utf8 else "device_tokenizer_unigram.json" if unigram else "device_tokenizer.json")
     if a.cpus and hasattr(os, "sched_setaffinity"):
         os.sched_setaffinity(0, sorted(os.sched_getaffinity(0))[: a.cpus])
     rng = np.random.default_rng(7)
     words = make_words(30_000, rng)
     vocab = make_unigram_vocab(words) if unigram else make_vocab(words)
+    if a.utf8:
+        for p in ["cafe", "café", "naive", "naïve", "\u201c", "\u201d", "\u4e2d", "\u6587", "\u5b57", "\u7b26"] + CJK_POOL:
+            vocab.setdefault(p, len(vocab))
+        for p in [p for p in vocab if p.replace("##", "", 1).isalpha() and p.isascii() and p.replace("##", "", 1).islower()]:
+            vocab.setdefault(p.translate(CYRILLIC), len(vocab))
     distinct = make_lines(20_000, words, rng)
     lines = [distinct[i % len(distinct)] for i in range(a.lines)]
-    flagged = [ln.replace(" ", " café ", 1) if i % 10 == 0 else ln for i, ln in enumerate(lines)]
     cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
     ctx = smt.Context(0)
     ctx.prof_enable(True)
@@ -161,17 +274,11 @@ def main():
             W.write_tokenizer(os.path.join(d, "tokenizer.json"), 7, vocab=vocab)
         with open(os.path.join(d, "config.json"), "w") as f:
             json.dump({"normalize": True, "unk_token": "<unk>" if unigram else "[UNK]"}, f)
-        for corpus_name, corpus in (("ascii", lines), ("ten_percent_flagged", flagged)):
-            content_b = ("\n".join(corpus) + "\n").encode()
-            query_b = corpus[17].encode()
-            entry = {"text_bytes": len(content_b)}
-            for setting, on in (("off", False), ("on", True)):
-                m = host.StaticModel(ctx, model_dir=d, device_tokenizer=on)
-                entry[setting] = run(ctx, m, content_b, query_b, a.lines)
-                m.close()
-            entry["on_over_off"] = round(entry["on"]["lines_per_s"] / entry["off"]["lines_per_s"], 3)
-            entry["same_first_hit"] = entry["on"]["first_hit"] == entry["off"]["first_hit"]
-            result[corpus_name] = entry
+        if a.utf8:
+            measure_utf8(ctx, d, lines, a.lines, result)
+        else:
+            flagged = [ln.replace(" ", " café ", 1) if i % 10 == 0 else ln for i, ln in enumerate(lines)]
+            measure_on_off(ctx, d, (("ascii", lines), ("ten_percent_flagged", flagged)), a.lines, result)
     ctx.close()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     merged = {}

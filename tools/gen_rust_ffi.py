@@ -62,6 +62,18 @@ pub struct SmtWordpieceParams {
     pub n_added: u32,
 }
 
+/// what every code point >= U+0080 becomes, for the UTF-8 form of the device tokenizer (smt_wordpiece_create_utf8 copies everything)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SmtWordpieceCodepoints {
+    pub first: *const u32,
+    pub last: *const u32,
+    pub cls: *const u8,
+    pub out_pool: *const c_char,
+    pub out_off: *const u32,
+    pub n: u64,
+}
+
 /// a Unigram vocabulary, Metaspace's settings and the byte table for the device tokenizer (smt_unigram_create copies everything)
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
