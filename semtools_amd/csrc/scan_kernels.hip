@@ -23,6 +23,7 @@
 #include "device_utils.h"
 #include "device_flags.h"
 #include "chunk_deal.h"
+#include "shared_list.h"
 
 namespace smt {
 
@@ -867,11 +868,12 @@ static inline size_t pair_smem_bytes(int threads)
 // query g in row g of the wave.  Phase B, behind a wave-uniform n_on > 4, keeps <c, c> (one register) and runs queries 4 .. 7
 // through the same heads, row steps and tail (wave_sum4_group_tail_queries: the query trees' additions without the <c, c>
 // column), query g + 4 in row g -- so every query's nominations are bit for bit the one-query loop's (the row-not-quad rule).
-// A lane holds two 16-byte LDS records, its query's of phase A and of phase B.
-// Eight lists at a register pair each do not fit 64 VGPRs: a pair holds two, query g's in lanes 0 .. 31 and query g + 4's in lanes
-// 32 .. 63, so this kernel serves kp <= 32.  An insert works inside its half: the position is counted from that half of the ballot,
-// the shifted entry is taken only by the half's lanes above the position (lane 32 never takes lane 31's), the threshold is read
-// from lane kp - 1 of the half.  The first kp entries of a sorted list do not depend on how many are kept behind them.
+// SHARED LISTS: the block keeps ONE sorted list per query, in LDS (shared_list.h: 32 keys, so this kernel serves kp <= 32), and
+// one 16-byte record per query, {1 / |q|, q is zero, threshold}.  Lanes 16 g .. 16 g + 15 read the record of their query at the top
+// of a phase (a broadcast), test their row against its threshold, and the wave offers what passed to the lists, query-major, rows
+// ascending.  A wave sees 1 / waves of the block's rows: against the block's threshold instead of its own, one in five of the
+// inserts remains, and the block's list -- the kp smallest keys of the block's rows, whichever wave met them -- is the answer the
+// block writes: there is no merge behind the row loop.
 constexpr int WIDE_MAX = 8;       // calls one corpus pass of scan_wide_kernel serves: the leader's and up to seven taken along
 constexpr int WIDE_RECS = 64;     // records (reuse distance 64 > 14, as PAIR_RECS)
 constexpr unsigned long long WIDE_FAMILY = 1ull << 16;   // PairSlot::kp_blocks of a scan_wide_kernel launch (kp <= 64 below it, the grid above)
@@ -896,13 +898,14 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
     constexpr int U = 4;
     constexpr int NQ = WIDE_MAX;
     extern __shared__ unsigned char smem_raw[];
-    key_t64 *s_keys = reinterpret_cast<key_t64 *>(smem_raw);  // [NQ][waves][32]; during the row loop [waves][2][64] lane records
+    key_t64 *s_list = reinterpret_cast<key_t64 *>(smem_raw);  // [NQ][32]: the block's lists (shared_list.h)
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int waves_per_block = blockDim.x >> 6;
-    unsigned int *s_valid = reinterpret_cast<unsigned int *>(s_keys + (size_t)NQ * waves_per_block * 32);   // [NQ][waves] (<= 256 B)
-    f32x4 *s_q = reinterpret_cast<f32x4 *>(s_valid + 64);                                // [NQ][64]: the queries, one image per block
+    f32x4 *s_rec = reinterpret_cast<f32x4 *>(s_list + NQ * SHARED_LIST_KEYS);            // [NQ]: {1 / |q|, q is zero, threshold distance, threshold row}
+    unsigned int *s_lock = reinterpret_cast<unsigned int *>(s_rec + NQ);                 // [NQ] (64 B)
+    f32x4 *s_q = reinterpret_cast<f32x4 *>(s_lock + 16);                                 // [NQ][64]: the queries, one image per block
     unsigned long long *s_ctl = reinterpret_cast<unsigned long long *>(s_q + NQ * 64);    // [0] absorbed?, [1] calls served, [2] record state as read, [3..10] the list sets, own first
     unsigned long long *s_qptr = s_ctl + 3 + NQ;                                         // [7] queries taken along
     uint32_t *s_next = reinterpret_cast<uint32_t *>(s_qptr + (NQ - 1));                  // the block's next unclaimed chunk
@@ -911,28 +914,34 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
     const unsigned long long tag = p.step << PAIR_SHIFT;
 
     const int jj = lane & 3, gq = lane >> 4;         // this lane's row of the chunk and its query of each phase's four
-    // What a lane needs of ITS query of a phase -- 1 / |q|, "q is zero", the threshold (distance, row) -- lies in LDS as in
-    // scan_pair_kernel: two 16-byte records per lane, [wave][phase][64], in the key regions.  A query's norm goes straight into the
-    // records of its lanes (sixteen scalar registers for eight norms are not there either); a lane reads only what it wrote itself.
-    f32x4 *s_mine = reinterpret_cast<f32x4 *>(smem_raw) + wave * 128 + lane;
-    {
-        f32x4 r;   // a query that is not there: zero, nothing under its threshold
-        r.x = 0.0f;
-        r.y = 1.0f;
-        r.z = __builtin_inff();
-        r.w = __uint_as_float(0xFFFFFFFFu);
-        s_mine[0] = r;
-        s_mine[64] = r;
+    // What a lane needs of ITS query of a phase -- 1 / |q|, "q is zero", the threshold (distance, row) -- is the query's record;
+    // the norms are not held in registers (sixteen scalar registers for eight norms are not there).  Wave 0 sets up the lists, the
+    // locks, the records and the query images; the barriers below stand between its stores and the row loop.
+    typedef float norm_f32x2 __attribute__((ext_vector_type(2)));
+    const norm_f32x2 *s_norm_a = reinterpret_cast<const norm_f32x2 *>(s_rec + gq);                   // this lane's record of phase A: the norm half ...
+    const unsigned long long *s_thr_a = reinterpret_cast<const unsigned long long *>(s_rec + gq) + 1;   // ... and the threshold (phase B: four records on)
+    if (wave == 0) {
+#pragma unroll
+        for (int i = 0; i < NQ * SHARED_LIST_KEYS / 64; ++i) s_list[64 * i + lane] = KEY_PAD;
+        if (lane < NQ) {
+            f32x4 r;   // a query that is not there: zero, nothing under its threshold
+            r.x = 0.0f;
+            r.y = 1.0f;
+            r.z = __builtin_inff();               // (SHARED_LIST_OPEN)
+            r.w = __uint_as_float(0xFFFFFFFFu);
+            s_rec[lane] = r;
+            s_lock[lane] = 0u;
+        }
     }
 #define SMT_QUERY_NORM(n, qn)                                                                                     \
     do {                                                                                                          \
-        if (wave == 0) s_q[(n) * 64 + lane] = (qn);                                                               \
+        s_q[(n) * 64 + lane] = (qn);                                                                              \
         const float a2 = wave_sum((qn).x * (qn).x + (qn).y * (qn).y + (qn).z * (qn).z + (qn).w * (qn).w);         \
         const bool qz = readlane_f(a2, 0) == 0.0f;                                                                \
         const float rq = qz ? 0.0f : readlane_f(__frsqrt_rn(a2), 0);                                              \
-        if (gq == ((n) & 3)) { s_mine[64 * ((n) >> 2)].x = rq; s_mine[64 * ((n) >> 2)].y = qz ? 1.0f : 0.0f; }    \
+        if (lane == 0) { s_rec[n].x = rq; s_rec[n].y = qz ? 1.0f : 0.0f; }                                        \
     } while (0)
-    {
+    if (wave == 0) {
         const f32x4 q0 = reinterpret_cast<const f32x4 *>(p.queries)[lane];
         SMT_QUERY_NORM(0, q0);
     }
@@ -1037,60 +1046,48 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
         // a phase's images are requested together, before its first norm is reduced: seven round trips one after the other would
         // stand in front of the row loop (a slot without a call reads the first taken query again: its lanes never insert, on_mine
         // below); a pass of four or fewer does not look at phase B's slots
-        f32x4 qn[NQ - 1];
+        if (wave == 0) {
+            f32x4 qn[NQ - 1];
 #pragma unroll
-        for (int n = 1; n < NQ; ++n)
-            if (n < 4 || n_on > 4) qn[n - 1] = reinterpret_cast<const f32x4 *>((uintptr_t)uniform_u64(s_qptr[n < n_on ? n - 1 : 0]))[lane];
+            for (int n = 1; n < NQ; ++n)
+                if (n < 4 || n_on > 4) qn[n - 1] = reinterpret_cast<const f32x4 *>((uintptr_t)uniform_u64(s_qptr[n < n_on ? n - 1 : 0]))[lane];
 #pragma unroll
-        for (int n = 1; n < NQ; ++n)
-            if (n < 4 || n_on > 4) SMT_QUERY_NORM(n, qn[n - 1]);
-        __syncthreads();   // the images are wave 0's stores
+            for (int n = 1; n < NQ; ++n)
+                if (n < 4 || n_on > 4) SMT_QUERY_NORM(n, qn[n - 1]);
+        }
+        __syncthreads();   // the images and the records are wave 0's stores
     }
 #undef SMT_QUERY_NORM
 
 #define SMT_ROW_DOT(cj, qv) __builtin_fmaf((cj).w, (qv).w, __builtin_fmaf((cj).z, (qv).z, __builtin_fmaf((cj).x, (qv).x, (cj).y * (qv).y)))
 #define SMT_OPAQUE(v) asm volatile("" : "+v"(v))
-    // list pair g, half h (query g + 4 h); D4: the phase's distances, lane 16 g + j holds row j against the query
-#define SMT_WIDE_INSERT(g, h, D4)                                                                                 \
+    // a lane's record of phase h as it stands now: the norm half never changes, the threshold is one 64-bit read (shared_list.h)
+#define SMT_WIDE_RECORD(MINE, h)                                                                                  \
+    f32x4 MINE;                                                                                                   \
     do {                                                                                                          \
-        uint32_t m = (((g) < 2 ? pending_lo : pending_hi) >> (16 * ((g) & 1))) & 0xFu;                            \
-        while (m) {                                                                                               \
-            const int j = __builtin_ctz(m);                                                                       \
-            m &= m - 1;                                                                                           \
-            const float d = readlane_f(D4, 16 * (g) + j);                                                         \
-            const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)r_mine, j);                               \
-            const bool less = (ld[g] < d) || (ld[g] == d && lr[g] < r);                                           \
-            const uint64_t before = __ballot(less);                                                               \
-            const int pos = __popc((h) ? (uint32_t)(before >> 32) : (uint32_t)before);                            \
-            /* (the test of SMT_GROUP_INSERT: fewer than kp entries of this list before (d, r)) */                \
-            if (pos < kp) {                                                                                       \
-                const float sd = dpp_f<DPP_WAVE_SHR1>(ld[g]);                                                     \
-                const uint32_t sr = dpp_u<DPP_WAVE_SHR1>(lr[g]);                                                  \
-                /* (the lane's half and query asked of an opaque copy: as loop invariants they would be hoisted into a dozen */ \
-                /* scalar registers of lane masks, which the loop does not have)                                             */ \
-                int ln = lane;                                                                                    \
-                asm volatile("" : "+v"(ln));                                                                      \
-                const int at = ln - 32 * (h);   /* the lane's place in list g + 4 h: 0 .. 31 inside it */         \
-                if (at > pos && at < 32) { ld[g] = sd; lr[g] = sr; }                                              \
-                else if (at == pos) { ld[g] = d; lr[g] = r; }                                                     \
-                const float td = readlane_f(ld[g], 32 * (h) + kp - 1);                                            \
-                const uint32_t tr = (uint32_t)__builtin_amdgcn_readlane((int)lr[g], 32 * (h) + kp - 1);           \
-                if ((ln >> 4) == (g)) { s_mine[64 * (h)].z = td; s_mine[64 * (h)].w = __uint_as_float(tr); }      \
-            }                                                                                                     \
-        }                                                                                                         \
+        const norm_f32x2 nz = s_norm_a[8 * (h)];   /* (8-byte units: phase B's record is four records on) */      \
+        const unsigned long long t = shared_list_threshold(s_thr_a + 8 * (h));                                    \
+        MINE.x = nz.x;                                                                                            \
+        MINE.y = nz.y;                                                                                            \
+        MINE.z = __uint_as_float((uint32_t)t);                                                                    \
+        MINE.w = __uint_as_float((uint32_t)(t >> 32));                                                            \
     } while (0)
+    // D4: the phase's distances, lane 16 g + j holds row j against query g + 4 h.  What passed the (possibly stale) threshold is
+    // offered to the lists in the order of the ballot's bits: query-major, rows ascending.
 #define SMT_WIDE_TEST_INSERT(h, MINE, ON, AB, D4)                                                                 \
     do {                                                                                                          \
         const float D4 = dist_f32(AB, b2, (MINE).x, (MINE).y != 0.0f);                                            \
         const uint32_t thr_r_mine = __float_as_uint((MINE).w);                                                    \
         const bool cand = ((ON) & valid_mine) & ((D4 < (MINE).z) | ((D4 == (MINE).z) & (r_mine < thr_r_mine)));   \
-        const uint64_t ballot = __ballot(cand);                                                                   \
-        const uint32_t pending_lo = (uint32_t)ballot & 0x000F000Fu, pending_hi = (uint32_t)(ballot >> 32) & 0x000F000Fu; \
-        if (pending_lo | pending_hi) {   /* query-major, rows ascending */                                        \
-            SMT_WIDE_INSERT(0, h, D4);                                                                            \
-            SMT_WIDE_INSERT(1, h, D4);                                                                            \
-            SMT_WIDE_INSERT(2, h, D4);                                                                            \
-            SMT_WIDE_INSERT(3, h, D4);                                                                            \
+        uint64_t pending = __ballot(cand) & 0x000F000F000F000Full;                                                \
+        while (pending) {                                                                                         \
+            const int b = __builtin_ctzll(pending);                                                               \
+            pending &= pending - 1;                                                                               \
+            const int n = (b >> 4) + 4 * (h);                                                                     \
+            const float d = readlane_f(D4, b);                                                                    \
+            const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)r_mine, b);                               \
+            shared_list_insert(s_list + n * SHARED_LIST_KEYS, s_lock + n, reinterpret_cast<unsigned long long *>(s_rec + n) + 1, d, r, \
+                               kp, lane, pp.ctl);                                                                 \
         }                                                                                                         \
     } while (0)
     // phase A: SMT_REDUCE_GROUP4 of scan_pair_kernel, instruction for instruction up to the distance; phase B behind it
@@ -1124,7 +1121,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
             v5[3] = v2[0]; v5[4] = v2[1];                                                                         \
         }                                                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
-        const f32x4 mine = s_mine[0];                                                                             \
+        SMT_WIDE_RECORD(mine, 0);                                                                                 \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         wave_sum4_rows<5>(v5);                                                                                    \
         wave_sum4_group_tail(v5[0], v5[1], v5[2], v5[3], v5[4]);                                                  \
@@ -1154,7 +1151,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
                 v4[2] = x2[0]; v4[3] = x2[1];                                                                     \
             }                                                                                                     \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
-            const f32x4 mine_b = s_mine[64];                                                                      \
+            SMT_WIDE_RECORD(mine_b, 1);                                                                           \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
             wave_sum4_rows<4>(v4);                                                                                \
             wave_sum4_group_tail_queries(v4[0], v4[1], v4[2], v4[3]);                                             \
@@ -1162,13 +1159,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
         }                                                                                                         \
     } while (0)
     const bool on_mine = gq < n_on, on_mine_b = gq + 4 < n_on;   // (an absent query has thr = +inf and must never insert)
-    float ld[4];
-    uint32_t lr[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        ld[g] = __builtin_inff();
-        lr[g] = 0xFFFFFFFFu;
-    }
     // (the two-buffer pipeline of scan_pair_kernel: one chunk in flight per wave, the claims in the same order)
 #define SMT_WIDE_STEP(cur, nxt)                                                                                   \
     do {                                                                                                          \
@@ -1188,51 +1178,22 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
 #undef SMT_WIDE_STEP
 #undef SMT_REDUCE_WIDE
 #undef SMT_WIDE_TEST_INSERT
-#undef SMT_WIDE_INSERT
+#undef SMT_WIDE_RECORD
 #undef SMT_OPAQUE
 #undef SMT_ROW_DOT
     __syncthreads();
     if (wave == 0 && lane == 0) (void)__hip_atomic_fetch_add(p.gate, (unsigned long long)n_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // block merge, two queries at a time: the lower half of the wave ranks list g, the upper half list g + 4
-    const int half = lane >> 5, l5 = lane & 31;      // this lane's list of a register pair and its place in it
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if (g >= n_on) break;
-        const bool have = l5 < kp && lr[g] != 0xFFFFFFFFu;
-        s_keys[((size_t)(g + 4 * half) * waves_per_block + wave) * 32 + l5] = have ? make_key(ld[g], lr[g]) : KEY_PAD;
-        const uint64_t kept = __ballot(have);
-        if (lane == 0) {
-            s_valid[g * waves_per_block + wave] = (unsigned int)__popc((uint32_t)kept);
-            s_valid[(g + 4) * waves_per_block + wave] = (unsigned int)__popc((uint32_t)(kept >> 32));
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if (g >= n_on) break;
-        const int n = g + 4 * half;
-        if (n >= n_on) continue;   // (the upper half of a pass that does not serve query g + 4)
-        const key_t64 *keys_n = s_keys + (size_t)n * waves_per_block * 32;
-        key_t64 *out = reinterpret_cast<key_t64 *>((uintptr_t)s_ctl[3 + n]) + (size_t)blockIdx.x * kp;
-        const key_t64 mine = keys_n[wave * 32 + l5];
-        if (mine != KEY_PAD) {
-            int rank = 0;
-            for (int w = 0; w < waves_per_block; ++w)
-                for (int i = 0; i < kp; ++i) rank += (keys_n[w * 32 + i] < mine) ? 1 : 0;
-            if (rank < kp) out[rank] = mine;
-        }
-        if (wave == 0 && l5 < kp) {   // the padding: slots [valid keys of the block, kp)
-            unsigned int total = 0;
-            for (int w = 0; w < waves_per_block; ++w) total += s_valid[n * waves_per_block + w];
-            if ((unsigned int)l5 >= total) out[l5] = KEY_PAD;
-        }
+    // the block's lists are its answer, sorted and padded: wave w writes those of queries w, w + waves, ...
+    for (int n = wave; n < n_on; n += waves_per_block) {
+        key_t64 *out = reinterpret_cast<key_t64 *>((uintptr_t)uniform_u64(s_ctl[3 + n])) + (size_t)blockIdx.x * kp;
+        if (lane < kp) out[lane] = s_list[n * SHARED_LIST_KEYS + lane];
     }
 }
-// dynamic LDS of a scan_wide_kernel launch: the eight key regions (32 keys a wave), the waves' key counts, the query images, the
-// block's control words
+// dynamic LDS of a scan_wide_kernel launch: the eight lists (32 keys each, whatever the block's size), the queries' records, the
+// lock words, the query images, the block's control words
 static inline size_t wide_smem_bytes(int threads)
 {
-    return (size_t)WIDE_MAX * (threads / 64) * 32 * sizeof(key_t64) + 256 + (size_t)WIDE_MAX * 1024 + 18 * 8 + 16;
+    return (size_t)WIDE_MAX * 32 * sizeof(key_t64) + (size_t)WIDE_MAX * 16 + 64 + (size_t)WIDE_MAX * 1024 + 18 * 8 + 16;
 }
 
 // ------------------------------------------------------------------ launchers
@@ -1292,7 +1253,7 @@ static ScanPlan plan_scan(const smt_ctx *ctx, const ScanArgs &a)
     // scan_pair: the launch may share its corpus pass with the call two steps later, or be absorbed by the one two steps earlier
     // (scan_pair_kernel).  Not with wave stamps (profiling of the plain kernel).
     pl.pair = pl.overlap && ctx->tune.scan_pair && pl.U == 4 && ctx->tune.scan_debug_ptr == 0;
-    // more than three calls taken along: scan_wide_kernel, whose half-wave lists hold 32 keys and whose LDS is sized for 8 waves
+    // more than three calls taken along: scan_wide_kernel, whose shared lists hold 32 keys and whose launch bound is 8 waves
     pl.wide = pl.pair && ctx->tune.scan_pair > GROUP_MAX - 1 && pl.kp <= 32 && pl.threads <= 512;
     pl.st = ctx->stream;
     return pl;
