@@ -836,6 +836,11 @@ int smt_debug_scan_groups(smt_ctx *ctx, uint64_t *by_size /* [4] */);
  * empty, whichever kernel served them.  With scan_take > 3, absorbed <= 7 x paired.  Synchronises. */
 int smt_debug_scan_groups_wide(smt_ctx *ctx, uint64_t *by_size /* [8] */);
 
+/* The launches of the sixteen-call kernel alone (tuning key scan_deep above 7): by_size[n - 1] = scans of scan_deep_kernel that
+ * served n calls, n = 1..16.  The eight entries above do not count these launches beyond by_size[0], which counts every scan that
+ * ran alone; smt_debug_scan_pairs counts them like any other.  All zero while scan_deep_kernel does not run.  Synchronises. */
+int smt_debug_scan_groups_deep(smt_ctx *ctx, uint64_t *by_size /* [16] */);
+
 /* Test hook for the SPMD error paths of multi-process groups: arms ONE injected failure with status `code` (an SMT_E_* value) on
  * THIS process's ranks; it fires at the next step of kind `where` and disarms.  The tests arm it on one rank of an n-rank group and
  * check that every rank returns `code` from the same call and that none is left waiting inside a collective.
@@ -946,10 +951,13 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *                        changes.  A launch bracketed by profiling events and its successor neither take nor are taken, and a
  *                        call made while the GPU keeps up runs the plain kernel.  1 = pairs only.  Switching it drains the
  *                        pipeline.  The key sets the limit that scan_take sets, within the range of the four-call kernel
- *   scan_take (0..7)     the same limit with the range of the eight-call kernel (default 7): above 3, a launch whose lists hold at
+ *   scan_take (0..7)     the same limit with the range of the eight-call kernel: above 3, a launch whose lists hold at
  *                        most 32 candidates (top_k <= 24 at the default guard_band) in blocks of at most 512 threads runs
  *                        scan_wide_kernel and looks for the calls two, four, ... fourteen steps later; any other launch runs as
  *                        with scan_pair = 3.  Switching it drains the pipeline
+ *   scan_deep (0..15)    the same limit with the range of the sixteen-call kernel: above 7, a launch that scan_take would give to
+ *                        scan_wide_kernel runs scan_deep_kernel and looks for the calls two, four, ... thirty steps later; up to 7
+ *                        the key is scan_take.  The default limit is 15.  Switching it drains the pipeline
  *   scan_pair_ring (64..4096, a power of two)  scan_pair: slots of the descriptor ring in use.  A call can be taken along while the
  *                        host is fewer calls ahead of the GPU than this; a call further ahead simply scans for itself.  Switching
  *                        it drains the pipeline (default 4096; tests use 64 to see slots reused)

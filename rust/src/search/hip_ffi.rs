@@ -849,6 +849,7 @@ extern "C" {
     pub fn smt_debug_scan_pairs(ctx: *mut SmtCtx, paired: *mut u64, alone: *mut u64, absorbed: *mut u64) -> c_int;
     pub fn smt_debug_scan_groups(ctx: *mut SmtCtx, by_size: *mut u64) -> c_int;
     pub fn smt_debug_scan_groups_wide(ctx: *mut SmtCtx, by_size: *mut u64) -> c_int;
+    pub fn smt_debug_scan_groups_deep(ctx: *mut SmtCtx, by_size: *mut u64) -> c_int;
     pub fn smt_debug_group_fail_next(group: *mut SmtGroup, where_: c_int, code: c_int) -> c_int;
     pub fn smt_debug_batched_scores(
         corpus: *mut SmtCorpus,

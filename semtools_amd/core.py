@@ -81,7 +81,7 @@ class Context:
         """(paired, alone, absorbed): one-query scans of the scan_overlap pipeline that took the query of the call two steps later
         along, ran alone, or were absorbed by the call two steps earlier (smt_debug_scan_pairs).  Synchronises.  With scan_pair > 1 a
         scan takes up to three later calls along: paired counts the scans that took any, absorbed every scan that ended at once.
-        Tuning keys: scan_pair (0..3 calls taken along; scan_take: the same limit, 0..7, default 7; switching either drains the pipeline), scan_pair_ring (slots of the descriptor ring in
+        Tuning keys: scan_pair (0..3 calls taken along; scan_take: the same limit, 0..7; scan_deep: the same limit, 0..15, the default 15; switching any of them drains the pipeline), scan_pair_ring (slots of the descriptor ring in
         use, 64..4096) and, for tests, scan_pair_wait_us (0..5000: the deciding block waits that long for the later call)."""
         v = [C.c_uint64(0) for _ in range(3)]
         L.check(L.lib().smt_debug_scan_pairs(self._h, *[C.byref(x) for x in v]))
@@ -95,10 +95,18 @@ class Context:
         return tuple(int(x) for x in v)
 
     def scan_groups_wide(self):
-        """by_size: the same for n = 1..8 (smt_debug_scan_groups_wide): with the tuning key scan_take above 3 (0..7, default 7; the
+        """by_size: the same for n = 1..8 (smt_debug_scan_groups_wide): with the tuning key scan_take above 3 (0..7; the
         limit scan_pair sets, with the range of the eight-call kernel) a pass serves up to eight calls.  Synchronises."""
         v = (C.c_uint64 * 8)()
         L.check(L.lib().smt_debug_scan_groups_wide(self._h, v))
+        return tuple(int(x) for x in v)
+
+    def scan_groups_deep(self):
+        """by_size: launches of the sixteen-call kernel by calls served, n = 1..16 (smt_debug_scan_groups_deep): with the tuning key
+        scan_deep above 7 (0..15, the default 15; the limit scan_pair and scan_take set, with the range of the sixteen-call kernel) a pass serves up
+        to sixteen calls.  scan_groups_wide() counts these launches only where they ran alone.  Synchronises."""
+        v = (C.c_uint64 * 16)()
+        L.check(L.lib().smt_debug_scan_groups_deep(self._h, v))
         return tuple(int(x) for x in v)
 
     def compact_stats(self, reset=False):

@@ -53,8 +53,8 @@ int ensure_async(smt_ctx *ctx)
 int ensure_overlap(smt_ctx *ctx)
 {
     if (ctx->ov_stream[0]) return SMT_OK;
-    SMT_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&ctx->d_gate), 128));
-    SMT_HIP_CHECK(hipMemsetAsync(ctx->d_gate, 0, 128, ctx->stream));
+    SMT_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&ctx->d_gate), 256));
+    SMT_HIP_CHECK(hipMemsetAsync(ctx->d_gate, 0, 256, ctx->stream));
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     ctx->gate_total = 0;
     ctx->gate_prev_blocks = 0;
@@ -405,6 +405,7 @@ void smt_ctx_destroy(smt_ctx *ctx)
     if (ctx->d_gate) (void)hipFree(ctx->d_gate);
     if (ctx->d_pair_recs) (void)hipFree(ctx->d_pair_recs);
     if (ctx->d_wide_recs) (void)hipFree(ctx->d_wide_recs);
+    if (ctx->d_deep_recs) (void)hipFree(ctx->d_deep_recs);
     if (ctx->h_pair_ring) (void)hipHostFree(ctx->h_pair_ring);
     if (ctx->d_flags) (void)hipFree(ctx->d_flags);
     if (ctx->d_status) (void)hipFree(ctx->d_status);
@@ -491,6 +492,20 @@ try {
     if (ctx->d_gate) SMT_HIP_CHECK(hipMemcpy(v, ctx->d_gate + 2, sizeof(v), hipMemcpyDeviceToHost));
     by_size[0] = v[1] + ctx->pair_alone_host;
     for (int n = 1; n < 8; ++n) by_size[n] = v[2 + n];
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_scan_groups_deep(smt_ctx *ctx, uint64_t *by_size)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    SMT_REQUIRE(by_size != nullptr, "null argument");
+    if ((rc = bind_device(ctx))) return rc;
+    SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if ((rc = sync_side_streams(ctx))) return rc;
+    unsigned long long v[16] = {};   // launches of scan_deep_kernel that served 1 .. 16 calls (scan_kernels.hip DeepParams::ctl)
+    if (ctx->d_gate) SMT_HIP_CHECK(hipMemcpy(v, ctx->d_gate + 12, sizeof(v), hipMemcpyDeviceToHost));
+    for (int n = 0; n < 16; ++n) by_size[n] = v[n];
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
@@ -616,6 +631,11 @@ try {
         int rc2 = drain_async(ctx);
         if (rc2) return rc2;
         SMT_REQUIRE(value >= 0 && value <= 7, "scan_take: 0..7 later calls a queued scan may take along");
+        ctx->tune.scan_pair = (int)value;
+    } else if (k == "scan_deep") {   // ... and with scan_deep_kernel's
+        int rc2 = drain_async(ctx);
+        if (rc2) return rc2;
+        SMT_REQUIRE(value >= 0 && value <= 15, "scan_deep: 0..15 later calls a queued scan may take along");
         ctx->tune.scan_pair = (int)value;
     } else if (k == "scan_pair_ring") {
         SMT_REQUIRE(value >= 64 && value <= 4096 && (value & (value - 1)) == 0, "scan_pair_ring: a power of two, 64..4096 slots");

@@ -65,7 +65,7 @@ struct Tuning {
     int async_select = 0;       // 1: single-query top-k searches overlap their select stage with the next scan
     int scan_overlap = 1;       // async_select, smt_search_topk_device: scan + select of call i on internal stream i & 1 (consecutive scans overlap; 0 = the aux-stream / flag pipeline)
     int scan_gate_pct = -1;     // scan_overlap: a scan's blocks start once this share of its predecessor call's blocks has finished its rows (0 = no gate; -1, the default: 50 in every mode -- DESIGN.md 4.1 has the sweeps)
-    int scan_pair = 7;          // scan_overlap: a scan that starts behind a predecessor takes the queries of up to this many later calls of its stream (steps + 2, + 4, ...) along in the same corpus pass (key scan_pair: 0..3, scan_kernels.hip scan_pair_kernel; key scan_take: 0..7, above 3 scan_wide_kernel where it applies)
+    int scan_pair = 15;         // scan_overlap: a scan that starts behind a predecessor takes the queries of up to this many later calls of its stream (steps + 2, + 4, ...) along in the same corpus pass (key scan_pair: 0..3, scan_kernels.hip scan_pair_kernel; key scan_take: 0..7, above 3 scan_wide_kernel where it applies; key scan_deep: 0..15, above 7 scan_deep_kernel)
     int scan_pair_ring = 4096;  // scan_pair: slots of the descriptor ring in use (a power of two, 64 .. 4096): a call is found by the scan two steps earlier while the host is fewer calls ahead of the GPU than this (tests use 64 to see slots reused)
     int scan_pair_wait_us = 0;  // scan_pair, tests only: the deciding block waits this long (<= 5000) for the partner's descriptor
     int gemm_image = 1;         // 1: batched searches read the corpus' fp16 operand image when it has one (0: A/B only)
@@ -142,10 +142,11 @@ struct smt_ctx {
     uint64_t gate_prev_blocks = 0;           // ... and of the latest one
     uint64_t gate_prev_rows = 0;
     // scan_pair: the descriptor ring (pinned host memory, one slot per step) and the per-step decision records (device); the
-    // counters and the wait-ran-out flag live behind the gate counter, d_gate[1..11] of 16 (scan_kernels.hip PairParams::ctl, WideParams::ctl)
+    // counters and the wait-ran-out flag live behind the gate counter, d_gate[1..27] of 32 (scan_kernels.hip PairParams::ctl, WideParams::ctl, DeepParams::ctl)
     void *h_pair_ring = nullptr;
     void *d_pair_recs = nullptr;
     void *d_wide_recs = nullptr;             // scan_take: the records of scan_wide_kernel launches
+    void *d_deep_recs = nullptr;             // scan_deep: the records of scan_deep_kernel launches
     uint64_t pair_alone_host = 0;            // scan_pair calls that got the plain kernel: nothing queued in front of them, or profiled (smt_debug_scan_pairs counts them as alone)
     bool pair_live = false;                  // paired-mode scans were launched since the last drain (their error flag is unread)
     unsigned int *d_steal = nullptr;         // K2 STEAL: 64 group counters, one per launch in rotation (scan_kernels.hip)

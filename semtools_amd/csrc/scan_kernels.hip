@@ -1,5 +1,5 @@
 // scan_kernels.hip -- K2 (single/few-query cosine scan + per-wave top-k'): scan_topk_kernel, the grouped
-// scan_pair_kernel (up to four calls per pass) and scan_wide_kernel (up to eight) with their host/device pairing
+// scan_pair_kernel (up to four calls per pass), scan_wide_kernel (up to eight) and scan_deep_kernel (up to sixteen) with their host/device pairing
 // protocol, and launch_scan_topk, which runs the passes of a call
 // and hands the block lists to the select stage (select.hip; optionally overlapped with the next scan: async
 // select).  The chunk table of range-filtered scans is built in range_tables.hip, the cross-shard top-k merge
@@ -1196,6 +1196,419 @@ static inline size_t wide_smem_bytes(int threads)
     return (size_t)WIDE_MAX * 32 * sizeof(key_t64) + (size_t)WIDE_MAX * 16 + 64 + (size_t)WIDE_MAX * 1024 + 18 * 8 + 16;
 }
 
+// ------------------------------------------------------------- K2, groups of sixteen (tuning key scan_deep)
+// scan_wide_kernel with twice the reach: a leader of step i reads the slots of steps i + 2 .. i + 30 and takes the longest prefix
+// that passes, up to fifteen calls, so one corpus pass serves up to sixteen.  What a pass costs beyond its queries' trees -- the row
+// loads and their waits, the <c, c> tree, the chunk claims, the loop -- is paid once per pass, whatever it serves.  A launch of
+// this kernel says so in its slot (DEEP_FAMILY in kp_blocks) and has a record of its own kind (DeepRecord, an array of its own): a
+// leader takes launches of its own kernel only, and the two older kernels refuse these by their compare.  Marks, the own-record
+// test, the bounded waits, the error flag, the gate and the first rows requested before the decision is known are theirs.
+// A chunk is reduced in FOUR phases over the same sixteen row registers.  Phase 0 is scan_wide_kernel's phase A; phases 1 .. 3 are
+// its phase B, written once (SMT_DEEP_PHASE) and instanced three times, each behind a wave-uniform n_on > 4 h: query 4 h + g in row g of
+// the wave, <c, c> kept in one register -- every query's nominations are bit for bit the one-query loop's (the row-not-quad rule).
+// The lists are scan_wide_kernel's shared lists (shared_list.h, kp <= 32), sixteen of them.
+// THE DECISION is taken by a wave, not a thread: group_decide reads slot after slot from pinned host memory, three dependent round
+// trips each, and fifteen slots in a row would stand in front of every block of the leader.  Here lane j reads the slot of step
+// i + 2 (j + 1), fields and both step checks included, one ballot gives the prefix, the lanes below it write the marks and the
+// record's entries, and one agent-scope release publishes the lot.
+constexpr int DEEP_MAX = 16;      // calls one corpus pass of scan_deep_kernel serves: the leader's and up to fifteen taken along
+constexpr int DEEP_RECS = 64;     // records (reuse distance 64 > 30, as PAIR_RECS)
+constexpr unsigned long long DEEP_FAMILY = 1ull << 17;   // PairSlot::kp_blocks of a scan_deep_kernel launch (next to WIDE_FAMILY)
+struct DeepRecord {   // 256 bytes
+    unsigned long long state;       // as PairRecord
+    unsigned long long taken;       // PAIR_PAIRED: calls taken along (1 .. DEEP_MAX - 1) ...
+    unsigned long long query[DEEP_MAX - 1], lists[DEEP_MAX - 1];   // ... and theirs
+};
+static_assert(sizeof(DeepRecord) == 256, "DeepRecord: state, taken and fifteen (query, lists) pairs");
+struct DeepParams {
+    const PairSlot *ring;
+    DeepRecord *recs;
+    unsigned long long *ctl;        // PairParams::ctl; [11..26] launches of this kernel that served 1 .. 16 calls
+    unsigned int absorbable;
+    unsigned int max_take;          // tuning key scan_deep: calls a launch may take along (1 .. DEEP_MAX - 1)
+    unsigned long long wait_ticks;
+    unsigned long long ring_mask;
+};
+constexpr int DEEP_CTL_BY_SIZE = 11;
+
+// The deciding WAVE (all 64 lanes): group_decide with the slots read side by side.  A lane's slot is PENDING until its step number
+// is there, then passes or fails once and for all (the same tests in the same order as group_decide: step, fields, step again);
+// what is taken is the run of passing lanes from lane 0.  Only the first lane behind that run is waited for, as long as
+// scan_pair_wait_us allows, for all of them together: the slot group_decide would be waiting at.  Returns the calls taken
+// (wave-uniform); the caller publishes.
+__device__ __forceinline__ unsigned int deep_decide(const ScanParams &p, const DeepParams &pp, DeepRecord *rec, int lane)
+{
+    enum : int { SLOT_PENDING = 0, SLOT_PASS = 1, SLOT_FAIL = 2 };
+    const unsigned long long t0 = wall_clock64();
+    const unsigned long long want = p.step + 2ull * (unsigned long long)(lane + 1);
+    const PairSlot *s = pp.ring + (want & pp.ring_mask);
+    const unsigned long long expect = (unsigned long long)p.kp | DEEP_FAMILY | (unsigned long long)gridDim.x << 32;
+    int status = (unsigned int)lane < pp.max_take ? SLOT_PENDING : SLOT_FAIL;   // (max_take <= 15: lanes 15 .. 63 never pass)
+    unsigned long long query = 0, lists = 0;
+    unsigned int taken = 0;
+    for (;;) {
+        if (status == SLOT_PENDING) {
+            const unsigned long long s1 = __hip_atomic_load(&s->step, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (s1 == want) {
+                const unsigned long long corpus = sys_load(&s->corpus), n_virtual = sys_load(&s->n_virtual), kp_blocks = sys_load(&s->kp_blocks);
+                const unsigned long long absorbable = sys_load(&s->absorbable);
+                query = sys_load(&s->query);
+                lists = sys_load(&s->lists);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+                const bool still = sys_load(&s->step) == want;   // (or the host was rewriting the slot, a ring's length ahead)
+                const bool same = corpus == (unsigned long long)(uintptr_t)p.corpus && n_virtual == p.n_virtual && kp_blocks == expect;
+                status = (still && absorbable && same) ? SLOT_PASS : SLOT_FAIL;
+            } else if (s1 > want) {
+                status = SLOT_FAIL;   // (a LATER step's number: the slot was reused)
+            }
+        }
+        const unsigned long long pass = __ballot(status == SLOT_PASS);
+        taken = (unsigned int)__builtin_ctzll(~pass);
+        const bool waited_for = status == SLOT_PENDING && (unsigned int)lane == taken;
+        if (__ballot(waited_for) == 0ull || pp.wait_ticks == 0ull || wall_clock64() - t0 >= pp.wait_ticks) break;
+        __builtin_amdgcn_s_sleep(32);
+    }
+    if ((unsigned int)lane < taken) {
+        flag_store(&rec->query[lane], query);
+        flag_store(&rec->lists[lane], lists);
+        flag_store(&pp.recs[want % DEEP_RECS].state, (want << PAIR_SHIFT) | PAIR_ABSORBED);   // the mark
+    }
+    if (lane == 0) flag_store(&rec->taken, (unsigned long long)taken);
+    return taken;
+}
+
+template <bool NT>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) scan_deep_kernel(ScanParams p, DeepParams pp)
+{
+    constexpr int U = 4;
+    constexpr int NQ = DEEP_MAX;
+    extern __shared__ unsigned char smem_raw[];
+    key_t64 *s_list = reinterpret_cast<key_t64 *>(smem_raw);  // [NQ][32]: the block's lists (shared_list.h)
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int waves_per_block = blockDim.x >> 6;
+    f32x4 *s_rec = reinterpret_cast<f32x4 *>(s_list + NQ * SHARED_LIST_KEYS);            // [NQ]: {1 / |q|, q is zero, threshold distance, threshold row}
+    unsigned int *s_lock = reinterpret_cast<unsigned int *>(s_rec + NQ);                 // [NQ] (64 B)
+    f32x4 *s_q = reinterpret_cast<f32x4 *>(s_lock + 16);                                 // [NQ][64]: the queries, one image per block
+    unsigned long long *s_ctl = reinterpret_cast<unsigned long long *>(s_q + NQ * 64);    // [0] absorbed?, [1] calls served, [2] record state as read, [3..18] the list sets, own first
+    unsigned long long *s_qptr = s_ctl + 3 + NQ;                                         // [15] queries taken along
+    uint32_t *s_next = reinterpret_cast<uint32_t *>(s_qptr + (NQ - 1));                  // the block's next unclaimed chunk
+    const int kp = (int)p.kp;
+    DeepRecord *rec = pp.recs + p.step % DEEP_RECS;
+    const unsigned long long tag = p.step << PAIR_SHIFT;
+
+    const int jj = lane & 3, gq = lane >> 4;         // this lane's row of the chunk and its query of each phase's four
+    // (the records, the lists and the locks: see scan_wide_kernel.  Wave 0 sets them up and the leader's image; the images of the
+    // calls taken along are set up phase by phase, wave h those of phase h)
+    typedef float norm_f32x2 __attribute__((ext_vector_type(2)));
+    const norm_f32x2 *s_norm_a = reinterpret_cast<const norm_f32x2 *>(s_rec + gq);                   // this lane's record of phase 0: the norm half ...
+    const unsigned long long *s_thr_a = reinterpret_cast<const unsigned long long *>(s_rec + gq) + 1;   // ... and the threshold (phase h: 4 h records on)
+    if (wave == 0) {
+#pragma unroll
+        for (int i = 0; i < NQ * SHARED_LIST_KEYS / 64; ++i) s_list[64 * i + lane] = KEY_PAD;
+        if (lane < NQ) {
+            f32x4 r;   // a query that is not there: zero, nothing under its threshold
+            r.x = 0.0f;
+            r.y = 1.0f;
+            r.z = __builtin_inff();               // (SHARED_LIST_OPEN)
+            r.w = __uint_as_float(0xFFFFFFFFu);
+            s_rec[lane] = r;
+            s_lock[lane] = 0u;
+        }
+    }
+#define SMT_QUERY_NORM(n, qn)                                                                                     \
+    do {                                                                                                          \
+        s_q[(n) * 64 + lane] = (qn);                                                                              \
+        const float a2 = wave_sum((qn).x * (qn).x + (qn).y * (qn).y + (qn).z * (qn).z + (qn).w * (qn).w);         \
+        const bool qz = readlane_f(a2, 0) == 0.0f;                                                                \
+        const float rq = qz ? 0.0f : readlane_f(__frsqrt_rn(a2), 0);                                              \
+        if (lane == 0) { s_rec[n].x = rq; s_rec[n].y = qz ? 1.0f : 0.0f; }                                        \
+    } while (0)
+    if (wave == 0) {
+        const f32x4 q0 = reinterpret_cast<const f32x4 *>(p.queries)[lane];
+        SMT_QUERY_NORM(0, q0);
+
+        // lane 0 looks at the record and the gate as thread 0 of scan_wide_kernel does; the block that wins the record decides with
+        // its whole wave (deep_decide), while the others wait at the gate
+        unsigned long long g = 0, cur = 0;
+        unsigned int absorbed = 0, won = 0;
+        if (lane == 0) {
+            *s_next = (uint32_t)waves_per_block;
+            g = p.gate_open ? flag_load(p.gate) : 0ull;
+            cur = flag_load(&rec->state);
+            if (pp.absorbable && cur == (tag | PAIR_ABSORBED))
+                absorbed = 1;   // (marked by the leader, an earlier launch of this stream)
+            else if ((cur >> PAIR_SHIFT) != p.step &&
+                     __hip_atomic_compare_exchange_strong(&rec->state, &cur, tag | PAIR_DECIDING, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                          __HIP_MEMORY_SCOPE_AGENT))
+                won = 1;
+        }
+        if (__builtin_amdgcn_readfirstlane((int)won) != 0) {
+            const unsigned int taken = deep_decide(p, pp, rec, lane);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // every lane's entries and marks before lane 0's state
+            if (lane == 0) {
+                cur = tag | (taken ? PAIR_PAIRED : PAIR_ALONE);
+                __hip_atomic_store(&rec->state, cur, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                (void)__hip_atomic_fetch_add(pp.ctl + (taken ? 1 : 2), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                (void)__hip_atomic_fetch_add(pp.ctl + DEEP_CTL_BY_SIZE + taken, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        if (lane == 0) {
+            if (!absorbed && g < p.gate_open) gate_wait(p);
+            s_ctl[0] = absorbed ? PAIR_ABSORBED : 0ull;
+            s_ctl[2] = cur;
+            s_ctl[3] = (unsigned long long)(uintptr_t)p.block_lists;
+        }
+    }
+    __syncthreads();
+    if (uniform_u64(s_ctl[0]) == PAIR_ABSORBED) {
+        if (blockIdx.x == 0 && wave == 0 && lane == 0)
+            (void)__hip_atomic_fetch_add(pp.ctl + 3, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+
+    // (the chunk deal, the scalar row test and the scalar row addresses: see scan_pair_kernel)
+    auto chunk_v0 = [&](uint32_t t) -> uint64_t { return deal_chunk(t, waves_per_block) * U; };
+    auto claim = [&]() -> uint32_t { return deal_claim(s_next, lane); };
+    auto in_corpus = [&](uint64_t v) -> bool {
+        uint32_t hi = (uint32_t)((v - p.n_virtual) >> 32);
+        asm("" : "+s"(hi));
+        return (int32_t)hi < 0;
+    };
+    typedef const f32x4 __attribute__((address_space(1))) *global_rows_ptr;
+    auto row_ptr = [&](uint64_t v) -> global_rows_ptr {
+        uint64_t base = (uint64_t)(uintptr_t)p.corpus + v * 1024u;
+        asm volatile("" : "+s"(base));
+        return (global_rows_ptr)(uintptr_t)base + lane;
+    };
+    auto issue_rows = [&](uint64_t v0, f32x4 (&c)[U]) {
+        if (in_corpus(v0 + (U - 1))) {   // (uniform)
+            const global_rows_ptr src = row_ptr(v0);
+#pragma unroll
+            for (int j = 0; j < U; ++j) c[j] = NT ? __builtin_nontemporal_load(src + 64 * j) : src[64 * j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                uint64_t v = v0 + j;
+                if (!in_corpus(v)) v = p.n_virtual - 1;  // clamp (result discarded)
+                const global_rows_ptr src = row_ptr((uint64_t)(uint32_t)v);
+                c[j] = NT ? __builtin_nontemporal_load(src) : *src;
+                asm volatile("" : "+v"(c[j]));
+            }
+        }
+    };
+    // the first rows are on their way before the decision is known: they are the same rows either way
+    f32x4 cn[U];
+    uint64_t v0 = chunk_v0((uint32_t)wave);
+    uint64_t v0n = 0;
+    if (in_corpus(v0)) {
+        issue_rows(v0, cn);
+        v0n = chunk_v0(claim());
+    }
+
+    if (wave == 0) {
+        unsigned long long cur = 0;
+        if (lane == 0) {
+            cur = s_ctl[2];   // (this step's: the block has won the record and decided, or lost it)
+            if (cur == (tag | PAIR_DECIDING)) {   // bounded like flag_wait: a decision that never comes ends in an error code
+                const unsigned long long t0 = wall_clock64();
+                while ((cur = flag_load(&rec->state)) == (tag | PAIR_DECIDING)) {
+                    __builtin_amdgcn_s_sleep(8);
+                    if (flag_load(pp.ctl) != 0ull) break;
+                    if (wall_clock64() - t0 > 200000000ull) { flag_store(pp.ctl, 1ull); break; }
+                }
+            }
+        }
+        cur = uniform_u64(cur);   // (lane 0's)
+        unsigned long long served = 1;
+        if (cur == (tag | PAIR_PAIRED)) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            unsigned long long taken = uniform_u64(flag_load(&rec->taken));
+            if (taken > (unsigned long long)(NQ - 1)) taken = NQ - 1;   // (never: the record is this step's)
+            if ((unsigned long long)lane < taken) {   // the entries side by side, as they were written
+                s_qptr[lane] = flag_load(&rec->query[lane]);
+                s_ctl[4 + lane] = flag_load(&rec->lists[lane]);
+            }
+            served = 1 + taken;
+        } else if (cur != (tag | PAIR_ALONE)) {
+            if (lane == 0) flag_store(pp.ctl, 1ull);   // (a wait that ran out, or a record that is not this step's: alone, and the context reports it)
+        }
+        if (lane == 0) s_ctl[1] = served;
+    }
+    __syncthreads();
+    const int n_on = (int)(uint32_t)uniform_u64(s_ctl[1]);   // calls this pass serves, 1 .. NQ (an LDS read: told to be wave-uniform)
+    if (n_on > 1) {   // (uniform over the block)
+        // Wave h sets up phase h (a block of fewer waves: h, h + waves, ...): four images requested together, then their norms --
+        // four query rows in registers at a time, not fifteen.  A slot without a call reads the first taken query again (its lanes
+        // never insert); a phase the pass does not reach is not looked at.
+        for (int h = wave; 4 * h < n_on; h += waves_per_block) {
+            f32x4 qn[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int n = 4 * h + g;
+                if (n > 0) qn[g] = reinterpret_cast<const f32x4 *>((uintptr_t)uniform_u64(s_qptr[n < n_on ? n - 1 : 0]))[lane];
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int n = 4 * h + g;
+                if (n > 0) SMT_QUERY_NORM(n, qn[g]);
+            }
+        }
+        __syncthreads();   // the images and the records are other waves' stores
+    }
+#undef SMT_QUERY_NORM
+
+#define SMT_ROW_DOT(cj, qv) __builtin_fmaf((cj).w, (qv).w, __builtin_fmaf((cj).z, (qv).z, __builtin_fmaf((cj).x, (qv).x, (cj).y * (qv).y)))
+#define SMT_OPAQUE(v) asm volatile("" : "+v"(v))
+    // a lane's record of phase h as it stands now: the norm half never changes, the threshold is one 64-bit read (shared_list.h)
+#define SMT_DEEP_RECORD(MINE, h)                                                                                  \
+    f32x4 MINE;                                                                                                   \
+    do {                                                                                                          \
+        const norm_f32x2 nz = s_norm_a[8 * (h)];   /* (8-byte units: phase h's record is 4 h records on) */       \
+        const unsigned long long t = shared_list_threshold(s_thr_a + 8 * (h));                                    \
+        MINE.x = nz.x;                                                                                            \
+        MINE.y = nz.y;                                                                                            \
+        MINE.z = __uint_as_float((uint32_t)t);                                                                    \
+        MINE.w = __uint_as_float((uint32_t)(t >> 32));                                                            \
+    } while (0)
+    // D4: the phase's distances, lane 16 g + j holds row j against query g + 4 h.  What passed the (possibly stale) threshold is
+    // offered to the lists in the order of the ballot's bits: query-major, rows ascending.
+#define SMT_DEEP_TEST_INSERT(h, MINE, ON, AB, D4)                                                                 \
+    do {                                                                                                          \
+        const float D4 = dist_f32(AB, b2, (MINE).x, (MINE).y != 0.0f);                                            \
+        const uint32_t thr_r_mine = __float_as_uint((MINE).w);                                                    \
+        const bool cand = ((ON) & valid_mine) & ((D4 < (MINE).z) | ((D4 == (MINE).z) & (r_mine < thr_r_mine)));   \
+        uint64_t pending = __ballot(cand) & 0x000F000F000F000Full;                                                \
+        while (pending) {                                                                                         \
+            const int b = __builtin_ctzll(pending);                                                               \
+            pending &= pending - 1;                                                                               \
+            const int n = (b >> 4) + 4 * (h);                                                                     \
+            const float d = readlane_f(D4, b);                                                                    \
+            const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)r_mine, b);                               \
+            shared_list_insert(s_list + n * SHARED_LIST_KEYS, s_lock + n, reinterpret_cast<unsigned long long *>(s_rec + n) + 1, d, r, \
+                               kp, lane, pp.ctl);                                                                 \
+        }                                                                                                         \
+    } while (0)
+    // Phase h = 1 .. 3, scan_wide_kernel's phase B: the heads of queries 4 h and 4 h + 1, behind n_on > 4 h + 2 those of 4 h + 2 and
+    // 4 h + 3 (trees that do not exist are fed registers that are there anyway: their rows are off), the row steps of the four, ONE
+    // tail without the <c, c> column, one distance, one compare, one ballot.  b2, valid_mine and r_mine are the chunk's.
+    // (n_h: the calls of this phase and behind it, asked of an opaque scalar copy chunk by chunk: as invariants of the row loop the
+    // six compares and the three lane masks would be hoisted into eighteen scalar registers, which that loop does not have)
+#define SMT_DEEP_PHASE(cq, h)                                                                                     \
+    int n_h##h = n_on - 4 * (h);                                                                                  \
+    asm volatile("" : "+s"(n_h##h));                                                                              \
+    if (n_h##h > 0) {                                                                                             \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        const f32x4 qva = s_q[256 * (h) + lane], qvb = s_q[256 * (h) + 64 + lane];                                \
+        float parta[2][4], w2[2];                                                                                 \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                           \
+            parta[0][j] = SMT_ROW_DOT((cq)[j], qva);                                                              \
+            parta[1][j] = SMT_ROW_DOT((cq)[j], qvb);                                                              \
+        }                                                                                                         \
+        wave_sum4_multi_head<2>(parta, w2, lane);                                                                 \
+        SMT_OPAQUE(w2[0]); SMT_OPAQUE(w2[1]);                                                                     \
+        float v4[4] = {w2[0], w2[1], w2[0], w2[1]};                                                               \
+        if (n_h##h > 2) {                                                                                         \
+            __builtin_amdgcn_sched_barrier(0);                                                                    \
+            const f32x4 qvc = s_q[256 * (h) + 128 + lane], qvd = s_q[256 * (h) + 192 + lane];                     \
+            float partc[2][4], x2[2];                                                                             \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                       \
+                partc[0][j] = SMT_ROW_DOT((cq)[j], qvc);                                                          \
+                partc[1][j] = SMT_ROW_DOT((cq)[j], qvd);                                                          \
+            }                                                                                                     \
+            wave_sum4_multi_head<2>(partc, x2, lane);                                                             \
+            SMT_OPAQUE(x2[0]); SMT_OPAQUE(x2[1]);                                                                 \
+            v4[2] = x2[0]; v4[3] = x2[1];                                                                         \
+        }                                                                                                         \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        SMT_DEEP_RECORD(mine_h, h);                                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        wave_sum4_rows<4>(v4);                                                                                    \
+        wave_sum4_group_tail_queries(v4[0], v4[1], v4[2], v4[3]);                                                 \
+        SMT_DEEP_TEST_INSERT(h, mine_h, gq < n_h##h, v4[0], d4h);                                                 \
+    }
+    // phase 0: scan_wide_kernel's phase A (SMT_REDUCE_GROUP4 of scan_pair_kernel), instruction for instruction up to the distance;
+    // the other three phases behind it
+#define SMT_REDUCE_DEEP(cq, rq4, VALID)                                                                           \
+    do {                                                                                                          \
+        const f32x4 qv0 = s_q[lane];                                                                              \
+        const bool valid_mine = (uint32_t)jj < (VALID);                                                           \
+        const uint32_t r_mine = (rq4) + (uint32_t)jj;                                                             \
+        float part[3][4];                                                                                         \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) part[0][j] = SMT_ROW_DOT((cq)[j], (cq)[j]);                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        const f32x4 qv1 = s_q[64 + lane];                                                                         \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) part[1][j] = SMT_ROW_DOT((cq)[j], qv0);                     \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) part[2][j] = SMT_ROW_DOT((cq)[j], qv1);                     \
+        float v3[3];                                                                                              \
+        wave_sum4_multi_head<3>(part, v3, lane);                                                                  \
+        SMT_OPAQUE(v3[0]); SMT_OPAQUE(v3[1]); SMT_OPAQUE(v3[2]);                                                  \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        const f32x4 qv2 = s_q[128 + lane], qv3 = s_q[192 + lane];                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        float v5[5] = {v3[0], v3[1], v3[2], v3[1], v3[2]};                                                        \
+        if (n_on > 2) {                                                                                           \
+            float part2[2][4], v2[2];                                                                             \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                       \
+                part2[0][j] = SMT_ROW_DOT((cq)[j], qv2);                                                          \
+                part2[1][j] = SMT_ROW_DOT((cq)[j], qv3);                                                          \
+            }                                                                                                     \
+            wave_sum4_multi_head<2>(part2, v2, lane);                                                             \
+            SMT_OPAQUE(v2[0]); SMT_OPAQUE(v2[1]);                                                                 \
+            v5[3] = v2[0]; v5[4] = v2[1];                                                                         \
+        }                                                                                                         \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        SMT_DEEP_RECORD(mine, 0);                                                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        wave_sum4_rows<5>(v5);                                                                                    \
+        wave_sum4_group_tail(v5[0], v5[1], v5[2], v5[3], v5[4]);                                                  \
+        const float b2 = v5[0];                                                                                   \
+        SMT_DEEP_TEST_INSERT(0, mine, on_mine, v5[1], d4);                                                        \
+        SMT_DEEP_PHASE(cq, 1)                                                                                     \
+        SMT_DEEP_PHASE(cq, 2)                                                                                     \
+        SMT_DEEP_PHASE(cq, 3)                                                                                     \
+    } while (0)
+    const bool on_mine = gq < n_on;   // (an absent query has thr = +inf and must never insert)
+    // (the two-buffer pipeline of scan_pair_kernel: one chunk in flight per wave, the claims in the same order)
+#define SMT_DEEP_STEP(cur, nxt)                                                                                   \
+    do {                                                                                                          \
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"((cur)[0]), "+v"((cur)[1]), "+v"((cur)[2]), "+v"((cur)[3]) : : "memory"); \
+        if (in_corpus(v0n)) issue_rows(v0n, nxt);                                                                 \
+        const uint64_t v0nn = chunk_v0(claim());                                                                  \
+        SMT_REDUCE_DEEP(cur, (uint32_t)v0, in_corpus(v0 + (U - 1)) ? 4u : (uint32_t)(p.n_virtual - v0));          \
+        v0 = v0n;                                                                                                 \
+        v0n = v0nn;                                                                                               \
+    } while (0)
+    f32x4 cm[U];
+    while (in_corpus(v0)) {
+        SMT_DEEP_STEP(cn, cm);
+        if (!in_corpus(v0)) break;
+        SMT_DEEP_STEP(cm, cn);
+    }
+#undef SMT_DEEP_STEP
+#undef SMT_REDUCE_DEEP
+#undef SMT_DEEP_PHASE
+#undef SMT_DEEP_TEST_INSERT
+#undef SMT_DEEP_RECORD
+#undef SMT_OPAQUE
+#undef SMT_ROW_DOT
+    __syncthreads();
+    if (wave == 0 && lane == 0) (void)__hip_atomic_fetch_add(p.gate, (unsigned long long)n_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the block's lists are its answer, sorted and padded: wave w writes those of queries w, w + waves, ...
+    for (int n = wave; n < n_on; n += waves_per_block) {
+        key_t64 *out = reinterpret_cast<key_t64 *>((uintptr_t)uniform_u64(s_ctl[3 + n])) + (size_t)blockIdx.x * kp;
+        if (lane < kp) out[lane] = s_list[n * SHARED_LIST_KEYS + lane];
+    }
+}
+// dynamic LDS of a scan_deep_kernel launch: the sixteen lists (32 keys each, whatever the block's size), the queries' records, the
+// lock words, the query images, the block's control words (3 + 16 list sets + 15 query addresses) and the chunk counter
+static inline size_t deep_smem_bytes(int threads)
+{
+    return (size_t)DEEP_MAX * 32 * sizeof(key_t64) + (size_t)DEEP_MAX * 16 + 64 + (size_t)DEEP_MAX * 1024 + 34 * 8 + 16;
+}
+
 // ------------------------------------------------------------------ launchers
 static inline uint32_t candidates_per_list(const smt_ctx *ctx, uint32_t k_out)
 {
@@ -1224,6 +1637,7 @@ struct ScanPlan {
     unsigned long long gate_open = 0, gate_ticks = 0;
     bool may_pair = false;    // scan_pair: this launch runs scan_pair_kernel (it looks for a partner, and may find itself absorbed)
     bool wide = false;        // scan_take: ... or scan_wide_kernel, when the limit exceeds what scan_pair_kernel serves
+    bool deep = false;        // scan_deep: ... or scan_deep_kernel, when it exceeds what scan_wide_kernel serves
     unsigned int absorbable = 0;
 };
 
@@ -1255,6 +1669,9 @@ static ScanPlan plan_scan(const smt_ctx *ctx, const ScanArgs &a)
     pl.pair = pl.overlap && ctx->tune.scan_pair && pl.U == 4 && ctx->tune.scan_debug_ptr == 0;
     // more than three calls taken along: scan_wide_kernel, whose shared lists hold 32 keys and whose launch bound is 8 waves
     pl.wide = pl.pair && ctx->tune.scan_pair > GROUP_MAX - 1 && pl.kp <= 32 && pl.threads <= 512;
+    // more than seven: scan_deep_kernel, under the same two conditions (a launch is of ONE family: deep, else wide, else the four-call kernel)
+    pl.deep = pl.wide && ctx->tune.scan_pair > WIDE_MAX - 1;
+    if (pl.deep) pl.wide = false;
     pl.st = ctx->stream;
     return pl;
 }
@@ -1272,12 +1689,14 @@ static int enter_pipeline(smt_ctx *ctx, const ScanArgs &a, ScanPlan &pl)
     const size_t list_bytes = pl.overlap ? (size_t)SEL_MAX_LISTS * 64 * sizeof(key_t64)
                                          : (((size_t)a.nq * pl.blocks * pl.kp * sizeof(key_t64)) + 255) & ~(size_t)255;
     const size_t table_bytes = pl.filtered ? (size_t)pl.n_chunks * sizeof(uint64_t) : 0;
-    // (scan_overlap: a ring of sixteen sets, step & 15.  A leading scan of step i fills the sets of steps i, i + 2, ... i + 14, all
-    // on its own stream, and set s is shared by the steps s, s +- 16, s +- 32 ...: the last readers of the eight sets it writes are the
-    // selects of steps i - 16, i - 14, ... i - 2, launched on the SAME stream before scan i, so stream order alone has them
-    // finished.  The other stream's steps have the other parity and the other eight sets.  With fewer sets the scan of step i
-    // would write the set of step i + 14 into one that a select of the other stream, ordered against nothing here, may be reading.)
-    const size_t n_sets = pl.overlap ? 2 * WIDE_MAX : 2;
+    // (scan_overlap: a ring of thirty-two sets, step & 31, 8 MiB, whichever kernel runs.  A leading scan of step i fills the sets of
+    // steps i, i + 2, ... at most i + 30, all on its own stream, and set s is shared by the steps s, s +- 32, s +- 64 ...: the last
+    // readers of the sixteen sets it may write are the selects of steps i - 32, i - 30, ... i - 2, launched on the SAME stream before
+    // scan i, so stream order alone has them finished.  The other stream's steps have the other parity and the other sixteen sets.
+    // With fewer sets the scan of step i would write the set of step i + 30 into one that a select of the other stream, ordered
+    // against nothing here, may be reading.  A leader with a shorter reach -- scan_wide_kernel's i + 14, scan_pair_kernel's i + 6 --
+    // writes a subset of those sets: more sets than its reach needs only move a set's next writer further away.)
+    const size_t n_sets = pl.overlap ? 2 * DEEP_MAX : 2;
     if ((rc = ensure_scratch(ctx, n_sets * list_bytes + table_bytes))) return rc;
     pl.lists = reinterpret_cast<key_t64 *>(reinterpret_cast<char *>(ctx->d_scratch) + (pl.step & (n_sets - 1)) * list_bytes);
     pl.table = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(ctx->d_scratch) + n_sets * list_bytes);
@@ -1405,13 +1824,15 @@ int ensure_pair(smt_ctx *ctx)
     SMT_HIP_CHECK(hipMemset(ctx->d_pair_recs, 0, PAIR_RECS * sizeof(PairRecord)));
     SMT_HIP_CHECK(hipMalloc(&ctx->d_wide_recs, WIDE_RECS * sizeof(WideRecord)));
     SMT_HIP_CHECK(hipMemset(ctx->d_wide_recs, 0, WIDE_RECS * sizeof(WideRecord)));
+    SMT_HIP_CHECK(hipMalloc(&ctx->d_deep_recs, DEEP_RECS * sizeof(DeepRecord)));
+    SMT_HIP_CHECK(hipMemset(ctx->d_deep_recs, 0, DEEP_RECS * sizeof(DeepRecord)));
     SMT_HIP_CHECK(hipHostMalloc(&ctx->h_pair_ring, PAIR_RING * sizeof(PairSlot), hipHostMallocDefault));
     memset(ctx->h_pair_ring, 0, PAIR_RING * sizeof(PairSlot));
     return SMT_OK;
 }
 
 // Publishes this step's slot (what a predecessor needs to take the call along), then launches the group-capable one-query scan:
-// scan_pair_kernel, or scan_wide_kernel (pl.wide).
+// scan_pair_kernel, scan_wide_kernel (pl.wide) or scan_deep_kernel (pl.deep).
 template <class PP>
 static void group_params(const smt_ctx *ctx, const ScanPlan &pl, PP &pp, int max_take)
 {
@@ -1426,20 +1847,26 @@ static int launch_scan_pair(smt_ctx *ctx, const ScanParams &p, const ScanPlan &p
 {
     PairParams pp{};
     WideParams wp{};
+    DeepParams dp{};
     group_params(ctx, pl, pp, GROUP_MAX - 1);
     group_params(ctx, pl, wp, WIDE_MAX - 1);
+    group_params(ctx, pl, dp, DEEP_MAX - 1);
     PairSlot *slot = reinterpret_cast<PairSlot *>(ctx->h_pair_ring) + (p.step & pp.ring_mask);
     __atomic_store_n(&slot->step, 0ull, __ATOMIC_SEQ_CST);   // (a reader of the slot's previous use fails its second check)
     slot->corpus = (unsigned long long)(uintptr_t)p.corpus;
     slot->n_virtual = p.n_virtual;
     slot->query = (unsigned long long)(uintptr_t)p.queries;
     slot->lists = (unsigned long long)(uintptr_t)p.block_lists;
-    slot->kp_blocks = (unsigned long long)p.kp | (pl.wide ? WIDE_FAMILY : 0ull) | (unsigned long long)pl.blocks << 32;
+    slot->kp_blocks = (unsigned long long)p.kp | (pl.wide ? WIDE_FAMILY : pl.deep ? DEEP_FAMILY : 0ull) | (unsigned long long)pl.blocks << 32;
     slot->absorbable = pp.absorbable;
     __atomic_store_n(&slot->step, p.step, __ATOMIC_RELEASE);
     pp.recs = reinterpret_cast<PairRecord *>(ctx->d_pair_recs);
     wp.recs = reinterpret_cast<WideRecord *>(ctx->d_wide_recs);
-    if (pl.wide)
+    dp.recs = reinterpret_cast<DeepRecord *>(ctx->d_deep_recs);
+    if (pl.deep)
+        hipLaunchKernelGGL(pl.nt ? scan_deep_kernel<true> : scan_deep_kernel<false>, dim3(pl.blocks), dim3(pl.threads),
+                           deep_smem_bytes(pl.threads), pl.st, p, dp);
+    else if (pl.wide)
         hipLaunchKernelGGL(pl.nt ? scan_wide_kernel<true> : scan_wide_kernel<false>, dim3(pl.blocks), dim3(pl.threads),
                            wide_smem_bytes(pl.threads), pl.st, p, wp);
     else

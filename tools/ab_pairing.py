@@ -1,7 +1,9 @@
-"""A/B of grouped one-query scans (tuning key scan_take = 0 .. 7 later calls taken along; scan_gate_pct swept at the limit of seven)
-in ONE process on one box, settings alternated: the wall time per pipelined step (async select, scan_overlap, no events) over two
-1 M-row corpora used in turn (as bench.py) and over one corpus alone, how many launches took calls along (smt_debug_scan_pairs) and
-how many calls each launch served (smt_debug_scan_groups_wide, eight entries), and the answers and status words compared with scan_take = 0.  "sync":
+"""A/B of grouped one-query scans (tuning keys scan_take = 0 .. 7 and scan_deep = 8 .. 15 later calls taken along; scan_gate_pct swept
+at the limit of fifteen) in ONE process on one box, settings alternated: the wall time per pipelined step (async select, scan_overlap,
+no events) over two 1 M-row corpora used in turn (as bench.py) and over one corpus alone, how many launches took calls along
+(smt_debug_scan_pairs) and how many calls each launch served (smt_debug_scan_groups_wide, eight entries, for the limits up to seven;
+smt_debug_scan_groups_deep, sixteen entries, above), and the answers and status words compared with the limit 0.  T(n), what one corpus
+pass serving n calls costs, is step x n at the limit n - 1 (the streams are always busy).  "sync":
 one call, synchronise, repeat -- the latency of a call when the GPU is not behind, where nothing can be taken along and the
 group-capable kernel must cost what the plain one does.  python tools/ab_pairing.py [rows] [rounds] [out.json]"""
 import json, os, sys, time
@@ -27,36 +29,42 @@ def run(n, corpora, sync_each=False):
                                                      out_status_ptr=st[i % 2048:].data_ptr())
         if sync_each: torch.cuda.synchronize()
     ctx.synchronize()
+def groups():
+    return ctx.scan_groups_wide() + ctx.scan_groups_deep()
 ctx.set_tuning("prof_select", 0)
 ctx.set_tuning("async_select", 1)
-# (scan_take, scan_gate_pct, scan_pair_wait_us): the eight group limits at the shipped gate, then the gate swept at the limit of seven
-settings = [(take, 50, 0) for take in range(8)] + [(7, 0, 0), (7, 25, 0), (7, 75, 0), (7, 100, 0)]
-loads = {"two_corpora": (both, False, settings), "one_corpus": (both[:1], False, settings), "sync": (both, True, settings[:8:7])}
+# (limit, scan_gate_pct, scan_pair_wait_us): the sixteen group limits at the shipped gate, then the gate swept at the limit of fifteen
+settings = [(take, 50, 0) for take in range(16)] + [(15, 0, 0), (15, 25, 0), (15, 75, 0), (15, 100, 0)]
+loads = {"two_corpora": (both, False, settings), "one_corpus": (both[:1], False, settings),
+         "sync": (both, True, [settings[0], settings[7], settings[15]])}
 res, ref = {}, {}
 for r in range(rounds):
     for load, (corpora, sync_each, todo) in loads.items():
         for pair, gate, wait_us in todo:
-            ctx.set_tuning("scan_take", pair)
+            ctx.set_tuning("scan_take" if pair < 8 else "scan_deep", pair)
             ctx.set_tuning("scan_gate_pct", gate)
             ctx.set_tuning("scan_pair_wait_us", wait_us)
             run(300, corpora, sync_each)
             st.fill_(7)
-            c0, g0 = ctx.scan_pairs(), ctx.scan_groups_wide()
+            c0, g0 = ctx.scan_pairs(), groups()
             t0 = time.perf_counter(); run(2000, corpora, sync_each); step = (time.perf_counter() - t0) / 2000 * 1e6
-            c1, g1 = ctx.scan_pairs(), ctx.scan_groups_wide()
+            c1, g1 = ctx.scan_pairs(), groups()
             ans = out.cpu().numpy().copy()
             ref.setdefault(load, ans)
             same = bool((ans == ref[load]).all()) and bool((st[:2000].cpu() == 0).all())
             key = f"{load}/" + ("off" if pair == 0 else f"take{pair}_gate{gate}")
-            res.setdefault(key, []).append({"step_us": round(step, 2), "paired": c1[0] - c0[0], "alone": c1[1] - c0[1],
-                                            "absorbed": c1[2] - c0[2], "launches_by_calls_served": [b - a for a, b in zip(g0, g1)],
-                                            "answers_and_status_match": same})
+            by = [b - a for a, b in zip(g0, g1)]
+            res.setdefault(key, []).append({"step_us": round(step, 2), "pass_us": round(step * (pair + 1), 1), "paired": c1[0] - c0[0],
+                                            "alone": c1[1] - c0[1], "absorbed": c1[2] - c0[2], "launches_by_calls_served": by[:8],
+                                            "deep_launches_by_calls_served": by[8:], "answers_and_status_match": same})
             print(json.dumps({"round": r, "setting": key, **res[key][-1]}), file=sys.stderr, flush=True)
 ctx.set_tuning("scan_gate_pct", -1)
 ctx.set_tuning("scan_pair_wait_us", 0)
 summary = {k: {"median_step_us": sorted(x["step_us"] for x in v)[len(v) // 2], "min": min(x["step_us"] for x in v),
-               "max": max(x["step_us"] for x in v), "paired_of_2000": [x["paired"] for x in v],
+               "max": max(x["step_us"] for x in v), "median_pass_us": sorted(x["pass_us"] for x in v)[len(v) // 2],
+               "paired_of_2000": [x["paired"] for x in v],
                "launches_by_calls_served": [x["launches_by_calls_served"] for x in v],
+               "deep_launches_by_calls_served": [x["deep_launches_by_calls_served"] for x in v],
                "all_match": all(x["answers_and_status_match"] for x in v)} for k, v in res.items()}
 report = json.dumps({"rows": rows, "rounds": rounds, "summary": summary, "by_setting": res}, indent=1)
 if len(sys.argv) > 3:
