@@ -841,6 +841,21 @@ int smt_debug_scan_groups_wide(smt_ctx *ctx, uint64_t *by_size /* [8] */);
  * ran alone; smt_debug_scan_pairs counts them like any other.  All zero while scan_deep_kernel does not run.  Synchronises. */
 int smt_debug_scan_groups_deep(smt_ctx *ctx, uint64_t *by_size /* [16] */);
 
+/* One select launch per pass (tuning key select_group, default 1): a launch of the sixteen-call kernel is followed by ONE select
+ * launch that serves every call of its pass, in place of one select launch per call.  by_size[n] = those select launches that served
+ * n calls, n = 0..16; 0 means the call was absorbed and its answer came from its leader's launch.  The sum of n x by_size[n] is the
+ * number of calls served that way; all zero with select_group = 0 or while the sixteen-call kernel does not run.  Synchronises. */
+int smt_debug_select_groups(smt_ctx *ctx, uint64_t *by_size /* [17] */);
+
+/* Pipeline calls (scan_overlap) that recorded an event on the caller's stream and made their internal stream wait for it.  With the
+ * tuning key ov_skip_ready (default 1) a call made while the caller's stream is empty records none.  Does not synchronise. */
+int smt_debug_ov_ready(smt_ctx *ctx, uint64_t *records);
+
+/* Host time of the pipeline calls since the tuning key host_timing was set to 1 (setting it clears the sums): ns[0] stream queries,
+ * ns[1] the ready event's record and wait, ns[2] the scan launch, ns[3] the select launch, ns[4] the aux-stream event, ns[5] the whole
+ * call below the entry point, ns[6..7] unused; *calls = pipeline calls timed.  Does not synchronise. */
+int smt_debug_host_timing(smt_ctx *ctx, uint64_t *ns /* [8] */, uint64_t *calls);
+
 /* Test hook for the SPMD error paths of multi-process groups: arms ONE injected failure with status `code` (an SMT_E_* value) on
  * THIS process's ranks; it fires at the next step of kind `where` and disarms.  The tests arm it on one rank of an n-rank group and
  * check that every rank returns `code` from the same call and that none is left waiting inside a collective.
@@ -958,6 +973,15 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *   scan_deep (0..15)    the same limit with the range of the sixteen-call kernel: above 7, a launch that scan_take would give to
  *                        scan_wide_kernel runs scan_deep_kernel and looks for the calls two, four, ... thirty steps later; up to 7
  *                        the key is scan_take.  The default limit is 15.  Switching it drains the pipeline
+ *   select_group (0/1)   1 (default): a launch of scan_deep_kernel is followed by ONE select launch that serves every call of its
+ *                        pass -- the calls it took along get their answers from it, earlier in stream order than from a select of
+ *                        their own, which is safe because a call is only taken when the context's stream was empty at the call --
+ *                        and the select launches of those calls return at once.  Rows, distances, status words and the uncertain
+ *                        count are bit for bit those of 0, where every call runs its own select.  Switching it drains the pipeline
+ *   ov_skip_ready (0/1)  1 (default): a scan_overlap call made while the context's stream is empty records no event on that stream
+ *                        and puts no wait in front of its scan; 0: every call does (smt_debug_ov_ready counts them)
+ *   host_timing (0/1)    1: clock_gettime around the runtime calls of a scan_overlap call, read with smt_debug_host_timing; setting
+ *                        the key clears the sums (default 0)
  *   scan_pair_ring (64..4096, a power of two)  scan_pair: slots of the descriptor ring in use.  A call can be taken along while the
  *                        host is fewer calls ahead of the GPU than this; a call further ahead simply scans for itself.  Switching
  *                        it drains the pipeline (default 4096; tests use 64 to see slots reused)

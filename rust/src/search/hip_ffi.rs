@@ -850,6 +850,9 @@ extern "C" {
     pub fn smt_debug_scan_groups(ctx: *mut SmtCtx, by_size: *mut u64) -> c_int;
     pub fn smt_debug_scan_groups_wide(ctx: *mut SmtCtx, by_size: *mut u64) -> c_int;
     pub fn smt_debug_scan_groups_deep(ctx: *mut SmtCtx, by_size: *mut u64) -> c_int;
+    pub fn smt_debug_select_groups(ctx: *mut SmtCtx, by_size: *mut u64) -> c_int;
+    pub fn smt_debug_ov_ready(ctx: *mut SmtCtx, records: *mut u64) -> c_int;
+    pub fn smt_debug_host_timing(ctx: *mut SmtCtx, ns: *mut u64, calls: *mut u64) -> c_int;
     pub fn smt_debug_group_fail_next(group: *mut SmtGroup, where_: c_int, code: c_int) -> c_int;
     pub fn smt_debug_batched_scores(
         corpus: *mut SmtCorpus,

@@ -46,6 +46,7 @@ EXPORTS = [
     "smt_model_create_indexed", "smt_model_create_from_file_indexed", "smt_model_create_from_device_indexed", "smt_model_token_info",
     "smt_sharded_model_create_indexed", "smt_sharded_model_create_from_file_indexed", "smt_sharded_model_token_info",
     "smt_debug_scan_pairs", "smt_debug_image_tile", "smt_debug_scan_groups", "smt_debug_scan_groups_wide", "smt_debug_scan_groups_deep","smt_debug_nominations",
+    "smt_debug_select_groups", "smt_debug_ov_ready", "smt_debug_host_timing",
     "smt_wordpiece_create", "smt_wordpiece_create_utf8", "smt_wordpiece_info", "smt_wordpiece_destroy", "smt_wordpiece_scan_device", "smt_wordpiece_emit_device", "smt_wordpiece_tokenize",
     "smt_unigram_create", "smt_unigram_destroy", "smt_unigram_scan_device", "smt_unigram_emit_device", "smt_unigram_tokenize",
 ]
@@ -299,6 +300,9 @@ def lib():
         L.smt_debug_nominations.argtypes = [vp, vp, u32, u32, vp, u32, vp, i32, vp, vp, vp, P(C.c_uint32)]
         L.smt_debug_scan_groups_wide.argtypes = [vp, P(C.c_uint64)]
         L.smt_debug_scan_groups_deep.argtypes = [vp, P(C.c_uint64)]
+        L.smt_debug_select_groups.argtypes = [vp, P(C.c_uint64)]
+        L.smt_debug_ov_ready.argtypes = [vp, P(C.c_uint64)]
+        L.smt_debug_host_timing.argtypes = [vp, P(C.c_uint64), P(C.c_uint64)]
     except AttributeError:
         pass
     L.smt_sharded_corpus_append_to_file_ex.argtypes = [vp, C.c_char_p, u64, u64, i32]

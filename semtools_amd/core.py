@@ -109,6 +109,27 @@ class Context:
         L.check(L.lib().smt_debug_scan_groups_deep(self._h, v))
         return tuple(int(x) for x in v)
 
+    def select_groups(self):
+        """by_size: select launches of the one-launch-per-pass route by calls served, n = 0..16 (smt_debug_select_groups; tuning key
+        select_group, default 1): 0 counts the launches of absorbed calls, whose answer their leader's launch wrote.  Synchronises."""
+        v = (C.c_uint64 * 17)()
+        L.check(L.lib().smt_debug_select_groups(self._h, v))
+        return tuple(int(x) for x in v)
+
+    def ov_ready_records(self):
+        """Pipeline calls that put a ready event on the caller's stream (smt_debug_ov_ready; tuning key ov_skip_ready, default 1: a
+        call made while that stream is empty puts none)."""
+        n = C.c_uint64(0)
+        L.check(L.lib().smt_debug_ov_ready(self._h, C.byref(n)))
+        return int(n.value)
+
+    def host_timing(self):
+        """(ns, calls): host nanoseconds of the pipeline calls since set_tuning("host_timing", 1) by kind -- stream queries, ready
+        event, scan launch, select launch, aux-stream event, the whole call -- and the calls timed (smt_debug_host_timing)."""
+        v, n = (C.c_uint64 * 8)(), C.c_uint64(0)
+        L.check(L.lib().smt_debug_host_timing(self._h, v, C.byref(n)))
+        return tuple(int(x) for x in v), int(n.value)
+
     def compact_stats(self, reset=False):
         """CompactStats(calls, rows_moved): the Corpus.compact calls that succeeded on this context and the rows they moved."""
         n, m = C.c_uint64(0), C.c_uint64(0)

@@ -407,6 +407,9 @@ void smt_ctx_destroy(smt_ctx *ctx)
     if (ctx->d_wide_recs) (void)hipFree(ctx->d_wide_recs);
     if (ctx->d_deep_recs) (void)hipFree(ctx->d_deep_recs);
     if (ctx->h_pair_ring) (void)hipHostFree(ctx->h_pair_ring);
+    if (ctx->d_deep_sel_recs) (void)hipFree(ctx->d_deep_sel_recs);
+    if (ctx->d_sel_groups) (void)hipFree(ctx->d_sel_groups);
+    if (ctx->h_sel_ring) (void)hipHostFree(ctx->h_sel_ring);
     if (ctx->d_flags) (void)hipFree(ctx->d_flags);
     if (ctx->d_status) (void)hipFree(ctx->d_status);
     if (ctx->d_steal) (void)hipFree(ctx->d_steal);
@@ -506,6 +509,39 @@ try {
     unsigned long long v[16] = {};   // launches of scan_deep_kernel that served 1 .. 16 calls (scan_kernels.hip DeepParams::ctl)
     if (ctx->d_gate) SMT_HIP_CHECK(hipMemcpy(v, ctx->d_gate + 12, sizeof(v), hipMemcpyDeviceToHost));
     for (int n = 0; n < 16; ++n) by_size[n] = v[n];
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_select_groups(smt_ctx *ctx, uint64_t *by_size)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    SMT_REQUIRE(by_size != nullptr, "null argument");
+    if ((rc = bind_device(ctx))) return rc;
+    SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if ((rc = sync_side_streams(ctx))) return rc;
+    unsigned long long v[17] = {};   // launches of group_select_kernel that served 0 (absorbed) .. 16 calls (select.hip)
+    if (ctx->d_sel_groups) SMT_HIP_CHECK(hipMemcpy(v, ctx->d_sel_groups, sizeof(v), hipMemcpyDeviceToHost));
+    for (int n = 0; n < 17; ++n) by_size[n] = v[n];
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_ov_ready(smt_ctx *ctx, uint64_t *records)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    SMT_REQUIRE(records != nullptr, "null argument");
+    *records = ctx->ov_ready_records;
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_host_timing(smt_ctx *ctx, uint64_t *ns, uint64_t *calls)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    SMT_REQUIRE(ns != nullptr && calls != nullptr, "null argument");
+    for (int i = 0; i < 8; ++i) ns[i] = ctx->host_ns[i];
+    *calls = ctx->host_ns_calls;
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
@@ -645,6 +681,16 @@ try {
     } else if (k == "scan_pair_wait_us") {
         SMT_REQUIRE(value >= 0 && value <= 5000, "scan_pair_wait_us: 0..5000 us (tests only)");
         ctx->tune.scan_pair_wait_us = (int)value;
+    } else if (k == "select_group") {
+        int rc2 = drain_async(ctx);
+        if (rc2) return rc2;
+        ctx->tune.select_group = value ? 1 : 0;
+    } else if (k == "ov_skip_ready") {
+        ctx->tune.ov_skip_ready = value ? 1 : 0;
+    } else if (k == "host_timing") {
+        ctx->tune.host_timing = value ? 1 : 0;
+        for (uint64_t &ns : ctx->host_ns) ns = 0;
+        ctx->host_ns_calls = 0;
     } else if (k == "scan_gate_pct") {
         SMT_REQUIRE(value >= -1 && value <= 100, "scan_gate_pct: 0..100 per cent of the previous scan's blocks (0 = no gate), or -1 for the default");
         ctx->tune.scan_gate_pct = (int)value;

@@ -68,6 +68,9 @@ struct Tuning {
     int scan_pair = 15;         // scan_overlap: a scan that starts behind a predecessor takes the queries of up to this many later calls of its stream (steps + 2, + 4, ...) along in the same corpus pass (key scan_pair: 0..3, scan_kernels.hip scan_pair_kernel; key scan_take: 0..7, above 3 scan_wide_kernel where it applies; key scan_deep: 0..15, above 7 scan_deep_kernel)
     int scan_pair_ring = 4096;  // scan_pair: slots of the descriptor ring in use (a power of two, 64 .. 4096): a call is found by the scan two steps earlier while the host is fewer calls ahead of the GPU than this (tests use 64 to see slots reused)
     int scan_pair_wait_us = 0;  // scan_pair, tests only: the deciding block waits this long (<= 5000) for the partner's descriptor
+    int select_group = 1;       // 1: a scan_deep_kernel launch is followed by ONE select launch for the calls its pass serves (select.hip group_select_kernel); 0: every call's own final_select_kernel, as before (switching drains the pipeline)
+    int ov_skip_ready = 1;      // 1: a pipeline call made while the caller's stream is empty records no ov_ready event and waits for none (0: always, as before)
+    int host_timing = 0;        // 1: clock_gettime around the runtime calls of a pipeline call, read with smt_debug_host_timing (tools/ab_select_group.py)
     int gemm_image = 1;         // 1: batched searches read the corpus' fp16 operand image when it has one (0: A/B only)
     int64_t image_scan_min_rows = 1500000;   // shards this large answer ONE query from the operand image too, when they have one; 2..7 queries from a third of this (0: never)
     int64_t image_use_min_rows = 400000;     // a corpus that already HAS its image answers one query from it from this many rows (unfiltered calls), two from 1/5 of it, three and more from 1/60 (0: only the image_scan_min_rows rule)
@@ -147,6 +150,15 @@ struct smt_ctx {
     void *d_pair_recs = nullptr;
     void *d_wide_recs = nullptr;             // scan_take: the records of scan_wide_kernel launches
     void *d_deep_recs = nullptr;             // scan_deep: the records of scan_deep_kernel launches
+    // select_group: what a leader's select launch needs of the calls it serves beyond (query, lists) -- a second pinned ring beside
+    // h_pair_ring (same index, same length), copied by the deciding wave into device records beside d_deep_recs; and the launches of
+    // group_select_kernel by calls served, [0] absorbed .. [16] (smt_debug_select_groups)
+    void *h_sel_ring = nullptr;
+    void *d_deep_sel_recs = nullptr;
+    unsigned long long *d_sel_groups = nullptr;
+    uint64_t ov_ready_records = 0;           // ov_ready events recorded by pipeline calls (smt_debug_ov_ready; ov_skip_ready)
+    uint64_t host_ns[8] = {};                // host_timing: ns spent in [0] stream queries [1] ov_ready record + wait [2] the scan launch [3] the select launch [4] the aux-stream event [5] the whole of launch_scan_topk
+    uint64_t host_ns_calls = 0;              // ... over this many pipeline calls
     uint64_t pair_alone_host = 0;            // scan_pair calls that got the plain kernel: nothing queued in front of them, or profiled (smt_debug_scan_pairs counts them as alone)
     bool pair_live = false;                  // paired-mode scans were launched since the last drain (their error flag is unread)
     unsigned int *d_steal = nullptr;         // K2 STEAL: 64 group counters, one per launch in rotation (scan_kernels.hip)
@@ -426,6 +438,21 @@ struct SelectArgs {
     hipStream_t stream = nullptr;        // the stream to enqueue on (nullptr: the context's; not with async_step)
 };
 int launch_select(smt_ctx *ctx, const SelectArgs &s);
+
+// One select launch per pass of scan_deep_kernel (select.hip group_select_kernel; tuning key select_group).  What the kernel
+// reads of the scan's record is named here as 8-byte words, and scan_kernels.hip asserts that DeepRecord and DeepSelRecord are laid
+// out that way.
+constexpr int GROUP_SEL_MAX = 16;                     // calls one launch serves: blocks of the grid (scan_kernels.hip DEEP_MAX)
+constexpr int GROUP_REC_STATE = 0, GROUP_REC_TAKEN = 1, GROUP_REC_QUERY = 2, GROUP_REC_LISTS = GROUP_REC_QUERY + GROUP_SEL_MAX - 1;
+struct GroupSelect {
+    const unsigned long long *rec;   // this step's DeepRecord
+    const unsigned long long *sel;   // this step's DeepSelRecord: {out_rows, out_dist, out_status, row_base} of the calls taken along
+    unsigned long long absorbed;     // the record's state word when the leader's launch serves this call: every block returns
+    unsigned long long paired;       // ... and when this launch took `taken` calls along
+    unsigned long long *hist;        // [GROUP_SEL_MAX + 1] launches by calls served (smt_debug_select_groups)
+};
+bool group_select_serves(const SelectArgs &s);       // a select that group_select_kernel can run: one query, nothing but rows, distances and status
+int launch_group_select(smt_ctx *ctx, const SelectArgs &s, const GroupSelect &gs);
 
 
 // |f32 scan distance - exact distance| bounds used for the certificate.  What an MFMA does to its accumulator was MEASURED

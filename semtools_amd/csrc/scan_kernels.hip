@@ -1220,8 +1220,30 @@ struct DeepRecord {   // 256 bytes
     unsigned long long query[DEEP_MAX - 1], lists[DEEP_MAX - 1];   // ... and theirs
 };
 static_assert(sizeof(DeepRecord) == 256, "DeepRecord: state, taken and fifteen (query, lists) pairs");
+// select_group (select.hip group_select_kernel): ONE select launch behind the leader serves every call of its pass, so the leader
+// also needs each member's output buffers, status word and row base.  They travel as (query, lists) do: the host writes them into a
+// second pinned ring beside the PairSlot ring (same index, same length, between the two stores of PairSlot::step, so the step checks
+// around the fields cover them; PairSlot keeps its 64 bytes and the two older kernels never see the ring), the deciding wave copies
+// them AT THE DECISION into a device record beside DeepRecord (same index, same reuse distance), and the select reads that copy --
+// never the pinned slot, which the host may have lapped by then (scan_pair_ring = 64).  A launch that is followed by a group select
+// says so in its slot (DEEP_SELGROUP, and its k_out above it: k' alone does not fix k_out when the guard band changes between
+// calls), so a leader takes only calls whose select it will run, and calls that will run none of their own.
+constexpr unsigned long long DEEP_SELGROUP = 1ull << 18;   // PairSlot::kp_blocks: the launch is followed by group_select_kernel ...
+constexpr int DEEP_KOUT_SHIFT = 24;                        // ... and k_out (<= 56) in bits 24 .. 29
+struct SelSlot {   // 32 bytes of pinned host memory, slot i beside PairSlot i
+    unsigned long long out_rows, out_dist, out_status, row_base;
+};
+struct DeepSelRecord {   // 512 bytes
+    SelSlot member[DEEP_MAX];   // [0 .. DEEP_MAX - 2]: the calls taken along, as DeepRecord::query
+};
+static_assert(DEEP_MAX == GROUP_SEL_MAX && offsetof(DeepRecord, state) == 8 * GROUP_REC_STATE && offsetof(DeepRecord, taken) == 8 * GROUP_REC_TAKEN &&
+                  offsetof(DeepRecord, query) == 8 * GROUP_REC_QUERY && offsetof(DeepRecord, lists) == 8 * GROUP_REC_LISTS && sizeof(SelSlot) == 32,
+              "group_select_kernel reads these records as 8-byte words (common.h GroupSelect)");
 struct DeepParams {
     const PairSlot *ring;
+    const SelSlot *sel_ring;        // select_group: the ring beside `ring`, or nullptr ...
+    DeepSelRecord *sel_recs;        // ... and the records beside `recs`
+    unsigned long long family;      // what a slot's kp_blocks holds beside k' and the grid: DEEP_FAMILY, and with select_group DEEP_SELGROUP | k_out << DEEP_KOUT_SHIFT
     DeepRecord *recs;
     unsigned long long *ctl;        // PairParams::ctl; [11..26] launches of this kernel that served 1 .. 16 calls
     unsigned int absorbable;
@@ -1242,9 +1264,11 @@ __device__ __forceinline__ unsigned int deep_decide(const ScanParams &p, const D
     const unsigned long long t0 = wall_clock64();
     const unsigned long long want = p.step + 2ull * (unsigned long long)(lane + 1);
     const PairSlot *s = pp.ring + (want & pp.ring_mask);
-    const unsigned long long expect = (unsigned long long)p.kp | DEEP_FAMILY | (unsigned long long)gridDim.x << 32;
+    const unsigned long long expect = (unsigned long long)p.kp | pp.family | (unsigned long long)gridDim.x << 32;
+    const SelSlot *ss = pp.sel_ring ? pp.sel_ring + (want & pp.ring_mask) : nullptr;   // (wave-uniform: all lanes or none)
     int status = (unsigned int)lane < pp.max_take ? SLOT_PENDING : SLOT_FAIL;   // (max_take <= 15: lanes 15 .. 63 never pass)
     unsigned long long query = 0, lists = 0;
+    SelSlot sel = {0, 0, 0, 0};
     unsigned int taken = 0;
     for (;;) {
         if (status == SLOT_PENDING) {
@@ -1254,6 +1278,12 @@ __device__ __forceinline__ unsigned int deep_decide(const ScanParams &p, const D
                 const unsigned long long absorbable = sys_load(&s->absorbable);
                 query = sys_load(&s->query);
                 lists = sys_load(&s->lists);
+                if (ss) {   // select_group: the call's select parameters, inside the same pair of step checks
+                    sel.out_rows = sys_load(&ss->out_rows);
+                    sel.out_dist = sys_load(&ss->out_dist);
+                    sel.out_status = sys_load(&ss->out_status);
+                    sel.row_base = sys_load(&ss->row_base);
+                }
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
                 const bool still = sys_load(&s->step) == want;   // (or the host was rewriting the slot, a ring's length ahead)
                 const bool same = corpus == (unsigned long long)(uintptr_t)p.corpus && n_virtual == p.n_virtual && kp_blocks == expect;
@@ -1271,6 +1301,13 @@ __device__ __forceinline__ unsigned int deep_decide(const ScanParams &p, const D
     if ((unsigned int)lane < taken) {
         flag_store(&rec->query[lane], query);
         flag_store(&rec->lists[lane], lists);
+        if (ss) {   // (the caller's agent-scope release publishes these with the rest)
+            SelSlot *m = &pp.sel_recs[p.step % DEEP_RECS].member[lane];
+            flag_store(&m->out_rows, sel.out_rows);
+            flag_store(&m->out_dist, sel.out_dist);
+            flag_store(&m->out_status, sel.out_status);
+            flag_store(&m->row_base, sel.row_base);
+        }
         flag_store(&pp.recs[want % DEEP_RECS].state, (want << PAIR_SHIFT) | PAIR_ABSORBED);   // the mark
     }
     if (lane == 0) flag_store(&rec->taken, (unsigned long long)taken);
@@ -1620,6 +1657,26 @@ static inline uint32_t candidates_per_list(const smt_ctx *ctx, uint32_t k_out)
     return std::min<uint32_t>(64, k_out + (uint32_t)ctx->tune.guard_band);
 }
 
+// host_timing (tuning key, off by default; tools/ab_select_group.py): clock_gettime around the runtime calls of a pipeline call,
+// summed per kind in smt_ctx::host_ns
+struct HostTimer {
+    smt_ctx *ctx;
+    bool on;
+    timespec t;
+    explicit HostTimer(smt_ctx *c) : ctx(c), on(c->tune.host_timing != 0)
+    {
+        if (on) clock_gettime(CLOCK_MONOTONIC, &t);
+    }
+    void lap(int kind)
+    {
+        if (!on) return;
+        timespec n;
+        clock_gettime(CLOCK_MONOTONIC, &n);
+        ctx->host_ns[kind] += (uint64_t)((n.tv_sec - t.tv_sec) * 1000000000ll + (n.tv_nsec - t.tv_nsec));
+        t = n;
+    }
+};
+
 // What the launches of one call have in common: plan_scan decides before anything is enqueued, the next two steps fill in the rest.
 struct ScanPlan {
     bool filtered, nt;
@@ -1639,6 +1696,9 @@ struct ScanPlan {
     bool wide = false;        // scan_take: ... or scan_wide_kernel, when the limit exceeds what scan_pair_kernel serves
     bool deep = false;        // scan_deep: ... or scan_deep_kernel, when it exceeds what scan_wide_kernel serves
     unsigned int absorbable = 0;
+    bool sel_group = false;   // select_group: the launch is followed by group_select_kernel, not by a select of its own
+    SelSlot sel = {0, 0, 0, 0};   // ... and what a leader's launch of it needs of this call
+    uint32_t sel_k_out = 0;
 };
 
 static ScanPlan plan_scan(const smt_ctx *ctx, const ScanArgs &a)
@@ -1712,15 +1772,28 @@ static int overlap_prologue(smt_ctx *ctx, ScanPlan &pl)
     // the caller's stream can still be writing may be taken
     // ... and only a launch that queues up behind a predecessor on its stream can be absorbed by it, or has reason to look for a
     // partner itself (a call made while the GPU is idle must cost what it did: no look, no wait; scan_pair_wait_us: tests)
+    // ov_skip_ready: the caller's stream is asked ONCE per call, and when it is empty there is nothing for the internal stream to be
+    // ordered behind -- no event is recorded on the caller's stream and no barrier stands in front of the scan.  (Those markers were
+    // also what the next call's query found on the caller's stream when the host ran far enough ahead of it.)  The answer serves as
+    // `idle` too.  0: an event and a wait for every call, and the caller's stream asked only behind a predecessor, as before.
+    const bool skip_ready = ctx->tune.ov_skip_ready != 0;
+    HostTimer ht(ctx);
+    bool caller_empty = false;
+    if (skip_ready) caller_empty = hipStreamQuery(ctx->stream) == hipSuccess;
     if (pl.pair) {
         const bool behind = ctx->tune.scan_pair_wait_us > 0 || hipStreamQuery(st) != hipSuccess;
-        const bool idle = behind && hipStreamQuery(ctx->stream) == hipSuccess;
-        (void)hipGetLastError();   // (hipErrorNotReady is an answer here)
+        const bool idle = behind && (skip_ready ? caller_empty : hipStreamQuery(ctx->stream) == hipSuccess);
         pl.absorbable = idle ? 1u : 0u;
         pl.may_pair = behind;
     }
-    SMT_HIP_CHECK(hipEventRecord(ctx->ov_ready[step & 1], ctx->stream));
-    SMT_HIP_CHECK(hipStreamWaitEvent(st, ctx->ov_ready[step & 1], 0));
+    (void)hipGetLastError();   // (hipErrorNotReady is an answer here)
+    ht.lap(0);
+    if (!caller_empty) {
+        SMT_HIP_CHECK(hipEventRecord(ctx->ov_ready[step & 1], ctx->stream));
+        SMT_HIP_CHECK(hipStreamWaitEvent(st, ctx->ov_ready[step & 1], 0));
+        ++ctx->ov_ready_records;
+    }
+    ht.lap(1);
     // a timed launch waits for its predecessor (and that one's select), and the launch after it waits for it: the events bracket a
     // kernel that has the part to itself, not a gate or an HBM shared with a neighbour
     const bool timed = prof_arms_next(ctx, "scan");
@@ -1826,6 +1899,12 @@ int ensure_pair(smt_ctx *ctx)
     SMT_HIP_CHECK(hipMemset(ctx->d_wide_recs, 0, WIDE_RECS * sizeof(WideRecord)));
     SMT_HIP_CHECK(hipMalloc(&ctx->d_deep_recs, DEEP_RECS * sizeof(DeepRecord)));
     SMT_HIP_CHECK(hipMemset(ctx->d_deep_recs, 0, DEEP_RECS * sizeof(DeepRecord)));
+    SMT_HIP_CHECK(hipMalloc(&ctx->d_deep_sel_recs, DEEP_RECS * sizeof(DeepSelRecord)));
+    SMT_HIP_CHECK(hipMemset(ctx->d_deep_sel_recs, 0, DEEP_RECS * sizeof(DeepSelRecord)));
+    SMT_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&ctx->d_sel_groups), (GROUP_SEL_MAX + 1) * sizeof(unsigned long long)));
+    SMT_HIP_CHECK(hipMemset(ctx->d_sel_groups, 0, (GROUP_SEL_MAX + 1) * sizeof(unsigned long long)));
+    SMT_HIP_CHECK(hipHostMalloc(&ctx->h_sel_ring, PAIR_RING * sizeof(SelSlot), hipHostMallocDefault));
+    memset(ctx->h_sel_ring, 0, PAIR_RING * sizeof(SelSlot));
     SMT_HIP_CHECK(hipHostMalloc(&ctx->h_pair_ring, PAIR_RING * sizeof(PairSlot), hipHostMallocDefault));
     memset(ctx->h_pair_ring, 0, PAIR_RING * sizeof(PairSlot));
     return SMT_OK;
@@ -1857,7 +1936,14 @@ static int launch_scan_pair(smt_ctx *ctx, const ScanParams &p, const ScanPlan &p
     slot->n_virtual = p.n_virtual;
     slot->query = (unsigned long long)(uintptr_t)p.queries;
     slot->lists = (unsigned long long)(uintptr_t)p.block_lists;
-    slot->kp_blocks = (unsigned long long)p.kp | (pl.wide ? WIDE_FAMILY : pl.deep ? DEEP_FAMILY : 0ull) | (unsigned long long)pl.blocks << 32;
+    dp.family = DEEP_FAMILY;
+    if (pl.sel_group) {
+        dp.family |= DEEP_SELGROUP | (unsigned long long)pl.sel_k_out << DEEP_KOUT_SHIFT;
+        dp.sel_ring = reinterpret_cast<const SelSlot *>(ctx->h_sel_ring);
+        dp.sel_recs = reinterpret_cast<DeepSelRecord *>(ctx->d_deep_sel_recs);
+        reinterpret_cast<SelSlot *>(ctx->h_sel_ring)[p.step & pp.ring_mask] = pl.sel;   // (between the two stores of slot->step)
+    }
+    slot->kp_blocks = (unsigned long long)p.kp | (pl.wide ? WIDE_FAMILY : pl.deep ? dp.family : 0ull) | (unsigned long long)pl.blocks << 32;
     slot->absorbable = pp.absorbable;
     __atomic_store_n(&slot->step, p.step, __ATOMIC_RELEASE);
     pp.recs = reinterpret_cast<PairRecord *>(ctx->d_pair_recs);
@@ -1927,7 +2013,23 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
     ScanPlan pl = plan_scan(ctx, a);
     int rc = enter_pipeline(ctx, a, pl);
     if (rc != SMT_OK) return rc;
+    HostTimer whole(ctx);
     if (pl.overlap && (rc = overlap_prologue(ctx, pl))) return rc;
+    // select_group: a launch of scan_deep_kernel whose select is a plain one (rows, distances, status) is followed by ONE launch of
+    // group_select_kernel for the calls its pass serves.  A call whose select carries more than the record holds keeps its own
+    // select and is taken along by nobody.
+    const SelectArgs sa = select_args(a, pl);
+    if (pl.deep && pl.may_pair && ctx->tune.select_group) {
+        pl.sel_group = group_select_serves(sa);
+        if (pl.sel_group) {
+            pl.sel = SelSlot{(unsigned long long)(uintptr_t)sa.out_rows, (unsigned long long)(uintptr_t)sa.out_dist,
+                             (unsigned long long)(uintptr_t)sa.out_status, (unsigned long long)sa.row_base};
+            pl.sel_k_out = sa.k_out;
+        } else {
+            pl.absorbable = 0;
+        }
+    }
+    HostTimer ht(ctx);
 
     prof_begin_on(ctx, "scan", pl.st);
     const uint64_t *chunk_table = pl.table;
@@ -1952,11 +2054,29 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
     } else if (pl.async) {
         ctx->async_overlap = false;
     }
-    rc = launch_select(ctx, select_args(a, pl));
-    // the aux stream's contract (smt_ctx_aux_stream): work a host chains there runs behind this call's select
+    ht.lap(2);
+    if (pl.sel_group) {
+        GroupSelect gs;
+        gs.rec = reinterpret_cast<const unsigned long long *>(reinterpret_cast<const DeepRecord *>(ctx->d_deep_recs) + pl.step % DEEP_RECS);
+        gs.sel = reinterpret_cast<const unsigned long long *>(reinterpret_cast<const DeepSelRecord *>(ctx->d_deep_sel_recs) + pl.step % DEEP_RECS);
+        gs.absorbed = (pl.step << PAIR_SHIFT) | PAIR_ABSORBED;
+        gs.paired = (pl.step << PAIR_SHIFT) | PAIR_PAIRED;
+        gs.hist = ctx->d_sel_groups;
+        rc = launch_group_select(ctx, sa, gs);
+    } else {
+        rc = launch_select(ctx, sa);
+    }
+    ht.lap(3);
+    // the aux stream's contract (smt_ctx_aux_stream): work a host chains there runs behind this call's select.  (select_group: the
+    // select launch of an absorbed call does nothing, but it follows the leader's, which holds the call's answer, on this stream.)
     if (rc == SMT_OK && pl.overlap && ctx->aux_stream) {
         SMT_HIP_CHECK(hipEventRecord(ctx->ov_sel[pl.step & 1], pl.st));
         SMT_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ctx->ov_sel[pl.step & 1], 0));
+    }
+    ht.lap(4);
+    if (pl.overlap) {
+        whole.lap(5);
+        if (whole.on) ++ctx->host_ns_calls;
     }
     return rc;
 }

@@ -541,6 +541,48 @@ __global__ void __launch_bounds__(SEL_THREADS) final_select_kernel(FinalParams p
     final_select_body<KREG, OVF>(p, blockIdx.x, smem_raw);
 }
 
+// One select launch for a pass of scan_deep_kernel (tuning key select_group): DEEP_MAX blocks behind a group-capable scan of the
+// same stream.  Block g reads the scan's record of this step.  Marked absorbed: the leader's launch of this kernel, earlier on this
+// stream, has the call's answer, and every block returns.  Otherwise the pass served n = 1 + taken calls: block 0 runs the call's own
+// select with the parameters it was launched with, block g in 1 .. n - 1 that of member g - 1 -- the shared fields (corpus, n_lists,
+// k', k_out, f32_err, the sticky counter: a leader takes calls that agree with it in all of them) and the member's own queries, list
+// set, output buffers, status word and row base, as the deciding wave copied them into the record (scan_kernels.hip deep_decide).
+// The body is final_select_body<KREG, false> with query index 0, unchanged: every answer, verdict and count is what the member's
+// own launch of final_select_kernel produced.
+// ORDER: a member's outputs are written at the leader's place in stream order, earlier than at its own.  That is safe for the reason
+// its query may be READ that early: a call is published as absorbable only when the caller's stream was empty at the call, so no
+// work of the caller's can still be reading or writing those buffers, and what the caller enqueues later is ordered behind the
+// call's own (empty) launch of this kernel, as before.
+template <int KREG>
+__global__ void __launch_bounds__(SEL_THREADS) group_select_kernel(FinalParams p, GroupSelect gs)
+{
+    extern __shared__ unsigned char smem_raw[];
+    const uint32_t g = blockIdx.x;
+    const unsigned long long state = uniform_u64(flag_load(gs.rec + GROUP_REC_STATE));
+    uint32_t n = 0;   // calls this launch serves
+    if (state != gs.absorbed) {
+        n = 1;
+        if (state == gs.paired) {
+            const uint32_t taken = (uint32_t)uniform_u64(flag_load(gs.rec + GROUP_REC_TAKEN));
+            n += taken < (uint32_t)GROUP_SEL_MAX ? taken : (uint32_t)GROUP_SEL_MAX - 1u;
+        }
+    }
+    if (g == 0 && threadIdx.x == 0) (void)__hip_atomic_fetch_add(gs.hist + n, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (g >= n) return;
+    FinalParams m = p;
+    if (g > 0) {
+        const unsigned long long *sel = gs.sel + 4 * (g - 1);
+        m.queries = reinterpret_cast<const float *>((uintptr_t)uniform_u64(flag_load(gs.rec + GROUP_REC_QUERY + (g - 1))));
+        m.lists = reinterpret_cast<const key_t64 *>((uintptr_t)uniform_u64(flag_load(gs.rec + GROUP_REC_LISTS + (g - 1))));
+        m.out_rows = reinterpret_cast<uint64_t *>((uintptr_t)uniform_u64(flag_load(sel + 0)));
+        m.out_dist = reinterpret_cast<double *>((uintptr_t)uniform_u64(flag_load(sel + 1)));
+        m.out_status = reinterpret_cast<unsigned int *>((uintptr_t)uniform_u64(flag_load(sel + 2)));
+        m.row_base = uniform_u64(flag_load(sel + 3));
+        m.dbg = nullptr;
+    }
+    final_select_body<KREG, false>(m, 0, smem_raw);
+}
+
 static size_t final_smem_bytes(uint32_t kp)
 {
     const size_t kp2 = (kp + 1) & ~1u;
@@ -555,18 +597,21 @@ using select_kernel_t = void (*)(FinalParams);
 static const select_kernel_t SELECT_KERNELS[2][2] = {{final_select_kernel<8>, final_select_kernel<36>},
                                                      {final_select_kernel<8, true>, final_select_kernel<36, true>}};
 
-// Block lists -> final answer in ONE launch (per query: prune + rank + rescore).
-int launch_select(smt_ctx *ctx, const SelectArgs &a)
+static int select_attrs(smt_ctx *ctx)
 {
-    SMT_REQUIRE(a.n_lists >= 1 && a.n_lists <= (uint32_t)SEL_MAX_LISTS, "select stage accepts 1..512 block lists");
-    SMT_REQUIRE(a.async_step == 0 || (a.nq == 1 && ctx->aux_stream && ctx->d_flags), "async select handles one query per launch");
-    if (!(ctx->attr_done & ATTR_SELECT)) {  // per context == per device (a group runs several GPUs in one process)
-        for (const auto &row : SELECT_KERNELS)
-            for (const select_kernel_t kernel : row)
-                SMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  160 * 1024));
-        ctx->attr_done |= ATTR_SELECT;
-    }
+    if (ctx->attr_done & ATTR_SELECT) return SMT_OK;   // per context == per device (a group runs several GPUs in one process)
+    for (const auto &row : SELECT_KERNELS)
+        for (const select_kernel_t kernel : row)
+            SMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              160 * 1024));
+    SMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(group_select_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      160 * 1024));
+    ctx->attr_done |= ATTR_SELECT;
+    return SMT_OK;
+}
+
+static FinalParams final_params(const smt_ctx *ctx, const SelectArgs &a)
+{
     FinalParams f;
     f.corpus = a.corpus;
     f.queries = a.queries;
@@ -597,6 +642,17 @@ int launch_select(smt_ctx *ctx, const SelectArgs &a)
     f.done = dl ? dl->done : nullptr;
     f.seq = dl ? dl->seq : 0;
     f.out_words = dl ? dl->n_words : 0;
+    return f;
+}
+
+// Block lists -> final answer in ONE launch (per query: prune + rank + rescore).
+int launch_select(smt_ctx *ctx, const SelectArgs &a)
+{
+    SMT_REQUIRE(a.n_lists >= 1 && a.n_lists <= (uint32_t)SEL_MAX_LISTS, "select stage accepts 1..512 block lists");
+    SMT_REQUIRE(a.async_step == 0 || (a.nq == 1 && ctx->aux_stream && ctx->d_flags), "async select handles one query per launch");
+    int rc = select_attrs(ctx);
+    if (rc) return rc;
+    const FinalParams f = final_params(ctx, a);
     const bool small = (uint64_t)a.n_lists * a.kp <= (uint64_t)8 * SEL_THREADS;
     // async select: on the aux stream, outside the "select" profiling label, and never the batched path's instantiation
     const bool on_aux = a.async_step != 0;
@@ -607,6 +663,29 @@ int launch_select(smt_ctx *ctx, const SelectArgs &a)
                        final_smem_bytes(a.kp), st, f);
     if (timed) prof_end_on(ctx, "select", st);
     if (on_aux) ctx->async_pending = true;
+    SMT_HIP_CHECK(hipGetLastError());
+    return SMT_OK;
+}
+
+// The select of a scan_deep_kernel pass (group_select_kernel, above): one query, a list set of at most 8 keys per thread, no
+// overflow flag, no delivery and nothing on the aux stream -- launch_scan_topk asks for it only then.
+bool group_select_serves(const SelectArgs &a)
+{
+    return a.nq == 1 && (uint64_t)a.n_lists * a.kp <= (uint64_t)8 * SEL_THREADS && a.async_step == 0 && !a.overflow && !a.deliver &&
+           !a.out_counts && !a.out_uncertain && !a.ws_threshold && (a.out_stride == 0 || a.out_stride == a.k_out);
+}
+int launch_group_select(smt_ctx *ctx, const SelectArgs &a, const GroupSelect &gs)
+{
+    SMT_REQUIRE(a.n_lists >= 1 && a.n_lists <= (uint32_t)SEL_MAX_LISTS, "select stage accepts 1..512 block lists");
+    SMT_REQUIRE(group_select_serves(a) && gs.rec && gs.sel && gs.hist, "group select: a plain one-query select of a grouped scan");
+    int rc = select_attrs(ctx);
+    if (rc) return rc;
+    const FinalParams f = final_params(ctx, a);
+    hipStream_t st = a.stream ? a.stream : ctx->stream;
+    const bool timed = ctx->tune.prof_select;
+    if (timed) prof_begin_on(ctx, "select", st);
+    hipLaunchKernelGGL(group_select_kernel<8>, dim3(GROUP_SEL_MAX), dim3(SEL_THREADS), final_smem_bytes(a.kp), st, f, gs);
+    if (timed) prof_end_on(ctx, "select", st);
     SMT_HIP_CHECK(hipGetLastError());
     return SMT_OK;
 }
