@@ -300,6 +300,31 @@ typedef struct smt_unigram_params {
     uint32_t n_added;
 } smt_unigram_params;
 int smt_unigram_create(smt_ctx *ctx, const smt_unigram_params *p, smt_unigram **out);
+/* The UTF-8 form of the same tokenizer (unigram_utf8_kernels.hip, DESIGN 4.9 "Unigram over UTF-8 lines"): the handle and the calls
+ * below are shared, only pass 1 differs.  The normalizers this form serves act on one code point without context, so the caller
+ * states what every code point >= U+0080 becomes, with the struct and the rules of smt_wordpiece_create_utf8.  Behind Metaspace the
+ * classes mean:
+ *   ORDINARY  every output character is a character of a piece (there may be several: a Hangul syllable becomes its jamo, and a
+ *             piece may end between them)
+ *   SPACE     the code point becomes exactly U+0020: Metaspace turns it into the replacement, and it starts a piece.  The
+ *             replacement's own code point is stated as SPACE when the normalizer leaves it alone: Metaspace splits at it too
+ *   DROPPED   no output
+ *   FLAG      the line is left to the caller (a code point in no range is FLAG)
+ *   ALONE     has no meaning here: SMT_E_INVALID
+ * ASCII keeps coming from p->byte_map.  An output may not hold more characters than the UTF-8 form of `first` has bytes: a piece's
+ * tokens <= its normalised characters <= its raw bytes, so the slot rule of the ASCII form holds.  All pieces enter the table, those
+ * with bytes >= 0x80 too; SMT_UG_MAX_WORD stays in raw bytes, with a SPACE character of any length counted as one; the added tokens
+ * stay pure ASCII.
+ * A line is FLAGGED for what flags it in the ASCII form other than a byte >= 0x80, and for a FLAG code point, malformed UTF-8 (a lone
+ * continuation byte, a sequence cut by the line's looked-at end, an overlong form, a surrogate, a value above U+10FFFF, a byte that
+ * leads nothing), or ANY byte >= 0x80 within the looked-at bytes of a line longer than keep_bytes (the host layer cuts such a line by
+ * characters).  Malformed input ends in a flag, never in an access outside the text.
+ * SMT_E_INVALID, before anything is uploaded, for what smt_wordpiece_create_utf8 refuses in the ranges, for a range of class ALONE,
+ * and for a non-ASCII added token.  Everything is copied. */
+int smt_unigram_create_utf8(smt_ctx *ctx, const smt_unigram_params *p, const smt_wordpiece_codepoints *cp, smt_unigram **out);
+/* what the handle holds on the device: all of its table in bytes, the code-point part of it (0 for the ASCII form), and which form
+ * it is.  Any out may be NULL. */
+int smt_unigram_info(const smt_unigram *tok, uint64_t *table_bytes, uint64_t *codepoint_bytes, int *utf8);
 void smt_unigram_destroy(smt_unigram *tok);
 /* The two passes and the host convenience: the contracts of smt_wordpiece_scan_device / _emit_device / _tokenize, with one
  * difference: a line can hold one token more than looked-at bytes (the prepended replacement), so

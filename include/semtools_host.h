@@ -142,13 +142,21 @@ int smt_host_tokenizer_to_device_utf8(smt_host_tokenizer *tok, smt_ctx *ctx, smt
  * is Unigram behind exactly one Metaspace (split, a replacement character >= U+0080) and its normalizer, if any, is built only of
  * Lowercase / NFD / StripAccents / BertNormalizer (each acts on an ASCII character without context). */
 int smt_host_tokenizer_to_device_unigram(smt_host_tokenizer *tok, smt_ctx *ctx, smt_unigram **out);
+/* ... and its UTF-8 form (smt_unigram_create_utf8): the same vocabulary, and what every code point U+0080 .. U+10FFFF becomes under the
+ * tokenizer's own normalizer, as ranges: SPACE when it becomes exactly ' ' (or is the replacement character, left alone), DROPPED
+ * when nothing is left, ORDINARY when no output is ' ' or the replacement.  A code point is FLAG when ' ' or the replacement stands
+ * beside other output (a Chinese character under handle_chinese_chars), when the chain holds NFD and an output keeps a character of
+ * non-zero canonical combining class, or when the output holds more characters than the code point has bytes.  SMT_E_UNSUPPORTED on
+ * the terms of smt_host_tokenizer_to_device_unigram, and when an added token matched on the raw text holds a non-ASCII byte. */
+int smt_host_tokenizer_to_device_unigram_utf8(smt_host_tokenizer *tok, smt_ctx *ctx, smt_unigram **out);
 /* The device tokenizer route of a model.  OFF by default; the environment variable SEMTOOLS_DEVICE_TOKENIZER=1 turns
  * it on when the model is created.  With it on, a batch of lines is packed, uploaded and tokenized on the GPU when the model's
  * tokenizer has a device form (smt_host_tokenizer_to_device), the group has one rank and the full table is resident (or about to be:
  * calls of more than 32768 lines); lines the kernel flags are tokenized by the host tokenizer and spliced in; everything else keeps
  * the host path.  Rows, search output and the workspace's cached ids are bit-identical with the switch on and off.
- * on = 2 (SEMTOOLS_DEVICE_TOKENIZER=2) chooses the UTF-8 form of a WordPiece tokenizer (smt_host_tokenizer_to_device_utf8) where it has
- * one: lines with valid UTF-8 of covered code points stay on the device.  Otherwise 2 chooses what 1 chooses.
+ * on = 2 (SEMTOOLS_DEVICE_TOKENIZER=2) chooses the UTF-8 form of a WordPiece tokenizer (smt_host_tokenizer_to_device_utf8) or of a
+ * Unigram tokenizer (smt_host_tokenizer_to_device_unigram_utf8) where it has one: lines with valid UTF-8 of covered code points stay
+ * on the device.  Otherwise 2 chooses what 1 chooses.
  * smt_host_debug_device_tokenized (test hook): lines of this model tokenized on the device so far. */
 int smt_host_model_set_device_tokenizer(smt_host_model *model, int on);
 int smt_host_debug_device_tokenized(smt_host_model *model, uint64_t *lines);

@@ -308,6 +308,18 @@ extern "C" {
         flags_out: *mut u8,
     ) -> c_int;
     pub fn smt_unigram_create(ctx: *mut SmtCtx, p: *const SmtUnigramParams, out: *mut *mut SmtUnigram) -> c_int;
+    pub fn smt_unigram_create_utf8(
+        ctx: *mut SmtCtx,
+        p: *const SmtUnigramParams,
+        cp: *const SmtWordpieceCodepoints,
+        out: *mut *mut SmtUnigram,
+    ) -> c_int;
+    pub fn smt_unigram_info(
+        tok: *const SmtUnigram,
+        table_bytes: *mut u64,
+        codepoint_bytes: *mut u64,
+        utf8: *mut c_int,
+    ) -> c_int;
     pub fn smt_unigram_destroy(tok: *mut SmtUnigram);
     pub fn smt_unigram_scan_device(
         tok: *mut SmtUnigram,

@@ -48,7 +48,7 @@ EXPORTS = [
     "smt_debug_scan_pairs", "smt_debug_image_tile", "smt_debug_scan_groups", "smt_debug_scan_groups_wide", "smt_debug_scan_groups_deep","smt_debug_nominations",
     "smt_debug_select_groups", "smt_debug_ov_ready", "smt_debug_host_timing",
     "smt_wordpiece_create", "smt_wordpiece_create_utf8", "smt_wordpiece_info", "smt_wordpiece_destroy", "smt_wordpiece_scan_device", "smt_wordpiece_emit_device", "smt_wordpiece_tokenize",
-    "smt_unigram_create", "smt_unigram_destroy", "smt_unigram_scan_device", "smt_unigram_emit_device", "smt_unigram_tokenize",
+    "smt_unigram_create", "smt_unigram_create_utf8", "smt_unigram_info", "smt_unigram_destroy", "smt_unigram_scan_device", "smt_unigram_emit_device", "smt_unigram_tokenize",
 ]
 WP_NORMALIZER, WP_CLEAN_TEXT, WP_LOWERCASE = 1, 2, 4
 WP_CP_ORDINARY, WP_CP_SPACE, WP_CP_ALONE, WP_CP_DROPPED, WP_CP_FLAG = 0, 1, 2, 3, 4
@@ -109,7 +109,7 @@ HOST_EXPORTS = [
     "smt_host_split_lines", "smt_host_to_lowercase",
     "smt_host_group_from_spec", "smt_host_model_create_group", "smt_host_model_from_dir_group",
     "smt_host_workspace_use_group", "smt_host_workspace_status_group", "smt_host_workspace_prune_group",
-    "smt_host_model_table_info", "smt_host_model_token_info", "smt_host_tokenizer_to_device", "smt_host_tokenizer_to_device_unigram", "smt_host_tokenizer_to_device_utf8",
+    "smt_host_model_table_info", "smt_host_model_token_info", "smt_host_tokenizer_to_device", "smt_host_tokenizer_to_device_unigram", "smt_host_tokenizer_to_device_utf8", "smt_host_tokenizer_to_device_unigram_utf8",
     "smt_host_model_set_device_tokenizer", "smt_host_debug_device_tokenized",
 ]
 TOKENIZE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
@@ -218,6 +218,8 @@ def lib():
     L.smt_wordpiece_emit_device.argtypes = [vp, u64, vp, vp, vp, u64, u64, vp, u64, vp]
     L.smt_wordpiece_tokenize.argtypes = [vp, vp, vp, vp, u64, u32, u32, i32, vp, u64, vp, vp]
     L.smt_unigram_create.argtypes = [vp, P(SmtUnigramParams), P(vp)]
+    L.smt_unigram_create_utf8.argtypes = [vp, P(SmtUnigramParams), P(SmtWordpieceCodepoints), P(vp)]
+    L.smt_unigram_info.argtypes = [vp, P(u64), P(u64), P(i32)]
     L.smt_unigram_destroy.argtypes = [vp]
     L.smt_unigram_destroy.restype = None
     L.smt_unigram_scan_device.argtypes = [vp, vp, u64, vp, vp, u64, u32, u32, i32, vp, vp, vp]
@@ -392,6 +394,7 @@ def lib():
     L.smt_host_tokenizer_to_device.argtypes = [vp, vp, P(vp)]
     L.smt_host_tokenizer_to_device_unigram.argtypes = [vp, vp, P(vp)]
     L.smt_host_tokenizer_to_device_utf8.argtypes = [vp, vp, P(vp)]
+    L.smt_host_tokenizer_to_device_unigram_utf8.argtypes = [vp, vp, P(vp)]
     L.smt_host_model_set_device_tokenizer.argtypes = [vp, i32]
     L.smt_host_debug_device_tokenized.argtypes = [vp, P(u64)]
     L.smt_host_timing_json.argtypes = []

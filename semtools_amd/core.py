@@ -396,22 +396,27 @@ class WordPiece(_DeviceTokenizer):
 
 
 class Unigram(_DeviceTokenizer):
-    """The device tokenizer (smt_unigram): pure-ASCII lines through a per-byte normalizer -> Metaspace -> Unigram.
+    """The device tokenizer (smt_unigram): lines through a per-character normalizer -> Metaspace -> Unigram.  Pure-ASCII lines by
+    default; with `codepoints` (or utf8=True beside host_tokenizer) the UTF-8 form, which covers the code points the caller states.
 
     Unigram(ctx, vocab=[(piece, score), ..], unk_id=.., replacement="\u2581", prepend="always", byte_map=.., added=[..]) builds it
     from a vocabulary (the id of a piece is its index; unk_score defaults to the lowest score - 10; byte_map: 128 entries, the byte
     a byte becomes or 0xFF for dropped, default the identity); Unigram(ctx, host_tokenizer=<smt_host_tokenizer handle>) takes the
-    device form of a loaded tokenizer.json (SmtError with code SMT_E_UNSUPPORTED when it has none).  Calls
-    smt_unigram_{tokenize,scan_device,emit_device,destroy}; a line can hold one token more than looked-at bytes."""
+    device form of a loaded tokenizer.json (SmtError with code SMT_E_UNSUPPORTED when it has none); utf8=True takes its UTF-8 form
+    (smt_host_tokenizer_to_device_unigram_utf8).  codepoints: a list of (first, last, class L.WP_CP_*, output str or bytes, "" =
+    itself) for the code points >= U+0080, sorted and disjoint (smt_unigram_create_utf8; no class ALONE; the replacement's own code
+    point is a SPACE).  Calls smt_unigram_{tokenize,scan_device,emit_device,destroy}; a line can hold one token more than looked-at
+    bytes."""
 
     _prefix, _extra_slot = "unigram", 1
 
     def __init__(self, ctx, vocab=None, unk_id=-1, replacement="\u2581", prepend="always", byte_map=None, added=(), unk_score=None,
-                 host_tokenizer=None):
+                 host_tokenizer=None, codepoints=None, utf8=False):
         self.ctx = ctx
         self._h = C.c_void_p()
         if host_tokenizer is not None:
-            L.check(L.lib().smt_host_tokenizer_to_device_unigram(host_tokenizer, ctx._h, C.byref(self._h)))
+            to_device = L.lib().smt_host_tokenizer_to_device_unigram_utf8 if utf8 else L.lib().smt_host_tokenizer_to_device_unigram
+            L.check(to_device(host_tokenizer, ctx._h, C.byref(self._h)))
             return
         pieces = [(p.encode() if isinstance(p, str) else bytes(p), float(s)) for p, s in vocab]
         pool = b"".join(p for p, _ in pieces)
@@ -431,7 +436,24 @@ class Unigram(_DeviceTokenizer):
         prm = L.SmtUnigramParams(pool, L.np_ptr(off), L.np_ptr(ids), len(pieces), L.np_ptr(scores), float(unk_score), int(unk_id), rep,
                                  len(rep), int(L.UG_PREPEND.get(prepend, prepend)), L.np_ptr(bmap), b"".join(added_b), L.np_ptr(aoff),
                                  len(added_b))
-        L.check(L.lib().smt_unigram_create(ctx._h, C.byref(prm), C.byref(self._h)))
+        if codepoints is None and not utf8:
+            L.check(L.lib().smt_unigram_create(ctx._h, C.byref(prm), C.byref(self._h)))
+            return
+        codepoints = list(codepoints or [])
+        outs = [(o.encode() if isinstance(o, str) else bytes(o)) for _, _, _, o in codepoints]
+        first = np.array([c[0] for c in codepoints], dtype=np.uint32)
+        last = np.array([c[1] for c in codepoints], dtype=np.uint32)
+        cls = np.array([c[2] for c in codepoints], dtype=np.uint8)
+        ooff = np.zeros(len(outs) + 1, dtype=np.uint32)
+        ooff[1:] = np.cumsum([len(o) for o in outs], dtype=np.uint64)
+        cps = L.SmtWordpieceCodepoints(L.np_ptr(first), L.np_ptr(last), L.np_ptr(cls), b"".join(outs), L.np_ptr(ooff), len(outs))
+        L.check(L.lib().smt_unigram_create_utf8(ctx._h, C.byref(prm), C.byref(cps), C.byref(self._h)))
+
+    def info(self):
+        """(bytes of the whole device table, bytes of its code-point part -- 0 for the ASCII form --, True for the UTF-8 form)"""
+        table, cps, utf8 = C.c_uint64(), C.c_uint64(), C.c_int()
+        L.check(L.lib().smt_unigram_info(self._h, C.byref(table), C.byref(cps), C.byref(utf8)))
+        return int(table.value), int(cps.value), bool(utf8.value)
 
 
 class Corpus:

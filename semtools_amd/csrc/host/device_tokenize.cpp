@@ -71,12 +71,19 @@ DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bo
     WordpieceExport x;
     UnigramExport u;
     WordpieceUtf8Export x8;
+    UnigramUtf8Export u8;
     if (utf8 && tok.export_wordpiece_utf8(x8)) {
         const smt_wordpiece_params p = x8.base.params();
         const smt_wordpiece_codepoints cp = x8.codepoints();
         smt_wordpiece *wp = nullptr;
         api_ok(smt_wordpiece_create_utf8(ctx, &p, &cp, &wp), "smt_wordpiece_create_utf8");
         h = smt::tok_handle(wp);
+    } else if (utf8 && tok.export_unigram_utf8(u8)) {
+        const smt_unigram_params p = u8.base.params();
+        const smt_wordpiece_codepoints cp = u8.codepoints();
+        smt_unigram *ug = nullptr;
+        api_ok(smt_unigram_create_utf8(ctx, &p, &cp, &ug), "smt_unigram_create_utf8");
+        h = smt::tok_handle(ug);
     } else if (tok.export_wordpiece(x)) {
         const smt_wordpiece_params p = x.params();
         smt_wordpiece *wp = nullptr;

@@ -712,7 +712,66 @@ public:
         return true;
     }
 
+    // The UTF-8 form: the normalizers export_unigram admits act on one code point without context, so the table is what
+    // apply_normalizer makes of every single code point.  Behind Metaspace a code point is a SPACE when it becomes exactly ' ' (or is
+    // the replacement itself, left alone: Metaspace splits at a literal replacement as at a replaced space), DROPPED when nothing is
+    // left, ORDINARY when no output is ' ' or the replacement.  FLAG (the line stays with encode()): ' ' or the replacement beside
+    // other characters (a Chinese character between its two spaces); under a chain with NFD an output of non-zero combining class
+    // (the canonical reordering would depend on the neighbours); more output characters than the source has bytes (the kernel's
+    // lattice nodes and token slots are the piece's own bytes).  Equal neighbours merge into ranges.
+    bool export_unigram_utf8(UnigramUtf8Export &x) const override
+    {
+        for (const AddedToken &t : added_) {
+            if (t.normalized) continue;
+            for (uint32_t c : t.content) if (c >= 0x80) return false;   // (matched on the raw text: the kernel's added tokens are ASCII)
+        }
+        if (!export_unigram(x.base)) return false;
+        const PreTokenizer *ms = pre_.kind == PreTokenizer::Seq ? &pre_.children[0] : &pre_;   // (export_unigram checked the shape)
+        const uint32_t rep = ms->replacement;
+        const bool reorders = has_norm_ && has_nfd(norm_);
+        x.first.clear(); x.last.clear(); x.cls.clear(); x.out_pool.clear();
+        x.out_off.assign(1, 0);
+        U32 s;
+        for (uint32_t cp = 0x80; cp <= 0x10FFFF; ++cp) {
+            if (cp == 0xD800) cp = 0xE000;
+            s.assign(1, cp);
+            if (has_norm_) apply_normalizer(norm_, s);
+            bool splits = false, marks = false;
+            for (uint32_t c : s) {
+                splits = splits || c == ' ' || c == rep;
+                marks = marks || ccc_of(c) != 0;
+            }
+            const size_t src = cp < 0x800 ? 2 : cp < 0x10000 ? 3 : 4;
+            uint8_t k = SMT_WP_CP_FLAG;
+            if (s.empty()) k = SMT_WP_CP_DROPPED;
+            else if (s.size() == 1 && splits) k = SMT_WP_CP_SPACE;
+            else if (!splits && s.size() <= src && !(reorders && marks)) k = SMT_WP_CP_ORDINARY;
+            if (k == SMT_WP_CP_FLAG) continue;   // (a code point in no range is FLAG)
+            std::string out;
+            if (k == SMT_WP_CP_ORDINARY && !(s.size() == 1 && s[0] == cp)) out = to_utf8(s, 0, s.size());
+            if (out.empty() && !x.first.empty() && x.last.back() + 1 == cp && x.cls.back() == k && x.out_off[x.out_off.size() - 2] == x.out_off.back()) {
+                x.last.back() = cp;
+                continue;
+            }
+            x.first.push_back(cp);
+            x.last.push_back(cp);
+            x.cls.push_back(k);
+            x.out_pool += out;
+            x.out_off.push_back((uint32_t)x.out_pool.size());
+        }
+        return true;
+    }
+
 private:
+    // NFD in the chain, directly or through BertNormalizer's strip_accents
+    static bool has_nfd(const Normalizer &n)
+    {
+        if (n.kind == Normalizer::Nfd) return true;
+        if (n.kind == Normalizer::Bert) return n.strip_accents;
+        if (n.kind == Normalizer::Seq)
+            for (const Normalizer &c : n.children) if (has_nfd(c)) return true;
+        return false;
+    }
     // a normalizer built only of components that map an ASCII character on its own (no Strip, no Replace)
     static bool bytewise(const Normalizer &n)
     {

@@ -123,6 +123,26 @@ struct UnigramExport {
     }
 };
 
+// the same family for UTF-8 lines (smt_unigram_create_utf8): the vocabulary as above, and what every code point >= U+0080 becomes
+// under the normalizer, as ranges (smt_wordpiece_codepoints, which points into these)
+struct UnigramUtf8Export {
+    UnigramExport base;
+    std::vector<uint32_t> first, last, out_off;
+    std::vector<uint8_t> cls;
+    std::string out_pool;
+    smt_wordpiece_codepoints codepoints() const   // (points into this object)
+    {
+        smt_wordpiece_codepoints c{};
+        c.first = first.data();
+        c.last = last.data();
+        c.cls = cls.data();
+        c.out_pool = out_pool.data();
+        c.out_off = out_off.data();
+        c.n = first.size();
+        return c;
+    }
+};
+
 class Tokenizer {
 public:
     virtual ~Tokenizer() = default;
@@ -139,6 +159,8 @@ public:
     virtual bool export_unigram(UnigramExport &) const { return false; }
     // the UTF-8 form of export_wordpiece: the same family, and no added token matched on the raw text may hold a non-ASCII byte
     virtual bool export_wordpiece_utf8(WordpieceUtf8Export &) const { return false; }
+    // the UTF-8 form of export_unigram, under the same two conditions
+    virtual bool export_unigram_utf8(UnigramUtf8Export &) const { return false; }
 };
 // whitespace words looked up in a vocab file (one token per line, id = line index)
 std::unique_ptr<Tokenizer> make_vocab_tokenizer(const std::string &vocab_path, const std::string &unk_token);
@@ -177,7 +199,7 @@ struct TokenCsr {
 struct DeviceTokenRoute;
 // fills the CSR (ids, offsets [lines.size() + 1]) of the batch's flagged lines, given by their index in the batch
 using DeviceFlaggedFn = std::function<void(const std::vector<uint64_t> &lines, std::vector<uint32_t> &ids, std::vector<uint64_t> &offsets)>;
-// utf8: the UTF-8 form of a WordPiece tokenizer where it has one (export_wordpiece_utf8), else what utf8 = false makes
+// utf8: the UTF-8 form where the tokenizer has one (export_wordpiece_utf8, then export_unigram_utf8), else what utf8 = false makes
 DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bool utf8 = false);
 void device_route_destroy(DeviceTokenRoute *r);
 uint64_t device_route_lines(const DeviceTokenRoute *r);   // lines tokenized on the device so far

@@ -355,6 +355,23 @@ int smt_host_tokenizer_to_device_unigram(smt_host_tokenizer *tok, smt_ctx *ctx, 
     } catch (const std::exception &e) { return fail(e); }
 }
 
+int smt_host_tokenizer_to_device_unigram_utf8(smt_host_tokenizer *tok, smt_ctx *ctx, smt_unigram **out)
+{
+    if (!tok || !out) { smt::set_error("null argument"); return SMT_E_INVALID; }
+    *out = nullptr;
+    try {
+        UnigramUtf8Export x;
+        if (!tok->t->export_unigram_utf8(x)) {
+            smt::set_error("this tokenizer has no UTF-8 Unigram device form (a per-character normalizer -> Metaspace -> Unigram with ASCII "
+                           "added tokens only)");
+            return SMT_E_UNSUPPORTED;
+        }
+        const smt_unigram_params p = x.base.params();
+        const smt_wordpiece_codepoints cp = x.codepoints();
+        return smt_unigram_create_utf8(ctx, &p, &cp, out);   // (no context: SMT_E_HIP on a machine without a device)
+    } catch (const std::exception &e) { return fail(e); }
+}
+
 static int host_model_from_dir(smt_ctx *ctx, smt_group *group, const char *dir, smt_host_model **out)
 {
     if ((!ctx && !group) || !dir || !out) { smt::set_error("null argument"); return SMT_E_INVALID; }

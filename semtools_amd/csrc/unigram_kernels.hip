@@ -20,6 +20,9 @@
 // pieces share a slot and slot order is token order; pass 2 is the shared one (tokenize_frame.h) on these slots.
 //
 // Every loop is bounded: probes by the table's capacity, walks by the longest piece and the piece's end, pieces by SMT_UG_MAX_WORD.
+//
+// Also here: the create of both forms of the handle.  The UTF-8 form's pass 1 is unigram_utf8_kernels.hip; the table and the handle
+// the two share are in unigram_table.h.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -27,32 +30,18 @@
 
 #include "common.h"
 #include "tokenize_frame.h"
+#include "unigram_table.h"
 
 namespace {
 
-constexpr unsigned UG_THREADS = 256;                       // pass 1: one position per thread
-constexpr unsigned UG_NODES = UG_THREADS + SMT_UG_MAX_WORD;
-constexpr uint8_t UG_DROP = 0xFF;                          // byte_map: the byte is dropped
-constexpr uint32_t KEY_START = 0, KEY_R = 1;               // a node's start: the piece's start, the node behind R, or 2 + (raw byte - owner)
-constexpr uint16_t FROM_UNSET = 0xFFFF, FROM_UNK = 0x8000;
-
-struct UgTable {
-    const unsigned long long *slots;   // (tag << 32) | entry + 1; 0 = empty
-    const uint4 *ent;                  // {pool offset of the piece, its length, its id, 1 = the piece starts with R}
-    const double *score;               // per entry
-    const uint8_t *pool;
-    const uint8_t *map;                // [128]: the normalised byte, UG_DROP
-    uint32_t mask;                     // capacity - 1
-    uint32_t max_piece;                // longest piece of the vocabulary, in bytes
-    uint32_t unk;                      // TOK_NONE: none
-    uint32_t rlen;                     // bytes of R
-    uint32_t prepend;                  // 0 always, 1 first, 2 never
-    uint32_t r_id, r_unk;              // the edge over R alone: the piece R, or the unknown edge
-    double r_score;
-    double unk_score;
-    unsigned long long r_state;        // the hash after R
-    smt::TokAdded added;
-};
+using smt::FROM_UNK;
+using smt::FROM_UNSET;
+using smt::KEY_R;
+using smt::KEY_START;
+using smt::UG_DROP;
+using smt::UG_NODES;
+using smt::UG_THREADS;
+using smt::UgTable;
 
 // the candidate: clen kept bytes from raw position s (dropped bytes skipped), behind R for kind 1, hash h: its entry + 1, or 0
 __device__ __forceinline__ uint32_t ug_probe(const UgTable &T, const uint8_t *__restrict__ text, const uint8_t *map, unsigned long long h,
@@ -209,33 +198,38 @@ constexpr smt::TokWords UG_WORDS = {"no scan to emit (smt_unigram_scan_device co
 
 }  // namespace
 
-struct smt_unigram : smt::TokHandle {   // every line has one slot more than bytes
-    UgTable T{};                      // points into d_table: slots | entries | scores | pool | byte map | added pool | added offsets
-    explicit smt_unigram(smt_ctx *c) : smt::TokHandle(c, true, UG_WORDS) {}
-    int pass1(const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev, uint64_t n_lines,
-              uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev) override
-    {
-        if (!n_lines) return SMT_OK;
-        hipLaunchKernelGGL(ug_slot_begin_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, ctx->stream, line_begin_dev, n_lines,
-                           S.slot_begin());
-        SMT_HIP_CHECK(hipGetLastError());
-        if (!text_bytes) return SMT_OK;
-        hipLaunchKernelGGL(ug_scan_kernel, dim3((unsigned)((text_bytes + UG_THREADS - 1) / UG_THREADS)), dim3(UG_THREADS), 0, ctx->stream, T, text_dev,
-                           text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, S.d_ids_tmp, S.raw_count(), flags_dev);
-        SMT_HIP_CHECK(hipGetLastError());
-        return SMT_OK;
-    }
-};
+smt_unigram::smt_unigram(smt_ctx *c) : smt::TokHandle(c, true, UG_WORDS) {}
+
+int smt::ug_slot_begin_launch(smt_unigram *tok, const uint64_t *line_begin_dev, uint64_t n_lines)
+{
+    hipLaunchKernelGGL(ug_slot_begin_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, tok->ctx->stream, line_begin_dev, n_lines,
+                       tok->S.slot_begin());
+    SMT_HIP_CHECK(hipGetLastError());
+    return SMT_OK;
+}
+
+int smt_unigram::pass1(const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev, uint64_t n_lines,
+                       uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev)
+{
+    if (!n_lines) return SMT_OK;
+    const int rc = smt::ug_slot_begin_launch(this, line_begin_dev, n_lines);
+    if (rc) return rc;
+    if (!text_bytes) return SMT_OK;
+    if (utf8) return smt::ug_scan_utf8_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev);
+    hipLaunchKernelGGL(ug_scan_kernel, dim3((unsigned)((text_bytes + UG_THREADS - 1) / UG_THREADS)), dim3(UG_THREADS), 0, ctx->stream, T, text_dev,
+                       text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, S.d_ids_tmp, S.raw_count(), flags_dev);
+    SMT_HIP_CHECK(hipGetLastError());
+    return SMT_OK;
+}
 
 using namespace smt;
 
 TokHandle *smt::tok_handle(smt_unigram *tok) { return tok; }
 
-extern "C" {
-
-int smt_unigram_create(smt_ctx *ctx, const smt_unigram_params *p, smt_unigram **out)
-try {
-    if (!ctx) return tok_null_handle("smt_unigram_create");
+// the body of both creates.  cp == nullptr: the ASCII form (a byte >= 0x80 flags its line, pieces with such a byte cannot match and
+// are left out); otherwise the UTF-8 form: all pieces enter, the code points come from *cp
+static int ug_create(smt_ctx *ctx, const smt_unigram_params *p, const smt_wordpiece_codepoints *cp, smt_unigram **out)
+{
     SMT_REQUIRE(p != nullptr && out != nullptr, "null argument");
     *out = nullptr;
     SMT_REQUIRE(p->n_pieces == 0 || (p->pool && p->piece_off && p->piece_id && p->scores), "vocabulary arrays");
@@ -250,11 +244,20 @@ try {
     SMT_REQUIRE(p->n_added == 0 || (p->added_pool && p->added_off), "added tokens");
     for (uint64_t i = 0; i < p->n_pieces; ++i) SMT_REQUIRE(p->piece_off[i] <= p->piece_off[i + 1], "piece_off must be non-decreasing");
     for (uint32_t i = 0; i < p->n_added; ++i) SMT_REQUIRE(p->added_off[i] <= p->added_off[i + 1], "added_off must be non-decreasing");
-    int rc = bind_device(ctx);
-    if (rc) return rc;
+    WpCodepointImage img;
+    int rc = SMT_OK;
+    if (cp) {   // (validated before anything is uploaded)
+        TokAdded probe;
+        if ((rc = tok_added_first(p, probe))) return rc;
+        for (uint64_t i = 0; i < cp->n && cp->cls; ++i)
+            SMT_REQUIRE(cp->cls[i] != SMT_WP_CP_ALONE, "a code point of class ALONE has no meaning behind Metaspace");
+        if ((rc = wp_codepoint_image(cp, img))) return rc;
+    }
+    if ((rc = bind_device(ctx))) return rc;
 
     // ---- entries: every ASCII piece (kind 0) and every piece that is R + ASCII bytes (kind 1).  R alone is no entry: its edge is
-    // fixed (T.r_*).  Every other piece with a byte >= 0x80 cannot match an ASCII line, but counts for the longest-piece bound.
+    // fixed (T.r_*).  ASCII form: every other piece with a byte >= 0x80 cannot match an ASCII line, but counts for the longest-piece
+    // bound.  UTF-8 form: those pieces enter too.
     const uint32_t rlen = p->replacement_len;
     const uint64_t r_state = tok_hash_bytes(p->replacement, rlen);
     std::vector<TokEntry> ents;
@@ -270,7 +273,7 @@ try {
         const bool with_r = len >= rlen && memcmp(p->pool + off, p->replacement, rlen) == 0;
         bool ascii = true;
         for (uint32_t j = with_r ? rlen : 0; j < len && ascii; ++j) ascii = (uint8_t)p->pool[off + j] < 0x80;
-        if (!ascii) continue;
+        if (!ascii && !cp) continue;
         if (with_r && len == rlen) { r_known = true; r_id = p->piece_id[i]; r_score = p->scores[i]; continue; }   // (repeated: the later one wins)
         ents.push_back({off, len, p->piece_id[i], with_r ? 1u : 0u, tok_hash_bytes(p->pool + off, len), i});
     }
@@ -281,17 +284,32 @@ try {
     std::unique_ptr<smt_unigram> tok(new smt_unigram(ctx));
     UgTable &T = tok->T;
     if ((rc = tok_added_first(p, T.added))) return rc;
-    const uint8_t *at[7];
-    if ((rc = tok_upload_table("unigram",
-                               {{table.slots.data(), table.slots.size() * 8},
-                                {table.ents.data(), table.ents.size() * sizeof(uint4)},
-                                {scores.data(), scores.size() * 8},
-                                {p->pool, p->n_pieces ? p->piece_off[p->n_pieces] : 0},
-                                {p->byte_map, 128},
-                                {p->added_pool, p->n_added ? p->added_off[p->n_added] : 0},
-                                {p->added_off, p->n_added ? ((size_t)p->n_added + 1) * 4 : 0}},
-                               &tok->d_table, at)))
-        return rc;
+    const uint8_t *at[10];
+    std::vector<std::pair<const void *, size_t>> parts = {{table.slots.data(), table.slots.size() * 8},
+                                                          {table.ents.data(), table.ents.size() * sizeof(uint4)},
+                                                          {scores.data(), scores.size() * 8},
+                                                          {p->pool, p->n_pieces ? p->piece_off[p->n_pieces] : 0},
+                                                          {p->byte_map, 128},
+                                                          {p->added_pool, p->n_added ? p->added_off[p->n_added] : 0},
+                                                          {p->added_off, p->n_added ? ((size_t)p->n_added + 1) * 4 : 0}};
+    if (cp) {
+        parts.push_back({img.page.data(), img.page.size() * 2});
+        parts.push_back({img.ent.data(), img.ent.size() * 4});
+        parts.push_back({img.out.data(), img.out.size()});
+    }
+    if ((rc = tok_upload_table("unigram", parts, &tok->d_table, at))) return rc;
+    tok->table_bytes = 0;
+    for (size_t i = 0; i < 7; ++i) tok->table_bytes += parts[i].second;
+    if (cp) {
+        tok->utf8 = true;
+        tok->codepoint_bytes = img.page.size() * 2 + img.ent.size() * 4 + img.out.size();
+        tok->table_bytes += tok->codepoint_bytes;
+        tok->U.page = reinterpret_cast<const uint16_t *>(at[7]);
+        tok->U.ent = reinterpret_cast<const uint32_t *>(at[8]);
+        tok->U.out = at[9];
+        tok->U.n_pages = (uint32_t)(img.ent.size() / 256);
+        tok->U.out_bytes = (uint32_t)img.out.size();
+    }
     T.slots = reinterpret_cast<const unsigned long long *>(at[0]);
     T.ent = reinterpret_cast<const uint4 *>(at[1]);
     T.score = reinterpret_cast<const double *>(at[2]);
@@ -310,6 +328,30 @@ try {
     T.unk_score = p->unk_score;
     T.r_state = r_state;
     *out = tok.release();
+    return SMT_OK;
+}
+
+extern "C" {
+
+int smt_unigram_create(smt_ctx *ctx, const smt_unigram_params *p, smt_unigram **out)
+try {
+    if (!ctx) return tok_null_handle("smt_unigram_create");
+    return ug_create(ctx, p, nullptr, out);
+} catch (...) { return smt::api_catch(); }
+
+int smt_unigram_create_utf8(smt_ctx *ctx, const smt_unigram_params *p, const smt_wordpiece_codepoints *cp, smt_unigram **out)
+try {
+    if (!ctx) return tok_null_handle("smt_unigram_create_utf8");
+    SMT_REQUIRE(cp != nullptr, "null argument");
+    return ug_create(ctx, p, cp, out);
+} catch (...) { return smt::api_catch(); }
+
+int smt_unigram_info(const smt_unigram *tok, uint64_t *table_bytes, uint64_t *codepoint_bytes, int *utf8)
+try {
+    if (!tok) return tok_null_handle("smt_unigram_info");
+    if (table_bytes) *table_bytes = tok->table_bytes;
+    if (codepoint_bytes) *codepoint_bytes = tok->codepoint_bytes;
+    if (utf8) *utf8 = tok->utf8 ? 1 : 0;
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 

@@ -1,0 +1,54 @@
+// unigram_table.h -- what the two pass-1 kernels of the Unigram device tokenizer share (unigram_kernels.hip: pure-ASCII lines,
+// unigram_utf8_kernels.hip: UTF-8 lines): the device table, the constants of a lattice node, the handle, and the launch
+// of the slot starts.  Internal to the library.
+#pragma once
+
+#include "common.h"
+#include "tokenize_frame.h"
+#include "wordpiece_table.h"
+
+namespace smt {
+
+constexpr unsigned UG_THREADS = 256;                       // pass 1: one position per thread
+constexpr unsigned UG_NODES = UG_THREADS + SMT_UG_MAX_WORD;
+constexpr uint8_t UG_DROP = 0xFF;                          // byte_map: the byte is dropped
+constexpr uint32_t KEY_START = 0, KEY_R = 1;               // a node's start: the piece's start, the node behind R, or 2 + (node - owner's node)
+constexpr uint16_t FROM_UNSET = 0xFFFF, FROM_UNK = 0x8000;
+
+struct UgTable {
+    const unsigned long long *slots;   // (tag << 32) | entry + 1; 0 = empty
+    const uint4 *ent;                  // {pool offset of the piece, its length, its id, 1 = the piece starts with R}
+    const double *score;               // per entry
+    const uint8_t *pool;
+    const uint8_t *map;                // [128]: the normalised byte, UG_DROP
+    uint32_t mask;                     // capacity - 1
+    uint32_t max_piece;                // longest piece of the vocabulary, in bytes
+    uint32_t unk;                      // TOK_NONE: none
+    uint32_t rlen;                     // bytes of R
+    uint32_t prepend;                  // 0 always, 1 first, 2 never
+    uint32_t r_id, r_unk;              // the edge over R alone: the piece R, or the unknown edge
+    double r_score;
+    double unk_score;
+    unsigned long long r_state;        // the hash after R
+    smt::TokAdded added;
+};
+
+}  // namespace smt
+
+struct smt_unigram : smt::TokHandle {   // every line has one slot more than bytes
+    smt::UgTable T{};                 // points into d_table: slots | entries | scores | pool | byte map | added pool | added offsets [| code points]
+    smt::WpCodepoints U{};            // the UTF-8 form only: the code points >= U+0080, the table of wordpiece_table.h
+    bool utf8 = false;
+    uint64_t table_bytes = 0, codepoint_bytes = 0;   // of d_table: all of it, and its code-point part
+    explicit smt_unigram(smt_ctx *c);   // (unigram_kernels.hip, with the family's wording of the frame's errors)
+    int pass1(const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev, uint64_t n_lines,
+              uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev) override;
+};
+
+namespace smt {
+// slot_begin[i] = line_begin[i] + i into the handle's scratch (unigram_kernels.hip: ug_slot_begin_kernel on the context's stream)
+int ug_slot_begin_launch(smt_unigram *tok, const uint64_t *line_begin_dev, uint64_t n_lines);
+// pass 1 of the UTF-8 form (unigram_utf8_kernels.hip): ug_scan_utf8_kernel on the context's stream
+int ug_scan_utf8_launch(smt_unigram *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev,
+                        const uint32_t *line_len_dev, uint64_t n_lines, uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev);
+}  // namespace smt

@@ -13,6 +13,9 @@ non-ASCII character (curly quotes, an accented word, a CJK phrase), the pure-ASC
 kernel: the price of 2 where it is not needed), the same lines transliterated into Cyrillic letters (every word non-ASCII, the
 vocabulary transliterated with them) and rewritten as CJK characters without spaces (every character a word of its own), and the size
 of the code-point table.  Writes profiles/device_tokenizer_utf8.json.
+--model unigram --utf8 does the same for the UTF-8 form of the Unigram route, on the same four texts, behind NFD -> Lowercase ->
+StripAccents -> Metaspace (no handle_chinese_chars: a spaced Chinese character is a FLAG behind Metaspace), with the covered share of
+every text (device_tokenized_lines_per_call).  Writes profiles/device_tokenizer_unigram_utf8.json.
 
     python tools/bench_device_tokenizer.py [--model wordpiece|unigram] [--utf8] [--lines 1000000] [--cpus 16] [--out profiles/device_tokenizer.json]"""
 import argparse
@@ -85,6 +88,25 @@ def make_unigram_vocab(words):
         if p not in seen:
             seen.add(p)
             vocab.append((p, 0.0 if p == "<unk>" else -(4.0 + math.log(len(vocab) + 1.0))))
+    return vocab
+
+
+def unigram_utf8_vocab(vocab):
+    """the Unigram vocabulary + the non-ASCII pieces of the --utf8 texts: the accented words, the curly quotes, the CJK characters
+    bare and behind R, and every alphabetic ASCII piece transliterated into Cyrillic letters"""
+    seen = {p for p, _ in vocab}
+    extra = [U.R + "cafe", U.R + "café", U.R + "naive", U.R + "naïve", "“", "”", U.R + "“"]
+    for c in ["中", "文", "字", "符"] + CJK_POOL:
+        extra += [c, U.R + c]
+    for p, _ in vocab:
+        body = p[len(U.R):] if p.startswith(U.R) else p
+        if body.isascii() and body.isalpha():
+            extra.append(p.translate(CYRILLIC))
+    vocab = list(vocab)
+    for p in extra:
+        if p not in seen:
+            seen.add(p)
+            vocab.append((p, -(4.0 + math.log(len(vocab) + 1.0))))
     return vocab
 
 
@@ -194,6 +216,7 @@ def run_utf8(ctx, d, corpus, n_lines, repeats=3):
     entry["2_over_1"] = round(entry["2"]["lines_per_s"] / entry["1"]["lines_per_s"], 3)
     entry["2_over_off"] = round(entry["2"]["lines_per_s"] / entry["off"]["lines_per_s"], 3)
     entry["1_over_off"] = round(entry["1"]["lines_per_s"] / entry["off"]["lines_per_s"], 3)
+    print("measured:", {name: entry[name]["lines_per_s"] for name in ("off", "1", "2")}, "lines/s", flush=True)
     return entry
 
 
@@ -211,7 +234,7 @@ def measure_on_off(ctx, d, corpora, n_lines, result):
         result[corpus_name] = entry
 
 
-def measure_utf8(ctx, d, lines, n_lines, result):
+def measure_utf8(ctx, d, lines, n_lines, result, unigram=False):
     result["what"] = "host-layer ingest (smt_host_search_content), device tokenizer route off / 1 (ASCII form) / 2 (UTF-8 form)"
     result["note"] = ("kernel profiling events are on in all settings; per setting one warm-up call is discarded, then three rounds visit "
                       "off, 1, 2 in turn; every timed call ends in a device synchronise; seconds_best is the best of 3, spread_percent "
@@ -219,7 +242,7 @@ def measure_utf8(ctx, d, lines, n_lines, result):
     h = C.c_void_p()
     L.check(L.lib().smt_host_tokenizer_load(os.path.join(d, "tokenizer.json").encode(), C.byref(h)))
     t0 = time.perf_counter()
-    tok = smt.WordPiece(ctx, host_tokenizer=h, utf8=True)
+    tok = (smt.Unigram if unigram else smt.WordPiece)(ctx, host_tokenizer=h, utf8=True)
     result["code_point_table"] = {"create_seconds": round(time.perf_counter() - t0, 3), "table_bytes": tok.info()[0],
                                   "code_point_bytes": tok.info()[1]}
     tok.close()
@@ -240,16 +263,18 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     unigram = a.model == "unigram"
-    if a.utf8 and unigram:
-        ap.error("--utf8 is the WordPiece route's")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "device_tokenizer_utf8.json" if a.utf8 else "device_tokenizer_unigram.json" if unigram else "device_tokenizer.json")
+        name = ("device_tokenizer_unigram_utf8.json" if unigram else "device_tokenizer_utf8.json") if a.utf8 else \
+            "device_tokenizer_unigram.json" if unigram else "device_tokenizer.json"
+        a.out = os.path.join(ROOT, "profiles", name)
     if a.cpus and hasattr(os, "sched_setaffinity"):
         os.sched_setaffinity(0, sorted(os.sched_getaffinity(0))[: a.cpus])
     rng = np.random.default_rng(7)
     words = make_words(30_000, rng)
     vocab = make_unigram_vocab(words) if unigram else make_vocab(words)
-    if a.utf8:
+    if a.utf8 and unigram:
+        vocab = unigram_utf8_vocab(vocab)
+    elif a.utf8:
         for p in ["cafe", "café", "naive", "naïve", "\u201c", "\u201d", "\u4e2d", "\u6587", "\u5b57", "\u7b26"] + CJK_POOL:
             vocab.setdefault(p, len(vocab))
         for p in [p for p in vocab if p.replace("##", "", 1).isalpha() and p.isascii() and p.replace("##", "", 1).islower()]:
@@ -268,14 +293,17 @@ def main():
         from safetensors.numpy import save_file
 
         save_file({"embeddings": synth.table(len(vocab), seed=2)}, os.path.join(d, "model.safetensors"))
-        if unigram:
+        if unigram and a.utf8:      # (a chain without handle_chinese_chars: behind Metaspace a spaced Chinese character is a FLAG)
+            result["tokenizer"] = "NFD -> Lowercase -> StripAccents -> Metaspace -> Unigram"
+            U.write_tokenizer(os.path.join(d, "tokenizer.json"), norm="seq", prepend="always", vocab=vocab, added=[])
+        elif unigram:
             U.write_tokenizer(os.path.join(d, "tokenizer.json"), norm="bert_clean", prepend="always", vocab=vocab, added=[])
         else:
             W.write_tokenizer(os.path.join(d, "tokenizer.json"), 7, vocab=vocab)
         with open(os.path.join(d, "config.json"), "w") as f:
             json.dump({"normalize": True, "unk_token": "<unk>" if unigram else "[UNK]"}, f)
         if a.utf8:
-            measure_utf8(ctx, d, lines, a.lines, result)
+            measure_utf8(ctx, d, lines, a.lines, result, unigram)
         else:
             flagged = [ln.replace(" ", " café ", 1) if i % 10 == 0 else ln for i, ln in enumerate(lines)]
             measure_on_off(ctx, d, (("ascii", lines), ("ten_percent_flagged", flagged)), a.lines, result)
