@@ -356,6 +356,12 @@ int smt_corpus_append_host(smt_corpus *corpus, const float *rows, uint64_t n_row
 int smt_corpus_write_rows(smt_corpus *corpus, uint64_t first_row, const float *rows,
                           uint64_t n_rows);
 int smt_corpus_read_rows(smt_corpus *corpus, uint64_t first_row, uint64_t n_rows, float *out_host);
+/* Forget the rows from n_rows on.  A host-side count: nothing is enqueued and the one-query pipeline is NOT drained -- calls
+ * queued earlier keep the row count they were made with, a call made behind a truncation that dropped rows has another count and so
+ * is not taken along by one of them (n_rows equal to the count drops nothing and changes nothing), and whatever writes the freed
+ * rows next (append, embed, write_rows) drains first.  Every other call that changes what a
+ * corpus holds drains the pipeline before it touches a row (append, write_rows, compact unless it keeps everything, prepack,
+ * embed into the corpus, destroy). */
 int smt_corpus_truncate(smt_corpus *corpus, uint64_t n_rows);
 /* Keep exactly the rows inside `keep` (sorted, disjoint, inside [0, rows)), in order, and close the gaps IN PLACE:
  * afterwards the corpus holds sum(len) rows and old row keep[i].begin + j is row prefix[i] + j.  n_keep == 0 empties it.
@@ -1016,7 +1022,15 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *   merge_on_aux (0/1)   smt_merge_topk_packed_device is enqueued on the aux stream (see smt_ctx_aux_stream)
  *   compact_bounce_rows (64 .. 2^20, default 65536 = 64 MiB)  smt_corpus_compact: a step whose rows move down by fewer rows than this
  *                        goes through a bounce buffer of this many rows in the context's scratch (a launch must not overwrite its own
- *                        sources); a step with a longer gap is one direct launch.  At most 2 x ceil(rows / this) enqueues per call */
+ *                        sources); a step with a longer gap is one direct launch.  At most 2 x ceil(rows / this) enqueues per call
+ * The keys and the one-query pipeline.  The keys that say so above drain it.  scan_blocks, scan_threads, scan_unroll and
+ * guard_band are stored without a drain, while the list sets of earlier calls are still in flight: they shape the NEXT launch
+ * only.  direct_delivery is stored without one too and concerns the host form alone (smt_search, smt_ivfpq_search), which drains
+ * the pipeline itself before it scans; a queued device call never reads the key.  A queued leader takes a later call when corpus address, scanned rows, list size and grid all agree, so a call
+ * made behind a changed guard_band or scan_blocks starts a group of its own; scan_threads is not part of that test and need not
+ * be -- a leader scans with its own block size and writes one list per block whatever the taken call's would have been; with
+ * scan_unroll other than 4 a call runs the plain kernel.  tests/test_gpu_pipeline_life.py switches every key named here between
+ * queued calls, away from its default and back, and compares every answer with the oracle. */
 int smt_set_tuning(smt_ctx *ctx, const char *key, int64_t value);
 
 /* ------------------------------------------------------------------ host ids
