@@ -468,7 +468,15 @@ int smt_search_topk_device_ex(smt_corpus *corpus, const float *queries_dev, uint
 /* Merge `n_lists` sorted (dist asc, row asc) lists of length k_in each (padded
  * with UINT64_MAX/+inf) per query into the best k_out.  Inputs are laid out
  * [n_lists][nq][k_in] -- exactly what an all-gather of per-rank
- * smt_search_topk_device outputs produces.  Host version: */
+ * smt_search_topk_device outputs produces.  The output is ordered (dist asc, row asc) and padded the same way.
+ * Preconditions, of the host and of every device form:
+ *   - rows are DISTINCT within a query across all lists (shards own disjoint rows).  Every candidate takes the output slot of its
+ *     rank among the others; two equal (distance, row) pairs would take the same slot and leave a padding entry in the middle
+ *     of the list (device forms; the host form would return the pair twice)
+ *   - n_lists x k_in <= 8192 on the device forms; more is SMT_E_INVALID and nothing is written
+ *   - padding is recognised by the ROW alone (UINT64_MAX); the distance stored beside it is never read
+ * n_lists == 0 writes k_out padding entries per query, also with the output buffers given as the (unread) inputs.
+ * Host version: */
 int smt_merge_topk(const uint64_t *rows, const double *dist, uint32_t n_lists, uint32_t nq,
                    uint32_t k_in, uint32_t k_out, uint64_t *out_rows, double *out_dist,
                    uint64_t *out_counts);
@@ -921,6 +929,26 @@ int smt_debug_batched_scores(smt_corpus *corpus, const float *queries, uint32_t 
  * A key that names a row outside the corpus, or a counted slot that was never written, is SMT_E_INVALID. */
 int smt_debug_nominations(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
                           const float *tau, int buffered, float *out_dist, uint32_t *out_hits, uint32_t *out_counts, uint32_t *out_route);
+
+/* Test hooks for the cross-shard merge (csrc/merge.hip): the kernels behind every sharded answer, run on lists a test constructs
+ * instead of lists a group's shards produced.  tests/test_gpu_merge.py compares them bit for bit with a NumPy merge
+ * (tests/merge_ref.py).  The preconditions of smt_merge_topk hold here too.  Device pointers unless said otherwise; asynchronous on the
+ * context's stream; nq == 0 or k_out == 0 returns SMT_OK and enqueues nothing.
+ *   smt_debug_merge_sources         the merge of lists that are NOT gathered, as the peer transport runs it: lists_dev is a HOST array of
+ *                                   n_lists (1..64) device pointers, each a packed [nq][2][k_in] list in a buffer of its own;
+ *                                   out_packed_dev receives [nq][2][k_out]
+ *   smt_debug_merge_packed_strided  smt_merge_topk_packed_device as the copy and RCCL transports run it: list l starts
+ *                                   l x list_stride_words words behind packed_dev (0 = dense, nq x 2 x k_in), so that a rank's status
+ *                                   words may lie between the lists
+ *   smt_debug_combine_status        out_status_dev[q] = the largest of the n sources' q-th 64-bit status word.  Exactly one of words_dev
+ *                                   (a HOST array of n <= 64 device pointers, nq words each) and base_dev (n blocks of nq words,
+ *                                   stride_words >= nq apart) is given; both or neither is SMT_E_INVALID */
+int smt_debug_merge_sources(smt_ctx *ctx, const uint64_t *const *lists_dev, uint32_t n_lists, uint32_t nq, uint32_t k_in, uint32_t k_out,
+                            uint64_t *out_packed_dev);
+int smt_debug_merge_packed_strided(smt_ctx *ctx, const uint64_t *packed_dev, uint64_t list_stride_words, uint32_t n_lists, uint32_t nq,
+                                   uint32_t k_in, uint32_t k_out, uint64_t *out_packed_dev);
+int smt_debug_combine_status(smt_ctx *ctx, const uint64_t *const *words_dev, const uint64_t *base_dev, uint64_t stride_words, uint32_t n,
+                             uint32_t nq, uint32_t *out_status_dev);
 
 /* The context's second stream (hipStream_t), created on first use: async selects run on it, or, with tuning key
  * scan_overlap, it waits for them (every select of an overlapped call enqueued before the work).  A host that

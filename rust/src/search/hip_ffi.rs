@@ -888,6 +888,34 @@ extern "C" {
         out_counts: *mut u32,
         out_route: *mut u32,
     ) -> c_int;
+    pub fn smt_debug_merge_sources(
+        ctx: *mut SmtCtx,
+        lists_dev: *const *const u64,
+        n_lists: u32,
+        nq: u32,
+        k_in: u32,
+        k_out: u32,
+        out_packed_dev: *mut u64,
+    ) -> c_int;
+    pub fn smt_debug_merge_packed_strided(
+        ctx: *mut SmtCtx,
+        packed_dev: *const u64,
+        list_stride_words: u64,
+        n_lists: u32,
+        nq: u32,
+        k_in: u32,
+        k_out: u32,
+        out_packed_dev: *mut u64,
+    ) -> c_int;
+    pub fn smt_debug_combine_status(
+        ctx: *mut SmtCtx,
+        words_dev: *const *const u64,
+        base_dev: *const u64,
+        stride_words: u64,
+        n: u32,
+        nq: u32,
+        out_status_dev: *mut u32,
+    ) -> c_int;
     pub fn smt_ctx_aux_stream(ctx: *mut SmtCtx, stream_out: *mut *mut c_void) -> c_int;
     pub fn smt_set_tuning(ctx: *mut SmtCtx, key: *const c_char, value: i64) -> c_int;
     pub fn smt_fnv1a_hash(bytes: *const u8, n: u64) -> u64;

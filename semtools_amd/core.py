@@ -166,6 +166,28 @@ class Context:
         L.check(L.lib().smt_merge_topk_packed_device(self._h, C.c_void_p(packed_ptr), n_lists, nq, k_in, k_out,
                                                      C.c_void_p(out_packed_ptr)))
 
+    def debug_merge_sources(self, list_ptrs, nq, k_in, k_out, out_packed_ptr, n_lists=None):
+        """Test hook (smt_debug_merge_sources): the in-place merge of the peer transport over packed [nq][2][k_in] lists, one device
+        pointer each.  n_lists: the count passed on, where it is not len(list_ptrs)."""
+        n = len(list_ptrs)
+        lp = (C.c_void_p * max(n, 1))(*[C.c_void_p(int(p)) for p in list_ptrs])
+        L.check(L.lib().smt_debug_merge_sources(self._h, lp, n if n_lists is None else int(n_lists), nq, k_in, k_out,
+                                                C.c_void_p(out_packed_ptr)))
+
+    def debug_merge_packed_strided(self, packed_ptr, list_stride_words, n_lists, nq, k_in, k_out, out_packed_ptr):
+        """Test hook (smt_debug_merge_packed_strided): merge_topk_packed_device over lists list_stride_words apart (0 = dense)."""
+        L.check(L.lib().smt_debug_merge_packed_strided(self._h, C.c_void_p(packed_ptr), int(list_stride_words), n_lists, nq, k_in, k_out,
+                                                       C.c_void_p(out_packed_ptr)))
+
+    def debug_combine_status(self, n, nq, out_status_ptr, word_ptrs=None, base_ptr=None, stride_words=0):
+        """Test hook (smt_debug_combine_status): the worst of n sources' status words per query, the sources given by pointer
+        (word_ptrs) or stride_words apart behind base_ptr -- exactly one of the two."""
+        wp = None
+        if word_ptrs is not None:
+            wp = (C.c_void_p * max(len(word_ptrs), 1))(*[C.c_void_p(int(p)) for p in word_ptrs])
+        L.check(L.lib().smt_debug_combine_status(self._h, wp, C.c_void_p(base_ptr) if base_ptr else None, int(stride_words), int(n), int(nq),
+                                                 C.c_void_p(out_status_ptr)))
+
 
 class Model:
     """Device-resident model2vec table (smt_model)."""

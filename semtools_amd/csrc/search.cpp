@@ -1072,4 +1072,45 @@ try {
     return launch_merge_topk_packed(ctx, packed_dev, n_lists, nq, k_in, k_out, out_packed_dev);
 } catch (...) { return smt::api_catch(); }
 
+// Test hooks: the launchers of merge.hip as the exchange calls them (group_exchange.cpp), on constructed lists.  Nothing is checked
+// here that the launchers check themselves: their refusals are what the tests look at.
+int smt_debug_merge_sources(smt_ctx *ctx, const uint64_t *const *lists_dev, uint32_t n_lists, uint32_t nq, uint32_t k_in, uint32_t k_out,
+                            uint64_t *out_packed_dev)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    SMT_REQUIRE(n_lists == 0 || lists_dev != nullptr, "null argument");
+    SMT_REQUIRE(nq == 0 || k_out == 0 || out_packed_dev != nullptr, "null output");
+    if ((rc = bind_device(ctx))) return rc;
+    if (nq == 0 || k_out == 0) return SMT_OK;
+    MergeSources src{};
+    for (uint32_t l = 0; l < n_lists && l < SMT_MAX_MERGE_SOURCES; ++l) src.list[l] = lists_dev[l];   // (more than 64: refused below)
+    return launch_merge_topk_sources_on(ctx->stream, src, n_lists, nq, k_in, k_out, out_packed_dev);
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_merge_packed_strided(smt_ctx *ctx, const uint64_t *packed_dev, uint64_t list_stride_words, uint32_t n_lists, uint32_t nq,
+                                   uint32_t k_in, uint32_t k_out, uint64_t *out_packed_dev)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    SMT_REQUIRE(nq == 0 || k_out == 0 || (packed_dev && out_packed_dev), "null argument");
+    SMT_REQUIRE(list_stride_words == 0 || list_stride_words >= (uint64_t)nq * 2 * k_in, "the list stride is shorter than a list");
+    if ((rc = bind_device(ctx))) return rc;
+    if (nq == 0 || k_out == 0) return SMT_OK;
+    return launch_merge_topk_packed_on(ctx, ctx->stream, packed_dev, n_lists, nq, k_in, k_out, out_packed_dev, list_stride_words);
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_combine_status(smt_ctx *ctx, const uint64_t *const *words_dev, const uint64_t *base_dev, uint64_t stride_words, uint32_t n,
+                             uint32_t nq, uint32_t *out_status_dev)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    SMT_REQUIRE(nq == 0 || out_status_dev != nullptr, "null output");
+    SMT_REQUIRE(base_dev == nullptr || stride_words >= nq, "the stride is shorter than a block of status words");
+    if ((rc = bind_device(ctx))) return rc;
+    MergeSources src{};
+    for (uint32_t j = 0; words_dev && j < n && j < SMT_MAX_MERGE_SOURCES; ++j) src.list[j] = words_dev[j];   // (more than 64: refused below)
+    return launch_combine_status_on(ctx->stream, words_dev ? &src : nullptr, base_dev, stride_words, n, nq, out_status_dev);
+} catch (...) { return smt::api_catch(); }
+
 }  // extern "C"

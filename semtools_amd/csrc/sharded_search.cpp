@@ -284,6 +284,9 @@ try {
     SMT_REQUIRE(top_k >= 1 && top_k <= (largek ? LARGEK_MAX_K : SCAN_MAX_K),
                 largek ? "top_k must be in [1, 1024]" : "top_k must be in [1, 56] (largek_sampled = 0)");
     SMT_REQUIRE((uint64_t)g->n_ranks * top_k <= 8192, "device merge handles up to 8192 candidates per query");
+    // (refused here, before a ring slot is taken and any rank's scan is enqueued)
+    for (int i = 0; out_status && i < g->n_local; ++i)
+        SMT_REQUIRE(!out_status[i] || out_packed[i], "a device that wants the verdicts takes the answer too");
     if (nq == 0) return SMT_OK;
     // with per-query verdicts wanted, every rank's nq status words (SMT_STATUS_* codes written by its select) travel behind its lists
     bool want_status = false;
@@ -332,7 +335,6 @@ try {
     if (!peer && (rc = allgather_words(g, 0, L.gath_off, L.rank_words, &on_aux))) return rc;
     for (int i = 0; i < g->n_local; ++i) {
         uint32_t *status_i = out_status ? out_status[i] : nullptr;
-        SMT_REQUIRE(!status_i || out_packed[i], "a device that wants the verdicts takes the answer too");
         if (!out_packed[i]) continue;
         const hipStream_t st = exchange_stream(g, i, &on_aux);
         // (peer: an answer wanted on ONE device -- the one-thread caller of SURVEY 8(b) -- costs n - 1 waits + a launch + a record here;

@@ -291,8 +291,20 @@ def test_sharded_device_form_refuses_more_than_8192_candidates(big):
         out = torch.zeros((1, 2, 1000), dtype=torch.int64, device="cuda")
         with pytest.raises(SmtError):
             sc.search_topk_device([qd.data_ptr()] * 9, 1, 1000, [out.data_ptr()] + [0] * 8)   # 9 x 1000 > 8192
-        sc.search_topk_device([qd.data_ptr()] * 9, 1, 900, [torch.zeros((1, 2, 900), dtype=torch.int64, device="cuda").data_ptr()] + [0] * 8)
+        # 9 x 900 = 8100 candidates are accepted: the in-place merge on its 128 KiB LDS branch.  Its answer is read: where every shard
+        # proved its list (combined status 0) it is the oracle's over the 90 000 rows
+        out900 = torch.full((1, 2, 900), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device="cuda")
+        st = torch.full((1,), 7, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        sc.search_topk_device([qd.data_ptr()] * 9, 1, 900, [out900.data_ptr()] + [0] * 8, [st.data_ptr()] + [0] * 8)
         g.synchronize()
+        m, s_ = out900.cpu().numpy(), st.cpu().numpy()
+        print("combined status of the 9 x 900 call", s_.tolist())
+        assert s_[0] in (0, 1, 2), s_
+        if s_[0] == 0:
+            orows, odist = _oracle(emb[:90_000], qs[0], 900)
+            assert np.ascontiguousarray(m[0, 0]).view(np.uint64).tolist() == orows
+            assert np.array_equal(np.ascontiguousarray(m[0, 1]).view(np.float64), odist)
         sc.close()
     finally:
         g.close()
