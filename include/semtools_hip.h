@@ -950,6 +950,27 @@ int smt_debug_merge_packed_strided(smt_ctx *ctx, const uint64_t *packed_dev, uin
 int smt_debug_combine_status(smt_ctx *ctx, const uint64_t *const *words_dev, const uint64_t *base_dev, uint64_t stride_words, uint32_t n,
                              uint32_t nq, uint32_t *out_status_dev);
 
+/* Test hook for the select stage (csrc/select.hip): the kernel behind every top_k <= 56 answer, run on block lists a test constructs
+ * instead of lists a scan produced.  tests/test_gpu_select.py compares it bit for bit with a NumPy select (tests/select_ref.py).
+ * Device pointers; asynchronous on the stream of the corpus's context; nq == 0 returns SMT_OK and enqueues nothing.  The corpus gives
+ * the context, the f32 rows behind the keys and nothing else: nothing is scanned.
+ *   queries_dev        [nq][256] f32
+ *   lists_dev          query q's lists start q x list_stride keys behind it (0 = dense, n_lists x kp): n_lists (1..512) lists of kp keys,
+ *                      a key = f32 distance bits << 32 | row, each list ascending, distinct rows within a query, UINT64_MAX padding
+ *                      at the tail of a list
+ *   kp, k_out          1 <= k_out <= kp <= 72; anything else, and a list count outside 1..512, is SMT_E_INVALID
+ *   ws_threshold, ws_thr_score   != 0: only rows with 1 - distance > ws_thr_score are kept
+ *   f32_err            > 0: the exactness certificate with this bound on |f32 distance - exact distance|; 0: none
+ *   overflow_dev       [nq] or NULL; given, a non-zero word makes the query's verdict SMT_STATUS_OVERFLOW
+ *   out_stride         words between two queries' output lists (0 = k_out); the words between the lists are not written
+ *   out_rows_dev, out_dist_dev   [nq][out_stride]: row_base + row and the exact distance, best first, UINT64_MAX / +inf behind them
+ *   out_counts_dev, out_uncertain_dev ([nq] 64-bit), out_status_dev ([nq] 32-bit)   each may be NULL
+ * THE CALLER'S CONTRACT: every row a key names lies below the corpus's row count -- the kernel reads that row and checks nothing. */
+int smt_debug_select_lists(smt_corpus *corpus, const float *queries_dev, uint32_t nq, const uint64_t *lists_dev, uint64_t list_stride,
+                           uint32_t n_lists, uint32_t kp, uint32_t k_out, int ws_threshold, float ws_thr_score, uint64_t row_base,
+                           double f32_err, const uint32_t *overflow_dev, uint64_t out_stride, uint64_t *out_rows_dev, double *out_dist_dev,
+                           uint64_t *out_counts_dev, uint64_t *out_uncertain_dev, uint32_t *out_status_dev);
+
 /* The context's second stream (hipStream_t), created on first use: async selects run on it, or, with tuning key
  * scan_overlap, it waits for them (every select of an overlapped call enqueued before the work).  A host that
  * chains more work behind an async select (an RCCL all-gather of its output, the merge of the gathered

@@ -916,6 +916,27 @@ extern "C" {
         nq: u32,
         out_status_dev: *mut u32,
     ) -> c_int;
+    pub fn smt_debug_select_lists(
+        corpus: *mut SmtCorpus,
+        queries_dev: *const f32,
+        nq: u32,
+        lists_dev: *const u64,
+        list_stride: u64,
+        n_lists: u32,
+        kp: u32,
+        k_out: u32,
+        ws_threshold: c_int,
+        ws_thr_score: f32,
+        row_base: u64,
+        f32_err: f64,
+        overflow_dev: *const u32,
+        out_stride: u64,
+        out_rows_dev: *mut u64,
+        out_dist_dev: *mut f64,
+        out_counts_dev: *mut u64,
+        out_uncertain_dev: *mut u64,
+        out_status_dev: *mut u32,
+    ) -> c_int;
     pub fn smt_ctx_aux_stream(ctx: *mut SmtCtx, stream_out: *mut *mut c_void) -> c_int;
     pub fn smt_set_tuning(ctx: *mut SmtCtx, key: *const c_char, value: i64) -> c_int;
     pub fn smt_fnv1a_hash(bytes: *const u8, n: u64) -> u64;

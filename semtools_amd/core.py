@@ -593,6 +593,18 @@ class Corpus:
                                               C.byref(route)))
         return dist, hits, counts, int(route.value)
 
+    def debug_select_lists(self, queries_ptr, nq, lists_ptr, n_lists, kp, k_out, out_rows_ptr, out_dist_ptr, list_stride=0, out_stride=0,
+                           ws_threshold=None, row_base=0, f32_err=0.0, overflow_ptr=None, out_counts_ptr=None, out_uncertain_ptr=None,
+                           out_status_ptr=None):
+        """Test hook (smt_debug_select_lists): the select stage on constructed block lists [nq][n_lists][kp] of keys (device pointers,
+        asynchronous on the context's stream).  ws_threshold: the score threshold, None = none.  Every row a key names must lie below
+        self.rows."""
+        opt = lambda p: C.c_void_p(int(p)) if p else None
+        L.check(L.lib().smt_debug_select_lists(self._h, opt(queries_ptr), int(nq), opt(lists_ptr), int(list_stride), int(n_lists), int(kp),
+                                               int(k_out), 0 if ws_threshold is None else 1, 0.0 if ws_threshold is None else float(ws_threshold),
+                                               int(row_base), float(f32_err), opt(overflow_ptr), int(out_stride), opt(out_rows_ptr),
+                                               opt(out_dist_ptr), opt(out_counts_ptr), opt(out_uncertain_ptr), opt(out_status_ptr)))
+
     def search(self, queries, top_k=3, max_distance=None, mode=L.MODE_DOCUMENTS, ranges=None, row_base=0,
                out_cap=None):
         """Returns a list (one per query) of (rows uint64[n], dist float64[n]).

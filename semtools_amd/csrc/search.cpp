@@ -1113,4 +1113,42 @@ try {
     return launch_combine_status_on(ctx->stream, words_dev ? &src : nullptr, base_dev, stride_words, n, nq, out_status_dev);
 } catch (...) { return smt::api_catch(); }
 
+// Test hook: launch_select (select.hip) on constructed block lists, on the context's stream, with the f32 rows of `corpus` behind the
+// keys.  No async step, no delivery.  The launcher's own refusals (list count, k', k_out) are what the tests look at.
+int smt_debug_select_lists(smt_corpus *corpus, const float *queries_dev, uint32_t nq, const uint64_t *lists_dev, uint64_t list_stride,
+                           uint32_t n_lists, uint32_t kp, uint32_t k_out, int ws_threshold, float ws_thr_score, uint64_t row_base,
+                           double f32_err, const uint32_t *overflow_dev, uint64_t out_stride, uint64_t *out_rows_dev, double *out_dist_dev,
+                           uint64_t *out_counts_dev, uint64_t *out_uncertain_dev, uint32_t *out_status_dev)
+try {
+    SMT_REQUIRE(corpus != nullptr, "corpus");
+    SMT_REQUIRE(nq == 0 || (queries_dev && lists_dev && out_rows_dev && out_dist_dev), "null argument");
+    SMT_REQUIRE(list_stride == 0 || list_stride >= (uint64_t)n_lists * kp, "the list stride is shorter than a query's lists");
+    SMT_REQUIRE(out_stride == 0 || out_stride >= k_out, "the output stride is shorter than an output list");
+    smt_ctx *ctx = corpus->ctx;
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    if (nq == 0) return SMT_OK;
+    SelectArgs s;
+    s.corpus = corpus->d_rows;
+    s.queries = queries_dev;
+    s.nq = nq;
+    s.lists = const_cast<key_t64 *>(reinterpret_cast<const key_t64 *>(lists_dev));
+    s.n_lists = n_lists;
+    s.kp = kp;
+    s.list_stride = list_stride ? list_stride : (uint64_t)n_lists * kp;
+    s.k_out = k_out;
+    s.ws_threshold = ws_threshold;
+    s.ws_thr_score = ws_thr_score;
+    s.row_base = row_base;
+    s.out_rows = out_rows_dev;
+    s.out_dist = out_dist_dev;
+    s.out_counts = out_counts_dev;
+    s.out_stride = out_stride;
+    s.f32_err = f32_err;
+    s.out_uncertain = out_uncertain_dev;
+    s.out_status = out_status_dev;
+    s.overflow = overflow_dev;
+    return launch_select(ctx, s);
+} catch (...) { return smt::api_catch(); }
+
 }  // extern "C"

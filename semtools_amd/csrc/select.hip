@@ -307,7 +307,10 @@ __device__ __forceinline__ void final_select_body(const FinalParams &p, const ui
         __syncthreads();
         int Sp = 128;
         while (Sp < S) Sp <<= 1;                      // <= SEL_SURV_CAP = SEL_THREADS
-        const int T = SEL_THREADS / Sp;               // 8, 4, 2 or 1 threads per survivor
+        // 8, 4, 2 or 1 threads per survivor.  (T = 1 needs S > 512: behind a pruning bound S <= 481 at k' = 72, the worst case, and
+        // without one -- the few-keys shortcut -- S <= SEL_FEW_KEYS = 512, so no call reaches it today.  It stays for the day either
+        // limit moves: tests/select_ref.py models S, tests/test_gpu_select.py reads it back.)
+        const int T = SEL_THREADS / Sp;
         const int e = (int)threadIdx.x / T, part = (int)threadIdx.x - e * T;
         if (e < S) {
             const key_t64 key = s_surv[e];
@@ -649,6 +652,8 @@ static FinalParams final_params(const smt_ctx *ctx, const SelectArgs &a)
 int launch_select(smt_ctx *ctx, const SelectArgs &a)
 {
     SMT_REQUIRE(a.n_lists >= 1 && a.n_lists <= (uint32_t)SEL_MAX_LISTS, "select stage accepts 1..512 block lists");
+    // the kernel's LDS carve (s_rank has 80 slots, the staged rows (kp + 1) x 1040 B) and its rank loops assume this
+    SMT_REQUIRE(a.k_out >= 1 && a.k_out <= a.kp && a.kp <= 72, "select stage accepts 1 <= k_out <= k' <= 72");
     SMT_REQUIRE(a.async_step == 0 || (a.nq == 1 && ctx->aux_stream && ctx->d_flags), "async select handles one query per launch");
     int rc = select_attrs(ctx);
     if (rc) return rc;
