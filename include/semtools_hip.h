@@ -280,8 +280,10 @@ int smt_wordpiece_tokenize(smt_wordpiece *tok, const char *text, const uint64_t 
  * piece with a byte >= 0x80 other than a leading replacement cannot match and is left out of the table (it still counts for the
  * longest piece).  unk_score: what an unknown character costs (the vocabulary's lowest score - 10); unk_id -1: none.  A line is
  * FLAGGED for a byte >= 0x80, an added token standing in it, an unknown character on its best path while unk_id is -1, or a piece
- * whose raw bytes (its space, dropped bytes and a prepended replacement counted) exceed SMT_UG_MAX_WORD.  Everything is copied. */
+ * whose raw bytes (its space, dropped bytes and a prepended replacement counted) exceed SMT_UG_MAX_WORD -- or, after
+ * smt_unigram_set_long_pieces, the limit set there.  Everything is copied. */
 #define SMT_UG_MAX_WORD 64
+#define SMT_UG_MAX_LONG 2048
 typedef struct smt_unigram smt_unigram;
 typedef struct smt_unigram_params {
     const char *pool;
@@ -313,8 +315,8 @@ int smt_unigram_create(smt_ctx *ctx, const smt_unigram_params *p, smt_unigram **
  *   ALONE     has no meaning here: SMT_E_INVALID
  * ASCII keeps coming from p->byte_map.  An output may not hold more characters than the UTF-8 form of `first` has bytes: a piece's
  * tokens <= its normalised characters <= its raw bytes, so the slot rule of the ASCII form holds.  All pieces enter the table, those
- * with bytes >= 0x80 too; SMT_UG_MAX_WORD stays in raw bytes, with a SPACE character of any length counted as one; the added tokens
- * stay pure ASCII.
+ * with bytes >= 0x80 too; SMT_UG_MAX_WORD (and the limit of smt_unigram_set_long_pieces) stays in raw bytes, with a SPACE character
+ * of any length counted as one; the added tokens stay pure ASCII.
  * A line is FLAGGED for what flags it in the ASCII form other than a byte >= 0x80, and for a FLAG code point, malformed UTF-8 (a lone
  * continuation byte, a sequence cut by the line's looked-at end, an overlong form, a surrogate, a value above U+10FFFF, a byte that
  * leads nothing), or ANY byte >= 0x80 within the looked-at bytes of a line longer than keep_bytes (the host layer cuts such a line by
@@ -326,6 +328,16 @@ int smt_unigram_create_utf8(smt_ctx *ctx, const smt_unigram_params *p, const smt
  * it is.  Any out may be NULL. */
 int smt_unigram_info(const smt_unigram *tok, uint64_t *table_bytes, uint64_t *codepoint_bytes, int *utf8);
 void smt_unigram_destroy(smt_unigram *tok);
+/* 0 (the default) = today's behaviour: a piece over SMT_UG_MAX_WORD raw bytes flags its line.
+ * Otherwise SMT_UG_MAX_WORD < max_raw_bytes <= SMT_UG_MAX_LONG: pieces up to that measure are tokenized on the device by
+ * ug_long_kernel, same ids as the host tokenizer; pieces over it flag the line.  Any other value: SMT_E_INVALID.  Takes effect
+ * from the next scan; both forms of the handle. */
+int smt_unigram_set_long_pieces(smt_unigram *tok, uint32_t max_raw_bytes);
+/* witness for tests and profiles: long pieces the last scan handed to ug_long_kernel and their raw bytes; waits for the stream.
+ * Counted are the pieces the kernel measured to their end within the limit (a piece that runs into a byte or character that flags
+ * its line, or over the limit, is not), each with its measure: its raw bytes, the SPACE character or a prepended replacement counted
+ * as one.  Both 0 after a scan with the switch off.  Either out may be NULL. */
+int smt_unigram_long_stats(smt_unigram *tok, uint64_t *pieces, uint64_t *raw_bytes);
 /* The two passes and the host convenience: the contracts of smt_wordpiece_scan_device / _emit_device / _tokenize, with one
  * difference: a line can hold one token more than looked-at bytes (the prepended replacement), so
  * ids_cap >= min(text_bytes, n_lines * keep_bytes) + n_lines + n_patch_ids for the device form, and the looked-at bytes of all

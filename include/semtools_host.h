@@ -157,8 +157,13 @@ int smt_host_tokenizer_to_device_unigram_utf8(smt_host_tokenizer *tok, smt_ctx *
  * on = 2 (SEMTOOLS_DEVICE_TOKENIZER=2) chooses the UTF-8 form of a WordPiece tokenizer (smt_host_tokenizer_to_device_utf8) or of a
  * Unigram tokenizer (smt_host_tokenizer_to_device_unigram_utf8) where it has one: lines with valid UTF-8 of covered code points stay
  * on the device.  Otherwise 2 chooses what 1 chooses.
+ * smt_host_model_set_device_tokenizer_long (SEMTOOLS_DEVICE_TOKENIZER_LONG=1 at creation): a separate switch, off by default.  With it
+ * on, the route's Unigram handle tokenizes pieces of more than SMT_UG_MAX_WORD and up to SMT_UG_MAX_LONG raw bytes on the device
+ * (smt_unigram_set_long_pieces) instead of flagging their lines: a URL, a hash, text written without spaces.  Same rows and ids;
+ * ignored for WordPiece and while the route is off.
  * smt_host_debug_device_tokenized (test hook): lines of this model tokenized on the device so far. */
 int smt_host_model_set_device_tokenizer(smt_host_model *model, int on);
+int smt_host_model_set_device_tokenizer_long(smt_host_model *model, int on);
 int smt_host_debug_device_tokenized(smt_host_model *model, uint64_t *lines);
 /* Wall-clock phases of this process so far as one JSON object (malloc'd): model_load, read_tokenize_embed_files,
  * embed_query, store_open_corpus_load, change_detection, embed_and_persist_changed_files, scan_select, ... -- what the

@@ -102,6 +102,7 @@ pub const SMT_WP_CP_ALONE: c_int = 2;
 pub const SMT_WP_CP_DROPPED: c_int = 3;
 pub const SMT_WP_CP_FLAG: c_int = 4;
 pub const SMT_UG_MAX_WORD: c_int = 64;
+pub const SMT_UG_MAX_LONG: c_int = 2048;
 pub const SMT_STATUS_PROVED: c_int = 0;
 pub const SMT_STATUS_UNCERTAIN: c_int = 1;
 pub const SMT_STATUS_OVERFLOW: c_int = 2;
@@ -321,6 +322,8 @@ extern "C" {
         utf8: *mut c_int,
     ) -> c_int;
     pub fn smt_unigram_destroy(tok: *mut SmtUnigram);
+    pub fn smt_unigram_set_long_pieces(tok: *mut SmtUnigram, max_raw_bytes: u32) -> c_int;
+    pub fn smt_unigram_long_stats(tok: *mut SmtUnigram, pieces: *mut u64, raw_bytes: *mut u64) -> c_int;
     pub fn smt_unigram_scan_device(
         tok: *mut SmtUnigram,
         text_dev: *const u8,

@@ -477,6 +477,17 @@ class Unigram(_DeviceTokenizer):
         L.check(L.lib().smt_unigram_info(self._h, C.byref(table), C.byref(cps), C.byref(utf8)))
         return int(table.value), int(cps.value), bool(utf8.value)
 
+    def set_long_pieces(self, n):
+        """0 (the default): a piece over L.UG_MAX_WORD raw bytes flags its line; L.UG_MAX_WORD < n <= L.UG_MAX_LONG: pieces up to n
+        raw bytes are tokenized on the device too, from the next scan on (smt_unigram_set_long_pieces)"""
+        L.check(L.lib().smt_unigram_set_long_pieces(self._h, int(n)))
+
+    def long_stats(self):
+        """(long pieces the last scan's long-piece kernel tokenized, their raw bytes); waits for the stream (smt_unigram_long_stats)"""
+        pieces, raw = C.c_uint64(), C.c_uint64()
+        L.check(L.lib().smt_unigram_long_stats(self._h, C.byref(pieces), C.byref(raw)))
+        return int(pieces.value), int(raw.value)
+
 
 class Corpus:
     """Row-major f32 [rows x 256] matrix resident in HBM (smt_corpus)."""

@@ -61,7 +61,7 @@ double ms_since(std::chrono::steady_clock::time_point t0)
 
 }  // namespace
 
-DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bool utf8)
+DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bool utf8, bool long_pieces)
 {
     int n_ranks = 0;
     if (smt_group_info(group, &n_ranks, nullptr, nullptr, nullptr, nullptr) != SMT_OK || n_ranks != 1) return nullptr;
@@ -83,6 +83,7 @@ DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bo
         const smt_wordpiece_codepoints cp = u8.codepoints();
         smt_unigram *ug = nullptr;
         api_ok(smt_unigram_create_utf8(ctx, &p, &cp, &ug), "smt_unigram_create_utf8");
+        if (long_pieces) api_ok(smt_unigram_set_long_pieces(ug, SMT_UG_MAX_LONG), "smt_unigram_set_long_pieces");
         h = smt::tok_handle(ug);
     } else if (tok.export_wordpiece(x)) {
         const smt_wordpiece_params p = x.params();
@@ -93,6 +94,7 @@ DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bo
         const smt_unigram_params p = u.params();
         smt_unigram *ug = nullptr;
         api_ok(smt_unigram_create(ctx, &p, &ug), "smt_unigram_create");
+        if (long_pieces) api_ok(smt_unigram_set_long_pieces(ug, SMT_UG_MAX_LONG), "smt_unigram_set_long_pieces");
         h = smt::tok_handle(ug);
     } else {
         return nullptr;

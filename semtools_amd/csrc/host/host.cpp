@@ -712,15 +712,16 @@ void StaticModel::tokenize_batch(const std::string_view *sentences, size_t begin
 DeviceTokenRoute *StaticModel::device_route() const
 {
     if (!device_tok_) return nullptr;
-    if (dev_route_tried_ && dev_route_mode_ != device_tok_) {
+    const int mode = device_tok_ + (device_tok_long_ ? 4 : 0);
+    if (dev_route_tried_ && dev_route_mode_ != mode) {
         device_route_destroy(dev_route_);
         dev_route_ = nullptr;
         dev_route_tried_ = false;
     }
     if (!dev_route_tried_) {
         dev_route_tried_ = true;
-        dev_route_mode_ = device_tok_;
-        dev_route_ = device_route_create(group_, *tok_, device_tok_ == 2);
+        dev_route_mode_ = mode;
+        dev_route_ = device_route_create(group_, *tok_, device_tok_ == 2, device_tok_long_);
     }
     return dev_route_;
 }

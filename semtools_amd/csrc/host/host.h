@@ -199,8 +199,9 @@ struct TokenCsr {
 struct DeviceTokenRoute;
 // fills the CSR (ids, offsets [lines.size() + 1]) of the batch's flagged lines, given by their index in the batch
 using DeviceFlaggedFn = std::function<void(const std::vector<uint64_t> &lines, std::vector<uint32_t> &ids, std::vector<uint64_t> &offsets)>;
-// utf8: the UTF-8 form where the tokenizer has one (export_wordpiece_utf8, then export_unigram_utf8), else what utf8 = false makes
-DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bool utf8 = false);
+// utf8: the UTF-8 form where the tokenizer has one (export_wordpiece_utf8, then export_unigram_utf8), else what utf8 = false makes.
+// long_pieces: a Unigram handle tokenizes pieces up to SMT_UG_MAX_LONG raw bytes (smt_unigram_set_long_pieces); ignored for WordPiece
+DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bool utf8 = false, bool long_pieces = false);
 void device_route_destroy(DeviceTokenRoute *r);
 uint64_t device_route_lines(const DeviceTokenRoute *r);   // lines tokenized on the device so far
 // the batch's bytes back to back into pinned slot `which` (0 / 1: one is packed while the other one runs); false: the batch is
@@ -261,6 +262,10 @@ public:
     // and what 1 chooses otherwise; 1 keeps the ASCII forms.
     void set_device_tokenizer(int mode) { device_tok_ = mode < 0 ? 0 : mode > 2 ? 2 : mode; }
     int device_tokenizer() const { return device_tok_; }
+    // a separate switch beside the mode (off by default; SEMTOOLS_DEVICE_TOKENIZER_LONG=1 turns it on at construction): the route's
+    // Unigram handle keeps pieces of up to SMT_UG_MAX_LONG raw bytes on the device instead of flagging their lines.  WordPiece ignores it.
+    void set_device_tokenizer_long(bool on) { device_tok_long_ = on; }
+    bool device_tokenizer_long() const { return device_tok_long_; }
     uint64_t device_tokenized_lines() const { return device_route_lines(dev_route_); }
     // the table as the device holds it (or will, in lazy mode before the full upload: *resident = false): SMT_TABLE_* kind, rows,
     // bytes per replica
@@ -284,9 +289,10 @@ private:
     bool device_batch(int which, size_t n, const std::string_view *sentences, std::optional<size_t> max_length, float *out_host,
                       smt_sharded_corpus *corpus, TokenCsr *sink) const;
     int device_tok_ = [] { const char *e = getenv("SEMTOOLS_DEVICE_TOKENIZER"); return e && e[0] == '1' ? 1 : e && e[0] == '2' ? 2 : 0; }();
+    bool device_tok_long_ = [] { const char *e = getenv("SEMTOOLS_DEVICE_TOKENIZER_LONG"); return e && e[0] == '1'; }();
     mutable DeviceTokenRoute *dev_route_ = nullptr;
     mutable bool dev_route_tried_ = false;
-    mutable int dev_route_mode_ = 0;   // the mode dev_route_ was made for: a change of mode makes it anew
+    mutable int dev_route_mode_ = 0;   // the mode (+ 4 with long pieces) dev_route_ was made for: a change makes it anew
     smt_group *group_;
     std::unique_ptr<Tokenizer> tok_;
     mutable smt_sharded_model *model_ = nullptr;

@@ -301,6 +301,13 @@ int smt_host_model_set_device_tokenizer(smt_host_model *model, int on)
     return SMT_OK;
 }
 
+int smt_host_model_set_device_tokenizer_long(smt_host_model *model, int on)
+{
+    if (!model) { smt::set_error("null argument"); return SMT_E_INVALID; }
+    model->m->set_device_tokenizer_long(on != 0);   // a Unigram route keeps pieces up to SMT_UG_MAX_LONG raw bytes on the device
+    return SMT_OK;
+}
+
 int smt_host_debug_device_tokenized(smt_host_model *model, uint64_t *lines)
 {
     if (!model || !lines) { smt::set_error("null argument"); return SMT_E_INVALID; }

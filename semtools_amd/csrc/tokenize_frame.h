@@ -124,6 +124,8 @@ struct TokScratch {
     uint64_t lines_cap = 0;
     void *d_chunks = nullptr;         // chunk_count u32 [c] | chunk_base u64 [c + 1]
     uint64_t chunks_cap = 0;
+    void *d_long = nullptr;           // a family's work list between two pass-1 kernels (Unigram's long pieces): a 32-byte header | 16-byte records [long_cap]
+    uint64_t long_cap = 0;
 
     uint32_t *raw_count() const { return static_cast<uint32_t *>(d_lines); }
     uint32_t *final_count() const { return raw_count() + lines_cap; }
@@ -133,9 +135,10 @@ struct TokScratch {
     uint64_t *chunk_base() const { return reinterpret_cast<uint64_t *>(chunk_count() + chunks_cap); }
     static uint64_t chunks_of(uint64_t n_slots) { return (n_slots + TOK_EMIT_CHUNK - 1) / TOK_EMIT_CHUNK; }
 };
-// room for n_slots slots (padded to whole chunks) and n_lines lines; waits for the stream before a buffer is replaced
-int tok_scratch_reserve(smt_ctx *ctx, TokScratch &s, uint64_t n_slots, uint64_t n_lines);
-// enqueues what every scan starts with: all slots empty, raw_count zero
+// room for n_slots slots (padded to whole chunks), n_lines lines and n_long work-list records; waits for the stream before a buffer is
+// replaced
+int tok_scratch_reserve(smt_ctx *ctx, TokScratch &s, uint64_t n_slots, uint64_t n_lines, uint64_t n_long = 0);
+// enqueues what every scan starts with: all slots empty, raw_count zero, the work list's header (where there is one) zero
 int tok_scratch_clear(smt_ctx *ctx, TokScratch &s, uint64_t n_slots, uint64_t n_lines);
 void tok_scratch_free(TokScratch &s);
 
@@ -172,6 +175,8 @@ struct TokHandle {
     TokHandle(smt_ctx *c, bool extra, const TokWords &w) : ctx(c), extra_slot(extra), words(w) {}
     virtual ~TokHandle() = default;
     uint64_t slots_of(uint64_t bytes, uint64_t lines) const { return bytes + (extra_slot ? lines : 0); }
+    // the work-list records the family's pass 1 can fill for a text of that many bytes (0: it keeps no list)
+    virtual uint64_t long_records(uint64_t) const { return 0; }
     // the family's pass 1 on a cleared scratch: ids into S.d_ids_tmp, counts into S.raw_count(), flags raised.  Enqueued.
     virtual int pass1(const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev, uint64_t n_lines,
                       uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev) = 0;

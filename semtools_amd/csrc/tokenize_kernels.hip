@@ -231,7 +231,7 @@ int tok_upload_table(const char *family, const std::vector<std::pair<const void 
     return SMT_OK;
 }
 
-int tok_scratch_reserve(smt_ctx *ctx, TokScratch &s, uint64_t n_slots, uint64_t n_lines)
+int tok_scratch_reserve(smt_ctx *ctx, TokScratch &s, uint64_t n_slots, uint64_t n_lines, uint64_t n_long)
 {
     int rc;
     const uint64_t chunks = TokScratch::chunks_of(n_slots);
@@ -250,6 +250,11 @@ int tok_scratch_reserve(smt_ctx *ctx, TokScratch &s, uint64_t n_slots, uint64_t 
         if ((rc = grow(ctx, &s.d_lines, (size_t)n_lines * 8 + ((size_t)n_lines + 1) * 8 + (size_t)n_lines * 8, "tokenizer line sums"))) return rc;
         s.lines_cap = n_lines;
     }
+    if (n_long > s.long_cap) {
+        s.long_cap = 0;
+        if ((rc = grow(ctx, &s.d_long, 32 + (size_t)n_long * 16, "tokenizer work list"))) return rc;
+        s.long_cap = n_long;
+    }
     return SMT_OK;
 }
 
@@ -258,6 +263,7 @@ int tok_scratch_clear(smt_ctx *ctx, TokScratch &s, uint64_t n_slots, uint64_t n_
     const uint64_t chunks = TokScratch::chunks_of(n_slots);
     if (n_lines) SMT_HIP_CHECK(hipMemsetAsync(s.raw_count(), 0, (size_t)n_lines * 4, ctx->stream));
     if (chunks) SMT_HIP_CHECK(hipMemsetAsync(s.d_ids_tmp, 0xFF, (size_t)chunks * EMIT_CHUNK * 4, ctx->stream));
+    if (s.d_long) SMT_HIP_CHECK(hipMemsetAsync(s.d_long, 0, 32, ctx->stream));
     return SMT_OK;
 }
 
@@ -266,6 +272,7 @@ void tok_scratch_free(TokScratch &s)
     if (s.d_ids_tmp) (void)hipFree(s.d_ids_tmp);
     if (s.d_lines) (void)hipFree(s.d_lines);
     if (s.d_chunks) (void)hipFree(s.d_chunks);
+    if (s.d_long) (void)hipFree(s.d_long);
     s = TokScratch();
 }
 
@@ -334,7 +341,7 @@ int tok_scan_device(TokHandle *tok, const uint8_t *text_dev, uint64_t text_bytes
     if (rc) return rc;
     tok->scanned = false;
     const uint64_t n_slots = tok->slots_of(text_bytes, n_lines);
-    if ((rc = tok_scratch_reserve(ctx, tok->S, n_slots, n_lines))) return rc;
+    if ((rc = tok_scratch_reserve(ctx, tok->S, n_slots, n_lines, tok->long_records(text_bytes)))) return rc;
     hipStream_t st = ctx->stream;
     SMT_HIP_CHECK(hipMemsetAsync(n_flagged_dev, 0, sizeof(uint32_t), st));
     if (n_lines) SMT_HIP_CHECK(hipMemsetAsync(flags_dev, 0, n_lines, st));

@@ -20,6 +20,8 @@
 // pieces share a slot and slot order is token order; pass 2 is the shared one (tokenize_frame.h) on these slots.
 //
 // Every loop is bounded: probes by the table's capacity, walks by the longest piece and the piece's end, pieces by SMT_UG_MAX_WORD.
+// A piece whose measure passes SMT_UG_MAX_WORD flags its line -- or, while smt_unigram_set_long_pieces has the switch on, its owner
+// leaves a record in the work list of unigram_table.h and ug_long_kernel (unigram_long_kernels.hip) tokenizes it with a wave.
 //
 // Also here: the create of both forms of the handle.  The UTF-8 form's pass 1 is unigram_utf8_kernels.hip; the table and the handle
 // the two share are in unigram_table.h.
@@ -83,7 +85,7 @@ __global__ void __launch_bounds__(256) ug_slot_begin_kernel(const uint64_t *__re
 __global__ void __launch_bounds__(UG_THREADS) ug_scan_kernel(UgTable T, const uint8_t *__restrict__ text, uint64_t text_bytes,
                                                              const uint64_t *__restrict__ line_begin, const uint32_t *__restrict__ line_len,
                                                              uint64_t n_lines, uint32_t keep_bytes, int drop_unk, uint32_t *__restrict__ ids_tmp,
-                                                             uint32_t *__restrict__ raw_count, uint8_t *__restrict__ flags)
+                                                             uint32_t *__restrict__ raw_count, uint8_t *__restrict__ flags, smt::UgLongList W)
 {
     __shared__ uint8_t s_map[128];
     __shared__ uint64_t s_win[2];
@@ -110,7 +112,7 @@ __global__ void __launch_bounds__(UG_THREADS) ug_scan_kernel(UgTable T, const ui
         if (b >= 0x80) return;                   // (the line is flagged by that byte's lane: nothing of it is used)
         const uint8_t m = s_map[b];
         if (m == ' ') break;
-        if (++measure > SMT_UG_MAX_WORD) { flags[line] = 1; return; }
+        if (++measure > SMT_UG_MAX_WORD) { smt::ug_hand_over(W, p, line, at_space, flags); return; }   // a long piece: flagged, or ug_long_kernel's
         if (m == UG_DROP) continue;
         s_from[end - first] = FROM_UNSET;
         last_q = end;
@@ -211,14 +213,19 @@ int smt::ug_slot_begin_launch(smt_unigram *tok, const uint64_t *line_begin_dev, 
 int smt_unigram::pass1(const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev, uint64_t n_lines,
                        uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev)
 {
+    long_scanned = max_long != 0;
     if (!n_lines) return SMT_OK;
-    const int rc = smt::ug_slot_begin_launch(this, line_begin_dev, n_lines);
+    int rc = smt::ug_slot_begin_launch(this, line_begin_dev, n_lines);
     if (rc) return rc;
     if (!text_bytes) return SMT_OK;
-    if (utf8) return smt::ug_scan_utf8_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev);
+    if (utf8) {
+        if ((rc = smt::ug_scan_utf8_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev))) return rc;
+        return max_long ? smt::ug_long_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev) : SMT_OK;
+    }
     hipLaunchKernelGGL(ug_scan_kernel, dim3((unsigned)((text_bytes + UG_THREADS - 1) / UG_THREADS)), dim3(UG_THREADS), 0, ctx->stream, T, text_dev,
-                       text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, S.d_ids_tmp, S.raw_count(), flags_dev);
+                       text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, S.d_ids_tmp, S.raw_count(), flags_dev, long_list());
     SMT_HIP_CHECK(hipGetLastError());
+    if (max_long) return smt::ug_long_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev);
     return SMT_OK;
 }
 

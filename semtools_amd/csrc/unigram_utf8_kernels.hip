@@ -8,7 +8,7 @@
 //   * the OWNER of a piece is the lane at a SPACE character's lead byte, or at the line's first byte; its walk to the piece's end steps
 //     by characters and stops at a SPACE character or the looked-at end;
 //   * the piece's measure stays in RAW BYTES against SMT_UG_MAX_WORD, with the SPACE character counted as one whatever its length, so
-//     ASCII lines are flagged exactly as by ug_scan_kernel;
+//     ASCII lines are flagged exactly as by ug_scan_kernel (or, with long pieces on, handed to ug_long_kernel exactly as there);
 //   * a lattice position is a normalised CHARACTER.  The node of output character j of the source character at raw byte q is the node
 //     of raw byte q + j: an output has no more characters than its source has bytes, so the nodes of two source characters never
 //     meet.  A SPACE character of s bytes shifts its piece's nodes down by s - 1, into its own bytes, so that the nodes a block's
@@ -86,7 +86,7 @@ __device__ __forceinline__ uint32_t ug_probe_utf8(const UgTable &T, const WpCode
 __global__ void __launch_bounds__(UG_THREADS) ug_scan_utf8_kernel(UgTable T, WpCodepoints U, const uint8_t *__restrict__ text, uint64_t text_bytes,
                                                                   const uint64_t *__restrict__ line_begin, const uint32_t *__restrict__ line_len,
                                                                   uint64_t n_lines, uint32_t keep_bytes, int drop_unk, uint32_t *__restrict__ ids_tmp,
-                                                                  uint32_t *__restrict__ raw_count, uint8_t *__restrict__ flags)
+                                                                  uint32_t *__restrict__ raw_count, uint8_t *__restrict__ flags, smt::UgLongList W)
 {
     __shared__ uint8_t s_bytes[256];   // cls[128] | nrm[128] of the ASCII bytes, from the byte map
     __shared__ uint64_t s_win[2];
@@ -125,7 +125,7 @@ __global__ void __launch_bounds__(UG_THREADS) ug_scan_utf8_kernel(UgTable T, WpC
         if (nc.cls == smt::WP_FLAG) return;      // (the line is flagged by that character's lane: nothing of it is used)
         if (nc.cls == smt::WP_SPACE) break;
         measure += nc.src;
-        if (measure > SMT_UG_MAX_WORD) { flags[line] = 1; return; }
+        if (measure > SMT_UG_MAX_WORD) { smt::ug_hand_over(W, p, line, at_space, flags); return; }   // a long piece: flagged, or ug_long_kernel's
         for (uint32_t j = 0; j < nc.chars; ++j) s_from[end - origin + j] = FROM_UNSET;   // (chars <= src: inside the character's own bytes)
         if (nc.chars) last_key = 2 + (uint32_t)(end - origin) + nc.chars - 1 - rel;
         n_kept += nc.chars;
@@ -232,7 +232,7 @@ int ug_scan_utf8_launch(smt_unigram *tok, const uint8_t *text_dev, uint64_t text
 {
     hipLaunchKernelGGL(ug_scan_utf8_kernel, dim3((unsigned)((text_bytes + UG_THREADS - 1) / UG_THREADS)), dim3(UG_THREADS), 0, tok->ctx->stream,
                        tok->T, tok->U, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, tok->S.d_ids_tmp,
-                       tok->S.raw_count(), flags_dev);
+                       tok->S.raw_count(), flags_dev, tok->long_list());
     SMT_HIP_CHECK(hipGetLastError());
     return SMT_OK;
 }

@@ -73,6 +73,11 @@ class StaticModel:
     def set_device_tokenizer(self, on):
         L.check(L.lib().smt_host_model_set_device_tokenizer(self._h, int(on)))
 
+    def set_device_tokenizer_long(self, on):
+        """a separate switch beside set_device_tokenizer (off unless SEMTOOLS_DEVICE_TOKENIZER_LONG=1): a Unigram route keeps pieces of
+        up to 2048 raw bytes -- a URL, a hash, text written without spaces -- on the device instead of flagging their lines"""
+        L.check(L.lib().smt_host_model_set_device_tokenizer_long(self._h, int(bool(on))))
+
     def device_tokenized_lines(self):
         """lines of this model tokenized on the device so far (test hook)"""
         n = C.c_uint64()

@@ -16,8 +16,13 @@ of the code-point table.  Writes profiles/device_tokenizer_utf8.json.
 --model unigram --utf8 does the same for the UTF-8 form of the Unigram route, on the same four texts, behind NFD -> Lowercase ->
 StripAccents -> Metaspace (no handle_chinese_chars: a spaced Chinese character is a FLAG behind Metaspace), with the covered share of
 every text (device_tokenized_lines_per_call).  Writes profiles/device_tokenizer_unigram_utf8.json.
+--model unigram --long measures the long pieces of the Unigram route (smt_host_model_set_device_tokenizer_long) with the same tokenizer
+and protocol: settings off / 2 / 2 with long pieces, on the CJK text without spaces (a line is one piece), on the ASCII text with a
+100-byte URL-like word in every tenth line, and on the plain ASCII text (no long piece: what the switch costs where it is not
+needed); with pass 1's time, the long-piece kernel's own time and smt_unigram_long_stats of the text's first 20000 lines.  Writes
+profiles/device_tokenizer_unigram_long.json.
 
-    python tools/bench_device_tokenizer.py [--model wordpiece|unigram] [--utf8] [--lines 1000000] [--cpus 16] [--out profiles/device_tokenizer.json]"""
+    python tools/bench_device_tokenizer.py [--model wordpiece|unigram] [--utf8|--long] [--lines 1000000] [--cpus 16] [--out profiles/device_tokenizer.json]"""
 import argparse
 import ctypes as C
 import json
@@ -220,6 +225,87 @@ def run_utf8(ctx, d, corpus, n_lines, repeats=3):
     return entry
 
 
+def run_long(ctx, d, corpus, n_lines, repeats=3):
+    """off / 2 / 2 with long pieces on one text: a model per setting, a discarded warm-up call each, then `repeats` rounds that visit
+    the settings in turn; every timed call ends in a device synchronise"""
+    content_b = ("\n".join(corpus) + "\n").encode()
+    query_b = corpus[17].encode()
+    models = {}
+    for name, mode, long_pieces in (("off", 0, False), ("2", 2, False), ("2_long", 2, True)):
+        models[name] = host.StaticModel(ctx, model_dir=d, device_tokenizer=mode)
+        models[name].set_device_tokenizer_long(long_pieces)
+    times = {name: [] for name in models}
+    prof = {name: {"tokenize": [0, 0.0], "tokenize_long": [0, 0.0]} for name in models}
+    first = {}
+
+    def call(m):
+        out = C.c_void_p()
+        L.check(L.lib().smt_host_search_content(m._h, query_b, b"<stdin>", content_b, 0, 3, float("nan"), 0, 0, 0, C.byref(out)))
+        ctx.synchronize()
+        return host._take_text(out).split("\n")[0]
+
+    for m in models.values():
+        call(m)
+    for _ in range(repeats):
+        for name, m in models.items():
+            ctx.prof_reset()
+            t0 = time.perf_counter()
+            first[name] = call(m)
+            times[name].append(time.perf_counter() - t0)
+            for key, acc in prof[name].items():
+                n, ms = ctx.prof_read(key)
+                acc[0] += n
+                acc[1] += ms
+    entry = {"text_bytes": len(content_b)}
+    for name, m in models.items():
+        best = min(times[name])
+        res = {"seconds_best": round(best, 4), "seconds_all": [round(t, 4) for t in times[name]],
+               "spread_percent": round(100.0 * (max(times[name]) - best) / best, 1), "lines_per_s": round(n_lines / best),
+               "device_tokenized_lines_per_call": m.device_tokenized_lines() // (repeats + 1), "first_hit": first[name][:80]}
+        if prof[name]["tokenize"][0]:
+            res["pass1_ms_per_call"] = round(prof[name]["tokenize"][1] / repeats, 3)
+            res["pass1_launches_per_call"] = prof[name]["tokenize"][0] // repeats
+        if prof[name]["tokenize_long"][0]:
+            res["long_kernel_ms_per_call"] = round(prof[name]["tokenize_long"][1] / repeats, 3)
+        entry[name] = res
+        m.close()
+    h = C.c_void_p()      # the witness, on the handle itself: the route keeps its own inside
+    L.check(L.lib().smt_host_tokenizer_load(os.path.join(d, "tokenizer.json").encode(), C.byref(h)))
+    tok = smt.Unigram(ctx, host_tokenizer=h, utf8=True)
+    tok.set_long_pieces(L.UG_MAX_LONG)
+    flags = tok.tokenize([ln.encode() for ln in corpus[:20000]])[2]
+    pieces, raw = tok.long_stats()
+    entry["long_stats_of_first_20000_lines"] = {"long_pieces": pieces, "raw_bytes": raw, "flagged_lines": int(flags.sum())}
+    tok.close()
+    L.lib().smt_host_tokenizer_free(h)
+    entry["same_first_hit"] = len(set(first.values())) == 1
+    for a, b in (("2_long", "2"), ("2_long", "off"), ("2", "off")):
+        entry["%s_over_%s" % (a, b)] = round(entry[a]["lines_per_s"] / entry[b]["lines_per_s"], 3)
+    print("measured:", {name: entry[name]["lines_per_s"] for name in models}, "lines/s", flush=True)
+    return entry
+
+
+def url_like(i):
+    """a word of 100 bytes: scheme, host and a path of syllables chosen by i"""
+    w = "https://" + SYL[i % len(SYL)] + SYL[(i // 7) % len(SYL)] + ".example.org"
+    k = i
+    while len(w) < 100:
+        w += "/" + SYL[k % len(SYL)] + SYL[(k // 3) % len(SYL)] + str(k % 97)
+        k = k * 31 + 7
+    return w[:100]
+
+
+def measure_long(ctx, d, lines, n_lines, result):
+    result["what"] = "host-layer ingest (smt_host_search_content), device tokenizer route off / 2 (UTF-8 form) / 2 with long pieces"
+    result["note"] = ("kernel profiling events are on in all settings; per setting one warm-up call is discarded, then three rounds visit "
+                      "off, 2, 2_long in turn; every timed call ends in a device synchronise; seconds_best is the best of 3, spread_percent "
+                      "(max - best) / best; long_kernel_ms_per_call is ug_long_kernel alone, inside pass1_ms_per_call")
+    result["cjk_no_spaces"] = run_long(ctx, d, [to_cjk(ln) for ln in lines], n_lines)
+    urls = [ln.replace(" ", " " + url_like(i) + " ", 1) if i % 10 == 0 else ln for i, ln in enumerate(lines)]
+    result["every_tenth_line_a_100_byte_url"] = run_long(ctx, d, urls, n_lines)
+    result["ascii_no_long_piece"] = run_long(ctx, d, lines, n_lines)
+
+
 def measure_on_off(ctx, d, corpora, n_lines, result):
     for corpus_name, corpus in corpora:
         content_b = ("\n".join(corpus) + "\n").encode()
@@ -257,12 +343,18 @@ def measure_utf8(ctx, d, lines, n_lines, result, unigram=False):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--utf8", action="store_true")
+    ap.add_argument("--long", action="store_true", help="the long pieces of the Unigram route (with --model unigram)")
     ap.add_argument("--lines", type=int, default=1_000_000)
     ap.add_argument("--cpus", type=int, default=16)
     ap.add_argument("--model", choices=["wordpiece", "unigram"], default="wordpiece")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     unigram = a.model == "unigram"
+    if a.long:
+        if not unigram or a.utf8:
+            ap.error("--long goes with --model unigram, without --utf8")
+        a.utf8 = True                                # the vocabulary, the texts and the tokenizer of the UTF-8 profile
+        a.out = a.out or os.path.join(ROOT, "profiles", "device_tokenizer_unigram_long.json")
     if a.out is None:
         name = ("device_tokenizer_unigram_utf8.json" if unigram else "device_tokenizer_utf8.json") if a.utf8 else \
             "device_tokenizer_unigram.json" if unigram else "device_tokenizer.json"
@@ -302,7 +394,9 @@ def main():
             W.write_tokenizer(os.path.join(d, "tokenizer.json"), 7, vocab=vocab)
         with open(os.path.join(d, "config.json"), "w") as f:
             json.dump({"normalize": True, "unk_token": "<unk>" if unigram else "[UNK]"}, f)
-        if a.utf8:
+        if a.long:
+            measure_long(ctx, d, lines, a.lines, result)
+        elif a.utf8:
             measure_utf8(ctx, d, lines, a.lines, result, unigram)
         else:
             flagged = [ln.replace(" ", " café ", 1) if i % 10 == 0 else ln for i, ln in enumerate(lines)]
