@@ -333,6 +333,15 @@ void smt_unigram_destroy(smt_unigram *tok);
  * ug_long_kernel, same ids as the host tokenizer; pieces over it flag the line.  Any other value: SMT_E_INVALID.  Takes effect
  * from the next scan; both forms of the handle. */
 int smt_unigram_set_long_pieces(smt_unigram *tok, uint32_t max_raw_bytes);
+/* The space rules an XLM-R-style chain puts around Metaspace (unigram_rules_kernels.hip, DESIGN 4.9 "Behind a Precompiled normalizer").
+ * 0, 0 (the default) = today's behaviour, bit for bit, by today's kernels.
+ * collapse_runs 1: a SPACE character whose nearest earlier not-dropped character of the line is a SPACE too is absorbed -- it starts
+ *   no piece and ends none, and counts toward the measure of the piece in front like a dropped byte: "a  b" is R+a, R+b.
+ * drop_trailing 1: a piece that is the replacement alone and ends at the line's looked-at end emits nothing: "a " is R+a.  A line
+ *   whose ONLY piece is such a one (spaces and dropped characters, nothing else) is FLAGGED.
+ * LONG PIECES: while a rule is on, a piece over SMT_UG_MAX_WORD raw bytes flags its line whatever smt_unigram_set_long_pieces set,
+ *   and smt_unigram_long_stats answers 0, 0.  Other values: SMT_E_INVALID.  Takes effect from the next scan; both forms. */
+int smt_unigram_set_space_rules(smt_unigram *tok, int collapse_runs, int drop_trailing);
 /* witness for tests and profiles: long pieces the last scan handed to ug_long_kernel and their raw bytes; waits for the stream.
  * Counted are the pieces the kernel measured to their end within the limit (a piece that runs into a byte or character that flags
  * its line, or over the limit, is not), each with its measure: its raw bytes, the SPACE character or a prepended replacement counted

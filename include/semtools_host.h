@@ -142,12 +142,22 @@ int smt_host_tokenizer_to_device_utf8(smt_host_tokenizer *tok, smt_ctx *ctx, smt
  * is Unigram behind exactly one Metaspace (split, a replacement character >= U+0080) and its normalizer, if any, is built only of
  * Lowercase / NFD / StripAccents / BertNormalizer (each acts on an ASCII character without context). */
 int smt_host_tokenizer_to_device_unigram(smt_host_tokenizer *tok, smt_ctx *ctx, smt_unigram **out);
+/* An XLM-R-style file has the form too, in both shapes in circulation: a Precompiled normalizer (the table states what the character
+ * map makes of each character on its own), then Strip(right) and / or Replace(Regex " {2,}") by a space or by the replacement, in front of
+ * Metaspace(always) with or without a WhitespaceSplit.  What those add is given to the handle as its space rules
+ * (smt_unigram_set_space_rules), which this call reads off the file without a device: the Replace and WhitespaceSplit collapse runs,
+ * WhitespaceSplit and Strip drop the trailing replacement; 0, 0 for every other tokenizer with the form.  A line with CR LF is
+ * flagged behind a Precompiled normalizer.  SMT_E_UNSUPPORTED as above.  Either out may be NULL. */
+int smt_host_tokenizer_unigram_space_rules(smt_host_tokenizer *tok, int *collapse_runs, int *drop_trailing);
 /* ... and its UTF-8 form (smt_unigram_create_utf8): the same vocabulary, and what every code point U+0080 .. U+10FFFF becomes under the
  * tokenizer's own normalizer, as ranges: SPACE when it becomes exactly ' ' (or is the replacement character, left alone), DROPPED
  * when nothing is left, ORDINARY when no output is ' ' or the replacement.  A code point is FLAG when ' ' or the replacement stands
  * beside other output (a Chinese character under handle_chinese_chars), when the chain holds NFD and an output keeps a character of
  * non-zero canonical combining class, or when the output holds more characters than the code point has bytes.  SMT_E_UNSUPPORTED on
- * the terms of smt_host_tokenizer_to_device_unigram, and when an added token matched on the raw text holds a non-ASCII byte. */
+ * the terms of smt_host_tokenizer_to_device_unigram, and when an added token matched on the raw text holds a non-ASCII byte.
+ * Behind a Precompiled normalizer, which looks up whole grapheme clusters, FLAG is also every code point that can join a neighbour
+ * into one cluster (Extend, ZWJ, SpacingMark, Prepend, conjoining jamo, Regional_Indicator) and every code point of category C* the
+ * map leaves alone; under a space rule also the replacement's own code point, and under drop_trailing white space that does not end as ' '. */
 int smt_host_tokenizer_to_device_unigram_utf8(smt_host_tokenizer *tok, smt_ctx *ctx, smt_unigram **out);
 /* The device tokenizer route of a model.  OFF by default; the environment variable SEMTOOLS_DEVICE_TOKENIZER=1 turns
  * it on when the model is created.  With it on, a batch of lines is packed, uploaded and tokenized on the GPU when the model's

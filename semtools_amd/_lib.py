@@ -50,7 +50,7 @@ EXPORTS = [
     "smt_debug_merge_sources", "smt_debug_merge_packed_strided", "smt_debug_combine_status", "smt_debug_select_lists",
     "smt_wordpiece_create", "smt_wordpiece_create_utf8", "smt_wordpiece_info", "smt_wordpiece_destroy", "smt_wordpiece_scan_device", "smt_wordpiece_emit_device", "smt_wordpiece_tokenize",
     "smt_unigram_create", "smt_unigram_create_utf8", "smt_unigram_info", "smt_unigram_destroy", "smt_unigram_scan_device", "smt_unigram_emit_device", "smt_unigram_tokenize",
-    "smt_unigram_set_long_pieces", "smt_unigram_long_stats",
+    "smt_unigram_set_long_pieces", "smt_unigram_long_stats", "smt_unigram_set_space_rules",
 ]
 WP_NORMALIZER, WP_CLEAN_TEXT, WP_LOWERCASE = 1, 2, 4
 WP_CP_ORDINARY, WP_CP_SPACE, WP_CP_ALONE, WP_CP_DROPPED, WP_CP_FLAG = 0, 1, 2, 3, 4
@@ -112,7 +112,7 @@ HOST_EXPORTS = [
     "smt_host_split_lines", "smt_host_to_lowercase",
     "smt_host_group_from_spec", "smt_host_model_create_group", "smt_host_model_from_dir_group",
     "smt_host_workspace_use_group", "smt_host_workspace_status_group", "smt_host_workspace_prune_group",
-    "smt_host_model_table_info", "smt_host_model_token_info", "smt_host_tokenizer_to_device", "smt_host_tokenizer_to_device_unigram", "smt_host_tokenizer_to_device_utf8", "smt_host_tokenizer_to_device_unigram_utf8",
+    "smt_host_model_table_info", "smt_host_model_token_info", "smt_host_tokenizer_to_device", "smt_host_tokenizer_to_device_unigram", "smt_host_tokenizer_to_device_utf8", "smt_host_tokenizer_to_device_unigram_utf8", "smt_host_tokenizer_unigram_space_rules",
     "smt_host_model_set_device_tokenizer", "smt_host_debug_device_tokenized", "smt_host_model_set_device_tokenizer_long",
 ]
 TOKENIZE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
@@ -229,6 +229,7 @@ def lib():
     L.smt_unigram_emit_device.argtypes = [vp, u64, vp, vp, vp, u64, u64, vp, u64, vp]
     L.smt_unigram_tokenize.argtypes = [vp, vp, vp, vp, u64, u32, u32, i32, vp, u64, vp, vp]
     L.smt_unigram_set_long_pieces.argtypes = [vp, u32]
+    L.smt_unigram_set_space_rules.argtypes = [vp, i32, i32]
     L.smt_unigram_long_stats.argtypes = [vp, P(u64), P(u64)]
     L.smt_corpus_create.argtypes = [vp, u32, u64, P(vp)]
     L.smt_corpus_from_device.argtypes = [vp, vp, u64, u32, P(vp)]
@@ -404,6 +405,7 @@ def lib():
     L.smt_host_tokenizer_to_device_unigram.argtypes = [vp, vp, P(vp)]
     L.smt_host_tokenizer_to_device_utf8.argtypes = [vp, vp, P(vp)]
     L.smt_host_tokenizer_to_device_unigram_utf8.argtypes = [vp, vp, P(vp)]
+    L.smt_host_tokenizer_unigram_space_rules.argtypes = [vp, P(i32), P(i32)]
     L.smt_host_model_set_device_tokenizer.argtypes = [vp, i32]
     L.smt_host_model_set_device_tokenizer_long.argtypes = [vp, i32]
     L.smt_host_debug_device_tokenized.argtypes = [vp, P(u64)]

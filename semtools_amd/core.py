@@ -482,6 +482,11 @@ class Unigram(_DeviceTokenizer):
         raw bytes are tokenized on the device too, from the next scan on (smt_unigram_set_long_pieces)"""
         L.check(L.lib().smt_unigram_set_long_pieces(self._h, int(n)))
 
+    def set_space_rules(self, collapse_runs, drop_trailing):
+        """the space rules of an XLM-R-style chain, from the next scan on (smt_unigram_set_space_rules): collapse_runs -- a space behind
+        a space starts no piece; drop_trailing -- the replacement alone at a line's end emits nothing.  False, False: the default"""
+        L.check(L.lib().smt_unigram_set_space_rules(self._h, int(bool(collapse_runs)), int(bool(drop_trailing))))
+
     def long_stats(self):
         """(long pieces the last scan's long-piece kernel tokenized, their raw bytes); waits for the stream (smt_unigram_long_stats)"""
         pieces, raw = C.c_uint64(), C.c_uint64()

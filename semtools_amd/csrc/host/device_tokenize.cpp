@@ -83,6 +83,7 @@ DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bo
         const smt_wordpiece_codepoints cp = u8.codepoints();
         smt_unigram *ug = nullptr;
         api_ok(smt_unigram_create_utf8(ctx, &p, &cp, &ug), "smt_unigram_create_utf8");
+        api_ok(smt_unigram_set_space_rules(ug, (int)u8.base.collapse_runs, (int)u8.base.drop_trailing), "smt_unigram_set_space_rules");
         if (long_pieces) api_ok(smt_unigram_set_long_pieces(ug, SMT_UG_MAX_LONG), "smt_unigram_set_long_pieces");
         h = smt::tok_handle(ug);
     } else if (tok.export_wordpiece(x)) {
@@ -94,6 +95,7 @@ DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bo
         const smt_unigram_params p = u.params();
         smt_unigram *ug = nullptr;
         api_ok(smt_unigram_create(ctx, &p, &ug), "smt_unigram_create");
+        api_ok(smt_unigram_set_space_rules(ug, (int)u.collapse_runs, (int)u.drop_trailing), "smt_unigram_set_space_rules");
         if (long_pieces) api_ok(smt_unigram_set_long_pieces(ug, SMT_UG_MAX_LONG), "smt_unigram_set_long_pieces");
         h = smt::tok_handle(ug);
     } else {

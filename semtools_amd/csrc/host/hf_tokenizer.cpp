@@ -5,7 +5,8 @@
 // `tokenizers` crate and calls encode_batch_fast(.., add_special_tokens = false) (call sites src/search/mod.rs:69,
 // src/cmds/search.rs:123-128,136,154).  That crate's algorithm is restated here for the component types model2vec
 // models are built from -- anything else fails loudly at load time:
-//   normalizers     BertNormalizer, Lowercase, NFD, StripAccents, Strip, Replace (string pattern), Sequence
+//   normalizers     BertNormalizer, Lowercase, NFD, StripAccents, Strip, Replace (a string, or the regex of one literal character
+//                   repeated: "c{n,}" or "c+"), Precompiled (precompiled.h), Sequence
 //   pre_tokenizers  BertPreTokenizer, Whitespace, WhitespaceSplit, Punctuation, Metaspace, Sequence
 //   models          WordPiece (greedy longest match), Unigram (Viterbi, fused unknowns)
 //   added_tokens    matched on the raw text (special / normalized = false) before everything else
@@ -19,6 +20,7 @@
 #include "host.h"
 #include "flat_vocab.h"
 #include "json.h"
+#include "precompiled.h"
 #include "unicode_lower.h"
 
 namespace semtools {
@@ -161,10 +163,12 @@ void nfd(const U32 &in, U32 &out)
 
 // ------------------------------------------------------------------ components
 struct Normalizer {
-    enum Kind { Bert, Lower, Nfd, StripAcc, Strip, Replace, Seq } kind = Seq;
+    enum Kind { Bert, Lower, Nfd, StripAcc, Strip, Replace, ReplaceRun, Precompiled, Seq } kind = Seq;
     bool clean_text = true, chinese = true, strip_accents = true, lowercase = true;  // Bert
     bool strip_left = true, strip_right = true;                                        // Strip
     U32 pattern, content;                                                              // Replace
+    uint32_t run_char = 0, run_min = 1;                                                // ReplaceRun: run_min or more run_char -> content
+    std::shared_ptr<const PrecompiledMap> charsmap;                                    // Precompiled
     std::vector<Normalizer> children;
 };
 struct PreTokenizer {
@@ -188,6 +192,27 @@ bool flag(const json::Value &v, const char *k, bool dflt)
     return x && x->kind == json::Value::Bool ? x->b : dflt;
 }
 
+// the one regex form read: ONE literal character followed by "{n,}" or "+" (XLM-R-style files collapse runs of spaces with " {2,}")
+void parse_run_regex(const std::string &regex, Normalizer &n)
+{
+    const U32 r = decode(regex);
+    static const U32 meta = U"\\.^$*+?()[]{}|";
+    bool ok = !r.empty() && meta.find(r[0]) == U32::npos && r[0] != 0xFFFD;
+    uint64_t least = 1;
+    if (ok && r.size() == 2) ok = r[1] == '+';
+    else if (ok) {
+        ok = r.size() >= 5 && r[1] == '{' && r[r.size() - 2] == ',' && r.back() == '}';
+        least = 0;
+        for (size_t i = 2; ok && i + 2 < r.size(); ++i) { ok = r[i] >= '0' && r[i] <= '9' && least < 100000; least = least * 10 + (r[i] - '0'); }
+        ok = ok && least >= 1;
+    }
+    if (!ok) throw Error("tokenizer.json: Replace normalizer with the Regex pattern '" + regex + "' is not supported by the native tokenizer "
+                         "(supported: one literal character followed by {n,} or +)");
+    n.kind = Normalizer::ReplaceRun;
+    n.run_char = r[0];
+    n.run_min = (uint32_t)least;
+}
+
 Normalizer parse_normalizer(const json::Value &v)
 {
     Normalizer n;
@@ -209,16 +234,18 @@ Normalizer parse_normalizer(const json::Value &v)
     } else if (type == "Replace") {
         n.kind = Normalizer::Replace;
         const json::Value &p = need(v, "pattern");
-        const json::Value *str = p.get("String");
-        if (!str) throw Error("tokenizer.json: Replace normalizer with a Regex pattern is not supported by the native tokenizer");
-        n.pattern = decode(str->s);
         n.content = decode(need(v, "content").s);
+        if (const json::Value *str = p.get("String")) n.pattern = decode(str->s);
+        else parse_run_regex(need(p, "Regex").s, n);
+    } else if (type == "Precompiled") {
+        n.kind = Normalizer::Precompiled;
+        n.charsmap = std::make_shared<const PrecompiledMap>(base64_decode(need(v, "precompiled_charsmap").s));
     } else if (type == "Sequence") {
         n.kind = Normalizer::Seq;
         for (auto &c : need(v, "normalizers").arr) n.children.push_back(parse_normalizer(c));
     } else {
         throw Error("tokenizer.json: normalizer type '" + type + "' is not supported by the native tokenizer "
-                    "(supported: BertNormalizer, Lowercase, NFD, StripAccents, Strip, Replace, Sequence)");
+                    "(supported: BertNormalizer, Lowercase, NFD, StripAccents, Strip, Replace, Precompiled, Sequence)");
     }
     return n;
 }
@@ -329,6 +356,20 @@ void apply_normalizer(const Normalizer &n, U32 &s)
             s.swap(t);
             return;
         }
+        case Normalizer::ReplaceRun:
+            for (size_t i = 0; i < s.size();) {
+                size_t j = i;
+                while (j < s.size() && s[j] == n.run_char) ++j;
+                if (j - i >= n.run_min) { t += n.content; i = j; }
+                else if (j > i) { t.append(s, i, j - i); i = j; }
+                else t.push_back(s[i++]);
+            }
+            s.swap(t);
+            return;
+        case Normalizer::Precompiled:
+            n.charsmap->normalize(s, t);
+            s.swap(t);
+            return;
         case Normalizer::Bert: {
             if (bert_normalize_below_0300(n, s, t)) { s.swap(t); return; }
             if (n.clean_text) {  // drop NUL / U+FFFD / control characters, every white space becomes ' '
@@ -677,24 +718,25 @@ public:
     }
 
     // Unigram behind exactly one Metaspace (split, a replacement >= U+0080) and a normalizer that acts on an ASCII character without
-    // context: the byte table is what apply_normalizer makes of every single byte
+    // context: the byte table is what apply_normalizer makes of every single byte.  An XLM-R-style chain (device_chain below) has the
+    // form too: its table is what the chain's character part makes of the byte, its Strip / regex Replace / WhitespaceSplit are the
+    // handle's space rules.  Behind a Precompiled normalizer CR LF is one cluster, looked up whole: the pair is listed with the added
+    // tokens, so that a line in which it stands is flagged.
     bool export_unigram(UnigramExport &x) const override
     {
-        if (wordpiece_ || !has_pre_) return false;
-        const PreTokenizer *ms = &pre_;
-        if (ms->kind == PreTokenizer::Seq) {
-            if (ms->children.size() != 1) return false;
-            ms = &ms->children[0];
-        }
-        if (ms->kind != PreTokenizer::Metaspace || !ms->split || ms->replacement < 0x80) return false;
-        if (has_norm_ && !bytewise(norm_)) return false;
+        DeviceChain ch;
+        if (!device_chain(ch)) return false;
+        const PreTokenizer *ms = ch.metaspace;
         for (uint32_t c = 0; c < 128; ++c) {
             U32 s(1, c);
-            if (has_norm_) apply_normalizer(norm_, s);
+            apply_normalizer(ch.chars, s);
             if (s.empty()) x.byte_map[c] = 0xFF;
             else if (s.size() == 1 && s[0] < 0x80) x.byte_map[c] = (uint8_t)s[0];
             else return false;
+            if (ch.drop_trailing && is_white_space(c) && !s.empty() && s[0] != ' ') return false;   // (Strip and WhitespaceSplit cut at any white space)
         }
+        x.collapse_runs = ch.collapse ? 1 : 0;
+        x.drop_trailing = ch.drop_trailing ? 1 : 0;
         vocab_.export_pieces(x.pool, x.piece_off, x.piece_id);
         if (x.piece_id.size() != scores_.size()) return false;
         x.scores = scores_;
@@ -709,6 +751,10 @@ public:
             x.added_pool.append(t.bytes);
             x.added_off.push_back((uint32_t)x.added_pool.size());
         }
+        if (ch.precompiled) {
+            x.added_pool.append("\r\n");
+            x.added_off.push_back((uint32_t)x.added_pool.size());
+        }
         return true;
     }
 
@@ -719,6 +765,12 @@ public:
     // other characters (a Chinese character between its two spaces); under a chain with NFD an output of non-zero combining class
     // (the canonical reordering would depend on the neighbours); more output characters than the source has bytes (the kernel's
     // lattice nodes and token slots are the piece's own bytes).  Equal neighbours merge into ranges.
+    // Behind a Precompiled normalizer (which looks up whole grapheme clusters) FLAG is also every code point that can stand in one
+    // cluster with a neighbour -- Extend, ZWJ, SpacingMark, Prepend, the conjoining jamo L / V / T, Regional_Indicator -- so that every
+    // remaining character is a cluster of its own and the table is exact; and a code point of category C* that the map leaves
+    // alone (unassigned here, private use).  Under a space rule FLAG is also the replacement's own code point (a literal replacement
+    // beside a space is no run of spaces); under drop_trailing (Strip and WhitespaceSplit cut at any white space) every character whose
+    // output holds white space other than ' '.
     bool export_unigram_utf8(UnigramUtf8Export &x) const override
     {
         for (const AddedToken &t : added_) {
@@ -726,8 +778,10 @@ public:
             for (uint32_t c : t.content) if (c >= 0x80) return false;   // (matched on the raw text: the kernel's added tokens are ASCII)
         }
         if (!export_unigram(x.base)) return false;
-        const PreTokenizer *ms = pre_.kind == PreTokenizer::Seq ? &pre_.children[0] : &pre_;   // (export_unigram checked the shape)
-        const uint32_t rep = ms->replacement;
+        DeviceChain ch;
+        device_chain(ch);   // (export_unigram checked the shape)
+        const uint32_t rep = ch.metaspace->replacement;
+        const bool rules = ch.collapse || ch.drop_trailing;
         const bool reorders = has_norm_ && has_nfd(norm_);
         x.first.clear(); x.last.clear(); x.cls.clear(); x.out_pool.clear();
         x.out_off.assign(1, 0);
@@ -735,14 +789,17 @@ public:
         for (uint32_t cp = 0x80; cp <= 0x10FFFF; ++cp) {
             if (cp == 0xD800) cp = 0xE000;
             s.assign(1, cp);
-            if (has_norm_) apply_normalizer(norm_, s);
-            bool splits = false, marks = false;
+            apply_normalizer(ch.chars, s);
+            bool splits = false, marks = false, other_space = false;
             for (uint32_t c : s) {
                 splits = splits || c == ' ' || c == rep;
                 marks = marks || ccc_of(c) != 0;
+                other_space = other_space || (c != ' ' && is_white_space(c));
             }
             const size_t src = cp < 0x800 ? 2 : cp < 0x10000 ? 3 : 4;
             uint8_t k = SMT_WP_CP_FLAG;
+            if (ch.precompiled && (joins_a_cluster(cp) || (is_other(cp) && s.size() == 1 && s[0] == cp))) continue;
+            if ((rules && cp == rep) || (ch.drop_trailing && other_space)) continue;
             if (s.empty()) k = SMT_WP_CP_DROPPED;
             else if (s.size() == 1 && splits) k = SMT_WP_CP_SPACE;
             else if (!splits && s.size() <= src && !(reorders && marks)) k = SMT_WP_CP_ORDINARY;
@@ -763,6 +820,58 @@ public:
     }
 
 private:
+    // What the device forms of a Unigram tokenizer read off the chain.  The normalizer: components that map a character on its own
+    // (`chars`: bytewise ones and Precompiled), then -- XLM-R-style files -- Strip(right only) and/or the regex Replace of two or more
+    // spaces by one space or by the replacement.  The pre-tokenizer: Metaspace, alone or in a Sequence, there behind WhitespaceSplit
+    // at most.  The space rules of smt_unigram_set_space_rules state the rest: the Replace and WhitespaceSplit collapse runs,
+    // WhitespaceSplit and Strip drop the trailing replacement.  The rules are exact only under the scheme `always`, and Strip (which
+    // strips a whole run) only together with a collapse.
+    struct DeviceChain {
+        Normalizer chars;
+        const PreTokenizer *metaspace = nullptr;
+        bool precompiled = false, collapse = false, drop_trailing = false;
+    };
+    bool device_chain(DeviceChain &ch) const
+    {
+        if (wordpiece_ || !has_pre_) return false;
+        const PreTokenizer *ms = &pre_;
+        bool ws_split = false;
+        if (ms->kind == PreTokenizer::Seq) {
+            const size_t n = ms->children.size();
+            if (n == 2 && ms->children[0].kind == PreTokenizer::WsSplit) ws_split = true;
+            else if (n != 1) return false;
+            ms = &ms->children[n - 1];
+        }
+        if (ms->kind != PreTokenizer::Metaspace || !ms->split || ms->replacement < 0x80) return false;
+        ch.metaspace = ms;
+        bool strip = false, replace = false;
+        if (has_norm_) {
+            const std::vector<Normalizer> one(1, norm_);
+            const std::vector<Normalizer> &parts = norm_.kind == Normalizer::Seq ? norm_.children : one;
+            size_t i = 0;
+            for (; i < parts.size() && (parts[i].kind == Normalizer::Precompiled || bytewise(parts[i])); ++i) {
+                ch.precompiled = ch.precompiled || parts[i].kind == Normalizer::Precompiled;
+                ch.chars.children.push_back(parts[i]);
+            }
+            if (i < parts.size() && parts[i].kind == Normalizer::Strip && !parts[i].strip_left && parts[i].strip_right) { strip = true; ++i; }
+            if (i < parts.size() && parts[i].kind == Normalizer::ReplaceRun && parts[i].run_char == ' ' && parts[i].run_min == 2 &&
+                (parts[i].content == U" " || parts[i].content == U32(1, ms->replacement))) { replace = true; ++i; }
+            if (i != parts.size()) return false;
+        }
+        ch.collapse = replace || ws_split;
+        ch.drop_trailing = strip || ws_split;
+        if (strip && !ch.collapse) return false;
+        if ((ch.collapse || ch.drop_trailing) && ms->prepend != 0) return false;
+        return true;
+    }
+    static bool joins_a_cluster(uint32_t cp)
+    {
+        switch (grapheme::gcb(cp)) {
+            case unicode::GCB_EXTEND: case unicode::GCB_ZWJ: case unicode::GCB_SPACINGMARK: case unicode::GCB_PREPEND: case unicode::GCB_L:
+            case unicode::GCB_V: case unicode::GCB_T: case unicode::GCB_REGIONAL_INDICATOR: return true;
+            default: return false;
+        }
+    }
     // NFD in the chain, directly or through BertNormalizer's strip_accents
     static bool has_nfd(const Normalizer &n)
     {

@@ -101,6 +101,7 @@ struct UnigramExport {
     double unk_score = 0.0;
     int64_t unk_id = -1;
     uint32_t prepend = 0;
+    uint32_t collapse_runs = 0, drop_trailing = 0;   // the space rules the handle is to be given (smt_unigram_set_space_rules)
     uint8_t byte_map[128] = {};
     smt_unigram_params params() const   // (points into this object)
     {

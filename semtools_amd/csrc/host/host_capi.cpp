@@ -358,7 +358,8 @@ int smt_host_tokenizer_to_device_unigram(smt_host_tokenizer *tok, smt_ctx *ctx, 
             return SMT_E_UNSUPPORTED;
         }
         const smt_unigram_params p = x.params();
-        return smt_unigram_create(ctx, &p, out);   // (no context: SMT_E_HIP on a machine without a device)
+        const int rc = smt_unigram_create(ctx, &p, out);   // (no context: SMT_E_HIP on a machine without a device)
+        return rc == SMT_OK ? smt_unigram_set_space_rules(*out, (int)x.collapse_runs, (int)x.drop_trailing) : rc;
     } catch (const std::exception &e) { return fail(e); }
 }
 
@@ -375,7 +376,23 @@ int smt_host_tokenizer_to_device_unigram_utf8(smt_host_tokenizer *tok, smt_ctx *
         }
         const smt_unigram_params p = x.base.params();
         const smt_wordpiece_codepoints cp = x.codepoints();
-        return smt_unigram_create_utf8(ctx, &p, &cp, out);   // (no context: SMT_E_HIP on a machine without a device)
+        const int rc = smt_unigram_create_utf8(ctx, &p, &cp, out);   // (no context: SMT_E_HIP on a machine without a device)
+        return rc == SMT_OK ? smt_unigram_set_space_rules(*out, (int)x.base.collapse_runs, (int)x.base.drop_trailing) : rc;
+    } catch (const std::exception &e) { return fail(e); }
+}
+
+int smt_host_tokenizer_unigram_space_rules(smt_host_tokenizer *tok, int *collapse_runs, int *drop_trailing)
+{
+    if (!tok) { smt::set_error("null argument"); return SMT_E_INVALID; }
+    try {
+        UnigramExport x;
+        if (!tok->t->export_unigram(x)) {
+            smt::set_error("this tokenizer has no Unigram device form (pure-ASCII lines of a per-byte normalizer -> Metaspace -> Unigram only)");
+            return SMT_E_UNSUPPORTED;
+        }
+        if (collapse_runs) *collapse_runs = (int)x.collapse_runs;
+        if (drop_trailing) *drop_trailing = (int)x.drop_trailing;
+        return SMT_OK;
     } catch (const std::exception &e) { return fail(e); }
 }
 

@@ -23,6 +23,9 @@
 // A piece whose measure passes SMT_UG_MAX_WORD flags its line -- or, while smt_unigram_set_long_pieces has the switch on, its owner
 // leaves a record in the work list of unigram_table.h and ug_long_kernel (unigram_long_kernels.hip) tokenizes it with a wave.
 //
+// While a space rule of smt_unigram_set_space_rules is on, pass 1 of either form is unigram_rules_kernels.hip's; the vocabulary probe the
+// kernels share is in unigram_probe.h.
+//
 // Also here: the create of both forms of the handle.  The UTF-8 form's pass 1 is unigram_utf8_kernels.hip; the table and the handle
 // the two share are in unigram_table.h.
 #include <algorithm>
@@ -32,6 +35,7 @@
 
 #include "common.h"
 #include "tokenize_frame.h"
+#include "unigram_probe.h"
 #include "unigram_table.h"
 
 namespace {
@@ -44,37 +48,7 @@ using smt::UG_DROP;
 using smt::UG_NODES;
 using smt::UG_THREADS;
 using smt::UgTable;
-
-// the candidate: clen kept bytes from raw position s (dropped bytes skipped), behind R for kind 1, hash h: its entry + 1, or 0
-__device__ __forceinline__ uint32_t ug_probe(const UgTable &T, const uint8_t *__restrict__ text, const uint8_t *map, unsigned long long h,
-                                             uint32_t kind, uint64_t s, uint32_t clen)
-{
-    uint32_t idx = (uint32_t)h & T.mask;
-    const uint32_t tag = (uint32_t)(h >> 32);
-    const uint32_t skip = kind ? T.rlen : 0;
-    for (uint32_t probe = 0; probe <= T.mask; ++probe) {
-        const unsigned long long slot = T.slots[idx];
-        if (slot == 0) return 0;
-        if ((uint32_t)(slot >> 32) == tag) {
-            const uint4 e = T.ent[(uint32_t)slot - 1];
-            if (e.w == kind && e.y == clen + skip) {
-                const uint8_t *piece = T.pool + e.x + skip;
-                uint64_t q = s;
-                uint32_t j = 0;
-                bool same = true;
-                while (j < clen) {   // (the candidate was walked once already: it has clen kept bytes before the piece's end)
-                    const uint8_t m = map[text[q++]];
-                    if (m == UG_DROP) continue;
-                    if (m != piece[j]) { same = false; break; }
-                    ++j;
-                }
-                if (same) return (uint32_t)slot;
-            }
-        }
-        idx = (idx + 1) & T.mask;
-    }
-    return 0;
-}
+using smt::ug_probe;
 
 __global__ void __launch_bounds__(256) ug_slot_begin_kernel(const uint64_t *__restrict__ line_begin, uint64_t n_lines, uint64_t *__restrict__ slot_begin)
 {
@@ -213,11 +187,12 @@ int smt::ug_slot_begin_launch(smt_unigram *tok, const uint64_t *line_begin_dev, 
 int smt_unigram::pass1(const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev, uint64_t n_lines,
                        uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev)
 {
-    long_scanned = max_long != 0;
+    long_scanned = max_long != 0 && !rules;
     if (!n_lines) return SMT_OK;
     int rc = smt::ug_slot_begin_launch(this, line_begin_dev, n_lines);
     if (rc) return rc;
     if (!text_bytes) return SMT_OK;
+    if (rules) return smt::ug_scan_rules_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev);
     if (utf8) {
         if ((rc = smt::ug_scan_utf8_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev))) return rc;
         return max_long ? smt::ug_long_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev) : SMT_OK;

@@ -14,6 +14,7 @@ constexpr unsigned UG_NODES = UG_THREADS + SMT_UG_MAX_WORD;
 constexpr uint8_t UG_DROP = 0xFF;                          // byte_map: the byte is dropped
 constexpr uint32_t KEY_START = 0, KEY_R = 1;               // a node's start: the piece's start, the node behind R, or 2 + (node - owner's node)
 constexpr uint16_t FROM_UNSET = 0xFFFF, FROM_UNK = 0x8000;
+constexpr uint32_t UG_RULE_COLLAPSE = 1, UG_RULE_DROP_TRAILING = 2;   // smt_unigram_set_space_rules (unigram_rules_kernels.hip)
 
 // ---- long pieces (unigram_long_kernels.hip): with the switch on, the owner of a piece whose measure passes SMT_UG_MAX_WORD appends one
 // record to the work list in the handle's scratch instead of flagging its line, and ug_long_kernel tokenizes the piece with a wave.
@@ -60,6 +61,7 @@ struct smt_unigram : smt::TokHandle {   // every line has one slot more than byt
     bool utf8 = false;
     uint64_t table_bytes = 0, codepoint_bytes = 0;   // of d_table: all of it, and its code-point part
     uint32_t max_long = 0;            // smt_unigram_set_long_pieces: 0 = off
+    uint32_t rules = 0;               // smt_unigram_set_space_rules: UG_RULE_* bits; 0 = the kernels without the rules
     bool long_scanned = false;        // the last scan ran with the switch on: the list's header holds its witness
     explicit smt_unigram(smt_ctx *c);   // (unigram_kernels.hip, with the family's wording of the frame's errors)
     int pass1(const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev, uint64_t n_lines,
@@ -78,6 +80,9 @@ int ug_slot_begin_launch(smt_unigram *tok, const uint64_t *line_begin_dev, uint6
 // pass 1 of the UTF-8 form (unigram_utf8_kernels.hip): ug_scan_utf8_kernel on the context's stream
 int ug_scan_utf8_launch(smt_unigram *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev,
                         const uint32_t *line_len_dev, uint64_t n_lines, uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev);
+// pass 1 of either form while a space rule is on (unigram_rules_kernels.hip); a piece over SMT_UG_MAX_WORD flags its line
+int ug_scan_rules_launch(smt_unigram *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev,
+                         const uint32_t *line_len_dev, uint64_t n_lines, uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev);
 // the long pieces of the scan just enqueued (unigram_long_kernels.hip): ug_long_kernel on the context's stream, a fixed grid over the
 // work list; nothing waits for the count
 int ug_long_launch(smt_unigram *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev,

@@ -25,6 +25,7 @@
 // end it may read to.
 #include "common.h"
 #include "tokenize_frame.h"
+#include "unigram_probe.h"
 #include "unigram_table.h"
 #include "utf8_cursor.h"
 
@@ -38,50 +39,13 @@ using smt::UG_DROP;
 using smt::UG_NODES;
 using smt::UG_THREADS;
 using smt::UgTable;
+using smt::UgCursor;
+using smt::ug_probe_utf8;
 using smt::WpChar;
 using smt::WpCodepoints;
 using smt::wp_byte;
 using smt::wp_char_at;
 using smt::wp_next_char;
-
-// the cursor: output character j of the source character at raw byte q starts at byte k of that character's output (c)
-struct UgCursor {
-    uint64_t q;
-    uint32_t k, j;
-    WpChar c;
-};
-
-// the candidate: clen normalised bytes from the cursor `s`, behind R for kind 1, hash h: its entry + 1, or 0
-__device__ __forceinline__ uint32_t ug_probe_utf8(const UgTable &T, const WpCodepoints &U, const uint8_t *__restrict__ text, const uint8_t *cls,
-                                                  const uint8_t *nrm, unsigned long long h, uint32_t kind, const UgCursor &s, uint64_t end,
-                                                  uint32_t clen)
-{
-    uint32_t idx = (uint32_t)h & T.mask;
-    const uint32_t tag = (uint32_t)(h >> 32);
-    const uint32_t skip = kind ? T.rlen : 0;
-    for (uint32_t probe = 0; probe <= T.mask; ++probe) {
-        const unsigned long long slot = T.slots[idx];
-        if (slot == 0) return 0;
-        if ((uint32_t)(slot >> 32) == tag) {
-            const uint4 e = T.ent[(uint32_t)slot - 1];
-            if (e.w == kind && e.y == clen + skip) {
-                const uint8_t *piece = T.pool + e.x + skip;
-                uint64_t q = s.q;
-                uint32_t k = s.k, j = 0;
-                WpChar qc = s.c;
-                bool same = true;
-                while (j < clen) {   // (the candidate was walked once already: it has clen bytes before the piece's end)
-                    if (q >= end || wp_byte(U, text, q, qc, k) != piece[j]) { same = false; break; }
-                    ++j;
-                    if (++k >= qc.n) { q += qc.src; k = 0; wp_next_char(U, cls, nrm, text, q, end, qc); }
-                }
-                if (same) return (uint32_t)slot;
-            }
-        }
-        idx = (idx + 1) & T.mask;
-    }
-    return 0;
-}
 
 __global__ void __launch_bounds__(UG_THREADS) ug_scan_utf8_kernel(UgTable T, WpCodepoints U, const uint8_t *__restrict__ text, uint64_t text_bytes,
                                                                   const uint64_t *__restrict__ line_begin, const uint32_t *__restrict__ line_len,

@@ -21,8 +21,11 @@ and protocol: settings off / 2 / 2 with long pieces, on the CJK text without spa
 100-byte URL-like word in every tenth line, and on the plain ASCII text (no long piece: what the switch costs where it is not
 needed); with pass 1's time, the long-piece kernel's own time and smt_unigram_long_stats of the text's first 20000 lines.  Writes
 profiles/device_tokenizer_unigram_long.json.
+--model unigram --precompiled measures an XLM-R-style chain -- Precompiled (the nmt_nfkc character map of tests/golden) -> Replace(" {2,}")
+-> WhitespaceSplit -> Metaspace, the same synthetic vocabulary -- with the protocol and the four texts of --utf8, and the ASCII text with
+two doubled spaces in every tenth line (the space rules at work).  Writes profiles/device_tokenizer_precompiled.json.
 
-    python tools/bench_device_tokenizer.py [--model wordpiece|unigram] [--utf8|--long] [--lines 1000000] [--cpus 16] [--out profiles/device_tokenizer.json]"""
+    python tools/bench_device_tokenizer.py [--model wordpiece|unigram] [--utf8|--long|--precompiled] [--lines 1000000] [--cpus 16] [--out profiles/device_tokenizer.json]"""
 import argparse
 import ctypes as C
 import json
@@ -45,6 +48,7 @@ import torch  # noqa: E402,F401  (one HIP runtime per process: torch's, loaded f
 import semtools_amd as smt  # noqa: E402
 from semtools_amd import _lib as L  # noqa: E402
 from semtools_amd import host  # noqa: E402
+from tests import precompiled_ref as P  # noqa: E402
 from tests import synth  # noqa: E402
 from tests import unigram_ref as U  # noqa: E402
 from tests import wordpiece_ref as W  # noqa: E402
@@ -320,7 +324,7 @@ def measure_on_off(ctx, d, corpora, n_lines, result):
         result[corpus_name] = entry
 
 
-def measure_utf8(ctx, d, lines, n_lines, result, unigram=False):
+def measure_utf8(ctx, d, lines, n_lines, result, unigram=False, precompiled=False):
     result["what"] = "host-layer ingest (smt_host_search_content), device tokenizer route off / 1 (ASCII form) / 2 (UTF-8 form)"
     result["note"] = ("kernel profiling events are on in all settings; per setting one warm-up call is discarded, then three rounds visit "
                       "off, 1, 2 in turn; every timed call ends in a device synchronise; seconds_best is the best of 3, spread_percent "
@@ -338,12 +342,16 @@ def measure_utf8(ctx, d, lines, n_lines, result, unigram=False):
     result["ascii"] = run_utf8(ctx, d, lines, n_lines)
     result["cyrillic"] = run_utf8(ctx, d, [ln.translate(CYRILLIC) for ln in lines], n_lines)
     result["cjk_no_spaces"] = run_utf8(ctx, d, [to_cjk(ln) for ln in lines], n_lines)
+    if precompiled:
+        doubled = [ln.replace(" ", "  ", 2) if i % 10 == 0 else ln for i, ln in enumerate(lines)]
+        result["ascii_every_tenth_line_doubled_spaces"] = run_utf8(ctx, d, doubled, n_lines)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--utf8", action="store_true")
     ap.add_argument("--long", action="store_true", help="the long pieces of the Unigram route (with --model unigram)")
+    ap.add_argument("--precompiled", action="store_true", help="an XLM-R-style chain in front of the Unigram route (with --model unigram)")
     ap.add_argument("--lines", type=int, default=1_000_000)
     ap.add_argument("--cpus", type=int, default=16)
     ap.add_argument("--model", choices=["wordpiece", "unigram"], default="wordpiece")
@@ -355,6 +363,11 @@ def main():
             ap.error("--long goes with --model unigram, without --utf8")
         a.utf8 = True                                # the vocabulary, the texts and the tokenizer of the UTF-8 profile
         a.out = a.out or os.path.join(ROOT, "profiles", "device_tokenizer_unigram_long.json")
+    if a.precompiled:
+        if not unigram or a.utf8 or a.long:
+            ap.error("--precompiled goes with --model unigram, without --utf8 or --long")
+        a.utf8 = True                                # the vocabulary, the texts and the protocol of the UTF-8 profile
+        a.out = a.out or os.path.join(ROOT, "profiles", "device_tokenizer_precompiled.json")
     if a.out is None:
         name = ("device_tokenizer_unigram_utf8.json" if unigram else "device_tokenizer_utf8.json") if a.utf8 else \
             "device_tokenizer_unigram.json" if unigram else "device_tokenizer.json"
@@ -385,7 +398,11 @@ def main():
         from safetensors.numpy import save_file
 
         save_file({"embeddings": synth.table(len(vocab), seed=2)}, os.path.join(d, "model.safetensors"))
-        if unigram and a.utf8:      # (a chain without handle_chinese_chars: behind Metaspace a spaced Chinese character is a FLAG)
+        if a.precompiled:
+            result["tokenizer"] = "Precompiled(nmt_nfkc) -> Replace(' {2,}') -> WhitespaceSplit -> Metaspace -> Unigram"
+            with open(os.path.join(d, "tokenizer.json"), "w") as f:
+                json.dump(P.tokenizer_json("A_ws", vocab=vocab, added=[]), f)
+        elif unigram and a.utf8:      # (a chain without handle_chinese_chars: behind Metaspace a spaced Chinese character is a FLAG)
             result["tokenizer"] = "NFD -> Lowercase -> StripAccents -> Metaspace -> Unigram"
             U.write_tokenizer(os.path.join(d, "tokenizer.json"), norm="seq", prepend="always", vocab=vocab, added=[])
         elif unigram:
@@ -397,7 +414,7 @@ def main():
         if a.long:
             measure_long(ctx, d, lines, a.lines, result)
         elif a.utf8:
-            measure_utf8(ctx, d, lines, a.lines, result, unigram)
+            measure_utf8(ctx, d, lines, a.lines, result, unigram, a.precompiled)
         else:
             flagged = [ln.replace(" ", " café ", 1) if i % 10 == 0 else ln for i, ln in enumerate(lines)]
             measure_on_off(ctx, d, (("ascii", lines), ("ten_percent_flagged", flagged)), a.lines, result)
