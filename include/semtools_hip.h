@@ -340,12 +340,25 @@ int smt_unigram_set_long_pieces(smt_unigram *tok, uint32_t max_raw_bytes);
  * drop_trailing 1: a piece that is the replacement alone and ends at the line's looked-at end emits nothing: "a " is R+a.  A line
  *   whose ONLY piece is such a one (spaces and dropped characters, nothing else) is FLAGGED.
  * LONG PIECES: while a rule is on, a piece over SMT_UG_MAX_WORD raw bytes flags its line whatever smt_unigram_set_long_pieces set,
- *   and smt_unigram_long_stats answers 0, 0.  Other values: SMT_E_INVALID.  Takes effect from the next scan; both forms. */
+ *   and smt_unigram_long_stats answers 0, 0 -- unless smt_unigram_set_long_rules (below) switched the long pieces on under the rules
+ *   too.  A SPACE character with more than SMT_UG_MAX_WORD raw bytes of dropped characters directly in front of it flags its line
+ *   either way (the look-back bound of the device form).  Other values: SMT_E_INVALID.  Takes effect from the next scan; both forms. */
 int smt_unigram_set_space_rules(smt_unigram *tok, int collapse_runs, int drop_trailing);
+/* Long pieces under the space rules (unigram_long_rules_kernels.hip, DESIGN 4.9 "long pieces under the space rules").  0 (the
+ * default) = today's behaviour.  1: while a space rule is on AND smt_unigram_set_long_pieces set a limit, a piece over
+ * SMT_UG_MAX_WORD raw bytes and within that limit is tokenized on the device by ug_long_rules_kernel instead of flagging its line,
+ * same ids as the host tokenizer, and smt_unigram_long_stats reports what that kernel measured.  The measure is the one of the
+ * rules: the owner's SPACE character counts one, every raw byte behind it up to the piece's end counts too, absorbed space, dropped
+ * or kept.  Under drop_trailing a long piece without a kept character at the line's looked-at end emits nothing, and FLAGS the line
+ * when it is the line's first piece.  With rules 0, 0, or without a limit, the switch is inert: the same kernels, the same bytes.
+ * Any other value: SMT_E_INVALID.  Takes effect from the next scan; both forms of the handle. */
+int smt_unigram_set_long_rules(smt_unigram *tok, int on);
 /* witness for tests and profiles: long pieces the last scan handed to ug_long_kernel and their raw bytes; waits for the stream.
  * Counted are the pieces the kernel measured to their end within the limit (a piece that runs into a byte or character that flags
  * its line, or over the limit, is not), each with its measure: its raw bytes, the SPACE character or a prepended replacement counted
- * as one.  Both 0 after a scan with the switch off.  Either out may be NULL. */
+ * as one.  Under the space rules (smt_unigram_set_long_rules) the measure is theirs, absorbed spaces counted, and a piece that
+ * drop_trailing then leaves without a token -- no kept character, at the line's looked-at end -- is counted too: it was measured to
+ * its end within the limit.  Both 0 after a scan with the switch off.  Either out may be NULL. */
 int smt_unigram_long_stats(smt_unigram *tok, uint64_t *pieces, uint64_t *raw_bytes);
 /* The two passes and the host convenience: the contracts of smt_wordpiece_scan_device / _emit_device / _tokenize, with one
  * difference: a line can hold one token more than looked-at bytes (the prepended replacement), so

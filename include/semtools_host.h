@@ -169,7 +169,8 @@ int smt_host_tokenizer_to_device_unigram_utf8(smt_host_tokenizer *tok, smt_ctx *
  * on the device.  Otherwise 2 chooses what 1 chooses.
  * smt_host_model_set_device_tokenizer_long (SEMTOOLS_DEVICE_TOKENIZER_LONG=1 at creation): a separate switch, off by default.  With it
  * on, the route's Unigram handle tokenizes pieces of more than SMT_UG_MAX_WORD and up to SMT_UG_MAX_LONG raw bytes on the device
- * (smt_unigram_set_long_pieces) instead of flagging their lines: a URL, a hash, text written without spaces.  Same rows and ids;
+ * (smt_unigram_set_long_pieces) instead of flagging their lines: a URL, a hash, text written without spaces.  A handle with space
+ * rules -- an XLM-R-style file behind a Precompiled normalizer -- is covered too (smt_unigram_set_long_rules).  Same rows and ids;
  * ignored for WordPiece and while the route is off.
  * smt_host_debug_device_tokenized (test hook): lines of this model tokenized on the device so far. */
 int smt_host_model_set_device_tokenizer(smt_host_model *model, int on);

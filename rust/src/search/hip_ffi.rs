@@ -324,6 +324,7 @@ extern "C" {
     pub fn smt_unigram_destroy(tok: *mut SmtUnigram);
     pub fn smt_unigram_set_long_pieces(tok: *mut SmtUnigram, max_raw_bytes: u32) -> c_int;
     pub fn smt_unigram_set_space_rules(tok: *mut SmtUnigram, collapse_runs: c_int, drop_trailing: c_int) -> c_int;
+    pub fn smt_unigram_set_long_rules(tok: *mut SmtUnigram, on: c_int) -> c_int;
     pub fn smt_unigram_long_stats(tok: *mut SmtUnigram, pieces: *mut u64, raw_bytes: *mut u64) -> c_int;
     pub fn smt_unigram_scan_device(
         tok: *mut SmtUnigram,

@@ -50,7 +50,7 @@ EXPORTS = [
     "smt_debug_merge_sources", "smt_debug_merge_packed_strided", "smt_debug_combine_status", "smt_debug_select_lists",
     "smt_wordpiece_create", "smt_wordpiece_create_utf8", "smt_wordpiece_info", "smt_wordpiece_destroy", "smt_wordpiece_scan_device", "smt_wordpiece_emit_device", "smt_wordpiece_tokenize",
     "smt_unigram_create", "smt_unigram_create_utf8", "smt_unigram_info", "smt_unigram_destroy", "smt_unigram_scan_device", "smt_unigram_emit_device", "smt_unigram_tokenize",
-    "smt_unigram_set_long_pieces", "smt_unigram_long_stats", "smt_unigram_set_space_rules",
+    "smt_unigram_set_long_pieces", "smt_unigram_long_stats", "smt_unigram_set_space_rules", "smt_unigram_set_long_rules",
 ]
 WP_NORMALIZER, WP_CLEAN_TEXT, WP_LOWERCASE = 1, 2, 4
 WP_CP_ORDINARY, WP_CP_SPACE, WP_CP_ALONE, WP_CP_DROPPED, WP_CP_FLAG = 0, 1, 2, 3, 4
@@ -230,6 +230,7 @@ def lib():
     L.smt_unigram_tokenize.argtypes = [vp, vp, vp, vp, u64, u32, u32, i32, vp, u64, vp, vp]
     L.smt_unigram_set_long_pieces.argtypes = [vp, u32]
     L.smt_unigram_set_space_rules.argtypes = [vp, i32, i32]
+    L.smt_unigram_set_long_rules.argtypes = [vp, i32]
     L.smt_unigram_long_stats.argtypes = [vp, P(u64), P(u64)]
     L.smt_corpus_create.argtypes = [vp, u32, u64, P(vp)]
     L.smt_corpus_from_device.argtypes = [vp, vp, u64, u32, P(vp)]

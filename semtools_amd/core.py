@@ -487,6 +487,11 @@ class Unigram(_DeviceTokenizer):
         a space starts no piece; drop_trailing -- the replacement alone at a line's end emits nothing.  False, False: the default"""
         L.check(L.lib().smt_unigram_set_space_rules(self._h, int(bool(collapse_runs)), int(bool(drop_trailing))))
 
+    def set_long_rules(self, on):
+        """True: while a space rule is on and set_long_pieces set a limit, pieces over L.UG_MAX_WORD raw bytes are tokenized on the
+        device too instead of flagging their lines, from the next scan on (smt_unigram_set_long_rules).  False: the default"""
+        L.check(L.lib().smt_unigram_set_long_rules(self._h, int(bool(on))))
+
     def long_stats(self):
         """(long pieces the last scan's long-piece kernel tokenized, their raw bytes); waits for the stream (smt_unigram_long_stats)"""
         pieces, raw = C.c_uint64(), C.c_uint64()

@@ -84,7 +84,10 @@ DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bo
         smt_unigram *ug = nullptr;
         api_ok(smt_unigram_create_utf8(ctx, &p, &cp, &ug), "smt_unigram_create_utf8");
         api_ok(smt_unigram_set_space_rules(ug, (int)u8.base.collapse_runs, (int)u8.base.drop_trailing), "smt_unigram_set_space_rules");
-        if (long_pieces) api_ok(smt_unigram_set_long_pieces(ug, SMT_UG_MAX_LONG), "smt_unigram_set_long_pieces");
+        if (long_pieces) {
+            api_ok(smt_unigram_set_long_pieces(ug, SMT_UG_MAX_LONG), "smt_unigram_set_long_pieces");
+            api_ok(smt_unigram_set_long_rules(ug, 1), "smt_unigram_set_long_rules");   // (a Precompiled chain has its space rules on)
+        }
         h = smt::tok_handle(ug);
     } else if (tok.export_wordpiece(x)) {
         const smt_wordpiece_params p = x.params();
@@ -96,7 +99,10 @@ DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bo
         smt_unigram *ug = nullptr;
         api_ok(smt_unigram_create(ctx, &p, &ug), "smt_unigram_create");
         api_ok(smt_unigram_set_space_rules(ug, (int)u.collapse_runs, (int)u.drop_trailing), "smt_unigram_set_space_rules");
-        if (long_pieces) api_ok(smt_unigram_set_long_pieces(ug, SMT_UG_MAX_LONG), "smt_unigram_set_long_pieces");
+        if (long_pieces) {
+            api_ok(smt_unigram_set_long_pieces(ug, SMT_UG_MAX_LONG), "smt_unigram_set_long_pieces");
+            api_ok(smt_unigram_set_long_rules(ug, 1), "smt_unigram_set_long_rules");
+        }
         h = smt::tok_handle(ug);
     } else {
         return nullptr;

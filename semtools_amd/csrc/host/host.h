@@ -201,7 +201,8 @@ struct DeviceTokenRoute;
 // fills the CSR (ids, offsets [lines.size() + 1]) of the batch's flagged lines, given by their index in the batch
 using DeviceFlaggedFn = std::function<void(const std::vector<uint64_t> &lines, std::vector<uint32_t> &ids, std::vector<uint64_t> &offsets)>;
 // utf8: the UTF-8 form where the tokenizer has one (export_wordpiece_utf8, then export_unigram_utf8), else what utf8 = false makes.
-// long_pieces: a Unigram handle tokenizes pieces up to SMT_UG_MAX_LONG raw bytes (smt_unigram_set_long_pieces); ignored for WordPiece
+// long_pieces: a Unigram handle tokenizes pieces up to SMT_UG_MAX_LONG raw bytes (smt_unigram_set_long_pieces, and
+// smt_unigram_set_long_rules for a handle with space rules); ignored for WordPiece
 DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bool utf8 = false, bool long_pieces = false);
 void device_route_destroy(DeviceTokenRoute *r);
 uint64_t device_route_lines(const DeviceTokenRoute *r);   // lines tokenized on the device so far

@@ -23,8 +23,9 @@
 // A piece whose measure passes SMT_UG_MAX_WORD flags its line -- or, while smt_unigram_set_long_pieces has the switch on, its owner
 // leaves a record in the work list of unigram_table.h and ug_long_kernel (unigram_long_kernels.hip) tokenizes it with a wave.
 //
-// While a space rule of smt_unigram_set_space_rules is on, pass 1 of either form is unigram_rules_kernels.hip's; the vocabulary probe the
-// kernels share is in unigram_probe.h.
+// While a space rule of smt_unigram_set_space_rules is on, pass 1 of either form is unigram_rules_kernels.hip's -- followed by
+// ug_long_rules_kernel (unigram_long_rules_kernels.hip) while smt_unigram_set_long_rules lets those kernels hand long pieces over; the
+// vocabulary probe the kernels share is in unigram_probe.h.
 //
 // Also here: the create of both forms of the handle.  The UTF-8 form's pass 1 is unigram_utf8_kernels.hip; the table and the handle
 // the two share are in unigram_table.h.
@@ -187,12 +188,15 @@ int smt::ug_slot_begin_launch(smt_unigram *tok, const uint64_t *line_begin_dev, 
 int smt_unigram::pass1(const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev, uint64_t n_lines,
                        uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev)
 {
-    long_scanned = max_long != 0 && !rules;
+    long_scanned = hands_over();
     if (!n_lines) return SMT_OK;
     int rc = smt::ug_slot_begin_launch(this, line_begin_dev, n_lines);
     if (rc) return rc;
     if (!text_bytes) return SMT_OK;
-    if (rules) return smt::ug_scan_rules_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev);
+    if (rules) {
+        if ((rc = smt::ug_scan_rules_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev))) return rc;
+        return hands_over() ? smt::ug_long_rules_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev) : SMT_OK;
+    }
     if (utf8) {
         if ((rc = smt::ug_scan_utf8_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev))) return rc;
         return max_long ? smt::ug_long_launch(this, text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev) : SMT_OK;

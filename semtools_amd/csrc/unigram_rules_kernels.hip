@@ -4,8 +4,8 @@
 // are; what is said there about the lattice, the nodes, the slots and the tie rule holds here word for word.
 //
 //   collapse_runs   a SPACE character whose nearest earlier not-dropped character of the line is a SPACE too is ABSORBED: its lane
-//                   looks back over dropped characters (at most SMT_UG_MAX_WORD raw bytes of them -- more flag the line, which the
-//                   measure of the piece they stand in has done anyway), finds the SPACE and leaves.  It owns no piece and ends none:
+//                   looks back over dropped characters (at most SMT_UG_MAX_WORD raw bytes of them -- more flag the line, as the
+//                   measure of the piece they stand in does without long pieces), finds the SPACE and leaves.  It owns no piece and ends none:
 //                   the owner in front skips the absorbed spaces and the dropped characters between them on its way to the piece's
 //                   first kept character, and counts their raw bytes into the measure like dropped bytes.
 //   drop_trailing   a piece that is the replacement alone and ends at the line's looked-at end emits nothing.  When that piece is the
@@ -14,9 +14,13 @@
 //
 // Bounds: a piece's raw bytes -- the owner's SPACE, the absorbed ones, dropped and kept characters -- stay within SMT_UG_MAX_WORD by the
 // measure, so its nodes stay inside UG_NODES, its keys below 2 + SMT_UG_MAX_WORD, and its tokens (<= 1 + its kept characters) inside
-// the slots of its own raw bytes: absorbed spaces only add raw bytes.  The look-back reads inside [line begin, p).  LONG PIECES: while a
-// rule is on, a piece over SMT_UG_MAX_WORD flags its line even after smt_unigram_set_long_pieces (ug_long_kernel does not know the
-// rules); the host tokenizer takes the line, so the ids are its either way.
+// the slots of its own raw bytes: absorbed spaces only add raw bytes.  The look-back reads inside [line begin, p).  LONG PIECES: a
+// piece over SMT_UG_MAX_WORD flags its line (the host tokenizer takes it, the ids are its either way) -- unless the launch hands the
+// kernels the handle's work list (W.head != nullptr: smt_unigram_set_long_pieces set a limit and smt_unigram_set_long_rules is on).
+// Then the owner leaves a record {position, line, at a SPACE | the line's first piece} where its measure passes the bound, in the
+// absorbed run or in the piece, and ug_long_rules_kernel (unigram_long_rules_kernels.hip) tokenizes the piece with a wave.  The
+// look-back of a SPACE lane stays bounded either way: more than SMT_UG_MAX_WORD raw bytes of dropped characters directly in front of
+// a SPACE flag the line -- a rule of the device form, no longer implied by the measure of the piece they stand in.
 #include "common.h"
 #include "tokenize_frame.h"
 #include "unigram_probe.h"
@@ -47,7 +51,7 @@ enum : uint32_t { FRONT_NONE = 0, FRONT_SPACE = 1, FRONT_KEPT = 2 };   // the ne
 __global__ void __launch_bounds__(UG_THREADS) ug_scan_rules_kernel(UgTable T, uint32_t rules, const uint8_t *__restrict__ text, uint64_t text_bytes,
                                                              const uint64_t *__restrict__ line_begin, const uint32_t *__restrict__ line_len,
                                                              uint64_t n_lines, uint32_t keep_bytes, int drop_unk, uint32_t *__restrict__ ids_tmp,
-                                                             uint32_t *__restrict__ raw_count, uint8_t *__restrict__ flags)
+                                                             uint32_t *__restrict__ raw_count, uint8_t *__restrict__ flags, smt::UgLongList W)
 {
     __shared__ uint8_t s_map[128];
     __shared__ uint64_t s_win[2];
@@ -62,8 +66,8 @@ __global__ void __launch_bounds__(UG_THREADS) ug_scan_rules_kernel(UgTable T, ui
     const uint64_t first = (uint64_t)blockIdx.x * UG_THREADS, p = first + threadIdx.x;
     const bool at_space = s_map[c] == ' ';
     if (!at_space && p != lb) return;            // no piece starts here
-    // ---- the space rules: what stands in front of a SPACE, dropped bytes skipped (at most SMT_UG_MAX_WORD of them: more have passed
-    // the measure of the piece they stand in)
+    // ---- the space rules: what stands in front of a SPACE, dropped bytes skipped (at most SMT_UG_MAX_WORD of them: more flag
+    // the line -- the look-back bound)
     const bool collapse = (rules & smt::UG_RULE_COLLAPSE) != 0;
     bool first_piece = !at_space;                // nothing of the line but dropped bytes stands in front of the owner
     if (at_space) {
@@ -90,7 +94,7 @@ __global__ void __launch_bounds__(UG_THREADS) ug_scan_rules_kernel(UgTable T, ui
             if (b >= 0x80) return;
             const uint8_t m = s_map[b];
             if (m != ' ' && m != UG_DROP) break;
-            if (++measure > SMT_UG_MAX_WORD) { flags[line] = 1; return; }
+            if (++measure > SMT_UG_MAX_WORD) { smt::ug_hand_over(W, p, line, at_space, flags, first_piece); return; }   // flagged, or ug_long_rules_kernel's
         }
     uint64_t end = run, last_q = run;
     for (; end < le; ++end) {
@@ -98,7 +102,7 @@ __global__ void __launch_bounds__(UG_THREADS) ug_scan_rules_kernel(UgTable T, ui
         if (b >= 0x80) return;                   // (the line is flagged by that byte's lane: nothing of it is used)
         const uint8_t m = s_map[b];
         if (m == ' ') break;
-        if (++measure > SMT_UG_MAX_WORD) { flags[line] = 1; return; }   // a long piece: flagged while a rule is on
+        if (++measure > SMT_UG_MAX_WORD) { smt::ug_hand_over(W, p, line, at_space, flags, first_piece); return; }   // a long piece: flagged, or ug_long_rules_kernel's
         if (m == UG_DROP) continue;
         s_from[end - first] = FROM_UNSET;
         last_q = end;
@@ -187,7 +191,7 @@ __global__ void __launch_bounds__(UG_THREADS) ug_scan_rules_kernel(UgTable T, ui
 __global__ void __launch_bounds__(UG_THREADS) ug_scan_utf8_rules_kernel(UgTable T, WpCodepoints U, uint32_t rules, const uint8_t *__restrict__ text, uint64_t text_bytes,
                                                                   const uint64_t *__restrict__ line_begin, const uint32_t *__restrict__ line_len,
                                                                   uint64_t n_lines, uint32_t keep_bytes, int drop_unk, uint32_t *__restrict__ ids_tmp,
-                                                                  uint32_t *__restrict__ raw_count, uint8_t *__restrict__ flags)
+                                                                  uint32_t *__restrict__ raw_count, uint8_t *__restrict__ flags, smt::UgLongList W)
 {
     __shared__ uint8_t s_bytes[256];   // cls[128] | nrm[128] of the ASCII bytes, from the byte map
     __shared__ uint64_t s_win[2];
@@ -210,7 +214,7 @@ __global__ void __launch_bounds__(UG_THREADS) ug_scan_utf8_rules_kernel(UgTable 
     const bool at_space = me.cls == smt::WP_SPACE;
     if (!at_space && p != lb) return;            // no piece starts here
     // ---- the space rules: what stands in front of a SPACE character, dropped characters skipped (at most SMT_UG_MAX_WORD raw bytes of
-    // them: more have passed the measure of the piece they stand in).  A character in front that does not end exactly here is
+    // them: more flag the line -- the look-back bound).  A character in front that does not end exactly here is
     // malformed, and its own lanes flag the line.
     const bool collapse = (rules & smt::UG_RULE_COLLAPSE) != 0;
     bool first_piece = !at_space;                // nothing of the line but dropped characters stands in front of the owner
@@ -246,7 +250,7 @@ __global__ void __launch_bounds__(UG_THREADS) ug_scan_utf8_rules_kernel(UgTable 
             if (nc.cls == smt::WP_FLAG) return;
             if (nc.cls != smt::WP_SPACE && nc.cls != smt::WP_DROPPED) break;
             measure += nc.src;
-            if (measure > SMT_UG_MAX_WORD) { flags[line] = 1; return; }
+            if (measure > SMT_UG_MAX_WORD) { smt::ug_hand_over(W, p, line, at_space, flags, first_piece); return; }   // flagged, or ug_long_rules_kernel's
             run += nc.src;
         }
     uint64_t end = run;
@@ -256,7 +260,7 @@ __global__ void __launch_bounds__(UG_THREADS) ug_scan_utf8_rules_kernel(UgTable 
         if (nc.cls == smt::WP_FLAG) return;      // (the line is flagged by that character's lane: nothing of it is used)
         if (nc.cls == smt::WP_SPACE) break;
         measure += nc.src;
-        if (measure > SMT_UG_MAX_WORD) { flags[line] = 1; return; }   // a long piece: flagged while a rule is on
+        if (measure > SMT_UG_MAX_WORD) { smt::ug_hand_over(W, p, line, at_space, flags, first_piece); return; }   // a long piece: flagged, or ug_long_rules_kernel's
         for (uint32_t j = 0; j < nc.chars; ++j) s_from[end - origin + j] = FROM_UNSET;   // (chars <= src: inside the character's own bytes)
         if (nc.chars) last_key = 2 + (uint32_t)(end - origin) + nc.chars - 1 - rel;
         n_kept += nc.chars;
@@ -366,12 +370,13 @@ int ug_scan_rules_launch(smt_unigram *tok, const uint8_t *text_dev, uint64_t tex
                          const uint32_t *line_len_dev, uint64_t n_lines, uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev)
 {
     const dim3 grid((unsigned)((text_bytes + UG_THREADS - 1) / UG_THREADS));
+    const smt::UgLongList W = tok->long_list();   // head == nullptr unless smt_unigram_set_long_pieces and _set_long_rules are both on
     if (tok->utf8)
         hipLaunchKernelGGL(ug_scan_utf8_rules_kernel, grid, dim3(UG_THREADS), 0, tok->ctx->stream, tok->T, tok->U, tok->rules, text_dev, text_bytes,
-                           line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, tok->S.d_ids_tmp, tok->S.raw_count(), flags_dev);
+                           line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, tok->S.d_ids_tmp, tok->S.raw_count(), flags_dev, W);
     else
         hipLaunchKernelGGL(ug_scan_rules_kernel, grid, dim3(UG_THREADS), 0, tok->ctx->stream, tok->T, tok->rules, text_dev, text_bytes, line_begin_dev,
-                           line_len_dev, n_lines, keep_bytes, drop_unk, tok->S.d_ids_tmp, tok->S.raw_count(), flags_dev);
+                           line_len_dev, n_lines, keep_bytes, drop_unk, tok->S.d_ids_tmp, tok->S.raw_count(), flags_dev, W);
     SMT_HIP_CHECK(hipGetLastError());
     return SMT_OK;
 }

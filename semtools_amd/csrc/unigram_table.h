@@ -20,18 +20,21 @@ constexpr uint32_t UG_RULE_COLLAPSE = 1, UG_RULE_DROP_TRAILING = 2;   // smt_uni
 // record to the work list in the handle's scratch instead of flagging its line, and ug_long_kernel tokenizes the piece with a wave.
 // The list: a header of UG_LONG_HEADER bytes -- the record counter (u32 at byte 0), and the witness of smt_unigram_long_stats: the
 // pieces ug_long_kernel measured to their end within the limit (u64 at byte 8) and the sum of their measures (u64 at byte 16) --,
-// then the records {owner position low, high, line, 1 = the piece starts at a SPACE}.  Pieces are disjoint and a handed-over piece
-// holds at least SMT_UG_MAX_WORD raw bytes, so text_bytes / SMT_UG_MAX_WORD + 1 records always suffice.
+// then the records {owner position low, high, line, bit 0: the piece starts at a SPACE | bit 1: nothing but dropped characters stands
+// in front of the owner (the line's first piece; set by the scan kernels under the space rules only, for drop_trailing)}.  Pieces are
+// disjoint and a handed-over piece holds at least SMT_UG_MAX_WORD raw bytes -- under the space rules too: absorbed spaces are raw
+// bytes of the piece in front --, so text_bytes / SMT_UG_MAX_WORD + 1 records always suffice.
 constexpr uint32_t UG_LONG_HEADER = 32;
 struct UgLongList {
     uint32_t *head;                    // nullptr: the switch is off, and the owner flags the line as ever
     uint4 *rec;
     uint32_t cap;
 };
-__device__ __forceinline__ void ug_hand_over(const UgLongList &W, uint64_t p, uint64_t line, bool at_space, uint8_t *__restrict__ flags)
+__device__ __forceinline__ void ug_hand_over(const UgLongList &W, uint64_t p, uint64_t line, bool at_space, uint8_t *__restrict__ flags,
+                                             bool first_piece = false)
 {
     const uint32_t i = W.head ? atomicAdd(W.head, 1u) : W.cap;
-    if (i < W.cap) W.rec[i] = make_uint4((uint32_t)p, (uint32_t)(p >> 32), (uint32_t)line, at_space ? 1u : 0u);
+    if (i < W.cap) W.rec[i] = make_uint4((uint32_t)p, (uint32_t)(p >> 32), (uint32_t)line, (at_space ? 1u : 0u) | (first_piece ? 2u : 0u));
     else flags[line] = 1;              // (the switch is off; a full list cannot be)
 }
 
@@ -62,14 +65,16 @@ struct smt_unigram : smt::TokHandle {   // every line has one slot more than byt
     uint64_t table_bytes = 0, codepoint_bytes = 0;   // of d_table: all of it, and its code-point part
     uint32_t max_long = 0;            // smt_unigram_set_long_pieces: 0 = off
     uint32_t rules = 0;               // smt_unigram_set_space_rules: UG_RULE_* bits; 0 = the kernels without the rules
+    bool long_rules = false;          // smt_unigram_set_long_rules: under a space rule the scan kernels hand long pieces over too
     bool long_scanned = false;        // the last scan ran with the switch on: the list's header holds its witness
     explicit smt_unigram(smt_ctx *c);   // (unigram_kernels.hip, with the family's wording of the frame's errors)
     int pass1(const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev, uint64_t n_lines,
               uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev) override;
     uint64_t long_records(uint64_t text_bytes) const override { return max_long ? text_bytes / SMT_UG_MAX_WORD + 1 : 0; }
+    bool hands_over() const { return max_long != 0 && (!rules || long_rules); }   // the scan kernels of the next scan leave records
     smt::UgLongList long_list() const
     {
-        if (!max_long || !S.d_long) return {nullptr, nullptr, 0};
+        if (!hands_over() || !S.d_long) return {nullptr, nullptr, 0};
         return {static_cast<uint32_t *>(S.d_long), reinterpret_cast<uint4 *>(static_cast<uint8_t *>(S.d_long) + smt::UG_LONG_HEADER), (uint32_t)S.long_cap};
     }
 };
@@ -80,11 +85,15 @@ int ug_slot_begin_launch(smt_unigram *tok, const uint64_t *line_begin_dev, uint6
 // pass 1 of the UTF-8 form (unigram_utf8_kernels.hip): ug_scan_utf8_kernel on the context's stream
 int ug_scan_utf8_launch(smt_unigram *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev,
                         const uint32_t *line_len_dev, uint64_t n_lines, uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev);
-// pass 1 of either form while a space rule is on (unigram_rules_kernels.hip); a piece over SMT_UG_MAX_WORD flags its line
+// pass 1 of either form while a space rule is on (unigram_rules_kernels.hip); a piece over SMT_UG_MAX_WORD flags its line, or goes
+// to the handle's work list while tok->hands_over()
 int ug_scan_rules_launch(smt_unigram *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev,
                          const uint32_t *line_len_dev, uint64_t n_lines, uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev);
 // the long pieces of the scan just enqueued (unigram_long_kernels.hip): ug_long_kernel on the context's stream, a fixed grid over the
 // work list; nothing waits for the count
 int ug_long_launch(smt_unigram *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev,
                    uint64_t n_lines, uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev);
+// the same behind ug_scan_rules_launch (unigram_long_rules_kernels.hip): ug_long_rules_kernel, which knows the space rules
+int ug_long_rules_launch(smt_unigram *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev,
+                         const uint32_t *line_len_dev, uint64_t n_lines, uint32_t keep_bytes, int drop_unk, uint8_t *flags_dev);
 }  // namespace smt

@@ -24,8 +24,14 @@ profiles/device_tokenizer_unigram_long.json.
 --model unigram --precompiled measures an XLM-R-style chain -- Precompiled (the nmt_nfkc character map of tests/golden) -> Replace(" {2,}")
 -> WhitespaceSplit -> Metaspace, the same synthetic vocabulary -- with the protocol and the four texts of --utf8, and the ASCII text with
 two doubled spaces in every tenth line (the space rules at work).  Writes profiles/device_tokenizer_precompiled.json.
+--model unigram --precompiled --long measures the long pieces under the space rules (smt_unigram_set_long_rules, which the long switch
+of the host layer sets too) on that chain with the protocol of --long: settings off / 2 / 2 with long pieces, on the CJK text without
+spaces, on the ASCII text with a 100-byte URL-like word in every tenth line, and on the ASCII text with two doubled spaces in every
+tenth line (no long piece: what the hand-over branch of the rules kernels and the second launch cost where they are not needed).
+Setting 2 without the switch is what the chain did before the switch covered it.  Writes
+profiles/device_tokenizer_precompiled_long.json.
 
-    python tools/bench_device_tokenizer.py [--model wordpiece|unigram] [--utf8|--long|--precompiled] [--lines 1000000] [--cpus 16] [--out profiles/device_tokenizer.json]"""
+    python tools/bench_device_tokenizer.py [--model wordpiece|unigram] [--utf8|--long|--precompiled [--long]] [--lines 1000000] [--cpus 16] [--out profiles/device_tokenizer.json]"""
 import argparse
 import ctypes as C
 import json
@@ -229,7 +235,7 @@ def run_utf8(ctx, d, corpus, n_lines, repeats=3):
     return entry
 
 
-def run_long(ctx, d, corpus, n_lines, repeats=3):
+def run_long(ctx, d, corpus, n_lines, repeats=3, rules=False):
     """off / 2 / 2 with long pieces on one text: a model per setting, a discarded warm-up call each, then `repeats` rounds that visit
     the settings in turn; every timed call ends in a device synchronise"""
     content_b = ("\n".join(corpus) + "\n").encode()
@@ -277,6 +283,8 @@ def run_long(ctx, d, corpus, n_lines, repeats=3):
     L.check(L.lib().smt_host_tokenizer_load(os.path.join(d, "tokenizer.json").encode(), C.byref(h)))
     tok = smt.Unigram(ctx, host_tokenizer=h, utf8=True)
     tok.set_long_pieces(L.UG_MAX_LONG)
+    if rules:                                        # (the handle of a Precompiled chain has its space rules from the file)
+        tok.set_long_rules(True)
     flags = tok.tokenize([ln.encode() for ln in corpus[:20000]])[2]
     pieces, raw = tok.long_stats()
     entry["long_stats_of_first_20000_lines"] = {"long_pieces": pieces, "raw_bytes": raw, "flagged_lines": int(flags.sum())}
@@ -299,15 +307,19 @@ def url_like(i):
     return w[:100]
 
 
-def measure_long(ctx, d, lines, n_lines, result):
+def measure_long(ctx, d, lines, n_lines, result, precompiled=False):
     result["what"] = "host-layer ingest (smt_host_search_content), device tokenizer route off / 2 (UTF-8 form) / 2 with long pieces"
     result["note"] = ("kernel profiling events are on in all settings; per setting one warm-up call is discarded, then three rounds visit "
                       "off, 2, 2_long in turn; every timed call ends in a device synchronise; seconds_best is the best of 3, spread_percent "
                       "(max - best) / best; long_kernel_ms_per_call is ug_long_kernel alone, inside pass1_ms_per_call")
-    result["cjk_no_spaces"] = run_long(ctx, d, [to_cjk(ln) for ln in lines], n_lines)
+    result["cjk_no_spaces"] = run_long(ctx, d, [to_cjk(ln) for ln in lines], n_lines, rules=precompiled)
     urls = [ln.replace(" ", " " + url_like(i) + " ", 1) if i % 10 == 0 else ln for i, ln in enumerate(lines)]
-    result["every_tenth_line_a_100_byte_url"] = run_long(ctx, d, urls, n_lines)
-    result["ascii_no_long_piece"] = run_long(ctx, d, lines, n_lines)
+    result["every_tenth_line_a_100_byte_url"] = run_long(ctx, d, urls, n_lines, rules=precompiled)
+    if precompiled:
+        doubled = [ln.replace(" ", "  ", 2) if i % 10 == 0 else ln for i, ln in enumerate(lines)]
+        result["ascii_every_tenth_line_doubled_spaces_no_long_piece"] = run_long(ctx, d, doubled, n_lines, rules=True)
+    else:
+        result["ascii_no_long_piece"] = run_long(ctx, d, lines, n_lines)
 
 
 def measure_on_off(ctx, d, corpora, n_lines, result):
@@ -362,10 +374,10 @@ def main():
         if not unigram or a.utf8:
             ap.error("--long goes with --model unigram, without --utf8")
         a.utf8 = True                                # the vocabulary, the texts and the tokenizer of the UTF-8 profile
-        a.out = a.out or os.path.join(ROOT, "profiles", "device_tokenizer_unigram_long.json")
-    if a.precompiled:
-        if not unigram or a.utf8 or a.long:
-            ap.error("--precompiled goes with --model unigram, without --utf8 or --long")
+        a.out = a.out or os.path.join(ROOT, "profiles", "device_tokenizer_precompiled_long.json" if a.precompiled else "device_tokenizer_unigram_long.json")
+    elif a.precompiled:
+        if not unigram or a.utf8:
+            ap.error("--precompiled goes with --model unigram, without --utf8")
         a.utf8 = True                                # the vocabulary, the texts and the protocol of the UTF-8 profile
         a.out = a.out or os.path.join(ROOT, "profiles", "device_tokenizer_precompiled.json")
     if a.out is None:
@@ -412,7 +424,7 @@ def main():
         with open(os.path.join(d, "config.json"), "w") as f:
             json.dump({"normalize": True, "unk_token": "<unk>" if unigram else "[UNK]"}, f)
         if a.long:
-            measure_long(ctx, d, lines, a.lines, result)
+            measure_long(ctx, d, lines, a.lines, result, a.precompiled)
         elif a.utf8:
             measure_utf8(ctx, d, lines, a.lines, result, unigram, a.precompiled)
         else:
