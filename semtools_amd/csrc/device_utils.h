@@ -120,6 +120,41 @@ __device__ __forceinline__ void wave_sum4_multi_head(const float (&in)[T][4], fl
 #pragma unroll
     for (int t = 0; t < T; ++t) v[t] = (upper ? cd[t] : ab[t]) + dpp_f<DPP_XOR2>(upper ? ab[t] : cd[t]);
 }
+// The same heads without their selects (scan_deep_kernel).  What a lane keeps and what it sends at the xor-1 and xor-2 steps is
+// decided by the lane alone, m = lane & 3, not by the tree: so the caller permutes the chunk's four ROWS by lane once
+// (swizzle_rows4: register k holds row k ^ m) and every tree's products come out in the registers the steps want --
+// in[t][k] = the partial of row k ^ m in this lane, p_{k ^ m}[m] -- whatever the number of trees behind the one permutation:
+//   ab = in[0] + xor1(in[1])   lane m: p_m[m] + p_m[m ^ 1]                  (kept + received)
+//   cd = in[2] + xor1(in[3])   lane m: p_{m ^ 2}[m] + p_{m ^ 2}[m ^ 1]
+//   v  = ab + xor2(cd)         lane m: ab + (p_m[m ^ 2] + p_m[m ^ 3])       (kept + received)
+// the additions of wave_sum4_multi_head, same operands, same order: v[t] is bit for bit what that head leaves.
+// (tools/micro/wave_sum4_swizzled.hip is the on-device test.)
+template <int T>
+__device__ __forceinline__ void wave_sum4_swizzled_head(const float (&in)[T][4], float (&v)[T])
+{
+    float ab[T], cd[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) ab[t] = in[t][0] + dpp_f<DPP_XOR1>(in[t][1]);
+#pragma unroll
+    for (int t = 0; t < T; ++t) cd[t] = in[t][2] + dpp_f<DPP_XOR1>(in[t][3]);
+#pragma unroll
+    for (int t = 0; t < T; ++t) v[t] = ab[t] + dpp_f<DPP_XOR2>(cd[t]);
+}
+// swizzle_rows4: c_k <- c_{k ^ (lane & 3)}, in place: odd lanes exchange (c0, c1) and (c2, c3), then the lanes with bit 1 set
+// exchange (c0, c2) and (c1, c3) -- 32 selects on the sixteen row registers, once per chunk, for the six selects per tree that the
+// heads no longer have.  The caller must let the permuted rows END behind their last use (an empty asm that defines the buffer
+// anew): rows that stay live into the next turn of a loop are copied about, and the copies do not fit the deep kernel's 64 VGPRs.
+// (Tried and not kept: the same exchanges as sixteen v_swap_b32 under two exec masks.  Fewer instructions, but a slower pass --
+// profiles/scan_deep_heads.json.)
+__device__ __forceinline__ void swizzle_rows4(f32x4 &c0, f32x4 &c1, f32x4 &c2, f32x4 &c3, int lane)
+{
+    const bool odd = lane & 1, upper = lane & 2;
+    f32x4 t;
+    t = odd ? c1 : c0; c1 = odd ? c0 : c1; c0 = t;
+    t = odd ? c3 : c2; c3 = odd ? c2 : c3; c2 = t;
+    t = upper ? c2 : c0; c2 = upper ? c0 : c2; c0 = t;
+    t = upper ? c3 : c1; c3 = upper ? c1 : c3; c1 = t;
+}
 template <int T>
 __device__ __forceinline__ void wave_sum4_multi_tail(float (&v)[T], float (&out)[T])
 {
@@ -220,6 +255,15 @@ __device__ __forceinline__ float dist_f32(float ab, float b2, float rq, bool q_z
     // the query is the zero vector, so "ab == 0 -> 1" falls out of the formula.
     if (b2 == 0.0f) return q_zero ? 0.0f : 1.0f;
     const float d = 1.0f - ab * rq * __frsqrt_rn(b2);
+    return fmaxf(d, 0.0f);
+}
+
+// dist_f32 for a row that meets several queries (scan_deep_kernel's four phases): rs_b2 = __frsqrt_rn(b2) and b2_zero = (b2 == 0)
+// computed once by the caller, the same expression behind them.
+__device__ __forceinline__ float dist_f32_rs(float ab, float rs_b2, bool b2_zero, float rq, bool q_zero)
+{
+    if (b2_zero) return q_zero ? 0.0f : 1.0f;
+    const float d = 1.0f - ab * rq * rs_b2;
     return fmaxf(d, 0.0f);
 }
 

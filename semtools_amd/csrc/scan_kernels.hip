@@ -1513,7 +1513,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
     // offered to the lists in the order of the ballot's bits: query-major, rows ascending.
 #define SMT_DEEP_TEST_INSERT(h, MINE, ON, AB, D4)                                                                 \
     do {                                                                                                          \
-        const float D4 = dist_f32(AB, b2, (MINE).x, (MINE).y != 0.0f);                                            \
+        const float D4 = dist_f32_rs(AB, rs_b2, b2_zero, (MINE).x, (MINE).y != 0.0f);                             \
         const uint32_t thr_r_mine = __float_as_uint((MINE).w);                                                    \
         const bool cand = ((ON) & valid_mine) & ((D4 < (MINE).z) | ((D4 == (MINE).z) & (r_mine < thr_r_mine)));   \
         uint64_t pending = __ballot(cand) & 0x000F000F000F000Full;                                                \
@@ -1543,7 +1543,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
             parta[0][j] = SMT_ROW_DOT((cq)[j], qva);                                                              \
             parta[1][j] = SMT_ROW_DOT((cq)[j], qvb);                                                              \
         }                                                                                                         \
-        wave_sum4_multi_head<2>(parta, w2, lane);                                                                 \
+        wave_sum4_swizzled_head<2>(parta, w2);                                                                    \
         SMT_OPAQUE(w2[0]); SMT_OPAQUE(w2[1]);                                                                     \
         float v4[4] = {w2[0], w2[1], w2[0], w2[1]};                                                               \
         if (n_h##h > 2) {                                                                                         \
@@ -1554,7 +1554,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
                 partc[0][j] = SMT_ROW_DOT((cq)[j], qvc);                                                          \
                 partc[1][j] = SMT_ROW_DOT((cq)[j], qvd);                                                          \
             }                                                                                                     \
-            wave_sum4_multi_head<2>(partc, x2, lane);                                                             \
+            wave_sum4_swizzled_head<2>(partc, x2);                                                                \
             SMT_OPAQUE(x2[0]); SMT_OPAQUE(x2[1]);                                                                 \
             v4[2] = x2[0]; v4[3] = x2[1];                                                                         \
         }                                                                                                         \
@@ -1565,8 +1565,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
         wave_sum4_group_tail_queries(v4[0], v4[1], v4[2], v4[3]);                                                 \
         SMT_DEEP_TEST_INSERT(h, mine_h, gq < n_h##h, v4[0], d4h);                                                 \
     }
-    // phase 0: scan_wide_kernel's phase A (SMT_REDUCE_GROUP4 of scan_pair_kernel), instruction for instruction up to the distance;
-    // the other three phases behind it
+    // phase 0: scan_wide_kernel's phase A (SMT_REDUCE_GROUP4 of scan_pair_kernel) up to the distance, but for the heads, which
+    // take the rows as SMT_DEEP_STEP has permuted them; the other three phases behind it
 #define SMT_REDUCE_DEEP(cq, rq4, VALID)                                                                           \
     do {                                                                                                          \
         const f32x4 qv0 = s_q[lane];                                                                              \
@@ -1580,7 +1580,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         _Pragma("unroll") for (int j = 0; j < 4; ++j) part[2][j] = SMT_ROW_DOT((cq)[j], qv1);                     \
         float v3[3];                                                                                              \
-        wave_sum4_multi_head<3>(part, v3, lane);                                                                  \
+        wave_sum4_swizzled_head<3>(part, v3);                                                                     \
         SMT_OPAQUE(v3[0]); SMT_OPAQUE(v3[1]); SMT_OPAQUE(v3[2]);                                                  \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         const f32x4 qv2 = s_q[128 + lane], qv3 = s_q[192 + lane];                                                 \
@@ -1592,7 +1592,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
                 part2[0][j] = SMT_ROW_DOT((cq)[j], qv2);                                                          \
                 part2[1][j] = SMT_ROW_DOT((cq)[j], qv3);                                                          \
             }                                                                                                     \
-            wave_sum4_multi_head<2>(part2, v2, lane);                                                             \
+            wave_sum4_swizzled_head<2>(part2, v2);                                                                \
             SMT_OPAQUE(v2[0]); SMT_OPAQUE(v2[1]);                                                                 \
             v5[3] = v2[0]; v5[4] = v2[1];                                                                         \
         }                                                                                                         \
@@ -1602,6 +1602,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
         wave_sum4_rows<5>(v5);                                                                                    \
         wave_sum4_group_tail(v5[0], v5[1], v5[2], v5[3], v5[4]);                                                  \
         const float b2 = v5[0];                                                                                   \
+        const float rs_b2 = __frsqrt_rn(b2);   /* once per chunk, for the four phases (v_rsq runs at quarter rate) */ \
+        const bool b2_zero = b2 == 0.0f;                                                                          \
         SMT_DEEP_TEST_INSERT(0, mine, on_mine, v5[1], d4);                                                        \
         SMT_DEEP_PHASE(cq, 1)                                                                                     \
         SMT_DEEP_PHASE(cq, 2)                                                                                     \
@@ -1609,12 +1611,20 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
     } while (0)
     const bool on_mine = gq < n_on;   // (an absent query has thr = +inf and must never insert)
     // (the two-buffer pipeline of scan_pair_kernel: one chunk in flight per wave, the claims in the same order)
+    // THE ROWS ARE PERMUTED BY LANE once a chunk has landed (device_utils.h swizzle_rows4: register k of lane l holds row
+    // k ^ (l & 3)), in place on the buffer that is reduced, and the seventeen trees' heads run without selects
+    // (wave_sum4_swizzled_head): what a lane keeps and sends in a head depends on the lane alone, so the choice is made once on
+    // the sixteen row registers and not seventeen times on the products.  Every product is the same chain on the same operands
+    // in another register, every addition has its operands in their order; behind the heads nothing knows of the permutation.
 #define SMT_DEEP_STEP(cur, nxt)                                                                                   \
     do {                                                                                                          \
         asm volatile("s_waitcnt vmcnt(0)" : "+v"((cur)[0]), "+v"((cur)[1]), "+v"((cur)[2]), "+v"((cur)[3]) : : "memory"); \
         if (in_corpus(v0n)) issue_rows(v0n, nxt);                                                                 \
         const uint64_t v0nn = chunk_v0(claim());                                                                  \
+        swizzle_rows4((cur)[0], (cur)[1], (cur)[2], (cur)[3], lane);                                              \
         SMT_REDUCE_DEEP(cur, (uint32_t)v0, in_corpus(v0 + (U - 1)) ? 4u : (uint32_t)(p.n_virtual - v0));          \
+        /* (the permuted rows end here: without this they count as live into the next turn and are copied about) */ \
+        asm volatile("" : "=v"((cur)[0]), "=v"((cur)[1]), "=v"((cur)[2]), "=v"((cur)[3]));                        \
         v0 = v0n;                                                                                                 \
         v0n = v0nn;                                                                                               \
     } while (0)
