@@ -236,6 +236,83 @@ __device__ __forceinline__ void wave_sum4_group_tail_queries(float &t0, float &t
                  : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3));
 }
 
+// ONE REGISTER FOR THE 64 (ROW, QUERY) PAIRS OF A CHUNK (scan_deep_kernel).  The group tails above deliver a chunk's sums sixteen at a
+// time, in quad 0 of each 16-lane row; the rotations by 4 and 8 in front of them replicate one value over a row.  Here the QUERIES are
+// permuted by lane as well, where their LDS images are written (once per pass), so that the steps at distance 4 and 8 FOLD four query
+// trees into one register, and the four phases' registers go through one tail.  For lane l, with R = l >> 4 the 16-lane row,
+// i = (l >> 2) & 3 the quad and j = l & 3:
+//   row of the chunk   m(l) = j ^ ((i & 1) ? 3 : 0)   odd quads hold the rows in reverse; register k of the row buffer holds row
+//                      k ^ m(l) (swizzle_rows4_folded).  m(l ^ 1) = m(l) ^ 1 and m(l ^ 2) = m(l) ^ 2 inside a quad, so the heads
+//                      (wave_sum4_swizzled_head) stay what they are: v = the quad's sum of row m(l).
+//   query              slot s (0 .. 3) of phase h holds query 4 h + (s ^ i'), i' = (4 - i) & 3 (wave_sum4_folded_slot)
+//   w0 = v[0] + row_mirror(v[1])   the lane 15 - p of the row is quad 3 - i, and its reversed rows put row m(l) there: same row,
+//   w1 = v[2] + row_mirror(v[3])   and 1 ^ i'(3 - i) = i'(i), 3 ^ i'(3 - i) = 2 ^ i'(i): same query.  q_i + q_{3 - i}.
+//   x  = w0 + row_ror8(w1)         quad i ^ 2, same j, same row; 2 ^ i'(i ^ 2) = i'(i): same query.
+// Quad i then holds (q_i + q_{3-i}) + (q_{i^2} + q_{3-(i^2)}) of row m(l) against query 4 h + i'.  wave_sum4 computes
+// (q_0 + q_3) + (q_2 + q_1) at quad 0, the lanes the kernels read: in every quad the new value is that sum with operands exchanged,
+// and IEEE addition is commutative bit for bit.  The swaps of the tail move lane p of a row to lane p of another, so a lane keeps
+// its (row, query); after the tail of x_0 .. x_3 lane l holds what wave_sum4 leaves for <row m(l), query 4 R + i'>: 64 pairs, each
+// once.  3 adds per four trees where wave_sum4_rows has 8, one tail where the phases had four.
+// (tools/micro/wave_sum4_folded.hip is the on-device test.)
+__device__ __forceinline__ int wave_sum4_folded_row(int lane) { return (lane & 3) ^ ((lane & 4) ? 3 : 0); }
+__device__ __forceinline__ int wave_sum4_folded_query(int lane) { return 4 * (lane >> 4) + ((4 - ((lane >> 2) & 3)) & 3); }   // (of the 16)
+__device__ __forceinline__ int wave_sum4_folded_slot(int n, int lane) { return (n & ~3) | ((n & 3) ^ ((4 - ((lane >> 2) & 3)) & 3)); }   // where lane keeps query n's 16 bytes
+// swizzle_rows4 with the masks of m(l): c_k <- c_{k ^ m(l)}, in place, the same 32 selects (and the same rule for the caller)
+__device__ __forceinline__ void swizzle_rows4_folded(f32x4 &c0, f32x4 &c1, f32x4 &c2, f32x4 &c3, int lane)
+{
+    const int m = wave_sum4_folded_row(lane);
+    const bool odd = m & 1, upper = m & 2;
+    f32x4 t;
+    t = odd ? c1 : c0; c1 = odd ? c0 : c1; c0 = t;
+    t = odd ? c3 : c2; c3 = odd ? c2 : c3; c2 = t;
+    t = upper ? c2 : c0; c2 = upper ? c0 : c2; c0 = t;
+    t = upper ? c3 : c1; c3 = upper ? c1 : c3; c1 = t;
+}
+// the folding row steps: wave_sum4_fold_mirror(v[0], v[1]) = w0, (v[2], v[3]) = w1, wave_sum4_fold_ror8(w0, w1) = x
+__device__ __forceinline__ float wave_sum4_fold_mirror(float keep, float send) { return keep + dpp_f<DPP_MIRROR>(send); }
+__device__ __forceinline__ float wave_sum4_fold_ror8(float keep, float send) { return keep + dpp_f<DPP_ROW_ROR8>(send); }
+// the <c, c> column's row steps: nothing to fold, but the same two distances, so that EVERY lane of the row ends with the canonical
+// (q_0 + q_3) + (q_2 + q_1) of its own row m(l) up to exchanged operands (behind ror4 and ror8 only quad 0 has it)
+__device__ __forceinline__ float wave_sum4_fold_cc_rows(float v)
+{
+    v += dpp_f<DPP_MIRROR>(v);
+    v += dpp_f<DPP_ROW_ROR8>(v);
+    return v;
+}
+// The tail in three parts, so that a caller short of registers folds as the phases come: (x_0, x_1) as soon as phase 1 is done, then
+// (x_2, x_3), then the two results -- the additions of wave_sum4_group_tail_queries, same operands, same order.  The first and the
+// last part take the <c, c> column along (the replicating tail of wave_sum4_group_tail).  t0 holds the result, t1 is used up; a
+// tree that does not exist may be any register.  (Wait states as in wave_sum4_group_tail: two between a VALU write and the swap.)
+__device__ __forceinline__ void wave_sum4_fold_tail16_cc(float &cc, float &t0, float &t1)
+{
+    float w;
+    asm volatile("v_mov_b32 %3, %0\n\t"
+                 "s_nop 0\n\t"
+                 "v_permlane16_swap_b32_e32 %1, %2\n\t"
+                 "v_permlane16_swap_b32_e32 %0, %3\n\t"
+                 "v_add_f32 %1, %1, %2\n\t"
+                 "v_add_f32 %0, %0, %3"
+                 : "+v"(cc), "+v"(t0), "+v"(t1), "=&v"(w));
+}
+__device__ __forceinline__ void wave_sum4_fold_tail16(float &t0, float &t1)
+{
+    asm volatile("s_nop 1\n\t"
+                 "v_permlane16_swap_b32_e32 %0, %1\n\t"
+                 "v_add_f32 %0, %0, %1"
+                 : "+v"(t0), "+v"(t1));
+}
+__device__ __forceinline__ void wave_sum4_fold_tail32_cc(float &cc, float &t0, float &t1)
+{
+    float w;
+    asm volatile("v_mov_b32 %3, %0\n\t"
+                 "s_nop 0\n\t"
+                 "v_permlane32_swap_b32_e32 %1, %2\n\t"
+                 "v_permlane32_swap_b32_e32 %0, %3\n\t"
+                 "v_add_f32 %1, %1, %2\n\t"
+                 "v_add_f32 %0, %0, %3"
+                 : "+v"(cc), "+v"(t0), "+v"(t1), "=&v"(w));
+}
+
 // Integer sum over the 64 lanes, result in every lane.
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 {

@@ -1203,9 +1203,12 @@ static inline size_t wide_smem_bytes(int threads)
 // this kernel says so in its slot (DEEP_FAMILY in kp_blocks) and has a record of its own kind (DeepRecord, an array of its own): a
 // leader takes launches of its own kernel only, and the two older kernels refuse these by their compare.  Marks, the own-record
 // test, the bounded waits, the error flag, the gate and the first rows requested before the decision is known are theirs.
-// A chunk is reduced in FOUR phases over the same sixteen row registers.  Phase 0 is scan_wide_kernel's phase A; phases 1 .. 3 are
-// its phase B, written once (SMT_DEEP_PHASE) and instanced three times, each behind a wave-uniform n_on > 4 h: query 4 h + g in row g of
-// the wave, <c, c> kept in one register -- every query's nominations are bit for bit the one-query loop's (the row-not-quad rule).
+// A chunk is reduced in FOUR phases over the same sixteen row registers, four queries each, phases 1 .. 3 written once
+// (SMT_DEEP_PHASE) and instanced three times, each behind a wave-uniform n_on > 4 h.  The sixteen queries x four rows of a chunk are
+// 64 (row, query) pairs, one per lane: rows AND queries are permuted by lane (device_utils.h, the folded lane map), so that the
+// row steps fold a phase's four trees into one register and the four phases' registers go through ONE tail, and one distance, one
+// compare and one ballot serve the chunk.  Every addition is one of wave_sum4's with its two operands, possibly exchanged -- every
+// query's nominations are bit for bit the one-query loop's.
 // The lists are scan_wide_kernel's shared lists (shared_list.h, kp <= 32), sixteen of them.
 // THE DECISION is taken by a wave, not a thread: group_decide reads slot after slot from pinned host memory, three dependent round
 // trips each, and fifteen slots in a row would stand in front of every block of the leader.  Here lane j reads the slot of step
@@ -1335,12 +1338,13 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
     DeepRecord *rec = pp.recs + p.step % DEEP_RECS;
     const unsigned long long tag = p.step << PAIR_SHIFT;
 
-    const int jj = lane & 3, gq = lane >> 4;         // this lane's row of the chunk and its query of each phase's four
+    // this lane's row of the chunk and its query of the sixteen (device_utils.h, the folded lane map: 64 lanes, 64 pairs)
+    const int jj = wave_sum4_folded_row(lane), gq = wave_sum4_folded_query(lane);
     // (the records, the lists and the locks: see scan_wide_kernel.  Wave 0 sets them up and the leader's image; the images of the
     // calls taken along are set up phase by phase, wave h those of phase h)
     typedef float norm_f32x2 __attribute__((ext_vector_type(2)));
-    const norm_f32x2 *s_norm_a = reinterpret_cast<const norm_f32x2 *>(s_rec + gq);                   // this lane's record of phase 0: the norm half ...
-    const unsigned long long *s_thr_a = reinterpret_cast<const unsigned long long *>(s_rec + gq) + 1;   // ... and the threshold (phase h: 4 h records on)
+    const norm_f32x2 *s_norm_a = reinterpret_cast<const norm_f32x2 *>(s_rec + gq);                   // this lane's query's record: the norm half ...
+    const unsigned long long *s_thr_a = reinterpret_cast<const unsigned long long *>(s_rec + gq) + 1;   // ... and the threshold
     if (wave == 0) {
 #pragma unroll
         for (int i = 0; i < NQ * SHARED_LIST_KEYS / 64; ++i) s_list[64 * i + lane] = KEY_PAD;
@@ -1355,8 +1359,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
         }
     }
 #define SMT_QUERY_NORM(n, qn)                                                                                     \
-    do {                                                                                                          \
-        s_q[(n) * 64 + lane] = (qn);                                                                              \
+    do {   /* (lane l keeps its 16 bytes of query n in the slot it reads them from: slot s of phase h holds query 4 h + (s ^ i')) */ \
+        s_q[wave_sum4_folded_slot(n, lane) * 64 + lane] = (qn);                                                   \
         const float a2 = wave_sum((qn).x * (qn).x + (qn).y * (qn).y + (qn).z * (qn).z + (qn).w * (qn).w);         \
         const bool qz = readlane_f(a2, 0) == 0.0f;                                                                \
         const float rq = qz ? 0.0f : readlane_f(__frsqrt_rn(a2), 0);                                              \
@@ -1498,80 +1502,76 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
 
 #define SMT_ROW_DOT(cj, qv) __builtin_fmaf((cj).w, (qv).w, __builtin_fmaf((cj).z, (qv).z, __builtin_fmaf((cj).x, (qv).x, (cj).y * (qv).y)))
 #define SMT_OPAQUE(v) asm volatile("" : "+v"(v))
-    // a lane's record of phase h as it stands now: the norm half never changes, the threshold is one 64-bit read (shared_list.h)
-#define SMT_DEEP_RECORD(MINE, h)                                                                                  \
+    // a lane's record as it stands now: the norm half never changes, the threshold is one 64-bit read (shared_list.h)
+#define SMT_DEEP_RECORD(MINE)                                                                                     \
     f32x4 MINE;                                                                                                   \
     do {                                                                                                          \
-        const norm_f32x2 nz = s_norm_a[8 * (h)];   /* (8-byte units: phase h's record is 4 h records on) */       \
-        const unsigned long long t = shared_list_threshold(s_thr_a + 8 * (h));                                    \
+        const norm_f32x2 nz = s_norm_a[0];                                                                        \
+        const unsigned long long t = shared_list_threshold(s_thr_a);                                              \
         MINE.x = nz.x;                                                                                            \
         MINE.y = nz.y;                                                                                            \
         MINE.z = __uint_as_float((uint32_t)t);                                                                    \
         MINE.w = __uint_as_float((uint32_t)(t >> 32));                                                            \
     } while (0)
-    // D4: the phase's distances, lane 16 g + j holds row j against query g + 4 h.  What passed the (possibly stale) threshold is
-    // offered to the lists in the order of the ballot's bits: query-major, rows ascending.
-#define SMT_DEEP_TEST_INSERT(h, MINE, ON, AB, D4)                                                                 \
+    // D4: the chunk's 64 distances, lane l holds row jj against query gq.  ONE distance, one compare, one ballot per chunk.  What
+    // passed the (possibly stale) threshold is offered to the lists in the order of the ballot's bits; the lists hold the k'
+    // smallest keys whatever the order.  The query of bit b is wave_sum4_folded_query(b), on scalars.
+#define SMT_DEEP_TEST_INSERT(MINE, AB, D4)                                                                        \
     do {                                                                                                          \
         const float D4 = dist_f32_rs(AB, rs_b2, b2_zero, (MINE).x, (MINE).y != 0.0f);                             \
         const uint32_t thr_r_mine = __float_as_uint((MINE).w);                                                    \
-        const bool cand = ((ON) & valid_mine) & ((D4 < (MINE).z) | ((D4 == (MINE).z) & (r_mine < thr_r_mine)));   \
-        uint64_t pending = __ballot(cand) & 0x000F000F000F000Full;                                                \
+        const bool cand = (on_mine & valid_mine) & ((D4 < (MINE).z) | ((D4 == (MINE).z) & (r_mine < thr_r_mine))); \
+        uint64_t pending = __ballot(cand);                                                                        \
         while (pending) {                                                                                         \
             const int b = __builtin_ctzll(pending);                                                               \
             pending &= pending - 1;                                                                               \
-            const int n = (b >> 4) + 4 * (h);                                                                     \
+            const int n = 4 * (b >> 4) + ((4 - ((b >> 2) & 3)) & 3);                                              \
             const float d = readlane_f(D4, b);                                                                    \
             const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)r_mine, b);                               \
             shared_list_insert(s_list + n * SHARED_LIST_KEYS, s_lock + n, reinterpret_cast<unsigned long long *>(s_rec + n) + 1, d, r, \
                                kp, lane, pp.ctl);                                                                 \
         }                                                                                                         \
     } while (0)
-    // Phase h = 1 .. 3, scan_wide_kernel's phase B: the heads of queries 4 h and 4 h + 1, behind n_on > 4 h + 2 those of 4 h + 2 and
-    // 4 h + 3 (trees that do not exist are fed registers that are there anyway: their rows are off), the row steps of the four, ONE
-    // tail without the <c, c> column, one distance, one compare, one ballot.  b2, valid_mine and r_mine are the chunk's.
+    // Phase h = 1 .. 3, behind a wave-uniform n_on > 4 h: the heads of the lane's four slots, two at a time (slot s of phase h in this
+    // lane is query 4 h + (s ^ i'), device_utils.h), each pair folded by the mirror step as soon as its heads are done, the two results
+    // by the rotation by 8: ONE register X, in which quad i of every row holds the row sums of query 4 h + i'.  A phase that is on
+    // computes all four slots; queries that are not there have images that are there anyway, and their lanes are off.
     // (n_h: the calls of this phase and behind it, asked of an opaque scalar copy chunk by chunk: as invariants of the row loop the
-    // six compares and the three lane masks would be hoisted into eighteen scalar registers, which that loop does not have)
-#define SMT_DEEP_PHASE(cq, h)                                                                                     \
-    int n_h##h = n_on - 4 * (h);                                                                                  \
-    asm volatile("" : "+s"(n_h##h));                                                                              \
-    if (n_h##h > 0) {                                                                                             \
+    // compares would be hoisted into scalar registers that loop does not have)
+#define SMT_DEEP_PHASE(cq, h, X)                                                                                  \
+    do {                                                                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         const f32x4 qva = s_q[256 * (h) + lane], qvb = s_q[256 * (h) + 64 + lane];                                \
-        float parta[2][4], w2[2];                                                                                 \
+        float parta[2][4], t2[2];                                                                                 \
         _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                           \
             parta[0][j] = SMT_ROW_DOT((cq)[j], qva);                                                              \
             parta[1][j] = SMT_ROW_DOT((cq)[j], qvb);                                                              \
         }                                                                                                         \
-        wave_sum4_swizzled_head<2>(parta, w2);                                                                    \
-        SMT_OPAQUE(w2[0]); SMT_OPAQUE(w2[1]);                                                                     \
-        float v4[4] = {w2[0], w2[1], w2[0], w2[1]};                                                               \
-        if (n_h##h > 2) {                                                                                         \
-            __builtin_amdgcn_sched_barrier(0);                                                                    \
-            const f32x4 qvc = s_q[256 * (h) + 128 + lane], qvd = s_q[256 * (h) + 192 + lane];                     \
-            float partc[2][4], x2[2];                                                                             \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                       \
-                partc[0][j] = SMT_ROW_DOT((cq)[j], qvc);                                                          \
-                partc[1][j] = SMT_ROW_DOT((cq)[j], qvd);                                                          \
-            }                                                                                                     \
-            wave_sum4_swizzled_head<2>(partc, x2);                                                                \
-            SMT_OPAQUE(x2[0]); SMT_OPAQUE(x2[1]);                                                                 \
-            v4[2] = x2[0]; v4[3] = x2[1];                                                                         \
+        wave_sum4_swizzled_head<2>(parta, t2);                                                                    \
+        float s0 = wave_sum4_fold_mirror(t2[0], t2[1]);                                                           \
+        SMT_OPAQUE(s0);                                                                                           \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        const f32x4 qvc = s_q[256 * (h) + 128 + lane], qvd = s_q[256 * (h) + 192 + lane];                         \
+        float partc[2][4], u2[2];                                                                                 \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                           \
+            partc[0][j] = SMT_ROW_DOT((cq)[j], qvc);                                                              \
+            partc[1][j] = SMT_ROW_DOT((cq)[j], qvd);                                                              \
         }                                                                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                                                        \
-        SMT_DEEP_RECORD(mine_h, h);                                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                                        \
-        wave_sum4_rows<4>(v4);                                                                                    \
-        wave_sum4_group_tail_queries(v4[0], v4[1], v4[2], v4[3]);                                                 \
-        SMT_DEEP_TEST_INSERT(h, mine_h, gq < n_h##h, v4[0], d4h);                                                 \
-    }
-    // phase 0: scan_wide_kernel's phase A (SMT_REDUCE_GROUP4 of scan_pair_kernel) up to the distance, but for the heads, which
-    // take the rows as SMT_DEEP_STEP has permuted them; the other three phases behind it
+        wave_sum4_swizzled_head<2>(partc, u2);                                                                    \
+        X = wave_sum4_fold_ror8(s0, wave_sum4_fold_mirror(u2[0], u2[1]));                                         \
+        SMT_OPAQUE(X);                                                                                            \
+    } while (0)
+#define SMT_DEEP_ON(h, N)                                                                                         \
+    int N = n_on - 4 * (h);                                                                                       \
+    asm volatile("" : "+s"(N));
+    // The chunk: phase 0 with the <c, c> tree beside its first two slots (the head of three), then the phases that are on, their
+    // registers folded through ONE tail as they come (x_0 with x_1 behind phase 1, x_2 with x_3 behind phase 3, then the two: the
+    // additions of wave_sum4_group_tail_queries), <c, c> through the replicating tail beside it.  Then lane l holds
+    // <row jj, query gq> and <c, c> of row jj: one record read, one distance, one compare, one ballot.  A register of a phase
+    // that is off is whatever it is (its rows of the wave are off, the other rows never see it).
 #define SMT_REDUCE_DEEP(cq, rq4, VALID)                                                                           \
     do {                                                                                                          \
         const f32x4 qv0 = s_q[lane];                                                                              \
-        const bool valid_mine = (uint32_t)jj < (VALID);                                                           \
-        const uint32_t r_mine = (rq4) + (uint32_t)jj;                                                             \
         float part[3][4];                                                                                         \
         _Pragma("unroll") for (int j = 0; j < 4; ++j) part[0][j] = SMT_ROW_DOT((cq)[j], (cq)[j]);                 \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
@@ -1581,47 +1581,54 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
         _Pragma("unroll") for (int j = 0; j < 4; ++j) part[2][j] = SMT_ROW_DOT((cq)[j], qv1);                     \
         float v3[3];                                                                                              \
         wave_sum4_swizzled_head<3>(part, v3);                                                                     \
-        SMT_OPAQUE(v3[0]); SMT_OPAQUE(v3[1]); SMT_OPAQUE(v3[2]);                                                  \
+        float cc = wave_sum4_fold_cc_rows(v3[0]);                                                                 \
+        float w0 = wave_sum4_fold_mirror(v3[1], v3[2]);                                                           \
+        SMT_OPAQUE(cc); SMT_OPAQUE(w0);                                                                           \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         const f32x4 qv2 = s_q[128 + lane], qv3 = s_q[192 + lane];                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                                        \
-        float v5[5] = {v3[0], v3[1], v3[2], v3[1], v3[2]};                                                        \
-        if (n_on > 2) {                                                                                           \
-            float part2[2][4], v2[2];                                                                             \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                       \
-                part2[0][j] = SMT_ROW_DOT((cq)[j], qv2);                                                          \
-                part2[1][j] = SMT_ROW_DOT((cq)[j], qv3);                                                          \
-            }                                                                                                     \
-            wave_sum4_swizzled_head<2>(part2, v2);                                                                \
-            SMT_OPAQUE(v2[0]); SMT_OPAQUE(v2[1]);                                                                 \
-            v5[3] = v2[0]; v5[4] = v2[1];                                                                         \
+        float part2[2][4], v2[2];                                                                                 \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                           \
+            part2[0][j] = SMT_ROW_DOT((cq)[j], qv2);                                                              \
+            part2[1][j] = SMT_ROW_DOT((cq)[j], qv3);                                                              \
         }                                                                                                         \
+        wave_sum4_swizzled_head<2>(part2, v2);                                                                    \
+        float x0 = wave_sum4_fold_ror8(w0, wave_sum4_fold_mirror(v2[0], v2[1]));                                  \
+        SMT_OPAQUE(x0);                                                                                           \
+        float x1, x2, x3;                                                                                         \
+        asm volatile("" : "=v"(x1), "=v"(x2));                                                                    \
+        SMT_DEEP_ON(1, n_h1)                                                                                      \
+        if (n_h1 > 0) SMT_DEEP_PHASE(cq, 1, x1);                                                                  \
+        wave_sum4_fold_tail16_cc(cc, x0, x1);                                                                     \
+        SMT_DEEP_ON(2, n_h2)                                                                                      \
+        if (n_h2 > 0) {                                                                                           \
+            SMT_DEEP_PHASE(cq, 2, x2);                                                                            \
+            asm volatile("" : "=v"(x3));                                                                          \
+            SMT_DEEP_ON(3, n_h3)                                                                                  \
+            if (n_h3 > 0) SMT_DEEP_PHASE(cq, 3, x3);                                                              \
+            wave_sum4_fold_tail16(x2, x3);                                                                        \
+        }                                                                                                         \
+        wave_sum4_fold_tail32_cc(cc, x0, x2);                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
-        SMT_DEEP_RECORD(mine, 0);                                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                                        \
-        wave_sum4_rows<5>(v5);                                                                                    \
-        wave_sum4_group_tail(v5[0], v5[1], v5[2], v5[3], v5[4]);                                                  \
-        const float b2 = v5[0];                                                                                   \
-        const float rs_b2 = __frsqrt_rn(b2);   /* once per chunk, for the four phases (v_rsq runs at quarter rate) */ \
-        const bool b2_zero = b2 == 0.0f;                                                                          \
-        SMT_DEEP_TEST_INSERT(0, mine, on_mine, v5[1], d4);                                                        \
-        SMT_DEEP_PHASE(cq, 1)                                                                                     \
-        SMT_DEEP_PHASE(cq, 2)                                                                                     \
-        SMT_DEEP_PHASE(cq, 3)                                                                                     \
+        SMT_DEEP_RECORD(mine);                                                                                    \
+        const bool valid_mine = (uint32_t)jj < (VALID);                                                           \
+        const uint32_t r_mine = (rq4) + (uint32_t)jj;                                                             \
+        const float rs_b2 = __frsqrt_rn(cc);                                                                      \
+        const bool b2_zero = cc == 0.0f;                                                                          \
+        SMT_DEEP_TEST_INSERT(mine, x0, d4);                                                                       \
     } while (0)
     const bool on_mine = gq < n_on;   // (an absent query has thr = +inf and must never insert)
     // (the two-buffer pipeline of scan_pair_kernel: one chunk in flight per wave, the claims in the same order)
-    // THE ROWS ARE PERMUTED BY LANE once a chunk has landed (device_utils.h swizzle_rows4: register k of lane l holds row
-    // k ^ (l & 3)), in place on the buffer that is reduced, and the seventeen trees' heads run without selects
+    // THE ROWS ARE PERMUTED BY LANE once a chunk has landed (device_utils.h swizzle_rows4_folded: register k of lane l holds row
+    // k ^ m(l), m the folded map's row), in place on the buffer that is reduced, and the seventeen trees' heads run without selects
     // (wave_sum4_swizzled_head): what a lane keeps and sends in a head depends on the lane alone, so the choice is made once on
     // the sixteen row registers and not seventeen times on the products.  Every product is the same chain on the same operands
-    // in another register, every addition has its operands in their order; behind the heads nothing knows of the permutation.
+    // in another register, every addition has the operands of wave_sum4's, possibly exchanged.
 #define SMT_DEEP_STEP(cur, nxt)                                                                                   \
     do {                                                                                                          \
         asm volatile("s_waitcnt vmcnt(0)" : "+v"((cur)[0]), "+v"((cur)[1]), "+v"((cur)[2]), "+v"((cur)[3]) : : "memory"); \
         if (in_corpus(v0n)) issue_rows(v0n, nxt);                                                                 \
         const uint64_t v0nn = chunk_v0(claim());                                                                  \
-        swizzle_rows4((cur)[0], (cur)[1], (cur)[2], (cur)[3], lane);                                              \
+        swizzle_rows4_folded((cur)[0], (cur)[1], (cur)[2], (cur)[3], lane);                                       \
         SMT_REDUCE_DEEP(cur, (uint32_t)v0, in_corpus(v0 + (U - 1)) ? 4u : (uint32_t)(p.n_virtual - v0));          \
         /* (the permuted rows end here: without this they count as live into the next turn and are copied about) */ \
         asm volatile("" : "=v"((cur)[0]), "=v"((cur)[1]), "=v"((cur)[2]), "=v"((cur)[3]));                        \
@@ -1636,6 +1643,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))
     }
 #undef SMT_DEEP_STEP
 #undef SMT_REDUCE_DEEP
+#undef SMT_DEEP_ON
 #undef SMT_DEEP_PHASE
 #undef SMT_DEEP_TEST_INSERT
 #undef SMT_DEEP_RECORD
