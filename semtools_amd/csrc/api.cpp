@@ -474,7 +474,7 @@ try {
     if ((rc = bind_device(ctx))) return rc;
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if ((rc = sync_side_streams(ctx))) return rc;
-    unsigned long long v[6] = {0, 0, 0, 0, 0, 0};   // paired, alone, absorbed, served 2 / 3 / 4 (scan_kernels.hip PairParams::ctl)
+    unsigned long long v[6] = {0, 0, 0, 0, 0, 0};   // paired, alone, absorbed, served 2 / 3 / 4 (scan_group.h PairParams::ctl)
     if (ctx->d_gate) SMT_HIP_CHECK(hipMemcpy(v, ctx->d_gate + 2, sizeof(v), hipMemcpyDeviceToHost));
     by_size[0] = v[1] + ctx->pair_alone_host;
     by_size[1] = v[3];
@@ -491,7 +491,7 @@ try {
     if ((rc = bind_device(ctx))) return rc;
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if ((rc = sync_side_streams(ctx))) return rc;
-    unsigned long long v[10] = {};   // paired, alone, absorbed, served 2 .. 8 (scan_kernels.hip PairParams::ctl, WideParams::ctl)
+    unsigned long long v[10] = {};   // paired, alone, absorbed, served 2 .. 8 (scan_group.h PairParams::ctl, WideParams::ctl)
     if (ctx->d_gate) SMT_HIP_CHECK(hipMemcpy(v, ctx->d_gate + 2, sizeof(v), hipMemcpyDeviceToHost));
     by_size[0] = v[1] + ctx->pair_alone_host;
     for (int n = 1; n < 8; ++n) by_size[n] = v[2 + n];
@@ -506,7 +506,7 @@ try {
     if ((rc = bind_device(ctx))) return rc;
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if ((rc = sync_side_streams(ctx))) return rc;
-    unsigned long long v[16] = {};   // launches of scan_deep_kernel that served 1 .. 16 calls (scan_kernels.hip DeepParams::ctl)
+    unsigned long long v[16] = {};   // launches of scan_deep_kernel that served 1 .. 16 calls (scan_group.h DeepParams::ctl)
     if (ctx->d_gate) SMT_HIP_CHECK(hipMemcpy(v, ctx->d_gate + 12, sizeof(v), hipMemcpyDeviceToHost));
     for (int n = 0; n < 16; ++n) by_size[n] = v[n];
     return SMT_OK;

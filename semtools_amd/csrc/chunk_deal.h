@@ -1,5 +1,5 @@
-// chunk_deal.h -- how the streaming kernels deal the chunks of a corpus to their waves: K2 (scan_topk_kernel, scan_pair_kernel:
-// scan_kernels.hip), K4 (scan_threshold_kernel: threshold.hip) and the large-k collect (largek_collect_kernel: topk_large.hip).
+// chunk_deal.h -- how the streaming kernels deal the chunks of a corpus to their waves: K2 (scan_topk_kernel and the grouped
+// kernels: scan_topk.hip, scan_pair.hip, scan_wide.hip, scan_deep.hip), K4 (scan_threshold_kernel: threshold.hip) and the large-k collect (largek_collect_kernel: topk_large.hip).
 // The loop skeletons -- how many stages, what a descriptor is made from -- stay in the kernels.
 #pragma once
 #include "device_utils.h"

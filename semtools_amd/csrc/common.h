@@ -57,7 +57,7 @@ struct Tuning {
     int scan_unroll = 4;
     int scan_nontemporal = 1;
     int scan_prefetch = 1;      // software-pipelined row loads (single-query kernel)
-    int scan_steal = 0;         // K2, unfiltered: rounds per dynamically dealt group (power of two; 0 = the static deal, the default: the dynamic deal evens the blocks out and gains nothing -- the launch is bound by the part's aggregate read rate): scan_kernels.hip STEAL
+    int scan_steal = 0;         // K2, unfiltered: rounds per dynamically dealt group (power of two; 0 = the static deal, the default: the dynamic deal evens the blocks out and gains nothing -- the launch is bound by the part's aggregate read rate): scan_topk.hip STEAL
     int scan_steal_pct = 6;     // ... and the share of the corpus dealt that way, at the end of the launch (1..50 per cent)
     int gemm_blocks = 0;        // 0 = CU count
     int prof_every = 1;         // HIP events bracket one launch in N (an event pair costs ~6 us of stream time)
@@ -65,7 +65,7 @@ struct Tuning {
     int async_select = 0;       // 1: single-query top-k searches overlap their select stage with the next scan
     int scan_overlap = 1;       // async_select, smt_search_topk_device: scan + select of call i on internal stream i & 1 (consecutive scans overlap; 0 = the aux-stream / flag pipeline)
     int scan_gate_pct = -1;     // scan_overlap: a scan's blocks start once this share of its predecessor call's blocks has finished its rows (0 = no gate; -1, the default: 50 in every mode -- DESIGN.md 4.1 has the sweeps)
-    int scan_pair = 15;         // scan_overlap: a scan that starts behind a predecessor takes the queries of up to this many later calls of its stream (steps + 2, + 4, ...) along in the same corpus pass (key scan_pair: 0..3, scan_kernels.hip scan_pair_kernel; key scan_take: 0..7, above 3 scan_wide_kernel where it applies; key scan_deep: 0..15, above 7 scan_deep_kernel)
+    int scan_pair = 15;         // scan_overlap: a scan that starts behind a predecessor takes the queries of up to this many later calls of its stream (steps + 2, + 4, ...) along in the same corpus pass (key scan_pair: 0..3, scan_pair.hip scan_pair_kernel; key scan_take: 0..7, above 3 scan_wide_kernel where it applies; key scan_deep: 0..15, above 7 scan_deep_kernel)
     int scan_pair_ring = 4096;  // scan_pair: slots of the descriptor ring in use (a power of two, 64 .. 4096): a call is found by the scan two steps earlier while the host is fewer calls ahead of the GPU than this (tests use 64 to see slots reused)
     int scan_pair_wait_us = 0;  // scan_pair, tests only: the deciding block waits this long (<= 5000) for the partner's descriptor
     int select_group = 1;       // 1: a scan_deep_kernel launch is followed by ONE select launch for the calls its pass serves (select.hip group_select_kernel); 0: every call's own final_select_kernel, as before (switching drains the pipeline)
@@ -133,7 +133,7 @@ struct smt_ctx {
     bool async_pending = false;
     bool async_overlap = false;              // the pending pipeline is the scan_overlap one (calls of the other kind drain it first)
     // scan_overlap (tuning key): call i enqueues its scan AND its select on ov_stream[i & 1], behind ov_ready[i & 1] recorded on
-    // `stream`; consecutive scans overlap, paced by the start gate d_gate (scan_kernels.hip ScanParams::gate)
+    // `stream`; consecutive scans overlap, paced by the start gate d_gate (scan_params.h ScanParams::gate)
     hipStream_t ov_stream[2] = {nullptr, nullptr};
     hipEvent_t ov_ready[2] = {nullptr, nullptr};
     hipEvent_t ov_done = nullptr;            // a profiled launch waits on its predecessor through this
@@ -145,7 +145,7 @@ struct smt_ctx {
     uint64_t gate_prev_blocks = 0;           // ... and of the latest one
     uint64_t gate_prev_rows = 0;
     // scan_pair: the descriptor ring (pinned host memory, one slot per step) and the per-step decision records (device); the
-    // counters and the wait-ran-out flag live behind the gate counter, d_gate[1..27] of 32 (scan_kernels.hip PairParams::ctl, WideParams::ctl, DeepParams::ctl)
+    // counters and the wait-ran-out flag live behind the gate counter, d_gate[1..27] of 32 (scan_group.h PairParams::ctl, WideParams::ctl, DeepParams::ctl)
     void *h_pair_ring = nullptr;
     void *d_pair_recs = nullptr;
     void *d_wide_recs = nullptr;             // scan_take: the records of scan_wide_kernel launches
@@ -161,7 +161,7 @@ struct smt_ctx {
     uint64_t host_ns_calls = 0;              // ... over this many pipeline calls
     uint64_t pair_alone_host = 0;            // scan_pair calls that got the plain kernel: nothing queued in front of them, or profiled (smt_debug_scan_pairs counts them as alone)
     bool pair_live = false;                  // paired-mode scans were launched since the last drain (their error flag is unread)
-    unsigned int *d_steal = nullptr;         // K2 STEAL: 64 group counters, one per launch in rotation (scan_kernels.hip)
+    unsigned int *d_steal = nullptr;         // K2 STEAL: 64 group counters, one per launch in rotation (scan_launch.hip steal_setup)
     uint64_t steal_seq = 0;
     unsigned long long deliver_seq = 0;      // sequence number of the last delivered answer (its completion word in pinned memory)
     uint64_t deliveries = 0;                 // host-form searches answered that way (smt_debug_deliveries)
@@ -295,7 +295,7 @@ int drain_async(smt_ctx *ctx);
 int ensure_overlap(smt_ctx *ctx);
 // every stream that may still run kernels of this context besides `stream` (aux, the two scan streams)
 int sync_side_streams(smt_ctx *ctx);
-// scan_pair: the descriptor ring and the decision records, made on first use (scan_kernels.hip)
+// scan_pair: the descriptor ring and the decision records, made on first use (scan_launch.hip)
 int ensure_pair(smt_ctx *ctx);
 // scan_overlap + an aux stream: work enqueued on aux from now on runs behind every overlapped select enqueued so far
 int order_aux_after_overlap(smt_ctx *ctx);
@@ -440,9 +440,9 @@ struct SelectArgs {
 int launch_select(smt_ctx *ctx, const SelectArgs &s);
 
 // One select launch per pass of scan_deep_kernel (select.hip group_select_kernel; tuning key select_group).  What the kernel
-// reads of the scan's record is named here as 8-byte words, and scan_kernels.hip asserts that DeepRecord and DeepSelRecord are laid
+// reads of the scan's record is named here as 8-byte words, and scan_group.h asserts that DeepRecord and DeepSelRecord are laid
 // out that way.
-constexpr int GROUP_SEL_MAX = 16;                     // calls one launch serves: blocks of the grid (scan_kernels.hip DEEP_MAX)
+constexpr int GROUP_SEL_MAX = 16;                     // calls one launch serves: blocks of the grid (scan_group.h DEEP_MAX)
 constexpr int GROUP_REC_STATE = 0, GROUP_REC_TAKEN = 1, GROUP_REC_QUERY = 2, GROUP_REC_LISTS = GROUP_REC_QUERY + GROUP_SEL_MAX - 1;
 struct GroupSelect {
     const unsigned long long *rec;   // this step's DeepRecord

@@ -1,5 +1,5 @@
 // device_flags.h -- device-scope flag words between kernels that run at the same time: the scan of step i and its select on
-// another stream (async select: scan_kernels.hip raises scan_done and waits for select_done, select.hip the other way round).
+// another stream (async select: scan_topk.hip raises scan_done and waits for select_done, select.hip the other way round).
 #pragma once
 #include "device_utils.h"
 

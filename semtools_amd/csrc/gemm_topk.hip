@@ -421,7 +421,7 @@ static GemmRoute gemm_route(const smt_ctx *ctx, const ScanArgs &a)
     // 2 x 2 M 0.310 against 0.228, one / three queries over a 5 M-row document subset 0.494 / 0.669 against 0.484 / 0.497
     // (profiles/r05_ab_image_scan.txt).  A wave's own k'-th is a loose threshold -- ~100 inserts per wave and query, each a
     // wave-wide affair out of MFMA accumulators -- where the levels' thresholds come from merged lists.  Not kept.)
-    // guard band, see candidates_per_list (scan_kernels.hip): the wider the certificate band, the more rows are nominated
+    // guard band, see candidates_per_list (scan_launch.hip): the wider the certificate band, the more rows are nominated
     // (the proof needs the k-th exact distance to lie 2 x the band below the worst nominated one): 8 / 16 / 24
     const uint32_t kp = std::min<uint32_t>(64, a.k_out + (uint32_t)std::max(ctx->tune.guard_band, f16x1 ? 24 : f16x2 ? 16 : 8));
     const bool lds_rows = !rowreg && ctx->tune.gemm_ldsrow && (filtered || nqt <= 2);

@@ -540,7 +540,7 @@ __device__ __forceinline__ void final_select_body(const FinalParams &p, const ui
 template <int KREG, bool OVF = false>
 __global__ void __launch_bounds__(SEL_THREADS) final_select_kernel(FinalParams p)
 {
-    extern __shared__ unsigned char smem_raw[];   // (no alignment attribute: see scan_topk_kernel, scan_kernels.hip)
+    extern __shared__ unsigned char smem_raw[];   // (no alignment attribute: see scan_topk_kernel, scan_topk.hip)
     final_select_body<KREG, OVF>(p, blockIdx.x, smem_raw);
 }
 
@@ -549,7 +549,7 @@ __global__ void __launch_bounds__(SEL_THREADS) final_select_kernel(FinalParams p
 // stream, has the call's answer, and every block returns.  Otherwise the pass served n = 1 + taken calls: block 0 runs the call's own
 // select with the parameters it was launched with, block g in 1 .. n - 1 that of member g - 1 -- the shared fields (corpus, n_lists,
 // k', k_out, f32_err, the sticky counter: a leader takes calls that agree with it in all of them) and the member's own queries, list
-// set, output buffers, status word and row base, as the deciding wave copied them into the record (scan_kernels.hip deep_decide).
+// set, output buffers, status word and row base, as the deciding wave copied them into the record (scan_deep.hip deep_decide).
 // The body is final_select_body<KREG, false> with query index 0, unchanged: every answer, verdict and count is what the member's
 // own launch of final_select_kernel produced.
 // ORDER: a member's outputs are written at the leader's place in stream order, earlier than at its own.  That is safe for the reason

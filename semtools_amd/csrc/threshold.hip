@@ -58,7 +58,7 @@ __global__ void __launch_bounds__(1024) scan_threshold_kernel(ThrParams p)
     // (the chunk deal of all streaming kernels: chunk_deal.h)
     auto fetch_desc = [&](uint64_t c) -> uint64_t {
         if (c >= n_chunks) return 0ull;
-        if (FILTERED) return const_table[c];  // constant address space: scalar load (see scan_topk_kernel, scan_kernels.hip)
+        if (FILTERED) return const_table[c];  // constant address space: scalar load (see scan_topk_kernel, scan_topk.hip)
         const uint64_t v0 = c * U;
         const uint64_t left = p.n_virtual - v0;
         return v0 | ((left < (uint64_t)U ? left : (uint64_t)U) << 32);

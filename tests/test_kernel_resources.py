@@ -36,7 +36,7 @@ def test_select_kernel_fits_beside_a_scan_block_and_nothing_spills():
     sel = [v for k, v in u.items() if "final_select_kernelILi8ELb0" in k]
     assert len(sel) == 1, list(u)
     assert sel[0]["VGPRs"] <= 96, sel[0]
-    u = _usage("scan_kernels.hip")
+    u = _usage("scan_topk.hip")
     scans = {k: v for k, v in u.items() if "scan_topk_kernel" in k}
     assert scans
     for k, v in scans.items():

@@ -11,8 +11,8 @@ from tests.test_kernel_resources_groups import CU_LDS, SELECT_LDS
 
 
 def _deep_smem_bytes(threads):
-    """deep_smem_bytes(threads) of scan_kernels.hip, evaluated from its source text."""
-    src = open(os.path.join(ROOT, "semtools_amd", "csrc", "scan_kernels.hip")).read()
+    """deep_smem_bytes(threads) of scan_group.h, evaluated from its source text."""
+    src = open(os.path.join(ROOT, "semtools_amd", "csrc", "scan_group.h")).read()
     deep_max = int(re.search(r"constexpr int DEEP_MAX = (\d+);", src).group(1))
     body = re.search(r"static inline size_t deep_smem_bytes\(int threads\)\s*\{\s*return ([^;]+);", src).group(1)
     expr = body.replace("(size_t)", "").replace("sizeof(key_t64)", "8").replace("DEEP_MAX", str(deep_max)).replace("/", "//")
@@ -22,7 +22,7 @@ def _deep_smem_bytes(threads):
 
 @pytest.mark.timeout(900)
 def test_deep_scan_fits_beside_the_select_without_spill_or_scratch():
-    u = _usage("scan_kernels.hip")
+    u = _usage("scan_deep.hip")
     deep = {k: v for k, v in u.items() if "scan_deep_kernel" in k}
     assert len(deep) == 2, list(u)                                 # temporal and non-temporal row loads
     deep_max, dynamic = _deep_smem_bytes(512)                      # (the launcher runs it in blocks of at most 512 threads)

@@ -23,8 +23,8 @@ PARENT_VGPRS = {
 
 
 def _pair_smem_bytes(threads):
-    """pair_smem_bytes(threads) of scan_kernels.hip, evaluated from its source text."""
-    src = open(os.path.join(ROOT, "semtools_amd", "csrc", "scan_kernels.hip")).read()
+    """pair_smem_bytes(threads) of scan_group.h, evaluated from its source text."""
+    src = open(os.path.join(ROOT, "semtools_amd", "csrc", "scan_group.h")).read()
     group_max = int(re.search(r"constexpr int GROUP_MAX = (\d+);", src).group(1))
     body = re.search(r"static inline size_t pair_smem_bytes\(int threads\)\s*\{\s*return ([^;]+);", src).group(1)
     expr = body.replace("(size_t)", "").replace("sizeof(key_t64)", "8").replace("GROUP_MAX", str(group_max)).replace("/", "//")
@@ -34,7 +34,7 @@ def _pair_smem_bytes(threads):
 
 @pytest.mark.timeout(900)
 def test_group_capable_scan_has_no_scratch_fits_its_lds_and_leaves_the_plain_scans_alone():
-    u = _usage("scan_kernels.hip")
+    u = {**_usage("scan_pair.hip"), **_usage("scan_topk.hip")}    # (the grouped kernel's unit and the plain scans')
     pair = {k: v for k, v in u.items() if "scan_pair_kernel" in k}
     assert len(pair) == 2, list(u)
     group_max, _ = _pair_smem_bytes(512)

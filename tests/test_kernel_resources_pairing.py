@@ -10,7 +10,7 @@ from tests.test_kernel_resources import _usage
 
 @pytest.mark.timeout(900)
 def test_pair_capable_scan_fits_beside_the_select_and_does_not_spill():
-    u = _usage("scan_kernels.hip")
+    u = _usage("scan_pair.hip")
     pair = {k: v for k, v in u.items() if "scan_pair_kernel" in k}
     assert len(pair) == 2, list(u)                                 # temporal and non-temporal row loads
     for k, v in pair.items():

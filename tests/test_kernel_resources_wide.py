@@ -12,8 +12,8 @@ from tests.test_kernel_resources_groups import CU_LDS, SELECT_LDS
 
 
 def _wide_smem_bytes(threads):
-    """wide_smem_bytes(threads) of scan_kernels.hip, evaluated from its source text."""
-    src = open(os.path.join(ROOT, "semtools_amd", "csrc", "scan_kernels.hip")).read()
+    """wide_smem_bytes(threads) of scan_group.h, evaluated from its source text."""
+    src = open(os.path.join(ROOT, "semtools_amd", "csrc", "scan_group.h")).read()
     wide_max = int(re.search(r"constexpr int WIDE_MAX = (\d+);", src).group(1))
     body = re.search(r"static inline size_t wide_smem_bytes\(int threads\)\s*\{\s*return ([^;]+);", src).group(1)
     expr = body.replace("(size_t)", "").replace("sizeof(key_t64)", "8").replace("WIDE_MAX", str(wide_max)).replace("/", "//")
@@ -23,7 +23,7 @@ def _wide_smem_bytes(threads):
 
 @pytest.mark.timeout(900)
 def test_wide_scan_fits_beside_the_select_without_spill_or_scratch():
-    u = _usage("scan_kernels.hip")
+    u = _usage("scan_wide.hip")
     wide = {k: v for k, v in u.items() if "scan_wide_kernel" in k}
     assert len(wide) == 2, list(u)                                 # temporal and non-temporal row loads
     wide_max, dynamic = _wide_smem_bytes(512)                      # (the launcher runs it in blocks of at most 512 threads)

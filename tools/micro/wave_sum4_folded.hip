@@ -17,7 +17,7 @@
 #include "../../semtools_amd/csrc/device_utils.h"
 using smt::f32x4;
 constexpr int ROUNDS = 64, NQ = 16, TREES = 1 + NQ, VECS = 4 + NQ;
-// (SMT_ROW_DOT of csrc/scan_kernels.hip)
+// (SMT_ROW_DOT of csrc/scan_group.h)
 #define ROW_DOT(cj, qv) __builtin_fmaf((cj).w, (qv).w, __builtin_fmaf((cj).z, (qv).z, __builtin_fmaf((cj).x, (qv).x, (cj).y * (qv).y)))
 // ref: [round][stage 0 head | 1 ror4 | 2 ror8 | 3 wave_sum4][tree][lane]; got_v [round][phase][slot][lane], got_w [round][phase][2][lane],
 // got_x [round][phase][lane], got_f and got_cc [round][phases on - 1][lane]

@@ -16,7 +16,7 @@
 #include "../../semtools_amd/csrc/device_utils.h"
 using smt::f32x4;
 constexpr int ROUNDS = 64, TREES = 5;
-// (SMT_ROW_DOT of csrc/scan_kernels.hip)
+// (SMT_ROW_DOT of csrc/scan_group.h)
 #define ROW_DOT(cj, qv) __builtin_fmaf((cj).w, (qv).w, __builtin_fmaf((cj).z, (qv).z, __builtin_fmaf((cj).x, (qv).x, (cj).y * (qv).y)))
 __global__ void k(const f32x4 *in, float *lone, float *got_a, float *got_b, f32x4 *swizzled)
 {
