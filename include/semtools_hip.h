@@ -1106,6 +1106,9 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *   compact_bounce_rows (64 .. 2^20, default 65536 = 64 MiB)  smt_corpus_compact: a step whose rows move down by fewer rows than this
  *                        goes through a bounce buffer of this many rows in the context's scratch (a launch must not overwrite its own
  *                        sources); a step with a longer gap is one direct launch.  At most 2 x ceil(rows / this) enqueues per call
+ *   thr_hit_cap (>= 1, default 2^20)  K4 (every row under max_distance): slots of the hit buffer of the first pass, at most the rows
+ *                        scanned.  A pass that counts more hits than slots is run again with a buffer of exactly that many; the
+ *                        answer does not depend on the key (tests lower it to reach the second pass on small corpora)
  * The keys and the one-query pipeline.  The keys that say so above drain it.  scan_blocks, scan_threads, scan_unroll and
  * guard_band are stored without a drain, while the list sets of earlier calls are still in flight: they shape the NEXT launch
  * only.  direct_delivery is stored without one too and concerns the host form alone (smt_search, smt_ivfpq_search), which drains

@@ -700,6 +700,10 @@ try {
     else if (k == "prof_select") ctx->tune.prof_select = (int)value;
     else if (k == "direct_delivery") ctx->tune.direct_delivery = (int)value;
     else if (k == "compact_bounce_rows") ctx->tune.compact_bounce_rows = std::max<int64_t>(64, std::min<int64_t>((int64_t)1 << 20, value));
+    else if (k == "thr_hit_cap") {
+        SMT_REQUIRE(value >= 1, "thr_hit_cap: at least one slot in the threshold scan's hit buffer");
+        ctx->tune.thr_hit_cap = value;
+    }
     else { set_error("unknown tuning key '%s'", key); return SMT_E_INVALID; }
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }

@@ -94,6 +94,7 @@ struct Tuning {
     int largek_sampled = 1;     // 1: 57 <= top_k <= 1024 take the sampled-threshold route (topk_large.hip); 0: the all-keys path (largek.hip, A/B and parity tests)
     int direct_delivery = 1;    // 1: host-form top-k searches with small answers (<= 8 KiB) get them DELIVERED by the select kernel into pinned host memory, completion word last; the host waits on that word (search.cpp; 0: D2H copy + hipStreamSynchronize, A/B)
     int64_t compact_bounce_rows = 65536;   // smt_corpus_compact: rows of the bounce buffer a step with a gap shorter than itself goes through (64 MiB; 64 .. 2^20), compact.hip
+    int64_t thr_hit_cap = (int64_t)1 << 20;   // K4: slots of the hit buffer of the first pass (at most the scanned rows); a pass that counts more hits is rerun with an exact-size buffer (tests lower it to reach the rerun on small corpora), threshold.hip
     int64_t scan_debug_ptr = 0;    // device pointer to (2*waves + blocks) u64 wall_clock64 stamps (profiling only)
     int64_t select_debug_ptr = 0;  // device pointer to 16 u64 for phase stamps (profiling only)
 };

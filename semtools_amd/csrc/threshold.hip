@@ -168,7 +168,7 @@ int run_threshold_query(smt_ctx *ctx, const ThresholdQuery &t, const uint32_t **
     const size_t smem = (size_t)(threads / 64) * HIT_BUF * sizeof(uint32_t) + 16;
     const float prefilter = (float)(t.max_distance + 8e-6) + 0.0f;
 
-    uint64_t cap = std::min<uint64_t>(t.n_virtual, (uint64_t)1 << 20);
+    uint64_t cap = std::min<uint64_t>(t.n_virtual, (uint64_t)ctx->tune.thr_hit_cap);
     for (;;) {
         // scratch: rows_a | rows_b | dist_a | bits_a | bits_b | count | rocprim temp
         size_t temp_keys = 0, temp_pairs = 0;
@@ -225,11 +225,13 @@ int run_threshold_query(smt_ctx *ctx, const ThresholdQuery &t, const uint32_t **
         const double *dist_final = dist_a;
         if (device_order) {
             size_t tb = b_temp;
+            prof_begin(ctx, "thr_sort");  // (also the witness of which ordering ran: tests/test_gpu_threshold.py)
             SMT_HIP_CHECK(rocprim::radix_sort_keys(temp, tb, rows_a, rows_b, n_hits, 0, 32, ctx->stream));
             if ((rc = launch_rescore_rows(ctx, t.corpus, t.query, rows_b, n_hits, dist_a))) return rc;
             hipLaunchKernelGGL(iota_bits_kernel, dim3((unsigned)((n_hits + 255) / 256)), dim3(256), 0, ctx->stream, dist_a, bits_a, n_hits);
             tb = b_temp;
             SMT_HIP_CHECK(rocprim::radix_sort_pairs(temp, tb, bits_a, bits_b, rows_b, rows_a, n_hits, 0, 64, ctx->stream));
+            prof_end(ctx, "thr_sort");
             rows_final = rows_a;                                      // sorted by (distance bits, row)
             dist_final = reinterpret_cast<const double *>(bits_b);    // the sorted bit patterns ARE the distances
         } else {
