@@ -1005,6 +1005,30 @@ int smt_debug_select_lists(smt_corpus *corpus, const float *queries_dev, uint32_
                            double f32_err, const uint32_t *overflow_dev, uint64_t out_stride, uint64_t *out_rows_dev, double *out_dist_dev,
                            uint64_t *out_counts_dev, uint64_t *out_uncertain_dev, uint32_t *out_status_dev);
 
+/* Test hooks for the scan stage (K2: csrc/scan_launch.hip and the units that hold its kernels): the block lists a scan WRITES, which
+ * answers show only through the select's guard band and f64 re-score.  tests/test_gpu_scan_lists.py checks them against a NumPy
+ * restatement of the deal and float64 distances (tests/scan_ref.py).
+ *   smt_debug_scan_lists   the synchronous path of a top_k call (1 <= top_k <= 56) of nq (1..8) HOST queries over the corpus, optional
+ *       row ranges as smt_search takes them, up to the select and no further: the plan, the pipeline step, the chunk table of a filtered
+ *       call, the STEAL set-up and one launch per pass -- the very functions a search runs, under the current tuning.  In front of the
+ *       first pass (nq + 1) x blocks x k' keys of the list area are preset to the byte 0x5A; behind the last all of them are copied to
+ *       out_keys (host), layout [nq + 1][blocks][k'].  A key = f32 distance bits << 32 | row, a list ascending with UINT64_MAX padding.
+ *       The extra set is a guard that no pass may touch: a pass of 3 queries rides in 4 slots, and slot 3 must write nothing.
+ *       out_blocks, out_kp  the grid and k' = min(64, top_k + guard_band); set before the capacity is checked, so a refused call says
+ *                           how many keys it needs
+ *       out_route           scan_unroll as planned (filtered: 4) | 0x10 non-temporal row loads | 0x20 range-filtered | 0x40 a pass ran
+ *                           the STEAL kernel | block size << 8 | query slots (1, 2, 4) of pass i << (20 + 4 i).  A pass of two or four
+ *                           slots planned at 2 rows per chunk runs the kernel built for 8.
+ *       SMT_E_INVALID for top_k outside 1..56, nq outside 1..8, nothing to scan, and out_cap_keys < (nq + 1) x blocks x k'.
+ *   smt_debug_scan_ring    waits for the one-query pipeline (async_select with scan_overlap), then copies the first n_keys keys
+ *       (<= 512 x 64) of the list set of the pipeline call made calls_back (< 32) calls ago to out_keys (host): set
+ *       (step - calls_back) & 31 of the ring, at the ring's fixed stride of 512 x 64 keys; a call's lists are [blocks][k'] at its head.
+ *       SMT_E_INVALID when the context has made no such call, or when its latest scan was not a call of that pipeline -- any other
+ *       scan carves the scratch buffer up its own way, smt_debug_scan_lists included: read the ring first. */
+int smt_debug_scan_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                         uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp, uint32_t *out_route);
+int smt_debug_scan_ring(smt_ctx *ctx, uint32_t calls_back, uint64_t n_keys, uint64_t *out_keys);
+
 /* The context's second stream (hipStream_t), created on first use: async selects run on it, or, with tuning key
  * scan_overlap, it waits for them (every select of an overlapped call enqueued before the work).  A host that
  * chains more work behind an async select (an RCCL all-gather of its output, the merge of the gathered

@@ -942,6 +942,20 @@ extern "C" {
         out_uncertain_dev: *mut u64,
         out_status_dev: *mut u32,
     ) -> c_int;
+    pub fn smt_debug_scan_lists(
+        corpus: *mut SmtCorpus,
+        queries: *const f32,
+        nq: u32,
+        top_k: u32,
+        ranges: *const SmtRange,
+        n_ranges: u32,
+        out_keys: *mut u64,
+        out_cap_keys: u64,
+        out_blocks: *mut u32,
+        out_kp: *mut u32,
+        out_route: *mut u32,
+    ) -> c_int;
+    pub fn smt_debug_scan_ring(ctx: *mut SmtCtx, calls_back: u32, n_keys: u64, out_keys: *mut u64) -> c_int;
     pub fn smt_ctx_aux_stream(ctx: *mut SmtCtx, stream_out: *mut *mut c_void) -> c_int;
     pub fn smt_set_tuning(ctx: *mut SmtCtx, key: *const c_char, value: i64) -> c_int;
     pub fn smt_fnv1a_hash(bytes: *const u8, n: u64) -> u64;

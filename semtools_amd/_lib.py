@@ -48,6 +48,7 @@ EXPORTS = [
     "smt_debug_scan_pairs", "smt_debug_image_tile", "smt_debug_scan_groups", "smt_debug_scan_groups_wide", "smt_debug_scan_groups_deep","smt_debug_nominations",
     "smt_debug_select_groups", "smt_debug_ov_ready", "smt_debug_host_timing",
     "smt_debug_merge_sources", "smt_debug_merge_packed_strided", "smt_debug_combine_status", "smt_debug_select_lists",
+    "smt_debug_scan_lists", "smt_debug_scan_ring",
     "smt_wordpiece_create", "smt_wordpiece_create_utf8", "smt_wordpiece_info", "smt_wordpiece_destroy", "smt_wordpiece_scan_device", "smt_wordpiece_emit_device", "smt_wordpiece_tokenize",
     "smt_unigram_create", "smt_unigram_create_utf8", "smt_unigram_info", "smt_unigram_destroy", "smt_unigram_scan_device", "smt_unigram_emit_device", "smt_unigram_tokenize",
     "smt_unigram_set_long_pieces", "smt_unigram_long_stats", "smt_unigram_set_space_rules", "smt_unigram_set_long_rules",
@@ -316,6 +317,8 @@ def lib():
         L.smt_debug_merge_packed_strided.argtypes = [vp, vp, u64, u32, u32, u32, u32, vp]
         L.smt_debug_combine_status.argtypes = [vp, P(vp), vp, u64, u32, u32, vp]
         L.smt_debug_select_lists.argtypes = [vp, vp, u32, vp, u64, u32, u32, u32, i32, C.c_float, u64, f64, vp, u64, vp, vp, vp, vp, vp]
+        L.smt_debug_scan_lists.argtypes = [vp, vp, u32, u32, vp, u32, vp, u64, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]
+        L.smt_debug_scan_ring.argtypes = [vp, u32, u64, vp]
     except AttributeError:
         pass
     L.smt_sharded_corpus_append_to_file_ex.argtypes = [vp, C.c_char_p, u64, u64, i32]

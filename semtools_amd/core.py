@@ -109,6 +109,13 @@ class Context:
         L.check(L.lib().smt_debug_scan_groups_deep(self._h, v))
         return tuple(int(x) for x in v)
 
+    def debug_scan_ring(self, calls_back, n_keys):
+        """Test hook (smt_debug_scan_ring): the first n_keys keys (uint64) of the list set of the one-query pipeline call made
+        `calls_back` calls ago.  Synchronises; read it before any other scan reuses the scratch."""
+        out = np.empty(int(n_keys), dtype=np.uint64)
+        L.check(L.lib().smt_debug_scan_ring(self._h, int(calls_back), int(n_keys), L.np_ptr(out)))
+        return out
+
     def select_groups(self):
         """by_size: select launches of the one-launch-per-pass route by calls served, n = 0..16 (smt_debug_select_groups; tuning key
         select_group, default 1): 0 counts the launches of absorbed calls, whose answer their leader's launch wrote.  Synchronises."""
@@ -613,6 +620,21 @@ class Corpus:
                                               n_rng, L.np_ptr(t), int(bool(buffered)), L.np_ptr(dist), L.np_ptr(hits), L.np_ptr(counts),
                                               C.byref(route)))
         return dist, hits, counts, int(route.value)
+
+    def debug_scan_lists(self, queries, top_k, ranges=None, cap_keys=None):
+        """Test hook (smt_debug_scan_lists): the block lists the scan stage writes for a synchronous top_k call of 1..8 queries under
+        the current tuning.  Returns (keys uint64 [nq + 1, blocks, k'], the last set the untouched guard; route, see the header).
+        cap_keys: the capacity handed to the library (default: the largest a call can need)."""
+        q = _f32c(queries).reshape(-1, L.DIM)
+        nq = q.shape[0]
+        rng, n_rng = _ranges_arg(ranges)
+        cap = (nq + 1) * 512 * 64 if cap_keys is None else int(cap_keys)
+        out = np.empty(max(cap, 1), dtype=np.uint64)
+        blocks, kp, route = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        L.check(L.lib().smt_debug_scan_lists(self._h, L.np_ptr(q), nq, int(top_k), C.cast(rng, C.c_void_p) if rng is not None else None,
+                                             n_rng, L.np_ptr(out), cap, C.byref(blocks), C.byref(kp), C.byref(route)))
+        b, k = int(blocks.value), int(kp.value)
+        return out[:(nq + 1) * b * k].reshape(nq + 1, b, k).copy(), int(route.value)
 
     def debug_select_lists(self, queries_ptr, nq, lists_ptr, n_lists, kp, k_out, out_rows_ptr, out_dist_ptr, list_stride=0, out_stride=0,
                            ws_threshold=None, row_base=0, f32_err=0.0, overflow_ptr=None, out_counts_ptr=None, out_uncertain_ptr=None,

@@ -142,6 +142,7 @@ struct smt_ctx {
     bool ov_after_timed = false;             // the previous overlapped scan was bracketed by profiling events
     unsigned long long *d_gate = nullptr;    // blocks of overlapped scans that have finished their rows (monotonic)
     uint64_t ov_step = 0;
+    bool ov_lists_live = false;              // the latest K2 call was one of this pipeline: its ring of list sets lies at the head of the scratch (smt_debug_scan_ring)
     uint64_t gate_total = 0;                 // blocks of all overlapped scans launched so far (the counter's value once they are done)
     uint64_t gate_prev_blocks = 0;           // ... and of the latest one
     uint64_t gate_prev_rows = 0;
@@ -351,6 +352,11 @@ struct ScanArgs {
     const struct Delivery *deliver = nullptr;   // the select stage delivers the answers to pinned host memory (below)
 };
 int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a);
+// test hooks (scan_launch.hip; smt_debug_scan_lists, smt_debug_scan_ring): the block lists a synchronous scan writes, and the list set
+// of an earlier call of the one-query pipeline
+int debug_scan_lists(smt_ctx *ctx, const ScanArgs &a, key_t64 *out_keys_host, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp,
+                     uint32_t *out_route);
+int debug_scan_ring(smt_ctx *ctx, uint32_t calls_back, uint64_t n_keys, key_t64 *out_keys_host);
 void corpus_range_sets_drop(smt_corpus *c);   // search.cpp (smt_corpus_destroy)
 // the kept set's table when there is one (built on first use), else `scratch_table` built for this call
 int range_tile_table(smt_ctx *ctx, const ScanArgs &a, uint64_t *scratch_table, const uint64_t **table);
@@ -463,7 +469,8 @@ int launch_group_select(smt_ctx *ctx, const SelectArgs &s, const GroupSelect &gs
 // instruction (measured on positive 256-dim dots: 2 ulp in total over 16 instructions).
 //   K2/K4: 4 FMAs per lane + a reduction tree of 6 levels (wave_sum4: xor 1, xor 2, rotate 4, rotate 8, +-16, +-32; wave_sum: four
 //   DPP levels and two scalar ones) -- the bound below was taken for an 8-step tree: <= 12 roundings of terms whose absolute sum is
-//   <= 1, plus two rsqrt/multiplies: < 1e-6.
+//   <= 1, plus two rsqrt/multiplies: < 1e-6.  MEASURED on every key the scan kernels write (smt_debug_scan_lists,
+//   tests/test_gpu_scan_lists.py, profiles/scan_nomination_errors.json): at most 1.9e-7 over every instantiation a search reaches.
 //   f32 MFMA: 256 products accumulated one by one, each add rounded to nearest: <= 256 * 2^-24 = 1.5e-5.
 constexpr double F32_ERR_SCAN = 4e-6;
 constexpr double F32_ERR_MFMA = 2e-5;

@@ -103,6 +103,7 @@ static int enter_pipeline(smt_ctx *ctx, const ScanArgs &a, ScanPlan &pl)
     if (pl.async && (rc = pl.overlap ? ensure_overlap(ctx) : ensure_async(ctx))) return rc;
     if (!pl.async && (rc = drain_async(ctx))) return rc;
     pl.step = pl.overlap ? ++ctx->ov_step : pl.async ? ++ctx->async_step : 0;
+    ctx->ov_lists_live = pl.overlap;   // (any other scan carves the scratch up its own way: smt_debug_scan_ring)
     // (scan_overlap: scans of consecutive calls run at the same time, and their grids differ with the corpus -- the two buffers get a
     // fixed place, the largest one-query list set, or a small call's buffer 1 would lie inside a large call's buffer 0)
     const size_t list_bytes = pl.overlap ? (size_t)SEL_MAX_LISTS * 64 * sizeof(key_t64)
@@ -353,12 +354,42 @@ static SelectArgs select_args(const ScanArgs &a, const ScanPlan &pl)
     return s;
 }
 
-int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
+// The two halves of a call's scan that launch_scan_topk and the test hook debug_scan_lists share, so that the hook cannot drift from
+// production.  scan_begin: the argument checks, the plan, the pipeline step and the list area.
+static int scan_begin(smt_ctx *ctx, const ScanArgs &a, ScanPlan &pl)
 {
     SMT_REQUIRE(a.k_out >= 1 && a.k_out <= SCAN_MAX_K, "top_k for the scan path must be in [1, 56]");
     SMT_REQUIRE(a.rows < 0xFFFFFFFFull, "a shard holds fewer than 2^32-1 rows");
-    ScanPlan pl = plan_scan(ctx, a);
-    int rc = enter_pipeline(ctx, a, pl);
+    pl = plan_scan(ctx, a);
+    return enter_pipeline(ctx, a, pl);
+}
+
+// scan_passes: the chunk table of a filtered call, then one pass per up to four queries.  `route` (the hook's; nullptr in production)
+// receives what was launched: SMT_SCAN_ROUTE_* of semtools_hip.h.
+static int scan_passes(smt_ctx *ctx, const ScanArgs &a, const ScanPlan &pl, uint32_t *route)
+{
+    int rc = SMT_OK;
+    const uint64_t *chunk_table = pl.table;
+    if (pl.filtered && (rc = range_chunk_table(ctx, a, pl.table, &chunk_table))) return rc;
+    if (route) *route = (uint32_t)pl.U | (pl.nt ? 0x10u : 0u) | (pl.filtered ? 0x20u : 0u) | (uint32_t)pl.threads << 8;
+    int pass = 0;
+    for (uint32_t q0 = 0; q0 < a.nq; ++pass) {
+        // (three queries ride in the four-query kernel: with the four rows of a chunk reduced together a pass costs 1.06 x / 1.4 x one
+        // query's for two / four queries -- 172 / 230 us at 1 M rows -- against 335 us for a pass of two and a pass of one)
+        const uint32_t left = a.nq - q0;
+        const int slots = left >= 3 ? 4 : (int)left;
+        ScanParams p = scan_params(ctx, a, pl, chunk_table, q0, std::min(left, 4u));
+        if ((rc = steal_setup(ctx, pl, p)) || (rc = launch_scan_pass(ctx, pl, p, slots))) return rc;
+        if (route && pass < 3) *route |= (p.steal_ctr ? 0x40u : 0u) | (uint32_t)slots << (20 + 4 * pass);
+        q0 += p.nq_active;
+    }
+    return SMT_OK;
+}
+
+int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
+{
+    ScanPlan pl;
+    int rc = scan_begin(ctx, a, pl);
     if (rc != SMT_OK) return rc;
     HostTimer whole(ctx);
     if (pl.overlap && (rc = overlap_prologue(ctx, pl))) return rc;
@@ -379,17 +410,7 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
     HostTimer ht(ctx);
 
     prof_begin_on(ctx, "scan", pl.st);
-    const uint64_t *chunk_table = pl.table;
-    if (pl.filtered && (rc = range_chunk_table(ctx, a, pl.table, &chunk_table))) return rc;
-    for (uint32_t q0 = 0; q0 < a.nq;) {
-        // (three queries ride in the four-query kernel: with the four rows of a chunk reduced together a pass costs 1.06 x / 1.4 x one
-        // query's for two / four queries -- 172 / 230 us at 1 M rows -- against 335 us for a pass of two and a pass of one)
-        const uint32_t left = a.nq - q0;
-        const int slots = left >= 3 ? 4 : (int)left;
-        ScanParams p = scan_params(ctx, a, pl, chunk_table, q0, std::min(left, 4u));
-        if ((rc = steal_setup(ctx, pl, p)) || (rc = launch_scan_pass(ctx, pl, p, slots))) return rc;
-        q0 += p.nq_active;
-    }
+    if ((rc = scan_passes(ctx, a, pl, nullptr))) return rc;
     prof_end_on(ctx, "scan", pl.st);
 
     if (pl.overlap) {
@@ -426,6 +447,46 @@ int launch_scan_topk(smt_ctx *ctx, const ScanArgs &a)
         if (whole.on) ++ctx->host_ns_calls;
     }
     return rc;
+}
+
+// ------------------------------------------------------------------ test hooks (smt_debug_scan_lists, smt_debug_scan_ring)
+// The synchronous scan of `a` up to the select and no further, through scan_begin and scan_passes as launch_scan_topk runs them.  The
+// list area of nq + 1 query sets is preset to the byte 0x5A in front of the first pass and copied out whole behind the last: the extra
+// set is a guard no pass may touch (a pass of three queries rides in four slots).
+int debug_scan_lists(smt_ctx *ctx, const ScanArgs &a, key_t64 *out_keys_host, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp,
+                     uint32_t *out_route)
+{
+    SMT_REQUIRE(!a.allow_async && !a.allow_overlap, "debug scan lists: the synchronous path");
+    ScanPlan pl;
+    int rc = scan_begin(ctx, a, pl);
+    if (rc != SMT_OK) return rc;
+    *out_blocks = (uint32_t)pl.blocks;
+    *out_kp = pl.kp;
+    const size_t n_keys = (size_t)(a.nq + 1) * pl.blocks * pl.kp;   // (inside the two list sets of enter_pipeline, in front of the chunk table)
+    SMT_REQUIRE(out_cap_keys >= n_keys, "debug scan lists: the output holds fewer than (nq + 1) x blocks x k' keys");
+    SMT_HIP_CHECK(hipMemsetAsync(pl.lists, 0x5A, n_keys * sizeof(key_t64), ctx->stream));
+    if ((rc = scan_passes(ctx, a, pl, out_route))) return rc;
+    SMT_HIP_CHECK(hipMemcpyAsync(out_keys_host, pl.lists, n_keys * sizeof(key_t64), hipMemcpyDeviceToHost, ctx->stream));
+    SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return SMT_OK;
+}
+
+// The first n_keys keys of the list set of the one-query pipeline call made calls_back calls ago: set (ov_step - calls_back) & 31 at the
+// fixed set stride of enter_pipeline.  Waits for the pipeline first.
+int debug_scan_ring(smt_ctx *ctx, uint32_t calls_back, uint64_t n_keys, key_t64 *out_keys_host)
+{
+    const size_t set_keys = (size_t)SEL_MAX_LISTS * 64, n_sets = 2 * DEEP_MAX;
+    SMT_REQUIRE(calls_back < n_sets, "debug scan ring: the ring holds the last 32 calls");
+    SMT_REQUIRE(n_keys <= set_keys, "debug scan ring: a list set holds at most 512 x 64 keys");
+    int rc = drain_async(ctx);
+    if (rc != SMT_OK) return rc;
+    SMT_REQUIRE(ctx->ov_lists_live && ctx->async_overlap, "debug scan ring: the last scan was not a call of the overlap pipeline");
+    SMT_REQUIRE(ctx->ov_step > calls_back, "debug scan ring: no such call");
+    SMT_REQUIRE(ctx->d_scratch && ctx->scratch_bytes >= n_sets * set_keys * sizeof(key_t64), "debug scan ring: no list ring");
+    if (n_keys == 0) return SMT_OK;
+    const key_t64 *set = reinterpret_cast<const key_t64 *>(ctx->d_scratch) + ((ctx->ov_step - calls_back) & (n_sets - 1)) * set_keys;
+    SMT_HIP_CHECK(hipMemcpy(out_keys_host, set, n_keys * sizeof(key_t64), hipMemcpyDeviceToHost));
+    return SMT_OK;
 }
 
 }  // namespace smt

@@ -1151,4 +1151,47 @@ try {
     return launch_select(ctx, s);
 } catch (...) { return smt::api_catch(); }
 
+// Test hook: the block lists of the scan stage.  The ScanArgs of a real synchronous top_k call of nq host queries over the corpus --
+// ranges through the range plan, as smt_debug_nominations -- handed to debug_scan_lists (scan_launch.hip), which runs the code
+// launch_scan_topk runs up to the select.
+int smt_debug_scan_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                         uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp, uint32_t *out_route)
+try {
+    SMT_REQUIRE(corpus && queries && out_keys && out_blocks && out_kp && out_route, "null argument");
+    SMT_REQUIRE(n_ranges == 0 || ranges != nullptr, "ranges");
+    SMT_REQUIRE(nq >= 1 && nq <= 8, "debug scan lists: 1..8 queries");
+    SMT_REQUIRE(top_k >= 1 && top_k <= SCAN_MAX_K, "debug scan lists: top_k in [1, 56]");
+    smt_ctx *ctx = corpus->ctx;
+    int rc = bind_device(ctx, true);
+    if (rc) return rc;
+    *out_blocks = 0; *out_kp = 0; *out_route = 0;
+    RangePlan plan;
+    plan.n_virtual = corpus->rows;
+    if (n_ranges && (rc = range_plan_find(corpus, ranges, n_ranges, plan))) return rc;
+    SMT_REQUIRE(plan.n_virtual >= 1, "debug scan lists: no row to scan");
+    if ((rc = range_plan_finish(corpus, plan))) return rc;
+    const size_t q_bytes = (size_t)nq * SMT_DIM * sizeof(float);
+    if ((rc = ensure_stage(ctx, q_bytes + plan.table_bytes() + 64))) return rc;
+    char *stage = reinterpret_cast<char *>(ctx->d_stage);
+    SMT_HIP_CHECK(hipMemcpyAsync(stage, queries, q_bytes, hipMemcpyHostToDevice, ctx->stream));
+    plan.bind(stage + q_bytes);
+    if (plan.upload_bytes()) {
+        SMT_HIP_CHECK(hipMemcpyAsync(const_cast<smt_range *>(plan.d_r), plan.rr.data(), plan.r_bytes(), hipMemcpyHostToDevice, ctx->stream));
+        SMT_HIP_CHECK(hipMemcpyAsync(const_cast<uint64_t *>(plan.d_p), plan.prefixes.data(), plan.prefixes.size() * sizeof(uint64_t),
+                                     hipMemcpyHostToDevice, ctx->stream));
+    }
+    ScanArgs a = scan_args(corpus, reinterpret_cast<const float *>(stage), nq, top_k, 0);
+    plan.apply(a);
+    return debug_scan_lists(ctx, a, reinterpret_cast<key_t64 *>(out_keys), out_cap_keys, out_blocks, out_kp, out_route);
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_scan_ring(smt_ctx *ctx, uint32_t calls_back, uint64_t n_keys, uint64_t *out_keys)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    SMT_REQUIRE(n_keys == 0 || out_keys != nullptr, "null output");
+    if ((rc = bind_device(ctx, false))) return rc;
+    return debug_scan_ring(ctx, calls_back, n_keys, reinterpret_cast<key_t64 *>(out_keys));
+} catch (...) { return smt::api_catch(); }
+
 }  // extern "C"
