@@ -374,6 +374,72 @@ int smt_unigram_tokenize(smt_unigram *tok, const char *text, const uint64_t *lin
                          uint32_t keep_bytes, uint32_t max_tokens, int drop_unk, uint32_t *ids_out, uint64_t ids_cap,
                          uint64_t *offsets_out, uint8_t *flags_out);
 
+/* -------------------------------------------------------------- lower-casing
+ * The lines of --ignore-case (reference src/search/mod.rs:63-67: every line through str::to_lowercase before it is embedded) lowered
+ * on the device (lower_kernels.hip, DESIGN 4.9 "Lower-casing"), so that they can go on into a device tokenizer without a host pass.
+ * Line i of the output is byte for byte what the host layer's to_lowercase (smt_host_to_lowercase) returns for line i ALONE:
+ *   ASCII A-Z get + 32; every other ASCII byte, NUL included, stays.  ASCII is fixed: the tables state code points >= U+0080 only,
+ *     the ASCII letters count as cased, and ' . : ^ ` as case-ignorable.
+ *   A code point cp inside a run [run_first, run_last] becomes cp + run_delta when (cp - run_first) % run_stride == 0, else itself.
+ *   A multi entry (multi_cp -> multi_n code points multi_to[3 * i ..]) is expanded; it goes before the runs.
+ *   final_sigma != 0: U+03A3 becomes U+03C2 when it is preceded by a cased code point and not followed by one, case-ignorable code
+ *     points skipped on both sides (a code point in both sets is skipped), and U+03C3 otherwise.  The look never leaves the line: the
+ *     previous line's last letter is no context, even with no separator between the lines.  final_sigma == 0: U+03A3 is a code point
+ *     like any other.
+ *   A code point in no table stays.
+ * Byte lengths change both ways (U+0130 2 -> 3, U+023A 2 -> 3, U+212A 3 -> 1, U+212B, U+2126, U+1E9E 3 -> 2); a line of n bytes yields
+ * at most n + n / 2, which smt_lower_tables_check holds every table to.
+ * smt_lower_tables_check (host only, needs no device) returns SMT_E_INVALID for: ranges or runs out of order or overlapping; last <
+ * first; stride 0; a delta that leaves [0, U+10FFFF] or lands on a surrogate; a multi entry with n outside 1 .. 3, with an invalid
+ * target (above U+10FFFF, a surrogate), or out of order; a multi code point that also lies in a run; any entry below U+0080; a mapping
+ * that grows a code point by more than half its bytes (two bytes to four, a multi entry likewise); more entries than the device form
+ * holds in LDS (256 runs, 8 multi entries, 192 cased and 512 case-ignorable ranges).  All arrays sorted by `first`; everything is
+ * copied by smt_lower_create. */
+typedef struct smt_lower smt_lower;
+typedef struct smt_lower_tables {
+    const uint32_t *run_first; /* [n_runs] */
+    const uint32_t *run_last;
+    const int32_t *run_delta;
+    const uint32_t *run_stride;
+    uint64_t n_runs;
+    const uint32_t *multi_cp; /* [n_multi] */
+    const uint32_t *multi_n;
+    const uint32_t *multi_to; /* [n_multi * 3] */
+    uint64_t n_multi;
+    const uint32_t *cased_first; /* [n_cased] */
+    const uint32_t *cased_last;
+    uint64_t n_cased;
+    const uint32_t *ignorable_first; /* [n_ignorable] */
+    const uint32_t *ignorable_last;
+    uint64_t n_ignorable;
+    uint32_t final_sigma; /* != 0: U+03A3 follows the Final_Sigma rule */
+} smt_lower_tables;
+int smt_lower_tables_check(const smt_lower_tables *t /* NULL: the library's own tables, those of smt_lower_create(ctx, NULL, ..) */);
+/* t == NULL: Rust's str::to_lowercase, from the arrays the host layer's to_lowercase reads (Unicode 13), final_sigma on.  Otherwise
+ * the caller's tables, refused with SMT_E_INVALID before anything is uploaded when smt_lower_tables_check refuses them. */
+int smt_lower_create(smt_ctx *ctx, const smt_lower_tables *t, smt_lower **out);
+void smt_lower_destroy(smt_lower *h);
+/* Lower n_lines lines of text_dev.  The line list follows the rule of smt_wordpiece_scan_device: line i is [line_begin[i],
+ * line_begin[i] + line_len[i]), the lines lie in line order and do not overlap, gaps are fine; the device form trusts the list -- one
+ * that breaks the rule gives unspecified bytes, but no access outside [0, text_bytes) or [0, out_cap).
+ * The lowered lines stand back to back in out_text_dev: out_begin[0] = 0, out_begin[i + 1] = out_begin[i] + out_len[i], and
+ * out_begin[n_lines] is the total.  Bytes in gaps are neither read as context nor written; nothing at or beyond out_begin[n_lines] is
+ * written.  out_cap >= text_bytes + text_bytes / 2 always suffices; less is SMT_E_INVALID before anything is enqueued.
+ * The decode is the strict one of the UTF-8 tokenizers.  A line that holds ill-formed UTF-8 -- a lone continuation byte, a sequence cut
+ * by the line's end, an overlong form, a surrogate, a value above U+10FFFF, 0xC0, 0xC1, 0xF5 .. 0xFF -- is FLAGGED: flags_dev[i] != 0,
+ * out_len[i] = line_len[i], its bytes copied unchanged, for the caller to lower elsewhere (to_lowercase of the host layer passes such
+ * bytes through one by one, which the device does not imitate).  *n_flagged_dev = flagged lines.  Ill-formed input ends in a flag,
+ * never in a read outside the line.
+ * The output depends on the input alone.  Enqueued on the context's stream; does not wait (but for the stream when an internal
+ * buffer has to grow). */
+int smt_lower_device(smt_lower *h, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev,
+                     const uint32_t *line_len_dev, uint64_t n_lines, uint8_t *out_text_dev, uint64_t out_cap,
+                     uint64_t *out_begin_dev /* [n_lines + 1] */, uint32_t *out_len_dev, uint8_t *flags_dev, uint32_t *n_flagged_dev);
+/* Host convenience (tests, small callers): upload, lower, download.  The text's end is taken as the largest line end; a line list
+ * out of order or overlapping is SMT_E_INVALID, and so is out_cap below text_bytes + text_bytes / 2.  flags_out may be NULL. */
+int smt_lower_lines(smt_lower *h, const char *text, const uint64_t *line_begin, const uint32_t *line_len, uint64_t n_lines, char *out_text,
+              uint64_t out_cap, uint64_t *out_begin /* [n_lines + 1] */, uint32_t *out_len, uint8_t *flags_out);
+
 /* ------------------------------------------------------------------- corpus
  * Replaces `Document::embeddings: Vec<Vec<f32>>` (src/search/mod.rs:18-22)
  * and the vector half of the workspace store (line_embeddings.qdrant,

@@ -57,6 +57,10 @@ void smt_host_model_destroy(smt_host_model *model);
 /* encode_with_args(texts, Some(max_length) / None when 0, batch 16384) -> out [n x 256] */
 int smt_host_encode(smt_host_model *model, const char *const *texts, uint64_t n, uint32_t max_length,
                     float *out);
+/* the rows of smt_host_to_lowercase(texts[i]): what an ignore_case search embeds for a line (src/search/mod.rs:63-67).  The texts
+ * are lowered inside the call -- on the device where smt_host_model_set_device_lower applies, else on the host; same rows */
+int smt_host_encode_lowered(smt_host_model *model, const char *const *texts, uint64_t n, uint32_t max_length,
+                            float *out);
 
 /* max_distance: NaN = None.  json != 0: SearchOutput JSON (to_string_pretty) instead of text. */
 int smt_host_search_files(smt_host_model *model, const char *query, const char *const *files, uint64_t n_files,
@@ -172,10 +176,19 @@ int smt_host_tokenizer_to_device_unigram_utf8(smt_host_tokenizer *tok, smt_ctx *
  * (smt_unigram_set_long_pieces) instead of flagging their lines: a URL, a hash, text written without spaces.  A handle with space
  * rules -- an XLM-R-style file behind a Precompiled normalizer -- is covered too (smt_unigram_set_long_rules).  Same rows and ids;
  * ignored for WordPiece and while the route is off.
- * smt_host_debug_device_tokenized (test hook): lines of this model tokenized on the device so far. */
+ * smt_host_debug_device_tokenized (test hook): lines of this model tokenized on the device so far.
+ * smt_host_model_set_device_lower (SEMTOOLS_DEVICE_LOWER=0 at creation turns it off): ON by default.  It only matters while the
+ * device tokenizer route is on and a call lowers (ignore_case): the batch's original lines are then packed and lowered on the GPU
+ * between the upload and the tokenizer (smt_lower_device: the bytes of to_lowercase), and the few lines the route flags are lowered
+ * by the host.  With it off, each batch is lowered on the host, on up to eight threads, by the thread that packs it while the previous
+ * batch runs on the GPU.  Without the route every batch is lowered on the tokenizer's threads.  Rows, search output and the
+ * workspace's cached ids are the same in all three cases; queries are always lowered on the host.
+ * smt_host_debug_device_lowered (test hook): lines of this model lowered on the device so far. */
 int smt_host_model_set_device_tokenizer(smt_host_model *model, int on);
 int smt_host_model_set_device_tokenizer_long(smt_host_model *model, int on);
 int smt_host_debug_device_tokenized(smt_host_model *model, uint64_t *lines);
+int smt_host_model_set_device_lower(smt_host_model *model, int on);
+int smt_host_debug_device_lowered(smt_host_model *model, uint64_t *lines);
 /* Wall-clock phases of this process so far as one JSON object (malloc'd): model_load, read_tokenize_embed_files,
  * embed_query, store_open_corpus_load, change_detection, embed_and_persist_changed_files, scan_select, ... -- what the
  * CLI prints to stderr under SEMTOOLS_TIMING=1. */

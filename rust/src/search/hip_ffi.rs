@@ -8,7 +8,7 @@
 use std::os::raw::{c_char, c_int, c_void};
 
 macro_rules! opaque { ($($name:ident),*) => { $( #[repr(C)] pub struct $name { _private: [u8; 0] } )* } }
-opaque!(SmtCtx, SmtModel, SmtCorpus, SmtIvfpq, SmtGroup, SmtShardedCorpus, SmtShardedIvfpq, SmtShardedModel, SmtWordpiece, SmtUnigram);
+opaque!(SmtCtx, SmtModel, SmtCorpus, SmtIvfpq, SmtGroup, SmtShardedCorpus, SmtShardedIvfpq, SmtShardedModel, SmtWordpiece, SmtUnigram, SmtLower);
 
 /// half-open range of corpus rows [begin, end)
 #[repr(C)]
@@ -78,6 +78,28 @@ pub struct SmtUnigramParams {
     pub added_pool: *const c_char,
     pub added_off: *const u32,
     pub n_added: u32,
+}
+
+/// the lower-casing tables for the device (smt_lower_create copies everything; a null pointer there means Rust's str::to_lowercase)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SmtLowerTables {
+    pub run_first: *const u32,
+    pub run_last: *const u32,
+    pub run_delta: *const i32,
+    pub run_stride: *const u32,
+    pub n_runs: u64,
+    pub multi_cp: *const u32,
+    pub multi_n: *const u32,
+    pub multi_to: *const u32,
+    pub n_multi: u64,
+    pub cased_first: *const u32,
+    pub cased_last: *const u32,
+    pub n_cased: u64,
+    pub ignorable_first: *const u32,
+    pub ignorable_last: *const u32,
+    pub n_ignorable: u64,
+    pub final_sigma: u32,
 }
 
 pub const SMT_OK: c_int = 0;
@@ -364,6 +386,35 @@ extern "C" {
         ids_out: *mut u32,
         ids_cap: u64,
         offsets_out: *mut u64,
+        flags_out: *mut u8,
+    ) -> c_int;
+    pub fn smt_lower_tables_check(t: *const SmtLowerTables) -> c_int;
+    pub fn smt_lower_create(ctx: *mut SmtCtx, t: *const SmtLowerTables, out: *mut *mut SmtLower) -> c_int;
+    pub fn smt_lower_destroy(h: *mut SmtLower);
+    pub fn smt_lower_device(
+        h: *mut SmtLower,
+        text_dev: *const u8,
+        text_bytes: u64,
+        line_begin_dev: *const u64,
+        line_len_dev: *const u32,
+        n_lines: u64,
+        out_text_dev: *mut u8,
+        out_cap: u64,
+        out_begin_dev: *mut u64,
+        out_len_dev: *mut u32,
+        flags_dev: *mut u8,
+        n_flagged_dev: *mut u32,
+    ) -> c_int;
+    pub fn smt_lower_lines(
+        h: *mut SmtLower,
+        text: *const c_char,
+        line_begin: *const u64,
+        line_len: *const u32,
+        n_lines: u64,
+        out_text: *mut c_char,
+        out_cap: u64,
+        out_begin: *mut u64,
+        out_len: *mut u32,
         flags_out: *mut u8,
     ) -> c_int;
     pub fn smt_corpus_create(ctx: *mut SmtCtx, D: u32, capacity_rows: u64, out: *mut *mut SmtCorpus) -> c_int;

@@ -52,6 +52,7 @@ EXPORTS = [
     "smt_wordpiece_create", "smt_wordpiece_create_utf8", "smt_wordpiece_info", "smt_wordpiece_destroy", "smt_wordpiece_scan_device", "smt_wordpiece_emit_device", "smt_wordpiece_tokenize",
     "smt_unigram_create", "smt_unigram_create_utf8", "smt_unigram_info", "smt_unigram_destroy", "smt_unigram_scan_device", "smt_unigram_emit_device", "smt_unigram_tokenize",
     "smt_unigram_set_long_pieces", "smt_unigram_long_stats", "smt_unigram_set_space_rules", "smt_unigram_set_long_rules",
+    "smt_lower_tables_check", "smt_lower_create", "smt_lower_destroy", "smt_lower_device", "smt_lower_lines",
 ]
 WP_NORMALIZER, WP_CLEAN_TEXT, WP_LOWERCASE = 1, 2, 4
 WP_CP_ORDINARY, WP_CP_SPACE, WP_CP_ALONE, WP_CP_DROPPED, WP_CP_FLAG = 0, 1, 2, 3, 4
@@ -115,6 +116,7 @@ HOST_EXPORTS = [
     "smt_host_workspace_use_group", "smt_host_workspace_status_group", "smt_host_workspace_prune_group",
     "smt_host_model_table_info", "smt_host_model_token_info", "smt_host_tokenizer_to_device", "smt_host_tokenizer_to_device_unigram", "smt_host_tokenizer_to_device_utf8", "smt_host_tokenizer_to_device_unigram_utf8", "smt_host_tokenizer_unigram_space_rules",
     "smt_host_model_set_device_tokenizer", "smt_host_debug_device_tokenized", "smt_host_model_set_device_tokenizer_long",
+    "smt_host_model_set_device_lower", "smt_host_debug_device_lowered", "smt_host_encode_lowered",
 ]
 TOKENIZE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
                           C.POINTER(C.c_uint64))
@@ -145,6 +147,13 @@ class SmtUnigramParams(C.Structure):
                 ("scores", C.c_void_p), ("unk_score", C.c_double), ("unk_id", C.c_int64), ("replacement", C.c_char_p),
                 ("replacement_len", C.c_uint32), ("prepend", C.c_uint32), ("byte_map", C.c_void_p), ("added_pool", C.c_char_p),
                 ("added_off", C.c_void_p), ("n_added", C.c_uint32)]
+
+
+class SmtLowerTables(C.Structure):
+    _fields_ = [("run_first", C.c_void_p), ("run_last", C.c_void_p), ("run_delta", C.c_void_p), ("run_stride", C.c_void_p), ("n_runs", C.c_uint64),
+                ("multi_cp", C.c_void_p), ("multi_n", C.c_void_p), ("multi_to", C.c_void_p), ("n_multi", C.c_uint64),
+                ("cased_first", C.c_void_p), ("cased_last", C.c_void_p), ("n_cased", C.c_uint64),
+                ("ignorable_first", C.c_void_p), ("ignorable_last", C.c_void_p), ("n_ignorable", C.c_uint64), ("final_sigma", C.c_uint32)]
 
 
 class SmtError(RuntimeError):
@@ -233,6 +242,12 @@ def lib():
     L.smt_unigram_set_space_rules.argtypes = [vp, i32, i32]
     L.smt_unigram_set_long_rules.argtypes = [vp, i32]
     L.smt_unigram_long_stats.argtypes = [vp, P(u64), P(u64)]
+    L.smt_lower_tables_check.argtypes = [P(SmtLowerTables)]
+    L.smt_lower_create.argtypes = [vp, P(SmtLowerTables), P(vp)]
+    L.smt_lower_destroy.argtypes = [vp]
+    L.smt_lower_destroy.restype = None
+    L.smt_lower_device.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp, vp]
+    L.smt_lower_lines.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, vp, vp]
     L.smt_corpus_create.argtypes = [vp, u32, u64, P(vp)]
     L.smt_corpus_from_device.argtypes = [vp, vp, u64, u32, P(vp)]
     L.smt_corpus_destroy.argtypes = [vp]
@@ -385,6 +400,7 @@ def lib():
     L.smt_host_model_destroy.argtypes = [vp]
     L.smt_host_model_destroy.restype = None
     L.smt_host_encode.argtypes = [vp, cpp, u64, u32, vp]
+    L.smt_host_encode_lowered.argtypes = [vp, cpp, u64, u32, vp]
     L.smt_host_search_files.argtypes = [vp, C.c_char_p, cpp, u64, u64, u64, f64, i32, i32, i32, P(vp)]
     L.smt_host_search_content.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, u64, u64, f64, i32, i32, i32, P(vp)]
     L.smt_host_search_workspace.argtypes = [vp, C.c_char_p, cpp, u64, u64, u64, f64, i32, C.c_char_p, i32, i32, P(vp)]
@@ -413,6 +429,8 @@ def lib():
     L.smt_host_model_set_device_tokenizer.argtypes = [vp, i32]
     L.smt_host_model_set_device_tokenizer_long.argtypes = [vp, i32]
     L.smt_host_debug_device_tokenized.argtypes = [vp, P(u64)]
+    L.smt_host_model_set_device_lower.argtypes = [vp, i32]
+    L.smt_host_debug_device_lowered.argtypes = [vp, P(u64)]
     L.smt_host_timing_json.argtypes = []
     L.smt_host_timing_json.restype = vp
     L.smt_host_format_float.argtypes = [f64, i32]

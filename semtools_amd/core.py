@@ -506,6 +506,90 @@ class Unigram(_DeviceTokenizer):
         return int(pieces.value), int(raw.value)
 
 
+class Lower:
+    """Lower-casing of packed UTF-8 lines on the device (smt_lower): line by line the bytes of the host layer's to_lowercase, lines
+    with ill-formed UTF-8 flagged and copied unchanged.
+
+    Lower(ctx) uses the library's own tables (Rust's str::to_lowercase).  Lower(ctx, tables=dict(runs=[(first, last, delta, stride)],
+    multi=[(cp, [to, ..])] or [(cp, n, [to, ..])], cased=[(first, last)], ignorable=[(first, last)], final_sigma=bool)) states them:
+    code points >= U+0080, every list sorted (smt_lower_tables_check).  Calls smt_lower_{create,device,lines,destroy}."""
+
+    def __init__(self, ctx, tables=None):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        if tables is None:
+            L.check(L.lib().smt_lower_create(ctx._h, None, C.byref(self._h)))
+            return
+        st, _keep = self.tables_struct(tables)
+        L.check(L.lib().smt_lower_create(ctx._h, C.byref(st), C.byref(self._h)))
+
+    @staticmethod
+    def tables_struct(tables):
+        """(SmtLowerTables, the arrays it points into) of a tables dict"""
+        runs = list(tables.get("runs", ()))
+        multi = [(m[0], len(m[1]), m[1]) if len(m) == 2 else tuple(m) for m in tables.get("multi", ())]
+        cased = list(tables.get("cased", ()))
+        ign = list(tables.get("ignorable", ()))
+        to = np.zeros(max(len(multi), 1) * 3, dtype=np.uint32)
+        for i, (_, _, t) in enumerate(multi):
+            to[i * 3:i * 3 + min(len(t), 3)] = list(t)[:3]
+        keep = [np.array([r[0] for r in runs], dtype=np.uint32), np.array([r[1] for r in runs], dtype=np.uint32),
+                np.array([r[2] for r in runs], dtype=np.int32), np.array([r[3] for r in runs], dtype=np.uint32),
+                np.array([m[0] for m in multi], dtype=np.uint32), np.array([m[1] for m in multi], dtype=np.uint32), to,
+                np.array([r[0] for r in cased], dtype=np.uint32), np.array([r[1] for r in cased], dtype=np.uint32),
+                np.array([r[0] for r in ign], dtype=np.uint32), np.array([r[1] for r in ign], dtype=np.uint32)]
+        p = [L.np_ptr(a) for a in keep]
+        st = L.SmtLowerTables(p[0], p[1], p[2], p[3], len(runs), p[4], p[5], p[6], len(multi), p[7], p[8], len(cased), p[9], p[10], len(ign),
+                              1 if tables.get("final_sigma", False) else 0)
+        return st, keep
+
+    @staticmethod
+    def check_tables(tables):
+        """smt_lower_tables_check on a tables dict: SMT_OK or SMT_E_INVALID (smt_last_error says why); needs no device"""
+        st, _keep = Lower.tables_struct(tables)
+        return L.lib().smt_lower_tables_check(C.byref(st))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            L.lib().smt_lower_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # best effort
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    pack = staticmethod(_DeviceTokenizer.pack)
+
+    def lower(self, lines=None, text=None, line_begin=None, line_len=None, out_cap=None):
+        """-> (out text bytes, out_begin uint64 [n + 1], out_len uint32 [n], flags uint8 [n]) through smt_lower_lines.  `lines` are packed back
+        to back; or give text / line_begin / line_len.  out_cap defaults to the bound, 1.5 x the text up to the last line's end."""
+        if lines is not None:
+            text, line_begin, line_len = self.pack(lines)
+        line_begin = np.ascontiguousarray(line_begin, dtype=np.uint64)
+        line_len = np.ascontiguousarray(line_len, dtype=np.uint32)
+        n = len(line_len)
+        text_bytes = int(line_begin[-1]) + int(line_len[-1]) if n else 0
+        if out_cap is None:
+            out_cap = text_bytes + text_bytes // 2
+        out = np.zeros(max(int(out_cap), 1), dtype=np.uint8)
+        out_begin = np.zeros(n + 1, dtype=np.uint64)
+        out_len = np.zeros(max(n, 1), dtype=np.uint32)
+        flags = np.zeros(max(n, 1), dtype=np.uint8)
+        buf = C.create_string_buffer(bytes(text), max(len(text), 1))
+        L.check(L.lib().smt_lower_lines(self._h, C.cast(buf, C.c_void_p), L.np_ptr(line_begin), L.np_ptr(line_len), n, L.np_ptr(out), int(out_cap),
+                                  L.np_ptr(out_begin), L.np_ptr(out_len), L.np_ptr(flags)))
+        return out[:int(out_begin[n])].tobytes(), out_begin, out_len[:n].copy(), flags[:n].copy()
+
+    def lower_device(self, text_ptr, text_bytes, line_begin_ptr, line_len_ptr, n_lines, out_text_ptr, out_cap, out_begin_ptr, out_len_ptr,
+                     flags_ptr, n_flagged_ptr):
+        """smt_lower_device on raw device pointers (ints); enqueued on the context's stream"""
+        vp = C.c_void_p
+        L.check(L.lib().smt_lower_device(self._h, vp(text_ptr), int(text_bytes), vp(line_begin_ptr), vp(line_len_ptr), int(n_lines),
+                                         vp(out_text_ptr), int(out_cap), vp(out_begin_ptr), vp(out_len_ptr), vp(flags_ptr), vp(n_flagged_ptr)))
+
+
 class Corpus:
     """Row-major f32 [rows x 256] matrix resident in HBM (smt_corpus)."""
 

@@ -2,6 +2,8 @@
 // pinned buffer, upload, tokenize on the device (tok_scan_device of tokenize_frame.h, whichever family the handle is), tokenize the lines
 // the kernel flags with the host tokenizer, splice them in (tok_emit_device) and pool the device CSR with K1 -- the token ids never visit the host
 // unless a caller wants them (the workspace's cached ids).  One-rank groups only; StaticModel decides when the route applies.
+// A batch of --ignore-case is packed as it is and lowered on the device between the upload and pass 1 (smt_lower_device, DESIGN.md 4.9
+// "Lower-casing"): pass 1 then reads the lowered lines and their line list in place of the uploaded ones.
 #include <chrono>
 
 #include "../common.h"
@@ -17,6 +19,8 @@ struct DeviceTokenRoute {
     smt_group *group = nullptr;
     smt_ctx *ctx = nullptr;
     smt::TokHandle *tok = nullptr;   // an smt_wordpiece or an smt_unigram
+    smt_lower *lower = nullptr;      // the library's own tables (to_lowercase's), made by the first call that lowers (device_route_can_lower)
+    bool lower_tried = false;
     struct Slot {   // one batch packed for upload: line_begin u64 [n] | line_len u32 [n] | text
         char *pin = nullptr;
         size_t pin_bytes = 0;
@@ -25,7 +29,7 @@ struct DeviceTokenRoute {
     } slot[2];
     void *d_main = nullptr, *d_ids = nullptr, *d_patch = nullptr, *d_rows = nullptr;
     size_t main_bytes = 0, ids_bytes = 0, patch_bytes = 0, rows_bytes = 0;
-    uint64_t lines_done = 0;
+    uint64_t lines_done = 0, lines_lowered = 0;
 };
 
 namespace {
@@ -118,6 +122,7 @@ void device_route_destroy(DeviceTokenRoute *r)
 {
     if (!r) return;
     smt::tok_destroy(r->tok);   // (waits for the stream)
+    smt_lower_destroy(r->lower);
     (void)hipSetDevice(r->ctx->device);
     for (auto &s : r->slot) if (s.pin) (void)hipHostFree(s.pin);
     for (void *p : {r->d_main, r->d_ids, r->d_patch, r->d_rows}) if (p) (void)hipFree(p);
@@ -125,8 +130,19 @@ void device_route_destroy(DeviceTokenRoute *r)
 }
 
 uint64_t device_route_lines(const DeviceTokenRoute *r) { return r ? r->lines_done : 0; }
+uint64_t device_route_lowered(const DeviceTokenRoute *r) { return r ? r->lines_lowered : 0; }
 
-bool device_route_pack(DeviceTokenRoute *r, int which, const std::string_view *sentences, size_t n)
+bool device_route_can_lower(DeviceTokenRoute *r)
+{
+    if (!r) return false;
+    if (!r->lower_tried) {
+        r->lower_tried = true;
+        if (smt_lower_create(r->ctx, nullptr, &r->lower) != SMT_OK) r->lower = nullptr;   // (the caller lowers on the host)
+    }
+    return r->lower != nullptr;
+}
+
+bool device_route_pack(DeviceTokenRoute *r, int which, const std::string_view *sentences, size_t n, bool lower)
 {
     const auto t0 = std::chrono::steady_clock::now();
     DeviceTokenRoute::Slot &s = r->slot[which];
@@ -135,7 +151,8 @@ bool device_route_pack(DeviceTokenRoute *r, int which, const std::string_view *s
         if (sentences[i].size() > 0xFFFFFFFFull) return false;
         total += sentences[i].size();
     }
-    if (total > (1ull << 32) || n > (1ull << 32)) return false;   // (the scan's limits: such a batch keeps the host path)
+    // (the scan's limits: such a batch keeps the host path.  lower: the scan is handed the lowered text's bound, half as much again)
+    if (total + (lower ? total / 2 : 0) > (1ull << 32) || n > (1ull << 32)) return false;
     s.n = n;
     s.text_bytes = total;
     s.o_len = up16(n * 8);
@@ -164,7 +181,7 @@ bool device_route_pack(DeviceTokenRoute *r, int which, const std::string_view *s
 }
 
 uint64_t device_route_run(DeviceTokenRoute *r, int which, smt_sharded_model *model, uint32_t keep_bytes, uint32_t max_tokens, bool drop_unk,
-                          const DeviceFlaggedFn &tokenize_flagged, float *out_host, smt_sharded_corpus *corpus, TokenCsr *sink)
+                          const DeviceFlaggedFn &tokenize_flagged, float *out_host, smt_sharded_corpus *corpus, TokenCsr *sink, bool lower)
 {
     const DeviceTokenRoute::Slot &s = r->slot[which];
     const uint64_t n = s.n;
@@ -173,9 +190,13 @@ uint64_t device_route_run(DeviceTokenRoute *r, int which, smt_sharded_model *mod
     hip_ok(hipSetDevice(ctx->device), "hipSetDevice");
     hipStream_t st = ctx->stream;
     auto t0 = std::chrono::steady_clock::now();
-    // ---- device block: [the uploaded block] | counts u32 [n] | flags u8 [n] | n_flagged | offsets u64 [n + 1]
+    if (lower && !r->lower) throw Error("device tokenizer route: a batch to lower without device_route_can_lower");
+    // ---- device block: [the uploaded block] | counts u32 [n] | flags u8 [n] | n_flagged, lines the lower-casing flagged | offsets u64 [n + 1]
+    // lower: | out_begin u64 [n + 1] | out_len u32 [n] | lower-casing flags u8 [n] | the lowered text, low_cap bytes
+    const uint64_t low_cap = lower ? s.text_bytes + s.text_bytes / 2 : 0;
     const size_t o_counts = up16(s.up_bytes), o_flags = o_counts + up16(n * 4), o_nflag = o_flags + up16(n), o_off = o_nflag + 16,
-                 main_total = o_off + up16((n + 1) * 8);
+                 o_lbegin = o_off + up16((n + 1) * 8), o_llen = o_lbegin + (lower ? up16((n + 1) * 8) : 0), o_lflags = o_llen + (lower ? up16(n * 4) : 0),
+                 o_ltext = o_lflags + (lower ? up16(n) : 0), main_total = o_ltext + (lower ? up16((size_t)low_cap + 1) : 0);
     grow_device(r, &r->d_main, &r->main_bytes, main_total, "line arrays");
     char *d = static_cast<char *>(r->d_main);
     hip_ok(hipMemcpyAsync(d, s.pin, s.up_bytes, hipMemcpyHostToDevice, st), "upload of the packed lines");
@@ -185,11 +206,32 @@ uint64_t device_route_run(DeviceTokenRoute *r, int which, smt_sharded_model *mod
         const uint64_t *begin = reinterpret_cast<const uint64_t *>(d);
         const uint32_t *len = reinterpret_cast<const uint32_t *>(d + s.o_len);
         uint32_t *counts = reinterpret_cast<uint32_t *>(d + o_counts), *nflag = reinterpret_cast<uint32_t *>(d + o_nflag);
-        api_ok(smt::tok_scan_device(r->tok, text, s.text_bytes, begin, len, n, keep_bytes, max_tokens, drop_unk ? 1 : 0, counts, d_flags, nflag), "pass 1");
+        uint64_t text_bytes = s.text_bytes;
+        const uint8_t *lower_flags = nullptr;
+        if (lower) {
+            // the lowered lines stand back to back in [0, out_begin[n]) of the region; pass 1 is handed the region's size as its
+            // text_bytes -- the total is known on the device only, and the bytes behind it belong to no line
+            uint8_t *ltext = reinterpret_cast<uint8_t *>(d + o_ltext);
+            uint64_t *lbegin = reinterpret_cast<uint64_t *>(d + o_lbegin);
+            uint32_t *llen = reinterpret_cast<uint32_t *>(d + o_llen);
+            api_ok(smt_lower_device(r->lower, text, s.text_bytes, begin, len, n, ltext, low_cap, lbegin, llen, reinterpret_cast<uint8_t *>(d + o_lflags),
+                                    nflag + 1),
+                   "lower-casing");
+            text = ltext;
+            begin = lbegin;
+            len = llen;
+            text_bytes = low_cap;   // (pass 1's grid and slots grow by half with it, most of them owning no line: intended)
+            // a line the lower-casing left as it was is flagged for pass 1 too, wherever its ill-formed byte stands: behind the cut of
+            // keep_bytes pass 1 would not see it, and would tokenize the line's un-lowered head
+            lower_flags = reinterpret_cast<const uint8_t *>(d + o_lflags);
+        }
+        api_ok(smt::tok_scan_device(r->tok, text, text_bytes, begin, len, n, keep_bytes, max_tokens, drop_unk ? 1 : 0, counts, d_flags, nflag, lower_flags),
+               "pass 1");
     }
-    uint32_t n_flagged = 0;
-    hip_ok(hipMemcpyAsync(&n_flagged, d + o_nflag, 4, hipMemcpyDeviceToHost, st), "n_flagged");
+    uint32_t n_flagged_both[2] = {0, 0};   // pass 1's, the lower-casing's
+    hip_ok(hipMemcpyAsync(n_flagged_both, d + o_nflag, lower ? 8 : 4, hipMemcpyDeviceToHost, st), "n_flagged");
     hip_ok(hipStreamSynchronize(st), "pass 1");
+    const uint32_t n_flagged = n_flagged_both[0];
     PhaseTimer::add("within_embed:device_upload_and_pass1", ms_since(t0));
     // ---- the lines the kernel does not cover go through the host tokenizer: same truncate, unk-drop and cap steps
     std::vector<uint64_t> patch_line, patch_off(1, 0);
@@ -244,6 +286,7 @@ uint64_t device_route_run(DeviceTokenRoute *r, int which, smt_sharded_model *mod
         for (uint64_t i = 0; i < n; ++i) sink->lens.push_back((uint32_t)(off[i + 1] - off[i]));
     }
     r->lines_done += n - n_flagged;
+    if (lower) r->lines_lowered += n - n_flagged_both[1];
     return n_flagged;
 }
 

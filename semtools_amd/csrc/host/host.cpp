@@ -18,7 +18,6 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
-#include <deque>
 #include <exception>
 #include <fstream>
 #include <mutex>
@@ -153,7 +152,7 @@ static void push_utf8(std::string &out, uint32_t cp)
     else { out.push_back((char)(0xF0 | (cp >> 18))); out.push_back((char)(0x80 | ((cp >> 12) & 0x3F))); out.push_back((char)(0x80 | ((cp >> 6) & 0x3F))); out.push_back((char)(0x80 | (cp & 0x3F))); }
 }
 // decode the code point starting at s[i]; *len = its byte length (malformed bytes pass through one by one)
-static uint32_t decode_utf8(const std::string &s, size_t i, size_t *len)
+static uint32_t decode_utf8(std::string_view s, size_t i, size_t *len)
 {
     const unsigned char c = (unsigned char)s[i];
     const size_t want = utf8_len(c);
@@ -166,7 +165,7 @@ static uint32_t decode_utf8(const std::string &s, size_t i, size_t *len)
     return ((c & 0x07u) << 18) | (((unsigned char)s[i + 1] & 0x3Fu) << 12) | (((unsigned char)s[i + 2] & 0x3Fu) << 6) | ((unsigned char)s[i + 3] & 0x3Fu);
 }
 
-std::string to_lowercase(const std::string &s)
+std::string to_lowercase(std::string_view s)
 {
     std::string out;
     out.reserve(s.size());
@@ -210,7 +209,7 @@ std::string to_lowercase(const std::string &s)
             }
         if (!multi) {
             const uint32_t lo = lower_simple(cp);
-            if (lo == cp) out.append(s, i, len);
+            if (lo == cp) out.append(s.data() + i, len);
             else push_utf8(out, lo);
         }
         i += len;
@@ -617,7 +616,7 @@ static size_t truncate_len(std::string_view s, size_t max_tokens, size_t median_
 
 void StaticModel::tokenize_batch(const std::string_view *sentences, size_t begin, size_t end,
                                  std::optional<size_t> max_length, std::vector<uint32_t> &ids,
-                                 std::vector<uint64_t> &offsets) const
+                                 std::vector<uint64_t> &offsets, bool lower) const
 {
     // encode_batch_fast is rayon-parallel upstream; here: one contiguous slice of the batch per thread, in two steps with a barrier
     // between them -- (A) tokenise the slice into the thread's own buffers, [the last thread to arrive sizes the batch's arrays from
@@ -643,6 +642,7 @@ void StaticModel::tokenize_batch(const std::string_view *sentences, size_t begin
         try {
             std::vector<uint32_t> tmp;
             std::string text;   // (the tokenizers take a std::string: one buffer per thread, refilled per line -- no allocation once it has grown)
+            std::string lowered;   // lower: the line as it is embedded (mod.rs:63-67), made on this thread: the truncation below cuts IT
             // the slice's ids and lengths grow in vectors of THIS thread's frame and are handed over once: the headers of
             // part_ids[t] / part_len[t] of neighbouring threads share cache lines, and an append per line into them made every
             // thread's line cost 0.7 us instead of 0.25 (false sharing; profiles/r04_ingest_phases.json)
@@ -652,7 +652,8 @@ void StaticModel::tokenize_batch(const std::string_view *sentences, size_t begin
             const size_t median = tok_->median_token_length();
             for (size_t i = b; i < e; ++i) {
                 tmp.clear();
-                const std::string_view src = sentences[i];
+                std::string_view src = sentences[i];
+                if (lower) { lowered = to_lowercase(src); src = lowered; }
                 const size_t keep = max_length ? truncate_len(src, *max_length, median) : src.size();
                 text.assign(src.data(), keep);
                 tok_->encode(text, tmp);
@@ -727,7 +728,7 @@ DeviceTokenRoute *StaticModel::device_route() const
 }
 
 bool StaticModel::device_batch(int which, size_t n, const std::string_view *sentences, std::optional<size_t> max_length, float *out_host,
-                               smt_sharded_corpus *corpus, TokenCsr *sink) const
+                               smt_sharded_corpus *corpus, TokenCsr *sink, bool lower) const
 {
     // keep_bytes = truncate_len's max_tokens * median characters: a line that is pure ASCII that far has one byte per character
     const uint64_t keep = max_length ? (uint64_t)*max_length * tok_->median_token_length() : 0;
@@ -743,16 +744,27 @@ bool StaticModel::device_batch(int which, size_t n, const std::string_view *sent
     const DeviceFlaggedFn flagged = [&](const std::vector<uint64_t> &lines, std::vector<uint32_t> &ids, std::vector<uint64_t> &offsets) {
         std::vector<std::string_view> views(lines.size());
         for (size_t i = 0; i < lines.size(); ++i) views[i] = sentences[lines[i]];
-        tokenize_batch(views.data(), 0, views.size(), max_length, ids, offsets);
+        tokenize_batch(views.data(), 0, views.size(), max_length, ids, offsets, lower);   // (lower: the original lines were packed)
     };
     const uint64_t n_flagged = device_route_run(dev_route_, which, model_, keep_bytes, max_tokens, tok_->unk_id().has_value(), flagged, out_host,
-                                                corpus, sink);
+                                                corpus, sink, lower);
     return n_flagged * 2 > n;
+}
+
+// to_lowercase of lines[0, n) on up to eight threads: the copies in `store`, views of them in `views` (a call that lowers while the device
+// route is on and device lower-casing is off: the route is handed lowered copies, made batch by batch)
+static void lower_batch(const std::string_view *lines, size_t n, std::vector<std::string> &store, std::vector<std::string_view> &views)
+{
+    store.resize(n);
+    views.resize(n);
+    parallel_slices(n, 8192, [&](size_t b, size_t e) {
+        for (size_t i = b; i < e; ++i) { store[i] = to_lowercase(lines[i]); views[i] = store[i]; }
+    });
 }
 
 std::vector<std::vector<float>> StaticModel::encode_with_args(const std::vector<std::string> &sentences,
                                                               std::optional<size_t> max_length,
-                                                              size_t batch_size) const
+                                                              size_t batch_size, bool lower) const
 {
     std::vector<std::vector<float>> out;
     out.reserve(sentences.size());
@@ -761,18 +773,25 @@ std::vector<std::vector<float>> StaticModel::encode_with_args(const std::vector<
     std::vector<float> buf;
     if (batch_size == 0) batch_size = 1;
     const std::vector<std::string_view> views(sentences.begin(), sentences.end());
+    std::vector<std::string> low_store;
+    std::vector<std::string_view> low_views;
     // the route needs the full table RESIDENT (model_ set): a lazy table keeps the host path, whose small calls pick the rows to upload
     // from the ids.  (Only encode_into has the "about to be resident" rule: it uploads the table for n > 32768 before it gets here.)
     bool on_device = model_ && device_route();
     for (size_t b = 0; b < sentences.size(); b += batch_size) {
         const size_t e = std::min(sentences.size(), b + batch_size);
         buf.resize((e - b) * SMT_DIM);
-        if (on_device && device_route_pack(dev_route_, 0, views.data() + b, e - b)) {
-            if (device_batch(0, e - b, views.data() + b, max_length, buf.data(), nullptr, nullptr)) on_device = false;
-            for (size_t i = 0; i < e - b; ++i) out.emplace_back(buf.begin() + i * SMT_DIM, buf.begin() + (i + 1) * SMT_DIM);
-            continue;
+        if (on_device) {
+            const bool dev_lower = lower && device_lower_ && device_route_can_lower(dev_route_);
+            const std::string_view *src = views.data() + b;
+            if (lower && !dev_lower) { lower_batch(src, e - b, low_store, low_views); src = low_views.data(); }
+            if (device_route_pack(dev_route_, 0, src, e - b, dev_lower)) {
+                if (device_batch(0, e - b, src, max_length, buf.data(), nullptr, nullptr, dev_lower)) on_device = false;
+                for (size_t i = 0; i < e - b; ++i) out.emplace_back(buf.begin() + i * SMT_DIM, buf.begin() + (i + 1) * SMT_DIM);
+                continue;
+            }
         }
-        tokenize_batch(views.data(), b, e, max_length, ids, offsets);
+        tokenize_batch(views.data(), b, e, max_length, ids, offsets, lower);
         embed_csr(ids, offsets, e - b, buf.data(), nullptr);   // (tokenize_batch already truncated to max_length)
         for (size_t i = 0; i < e - b; ++i) out.emplace_back(buf.begin() + i * SMT_DIM, buf.begin() + (i + 1) * SMT_DIM);
     }
@@ -780,13 +799,15 @@ std::vector<std::vector<float>> StaticModel::encode_with_args(const std::vector<
 }
 
 uint64_t StaticModel::encode_into(const std::vector<std::string> &sentences, std::optional<size_t> max_length,
-                                  size_t batch_size, smt_sharded_corpus *corpus, TokenCsr *sink, const std::function<void()> *after_batch) const
+                                  size_t batch_size, smt_sharded_corpus *corpus, TokenCsr *sink, const std::function<void()> *after_batch,
+                                  bool lower) const
 {
-    return encode_into(std::vector<std::string_view>(sentences.begin(), sentences.end()), max_length, batch_size, corpus, sink, after_batch);
+    return encode_into(std::vector<std::string_view>(sentences.begin(), sentences.end()), max_length, batch_size, corpus, sink, after_batch, lower);
 }
 
 uint64_t StaticModel::encode_into(const std::vector<std::string_view> &sentences, std::optional<size_t> max_length,
-                                  size_t batch_size, smt_sharded_corpus *corpus, TokenCsr *sink, const std::function<void()> *after_batch) const
+                                  size_t batch_size, smt_sharded_corpus *corpus, TokenCsr *sink, const std::function<void()> *after_batch,
+                                  bool lower) const
 {
     // Double-buffered pipeline: while the GPU gathers/pools batch i (H2D of the ids + K1),
     // the host threads already tokenise batch i+1.  Batches are appended in order, so rows == line order.
@@ -808,28 +829,44 @@ uint64_t StaticModel::encode_into(const std::vector<std::string_view> &sentences
     auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
     auto tokenize = [&](size_t b, Slot &s) {
         const auto t0 = std::chrono::steady_clock::now();
-        tokenize_batch(sentences.data(), b, std::min(n, b + batch_size), max_length, s.ids, s.offsets);
+        tokenize_batch(sentences.data(), b, std::min(n, b + batch_size), max_length, s.ids, s.offsets, lower);   // (lower: on the tokenizer's threads, inside the batch)
         PhaseTimer::add("within_embed:tokenize_batches", ms_since(t0));
     };
     // ---- the device route (off by default): batch i runs on the GPU -- upload, tokenize, pool -- while batch i + 1 is packed into
     // the other pinned slot.  A batch that comes back mostly flagged (a corpus that is not ASCII runs pass 1 for nothing) hands the
     // rest of the call to the host path below; rows and cached ids are the same either way.
     // model_ is set when the table is resident -- from the start, or by the n > 32768 rule's full_model() a few lines up ("about to be").
+    // lower: the ORIGINAL lines are packed and lowered on the device (device_lower_), or -- with that switch off -- each batch is lowered
+    // on the host by the thread that packs it, while the previous batch runs on the GPU.
     size_t done = 0;
     if (model_ && device_route()) {
         int cur = 0;
-        bool packed = device_route_pack(dev_route_, 0, sentences.data(), std::min(n, batch_size));
+        const bool dev_lower = lower && device_lower_ && device_route_can_lower(dev_route_);
+        std::vector<std::string> low_store[2];
+        std::vector<std::string_view> low_views[2];
+        const std::string_view *src[2] = {nullptr, nullptr};
+        auto pack = [&](int slot, size_t b, size_t e) {
+            src[slot] = sentences.data() + b;
+            if (lower && !dev_lower) {
+                const auto t0 = std::chrono::steady_clock::now();
+                lower_batch(sentences.data() + b, e - b, low_store[slot], low_views[slot]);
+                src[slot] = low_views[slot].data();
+                PhaseTimer::add("within_embed:lower_on_host", ms_since(t0));
+            }
+            return device_route_pack(dev_route_, slot, src[slot], e - b, dev_lower);
+        };
+        bool packed = pack(0, 0, std::min(n, batch_size));
         while (packed && done < n) {
             const size_t e = std::min(n, done + batch_size);
             std::thread next;
             std::exception_ptr next_failed, run_failed;
             bool next_packed = false, give_up = false;
             if (e < n) next = std::thread([&, e, cur]() {
-                try { next_packed = device_route_pack(dev_route_, cur ^ 1, sentences.data() + e, std::min(n, e + batch_size) - e); }
+                try { next_packed = pack(cur ^ 1, e, std::min(n, e + batch_size)); }
                 catch (...) { next_failed = std::current_exception(); }
             });
             try {
-                give_up = device_batch(cur, e - done, sentences.data() + done, max_length, nullptr, corpus, sink);
+                give_up = device_batch(cur, e - done, src[cur], max_length, nullptr, corpus, sink, dev_lower);
                 if (after_batch && *after_batch) {
                     const auto t_after = std::chrono::steady_clock::now();
                     (*after_batch)();
@@ -915,15 +952,8 @@ std::optional<Document> create_document_from_content(const std::string &filename
     PhaseTimer::mark("split_lines");
     Document doc;
     doc.filename = filename;
-    if (ignore_case) {
-        std::vector<std::string> lowered(lines.size());
-        parallel_slices(lines.size(), 16384, [&](size_t b, size_t e) {
-            for (size_t i = b; i < e; ++i) lowered[i] = to_lowercase(std::string(lines[i]));
-        });
-        doc.first_row = model.encode_into(lowered, 2048, 16384, emb.corpus());  // mod.rs:69
-    } else {
-        doc.first_row = model.encode_into(lines, 2048, 16384, emb.corpus());
-    }
+    // (mod.rs:61-69: with ignore_case the lowered lines are what is embedded -- lowered inside the pipeline, on the device or the host)
+    doc.first_row = model.encode_into(lines, 2048, 16384, emb.corpus(), nullptr, nullptr, ignore_case);
     PhaseTimer::mark("tokenize_and_embed");
     doc.lines = std::move(lines);
     return doc;
@@ -1014,7 +1044,6 @@ std::vector<Document> load_documents(const std::vector<std::string> &files, cons
     // (tokenise || H2D || K1 across file borders instead of a round of threads and a K1 launch per file)
     std::vector<Document> documents;
     std::vector<std::string_view> all;
-    std::deque<std::string> lowered;   // (mod.rs:61-67: the lowered copies are what is embedded; a deque never moves its elements)
     // the files are read (and cut into lines) on up to eight threads; the first unreadable file IN ORDER is the error (mod.rs:130 `?`)
     std::vector<std::shared_ptr<const std::string>> texts(files.size());
     std::vector<std::vector<std::string_view>> views(files.size());
@@ -1036,19 +1065,15 @@ std::vector<Document> load_documents(const std::vector<std::string> &files, cons
         Document doc;
         doc.filename = f;
         doc.first_row = all.size();
-        if (ignore_case) {
-            for (auto &l : lines) {
-                lowered.push_back(to_lowercase(std::string(l)));
-                all.push_back(lowered.back());
-            }
-        } else all.insert(all.end(), lines.begin(), lines.end());
+        all.insert(all.end(), lines.begin(), lines.end());
         doc.lines = std::move(lines);
         doc.text = std::move(text);
         documents.push_back(std::move(doc));
     }
     PhaseTimer::mark("split_lines");
     if (!all.empty()) {
-        const uint64_t first = model.encode_into(all, 2048, 16384, emb.corpus());     // mod.rs:69
+        // mod.rs:61-69: with ignore_case the lowered lines are what is embedded -- lowered inside the pipeline, on the device or the host
+        const uint64_t first = model.encode_into(all, 2048, 16384, emb.corpus(), nullptr, nullptr, ignore_case);
         for (auto &d : documents) d.first_row += first;
     }
     PhaseTimer::mark("tokenize_and_embed");
@@ -1096,24 +1121,18 @@ std::vector<workspace::RankedLine> search_with_workspace(const std::vector<std::
     // Step 2+3: embed new/changed documents straight into the resident store
     size_t n_lines_upserted = 0;
     std::vector<DocMeta> docs_to_upsert;
-    std::vector<std::pair<std::string, std::vector<std::string_view>>> pending;   // views into doc_states' contents ...
-    std::deque<std::string> lowered;                                                // ... or into the lowered copies (mod.rs:61-67)
+    std::vector<std::pair<std::string, std::vector<std::string_view>>> pending;   // views into doc_states' contents
     for (auto &st : doc_states) {
         if (st.kind == DocumentState::Unchanged) continue;
         std::vector<std::string_view> lines = line_views(st.info.content);
         if (lines.empty()) continue;  // create_document_from_content -> None
-        if (config.ignore_case)
-            for (auto &s : lines) {
-                lowered.push_back(to_lowercase(std::string(s)));
-                s = lowered.back();
-            }
         n_lines_upserted += lines.size();
         pending.emplace_back(st.info.filename, std::move(lines));
         docs_to_upsert.push_back(st.info.meta);
     }
     if (n_lines_upserted) {
         fprintf(stderr, "Updating workspace with %zu lines from new/changed docs...\n", n_lines_upserted);  // mod.rs:194-197
-        store->upsert_documents_lines(pending, model);
+        store->upsert_documents_lines(pending, model, config.ignore_case);   // (mod.rs:61-67: the lowered lines are what is embedded)
         store->compact_if_sparse();  // every re-embedded document left its old rows behind: bound the dead rows
         store->flush_line_embeddings();
     }

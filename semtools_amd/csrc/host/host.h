@@ -39,7 +39,7 @@ struct Error : std::runtime_error {
 std::vector<std::string_view> line_views(std::string_view content);
 std::vector<std::string> lines_of(std::string_view content);
 // Rust str::to_lowercase() (simple per-code-point mapping; see DESIGN.md for the caveat).
-std::string to_lowercase(const std::string &s);
+std::string to_lowercase(std::string_view s);
 std::string read_to_string(const std::string &path);  // throws Error like `?` on io::Error
 
 // ------------------------------------------------------------------ tokenizer
@@ -206,13 +206,21 @@ using DeviceFlaggedFn = std::function<void(const std::vector<uint64_t> &lines, s
 DeviceTokenRoute *device_route_create(smt_group *group, const Tokenizer &tok, bool utf8 = false, bool long_pieces = false);
 void device_route_destroy(DeviceTokenRoute *r);
 uint64_t device_route_lines(const DeviceTokenRoute *r);   // lines tokenized on the device so far
+uint64_t device_route_lowered(const DeviceTokenRoute *r); // lines lowered on the device so far
+// the route can run batches with lower = true: it owns an smt_lower with the library's own tables (to_lowercase's), made at the first
+// call of this; false (and nothing thrown) when that cannot be made -- the caller then lowers on the host
+bool device_route_can_lower(DeviceTokenRoute *r);
 // the batch's bytes back to back into pinned slot `which` (0 / 1: one is packed while the other one runs); false: the batch is
-// outside the scan's limits and keeps the host path
-bool device_route_pack(DeviceTokenRoute *r, int which, const std::string_view *sentences, size_t n);
+// outside the scan's limits and keeps the host path.  lower: the batch will run with lower = true (its text may grow by half)
+bool device_route_pack(DeviceTokenRoute *r, int which, const std::string_view *sentences, size_t n, bool lower = false);
 // upload, pass 1, flagged lines on the host, pass 2, K1 into out_host and / or appended to corpus; sink receives the pooled ids.
-// Returns the number of flagged lines.
+// lower (after device_route_can_lower): the uploaded lines are lowered on the device first (smt_lower_device, enqueued behind the
+// upload: no host synchronisation of its own) and pass 1 reads the lowered lines; a line with ill-formed UTF-8 stays as it is there,
+// its flag is handed to pass 1 (which would not see a bad byte behind the cut of keep_bytes), and tokenize_flagged lowers it on the
+// host like every other flagged line.  Returns the number of flagged lines.
 uint64_t device_route_run(DeviceTokenRoute *r, int which, smt_sharded_model *model, uint32_t keep_bytes, uint32_t max_tokens, bool drop_unk,
-                          const DeviceFlaggedFn &tokenize_flagged, float *out_host, smt_sharded_corpus *corpus, TokenCsr *sink);
+                          const DeviceFlaggedFn &tokenize_flagged, float *out_host, smt_sharded_corpus *corpus, TokenCsr *sink,
+                          bool lower = false);
 
 class StaticModel {
 public:
@@ -236,19 +244,22 @@ public:
     StaticModel(const StaticModel &) = delete;
 
     // encode_with_args(sentences, Some(max_length), batch_size): returns host vectors
+    // lower (here and in encode_into): what is embedded is to_lowercase of every sentence (--ignore-case, mod.rs:63-67) -- lowered on
+    // the device when the device tokenizer route serves the batch and device_lower() is on, else on the host inside the batch, on the
+    // tokenizer's threads; the rows and the cached ids are those of lowering every sentence up front
     std::vector<std::vector<float>> encode_with_args(const std::vector<std::string> &sentences,
-                                                     std::optional<size_t> max_length, size_t batch_size) const;
+                                                     std::optional<size_t> max_length, size_t batch_size, bool lower = false) const;
     // same, but the rows are appended to `corpus` (resident); returns the first new row
     // (sink, if given, receives the pooled token ids of every sentence in order)
     // (after_batch, if given, runs on the calling thread each time a batch's rows are resident in `corpus` -- while the next
     // batch is being tokenised: the workspace store writes the new rows ahead to its file there)
     uint64_t encode_into(const std::vector<std::string> &sentences, std::optional<size_t> max_length,
                          size_t batch_size, smt_sharded_corpus *corpus, TokenCsr *sink = nullptr,
-                         const std::function<void()> *after_batch = nullptr) const;
+                         const std::function<void()> *after_batch = nullptr, bool lower = false) const;
     // (the sentences as views: the lines of a file are embedded where they lie in its content)
     uint64_t encode_into(const std::vector<std::string_view> &sentences, std::optional<size_t> max_length,
                          size_t batch_size, smt_sharded_corpus *corpus, TokenCsr *sink = nullptr,
-                         const std::function<void()> *after_batch = nullptr) const;
+                         const std::function<void()> *after_batch = nullptr, bool lower = false) const;
     // pool step only: n_lines lines given as token CSR (already filtered / truncated) appended to `corpus`
     void embed_tokens_into(const uint32_t *ids, const uint64_t *offsets, uint64_t n_lines, smt_sharded_corpus *corpus) const;
     // identifies the tokenizer (vocab size, unk id, ids of a fixed probe text): cached tokens are only valid for it
@@ -269,6 +280,11 @@ public:
     void set_device_tokenizer_long(bool on) { device_tok_long_ = on; }
     bool device_tokenizer_long() const { return device_tok_long_; }
     uint64_t device_tokenized_lines() const { return device_route_lines(dev_route_); }
+    // lower-casing on the device (on by default; SEMTOOLS_DEVICE_LOWER=0 turns it off at construction).  It only matters while the
+    // device tokenizer route is on and a call lowers: with it off such a call lowers every batch on the host before it is packed.
+    void set_device_lower(bool on) { device_lower_ = on; }
+    bool device_lower() const { return device_lower_; }
+    uint64_t device_lowered_lines() const { return device_route_lowered(dev_route_); }
     // the table as the device holds it (or will, in lazy mode before the full upload: *resident = false): SMT_TABLE_* kind, rows,
     // bytes per replica
     void table_info(int *table_dtype, uint64_t *V, uint64_t *table_bytes, bool *resident) const;
@@ -279,7 +295,7 @@ public:
 private:
     void tokenize_batch(const std::string_view *sentences, size_t begin, size_t end,
                         std::optional<size_t> max_length, std::vector<uint32_t> &ids,
-                        std::vector<uint64_t> &offsets) const;
+                        std::vector<uint64_t> &offsets, bool lower = false) const;
     // one batch of token CSR -> rows (host buffer and / or appended to a corpus) through the full or a compact table
     void embed_csr(const std::vector<uint32_t> &ids, const std::vector<uint64_t> &offsets, uint64_t n_lines, float *out_host,
                    smt_sharded_corpus *corpus) const;
@@ -289,9 +305,10 @@ private:
     DeviceTokenRoute *device_route() const;
     // one packed batch through the route; true: the batch was mostly flagged (the rest of the call keeps the host path)
     bool device_batch(int which, size_t n, const std::string_view *sentences, std::optional<size_t> max_length, float *out_host,
-                      smt_sharded_corpus *corpus, TokenCsr *sink) const;
+                      smt_sharded_corpus *corpus, TokenCsr *sink, bool lower = false) const;
     int device_tok_ = [] { const char *e = getenv("SEMTOOLS_DEVICE_TOKENIZER"); return e && e[0] == '1' ? 1 : e && e[0] == '2' ? 2 : 0; }();
     bool device_tok_long_ = [] { const char *e = getenv("SEMTOOLS_DEVICE_TOKENIZER_LONG"); return e && e[0] == '1'; }();
+    bool device_lower_ = [] { const char *e = getenv("SEMTOOLS_DEVICE_LOWER"); return !(e && e[0] == '0'); }();
     mutable DeviceTokenRoute *dev_route_ = nullptr;
     mutable bool dev_route_tried_ = false;
     mutable int dev_route_mode_ = 0;   // the mode (+ 4 with long pieces) dev_route_ was made for: a change makes it anew
@@ -464,11 +481,12 @@ public:
     void upsert_line_embeddings(const std::vector<LineEmbedding> &line_embeddings);
     // ... and the resident form used by search_with_workspace: embed straight into the store's corpus
     void upsert_document_lines(const std::string &path, const std::vector<std::string_view> &lines_for_embedding,
-                               const search::StaticModel &model);
+                               const search::StaticModel &model, bool lower = false);
     // the same for a batch of documents through ONE embedding pipeline run (tokenise || H2D || K1 across document
     // borders; one round of tokenizer threads per 65536 lines instead of one per file)
-    // (the lines are views: into the documents' contents, or into the lowered copies the caller holds)
-    void upsert_documents_lines(const std::vector<std::pair<std::string, std::vector<std::string_view>>> &docs, const search::StaticModel &model);
+    // (the lines are views into the documents' contents; lower: what is embedded is to_lowercase of every line, StaticModel::encode_into)
+    void upsert_documents_lines(const std::vector<std::pair<std::string, std::vector<std::string_view>>> &docs, const search::StaticModel &model,
+                                bool lower = false);
     WorkspaceStats get_stats() const;
     std::vector<std::string> get_all_document_paths() const;
     std::vector<RankedLine> search_line_embeddings(const std::vector<float> &query_vec,

@@ -315,6 +315,20 @@ int smt_host_debug_device_tokenized(smt_host_model *model, uint64_t *lines)
     return SMT_OK;
 }
 
+int smt_host_model_set_device_lower(smt_host_model *model, int on)
+{
+    if (!model) { smt::set_error("null argument"); return SMT_E_INVALID; }
+    model->m->set_device_lower(on != 0);   // the lines of an ignore_case call are lowered on the device while the route serves them
+    return SMT_OK;
+}
+
+int smt_host_debug_device_lowered(smt_host_model *model, uint64_t *lines)
+{
+    if (!model || !lines) { smt::set_error("null argument"); return SMT_E_INVALID; }
+    *lines = model->m->device_lowered_lines();
+    return SMT_OK;
+}
+
 int smt_host_tokenizer_to_device(smt_host_tokenizer *tok, smt_ctx *ctx, smt_wordpiece **out)
 {
     if (!tok || !out) { smt::set_error("null argument"); return SMT_E_INVALID; }
@@ -479,6 +493,17 @@ int smt_host_encode(smt_host_model *model, const char *const *texts, uint64_t n,
     try {
         std::vector<std::string> s(texts, texts + n);
         auto v = model->m->encode_with_args(s, max_length ? std::optional<size_t>(max_length) : std::nullopt, 16384);
+        for (uint64_t i = 0; i < n; ++i) memcpy(out + i * SMT_DIM, v[i].data(), SMT_DIM * sizeof(float));
+        return SMT_OK;
+    } catch (const std::exception &e) { return fail(e); }
+}
+
+int smt_host_encode_lowered(smt_host_model *model, const char *const *texts, uint64_t n, uint32_t max_length, float *out)
+{
+    if (!model || (n && (!texts || !out))) { smt::set_error("null argument"); return SMT_E_INVALID; }
+    try {
+        std::vector<std::string> s(texts, texts + n);
+        auto v = model->m->encode_with_args(s, max_length ? std::optional<size_t>(max_length) : std::nullopt, 16384, true);
         for (uint64_t i = 0; i < n; ++i) memcpy(out + i * SMT_DIM, v[i].data(), SMT_DIM * sizeof(float));
         return SMT_OK;
     } catch (const std::exception &e) { return fail(e); }

@@ -381,10 +381,11 @@ void Store::upsert_line_embeddings(const std::vector<LineEmbedding> &line_embedd
 
 static bool token_cache_enabled();
 
-void Store::upsert_documents_lines(const std::vector<std::pair<std::string, std::vector<std::string_view>>> &docs, const search::StaticModel &model)
+void Store::upsert_documents_lines(const std::vector<std::pair<std::string, std::vector<std::string_view>>> &docs, const search::StaticModel &model,
+                                   bool lower)
 {
     if (docs.empty()) return;
-    if (docs.size() == 1) { upsert_document_lines(docs[0].first, docs[0].second, model); return; }
+    if (docs.size() == 1) { upsert_document_lines(docs[0].first, docs[0].second, model, lower); return; }
     size_t total = 0;
     for (auto &d : docs) total += d.second.size();
     std::vector<std::string_view> all;
@@ -398,7 +399,7 @@ void Store::upsert_documents_lines(const std::vector<std::pair<std::string, std:
     search::TokenCsr tokens;
     const auto t_embed = std::chrono::steady_clock::now();
     const std::function<void()> ahead = [this] { write_rows_ahead(); };
-    uint64_t row = model.encode_into(all, 2048, 16384, corpus_, cache ? &tokens : nullptr, &ahead);
+    uint64_t row = model.encode_into(all, 2048, 16384, corpus_, cache ? &tokens : nullptr, &ahead, lower);
     search::PhaseTimer::add("within_persist:encode_into", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_embed).count());
     const auto t_tok = std::chrono::steady_clock::now();
     const uint64_t fingerprint = cache ? model.tokenizer_fingerprint() : 0;
@@ -449,13 +450,13 @@ void Store::write_rows_ahead() const
 }
 
 void Store::upsert_document_lines(const std::string &path, const std::vector<std::string_view> &lines_for_embedding,
-                                  const search::StaticModel &model)
+                                  const search::StaticModel &model, bool lower)
 {
     auto it = extents_.find(path);
     if (it != extents_.end()) dead_rows_ += it->second.n_rows;  // the whole old document is replaced (no stale tail)
     const bool cache = token_cache_enabled();
     search::TokenCsr tokens;
-    const uint64_t first = model.encode_into(lines_for_embedding, 2048, 16384, corpus_, cache ? &tokens : nullptr);
+    const uint64_t first = model.encode_into(lines_for_embedding, 2048, 16384, corpus_, cache ? &tokens : nullptr, nullptr, lower);
     extents_[path] = Extent{first, (uint64_t)lines_for_embedding.size()};
     if (cache) token_log_append(path, &tokens, model.tokenizer_fingerprint());
 }

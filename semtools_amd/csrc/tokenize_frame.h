@@ -142,9 +142,12 @@ int tok_scratch_reserve(smt_ctx *ctx, TokScratch &s, uint64_t n_slots, uint64_t 
 int tok_scratch_clear(smt_ctx *ctx, TokScratch &s, uint64_t n_slots, uint64_t n_lines);
 void tok_scratch_free(TokScratch &s);
 
-// counts[i] = flagged ? 0 : min(raw_count[i], max_tokens); *n_flagged += flagged lines.  Enqueued.
-int tok_line_counts(smt_ctx *ctx, const TokScratch &s, uint64_t n_lines, const uint8_t *flags_dev, uint32_t max_tokens, uint32_t *counts_dev,
-                    uint32_t *n_flagged_dev);
+// the frame's one-block prefix sum: out[i] = in[0] + ... + in[i - 1] for i in [0, n] (n == 0: out[0] = 0, `in` is not read).  Enqueued.
+int tok_exscan(smt_ctx *ctx, const uint32_t *in_dev, uint64_t n, uint64_t *out_dev);
+// counts[i] = flagged ? 0 : min(raw_count[i], max_tokens); *n_flagged += flagged lines.  pre_flags_dev (nullptr: none): flags an
+// earlier step raised, ORed into flags_dev first.  Enqueued.
+int tok_line_counts(smt_ctx *ctx, const TokScratch &s, uint64_t n_lines, uint8_t *flags_dev, uint32_t max_tokens, uint32_t *counts_dev,
+                    uint32_t *n_flagged_dev, const uint8_t *pre_flags_dev = nullptr);
 // pass 2 on a scratch that pass 1 filled: offsets_out = prefix sum of the (capped, or patched) counts, the ids to their place, the
 // patch lines copied in.  slot_begin_dev: the first slot of every line.  Enqueued.
 int tok_pass2(smt_ctx *ctx, const TokScratch &s, uint64_t n_slots, const uint64_t *slot_begin_dev, uint64_t n_lines, const uint32_t *counts_dev,
@@ -185,10 +188,12 @@ TokHandle *tok_handle(smt_wordpiece *tok);
 TokHandle *tok_handle(smt_unigram *tok);
 void tok_destroy(TokHandle *tok);   // waits for the context's stream; null is fine
 
-// the bodies of smt_*_scan_device, smt_*_emit_device and smt_*_tokenize (include/semtools_hip.h), behind the entry's null check
+// the bodies of smt_*_scan_device, smt_*_emit_device and smt_*_tokenize (include/semtools_hip.h), behind the entry's null check.
+// pre_flags_dev (nullptr: none): [n_lines] flags an earlier step raised -- the lower-casing's, for lines it left as they were; a line
+// flagged there is flagged here whatever pass 1 finds in its looked-at bytes (count 0, counted in *n_flagged_dev, patched like the others)
 int tok_scan_device(TokHandle *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev,
                     uint64_t n_lines, uint32_t keep_bytes, uint32_t max_tokens, int drop_unk, uint32_t *counts_dev, uint8_t *flags_dev,
-                    uint32_t *n_flagged_dev);
+                    uint32_t *n_flagged_dev, const uint8_t *pre_flags_dev = nullptr);
 int tok_emit_device(TokHandle *tok, uint64_t n_lines, const uint64_t *patch_line_dev, const uint64_t *patch_off_dev, const uint32_t *patch_ids_dev,
                     uint64_t n_patch, uint64_t n_patch_ids, uint32_t *ids_out_dev, uint64_t ids_cap, uint64_t *offsets_out_dev);
 int tok_tokenize(TokHandle *tok, const char *text, const uint64_t *line_begin, const uint32_t *line_len, uint64_t n_lines, uint32_t keep_bytes,

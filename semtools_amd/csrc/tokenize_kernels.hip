@@ -17,12 +17,15 @@ constexpr uint32_t WP_NONE = smt::TOK_NONE;   // an ids_tmp slot that holds no t
 constexpr unsigned EMIT_THREADS = smt::TOK_EMIT_THREADS;   // pass 2: four slots per thread
 constexpr unsigned EMIT_CHUNK = smt::TOK_EMIT_CHUNK;
 
-__global__ void __launch_bounds__(256) wp_lines_kernel(uint64_t n_lines, const uint32_t *__restrict__ raw_count, const uint8_t *__restrict__ flags,
-                                                       uint32_t max_tokens, uint32_t *__restrict__ counts, uint32_t *__restrict__ n_flagged)
+// pre (nullptr: none): flags an earlier step raised; such a line is flagged here too, whatever pass 1 looked at
+__global__ void __launch_bounds__(256) wp_lines_kernel(uint64_t n_lines, const uint32_t *__restrict__ raw_count, uint8_t *__restrict__ flags,
+                                                       const uint8_t *__restrict__ pre, uint32_t max_tokens, uint32_t *__restrict__ counts,
+                                                       uint32_t *__restrict__ n_flagged)
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_lines) return;
-    const bool f = flags[i] != 0;
+    bool f = flags[i] != 0;
+    if (!f && pre && pre[i]) { f = true; flags[i] = 1; }
     const uint32_t r = raw_count[i];
     counts[i] = f ? 0 : (max_tokens && r > max_tokens ? max_tokens : r);
     if (f) atomicAdd(n_flagged, 1u);
@@ -276,12 +279,19 @@ void tok_scratch_free(TokScratch &s)
     s = TokScratch();
 }
 
-int tok_line_counts(smt_ctx *ctx, const TokScratch &s, uint64_t n_lines, const uint8_t *flags_dev, uint32_t max_tokens, uint32_t *counts_dev,
-                    uint32_t *n_flagged_dev)
+int tok_exscan(smt_ctx *ctx, const uint32_t *in_dev, uint64_t n, uint64_t *out_dev)
+{
+    hipLaunchKernelGGL(wp_exscan_kernel, dim3(1), dim3(1024), 0, ctx->stream, in_dev, n, out_dev);
+    SMT_HIP_CHECK(hipGetLastError());
+    return SMT_OK;
+}
+
+int tok_line_counts(smt_ctx *ctx, const TokScratch &s, uint64_t n_lines, uint8_t *flags_dev, uint32_t max_tokens, uint32_t *counts_dev,
+                    uint32_t *n_flagged_dev, const uint8_t *pre_flags_dev)
 {
     if (!n_lines) return SMT_OK;
     hipLaunchKernelGGL(wp_lines_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), 0, ctx->stream, n_lines, s.raw_count(), flags_dev,
-                       max_tokens, counts_dev, n_flagged_dev);
+                       pre_flags_dev, max_tokens, counts_dev, n_flagged_dev);
     SMT_HIP_CHECK(hipGetLastError());
     return SMT_OK;
 }
@@ -329,7 +339,7 @@ void tok_destroy(TokHandle *tok)
 
 int tok_scan_device(TokHandle *tok, const uint8_t *text_dev, uint64_t text_bytes, const uint64_t *line_begin_dev, const uint32_t *line_len_dev,
                     uint64_t n_lines, uint32_t keep_bytes, uint32_t max_tokens, int drop_unk, uint32_t *counts_dev, uint8_t *flags_dev,
-                    uint32_t *n_flagged_dev)
+                    uint32_t *n_flagged_dev, const uint8_t *pre_flags_dev)
 {
     SMT_REQUIRE(n_flagged_dev != nullptr, "n_flagged_dev");
     SMT_REQUIRE(n_lines == 0 || (line_begin_dev && line_len_dev && counts_dev && flags_dev), "null argument");
@@ -346,10 +356,15 @@ int tok_scan_device(TokHandle *tok, const uint8_t *text_dev, uint64_t text_bytes
     SMT_HIP_CHECK(hipMemsetAsync(n_flagged_dev, 0, sizeof(uint32_t), st));
     if (n_lines) SMT_HIP_CHECK(hipMemsetAsync(flags_dev, 0, n_lines, st));
     if ((rc = tok_scratch_clear(ctx, tok->S, n_slots, n_lines))) return rc;
+    const auto launches = [&]() -> int {
+        int r = tok->pass1(text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev);
+        if (r) return r;
+        return tok_line_counts(ctx, tok->S, n_lines, flags_dev, max_tokens, counts_dev, n_flagged_dev, pre_flags_dev);
+    };
     prof_begin(ctx, "tokenize");
-    if ((rc = tok->pass1(text_dev, text_bytes, line_begin_dev, line_len_dev, n_lines, keep_bytes, drop_unk, flags_dev))) return rc;
-    if ((rc = tok_line_counts(ctx, tok->S, n_lines, flags_dev, max_tokens, counts_dev, n_flagged_dev))) return rc;
-    prof_end(ctx, "tokenize");
+    rc = launches();
+    prof_end(ctx, "tokenize");   // (on every path: an event pair left open would be read as a running one)
+    if (rc) return rc;
     tok->scanned = true;
     tok->text_bytes = text_bytes;
     tok->n_lines = n_lines;

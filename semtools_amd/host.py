@@ -20,7 +20,7 @@ def _take_text(ptr):
 def _cstrs(items):
     arr = (C.c_char_p * max(len(items), 1))()
     for i, s in enumerate(items):
-        arr[i] = s.encode()
+        arr[i] = s if isinstance(s, bytes) else s.encode()
     return arr
 
 
@@ -30,10 +30,13 @@ class StaticModel:
     tokenizer: "hash" (whitespace words hashed into the table), ("vocab", path, unk_token) or a
     Python callable text -> list of ids (e.g. tokenizers.Tokenizer(...).encode(t, add_special_tokens=False).ids)."""
 
-    def __init__(self, ctx, table=None, tokenizer="hash", normalize=True, unk_id=None, median_len=5, model_dir=None, device_tokenizer=None):
+    def __init__(self, ctx, table=None, tokenizer="hash", normalize=True, unk_id=None, median_len=5, model_dir=None, device_tokenizer=None,
+                 device_lower=None):
         """ctx: a core.Context (one GPU) or a core.Group (the host layer then runs sharded over its GPUs).
         device_tokenizer: True / False switch the device tokenizer route on / off (None: the library's default, off unless
-        SEMTOOLS_DEVICE_TOKENIZER=1 or 2); 2 chooses the UTF-8 form of a WordPiece tokenizer where it has one; it applies to tokenizer.json models of the Bert / WordPiece and the Metaspace / Unigram families on one GPU."""
+        SEMTOOLS_DEVICE_TOKENIZER=1 or 2); 2 chooses the UTF-8 form of a WordPiece tokenizer where it has one; it applies to tokenizer.json models of the Bert / WordPiece and the Metaspace / Unigram families on one GPU.
+        device_lower: True / False switch lower-casing on the device on / off (None: the library's default, on unless
+        SEMTOOLS_DEVICE_LOWER=0); it matters only while the device tokenizer route serves an ignore_case call."""
         from .core import Group
         self.ctx = ctx
         on_group = isinstance(ctx, Group)
@@ -45,6 +48,8 @@ class StaticModel:
             L.check(fn(ctx._h, str(model_dir).encode(), C.byref(self._h)))
             if device_tokenizer is not None:
                 self.set_device_tokenizer(device_tokenizer)
+            if device_lower is not None:
+                self.set_device_lower(device_lower)
             return
         table = np.ascontiguousarray(table, dtype=np.float32)
         kind, vocab, unk = 0, None, None
@@ -69,6 +74,8 @@ class StaticModel:
                    self._cb, None, 0xFFFFFFFF if unk_id is None else int(unk_id), int(median_len), C.byref(self._h)))
         if device_tokenizer is not None:
             self.set_device_tokenizer(device_tokenizer)
+        if device_lower is not None:
+            self.set_device_lower(device_lower)
 
     def set_device_tokenizer(self, on):
         L.check(L.lib().smt_host_model_set_device_tokenizer(self._h, int(on)))
@@ -82,6 +89,17 @@ class StaticModel:
         """lines of this model tokenized on the device so far (test hook)"""
         n = C.c_uint64()
         L.check(L.lib().smt_host_debug_device_tokenized(self._h, C.byref(n)))
+        return int(n.value)
+
+    def set_device_lower(self, on):
+        """lower-casing on the device (on unless SEMTOOLS_DEVICE_LOWER=0): while the device tokenizer route serves an ignore_case call,
+        its lines are lowered on the GPU; off: on the host, batch by batch"""
+        L.check(L.lib().smt_host_model_set_device_lower(self._h, int(bool(on))))
+
+    def device_lowered_lines(self):
+        """lines of this model lowered on the device so far (test hook)"""
+        n = C.c_uint64()
+        L.check(L.lib().smt_host_debug_device_lowered(self._h, C.byref(n)))
         return int(n.value)
 
     def close(self):
@@ -112,9 +130,11 @@ class StaticModel:
         L.check(L.lib().smt_host_model_token_info(self._h, C.byref(n), C.byref(hm), C.byref(hw), C.byref(nb)))
         return int(n.value), bool(hm.value), bool(hw.value), int(nb.value)
 
-    def encode_with_args(self, sentences, max_length=2048):
+    def encode_with_args(self, sentences, max_length=2048, lower=False):
+        """lower: the rows of the lowered sentences (what an ignore_case search embeds), lowered inside the call"""
         out = np.empty((len(sentences), L.DIM), dtype=np.float32)
-        L.check(L.lib().smt_host_encode(self._h, _cstrs(sentences), len(sentences), int(max_length or 0), L.np_ptr(out)))
+        fn = L.lib().smt_host_encode_lowered if lower else L.lib().smt_host_encode
+        L.check(fn(self._h, _cstrs(sentences), len(sentences), int(max_length or 0), L.np_ptr(out)))
         return out
 
     def encode_single(self, sentence):

@@ -30,8 +30,20 @@ spaces, on the ASCII text with a 100-byte URL-like word in every tenth line, and
 tenth line (no long piece: what the hand-over branch of the rules kernels and the second launch cost where they are not needed).
 Setting 2 without the switch is what the chain did before the switch covered it.  Writes
 profiles/device_tokenizer_precompiled_long.json.
+--ignore-case measures the ingest of an ignore_case search (every line through to_lowercase before it is embedded) with the WordPiece
+tokenizer, the vocabulary and the protocol of --utf8, the route at setting 2, on three texts with capitals: the pure-ASCII prose with
+every word capitalised and every fifth one in upper case, the same with a non-ASCII line with capitals in every tenth place, and the
+prose transliterated into Cyrillic with every word capitalised.  Settings, alternated in one process: host_lower (the route on,
+SEMTOOLS_DEVICE_LOWER=0: each batch lowered on the host by the thread that packs it), device_lower (lowered on the GPU), no_ignore_case
+(the same text without the option: the ceiling) and route_off (no device route: lowered on the tokenizer's threads).  --parent-build
+runs in a tree whose library has no device lower-casing -- a build of the parent commit, where every line is lowered up front on the
+calling thread -- and measures ignore_case / no_ignore_case there; its result goes under the key parent_build.  --files measures the
+same settings through smt_host_session_open on a file of the text (load_documents: where the parent lowered one line at a time on the
+calling thread) instead of smt_host_search_content (where it already used eight threads); under the key through_load_documents.
+--kernels TEXT runs
+smt_lower_device alone five times on one of the three texts, for a kernel trace taken from outside.  Writes profiles/device_lower.json.
 
-    python tools/bench_device_tokenizer.py [--model wordpiece|unigram] [--utf8|--long|--precompiled [--long]] [--lines 1000000] [--cpus 16] [--out profiles/device_tokenizer.json]"""
+    python tools/bench_device_tokenizer.py [--model wordpiece|unigram] [--utf8|--long|--precompiled [--long]|--ignore-case [--files] [--parent-build] | --ignore-case --kernels TEXT] [--lines 1000000] [--cpus 16] [--out profiles/device_tokenizer.json]"""
 import argparse
 import ctypes as C
 import json
@@ -235,6 +247,126 @@ def run_utf8(ctx, d, corpus, n_lines, repeats=3):
     return entry
 
 
+def lower_texts(lines):
+    """the three texts of --ignore-case"""
+    def caps(ln):
+        return " ".join(w.upper() if i % 5 == 4 else w.capitalize() for i, w in enumerate(ln.split(" ")))
+    ascii_caps = [caps(ln) for ln in lines]
+    odd = ["\u00c9COLE \u00dcBER Caf\u00e9 NA\u00cfVE", "\u039f\u0394\u03a5\u03a3\u03a3\u0395\u03a5\u03a3 \u039a\u0391\u0399 \u039b\u039f\u0393\u039f\u03a3", "\u0130STANBUL 300 \u212a \u4e2d\u6587"]
+    mixed = [ln.replace(" ", " " + odd[(i // 10) % 3] + " ", 1) if i % 10 == 0 else ln for i, ln in enumerate(ascii_caps)]
+    cyrillic = [" ".join(w.capitalize() for w in ln.translate(CYRILLIC).split(" ")) for ln in lines]
+    return (("ascii_with_capitals", ascii_caps), ("every_tenth_line_non_ascii_with_capitals", mixed), ("cyrillic_capitalised_words", cyrillic))
+
+
+def run_lower(ctx, d, corpus, n_lines, repeats=3, parent=False, files_dir=None):
+    """the settings of --ignore-case on one text: a model per setting, a discarded warm-up call each, then `repeats` rounds that visit
+    the settings in turn; every timed call ends in a device synchronise"""
+    content_b = ("\n".join(corpus) + "\n").encode()
+    query_b = corpus[17].encode()
+    if parent:
+        settings = (("ignore_case", 2, None, 1), ("no_ignore_case", 2, None, 0))
+    else:
+        settings = (("host_lower", 2, False, 1), ("device_lower", 2, True, 1), ("no_ignore_case", 2, True, 0), ("route_off", 0, True, 1))
+    models, ic = {}, {}
+    for name, mode, dev_lower, ignore_case in settings:
+        models[name] = host.StaticModel(ctx, model_dir=d, device_tokenizer=mode) if dev_lower is None else \
+            host.StaticModel(ctx, model_dir=d, device_tokenizer=mode, device_lower=dev_lower)
+        ic[name] = ignore_case
+    times = {name: [] for name in models}
+    prof = {name: {"lower": [0, 0.0], "tokenize": [0, 0.0]} for name in models}
+    phases = {name: {} for name in models}
+    first = {}
+
+    path = None
+    if files_dir:
+        path = os.path.join(files_dir, "corpus.txt")
+        with open(path, "wb") as f:
+            f.write(content_b)
+
+    def call(name):
+        if path:                                     # smt_host_session_open: read, split, (lower,) tokenize, K1
+            s = host.Session(models[name], [path], ignore_case=bool(ic[name]))
+            n = s.lines
+            s.close()
+            ctx.synchronize()
+            return "%d lines" % n
+        out = C.c_void_p()
+        L.check(L.lib().smt_host_search_content(models[name]._h, query_b, b"<stdin>", content_b, 0, 3, float("nan"), ic[name], 0, 0, C.byref(out)))
+        ctx.synchronize()
+        return host._take_text(out).split("\n")[0]
+
+    for name in models:
+        call(name)
+    for _ in range(repeats):
+        for name in models:
+            ctx.prof_reset()
+            before = phases_now()
+            t0 = time.perf_counter()
+            first[name] = call(name)
+            times[name].append(time.perf_counter() - t0)
+            for k, v in phases_now().items():
+                if (k.startswith("within_embed") or k in ("split_lines", "tokenize_and_embed")) and v - before.get(k, 0.0) > 0:
+                    phases[name][k] = phases[name].get(k, 0.0) + v - before.get(k, 0.0)
+            for key, acc in prof[name].items():
+                n, ms = ctx.prof_read(key)
+                acc[0] += n
+                acc[1] += ms
+    entry = {"text_bytes": len(content_b)}
+    for name, m in models.items():
+        best = min(times[name])
+        res = {"seconds_best": round(best, 4), "seconds_all": [round(t, 4) for t in times[name]],
+               "spread_percent": round(100.0 * (max(times[name]) - best) / best, 1), "lines_per_s": round(n_lines / best),
+               "device_tokenized_lines_per_call": m.device_tokenized_lines() // (repeats + 1), "first_hit": first[name][:80],
+               "phases_ms_per_call": {k: round(v / repeats, 2) for k, v in sorted(phases[name].items())}}
+        if not parent:
+            res["device_lowered_lines_per_call"] = m.device_lowered_lines() // (repeats + 1)
+        if prof[name]["lower"][0]:
+            res["lower_ms_per_call"] = round(prof[name]["lower"][1] / repeats, 3)      # the three launches and the two prefix sums, by events
+            res["lower_GB_per_s"] = round(len(content_b) * repeats / (prof[name]["lower"][1] * 1e-3) / 1e9, 2)
+        if prof[name]["tokenize"][0]:
+            res["pass1_ms_per_call"] = round(prof[name]["tokenize"][1] / repeats, 3)
+        entry[name] = res
+        m.close()
+    lowered = [n for n in models if ic[n]]
+    entry["same_first_hit_among_the_lowering_settings"] = len({first[n] for n in lowered}) == 1
+    if not parent:
+        entry["device_over_host_lower"] = round(entry["device_lower"]["lines_per_s"] / entry["host_lower"]["lines_per_s"], 3)
+        entry["device_lower_over_no_ignore_case"] = round(entry["device_lower"]["lines_per_s"] / entry["no_ignore_case"]["lines_per_s"], 3)
+        a, b = entry["device_lower"], entry["host_lower"]
+        entry["device_lower_slower_beyond_the_spreads"] = a["seconds_best"] > max(b["seconds_all"])
+    print("measured:", {name: entry[name]["lines_per_s"] for name in models}, "lines/s", flush=True)
+    return entry
+
+
+def run_lower_kernels(ctx, corpus, repeats=5):
+    """smt_lower_device alone on one text, `repeats` times behind a warm-up call: for a kernel trace taken from outside"""
+    text, begin, lens = smt.Lower.pack([ln.encode() for ln in corpus])
+    n, tb = len(lens), len(text)
+    cap = tb + tb // 2
+    d_text = torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).cuda()
+    d_begin = torch.from_numpy(begin.view(np.int64)).cuda()
+    d_len = torch.from_numpy(lens.view(np.int32)).cuda()
+    d_out = torch.zeros(cap + 16, dtype=torch.uint8, device="cuda")
+    d_ob = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    d_ol = torch.zeros(n + 1, dtype=torch.int32, device="cuda")
+    d_fl = torch.zeros(n + 1, dtype=torch.uint8, device="cuda")
+    d_nf = torch.zeros(1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    h = smt.Lower(ctx)
+    times = []
+    for _ in range(repeats + 1):
+        t0 = time.perf_counter()
+        h.lower_device(d_text.data_ptr(), tb, d_begin.data_ptr(), d_len.data_ptr(), n, d_out.data_ptr(), cap, d_ob.data_ptr(), d_ol.data_ptr(),
+                       d_fl.data_ptr(), d_nf.data_ptr())
+        ctx.synchronize()
+        times.append(time.perf_counter() - t0)
+    h.close()
+    res = {"text_bytes": tb, "lines": n, "lowered_bytes": int(d_ob[n].item()), "flagged_lines": int(d_nf[0].item()), "calls_traced": repeats + 1,
+           "call_seconds_best_host_clock": round(min(times[1:]), 6)}
+    print(json.dumps(res), flush=True)
+    return res
+
+
 def run_long(ctx, d, corpus, n_lines, repeats=3, rules=False):
     """off / 2 / 2 with long pieces on one text: a model per setting, a discarded warm-up call each, then `repeats` rounds that visit
     the settings in turn; every timed call ends in a device synchronise"""
@@ -364,12 +496,21 @@ def main():
     ap.add_argument("--utf8", action="store_true")
     ap.add_argument("--long", action="store_true", help="the long pieces of the Unigram route (with --model unigram)")
     ap.add_argument("--precompiled", action="store_true", help="an XLM-R-style chain in front of the Unigram route (with --model unigram)")
+    ap.add_argument("--ignore-case", action="store_true", help="the ingest of an ignore_case search: where the lines are lowered")
+    ap.add_argument("--parent-build", action="store_true", help="with --ignore-case: the library has no device lower-casing (a build of the parent commit)")
+    ap.add_argument("--files", action="store_true", help="with --ignore-case: through smt_host_session_open on a file (load_documents)")
+    ap.add_argument("--kernels", default=None, help="with --ignore-case: smt_lower_device alone on this text (for a kernel trace)")
     ap.add_argument("--lines", type=int, default=1_000_000)
     ap.add_argument("--cpus", type=int, default=16)
     ap.add_argument("--model", choices=["wordpiece", "unigram"], default="wordpiece")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     unigram = a.model == "unigram"
+    if a.ignore_case:
+        if unigram or a.utf8 or a.long or a.precompiled:
+            ap.error("--ignore-case goes alone (WordPiece, the vocabulary of --utf8)")
+        a.utf8 = True
+        a.out = a.out or os.path.join(ROOT, "profiles", "device_lower.json")
     if a.long:
         if not unigram or a.utf8:
             ap.error("--long goes with --model unigram, without --utf8")
@@ -423,7 +564,19 @@ def main():
             W.write_tokenizer(os.path.join(d, "tokenizer.json"), 7, vocab=vocab)
         with open(os.path.join(d, "config.json"), "w") as f:
             json.dump({"normalize": True, "unk_token": "<unk>" if unigram else "[UNK]"}, f)
-        if a.long:
+        if a.ignore_case and a.kernels:
+            result = {"what": "smt_lower_device alone, for a kernel trace", a.kernels: run_lower_kernels(ctx, dict(lower_texts(lines))[a.kernels])}
+        elif a.ignore_case:
+            result["what"] = "host-layer ingest of an ignore_case search (smt_host_search_content), by where the lines are lowered"
+            result["note"] = ("route at setting 2 (UTF-8 form) but for route_off; kernel profiling events are on in all settings; per setting one "
+                              "warm-up call is discarded, then three rounds visit the settings in turn; every timed call ends in a device "
+                              "synchronise; seconds_best is the best of 3, spread_percent (max - best) / best; lower_ms_per_call is the three "
+                              "launches of smt_lower_device and its two prefix sums, by events")
+            if a.files:
+                result["what"] = "host-layer ingest of an ignore_case session (smt_host_session_open on one file: load_documents), by where the lines are lowered"
+            for name, corpus in lower_texts(lines):
+                result[name] = run_lower(ctx, d, corpus, a.lines, parent=a.parent_build, files_dir=d if a.files else None)
+        elif a.long:
             measure_long(ctx, d, lines, a.lines, result, a.precompiled)
         elif a.utf8:
             measure_utf8(ctx, d, lines, a.lines, result, unigram, a.precompiled)
@@ -436,7 +589,21 @@ def main():
     if os.path.exists(a.out):
         with open(a.out) as f:
             merged = json.load(f)
-    merged["cpus_%d" % cores] = result
+    key = "cpus_%d" % cores
+    if a.ignore_case and a.kernels:
+        merged.setdefault(key, {}).setdefault("kernels_alone", {}).update({a.kernels: result[a.kernels]})
+    elif a.ignore_case and a.files:
+        sub = merged.setdefault(key, {}).setdefault("through_load_documents", {})
+        if a.parent_build:
+            sub["parent_build"] = result
+        else:
+            sub.update(result)
+    elif a.ignore_case and a.parent_build:
+        merged.setdefault(key, {})["parent_build"] = result
+    elif a.ignore_case and key in merged:
+        merged[key].update(result)
+    else:
+        merged[key] = result
     with open(a.out, "w") as f:
         json.dump(merged, f, indent=1)
     print(json.dumps(result, indent=1))

@@ -22,7 +22,7 @@ PRELUDE = '''//! FFI declarations for libsemtools_hip.so -- GENERATED from inclu
 use std::os::raw::{c_char, c_int, c_void};
 
 macro_rules! opaque { ($($name:ident),*) => { $( #[repr(C)] pub struct $name { _private: [u8; 0] } )* } }
-opaque!(SmtCtx, SmtModel, SmtCorpus, SmtIvfpq, SmtGroup, SmtShardedCorpus, SmtShardedIvfpq, SmtShardedModel, SmtWordpiece, SmtUnigram);
+opaque!(SmtCtx, SmtModel, SmtCorpus, SmtIvfpq, SmtGroup, SmtShardedCorpus, SmtShardedIvfpq, SmtShardedModel, SmtWordpiece, SmtUnigram, SmtLower);
 
 /// half-open range of corpus rows [begin, end)
 #[repr(C)]
@@ -92,6 +92,28 @@ pub struct SmtUnigramParams {
     pub added_pool: *const c_char,
     pub added_off: *const u32,
     pub n_added: u32,
+}
+
+/// the lower-casing tables for the device (smt_lower_create copies everything; a null pointer there means Rust's str::to_lowercase)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SmtLowerTables {
+    pub run_first: *const u32,
+    pub run_last: *const u32,
+    pub run_delta: *const i32,
+    pub run_stride: *const u32,
+    pub n_runs: u64,
+    pub multi_cp: *const u32,
+    pub multi_n: *const u32,
+    pub multi_to: *const u32,
+    pub n_multi: u64,
+    pub cased_first: *const u32,
+    pub cased_last: *const u32,
+    pub n_cased: u64,
+    pub ignorable_first: *const u32,
+    pub ignorable_last: *const u32,
+    pub n_ignorable: u64,
+    pub final_sigma: u32,
 }
 
 '''
