@@ -1030,6 +1030,55 @@ int smt_debug_batched_scores(smt_corpus *corpus, const float *queries, uint32_t 
 int smt_debug_nominations(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
                           const float *tau, int buffered, float *out_dist, uint32_t *out_hits, uint32_t *out_counts, uint32_t *out_route);
 
+/* Test hooks for the K3 LEVEL STAGE: everything between "one level nominates" (smt_debug_nominations) and "the select ranks"
+ * (smt_debug_select_lists).  tests/test_level_plan_cpu.py and tests/test_gpu_level_stage.py hold them against tests/level_ref.py.
+ *
+ * smt_debug_gemm_plan   the LEVEL PLAN of a batched call: the ordered launches launch_gemm_topk makes (it walks the very list this
+ *     returns).  A pure host function: no context, no GPU.  plan_tiles: tiles of the call (32-row tiles, entries of the tile table, or
+ *     groups of 8 chunk-table entries; 1 .. 2^27 - 1); kp: k' (1..64); family: 0 row-register, 1 LDS-row, 2 level kernel; blocks: tuning
+ *     key gemm_blocks or the CU count; then the tuning keys of those names.  out [out_cap][SMT_GEMM_PLAN_WORDS] receives per launch
+ *       [0] kind: 0 bootstrap (tile minima, bootstrap_tau_kernel behind it), 1 appended (level_select_kernel behind it)
+ *       [1] stride  [2] skip (0, 4, 16, 64)  [3] tile_begin  [4] tile_end: level tile indices [tile_begin, tile_end); level tile i is
+ *           tile stride x i (skip 0) resp. stride x the (i + 1)-th positive integer that is no multiple of skip
+ *       [5] qsplit  [6] blocks of the launch  [7] bootstrap slots  [8] 1: a select pass follows
+ *       [9] bit 0: runs under thresholds an earlier select published; bit 1: its nominations fit the waves' LDS buffers
+ *     *out_n: the launches of the plan, also when they exceed out_cap (SMT_E_INVALID then).
+ * smt_debug_level_nominations   smt_debug_nominations for an arbitrary level: the launch visits level tiles [tile_begin, tile_end) of
+ *     (stride, skip) instead of every tile.  At most 2048 rows may be visited; the last tile must exist; tile_begin != 0 only with the
+ *     row-register kernel (the others always start at 0); anything else is SMT_E_INVALID.
+ * smt_debug_bootstrap_minima    the BOOTSTRAP launch of the batched call over the corpus (1..64 host queries, optional ranges), exactly
+ *     as launch_gemm_topk makes it: the head launch with the +inf fill, then gemm_rowreg_kernel with tile_min, grid and query split as
+ *     planned.  out_tile_min [*out_slots][ceil(nq / 32) * 32] (host, room for 1024 slots): slot s = the minimum over the level tiles
+ *     with index = s mod 1024 of the tile's best nominating distance.  No candidates are written, so any number of rows may be scanned.
+ *     SMT_E_INVALID when the call's plan has no bootstrap level.  out_stride: the bootstrap stride; out_route as smt_debug_nominations.
+ * smt_debug_bootstrap_tau       bootstrap_tau_kernel on device buffers: tile_min_dev [n_slots <= 1024][nq_pad], nq <= nq_pad (a multiple
+ *     of 32), kp 1..64; tau_dev [nq_pad]; qconst_dev [nq_pad][2], word 2q + 1 = 1/|q| as the head launch left it, word 2q receives the
+ *     score threshold of the new tau.  Asynchronous on the context's stream.
+ * smt_debug_level_select        level_select_kernel on device buffers, in place: cand_dev [nq][2048] keys (f32 distance bits << 32 | row),
+ *     counts_dev [nq] (any value: above 2048 the query overflowed), overflow_dev [nq] (sticky), tau_dev [nq], qconst_dev [nq][2] or NULL.
+ *     PRECONDITION: the first min(count, 2048) keys of a query are DISTINCT -- the kernel ranks with a strict <, two equal keys would
+ *     share a rank and leave a hole.  Production keeps it because every tile belongs to exactly one appended launch (the plan, P1 of
+ *     tests/test_level_plan_cpu.py).  Asynchronous on the context's stream.
+ * smt_debug_gemm_trace          sets (buf_dev != NULL, cap_words 32-bit words) or clears the TRACE BUFFER of the context and returns what
+ *     was recorded since it was last set: *out_selects select passes, *out_words words.  While set, every batched top_k call appends,
+ *     with device-to-device copies on its stream, per select pass (bootstrap_tau_kernel, the select between the two parts of a level,
+ *     the select at a level's end) nq count words as the pass finds them and nq tau words as it leaves them, and at its end nq overflow
+ *     words and [nq][k'] keys from the head of the candidate buffers.  Nothing else changes, and nothing at all while no buffer is
+ *     set.  SMT_E_INVALID when the buffer was too small.  Synchronise before reading the buffer. */
+#define SMT_GEMM_PLAN_WORDS 10
+int smt_debug_gemm_plan(uint64_t plan_tiles, uint32_t nq, uint32_t kp, int family, int f16x1, uint32_t blocks, int gemm_bootstrap,
+                        int gemm_boot_fine, int gemm_split_last, int gemm_qsplit, uint64_t *out, uint32_t out_cap, uint32_t *out_n);
+int smt_debug_level_nominations(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges,
+                                uint32_t n_ranges, const float *tau, int buffered, uint64_t stride, uint32_t skip, uint64_t tile_begin,
+                                uint64_t tile_end, float *out_dist, uint32_t *out_hits, uint32_t *out_counts, uint32_t *out_route);
+int smt_debug_bootstrap_minima(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges,
+                               uint32_t n_ranges, float *out_tile_min, uint32_t *out_slots, uint64_t *out_stride, uint32_t *out_route);
+int smt_debug_bootstrap_tau(smt_ctx *ctx, const float *tile_min_dev, uint32_t n_slots, uint32_t nq, uint32_t nq_pad, uint32_t kp,
+                            float *tau_dev, float *qconst_dev);
+int smt_debug_level_select(smt_ctx *ctx, uint64_t *cand_dev, uint32_t *counts_dev, uint32_t *overflow_dev, float *tau_dev, float *qconst_dev,
+                           uint32_t nq, uint32_t kp);
+int smt_debug_gemm_trace(smt_ctx *ctx, uint32_t *buf_dev, uint64_t cap_words, uint32_t *out_selects, uint64_t *out_words);
+
 /* Test hooks for the cross-shard merge (csrc/merge.hip): the kernels behind every sharded answer, run on lists a test constructs
  * instead of lists a group's shards produced.  tests/test_gpu_merge.py compares them bit for bit with a NumPy merge
  * (tests/merge_ref.py).  The preconditions of smt_merge_topk hold here too.  Device pointers unless said otherwise; asynchronous on the

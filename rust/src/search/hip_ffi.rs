@@ -138,6 +138,7 @@ pub const SMT_APPEND_CREATE: c_int = 2;
 pub const SMT_DEBUG_FAIL_STAGE: c_int = 1;
 pub const SMT_DEBUG_FAIL_AGREE: c_int = 2;
 pub const SMT_DEBUG_FAIL_BUILD: c_int = 3;
+pub const SMT_GEMM_PLAN_WORDS: c_int = 10;
 
 extern "C" {
     pub fn smt_ctx_create(device: c_int, out: *mut *mut SmtCtx) -> c_int;
@@ -943,6 +944,78 @@ extern "C" {
         out_hits: *mut u32,
         out_counts: *mut u32,
         out_route: *mut u32,
+    ) -> c_int;
+    pub fn smt_debug_gemm_plan(
+        plan_tiles: u64,
+        nq: u32,
+        kp: u32,
+        family: c_int,
+        f16x1: c_int,
+        blocks: u32,
+        gemm_bootstrap: c_int,
+        gemm_boot_fine: c_int,
+        gemm_split_last: c_int,
+        gemm_qsplit: c_int,
+        out: *mut u64,
+        out_cap: u32,
+        out_n: *mut u32,
+    ) -> c_int;
+    pub fn smt_debug_level_nominations(
+        corpus: *mut SmtCorpus,
+        queries: *const f32,
+        nq: u32,
+        top_k: u32,
+        ranges: *const SmtRange,
+        n_ranges: u32,
+        tau: *const f32,
+        buffered: c_int,
+        stride: u64,
+        skip: u32,
+        tile_begin: u64,
+        tile_end: u64,
+        out_dist: *mut f32,
+        out_hits: *mut u32,
+        out_counts: *mut u32,
+        out_route: *mut u32,
+    ) -> c_int;
+    pub fn smt_debug_bootstrap_minima(
+        corpus: *mut SmtCorpus,
+        queries: *const f32,
+        nq: u32,
+        top_k: u32,
+        ranges: *const SmtRange,
+        n_ranges: u32,
+        out_tile_min: *mut f32,
+        out_slots: *mut u32,
+        out_stride: *mut u64,
+        out_route: *mut u32,
+    ) -> c_int;
+    pub fn smt_debug_bootstrap_tau(
+        ctx: *mut SmtCtx,
+        tile_min_dev: *const f32,
+        n_slots: u32,
+        nq: u32,
+        nq_pad: u32,
+        kp: u32,
+        tau_dev: *mut f32,
+        qconst_dev: *mut f32,
+    ) -> c_int;
+    pub fn smt_debug_level_select(
+        ctx: *mut SmtCtx,
+        cand_dev: *mut u64,
+        counts_dev: *mut u32,
+        overflow_dev: *mut u32,
+        tau_dev: *mut f32,
+        qconst_dev: *mut f32,
+        nq: u32,
+        kp: u32,
+    ) -> c_int;
+    pub fn smt_debug_gemm_trace(
+        ctx: *mut SmtCtx,
+        buf_dev: *mut u32,
+        cap_words: u64,
+        out_selects: *mut u32,
+        out_words: *mut u64,
     ) -> c_int;
     pub fn smt_debug_merge_sources(
         ctx: *mut SmtCtx,

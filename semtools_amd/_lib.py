@@ -49,11 +49,14 @@ EXPORTS = [
     "smt_debug_select_groups", "smt_debug_ov_ready", "smt_debug_host_timing",
     "smt_debug_merge_sources", "smt_debug_merge_packed_strided", "smt_debug_combine_status", "smt_debug_select_lists",
     "smt_debug_scan_lists", "smt_debug_scan_ring",
+    "smt_debug_gemm_plan", "smt_debug_level_nominations", "smt_debug_bootstrap_minima", "smt_debug_bootstrap_tau", "smt_debug_level_select",
+    "smt_debug_gemm_trace",
     "smt_wordpiece_create", "smt_wordpiece_create_utf8", "smt_wordpiece_info", "smt_wordpiece_destroy", "smt_wordpiece_scan_device", "smt_wordpiece_emit_device", "smt_wordpiece_tokenize",
     "smt_unigram_create", "smt_unigram_create_utf8", "smt_unigram_info", "smt_unigram_destroy", "smt_unigram_scan_device", "smt_unigram_emit_device", "smt_unigram_tokenize",
     "smt_unigram_set_long_pieces", "smt_unigram_long_stats", "smt_unigram_set_space_rules", "smt_unigram_set_long_rules",
     "smt_lower_tables_check", "smt_lower_create", "smt_lower_destroy", "smt_lower_device", "smt_lower_lines",
 ]
+GEMM_PLAN_WORDS = 10   # SMT_GEMM_PLAN_WORDS
 WP_NORMALIZER, WP_CLEAN_TEXT, WP_LOWERCASE = 1, 2, 4
 WP_CP_ORDINARY, WP_CP_SPACE, WP_CP_ALONE, WP_CP_DROPPED, WP_CP_FLAG = 0, 1, 2, 3, 4
 UG_MAX_WORD = 64
@@ -334,6 +337,12 @@ def lib():
         L.smt_debug_select_lists.argtypes = [vp, vp, u32, vp, u64, u32, u32, u32, i32, C.c_float, u64, f64, vp, u64, vp, vp, vp, vp, vp]
         L.smt_debug_scan_lists.argtypes = [vp, vp, u32, u32, vp, u32, vp, u64, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]
         L.smt_debug_scan_ring.argtypes = [vp, u32, u64, vp]
+        L.smt_debug_gemm_plan.argtypes = [u64, u32, u32, i32, i32, u32, i32, i32, i32, i32, vp, u32, P(C.c_uint32)]
+        L.smt_debug_level_nominations.argtypes = [vp, vp, u32, u32, vp, u32, vp, i32, u64, u32, u64, u64, vp, vp, vp, P(C.c_uint32)]
+        L.smt_debug_bootstrap_minima.argtypes = [vp, vp, u32, u32, vp, u32, vp, P(C.c_uint32), P(C.c_uint64), P(C.c_uint32)]
+        L.smt_debug_bootstrap_tau.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp]
+        L.smt_debug_level_select.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32]
+        L.smt_debug_gemm_trace.argtypes = [vp, vp, u64, P(C.c_uint32), P(C.c_uint64)]
     except AttributeError:
         pass
     L.smt_sharded_corpus_append_to_file_ex.argtypes = [vp, C.c_char_p, u64, u64, i32]

@@ -195,6 +195,43 @@ class Context:
         L.check(L.lib().smt_debug_combine_status(self._h, wp, C.c_void_p(base_ptr) if base_ptr else None, int(stride_words), int(n), int(nq),
                                                  C.c_void_p(out_status_ptr)))
 
+    @staticmethod
+    def debug_gemm_plan(plan_tiles, nq, kp, family=0, f16x1=False, blocks=256, gemm_bootstrap=1, gemm_boot_fine=1, gemm_split_last=2,
+                        gemm_qsplit=1):
+        """Test hook (smt_debug_gemm_plan; host only: no GPU and no context, call it on the class): the launches of a batched call's level plan, in order -- a list of dicts
+        with the keys kind (0 bootstrap, 1 appended), stride, skip, tile_begin, tile_end, qsplit, blocks, slots, select, thresholds,
+        buffer_fits."""
+        cap = 16
+        out = np.zeros((cap, L.GEMM_PLAN_WORDS), dtype=np.uint64)
+        n = C.c_uint32(0)
+        L.check(L.lib().smt_debug_gemm_plan(int(plan_tiles), int(nq), int(kp), int(family), int(bool(f16x1)), int(blocks), int(gemm_bootstrap),
+                                            int(gemm_boot_fine), int(gemm_split_last), int(gemm_qsplit), L.np_ptr(out), cap, C.byref(n)))
+        keys = ("kind", "stride", "skip", "tile_begin", "tile_end", "qsplit", "blocks", "slots", "select")
+        plan = []
+        for w in out[:int(n.value)].tolist():
+            e = dict(zip(keys, w))
+            e["thresholds"], e["buffer_fits"] = bool(w[9] & 1), bool(w[9] & 2)
+            plan.append(e)
+        return plan
+
+    def debug_bootstrap_tau(self, tile_min_ptr, n_slots, nq, nq_pad, kp, tau_ptr, qconst_ptr):
+        """Test hook (smt_debug_bootstrap_tau): bootstrap_tau_kernel on device buffers, asynchronous on the context's stream."""
+        L.check(L.lib().smt_debug_bootstrap_tau(self._h, C.c_void_p(int(tile_min_ptr)), int(n_slots), int(nq), int(nq_pad), int(kp),
+                                                C.c_void_p(int(tau_ptr)), C.c_void_p(int(qconst_ptr))))
+
+    def debug_level_select(self, cand_ptr, counts_ptr, overflow_ptr, tau_ptr, nq, kp, qconst_ptr=None):
+        """Test hook (smt_debug_level_select): level_select_kernel in place on device buffers (distinct keys per query), asynchronous on
+        the context's stream."""
+        L.check(L.lib().smt_debug_level_select(self._h, C.c_void_p(int(cand_ptr)), C.c_void_p(int(counts_ptr)), C.c_void_p(int(overflow_ptr)),
+                                               C.c_void_p(int(tau_ptr)), C.c_void_p(int(qconst_ptr)) if qconst_ptr else None, int(nq), int(kp)))
+
+    def debug_gemm_trace(self, buf_ptr=None, cap_words=0):
+        """Test hook (smt_debug_gemm_trace): sets (or, without a pointer, clears) the trace buffer of batched calls; returns
+        (select passes, 32-bit words) recorded since it was last set."""
+        n, w = C.c_uint32(0), C.c_uint64(0)
+        L.check(L.lib().smt_debug_gemm_trace(self._h, C.c_void_p(int(buf_ptr)) if buf_ptr else None, int(cap_words), C.byref(n), C.byref(w)))
+        return int(n.value), int(w.value)
+
 
 class Model:
     """Device-resident model2vec table (smt_model)."""
@@ -686,11 +723,12 @@ class Corpus:
         L.check(L.lib().smt_debug_batched_scores(self._h, L.np_ptr(q), q.shape[0], int(first_row), n_rows, L.np_ptr(out)))
         return out[:, :q.shape[0]].copy()
 
-    def debug_nominations(self, queries, tau=None, buffered=False, ranges=None, top_k=10):
+    def debug_nominations(self, queries, tau=None, buffered=False, ranges=None, top_k=10, level=None):
         """Test hook (smt_debug_nominations): what the PRODUCTION kernels of a batched top_k call over this corpus nominate in one
         level over all tiles, under the distance thresholds tau (one per query; None = +inf, admit everything).  Returns
         (dist float32 [rows, nq], NaN where the pair was not nominated; hits uint32 [rows, nq], the keys that named the pair;
-        counts uint32 [ceil(nq / 32) * 32], raw per query, padding queries included; route, see the header)."""
+        counts uint32 [ceil(nq / 32) * 32], raw per query, padding queries included; route, see the header).
+        level = (stride, skip, tile_begin, tile_end): that level launch instead (smt_debug_level_nominations)."""
         q = _f32c(queries).reshape(-1, L.DIM)
         nq = q.shape[0]
         t = np.full(nq, np.inf, dtype=np.float32) if tau is None else np.ascontiguousarray(tau, dtype=np.float32).reshape(nq)
@@ -700,10 +738,29 @@ class Corpus:
         hits = np.empty((rows, nq), dtype=np.uint32)
         counts = np.empty((nq + 31) // 32 * 32, dtype=np.uint32)
         route = C.c_uint32(0)
-        L.check(L.lib().smt_debug_nominations(self._h, L.np_ptr(q), nq, int(top_k), C.cast(rng, C.c_void_p) if rng is not None else None,
-                                              n_rng, L.np_ptr(t), int(bool(buffered)), L.np_ptr(dist), L.np_ptr(hits), L.np_ptr(counts),
-                                              C.byref(route)))
+        rng_p = C.cast(rng, C.c_void_p) if rng is not None else None
+        if level is None:
+            L.check(L.lib().smt_debug_nominations(self._h, L.np_ptr(q), nq, int(top_k), rng_p, n_rng, L.np_ptr(t), int(bool(buffered)),
+                                                  L.np_ptr(dist), L.np_ptr(hits), L.np_ptr(counts), C.byref(route)))
+        else:
+            stride, skip, tile_begin, tile_end = (int(v) for v in level)
+            L.check(L.lib().smt_debug_level_nominations(self._h, L.np_ptr(q), nq, int(top_k), rng_p, n_rng, L.np_ptr(t), int(bool(buffered)),
+                                                        stride, skip, tile_begin, tile_end, L.np_ptr(dist), L.np_ptr(hits),
+                                                        L.np_ptr(counts), C.byref(route)))
         return dist, hits, counts, int(route.value)
+
+    def debug_bootstrap_minima(self, queries, ranges=None, top_k=10):
+        """Test hook (smt_debug_bootstrap_minima): the bootstrap launch of the batched top_k call over this corpus.  Returns
+        (tile_min float32 [slots, ceil(nq / 32) * 32], the bootstrap stride, route)."""
+        q = _f32c(queries).reshape(-1, L.DIM)
+        nq = q.shape[0]
+        nq_pad = (nq + 31) // 32 * 32
+        rng, n_rng = _ranges_arg(ranges)
+        out = np.empty((1024, nq_pad), dtype=np.float32)
+        slots, stride, route = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+        L.check(L.lib().smt_debug_bootstrap_minima(self._h, L.np_ptr(q), nq, int(top_k), C.cast(rng, C.c_void_p) if rng is not None else None,
+                                                   n_rng, L.np_ptr(out), C.byref(slots), C.byref(stride), C.byref(route)))
+        return out[:int(slots.value)].copy(), int(stride.value), int(route.value)
 
     def debug_scan_lists(self, queries, top_k, ranges=None, cap_keys=None):
         """Test hook (smt_debug_scan_lists): the block lists the scan stage writes for a synchronous top_k call of 1..8 queries under

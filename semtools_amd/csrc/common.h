@@ -169,6 +169,10 @@ struct smt_ctx {
     uint64_t deliveries = 0;                 // host-form searches answered that way (smt_debug_deliveries)
     uint64_t compact_calls = 0;              // smt_corpus_compact calls that succeeded on this context, and the rows they moved (smt_ctx_compact_stats)
     uint64_t compact_rows_moved = 0;
+    // smt_debug_gemm_trace: while set, launch_gemm_topk copies what its selects read and publish into this device buffer (32-bit words)
+    uint32_t *d_gemm_trace = nullptr;
+    uint64_t gemm_trace_cap = 0, gemm_trace_used = 0;   // words
+    uint32_t gemm_trace_selects = 0;                     // select passes seen since the buffer was set, recorded or not
     bool prof_on = false;
     // kernels whose >64 KiB dynamic-LDS attribute has been set ON THIS DEVICE (bit per kernel family, smt::ATTR_*).
     // Per context, not per process: hipFuncSetAttribute applies to the current device's copy of the function, and a
@@ -600,10 +604,50 @@ int launch_gemm_threshold(smt_ctx *ctx, const float *corpus, uint64_t rows, cons
                           const float *queries, uint32_t nq, const float *tau, const key_t64 **cand_out,
                           const unsigned int **counts_out, uint32_t *cand_stride, uint32_t cap = 2048 /* CAND_CAP */,
                           key_t64 *cand_ext = nullptr, unsigned int *counts_ext = nullptr);
-// test hook: what the production kernels of a batched call's route nominate in ONE level over all tiles, under the caller's
+// THE LEVEL PLAN of a batched call (gemm_topk.hip gemm_level_plan): the ordered launches launch_gemm_topk makes, as a pure function of
+// what they depend on.  launch_gemm_topk walks the result; smt_debug_gemm_plan returns it (tests/test_level_plan_cpu.py, no GPU).
+struct GemmPlanInput {
+    uint64_t plan_tiles;   // tiles of the call: 32-row tiles, entries of the tile table, or groups of 8 chunk-table entries
+    uint32_t nq, kp;
+    int family;            // 0 row-register, 1 LDS-row, 2 level kernel (the codes of launch_gemm_debug_nominations' route)
+    bool f16x1;
+    int blocks;            // tuning key gemm_blocks, or the CU count
+    int bootstrap, boot_fine, split_last, qsplit;   // tuning keys gemm_bootstrap, gemm_boot_fine, gemm_split_last, gemm_qsplit
+};
+struct GemmPlanLaunch {
+    bool bootstrap;        // tile minima only (GemmParams::tile_min), bootstrap_tau_kernel behind it; else appended to the candidate lists
+    uint64_t stride;       // GemmParams::stride
+    int skip;              // GemmParams::skip16
+    uint64_t tile_begin, tile_end;   // level tile indices [tile_begin, tile_end): GemmParams::tile_begin, level_tiles (empty: no launch)
+    uint32_t qsplit;       // GemmParams::qsplit
+    int nb;                // blocks of the launch
+    uint32_t slots;        // bootstrap: slots of tile_min
+    bool select;           // a select pass follows: bootstrap_tau_kernel resp. level_select_kernel
+    bool thresholds;       // the launch runs under thresholds an earlier select published
+    bool buffer_fits;      // row-register kernel: its nominations may go through the waves' LDS buffers (GemmParams::buffered, with gemm_buffered)
+};
+std::vector<GemmPlanLaunch> gemm_level_plan(const GemmPlanInput &in);
+
+// One level of a test hook's launch (launch_gemm_debug_nominations): GemmParams::stride, skip16, tile_begin, level_tiles.
+struct GemmDebugLevel {
+    uint64_t stride = 1;
+    int skip = 0;
+    uint64_t tile_begin = 0;
+    uint64_t tile_end = UINT64_MAX;   // UINT64_MAX: every tile of the call (stride 1, skip 0)
+};
+// test hook: what the production kernels of a batched call's route nominate in ONE level launch, under the caller's
 // thresholds (gemm_topk.hip): keys [ceil(nq / 32) * 32][2048] and raw counts in scratch, padding queries included
-int launch_gemm_debug_nominations(smt_ctx *ctx, const ScanArgs &a, const float *tau_dev, int buffered, const key_t64 **cand_out,
-                                  const unsigned int **counts_out, uint32_t *route_out);
+int launch_gemm_debug_nominations(smt_ctx *ctx, const ScanArgs &a, const float *tau_dev, int buffered, const GemmDebugLevel &level,
+                                  const key_t64 **cand_out, const unsigned int **counts_out, uint32_t *route_out);
+// test hook: the bootstrap launch of a real batched call over `a` (head launch with the +inf fill, gemm_rowreg_kernel with tile_min, both
+// as launch_gemm_topk plans them); tile_min [slots][ceil(nq / 32) * 32] in scratch
+int launch_gemm_debug_bootstrap(smt_ctx *ctx, const ScanArgs &a, const float **tile_min_out, uint32_t *slots_out, uint64_t *stride_out,
+                                uint32_t *route_out);
+// test hooks: bootstrap_tau_kernel and level_select_kernel on the caller's device buffers, launched as launch_gemm_topk launches them
+int launch_debug_bootstrap_tau(smt_ctx *ctx, const float *tile_min, uint32_t n_slots, uint32_t nq, uint32_t nq_pad, uint32_t kp, float *tau,
+                               float *qconst);
+int launch_debug_level_select(smt_ctx *ctx, key_t64 *cand, unsigned int *counts, unsigned int *overflow, float *tau, float *qconst,
+                              uint32_t nq, uint32_t kp);
 // test hook: the nominating f32 distances of the K3 kernels for <= 32 queries (gemm_topk.hip)
 int launch_gemm_debug_scores(smt_ctx *ctx, const float *corpus, uint64_t first_row, uint32_t n_rows, const float *queries,
                              uint32_t nq, float *out);

@@ -67,7 +67,8 @@ struct GemmParams {
     unsigned long long *stamps;   // trace builds only (SMT_RR_EXP & 256, tools/exp_k3_trace.sh): s_memtime stamps of one block
 };
 
-__device__ __forceinline__ uint64_t level_tile(uint64_t i, uint64_t stride, int skip16)
+// (also on the host: the test hooks check a caller's level against the tiles there are before they launch it)
+__host__ __device__ __forceinline__ uint64_t level_tile(uint64_t i, uint64_t stride, int skip16)
 {
     if (!skip16) return i * stride;
     // i-th positive integer that is not a multiple of the ratio (constant divisors: no runtime division)

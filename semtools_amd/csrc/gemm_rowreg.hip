@@ -522,8 +522,10 @@ __global__ void __launch_bounds__(RR_THREADS, 2) gemm_rowreg_kernel(GemmParams p
                 const bool zero_row = __builtin_amdgcn_ballot_w64((zero16 & valid16) != 0u) != 0ull;   // simsimd: 0 against a zero row, else 1
                 const float d = qc.y == 0.0f ? (zero_row ? 0.0f : 1.0f) : fmaxf(1.0f - m * qc.y, 0.0f);
                 // slot = level tile index mod 1024: the tiles that share a slot are distinct (so are their best rows), the slot keeps
-                // their minimum -- a fire-and-forget atomic (distances are >= 0: their bit patterns order like unsigned integers)
-                if (h == 0)
+                // their minimum -- a fire-and-forget atomic (distances are >= 0: their bit patterns order like unsigned integers).
+                // Only for queries there are: a padding query of the last query tile has rq == 0 and would store the zero query's 0 / 1
+                // into a column nobody asked for (tests/test_gpu_level_stage.py: the padding columns keep the head launch's +inf)
+                if (h == 0 && qt * QT_ROWS + (uint32_t)j < p.nq)
                     (void)__hip_atomic_fetch_min(reinterpret_cast<unsigned int *>(p.tile_min) + (size_t)(it & 1023u) * ((size_t)p.nqt * QT_ROWS) +
                                                      (size_t)qt * QT_ROWS + j,
                                                  __float_as_uint(d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -193,7 +193,13 @@ __global__ void __launch_bounds__(1024) level_select_kernel(LevelSelectParams p)
     if (threadIdx.x < p.kp) buf[threadIdx.x] = s_best[threadIdx.x];
     if (threadIdx.x == 0) {
         p.counts[q] = n < p.kp ? n : p.kp;
-        const float tau = n >= p.kp ? __uint_as_float((unsigned)(s_best[p.kp - 1] >> 32)) : __builtin_inff();
+        // A threshold NEVER RISES: the one in force (+inf at the head of a call) bounds the final kp-th distance whatever this pass
+        // found.  The select between the two parts of a level can find fewer than kp candidates -- a bootstrap over every 2nd tile
+        // leaves ~2 k' rows under its threshold, the first quarter of the level holds ~k'/2 of them -- and used to publish +inf there:
+        // the rest of the level was appended whole, the buffers overflowed and every query was re-answered (tests/test_gpu_level_stage.py,
+        // the split-level case).
+        const float found = n >= p.kp ? __uint_as_float((unsigned)(s_best[p.kp - 1] >> 32)) : __builtin_inff();
+        const float tau = fminf(found, p.tau[q]);
         p.tau[q] = tau;
         if (p.qconst) p.qconst[2 * q] = score_threshold(tau, p.qconst[2 * q + 1]);
     }
@@ -455,6 +461,210 @@ static int gemm_prepare_queries(smt_ctx *ctx, const GemmRoute &r, const ScanArgs
     return SMT_OK;
 }
 
+// LEVEL PLAN.  A level = every stride-th tile that no coarser level has visited (`skip` = the ratio to the coarser level: the
+// multiples of it are left out; 0 = none left out), appended under the thresholds the levels before it produced.
+//  * appended-levels plan (rounds 1-3; the f32 / LDS-row kernels, gemm_bootstrap = 0): strides 16^(L-1) ... 16, 1, the first level
+//    <= LEVEL0_MAX_TILES tiles appended without a threshold.
+//  * bootstrap plan (gemm_rowreg_kernel, round 4): a bootstrap level of tile minima gives the first thresholds; then
+//      <= 2048 tiles: bootstrap over ALL tiles, one appended level over all of them (twice the work of a corpus of <= 64 k rows);
+//      <= 128 Ki tiles: bootstrap over every 2nd / 4th / 8th / 16th (4 Ki / 8 Ki / 32 Ki / 128 Ki tiles), one appended level over ALL tiles;
+//      larger: bootstrap over every 64th (x 16 while more than BOOTSTRAP_MAX_TILES are left), appended levels at strides
+//      ... 64, 4 -- the first visits every multiple of its stride, the bootstrap's tiles included -- and a LAST level of
+//      ratio 4: the 3/4 of the corpus it holds are appended under thresholds a quarter of the corpus produced (~4 k' rows per
+//      query), and the level before it is a quarter of the corpus -- no level is thin any more.  (Rounds 2-3 had a 1/16 level
+//      whose ~16 k' admissions per query fell on 6 % of the products -- 0.87 nominations per product against 0.06 in the main
+//      level -- and a main level split in two to tighten its thresholds after an eighth: profiles/r04_k3/.)
+// The result is the ordered list of launches; launch_gemm_topk walks it and smt_debug_gemm_plan hands it out, so that what
+// tests/test_level_plan_cpu.py proves of it (every tile in exactly one appended launch: the distinct keys level_select_kernel needs) is
+// proved of production.  A pure function: no context, no device.
+std::vector<GemmPlanLaunch> gemm_level_plan(const GemmPlanInput &in)
+{
+    const uint64_t plan_tiles = in.plan_tiles, n_tiles = in.plan_tiles;
+    const bool rowreg = in.family == 0, lds_rows = in.family == 1;
+    const uint32_t nqt = (in.nq + QT_ROWS - 1) / QT_ROWS, kp = in.kp;
+    const int blocks = in.blocks;
+    // blocks of a launch and its query split, for a level of n tiles
+    const uint64_t waves = rowreg ? RR_WAVES : lds_rows ? LR_WAVES : GEMM_WAVES;
+    auto shape = [&](uint64_t n, GemmPlanLaunch &e) {
+        e.qsplit = 1;
+        e.nb = 0;
+        if (n == 0) return;
+        const uint64_t need_blocks = (n + waves - 1) / waves;
+        e.nb = (int)std::min<uint64_t>((uint64_t)blocks, need_blocks);
+        // a level with fewer row-tile groups than CUs is a latency-bound sweep over the query tiles: spread the query tiles over
+        // about two blocks per CU (the LDS-row kernel keeps its queries resident: no split)
+        if (!lds_rows && in.qsplit && need_blocks < (uint64_t)blocks) {
+            e.qsplit = (uint32_t)std::min<uint64_t>(nqt, std::max<uint64_t>(1, (uint64_t)2 * blocks / need_blocks));
+            e.nb = (int)(need_blocks * e.qsplit);
+        }
+    };
+    std::vector<GemmPlanLaunch> out;
+    const bool bootstrap = rowreg && plan_tiles > (uint64_t)LEVEL0_MAX_TILES && in.bootstrap != 0;
+    const int LEVEL_RATIO = kp <= LEVEL_RATIO_KP_LIMIT ? LEVEL_RATIO_SMALL_K : LEVEL_RATIO_LARGE_K;
+    struct PlanLevel { uint64_t stride; int skip; };
+    std::vector<PlanLevel> plan;
+    if (bootstrap) {
+        // Bootstrap stride: every tile up to 2048 tiles; every 16th up to 128 Ki tiles (4 M rows) -- ONE appended level over all tiles
+        // follows; beyond that every 64th (x 16 until <= BOOTSTRAP_MAX_TILES tiles are left).
+        uint64_t boot_stride = 1;
+        if (plan_tiles > 2048) {
+            // Graded since the end of round 5 (tools/ab_boot_stride.py, profiles/r05_boot_stride.txt; ms per call, 1000 queries, every 16th
+            // tile | the stride below): 66 k rows 0.67 | 0.44, 131 k 0.53 | 0.41, 262 k 0.59 | 0.51, 524 k 0.75 | 0.69, 1 M 1.01 | 1.02; 256
+            // queries 66 k 0.27 | 0.19, 262 k 0.30 | 0.21, 524 k 0.34 | 0.26 -- a 1/16 sample of a SMALL corpus leaves thresholds that admit
+            // 16 k' rows per query into few tiles (4 nominations per product at 2050 tiles), and the bootstrap's own pass is cheap there.
+            // (tuning key gemm_boot_fine = 0: every 16th tile up to 131 072 tiles, as in round 4)
+            boot_stride = !in.boot_fine ? (plan_tiles <= (uint64_t)131072 ? 16 : 64)
+                          : plan_tiles <= 4096 ? 2 : plan_tiles <= 8192 ? 4 : plan_tiles <= 32768 ? 8 : plan_tiles <= (uint64_t)131072 ? 16 : 64;
+            while ((plan_tiles + boot_stride - 1) / boot_stride > (uint64_t)BOOTSTRAP_MAX_TILES) boot_stride *= 16;
+        }
+        const uint64_t boot_tiles = (plan_tiles + boot_stride - 1) / boot_stride;
+        // ---- BOOTSTRAP: every boot_stride-th tile, tile minima only, then the first thresholds; the appended levels start at
+        // stride boot_stride / ratio (or 1) and their first one visits EVERY multiple of its stride, the bootstrap's tiles included
+        // (1/ratio of that level: the price of a level without candidate lists)
+        GemmPlanLaunch b{};
+        b.bootstrap = true;
+        b.stride = boot_stride;
+        b.skip = 0;
+        b.tile_begin = 0;
+        b.tile_end = boot_tiles;
+        shape(boot_tiles, b);
+        b.slots = (uint32_t)std::min<uint64_t>(boot_tiles, BOOTSTRAP_SLOTS);
+        b.select = true;
+        b.thresholds = false;
+        b.buffer_fits = false;
+        out.push_back(b);
+        if (boot_stride <= 16) plan.push_back({1, 0});
+        else {
+            uint64_t st = boot_stride / 16;           // 4 x 16^j
+            plan.push_back({st, 0});
+            while (st > 4) { st /= 16; plan.push_back({st, 16}); }
+            plan.push_back({1, 4});
+        }
+    } else {
+        uint64_t s0 = 1;
+        while ((n_tiles + s0 - 1) / s0 > (uint64_t)LEVEL0_MAX_TILES) s0 *= LEVEL_RATIO;
+        plan.push_back({s0, 0});
+        for (uint64_t st = s0; st > 1;) { st /= LEVEL_RATIO; plan.push_back({st, LEVEL_RATIO}); }
+    }
+    const int L = (int)plan.size();
+
+    for (int lev = 0; lev < L; ++lev) {
+        const uint64_t stride = plan[lev].stride;
+        const int skip = plan[lev].skip;
+        const uint64_t multiples = (n_tiles + stride - 1) / stride;                        // u in [0, multiples)
+        const uint64_t parents = skip == 0 ? 0 : (multiples + (uint64_t)skip - 1) / (uint64_t)skip;   // u % skip == 0: visited before
+        const uint64_t level_end = multiples - parents;
+        GemmPlanLaunch e{};
+        e.bootstrap = false;
+        e.stride = stride;
+        e.skip = skip;
+        e.tile_begin = 0;
+        e.tile_end = level_end;
+        shape(level_end, e);
+        e.slots = 0;
+        e.select = true;
+        e.thresholds = lev > 0 || bootstrap;
+        e.buffer_fits = true;
+        uint64_t part_end = level_end;
+        if (level_end > 0 && rowreg) {
+            // THE LAST LEVEL IN TWO PARTS when it is MFMA-bound (a streamed sweep): its thresholds come from a 1/ratio sample and
+            // admit ~ratio x k' rows per query -- 12 % of the (row tile, query tile) products of a 1000 x 10 M batch nominate
+            // something, and a nominating wave holds its block's other seven at the ring barrier (wave timeline: 63 % of the
+            // barriers had such a straggler).  After the first eighth of the level a select pass tightens the thresholds to what
+            // 18 % of the rows know (~3 x fewer nominations for the remaining 7/8); it costs one more launch and select pass.
+            // the LDS nomination buffer pays where a wave's sweep nominates fewer pairs than it holds (a level admits ~ratio x k'
+            // rows per query): the thin early levels go straight to the lists, one slot grab per lane and tile -- fewer atomics
+            // on the same thousand counters, which is what those levels are bound by
+            const int admit_ratio = skip ? skip : 16;   // rows admitted per query ~ admit_ratio x k'
+            if ((double)admit_ratio * kp * in.nq / ((double)level_end * e.qsplit) > 0.75 * RR_CB_CAP) e.buffer_fits = false;
+            // ... and the FIRST appended level of a bootstrap plan (the quarter-corpus level) likewise: its thresholds come from the
+            // bootstrap's 1/64 sample (~16 k' admissions per query, 0.2 nominations per product); after its first quarter a select
+            // pass tightens them to what 1/16 of the corpus knows.  Timelines on one box (1000 x 10 M, image): 1598 -> 431 + 1061 us
+            // for the level and 42 -> 11 + 9 us of select: 5.82 -> 5.69 ms per call (-2.3 %); from f32 rows 6.55 -> 6.42; 512
+            // queries 3.27 -> 3.16.  The same for the ONE appended level of a mid-sized corpus (<= 128 Ki tiles: bootstrap over every
+            // 16th tile, then everything under ~16 k' admissions per query): 1000 x 1 M 867 -> 803 us, x 2 M 1441 -> 1347, x 4 M
+            // 2513 -> 2428, 512 x 1 M 512 -> 482.  (Tuning key gemm_split_last: 0 none, 1 a ratio-16 last level only, 2 both.)
+            const bool first_after_boot = in.split_last >= 2 && bootstrap && lev == 0;   // (also when it is the only level)
+            const bool split_level = lev == L - 1 || first_after_boot;
+            if (in.split_last && split_level && (lev > 0 || bootstrap) && admit_ratio >= 16 && nqt > (uint32_t)(in.f16x1 ? RrGeom<2>::SLOTS : RR_SLOTS) &&
+                level_end >= (uint64_t)(first_after_boot ? 12 : 64) * blocks * RR_WAVES)
+                part_end = (level_end / (first_after_boot ? 4 : 8) + (uint64_t)blocks * RR_WAVES - 1) / ((uint64_t)blocks * RR_WAVES) * ((uint64_t)blocks * RR_WAVES);
+        }
+        if (part_end != level_end) {   // two launches with the level's shape, a select pass behind each
+            e.tile_end = part_end;
+            out.push_back(e);
+            e.tile_begin = part_end;
+            e.tile_end = level_end;
+        }
+        out.push_back(e);
+    }
+    return out;
+}
+
+// The bootstrap launch of a plan: gemm_rowreg_kernel over every stride-th tile with tile_min set (no nominations).  Shared by
+// launch_gemm_topk and the test hook that returns the slot minima (launch_gemm_debug_bootstrap).
+static GemmParams gemm_bootstrap_params(const ScanArgs &a, const GemmRoute &r, const GemmPlanLaunch &e, const uint32_t *q_split, float *tau,
+                                        float *qconst, key_t64 *cand, unsigned int *counts, const uint64_t *tile_table, float *tile_min)
+{
+    GemmParams g;
+    memset(&g, 0, sizeof(g));
+    g.corpus = a.corpus;
+    g.n_rows = a.rows;
+    g.queries = a.queries;
+    g.queries_split = q_split;
+    g.nq = a.nq;
+    g.nqt = r.nqt;
+    g.level_tiles = e.tile_end;
+    g.tile_begin = e.tile_begin;
+    g.stride = e.stride;
+    g.skip16 = e.skip;
+    g.qsplit = e.qsplit;
+    g.tau = tau;
+    g.qconst = qconst;
+    g.cand = cand;
+    g.counts = counts;
+    g.tile_table = tile_table;
+    g.tile_min = tile_min;
+    g.image = r.use_image ? a.image : nullptr;
+    g.image_zero = r.use_image ? a.image_zero : nullptr;
+    return g;
+}
+
+// The trace tap of launch_gemm_topk (smt_debug_gemm_trace): a host-side enqueue of device-to-device copies, nothing when no buffer is
+// set.  Per select pass nq count words as the select finds them, then nq tau words as it leaves them; at the end of the call nq overflow
+// words and the kp keys at the head of every query's buffer.  A record that does not fit is left out; the passes are counted all the same.
+struct GemmTrace {
+    smt_ctx *ctx;
+    uint32_t nq;
+    const unsigned int *counts;
+    const float *tau;
+    int put(const void *src, size_t words)
+    {
+        if (ctx->gemm_trace_used + words > ctx->gemm_trace_cap) { ctx->gemm_trace_used = ctx->gemm_trace_cap + 1; return SMT_OK; }
+        SMT_HIP_CHECK(hipMemcpyAsync(ctx->d_gemm_trace + ctx->gemm_trace_used, src, words * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->gemm_trace_used += words;
+        return SMT_OK;
+    }
+    int before_select()
+    {
+        if (ctx->d_gemm_trace == nullptr) return SMT_OK;
+        ++ctx->gemm_trace_selects;
+        return put(counts, nq);
+    }
+    int after_select() { return ctx->d_gemm_trace == nullptr ? SMT_OK : put(tau, nq); }
+    int end_of_call(const key_t64 *cand, const unsigned int *overflow, uint32_t kp)
+    {
+        if (ctx->d_gemm_trace == nullptr) return SMT_OK;
+        if (int rc = put(overflow, nq)) return rc;
+        const size_t words = (size_t)nq * kp * 2;
+        if (ctx->gemm_trace_used + words > ctx->gemm_trace_cap) { ctx->gemm_trace_used = ctx->gemm_trace_cap + 1; return SMT_OK; }
+        SMT_HIP_CHECK(hipMemcpy2DAsync(ctx->d_gemm_trace + ctx->gemm_trace_used, (size_t)kp * sizeof(key_t64), cand, (size_t)CAND_CAP * sizeof(key_t64),
+                                       (size_t)kp * sizeof(key_t64), nq, hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->gemm_trace_used += words;
+        return SMT_OK;
+    }
+};
+
 int launch_gemm_topk(smt_ctx *ctx, const ScanArgs &a)
 {
     if (a.k_out + 8 > 64 || a.k_out < 1) { set_error("batched path: top_k must be in [1, 56]"); return SMT_E_UNSUPPORTED; }
@@ -497,26 +707,16 @@ int launch_gemm_topk(smt_ctx *ctx, const ScanArgs &a)
     const size_t b_split = bf16 ? (size_t)nqt * QT_ROWS * 1024 : 0;
     const size_t o_split = (b_cand + 2 * b_cnt + 3 * b_tau + 255) & ~(size_t)255;  // tau | thr | rq
     const size_t b_head = o_split + b_split;
-    // the row-register kernel's bootstrap level: every s0-th tile, at most BOOTSTRAP_MAX_TILES of them (level plan below)
+    // the launches of the call (gemm_level_plan above); the row-register kernel's bootstrap level, when there is one, comes first
     const uint64_t plan_tiles = !filtered ? (a.rows + 31) / 32 : rowreg ? n_chunks : (n_chunks + 7) / 8;
-    const bool bootstrap = rowreg && plan_tiles > (uint64_t)LEVEL0_MAX_TILES && ctx->tune.gemm_bootstrap != 0;
-    // Bootstrap stride (see the level plan below): every tile up to 2048 tiles; every 16th up to 128 Ki tiles (4 M rows) -- ONE
-    // appended level over all tiles follows; beyond that every 64th (x 16 until <= BOOTSTRAP_MAX_TILES tiles are left).
-    uint64_t boot_stride = 1;
-    if (bootstrap && plan_tiles > 2048) {
-        // Graded since the end of round 5 (tools/ab_boot_stride.py, profiles/r05_boot_stride.txt; ms per call, 1000 queries, every 16th
-        // tile | the stride below): 66 k rows 0.67 | 0.44, 131 k 0.53 | 0.41, 262 k 0.59 | 0.51, 524 k 0.75 | 0.69, 1 M 1.01 | 1.02; 256
-        // queries 66 k 0.27 | 0.19, 262 k 0.30 | 0.21, 524 k 0.34 | 0.26 -- a 1/16 sample of a SMALL corpus leaves thresholds that admit
-        // 16 k' rows per query into few tiles (4 nominations per product at 2050 tiles), and the bootstrap's own pass is cheap there.
-        // (tuning key gemm_boot_fine = 0: every 16th tile up to 131 072 tiles, as in round 4)
-        boot_stride = !ctx->tune.gemm_boot_fine ? (plan_tiles <= (uint64_t)131072 ? 16 : 64)
-                      : plan_tiles <= 4096 ? 2 : plan_tiles <= 8192 ? 4 : plan_tiles <= 32768 ? 8 : plan_tiles <= (uint64_t)131072 ? 16 : 64;
-        while ((plan_tiles + boot_stride - 1) / boot_stride > (uint64_t)BOOTSTRAP_MAX_TILES) boot_stride *= 16;
-    }
-    const uint64_t boot_tiles = bootstrap ? (plan_tiles + boot_stride - 1) / boot_stride : 0;
+    const int blocks = ctx->tune.gemm_blocks > 0 ? ctx->tune.gemm_blocks : ctx->num_cus;
+    const std::vector<GemmPlanLaunch> plan = gemm_level_plan(GemmPlanInput{plan_tiles, a.nq, kp, rowreg ? 0 : lds_rows ? 1 : 2, f16x1, blocks,
+                                                                            ctx->tune.gemm_bootstrap, ctx->tune.gemm_boot_fine,
+                                                                            ctx->tune.gemm_split_last, ctx->tune.gemm_qsplit});
+    const bool bootstrap = plan.front().bootstrap;
+    const uint64_t boot_slots = bootstrap ? plan.front().slots : 0;
     const size_t o_table = (b_head + 255) & ~(size_t)255;
     const size_t o_tmin = (o_table + (size_t)n_chunks * sizeof(uint64_t) + 255) & ~(size_t)255;
-    const uint64_t boot_slots = std::min<uint64_t>(boot_tiles, BOOTSTRAP_SLOTS);
     int rc = ensure_scratch(ctx, o_tmin + (size_t)boot_slots * nqt * QT_ROWS * sizeof(float) + 64);
     if (rc) return rc;
     char *base = reinterpret_cast<char *>(ctx->d_scratch);
@@ -540,82 +740,39 @@ int launch_gemm_topk(smt_ctx *ctx, const ScanArgs &a)
         if ((rc = range_tile_table(ctx, a, chunk_table, &use_table))) return rc;
     } else if (filtered && (rc = range_chunk_table(ctx, a, chunk_table, &use_table))) return rc;
 
-    // LEVEL PLAN.  A level = every stride-th tile that no coarser level has visited (`skip` = the ratio to the coarser level: the
-    // multiples of it are left out; 0 = none left out), appended under the thresholds the levels before it produced.
-    //  * appended-levels plan (rounds 1-3; the f32 / LDS-row kernels, gemm_bootstrap = 0): strides 16^(L-1) ... 16, 1, the first level
-    //    <= LEVEL0_MAX_TILES tiles appended without a threshold.
-    //  * bootstrap plan (gemm_rowreg_kernel, round 4): a bootstrap level of tile minima gives the first thresholds; then
-    //      <= 2048 tiles: bootstrap over ALL tiles, one appended level over all of them (twice the work of a corpus of <= 64 k rows);
-    //      <= 128 Ki tiles: bootstrap over every 2nd / 4th / 8th / 16th (4 Ki / 8 Ki / 32 Ki / 128 Ki tiles), one appended level over ALL tiles;
-    //      larger: bootstrap over every 64th (x 16 while more than BOOTSTRAP_MAX_TILES are left), appended levels at strides
-    //      ... 64, 4 -- the first visits every multiple of its stride, the bootstrap's tiles included -- and a LAST level of
-    //      ratio 4: the 3/4 of the corpus it holds are appended under thresholds a quarter of the corpus produced (~4 k' rows per
-    //      query), and the level before it is a quarter of the corpus -- no level is thin any more.  (Rounds 2-3 had a 1/16 level
-    //      whose ~16 k' admissions per query fell on 6 % of the products -- 0.87 nominations per product against 0.06 in the main
-    //      level -- and a main level split in two to tighten its thresholds after an eighth: profiles/r04_k3/.)
-    const int LEVEL_RATIO = kp <= LEVEL_RATIO_KP_LIMIT ? LEVEL_RATIO_SMALL_K : LEVEL_RATIO_LARGE_K;
-    const uint64_t n_tiles = plan_tiles;
-    struct PlanLevel { uint64_t stride; int skip; };
-    std::vector<PlanLevel> plan;
-    int blocks = ctx->tune.gemm_blocks > 0 ? ctx->tune.gemm_blocks : ctx->num_cus;
-    if (bootstrap) {
-        // ---- BOOTSTRAP: every boot_stride-th tile, tile minima only, then the first thresholds; the appended levels start at
-        // stride boot_stride / ratio (or 1) and their first one visits EVERY multiple of its stride, the bootstrap's tiles included
-        // (1/ratio of that level: the price of a level without candidate lists)
-        GemmParams g;
-        memset(&g, 0, sizeof(g));
-        g.corpus = a.corpus;
-        g.n_rows = a.rows;
-        g.queries = a.queries;
-        g.queries_split = q_split;
-        g.nq = a.nq;
-        g.nqt = nqt;
-        g.level_tiles = boot_tiles;
-        g.tile_begin = 0;
-        g.stride = boot_stride;
-        g.skip16 = 0;
-        g.qsplit = 1;
-        g.tau = tau;
-        g.qconst = qconst;
-        g.cand = cand;
-        g.counts = counts;
-        g.tile_table = filtered ? use_table : nullptr;
-        g.tile_min = tile_min;
-        g.image = use_image ? a.image : nullptr;
-        g.image_zero = use_image ? a.image_zero : nullptr;
-        const uint64_t need_blocks = (boot_tiles + RR_WAVES - 1) / RR_WAVES;
-        int nb = (int)std::min<uint64_t>((uint64_t)blocks, need_blocks);
-        if (ctx->tune.gemm_qsplit && need_blocks < (uint64_t)blocks) {
-            g.qsplit = (uint32_t)std::min<uint64_t>(nqt, std::max<uint64_t>(1, (uint64_t)2 * blocks / need_blocks));
-            nb = (int)(need_blocks * g.qsplit);
-        }
-        prof_begin(ctx, "gemm");
-        gemm_rowreg_launch(ctx, f16x1 ? 2 : f16x2 ? 1 : 0, use_image, nb, g);
-        prof_end(ctx, "gemm");
+    // The selects of the call: level_select_kernel behind every appended launch, bootstrap_tau_kernel behind the bootstrap's.  With a
+    // trace buffer set (smt_debug_gemm_trace) the counts each of them reads and the tau it publishes are copied out around it.
+    GemmTrace trace{ctx, a.nq, counts, tau};
+    auto level_select = [&](float *select_qconst) {
+        LevelSelectParams ls;
+        ls.cand = cand;
+        ls.counts = counts;
+        ls.tau = tau;
+        ls.overflow = overflow;
+        ls.kp = kp;
+        ls.qconst = select_qconst;
+        if ((rc = trace.before_select())) return;
         prof_begin(ctx, "select");
-        hipLaunchKernelGGL(bootstrap_tau_kernel, dim3(nqt * QT_ROWS / 2), dim3(64), 0, ctx->stream, tile_min, (uint32_t)boot_slots, a.nq,
-                           nqt * QT_ROWS, kp, tau, qconst);
+        hipLaunchKernelGGL(level_select_kernel, dim3(a.nq), dim3(1024), 0, ctx->stream, ls);
         prof_end(ctx, "select");
-        if (boot_stride <= 16) plan.push_back({1, 0});
-        else {
-            uint64_t st = boot_stride / 16;           // 4 x 16^j
-            plan.push_back({st, 0});
-            while (st > 4) { st /= 16; plan.push_back({st, 16}); }
-            plan.push_back({1, 4});
+        rc = trace.after_select();
+    };
+    for (size_t i = 0; i < plan.size(); ++i) {
+        const GemmPlanLaunch &e = plan[i];
+        if (e.bootstrap) {
+            // ---- BOOTSTRAP: every stride-th tile, tile minima only, then the first thresholds
+            const GemmParams g = gemm_bootstrap_params(a, route, e, q_split, tau, qconst, cand, counts, filtered ? use_table : nullptr, tile_min);
+            prof_begin(ctx, "gemm");
+            gemm_rowreg_launch(ctx, f16x1 ? 2 : f16x2 ? 1 : 0, use_image, e.nb, g);
+            prof_end(ctx, "gemm");
+            if ((rc = trace.before_select())) return rc;
+            prof_begin(ctx, "select");
+            hipLaunchKernelGGL(bootstrap_tau_kernel, dim3(nqt * QT_ROWS / 2), dim3(64), 0, ctx->stream, tile_min, e.slots, a.nq,
+                               nqt * QT_ROWS, kp, tau, qconst);
+            prof_end(ctx, "select");
+            if ((rc = trace.after_select())) return rc;
+            continue;
         }
-    } else {
-        uint64_t s0 = 1;
-        while ((n_tiles + s0 - 1) / s0 > (uint64_t)LEVEL0_MAX_TILES) s0 *= LEVEL_RATIO;
-        plan.push_back({s0, 0});
-        for (uint64_t st = s0; st > 1;) { st /= LEVEL_RATIO; plan.push_back({st, LEVEL_RATIO}); }
-    }
-    const int L = (int)plan.size();
-
-    for (int lev = 0; lev < L; ++lev) {
-        const uint64_t stride = plan[lev].stride;
-        const int skip = plan[lev].skip;
-        const uint64_t multiples = (n_tiles + stride - 1) / stride;                        // u in [0, multiples)
-        const uint64_t parents = skip == 0 ? 0 : (multiples + (uint64_t)skip - 1) / (uint64_t)skip;   // u % skip == 0: visited before
         GemmParams g;
         g.corpus = a.corpus;
         g.n_rows = a.rows;
@@ -623,11 +780,11 @@ int launch_gemm_topk(smt_ctx *ctx, const ScanArgs &a)
         g.queries_split = bf16 ? q_split : nullptr;
         g.nq = a.nq;
         g.nqt = nqt;
-        g.level_tiles = multiples - parents;
-        g.tile_begin = 0;
-        g.stride = stride;
-        g.skip16 = skip;
-        g.qsplit = 1;
+        g.level_tiles = e.tile_end;
+        g.tile_begin = e.tile_begin;
+        g.stride = e.stride;
+        g.skip16 = e.skip;
+        g.qsplit = e.qsplit;
         g.tau = tau;
         g.qconst = qconst;
         g.cand = cand;
@@ -636,90 +793,23 @@ int launch_gemm_topk(smt_ctx *ctx, const ScanArgs &a)
         g.tile_table = filtered && rowreg ? use_table : nullptr;
         g.tile_min = nullptr;
         g.stamps = reinterpret_cast<unsigned long long *>(ctx->tune.scan_debug_ptr);
-        g.buffered = (lev > 0 || bootstrap) && ctx->tune.gemm_buffered != 0;   // (thresholds exist: nominations are few)
+        g.buffered = e.thresholds && ctx->tune.gemm_buffered != 0 && e.buffer_fits;   // (thresholds exist: nominations are few)
         g.image = use_image ? a.image : nullptr;
         g.image_zero = use_image ? a.image_zero : nullptr;
         g.n_chunks = n_chunks;
-        if (g.level_tiles > 0 && rowreg) {
-            const uint64_t need_blocks = (g.level_tiles + RR_WAVES - 1) / RR_WAVES;
-            int nb = (int)std::min<uint64_t>((uint64_t)blocks, need_blocks);
-            if (ctx->tune.gemm_qsplit && need_blocks < (uint64_t)blocks) {   // small levels: split the query tiles over more blocks
-                g.qsplit = (uint32_t)std::min<uint64_t>(nqt, std::max<uint64_t>(1, (uint64_t)2 * blocks / need_blocks));
-                nb = (int)(need_blocks * g.qsplit);
-            }
-            // THE LAST LEVEL IN TWO PARTS when it is MFMA-bound (a streamed sweep): its thresholds come from a 1/ratio sample and
-            // admit ~ratio x k' rows per query -- 12 % of the (row tile, query tile) products of a 1000 x 10 M batch nominate
-            // something, and a nominating wave holds its block's other seven at the ring barrier (wave timeline: 63 % of the
-            // barriers had such a straggler).  After the first eighth of the level a select pass tightens the thresholds to what
-            // 18 % of the rows know (~3 x fewer nominations for the remaining 7/8); it costs one more launch and select pass.
-            // the LDS nomination buffer pays where a wave's sweep nominates fewer pairs than it holds (a level admits ~ratio x k'
-            // rows per query): the thin early levels go straight to the lists, one slot grab per lane and tile -- fewer atomics
-            // on the same thousand counters, which is what those levels are bound by
-            const int admit_ratio = skip ? skip : 16;   // rows admitted per query ~ admit_ratio x k'
-            if ((double)admit_ratio * kp * a.nq / ((double)g.level_tiles * g.qsplit) > 0.75 * RR_CB_CAP) g.buffered = 0;
-            const uint64_t level_end = g.level_tiles;
-            uint64_t part_end = level_end;
-            // ... and the FIRST appended level of a bootstrap plan (the quarter-corpus level) likewise: its thresholds come from the
-            // bootstrap's 1/64 sample (~16 k' admissions per query, 0.2 nominations per product); after its first quarter a select
-            // pass tightens them to what 1/16 of the corpus knows.  Timelines on one box (1000 x 10 M, image): 1598 -> 431 + 1061 us
-            // for the level and 42 -> 11 + 9 us of select: 5.82 -> 5.69 ms per call (-2.3 %); from f32 rows 6.55 -> 6.42; 512
-            // queries 3.27 -> 3.16.  The same for the ONE appended level of a mid-sized corpus (<= 128 Ki tiles: bootstrap over every
-            // 16th tile, then everything under ~16 k' admissions per query): 1000 x 1 M 867 -> 803 us, x 2 M 1441 -> 1347, x 4 M
-            // 2513 -> 2428, 512 x 1 M 512 -> 482.  (Tuning key gemm_split_last: 0 none, 1 a ratio-16 last level only, 2 both.)
-            const bool first_after_boot = ctx->tune.gemm_split_last >= 2 && bootstrap && lev == 0;   // (also when it is the only level)
-            const bool split_level = lev == L - 1 || first_after_boot;
-            if (ctx->tune.gemm_split_last && split_level && (lev > 0 || bootstrap) && admit_ratio >= 16 && nqt > (uint32_t)(f16x1 ? RrGeom<2>::SLOTS : RR_SLOTS) &&
-                level_end >= (uint64_t)(first_after_boot ? 12 : 64) * blocks * RR_WAVES)
-                part_end = (level_end / (first_after_boot ? 4 : 8) + (uint64_t)blocks * RR_WAVES - 1) / ((uint64_t)blocks * RR_WAVES) * ((uint64_t)blocks * RR_WAVES);
-            for (;;) {
-                g.level_tiles = part_end;
-                prof_begin(ctx, "gemm");
-                gemm_rowreg_launch(ctx, f16x1 ? 2 : f16x2 ? 1 : 0, use_image, nb, g);
-                prof_end(ctx, "gemm");
-                if (part_end == level_end) break;
-                LevelSelectParams mid;
-                mid.cand = cand;
-                mid.counts = counts;
-                mid.tau = tau;
-                mid.overflow = overflow;
-                mid.kp = kp;
-                mid.qconst = qconst;
-                prof_begin(ctx, "select");
-                hipLaunchKernelGGL(level_select_kernel, dim3(a.nq), dim3(1024), 0, ctx->stream, mid);
-                prof_end(ctx, "select");
-                g.tile_begin = part_end;
-                part_end = level_end;
-            }
-        } else if (g.level_tiles > 0 && lds_rows) {
-            const uint64_t need_blocks = (g.level_tiles + LR_WAVES - 1) / LR_WAVES;
-            const int nb = (int)std::min<uint64_t>((uint64_t)blocks, need_blocks);
+        if (e.tile_end > e.tile_begin) {
             prof_begin(ctx, "gemm");
-            gemm_ldsrow_launch(ctx, bf16, nqt, filtered, ctx->tune.gemm_dma_nt != 0, nb, g);
-            prof_end(ctx, "gemm");
-        } else if (g.level_tiles > 0) {
-            const uint64_t need_blocks = (g.level_tiles + GEMM_WAVES - 1) / GEMM_WAVES;
-            int nb = (int)std::min<uint64_t>((uint64_t)blocks, need_blocks);
-            // a level with fewer row-tile groups than CUs is a latency-bound sweep over the query tiles:
-            // spread the query tiles over about two blocks per CU
-            if (ctx->tune.gemm_qsplit && need_blocks < (uint64_t)blocks) {
-                g.qsplit = (uint32_t)std::min<uint64_t>(nqt, std::max<uint64_t>(1, (uint64_t)2 * blocks / need_blocks));
-                nb = (int)(need_blocks * g.qsplit);
-            }
-            prof_begin(ctx, "gemm");
-            gemm_level_launch(ctx, bf16, nqt, nb, g);
+            if (rowreg) gemm_rowreg_launch(ctx, f16x1 ? 2 : f16x2 ? 1 : 0, use_image, e.nb, g);
+            else if (lds_rows) gemm_ldsrow_launch(ctx, bf16, nqt, filtered, ctx->tune.gemm_dma_nt != 0, e.nb, g);
+            else gemm_level_launch(ctx, bf16, nqt, e.nb, g);
             prof_end(ctx, "gemm");
         }
-        LevelSelectParams ls;
-        ls.cand = cand;
-        ls.counts = counts;
-        ls.tau = tau;
-        ls.overflow = overflow;
-        ls.kp = kp;
-        ls.qconst = rowreg ? qconst : nullptr;
-        prof_begin(ctx, "select");
-        hipLaunchKernelGGL(level_select_kernel, dim3(a.nq), dim3(1024), 0, ctx->stream, ls);
-        prof_end(ctx, "select");
+        if (e.select) {
+            level_select(rowreg ? qconst : nullptr);
+            if (rc) return rc;
+        }
     }
+    if ((rc = trace.end_of_call(cand, overflow, kp))) return rc;
     SMT_HIP_CHECK(hipGetLastError());
 
     // each query now has ONE sorted list of kp keys at the head of its buffer
@@ -831,93 +921,196 @@ int launch_gemm_threshold(smt_ctx *ctx, const float *corpus, uint64_t rows, cons
     return SMT_OK;
 }
 
-// ---- test hook: what the PRODUCTION kernels nominate.  The route of a real batched call (gemm_route), its query preparation
-// (gemm_prepare_queries), then ONE level over all tiles -- for a range-filtered call the entries of the tile resp. chunk table -- with
-// the caller's distance threshold per query (tau_dev [nq], +inf = admit everything) in place of the level plan's.  The lists hold up to
-// CAND_CAP keys per query, so a.n_virtual <= CAND_CAP rows may be scanned; they and the counts cover the PADDING queries of the last
-// query tile too (nothing may ever land there), preset to KEY_PAD resp. 0.  route_out: family (0 row-register, 1 LDS-row, 2 level)
-// | arithmetic << 4 (0 bf16 x 3, 1 f16 x 2, 2 f16 x 1, 3 f32 MFMA) | 0x100 from the operand image | 0x200 range-filtered.
-// The buffers live in the context's scratch until the next launch.
-int launch_gemm_debug_nominations(smt_ctx *ctx, const ScanArgs &a, const float *tau_dev, int buffered, const key_t64 **cand_out,
-                                  const unsigned int **counts_out, uint32_t *route_out)
+// ---- test hooks: what the PRODUCTION kernels nominate, and what the bootstrap launch stores.  Both start as a real batched call
+// does: its route (gemm_route), the scratch carved up, its query preparation (gemm_prepare_queries), the table of a range-filtered call.
+// The lists and the counts cover the PADDING queries of the last query tile too (nothing may ever land there), preset to KEY_PAD resp. 0.
+// route: family (0 row-register, 1 LDS-row, 2 level) | arithmetic << 4 (0 bf16 x 3, 1 f16 x 2, 2 f16 x 1, 3 f32 MFMA) | 0x100 from the
+// operand image | 0x200 range-filtered.  The buffers live in the context's scratch until the next launch.
+struct GemmDebugBatch {
+    GemmRoute r;
+    bool bf16;
+    uint32_t nqt, nq_pad, route;
+    uint64_t n_table, n_tiles;
+    int blocks;
+    key_t64 *cand;
+    unsigned int *counts, *overflow;
+    float *tau, *qconst, *tile_min;
+    uint32_t *q_split;
+    const uint64_t *use_table;
+    GemmPlanLaunch boot;   // with_bootstrap: the bootstrap launch of the call's plan
+};
+static int gemm_debug_batch(smt_ctx *ctx, const ScanArgs &a, bool with_bootstrap, GemmDebugBatch &b)
 {
     SMT_REQUIRE(a.nq >= 1 && a.nq <= 2 * QT_ROWS, "debug nominations: 1..64 queries");
-    SMT_REQUIRE(a.n_virtual >= 1 && a.n_virtual <= CAND_CAP, "debug nominations: 1..2048 scanned rows (the capacity of a candidate list)");
     SMT_REQUIRE(a.k_out >= 1 && a.k_out + 8 <= 64, "debug nominations: top_k must be in [1, 56]");
+    SMT_REQUIRE(a.n_virtual >= 1 && a.rows < 0xFFFFFFFFull, "debug nominations: at least one row to scan, fewer than 2^32-1 in the shard");
     const GemmRoute r = gemm_route(ctx, a);
+    b.r = r;
     if (r.filtered && !r.lds_rows && !r.rowreg) { set_error("range-filtered batches need the row-register or the LDS-row kernel (tuning keys gemm_rowreg, gemm_ldsrow)"); return SMT_E_UNSUPPORTED; }
     if (int rc_attr = ensure_gemm_attrs(ctx)) return rc_attr;
-    const bool bf16 = ctx->tune.gemm_bf16x3 != 0;
+    b.bf16 = ctx->tune.gemm_bf16x3 != 0;
     const uint32_t nqt = r.nqt, nq_pad = nqt * QT_ROWS;
-    const uint64_t n_table = !r.filtered ? 0 : r.rowreg ? a.n_vtiles : a.n_chunks;
-    const uint64_t n_tiles = !r.filtered ? (a.rows + 31) / 32 : r.rowreg ? n_table : (n_table + 7) / 8;
-    // scratch: cand [nq_pad][CAP] | counts [nq_pad] | overflow [nq_pad] | tau [nq_pad] | qconst [nq_pad][2] | split queries | table
+    b.nqt = nqt;
+    b.nq_pad = nq_pad;
+    b.n_table = !r.filtered ? 0 : r.rowreg ? a.n_vtiles : a.n_chunks;
+    b.n_tiles = !r.filtered ? (a.rows + 31) / 32 : r.rowreg ? b.n_table : (b.n_table + 7) / 8;
+    b.blocks = ctx->tune.gemm_blocks > 0 ? ctx->tune.gemm_blocks : ctx->num_cus;
+    b.route = (r.rowreg ? 0u : r.lds_rows ? 1u : 2u) | ((r.f16x1 ? 2u : r.f16x2 ? 1u : b.bf16 ? 0u : 3u) << 4) | (r.use_image ? 0x100u : 0u) |
+              (r.filtered ? 0x200u : 0u);
+    uint32_t slots = 0;
+    if (with_bootstrap) {
+        const std::vector<GemmPlanLaunch> plan = gemm_level_plan(GemmPlanInput{b.n_tiles, a.nq, r.kp, r.rowreg ? 0 : r.lds_rows ? 1 : 2, r.f16x1, b.blocks,
+                                                                                ctx->tune.gemm_bootstrap, ctx->tune.gemm_boot_fine,
+                                                                                ctx->tune.gemm_split_last, ctx->tune.gemm_qsplit});
+        SMT_REQUIRE(plan.front().bootstrap, "debug bootstrap: the plan of this call has no bootstrap level (row-register kernel, more than 32 tiles, gemm_bootstrap)");
+        b.boot = plan.front();
+        slots = b.boot.slots;
+    }
+    // scratch: cand [nq_pad][CAP] | counts [nq_pad] | overflow [nq_pad] | tau [nq_pad] | qconst [nq_pad][2] | split queries | table | tile_min
     const size_t b_cand = (size_t)nq_pad * CAND_CAP * sizeof(key_t64);
     const size_t b_cnt = (size_t)nq_pad * 4;
     const size_t o_split = (b_cand + 2 * b_cnt + 3 * (size_t)nq_pad * 4 + 255) & ~(size_t)255;
     const size_t o_table = o_split + (size_t)nq_pad * 1024;
-    int rc = ensure_scratch(ctx, o_table + (size_t)n_table * sizeof(uint64_t) + 64);
+    const size_t o_tmin = (o_table + (size_t)b.n_table * sizeof(uint64_t) + 255) & ~(size_t)255;
+    int rc = ensure_scratch(ctx, o_tmin + (size_t)slots * nq_pad * sizeof(float) + 64);
     if (rc) return rc;
     char *base = reinterpret_cast<char *>(ctx->d_scratch);
-    key_t64 *cand = reinterpret_cast<key_t64 *>(base);
-    unsigned int *counts = reinterpret_cast<unsigned int *>(base + b_cand);
-    unsigned int *overflow = reinterpret_cast<unsigned int *>(base + b_cand + b_cnt);
-    float *tau = reinterpret_cast<float *>(base + b_cand + 2 * b_cnt);
-    float *qconst = tau + nq_pad;
-    uint32_t *q_split = reinterpret_cast<uint32_t *>(base + o_split);
+    b.cand = reinterpret_cast<key_t64 *>(base);
+    b.counts = reinterpret_cast<unsigned int *>(base + b_cand);
+    b.overflow = reinterpret_cast<unsigned int *>(base + b_cand + b_cnt);
+    b.tau = reinterpret_cast<float *>(base + b_cand + 2 * b_cnt);
+    b.qconst = b.tau + nq_pad;
+    b.q_split = reinterpret_cast<uint32_t *>(base + o_split);
     uint64_t *table = reinterpret_cast<uint64_t *>(base + o_table);
-    SMT_HIP_CHECK(hipMemsetAsync(cand, 0xFF, b_cand, ctx->stream));
-    SMT_HIP_CHECK(hipMemsetAsync(counts, 0, 2 * b_cnt, ctx->stream));
-    const BatchHead head{qconst, counts, overflow, tau};
-    if ((rc = gemm_prepare_queries(ctx, r, a, q_split, head, b_cnt))) return rc;
-    // the caller's thresholds: the f32 / LDS-row / level kernels read tau, the row-register kernels its score-domain form
-    SMT_HIP_CHECK(hipMemcpyAsync(tau, tau_dev, (size_t)a.nq * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    if (r.rowreg) hipLaunchKernelGGL(set_qconst_thresholds_kernel, dim3(1), dim3(256), 0, ctx->stream, qconst, tau, a.nq);
-    const uint64_t *use_table = table;
+    b.tile_min = reinterpret_cast<float *>(base + o_tmin);
+    SMT_HIP_CHECK(hipMemsetAsync(b.cand, 0xFF, b_cand, ctx->stream));
+    SMT_HIP_CHECK(hipMemsetAsync(b.counts, 0, 2 * b_cnt, ctx->stream));
+    BatchHead head{b.qconst, b.counts, b.overflow, b.tau};
+    if (with_bootstrap) {   // as launch_gemm_topk: the head launch presets the slot minima to +inf
+        head.fill = b.tile_min;
+        head.n_fill = slots * nq_pad;
+    }
+    if ((rc = gemm_prepare_queries(ctx, r, a, b.q_split, head, b_cnt))) return rc;
+    b.use_table = table;
     if (r.filtered && r.rowreg) {
-        if ((rc = range_tile_table(ctx, a, table, &use_table))) return rc;
-    } else if (r.filtered && (rc = range_chunk_table(ctx, a, table, &use_table))) return rc;
+        if ((rc = range_tile_table(ctx, a, table, &b.use_table))) return rc;
+    } else if (r.filtered && (rc = range_chunk_table(ctx, a, table, &b.use_table))) return rc;
+    return SMT_OK;
+}
+
+// ONE level launch -- by default stride 1 over all tiles; for a range-filtered call the entries of the tile resp. chunk table -- with the
+// caller's distance threshold per query (tau_dev [nq], +inf = admit everything) in place of the level plan's.  The lists hold up to
+// CAND_CAP keys per query, so the launch may visit at most CAND_CAP rows.  A level is (stride, skip, [tile_begin, tile_end)) as
+// GemmParams takes them; skip must be one level_tile implements, the last tile must exist, and only the row-register kernel starts
+// anywhere but at 0.
+int launch_gemm_debug_nominations(smt_ctx *ctx, const ScanArgs &a, const float *tau_dev, int buffered, const GemmDebugLevel &level,
+                                  const key_t64 **cand_out, const unsigned int **counts_out, uint32_t *route_out)
+{
+    GemmDebugBatch b;
+    int rc = gemm_debug_batch(ctx, a, false, b);
+    if (rc) return rc;
+    const GemmRoute &r = b.r;
+    const uint64_t tile_end = level.tile_end == UINT64_MAX ? b.n_tiles : level.tile_end;
+    SMT_REQUIRE(level.skip == 0 || level.skip == 4 || level.skip == 16 || level.skip == 64, "debug nominations: skip is 0, 4, 16 or 64");
+    SMT_REQUIRE(level.stride >= 1 && level.tile_begin <= tile_end && tile_end <= b.n_tiles, "debug nominations: the level's tile range");
+    SMT_REQUIRE(tile_end == 0 || level_tile(tile_end - 1, level.stride, level.skip) < b.n_tiles, "debug nominations: the level's last tile lies beyond the tiles of the call");
+    SMT_REQUIRE(level.tile_begin == 0 || r.rowreg, "debug nominations: only the row-register kernel starts a level anywhere but at 0");
+    const uint64_t rows_per_tile = r.filtered && !r.rowreg ? 8 * FILTER_CHUNK : 32;
+    SMT_REQUIRE(std::min<uint64_t>((tile_end - level.tile_begin) * rows_per_tile, a.n_virtual) <= CAND_CAP,
+                "debug nominations: at most 2048 rows may be visited (the capacity of a candidate list)");
+    // the caller's thresholds: the f32 / LDS-row / level kernels read tau, the row-register kernels its score-domain form
+    SMT_HIP_CHECK(hipMemcpyAsync(b.tau, tau_dev, (size_t)a.nq * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    if (r.rowreg) hipLaunchKernelGGL(set_qconst_thresholds_kernel, dim3(1), dim3(256), 0, ctx->stream, b.qconst, b.tau, a.nq);
     GemmParams g;
     memset(&g, 0, sizeof(g));
     g.corpus = a.corpus;
     g.n_rows = a.rows;
     g.queries = a.queries;
-    g.queries_split = bf16 ? q_split : nullptr;
+    g.queries_split = b.bf16 ? b.q_split : nullptr;
     g.nq = a.nq;
-    g.nqt = nqt;
-    g.level_tiles = n_tiles;
-    g.tile_begin = 0;
-    g.stride = 1;
-    g.skip16 = 0;
+    g.nqt = b.nqt;
+    g.level_tiles = tile_end;
+    g.tile_begin = level.tile_begin;
+    g.stride = level.stride;
+    g.skip16 = level.skip;
     g.qsplit = 1;
-    g.tau = tau;
-    g.qconst = qconst;
-    g.cand = cand;
-    g.counts = counts;
+    g.tau = b.tau;
+    g.qconst = b.qconst;
+    g.cand = b.cand;
+    g.counts = b.counts;
     g.cand_cap = CAND_CAP;
-    g.chunk_table = r.filtered && !r.rowreg ? use_table : nullptr;
-    g.tile_table = r.filtered && r.rowreg ? use_table : nullptr;
-    g.n_chunks = n_table;
+    g.chunk_table = r.filtered && !r.rowreg ? b.use_table : nullptr;
+    g.tile_table = r.filtered && r.rowreg ? b.use_table : nullptr;
+    g.n_chunks = b.n_table;
     g.buffered = buffered ? 1 : 0;
     g.image = r.use_image ? a.image : nullptr;
     g.image_zero = r.use_image ? a.image_zero : nullptr;
     // blocks and the query split as launch_gemm_topk sizes them for a level of this many tiles
-    const int blocks = ctx->tune.gemm_blocks > 0 ? ctx->tune.gemm_blocks : ctx->num_cus;
     const int waves = r.rowreg ? RR_WAVES : r.lds_rows ? LR_WAVES : GEMM_WAVES;
-    const uint64_t need_blocks = (n_tiles + waves - 1) / waves;
-    int nb = (int)std::min<uint64_t>((uint64_t)blocks, need_blocks);
-    if (!r.lds_rows && ctx->tune.gemm_qsplit && need_blocks < (uint64_t)blocks) {
-        g.qsplit = (uint32_t)std::min<uint64_t>(nqt, std::max<uint64_t>(1, (uint64_t)2 * blocks / need_blocks));
+    const uint64_t need_blocks = std::max<uint64_t>(1, (tile_end + waves - 1) / waves);
+    int nb = (int)std::min<uint64_t>((uint64_t)b.blocks, need_blocks);
+    if (!r.lds_rows && ctx->tune.gemm_qsplit && need_blocks < (uint64_t)b.blocks) {
+        g.qsplit = (uint32_t)std::min<uint64_t>(b.nqt, std::max<uint64_t>(1, (uint64_t)2 * b.blocks / need_blocks));
         nb = (int)(need_blocks * g.qsplit);
     }
-    if (r.rowreg) gemm_rowreg_launch(ctx, r.f16x1 ? 2 : r.f16x2 ? 1 : 0, r.use_image, nb, g);
-    else if (r.lds_rows) gemm_ldsrow_launch(ctx, bf16, nqt, r.filtered, ctx->tune.gemm_dma_nt != 0, nb, g);
-    else gemm_level_launch(ctx, bf16, nqt, nb, g);
+    if (tile_end > level.tile_begin) {
+        if (r.rowreg) gemm_rowreg_launch(ctx, r.f16x1 ? 2 : r.f16x2 ? 1 : 0, r.use_image, nb, g);
+        else if (r.lds_rows) gemm_ldsrow_launch(ctx, b.bf16, b.nqt, r.filtered, ctx->tune.gemm_dma_nt != 0, nb, g);
+        else gemm_level_launch(ctx, b.bf16, b.nqt, nb, g);
+    }
     SMT_HIP_CHECK(hipGetLastError());
-    *cand_out = cand;
-    *counts_out = counts;
-    *route_out = (r.rowreg ? 0u : r.lds_rows ? 1u : 2u) | ((r.f16x1 ? 2u : r.f16x2 ? 1u : bf16 ? 0u : 3u) << 4) | (r.use_image ? 0x100u : 0u) |
-                 (r.filtered ? 0x200u : 0u);
+    *cand_out = b.cand;
+    *counts_out = b.counts;
+    *route_out = b.route;
+    return SMT_OK;
+}
+
+// The bootstrap launch of the call launch_gemm_topk would make over `a`: the plan's first entry (refused when the plan has none), the
+// head launch with the +inf fill, gemm_rowreg_kernel with tile_min and the planned grid and query split.  No candidates are written.
+int launch_gemm_debug_bootstrap(smt_ctx *ctx, const ScanArgs &a, const float **tile_min_out, uint32_t *slots_out, uint64_t *stride_out,
+                                uint32_t *route_out)
+{
+    GemmDebugBatch b;
+    int rc = gemm_debug_batch(ctx, a, true, b);
+    if (rc) return rc;
+    const GemmRoute &r = b.r;
+    const GemmParams g = gemm_bootstrap_params(a, r, b.boot, b.q_split, b.tau, b.qconst, b.cand, b.counts, r.filtered ? b.use_table : nullptr, b.tile_min);
+    gemm_rowreg_launch(ctx, r.f16x1 ? 2 : r.f16x2 ? 1 : 0, r.use_image, b.boot.nb, g);
+    SMT_HIP_CHECK(hipGetLastError());
+    *tile_min_out = b.tile_min;
+    *slots_out = b.boot.slots;
+    *stride_out = b.boot.stride;
+    *route_out = b.route;
+    return SMT_OK;
+}
+
+// bootstrap_tau_kernel and level_select_kernel on the caller's buffers, with the grids launch_gemm_topk gives them.
+// level_select_kernel's PRECONDITION: the keys of a query are distinct -- it ranks with a strict <, so two equal keys would share a rank
+// and leave a KEY_PAD hole at the next.  In production a key is (distance, row) and every row is visited by exactly one appended launch
+// (tests/test_level_plan_cpu.py, P1), so no key is written twice.
+int launch_debug_bootstrap_tau(smt_ctx *ctx, const float *tile_min, uint32_t n_slots, uint32_t nq, uint32_t nq_pad, uint32_t kp, float *tau,
+                               float *qconst)
+{
+    SMT_REQUIRE(nq >= 1 && nq <= nq_pad && nq_pad % QT_ROWS == 0, "debug bootstrap tau: nq within nq_pad, a multiple of 32");
+    SMT_REQUIRE(n_slots <= BOOTSTRAP_SLOTS && kp >= 1 && kp <= 64, "debug bootstrap tau: at most 1024 slots, k' in [1, 64]");
+    hipLaunchKernelGGL(bootstrap_tau_kernel, dim3(nq_pad / 2), dim3(64), 0, ctx->stream, tile_min, n_slots, nq, nq_pad, kp, tau, qconst);
+    SMT_HIP_CHECK(hipGetLastError());
+    return SMT_OK;
+}
+
+int launch_debug_level_select(smt_ctx *ctx, key_t64 *cand, unsigned int *counts, unsigned int *overflow, float *tau, float *qconst,
+                              uint32_t nq, uint32_t kp)
+{
+    SMT_REQUIRE(nq >= 1 && kp >= 1 && kp <= 64, "debug level select: >= 1 query, k' in [1, 64]");
+    LevelSelectParams ls;
+    ls.cand = cand;
+    ls.counts = counts;
+    ls.tau = tau;
+    ls.overflow = overflow;
+    ls.kp = kp;
+    ls.qconst = qconst;
+    hipLaunchKernelGGL(level_select_kernel, dim3(nq), dim3(1024), 0, ctx->stream, ls);
+    SMT_HIP_CHECK(hipGetLastError());
     return SMT_OK;
 }
 

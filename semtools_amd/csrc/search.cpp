@@ -964,9 +964,42 @@ try {
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
-int smt_debug_nominations(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
-                          const float *tau, int buffered, float *out_dist, uint32_t *out_hits, uint32_t *out_counts, uint32_t *out_route)
-try {
+// The ScanArgs of a real batched call of nq host queries over the whole corpus, for the K3 test hooks: ranges through the range plan,
+// the operand image as topk_dispatch.  Staged: the queries, then nq_pad floats (tau, may be null), then the plan's tables.
+static int debug_batch_args(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                            const float *tau, RangePlan &plan, ScanArgs &a, const float **tau_dev)
+{
+    smt_ctx *ctx = corpus->ctx;
+    const uint32_t nq_pad = (nq + 31) / 32 * 32;
+    int rc;
+    plan.n_virtual = corpus->rows;
+    if (n_ranges && (rc = range_plan_find(corpus, ranges, n_ranges, plan))) return rc;
+    SMT_REQUIRE(plan.n_virtual >= 1, "debug nominations: nothing to scan");
+    if ((rc = range_plan_finish(corpus, plan))) return rc;
+    const size_t q_bytes = (size_t)nq * SMT_DIM * sizeof(float), t_bytes = (size_t)nq_pad * sizeof(float);
+    if ((rc = ensure_stage(ctx, q_bytes + t_bytes + plan.table_bytes() + 64))) return rc;
+    char *stage = reinterpret_cast<char *>(ctx->d_stage);
+    SMT_HIP_CHECK(hipMemcpyAsync(stage, queries, q_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (tau) { SMT_HIP_CHECK(hipMemcpyAsync(stage + q_bytes, tau, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, ctx->stream)); }
+    plan.bind(stage + q_bytes + t_bytes);
+    if (plan.upload_bytes()) {
+        SMT_HIP_CHECK(hipMemcpyAsync(const_cast<smt_range *>(plan.d_r), plan.rr.data(), plan.r_bytes(), hipMemcpyHostToDevice, ctx->stream));
+        SMT_HIP_CHECK(hipMemcpyAsync(const_cast<uint64_t *>(plan.d_p), plan.prefixes.data(), plan.prefixes.size() * sizeof(uint64_t),
+                                     hipMemcpyHostToDevice, ctx->stream));
+    }
+    a = scan_args(corpus, reinterpret_cast<const float *>(stage), nq, top_k, 0);
+    plan.apply(a);
+    if (ctx->tune.gemm_bf16x3 && ctx->tune.gemm_rowreg && (a.n_ranges == 0 || tiles_dense(a.n_virtual, a.n_vtiles))) {
+        if ((rc = corpus_image_sync(corpus, a.nq, &a.image, &a.image_zero))) return rc;
+    }
+    *tau_dev = reinterpret_cast<const float *>(stage + q_bytes);
+    return SMT_OK;
+}
+
+static int debug_nominations(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                             const float *tau, int buffered, const GemmDebugLevel &level, float *out_dist, uint32_t *out_hits,
+                             uint32_t *out_counts, uint32_t *out_route)
+{
     SMT_REQUIRE(corpus && queries && tau && out_dist && out_hits && out_counts && out_route, "null argument");
     SMT_REQUIRE(n_ranges == 0 || ranges != nullptr, "ranges");
     SMT_REQUIRE(nq >= 1 && nq <= 64, "debug nominations: 1..64 queries");
@@ -978,32 +1011,13 @@ try {
     for (uint64_t i = 0; i < rows * nq; ++i) { out_dist[i] = std::numeric_limits<float>::quiet_NaN(); out_hits[i] = 0; }
     for (uint32_t q = 0; q < nq_pad; ++q) out_counts[q] = 0;
     *out_route = 0;
-    // the ScanArgs of a real batched call over the whole corpus: ranges through the range plan, the operand image as topk_dispatch
     RangePlan plan;
-    plan.n_virtual = rows;
-    if (n_ranges && (rc = range_plan_find(corpus, ranges, n_ranges, plan))) return rc;
-    SMT_REQUIRE(plan.n_virtual >= 1 && plan.n_virtual <= 2048, "debug nominations: 1..2048 scanned rows (the capacity of a candidate list)");
-    if ((rc = range_plan_finish(corpus, plan))) return rc;
-    const size_t q_bytes = (size_t)nq * SMT_DIM * sizeof(float), t_bytes = (size_t)nq_pad * sizeof(float);
-    if ((rc = ensure_stage(ctx, q_bytes + t_bytes + plan.table_bytes() + 64))) return rc;
-    char *stage = reinterpret_cast<char *>(ctx->d_stage);
-    SMT_HIP_CHECK(hipMemcpyAsync(stage, queries, q_bytes, hipMemcpyHostToDevice, ctx->stream));
-    SMT_HIP_CHECK(hipMemcpyAsync(stage + q_bytes, tau, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    plan.bind(stage + q_bytes + t_bytes);
-    if (plan.upload_bytes()) {
-        SMT_HIP_CHECK(hipMemcpyAsync(const_cast<smt_range *>(plan.d_r), plan.rr.data(), plan.r_bytes(), hipMemcpyHostToDevice, ctx->stream));
-        SMT_HIP_CHECK(hipMemcpyAsync(const_cast<uint64_t *>(plan.d_p), plan.prefixes.data(), plan.prefixes.size() * sizeof(uint64_t),
-                                     hipMemcpyHostToDevice, ctx->stream));
-    }
-    ScanArgs a = scan_args(corpus, reinterpret_cast<const float *>(stage), nq, top_k, 0);
-    plan.apply(a);
-    if (ctx->tune.gemm_bf16x3 && ctx->tune.gemm_rowreg && (a.n_ranges == 0 || tiles_dense(a.n_virtual, a.n_vtiles))) {
-        if ((rc = corpus_image_sync(corpus, a.nq, &a.image, &a.image_zero))) return rc;
-    }
+    ScanArgs a;
+    const float *tau_dev = nullptr;
+    if ((rc = debug_batch_args(corpus, queries, nq, top_k, ranges, n_ranges, tau, plan, a, &tau_dev))) return rc;
     const key_t64 *cand = nullptr;
     const unsigned int *counts = nullptr;
-    if ((rc = launch_gemm_debug_nominations(ctx, a, reinterpret_cast<const float *>(stage + q_bytes), buffered, &cand, &counts, out_route)))
-        return rc;
+    if ((rc = launch_gemm_debug_nominations(ctx, a, tau_dev, buffered, level, &cand, &counts, out_route))) return rc;
     std::vector<key_t64> keys((size_t)nq_pad * 2048);
     SMT_HIP_CHECK(hipMemcpyAsync(keys.data(), cand, keys.size() * sizeof(key_t64), hipMemcpyDeviceToHost, ctx->stream));
     SMT_HIP_CHECK(hipMemcpyAsync(out_counts, counts, (size_t)nq_pad * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -1023,6 +1037,111 @@ try {
             ++out_hits[row * nq + q];
         }
     }
+    return SMT_OK;
+}
+
+int smt_debug_nominations(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                          const float *tau, int buffered, float *out_dist, uint32_t *out_hits, uint32_t *out_counts, uint32_t *out_route)
+try {
+    return debug_nominations(corpus, queries, nq, top_k, ranges, n_ranges, tau, buffered, GemmDebugLevel{}, out_dist, out_hits, out_counts, out_route);
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_level_nominations(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges,
+                                uint32_t n_ranges, const float *tau, int buffered, uint64_t stride, uint32_t skip, uint64_t tile_begin,
+                                uint64_t tile_end, float *out_dist, uint32_t *out_hits, uint32_t *out_counts, uint32_t *out_route)
+try {
+    SMT_REQUIRE(skip <= 64 && tile_end != UINT64_MAX, "debug nominations: the level");
+    GemmDebugLevel level;
+    level.stride = stride;
+    level.skip = (int)skip;
+    level.tile_begin = tile_begin;
+    level.tile_end = tile_end;
+    return debug_nominations(corpus, queries, nq, top_k, ranges, n_ranges, tau, buffered, level, out_dist, out_hits, out_counts, out_route);
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_bootstrap_minima(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges,
+                               uint32_t n_ranges, float *out_tile_min, uint32_t *out_slots, uint64_t *out_stride, uint32_t *out_route)
+try {
+    SMT_REQUIRE(corpus && queries && out_tile_min && out_slots && out_stride && out_route, "null argument");
+    SMT_REQUIRE(n_ranges == 0 || ranges != nullptr, "ranges");
+    SMT_REQUIRE(nq >= 1 && nq <= 64, "debug bootstrap: 1..64 queries");
+    smt_ctx *ctx = corpus->ctx;
+    int rc = bind_device(ctx, true);
+    if (rc) return rc;
+    *out_slots = 0; *out_stride = 0; *out_route = 0;
+    RangePlan plan;
+    ScanArgs a;
+    const float *unused = nullptr;
+    if ((rc = debug_batch_args(corpus, queries, nq, top_k, ranges, n_ranges, nullptr, plan, a, &unused))) return rc;
+    const float *tile_min = nullptr;
+    if ((rc = launch_gemm_debug_bootstrap(ctx, a, &tile_min, out_slots, out_stride, out_route))) return rc;
+    const uint32_t nq_pad = (nq + 31) / 32 * 32;
+    SMT_HIP_CHECK(hipMemcpyAsync(out_tile_min, tile_min, (size_t)*out_slots * nq_pad * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_bootstrap_tau(smt_ctx *ctx, const float *tile_min_dev, uint32_t n_slots, uint32_t nq, uint32_t nq_pad, uint32_t kp,
+                            float *tau_dev, float *qconst_dev)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    SMT_REQUIRE(tile_min_dev && tau_dev && qconst_dev, "null argument");
+    if ((rc = bind_device(ctx))) return rc;
+    return launch_debug_bootstrap_tau(ctx, tile_min_dev, n_slots, nq, nq_pad, kp, tau_dev, qconst_dev);
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_level_select(smt_ctx *ctx, uint64_t *cand_dev, uint32_t *counts_dev, uint32_t *overflow_dev, float *tau_dev, float *qconst_dev,
+                           uint32_t nq, uint32_t kp)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    SMT_REQUIRE(cand_dev && counts_dev && overflow_dev && tau_dev, "null argument");
+    if ((rc = bind_device(ctx))) return rc;
+    return launch_debug_level_select(ctx, reinterpret_cast<key_t64 *>(cand_dev), counts_dev, overflow_dev, tau_dev, qconst_dev, nq, kp);
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_gemm_plan(uint64_t plan_tiles, uint32_t nq, uint32_t kp, int family, int f16x1, uint32_t blocks, int gemm_bootstrap,
+                        int gemm_boot_fine, int gemm_split_last, int gemm_qsplit, uint64_t *out, uint32_t out_cap, uint32_t *out_n)
+try {
+    SMT_REQUIRE(out_n != nullptr && (out != nullptr || out_cap == 0), "null argument");
+    SMT_REQUIRE(plan_tiles >= 1 && plan_tiles < (1ull << 27) && nq >= 1 && nq <= 3584 && kp >= 1 && kp <= 64 && family >= 0 && family <= 2 &&
+                    blocks >= 1 && blocks <= 65536,
+                "debug plan: 1 .. 2^27 - 1 tiles, 1..3584 queries, k' in [1, 64], family 0..2, 1..65536 blocks");
+    const std::vector<GemmPlanLaunch> plan = gemm_level_plan(GemmPlanInput{plan_tiles, nq, kp, family, f16x1 != 0, (int)blocks, gemm_bootstrap,
+                                                                            gemm_boot_fine, gemm_split_last, gemm_qsplit});
+    *out_n = (uint32_t)plan.size();
+    SMT_REQUIRE(plan.size() <= out_cap, "debug plan: more launches than the output holds (out_n says how many)");
+    for (size_t i = 0; i < plan.size(); ++i) {
+        const GemmPlanLaunch &e = plan[i];
+        uint64_t *w = out + i * SMT_GEMM_PLAN_WORDS;
+        w[0] = e.bootstrap ? 0 : 1;
+        w[1] = e.stride;
+        w[2] = (uint64_t)e.skip;
+        w[3] = e.tile_begin;
+        w[4] = e.tile_end;
+        w[5] = e.qsplit;
+        w[6] = (uint64_t)e.nb;
+        w[7] = e.slots;
+        w[8] = e.select ? 1 : 0;
+        w[9] = (e.thresholds ? 1u : 0u) | (e.buffer_fits ? 2u : 0u);
+    }
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_debug_gemm_trace(smt_ctx *ctx, uint32_t *buf_dev, uint64_t cap_words, uint32_t *out_selects, uint64_t *out_words)
+try {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    SMT_REQUIRE(buf_dev == nullptr || cap_words >= 1, "debug trace: a buffer needs a capacity");
+    if (out_selects) *out_selects = ctx->gemm_trace_selects;
+    if (out_words) *out_words = ctx->gemm_trace_used;
+    const bool truncated = ctx->d_gemm_trace != nullptr && ctx->gemm_trace_used > ctx->gemm_trace_cap;
+    ctx->d_gemm_trace = buf_dev;
+    ctx->gemm_trace_cap = buf_dev ? cap_words : 0;
+    ctx->gemm_trace_used = 0;
+    ctx->gemm_trace_selects = 0;
+    if (truncated) { set_error("debug trace: the buffer was too small for what the calls recorded"); return SMT_E_INVALID; }
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
