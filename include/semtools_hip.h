@@ -1188,6 +1188,12 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *   gemm_resident        accepted and ignored (its kernel left in round 2)
  *   gemm_bf16x3 (1/0)    K3 nominates with bf16 x 3 split products on the bf16 MFMA pipe (default) or with f32 MFMAs;
  *                        answers are identical either way (exact re-scoring + the exactness certificate)
+ *   largek_sampled (1/0) 57 <= top_k <= 1024 take the sampled-threshold route (0: the all-keys path, top_k <= 56 on the device forms)
+ *   largek_group (1..4, default 4)  that route's collect stage serves up to this many queries of a call per corpus pass
+ *                        (largek_collect_group_kernel; the rounds of two or more queries that do not take the batched sweep);
+ *                        1: a pass per query.  The answers and the status words are the same bytes at every value
+ *   largek_sweep_filtered (default 8; 0 = never)  range-filtered calls of that route with at least this many queries collect in
+ *                        ONE sweep of the batched kernel over the tile table of their ranges, as unfiltered calls of five do
  *   direct_delivery (1/0)  smt_search top-k calls with a small answer (<= 32 queries, <= 8 KiB of rows and distances) get it DELIVERED
  *                        by the select kernel: its last block writes the answer into pinned host memory and a completion word behind
  *                        it, which the host waits on -- no D2H copy command, no hipStreamSynchronize (~10 us of a small call); 0: A/B

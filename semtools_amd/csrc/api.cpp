@@ -624,6 +624,13 @@ try {
     else if (k == "gemm_rowreg") ctx->tune.gemm_rowreg = (int)value;
     else if (k == "gemm_nominate") ctx->tune.gemm_nominate = (value >= 1 && value <= 3) ? (int)value : 0;
     else if (k == "largek_sampled") ctx->tune.largek_sampled = value ? 1 : 0;
+    else if (k == "largek_group") {
+        SMT_REQUIRE(value >= 1 && value <= 4, "largek_group: 1..4 queries per corpus pass of the large-k collect");
+        ctx->tune.largek_group = (int)value;
+    } else if (k == "largek_sweep_filtered") {
+        SMT_REQUIRE(value >= 0 && value <= 0x7fffffff, "largek_sweep_filtered: queries from which a range-filtered large-k batch takes the sweep (0 = never)");
+        ctx->tune.largek_sweep_filtered = (int)value;
+    }
     else if (k == "fallback_batch_min_rows") ctx->tune.fallback_batch_min_rows = value < 0 ? 0 : value;
     else if (k == "guard_band") ctx->tune.guard_band = (int)std::max<int64_t>(8, std::min<int64_t>(56, value));
     else if (k == "gemm_min_nq") ctx->tune.gemm_min_nq = (int)std::max<int64_t>(2, std::min<int64_t>(8, value));

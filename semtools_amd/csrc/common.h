@@ -92,6 +92,8 @@ struct Tuning {
     int gemm_ldsrow = 1;        // 1: batches <= 128 queries and range-filtered batches use the LDS-row kernel (64 queries per pass)
     int prof_select = 1;        // 0: do not bracket the select stage with events (2 fewer event records per query)
     int largek_sampled = 1;     // 1: 57 <= top_k <= 1024 take the sampled-threshold route (topk_large.hip); 0: the all-keys path (largek.hip, A/B and parity tests)
+    int largek_group = 4;       // the large-k collect serves up to this many queries of a round per corpus pass (1 .. 4; topk_large.hip largek_collect_group_kernel); 1: a pass per query
+    int largek_sweep_filtered = 8;   // range-filtered large-k batches of this many queries collect in ONE sweep of the batched kernel over the tile table, like unfiltered batches of five (0: never); 8: where the sweep first beat the grouped passes (profiles/largek_group_ab.json)
     int direct_delivery = 1;    // 1: host-form top-k searches with small answers (<= 8 KiB) get them DELIVERED by the select kernel into pinned host memory, completion word last; the host waits on that word (search.cpp; 0: D2H copy + hipStreamSynchronize, A/B)
     int64_t compact_bounce_rows = 65536;   // smt_corpus_compact: rows of the bounce buffer a step with a gap shorter than itself goes through (64 MiB; 64 .. 2^20), compact.hip
     int64_t thr_hit_cap = (int64_t)1 << 20;   // K4: slots of the hit buffer of the first pass (at most the scanned rows); a pass that counts more hits is rerun with an exact-size buffer (tests lower it to reach the rerun on small corpora), threshold.hip
@@ -603,7 +605,8 @@ int launch_split_rows_bf16(smt_ctx *ctx, const float *rows, uint32_t n, uint32_t
 int launch_gemm_threshold(smt_ctx *ctx, const float *corpus, uint64_t rows, const void *image, const uint32_t *image_zero,
                           const float *queries, uint32_t nq, const float *tau, const key_t64 **cand_out,
                           const unsigned int **counts_out, uint32_t *cand_stride, uint32_t cap = 2048 /* CAND_CAP */,
-                          key_t64 *cand_ext = nullptr, unsigned int *counts_ext = nullptr);
+                          key_t64 *cand_ext = nullptr, unsigned int *counts_ext = nullptr,
+                          const uint64_t *tile_table = nullptr, uint64_t n_tiles = 0);   // range-filtered: the sweep walks this tile table
 // THE LEVEL PLAN of a batched call (gemm_topk.hip gemm_level_plan): the ordered launches launch_gemm_topk makes, as a pure function of
 // what they depend on.  launch_gemm_topk walks the result; smt_debug_gemm_plan returns it (tests/test_level_plan_cpu.py, no GPU).
 struct GemmPlanInput {

@@ -858,13 +858,17 @@ int launch_split_rows_bf16(smt_ctx *ctx, const float *rows, uint32_t n, uint32_t
 // whose nominating distance is <= tau[q] lands in query q's candidate buffer: gemm_rowreg_kernel over all tiles as a
 // single level with preset thresholds.  A query with more than `cap` such rows reports count > cap (the caller
 // re-answers it with the streaming K4 scan).  Buffers live in the context's scratch until the next launch.
+// With a tile table (range_tables.hip: tile | row mask << 32, n_tiles entries) the sweep walks the table instead of every tile of
+// the corpus and nominates only the rows the masks name: the range-filtered batches of the large-k route (topk_large.hip).
 int launch_gemm_threshold(smt_ctx *ctx, const float *corpus, uint64_t rows, const void *image, const uint32_t *image_zero,
                           const float *queries, uint32_t nq, const float *tau, const key_t64 **cand_out,
-                          const unsigned int **counts_out, uint32_t *cand_stride, uint32_t cap, key_t64 *cand_ext, unsigned int *counts_ext)
+                          const unsigned int **counts_out, uint32_t *cand_stride, uint32_t cap, key_t64 *cand_ext, unsigned int *counts_ext,
+                          const uint64_t *tile_table, uint64_t n_tiles)
 {
     const bool f16 = image != nullptr;   // over the corpus' operand image: f16 x 2 (the caller widened tau by F32_ERR_F16X2)
     SMT_REQUIRE(nq >= 1 && rows >= 1 && rows < 0xFFFFFFFFull, "threshold pass: bad sizes");
     SMT_REQUIRE(cap >= 1 && (cand_ext == nullptr) == (counts_ext == nullptr), "threshold pass: candidate buffers");
+    SMT_REQUIRE(tile_table == nullptr || (n_tiles >= 1 && n_tiles <= (rows + 31) / 32), "threshold pass: tile table");
     if (int rc_attr = ensure_gemm_attrs(ctx)) return rc_attr;
     const uint32_t nqt = (nq + QT_ROWS - 1) / QT_ROWS;
     const bool ext = cand_ext != nullptr;   // the caller's buffers [nq][cap] + [nq] (topk_large.hip): only the query staging is scratch
@@ -891,7 +895,7 @@ int launch_gemm_threshold(smt_ctx *ctx, const float *corpus, uint64_t rows, cons
     g.queries_split = q_split;
     g.nq = nq;
     g.nqt = nqt;
-    g.level_tiles = (rows + 31) / 32;
+    g.level_tiles = tile_table ? n_tiles : (rows + 31) / 32;
     g.stride = 1;
     g.skip16 = 0;
     g.qsplit = 1;
@@ -901,7 +905,7 @@ int launch_gemm_threshold(smt_ctx *ctx, const float *corpus, uint64_t rows, cons
     g.counts = counts;
     g.cand_cap = cap;
     g.chunk_table = nullptr;
-    g.tile_table = nullptr;
+    g.tile_table = tile_table;
     g.stamps = nullptr;
     g.buffered = 0;
     g.image = image;

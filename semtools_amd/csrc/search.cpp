@@ -465,11 +465,13 @@ static int topk_dispatch(smt_ctx *ctx, smt_corpus *corpus, ScanArgs &a)
     return rc;
 }
 
-// The large-k route (topk_large.hip) for a staged call: unfiltered batches of five or more queries sweep the corpus' fp16 operand image
-// when it has one (f16 x 2, half the bytes), like the batched re-answer; everything else reads the f32 rows.
+// The large-k route (topk_large.hip) for a staged call: batches that take its sweep -- unfiltered from five queries, range-filtered from
+// tuning key largek_sweep_filtered -- sweep the corpus' fp16 operand image when it has one (f16 x 2, half the bytes), like the batched
+// re-answer; everything else reads the f32 rows.
 static int largek_route(smt_ctx *ctx, smt_corpus *corpus, ScanArgs &a)
 {
-    if (a.n_ranges == 0 && a.nq >= 5 && image_sweep_allowed(ctx, corpus)) {
+    const uint32_t sweep_min = a.n_ranges == 0 ? 5u : (uint32_t)ctx->tune.largek_sweep_filtered;
+    if (sweep_min > 0 && a.nq >= sweep_min && image_sweep_allowed(ctx, corpus)) {
         if (int rc_img = corpus_image_sync(corpus, a.nq, &a.image, &a.image_zero)) return rc_img;
     }
     return launch_topk_large(ctx, a);

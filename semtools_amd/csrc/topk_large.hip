@@ -7,6 +7,13 @@
 //      prefetched, chunks claimed from the block's LDS counter), unfiltered or over the chunk table, one query per
 //      blockIdx.y.  Rows with d32 <= tau go to the query's candidate buffer as keys (d32 bits << 32 | row), one global
 //      atomic per wave flush.  The count goes on past the capacity: an overflow is seen, never silent.
+//      Rounds of two or more queries that do not take the batched sweep run largek_collect_group_kernel<G> instead (tuning key
+//      largek_group, G = 2 .. 4 queries per blockIdx.y): a wave loads each row ONCE and tests it against its G queries, whose
+//      slices it holds in registers -- the G + 1 product trees of a chunk reduced together (wave_sum4_multi_head, wave_sum4_rows,
+//      wave_sum4_group_tail), lane 16 g + j testing row j against query g, a 64-key LDS buffer per wave and query.  The d32 of a
+//      (row, query) pair is bit for bit the one-query kernel's, so the collected sets, the counts and the verdicts are too.
+//      Batches take ONE sweep of the batched kernel (launch_gemm_threshold): unfiltered from five queries, range-filtered
+//      (over the tile table) from tuning key largek_sweep_filtered.
 //   3. largek_finish: one block per query sorts the keys in LDS, rescores the best k + guard exactly (f64, index order:
 //      device_utils.h exact_distance, the code of the select and of rescore_rows_kernel), orders them by (f64 distance,
 //      row), applies the workspace score filter, writes the padded list and the verdict of the select's certificate:
@@ -31,6 +38,8 @@ constexpr int LK_HIT_BUF = 256;          // per-wave LDS buffer of the collect (
 constexpr int LK_SORT_MAX = 2048;        // rescored rows per query: k + guard <= 1024 + 64, padded to a power of two
 constexpr int LK_THREADS = 1024;
 constexpr uint32_t LK_K3_MIN_NQ = 5;     // unfiltered batches from this size take the K3 sweep instead of a pass per query
+constexpr int LK_GROUP_MAX = 4;          // queries per pass of the grouped collect: one 16-lane row of the wave each
+constexpr int LK_GROUP_BUF = 64;         // ... and its per-wave, per-query LDS buffer (keys): a chunk adds at most 4 to a query
 
 struct SampleParams {
     const float *corpus;
@@ -152,6 +161,7 @@ struct CollectParams {
     key_t64 *cand;                 // [nq][cap]
     unsigned int *counts;          // [nq]: rows under tau, counted past cap
     uint32_t cap;
+    uint32_t nq;                   // the grouped kernel: queries of the round (the last group may be partial)
 };
 
 // grid (blocks, nq): the K4 loop of threshold.hip with the test d32 <= tau[q] and keys in place of rows
@@ -252,6 +262,169 @@ __global__ void __launch_bounds__(1024) largek_collect_kernel(CollectParams p)
         cB = cN; dB = dN;
     }
     flush();
+}
+
+// ---- the grouped collect: G queries per corpus pass.
+// The arithmetic is frozen on largek_collect_kernel's, because the verdicts depend on which near-ties the f32 pass collected:
+//   * |q|^2 per lane as that kernel forms it, four rounded products added in index order (lk_norm2_lane), then wave_sum;
+//   * the per-lane product of a row slice with a query slice as the compiler contracts "x qx + y qy + z qz + w qw" there --
+//     y qy, then fused adds of x, z, w (lk_row_dot);
+//   * every tree performs wave_sum4's additions in wave_sum4's order (device_utils.h), and dist_f32 is the same function.
+// The kernel is built without the packed f32 VALU forms, so the expressions above are compiled as they are written.  (A function
+// inlines only callees of its own feature set or forced ones: hence the forced lambdas, the builtins in place of __ballot and
+// __popc, and a barrier of its own.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SMT_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define SMT_NO_PACKED_F32   // (a device feature: the host pass does not know it)
+#endif
+__device__ __forceinline__ float lk_norm2_lane(f32x4 q)
+{
+#pragma clang fp contract(off)
+    return ((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w;
+}
+__device__ __forceinline__ void lk_block_barrier()   // __syncthreads
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+__device__ __forceinline__ float lk_row_dot(f32x4 c, f32x4 q)
+{
+    return __builtin_fmaf(c.w, q.w, __builtin_fmaf(c.z, q.z, __builtin_fmaf(c.x, q.x, c.y * q.y)));
+}
+
+// grid (blocks, ceil(nq / G)): block (x, y) streams the chunks of block x of the one-query kernel for the queries G y .. G y + G - 1.
+// Query g of the group lives in ROW g of the wave: lane 16 g + j holds 1 / |q_g|, "q_g is zero" and tau_g, and tests row j of the
+// chunk against it -- one distance, one compare and one ballot for the 4 G (row, query) pairs.  A padding query of the last group
+// re-reads the round's last query and is switched off in its lanes (and tau = -1 passes nothing): it never produces a key.
+// Dynamic LDS: waves x G x LK_GROUP_BUF keys + the chunk counter (32 KiB + 16 at 16 waves and G = 4, the one-query kernel's).
+template <int G, bool FILTERED>
+__global__ void __launch_bounds__(1024) SMT_NO_PACKED_F32 largek_collect_group_kernel(CollectParams p)
+{
+    constexpr int U = FILTER_CHUNK;
+    static_assert(U == 4 && G >= 2 && G <= LK_GROUP_MAX, "one 16-lane row per query, one lane of its first quad per row of the chunk");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int waves_per_block = blockDim.x >> 6;
+    const uint32_t q0 = blockIdx.y * (uint32_t)G;
+    volatile key_t64 *s_hits = reinterpret_cast<key_t64 *>(smem_raw) + wave * (G * LK_GROUP_BUF);   // [G][LK_GROUP_BUF]
+    uint32_t *s_next = reinterpret_cast<uint32_t *>(reinterpret_cast<key_t64 *>(smem_raw) + waves_per_block * (G * LK_GROUP_BUF));
+
+    const int jj = lane & 3, gq = lane >> 4;
+    const bool tester = (lane & 12) == 0;   // lanes 16 g + j, j < 4: where the group tail leaves tree g's total of row j
+    f32x4 qv[G];
+    float rq_mine = 0.0f, tau_mine = -1.0f;
+    bool qz_mine = true, on_mine = false;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const bool on = q0 + (uint32_t)g < p.nq;
+        const uint32_t qi = on ? q0 + (uint32_t)g : p.nq - 1;
+        qv[g] = reinterpret_cast<const f32x4 *>(p.queries + (size_t)qi * 256)[lane];
+        const float a2 = wave_sum(lk_norm2_lane(qv[g]));
+        const bool qz = (a2 == 0.0f);
+        const float rq = qz ? 0.0f : __frsqrt_rn(a2);
+        const float tau = on ? p.tau[qi] : -1.0f;
+        if (gq == g) { rq_mine = rq; qz_mine = qz; tau_mine = tau; on_mine = on && tester; }
+    }
+
+    const uint64_t n_chunks = p.n_chunks;
+    const const_u64_ptr const_table = (const_u64_ptr)(uintptr_t)p.chunk_table;
+    // (the chunk deal of all streaming kernels: chunk_deal.h)
+    auto fetch_desc = [&](uint64_t c) __attribute__((always_inline)) -> uint64_t {
+        if (c >= n_chunks) return 0ull;
+        if (FILTERED) return const_table[c];
+        const uint64_t v0 = c * U;
+        const uint64_t left = p.n_virtual - v0;
+        return v0 | ((left < (uint64_t)U ? left : (uint64_t)U) << 32);
+    };
+    if (threadIdx.x == 0) *s_next = (uint32_t)waves_per_block;
+    lk_block_barrier();
+
+    uint32_t n_buf[G];  // wave-uniform: keys waiting in query g's part of s_hits
+#pragma unroll
+    for (int g = 0; g < G; ++g) n_buf[g] = 0;
+    auto flush = [&](int g) __attribute__((always_inline)) {   // (only a query of the round ever has keys waiting: q0 + g < p.nq)
+        if (n_buf[g] == 0) return;
+        unsigned int base = 0;
+        if (lane == 0) base = atomicAdd(p.counts + q0 + g, n_buf[g]);
+        base = (unsigned int)__builtin_amdgcn_readfirstlane((int)base);
+        __builtin_amdgcn_wave_barrier();
+        key_t64 *cand = p.cand + (size_t)(q0 + g) * p.cap;
+        for (uint32_t i = lane; i < n_buf[g]; i += 64) {
+            const uint64_t slot = (uint64_t)base + i;
+            if (slot < p.cap) cand[slot] = s_hits[g * LK_GROUP_BUF + i];   // beyond cap: counted, not stored (SMT_STATUS_OVERFLOW)
+        }
+        __builtin_amdgcn_wave_barrier();
+        n_buf[g] = 0;
+    };
+
+    f32x4 cn[U];
+    uint32_t rown[U];
+    uint64_t cA = deal_chunk((uint32_t)wave, waves_per_block), cB = n_chunks, cC = n_chunks;
+    uint64_t dA = fetch_desc(cA), dB = 0;
+    if (cA < n_chunks) {
+        deal_issue_loads<U, true>(p, dA, lane, cn, rown);
+        cB = deal_chunk(deal_claim(s_next, lane), waves_per_block);
+        dB = fetch_desc(cB);
+        if (FILTERED) cC = deal_chunk(deal_claim(s_next, lane), waves_per_block);
+    }
+    while (cA < n_chunks) {
+        f32x4 c[U];
+        uint32_t row[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) { c[j] = cn[j]; row[j] = rown[j]; }
+        const uint64_t first = dA & 0xFFFFFFFFull, end = first + (dA >> 32);
+        if (cB < n_chunks) deal_issue_loads<U, true>(p, dB, lane, cn, rown);
+        uint64_t cN, dN;
+        if (FILTERED) { cN = cC; dN = fetch_desc(cC); cC = deal_chunk(deal_claim(s_next, lane), waves_per_block); }
+        else { cN = deal_chunk(deal_claim(s_next, lane), waves_per_block); dN = fetch_desc(cN); }
+
+        // the G + 1 trees of the chunk: <c, c>, then <c, q_g>; heads and row steps interleaved, ONE tail for the query trees
+        float part[G + 1][4], v[G + 1];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) part[0][j] = lk_row_dot(c[j], c[j]);
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) part[1 + g][j] = lk_row_dot(c[j], qv[g]);
+        wave_sum4_multi_head<G + 1>(part, v, lane);
+        wave_sum4_rows<G + 1>(v);
+        // (a tree that does not exist is fed a register that is there anyway: its row is switched off)
+        float b2 = v[0], t0 = v[1], t1 = v[2], t2 = v[G >= 3 ? 3 : 1], t3 = v[G >= 4 ? 4 : 2];
+        wave_sum4_group_tail(b2, t0, t1, t2, t3);
+        float d = dist_f32(t0, b2, rq_mine, qz_mine);
+        if (!(d == d)) d = __builtin_inff();
+        const bool pass_mine = on_mine && (first + (uint64_t)jj < end) && (d <= tau_mine);
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(pass_mine);
+        if (m != 0ull) {
+            const key_t64 my_key = make_key(d, jj == 0 ? row[0] : jj == 1 ? row[1] : jj == 2 ? row[2] : row[3]);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const uint32_t mg = (uint32_t)(m >> (16 * g)) & 0xFu;   // rows of the chunk that pass query g
+                if (mg == 0u) continue;
+                const uint32_t cnt = (uint32_t)__builtin_popcount(mg);
+                if (n_buf[g] + cnt > (uint32_t)LK_GROUP_BUF) flush(g);
+                if (pass_mine && gq == g) s_hits[g * LK_GROUP_BUF + n_buf[g] + (uint32_t)__builtin_popcount(mg & ((1u << jj) - 1u))] = my_key;
+                n_buf[g] += cnt;
+            }
+        }
+        cA = cB; dA = dB;
+        cB = cN; dB = dN;
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) flush(g);
+}
+
+using CollectKernel = void (*)(CollectParams);
+CollectKernel largek_group_kernel_for(int G, bool filtered)
+{
+    switch (G) {
+    case 2: return filtered ? largek_collect_group_kernel<2, true> : largek_collect_group_kernel<2, false>;
+    case 3: return filtered ? largek_collect_group_kernel<3, true> : largek_collect_group_kernel<3, false>;
+    default: return filtered ? largek_collect_group_kernel<4, true> : largek_collect_group_kernel<4, false>;
+    }
 }
 
 struct FinishParams {
@@ -403,11 +576,18 @@ int launch_topk_large(smt_ctx *ctx, const ScanArgs &a)
     while (cap_p < cap) cap_p <<= 1;
     const uint32_t nq_round = std::min<uint32_t>(a.nq, LK_MAX_QUERIES);
     const bool filtered = a.n_ranges > 0;
+    // Batches collect in ONE sweep of the batched kernel with preset thresholds (launch_gemm_threshold) instead of streaming passes:
+    // unfiltered from LK_K3_MIN_NQ queries, range-filtered -- over the tile table -- from tuning key largek_sweep_filtered (0: never).
+    // Its keys carry the nominating distance, whose band (bf16 x 3 over the f32 rows, f16 x 2 over the operand image) widens tau and
+    // the certificate alike
+    const uint32_t sweep_min = filtered ? (uint32_t)ctx->tune.largek_sweep_filtered : LK_K3_MIN_NQ;
+    const bool k3 = !skip && sweep_min > 0 && a.nq >= sweep_min;
+    const uint64_t n_table = !filtered ? 0 : k3 ? a.n_vtiles : a.n_chunks;   // entries of the tile resp. chunk table
     const size_t b_samp = lk_align((size_t)nq_round * S * sizeof(float));
     const size_t b_tau = lk_align((size_t)nq_round * sizeof(float));
     const size_t b_cnt = lk_align((size_t)nq_round * sizeof(unsigned int));
     const size_t b_cand = lk_align((size_t)nq_round * cap * sizeof(key_t64));
-    const size_t b_table = filtered ? lk_align((size_t)a.n_chunks * sizeof(uint64_t)) : 0;
+    const size_t b_table = lk_align((size_t)n_table * sizeof(uint64_t));
     int rc = ensure_largek(ctx, b_samp + b_tau + b_cnt + b_cand + b_table);
     if (rc) return rc;
     char *base = reinterpret_cast<char *>(ctx->d_largek);
@@ -416,7 +596,8 @@ int launch_topk_large(smt_ctx *ctx, const ScanArgs &a)
     unsigned int *counts = reinterpret_cast<unsigned int *>(base + b_samp + b_tau);
     key_t64 *cand = reinterpret_cast<key_t64 *>(base + b_samp + b_tau + b_cnt);
     const uint64_t *table = nullptr;
-    if (filtered && (rc = range_chunk_table(ctx, a, reinterpret_cast<uint64_t *>(base + b_samp + b_tau + b_cnt + b_cand), &table))) return rc;
+    uint64_t *scratch_table = reinterpret_cast<uint64_t *>(base + b_samp + b_tau + b_cnt + b_cand);
+    if (filtered && (rc = k3 ? range_tile_table(ctx, a, scratch_table, &table) : range_chunk_table(ctx, a, scratch_table, &table))) return rc;
 
     const size_t finish_smem = (size_t)cap_p * sizeof(key_t64);
     static bool attrs_set[64] = {};
@@ -428,10 +609,7 @@ int launch_topk_large(smt_ctx *ctx, const ScanArgs &a)
     const int blocks = ctx->tune.scan_blocks > 0 ? ctx->tune.scan_blocks : ctx->num_cus;
     const int threads = ctx->tune.scan_threads;
     const size_t collect_smem = (size_t)(threads / 64) * LK_HIT_BUF * sizeof(key_t64) + 16;
-    // Unfiltered batches of LK_K3_MIN_NQ or more queries collect in ONE sweep of the batched kernel with preset thresholds
-    // (launch_gemm_threshold) instead of a streaming pass per query; its keys carry the nominating distance, whose band (bf16 x 3 over
-    // the f32 rows, f16 x 2 over the operand image) widens tau and the certificate alike
-    const bool k3 = !filtered && !skip && a.nq >= LK_K3_MIN_NQ;
+    const uint32_t group_max = (uint32_t)std::min(std::max(ctx->tune.largek_group, 1), LK_GROUP_MAX);
     const double err = !k3 ? F32_ERR_SCAN : a.image ? F32_ERR_F16X2 : F32_ERR_BF16X3;
     const float ws_clamp = nextafterf((float)(1.0 - (double)a.ws_thr_score + 2 * err), INFINITY);
     for (uint32_t q0 = 0; q0 < a.nq; q0 += nq_round) {
@@ -470,7 +648,7 @@ int launch_topk_large(smt_ctx *ctx, const ScanArgs &a)
             const unsigned int *n_out = nullptr;
             uint32_t stride = 0;
             if ((rc = launch_gemm_threshold(ctx, a.corpus, a.rows, a.image, a.image_zero, queries, nqr, tau, &c_out, &n_out, &stride, cap,
-                                            cand, counts)))
+                                            cand, counts, table, n_table)))
                 return rc;
         } else {
         CollectParams cp;
@@ -483,7 +661,17 @@ int launch_topk_large(smt_ctx *ctx, const ScanArgs &a)
         cp.cand = cand;
         cp.counts = counts;
         cp.cap = cap;
+        cp.nq = nqr;
         prof_begin(ctx, "largek_collect");
+        if (group_max >= 2 && nqr >= 2) {
+            // ONE pass serves the round: as few groups as largek_group allows, evenly filled (five queries: 3 + 2, not 4 + 1)
+            const uint32_t groups = (nqr + group_max - 1) / group_max;
+            const int G = (int)((nqr + groups - 1) / groups);
+            const size_t group_smem = (size_t)(threads / 64) * G * LK_GROUP_BUF * sizeof(key_t64) + 16;
+            prof_begin(ctx, "largek_group");
+            hipLaunchKernelGGL(largek_group_kernel_for(G, filtered), dim3(blocks, (nqr + G - 1) / G), dim3(threads), group_smem, ctx->stream, cp);
+            prof_end(ctx, "largek_group");
+        } else
         if (filtered) hipLaunchKernelGGL((largek_collect_kernel<true>), dim3(blocks, nqr), dim3(threads), collect_smem, ctx->stream, cp);
         else hipLaunchKernelGGL((largek_collect_kernel<false>), dim3(blocks, nqr), dim3(threads), collect_smem, ctx->stream, cp);
         prof_end(ctx, "largek_collect");

@@ -1,7 +1,13 @@
 """A/B of the large-k routes in one process: tuning key largek_sampled 1 (sampled threshold, collect, exact finish: topk_large.hip)
 against 0 (all keys + radix sort: largek.hip), host-form smt_search, wall ms per call.  Legs: 1 query x 1 M rows at k = 57, 100,
 1000; 256 queries x 10 M rows at k = 100 next to k = 10 (the K3 sweep); the fraction of device-form answers that were not PROVED.
-Prints one JSON line."""
+Prints one JSON line.
+
+`ab_largek.py group ROOT ROWS` is one leg of the A/B behind profiles/largek_group_ab.json: the library of the build under ROOT (this
+tree, or a worktree of the parent commit built beside it), host-form wall ms at k = 100 over ROWS rows, unfiltered with 2 / 3 / 4
+queries and inside every second document (5 000 ranges) with 1 .. 256 queries -- on a build that has the keys also at largek_group
+= 1 and, from 8 queries, on the sweep (largek_sweep_filtered = 8).  Every figure is [median, min, max] of its repetitions; run the
+legs of the two builds alternately in one session and compare medians against the spread."""
 import json
 import os
 import sys
@@ -10,7 +16,8 @@ import time
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+GROUP_LEG = len(sys.argv) > 3 and sys.argv[1] == "group"
+sys.path.insert(0, os.path.abspath(sys.argv[2]) if GROUP_LEG else os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import semtools_amd as smt  # noqa: E402
 
 
@@ -34,7 +41,55 @@ def timed(fn, reps):
     return float(np.median(t))
 
 
+def spread(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return [round(float(np.median(t)), 3), round(min(t), 3), round(max(t), 3)]
+
+
+def group_leg(root, rows):
+    assert os.path.abspath(smt.__file__).startswith(os.path.abspath(root)), smt.__file__
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(7)
+    ctx = smt.Context(0, stream=torch.cuda.current_stream().cuda_stream)
+    x = unit(rows, dev, g)
+    c = smt.Corpus(ctx, device_ptr=x.data_ptr(), rows=rows)
+    q = torch.nn.functional.normalize(torch.randn(256, 256, device=dev, generator=g), dim=1).cpu().numpy()
+    doc = rows // 10_000
+    every_second = [(2 * i * doc, (2 * i + 1) * doc) for i in range(5_000)]
+    try:
+        ctx.set_tuning("largek_group", 4)
+        has_keys = True
+    except Exception:
+        has_keys = False   # the parent build: a pass per query, no filtered sweep
+    out = {"tool": "ab_largek group", "root": os.path.basename(os.path.abspath(root)), "rows": rows, "k": 100}
+    legs = [("group4", 4, 0), ("group1", 1, 0), ("sweep", 4, 8)] if has_keys else [("parent", None, None)]
+    for name, grp, sweep in legs:
+        if grp is not None:
+            ctx.set_tuning("largek_group", grp)
+            ctx.set_tuning("largek_sweep_filtered", sweep)
+        if name != "sweep":
+            for nq in (1, 2, 3, 4, 8):
+                out[f"unfiltered_{nq}q_{name}_ms"] = spread(lambda: c.search(q[:nq], top_k=100), 7 if rows <= 1_000_000 else 5)
+        for nq in (1, 2, 4, 8, 9, 16, 64, 256):
+            if name == "sweep" and nq < 8:
+                continue
+            reps = 7 if nq <= 16 and rows <= 1_000_000 else 3
+            out[f"every_second_{nq}q_{name}_ms"] = spread(lambda: c.search(q[:nq], top_k=100, ranges=every_second), reps)
+    c.close()
+    ctx.close()
+    print(json.dumps(out), flush=True)
+
+
 def main():
+    if GROUP_LEG:
+        return group_leg(sys.argv[2], int(sys.argv[3]))
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev)
     g.manual_seed(7)
