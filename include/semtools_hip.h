@@ -444,7 +444,21 @@ int smt_lower_lines(smt_lower *h, const char *text, const uint64_t *line_begin, 
  * Replaces `Document::embeddings: Vec<Vec<f32>>` (src/search/mod.rs:18-22)
  * and the vector half of the workspace store (line_embeddings.qdrant,
  * src/workspace/store.rs:152-166, upsert :402-434): one row-major f32 matrix
- * [rows x D] resident in HBM; row index == insertion order. */
+ * [rows x D] resident in HBM; row index == insertion order.
+ *
+ * WIDTHS.  D = 256 (SMT_DIM, the reference model's) or a WIDE row of 512, 768 or 1024 floats -- S = 2, 3, 4 slabs of 1 KiB; any other
+ * D is SMT_E_UNSUPPORTED here, in smt_corpus_from_device, smt_corpus_load and every smt_model_create* form.  D = 256 runs the
+ * kernels it always ran.  Wide rows have units of their own (embed_slab.hip, scan_slab.hip, finish_slab.hip, search_slab.cpp):
+ *   served   append, write_rows, read_rows, truncate, save, load, append_to_file, the domain check over the whole row;
+ *            smt_embed / smt_embed_device from a plain f32, f16 or int8 table, bit-identical to pooling on the CPU;
+ *            smt_search in SMT_MODE_DOCUMENTS without max_distance and in SMT_MODE_WORKSPACE with or without it, 0 <= top_k <= 56,
+ *            with ranges and row_base, any nq (passes of four queries); smt_search_topk_device[_ex], 1 <= top_k <= 56, with the
+ *            per-query verdict.  Distances are the same exact f64 values, lists the same (distance, row) order, an unproved list
+ *            is re-answered exhaustively by smt_search and counted by smt_ctx_uncertain_count, as for 256.
+ *   wide rows: not yet (SMT_E_UNSUPPORTED, the message names the width, nothing is enqueued or changed)
+ *            SMT_MODE_DOCUMENTS with max_distance (the threshold kernel); top_k > 56 (the large-k route); smt_corpus_prepack and the
+ *            batched MFMA route; smt_corpus_compact; smt_ivfpq_build / smt_ivfpq_load; models with a token mapping or weights;
+ *            the sharded corpus and model constructors; the host layer (include/semtools_host.h) and the CLI, which stay 256. */
 int smt_corpus_create(smt_ctx *ctx, uint32_t D, uint64_t capacity_rows, smt_corpus **out);
 /* adopt rows already in device memory (not copied, not freed, not growable) */
 int smt_corpus_from_device(smt_ctx *ctx, const float *rows_dev, uint64_t n_rows, uint32_t D,

@@ -237,8 +237,9 @@ class Model:
     """Device-resident model2vec table (smt_model)."""
 
     def __init__(self, ctx, table=None, normalize=True, device_ptr=None, V=None, dtype=np.float32, mapping=None, weights=None,
-                 mapping_ptr=None, weights_ptr=None, n_tokens=None):
-        """table: a float32, float16 or int8 array [V x 256], uploaded as it is (K1 widens narrow rows in registers).
+                 mapping_ptr=None, weights_ptr=None, n_tokens=None, dim=L.DIM):
+        """table: a float32, float16 or int8 array [V x D], D = 256 or a wide 512, 768, 1024 (plain models only), uploaded as it is
+        (K1 widens narrow rows in registers).  dim: the width of a table given by device_ptr.
         device_ptr / V / dtype: adopt a table of that dtype already in device memory.
         mapping / weights: the indexed form of a vocabulary-quantised model -- token id -> table row (integers) and one scalar per
         token (converted to float32 by value); either may be None (identity / 1).  A line pools weights[t] * table[mapping[t]].
@@ -250,10 +251,11 @@ class Model:
                 raise ValueError("with device_ptr the token arrays are device pointers too: mapping_ptr / weights_ptr / n_tokens")
             indexed = mapping_ptr is not None or weights_ptr is not None
             L.check(L.lib().smt_model_create_from_device_indexed(
-                ctx._h, C.c_void_p(device_ptr), L.table_dtype_code(dtype), int(V), L.DIM,
+                ctx._h, C.c_void_p(device_ptr), L.table_dtype_code(dtype), int(V), int(dim),
                 C.c_void_p(mapping_ptr) if mapping_ptr is not None else None, C.c_void_p(weights_ptr) if weights_ptr is not None else None,
                 int(n_tokens if n_tokens is not None else V) if indexed else 0, int(normalize), C.byref(self._h)))
             self.V = int(V)
+            self.dim = int(dim)
         else:
             table = _table(table)
             assert table.ndim == 2
@@ -262,19 +264,21 @@ class Model:
                                                      table.shape[1], L.np_ptr(mapping), L.np_ptr(weights), n_tok, int(normalize),
                                                      C.byref(self._h)))
             self.V = table.shape[0]
+            self.dim = int(table.shape[1])
 
     @classmethod
-    def from_file(cls, ctx, path, byte_offset, V, normalize=True, dtype=np.float32, mapping=None, weights=None):
-        """Stream a table [V x 256] of `dtype` that sits at `byte_offset` of a file into device memory as stored; mapping / weights
+    def from_file(cls, ctx, path, byte_offset, V, normalize=True, dtype=np.float32, mapping=None, weights=None, dim=L.DIM):
+        """Stream a table [V x dim] of `dtype` that sits at `byte_offset` of a file into device memory as stored; mapping / weights
         (host arrays) as in the constructor."""
         mapping, weights, n_tok = L.token_arrays(mapping, weights, int(V))
         self = cls.__new__(cls)
         self.ctx = ctx
         self._h = C.c_void_p()
         L.check(L.lib().smt_model_create_from_file_indexed(ctx._h, str(path).encode(), int(byte_offset), L.table_dtype_code(dtype), int(V),
-                                                           L.DIM, L.np_ptr(mapping), L.np_ptr(weights), n_tok, int(normalize),
+                                                           int(dim), L.np_ptr(mapping), L.np_ptr(weights), n_tok, int(normalize),
                                                            C.byref(self._h)))
         self.V = int(V)
+        self.dim = int(dim)
         return self
 
     def _token_info(self):
@@ -330,11 +334,11 @@ class Model:
 
     def embed(self, ids, offsets, max_tokens=2048, append_to=None, want_host=True):
         """encode_with_args' pool step for a CSR batch of token ids.  Returns
-        ([n_lines x 256] f32 or None, first_row or None)."""
+        ([n_lines x dim] f32 or None, first_row or None)."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = max(offsets.size - 1, 0)
-        out = np.empty((n, L.DIM), dtype=np.float32) if want_host else None
+        out = np.empty((n, self.dim), dtype=np.float32) if want_host else None
         first = C.c_uint64(0)
         L.check(L.lib().smt_embed(self._h, L.np_ptr(ids), L.np_ptr(offsets), n, int(max_tokens),
                                   L.np_ptr(out) if want_host else None,
@@ -628,18 +632,19 @@ class Lower:
 
 
 class Corpus:
-    """Row-major f32 [rows x 256] matrix resident in HBM (smt_corpus)."""
+    """Row-major f32 [rows x dim] matrix resident in HBM (smt_corpus); dim = 256, or a wide 512, 768, 1024."""
 
-    def __init__(self, ctx, capacity_rows=0, device_ptr=None, rows=None, _handle=None, _borrowed=False):
+    def __init__(self, ctx, capacity_rows=0, device_ptr=None, rows=None, _handle=None, _borrowed=False, dim=L.DIM):
         self.ctx = ctx
         self._h = C.c_void_p()
         self._borrowed = _borrowed     # a shard owned by a ShardedCorpus
         if _handle is not None:
             self._h = _handle
         elif device_ptr is not None:
-            L.check(L.lib().smt_corpus_from_device(ctx._h, C.c_void_p(device_ptr), int(rows), L.DIM, C.byref(self._h)))
+            L.check(L.lib().smt_corpus_from_device(ctx._h, C.c_void_p(device_ptr), int(rows), int(dim), C.byref(self._h)))
         else:
-            L.check(L.lib().smt_corpus_create(ctx._h, L.DIM, int(capacity_rows), C.byref(self._h)))
+            L.check(L.lib().smt_corpus_create(ctx._h, int(dim), int(capacity_rows), C.byref(self._h)))
+        self.dim = int(L.lib().smt_corpus_dim(self._h))   # (a loaded or borrowed corpus: the width it was made with)
 
     @classmethod
     def load(cls, ctx, path):
@@ -673,17 +678,17 @@ class Corpus:
         return self.rows
 
     def append(self, rows):
-        rows = _f32c(rows).reshape(-1, L.DIM)
+        rows = _f32c(rows).reshape(-1, self.dim)
         first = C.c_uint64(0)
         L.check(L.lib().smt_corpus_append_host(self._h, L.np_ptr(rows), rows.shape[0], C.byref(first)))
         return int(first.value)
 
     def write_rows(self, first_row, rows):
-        rows = _f32c(rows).reshape(-1, L.DIM)
+        rows = _f32c(rows).reshape(-1, self.dim)
         L.check(L.lib().smt_corpus_write_rows(self._h, int(first_row), L.np_ptr(rows), rows.shape[0]))
 
     def read_rows(self, first_row, n_rows):
-        out = np.empty((int(n_rows), L.DIM), dtype=np.float32)
+        out = np.empty((int(n_rows), self.dim), dtype=np.float32)
         L.check(L.lib().smt_corpus_read_rows(self._h, int(first_row), int(n_rows), L.np_ptr(out)))
         return out
 
@@ -794,7 +799,7 @@ class Corpus:
         """Returns a list (one per query) of (rows uint64[n], dist float64[n]).
 
         mode/threshold semantics: see include/semtools_hip.h (smt_search)."""
-        q = _f32c(queries).reshape(-1, L.DIM)
+        q = _f32c(queries).reshape(-1, self.dim)
         nq = q.shape[0]
         if out_cap is None:
             out_cap = max(int(top_k), 1)
@@ -825,12 +830,14 @@ class Corpus:
     def search_topk_device(self, queries_ptr, nq, top_k, row_base, out_rows_ptr, out_dist_ptr, out_status_ptr=None):
         """out_status_ptr: device-addressable uint32[nq] receiving the per-query verdict (smt_search_topk_device_ex: 0 proved exact,
         1 certificate failed, 2 candidate buffer overflowed, 3 = SMT_STATUS_INVALID_QUERY: the query lies outside the domain), or None."""
+        # (the hot call of a resident caller: the pointers go through the argtypes' own conversion, no ctypes object is built per call)
         if out_status_ptr:
-            L.check(L.lib().smt_search_topk_device_ex(self._h, C.c_void_p(queries_ptr), int(nq), int(top_k), int(row_base),
-                                                      C.c_void_p(out_rows_ptr), C.c_void_p(out_dist_ptr), C.c_void_p(int(out_status_ptr))))
-            return
-        L.check(L.lib().smt_search_topk_device(self._h, C.c_void_p(queries_ptr), int(nq), int(top_k), int(row_base),
-                                               C.c_void_p(out_rows_ptr), C.c_void_p(out_dist_ptr)))
+            rc = L.lib().smt_search_topk_device_ex(self._h, queries_ptr, int(nq), int(top_k), int(row_base), out_rows_ptr, out_dist_ptr,
+                                                   int(out_status_ptr))
+        else:
+            rc = L.lib().smt_search_topk_device(self._h, queries_ptr, int(nq), int(top_k), int(row_base), out_rows_ptr, out_dist_ptr)
+        if rc:
+            L.check(rc)
 
 
 class IvfPq:

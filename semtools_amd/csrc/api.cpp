@@ -11,6 +11,7 @@
 #include <unistd.h>
 
 #include "common.h"
+#include "wide_rows.h"
 
 namespace smt {
 
@@ -730,7 +731,7 @@ try {
     SMT_REQUIRE(out && table_host, "null argument");
     *out = nullptr;
     SMT_REQUIRE_DTYPE(table_dtype);
-    if (D != SMT_DIM) { set_error("embedding dim %u unsupported (kernels are specialised for 256)", D); return SMT_E_UNSUPPORTED; }
+    if (!dim_supported(D)) return refuse_dim(D);
     SMT_REQUIRE(V > 0, "empty table");
     if ((rc = bind_device(ctx))) return rc;
     smt_model *m = new (std::nothrow) smt_model();
@@ -760,7 +761,7 @@ try {
     SMT_REQUIRE(out && table_dev, "null argument");
     *out = nullptr;
     SMT_REQUIRE_DTYPE(table_dtype);
-    if (D != SMT_DIM) { set_error("embedding dim %u unsupported", D); return SMT_E_UNSUPPORTED; }
+    if (!dim_supported(D)) return refuse_dim(D);
     // K1 reads rows with 16-byte lane loads
     if (reinterpret_cast<uintptr_t>(table_dev) % 16 != 0) { set_error("the device table must be 16-byte aligned"); return SMT_E_INVALID; }
     smt_model *m = new (std::nothrow) smt_model();
@@ -849,6 +850,7 @@ try {
     SMT_REQUIRE(out != nullptr, "out");
     int rc = smt::check_indexed_args(mapping_host, weights_host, n_tokens, n_rows);
     if (rc) return rc;
+    if (dim_is_wide(D) && (mapping_host || weights_host)) return refuse_wide(D, "a model with a token mapping or weights");
     smt_model *m = nullptr;
     if ((rc = smt_model_create_typed(ctx, table_host, table_dtype, n_rows, D, normalize, &m))) return rc;
     if ((rc = smt::model_attach_tokens(m, mapping_host, weights_host, n_tokens, false))) { smt_model_destroy(m); return rc; }
@@ -862,6 +864,7 @@ try {
     SMT_REQUIRE(out != nullptr, "out");
     int rc = smt::check_indexed_args(mapping_dev, weights_dev, n_tokens, n_rows);
     if (rc) return rc;
+    if (dim_is_wide(D) && (mapping_dev || weights_dev)) return refuse_wide(D, "a model with a token mapping or weights");
     smt_model *m = nullptr;
     if ((rc = smt_model_create_from_device_typed(ctx, table_dev, table_dtype, n_rows, D, normalize, &m))) return rc;
     if ((rc = smt::model_attach_tokens(m, mapping_dev, weights_dev, n_tokens, true))) { smt_model_destroy(m); return rc; }
@@ -897,7 +900,7 @@ try {
     if (rc) return rc;
     SMT_REQUIRE(out != nullptr, "out");
     *out = nullptr;
-    if (D != SMT_DIM) { set_error("embedding dim %u unsupported (kernels are specialised for 256)", D); return SMT_E_UNSUPPORTED; }
+    if (!dim_supported(D)) return refuse_dim(D);
     if ((rc = bind_device(ctx))) return rc;
     smt_corpus *c = new (std::nothrow) smt_corpus();
     if (!c) { set_error("out of host memory"); return SMT_E_NOMEM; }
@@ -916,7 +919,7 @@ try {
     if (rc) return rc;
     SMT_REQUIRE(out && (rows_dev || n_rows == 0), "null argument");
     *out = nullptr;
-    if (D != SMT_DIM) { set_error("embedding dim %u unsupported", D); return SMT_E_UNSUPPORTED; }
+    if (!dim_supported(D)) return refuse_dim(D);
     smt_corpus *c = new (std::nothrow) smt_corpus();
     if (!c) { set_error("out of host memory"); return SMT_E_NOMEM; }
     c->ctx = ctx; c->dim = D; c->owned = false;
@@ -925,7 +928,7 @@ try {
     // the rows as they are NOW must be in the library's domain (domain.hip); the caller answers for what it writes there later
     if (n_rows) {
         int rc2 = bind_device(ctx);
-        if (!rc2) rc2 = require_rows_domain(ctx, rows_dev, n_rows, "smt_corpus_from_device");
+        if (!rc2) rc2 = require_rows_domain_dim(ctx, rows_dev, n_rows, D, "smt_corpus_from_device");
         if (rc2) { delete c; return rc2; }
     }
     *out = c;
@@ -960,7 +963,7 @@ try {
     SMT_HIP_CHECK(hipMemcpyAsync(c->d_rows + (size_t)c->rows * c->dim, rows, (size_t)n_rows * c->dim * sizeof(float),
                                  hipMemcpyHostToDevice, c->ctx->stream));
     // (checked where they landed, behind the last counted row: a refused batch leaves the corpus as it was)
-    if ((rc = require_rows_domain(c->ctx, c->d_rows + (size_t)c->rows * c->dim, n_rows, "smt_corpus_append_host", 0))) return rc;
+    if ((rc = require_rows_domain_dim(c->ctx, c->d_rows + (size_t)c->rows * c->dim, n_rows, c->dim, "smt_corpus_append_host", 0))) return rc;
     c->rows += n_rows;
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
@@ -991,6 +994,7 @@ try {
 int smt_corpus_prepack(smt_corpus *c, int enable)
 try {
     SMT_REQUIRE(c != nullptr, "corpus");
+    if (dim_is_wide(c->dim)) return refuse_wide(c->dim, "smt_corpus_prepack (the fp16 operand image)");
     int rc = bind_device(c->ctx);
     if (rc) return rc;
     if (!enable) {
@@ -1051,6 +1055,7 @@ try {
 
 int smt_corpus_compact(smt_corpus *c, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved)
 try {
+    if (c && dim_is_wide(c->dim)) return refuse_wide(c->dim, "smt_corpus_compact");
     return corpus_compact(c, keep, n_keep, rows_moved);
 } catch (...) { return smt::api_catch(); }
 
@@ -1073,6 +1078,9 @@ try {
     SMT_REQUIRE(n_lines == 0 || (offsets_dev && out_dev), "null argument");
     int rc = bind_device(model->ctx);
     if (rc) return rc;
+    if (dim_is_wide(model->D))   // (a wide model is a plain one: embed_slab.hip)
+        return launch_embed_slab(model->ctx, model->d_table, model->table_dtype, model->V, model->D, model->normalize, ids_dev, offsets_dev,
+                                 n_lines, max_tokens, out_dev);
     return launch_embed(model->ctx, model->d_table, model->table_dtype, model->V, model->normalize, ids_dev, offsets_dev, n_lines,
                         max_tokens, out_dev, 0, model->d_tok, model->n_tokens);
 } catch (...) { return smt::api_catch(); }
@@ -1119,15 +1127,18 @@ try {
         if ((rc = corpus_reserve(append_to, append_to->rows + n_lines))) return rc;
         d_out = append_to->d_rows + (size_t)append_to->rows * append_to->dim;
     }
-    rc = launch_embed(ctx, model->d_table, model->table_dtype, model->V, model->normalize, d_ids, d_off, n_lines, max_tokens, d_out,
-                      std::max<uint64_t>(n_ids, 1), model->d_tok, model->n_tokens);
+    if (dim_is_wide(model->D))
+        rc = launch_embed_slab(ctx, model->d_table, model->table_dtype, model->V, model->D, model->normalize, d_ids, d_off, n_lines, max_tokens, d_out);
+    else
+        rc = launch_embed(ctx, model->d_table, model->table_dtype, model->V, model->normalize, d_ids, d_off, n_lines, max_tokens, d_out,
+                          std::max<uint64_t>(n_ids, 1), model->d_tok, model->n_tokens);
     if (rc) return rc;
     if (out_host)
         SMT_HIP_CHECK(hipMemcpyAsync(out_host, d_out, (size_t)n_lines * model->D * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (append_to) {
         // a table with non-finite or absurd entries pools rows no search kernel answers for: they do not enter the corpus
-        if ((rc = require_rows_domain(ctx, d_out, n_lines, "smt_embed (rows pooled from the table)", 0))) return rc;
+        if ((rc = require_rows_domain_dim(ctx, d_out, n_lines, model->D, "smt_embed (rows pooled from the table)", 0))) return rc;
         append_to->rows += n_lines;
     }
     return SMT_OK;

@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "common.h"
+#include "wide_rows.h"
 
 using namespace smt;
 
@@ -318,7 +319,7 @@ int corpus_load_slice(smt_corpus *c, const char *path, uint64_t first_row, uint6
     // a foreign or damaged file may hold anything: its rows enter the corpus only if they are in the library's domain (domain.hip)
     {
         uint64_t n_bad = 0, first = 0;
-        if ((rc = check_rows_domain(ctx, c->d_rows + (size_t)c->rows * c->dim, n_rows, &n_bad, &first))) return rc;
+        if ((rc = check_rows_domain_dim(ctx, c->d_rows + (size_t)c->rows * c->dim, n_rows, c->dim, &n_bad, &first))) return rc;
         if (n_bad) {
             set_error("'%s': %llu rows are outside the library's domain (first: row %llu of the file) -- non-finite or absurd "
                       "magnitudes: a damaged or foreign file (include/semtools_hip.h, \"Domain\")", path, (unsigned long long)n_bad,
@@ -523,7 +524,7 @@ try {
     *out = nullptr;
     const size_t elem = smt::table_elem_bytes(table_dtype);
     if (elem == 0) { set_error("unknown table dtype %d (SMT_TABLE_F32, SMT_TABLE_F16, SMT_TABLE_I8)", table_dtype); return SMT_E_INVALID; }
-    if (D != SMT_DIM) { set_error("embedding dim %u unsupported (kernels are specialised for 256)", D); return SMT_E_UNSUPPORTED; }
+    if (!dim_supported(D)) return refuse_dim(D);
     SMT_REQUIRE(V > 0, "empty table");
     if ((rc = bind_device(ctx))) return rc;
     FILE *f = fopen(path, "rb");
@@ -565,6 +566,7 @@ try {
     SMT_REQUIRE(out != nullptr, "out");
     int rc = smt::check_indexed_args(mapping_host, weights_host, n_tokens, n_rows);
     if (rc) return rc;
+    if (smt::dim_is_wide(D) && (mapping_host || weights_host)) return smt::refuse_wide(D, "a model with a token mapping or weights");
     smt_model *m = nullptr;
     if ((rc = smt_model_create_from_file_typed(ctx, path, byte_offset, table_dtype, n_rows, D, normalize, &m))) return rc;
     if ((rc = smt::model_attach_tokens(m, mapping_host, weights_host, n_tokens, false))) { smt_model_destroy(m); return rc; }

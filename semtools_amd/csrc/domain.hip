@@ -24,6 +24,7 @@
 // only a corrupt table or hand-made vectors are.
 #include "common.h"
 #include "device_utils.h"
+#include "wide_rows.h"
 
 namespace smt {
 
@@ -85,6 +86,67 @@ int require_rows_domain(smt_ctx *ctx, const float *d_rows, uint64_t n_rows, cons
 {
     uint64_t n_bad = 0, first = 0;
     const int rc = check_rows_domain(ctx, d_rows, n_rows, &n_bad, &first);
+    if (rc) return rc;
+    if (n_bad == 0) return SMT_OK;
+    set_error("%s: %llu of %llu rows are outside the library's domain (first: row %llu) -- every component must be finite and the "
+              "largest magnitude of a row 0 or within [2^-40, 2^40] (include/semtools_hip.h, \"Domain\")",
+              what, (unsigned long long)n_bad, (unsigned long long)n_rows, (unsigned long long)(base + first));
+    return SMT_E_INVALID;
+}
+
+// WIDE rows (wide_rows.h: n_slabs = 2, 3, 4 slabs of 256 floats): the same verdict over the WHOLE row.  One wave per row, lane l
+// holds float4 number l of every slab -- the scan's layout (scan_slab.hip) -- and folds the slabs' magnitudes before the lanes meet.
+__global__ void __launch_bounds__(256) rows_domain_slab_kernel(const float *rows, uint64_t n_rows, uint32_t n_slabs, unsigned long long *out /* [count, first] */)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    for (uint64_t r = wave; r < n_rows; r += n_waves) {
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(rows + r * 256 * n_slabs) + lane;
+        uint32_t m = 0;
+        for (uint32_t s = 0; s < n_slabs; ++s) {
+            const u32x4 v = __builtin_nontemporal_load(src + s * 64);
+            m = max(m, max(max(v.x & 0x7fffffffu, v.y & 0x7fffffffu), max(v.z & 0x7fffffffu, v.w & 0x7fffffffu)));
+        }
+        m = max(m, dpp_u<DPP_XOR1>(m));
+        m = max(m, dpp_u<DPP_XOR2>(m));
+        m = max(m, dpp_u<DPP_HALF_MIRROR>(m));
+        m = max(m, dpp_u<DPP_MIRROR>(m));
+        const uint32_t m0 = (uint32_t)__builtin_amdgcn_readlane((int)m, 0), m1 = (uint32_t)__builtin_amdgcn_readlane((int)m, 16);
+        const uint32_t m2 = (uint32_t)__builtin_amdgcn_readlane((int)m, 32), m3 = (uint32_t)__builtin_amdgcn_readlane((int)m, 48);
+        if (!magnitude_in_domain(max(max(m0, m1), max(m2, m3))) && lane == 0) {
+            atomicAdd(out, 1ull);
+            atomicMin(out + 1, (unsigned long long)r);
+        }
+    }
+}
+
+int check_rows_domain_dim(smt_ctx *ctx, const float *d_rows, uint64_t n_rows, uint32_t dim, uint64_t *n_bad, uint64_t *first_bad)
+{
+    if (dim == SMT_DIM) return check_rows_domain(ctx, d_rows, n_rows, n_bad, first_bad);
+    *n_bad = 0;
+    *first_bad = ~0ull;
+    if (n_rows == 0) return SMT_OK;
+    SMT_REQUIRE(dim_is_wide(dim), "rows of 256, 512, 768 or 1024 floats");
+    unsigned long long init[2] = {0ull, ~0ull}, got[2] = {0ull, ~0ull};
+    unsigned long long *d = ctx->d_status + 2;
+    SMT_HIP_CHECK(hipMemcpyAsync(d, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
+    const int blocks = (int)std::min<uint64_t>((n_rows + 3) / 4, (uint64_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) * 8);
+    hipLaunchKernelGGL(rows_domain_slab_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_rows, n_rows, dim / 256, d);
+    SMT_HIP_CHECK(hipGetLastError());
+    SMT_HIP_CHECK(hipMemcpyAsync(got, d, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
+    SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    *n_bad = got[0];
+    *first_bad = got[1];
+    return SMT_OK;
+}
+
+int require_rows_domain_dim(smt_ctx *ctx, const float *d_rows, uint64_t n_rows, uint32_t dim, const char *what, uint64_t base)
+{
+    if (dim == SMT_DIM) return require_rows_domain(ctx, d_rows, n_rows, what, base);
+    uint64_t n_bad = 0, first = 0;
+    const int rc = check_rows_domain_dim(ctx, d_rows, n_rows, dim, &n_bad, &first);
     if (rc) return rc;
     if (n_bad == 0) return SMT_OK;
     set_error("%s: %llu of %llu rows are outside the library's domain (first: row %llu) -- every component must be finite and the "

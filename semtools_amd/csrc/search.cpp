@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "common.h"
+#include "wide_rows.h"
 
 using namespace smt;
 
@@ -781,6 +782,8 @@ static int search_local_host_impl(smt_corpus *corpus, const float *queries, uint
 int search_local_host(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, double max_distance, int mode,
                       const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, std::vector<LocalHits> &out)
 {
+    // a wide corpus takes its own route at the top and never reaches a 256 kernel (search_slab.cpp)
+    if (corpus && dim_is_wide(corpus->dim)) return search_wide_host(corpus, queries, nq, top_k, max_distance, mode, ranges, n_ranges, row_base, out);
     if (mode != SMT_MODE_WORKSPACE || !queries || nq == 0)
         return search_local_host_impl(corpus, queries, nq, top_k, max_distance, mode, ranges, n_ranges, row_base, out);
     // workspace mode: zero queries never reach the GPU (every row ties at distance 1.0: the kernels would flag the answer uncertain
@@ -842,6 +845,7 @@ int search_topk_packed_local(smt_corpus *corpus, const float *queries_dev, uint3
                              uint64_t row_base, uint64_t *packed_dev, uint64_t *uncertain_dev, bool allow_async)
 {
     SMT_REQUIRE(corpus && queries_dev && packed_dev, "null argument");
+    if (dim_is_wide(corpus->dim)) return refuse_wide(corpus->dim, "the sharded exchange path");
     smt_ctx *ctx = corpus->ctx;
     SMT_REQUIRE(k_pad >= 1 && k_pad <= (ctx->tune.largek_sampled ? LARGEK_MAX_K : SCAN_MAX_K),
                 ctx->tune.largek_sampled ? "top_k of the device exchange path must be in [1, 1024]"
@@ -923,6 +927,7 @@ int smt_search_topk_device_ex(smt_corpus *corpus, const float *queries_dev, uint
                               uint64_t *out_rows_dev, double *out_dist_dev, uint32_t *out_status_dev)
 try {
     SMT_REQUIRE(corpus != nullptr, "corpus");
+    if (corpus->dim != SMT_DIM) return search_wide_device(corpus, queries_dev, nq, top_k, row_base, out_rows_dev, out_dist_dev, out_status_dev);
     SMT_REQUIRE(nq == 0 || (queries_dev && out_rows_dev && out_dist_dev), "null argument");
     smt_ctx *ctx = corpus->ctx;
     const bool large = top_k > SCAN_MAX_K;   // 57..1024: the sampled-threshold route (topk_large.hip; tuning key largek_sampled)

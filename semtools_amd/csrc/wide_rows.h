@@ -1,0 +1,64 @@
+// wide_rows.h -- rows of D = 256 * S floats, S in {2, 3, 4}: what the wide units share (embed_slab.hip, scan_slab.hip,
+// finish_slab.hip, search_slab.cpp).  A wide row is S SLABS of 1 KiB; D = 256 runs none of this.
+#pragma once
+#include "common.h"
+
+namespace smt {
+
+inline bool dim_is_wide(uint32_t D) { return D == 512 || D == 768 || D == 1024; }
+inline bool dim_supported(uint32_t D) { return D == SMT_DIM || dim_is_wide(D); }
+// SMT_E_UNSUPPORTED for a width no kernel serves (the message names 256 and lists the four widths)
+int refuse_dim(uint32_t D);
+// SMT_E_UNSUPPORTED for a call wide rows do not serve yet: `what` names it, the message names the width
+int refuse_wide(uint32_t D, const char *what);
+
+// |f32 scan distance - exact distance| of scan_slab_kernel<S, .>, by the counting rule at F32_ERR_SCAN (common.h): a lane runs
+// 4 S fused multiply-adds, the tree (wave_sum4 or wave_sum: six levels) is taken as eight steps as there, on terms whose absolute
+// sum is <= 1, and two rsqrt and two multiplies follow: (4 S + 8 + 4) roundings of 2^-24 -- 1.19e-6, 1.43e-6, 1.67e-6 at
+// S = 2, 3, 4 (the rule gives 9.5e-7 at S = 1, the "< 1e-6" written there).  The constant keeps the factor 4 that 4e-6 has over
+// that figure: 4.8e-6, 5.8e-6, 6.7e-6.  (A count that also carries the error of |c|^2 and |q|^2 through their rsqrt comes to
+// (8 S + 22) x 2^-24 = 3.2e-6 at S = 4: inside the margin.)  Not measured on keys yet, unlike the 256 kernels' bound.
+constexpr double f32_err_slab(int S) { return 4.0 * (double)(4 * S + 12) / 16777216.0; }
+
+constexpr int SLAB_MAX_LISTS = 256;   // block lists per query the finish kernel merges: the scan launches at most this many blocks
+
+// K1 (embed_slab.hip): plain tables of `table_dtype`, rows of D elements
+int launch_embed_slab(smt_ctx *ctx, const void *table, int table_dtype, uint64_t V, uint32_t D, int normalize, const uint32_t *ids,
+                      const uint64_t *offsets, uint64_t n_lines, uint32_t max_tokens, float *out);
+
+// K2 + finish for the queries of one call, in passes of up to four (scan_slab.hip, finish_slab.hip).  All pointers device; enqueued
+// on the context's stream, nothing waits.  chunk_table / n_chunks: the range filter (range_tables.hip), nullptr / 0 without one.
+struct SlabSearch {
+    const float *corpus = nullptr;
+    uint64_t rows = 0;                 // < 2^32 - 1
+    uint32_t dim = 0;
+    const float *queries = nullptr;    // [nq x dim]
+    uint32_t nq = 0;
+    uint32_t k_out = 0;                // 1 .. SCAN_MAX_K; slots beyond the rows there are hold (UINT64_MAX, +inf)
+    const uint64_t *chunk_table = nullptr;
+    uint64_t n_chunks = 0;
+    uint64_t row_base = 0;
+    uint64_t *out_rows = nullptr;      // [nq][k_out]
+    double *out_dist = nullptr;        // [nq][k_out]
+    uint64_t *out_counts = nullptr;    // [nq] or nullptr
+    uint32_t *out_status = nullptr;    // [nq] or nullptr: SMT_STATUS_*
+};
+int launch_search_slab(smt_ctx *ctx, const SlabSearch &a);
+// the finish stage alone (finish_slab.hip): lists [nq][n_lists][kp] of block lists -> answers, one block per query
+int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, uint32_t n_lists, uint32_t kp, uint32_t first_query,
+                       uint32_t nq_pass);
+// the exhaustive re-answer's kernel (finish_slab.hip): out[i] = exact f64 distance of row i (no table), or of row j of chunk c at
+// out[4 c + j] (slots past a chunk's rows are not written)
+int launch_exact_all_slab(smt_ctx *ctx, const float *corpus, uint64_t rows, uint32_t dim, const float *query, const uint64_t *chunk_table,
+                          uint64_t n_chunks, double *out);
+// domain.hip: rows of `dim` floats (the whole row: every slab), as check_rows_domain does for 256
+int check_rows_domain_dim(smt_ctx *ctx, const float *d_rows, uint64_t n_rows, uint32_t dim, uint64_t *n_bad, uint64_t *first_bad);
+int require_rows_domain_dim(smt_ctx *ctx, const float *d_rows, uint64_t n_rows, uint32_t dim, const char *what, uint64_t base = 0);
+
+// search_slab.cpp: what smt_search / smt_search_topk_device[_ex] do for a wide corpus
+int search_wide_host(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, double max_distance, int mode,
+                     const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, std::vector<LocalHits> &out);
+int search_wide_device(smt_corpus *corpus, const float *queries_dev, uint32_t nq, uint32_t top_k, uint64_t row_base, uint64_t *out_rows_dev,
+                       double *out_dist_dev, uint32_t *out_status_dev);
+
+}  // namespace smt
