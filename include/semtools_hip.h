@@ -452,9 +452,14 @@ int smt_lower_lines(smt_lower *h, const char *text, const uint64_t *line_begin, 
  *   served   append, write_rows, read_rows, truncate, save, load, append_to_file, the domain check over the whole row;
  *            smt_embed / smt_embed_device from a plain f32, f16 or int8 table, bit-identical to pooling on the CPU;
  *            smt_search in SMT_MODE_DOCUMENTS without max_distance and in SMT_MODE_WORKSPACE with or without it, 0 <= top_k <= 56,
- *            with ranges and row_base, any nq (passes of four queries); smt_search_topk_device[_ex], 1 <= top_k <= 56, with the
+ *            with ranges and row_base, any nq (passes of four queries, batches below); smt_search_topk_device[_ex], 1 <= top_k <= 56, with the
  *            per-query verdict.  Distances are the same exact f64 values, lists the same (distance, row) order, an unproved list
  *            is re-answered exhaustively by smt_search and counted by smt_ctx_uncertain_count, as for 256.
+ *            From tuning key slab_batch_min queries on (default 8) a call runs the BATCHED route (batch_slab.hip): passes of 64 / 32 / 32
+ *            queries at 512 / 768 / 1024 dimensions share one read of the corpus, nominated by bf16 x 3 split products.  The verdict of
+ *            smt_search_topk_device[_ex] then rests on that route's WIDER bound (8.4e-5, 9.7e-5, 1.11e-4 against the scan's 4.8e-6 ..
+ *            6.7e-6): near-ties inside it past the guard band come back SMT_STATUS_UNCERTAIN where the scan would have proved them.
+ *            smt_search first runs such queries again through the scan and re-answers exhaustively only what that leaves unproved.
  *   wide rows: not yet (SMT_E_UNSUPPORTED, the message names the width, nothing is enqueued or changed)
  *            SMT_MODE_DOCUMENTS with max_distance (the threshold kernel); top_k > 56 (the large-k route); smt_corpus_prepack and the
  *            batched MFMA route; smt_corpus_compact; smt_ivfpq_build / smt_ivfpq_load; models with a token mapping or weights;
@@ -1157,6 +1162,14 @@ int smt_debug_select_lists(smt_corpus *corpus, const float *queries_dev, uint32_
 int smt_debug_scan_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
                          uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp, uint32_t *out_route);
 int smt_debug_scan_ring(smt_ctx *ctx, uint32_t calls_back, uint64_t n_keys, uint64_t *out_keys);
+/*   smt_debug_batch_slab_lists   the analogue for the batched route of WIDE rows (csrc/batch_slab.hip): the production query split and
+ *       the launches of batch_slab_kernel for nq (1..256) HOST queries -- one per pass: 64 queries at 512 dimensions, 32 at 768 and 1024
+ *       -- over a wide corpus, optional ranges, the grid the current tuning gives (scan_blocks, guard_band), no finish.  (nq + 1) x
+ *       blocks x k' keys are preset to 0x5A and copied to out_keys, layout [nq + 1][blocks][k']; the last set is the guard.
+ *       tests/test_gpu_wide_batch.py.  SMT_E_INVALID for a corpus that is not wide, top_k outside 1..56, nq outside 1..256, nothing to scan, and
+ *       out_cap_keys < (nq + 1) x blocks x k' (out_blocks and out_kp are set first). */
+int smt_debug_batch_slab_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                               uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp);
 
 /* The context's second stream (hipStream_t), created on first use: async selects run on it, or, with tuning key
  * scan_overlap, it waits for them (every select of an overlapped call enqueued before the work).  A host that
@@ -1208,6 +1221,9 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *                        1: a pass per query.  The answers and the status words are the same bytes at every value
  *   largek_sweep_filtered (default 8; 0 = never)  range-filtered calls of that route with at least this many queries collect in
  *                        ONE sweep of the batched kernel over the tile table of their ranges, as unfiltered calls of five do
+ *   slab_batch_min (default 8; 0 = never)  WIDE rows: calls of at least this many queries run in passes of 64 (512 dimensions) or 32
+ *                        (768, 1024) queries that share one read of the corpus, dot products on the bf16 MFMA pipe (batch_slab.hip);
+ *                        fewer queries run the f32 scan in passes of four, exactly as before.  The answers are the same bytes
  *   direct_delivery (1/0)  smt_search top-k calls with a small answer (<= 32 queries, <= 8 KiB of rows and distances) get it DELIVERED
  *                        by the select kernel: its last block writes the answer into pinned host memory and a completion word behind
  *                        it, which the host waits on -- no D2H copy command, no hipStreamSynchronize (~10 us of a small call); 0: A/B

@@ -36,7 +36,7 @@ void set_error(const char *fmt, ...);
     } while (0)
 
 // bits of smt_ctx::attr_done
-enum : uint32_t { ATTR_SELECT = 1u, ATTR_GEMM = 2u, ATTR_IVF_ASSIGN = 4u, ATTR_IVF_SCORE = 8u, ATTR_GEMM_LDS = 16u, ATTR_IVF_LPCA = 32u };
+enum : uint32_t { ATTR_SELECT = 1u, ATTR_GEMM = 2u, ATTR_IVF_ASSIGN = 4u, ATTR_IVF_SCORE = 8u, ATTR_GEMM_LDS = 16u, ATTR_IVF_LPCA = 32u, ATTR_BATCH_SLAB = 64u };
 
 // One candidate on the device: key = (f32 distance bits << 32) | local row.
 // Distances are clipped to >= 0, so the IEEE bit pattern is order-preserving
@@ -93,7 +93,8 @@ struct Tuning {
     int prof_select = 1;        // 0: do not bracket the select stage with events (2 fewer event records per query)
     int largek_sampled = 1;     // 1: 57 <= top_k <= 1024 take the sampled-threshold route (topk_large.hip); 0: the all-keys path (largek.hip, A/B and parity tests)
     int largek_group = 4;       // the large-k collect serves up to this many queries of a round per corpus pass (1 .. 4; topk_large.hip largek_collect_group_kernel); 1: a pass per query
-    int largek_sweep_filtered = 8;   // range-filtered large-k batches of this many queries collect in ONE sweep of the batched kernel over the tile table, like unfiltered batches of five (0: never); 8: where the sweep first beat the grouped passes (profiles/largek_group_ab.json)
+    int slab_batch_min = 8;     // wide rows: calls of this many queries take the batched bf16 MFMA route (batch_slab.hip; 0: never); 8: the smallest measured batch from which it beats passes of four at all three widths (profiles/wide_batch.json)
+    int largek_sweep_filtered = 8;  // range-filtered large-k batches of this many queries collect in ONE sweep of the batched kernel over the tile table, like unfiltered batches of five (0: never); 8: where the sweep first beat the grouped passes (profiles/largek_group_ab.json)
     int direct_delivery = 1;    // 1: host-form top-k searches with small answers (<= 8 KiB) get them DELIVERED by the select kernel into pinned host memory, completion word last; the host waits on that word (search.cpp; 0: D2H copy + hipStreamSynchronize, A/B)
     int64_t compact_bounce_rows = 65536;   // smt_corpus_compact: rows of the bounce buffer a step with a gap shorter than itself goes through (64 MiB; 64 .. 2^20), compact.hip
     int64_t thr_hit_cap = (int64_t)1 << 20;   // K4: slots of the hit buffer of the first pass (at most the scanned rows); a pass that counts more hits is rerun with an exact-size buffer (tests lower it to reach the rerun on small corpora), threshold.hip

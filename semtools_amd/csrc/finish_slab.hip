@@ -204,7 +204,7 @@ static size_t finish_smem_bytes(uint32_t dim)
 }
 
 int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, uint32_t n_lists, uint32_t kp, uint32_t first_query,
-                       uint32_t nq_pass)
+                       uint32_t nq_pass, double f32_err)
 {
     SMT_REQUIRE(n_lists <= (uint32_t)SLAB_MAX_LISTS && kp >= a.k_out && kp <= 64 && nq_pass >= 1, "wide finish: <= 256 lists, k_out <= k' <= 64");
     SlabFinishParams p;
@@ -220,7 +220,7 @@ int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, 
     p.out_counts = a.out_counts ? a.out_counts + first_query : nullptr;
     p.out_status = a.out_status ? a.out_status + first_query : nullptr;
     const int S = (int)(a.dim / 256);
-    p.f32_err = S == 2 ? f32_err_slab(2) : S == 3 ? f32_err_slab(3) : f32_err_slab(4);
+    p.f32_err = f32_err > 0.0 ? f32_err : S == 2 ? f32_err_slab(2) : S == 3 ? f32_err_slab(3) : f32_err_slab(4);
     p.sticky = ctx->d_status;
     const size_t smem = finish_smem_bytes(a.dim);
     prof_begin(ctx, "finish_slab");

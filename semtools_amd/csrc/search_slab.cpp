@@ -1,6 +1,8 @@
 // search_slab.cpp -- the search entry points over a WIDE corpus (rows of 512, 768 or 1024 floats): what smt_search and
 // smt_search_topk_device[_ex] do before they would reach a 256 kernel.  Served: top-k (1 .. 56) in documents mode without a
-// distance bound, workspace mode with or without one, ranges, row_base, any number of queries in passes of four.  Everything is
+// distance bound, workspace mode with or without one, ranges, row_base, any number of queries in passes of four, or -- from tuning
+// key slab_batch_min queries on -- in batched passes on the MFMA pipe (batch_slab.hip) whose unproved answers the host form runs
+// again through the scan.  Also the test hook of that route (smt_debug_batch_slab_lists).  Everything is
 // enqueued on the context's stream directly: no one-query pipeline, no grouping, no operand image.  Also the two refusals every
 // other entry point answers a wide corpus or model with.
 #include <algorithm>
@@ -148,6 +150,31 @@ int search_wide_host(smt_corpus *corpus, const float *queries, uint32_t nq, uint
     }
     if (redo.empty()) return SMT_OK;
 
+    // What the batched route left unproved is first run again, together, through the scan route and its tighter f32_err_slab: the
+    // queries move to the front of the stage (ascending, so none is overwritten before it has moved), `redo` then indexes them there.
+    if (slab_batch_serves(ctx, a)) {
+        const uint32_t nr = (uint32_t)redo.size();
+        for (uint32_t i = 0; i < nr; ++i)
+            if (redo[i] != i)
+                SMT_HIP_CHECK(hipMemcpyAsync(const_cast<float *>(d_q) + (size_t)i * dim, d_q + (size_t)redo[i] * dim, (size_t)dim * sizeof(float),
+                                             hipMemcpyDeviceToDevice, ctx->stream));
+        for (uint32_t i = 0; i < nr; ++i) live[i] = live[redo[i]];
+        a.nq = nr;
+        a.scan_only = true;
+        if ((rc = launch_search_slab(ctx, a))) return rc;
+        SMT_HIP_CHECK(hipMemcpyAsync(h, d_out, o_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        redo.clear();
+        for (uint32_t i = 0; i < nr; ++i) {
+            LocalHits &hits = out[live[i]];
+            if (h_st[i] != SMT_STATUS_PROVED) { redo.push_back(i); continue; }
+            hits.rows.assign(h_rows + (size_t)i * k_eff, h_rows + (size_t)i * k_eff + h_cnt[i]);
+            hits.dist.assign(h_dist + (size_t)i * k_eff, h_dist + (size_t)i * k_eff + h_cnt[i]);
+            if (ws_thr) cut_at_score(hits, thr_score);
+        }
+        if (redo.empty()) return SMT_OK;
+    }
+
     // An unproved list is never returned: the exact f64 distance of EVERY allowed row (exact_all_slab_kernel), selected here by
     // (distance, row).  Slow, rare -- near-ties past the guard band -- and correct.
     const uint64_t n_slots = d_table ? n_chunks * FILTER_CHUNK : corpus->rows;
@@ -212,3 +239,65 @@ int search_wide_device(smt_corpus *corpus, const float *queries_dev, uint32_t nq
 }
 
 }  // namespace smt
+
+using namespace smt;
+
+extern "C" {
+
+// Test hook: the block lists of the batched wide route.  The production query split and ONE launch of batch_slab_kernel for nq host
+// queries (at most a pass) over a wide corpus, optional ranges through the chunk table, the grid the current tuning gives
+// (debug_batch_slab_lists, batch_slab.hip).
+int smt_debug_batch_slab_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                               uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp)
+try {
+    SMT_REQUIRE(corpus && queries && out_keys && out_blocks && out_kp, "null argument");
+    SMT_REQUIRE(dim_is_wide(corpus->dim), "debug batch lists: a wide corpus (512, 768 or 1024 dimensions)");
+    SMT_REQUIRE(top_k >= 1 && top_k <= SCAN_MAX_K, "debug batch lists: top_k in [1, 56]");
+    SMT_REQUIRE(nq >= 1 && nq <= 256, "debug batch lists: 1 .. 256 queries");
+    smt_ctx *ctx = corpus->ctx;
+    int rc = bind_device(ctx);
+    if (rc) return rc;
+    *out_blocks = 0; *out_kp = 0;
+    if ((rc = validate_ranges(ranges, n_ranges, corpus->rows))) return rc;
+    const uint32_t dim = corpus->dim;
+    std::vector<smt_range> rr;
+    std::vector<uint64_t> chunk_prefix(1, 0);
+    for (uint32_t i = 0; i < n_ranges; ++i) {
+        const uint64_t len = ranges[i].end - ranges[i].begin;
+        if (!len) continue;
+        rr.push_back(ranges[i]);
+        chunk_prefix.push_back(chunk_prefix.back() + (len + FILTER_CHUNK - 1) / FILTER_CHUNK);
+    }
+    SMT_REQUIRE(n_ranges ? !rr.empty() : corpus->rows > 0, "debug batch lists: no row to scan");
+    const uint64_t n_chunks = chunk_prefix.back();
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t q_bytes = al((size_t)nq * dim * sizeof(float)), r_bytes = al(rr.size() * sizeof(smt_range));
+    const size_t cp_bytes = al(chunk_prefix.size() * sizeof(uint64_t)), t_bytes = al((size_t)n_chunks * sizeof(uint64_t));
+    if ((rc = ensure_stage(ctx, q_bytes + r_bytes + cp_bytes + t_bytes))) return rc;
+    char *stage = reinterpret_cast<char *>(ctx->d_stage);
+    SMT_HIP_CHECK(hipMemcpyAsync(stage, queries, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    uint64_t *d_table = nullptr;
+    if (!rr.empty()) {
+        SMT_HIP_CHECK(hipMemcpyAsync(stage + q_bytes, rr.data(), rr.size() * sizeof(smt_range), hipMemcpyHostToDevice, ctx->stream));
+        SMT_HIP_CHECK(hipMemcpyAsync(stage + q_bytes + r_bytes, chunk_prefix.data(), chunk_prefix.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
+                                     ctx->stream));
+        d_table = reinterpret_cast<uint64_t *>(stage + q_bytes + r_bytes + cp_bytes);
+        if ((rc = launch_build_chunk_table(ctx, reinterpret_cast<const smt_range *>(stage + q_bytes),
+                                           reinterpret_cast<const uint64_t *>(stage + q_bytes + r_bytes), (uint32_t)rr.size(), n_chunks, d_table)))
+            return rc;
+    }
+    SlabSearch a;
+    a.corpus = corpus->d_rows;
+    a.rows = corpus->rows;
+    a.dim = dim;
+    a.queries = reinterpret_cast<const float *>(stage);
+    a.nq = nq;
+    a.k_out = top_k;
+    a.chunk_table = d_table;
+    a.n_chunks = n_chunks;
+    rc = debug_batch_slab_lists(ctx, a, reinterpret_cast<key_t64 *>(out_keys), out_cap_keys, out_blocks, out_kp);
+    if (rc) (void)hipStreamSynchronize(ctx->stream);   // (the uploads read this frame's vectors)
+    return rc;
+} catch (...) { return smt::api_catch(); }
+
+}  // extern "C"

@@ -20,7 +20,14 @@ int refuse_wide(uint32_t D, const char *what);
 // (8 S + 22) x 2^-24 = 3.2e-6 at S = 4: inside the margin.)  Not measured on keys yet, unlike the 256 kernels' bound.
 constexpr double f32_err_slab(int S) { return 4.0 * (double)(4 * S + 12) / 16777216.0; }
 
-constexpr int SLAB_MAX_LISTS = 256;   // block lists per query the finish kernel merges: the scan launches at most this many blocks
+// ... of batch_slab_kernel<S, .> (batch_slab.hip), by the rule for bf16 x 3 at F32_ERR_BF16X3 (common.h): representation
+// 3 x 2^-16 |x||q| (4.6e-5), 48 S MFMA instructions at 2 ulp = 2^-23 each (2.3e-5, 3.4e-5, 4.6e-5), the two f32 scalings (1e-6),
+// the whole times the 1.2 that took 5.8e-5 to 7e-5 there: 8.4e-5, 9.7e-5, 1.11e-4 at S = 2, 3, 4.
+// MEASURED on every key tests/test_gpu_wide_batch.py reads through smt_debug_batch_slab_lists (profiles/wide_batch.json): at most
+// 7.7e-7 on random rows, 2.6e-5 on the constructed worst-case rows (1024 dimensions).
+constexpr double f32_err_batch_slab(int S) { return 1.2 * (3.0 / 65536.0 + 48.0 * S * 2.0 / 8388608.0 + 1e-6); }
+
+constexpr int SLAB_MAX_LISTS = 256;  // block lists per query the finish kernel merges: the scan launches at most this many blocks
 
 // K1 (embed_slab.hip): plain tables of `table_dtype`, rows of D elements
 int launch_embed_slab(smt_ctx *ctx, const void *table, int table_dtype, uint64_t V, uint32_t D, int normalize, const uint32_t *ids,
@@ -42,11 +49,23 @@ struct SlabSearch {
     double *out_dist = nullptr;        // [nq][k_out]
     uint64_t *out_counts = nullptr;    // [nq] or nullptr
     uint32_t *out_status = nullptr;    // [nq] or nullptr: SMT_STATUS_*
+    bool scan_only = false;            // never the batched route (the host form's re-run of what that route left unproved)
 };
 int launch_search_slab(smt_ctx *ctx, const SlabSearch &a);
-// the finish stage alone (finish_slab.hip): lists [nq][n_lists][kp] of block lists -> answers, one block per query
+// the finish stage alone (finish_slab.hip): lists [nq][n_lists][kp] of block lists -> answers, one block per query, certified under
+// f32_err (0: the scan's f32_err_slab)
 int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, uint32_t n_lists, uint32_t kp, uint32_t first_query,
-                       uint32_t nq_pass);
+                       uint32_t nq_pass, double f32_err = 0.0);
+// The batched route (batch_slab.hip): calls of at least tuning key slab_batch_min queries (0: never) run passes of slab_batch_qb
+// queries -- 64 at 512 dimensions, 32 at 768 and 1024 -- on the bf16 MFMA pipe, certified under f32_err_batch_slab.
+inline bool slab_batch_serves(const smt_ctx *ctx, const SlabSearch &a)
+{
+    return !a.scan_only && ctx->tune.slab_batch_min > 0 && a.nq >= (uint32_t)ctx->tune.slab_batch_min;
+}
+uint32_t slab_batch_qb(uint32_t dim);
+int launch_batch_slab(smt_ctx *ctx, const SlabSearch &a);
+int debug_batch_slab_lists(smt_ctx *ctx, const SlabSearch &a, key_t64 *out_keys_host, uint64_t out_cap_keys, uint32_t *out_blocks,
+                           uint32_t *out_kp);
 // the exhaustive re-answer's kernel (finish_slab.hip): out[i] = exact f64 distance of row i (no table), or of row j of chunk c at
 // out[4 c + j] (slots past a chunk's rows are not written)
 int launch_exact_all_slab(smt_ctx *ctx, const float *corpus, uint64_t rows, uint32_t dim, const float *query, const uint64_t *chunk_table,
