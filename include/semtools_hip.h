@@ -463,11 +463,44 @@ int smt_lower_lines(smt_lower *h, const char *text, const uint64_t *line_begin, 
  *   wide rows: not yet (SMT_E_UNSUPPORTED, the message names the width, nothing is enqueued or changed)
  *            SMT_MODE_DOCUMENTS with max_distance (the threshold kernel); top_k > 56 (the large-k route); smt_corpus_prepack and the
  *            batched MFMA route; smt_corpus_compact; smt_ivfpq_build / smt_ivfpq_load; models with a token mapping or weights;
- *            the sharded corpus and model constructors; the host layer (include/semtools_host.h) and the CLI, which stay 256. */
+ *            the sharded corpus and model constructors; the host layer (include/semtools_host.h) and the CLI, which stay 256.
+ *
+ * HALF ROWS.  A corpus made with SMT_ROWS_F16 stores each row as 256 IEEE binary16 values: 512 B, half the bytes of every scan
+ * and twice the lines per GPU.  D = 256 only: SMT_ROWS_F16 with a wide D is SMT_E_UNSUPPORTED, an unknown row_dtype SMT_E_INVALID.
+ * Everything the library promises about answers holds over the STORED values: the exact distance of a row is the f64 distance
+ * (sequential sums, simsimd's accurate form) of the row widened to f32 -- which is exact -- and the query as given in f32; lists
+ * are in (distance, row) order, distances bit-identical to that, an unproved list is never returned by smt_search, and
+ * smt_search_topk_device_ex gives the per-query verdict.  Units of their own: rows_half.hip, scan_half.hip; the finish stage and
+ * the host entry are the wide rows' with the element type (finish_slab.hip, search_slab.cpp).
+ * Rows that enter as f32 (append_host, write_rows, smt_embed with a corpus to append to) are rounded to nearest-even ONCE, on
+ * the device, bit for bit what NumPy's astype(float16) gives: subnormal halves are kept (not flushed, at the store or when the
+ * scan widens them), -0.0 stays -0.0.  The domain check refuses a row that is outside the f32 domain below ("Domain") OR has a
+ * component that would round to an infinity (|x| >= 65520): SMT_E_INVALID, the corpus untouched.  A row that rounds to all zeros
+ * is a zero row like any other.  The f32 domain's "scaling by a power of two changes no answer" is NOT claimed for half rows:
+ * a scaled row can round into or out of the subnormal halves, which changes the stored direction.
+ *   served   append_host, write_rows, read_rows (widened to f32, exact), truncate, destroy; smt_embed appending into it (the
+ *            stored bits equal float16(pooled f32 row)); smt_search in SMT_MODE_DOCUMENTS without max_distance and in
+ *            SMT_MODE_WORKSPACE with or without it, 0 <= top_k <= 56, ranges, row_base, any nq in passes of up to four queries,
+ *            the zero-query shortcut of workspace mode; smt_search_topk_device[_ex], 1 <= top_k <= 56, with verdicts; unproved
+ *            lists of smt_search re-answered exhaustively and counted by smt_ctx_uncertain_count.
+ *   half rows: not yet (SMT_E_UNSUPPORTED, the message names the half rows, nothing is enqueued or changed)
+ *            SMT_MODE_DOCUMENTS with max_distance; top_k > 56; smt_corpus_prepack and the batched MFMA route;
+ *            smt_corpus_compact; smt_corpus_save / smt_corpus_append_to_file (and smt_corpus_load: the file format holds f32 rows
+ *            only, so it never yields a half corpus); smt_ivfpq_build / smt_ivfpq_load; the test hooks of the 256 kernels.  The
+ *            sharded corpus constructors, the host layer and the CLI make their own f32 corpora and have no typed form.
+ * These calls skip the one-query pipeline, its grouping and direct delivery: everything is enqueued on the context's stream. */
+#define SMT_ROWS_F32 0
+#define SMT_ROWS_F16 1
 int smt_corpus_create(smt_ctx *ctx, uint32_t D, uint64_t capacity_rows, smt_corpus **out);
 /* adopt rows already in device memory (not copied, not freed, not growable) */
 int smt_corpus_from_device(smt_ctx *ctx, const float *rows_dev, uint64_t n_rows, uint32_t D,
                            smt_corpus **out);
+/* The same two with the element type of the stored rows (SMT_ROWS_*); the untyped forms are the SMT_ROWS_F32 case.  Adopted half
+ * rows: [n_rows x 256] binary16, 16-byte aligned, every value finite (an Inf or NaN is SMT_E_INVALID as a row outside the domain). */
+int smt_corpus_create_typed(smt_ctx *ctx, uint32_t D, int row_dtype, uint64_t capacity_rows, smt_corpus **out);
+int smt_corpus_from_device_typed(smt_ctx *ctx, const void *rows_dev, int row_dtype, uint64_t n_rows, uint32_t D, smt_corpus **out);
+/* what a corpus stores: SMT_ROWS_*, D, bytes per stored row; any pointer may be NULL */
+int smt_corpus_info(const smt_corpus *corpus, int *row_dtype, uint32_t *D, uint64_t *row_bytes);
 void smt_corpus_destroy(smt_corpus *corpus);
 int smt_corpus_append_host(smt_corpus *corpus, const float *rows, uint64_t n_rows,
                            uint64_t *first_row);

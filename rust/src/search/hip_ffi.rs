@@ -125,6 +125,8 @@ pub const SMT_WP_CP_DROPPED: c_int = 3;
 pub const SMT_WP_CP_FLAG: c_int = 4;
 pub const SMT_UG_MAX_WORD: c_int = 64;
 pub const SMT_UG_MAX_LONG: c_int = 2048;
+pub const SMT_ROWS_F32: c_int = 0;
+pub const SMT_ROWS_F16: c_int = 1;
 pub const SMT_STATUS_PROVED: c_int = 0;
 pub const SMT_STATUS_UNCERTAIN: c_int = 1;
 pub const SMT_STATUS_OVERFLOW: c_int = 2;
@@ -425,6 +427,27 @@ extern "C" {
         n_rows: u64,
         D: u32,
         out: *mut *mut SmtCorpus,
+    ) -> c_int;
+    pub fn smt_corpus_create_typed(
+        ctx: *mut SmtCtx,
+        D: u32,
+        row_dtype: c_int,
+        capacity_rows: u64,
+        out: *mut *mut SmtCorpus,
+    ) -> c_int;
+    pub fn smt_corpus_from_device_typed(
+        ctx: *mut SmtCtx,
+        rows_dev: *const c_void,
+        row_dtype: c_int,
+        n_rows: u64,
+        D: u32,
+        out: *mut *mut SmtCorpus,
+    ) -> c_int;
+    pub fn smt_corpus_info(
+        corpus: *const SmtCorpus,
+        row_dtype: *mut c_int,
+        D: *mut u32,
+        row_bytes: *mut u64,
     ) -> c_int;
     pub fn smt_corpus_destroy(corpus: *mut SmtCorpus);
     pub fn smt_corpus_append_host(

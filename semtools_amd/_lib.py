@@ -41,6 +41,7 @@ EXPORTS = [
     "smt_group_set_transport", "smt_group_transport", "smt_debug_range_sets", "smt_sharded_corpus_append_to_file_ex",
     "smt_debug_group_fail_next", "smt_search_topk_device_ex", "smt_sharded_search_topk_device_ex", "smt_debug_deliveries",
     "smt_corpus_compact", "smt_ctx_compact_stats", "smt_sharded_corpus_compact",
+    "smt_corpus_create_typed", "smt_corpus_from_device_typed", "smt_corpus_info",
     "smt_model_create_typed", "smt_model_create_from_file_typed", "smt_model_create_from_device_typed", "smt_model_info",
     "smt_sharded_model_create_typed", "smt_sharded_model_create_from_file_typed", "smt_sharded_model_info",
     "smt_model_create_indexed", "smt_model_create_from_file_indexed", "smt_model_create_from_device_indexed", "smt_model_token_info",
@@ -65,6 +66,9 @@ UG_PREPEND = {"always": 0, "first": 1, "never": 2}
 TABLE_F32, TABLE_F16, TABLE_I8 = 0, 1, 2
 TABLE_DTYPES = {np.dtype(np.float32): TABLE_F32, np.dtype(np.float16): TABLE_F16, np.dtype(np.int8): TABLE_I8}
 TABLE_NP = {v: k for k, v in TABLE_DTYPES.items()}
+ROWS_F32, ROWS_F16 = 0, 1
+ROWS_DTYPES = {np.dtype(np.float32): ROWS_F32, np.dtype(np.float16): ROWS_F16}
+ROWS_NP = {v: k for k, v in ROWS_DTYPES.items()}
 
 
 def table_dtype_code(dtype):
@@ -253,6 +257,9 @@ def lib():
     L.smt_lower_lines.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, vp, vp]
     L.smt_corpus_create.argtypes = [vp, u32, u64, P(vp)]
     L.smt_corpus_from_device.argtypes = [vp, vp, u64, u32, P(vp)]
+    L.smt_corpus_create_typed.argtypes = [vp, u32, i32, u64, P(vp)]
+    L.smt_corpus_from_device_typed.argtypes = [vp, vp, i32, u64, u32, P(vp)]
+    L.smt_corpus_info.argtypes = [vp, P(i32), P(u32), P(u64)]
     L.smt_corpus_destroy.argtypes = [vp]
     L.smt_corpus_destroy.restype = None
     L.smt_corpus_append_host.argtypes = [vp, vp, u64, P(u64)]

@@ -632,19 +632,29 @@ class Lower:
 
 
 class Corpus:
-    """Row-major f32 [rows x dim] matrix resident in HBM (smt_corpus); dim = 256, or a wide 512, 768, 1024."""
+    """Row-major [rows x dim] matrix resident in HBM (smt_corpus); dim = 256, or a wide 512, 768, 1024.  dtype: how the rows are
+    STORED -- np.float32, or np.float16 at dim 256 (half rows: rows go in and come out as f32, rounded to nearest-even once on the
+    device; a device_ptr then points at binary16 values).  A number outside L.ROWS_NP is handed on for the library to refuse."""
 
-    def __init__(self, ctx, capacity_rows=0, device_ptr=None, rows=None, _handle=None, _borrowed=False, dim=L.DIM):
+    def __init__(self, ctx, capacity_rows=0, device_ptr=None, rows=None, _handle=None, _borrowed=False, dim=L.DIM, dtype=np.float32):
         self.ctx = ctx
         self._h = C.c_void_p()
         self._borrowed = _borrowed     # a shard owned by a ShardedCorpus
         if _handle is not None:
             self._h = _handle
         elif device_ptr is not None:
-            L.check(L.lib().smt_corpus_from_device(ctx._h, C.c_void_p(device_ptr), int(rows), int(dim), C.byref(self._h)))
+            L.check(L.lib().smt_corpus_from_device_typed(ctx._h, C.c_void_p(device_ptr), self._rows_code(dtype), int(rows), int(dim),
+                                                         C.byref(self._h)))
         else:
-            L.check(L.lib().smt_corpus_create(ctx._h, int(dim), int(capacity_rows), C.byref(self._h)))
+            L.check(L.lib().smt_corpus_create_typed(ctx._h, int(dim), self._rows_code(dtype), int(capacity_rows), C.byref(self._h)))
         self.dim = int(L.lib().smt_corpus_dim(self._h))   # (a loaded or borrowed corpus: the width it was made with)
+        code = C.c_int32(0)
+        L.check(L.lib().smt_corpus_info(self._h, C.byref(code), None, None))
+        self.dtype = L.ROWS_NP[code.value]
+
+    @staticmethod
+    def _rows_code(dtype):
+        return int(dtype) if isinstance(dtype, int) else L.ROWS_DTYPES[np.dtype(dtype)]
 
     @classmethod
     def load(cls, ctx, path):

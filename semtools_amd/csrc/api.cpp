@@ -11,7 +11,7 @@
 #include <unistd.h>
 
 #include "common.h"
-#include "wide_rows.h"
+#include "half_rows.h"
 
 namespace smt {
 
@@ -237,7 +237,7 @@ int corpus_reserve(smt_corpus *c, uint64_t rows_needed)
     uint64_t cap = std::max<uint64_t>(c->capacity * 2, rows_needed);
     cap = std::max<uint64_t>(cap, 1024);
     float *nd = nullptr;
-    const size_t bytes = (size_t)cap * c->dim * sizeof(float);
+    const size_t bytes = (size_t)cap * c->row_bytes();
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&nd), bytes);
     if (e != hipSuccess && c->image) {
         // the operand image is derived data (up to as many bytes as the rows): the rows' growth goes first.  A later batch builds
@@ -249,7 +249,7 @@ int corpus_reserve(smt_corpus *c, uint64_t rows_needed)
     }
     if (e != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc(%zu) for corpus rows: %s", bytes, hipGetErrorString(e)); return SMT_E_NOMEM; }
     if (c->rows) {
-        e = hipMemcpyAsync(nd, c->d_rows, (size_t)c->rows * c->dim * sizeof(float), hipMemcpyDeviceToDevice, c->ctx->stream);
+        e = hipMemcpyAsync(nd, c->d_rows, (size_t)c->rows * c->row_bytes(), hipMemcpyDeviceToDevice, c->ctx->stream);
         if (e != hipSuccess) { (void)hipFree(nd); set_error("corpus grow copy: %s", hipGetErrorString(e)); return SMT_E_HIP; }
     }
     SMT_HIP_CHECK(hipStreamSynchronize(c->ctx->stream));
@@ -898,17 +898,26 @@ void smt_model_destroy(smt_model *model)
 
 /* --------------------------------------------------------------- corpus ---- */
 
-int smt_corpus_create(smt_ctx *ctx, uint32_t D, uint64_t capacity_rows, smt_corpus **out)
+// the row type of a typed creator: an unknown one is SMT_E_INVALID, half rows exist at 256 dimensions only
+static int check_row_dtype(int row_dtype, uint32_t D)
+{
+    if (row_dtype != SMT_ROWS_F32 && row_dtype != SMT_ROWS_F16) { set_error("unknown row dtype %d (SMT_ROWS_F32, SMT_ROWS_F16)", row_dtype); return SMT_E_INVALID; }
+    if (!dim_supported(D)) return refuse_dim(D);
+    if (row_dtype == SMT_ROWS_F16 && D != SMT_DIM) return refuse_half("a corpus of half rows wider than 256 dimensions");
+    return SMT_OK;
+}
+
+int smt_corpus_create_typed(smt_ctx *ctx, uint32_t D, int row_dtype, uint64_t capacity_rows, smt_corpus **out)
 try {
     int rc = check_ctx(ctx);
     if (rc) return rc;
     SMT_REQUIRE(out != nullptr, "out");
     *out = nullptr;
-    if (!dim_supported(D)) return refuse_dim(D);
+    if ((rc = check_row_dtype(row_dtype, D))) return rc;
     if ((rc = bind_device(ctx))) return rc;
     smt_corpus *c = new (std::nothrow) smt_corpus();
     if (!c) { set_error("out of host memory"); return SMT_E_NOMEM; }
-    c->ctx = ctx; c->dim = D; c->owned = true;
+    c->ctx = ctx; c->dim = D; c->row_dtype = row_dtype; c->owned = true;
     if (capacity_rows) {
         rc = corpus_reserve(c, capacity_rows);
         if (rc) { delete c; return rc; }
@@ -917,25 +926,48 @@ try {
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
-int smt_corpus_from_device(smt_ctx *ctx, const float *rows_dev, uint64_t n_rows, uint32_t D, smt_corpus **out)
+int smt_corpus_create(smt_ctx *ctx, uint32_t D, uint64_t capacity_rows, smt_corpus **out)
+try {
+    return smt_corpus_create_typed(ctx, D, SMT_ROWS_F32, capacity_rows, out);
+} catch (...) { return smt::api_catch(); }
+
+int smt_corpus_from_device_typed(smt_ctx *ctx, const void *rows_dev, int row_dtype, uint64_t n_rows, uint32_t D, smt_corpus **out)
 try {
     int rc = check_ctx(ctx);
     if (rc) return rc;
     SMT_REQUIRE(out && (rows_dev || n_rows == 0), "null argument");
     *out = nullptr;
-    if (!dim_supported(D)) return refuse_dim(D);
+    if ((rc = check_row_dtype(row_dtype, D))) return rc;
+    const bool half = row_dtype == SMT_ROWS_F16;
+    // the half scan reads a row with 16-byte lane loads
+    if (half && reinterpret_cast<uintptr_t>(rows_dev) % 16 != 0) { set_error("half rows in device memory must be 16-byte aligned"); return SMT_E_INVALID; }
     smt_corpus *c = new (std::nothrow) smt_corpus();
     if (!c) { set_error("out of host memory"); return SMT_E_NOMEM; }
-    c->ctx = ctx; c->dim = D; c->owned = false;
-    c->d_rows = const_cast<float *>(rows_dev);
+    c->ctx = ctx; c->dim = D; c->row_dtype = row_dtype; c->owned = false;
+    c->d_rows = static_cast<float *>(const_cast<void *>(rows_dev));
     c->rows = n_rows; c->capacity = n_rows;
     // the rows as they are NOW must be in the library's domain (domain.hip); the caller answers for what it writes there later
     if (n_rows) {
         int rc2 = bind_device(ctx);
-        if (!rc2) rc2 = require_rows_domain_dim(ctx, rows_dev, n_rows, D, "smt_corpus_from_device");
+        if (!rc2) rc2 = half ? require_half_rows_domain(ctx, rows_dev, n_rows, "smt_corpus_from_device_typed")
+                             : require_rows_domain_dim(ctx, c->d_rows, n_rows, D, "smt_corpus_from_device");
         if (rc2) { delete c; return rc2; }
     }
     *out = c;
+    return SMT_OK;
+} catch (...) { return smt::api_catch(); }
+
+int smt_corpus_from_device(smt_ctx *ctx, const float *rows_dev, uint64_t n_rows, uint32_t D, smt_corpus **out)
+try {
+    return smt_corpus_from_device_typed(ctx, rows_dev, SMT_ROWS_F32, n_rows, D, out);
+} catch (...) { return smt::api_catch(); }
+
+int smt_corpus_info(const smt_corpus *corpus, int *row_dtype, uint32_t *D, uint64_t *row_bytes)
+try {
+    SMT_REQUIRE(corpus != nullptr, "corpus");
+    if (row_dtype) *row_dtype = corpus->row_dtype;
+    if (D) *D = corpus->dim;
+    if (row_bytes) *row_bytes = corpus->row_bytes();
     return SMT_OK;
 } catch (...) { return smt::api_catch(); }
 
@@ -964,6 +996,18 @@ try {
     if (first_row) *first_row = c->rows;
     if (n_rows == 0) return SMT_OK;
     if ((rc = corpus_reserve(c, c->rows + n_rows))) return rc;
+    if (rows_are_half(c)) {
+        // uploaded as f32 beside the corpus, rounded and checked on their way behind the last counted row (rows_half.hip)
+        DeviceTemp tmp;
+        const size_t bytes = (size_t)n_rows * c->dim * sizeof(float);
+        if (hipMalloc(&tmp.p, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc(%zu) for the rows to round", bytes); return SMT_E_NOMEM; }
+        SMT_HIP_CHECK(hipMemcpyAsync(tmp.p, rows, bytes, hipMemcpyHostToDevice, c->ctx->stream));
+        if ((rc = rows_to_half(c->ctx, static_cast<const float *>(tmp.p), n_rows, reinterpret_cast<char *>(c->d_rows) + (size_t)c->rows * c->row_bytes(),
+                               "smt_corpus_append_host")))
+            return rc;
+        c->rows += n_rows;
+        return SMT_OK;
+    }
     SMT_HIP_CHECK(hipMemcpyAsync(c->d_rows + (size_t)c->rows * c->dim, rows, (size_t)n_rows * c->dim * sizeof(float),
                                  hipMemcpyHostToDevice, c->ctx->stream));
     // (checked where they landed, behind the last counted row: a refused batch leaves the corpus as it was)
@@ -987,6 +1031,19 @@ try {
             return SMT_E_INVALID;
         }
     }
+    if (rows_are_half(c)) {
+        // rounded and checked beside the corpus first: a refused batch overwrites nothing
+        DeviceTemp tmp;
+        const size_t f_bytes = (size_t)n_rows * c->dim * sizeof(float), h_bytes = (size_t)n_rows * c->row_bytes();
+        if (hipMalloc(&tmp.p, f_bytes + h_bytes) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc(%zu) for the rows to round", f_bytes + h_bytes); return SMT_E_NOMEM; }
+        char *d_half = static_cast<char *>(tmp.p) + f_bytes;
+        SMT_HIP_CHECK(hipMemcpyAsync(tmp.p, rows, f_bytes, hipMemcpyHostToDevice, c->ctx->stream));
+        if ((rc = rows_to_half(c->ctx, static_cast<const float *>(tmp.p), n_rows, d_half, "smt_corpus_write_rows"))) return rc;
+        SMT_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char *>(c->d_rows) + (size_t)first_row * c->row_bytes(), d_half, h_bytes, hipMemcpyDeviceToDevice,
+                                     c->ctx->stream));
+        SMT_HIP_CHECK(hipStreamSynchronize(c->ctx->stream));
+        return SMT_OK;
+    }
     corpus_writer_drain(c);   // (a write-ahead job may be reading these rows)
     SMT_HIP_CHECK(hipMemcpyAsync(c->d_rows + (size_t)first_row * c->dim, rows, (size_t)n_rows * c->dim * sizeof(float),
                                  hipMemcpyHostToDevice, c->ctx->stream));
@@ -998,7 +1055,7 @@ try {
 int smt_corpus_prepack(smt_corpus *c, int enable)
 try {
     SMT_REQUIRE(c != nullptr, "corpus");
-    if (dim_is_wide(c->dim)) return refuse_wide(c->dim, "smt_corpus_prepack (the fp16 operand image)");
+    if (dim_is_wide(c->dim) || rows_are_half(c)) return refuse_rows(c, "smt_corpus_prepack (the fp16 operand image)");
     int rc = bind_device(c->ctx);
     if (rc) return rc;
     if (!enable) {
@@ -1021,6 +1078,7 @@ uint64_t smt_corpus_image_bytes(const smt_corpus *c) { return c && c->image ? c-
 int smt_debug_image_tile(smt_corpus *c, uint64_t tile, void *out_tile_host, uint32_t *out_zero_mask)
 try {
     SMT_REQUIRE(c != nullptr && out_tile_host != nullptr && out_zero_mask != nullptr, "null argument");
+    if (rows_are_half(c)) return refuse_half("smt_debug_image_tile (the fp16 operand image)");
     int rc = bind_device(c->ctx);
     if (rc) return rc;
     const void *img = nullptr;
@@ -1041,6 +1099,16 @@ try {
     int rc = bind_device(c->ctx);
     if (rc) return rc;
     if (n_rows == 0) return SMT_OK;
+    if (rows_are_half(c)) {   // widened on the device (exact), then copied
+        DeviceTemp tmp;
+        const size_t bytes = (size_t)n_rows * c->dim * sizeof(float);
+        if (hipMalloc(&tmp.p, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc(%zu) for the widened rows", bytes); return SMT_E_NOMEM; }
+        if ((rc = launch_half_to_f32(c->ctx, reinterpret_cast<const char *>(c->d_rows) + (size_t)first_row * c->row_bytes(), n_rows, static_cast<float *>(tmp.p))))
+            return rc;
+        SMT_HIP_CHECK(hipMemcpyAsync(out_host, tmp.p, bytes, hipMemcpyDeviceToHost, c->ctx->stream));
+        SMT_HIP_CHECK(hipStreamSynchronize(c->ctx->stream));
+        return SMT_OK;
+    }
     SMT_HIP_CHECK(hipMemcpyAsync(out_host, c->d_rows + (size_t)first_row * c->dim, (size_t)n_rows * c->dim * sizeof(float),
                                  hipMemcpyDeviceToHost, c->ctx->stream));
     SMT_HIP_CHECK(hipStreamSynchronize(c->ctx->stream));
@@ -1059,7 +1127,7 @@ try {
 
 int smt_corpus_compact(smt_corpus *c, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved)
 try {
-    if (c && dim_is_wide(c->dim)) return refuse_wide(c->dim, "smt_corpus_compact");
+    if (c && (dim_is_wide(c->dim) || rows_are_half(c))) return refuse_rows(c, "smt_corpus_compact");
     return corpus_compact(c, keep, n_keep, rows_moved);
 } catch (...) { return smt::api_catch(); }
 
@@ -1111,7 +1179,8 @@ try {
     // staging: ids + rebased offsets (+ output rows when not appending)
     const size_t ids_bytes = ((size_t)n_ids * sizeof(uint32_t) + 15) & ~(size_t)15;
     const size_t off_bytes = ((size_t)(n_lines + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
-    const size_t out_bytes = append_to ? 0 : (size_t)n_lines * model->D * sizeof(float);
+    const bool to_half = append_to && rows_are_half(append_to);   // K1 pools f32 rows into the staging, rows_half.hip stores the halves
+    const size_t out_bytes = append_to && !to_half ? 0 : (size_t)n_lines * model->D * sizeof(float);
     DeviceTemp tmp;
     {
         hipError_t e = hipMalloc(&tmp.p, ids_bytes + off_bytes + out_bytes + 16);
@@ -1129,7 +1198,7 @@ try {
 
     if (append_to) {
         if ((rc = corpus_reserve(append_to, append_to->rows + n_lines))) return rc;
-        d_out = append_to->d_rows + (size_t)append_to->rows * append_to->dim;
+        if (!to_half) d_out = append_to->d_rows + (size_t)append_to->rows * append_to->dim;
     }
     if (dim_is_wide(model->D))
         rc = launch_embed_slab(ctx, model->d_table, model->table_dtype, model->V, model->D, model->normalize, d_ids, d_off, n_lines, max_tokens, d_out);
@@ -1140,7 +1209,12 @@ try {
     if (out_host)
         SMT_HIP_CHECK(hipMemcpyAsync(out_host, d_out, (size_t)n_lines * model->D * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (append_to) {
+    if (to_half) {
+        if ((rc = rows_to_half(ctx, d_out, n_lines, reinterpret_cast<char *>(append_to->d_rows) + (size_t)append_to->rows * append_to->row_bytes(),
+                               "smt_embed (rows pooled from the table)")))
+            return rc;
+        append_to->rows += n_lines;
+    } else if (append_to) {
         // a table with non-finite or absurd entries pools rows no search kernel answers for: they do not enter the corpus
         if ((rc = require_rows_domain_dim(ctx, d_out, n_lines, model->D, "smt_embed (rows pooled from the table)", 0))) return rc;
         append_to->rows += n_lines;

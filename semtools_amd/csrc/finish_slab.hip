@@ -14,7 +14,9 @@
 // CERTIFICATE.  As select.hip's: when k' keys were nominated, a row outside them has scan distance >= the k'-th key's, hence exact
 // distance >= that - f32_err_slab(S) (wide_rows.h); the answer is PROVED when the k_out-th exact distance lies under that floor.
 // Fewer than k' nominated keys are all the rows there are: proved.  A query outside the domain: SMT_STATUS_INVALID_QUERY.
-#include "wide_rows.h"
+// HALF rows (half_rows.h) come here as <1, _Float16>: the row read widens the stored halves -- exactly, in integer arithmetic -- on
+// their way into LDS or the sums, everything behind it is the f32 code; the bound is f32_err_half.
+#include "half_rows.h"
 #include "device_utils.h"
 
 namespace smt {
@@ -36,11 +38,29 @@ struct SlabFinishParams {
 constexpr int FIN_THREADS = 1024;
 constexpr int FIN_SURV_CAP = 4096;   // k'^2 at k' = 64
 
-template <int S>
+// four components of a stored row, widened: e counts float4 (f32 rows) resp. groups of four halves
+template <typename RowT>
+__device__ __forceinline__ f32x4 row_quad(const float *rows, uint64_t row, uint32_t dim, uint32_t e)
+{
+    if constexpr (sizeof(RowT) == 4) {
+        return reinterpret_cast<const f32x4 *>(rows + row * dim)[e];
+    } else {
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 h = reinterpret_cast<const u32x2 *>(reinterpret_cast<const uint16_t *>(rows) + row * dim)[e];
+        f32x4 v;
+        v.x = f32_from_half_bits((uint16_t)h.x);
+        v.y = f32_from_half_bits((uint16_t)(h.x >> 16));
+        v.z = f32_from_half_bits((uint16_t)h.y);
+        v.w = f32_from_half_bits((uint16_t)(h.y >> 16));
+        return v;
+    }
+}
+
+template <int S, typename RowT>
 __global__ void __launch_bounds__(FIN_THREADS) finish_slab_kernel(SlabFinishParams p)
 {
     constexpr int D = 256 * S;
-    constexpr int TB = 32 / S;            // candidate rows staged per tile
+    constexpr int TB = 32 / S < FIN_THREADS / 64 ? 32 / S : FIN_THREADS / 64;   // candidate rows staged per tile
     constexpr int RS = D / 4 + 1;         // LDS row stride in float4: neighbouring rows start 16 bytes apart in the banks
     static_assert(TB <= FIN_THREADS / 64 && (size_t)TB * RS * 16 <= (size_t)FIN_SURV_CAP * 8 + 1024, "a wave per staged row; tiles share the survivors' space");
     extern __shared__ __align__(16) unsigned char fin_smem[];
@@ -113,9 +133,8 @@ __global__ void __launch_bounds__(FIN_THREADS) finish_slab_kernel(SlabFinishPara
     for (int tile0 = 0; tile0 < kp; tile0 += TB) {
         if (wave < TB && tile0 + wave < kp && s_best[tile0 + wave] != KEY_PAD) {
             const uint32_t row = (uint32_t)(s_best[tile0 + wave] & 0xFFFFFFFFull);
-            const f32x4 *src = reinterpret_cast<const f32x4 *>(p.corpus + (uint64_t)row * D);
 #pragma unroll
-            for (int s = 0; s < S; ++s) s_rows[wave * RS + s * 64 + lane] = src[s * 64 + lane];
+            for (int s = 0; s < S; ++s) s_rows[wave * RS + s * 64 + lane] = row_quad<RowT>(p.corpus, row, D, s * 64 + lane);
         }
         __syncthreads();
         const f32x4 *q4 = reinterpret_cast<const f32x4 *>(s_q);
@@ -207,6 +226,7 @@ int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, 
                        uint32_t nq_pass, double f32_err)
 {
     SMT_REQUIRE(n_lists <= (uint32_t)SLAB_MAX_LISTS && kp >= a.k_out && kp <= 64 && nq_pass >= 1, "wide finish: <= 256 lists, k_out <= k' <= 64");
+    const bool half = a.row_dtype == SMT_ROWS_F16;
     SlabFinishParams p;
     p.corpus = a.corpus;
     p.queries = a.queries + (size_t)first_query * a.dim;
@@ -220,13 +240,14 @@ int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, 
     p.out_counts = a.out_counts ? a.out_counts + first_query : nullptr;
     p.out_status = a.out_status ? a.out_status + first_query : nullptr;
     const int S = (int)(a.dim / 256);
-    p.f32_err = f32_err > 0.0 ? f32_err : S == 2 ? f32_err_slab(2) : S == 3 ? f32_err_slab(3) : f32_err_slab(4);
+    p.f32_err = f32_err > 0.0 ? f32_err : half ? f32_err_half : S == 2 ? f32_err_slab(2) : S == 3 ? f32_err_slab(3) : f32_err_slab(4);
     p.sticky = ctx->d_status;
     const size_t smem = finish_smem_bytes(a.dim);
     prof_begin(ctx, "finish_slab");
-    if (S == 2) hipLaunchKernelGGL(finish_slab_kernel<2>, dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
-    else if (S == 3) hipLaunchKernelGGL(finish_slab_kernel<3>, dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
-    else hipLaunchKernelGGL(finish_slab_kernel<4>, dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
+    if (half) hipLaunchKernelGGL((finish_slab_kernel<1, _Float16>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
+    else if (S == 2) hipLaunchKernelGGL((finish_slab_kernel<2, float>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
+    else if (S == 3) hipLaunchKernelGGL((finish_slab_kernel<3, float>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
+    else hipLaunchKernelGGL((finish_slab_kernel<4, float>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
     prof_end(ctx, "finish_slab");
     SMT_HIP_CHECK(hipGetLastError());
     return SMT_OK;
@@ -235,6 +256,7 @@ int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, 
 // The exhaustive re-answer (search_slab.cpp): the exact f64 distance of EVERY allowed row, one thread per row walking its D components
 // in index order; the host then selects by (distance, row).  Slow (a thread's loads are its own row's: nothing coalesces), rare --
 // only a query whose certificate failed comes here -- and correct.
+template <typename RowT>
 __global__ void __launch_bounds__(256) exact_all_slab_kernel(const float *corpus, uint64_t n_rows, uint32_t dim, const float *query,
                                                              const uint64_t *chunk_table, uint64_t n_chunks, double *out)
 {
@@ -255,11 +277,10 @@ __global__ void __launch_bounds__(256) exact_all_slab_kernel(const float *corpus
         row = i;
     }
     const f32x4 *q4 = reinterpret_cast<const f32x4 *>(s_q);
-    const f32x4 *r4 = reinterpret_cast<const f32x4 *>(corpus + row * dim);
     double ab = 0.0, a2 = 0.0, b2 = 0.0;
 #pragma unroll 4
     for (uint32_t e = 0; e < dim / 4; ++e) {
-        const f32x4 a = q4[e], b = r4[e];
+        const f32x4 a = q4[e], b = row_quad<RowT>(corpus, row, dim, e);
         const double ax = a.x, ay = a.y, az = a.z, aw = a.w, bx = b.x, by = b.y, bz = b.z, bw = b.w;
         ab = ab + ax * bx; a2 = a2 + ax * ax; b2 = b2 + bx * bx;
         ab = ab + ay * by; a2 = a2 + ay * ay; b2 = b2 + by * by;
@@ -269,16 +290,18 @@ __global__ void __launch_bounds__(256) exact_all_slab_kernel(const float *corpus
     out[i] = cos_finish_exact(ab, a2, b2);
 }
 
-int launch_exact_all_slab(smt_ctx *ctx, const float *corpus, uint64_t rows, uint32_t dim, const float *query, const uint64_t *chunk_table,
-                          uint64_t n_chunks, double *out)
+int launch_exact_all_slab(smt_ctx *ctx, const float *corpus, int row_dtype, uint64_t rows, uint32_t dim, const float *query,
+                          const uint64_t *chunk_table, uint64_t n_chunks, double *out)
 {
-    SMT_REQUIRE(dim_is_wide(dim), "wide rows: 512, 768 or 1024 dimensions");
+    const bool half = row_dtype == SMT_ROWS_F16;
+    SMT_REQUIRE(half ? dim == SMT_DIM : dim_is_wide(dim), "wide rows: 512, 768 or 1024 dimensions, or half rows of 256");
     const uint64_t n = chunk_table ? n_chunks * FILTER_CHUNK : rows;
     if (n == 0) return SMT_OK;
     const uint64_t blocks = (n + 255) / 256;
     SMT_REQUIRE(blocks < (1ull << 31), "too many rows for one exhaustive launch");
     prof_begin(ctx, "exact_slab");
-    hipLaunchKernelGGL(exact_all_slab_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, corpus, rows, dim, query, chunk_table, n_chunks, out);
+    if (half) hipLaunchKernelGGL(exact_all_slab_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, corpus, rows, dim, query, chunk_table, n_chunks, out);
+    else hipLaunchKernelGGL(exact_all_slab_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, corpus, rows, dim, query, chunk_table, n_chunks, out);
     prof_end(ctx, "exact_slab");
     SMT_HIP_CHECK(hipGetLastError());
     return SMT_OK;

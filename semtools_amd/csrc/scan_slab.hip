@@ -25,25 +25,15 @@
 // the instruction counts; the 256 kernel measured the same trade (2 x 15 against 8 x 11) at 155.6 -> 152.8 us.
 // Either tree has six levels; f32_err_slab (wide_rows.h) counts them as the 256 bound does.
 //
-// Lists, block merge, padding and order are the 256 kernel's ideas, written again for this unit: a lane-distributed sorted list per
+// Lists, block merge, padding and order are the 256 kernel's ideas, written again (lane_list.h, shared with scan_half.hip, whose
+// kernel this file's launch_search_slab also launches): a lane-distributed sorted list per
 // query, k' = min(64, top_k + guard band); every block merges its waves' lists by counting ranks into ONE block list of key_t64 per
 // query, strictly ascending by (distance, row), padded with KEY_PAD.  Range-filtered scans walk the chunk table of
 // range_tables.hip (first row | valid rows << 32, FILTER_CHUNK rows per entry), U rows of an entry per step.
-#include "wide_rows.h"
-#include "device_utils.h"
+#include "half_rows.h"
+#include "lane_list.h"
 
 namespace smt {
-
-struct SlabScanParams {
-    const float *corpus;
-    uint64_t n_rows;
-    const float *queries;          // the pass' first query
-    uint32_t nq_active;            // 1 .. NQ
-    uint32_t kp;
-    const uint64_t *chunk_table;   // FILTERED
-    uint64_t n_chunks;
-    key_t64 *block_lists;          // [NQ][gridDim.x][kp]
-};
 
 template <int S>
 __device__ __forceinline__ float slab_dot(const f32x4 (&a)[S], const f32x4 (&b)[S])
@@ -60,24 +50,6 @@ __device__ __forceinline__ float slab_dot(const f32x4 (&a)[S], const f32x4 (&b)[
         acc = fmaf(a[s].w, b[s].w, acc);
     }
     return acc;
-}
-
-// (d, r) into a lane-distributed list kept in (distance asc, row asc) order; the threshold is the entry of lane kp - 1
-__device__ __forceinline__ void slab_list_insert(float &ld, uint32_t &lr, float &thr_d, uint32_t &thr_r, float d, uint32_t r, int lane, int kp)
-{
-    const bool less = (ld < d) || (ld == d && lr < r);
-    const int pos = __popcll(__ballot(less));
-    const float sd = dpp_f<DPP_WAVE_SHR1>(ld);
-    const uint32_t sr = dpp_u<DPP_WAVE_SHR1>(lr);
-    if (lane > pos) { ld = sd; lr = sr; }
-    else if (lane == pos) { ld = d; lr = r; }
-    thr_d = readlane_f(ld, kp - 1);
-    thr_r = (uint32_t)__builtin_amdgcn_readlane((int)lr, kp - 1);
-}
-
-__device__ __forceinline__ bool slab_under(float d, uint32_t r, float thr_d, uint32_t thr_r)
-{
-    return d < thr_d || (d == thr_d && r < thr_r);
 }
 
 template <int S, int NQ, bool FILTERED>
@@ -219,38 +191,9 @@ __global__ void __launch_bounds__(512) scan_slab_kernel(SlabScanParams p)
         k = kn;
     }
 
-    // block merge: every wave's candidates ranked among all of the block's, one barrier for all queries, every slot of a block list
-    // written once (its key, or the padding from the first slot no key ranks into)
-    unsigned int *s_valid = reinterpret_cast<unsigned int *>(s_keys + (size_t)NQ * waves_per_block * 64);   // [NQ][waves]
-#pragma unroll
-    for (int n = 0; n < NQ; ++n) {
-        const bool have = lane < kp && lr[n] != 0xFFFFFFFFu;
-        s_keys[((size_t)n * waves_per_block + wave) * 64 + lane] = have ? make_key(ld[n], lr[n]) : KEY_PAD;
-        const unsigned int cnt = (unsigned int)__popcll(__ballot(have));
-        if (lane == 0) s_valid[n * waves_per_block + wave] = cnt;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < NQ; ++n) {
-        if ((uint32_t)n >= p.nq_active) break;   // (uniform over the block)
-        const key_t64 *keys_n = s_keys + (size_t)n * waves_per_block * 64;
-        key_t64 *out = p.block_lists + ((size_t)n * gridDim.x + blockIdx.x) * kp;
-        const key_t64 mine = keys_n[wave * 64 + lane];
-        if (mine != KEY_PAD) {
-            int rank = 0;
-            for (int w = 0; w < waves_per_block; ++w)
-                for (int i = 0; i < kp; ++i) rank += (keys_n[w * 64 + i] < mine) ? 1 : 0;
-            if (rank < kp) out[rank] = mine;
-        }
-        if (wave == 0 && lane < kp) {
-            unsigned int total = 0;
-            for (int w = 0; w < waves_per_block; ++w) total += s_valid[n * waves_per_block + w];
-            if ((unsigned int)lane >= total) out[lane] = KEY_PAD;
-        }
-    }
+    slab_block_merge<NQ>(s_keys, ld, lr, p.nq_active, kp, p.block_lists, lane, wave, waves_per_block);
 }
 
-using slab_scan_kernel_t = void (*)(SlabScanParams);
 template <int S>
 static slab_scan_kernel_t slab_scan_kernel_of(int slots, bool filtered)
 {
@@ -263,15 +206,18 @@ constexpr int SLAB_THREADS = 512;   // 8 waves per block, as the 256 scan
 // The passes of one call: up to four queries share a corpus pass (one query: the one-slot kernel), each pass followed by its finish.
 int launch_search_slab(smt_ctx *ctx, const SlabSearch &a)
 {
-    SMT_REQUIRE(dim_is_wide(a.dim), "wide scan: 512, 768 or 1024 dimensions");
+    const bool half = a.row_dtype == SMT_ROWS_F16;   // 512-byte rows of 256 halves: scan_half.hip, eight rows a step
+    SMT_REQUIRE(half ? a.dim == SMT_DIM : dim_is_wide(a.dim), "wide scan: 512, 768 or 1024 dimensions, or half rows of 256");
     SMT_REQUIRE(a.k_out >= 1 && a.k_out <= SCAN_MAX_K, "wide scan: 1 <= top_k <= 56");
     SMT_REQUIRE(a.rows < 0xFFFFFFFFull, "wide scan: fewer than 2^32 - 1 rows per corpus");
     SMT_REQUIRE(a.nq >= 1 && a.queries && a.out_rows && a.out_dist, "wide scan: null argument");
     if (slab_batch_serves(ctx, a) && (a.chunk_table ? a.n_chunks : a.rows) > 0) return launch_batch_slab(ctx, a);   // batch_slab.hip
     const int S = (int)(a.dim / 256);
-    const int U = S == 2 ? 2 : 1;
+    const int U = half ? HALF_STEP_ROWS : S == 2 ? 2 : 1;
     const bool filtered = a.chunk_table != nullptr;
-    const uint64_t n_steps = filtered ? a.n_chunks * (uint64_t)(FILTER_CHUNK / U) : (a.rows + U - 1) / U;
+    const uint64_t n_steps = !filtered ? (a.rows + U - 1) / U
+                             : half    ? (a.n_chunks + HALF_STEP_ROWS / FILTER_CHUNK - 1) / (HALF_STEP_ROWS / FILTER_CHUNK)
+                                       : a.n_chunks * (uint64_t)(FILTER_CHUNK / U);
     const uint32_t kp = std::min<uint32_t>(64, a.k_out + (uint32_t)ctx->tune.guard_band);
     const int waves = SLAB_THREADS / 64;
     const int cus = ctx->tune.scan_blocks > 0 ? ctx->tune.scan_blocks : std::max(ctx->num_cus, 1);
@@ -293,12 +239,13 @@ int launch_search_slab(smt_ctx *ctx, const SlabSearch &a)
         p.chunk_table = a.chunk_table;
         p.n_chunks = a.n_chunks;
         p.block_lists = lists;
-        const slab_scan_kernel_t kernel = S == 2 ? slab_scan_kernel_of<2>(slots, filtered)
+        const slab_scan_kernel_t kernel = half   ? half_scan_kernel_of(slots, filtered)
+                                        : S == 2 ? slab_scan_kernel_of<2>(slots, filtered)
                                         : S == 3 ? slab_scan_kernel_of<3>(slots, filtered) : slab_scan_kernel_of<4>(slots, filtered);
-        const size_t smem = (size_t)slots * waves * 64 * sizeof(key_t64) + (size_t)slots * waves * sizeof(unsigned int);
-        prof_begin(ctx, "scan_slab");
+        const size_t smem = slab_list_smem_bytes(slots, waves);
+        prof_begin(ctx, half ? "scan_half" : "scan_slab");
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(SLAB_THREADS), smem, ctx->stream, p);
-        prof_end(ctx, "scan_slab");
+        prof_end(ctx, half ? "scan_half" : "scan_slab");
         SMT_HIP_CHECK(hipGetLastError());
         if ((rc = launch_finish_slab(ctx, a, lists, (uint32_t)blocks, kp, q0, nq_pass))) return rc;
     }

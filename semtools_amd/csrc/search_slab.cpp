@@ -1,4 +1,5 @@
-// search_slab.cpp -- the search entry points over a WIDE corpus (rows of 512, 768 or 1024 floats): what smt_search and
+// search_slab.cpp -- the search entry points over a WIDE corpus (rows of 512, 768 or 1024 floats) or a HALF corpus (rows of 256
+// binary16 values, half_rows.h: the same calls with the row type handed on, never the batched route): what smt_search and
 // smt_search_topk_device[_ex] do before they would reach a 256 kernel.  Served: top-k (1 .. 56) in documents mode without a
 // distance bound, workspace mode with or without one, ranges, row_base, any number of queries in passes of four, or -- from tuning
 // key slab_batch_min queries on -- in batched passes on the MFMA pipe (batch_slab.hip) whose unproved answers the host form runs
@@ -10,7 +11,7 @@
 #include <limits>
 #include <vector>
 
-#include "wide_rows.h"
+#include "half_rows.h"
 
 namespace smt {
 
@@ -24,6 +25,13 @@ int refuse_wide(uint32_t D, const char *what)
 {
     set_error("%s: not served for %u-dimensional rows yet (wide rows: top-k searches up to 56, ranges, workspace mode; everything else is 256 only)",
               what, D);
+    return SMT_E_UNSUPPORTED;
+}
+
+int refuse_half(const char *what)
+{
+    set_error("%s: not served for half rows (SMT_ROWS_F16) yet (half rows: append, write, read, truncate, embed into the corpus, top-k "
+              "searches up to 56, ranges, workspace mode; everything else needs f32 rows)", what);
     return SMT_E_UNSUPPORTED;
 }
 
@@ -50,8 +58,8 @@ int search_wide_host(smt_corpus *corpus, const float *queries, uint32_t nq, uint
     SMT_REQUIRE(nq == 0 || queries, "null argument");
     const uint32_t dim = corpus->dim;
     const bool has_thr = !std::isnan(max_distance);
-    if (mode == SMT_MODE_DOCUMENTS && has_thr) return refuse_wide(dim, "smt_search with max_distance in documents mode (the threshold kernel)");
-    if (top_k > SCAN_MAX_K) return refuse_wide(dim, "smt_search with top_k > 56 (the large-k route)");
+    if (mode == SMT_MODE_DOCUMENTS && has_thr) return refuse_rows(corpus, "smt_search with max_distance in documents mode (the threshold kernel)");
+    if (top_k > SCAN_MAX_K) return refuse_rows(corpus, "smt_search with top_k > 56 (the large-k route)");
     smt_ctx *ctx = corpus->ctx;
     int rc = bind_device(ctx);
     if (rc) return rc;
@@ -120,6 +128,7 @@ int search_wide_host(smt_corpus *corpus, const float *queries, uint32_t nq, uint
 
     SlabSearch a;
     a.corpus = corpus->d_rows;
+    a.row_dtype = corpus->row_dtype;
     a.rows = corpus->rows;
     a.dim = dim;
     a.queries = d_q;
@@ -191,7 +200,7 @@ int search_wide_host(smt_corpus *corpus, const float *queries, uint32_t nq, uint
     std::vector<double> all(n_slots);
     std::vector<uint64_t> order(n_virtual);
     for (uint32_t j : redo) {
-        rc = launch_exact_all_slab(ctx, corpus->d_rows, corpus->rows, dim, d_q + (size_t)j * dim, d_table, n_chunks, d_all);
+        rc = launch_exact_all_slab(ctx, corpus->d_rows, corpus->row_dtype, corpus->rows, dim, d_q + (size_t)j * dim, d_table, n_chunks, d_all);
         hipError_t e = rc ? hipSuccess : hipMemcpyAsync(all.data(), d_all, n_slots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
         if (!rc && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (rc || e != hipSuccess) {
@@ -220,12 +229,13 @@ int search_wide_device(smt_corpus *corpus, const float *queries_dev, uint32_t nq
 {
     SMT_REQUIRE(nq == 0 || (queries_dev && out_rows_dev && out_dist_dev), "null argument");
     SMT_REQUIRE(top_k >= 1, "top_k must be at least 1");
-    if (top_k > SCAN_MAX_K) return refuse_wide(corpus->dim, "smt_search_topk_device with top_k > 56 (the large-k route)");
+    if (top_k > SCAN_MAX_K) return refuse_rows(corpus, "smt_search_topk_device with top_k > 56 (the large-k route)");
     int rc = bind_device(corpus->ctx);
     if (rc) return rc;
     if (nq == 0) return SMT_OK;
     SlabSearch a;
     a.corpus = corpus->d_rows;
+    a.row_dtype = corpus->row_dtype;
     a.rows = corpus->rows;
     a.dim = corpus->dim;
     a.queries = queries_dev;

@@ -11,6 +11,10 @@ inline bool dim_supported(uint32_t D) { return D == SMT_DIM || dim_is_wide(D); }
 int refuse_dim(uint32_t D);
 // SMT_E_UNSUPPORTED for a call wide rows do not serve yet: `what` names it, the message names the width
 int refuse_wide(uint32_t D, const char *what);
+// ... and for one half rows do not serve yet (half_rows.h): the message names the half rows
+int refuse_half(const char *what);
+// whichever of the two fits a corpus that is wide or half
+inline int refuse_rows(const smt_corpus *c, const char *what) { return c->row_dtype == SMT_ROWS_F16 ? refuse_half(what) : refuse_wide(c->dim, what); }
 
 // |f32 scan distance - exact distance| of scan_slab_kernel<S, .>, by the counting rule at F32_ERR_SCAN (common.h): a lane runs
 // 4 S fused multiply-adds, the tree (wave_sum4 or wave_sum: six levels) is taken as eight steps as there, on terms whose absolute
@@ -36,7 +40,8 @@ int launch_embed_slab(smt_ctx *ctx, const void *table, int table_dtype, uint64_t
 // K2 + finish for the queries of one call, in passes of up to four (scan_slab.hip, finish_slab.hip).  All pointers device; enqueued
 // on the context's stream, nothing waits.  chunk_table / n_chunks: the range filter (range_tables.hip), nullptr / 0 without one.
 struct SlabSearch {
-    const float *corpus = nullptr;
+    const float *corpus = nullptr;     // (binary16 values behind it when row_dtype is SMT_ROWS_F16: half_rows.h)
+    int row_dtype = SMT_ROWS_F32;
     uint64_t rows = 0;                 // < 2^32 - 1
     uint32_t dim = 0;
     const float *queries = nullptr;    // [nq x dim]
@@ -52,6 +57,18 @@ struct SlabSearch {
     bool scan_only = false;            // never the batched route (the host form's re-run of what that route left unproved)
 };
 int launch_search_slab(smt_ctx *ctx, const SlabSearch &a);
+// what a K2 kernel of this family is launched with (scan_slab.hip, scan_half.hip)
+struct SlabScanParams {
+    const float *corpus;
+    uint64_t n_rows;
+    const float *queries;          // the pass' first query
+    uint32_t nq_active;            // 1 .. NQ
+    uint32_t kp;
+    const uint64_t *chunk_table;   // FILTERED
+    uint64_t n_chunks;
+    key_t64 *block_lists;          // [NQ][gridDim.x][kp]
+};
+using slab_scan_kernel_t = void (*)(SlabScanParams);
 // the finish stage alone (finish_slab.hip): lists [nq][n_lists][kp] of block lists -> answers, one block per query, certified under
 // f32_err (0: the scan's f32_err_slab)
 int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, uint32_t n_lists, uint32_t kp, uint32_t first_query,
@@ -60,7 +77,7 @@ int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, 
 // queries -- 64 at 512 dimensions, 32 at 768 and 1024 -- on the bf16 MFMA pipe, certified under f32_err_batch_slab.
 inline bool slab_batch_serves(const smt_ctx *ctx, const SlabSearch &a)
 {
-    return !a.scan_only && ctx->tune.slab_batch_min > 0 && a.nq >= (uint32_t)ctx->tune.slab_batch_min;
+    return !a.scan_only && a.row_dtype == SMT_ROWS_F32 && ctx->tune.slab_batch_min > 0 && a.nq >= (uint32_t)ctx->tune.slab_batch_min;
 }
 uint32_t slab_batch_qb(uint32_t dim);
 int launch_batch_slab(smt_ctx *ctx, const SlabSearch &a);
@@ -68,8 +85,8 @@ int debug_batch_slab_lists(smt_ctx *ctx, const SlabSearch &a, key_t64 *out_keys_
                            uint32_t *out_kp);
 // the exhaustive re-answer's kernel (finish_slab.hip): out[i] = exact f64 distance of row i (no table), or of row j of chunk c at
 // out[4 c + j] (slots past a chunk's rows are not written)
-int launch_exact_all_slab(smt_ctx *ctx, const float *corpus, uint64_t rows, uint32_t dim, const float *query, const uint64_t *chunk_table,
-                          uint64_t n_chunks, double *out);
+int launch_exact_all_slab(smt_ctx *ctx, const float *corpus, int row_dtype, uint64_t rows, uint32_t dim, const float *query,
+                          const uint64_t *chunk_table, uint64_t n_chunks, double *out);
 // domain.hip: rows of `dim` floats (the whole row: every slab), as check_rows_domain does for 256
 int check_rows_domain_dim(smt_ctx *ctx, const float *d_rows, uint64_t n_rows, uint32_t dim, uint64_t *n_bad, uint64_t *first_bad);
 int require_rows_domain_dim(smt_ctx *ctx, const float *d_rows, uint64_t n_rows, uint32_t dim, const char *what, uint64_t base = 0);
