@@ -480,11 +480,18 @@ int smt_lower_lines(smt_lower *h, const char *text, const uint64_t *line_begin, 
  * a scaled row can round into or out of the subnormal halves, which changes the stored direction.
  *   served   append_host, write_rows, read_rows (widened to f32, exact), truncate, destroy; smt_embed appending into it (the
  *            stored bits equal float16(pooled f32 row)); smt_search in SMT_MODE_DOCUMENTS without max_distance and in
- *            SMT_MODE_WORKSPACE with or without it, 0 <= top_k <= 56, ranges, row_base, any nq in passes of up to four queries,
+ *            SMT_MODE_WORKSPACE with or without it, 0 <= top_k <= 56, ranges, row_base, any nq in passes of up to four queries
+ *            or batched (below),
  *            the zero-query shortcut of workspace mode; smt_search_topk_device[_ex], 1 <= top_k <= 56, with verdicts; unproved
  *            lists of smt_search re-answered exhaustively and counted by smt_ctx_uncertain_count.
+ *            From tuning key half_batch_min queries on (default 4) a call runs the BATCHED route (batch_half.hip): passes of 128
+ *            queries share one read of the corpus, nominated on the f16 MFMA pipe (the stored row is the operand, the query is split
+ *            into f16 hi + lo).  The verdict of smt_search_topk_device[_ex] then rests on that route's WIDER bound (1.06e-5 against
+ *            the scan's 4.8e-6): near-ties inside it past the guard band come back SMT_STATUS_UNCERTAIN where the scan would have
+ *            proved them.  smt_search first runs such queries again through the scan and re-answers exhaustively only what that
+ *            leaves unproved.  Rows of subnormal halves take the route like any other (the MFMA keeps them: profiles/half_batch.json).
  *   half rows: not yet (SMT_E_UNSUPPORTED, the message names the half rows, nothing is enqueued or changed)
- *            SMT_MODE_DOCUMENTS with max_distance; top_k > 56; smt_corpus_prepack and the batched MFMA route;
+ *            SMT_MODE_DOCUMENTS with max_distance; top_k > 56; smt_corpus_prepack and the operand image;
  *            smt_corpus_compact; smt_corpus_save / smt_corpus_append_to_file (and smt_corpus_load: the file format holds f32 rows
  *            only, so it never yields a half corpus); smt_ivfpq_build / smt_ivfpq_load; the test hooks of the 256 kernels.  The
  *            sharded corpus constructors, the host layer and the CLI make their own f32 corpora and have no typed form.
@@ -1203,6 +1210,11 @@ int smt_debug_scan_ring(smt_ctx *ctx, uint32_t calls_back, uint64_t n_keys, uint
  *       out_cap_keys < (nq + 1) x blocks x k' (out_blocks and out_kp are set first). */
 int smt_debug_batch_slab_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
                                uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp);
+/*   smt_debug_batch_half_lists   the same for the batched route of HALF rows (csrc/batch_half.hip): the production query split and the
+ *       launches of batch_half_kernel, one per pass of 128 queries, over a half corpus (anything else: SMT_E_INVALID); arguments, layout,
+ *       guard set and errors as above.  tests/test_gpu_half_batch.py. */
+int smt_debug_batch_half_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                               uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp);
 
 /* The context's second stream (hipStream_t), created on first use: async selects run on it, or, with tuning key
  * scan_overlap, it waits for them (every select of an overlapped call enqueued before the work).  A host that
@@ -1257,6 +1269,11 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *   slab_batch_min (default 8; 0 = never)  WIDE rows: calls of at least this many queries run in passes of 64 (512 dimensions) or 32
  *                        (768, 1024) queries that share one read of the corpus, dot products on the bf16 MFMA pipe (batch_slab.hip);
  *                        fewer queries run the f32 scan in passes of four, exactly as before.  The answers are the same bytes
+ *   half_batch_min (default 4; 0 = never)  HALF rows: calls of at least this many queries run in passes of 128 queries that share one
+ *                        read of the corpus, dot products on the f16 MFMA pipe (batch_half.hip); fewer queries run the scan in
+ *                        passes of four, exactly as before.  The answers are the same bytes
+ *   half_batch_direct (0/1)  that kernel's row path: 0 (default) 128-byte runs through an LDS transpose, 1 operand layout straight
+ *                        from memory in 32-byte runs (A/B only)
  *   direct_delivery (1/0)  smt_search top-k calls with a small answer (<= 32 queries, <= 8 KiB of rows and distances) get it DELIVERED
  *                        by the select kernel: its last block writes the answer into pinned host memory and a completion word behind
  *                        it, which the host waits on -- no D2H copy command, no hipStreamSynchronize (~10 us of a small call); 0: A/B

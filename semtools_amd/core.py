@@ -792,19 +792,23 @@ class Corpus:
         b, k = int(blocks.value), int(kp.value)
         return out[:(nq + 1) * b * k].reshape(nq + 1, b, k).copy(), int(route.value)
 
-    def debug_batch_slab_lists(self, queries, top_k, ranges=None):
-        """Test hook (smt_debug_batch_slab_lists): the block lists one launch of the batched wide kernel writes for at most a pass of
-        queries under the current tuning.  Returns keys uint64 [nq + 1, blocks, k'], the last set the untouched guard."""
+    def debug_batch_slab_lists(self, queries, top_k, ranges=None, _hook="smt_debug_batch_slab_lists"):
+        """Test hook (smt_debug_batch_slab_lists): the block lists the batched wide kernel writes for up to 256 queries, a launch per
+        pass, under the current tuning.  Returns keys uint64 [nq + 1, blocks, k'], the last set the untouched guard."""
         q = _f32c(queries).reshape(-1, self.dim)
         nq = q.shape[0]
         rng, n_rng = _ranges_arg(ranges)
         cap = (nq + 1) * 256 * 64
         out = np.empty(cap, dtype=np.uint64)
         blocks, kp = C.c_uint32(0), C.c_uint32(0)
-        L.check(L.lib().smt_debug_batch_slab_lists(self._h, L.np_ptr(q), nq, int(top_k), C.cast(rng, C.c_void_p) if rng is not None else None,
-                                                   n_rng, L.np_ptr(out), cap, C.byref(blocks), C.byref(kp)))
+        L.check(getattr(L.lib(), _hook)(self._h, L.np_ptr(q), nq, int(top_k), C.cast(rng, C.c_void_p) if rng is not None else None,
+                                        n_rng, L.np_ptr(out), cap, C.byref(blocks), C.byref(kp)))
         b, k = int(blocks.value), int(kp.value)
         return out[:(nq + 1) * b * k].reshape(nq + 1, b, k).copy()
+
+    def debug_batch_half_lists(self, queries, top_k, ranges=None):
+        """Test hook (smt_debug_batch_half_lists): the same for the batched route of a half corpus (batch_half.hip)."""
+        return self.debug_batch_slab_lists(queries, top_k, ranges, _hook="smt_debug_batch_half_lists")
 
     def debug_select_lists(self, queries_ptr, nq, lists_ptr, n_lists, kp, k_out, out_rows_ptr, out_dist_ptr, list_stride=0, out_stride=0,
                            ws_threshold=None, row_base=0, f32_err=0.0, overflow_ptr=None, out_counts_ptr=None, out_uncertain_ptr=None,

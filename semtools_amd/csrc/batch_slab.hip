@@ -26,21 +26,16 @@
 // are four 32-byte LDS reads.  One f32x16 accumulator per 32-query tile, carried over the tile's 2 S units, mfma_bf16x3 per K-step.
 // Epilogue: d = max(1 - acc / |x|, 0) (the query operand is the UNIT query), 1 against a zero row or for a zero query, 0 for both.
 //
-// LISTS.  Form built: the per-(block, query) list of k' keys lives IN the block_lists area the finish reads (global memory, L2
+// LISTS (batch_list.h, shared with batch_half.hip).  Form built: the per-(block, query) list of k' keys lives IN the block_lists area the finish reads (global memory, L2
 // resident: 64 x k' x 8 bytes per block), ascending, preset to KEY_PAD; LDS holds only the QB thresholds (the k'-th key, KEY_PAD while
 // the list is short, 0 for a padding query) and QB lock words.  Why not LDS lists: 133,120 bytes of queries and 20,480 of transpose
 // buffers leave 10 KiB at S = 2 and 4, the lists need 16 to 32.  Serialisation: an LDS LOCK WORD per query, taken by the wave that found
 // a candidate (lane 0 spins on a compare-and-swap; a wave holds one lock at a time); under it the wave reads the list into its lanes,
 // inserts by ballot rank as scan_slab_kernel does, stores it back and publishes the new threshold.  A stale threshold only admits
 // more: every candidate is compared again under the lock.  An owner wave per query would need a queue in the LDS that is not there.
-#include "wide_rows.h"
-#include "device_utils.h"
-#include "mfma_tile.h"
-#include "gemm.h"
+#include "batch_list.h"
 
 namespace smt {
-
-constexpr int BS_THREADS = 512, BS_WAVES = BS_THREADS / 64;
 
 struct BatchSlabParams {
     const float *corpus;
@@ -89,39 +84,6 @@ __global__ void __launch_bounds__(256) batch_slab_split_kernel(const float *quer
     if (lane == 0) qzero[q] = zero ? 1u : 0u;
 }
 
-__device__ __forceinline__ key_t64 readlane_key(key_t64 v, int l)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-    return ((key_t64)hi << 32) | lo;
-}
-
-// The candidates `cand` (a lane mask; lane l: key ck) into the list of one (block, query) pair, under the query's lock (header: LISTS)
-__device__ __forceinline__ void batch_list_insert(key_t64 *list, int kp, unsigned long long cand, key_t64 ck, int lane, unsigned int *lock,
-                                                  key_t64 *thr)
-{
-    if (lane == 0)
-        while (atomicCAS(lock, 0u, 1u) != 0u) __builtin_amdgcn_s_sleep(1);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    key_t64 key = lane < kp ? __hip_atomic_load(list + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : KEY_PAD;
-    while (cand) {
-        const int l = __builtin_ctzll(cand);
-        cand &= cand - 1;
-        const key_t64 c = readlane_key(ck, l);
-        if (c < readlane_key(key, kp - 1)) {   // (wave-uniform)
-            const int pos = __popcll(__ballot(key < c));
-            const uint32_t slo = dpp_u<DPP_WAVE_SHR1>((uint32_t)key), shi = dpp_u<DPP_WAVE_SHR1>((uint32_t)(key >> 32));
-            if (lane > pos) key = ((key_t64)shi << 32) | slo;
-            else if (lane == pos) key = c;
-            if (lane >= kp) key = KEY_PAD;
-        }
-    }
-    if (lane < kp) __hip_atomic_store(list + lane, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    const key_t64 last = readlane_key(key, kp - 1);
-    if (lane == 0) __hip_atomic_store(thr, last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // (one 8-byte LDS write: never torn)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane == 0) __hip_atomic_store(lock, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
 template <int S, bool FILTERED>
 __global__ void __launch_bounds__(BS_THREADS, 2) batch_slab_kernel(BatchSlabParams p)
 {
@@ -150,18 +112,7 @@ __global__ void __launch_bounds__(BS_THREADS, 2) batch_slab_kernel(BatchSlabPara
         const int s = r / QB, qq = r - s * QB;
         s_q[r * QT_STRIDE_F4 + lane] = reinterpret_cast<const f32x4 *>(p.split + ((size_t)qq * S + s) * 256)[lane];
     }
-    if (threadIdx.x < QB) {
-        s_thr[threadIdx.x] = threadIdx.x < p.nq_active ? KEY_PAD : 0ull;   // padding queries: nothing is under 0
-        s_lock[threadIdx.x] = 0u;
-    }
-    if (wave < NT) {
-        const unsigned long long z = __ballot(lane < 32 && p.qzero[wave * 32 + (lane & 31)] != 0u);
-        if (lane == 0) s_qz[wave] = (unsigned int)z;
-    }
-    for (uint32_t i = threadIdx.x; i < p.nq_active * (uint32_t)kp; i += BS_THREADS) {
-        const uint32_t qq = i / (uint32_t)kp, sl = i - qq * (uint32_t)kp;
-        p.block_lists[((size_t)qq * gridDim.x + blockIdx.x) * kp + sl] = KEY_PAD;
-    }
+    batch_lists_init<QB>(s_thr, s_lock, s_qz, p.qzero, p.nq_active, kp, p.block_lists, lane, wave);
     __syncthreads();
 
     const uint64_t n_waves = (uint64_t)gridDim.x * BS_WAVES;
@@ -273,42 +224,7 @@ __global__ void __launch_bounds__(BS_THREADS, 2) batch_slab_kernel(BatchSlabPara
             validj = tile * 32 + j < p.n_rows;
             rowj = (uint32_t)(tile * 32 + j);
         }
-        const bool xz = rxj == 0.0f;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            if (t >= nt_active) break;   // (wave-uniform)
-            const unsigned int qzm = s_qz[t] >> (4 * h);   // bit acc_row(r, 0): query acc_row(r, h)
-            // which of the lane's 16 scores lie under their query's threshold (bit r <-> accumulator register r)
-            auto score = [&](float a, bool qz) __attribute__((always_inline)) { return qz ? (xz ? 0.0f : 1.0f) : fmaxf(1.0f - a * rxj, 0.0f); };
-            unsigned pass = 0;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                // queries 32 t + 8 u + 4 h + c, c = 0 .. 3: registers 4 u + c
-                const key_t64 *tq = s_thr + 32 * t + 8 * u + 4 * h;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const key_t64 k = make_key(score(acc[t][4 * u + c], (qzm >> (8 * u + c)) & 1u), rowj);
-                    if (k < __hip_atomic_load(tq + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) pass |= 1u << (4 * u + c);
-                }
-            }
-            if (!validj) pass = 0;
-            if (!__ballot(pass != 0)) continue;   // the common case: nothing under any threshold
-            // the rare case, one (register, half) pair at a time: bit 2 r + hh of todo <-> query acc_row(r, hh) has candidates
-            unsigned todo = 0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const unsigned long long m = __ballot((pass >> r) & 1u);
-                todo |= ((uint32_t)m ? 1u : 0u) << (2 * r) | ((uint32_t)(m >> 32) ? 2u : 0u) << (2 * r);
-            }
-            while (todo) {
-                const int rh = __builtin_ctz(todo), r = rh >> 1, hh = rh & 1;
-                todo &= todo - 1;
-                const int qq = 32 * t + acc_row(r, hh);
-                const bool mine = h == hh && ((pass >> r) & 1u);
-                const key_t64 ck = make_key(score(acc_select(acc[t], r), (qzm >> acc_row(r, 0)) & 1u), rowj);
-                batch_list_insert(p.block_lists + ((size_t)qq * gridDim.x + blockIdx.x) * kp, kp, __ballot(mine), ck, lane, s_lock + qq, s_thr + qq);
-            }
-        }
+        batch_tile_nominate<NT>(acc, nt_active, rxj, rxj == 0.0f, rowj, validj, s_qz, s_thr, s_lock, p.block_lists, kp, lane);
         tile = tile_next;
     }
 }
@@ -327,13 +243,6 @@ static batch_slab_kernel_t batch_slab_kernel_of(int S, bool filtered)
     if (S == 2) return filtered ? batch_slab_kernel<2, true> : batch_slab_kernel<2, false>;
     if (S == 3) return filtered ? batch_slab_kernel<3, true> : batch_slab_kernel<3, false>;
     return filtered ? batch_slab_kernel<4, true> : batch_slab_kernel<4, false>;
-}
-
-// the grid of a pass: at most SLAB_MAX_LISTS blocks, no block without a tile
-static int batch_slab_blocks(const smt_ctx *ctx, uint64_t n_tiles)
-{
-    const int cus = ctx->tune.scan_blocks > 0 ? ctx->tune.scan_blocks : std::max(ctx->num_cus, 1);
-    return (int)std::max<uint64_t>(1, std::min<uint64_t>(std::min(cus, SLAB_MAX_LISTS), (n_tiles + BS_WAVES - 1) / BS_WAVES));
 }
 
 // split image + one pass: the queries [q0, q0 + nq_pass) of `a` into lists [nq_pass][blocks][kp]
@@ -378,31 +287,6 @@ static int batch_slab_split(smt_ctx *ctx, const SlabSearch &a, uint32_t nq_pad, 
     return SMT_OK;
 }
 
-// scratch of a call: [split image nq_pad x 4 D bytes | zero flags nq_pad | lists], each 256-byte aligned
-struct BatchSlabScratch {
-    uint32_t *split, *qzero;
-    key_t64 *lists;
-};
-static int batch_slab_scratch(smt_ctx *ctx, uint32_t dim, uint32_t nq_pad, size_t list_keys, BatchSlabScratch &s)
-{
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t b_split = al((size_t)nq_pad * dim * 4), b_zero = al((size_t)nq_pad * 4);
-    int rc = ensure_scratch(ctx, b_split + b_zero + list_keys * sizeof(key_t64));
-    if (rc) return rc;
-    char *base = reinterpret_cast<char *>(ctx->d_scratch);
-    s.split = reinterpret_cast<uint32_t *>(base);
-    s.qzero = reinterpret_cast<uint32_t *>(base + b_split);
-    s.lists = reinterpret_cast<key_t64 *>(base + b_split + b_zero);
-    return SMT_OK;
-}
-
-static void batch_slab_shape(smt_ctx *ctx, const SlabSearch &a, uint32_t &kp, uint64_t &n_tiles, int &blocks)
-{
-    kp = std::min<uint32_t>(64, a.k_out + (uint32_t)ctx->tune.guard_band);
-    n_tiles = a.chunk_table ? (a.n_chunks + 7) / 8 : (a.rows + 31) / 32;
-    blocks = batch_slab_blocks(ctx, n_tiles);
-}
-
 // The passes of one call on the batched route: the query split once, then per pass of QB queries the kernel and its finish under
 // f32_err_batch_slab.  The last pass may be ragged: its padding queries nominate nothing and no list of theirs is read.
 int launch_batch_slab(smt_ctx *ctx, const SlabSearch &a)
@@ -412,10 +296,10 @@ int launch_batch_slab(smt_ctx *ctx, const SlabSearch &a)
     uint32_t kp;
     uint64_t n_tiles;
     int blocks;
-    batch_slab_shape(ctx, a, kp, n_tiles, blocks);
+    batch_shape(ctx, a, kp, n_tiles, blocks);
     const uint32_t nq_pad = (a.nq + QB - 1) / QB * QB;
-    BatchSlabScratch s;
-    int rc = batch_slab_scratch(ctx, a.dim, nq_pad, (size_t)QB * blocks * kp, s);
+    BatchScratch s;
+    int rc = batch_scratch(ctx, a.dim, nq_pad, (size_t)QB * blocks * kp, s);
     if (rc) return rc;
     if ((rc = batch_slab_split(ctx, a, nq_pad, s.split, s.qzero))) return rc;
     const double err = S == 2 ? f32_err_batch_slab(2) : S == 3 ? f32_err_batch_slab(3) : f32_err_batch_slab(4);
@@ -427,35 +311,16 @@ int launch_batch_slab(smt_ctx *ctx, const SlabSearch &a)
     return SMT_OK;
 }
 
-// Test hook (smt_debug_batch_slab_lists): the production split and the passes of a.nq queries, no finish; the list area
-// [nq + 1][blocks][k'] is preset to 0x5A, every pass writes its queries' sets, the last set is the guard nothing may touch.
+// Test hook (smt_debug_batch_slab_lists): the production split and the passes of a.nq queries, no finish (batch_list.h)
 int debug_batch_slab_lists(smt_ctx *ctx, const SlabSearch &a, key_t64 *out_keys_host, uint64_t out_cap_keys, uint32_t *out_blocks,
                            uint32_t *out_kp)
 {
-    const uint32_t QB = slab_batch_qb(a.dim);
-    SMT_REQUIRE(a.nq >= 1 && a.nq <= 256, "debug batch lists: 1 .. 256 queries");
-    uint32_t kp;
-    uint64_t n_tiles;
-    int blocks;
-    batch_slab_shape(ctx, a, kp, n_tiles, blocks);
-    SMT_REQUIRE(n_tiles >= 1, "debug batch lists: no row to scan");
-    *out_blocks = (uint32_t)blocks;
-    *out_kp = kp;
-    const size_t n_keys = (size_t)(a.nq + 1) * blocks * kp;
-    SMT_REQUIRE(out_cap_keys >= n_keys, "debug batch lists: output capacity");
-    BatchSlabScratch s;
-    const uint32_t nq_pad = (a.nq + QB - 1) / QB * QB;
-    int rc = batch_slab_scratch(ctx, a.dim, nq_pad, n_keys, s);
-    if (rc) return rc;
-    SMT_HIP_CHECK(hipMemsetAsync(s.lists, 0x5A, n_keys * sizeof(key_t64), ctx->stream));
-    if ((rc = batch_slab_split(ctx, a, nq_pad, s.split, s.qzero))) return rc;
-    for (uint32_t q0 = 0; q0 < a.nq; q0 += QB)
-        if ((rc = batch_slab_pass(ctx, a, s.split, s.qzero, q0, std::min<uint32_t>(QB, a.nq - q0), kp, n_tiles, blocks,
-                                  s.lists + (size_t)q0 * blocks * kp)))
-            return rc;
-    SMT_HIP_CHECK(hipMemcpyAsync(out_keys_host, s.lists, n_keys * sizeof(key_t64), hipMemcpyDeviceToHost, ctx->stream));
-    SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return SMT_OK;
+    return debug_batch_lists(
+        ctx, a, slab_batch_qb(a.dim), [&](uint32_t nq_pad, const BatchScratch &s) { return batch_slab_split(ctx, a, nq_pad, s.split, s.qzero); },
+        [&](const BatchScratch &s, uint32_t q0, uint32_t nq_pass, uint32_t kp, uint64_t n_tiles, int blocks, key_t64 *lists) {
+            return batch_slab_pass(ctx, a, s.split, s.qzero, q0, nq_pass, kp, n_tiles, blocks, lists);
+        },
+        out_keys_host, out_cap_keys, out_blocks, out_kp);
 }
 
 }  // namespace smt

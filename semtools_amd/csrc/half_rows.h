@@ -1,5 +1,5 @@
 // half_rows.h -- corpora whose rows are stored as 256 IEEE binary16 values (SMT_ROWS_F16, 512 B a row): what rows_half.hip,
-// scan_half.hip and the element-typed parts of finish_slab.hip, scan_slab.hip's launch and search_slab.cpp share.  The answers are
+// scan_half.hip, batch_half.hip and the element-typed parts of finish_slab.hip, scan_slab.hip's launch and search_slab.cpp share.  The answers are
 // defined over the STORED values: a half widens to f32 exactly, and the exact distance is the f64 distance of the widened row.
 #pragma once
 #include "wide_rows.h"
@@ -56,6 +56,27 @@ int rows_to_half(smt_ctx *ctx, const float *src_dev, uint64_t n_rows, void *dst_
 int require_half_rows_domain(smt_ctx *ctx, const void *rows_dev, uint64_t n_rows, const char *what);
 // n_rows half rows widened into dst_dev (f32); enqueued on the context's stream
 int launch_half_to_f32(smt_ctx *ctx, const void *src_dev, uint64_t n_rows, float *dst_dev);
+
+// |nominated distance - exact distance| of batch_half_kernel (batch_half.hip), by the rules at F32_ERR_BF16X3 (common.h, mfma_tile.h)
+// and f32_err_batch_slab (wide_rows.h): the query's hi + lo carry 22 bits -- representation 2^-22 |x||u|; the ROWS contribute nothing,
+// a stored half is the operand; 32 MFMA instructions at 2 ulp = 2^-23 each of an accumulator whose magnitude, scaled back, is <= 1:
+// 32 x 2^-22 (the 7.6e-6 of the f16 x 2 note); the two f32 scalings 1e-6; the whole times the project's 1.2:
+// 1.2 x (33 x 2^-22 + 1e-6) = 1.06e-5, an eighth of f32_err_batch_slab(2).  DERIVED, not measured; profiles/half_batch.json records
+// the largest |d32 - d64| tests/test_gpu_half_batch.py saw on random, worst-case and subnormal rows.
+constexpr double f32_err_batch_half = 1.2 * (33.0 / 4194304.0 + 1e-6);
+
+// The batched route (batch_half.hip): calls of at least tuning key half_batch_min queries (0: never) run passes of half_batch_qb
+// queries on the f16 MFMA pipe, certified under f32_err_batch_half.
+inline bool half_batch_serves(const smt_ctx *ctx, const SlabSearch &a)
+{
+    return !a.scan_only && a.row_dtype == SMT_ROWS_F16 && ctx->tune.half_batch_min > 0 && a.nq >= (uint32_t)ctx->tune.half_batch_min;
+}
+// either batched route: what it leaves unproved, search_wide_host runs again through the scan
+inline bool batch_route_serves(const smt_ctx *ctx, const SlabSearch &a) { return slab_batch_serves(ctx, a) || half_batch_serves(ctx, a); }
+uint32_t half_batch_qb();
+int launch_batch_half(smt_ctx *ctx, const SlabSearch &a);
+int debug_batch_half_lists(smt_ctx *ctx, const SlabSearch &a, key_t64 *out_keys_host, uint64_t out_cap_keys, uint32_t *out_blocks,
+                           uint32_t *out_kp);
 
 // scan_half.hip: scan_half_kernel<slots, filtered>, launched by launch_search_slab (scan_slab.hip) like the wide kernels
 slab_scan_kernel_t half_scan_kernel_of(int slots, bool filtered);

@@ -114,6 +114,14 @@ __device__ __forceinline__ f32x16 mfma_f16x2(const u32x4 &a, const u32x4 &bh, co
     return acc;
 }
 
+// acc += (ah + al) . b: the same two products with the split operand FIRST (batch_half.hip: accumulator columns are the rows of b)
+__device__ __forceinline__ f32x16 mfma_f16x2_first(const u32x4 &ah, const u32x4 &al, const u32x4 &b, f32x16 acc)
+{
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, al), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
+    return acc;
+}
+
 // accumulator register r of lane (j, h) holds tile row acc_row(r, h) and tile column j
 __device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 

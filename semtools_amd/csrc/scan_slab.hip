@@ -211,7 +211,10 @@ int launch_search_slab(smt_ctx *ctx, const SlabSearch &a)
     SMT_REQUIRE(a.k_out >= 1 && a.k_out <= SCAN_MAX_K, "wide scan: 1 <= top_k <= 56");
     SMT_REQUIRE(a.rows < 0xFFFFFFFFull, "wide scan: fewer than 2^32 - 1 rows per corpus");
     SMT_REQUIRE(a.nq >= 1 && a.queries && a.out_rows && a.out_dist, "wide scan: null argument");
-    if (slab_batch_serves(ctx, a) && (a.chunk_table ? a.n_chunks : a.rows) > 0) return launch_batch_slab(ctx, a);   // batch_slab.hip
+    if ((a.chunk_table ? a.n_chunks : a.rows) > 0) {
+        if (slab_batch_serves(ctx, a)) return launch_batch_slab(ctx, a);   // batch_slab.hip
+        if (half_batch_serves(ctx, a)) return launch_batch_half(ctx, a);   // batch_half.hip
+    }
     const int S = (int)(a.dim / 256);
     const int U = half ? HALF_STEP_ROWS : S == 2 ? 2 : 1;
     const bool filtered = a.chunk_table != nullptr;

@@ -1,9 +1,10 @@
 // search_slab.cpp -- the search entry points over a WIDE corpus (rows of 512, 768 or 1024 floats) or a HALF corpus (rows of 256
-// binary16 values, half_rows.h: the same calls with the row type handed on, never the batched route): what smt_search and
+// binary16 values, half_rows.h: the same calls with the row type handed on): what smt_search and
 // smt_search_topk_device[_ex] do before they would reach a 256 kernel.  Served: top-k (1 .. 56) in documents mode without a
 // distance bound, workspace mode with or without one, ranges, row_base, any number of queries in passes of four, or -- from tuning
-// key slab_batch_min queries on -- in batched passes on the MFMA pipe (batch_slab.hip) whose unproved answers the host form runs
-// again through the scan.  Also the test hook of that route (smt_debug_batch_slab_lists).  Everything is
+// key slab_batch_min (half rows: half_batch_min) queries on -- in batched passes on the MFMA pipe (batch_slab.hip, batch_half.hip)
+// whose unproved answers the host form runs again through the scan.  Also the test hooks of those routes
+// (smt_debug_batch_slab_lists, smt_debug_batch_half_lists).  Everything is
 // enqueued on the context's stream directly: no one-query pipeline, no grouping, no operand image.  Also the two refusals every
 // other entry point answers a wide corpus or model with.
 #include <algorithm>
@@ -161,7 +162,7 @@ int search_wide_host(smt_corpus *corpus, const float *queries, uint32_t nq, uint
 
     // What the batched route left unproved is first run again, together, through the scan route and its tighter f32_err_slab: the
     // queries move to the front of the stage (ascending, so none is overwritten before it has moved), `redo` then indexes them there.
-    if (slab_batch_serves(ctx, a)) {
+    if (batch_route_serves(ctx, a)) {
         const uint32_t nr = (uint32_t)redo.size();
         for (uint32_t i = 0; i < nr; ++i)
             if (redo[i] != i)
@@ -252,16 +253,14 @@ int search_wide_device(smt_corpus *corpus, const float *queries_dev, uint32_t nq
 
 using namespace smt;
 
-extern "C" {
-
-// Test hook: the block lists of the batched wide route.  The production query split and ONE launch of batch_slab_kernel for nq host
-// queries (at most a pass) over a wide corpus, optional ranges through the chunk table, the grid the current tuning gives
-// (debug_batch_slab_lists, batch_slab.hip).
-int smt_debug_batch_slab_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
-                               uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp)
-try {
+// What the two list hooks share: nq host queries and the optional ranges (through the chunk table) onto the stage, then the route's
+// debug_batch_*_lists (batch_slab.hip, batch_half.hip) under the grid the current tuning gives.
+static int debug_batch_lists_staged(smt_corpus *corpus, bool half, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges,
+                                    uint32_t n_ranges, uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp)
+{
     SMT_REQUIRE(corpus && queries && out_keys && out_blocks && out_kp, "null argument");
-    SMT_REQUIRE(dim_is_wide(corpus->dim), "debug batch lists: a wide corpus (512, 768 or 1024 dimensions)");
+    if (half) SMT_REQUIRE(rows_are_half(corpus), "debug batch lists: a half corpus (SMT_ROWS_F16)");
+    else SMT_REQUIRE(dim_is_wide(corpus->dim), "debug batch lists: a wide corpus (512, 768 or 1024 dimensions)");
     SMT_REQUIRE(top_k >= 1 && top_k <= SCAN_MAX_K, "debug batch lists: top_k in [1, 56]");
     SMT_REQUIRE(nq >= 1 && nq <= 256, "debug batch lists: 1 .. 256 queries");
     smt_ctx *ctx = corpus->ctx;
@@ -305,9 +304,26 @@ try {
     a.k_out = top_k;
     a.chunk_table = d_table;
     a.n_chunks = n_chunks;
-    rc = debug_batch_slab_lists(ctx, a, reinterpret_cast<key_t64 *>(out_keys), out_cap_keys, out_blocks, out_kp);
+    a.row_dtype = corpus->row_dtype;
+    rc = (half ? debug_batch_half_lists : debug_batch_slab_lists)(ctx, a, reinterpret_cast<key_t64 *>(out_keys), out_cap_keys, out_blocks, out_kp);
     if (rc) (void)hipStreamSynchronize(ctx->stream);   // (the uploads read this frame's vectors)
     return rc;
+}
+
+extern "C" {
+
+// Test hook: the block lists of the batched wide route (batch_slab_kernel, one launch per pass of the nq host queries)
+int smt_debug_batch_slab_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                               uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp)
+try {
+    return debug_batch_lists_staged(corpus, false, queries, nq, top_k, ranges, n_ranges, out_keys, out_cap_keys, out_blocks, out_kp);
+} catch (...) { return smt::api_catch(); }
+
+// ... and of the batched half route (batch_half_kernel)
+int smt_debug_batch_half_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                               uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp)
+try {
+    return debug_batch_lists_staged(corpus, true, queries, nq, top_k, ranges, n_ranges, out_keys, out_cap_keys, out_blocks, out_kp);
 } catch (...) { return smt::api_catch(); }
 
 }  // extern "C"
