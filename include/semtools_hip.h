@@ -495,15 +495,43 @@ int smt_lower_lines(smt_lower *h, const char *text, const uint64_t *line_begin, 
  *            smt_corpus_compact; smt_corpus_save / smt_corpus_append_to_file (and smt_corpus_load: the file format holds f32 rows
  *            only, so it never yields a half corpus); smt_ivfpq_build / smt_ivfpq_load; the test hooks of the 256 kernels.  The
  *            sharded corpus constructors, the host layer and the CLI make their own f32 corpora and have no typed form.
+ *
+ * BYTE ROWS.  A corpus made with SMT_ROWS_I8 stores each row as 256 signed bytes: 256 B, a quarter of the f32 bytes of every scan
+ * and four times the lines per GPU.  D = 256 only: SMT_ROWS_I8 with a wide D is SMT_E_UNSUPPORTED.  Cosine distance does not
+ * depend on a row's length, so the stored row is an int8 DIRECTION and nothing else: there is no scale to keep.  As for half rows,
+ * everything the library promises about answers holds over the STORED values: the exact distance of a row is the f64 distance
+ * (sequential sums, simsimd's accurate form) of the row's integers widened to f32 -- which is exact -- and the query as given in
+ * f32; (distance, row) order, bit-identical distances, verdicts from smt_search_topk_device_ex, never an unproved list from
+ * smt_search.  Units of their own: rows_byte.hip, scan_byte.hip; finish stage and host entry are the wide rows' with the element type.
+ * Rows that enter as f32 (append_host, write_rows, smt_embed with a corpus to append to) are quantised ONCE, on the device, bit
+ * for bit this NumPy expression with every array float32:
+ *     amax = np.abs(X).max(1, keepdims=True);  s = np.where(amax > 0, np.float32(127) / amax, np.float32(0))
+ *     q = np.rint(X * s).astype(np.int8)
+ * (one correctly rounded division, one multiply, nearest with ties to even; the largest component stores +-127, -128 is never
+ * produced, a zero row is stored as zeros).  A row outside the f32 domain below ("Domain") is SMT_E_INVALID, the corpus untouched;
+ * there is no further condition.  Scaling a row by a power of two changes NO stored byte -- amax, hence s, scales by the exact
+ * inverse and every product is the same number -- so the f32 domain's "scaling by a power of two changes no answer" holds here,
+ * unlike half rows.  smt_corpus_from_device_typed adopts [n_rows x 256] int8, 16-byte aligned; every byte is a valid value, -128
+ * included, so there is no pass over the rows and the call does not wait.
+ * smt_corpus_read_rows returns the stored integers as f32 (widened on the device, exact): the stored DIRECTION, not the row given.
+ *   served   what half rows serve, but no batched route: append_host, write_rows, read_rows, truncate, destroy; smt_embed
+ *            appending into it; smt_search in SMT_MODE_DOCUMENTS without max_distance and in SMT_MODE_WORKSPACE with or without
+ *            it, 0 <= top_k <= 56, ranges, row_base, any nq in passes of up to four queries, the zero-query shortcut;
+ *            smt_search_topk_device[_ex], 1 <= top_k <= 56, with verdicts under the scan's bound 6.7e-6; unproved lists of
+ *            smt_search re-answered exhaustively and counted by smt_ctx_uncertain_count.
+ *   byte rows: not yet (SMT_E_UNSUPPORTED, the message names the byte rows, nothing is enqueued or changed)
+ *            everything half rows refuse, and the test hooks of the batched routes (smt_debug_batch_*_lists).
  * These calls skip the one-query pipeline, its grouping and direct delivery: everything is enqueued on the context's stream. */
 #define SMT_ROWS_F32 0
 #define SMT_ROWS_F16 1
+#define SMT_ROWS_I8 2
 int smt_corpus_create(smt_ctx *ctx, uint32_t D, uint64_t capacity_rows, smt_corpus **out);
 /* adopt rows already in device memory (not copied, not freed, not growable) */
 int smt_corpus_from_device(smt_ctx *ctx, const float *rows_dev, uint64_t n_rows, uint32_t D,
                            smt_corpus **out);
 /* The same two with the element type of the stored rows (SMT_ROWS_*); the untyped forms are the SMT_ROWS_F32 case.  Adopted half
- * rows: [n_rows x 256] binary16, 16-byte aligned, every value finite (an Inf or NaN is SMT_E_INVALID as a row outside the domain). */
+ * rows: [n_rows x 256] binary16, 16-byte aligned, every value finite (an Inf or NaN is SMT_E_INVALID as a row outside the domain).
+ * Adopted byte rows: [n_rows x 256] int8, 16-byte aligned, any value. */
 int smt_corpus_create_typed(smt_ctx *ctx, uint32_t D, int row_dtype, uint64_t capacity_rows, smt_corpus **out);
 int smt_corpus_from_device_typed(smt_ctx *ctx, const void *rows_dev, int row_dtype, uint64_t n_rows, uint32_t D, smt_corpus **out);
 /* what a corpus stores: SMT_ROWS_*, D, bytes per stored row; any pointer may be NULL */

@@ -634,7 +634,9 @@ class Lower:
 class Corpus:
     """Row-major [rows x dim] matrix resident in HBM (smt_corpus); dim = 256, or a wide 512, 768, 1024.  dtype: how the rows are
     STORED -- np.float32, or np.float16 at dim 256 (half rows: rows go in and come out as f32, rounded to nearest-even once on the
-    device; a device_ptr then points at binary16 values).  A number outside L.ROWS_NP is handed on for the library to refuse."""
+    device; a device_ptr then points at binary16 values), or np.int8 at dim 256 (byte rows: a row is stored as its int8 direction,
+    rint(x * (127 / max|x|)), and read_rows returns those integers as f32; a device_ptr then points at int8 values).  A number
+    outside L.ROWS_NP is handed on for the library to refuse."""
 
     def __init__(self, ctx, capacity_rows=0, device_ptr=None, rows=None, _handle=None, _borrowed=False, dim=L.DIM, dtype=np.float32):
         self.ctx = ctx

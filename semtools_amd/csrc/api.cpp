@@ -11,7 +11,7 @@
 #include <unistd.h>
 
 #include "common.h"
-#include "half_rows.h"
+#include "byte_rows.h"
 
 namespace smt {
 
@@ -903,13 +903,27 @@ void smt_model_destroy(smt_model *model)
 
 /* --------------------------------------------------------------- corpus ---- */
 
-// the row type of a typed creator: an unknown one is SMT_E_INVALID, half rows exist at 256 dimensions only
+// the row type of a typed creator: an unknown one is SMT_E_INVALID, half and byte rows exist at 256 dimensions only
 static int check_row_dtype(int row_dtype, uint32_t D)
 {
-    if (row_dtype != SMT_ROWS_F32 && row_dtype != SMT_ROWS_F16) { set_error("unknown row dtype %d (SMT_ROWS_F32, SMT_ROWS_F16)", row_dtype); return SMT_E_INVALID; }
+    if (row_dtype != SMT_ROWS_F32 && row_dtype != SMT_ROWS_F16 && row_dtype != SMT_ROWS_I8) {
+        set_error("unknown row dtype %d (SMT_ROWS_F32, SMT_ROWS_F16, SMT_ROWS_I8)", row_dtype);
+        return SMT_E_INVALID;
+    }
     if (!dim_supported(D)) return refuse_dim(D);
     if (row_dtype == SMT_ROWS_F16 && D != SMT_DIM) return refuse_half("a corpus of half rows wider than 256 dimensions");
+    if (row_dtype == SMT_ROWS_I8 && D != SMT_DIM) return refuse_byte("a corpus of byte rows wider than 256 dimensions");
     return SMT_OK;
+}
+
+// f32 rows on the device into what a half or byte corpus stores, checked on the way (rows_half.hip, rows_byte.hip), and back
+static int rows_to_stored(const smt_corpus *c, const float *src_dev, uint64_t n_rows, void *dst_dev, const char *what)
+{
+    return rows_are_byte(c) ? rows_to_byte(c->ctx, src_dev, n_rows, dst_dev, what) : rows_to_half(c->ctx, src_dev, n_rows, dst_dev, what);
+}
+static int stored_to_f32(const smt_corpus *c, const void *src_dev, uint64_t n_rows, float *dst_dev)
+{
+    return rows_are_byte(c) ? launch_byte_to_f32(c->ctx, src_dev, n_rows, dst_dev) : launch_half_to_f32(c->ctx, src_dev, n_rows, dst_dev);
 }
 
 int smt_corpus_create_typed(smt_ctx *ctx, uint32_t D, int row_dtype, uint64_t capacity_rows, smt_corpus **out)
@@ -943,16 +957,20 @@ try {
     SMT_REQUIRE(out && (rows_dev || n_rows == 0), "null argument");
     *out = nullptr;
     if ((rc = check_row_dtype(row_dtype, D))) return rc;
-    const bool half = row_dtype == SMT_ROWS_F16;
-    // the half scan reads a row with 16-byte lane loads
-    if (half && reinterpret_cast<uintptr_t>(rows_dev) % 16 != 0) { set_error("half rows in device memory must be 16-byte aligned"); return SMT_E_INVALID; }
+    const bool half = row_dtype == SMT_ROWS_F16, byte = row_dtype == SMT_ROWS_I8;
+    // the half and byte scans read a row with 16-byte lane loads
+    if ((half || byte) && reinterpret_cast<uintptr_t>(rows_dev) % 16 != 0) {
+        set_error("%s rows in device memory must be 16-byte aligned", half ? "half" : "byte");
+        return SMT_E_INVALID;
+    }
     smt_corpus *c = new (std::nothrow) smt_corpus();
     if (!c) { set_error("out of host memory"); return SMT_E_NOMEM; }
     c->ctx = ctx; c->dim = D; c->row_dtype = row_dtype; c->owned = false;
     c->d_rows = static_cast<float *>(const_cast<void *>(rows_dev));
     c->rows = n_rows; c->capacity = n_rows;
-    // the rows as they are NOW must be in the library's domain (domain.hip); the caller answers for what it writes there later
-    if (n_rows) {
+    // the rows as they are NOW must be in the library's domain (domain.hip); the caller answers for what it writes there later.
+    // Byte rows have no value outside it: no pass over them, nothing waits.
+    if (n_rows && !byte) {
         int rc2 = bind_device(ctx);
         if (!rc2) rc2 = half ? require_half_rows_domain(ctx, rows_dev, n_rows, "smt_corpus_from_device_typed")
                              : require_rows_domain_dim(ctx, c->d_rows, n_rows, D, "smt_corpus_from_device");
@@ -1001,14 +1019,14 @@ try {
     if (first_row) *first_row = c->rows;
     if (n_rows == 0) return SMT_OK;
     if ((rc = corpus_reserve(c, c->rows + n_rows))) return rc;
-    if (rows_are_half(c)) {
-        // uploaded as f32 beside the corpus, rounded and checked on their way behind the last counted row (rows_half.hip)
+    if (rows_are_typed(c)) {
+        // uploaded as f32 beside the corpus, rounded and checked on their way behind the last counted row (rows_half.hip, rows_byte.hip)
         DeviceTemp tmp;
         const size_t bytes = (size_t)n_rows * c->dim * sizeof(float);
         if (hipMalloc(&tmp.p, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc(%zu) for the rows to round", bytes); return SMT_E_NOMEM; }
         SMT_HIP_CHECK(hipMemcpyAsync(tmp.p, rows, bytes, hipMemcpyHostToDevice, c->ctx->stream));
-        if ((rc = rows_to_half(c->ctx, static_cast<const float *>(tmp.p), n_rows, reinterpret_cast<char *>(c->d_rows) + (size_t)c->rows * c->row_bytes(),
-                               "smt_corpus_append_host")))
+        if ((rc = rows_to_stored(c, static_cast<const float *>(tmp.p), n_rows, reinterpret_cast<char *>(c->d_rows) + (size_t)c->rows * c->row_bytes(),
+                                 "smt_corpus_append_host")))
             return rc;
         c->rows += n_rows;
         return SMT_OK;
@@ -1036,14 +1054,14 @@ try {
             return SMT_E_INVALID;
         }
     }
-    if (rows_are_half(c)) {
+    if (rows_are_typed(c)) {
         // rounded and checked beside the corpus first: a refused batch overwrites nothing
         DeviceTemp tmp;
         const size_t f_bytes = (size_t)n_rows * c->dim * sizeof(float), h_bytes = (size_t)n_rows * c->row_bytes();
         if (hipMalloc(&tmp.p, f_bytes + h_bytes) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc(%zu) for the rows to round", f_bytes + h_bytes); return SMT_E_NOMEM; }
         char *d_half = static_cast<char *>(tmp.p) + f_bytes;
         SMT_HIP_CHECK(hipMemcpyAsync(tmp.p, rows, f_bytes, hipMemcpyHostToDevice, c->ctx->stream));
-        if ((rc = rows_to_half(c->ctx, static_cast<const float *>(tmp.p), n_rows, d_half, "smt_corpus_write_rows"))) return rc;
+        if ((rc = rows_to_stored(c, static_cast<const float *>(tmp.p), n_rows, d_half, "smt_corpus_write_rows"))) return rc;
         SMT_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char *>(c->d_rows) + (size_t)first_row * c->row_bytes(), d_half, h_bytes, hipMemcpyDeviceToDevice,
                                      c->ctx->stream));
         SMT_HIP_CHECK(hipStreamSynchronize(c->ctx->stream));
@@ -1060,7 +1078,7 @@ try {
 int smt_corpus_prepack(smt_corpus *c, int enable)
 try {
     SMT_REQUIRE(c != nullptr, "corpus");
-    if (dim_is_wide(c->dim) || rows_are_half(c)) return refuse_rows(c, "smt_corpus_prepack (the fp16 operand image)");
+    if (dim_is_wide(c->dim) || rows_are_typed(c)) return refuse_rows(c, "smt_corpus_prepack (the fp16 operand image)");
     int rc = bind_device(c->ctx);
     if (rc) return rc;
     if (!enable) {
@@ -1083,7 +1101,7 @@ uint64_t smt_corpus_image_bytes(const smt_corpus *c) { return c && c->image ? c-
 int smt_debug_image_tile(smt_corpus *c, uint64_t tile, void *out_tile_host, uint32_t *out_zero_mask)
 try {
     SMT_REQUIRE(c != nullptr && out_tile_host != nullptr && out_zero_mask != nullptr, "null argument");
-    if (rows_are_half(c)) return refuse_half("smt_debug_image_tile (the fp16 operand image)");
+    if (rows_are_typed(c)) return refuse_rows(c, "smt_debug_image_tile (the fp16 operand image)");
     int rc = bind_device(c->ctx);
     if (rc) return rc;
     const void *img = nullptr;
@@ -1104,11 +1122,11 @@ try {
     int rc = bind_device(c->ctx);
     if (rc) return rc;
     if (n_rows == 0) return SMT_OK;
-    if (rows_are_half(c)) {   // widened on the device (exact), then copied
+    if (rows_are_typed(c)) {   // widened on the device (exact), then copied
         DeviceTemp tmp;
         const size_t bytes = (size_t)n_rows * c->dim * sizeof(float);
         if (hipMalloc(&tmp.p, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc(%zu) for the widened rows", bytes); return SMT_E_NOMEM; }
-        if ((rc = launch_half_to_f32(c->ctx, reinterpret_cast<const char *>(c->d_rows) + (size_t)first_row * c->row_bytes(), n_rows, static_cast<float *>(tmp.p))))
+        if ((rc = stored_to_f32(c, reinterpret_cast<const char *>(c->d_rows) + (size_t)first_row * c->row_bytes(), n_rows, static_cast<float *>(tmp.p))))
             return rc;
         SMT_HIP_CHECK(hipMemcpyAsync(out_host, tmp.p, bytes, hipMemcpyDeviceToHost, c->ctx->stream));
         SMT_HIP_CHECK(hipStreamSynchronize(c->ctx->stream));
@@ -1132,7 +1150,7 @@ try {
 
 int smt_corpus_compact(smt_corpus *c, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved)
 try {
-    if (c && (dim_is_wide(c->dim) || rows_are_half(c))) return refuse_rows(c, "smt_corpus_compact");
+    if (c && (dim_is_wide(c->dim) || rows_are_typed(c))) return refuse_rows(c, "smt_corpus_compact");
     return corpus_compact(c, keep, n_keep, rows_moved);
 } catch (...) { return smt::api_catch(); }
 
@@ -1184,7 +1202,7 @@ try {
     // staging: ids + rebased offsets (+ output rows when not appending)
     const size_t ids_bytes = ((size_t)n_ids * sizeof(uint32_t) + 15) & ~(size_t)15;
     const size_t off_bytes = ((size_t)(n_lines + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
-    const bool to_half = append_to && rows_are_half(append_to);   // K1 pools f32 rows into the staging, rows_half.hip stores the halves
+    const bool to_half = append_to && rows_are_typed(append_to);   // K1 pools f32 rows into the staging, rows_half.hip / rows_byte.hip store them
     const size_t out_bytes = append_to && !to_half ? 0 : (size_t)n_lines * model->D * sizeof(float);
     DeviceTemp tmp;
     {
@@ -1215,8 +1233,8 @@ try {
         SMT_HIP_CHECK(hipMemcpyAsync(out_host, d_out, (size_t)n_lines * model->D * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (to_half) {
-        if ((rc = rows_to_half(ctx, d_out, n_lines, reinterpret_cast<char *>(append_to->d_rows) + (size_t)append_to->rows * append_to->row_bytes(),
-                               "smt_embed (rows pooled from the table)")))
+        if ((rc = rows_to_stored(append_to, d_out, n_lines, reinterpret_cast<char *>(append_to->d_rows) + (size_t)append_to->rows * append_to->row_bytes(),
+                                 "smt_embed (rows pooled from the table)")))
             return rc;
         append_to->rows += n_lines;
     } else if (append_to) {

@@ -480,7 +480,7 @@ extern "C" {
 int smt_corpus_save(smt_corpus *c, const char *path)
 try {
     SMT_REQUIRE(c != nullptr && path != nullptr, "null argument");
-    if (c->row_dtype == SMT_ROWS_F16) return smt::refuse_half("smt_corpus_save (the file format holds f32 rows)");
+    if (c->row_dtype != SMT_ROWS_F32) return smt::refuse_rows(c, "smt_corpus_save (the file format holds f32 rows)");
     // never rewrite the live file in place: a crash or ENOSPC half way would leave a truncated corpus that
     // every later workspace command rejects.  Write a sibling, fsync, rename.
     const std::string tmp = std::string(path) + ".tmp";
@@ -497,7 +497,7 @@ try {
 
 int smt_corpus_append_to_file(smt_corpus *c, const char *path, uint64_t rows_on_disk)
 try {
-    if (c && c->row_dtype == SMT_ROWS_F16) return smt::refuse_half("smt_corpus_append_to_file (the file format holds f32 rows)");
+    if (c && c->row_dtype != SMT_ROWS_F32) return smt::refuse_rows(c, "smt_corpus_append_to_file (the file format holds f32 rows)");
     return smt::corpus_append_to_file_ex(c, path, rows_on_disk, rows_on_disk, 0);
 } catch (...) { return smt::api_catch(); }
 

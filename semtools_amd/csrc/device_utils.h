@@ -325,6 +325,18 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
     return (s0 + s1) + (s2 + s3);
 }
 
+// Max over the 64 lanes of an unsigned value, result in every lane (rows_half.hip, rows_byte.hip).
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t m)
+{
+    m = max(m, dpp_u<DPP_XOR1>(m));
+    m = max(m, dpp_u<DPP_XOR2>(m));
+    m = max(m, dpp_u<DPP_HALF_MIRROR>(m));
+    m = max(m, dpp_u<DPP_MIRROR>(m));
+    const uint32_t m0 = (uint32_t)__builtin_amdgcn_readlane((int)m, 0), m1 = (uint32_t)__builtin_amdgcn_readlane((int)m, 16);
+    const uint32_t m2 = (uint32_t)__builtin_amdgcn_readlane((int)m, 32), m3 = (uint32_t)__builtin_amdgcn_readlane((int)m, 48);
+    return max(max(m0, m1), max(m2, m3));
+}
+
 __device__ __forceinline__ float dist_f32(float ab, float b2, float rq, bool q_zero)
 {
     // simsimd rules (oracle/semtools_oracle.c cos_finish): both zero -> 0,

@@ -15,18 +15,6 @@ namespace smt {
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-// max over the wave of an unsigned value, result in every lane
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t m)
-{
-    m = max(m, dpp_u<DPP_XOR1>(m));
-    m = max(m, dpp_u<DPP_XOR2>(m));
-    m = max(m, dpp_u<DPP_HALF_MIRROR>(m));
-    m = max(m, dpp_u<DPP_MIRROR>(m));
-    const uint32_t m0 = (uint32_t)__builtin_amdgcn_readlane((int)m, 0), m1 = (uint32_t)__builtin_amdgcn_readlane((int)m, 16);
-    const uint32_t m2 = (uint32_t)__builtin_amdgcn_readlane((int)m, 32), m3 = (uint32_t)__builtin_amdgcn_readlane((int)m, 48);
-    return max(max(m0, m1), max(m2, m3));
-}
-
 // FROM_F32: src = f32 rows, dst = the halves (stored).  Otherwise src = half rows, nothing is stored: the test alone.
 template <bool FROM_F32>
 __global__ void __launch_bounds__(256) rows_half_kernel(const void *src, uint64_t n_rows, u32x2 *dst, unsigned long long *out /* [count, first] */)

@@ -1,5 +1,6 @@
 // search_slab.cpp -- the search entry points over a WIDE corpus (rows of 512, 768 or 1024 floats) or a HALF corpus (rows of 256
-// binary16 values, half_rows.h: the same calls with the row type handed on): what smt_search and
+// binary16 values, half_rows.h: the same calls with the row type handed on) or a BYTE corpus (rows of 256 int8, byte_rows.h: the
+// same again, passes of four queries only, no batched route): what smt_search and
 // smt_search_topk_device[_ex] do before they would reach a 256 kernel.  Served: top-k (1 .. 56) in documents mode without a
 // distance bound, workspace mode with or without one, ranges, row_base, any number of queries in passes of four, or -- from tuning
 // key slab_batch_min (half rows: half_batch_min) queries on -- in batched passes on the MFMA pipe (batch_slab.hip, batch_half.hip)
@@ -12,7 +13,7 @@
 #include <limits>
 #include <vector>
 
-#include "half_rows.h"
+#include "byte_rows.h"
 
 namespace smt {
 
@@ -32,6 +33,13 @@ int refuse_wide(uint32_t D, const char *what)
 int refuse_half(const char *what)
 {
     set_error("%s: not served for half rows (SMT_ROWS_F16) yet (half rows: append, write, read, truncate, embed into the corpus, top-k "
+              "searches up to 56, ranges, workspace mode; everything else needs f32 rows)", what);
+    return SMT_E_UNSUPPORTED;
+}
+
+int refuse_byte(const char *what)
+{
+    set_error("%s: not served for byte rows (SMT_ROWS_I8) yet (byte rows: append, write, read, truncate, embed into the corpus, top-k "
               "searches up to 56, ranges, workspace mode; everything else needs f32 rows)", what);
     return SMT_E_UNSUPPORTED;
 }
@@ -259,6 +267,7 @@ static int debug_batch_lists_staged(smt_corpus *corpus, bool half, const float *
                                     uint32_t n_ranges, uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp)
 {
     SMT_REQUIRE(corpus && queries && out_keys && out_blocks && out_kp, "null argument");
+    if (rows_are_byte(corpus)) return refuse_byte(half ? "smt_debug_batch_half_lists (byte rows have no batched route)" : "smt_debug_batch_slab_lists (byte rows have no batched route)");
     if (half) SMT_REQUIRE(rows_are_half(corpus), "debug batch lists: a half corpus (SMT_ROWS_F16)");
     else SMT_REQUIRE(dim_is_wide(corpus->dim), "debug batch lists: a wide corpus (512, 768 or 1024 dimensions)");
     SMT_REQUIRE(top_k >= 1 && top_k <= SCAN_MAX_K, "debug batch lists: top_k in [1, 56]");

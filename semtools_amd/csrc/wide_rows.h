@@ -13,8 +13,13 @@ int refuse_dim(uint32_t D);
 int refuse_wide(uint32_t D, const char *what);
 // ... and for one half rows do not serve yet (half_rows.h): the message names the half rows
 int refuse_half(const char *what);
-// whichever of the two fits a corpus that is wide or half
-inline int refuse_rows(const smt_corpus *c, const char *what) { return c->row_dtype == SMT_ROWS_F16 ? refuse_half(what) : refuse_wide(c->dim, what); }
+// ... and for one byte rows do not serve yet (byte_rows.h): the message names the byte rows
+int refuse_byte(const char *what);
+// whichever of the three fits a corpus that is wide, half or byte
+inline int refuse_rows(const smt_corpus *c, const char *what)
+{
+    return c->row_dtype == SMT_ROWS_I8 ? refuse_byte(what) : c->row_dtype == SMT_ROWS_F16 ? refuse_half(what) : refuse_wide(c->dim, what);
+}
 
 // |f32 scan distance - exact distance| of scan_slab_kernel<S, .>, by the counting rule at F32_ERR_SCAN (common.h): a lane runs
 // 4 S fused multiply-adds, the tree (wave_sum4 or wave_sum: six levels) is taken as eight steps as there, on terms whose absolute
@@ -40,7 +45,7 @@ int launch_embed_slab(smt_ctx *ctx, const void *table, int table_dtype, uint64_t
 // K2 + finish for the queries of one call, in passes of up to four (scan_slab.hip, finish_slab.hip).  All pointers device; enqueued
 // on the context's stream, nothing waits.  chunk_table / n_chunks: the range filter (range_tables.hip), nullptr / 0 without one.
 struct SlabSearch {
-    const float *corpus = nullptr;     // (binary16 values behind it when row_dtype is SMT_ROWS_F16: half_rows.h)
+    const float *corpus = nullptr;     // (binary16 values behind it when row_dtype is SMT_ROWS_F16, signed bytes when SMT_ROWS_I8)
     int row_dtype = SMT_ROWS_F32;
     uint64_t rows = 0;                 // < 2^32 - 1
     uint32_t dim = 0;
@@ -57,7 +62,7 @@ struct SlabSearch {
     bool scan_only = false;            // never the batched route (the host form's re-run of what that route left unproved)
 };
 int launch_search_slab(smt_ctx *ctx, const SlabSearch &a);
-// what a K2 kernel of this family is launched with (scan_slab.hip, scan_half.hip)
+// what a K2 kernel of this family is launched with (scan_slab.hip, scan_half.hip, scan_byte.hip)
 struct SlabScanParams {
     const float *corpus;
     uint64_t n_rows;
