@@ -502,7 +502,7 @@ int smt_lower_lines(smt_lower *h, const char *text, const uint64_t *line_begin, 
  * everything the library promises about answers holds over the STORED values: the exact distance of a row is the f64 distance
  * (sequential sums, simsimd's accurate form) of the row's integers widened to f32 -- which is exact -- and the query as given in
  * f32; (distance, row) order, bit-identical distances, verdicts from smt_search_topk_device_ex, never an unproved list from
- * smt_search.  Units of their own: rows_byte.hip, scan_byte.hip; finish stage and host entry are the wide rows' with the element type.
+ * smt_search.  Units of their own: rows_byte.hip, scan_byte.hip, batch_byte.hip; finish stage and host entry are the wide rows' with the element type.
  * Rows that enter as f32 (append_host, write_rows, smt_embed with a corpus to append to) are quantised ONCE, on the device, bit
  * for bit this NumPy expression with every array float32:
  *     amax = np.abs(X).max(1, keepdims=True);  s = np.where(amax > 0, np.float32(127) / amax, np.float32(0))
@@ -514,13 +514,20 @@ int smt_lower_lines(smt_lower *h, const char *text, const uint64_t *line_begin, 
  * unlike half rows.  smt_corpus_from_device_typed adopts [n_rows x 256] int8, 16-byte aligned; every byte is a valid value, -128
  * included, so there is no pass over the rows and the call does not wait.
  * smt_corpus_read_rows returns the stored integers as f32 (widened on the device, exact): the stored DIRECTION, not the row given.
- *   served   what half rows serve, but no batched route: append_host, write_rows, read_rows, truncate, destroy; smt_embed
+ *   served   what half rows serve: append_host, write_rows, read_rows, truncate, destroy; smt_embed
  *            appending into it; smt_search in SMT_MODE_DOCUMENTS without max_distance and in SMT_MODE_WORKSPACE with or without
- *            it, 0 <= top_k <= 56, ranges, row_base, any nq in passes of up to four queries, the zero-query shortcut;
- *            smt_search_topk_device[_ex], 1 <= top_k <= 56, with verdicts under the scan's bound 6.7e-6; unproved lists of
- *            smt_search re-answered exhaustively and counted by smt_ctx_uncertain_count.
+ *            it, 0 <= top_k <= 56, ranges, row_base, any nq in passes of up to four queries or batched (below), the zero-query
+ *            shortcut; smt_search_topk_device[_ex], 1 <= top_k <= 56, with verdicts under the scan's bound 6.7e-6; unproved lists
+ *            of smt_search re-answered exhaustively and counted by smt_ctx_uncertain_count.
+ *            From tuning key byte_batch_min queries on (default 4) a call runs the BATCHED route (batch_byte.hip): passes of 128
+ *            queries share one read of the corpus, nominated on the int8 MFMA pipe.  The stored row is the operand; the unit query
+ *            becomes rint(2^22 u) in three balanced base-256 digit planes, each with an i32 accumulator of its own, so no
+ *            instruction rounds and the only error is the query's representation.  The verdicts then rest on that route's bound,
+ *            3.5e-6 -- TIGHTER than the scan's, so smt_search does not run its unproved queries again through the scan: they are
+ *            re-answered exhaustively.  -128, which only an adopted corpus holds, takes the route like any other byte.
  *   byte rows: not yet (SMT_E_UNSUPPORTED, the message names the byte rows, nothing is enqueued or changed)
- *            everything half rows refuse, and the test hooks of the batched routes (smt_debug_batch_*_lists).
+ *            everything half rows refuse, and the test hooks of the other batched routes (smt_debug_batch_slab_lists,
+ *            smt_debug_batch_half_lists: the message names smt_debug_batch_byte_lists).
  * These calls skip the one-query pipeline, its grouping and direct delivery: everything is enqueued on the context's stream. */
 #define SMT_ROWS_F32 0
 #define SMT_ROWS_F16 1
@@ -1243,6 +1250,11 @@ int smt_debug_batch_slab_lists(smt_corpus *corpus, const float *queries, uint32_
  *       guard set and errors as above.  tests/test_gpu_half_batch.py. */
 int smt_debug_batch_half_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
                                uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp);
+/*   smt_debug_batch_byte_lists   the same for the batched route of BYTE rows (csrc/batch_byte.hip): the production digit split and the
+ *       launches of batch_byte_kernel, one per pass of 128 queries, over a byte corpus (anything else: SMT_E_INVALID); arguments, layout,
+ *       guard set and errors as above.  tests/test_gpu_byte_batch.py. */
+int smt_debug_batch_byte_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                               uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp);
 
 /* The context's second stream (hipStream_t), created on first use: async selects run on it, or, with tuning key
  * scan_overlap, it waits for them (every select of an overlapped call enqueued before the work).  A host that
@@ -1302,6 +1314,9 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *                        passes of four, exactly as before.  The answers are the same bytes
  *   half_batch_direct (0/1)  that kernel's row path: 0 (default) 128-byte runs through an LDS transpose, 1 operand layout straight
  *                        from memory in 32-byte runs (A/B only)
+ *   byte_batch_min (default 4; 0 = never)  BYTE rows: calls of at least this many queries run in passes of 128 queries that share one
+ *                        read of the corpus, dot products on the int8 MFMA pipe (batch_byte.hip); fewer queries run the scan in
+ *                        passes of four, exactly as before.  The answers are the same bytes
  *   direct_delivery (1/0)  smt_search top-k calls with a small answer (<= 32 queries, <= 8 KiB of rows and distances) get it DELIVERED
  *                        by the select kernel: its last block writes the answer into pinned host memory and a completion word behind
  *                        it, which the host waits on -- no D2H copy command, no hipStreamSynchronize (~10 us of a small call); 0: A/B

@@ -105,15 +105,6 @@ __device__ __forceinline__ float half_sumsq8(const u32x4 &r, float acc)
     return acc;
 }
 
-// Lanes of one wave hand data to each other through LDS: only half the lanes write a slice, so without this the compiler takes a
-// lane that wrote nothing to read what it read before.  Wavefront scope: no instruction, an ordering for the compiler alone.
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 template <bool FILTERED, bool DIRECT>
 __global__ void __launch_bounds__(BS_THREADS, 2) batch_half_kernel(BatchHalfParams p)
 {

@@ -1,5 +1,5 @@
 // batch_list.h -- what the batched streaming kernels share (batch_slab.hip: wide f32 rows on the bf16 MFMA pipe; batch_half.hip: half
-// rows on the f16 pipe): the frame of a launch (512 threads, a wave owns 32-row tiles dealt round robin, at most SLAB_MAX_LISTS
+// rows on the f16 pipe; batch_byte.hip: byte rows on the int8 pipe): the frame of a launch (512 threads, a wave owns 32-row tiles dealt round robin, at most SLAB_MAX_LISTS
 // blocks), the per-(block, query) lists in the block_lists area under an LDS lock word per query, the epilogue that turns a tile's
 // accumulators into candidates, and the host side's grid, scratch layout and list test hook.
 //
@@ -22,6 +22,15 @@ __device__ __forceinline__ key_t64 readlane_key(key_t64 v, int l)
 {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
     return ((key_t64)hi << 32) | lo;
+}
+
+// Lanes of one wave hand data to each other through LDS: only half the lanes write a slice, so without this the compiler takes a
+// lane that wrote nothing to read what it read before.  Wavefront scope: no instruction, an ordering for the compiler alone.
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // The candidates `cand` (a lane mask; lane l: key ck) into the list of one (block, query) pair, under the query's lock (header: LISTS)

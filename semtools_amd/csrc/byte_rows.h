@@ -40,6 +40,30 @@ int rows_to_byte(smt_ctx *ctx, const float *src_dev, uint64_t n_rows, void *dst_
 // n_rows byte rows widened into dst_dev (f32); enqueued on the context's stream
 int launch_byte_to_f32(smt_ctx *ctx, const void *src_dev, uint64_t n_rows, float *dst_dev);
 
+// |nominated distance - exact distance| of batch_byte_kernel (batch_byte.hip), by the rules f32_err_batch_half (half_rows.h) uses.
+// The ROWS contribute nothing, a stored row is the operand, and the INSTRUCTIONS contribute nothing either: the three digit planes
+// accumulate in i32, |A_d| <= 2^22, exact (where the half route counts 32 x 2^-22).  Representation, the query's alone: n_i =
+// rint(2^22 u_i) is off by at most 1/2, that is |e_i| <= 2^-23 on u_i, and over a row |<e, c>| / |c| <= |e|_2 <= 16 x 2^-23 = 2^-19.
+// The f32 scalings, in units of 2^-24 of the cosine, as built: |q|^2 -- four fused multiply-adds and the six levels of wave_sum,
+// ten roundings, halved by the root -- 5; its rsqrt 1; u_i = q_i x that 1; x 2^22 exact; |c|^2 an exact integer, its rsqrt 1,
+// x 2^-22 exact; the combination 256 A1 + A2 rounds at magnitude <= 2^19 |c| (|d1|_2, |d2|_2 <= 2^11), 1/8, and 65536 A0 + that 1;
+// score x rxj 1; 1 - that 1: 11.2 x 2^-24 = 6.7e-7, inside the 1e-6 the half route allots to its two scalings.  The whole times the
+// project's 1.2: 1.2 x (2^-19 + 1e-6) = 3.49e-6 -- UNDER the scan's f32_err_byte, so what this route leaves unproved the scan
+// cannot prove either: search_wide_host does not run byte rows again through the scan, they fall to the exhaustive re-answer.
+// DERIVED, not measured; profiles/byte_batch.json records the largest |d32 - d64| tests/test_gpu_byte_batch.py saw.
+constexpr double f32_err_batch_byte = 1.2 * (1.0 / 524288.0 + 1e-6);
+
+// The batched route (batch_byte.hip): calls of at least tuning key byte_batch_min queries (0: never) run passes of byte_batch_qb
+// queries on the int8 MFMA pipe, certified under f32_err_batch_byte.
+inline bool byte_batch_serves(const smt_ctx *ctx, const SlabSearch &a)
+{
+    return !a.scan_only && a.row_dtype == SMT_ROWS_I8 && ctx->tune.byte_batch_min > 0 && a.nq >= (uint32_t)ctx->tune.byte_batch_min;
+}
+uint32_t byte_batch_qb();
+int launch_batch_byte(smt_ctx *ctx, const SlabSearch &a);
+int debug_batch_byte_lists(smt_ctx *ctx, const SlabSearch &a, key_t64 *out_keys_host, uint64_t out_cap_keys, uint32_t *out_blocks,
+                           uint32_t *out_kp);
+
 // scan_byte.hip: scan_byte_kernel<slots, filtered>, launched by launch_search_slab (scan_slab.hip) like the wide and half kernels
 slab_scan_kernel_t byte_scan_kernel_of(int slots, bool filtered);
 
