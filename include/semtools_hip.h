@@ -528,17 +528,51 @@ int smt_lower_lines(smt_lower *h, const char *text, const uint64_t *line_begin, 
  *   byte rows: not yet (SMT_E_UNSUPPORTED, the message names the byte rows, nothing is enqueued or changed)
  *            everything half rows refuse, and the test hooks of the other batched routes (smt_debug_batch_slab_lists,
  *            smt_debug_batch_half_lists: the message names smt_debug_batch_byte_lists).
+ *
+ * NIBBLE ROWS.  A corpus made with SMT_ROWS_I4 stores each row as 256 signed 4-bit integers: 128 B, an eighth of the f32 bytes of
+ * every scan, eight times the lines per GPU and twice those of byte rows.  D = 256 only: SMT_ROWS_I4 with a wide D is
+ * SMT_E_UNSUPPORTED.  As for byte rows the stored row is a DIRECTION without a scale, and everything the library promises about
+ * answers holds over the STORED values: the exact distance of a row is the f64 distance (sequential sums) of the row's integers
+ * widened to f32 -- which is exact -- and the query as given in f32; (distance, row) order, bit-identical distances, verdicts from
+ * smt_search_topk_device_ex, never an unproved list from smt_search.  Units of their own: rows_nibble.hip, scan_nibble.hip.
+ * LAYOUT: byte j of a row holds element 2 j in bits 0 .. 3 and element 2 j + 1 in bits 4 .. 7, two's complement, [-8, 7]; a
+ * little-endian dword holds eight consecutive elements in the order v_dot8_i32_i4 pairs them.
+ * Rows that enter as f32 (append_host, write_rows, smt_embed with a corpus to append to) are quantised ONCE, on the device, bit
+ * for bit this NumPy expression with every array float32:
+ *     amax = np.abs(X).max(1, keepdims=True);  s = np.where(amax > 0, np.float32(7) / amax, np.float32(0))
+ *     q = np.rint(X * s).astype(np.int8)
+ *     packed = ((q[:, 0::2] & 15) | ((q[:, 1::2] & 15) << 4)).astype(np.uint8)
+ * (one correctly rounded division, one multiply, nearest with ties to even; the largest component stores +-7, -8 is never produced,
+ * a zero row is stored as zeros; scaling a row by a power of two changes no stored nibble).  A row outside the f32 domain below
+ * ("Domain") is SMT_E_INVALID, the corpus untouched; there is no further condition.  smt_corpus_from_device_typed adopts
+ * [n_rows x 128] bytes, 16-byte aligned; every byte is a valid pair, -8 included, so there is no pass over the rows and the call
+ * does not wait.  smt_corpus_info reports 128 bytes a row.  smt_corpus_read_rows returns the stored integers as f32 (widened on the
+ * device, exact): the stored DIRECTION, not the row given.
+ * THE SCAN keeps the dot product in integers: the unit query becomes n = rint(2^22 u) once per wave, in six balanced base-16 digit
+ * planes; v_dot8_i32_i4 multiplies eight nibble pairs an instruction, <row, n> and |row|^2 are exact i32, and one conversion, one
+ * rsqrt and two multiplies follow.  The only errors are the query's representation (2^-19 over a row) and those few f32 operations:
+ * the verdicts rest on the derived bound 3.5e-6.
+ *   served   what byte rows serve, WITHOUT a batched route: append_host, write_rows, read_rows, truncate, destroy; smt_embed
+ *            appending into it; smt_search in SMT_MODE_DOCUMENTS without max_distance and in SMT_MODE_WORKSPACE with or without
+ *            it, 0 <= top_k <= 56, ranges, row_base, any nq in passes of up to four queries, the zero-query shortcut;
+ *            smt_search_topk_device[_ex], 1 <= top_k <= 56, with verdicts under 3.5e-6; unproved lists of smt_search re-answered
+ *            exhaustively and counted by smt_ctx_uncertain_count.
+ *   nibble rows: not yet (SMT_E_UNSUPPORTED, the message names the nibble rows, nothing is enqueued or changed)
+ *            everything byte rows refuse, and the test hooks of all three batched routes (smt_debug_batch_slab_lists,
+ *            smt_debug_batch_half_lists, smt_debug_batch_byte_lists).
  * These calls skip the one-query pipeline, its grouping and direct delivery: everything is enqueued on the context's stream. */
 #define SMT_ROWS_F32 0
 #define SMT_ROWS_F16 1
 #define SMT_ROWS_I8 2
+#define SMT_ROWS_I4 3
 int smt_corpus_create(smt_ctx *ctx, uint32_t D, uint64_t capacity_rows, smt_corpus **out);
 /* adopt rows already in device memory (not copied, not freed, not growable) */
 int smt_corpus_from_device(smt_ctx *ctx, const float *rows_dev, uint64_t n_rows, uint32_t D,
                            smt_corpus **out);
 /* The same two with the element type of the stored rows (SMT_ROWS_*); the untyped forms are the SMT_ROWS_F32 case.  Adopted half
  * rows: [n_rows x 256] binary16, 16-byte aligned, every value finite (an Inf or NaN is SMT_E_INVALID as a row outside the domain).
- * Adopted byte rows: [n_rows x 256] int8, 16-byte aligned, any value. */
+ * Adopted byte rows: [n_rows x 256] int8, 16-byte aligned, any value.  Adopted nibble rows: [n_rows x 128] bytes of packed int4
+ * pairs, 16-byte aligned, any value. */
 int smt_corpus_create_typed(smt_ctx *ctx, uint32_t D, int row_dtype, uint64_t capacity_rows, smt_corpus **out);
 int smt_corpus_from_device_typed(smt_ctx *ctx, const void *rows_dev, int row_dtype, uint64_t n_rows, uint32_t D, smt_corpus **out);
 /* what a corpus stores: SMT_ROWS_*, D, bytes per stored row; any pointer may be NULL */

@@ -128,6 +128,7 @@ pub const SMT_UG_MAX_LONG: c_int = 2048;
 pub const SMT_ROWS_F32: c_int = 0;
 pub const SMT_ROWS_F16: c_int = 1;
 pub const SMT_ROWS_I8: c_int = 2;
+pub const SMT_ROWS_I4: c_int = 3;
 pub const SMT_STATUS_PROVED: c_int = 0;
 pub const SMT_STATUS_UNCERTAIN: c_int = 1;
 pub const SMT_STATUS_OVERFLOW: c_int = 2;

@@ -66,9 +66,10 @@ UG_PREPEND = {"always": 0, "first": 1, "never": 2}
 TABLE_F32, TABLE_F16, TABLE_I8 = 0, 1, 2
 TABLE_DTYPES = {np.dtype(np.float32): TABLE_F32, np.dtype(np.float16): TABLE_F16, np.dtype(np.int8): TABLE_I8}
 TABLE_NP = {v: k for k, v in TABLE_DTYPES.items()}
-ROWS_F32, ROWS_F16, ROWS_I8 = 0, 1, 2
+ROWS_F32, ROWS_F16, ROWS_I8, ROWS_I4 = 0, 1, 2, 3
 ROWS_DTYPES = {np.dtype(np.float32): ROWS_F32, np.dtype(np.float16): ROWS_F16, np.dtype(np.int8): ROWS_I8}
 ROWS_NP = {v: k for k, v in ROWS_DTYPES.items()}
+ROWS_NP[ROWS_I4] = "int4"   # nibble rows: NumPy has no such type, the name stands for it
 
 
 def table_dtype_code(dtype):

@@ -635,8 +635,10 @@ class Corpus:
     """Row-major [rows x dim] matrix resident in HBM (smt_corpus); dim = 256, or a wide 512, 768, 1024.  dtype: how the rows are
     STORED -- np.float32, or np.float16 at dim 256 (half rows: rows go in and come out as f32, rounded to nearest-even once on the
     device; a device_ptr then points at binary16 values), or np.int8 at dim 256 (byte rows: a row is stored as its int8 direction,
-    rint(x * (127 / max|x|)), and read_rows returns those integers as f32; a device_ptr then points at int8 values).  A number
-    outside L.ROWS_NP is handed on for the library to refuse."""
+    rint(x * (127 / max|x|)), and read_rows returns those integers as f32; a device_ptr then points at int8 values), or "int4"
+    (also L.ROWS_I4; NumPy has no such type) at dim 256 (nibble rows: a row is stored as its int4 direction, rint(x * (7 / max|x|)),
+    128 bytes, and read_rows returns those integers as f32; a device_ptr then points at PACKED bytes, element 2 j in the low nibble
+    of byte j, element 2 j + 1 in the high one).  A number outside L.ROWS_NP is handed on for the library to refuse."""
 
     def __init__(self, ctx, capacity_rows=0, device_ptr=None, rows=None, _handle=None, _borrowed=False, dim=L.DIM, dtype=np.float32):
         self.ctx = ctx
@@ -656,6 +658,8 @@ class Corpus:
 
     @staticmethod
     def _rows_code(dtype):
+        if isinstance(dtype, str) and dtype == "int4":
+            return L.ROWS_I4
         return int(dtype) if isinstance(dtype, int) else L.ROWS_DTYPES[np.dtype(dtype)]
 
     @classmethod

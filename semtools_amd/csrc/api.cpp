@@ -11,7 +11,7 @@
 #include <unistd.h>
 
 #include "common.h"
-#include "byte_rows.h"
+#include "nibble_rows.h"
 
 namespace smt {
 
@@ -907,26 +907,30 @@ void smt_model_destroy(smt_model *model)
 
 /* --------------------------------------------------------------- corpus ---- */
 
-// the row type of a typed creator: an unknown one is SMT_E_INVALID, half and byte rows exist at 256 dimensions only
+// the row type of a typed creator: an unknown one is SMT_E_INVALID, half, byte and nibble rows exist at 256 dimensions only
 static int check_row_dtype(int row_dtype, uint32_t D)
 {
-    if (row_dtype != SMT_ROWS_F32 && row_dtype != SMT_ROWS_F16 && row_dtype != SMT_ROWS_I8) {
-        set_error("unknown row dtype %d (SMT_ROWS_F32, SMT_ROWS_F16, SMT_ROWS_I8)", row_dtype);
+    if (row_dtype != SMT_ROWS_F32 && row_dtype != SMT_ROWS_F16 && row_dtype != SMT_ROWS_I8 && row_dtype != SMT_ROWS_I4) {
+        set_error("unknown row dtype %d (SMT_ROWS_F32, SMT_ROWS_F16, SMT_ROWS_I8, SMT_ROWS_I4)", row_dtype);
         return SMT_E_INVALID;
     }
     if (!dim_supported(D)) return refuse_dim(D);
     if (row_dtype == SMT_ROWS_F16 && D != SMT_DIM) return refuse_half("a corpus of half rows wider than 256 dimensions");
     if (row_dtype == SMT_ROWS_I8 && D != SMT_DIM) return refuse_byte("a corpus of byte rows wider than 256 dimensions");
+    if (row_dtype == SMT_ROWS_I4 && D != SMT_DIM) return refuse_nibble("a corpus of nibble rows wider than 256 dimensions");
     return SMT_OK;
 }
 
-// f32 rows on the device into what a half or byte corpus stores, checked on the way (rows_half.hip, rows_byte.hip), and back
+// f32 rows on the device into what a half, byte or nibble corpus stores, checked on the way (rows_half.hip, rows_byte.hip,
+// rows_nibble.hip), and back
 static int rows_to_stored(const smt_corpus *c, const float *src_dev, uint64_t n_rows, void *dst_dev, const char *what)
 {
+    if (rows_are_nibble(c)) return rows_to_nibble(c->ctx, src_dev, n_rows, dst_dev, what);
     return rows_are_byte(c) ? rows_to_byte(c->ctx, src_dev, n_rows, dst_dev, what) : rows_to_half(c->ctx, src_dev, n_rows, dst_dev, what);
 }
 static int stored_to_f32(const smt_corpus *c, const void *src_dev, uint64_t n_rows, float *dst_dev)
 {
+    if (rows_are_nibble(c)) return launch_nibble_to_f32(c->ctx, src_dev, n_rows, dst_dev);
     return rows_are_byte(c) ? launch_byte_to_f32(c->ctx, src_dev, n_rows, dst_dev) : launch_half_to_f32(c->ctx, src_dev, n_rows, dst_dev);
 }
 
@@ -961,10 +965,10 @@ try {
     SMT_REQUIRE(out && (rows_dev || n_rows == 0), "null argument");
     *out = nullptr;
     if ((rc = check_row_dtype(row_dtype, D))) return rc;
-    const bool half = row_dtype == SMT_ROWS_F16, byte = row_dtype == SMT_ROWS_I8;
-    // the half and byte scans read a row with 16-byte lane loads
-    if ((half || byte) && reinterpret_cast<uintptr_t>(rows_dev) % 16 != 0) {
-        set_error("%s rows in device memory must be 16-byte aligned", half ? "half" : "byte");
+    const bool half = row_dtype == SMT_ROWS_F16, byte = row_dtype == SMT_ROWS_I8, nibble = row_dtype == SMT_ROWS_I4;
+    // the half, byte and nibble scans read a row with 16-byte lane loads
+    if ((half || byte || nibble) && reinterpret_cast<uintptr_t>(rows_dev) % 16 != 0) {
+        set_error("%s rows in device memory must be 16-byte aligned", half ? "half" : nibble ? "nibble" : "byte");
         return SMT_E_INVALID;
     }
     smt_corpus *c = new (std::nothrow) smt_corpus();
@@ -973,8 +977,8 @@ try {
     c->d_rows = static_cast<float *>(const_cast<void *>(rows_dev));
     c->rows = n_rows; c->capacity = n_rows;
     // the rows as they are NOW must be in the library's domain (domain.hip); the caller answers for what it writes there later.
-    // Byte rows have no value outside it: no pass over them, nothing waits.
-    if (n_rows && !byte) {
+    // Byte and nibble rows have no value outside it: no pass over them, nothing waits.
+    if (n_rows && !byte && !nibble) {
         int rc2 = bind_device(ctx);
         if (!rc2) rc2 = half ? require_half_rows_domain(ctx, rows_dev, n_rows, "smt_corpus_from_device_typed")
                              : require_rows_domain_dim(ctx, c->d_rows, n_rows, D, "smt_corpus_from_device");
@@ -1024,7 +1028,7 @@ try {
     if (n_rows == 0) return SMT_OK;
     if ((rc = corpus_reserve(c, c->rows + n_rows))) return rc;
     if (rows_are_typed(c)) {
-        // uploaded as f32 beside the corpus, rounded and checked on their way behind the last counted row (rows_half.hip, rows_byte.hip)
+        // uploaded as f32 beside the corpus, rounded and checked on their way behind the last counted row (rows_half.hip, rows_byte.hip, rows_nibble.hip)
         DeviceTemp tmp;
         const size_t bytes = (size_t)n_rows * c->dim * sizeof(float);
         if (hipMalloc(&tmp.p, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc(%zu) for the rows to round", bytes); return SMT_E_NOMEM; }
@@ -1206,7 +1210,7 @@ try {
     // staging: ids + rebased offsets (+ output rows when not appending)
     const size_t ids_bytes = ((size_t)n_ids * sizeof(uint32_t) + 15) & ~(size_t)15;
     const size_t off_bytes = ((size_t)(n_lines + 1) * sizeof(uint64_t) + 15) & ~(size_t)15;
-    const bool to_half = append_to && rows_are_typed(append_to);   // K1 pools f32 rows into the staging, rows_half.hip / rows_byte.hip store them
+    const bool to_half = append_to && rows_are_typed(append_to);   // K1 pools f32 rows into the staging, rows_half.hip / rows_byte.hip / rows_nibble.hip store them
     const size_t out_bytes = append_to && !to_half ? 0 : (size_t)n_lines * model->D * sizeof(float);
     DeviceTemp tmp;
     {

@@ -218,8 +218,8 @@ struct smt_corpus {
     uint64_t rows = 0;
     uint64_t capacity = 0;
     uint32_t dim = 0;
-    int row_dtype = SMT_ROWS_F32;   // SMT_ROWS_F16: d_rows points at binary16 values, `dim` of them per row (half_rows.h); SMT_ROWS_I8: at signed bytes (byte_rows.h)
-    size_t row_bytes() const { return (size_t)dim * (row_dtype == SMT_ROWS_I8 ? 1 : row_dtype == SMT_ROWS_F16 ? 2 : 4); }
+    int row_dtype = SMT_ROWS_F32;   // SMT_ROWS_F16: d_rows points at binary16 values, `dim` of them per row (half_rows.h); SMT_ROWS_I8: at signed bytes (byte_rows.h); SMT_ROWS_I4: at packed signed nibbles, dim / 2 bytes per row (nibble_rows.h)
+    size_t row_bytes() const { return row_dtype == SMT_ROWS_I4 ? (size_t)dim / 2 : (size_t)dim * (row_dtype == SMT_ROWS_I8 ? 1 : row_dtype == SMT_ROWS_F16 ? 2 : 4); }
     bool owned = true;
     // fp16 OPERAND IMAGE (gemm_rowreg.hip: pack_image_kernel): what the batched fp16 nomination modes multiply with, kept
     // beside the f32 rows -- 512 B per row, 16 KiB per 32-row tile -- so that a batch reads half the bytes and converts nothing.

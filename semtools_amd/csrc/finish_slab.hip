@@ -16,8 +16,12 @@
 // Fewer than k' nominated keys are all the rows there are: proved.  A query outside the domain: SMT_STATUS_INVALID_QUERY.
 // HALF rows (half_rows.h) come here as <1, _Float16>: the row read widens the stored halves -- exactly, in integer arithmetic -- on
 // their way into LDS or the sums, everything behind it is the f32 code; the bound is f32_err_half.  BYTE rows (byte_rows.h) come
-// as <1, int8_t>: sign extension and an integer conversion, exact as well; the bound is f32_err_byte.
-#include "byte_rows.h"
+// as <1, int8_t>: sign extension and an integer conversion, exact as well; the bound is f32_err_byte.  NIBBLE rows (nibble_rows.h)
+// come as <1, nibble_t>: four components are two bytes, a shift pair sign-extends each nibble, an integer conversion follows --
+// exact again; the bound is f32_err_nibble.
+#include <type_traits>
+
+#include "nibble_rows.h"
 #include "device_utils.h"
 
 namespace smt {
@@ -39,11 +43,19 @@ struct SlabFinishParams {
 constexpr int FIN_THREADS = 1024;
 constexpr int FIN_SURV_CAP = 4096;   // k'^2 at k' = 64
 
-// four components of a stored row, widened: e counts float4 (f32 rows) resp. groups of four halves or four bytes
+// four components of a stored row, widened: e counts float4 (f32 rows) resp. groups of four halves, four bytes or four nibbles
 template <typename RowT>
 __device__ __forceinline__ f32x4 row_quad(const float *rows, uint64_t row, uint32_t dim, uint32_t e)
 {
-    if constexpr (sizeof(RowT) == 4) {
+    if constexpr (std::is_same_v<RowT, nibble_t>) {
+        const uint32_t w = reinterpret_cast<const uint16_t *>(reinterpret_cast<const uint8_t *>(rows) + row * (dim / 2))[e];
+        f32x4 v;
+        v.x = (float)((int)(w << 28) >> 28);
+        v.y = (float)((int)(w << 24) >> 28);
+        v.z = (float)((int)(w << 20) >> 28);
+        v.w = (float)((int)(w << 16) >> 28);
+        return v;
+    } else if constexpr (sizeof(RowT) == 4) {
         return reinterpret_cast<const f32x4 *>(rows + row * dim)[e];
     } else if constexpr (sizeof(RowT) == 1) {
         const uint32_t w = reinterpret_cast<const uint32_t *>(reinterpret_cast<const int8_t *>(rows) + row * dim)[e];
@@ -235,7 +247,7 @@ int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, 
                        uint32_t nq_pass, double f32_err)
 {
     SMT_REQUIRE(n_lists <= (uint32_t)SLAB_MAX_LISTS && kp >= a.k_out && kp <= 64 && nq_pass >= 1, "wide finish: <= 256 lists, k_out <= k' <= 64");
-    const bool half = a.row_dtype == SMT_ROWS_F16, byte = a.row_dtype == SMT_ROWS_I8;
+    const bool half = a.row_dtype == SMT_ROWS_F16, byte = a.row_dtype == SMT_ROWS_I8, nibble = a.row_dtype == SMT_ROWS_I4;
     SlabFinishParams p;
     p.corpus = a.corpus;
     p.queries = a.queries + (size_t)first_query * a.dim;
@@ -249,11 +261,12 @@ int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, 
     p.out_counts = a.out_counts ? a.out_counts + first_query : nullptr;
     p.out_status = a.out_status ? a.out_status + first_query : nullptr;
     const int S = (int)(a.dim / 256);
-    p.f32_err = f32_err > 0.0 ? f32_err : byte ? f32_err_byte : half ? f32_err_half : S == 2 ? f32_err_slab(2) : S == 3 ? f32_err_slab(3) : f32_err_slab(4);
+    p.f32_err = f32_err > 0.0 ? f32_err : nibble ? f32_err_nibble : byte ? f32_err_byte : half ? f32_err_half : S == 2 ? f32_err_slab(2) : S == 3 ? f32_err_slab(3) : f32_err_slab(4);
     p.sticky = ctx->d_status;
     const size_t smem = finish_smem_bytes(a.dim);
     prof_begin(ctx, "finish_slab");
-    if (byte) hipLaunchKernelGGL((finish_slab_kernel<1, int8_t>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
+    if (nibble) hipLaunchKernelGGL((finish_slab_kernel<1, nibble_t>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
+    else if (byte) hipLaunchKernelGGL((finish_slab_kernel<1, int8_t>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
     else if (half) hipLaunchKernelGGL((finish_slab_kernel<1, _Float16>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
     else if (S == 2) hipLaunchKernelGGL((finish_slab_kernel<2, float>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
     else if (S == 3) hipLaunchKernelGGL((finish_slab_kernel<3, float>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
@@ -303,14 +316,15 @@ __global__ void __launch_bounds__(256) exact_all_slab_kernel(const float *corpus
 int launch_exact_all_slab(smt_ctx *ctx, const float *corpus, int row_dtype, uint64_t rows, uint32_t dim, const float *query,
                           const uint64_t *chunk_table, uint64_t n_chunks, double *out)
 {
-    const bool half = row_dtype == SMT_ROWS_F16, byte = row_dtype == SMT_ROWS_I8;
-    SMT_REQUIRE(half || byte ? dim == SMT_DIM : dim_is_wide(dim), "wide rows: 512, 768 or 1024 dimensions, or half or byte rows of 256");
+    const bool half = row_dtype == SMT_ROWS_F16, byte = row_dtype == SMT_ROWS_I8, nibble = row_dtype == SMT_ROWS_I4;
+    SMT_REQUIRE(half || byte || nibble ? dim == SMT_DIM : dim_is_wide(dim), "wide rows: 512, 768 or 1024 dimensions, or half, byte or nibble rows of 256");
     const uint64_t n = chunk_table ? n_chunks * FILTER_CHUNK : rows;
     if (n == 0) return SMT_OK;
     const uint64_t blocks = (n + 255) / 256;
     SMT_REQUIRE(blocks < (1ull << 31), "too many rows for one exhaustive launch");
     prof_begin(ctx, "exact_slab");
-    if (byte) hipLaunchKernelGGL(exact_all_slab_kernel<int8_t>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, corpus, rows, dim, query, chunk_table, n_chunks, out);
+    if (nibble) hipLaunchKernelGGL(exact_all_slab_kernel<nibble_t>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, corpus, rows, dim, query, chunk_table, n_chunks, out);
+    else if (byte) hipLaunchKernelGGL(exact_all_slab_kernel<int8_t>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, corpus, rows, dim, query, chunk_table, n_chunks, out);
     else if (half) hipLaunchKernelGGL(exact_all_slab_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, corpus, rows, dim, query, chunk_table, n_chunks, out);
     else hipLaunchKernelGGL(exact_all_slab_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, corpus, rows, dim, query, chunk_table, n_chunks, out);
     prof_end(ctx, "exact_slab");

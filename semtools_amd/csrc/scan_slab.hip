@@ -26,11 +26,11 @@
 // Either tree has six levels; f32_err_slab (wide_rows.h) counts them as the 256 bound does.
 //
 // Lists, block merge, padding and order are the 256 kernel's ideas, written again (lane_list.h, shared with scan_half.hip, whose
-// kernel this file's launch_search_slab also launches, as it does scan_byte.hip's): a lane-distributed sorted list per
+// kernel this file's launch_search_slab also launches, as it does scan_byte.hip's and scan_nibble.hip's): a lane-distributed sorted list per
 // query, k' = min(64, top_k + guard band); every block merges its waves' lists by counting ranks into ONE block list of key_t64 per
 // query, strictly ascending by (distance, row), padded with KEY_PAD.  Range-filtered scans walk the chunk table of
 // range_tables.hip (first row | valid rows << 32, FILTER_CHUNK rows per entry), U rows of an entry per step.
-#include "byte_rows.h"
+#include "nibble_rows.h"
 #include "lane_list.h"
 
 namespace smt {
@@ -208,7 +208,8 @@ int launch_search_slab(smt_ctx *ctx, const SlabSearch &a)
 {
     const bool half = a.row_dtype == SMT_ROWS_F16;   // 512-byte rows of 256 halves: scan_half.hip, eight rows a step
     const bool byte = a.row_dtype == SMT_ROWS_I8;    // 256-byte rows of 256 int8: scan_byte.hip, sixteen rows a step
-    SMT_REQUIRE(half || byte ? a.dim == SMT_DIM : dim_is_wide(a.dim), "wide scan: 512, 768 or 1024 dimensions, or half or byte rows of 256");
+    const bool nibble = a.row_dtype == SMT_ROWS_I4;  // 128-byte rows of 256 int4: scan_nibble.hip, thirty-two rows a step, never batched
+    SMT_REQUIRE(half || byte || nibble ? a.dim == SMT_DIM : dim_is_wide(a.dim), "wide scan: 512, 768 or 1024 dimensions, or half, byte or nibble rows of 256");
     SMT_REQUIRE(a.k_out >= 1 && a.k_out <= SCAN_MAX_K, "wide scan: 1 <= top_k <= 56");
     SMT_REQUIRE(a.rows < 0xFFFFFFFFull, "wide scan: fewer than 2^32 - 1 rows per corpus");
     SMT_REQUIRE(a.nq >= 1 && a.queries && a.out_rows && a.out_dist, "wide scan: null argument");
@@ -218,9 +219,10 @@ int launch_search_slab(smt_ctx *ctx, const SlabSearch &a)
         if (byte_batch_serves(ctx, a)) return launch_batch_byte(ctx, a);   // batch_byte.hip
     }
     const int S = (int)(a.dim / 256);
-    const int U = byte ? BYTE_STEP_ROWS : half ? HALF_STEP_ROWS : S == 2 ? 2 : 1;
+    const int U = nibble ? NIBBLE_STEP_ROWS : byte ? BYTE_STEP_ROWS : half ? HALF_STEP_ROWS : S == 2 ? 2 : 1;
     const bool filtered = a.chunk_table != nullptr;
     const uint64_t n_steps = !filtered ? (a.rows + U - 1) / U
+                             : nibble  ? (a.n_chunks + NIBBLE_STEP_ROWS / FILTER_CHUNK - 1) / (NIBBLE_STEP_ROWS / FILTER_CHUNK)
                              : byte    ? (a.n_chunks + BYTE_STEP_ROWS / FILTER_CHUNK - 1) / (BYTE_STEP_ROWS / FILTER_CHUNK)
                              : half    ? (a.n_chunks + HALF_STEP_ROWS / FILTER_CHUNK - 1) / (HALF_STEP_ROWS / FILTER_CHUNK)
                                        : a.n_chunks * (uint64_t)(FILTER_CHUNK / U);
@@ -245,12 +247,13 @@ int launch_search_slab(smt_ctx *ctx, const SlabSearch &a)
         p.chunk_table = a.chunk_table;
         p.n_chunks = a.n_chunks;
         p.block_lists = lists;
-        const slab_scan_kernel_t kernel = byte   ? byte_scan_kernel_of(slots, filtered)
+        const slab_scan_kernel_t kernel = nibble ? nibble_scan_kernel_of(slots, filtered)
+                                        : byte   ? byte_scan_kernel_of(slots, filtered)
                                         : half   ? half_scan_kernel_of(slots, filtered)
                                         : S == 2 ? slab_scan_kernel_of<2>(slots, filtered)
                                         : S == 3 ? slab_scan_kernel_of<3>(slots, filtered) : slab_scan_kernel_of<4>(slots, filtered);
         const size_t smem = slab_list_smem_bytes(slots, waves);
-        const char *prof_name = byte ? "scan_byte" : half ? "scan_half" : "scan_slab";
+        const char *prof_name = nibble ? "scan_nibble" : byte ? "scan_byte" : half ? "scan_half" : "scan_slab";
         prof_begin(ctx, prof_name);
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(SLAB_THREADS), smem, ctx->stream, p);
         prof_end(ctx, prof_name);

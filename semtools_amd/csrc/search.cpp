@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "common.h"
-#include "byte_rows.h"
+#include "nibble_rows.h"
 
 using namespace smt;
 

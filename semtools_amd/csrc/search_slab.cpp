@@ -1,6 +1,7 @@
 // search_slab.cpp -- the search entry points over a WIDE corpus (rows of 512, 768 or 1024 floats) or a HALF corpus (rows of 256
 // binary16 values, half_rows.h: the same calls with the row type handed on) or a BYTE corpus (rows of 256 int8, byte_rows.h: the
-// same again): what smt_search and
+// same again) or a NIBBLE corpus (rows of 256 int4, nibble_rows.h: passes of four queries through scan_nibble.hip, no batched route,
+// so nothing is run a second time through the scan): what smt_search and
 // smt_search_topk_device[_ex] do before they would reach a 256 kernel.  Served: top-k (1 .. 56) in documents mode without a
 // distance bound, workspace mode with or without one, ranges, row_base, any number of queries in passes of four, or -- from tuning
 // key slab_batch_min (half rows: half_batch_min, byte rows: byte_batch_min) queries on -- in batched passes on the MFMA pipe
@@ -14,7 +15,7 @@
 #include <limits>
 #include <vector>
 
-#include "byte_rows.h"
+#include "nibble_rows.h"
 
 namespace smt {
 
@@ -42,6 +43,13 @@ int refuse_byte(const char *what)
 {
     set_error("%s: not served for byte rows (SMT_ROWS_I8) yet (byte rows: append, write, read, truncate, embed into the corpus, top-k "
               "searches up to 56, ranges, workspace mode; everything else needs f32 rows)", what);
+    return SMT_E_UNSUPPORTED;
+}
+
+int refuse_nibble(const char *what)
+{
+    set_error("%s: not served for nibble rows (SMT_ROWS_I4) yet (nibble rows: append, write, read, truncate, embed into the corpus, "
+              "top-k searches up to 56, ranges, workspace mode; everything else needs f32 rows)", what);
     return SMT_E_UNSUPPORTED;
 }
 
@@ -271,6 +279,10 @@ static int debug_batch_lists_staged(smt_corpus *corpus, int rows, const float *q
 {
     SMT_REQUIRE(corpus && queries && out_keys && out_blocks && out_kp, "null argument");
     const bool half = rows == SMT_ROWS_F16, byte = rows == SMT_ROWS_I8;
+    if (rows_are_nibble(corpus))
+        return refuse_nibble(byte   ? "smt_debug_batch_byte_lists (nibble rows have no batched route)"
+                             : half ? "smt_debug_batch_half_lists (nibble rows have no batched route)"
+                                    : "smt_debug_batch_slab_lists (nibble rows have no batched route)");
     if (rows_are_byte(corpus) && !byte)
         return refuse_byte(half ? "smt_debug_batch_half_lists (the batched route of byte rows has smt_debug_batch_byte_lists)"
                                 : "smt_debug_batch_slab_lists (the batched route of byte rows has smt_debug_batch_byte_lists)");

@@ -15,10 +15,14 @@ int refuse_wide(uint32_t D, const char *what);
 int refuse_half(const char *what);
 // ... and for one byte rows do not serve yet (byte_rows.h): the message names the byte rows
 int refuse_byte(const char *what);
-// whichever of the three fits a corpus that is wide, half or byte
+// ... and for one nibble rows do not serve yet (nibble_rows.h): the message names the nibble rows
+int refuse_nibble(const char *what);
+// whichever of the four fits a corpus that is wide, half, byte or nibble
 inline int refuse_rows(const smt_corpus *c, const char *what)
 {
-    return c->row_dtype == SMT_ROWS_I8 ? refuse_byte(what) : c->row_dtype == SMT_ROWS_F16 ? refuse_half(what) : refuse_wide(c->dim, what);
+    return c->row_dtype == SMT_ROWS_I4   ? refuse_nibble(what)
+           : c->row_dtype == SMT_ROWS_I8 ? refuse_byte(what)
+           : c->row_dtype == SMT_ROWS_F16 ? refuse_half(what) : refuse_wide(c->dim, what);
 }
 
 // |f32 scan distance - exact distance| of scan_slab_kernel<S, .>, by the counting rule at F32_ERR_SCAN (common.h): a lane runs
@@ -45,7 +49,7 @@ int launch_embed_slab(smt_ctx *ctx, const void *table, int table_dtype, uint64_t
 // K2 + finish for the queries of one call, in passes of up to four (scan_slab.hip, finish_slab.hip).  All pointers device; enqueued
 // on the context's stream, nothing waits.  chunk_table / n_chunks: the range filter (range_tables.hip), nullptr / 0 without one.
 struct SlabSearch {
-    const float *corpus = nullptr;     // (binary16 values behind it when row_dtype is SMT_ROWS_F16, signed bytes when SMT_ROWS_I8)
+    const float *corpus = nullptr;     // (binary16 values behind it when row_dtype is SMT_ROWS_F16, signed bytes when SMT_ROWS_I8, packed nibbles when SMT_ROWS_I4)
     int row_dtype = SMT_ROWS_F32;
     uint64_t rows = 0;                 // < 2^32 - 1
     uint32_t dim = 0;
@@ -62,7 +66,7 @@ struct SlabSearch {
     bool scan_only = false;            // never the batched route (the host form's re-run of what that route left unproved)
 };
 int launch_search_slab(smt_ctx *ctx, const SlabSearch &a);
-// what a K2 kernel of this family is launched with (scan_slab.hip, scan_half.hip, scan_byte.hip)
+// what a K2 kernel of this family is launched with (scan_slab.hip, scan_half.hip, scan_byte.hip, scan_nibble.hip)
 struct SlabScanParams {
     const float *corpus;
     uint64_t n_rows;
