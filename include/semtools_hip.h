@@ -534,7 +534,8 @@ int smt_lower_lines(smt_lower *h, const char *text, const uint64_t *line_begin, 
  * SMT_E_UNSUPPORTED.  As for byte rows the stored row is a DIRECTION without a scale, and everything the library promises about
  * answers holds over the STORED values: the exact distance of a row is the f64 distance (sequential sums) of the row's integers
  * widened to f32 -- which is exact -- and the query as given in f32; (distance, row) order, bit-identical distances, verdicts from
- * smt_search_topk_device_ex, never an unproved list from smt_search.  Units of their own: rows_nibble.hip, scan_nibble.hip.
+ * smt_search_topk_device_ex, never an unproved list from smt_search.  Units of their own: rows_nibble.hip, scan_nibble.hip,
+ * batch_nibble.hip.
  * LAYOUT: byte j of a row holds element 2 j in bits 0 .. 3 and element 2 j + 1 in bits 4 .. 7, two's complement, [-8, 7]; a
  * little-endian dword holds eight consecutive elements in the order v_dot8_i32_i4 pairs them.
  * Rows that enter as f32 (append_host, write_rows, smt_embed with a corpus to append to) are quantised ONCE, on the device, bit
@@ -552,14 +553,21 @@ int smt_lower_lines(smt_lower *h, const char *text, const uint64_t *line_begin, 
  * planes; v_dot8_i32_i4 multiplies eight nibble pairs an instruction, <row, n> and |row|^2 are exact i32, and one conversion, one
  * rsqrt and two multiplies follow.  The only errors are the query's representation (2^-19 over a row) and those few f32 operations:
  * the verdicts rest on the derived bound 3.5e-6.
- *   served   what byte rows serve, WITHOUT a batched route: append_host, write_rows, read_rows, truncate, destroy; smt_embed
+ *   served   what byte rows serve: append_host, write_rows, read_rows, truncate, destroy; smt_embed
  *            appending into it; smt_search in SMT_MODE_DOCUMENTS without max_distance and in SMT_MODE_WORKSPACE with or without
- *            it, 0 <= top_k <= 56, ranges, row_base, any nq in passes of up to four queries, the zero-query shortcut;
- *            smt_search_topk_device[_ex], 1 <= top_k <= 56, with verdicts under 3.5e-6; unproved lists of smt_search re-answered
- *            exhaustively and counted by smt_ctx_uncertain_count.
+ *            it, 0 <= top_k <= 56, ranges, row_base, any nq in passes of up to four queries or batched (below), the zero-query
+ *            shortcut; smt_search_topk_device[_ex], 1 <= top_k <= 56, with verdicts under 3.5e-6; unproved lists of smt_search
+ *            re-answered exhaustively and counted by smt_ctx_uncertain_count.
+ *            From tuning key nibble_batch_min queries on (default 4) a call runs the BATCHED route (batch_nibble.hip): passes of
+ *            128 queries share one read of the corpus, nominated on the int8 MFMA pipe.  gfx950 has no int4 MFMA: a packed dword
+ *            becomes two int8 operand dwords, 16 x its even and 16 x its odd elements, by a shift and two masks (no sign
+ *            extension; -8 becomes -128), and the query's three base-256 digit planes of rint(2^22 u) are written in that order.
+ *            Every accumulator is an exact i32, so the only error is the query's representation and the verdicts rest on the
+ *            same 3.5e-6 as the scan's: smt_search does not run the route's unproved queries again through the scan, they are
+ *            re-answered exhaustively.
  *   nibble rows: not yet (SMT_E_UNSUPPORTED, the message names the nibble rows, nothing is enqueued or changed)
- *            everything byte rows refuse, and the test hooks of all three batched routes (smt_debug_batch_slab_lists,
- *            smt_debug_batch_half_lists, smt_debug_batch_byte_lists).
+ *            everything byte rows refuse, and the test hooks of the other batched routes (smt_debug_batch_slab_lists,
+ *            smt_debug_batch_half_lists, smt_debug_batch_byte_lists: the message names smt_debug_batch_nibble_lists).
  * These calls skip the one-query pipeline, its grouping and direct delivery: everything is enqueued on the context's stream. */
 #define SMT_ROWS_F32 0
 #define SMT_ROWS_F16 1
@@ -1289,6 +1297,11 @@ int smt_debug_batch_half_lists(smt_corpus *corpus, const float *queries, uint32_
  *       guard set and errors as above.  tests/test_gpu_byte_batch.py. */
 int smt_debug_batch_byte_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
                                uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp);
+/*   smt_debug_batch_nibble_lists   the same for the batched route of NIBBLE rows (csrc/batch_nibble.hip): the production digit split and
+ *       the launches of batch_nibble_kernel, one per pass of 128 queries, over a nibble corpus (a byte corpus: SMT_E_UNSUPPORTED, anything
+ *       else: SMT_E_INVALID); arguments, layout, guard set and errors as above.  tests/test_gpu_nibble_batch.py. */
+int smt_debug_batch_nibble_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                                 uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp);
 
 /* The context's second stream (hipStream_t), created on first use: async selects run on it, or, with tuning key
  * scan_overlap, it waits for them (every select of an overlapped call enqueued before the work).  A host that
@@ -1350,6 +1363,9 @@ int smt_ctx_aux_stream(smt_ctx *ctx, void **stream_out);
  *                        from memory in 32-byte runs (A/B only)
  *   byte_batch_min (default 4; 0 = never)  BYTE rows: calls of at least this many queries run in passes of 128 queries that share one
  *                        read of the corpus, dot products on the int8 MFMA pipe (batch_byte.hip); fewer queries run the scan in
+ *                        passes of four, exactly as before.  The answers are the same bytes
+ *   nibble_batch_min (default 4; 0 = never)  NIBBLE rows: calls of at least this many queries run in passes of 128 queries that share
+ *                        one read of the corpus, dot products on the int8 MFMA pipe (batch_nibble.hip); fewer queries run the scan in
  *                        passes of four, exactly as before.  The answers are the same bytes
  *   direct_delivery (1/0)  smt_search top-k calls with a small answer (<= 32 queries, <= 8 KiB of rows and distances) get it DELIVERED
  *                        by the select kernel: its last block writes the answer into pinned host memory and a completion word behind

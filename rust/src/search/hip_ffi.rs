@@ -1141,6 +1141,18 @@ extern "C" {
         out_blocks: *mut u32,
         out_kp: *mut u32,
     ) -> c_int;
+    pub fn smt_debug_batch_nibble_lists(
+        corpus: *mut SmtCorpus,
+        queries: *const f32,
+        nq: u32,
+        top_k: u32,
+        ranges: *const SmtRange,
+        n_ranges: u32,
+        out_keys: *mut u64,
+        out_cap_keys: u64,
+        out_blocks: *mut u32,
+        out_kp: *mut u32,
+    ) -> c_int;
     pub fn smt_ctx_aux_stream(ctx: *mut SmtCtx, stream_out: *mut *mut c_void) -> c_int;
     pub fn smt_set_tuning(ctx: *mut SmtCtx, key: *const c_char, value: i64) -> c_int;
     pub fn smt_fnv1a_hash(bytes: *const u8, n: u64) -> u64;

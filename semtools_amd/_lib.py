@@ -49,7 +49,7 @@ EXPORTS = [
     "smt_debug_scan_pairs", "smt_debug_image_tile", "smt_debug_scan_groups", "smt_debug_scan_groups_wide", "smt_debug_scan_groups_deep","smt_debug_nominations",
     "smt_debug_select_groups", "smt_debug_ov_ready", "smt_debug_host_timing",
     "smt_debug_merge_sources", "smt_debug_merge_packed_strided", "smt_debug_combine_status", "smt_debug_select_lists",
-    "smt_debug_scan_lists", "smt_debug_scan_ring", "smt_debug_batch_slab_lists", "smt_debug_batch_half_lists", "smt_debug_batch_byte_lists",
+    "smt_debug_scan_lists", "smt_debug_scan_ring", "smt_debug_batch_slab_lists", "smt_debug_batch_half_lists", "smt_debug_batch_byte_lists", "smt_debug_batch_nibble_lists",
     "smt_debug_gemm_plan", "smt_debug_level_nominations", "smt_debug_bootstrap_minima", "smt_debug_bootstrap_tau", "smt_debug_level_select",
     "smt_debug_gemm_trace",
     "smt_wordpiece_create", "smt_wordpiece_create_utf8", "smt_wordpiece_info", "smt_wordpiece_destroy", "smt_wordpiece_scan_device", "smt_wordpiece_emit_device", "smt_wordpiece_tokenize",
@@ -348,6 +348,7 @@ def lib():
         L.smt_debug_batch_slab_lists.argtypes = [vp, vp, u32, u32, vp, u32, vp, u64, P(C.c_uint32), P(C.c_uint32)]
         L.smt_debug_batch_half_lists.argtypes = L.smt_debug_batch_slab_lists.argtypes
         L.smt_debug_batch_byte_lists.argtypes = L.smt_debug_batch_slab_lists.argtypes
+        L.smt_debug_batch_nibble_lists.argtypes = L.smt_debug_batch_slab_lists.argtypes
         L.smt_debug_gemm_plan.argtypes = [u64, u32, u32, i32, i32, u32, i32, i32, i32, i32, vp, u32, P(C.c_uint32)]
         L.smt_debug_level_nominations.argtypes = [vp, vp, u32, u32, vp, u32, vp, i32, u64, u32, u64, u64, vp, vp, vp, P(C.c_uint32)]
         L.smt_debug_bootstrap_minima.argtypes = [vp, vp, u32, u32, vp, u32, vp, P(C.c_uint32), P(C.c_uint64), P(C.c_uint32)]

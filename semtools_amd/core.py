@@ -820,6 +820,10 @@ class Corpus:
         """Test hook (smt_debug_batch_byte_lists): the same for the batched route of a byte corpus (batch_byte.hip)."""
         return self.debug_batch_slab_lists(queries, top_k, ranges, _hook="smt_debug_batch_byte_lists")
 
+    def debug_batch_nibble_lists(self, queries, top_k, ranges=None):
+        """Test hook (smt_debug_batch_nibble_lists): the same for the batched route of a nibble corpus (batch_nibble.hip)."""
+        return self.debug_batch_slab_lists(queries, top_k, ranges, _hook="smt_debug_batch_nibble_lists")
+
     def debug_select_lists(self, queries_ptr, nq, lists_ptr, n_lists, kp, k_out, out_rows_ptr, out_dist_ptr, list_stride=0, out_stride=0,
                            ws_threshold=None, row_base=0, f32_err=0.0, overflow_ptr=None, out_counts_ptr=None, out_uncertain_ptr=None,
                            out_status_ptr=None):

@@ -644,6 +644,10 @@ try {
         SMT_REQUIRE(value >= 0 && value <= 0x7fffffff, "byte_batch_min: queries from which a search over byte rows takes the batched route (0 = never)");
         ctx->tune.byte_batch_min = (int)value;
     }
+    else if (k == "nibble_batch_min") {
+        SMT_REQUIRE(value >= 0 && value <= 0x7fffffff, "nibble_batch_min: queries from which a search over nibble rows takes the batched route (0 = never)");
+        ctx->tune.nibble_batch_min = (int)value;
+    }
     else if (k == "half_batch_direct") ctx->tune.half_batch_direct = value ? 1 : 0;
     else if (k == "fallback_batch_min_rows") ctx->tune.fallback_batch_min_rows = value < 0 ? 0 : value;
     else if (k == "guard_band") ctx->tune.guard_band = (int)std::max<int64_t>(8, std::min<int64_t>(56, value));

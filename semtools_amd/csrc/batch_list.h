@@ -1,5 +1,5 @@
 // batch_list.h -- what the batched streaming kernels share (batch_slab.hip: wide f32 rows on the bf16 MFMA pipe; batch_half.hip: half
-// rows on the f16 pipe; batch_byte.hip: byte rows on the int8 pipe): the frame of a launch (512 threads, a wave owns 32-row tiles dealt round robin, at most SLAB_MAX_LISTS
+// rows on the f16 pipe; batch_byte.hip: byte rows on the int8 pipe; batch_nibble.hip: nibble rows, unpacked, on the same pipe): the frame of a launch (512 threads, a wave owns 32-row tiles dealt round robin, at most SLAB_MAX_LISTS
 // blocks), the per-(block, query) lists in the block_lists area under an LDS lock word per query, the epilogue that turns a tile's
 // accumulators into candidates, and the host side's grid, scratch layout and list test hook.
 //

@@ -36,7 +36,7 @@ void set_error(const char *fmt, ...);
     } while (0)
 
 // bits of smt_ctx::attr_done
-enum : uint32_t { ATTR_SELECT = 1u, ATTR_GEMM = 2u, ATTR_IVF_ASSIGN = 4u, ATTR_IVF_SCORE = 8u, ATTR_GEMM_LDS = 16u, ATTR_IVF_LPCA = 32u, ATTR_BATCH_SLAB = 64u, ATTR_BATCH_HALF = 128u, ATTR_BATCH_BYTE = 256u };
+enum : uint32_t { ATTR_SELECT = 1u, ATTR_GEMM = 2u, ATTR_IVF_ASSIGN = 4u, ATTR_IVF_SCORE = 8u, ATTR_GEMM_LDS = 16u, ATTR_IVF_LPCA = 32u, ATTR_BATCH_SLAB = 64u, ATTR_BATCH_HALF = 128u, ATTR_BATCH_BYTE = 256u, ATTR_BATCH_NIBBLE = 512u };
 
 // One candidate on the device: key = (f32 distance bits << 32) | local row.
 // Distances are clipped to >= 0, so the IEEE bit pattern is order-preserving
@@ -97,6 +97,7 @@ struct Tuning {
     int half_batch_min = 4;     // half rows: calls of this many queries take the batched f16 MFMA route (batch_half.hip; 0: never); 4: the smallest measured batch from which it beats the passes of four beyond the rounds' spread -- the nq 4 cell of profiles/half_batch.json, 0.273 ms [0.272, 0.278] against 0.327 ms [0.319, 0.344] over 1 GiB, and every larger cell
     int half_batch_direct = 0;  // batch_half_kernel's row path: 0 coalesced 128-byte runs + LDS transpose (the default: 0.273 against 0.366 ms at 4 queries, 0.318 against 0.392 at 8, level from 64 on), 1 straight into operand layout in 32-byte runs (A/B only: profiles/half_batch.json)
     int byte_batch_min = 4;     // byte rows: calls of this many queries take the batched int8 MFMA route (batch_byte.hip; 0: never); 4: the smallest measured batch from which it beats the passes of four beyond the rounds' spread -- the nq 4 cell of profiles/byte_batch.json, 0.286 ms [0.282, 0.293] against 0.386 ms [0.385, 0.419] over 1 GiB, and every larger cell
+    int nibble_batch_min = 4;   // nibble rows: calls of this many queries take the batched int8 MFMA route (batch_nibble.hip; 0: never); 4: the smallest measured batch from which it beats the passes of four beyond the rounds' spread -- the nq 4 cell of profiles/nibble_batch.json, 0.377 ms [0.375, 0.385] against 0.504 ms [0.501, 0.525] over 1 GiB, and every larger cell
     int largek_sweep_filtered = 8;  // range-filtered large-k batches of this many queries collect in ONE sweep of the batched kernel over the tile table, like unfiltered batches of five (0: never); 8: where the sweep first beat the grouped passes (profiles/largek_group_ab.json)
     int direct_delivery = 1;    // 1: host-form top-k searches with small answers (<= 8 KiB) get them DELIVERED by the select kernel into pinned host memory, completion word last; the host waits on that word (search.cpp; 0: D2H copy + hipStreamSynchronize, A/B)
     int64_t compact_bounce_rows = 65536;   // smt_corpus_compact: rows of the bounce buffer a step with a gap shorter than itself goes through (64 MiB; 64 .. 2^20), compact.hip

@@ -53,6 +53,32 @@ int rows_to_nibble(smt_ctx *ctx, const float *src_dev, uint64_t n_rows, void *ds
 // n_rows nibble rows widened into dst_dev (f32); enqueued on the context's stream
 int launch_nibble_to_f32(smt_ctx *ctx, const void *src_dev, uint64_t n_rows, float *dst_dev);
 
+// |nominated distance - exact distance| of batch_nibble_kernel (batch_nibble.hip), by the rules of f32_err_batch_byte
+// (byte_rows.h), RECOUNTED for this kernel.  The ROWS contribute nothing: the operand is 16 x the stored nibble, exactly (a shift
+// and a mask), and the 16 leaves as a power of two.  The INSTRUCTIONS contribute nothing: the three digit planes accumulate in
+// i32, |A_d| <= 256 x 128 x 128 = 2^22 (a digit's 128 against 16 x 8), exact, and |c|^2 <= 2^14 is an exact v_dot8_i32_i4 sum.
+// Representation, the query's alone: n_i = rint(2^22 u_i) is off by at most 1/2, |e_i| <= 2^-23 on u_i, and over a row
+// |<e, c>| / |c| <= |e|_2 <= 16 x 2^-23 = 2^-19.  The f32 scalings, in units of 2^-24 of the cosine, as built: |q|^2 -- four fused
+// multiply-adds and the six levels of wave_sum, ten roundings, halved by the root -- 5; its rsqrt 1; u_i = q_i x that 1; x 2^22
+// exact; |c|^2 converts exactly, its rsqrt 1, x 2^-26 exact; the combination 256 A1 + A2 rounds at magnitude <= 2^19 x 16 |c|
+// (|d1|_2, |d2|_2 <= 2^11) against a full scale of 2^22 x 16 |c|, 1/8, and 65536 A0 + that 1; score x rxj 1; 1 - that 1:
+// 11.2 x 2^-24 = 6.7e-7, inside the 1e-6 the batched routes allot to their scalings.  The whole times the project's 1.2:
+// 1.2 x (2^-19 + 1e-6) = 3.49e-6 -- EQUAL to the scan's f32_err_nibble, so what this route leaves unproved the scan cannot prove
+// either: search_wide_host does not run nibble rows again through the scan, they fall to the exhaustive re-answer.
+// DERIVED, not measured; profiles/nibble_batch.json records the largest |d32 - d64| tests/test_gpu_nibble_batch.py saw.
+constexpr double f32_err_batch_nibble = 1.2 * (1.0 / 524288.0 + 1e-6);
+
+// The batched route (batch_nibble.hip): calls of at least tuning key nibble_batch_min queries (0: never) run passes of
+// nibble_batch_qb queries on the int8 MFMA pipe, certified under f32_err_batch_nibble.
+inline bool nibble_batch_serves(const smt_ctx *ctx, const SlabSearch &a)
+{
+    return !a.scan_only && a.row_dtype == SMT_ROWS_I4 && ctx->tune.nibble_batch_min > 0 && a.nq >= (uint32_t)ctx->tune.nibble_batch_min;
+}
+uint32_t nibble_batch_qb();
+int launch_batch_nibble(smt_ctx *ctx, const SlabSearch &a);
+int debug_batch_nibble_lists(smt_ctx *ctx, const SlabSearch &a, key_t64 *out_keys_host, uint64_t out_cap_keys, uint32_t *out_blocks,
+                             uint32_t *out_kp);
+
 // scan_nibble.hip: scan_nibble_kernel<slots, filtered>, launched by launch_search_slab (scan_slab.hip) like the half and byte kernels
 slab_scan_kernel_t nibble_scan_kernel_of(int slots, bool filtered);
 

@@ -208,7 +208,7 @@ int launch_search_slab(smt_ctx *ctx, const SlabSearch &a)
 {
     const bool half = a.row_dtype == SMT_ROWS_F16;   // 512-byte rows of 256 halves: scan_half.hip, eight rows a step
     const bool byte = a.row_dtype == SMT_ROWS_I8;    // 256-byte rows of 256 int8: scan_byte.hip, sixteen rows a step
-    const bool nibble = a.row_dtype == SMT_ROWS_I4;  // 128-byte rows of 256 int4: scan_nibble.hip, thirty-two rows a step, never batched
+    const bool nibble = a.row_dtype == SMT_ROWS_I4;  // 128-byte rows of 256 int4: scan_nibble.hip, thirty-two rows a step
     SMT_REQUIRE(half || byte || nibble ? a.dim == SMT_DIM : dim_is_wide(a.dim), "wide scan: 512, 768 or 1024 dimensions, or half, byte or nibble rows of 256");
     SMT_REQUIRE(a.k_out >= 1 && a.k_out <= SCAN_MAX_K, "wide scan: 1 <= top_k <= 56");
     SMT_REQUIRE(a.rows < 0xFFFFFFFFull, "wide scan: fewer than 2^32 - 1 rows per corpus");
@@ -217,6 +217,7 @@ int launch_search_slab(smt_ctx *ctx, const SlabSearch &a)
         if (slab_batch_serves(ctx, a)) return launch_batch_slab(ctx, a);   // batch_slab.hip
         if (half_batch_serves(ctx, a)) return launch_batch_half(ctx, a);   // batch_half.hip
         if (byte_batch_serves(ctx, a)) return launch_batch_byte(ctx, a);   // batch_byte.hip
+        if (nibble_batch_serves(ctx, a)) return launch_batch_nibble(ctx, a);   // batch_nibble.hip
     }
     const int S = (int)(a.dim / 256);
     const int U = nibble ? NIBBLE_STEP_ROWS : byte ? BYTE_STEP_ROWS : half ? HALF_STEP_ROWS : S == 2 ? 2 : 1;

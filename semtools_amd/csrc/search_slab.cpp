@@ -1,13 +1,13 @@
 // search_slab.cpp -- the search entry points over a WIDE corpus (rows of 512, 768 or 1024 floats) or a HALF corpus (rows of 256
 // binary16 values, half_rows.h: the same calls with the row type handed on) or a BYTE corpus (rows of 256 int8, byte_rows.h: the
-// same again) or a NIBBLE corpus (rows of 256 int4, nibble_rows.h: passes of four queries through scan_nibble.hip, no batched route,
-// so nothing is run a second time through the scan): what smt_search and
+// same again) or a NIBBLE corpus (rows of 256 int4, nibble_rows.h: the same again): what smt_search and
 // smt_search_topk_device[_ex] do before they would reach a 256 kernel.  Served: top-k (1 .. 56) in documents mode without a
 // distance bound, workspace mode with or without one, ranges, row_base, any number of queries in passes of four, or -- from tuning
-// key slab_batch_min (half rows: half_batch_min, byte rows: byte_batch_min) queries on -- in batched passes on the MFMA pipe
-// (batch_slab.hip, batch_half.hip, batch_byte.hip) whose unproved answers the host form runs again through the scan (not for byte
-// rows: their batched bound is the tighter one).  Also the test hooks of those routes (smt_debug_batch_slab_lists,
-// smt_debug_batch_half_lists, smt_debug_batch_byte_lists).  Everything is
+// key slab_batch_min (half rows: half_batch_min, byte rows: byte_batch_min, nibble rows: nibble_batch_min) queries on -- in batched
+// passes on the MFMA pipe (batch_slab.hip, batch_half.hip, batch_byte.hip, batch_nibble.hip) whose unproved answers the host form
+// runs again through the scan (not for byte and nibble rows: their batched bound is not wider than the scan's).  Also the test
+// hooks of those routes (smt_debug_batch_slab_lists, smt_debug_batch_half_lists, smt_debug_batch_byte_lists,
+// smt_debug_batch_nibble_lists).  Everything is
 // enqueued on the context's stream directly: no one-query pipeline, no grouping, no operand image.  Also the two refusals every
 // other entry point answers a wide corpus or model with.
 #include <algorithm>
@@ -180,6 +180,7 @@ int search_wide_host(smt_corpus *corpus, const float *queries, uint32_t nq, uint
     // What the batched route left unproved is first run again, together, through the scan route and its tighter f32_err_slab: the
     // queries move to the front of the stage (ascending, so none is overwritten before it has moved), `redo` then indexes them there.
     // Byte rows are left out: f32_err_batch_byte is UNDER the scan's f32_err_byte (byte_rows.h), the scan could prove no more.
+    // Nibble rows too: f32_err_batch_nibble EQUALS the scan's f32_err_nibble (nibble_rows.h).
     if (batch_route_serves(ctx, a)) {
         const uint32_t nr = (uint32_t)redo.size();
         for (uint32_t i = 0; i < nr; ++i)
@@ -271,22 +272,24 @@ int search_wide_device(smt_corpus *corpus, const float *queries_dev, uint32_t nq
 
 using namespace smt;
 
-// What the three list hooks share: nq host queries and the optional ranges (through the chunk table) onto the stage, then the
-// route's debug_batch_*_lists (batch_slab.hip, batch_half.hip, batch_byte.hip) under the grid the current tuning gives.  `rows`: the
-// element type the hook is for (SMT_ROWS_F32: the wide route).
+// What the four list hooks share: nq host queries and the optional ranges (through the chunk table) onto the stage, then the
+// route's debug_batch_*_lists (batch_slab.hip, batch_half.hip, batch_byte.hip, batch_nibble.hip) under the grid the current tuning
+// gives.  `rows`: the element type the hook is for (SMT_ROWS_F32: the wide route).
 static int debug_batch_lists_staged(smt_corpus *corpus, int rows, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges,
                                     uint32_t n_ranges, uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp)
 {
     SMT_REQUIRE(corpus && queries && out_keys && out_blocks && out_kp, "null argument");
-    const bool half = rows == SMT_ROWS_F16, byte = rows == SMT_ROWS_I8;
-    if (rows_are_nibble(corpus))
-        return refuse_nibble(byte   ? "smt_debug_batch_byte_lists (nibble rows have no batched route)"
-                             : half ? "smt_debug_batch_half_lists (nibble rows have no batched route)"
-                                    : "smt_debug_batch_slab_lists (nibble rows have no batched route)");
+    const bool half = rows == SMT_ROWS_F16, byte = rows == SMT_ROWS_I8, nibble = rows == SMT_ROWS_I4;
+    if (rows_are_nibble(corpus) && !nibble)
+        return refuse_nibble(byte   ? "smt_debug_batch_byte_lists (the batched route of nibble rows has smt_debug_batch_nibble_lists)"
+                             : half ? "smt_debug_batch_half_lists (the batched route of nibble rows has smt_debug_batch_nibble_lists)"
+                                    : "smt_debug_batch_slab_lists (the batched route of nibble rows has smt_debug_batch_nibble_lists)");
     if (rows_are_byte(corpus) && !byte)
-        return refuse_byte(half ? "smt_debug_batch_half_lists (the batched route of byte rows has smt_debug_batch_byte_lists)"
-                                : "smt_debug_batch_slab_lists (the batched route of byte rows has smt_debug_batch_byte_lists)");
-    if (byte) SMT_REQUIRE(rows_are_byte(corpus), "debug batch lists: a byte corpus (SMT_ROWS_I8)");
+        return refuse_byte(nibble ? "smt_debug_batch_nibble_lists (the batched route of byte rows has smt_debug_batch_byte_lists)"
+                           : half ? "smt_debug_batch_half_lists (the batched route of byte rows has smt_debug_batch_byte_lists)"
+                                  : "smt_debug_batch_slab_lists (the batched route of byte rows has smt_debug_batch_byte_lists)");
+    if (nibble) SMT_REQUIRE(rows_are_nibble(corpus), "debug batch lists: a nibble corpus (SMT_ROWS_I4)");
+    else if (byte) SMT_REQUIRE(rows_are_byte(corpus), "debug batch lists: a byte corpus (SMT_ROWS_I8)");
     else if (half) SMT_REQUIRE(rows_are_half(corpus), "debug batch lists: a half corpus (SMT_ROWS_F16)");
     else SMT_REQUIRE(dim_is_wide(corpus->dim), "debug batch lists: a wide corpus (512, 768 or 1024 dimensions)");
     SMT_REQUIRE(top_k >= 1 && top_k <= SCAN_MAX_K, "debug batch lists: top_k in [1, 56]");
@@ -333,7 +336,7 @@ static int debug_batch_lists_staged(smt_corpus *corpus, int rows, const float *q
     a.chunk_table = d_table;
     a.n_chunks = n_chunks;
     a.row_dtype = corpus->row_dtype;
-    rc = (byte ? debug_batch_byte_lists : half ? debug_batch_half_lists : debug_batch_slab_lists)(ctx, a, reinterpret_cast<key_t64 *>(out_keys), out_cap_keys, out_blocks, out_kp);
+    rc = (nibble ? debug_batch_nibble_lists : byte ? debug_batch_byte_lists : half ? debug_batch_half_lists : debug_batch_slab_lists)(ctx, a, reinterpret_cast<key_t64 *>(out_keys), out_cap_keys, out_blocks, out_kp);
     if (rc) (void)hipStreamSynchronize(ctx->stream);   // (the uploads read this frame's vectors)
     return rc;
 }
@@ -359,6 +362,13 @@ int smt_debug_batch_byte_lists(smt_corpus *corpus, const float *queries, uint32_
                                uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp)
 try {
     return debug_batch_lists_staged(corpus, SMT_ROWS_I8, queries, nq, top_k, ranges, n_ranges, out_keys, out_cap_keys, out_blocks, out_kp);
+} catch (...) { return smt::api_catch(); }
+
+// ... and of the batched nibble route (batch_nibble_kernel)
+int smt_debug_batch_nibble_lists(smt_corpus *corpus, const float *queries, uint32_t nq, uint32_t top_k, const smt_range *ranges, uint32_t n_ranges,
+                                 uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp)
+try {
+    return debug_batch_lists_staged(corpus, SMT_ROWS_I4, queries, nq, top_k, ranges, n_ranges, out_keys, out_cap_keys, out_blocks, out_kp);
 } catch (...) { return smt::api_catch(); }
 
 }  // extern "C"
