@@ -464,6 +464,13 @@ int smt_lower_lines(smt_lower *h, const char *text, const uint64_t *line_begin, 
  *            SMT_MODE_DOCUMENTS with max_distance (the threshold kernel); top_k > 56 (the large-k route); smt_corpus_prepack and the
  *            batched MFMA route; smt_corpus_compact; smt_ivfpq_build / smt_ivfpq_load; models with a token mapping or weights;
  *            the sharded corpus and model constructors; the host layer (include/semtools_host.h) and the CLI, which stay 256.
+ *   narrow rows: D = 64 (potion-base-2M), f32 rows of 256 B, four to a 1 KiB load; units of their own (embed_narrow.hip,
+ *            scan_narrow.hip), the finish stage and the entry points are the wide rows'.  D = 128 and 384 stay SMT_E_UNSUPPORTED.
+ *            served: everything the "served" list above names, through the same calls with D = 64 -- plain f32, f16 and int8 tables
+ *            pooled bit-identically, the same exact f64 distances and (distance, row) order, the certificate under the scan's own
+ *            bound (3.8e-6), the exhaustive re-answer in smt_search.  There is no batched route: every call runs passes of four.
+ *            not yet (SMT_E_UNSUPPORTED, the message names 64, nothing is enqueued or changed): the wide rows' list above, the test
+ *            hooks of the 256 kernels and of the batched routes, and D = 64 with a row_dtype other than SMT_ROWS_F32.
  *
  * HALF ROWS.  A corpus made with SMT_ROWS_F16 stores each row as 256 IEEE binary16 values: 512 B, half the bytes of every scan
  * and twice the lines per GPU.  D = 256 only: SMT_ROWS_F16 with a wide D is SMT_E_UNSUPPORTED, an unknown row_dtype SMT_E_INVALID.

@@ -867,7 +867,7 @@ try {
     SMT_REQUIRE(out != nullptr, "out");
     int rc = smt::check_indexed_args(mapping_host, weights_host, n_tokens, n_rows);
     if (rc) return rc;
-    if (dim_is_wide(D) && (mapping_host || weights_host)) return refuse_wide(D, "a model with a token mapping or weights");
+    if (dim_in_family(D) && (mapping_host || weights_host)) return refuse_width(D, "a model with a token mapping or weights");
     smt_model *m = nullptr;
     if ((rc = smt_model_create_typed(ctx, table_host, table_dtype, n_rows, D, normalize, &m))) return rc;
     if ((rc = smt::model_attach_tokens(m, mapping_host, weights_host, n_tokens, false))) { smt_model_destroy(m); return rc; }
@@ -881,7 +881,7 @@ try {
     SMT_REQUIRE(out != nullptr, "out");
     int rc = smt::check_indexed_args(mapping_dev, weights_dev, n_tokens, n_rows);
     if (rc) return rc;
-    if (dim_is_wide(D) && (mapping_dev || weights_dev)) return refuse_wide(D, "a model with a token mapping or weights");
+    if (dim_in_family(D) && (mapping_dev || weights_dev)) return refuse_width(D, "a model with a token mapping or weights");
     smt_model *m = nullptr;
     if ((rc = smt_model_create_from_device_typed(ctx, table_dev, table_dtype, n_rows, D, normalize, &m))) return rc;
     if ((rc = smt::model_attach_tokens(m, mapping_dev, weights_dev, n_tokens, true))) { smt_model_destroy(m); return rc; }
@@ -919,6 +919,7 @@ static int check_row_dtype(int row_dtype, uint32_t D)
         return SMT_E_INVALID;
     }
     if (!dim_supported(D)) return refuse_dim(D);
+    if (row_dtype != SMT_ROWS_F32 && dim_is_narrow(D)) return refuse_narrow("a corpus of half, byte or nibble rows (narrow rows are stored as f32)");
     if (row_dtype == SMT_ROWS_F16 && D != SMT_DIM) return refuse_half("a corpus of half rows wider than 256 dimensions");
     if (row_dtype == SMT_ROWS_I8 && D != SMT_DIM) return refuse_byte("a corpus of byte rows wider than 256 dimensions");
     if (row_dtype == SMT_ROWS_I4 && D != SMT_DIM) return refuse_nibble("a corpus of nibble rows wider than 256 dimensions");
@@ -1090,7 +1091,7 @@ try {
 int smt_corpus_prepack(smt_corpus *c, int enable)
 try {
     SMT_REQUIRE(c != nullptr, "corpus");
-    if (dim_is_wide(c->dim) || rows_are_typed(c)) return refuse_rows(c, "smt_corpus_prepack (the fp16 operand image)");
+    if (dim_in_family(c->dim) || rows_are_typed(c)) return refuse_rows(c, "smt_corpus_prepack (the fp16 operand image)");
     int rc = bind_device(c->ctx);
     if (rc) return rc;
     if (!enable) {
@@ -1113,7 +1114,7 @@ uint64_t smt_corpus_image_bytes(const smt_corpus *c) { return c && c->image ? c-
 int smt_debug_image_tile(smt_corpus *c, uint64_t tile, void *out_tile_host, uint32_t *out_zero_mask)
 try {
     SMT_REQUIRE(c != nullptr && out_tile_host != nullptr && out_zero_mask != nullptr, "null argument");
-    if (rows_are_typed(c)) return refuse_rows(c, "smt_debug_image_tile (the fp16 operand image)");
+    if (rows_are_typed(c) || rows_are_narrow(c)) return refuse_rows(c, "smt_debug_image_tile (the fp16 operand image)");
     int rc = bind_device(c->ctx);
     if (rc) return rc;
     const void *img = nullptr;
@@ -1162,7 +1163,7 @@ try {
 
 int smt_corpus_compact(smt_corpus *c, const smt_range *keep, uint32_t n_keep, uint64_t *rows_moved)
 try {
-    if (c && (dim_is_wide(c->dim) || rows_are_typed(c))) return refuse_rows(c, "smt_corpus_compact");
+    if (c && (dim_in_family(c->dim) || rows_are_typed(c))) return refuse_rows(c, "smt_corpus_compact");
     return corpus_compact(c, keep, n_keep, rows_moved);
 } catch (...) { return smt::api_catch(); }
 
@@ -1185,6 +1186,9 @@ try {
     SMT_REQUIRE(n_lines == 0 || (offsets_dev && out_dev), "null argument");
     int rc = bind_device(model->ctx);
     if (rc) return rc;
+    if (dim_is_narrow(model->D))   // (a narrow model is a plain one: embed_narrow.hip)
+        return launch_embed_narrow(model->ctx, model->d_table, model->table_dtype, model->V, model->normalize, ids_dev, offsets_dev, n_lines,
+                                   max_tokens, out_dev);
     if (dim_is_wide(model->D))   // (a wide model is a plain one: embed_slab.hip)
         return launch_embed_slab(model->ctx, model->d_table, model->table_dtype, model->V, model->D, model->normalize, ids_dev, offsets_dev,
                                  n_lines, max_tokens, out_dev);
@@ -1235,7 +1239,9 @@ try {
         if ((rc = corpus_reserve(append_to, append_to->rows + n_lines))) return rc;
         if (!to_half) d_out = append_to->d_rows + (size_t)append_to->rows * append_to->dim;
     }
-    if (dim_is_wide(model->D))
+    if (dim_is_narrow(model->D))
+        rc = launch_embed_narrow(ctx, model->d_table, model->table_dtype, model->V, model->normalize, d_ids, d_off, n_lines, max_tokens, d_out);
+    else if (dim_is_wide(model->D))
         rc = launch_embed_slab(ctx, model->d_table, model->table_dtype, model->V, model->D, model->normalize, d_ids, d_off, n_lines, max_tokens, d_out);
     else
         rc = launch_embed(ctx, model->d_table, model->table_dtype, model->V, model->normalize, d_ids, d_off, n_lines, max_tokens, d_out,

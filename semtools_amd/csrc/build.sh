@@ -11,12 +11,12 @@ pids=()
 n_cpu="$(nproc)"
 jobs_max="${BUILD_JOBS:-$(( n_cpu < 16 ? n_cpu : 16 ))}"   # min(nproc, 16): the build machines are shared
 newest_hdr="$(ls -t "$here"/*.h "$here"/host/*.h "$here"/../../include/*.h | head -1)"
-for src in api.cpp search.cpp corpus_io.cpp group.cpp group_exchange.cpp sharded_search.cpp sharded.cpp scan_topk.hip scan_pair.hip scan_wide.hip scan_deep.hip scan_launch.hip scan_slab.hip scan_half.hip rows_half.hip scan_byte.hip rows_byte.hip scan_nibble.hip rows_nibble.hip batch_slab.hip batch_half.hip batch_byte.hip batch_nibble.hip finish_slab.hip embed_slab.hip search_slab.cpp select.hip merge.hip range_tables.hip embed_kernels.hip tokenize_kernels.hip wordpiece_kernels.hip wordpiece_utf8_kernels.hip unigram_kernels.hip unigram_utf8_kernels.hip unigram_long_kernels.hip unigram_long_rules_kernels.hip unigram_rules_kernels.hip lower_kernels.hip gemm_topk.hip gemm_rowreg.hip gemm_ldsrow.hip gemm_level.hip largek.hip topk_large.hip compact.hip threshold.hip domain.hip ivfpq_build.hip ivfpq_search.hip ivfpq_io.hip ivfpq_compact.hip host/host.cpp host/store.cpp host/output.cpp host/hf_tokenizer.cpp host/device_tokenize.cpp host/host_capi.cpp; do
+for src in api.cpp search.cpp corpus_io.cpp group.cpp group_exchange.cpp sharded_search.cpp sharded.cpp scan_topk.hip scan_pair.hip scan_wide.hip scan_deep.hip scan_launch.hip scan_slab.hip scan_half.hip rows_half.hip scan_byte.hip rows_byte.hip scan_nibble.hip rows_nibble.hip batch_slab.hip batch_half.hip batch_byte.hip batch_nibble.hip scan_narrow.hip finish_slab.hip embed_slab.hip embed_narrow.hip search_slab.cpp select.hip merge.hip range_tables.hip embed_kernels.hip tokenize_kernels.hip wordpiece_kernels.hip wordpiece_utf8_kernels.hip unigram_kernels.hip unigram_utf8_kernels.hip unigram_long_kernels.hip unigram_long_rules_kernels.hip unigram_rules_kernels.hip lower_kernels.hip gemm_topk.hip gemm_rowreg.hip gemm_ldsrow.hip gemm_level.hip largek.hip topk_large.hip compact.hip threshold.hip domain.hip ivfpq_build.hip ivfpq_search.hip ivfpq_io.hip ivfpq_compact.hip host/host.cpp host/store.cpp host/output.cpp host/hf_tokenizer.cpp host/device_tokenize.cpp host/host_capi.cpp; do
   base="$(basename "${src%.*}")"
   obj="$out/$base.o"
   if [[ ! -f "$obj" || "$here/$src" -nt "$obj" || "$newest_hdr" -nt "$obj" ]]; then
     unit_flags=()
-    case "$src" in *_slab.hip|*_half.hip|*_byte.hip|*_nibble.hip) unit_flags=(-Xclang -target-feature -Xclang -packed-fp32-ops) ;; esac   # the wide-row, half-row, byte-row and nibble-row units: no packed f32 math
+    case "$src" in *_slab.hip|*_narrow.hip|*_half.hip|*_byte.hip|*_nibble.hip) unit_flags=(-Xclang -target-feature -Xclang -packed-fp32-ops) ;; esac   # the wide-row, narrow-row, half-row, byte-row and nibble-row units: no packed f32 math
     "$HIPCC" "${FLAGS[@]}" "${unit_flags[@]}" -x hip -c "$here/$src" -o "$obj" ${EXTRA_HIPCC_FLAGS:-} &
     pids+=($!)
     while (( $(jobs -rp | wc -l) >= jobs_max )); do wait -n || { echo "compile failed" >&2; exit 1; }; done

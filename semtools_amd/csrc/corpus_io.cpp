@@ -568,7 +568,7 @@ try {
     SMT_REQUIRE(out != nullptr, "out");
     int rc = smt::check_indexed_args(mapping_host, weights_host, n_tokens, n_rows);
     if (rc) return rc;
-    if (smt::dim_is_wide(D) && (mapping_host || weights_host)) return smt::refuse_wide(D, "a model with a token mapping or weights");
+    if (smt::dim_in_family(D) && (mapping_host || weights_host)) return smt::refuse_width(D, "a model with a token mapping or weights");
     smt_model *m = nullptr;
     if ((rc = smt_model_create_from_file_typed(ctx, path, byte_offset, table_dtype, n_rows, D, normalize, &m))) return rc;
     if ((rc = smt::model_attach_tokens(m, mapping_host, weights_host, n_tokens, false))) { smt_model_destroy(m); return rc; }

@@ -122,18 +122,47 @@ __global__ void __launch_bounds__(256) rows_domain_slab_kernel(const float *rows
     }
 }
 
+// NARROW rows (64 floats): a wave load covers four rows, lane l float4 number l % 16 of row 4 w + l / 16 -- the scan's layout
+// (scan_narrow.hip) -- and the magnitudes meet inside the row's own 16 lanes only.  Lanes whose row does not exist read the last row.
+__global__ void __launch_bounds__(256) rows_domain_narrow_kernel(const float *rows, uint64_t n_rows, unsigned long long *out /* [count, first] */)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    for (uint64_t r0 = wave * 4; r0 < n_rows; r0 += n_waves * 4) {
+        const uint64_t r = r0 + (uint64_t)(lane >> 4);
+        const bool have = r < n_rows;
+        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(rows + (have ? r : n_rows - 1) * 64) + (lane & 15));
+        uint32_t m = max(max(v.x & 0x7fffffffu, v.y & 0x7fffffffu), max(v.z & 0x7fffffffu, v.w & 0x7fffffffu));
+        m = max(m, dpp_u<DPP_XOR1>(m));
+        m = max(m, dpp_u<DPP_XOR2>(m));
+        m = max(m, dpp_u<DPP_HALF_MIRROR>(m));
+        m = max(m, dpp_u<DPP_MIRROR>(m));
+        if (have && (lane & 15) == 0 && !magnitude_in_domain(m)) {
+            atomicAdd(out, 1ull);
+            atomicMin(out + 1, (unsigned long long)r);
+        }
+    }
+}
+
 int check_rows_domain_dim(smt_ctx *ctx, const float *d_rows, uint64_t n_rows, uint32_t dim, uint64_t *n_bad, uint64_t *first_bad)
 {
     if (dim == SMT_DIM) return check_rows_domain(ctx, d_rows, n_rows, n_bad, first_bad);
     *n_bad = 0;
     *first_bad = ~0ull;
     if (n_rows == 0) return SMT_OK;
-    SMT_REQUIRE(dim_is_wide(dim), "rows of 256, 512, 768 or 1024 floats");
+    SMT_REQUIRE(dim_in_family(dim), "rows of 64, 256, 512, 768 or 1024 floats");
     unsigned long long init[2] = {0ull, ~0ull}, got[2] = {0ull, ~0ull};
     unsigned long long *d = ctx->d_status + 2;
     SMT_HIP_CHECK(hipMemcpyAsync(d, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
-    const int blocks = (int)std::min<uint64_t>((n_rows + 3) / 4, (uint64_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) * 8);
-    hipLaunchKernelGGL(rows_domain_slab_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_rows, n_rows, dim / 256, d);
+    if (dim_is_narrow(dim)) {
+        const int blocks = (int)std::min<uint64_t>((n_rows + 15) / 16, (uint64_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) * 8);
+        hipLaunchKernelGGL(rows_domain_narrow_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_rows, n_rows, d);
+    } else {
+        const int blocks = (int)std::min<uint64_t>((n_rows + 3) / 4, (uint64_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) * 8);
+        hipLaunchKernelGGL(rows_domain_slab_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_rows, n_rows, dim / 256, d);
+    }
     SMT_HIP_CHECK(hipGetLastError());
     SMT_HIP_CHECK(hipMemcpyAsync(got, d, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
     SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));

@@ -163,14 +163,8 @@ static void launch_embed_slab_typed(int S, unsigned blocks, hipStream_t st, cons
     else hipLaunchKernelGGL((embed_slab_kernel<T, 4>), dim3(blocks), dim3(256), 0, st, p);
 }
 
-int launch_embed_slab(smt_ctx *ctx, const void *table, int table_dtype, uint64_t V, uint32_t D, int normalize, const uint32_t *ids,
-                      const uint64_t *offsets, uint64_t n_lines, uint32_t max_tokens, float *out)
+int launch_embed_runs(smt_ctx *ctx, const uint64_t *offsets, uint64_t n_lines, uint64_t groups)
 {
-    if (n_lines == 0) return SMT_OK;
-    SMT_REQUIRE(dim_is_wide(D), "wide embed: 512, 768 or 1024 dimensions");
-    SMT_REQUIRE(table_dtype == SMT_TABLE_F32 || table_dtype == SMT_TABLE_F16 || table_dtype == SMT_TABLE_I8, "unknown table dtype");
-    // enough groups to fill the chip (16 waves x 4 groups per CU), never more than lines
-    const uint64_t groups = std::min<uint64_t>(n_lines, (uint64_t)std::max(ctx->num_cus, 1) * 64);
     if (ctx->embed_runs_cap < groups + 1) {
         SMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         if (ctx->d_embed_runs) SMT_HIP_CHECK(hipFree(ctx->d_embed_runs));
@@ -179,6 +173,22 @@ int launch_embed_slab(smt_ctx *ctx, const void *table, int table_dtype, uint64_t
         SMT_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&ctx->d_embed_runs), (groups + 1) * sizeof(uint64_t)));
         ctx->embed_runs_cap = groups + 1;
     }
+    hipLaunchKernelGGL(embed_slab_runs_kernel, dim3((unsigned)((groups + 1 + 255) / 256)), dim3(256), 0, ctx->stream, offsets, n_lines, groups,
+                       ctx->d_embed_runs);
+    SMT_HIP_CHECK(hipGetLastError());
+    return SMT_OK;
+}
+
+int launch_embed_slab(smt_ctx *ctx, const void *table, int table_dtype, uint64_t V, uint32_t D, int normalize, const uint32_t *ids,
+                      const uint64_t *offsets, uint64_t n_lines, uint32_t max_tokens, float *out)
+{
+    if (n_lines == 0) return SMT_OK;
+    SMT_REQUIRE(dim_is_wide(D), "wide embed: 512, 768 or 1024 dimensions");
+    SMT_REQUIRE(table_dtype == SMT_TABLE_F32 || table_dtype == SMT_TABLE_F16 || table_dtype == SMT_TABLE_I8, "unknown table dtype");
+    // enough groups to fill the chip (16 waves x 4 groups per CU), never more than lines
+    const uint64_t groups = std::min<uint64_t>(n_lines, (uint64_t)std::max(ctx->num_cus, 1) * 64);
+    const int rc = launch_embed_runs(ctx, offsets, n_lines, groups);   // (may move ctx->d_embed_runs: before it is read below)
+    if (rc) return rc;
     EmbedSlabParams p;
     p.table = static_cast<const unsigned char *>(table);
     p.V = V;
@@ -193,8 +203,6 @@ int launch_embed_slab(smt_ctx *ctx, const void *table, int table_dtype, uint64_t
     const unsigned blocks = (unsigned)((groups + 15) / 16);   // 256 threads = 16 groups
     const int S = (int)(D / 256);
     prof_begin(ctx, "embed_slab");
-    hipLaunchKernelGGL(embed_slab_runs_kernel, dim3((unsigned)((groups + 1 + 255) / 256)), dim3(256), 0, ctx->stream, offsets, n_lines, groups,
-                       ctx->d_embed_runs);
     if (table_dtype == SMT_TABLE_F16) launch_embed_slab_typed<_Float16>(S, blocks, ctx->stream, p);
     else if (table_dtype == SMT_TABLE_I8) launch_embed_slab_typed<signed char>(S, blocks, ctx->stream, p);
     else launch_embed_slab_typed<float>(S, blocks, ctx->stream, p);

@@ -1,23 +1,23 @@
 // finish_slab.hip -- the finish stage of a WIDE scan (scan_slab.hip) and the exhaustive re-answer's kernel.
 //
-// finish_slab_kernel<S>, one block per query: merges the query's block lists, recomputes every surviving candidate's distance in f64
-// in index order over all D = 256 S components (simsimd's accurate form, oracle cosine_accurate), orders by (f64 distance, row),
+// finish_slab_kernel<D, RowT>, one block per query: merges the query's block lists, recomputes every surviving candidate's distance in f64
+// in index order over all D components (D = 256 S, or 64: narrow rows, scan_narrow.hip, certified under f32_err_narrow) (simsimd's accurate form, oracle cosine_accurate), orders by (f64 distance, row),
 // writes rows (+ row_base), distances, the count and the status word.
 //
 // MERGE.  The lists are sorted and their keys distinct, so the k'-th smallest of the lists' HEADS bounds the union's k'-th smallest
 // key from above once k' lists are non-empty (k' lists hold a key that small).  Exactly k' lists then start at or under it, each
 // with at most k' keys: at most k'^2 <= 4096 survivors, fewer lists than k' hold fewer keys than that in all.  The survivors are
 // sorted in LDS (bitonic) and the first k' kept.
-// RESCORE.  Candidate rows are staged in LDS a tile at a time (32 / S rows of 256 S floats, one wave per row, coalesced); one thread
+// RESCORE.  Candidate rows are staged in LDS a tile at a time (min(16, 8192 / D) rows of D floats, one wave per row, coalesced); one thread
 // per candidate and sum then runs the D dependent f64 adds from LDS: <q, c> in wave 0, <c, c> in wave 1, <q, q> once in wave 2.
 // The product of two f32 values is exact in f64, so a fused multiply-add rounds like the oracle's multiply and add.
 // CERTIFICATE.  As select.hip's: when k' keys were nominated, a row outside them has scan distance >= the k'-th key's, hence exact
 // distance >= that - f32_err_slab(S) (wide_rows.h); the answer is PROVED when the k_out-th exact distance lies under that floor.
 // Fewer than k' nominated keys are all the rows there are: proved.  A query outside the domain: SMT_STATUS_INVALID_QUERY.
-// HALF rows (half_rows.h) come here as <1, _Float16>: the row read widens the stored halves -- exactly, in integer arithmetic -- on
+// HALF rows (half_rows.h) come here as <256, _Float16>: the row read widens the stored halves -- exactly, in integer arithmetic -- on
 // their way into LDS or the sums, everything behind it is the f32 code; the bound is f32_err_half.  BYTE rows (byte_rows.h) come
-// as <1, int8_t>: sign extension and an integer conversion, exact as well; the bound is f32_err_byte.  NIBBLE rows (nibble_rows.h)
-// come as <1, nibble_t>: four components are two bytes, a shift pair sign-extends each nibble, an integer conversion follows --
+// as <256, int8_t>: sign extension and an integer conversion, exact as well; the bound is f32_err_byte.  NIBBLE rows (nibble_rows.h)
+// come as <256, nibble_t>: four components are two bytes, a shift pair sign-extends each nibble, an integer conversion follows --
 // exact again; the bound is f32_err_nibble.
 #include <type_traits>
 
@@ -77,11 +77,11 @@ __device__ __forceinline__ f32x4 row_quad(const float *rows, uint64_t row, uint3
     }
 }
 
-template <int S, typename RowT>
+template <int D, typename RowT>
 __global__ void __launch_bounds__(FIN_THREADS) finish_slab_kernel(SlabFinishParams p)
 {
-    constexpr int D = 256 * S;
-    constexpr int TB = 32 / S < FIN_THREADS / 64 ? 32 / S : FIN_THREADS / 64;   // candidate rows staged per tile
+    static_assert(D == 64 || (D % 256 == 0 && D <= 1024), "64 floats (narrow rows) or 1 .. 4 slabs of 256");
+    constexpr int TB = 8192 / D < FIN_THREADS / 64 ? 8192 / D : FIN_THREADS / 64;   // candidate rows staged per tile
     constexpr int RS = D / 4 + 1;         // LDS row stride in float4: neighbouring rows start 16 bytes apart in the banks
     static_assert(TB <= FIN_THREADS / 64 && (size_t)TB * RS * 16 <= (size_t)FIN_SURV_CAP * 8 + 1024, "a wave per staged row; tiles share the survivors' space");
     extern __shared__ __align__(16) unsigned char fin_smem[];
@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(FIN_THREADS) finish_slab_kernel(SlabFinishPara
         if (wave < TB && tile0 + wave < kp && s_best[tile0 + wave] != KEY_PAD) {
             const uint32_t row = (uint32_t)(s_best[tile0 + wave] & 0xFFFFFFFFull);
 #pragma unroll
-            for (int s = 0; s < S; ++s) s_rows[wave * RS + s * 64 + lane] = row_quad<RowT>(p.corpus, row, D, s * 64 + lane);
+            for (int e = lane; e < D / 4; e += 64) s_rows[wave * RS + e] = row_quad<RowT>(p.corpus, row, D, e);   // (a narrow row: lanes 0 .. 15)
         }
         __syncthreads();
         const f32x4 *q4 = reinterpret_cast<const f32x4 *>(s_q);
@@ -261,16 +261,18 @@ int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, 
     p.out_counts = a.out_counts ? a.out_counts + first_query : nullptr;
     p.out_status = a.out_status ? a.out_status + first_query : nullptr;
     const int S = (int)(a.dim / 256);
-    p.f32_err = f32_err > 0.0 ? f32_err : nibble ? f32_err_nibble : byte ? f32_err_byte : half ? f32_err_half : S == 2 ? f32_err_slab(2) : S == 3 ? f32_err_slab(3) : f32_err_slab(4);
+    const bool narrow = dim_is_narrow(a.dim);
+    p.f32_err = f32_err > 0.0 ? f32_err : nibble ? f32_err_nibble : byte ? f32_err_byte : half ? f32_err_half : narrow ? f32_err_narrow : S == 2 ? f32_err_slab(2) : S == 3 ? f32_err_slab(3) : f32_err_slab(4);
     p.sticky = ctx->d_status;
     const size_t smem = finish_smem_bytes(a.dim);
     prof_begin(ctx, "finish_slab");
-    if (nibble) hipLaunchKernelGGL((finish_slab_kernel<1, nibble_t>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
-    else if (byte) hipLaunchKernelGGL((finish_slab_kernel<1, int8_t>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
-    else if (half) hipLaunchKernelGGL((finish_slab_kernel<1, _Float16>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
-    else if (S == 2) hipLaunchKernelGGL((finish_slab_kernel<2, float>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
-    else if (S == 3) hipLaunchKernelGGL((finish_slab_kernel<3, float>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
-    else hipLaunchKernelGGL((finish_slab_kernel<4, float>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
+    if (nibble) hipLaunchKernelGGL((finish_slab_kernel<256, nibble_t>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
+    else if (byte) hipLaunchKernelGGL((finish_slab_kernel<256, int8_t>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
+    else if (half) hipLaunchKernelGGL((finish_slab_kernel<256, _Float16>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
+    else if (narrow) hipLaunchKernelGGL((finish_slab_kernel<64, float>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
+    else if (S == 2) hipLaunchKernelGGL((finish_slab_kernel<512, float>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
+    else if (S == 3) hipLaunchKernelGGL((finish_slab_kernel<768, float>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
+    else hipLaunchKernelGGL((finish_slab_kernel<1024, float>), dim3(nq_pass), dim3(FIN_THREADS), smem, ctx->stream, p);
     prof_end(ctx, "finish_slab");
     SMT_HIP_CHECK(hipGetLastError());
     return SMT_OK;
@@ -279,6 +281,54 @@ int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, 
 // The exhaustive re-answer (search_slab.cpp): the exact f64 distance of EVERY allowed row, one thread per row walking its D components
 // in index order; the host then selects by (distance, row).  Slow (a thread's loads are its own row's: nothing coalesces), rare --
 // only a query whose certificate failed comes here -- and correct.
+// NARROW rows: the same sums, but a thread that walked its own 256-byte row would make a wave touch 64 rows 16 B at a time.  Here a
+// wave load reads 1 KiB -- RPL = four rows (resp. the rows of one chunk-table entry), lane l float4 number l % 16 of row l / 16, the
+// scan's geometry -- into LDS, a block stages its 128 slots so, and thread t then walks slot t's 64 components from LDS in index
+// order.  Slot i is what it is in exact_all_slab_kernel; rows that do not exist are read as a row that does and not written.
+template <int RPL>
+__global__ void __launch_bounds__(128) exact_all_narrow_kernel(const float *corpus, uint64_t n_rows, const float *query,
+                                                               const uint64_t *chunk_table, uint64_t n_chunks, double *out)
+{
+    static_assert(RPL == 4 && FILTER_CHUNK == RPL, "four rows per 1 KiB load; a chunk-table entry is one load");
+    constexpr int D = 256 / RPL, LPR = 64 / RPL, SLOTS = 128, RS = D / 4 + 1;   // (stride 17 float4: neighbouring slots 16 B apart in the banks)
+    __shared__ f32x4 s_rows[SLOTS * RS];
+    __shared__ f32x4 s_q[D / 4];
+    __shared__ unsigned char s_ok[SLOTS];
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, grp = lane / LPR, sub = lane % LPR;
+    if (t < D / 4) s_q[t] = reinterpret_cast<const f32x4 *>(query)[t];
+    const uint64_t slot0 = (uint64_t)blockIdx.x * SLOTS;
+    for (int l = wave; l < SLOTS / RPL; l += 2) {   // load l of the block: slots 4 l .. 4 l + 3
+        const uint64_t i = slot0 + (uint64_t)l * RPL + grp;
+        uint64_t row = 0;
+        bool ok;
+        if (chunk_table) {
+            const uint64_t c = i / FILTER_CHUNK;
+            const uint64_t desc = c < n_chunks ? chunk_table[c] : 0ull;
+            ok = (uint32_t)grp < (uint32_t)(desc >> 32);
+            row = (desc & 0xFFFFFFFFull) + (ok ? grp : 0);
+        } else {
+            ok = i < n_rows;
+            row = ok ? i : n_rows - 1;
+        }
+        s_rows[(l * RPL + grp) * RS + sub] = reinterpret_cast<const f32x4 *>(corpus + row * D)[sub];
+        if (sub == 0) s_ok[l * RPL + grp] = ok ? 1 : 0;
+    }
+    __syncthreads();
+    if (!s_ok[t]) return;
+    const f32x4 *r4 = s_rows + t * RS;
+    double ab = 0.0, a2 = 0.0, b2 = 0.0;
+#pragma unroll 4
+    for (int e = 0; e < D / 4; ++e) {
+        const f32x4 a = s_q[e], b = r4[e];
+        const double ax = a.x, ay = a.y, az = a.z, aw = a.w, bx = b.x, by = b.y, bz = b.z, bw = b.w;
+        ab = ab + ax * bx; a2 = a2 + ax * ax; b2 = b2 + bx * bx;
+        ab = ab + ay * by; a2 = a2 + ay * ay; b2 = b2 + by * by;
+        ab = ab + az * bz; a2 = a2 + az * az; b2 = b2 + bz * bz;
+        ab = ab + aw * bw; a2 = a2 + aw * aw; b2 = b2 + bw * bw;
+    }
+    out[slot0 + t] = cos_finish_exact(ab, a2, b2);
+}
+
 template <typename RowT>
 __global__ void __launch_bounds__(256) exact_all_slab_kernel(const float *corpus, uint64_t n_rows, uint32_t dim, const float *query,
                                                              const uint64_t *chunk_table, uint64_t n_chunks, double *out)
@@ -317,9 +367,18 @@ int launch_exact_all_slab(smt_ctx *ctx, const float *corpus, int row_dtype, uint
                           const uint64_t *chunk_table, uint64_t n_chunks, double *out)
 {
     const bool half = row_dtype == SMT_ROWS_F16, byte = row_dtype == SMT_ROWS_I8, nibble = row_dtype == SMT_ROWS_I4;
-    SMT_REQUIRE(half || byte || nibble ? dim == SMT_DIM : dim_is_wide(dim), "wide rows: 512, 768 or 1024 dimensions, or half, byte or nibble rows of 256");
+    SMT_REQUIRE(half || byte || nibble ? dim == SMT_DIM : dim_in_family(dim), "wide rows: 64, 512, 768 or 1024 dimensions, or half, byte or nibble rows of 256");
     const uint64_t n = chunk_table ? n_chunks * FILTER_CHUNK : rows;
     if (n == 0) return SMT_OK;
+    if (dim_is_narrow(dim) && !(half || byte || nibble)) {
+        const uint64_t nb = (n + 127) / 128;
+        SMT_REQUIRE(nb < (1ull << 31), "too many rows for one exhaustive launch");
+        prof_begin(ctx, "exact_narrow");
+        hipLaunchKernelGGL(exact_all_narrow_kernel<4>, dim3((unsigned)nb), dim3(128), 0, ctx->stream, corpus, rows, query, chunk_table, n_chunks, out);
+        prof_end(ctx, "exact_narrow");
+        SMT_HIP_CHECK(hipGetLastError());
+        return SMT_OK;
+    }
     const uint64_t blocks = (n + 255) / 256;
     SMT_REQUIRE(blocks < (1ull << 31), "too many rows for one exhaustive launch");
     prof_begin(ctx, "exact_slab");

@@ -536,7 +536,7 @@ extern "C" {
 
 int smt_ivfpq_build(smt_corpus *corpus, const smt_ivfpq_params *prm, smt_ivfpq **out)
 try {
-    if (corpus && (smt::dim_is_wide(corpus->dim) || corpus->row_dtype != SMT_ROWS_F32)) return smt::refuse_rows(corpus, "smt_ivfpq_build (the approximate index)");
+    if (corpus && (smt::dim_in_family(corpus->dim) || corpus->row_dtype != SMT_ROWS_F32)) return smt::refuse_rows(corpus, "smt_ivfpq_build (the approximate index)");
     return smt::ivfpq_build_shared(corpus, prm, nullptr, out);
 } catch (...) { return smt::api_catch(); }
 

@@ -149,7 +149,7 @@ int smt_ivfpq_load(smt_corpus *corpus, const char *path, smt_ivfpq **out)
 try {
     SMT_REQUIRE(corpus && path && out, "null argument");
     *out = nullptr;
-    if (smt::dim_is_wide(corpus->dim) || corpus->row_dtype != SMT_ROWS_F32) return smt::refuse_rows(corpus, "smt_ivfpq_load (the approximate index)");
+    if (smt::dim_in_family(corpus->dim) || corpus->row_dtype != SMT_ROWS_F32) return smt::refuse_rows(corpus, "smt_ivfpq_load (the approximate index)");
     smt_ctx *ctx = corpus->ctx;
     IVF_HIP(hipSetDevice(ctx->device));
     { int rc_drain = smt::drain_async(ctx); if (rc_drain) return rc_drain; }

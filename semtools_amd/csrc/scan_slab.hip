@@ -1,5 +1,6 @@
 // scan_slab.hip -- K2 for WIDE rows: scan_slab_kernel<S, NQ, FILTERED>, rows of D = 256 S floats (S = 2, 3, 4 slabs of 1 KiB)
-// against 1 or up to 4 queries, and the launch of a call's passes (scan + finish_slab.hip).  D = 256 never comes here.
+// against 1 or up to 4 queries, and the launch of a call's passes (scan + finish_slab.hip).  D = 256 never comes here; D = 64
+// comes to the launch only (its kernel: scan_narrow.hip).
 //
 // LAYOUT.  A wave owns a row.  Lane l holds float4 number l of EVERY slab -- row[s * 64 + l], s = 0 .. S - 1 -- so each of the
 // S load instructions of a row still reads 1 KiB contiguous, as the 256 kernel's one load does.  The queries sit in registers in
@@ -209,7 +210,8 @@ int launch_search_slab(smt_ctx *ctx, const SlabSearch &a)
     const bool half = a.row_dtype == SMT_ROWS_F16;   // 512-byte rows of 256 halves: scan_half.hip, eight rows a step
     const bool byte = a.row_dtype == SMT_ROWS_I8;    // 256-byte rows of 256 int8: scan_byte.hip, sixteen rows a step
     const bool nibble = a.row_dtype == SMT_ROWS_I4;  // 128-byte rows of 256 int4: scan_nibble.hip, thirty-two rows a step
-    SMT_REQUIRE(half || byte || nibble ? a.dim == SMT_DIM : dim_is_wide(a.dim), "wide scan: 512, 768 or 1024 dimensions, or half, byte or nibble rows of 256");
+    const bool narrow = dim_is_narrow(a.dim);        // 256-byte rows of 64 floats: scan_narrow.hip, sixteen rows a step
+    SMT_REQUIRE(half || byte || nibble ? a.dim == SMT_DIM : dim_in_family(a.dim), "wide scan: 64, 512, 768 or 1024 dimensions, or half, byte or nibble rows of 256");
     SMT_REQUIRE(a.k_out >= 1 && a.k_out <= SCAN_MAX_K, "wide scan: 1 <= top_k <= 56");
     SMT_REQUIRE(a.rows < 0xFFFFFFFFull, "wide scan: fewer than 2^32 - 1 rows per corpus");
     SMT_REQUIRE(a.nq >= 1 && a.queries && a.out_rows && a.out_dist, "wide scan: null argument");
@@ -220,12 +222,13 @@ int launch_search_slab(smt_ctx *ctx, const SlabSearch &a)
         if (nibble_batch_serves(ctx, a)) return launch_batch_nibble(ctx, a);   // batch_nibble.hip
     }
     const int S = (int)(a.dim / 256);
-    const int U = nibble ? NIBBLE_STEP_ROWS : byte ? BYTE_STEP_ROWS : half ? HALF_STEP_ROWS : S == 2 ? 2 : 1;
+    const int U = nibble ? NIBBLE_STEP_ROWS : byte ? BYTE_STEP_ROWS : half ? HALF_STEP_ROWS : narrow ? NARROW_STEP_ROWS : S == 2 ? 2 : 1;
     const bool filtered = a.chunk_table != nullptr;
     const uint64_t n_steps = !filtered ? (a.rows + U - 1) / U
                              : nibble  ? (a.n_chunks + NIBBLE_STEP_ROWS / FILTER_CHUNK - 1) / (NIBBLE_STEP_ROWS / FILTER_CHUNK)
                              : byte    ? (a.n_chunks + BYTE_STEP_ROWS / FILTER_CHUNK - 1) / (BYTE_STEP_ROWS / FILTER_CHUNK)
                              : half    ? (a.n_chunks + HALF_STEP_ROWS / FILTER_CHUNK - 1) / (HALF_STEP_ROWS / FILTER_CHUNK)
+                             : narrow  ? (a.n_chunks + NARROW_STEP_ROWS / FILTER_CHUNK - 1) / (NARROW_STEP_ROWS / FILTER_CHUNK)
                                        : a.n_chunks * (uint64_t)(FILTER_CHUNK / U);
     const uint32_t kp = std::min<uint32_t>(64, a.k_out + (uint32_t)ctx->tune.guard_band);
     const int waves = SLAB_THREADS / 64;
@@ -251,10 +254,11 @@ int launch_search_slab(smt_ctx *ctx, const SlabSearch &a)
         const slab_scan_kernel_t kernel = nibble ? nibble_scan_kernel_of(slots, filtered)
                                         : byte   ? byte_scan_kernel_of(slots, filtered)
                                         : half   ? half_scan_kernel_of(slots, filtered)
+                                        : narrow ? narrow_scan_kernel_of(slots, filtered)
                                         : S == 2 ? slab_scan_kernel_of<2>(slots, filtered)
                                         : S == 3 ? slab_scan_kernel_of<3>(slots, filtered) : slab_scan_kernel_of<4>(slots, filtered);
         const size_t smem = slab_list_smem_bytes(slots, waves);
-        const char *prof_name = nibble ? "scan_nibble" : byte ? "scan_byte" : half ? "scan_half" : "scan_slab";
+        const char *prof_name = nibble ? "scan_nibble" : byte ? "scan_byte" : half ? "scan_half" : narrow ? "scan_narrow" : "scan_slab";
         prof_begin(ctx, prof_name);
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(SLAB_THREADS), smem, ctx->stream, p);
         prof_end(ctx, prof_name);

@@ -783,7 +783,7 @@ int search_local_host(smt_corpus *corpus, const float *queries, uint32_t nq, uin
                       const smt_range *ranges, uint32_t n_ranges, uint64_t row_base, std::vector<LocalHits> &out)
 {
     // a wide corpus takes its own route at the top and never reaches a 256 kernel (search_slab.cpp)
-    if (corpus && (dim_is_wide(corpus->dim) || rows_are_typed(corpus))) return search_wide_host(corpus, queries, nq, top_k, max_distance, mode, ranges, n_ranges, row_base, out);
+    if (corpus && (dim_in_family(corpus->dim) || rows_are_typed(corpus))) return search_wide_host(corpus, queries, nq, top_k, max_distance, mode, ranges, n_ranges, row_base, out);
     if (mode != SMT_MODE_WORKSPACE || !queries || nq == 0)
         return search_local_host_impl(corpus, queries, nq, top_k, max_distance, mode, ranges, n_ranges, row_base, out);
     // workspace mode: zero queries never reach the GPU (every row ties at distance 1.0: the kernels would flag the answer uncertain
@@ -845,7 +845,7 @@ int search_topk_packed_local(smt_corpus *corpus, const float *queries_dev, uint3
                              uint64_t row_base, uint64_t *packed_dev, uint64_t *uncertain_dev, bool allow_async)
 {
     SMT_REQUIRE(corpus && queries_dev && packed_dev, "null argument");
-    if (dim_is_wide(corpus->dim) || rows_are_typed(corpus)) return refuse_rows(corpus, "the sharded exchange path");
+    if (dim_in_family(corpus->dim) || rows_are_typed(corpus)) return refuse_rows(corpus, "the sharded exchange path");
     smt_ctx *ctx = corpus->ctx;
     SMT_REQUIRE(k_pad >= 1 && k_pad <= (ctx->tune.largek_sampled ? LARGEK_MAX_K : SCAN_MAX_K),
                 ctx->tune.largek_sampled ? "top_k of the device exchange path must be in [1, 1024]"
@@ -956,7 +956,7 @@ int smt_debug_batched_scores(smt_corpus *corpus, const float *queries, uint32_t 
                              float *out)
 try {
     SMT_REQUIRE(corpus && queries && out, "null argument");
-    if (rows_are_typed(corpus)) return refuse_rows(corpus, "smt_debug_batched_scores");
+    if (rows_are_typed(corpus) || rows_are_narrow(corpus)) return refuse_rows(corpus, "smt_debug_batched_scores");
     SMT_REQUIRE(first_row + n_rows <= corpus->rows, "row range outside the corpus");
     smt_ctx *ctx = corpus->ctx;
     int rc = bind_device(ctx, true);
@@ -1009,7 +1009,7 @@ static int debug_nominations(smt_corpus *corpus, const float *queries, uint32_t 
                              uint32_t *out_counts, uint32_t *out_route)
 {
     SMT_REQUIRE(corpus && queries && tau && out_dist && out_hits && out_counts && out_route, "null argument");
-    if (rows_are_typed(corpus)) return refuse_rows(corpus, "smt_debug_nominations (the K3 test hooks)");
+    if (rows_are_typed(corpus) || rows_are_narrow(corpus)) return refuse_rows(corpus, "smt_debug_nominations (the K3 test hooks)");
     SMT_REQUIRE(n_ranges == 0 || ranges != nullptr, "ranges");
     SMT_REQUIRE(nq >= 1 && nq <= 64, "debug nominations: 1..64 queries");
     smt_ctx *ctx = corpus->ctx;
@@ -1072,7 +1072,7 @@ int smt_debug_bootstrap_minima(smt_corpus *corpus, const float *queries, uint32_
                                uint32_t n_ranges, float *out_tile_min, uint32_t *out_slots, uint64_t *out_stride, uint32_t *out_route)
 try {
     SMT_REQUIRE(corpus && queries && out_tile_min && out_slots && out_stride && out_route, "null argument");
-    if (rows_are_typed(corpus)) return refuse_rows(corpus, "smt_debug_bootstrap_minima");
+    if (rows_are_typed(corpus) || rows_are_narrow(corpus)) return refuse_rows(corpus, "smt_debug_bootstrap_minima");
     SMT_REQUIRE(n_ranges == 0 || ranges != nullptr, "ranges");
     SMT_REQUIRE(nq >= 1 && nq <= 64, "debug bootstrap: 1..64 queries");
     smt_ctx *ctx = corpus->ctx;
@@ -1250,7 +1250,7 @@ int smt_debug_select_lists(smt_corpus *corpus, const float *queries_dev, uint32_
                            uint64_t *out_counts_dev, uint64_t *out_uncertain_dev, uint32_t *out_status_dev)
 try {
     SMT_REQUIRE(corpus != nullptr, "corpus");
-    if (rows_are_typed(corpus)) return refuse_rows(corpus, "smt_debug_select_lists");
+    if (rows_are_typed(corpus) || rows_are_narrow(corpus)) return refuse_rows(corpus, "smt_debug_select_lists");
     SMT_REQUIRE(nq == 0 || (queries_dev && lists_dev && out_rows_dev && out_dist_dev), "null argument");
     SMT_REQUIRE(list_stride == 0 || list_stride >= (uint64_t)n_lists * kp, "the list stride is shorter than a query's lists");
     SMT_REQUIRE(out_stride == 0 || out_stride >= k_out, "the output stride is shorter than an output list");
@@ -1288,7 +1288,7 @@ int smt_debug_scan_lists(smt_corpus *corpus, const float *queries, uint32_t nq, 
                          uint64_t *out_keys, uint64_t out_cap_keys, uint32_t *out_blocks, uint32_t *out_kp, uint32_t *out_route)
 try {
     SMT_REQUIRE(corpus && queries && out_keys && out_blocks && out_kp && out_route, "null argument");
-    if (rows_are_typed(corpus)) return refuse_rows(corpus, "smt_debug_scan_lists");
+    if (rows_are_typed(corpus) || rows_are_narrow(corpus)) return refuse_rows(corpus, "smt_debug_scan_lists");
     SMT_REQUIRE(n_ranges == 0 || ranges != nullptr, "ranges");
     SMT_REQUIRE(nq >= 1 && nq <= 8, "debug scan lists: 1..8 queries");
     SMT_REQUIRE(top_k >= 1 && top_k <= SCAN_MAX_K, "debug scan lists: top_k in [1, 56]");

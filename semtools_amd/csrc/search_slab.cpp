@@ -1,4 +1,5 @@
-// search_slab.cpp -- the search entry points over a WIDE corpus (rows of 512, 768 or 1024 floats) or a HALF corpus (rows of 256
+// search_slab.cpp -- the search entry points over a WIDE corpus (rows of 512, 768 or 1024 floats) or a NARROW one (rows of 64
+// floats, scan_narrow.hip: the same calls, no batched route) or a HALF corpus (rows of 256
 // binary16 values, half_rows.h: the same calls with the row type handed on) or a BYTE corpus (rows of 256 int8, byte_rows.h: the
 // same again) or a NIBBLE corpus (rows of 256 int4, nibble_rows.h: the same again): what smt_search and
 // smt_search_topk_device[_ex] do before they would reach a 256 kernel.  Served: top-k (1 .. 56) in documents mode without a
@@ -21,7 +22,7 @@ namespace smt {
 
 int refuse_dim(uint32_t D)
 {
-    set_error("embedding dim %u unsupported (kernels are specialised for 256; wide rows: 512, 768, 1024)", D);
+    set_error("embedding dim %u unsupported (kernels are specialised for 256; wide rows: 512, 768, 1024; narrow rows: 64)", D);
     return SMT_E_UNSUPPORTED;
 }
 
@@ -29,6 +30,13 @@ int refuse_wide(uint32_t D, const char *what)
 {
     set_error("%s: not served for %u-dimensional rows yet (wide rows: top-k searches up to 56, ranges, workspace mode; everything else is 256 only)",
               what, D);
+    return SMT_E_UNSUPPORTED;
+}
+
+int refuse_narrow(const char *what)
+{
+    set_error("%s: not served for 64-dimensional rows yet (narrow rows: f32 rows, plain models, append, write, read, truncate, save, "
+              "load, embed into the corpus, top-k searches up to 56, ranges, workspace mode; everything else is 256 only)", what);
     return SMT_E_UNSUPPORTED;
 }
 
@@ -280,6 +288,7 @@ static int debug_batch_lists_staged(smt_corpus *corpus, int rows, const float *q
 {
     SMT_REQUIRE(corpus && queries && out_keys && out_blocks && out_kp, "null argument");
     const bool half = rows == SMT_ROWS_F16, byte = rows == SMT_ROWS_I8, nibble = rows == SMT_ROWS_I4;
+    if (rows_are_narrow(corpus)) return refuse_narrow("the list hooks of the batched routes (narrow rows have no batched route)");
     if (rows_are_nibble(corpus) && !nibble)
         return refuse_nibble(byte   ? "smt_debug_batch_byte_lists (the batched route of nibble rows has smt_debug_batch_nibble_lists)"
                              : half ? "smt_debug_batch_half_lists (the batched route of nibble rows has smt_debug_batch_nibble_lists)"

@@ -651,7 +651,7 @@ static int sharded_model_make(smt_group *group, const std::function<int(int, smt
 int smt_sharded_model_create(smt_group *group, const float *table_host, uint64_t V, uint32_t D, int normalize, smt_sharded_model **out)
 try {
     SMT_REQUIRE(group && table_host && out, "null argument");
-    if (D != SMT_DIM) return smt::dim_is_wide(D) ? smt::refuse_wide(D, "a sharded model") : smt::refuse_dim(D);
+    if (D != SMT_DIM) return smt::dim_in_family(D) ? smt::refuse_width(D, "a sharded model") : smt::refuse_dim(D);
     return sharded_model_make(group, [&](int i, smt_model **m) { return smt_model_create(group->ctx[i], table_host, V, D, normalize, m); }, out);
 } catch (...) { return smt::api_catch(); }
 
@@ -659,7 +659,7 @@ int smt_sharded_model_create_from_file(smt_group *group, const char *path, uint6
                                        smt_sharded_model **out)
 try {
     SMT_REQUIRE(group && path && out, "null argument");
-    if (D != SMT_DIM) return smt::dim_is_wide(D) ? smt::refuse_wide(D, "a sharded model") : smt::refuse_dim(D);
+    if (D != SMT_DIM) return smt::dim_in_family(D) ? smt::refuse_width(D, "a sharded model") : smt::refuse_dim(D);
     return sharded_model_make(group, [&](int i, smt_model **m) { return smt_model_create_from_file(group->ctx[i], path, byte_offset, V, D, normalize, m); }, out);
 } catch (...) { return smt::api_catch(); }
 
@@ -667,7 +667,7 @@ int smt_sharded_model_create_typed(smt_group *group, const void *table_host, int
                                    smt_sharded_model **out)
 try {
     SMT_REQUIRE(group && table_host && out, "null argument");
-    if (D != SMT_DIM) return smt::dim_is_wide(D) ? smt::refuse_wide(D, "a sharded model") : smt::refuse_dim(D);
+    if (D != SMT_DIM) return smt::dim_in_family(D) ? smt::refuse_width(D, "a sharded model") : smt::refuse_dim(D);
     return sharded_model_make(group, [&](int i, smt_model **m) { return smt_model_create_typed(group->ctx[i], table_host, table_dtype, V, D, normalize, m); }, out);
 } catch (...) { return smt::api_catch(); }
 
@@ -675,7 +675,7 @@ int smt_sharded_model_create_from_file_typed(smt_group *group, const char *path,
                                              uint32_t D, int normalize, smt_sharded_model **out)
 try {
     SMT_REQUIRE(group && path && out, "null argument");
-    if (D != SMT_DIM) return smt::dim_is_wide(D) ? smt::refuse_wide(D, "a sharded model") : smt::refuse_dim(D);
+    if (D != SMT_DIM) return smt::dim_in_family(D) ? smt::refuse_width(D, "a sharded model") : smt::refuse_dim(D);
     return sharded_model_make(group, [&](int i, smt_model **m) { return smt_model_create_from_file_typed(group->ctx[i], path, byte_offset, table_dtype, V, D, normalize, m); }, out);
 } catch (...) { return smt::api_catch(); }
 
@@ -684,7 +684,7 @@ int smt_sharded_model_create_indexed(smt_group *group, const void *table_host, i
                                      smt_sharded_model **out)
 try {
     SMT_REQUIRE(group && table_host && out, "null argument");
-    if (D != SMT_DIM) return smt::dim_is_wide(D) ? smt::refuse_wide(D, "a sharded model") : smt::refuse_dim(D);
+    if (D != SMT_DIM) return smt::dim_in_family(D) ? smt::refuse_width(D, "a sharded model") : smt::refuse_dim(D);
     int rc = smt::check_indexed_args(mapping_host, weights_host, n_tokens, n_rows);
     if (rc) return rc;
     smt_sharded_model *sm = nullptr;
@@ -700,7 +700,7 @@ int smt_sharded_model_create_from_file_indexed(smt_group *group, const char *pat
                                                int normalize, smt_sharded_model **out)
 try {
     SMT_REQUIRE(group && path && out, "null argument");
-    if (D != SMT_DIM) return smt::dim_is_wide(D) ? smt::refuse_wide(D, "a sharded model") : smt::refuse_dim(D);
+    if (D != SMT_DIM) return smt::dim_in_family(D) ? smt::refuse_width(D, "a sharded model") : smt::refuse_dim(D);
     int rc = smt::check_indexed_args(mapping_host, weights_host, n_tokens, n_rows);
     if (rc) return rc;
     smt_sharded_model *sm = nullptr;

@@ -6,24 +6,33 @@
 namespace smt {
 
 inline bool dim_is_wide(uint32_t D) { return D == 512 || D == 768 || D == 1024; }
-inline bool dim_supported(uint32_t D) { return D == SMT_DIM || dim_is_wide(D); }
-// SMT_E_UNSUPPORTED for a width no kernel serves (the message names 256 and lists the four widths)
+// NARROW rows: 64 floats, 256 B, four rows per 1 KiB wave load (embed_narrow.hip, scan_narrow.hip); f32 rows only
+inline bool dim_is_narrow(uint32_t D) { return D == 64; }
+// a width of this family: its own K1 and K2, the finish stage and the entry points of search_slab.cpp; the 256 kernels never see it
+inline bool dim_in_family(uint32_t D) { return dim_is_wide(D) || dim_is_narrow(D); }
+inline bool dim_supported(uint32_t D) { return D == SMT_DIM || dim_in_family(D); }
+// SMT_E_UNSUPPORTED for a width no kernel serves (the message names 256 and lists the five widths)
 int refuse_dim(uint32_t D);
 // SMT_E_UNSUPPORTED for a call wide rows do not serve yet: `what` names it, the message names the width
 int refuse_wide(uint32_t D, const char *what);
+// ... and for one narrow rows do not serve yet: the message names the 64 dimensions
+int refuse_narrow(const char *what);
+// whichever of the two fits a width of the family
+inline int refuse_width(uint32_t D, const char *what) { return dim_is_narrow(D) ? refuse_narrow(what) : refuse_wide(D, what); }
 // ... and for one half rows do not serve yet (half_rows.h): the message names the half rows
 int refuse_half(const char *what);
 // ... and for one byte rows do not serve yet (byte_rows.h): the message names the byte rows
 int refuse_byte(const char *what);
 // ... and for one nibble rows do not serve yet (nibble_rows.h): the message names the nibble rows
 int refuse_nibble(const char *what);
-// whichever of the four fits a corpus that is wide, half, byte or nibble
+// whichever of the five fits a corpus that is wide, narrow, half, byte or nibble
 inline int refuse_rows(const smt_corpus *c, const char *what)
 {
     return c->row_dtype == SMT_ROWS_I4   ? refuse_nibble(what)
            : c->row_dtype == SMT_ROWS_I8 ? refuse_byte(what)
-           : c->row_dtype == SMT_ROWS_F16 ? refuse_half(what) : refuse_wide(c->dim, what);
+           : c->row_dtype == SMT_ROWS_F16 ? refuse_half(what) : refuse_width(c->dim, what);
 }
+inline bool rows_are_narrow(const smt_corpus *c) { return dim_is_narrow(c->dim); }
 
 // |f32 scan distance - exact distance| of scan_slab_kernel<S, .>, by the counting rule at F32_ERR_SCAN (common.h): a lane runs
 // 4 S fused multiply-adds, the tree (wave_sum4 or wave_sum: six levels) is taken as eight steps as there, on terms whose absolute
@@ -40,11 +49,25 @@ constexpr double f32_err_slab(int S) { return 4.0 * (double)(4 * S + 12) / 16777
 // 7.7e-7 on random rows, 2.6e-5 on the constructed worst-case rows (1024 dimensions).
 constexpr double f32_err_batch_slab(int S) { return 1.2 * (3.0 / 65536.0 + 48.0 * S * 2.0 / 8388608.0 + 1e-6); }
 
+// ... of scan_narrow_kernel (scan_narrow.hip), by the same rule: a lane runs four fused multiply-adds, the tree inside a 16-lane row
+// (four levels) is taken as eight steps as there, two rsqrt and two multiplies follow: (4 + 8 + 4) roundings of 2^-24 = 9.5e-7 --
+// the 256 kernel's own count, a row of 64 floats in 16 lanes is a row of 256 in 64 -- times the factor 4: 3.8e-6.
+// DERIVED, not measured on keys.
+constexpr double f32_err_narrow = 4.0 * 16.0 / 16777216.0;
+constexpr int NARROW_STEP_ROWS = 16;   // rows a wave of scan_narrow_kernel takes per step: four 1 KiB loads of four rows each
+
 constexpr int SLAB_MAX_LISTS = 256;  // block lists per query the finish kernel merges: the scan launches at most this many blocks
 
 // K1 (embed_slab.hip): plain tables of `table_dtype`, rows of D elements
 int launch_embed_slab(smt_ctx *ctx, const void *table, int table_dtype, uint64_t V, uint32_t D, int normalize, const uint32_t *ids,
                       const uint64_t *offsets, uint64_t n_lines, uint32_t max_tokens, float *out);
+
+// the run table of the K1 kernels of this family (embed_slab.hip): ctx->d_embed_runs[g] = the first line of group g when the lines
+// are cut by tokens + 4 per line into `groups` runs, [groups] = n_lines; grows the table, enqueues one launch
+int launch_embed_runs(smt_ctx *ctx, const uint64_t *offsets, uint64_t n_lines, uint64_t groups);
+// K1 for 64-wide tables (embed_narrow.hip): plain tables of `table_dtype`, rows of 64 elements
+int launch_embed_narrow(smt_ctx *ctx, const void *table, int table_dtype, uint64_t V, int normalize, const uint32_t *ids,
+                        const uint64_t *offsets, uint64_t n_lines, uint32_t max_tokens, float *out);
 
 // K2 + finish for the queries of one call, in passes of up to four (scan_slab.hip, finish_slab.hip).  All pointers device; enqueued
 // on the context's stream, nothing waits.  chunk_table / n_chunks: the range filter (range_tables.hip), nullptr / 0 without one.
@@ -66,7 +89,7 @@ struct SlabSearch {
     bool scan_only = false;            // never the batched route (the host form's re-run of what that route left unproved)
 };
 int launch_search_slab(smt_ctx *ctx, const SlabSearch &a);
-// what a K2 kernel of this family is launched with (scan_slab.hip, scan_half.hip, scan_byte.hip, scan_nibble.hip)
+// what a K2 kernel of this family is launched with (scan_slab.hip, scan_narrow.hip, scan_half.hip, scan_byte.hip, scan_nibble.hip)
 struct SlabScanParams {
     const float *corpus;
     uint64_t n_rows;
@@ -78,6 +101,8 @@ struct SlabScanParams {
     key_t64 *block_lists;          // [NQ][gridDim.x][kp]
 };
 using slab_scan_kernel_t = void (*)(SlabScanParams);
+// scan_narrow.hip: scan_narrow_kernel<4, slots, filtered>, launched by launch_search_slab (scan_slab.hip) like the wide kernels
+slab_scan_kernel_t narrow_scan_kernel_of(int slots, bool filtered);
 // the finish stage alone (finish_slab.hip): lists [nq][n_lists][kp] of block lists -> answers, one block per query, certified under
 // f32_err (0: the scan's f32_err_slab)
 int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, uint32_t n_lists, uint32_t kp, uint32_t first_query,
@@ -86,7 +111,8 @@ int launch_finish_slab(smt_ctx *ctx, const SlabSearch &a, const key_t64 *lists, 
 // queries -- 64 at 512 dimensions, 32 at 768 and 1024 -- on the bf16 MFMA pipe, certified under f32_err_batch_slab.
 inline bool slab_batch_serves(const smt_ctx *ctx, const SlabSearch &a)
 {
-    return !a.scan_only && a.row_dtype == SMT_ROWS_F32 && ctx->tune.slab_batch_min > 0 && a.nq >= (uint32_t)ctx->tune.slab_batch_min;
+    return !a.scan_only && a.row_dtype == SMT_ROWS_F32 && dim_is_wide(a.dim) && ctx->tune.slab_batch_min > 0 &&   // (narrow rows: the scan only)
+           a.nq >= (uint32_t)ctx->tune.slab_batch_min;
 }
 uint32_t slab_batch_qb(uint32_t dim);
 int launch_batch_slab(smt_ctx *ctx, const SlabSearch &a);
